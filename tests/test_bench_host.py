@@ -43,3 +43,32 @@ def test_self_launch_starts_one_child_launcher_and_forwards_its_exit_code(monkey
     i = cmd.index(os.path.join(ROOT, "bench.py"))
     assert cmd[i + 1:] == ["--gpus", "4", "--steps", "2", "--warmup", "1"]
     assert seen["env"].get("HSA_ENABLE_IPC_MODE_LEGACY") == "0"
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb_and_samples_a_fixed_set_of_pairs(tmp_path):
+    """--dump-outputs: every record field as float64, the masks as float32; a batch whose masks exceed the budget (one rank's share of
+    BASELINE configs[4] at N = 5000) is written for the same seeded sample of pairs on every run"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from mdrp_amd import _capi
+    rng = np.random.default_rng(5)
+    for B, n in ((1024, 2000), (12500, 5000)):
+        res = np.zeros(B, dtype=_capi.RESULT_DTYPE)
+        res["num_inliers"] = rng.integers(0, n, B)
+        res["model"]["t"] = rng.normal(size=(B, 3))
+        mask = (rng.random((B, n)) < 0.5).astype(np.uint8)
+        dirs = [tmp_path / f"{B}_a", tmp_path / f"{B}_b"]
+        for d in dirs:
+            bench.dump_outputs(str(d), res, mask)
+        files = sorted(os.listdir(dirs[0]))
+        assert files == sorted(os.listdir(dirs[1])) and "inlier_mask.npy" in files and "model_t.npy" in files
+        assert sum(os.path.getsize(dirs[0] / f) for f in files) <= 64_000_000
+        for f in files:
+            a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+            assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        assert np.array_equal(np.load(dirs[0] / "num_inliers.npy"), res["num_inliers"].astype(np.float64))
+        assert np.array_equal(np.load(dirs[0] / "model_t.npy"), res["model"]["t"])
+        rows = np.load(dirs[0] / "inlier_mask_pairs.npy").astype(np.int64) if "inlier_mask_pairs.npy" in files else np.arange(B)
+        assert (B == 1024) == (len(rows) == B)
+        assert np.array_equal(np.load(dirs[0] / "inlier_mask.npy"), mask[rows].astype(np.float32))
