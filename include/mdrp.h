@@ -253,7 +253,8 @@ typedef struct {
      * Fused tail (the last LO launch and the final refinements overlap on two streams): bounded waits that expired in the
      * last call.  Non-zero means kernels of the handle's streams did not run side by side (serialising profiler / debugger,
      * AMD_SERIALIZE_KERNEL, a busy shared GPU): results are unaffected, the call was slower, final_ms includes the waits, and the
-     * handle runs unfused for its next 64 calls (MDRP_FUSE_RETRY_CALLS), then tries again. */
+     * handle runs unfused for a number of calls, then tries again: 64 after the first call with an expired wait, doubling with every further such
+     * call up to 16384, back to 64 after a clean call (mdrp_capi.hip finish_timing). */
     int64_t fuse_gate_timeouts;
     int64_t fuse_wait_timeouts;
     /* ---- appended in ABI 0.5 (mdrp_last_stats_sized only) ----

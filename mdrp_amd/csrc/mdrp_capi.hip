@@ -128,7 +128,7 @@ struct mdrp_handle {
     DevBuf cplan;              // work plan of k_count / k_bound
     DevBuf surv2_count;        // survivors of k_bound per pair
     DevBuf lo_mask;            // 5-point LO: inlier subset of the refined model, one row per LO workgroup
-    DevBuf red5;               // 5-point solver: the Reduce5 blocks between its two kernels, [pair][ceil(chunk / 64)][76][64] doubles
+    DevBuf red5;               // 5-point solver: the Reduce5 blocks between its kernels, [pair][ceil(chunk / 64)][76][64] doubles, + a region for the first chunk (run_pass)
     DevBuf lm_stats;                  // six u64: correspondences evaluated by the LM cost / accumulate sweeps of the LO kernel | of the final kernel |
                                       // fused tail: gate time-outs | final-refinement wait time-outs
     unsigned long long *lm_stats_host = nullptr; // pinned copy, valid after finish_timing
@@ -394,7 +394,6 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     const bool fuse_env = env_int("MDRP_FUSE_TAIL", ((kind == MDRP_CALIB && est_shift) || h->fuse_disabled) ? 0 : 1) != 0;
     bool final_done = false;
     // the 5-point LO keeps the inlier subset of the model it refines: one row per LO workgroup and chunk (LOs of two chunks overlap)
-    if (kind == MDRP_RELPOSE_5PT && (rc = h->red5.ensure(sizeof(double) * (size_t)batch * ((size_t)(chunk_cap + 63) / 64) * RED5_STRIDE * 64))) return rc;
     const size_t lo_mask_rows = (size_t)h->num_cu * 8; // kc_lo launches num_cu * (8 | 2) workgroups
     if ((kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT) && (rc = h->lo_mask.ensure(lo_mask_rows * (size_t)std::max(n_max, 1)))) return rc;
     int32_t *cnt = h->counters.as<int32_t>();
@@ -453,6 +452,15 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                 lead[0] = (uint64_t)std::min(1024.0, std::max(128.0, std::ceil(h->seen_wish[kind] / 64.0) * 64.0));
         }
     }
+    // Reduce5 blocks of the 5-point solver (issue_solve): [pair][ceil(len / 64)] blocks of RED5_STRIDE x 64 doubles per solve, in two regions.
+    // The first chunk of a super-chunk of several chunks is solved on the main stream while the second chunk's solver may run on `aux` (the
+    // sliced host-buffer front: the main stream waits for a slice's k_prep only, not for the solver issued behind it), so it gets a region of
+    // its own behind the shared one.  Its length is a leading chunk that leaves at least as much again behind it: at most lead[0] and
+    // chunk_cap / 2 iterations (red5_first_blocks; the budget in estimate_device reserves the same).
+    const size_t red5_blocks = ((size_t)chunk_cap + 63) / 64;
+    const size_t red5_first_blocks = (std::min<uint64_t>(lead.empty() ? 0 : lead[0], (uint64_t)chunk_cap / 2) + 63) / 64;
+    if (kind == MDRP_RELPOSE_5PT &&
+        (rc = h->red5.ensure(sizeof(double) * (size_t)batch * (red5_blocks + red5_first_blocks) * RED5_STRIDE * 64))) return rc;
     uint64_t max_needed = 0;
     rp.slot_stride = chunk_cap * mps;
     while (true) {
@@ -541,7 +549,13 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                     hipLaunchKernelGGL(kc_solve<CLASSIC_SHARED>, sgrid, dim3(64), 0, st_, r, st_p, smp, pts_p, models_p, inl_p, tg, mc);
                 else if (kind == MDRP_RELPOSE_5PT) {
                     // three kernels (mdrp_classic.h): null space and roots + poses at six wavefronts per CU, the elimination between them at three
-                    double *red5 = h->red5.as<double>() + (size_t)p0 * sgrid.x * RED5_STRIDE * 64;
+                    // Invariant: two solves that may run at the same time never share a Reduce5 block.  A chunk's solve writes blocks
+                    // [p0 * sgrid.x, (p0 + pc) * sgrid.x) of its region, and only the first chunk of a super-chunk of several chunks is ever solved
+                    // beside another chunk's solver (the sliced front: chunk 0 on `s`, chunk 1 on `aux`): it alone uses the second region.  Every
+                    // other solve is ordered behind the previous one by its stream or by ev_solved.
+                    const bool first_region = c == 0 && n_chunks > 1;
+                    if (first_region && (size_t)sgrid.x > red5_first_blocks) { g_err = "5-point first chunk longer than its Reduce5 region"; return MDRP_ERR_INVALID; }
+                    double *red5 = h->red5.as<double>() + ((first_region ? (size_t)batch * red5_blocks : 0) + (size_t)p0 * sgrid.x) * RED5_STRIDE * 64;
                     hipLaunchKernelGGL(kc_solve5_null, sgrid, dim3(64), SOLVE5N_LDS_BYTES, st_, r, st_p, smp, pts_p, red5);
                     hipLaunchKernelGGL(kc_solve5_reduce, sgrid, dim3(64), SOLVE5_LDS_BYTES, st_, r, st_p, red5);
                     hipLaunchKernelGGL(kc_solve5_roots, sgrid, dim3(64), SOLVE5B_LDS_BYTES, st_, r, st_p, smp, pts_p, red5, models_p, inl_p, tg, mc);
@@ -820,6 +834,22 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     return MDRP_OK;
 }
 
+// longest first chunk of the 5-point estimator that is solved beside the second one (run_pass: the second Reduce5 region): the first leading
+// chunk (MDRP_CHUNKS, default at most 512 iterations), at most half the chunk capacity
+size_t red5_first_len(int chunk_cap) {
+    uint64_t first = 512;
+    if (const char *e = getenv("MDRP_CHUNKS")) {
+        first = 0;
+        for (const char *q = e; *q; ++q) { // the first positive entry, as run_pass parses the list
+            const long v = atol(q);
+            if (v > 0) { first = (uint64_t)v; break; }
+            while (*q && *q != ',') ++q;
+            if (!*q) break;
+        }
+    }
+    return (size_t)std::min<uint64_t>(first, (uint64_t)chunk_cap / 2);
+}
+
 int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
                     int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
                     const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr) {
@@ -858,7 +888,7 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     const size_t per_pair = (size_t)chunk_cap * mps * (sizeof(Model) + sizeof(double) + 2 * sizeof(int32_t) + 4 * sizeof(uint32_t) /*tag lists*/) +
                             (size_t)chunk_cap * (sizeof(Trigger) + 8) + (size_t)n_max * (PT_STRIDE + 2) * sizeof(double) + 1024;
     const size_t per_pair_all = per_pair + (size_t)chunk_cap * mps * sizeof(uint32_t) /*tags_v*/ + ((size_t)n_max + 15) / 16 * 1024 /*rfrag*/ +
-                                (kind == MDRP_RELPOSE_5PT ? ((size_t)chunk_cap + 63) / 64 * RED5_STRIDE * 64 * sizeof(double) : 0) /*red5*/;
+                                (kind == MDRP_RELPOSE_5PT ? (((size_t)chunk_cap + 63) / 64 + (red5_first_len(chunk_cap) + 63) / 64) * RED5_STRIDE * 64 * sizeof(double) : 0) /*red5*/;
     size_t budget = std::min<size_t>((size_t)(0.5 * (double)free_b), (size_t)96 << 30);
     int per_pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, budget / per_pair_all));
     per_pass = std::min(per_pass, 65535); // k_solve / k_probe put the pair index on grid.y

@@ -1818,7 +1818,7 @@ __device__ __forceinline__ void lm_flush_stats(LmShared &sh) {
 
 #define MDRP_LM_COST_UNROLL 1 // records per lane and trip of the cost sweep (lm_cost)
 // IRLS weight of the Sampson row: ws^2 w(r^2) in the calibrated refiner, ws^2 w(ws r^2) in the two focal ones (the COST carries ws rho(r^2) in all
-// three) — see lm_accumulate_point.  The work lists of lm_cost and of the list engine (mdrp_lm.h) are built with the same expression.
+// three) — see lm_accumulate_point.  The work lists of lm_cost are built with the same expression.
 template <int KIND>
 __device__ __forceinline__ double sampson_row_weight(int loss, double lsc, double mu, double ws, double ws2, double rs) {
     return ws2 * loss_weight(loss, lsc, KIND != 0 ? ws * rs : rs, mu);

@@ -41,7 +41,7 @@ MDRP_HD void model_identity(Model &m) {
 // square root ~15 with its range scaling; the calibrated P3P path has 71 + 35 of them among 5 800 instructions (round 4 count).  The device
 // build takes the hardware seed and two Newton steps (<= 1.5 ulp instead of correctly rounded: the same class of difference as the FMA
 // contraction it already has against the oracle; every solution is Newton-polished against its own equations afterwards).  The host build of
-// this header — the CPU tests against the oracle — keeps the IEEE operations.  MDRP_SOLVER_IEEE_DIV=1 restores them on the device.
+// this header — the CPU tests against the oracle — keeps the IEEE operations.  There is no switch back to IEEE division on the device.
 MDRP_HD double sv_rcp(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     double y = __builtin_amdgcn_rcp(x);

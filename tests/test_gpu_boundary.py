@@ -230,7 +230,8 @@ def test_host_buffer_call_in_h2d_slices_equals_the_resident_call():
     """a host-buffer call of >= 512 pairs copies the correspondences in 256-pair slices on the handle's copy stream and runs k_prep,
     the first chunk and the second chunk's solver of each slice beside the next slice's copy (mdrp_capi.hip run_pass).  Pairs are independent units:
     records and masks must equal those of the SAME batch resident on the device bit for bit — ragged counts (incl. pairs below the sample size), per-pair
-    cameras, a last slice that is short (600 = 256 + 256 + 88), for a monodepth estimator and a classic one."""
+    cameras, a last slice that is short (600 = 256 + 256 + 88), for all six estimators (tests/test_gpu_schedules.py: the shapes where the 5-point
+    solver's first and second chunk used to share Reduce5 scratch)."""
     import torch
     from mdrp_amd import _capi, synth
     B, N = 600, 640
@@ -250,13 +251,15 @@ def test_host_buffer_call_in_h2d_slices_equals_the_resident_call():
     dev = torch.device("cuda", 0)
     h = _capi.Handle(0)
     try:
-        for kind in (0, 5):
-            c = cams if kind == 0 else None
-            res_h, mask_h = h.estimate_batch(kind, x1, x2, d1 if kind == 0 else None, d2 if kind == 0 else None, ro, bo, ns, c, c)
+        pp0 = np.zeros(B, dtype=_capi.CAMERA_DTYPE)                         # the 6-point estimator: principal point (0, 0) in cam1
+        for kind in range(6):
+            c = cams if kind in (0, 3) else (pp0 if kind == 4 else None)
+            mono = kind <= 2
+            res_h, mask_h = h.estimate_batch(kind, x1, x2, d1 if mono else None, d2 if mono else None, ro, bo, ns, c, c)
             t = [torch.from_numpy(a).to(dev) for a in (x1, x2, d1, d2)]
             mask_d = torch.zeros((B, N), dtype=torch.uint8, device=dev)
             torch.cuda.synchronize(dev)
-            h.estimate_batch_device(kind, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr() if kind == 0 else 0, t[3].data_ptr() if kind == 0 else 0, B, N, ro, bo, ns, c, c,
+            h.estimate_batch_device(kind, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr() if mono else 0, t[3].data_ptr() if mono else 0, B, N, ro, bo, ns, c, c,
                                     mask_d.data_ptr())
             res_d = h.fetch_results(B)
             assert res_h.tobytes() == res_d.tobytes(), kind
