@@ -108,7 +108,7 @@ struct mdrp_handle {
     hipStream_t aux_stream = nullptr;  // the second chunk's sampler + solver run here, beside the first chunk's sweep
     hipStream_t aux_stream2 = nullptr; // the sample tables and the super-chunk's LO launch run here
     hipStream_t copy_stream = nullptr; // host-buffer calls: the H2D slices of the correspondences
-    hipEvent_t ev_copied = nullptr, ev_prepped = nullptr;
+    hipEvent_t ev_copied = nullptr, ev_prepped = nullptr, ev_solved6 = nullptr;
     DevBuf fuse;                       // fused tail: control words (64 B) | done_cnt[batch] | fin_done[batch] | ready[batch]
     static constexpr int NC_MAX = 8; // chunks of a super-chunk
     hipEvent_t ev_lo = nullptr, ev_tables = nullptr, ev_sampled[2] = {}, ev_solved[NC_MAX] = {}, ev_scanned[NC_MAX] = {};
@@ -701,8 +701,19 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                 // whatever the number of pairs: one sweep per slice cost four times that on the main stream, 10.3 ms per step against 10.0.)
                 const bool last = p0 + sl >= batch, last_but_one = !last && p0 + 2 * sl >= batch;
                 if (last_but_one || last) HIPCHK(hipStreamWaitEvent(s, h->ev_prepped, 0)); // (the prep of this slice and, by stream order, of every slice before it)
-                if (last_but_one) { swept0 = p0 + pc; if ((rc = issue_solve(0, s, 0, swept0)) || (rc = sweep_chunk(0, 0, swept0))) return rc; }
-                if (last) { if ((rc = issue_solve(0, s, swept0, batch - swept0)) || (rc = sweep_chunk(0, swept0, batch - swept0))) return rc; swept0 = batch; }
+                // The 6-point solver (11.5 KB of scratch per lane) solves the first chunk on the solver stream too, behind the second chunk's slices:
+                // two of its dispatches at once on two queues need two whole-device scratch areas (~6 GB each) at the same time, and the runtime
+                // aborts the queue (out of resources) when it cannot have the second one.  The main stream sweeps behind that solve.
+                auto solve_first = [&](int q0, int qc) -> int {
+                    if (kind != MDRP_SHARED_6PT) return issue_solve(0, s, q0, qc);
+                    int rc_ = issue_solve(0, aux, q0, qc);
+                    if (rc_) return rc_;
+                    HIPCHK(hipEventRecord(h->ev_solved6, aux));
+                    HIPCHK(hipStreamWaitEvent(s, h->ev_solved6, 0));
+                    return MDRP_OK;
+                };
+                if (last_but_one) { swept0 = p0 + pc; if ((rc = solve_first(0, swept0)) || (rc = sweep_chunk(0, 0, swept0))) return rc; }
+                if (last) { if ((rc = solve_first(swept0, batch - swept0)) || (rc = sweep_chunk(0, swept0, batch - swept0))) return rc; swept0 = batch; }
             }
             if (sliced) { HIPCHK(hipEventRecord(h->ev_solved[1], aux)); solved1 = true; }
         }
@@ -1012,6 +1023,7 @@ static int create_handle(int device, hipStream_t stream, bool own_stream, mdrp_h
     HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&h->ev_copied, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->ev_prepped, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_solved6, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->ev_lo, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->ev_tables, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->ev_sampled[0], hipEventDisableTiming));
@@ -1053,6 +1065,7 @@ void mdrp_destroy(mdrp_handle *h) {
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     if (h->ev_copied) (void)hipEventDestroy(h->ev_copied);
     if (h->ev_prepped) (void)hipEventDestroy(h->ev_prepped);
+    if (h->ev_solved6) (void)hipEventDestroy(h->ev_solved6);
     if (h->ev_lo) (void)hipEventDestroy(h->ev_lo);
     if (h->ev_tables) (void)hipEventDestroy(h->ev_tables);
     for (int i = 0; i < 2; ++i) if (h->ev_sampled[i]) (void)hipEventDestroy(h->ev_sampled[i]);

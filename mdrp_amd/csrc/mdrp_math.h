@@ -42,6 +42,9 @@ MDRP_HD void model_identity(Model &m) {
 // build takes the hardware seed and two Newton steps (<= 1.5 ulp instead of correctly rounded: the same class of difference as the FMA
 // contraction it already has against the oracle; every solution is Newton-polished against its own equations afterwards).  The host build of
 // this header — the CPU tests against the oracle — keeps the IEEE operations.  There is no switch back to IEEE division on the device.
+// Measured on the device (tests/test_gpu_devmath.py, normal arguments): sv_rcp 0.5, sv_div 1.34, sv_rsqrt 1.49, sv_sqrt 0.56 ulp.  Outside
+// that: 1 / 0, 1 / inf and the reciprocal of |x| < 2^-1024 (it overflows) are NaN, not inf / 0; sv_sqrt(inf) and sv_rsqrt(0 | inf) are
+// NaN; subnormal arguments of sv_rsqrt / sv_sqrt are off by a factor of up to ~2.3 (the hardware seed's range).
 MDRP_HD double sv_rcp(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     double y = __builtin_amdgcn_rcp(x);
@@ -730,9 +733,12 @@ MDRP_HD int run_solver(int solver, const Sample3 &s, Model out[4]) {
 // Reciprocal and reciprocal square root of the LM sweeps.  The oracle (and the host build of this header) divide; on the device an IEEE
 // fp64 division is an 11-instruction dependent chain (v_div_scale x 2, v_rcp, four FMAs, v_div_fmas, v_div_fixup) and `1 / sqrt(x)` a
 // square root followed by one — three of them per correspondence and sweep, ~18 % of the cost sweep's instructions.  The device takes the
-// hardware seed and two Newton steps: <= 1 ulp instead of correctly rounded, the same class of difference as the FMA contraction the
-// device build already has against the oracle (gated by the 3 x 1024-pair fixtures of tests/test_gpu_headline.py: masks and inlier
-// counts identical, models to 1e-8).  x = 0 gives NaN where the division gives inf; both end as "term truncated / row of weight zero".
+// hardware seed and two Newton steps: lm_rcp <= 1 ulp for every normal x (0.5 measured on the device by tests/test_gpu_devmath.py), lm_rsqrt
+// <= 1.5 ulp for every normal x > 0 (1.49 measured: the last step rounds the factor 1.5 - x y^2 / 2 before the product), instead of correctly
+// rounded: the same class of difference as the FMA contraction the device build already has against the oracle (gated by the 3 x 1024-pair
+// fixtures of tests/test_gpu_headline.py: masks and inlier counts identical, models to 1e-8).
+// x = 0 gives NaN where the division gives inf; both end as "term truncated / row of weight zero".  So do x = +-inf (1 / x = 0) and
+// |x| < 2^-1024, whose reciprocal overflows; lm_rsqrt of a subnormal is not accurate (the seed's range).
 MDRP_HD double lm_rcp(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     double y = __builtin_amdgcn_rcp(x);
@@ -773,14 +779,18 @@ MDRP_HD double loss_value(int type, double thr, double r2) {
 #if defined(__HIPCC__)
 // log(1 + x), x >= 0, from a 128-entry table in LDS (mdrp_logtab.h: per mantissa interval of width 1 / 128 the double inv = fl(1 / c), c its
 // midpoint, and -ln(inv)).  1 + x = 2^e m, m in [1, 2);  r = m inv - 1 (one FMA: |r| <= 1 / 256, exact to half an ulp of r);
-// log(1 + x) = e ln 2 - ln(inv) + log1p(r), log1p(r) by its series to r^6 (truncation r^7 / 7 < 2e-18).  The rounding of 1 + x is put back
-// to first order (err / (1 + x), err = x - ((1 + x) - 1)).  ~22 instructions against ~150 of the library's log1p: the Cauchy losses take
-// three per record in every cost sweep of the final refinements (round 5).  Non-finite arguments come back as they are (inf, NaN).
+// log(1 + x) = e ln 2 - ln(inv) + log1p(r), log1p(r) by its series to r^7 (truncation r^8 / 8 < 2^-67).  The rounding of 1 + x is put back
+// to first order (err / (1 + x), err = x - ((1 + x) - 1)).  For |x| < 2^-8 the result is the series on x itself, without the table:
+// cell 0 is centred on 1 + 1 / 256, so there -ln(inv) + log1p(r) cancels to an absolute error of ~ulp(1 / 256) = 1.7e-18 (95 ulp at
+// x = 1e-4, 1.7e-18 for x = 0) and the cost of a near-exact inlier would be a constant.  <= 2 ulp for every finite x >= 0, 1.11 measured
+// (tests/test_gpu_devmath.py; the series to r^6 had 3 ulp just above 2^-8), and lm_log1p(0) = 0.  ~24 instructions against ~150 of the library's log1p: the Cauchy losses take three per record in every cost sweep of
+// the final refinements (round 5).  Non-finite arguments come back as they are (inf, NaN).
 // (Declared in the host pass too — templates that call it are parsed there — with the device body only in the device pass.)
 __device__ __forceinline__ double lm_log1p(double x, const double *tab_lds) {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(3))) const double lds_cdouble;
     const double y = 1.0 + x;
+    const bool near0 = fabs(x) < 0x1p-8; // (false for NaN)
     const double err = x - (y - 1.0);
     const unsigned hi = (unsigned)__double2hiint(y);
     const int e = (int)(hi >> 20) - 1023;
@@ -788,14 +798,15 @@ __device__ __forceinline__ double lm_log1p(double x, const double *tab_lds) {
     const double m = __hiloint2double((int)((hi & 0x000FFFFFu) | 0x3FF00000u), __double2loint(y));
     lds_cdouble *t = (lds_cdouble *)tab_lds + 2 * idx;
     const double inv_c = t[0], log_c = t[1];
-    const double r = fma(m, inv_c, -1.0);
-    double q = fma(r, -1.0 / 6.0, 0.2);
+    const double r = near0 ? x : fma(m, inv_c, -1.0);
+    double q = fma(r, 1.0 / 7.0, -1.0 / 6.0);
+    q = fma(r, q, 0.2);
     q = fma(r, q, -0.25);
     q = fma(r, q, 1.0 / 3.0);
     q = fma(r, q, -0.5);
-    const double lp = fma(r * r, q, r) + ldexp(err * inv_c, -e);
-    const double v = fma((double)e, 0.69314718055994530942, log_c + lp);
-    return y < __builtin_huge_val() ? v : y;
+    const double s = fma(r * r, q, r);
+    const double v = fma((double)e, 0.69314718055994530942, log_c + (s + ldexp(err * inv_c, -e)));
+    return near0 ? s : (y < __builtin_huge_val() ? v : y);
 #else
     (void)tab_lds;
     return log1p(x);

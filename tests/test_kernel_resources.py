@@ -26,6 +26,15 @@ def test_every_kernel_family_is_in_the_library(tables):
         assert sum(1 for k in regs if k.startswith(fam)) == count, fam
 
 
+def test_every_final_instantiation_is_in_the_lm_matrix(tables):
+    """the k_final / kc_final instantiations of the built library are exactly those tests/test_gpu_lm_matrix.py runs against the oracle: one
+    added later without a test fails here"""
+    from test_gpu_lm_matrix import final_instantiations
+    regs, _ = tables
+    built = {k for k in regs if k.startswith(("mdrp::k_final<", "mdrp::kc_final<"))}
+    assert built == final_instantiations(), (sorted(built - final_instantiations()), sorted(final_instantiations() - built))
+
+
 def test_lm_kernels_keep_two_wavefronts_per_simd_and_spill_nothing_into_their_sweeps(tables):
     regs, sites = tables
     for k, r in regs.items():
