@@ -8,7 +8,12 @@ HBM: calibrated 3-point solver (P3P path, shift off), 2000 correspondences per p
 with one device-side RCCL all_gather of the fixed-size result records.  --total-pairs P switches to BASELINE.json
 configs[4]: P pairs in total, ceil(P/N) contiguous pairs per rank, each rank generating only its own block (strong scaling).
 
+A plain run generates its inputs, warms up, times the steps and prints the line (with what the timed steps' own counters give:
+roofline, per-kernel times, quality).  --full also runs everything else the line can carry: the CPU baselines, the in-flight and
+host-buffer steps and, on the default run, the other configs, one rank's share of configs[4] and the latency block.
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python -m torch.distributed.run ... bench.py --gpus 8 --total-pairs 100000
 """
@@ -532,7 +537,11 @@ def self_launch(gpus, argv=None, out=None):
     return subprocess.run(cmd, env=env, stdout=out).returncode
 
 
-def main():
+# the measurements beyond the headline: (value with --full, value without).  An option given on the command line wins either way.
+EXTRA_DEFAULTS = {"cpu_pairs": (96, 0), "inflight": (2, 1), "host_steps": (6, 0), "extra_configs": (5, 0), "c5_share": (12500, 0), "latency": (1, 0)}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -542,23 +551,37 @@ def main():
                     help="BASELINE configs[4]: this many pairs in total, ceil(P/G) contiguous pairs per rank (strong scaling); "
                          "e.g. --total-pairs 100000 --gpus 8, or --total-pairs 12500 --gpus 1 for one rank's share")
     ap.add_argument("--workload", default="calib_p3p_n2000_i10k", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-pairs", type=int, default=96, help="pairs timed on the CPU baseline (0 = skip)")
-    ap.add_argument("--inflight", type=int, default=2, help="extra measurement at N = 1: the same steps with this many in flight "
-                                                              "(one handle + host thread each, mdrp_amd.pipeline); 1 = skip.  Never `value`.")
-    ap.add_argument("--host-steps", type=int, default=6, help="extra steps through the host-buffer (PCIe-inclusive) entry point, N = 1 only (0 = skip)")
-    ap.add_argument("--extra-configs", type=int, default=-1,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement: CPU baselines, the in-flight and host-buffer steps and, on the default "
+                         "run, the other configs, one rank's share of configs[4] and the latency block.  Without it these are skipped unless "
+                         "their own option below asks for them")
+    ap.add_argument("--cpu-pairs", type=int, default=None, help="pairs timed on the CPU baseline (default 96 with --full; 0 = skip)")
+    ap.add_argument("--inflight", type=int, default=None, help="extra measurement at N = 1: the same steps with this many in flight "
+                                                                 "(one handle + host thread each, mdrp_amd.pipeline; default 2 with --full); 1 = skip.  Never `value`.")
+    ap.add_argument("--host-steps", type=int, default=None,
+                    help="extra steps through the host-buffer (PCIe-inclusive) entry point, N = 1 only (default 6 with --full; 0 = skip)")
+    ap.add_argument("--extra-configs", type=int, default=None,
                     help="after the headline, also measure BASELINE configs[2] and [3] (shared focal; varying focal N = 5000 with the shift flag) "
-                         "with this many steps each and report them under `configs` (N = 1, default workload only; default 5; 0 = skip)")
-    ap.add_argument("--c5-share", type=int, default=-1,
+                         "with this many steps each and report them under `configs` (N = 1, default workload only; default 5 with --full; 0 = skip)")
+    ap.add_argument("--c5-share", type=int, default=None,
                     help="pairs of the `c5_one_rank_share` entry under `configs` (one rank's share of BASELINE configs[4]: 100000 pairs / 8 GPUs = 12500; "
-                         "N = 1 default run only; default 12500 there; 0 = skip)")
-    ap.add_argument("--latency", type=int, default=-1, help="single-pair / small-batch latency block on the line (N = 1 default run only; 0 = skip)")
+                         "N = 1 default run only; default 12500 there with --full; 0 = skip)")
+    ap.add_argument("--latency", type=int, default=None,
+                    help="single-pair / small-batch latency block on the line (N = 1 default run only; on with --full; 0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the result records and inlier masks of the last step as DIR/<name>.npy (float64 / float32, "
                          "at most 64 MB; masks of a larger batch for a fixed sample of pairs).  N > 1: rank 0 writes the gathered records and its own masks")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for k, (with_full, without) in EXTRA_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, with_full if args.full else without)
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the one-process-per-GPU job OURSELVES, as a CHILD process, before this process touches
@@ -568,9 +591,7 @@ def main():
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     default_run = world_env == 1 and args.workload == "calib_p3p_n2000_i10k" and args.total_pairs == 0 and args.batch == 1024
-    extra_steps = args.extra_configs if args.extra_configs >= 0 else (5 if default_run else 0)
-    if not default_run:
-        extra_steps = 0
+    extra_steps = args.extra_configs if default_run else 0
     cpu_line, cpu_extra = None, {}
     if world_env == 1 and args.cpu_pairs > 0:  # forks workers: before anything initialises the GPU
         cpu_line = cpu_baseline(args.workload, args.cpu_pairs)
@@ -592,7 +613,7 @@ def main():
     t_gen = time.perf_counter() - t_gen
     # one rank's share of BASELINE configs[4] (100 000 pairs over 8 GPUs = 12 500 pairs) on the N = 1 line: its inputs are generated here, by forked
     # workers, before the GPU is touched and outside every timed region (rank 3 of 8 would own pairs [37500, 50000): those)
-    c5_pairs = (args.c5_share if args.c5_share >= 0 else 12500) if default_run else 0
+    c5_pairs = max(args.c5_share, 0) if default_run else 0
     c5_first = 3 * c5_pairs
     c5_inputs, t_gen_c5 = None, 0.0
     if c5_pairs > 0:

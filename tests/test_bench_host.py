@@ -72,3 +72,19 @@ def test_dump_outputs_writes_float_arrays_within_64_mb_and_samples_a_fixed_set_o
         rows = np.load(dirs[0] / "inlier_mask_pairs.npy").astype(np.int64) if "inlier_mask_pairs.npy" in files else np.arange(B)
         assert (B == 1024) == (len(rows) == B)
         assert np.array_equal(np.load(dirs[0] / "inlier_mask.npy"), mask[rows].astype(np.float32))
+
+
+def test_a_plain_run_skips_every_extra_measurement_and_full_restores_them():
+    """a plain `bench.py --gpus 1 --steps N --warmup W` times the headline alone; --full brings back every other measurement with the
+    defaults it had, and an option given on the command line wins either way"""
+    sys.path.insert(0, ROOT)
+    import bench
+    extras = ("cpu_pairs", "inflight", "host_steps", "extra_configs", "c5_share", "latency")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and (plain.steps, plain.warmup) == (20, 5)
+    assert {k: getattr(plain, k) for k in extras} == {"cpu_pairs": 0, "inflight": 1, "host_steps": 0, "extra_configs": 0, "c5_share": 0, "latency": 0}
+    full = bench.parse_args(["--full", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert full.full and (full.steps, full.warmup) == (20, 5)
+    assert {k: getattr(full, k) for k in extras} == {"cpu_pairs": 96, "inflight": 2, "host_steps": 6, "extra_configs": 5, "c5_share": 12500, "latency": 1}
+    assert bench.parse_args(["--cpu-pairs", "8"]).cpu_pairs == 8
+    assert bench.parse_args(["--full", "--cpu-pairs", "0", "--inflight", "1"]).cpu_pairs == 0

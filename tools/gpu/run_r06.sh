@@ -6,7 +6,7 @@ WL=${@:-"calib_p3p_n2000_i10k shared_n2000_i10k varying_n5000_i10k calib_shift_n
 for w in $WL; do
   timeout 600 bash tools/profile_round.sh r06 $w > gpurun_out/pr_r06_$w.log 2>&1
 done
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r06_default_bench_line.json 2> gpurun_out/r06_default.err
+timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > profiles/r06_default_bench_line.json
 timeout 300 python bench.py --batch 12500 --steps 3 --warmup 1 --cpu-pairs 0 --host-steps 0 --extra-configs 0 --c5-share 0 --latency 0 > gpurun_out/r06_c5_bench_12500_pairs_1gpu.json 2> gpurun_out/r06_c5.err
 timeout 300 python bench.py --total-pairs 12500 --gpus 1 --steps 3 --warmup 1 --cpu-pairs 0 --host-steps 0 --inflight 1 > gpurun_out/r06_c5_total_pairs_1gpu.json 2>> gpurun_out/r06_c5.err
 timeout 300 python bench.py --workload shared_6pt_n2000_i10k --batch 256 --steps 2 --warmup 1 --inflight 1 --host-steps 0 --cpu-pairs 8 > gpurun_out/r06_shared_6pt_n2000_i10k_bench.json 2> gpurun_out/r06_6pt.err

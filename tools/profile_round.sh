@@ -28,7 +28,7 @@ for C in "FETCH_SIZE GRBM_GUI_ACTIVE" "WRITE_SIZE GRBM_GUI_ACTIVE" \
 done
 python3 $R/tools/pmc_json.py $W $B 2 $O/pmc_1.csv $O/pmc_2.csv $O/pmc_3.csv $O/pmc_4.csv > $O/pmc.json
 cp $O/pmc.json $R/profiles/${TAG}_pmc_$W.json   # so that the bench line below cites this round's PMC passes
-cd $R && python3 bench.py --workload $W --batch $B --extra-configs 0 --c5-share 0 --latency 0 --cpu-pairs ${CPU_PAIRS:-0} > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-400
+cd $R && python3 bench.py --full --workload $W --batch $B --extra-configs 0 --c5-share 0 --latency 0 --cpu-pairs ${CPU_PAIRS:-0} > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-400
 cp $O/kernel_stats.txt $R/profiles/${TAG}_${W}_kernel_stats.txt; cp $O/timeline.txt $R/profiles/${TAG}_${W}_timeline.txt
 tail -1 $O/bench.json > $R/profiles/${TAG}_${W}_bench.json
 mkdir -p $R/gpurun_out/profiles_$TAG; cp $R/profiles/${TAG}_*${W}* $R/gpurun_out/profiles_$TAG/
