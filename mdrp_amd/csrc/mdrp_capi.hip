@@ -24,6 +24,7 @@ MDRP_INSTANCES_CLASSIC
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -49,9 +50,14 @@ thread_local std::string g_err;
         }                                                                                                  \
     } while (0)
 
+// device memory of a handle: grows on demand, freed with the handle
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return MDRP_OK;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -66,9 +72,25 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// read back once per super-chunk: device counters at int32 index 2.. of the `counters` buffer
+// any other HIP object of a handle (stream, event, pinned host memory): destroyed with the handle, or when creating the handle fails half-way
+template <typename T, auto Destroy> struct Owned {
+    T v = nullptr;
+    Owned() = default;
+    Owned(Owned &&o) noexcept : v(o.v) { o.v = nullptr; }
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { reset(); }
+    void reset() { if (v) (void)Destroy(v); v = nullptr; }
+    operator T() const { return v; }
+    T operator->() const { return v; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+template <typename T> using Pinned = Owned<T *, hipHostFree>;
+
+// read back once per super-chunk
 struct Progress {
-    int32_t n_active; int32_t lo_overflow; // lo_overflow: a chunk found more triggers than the LM engine's problem table holds per pass
+    int32_t n_active, pad_;         // (pad_ keeps max_needed 8-byte aligned)
     unsigned long long max_needed;
     unsigned long long evals;       // (model x correspondence) evaluations the CPU loop would do: sum over pairs of models * n
     unsigned long long evals_mfma;  // evaluations executed by k_count on the matrix cores (padded to 16 x 16 tiles)
@@ -76,11 +98,17 @@ struct Progress {
     unsigned long long evals_bound; // evaluations executed by k_bound in fp32 (k_count's survivors * n)
     int32_t wish_sum, wish_pairs;   // final refinements: sum over the pairs of first_chunk_wish(inlier ratio of the result), number of pairs (RunParams::inl_stat)
 };
-static_assert(sizeof(Progress) == 14 * sizeof(int32_t), "Progress ends where the LO queue heads begin");
-constexpr int CNT_INL_STAT = 14; // int32 index of Progress::wish_sum in the `counters` buffer
-constexpr int CNT_LO_HEAD = 16; // int32 index of the LO queue heads (one per chunk) in the `counters` buffer
-constexpr int CNT_XCD_HEAD = 32; // int32 index of the per-XCD LO queue heads: [chunk][8] at LO_XCD_STRIDE ints (lo_take, mdrp_kernels.h)
-constexpr size_t COUNTERS_BYTES = sizeof(int32_t) * (CNT_XCD_HEAD + 8 * LO_XCD_STRIDE);
+// the `counters` buffer, zeroed at the start of every super-chunk
+struct Counters {
+    int32_t unused_[2];
+    Progress progress;
+    int32_t lo_head[16];                 // queue head of the super-chunk's LO launch, in a 64-byte block of its own
+    int32_t xcd_head[8 * LO_XCD_STRIDE]; // per-XCD LO queue heads, LO_XCD_STRIDE ints apart (lo_take, mdrp_kernels.h)
+};
+static_assert(offsetof(Counters, progress) == 2 * sizeof(int32_t) && offsetof(Counters, lo_head) == 16 * sizeof(int32_t) &&
+              offsetof(Counters, xcd_head) == 32 * sizeof(int32_t) && sizeof(Counters) == 640, "counter block layout");
+static_assert(offsetof(Progress, evals_mfma) == offsetof(Progress, evals) + sizeof(unsigned long long), "k_count adds to stats[0] and stats[1]");
+static_assert(offsetof(Progress, wish_pairs) == offsetof(Progress, wish_sum) + sizeof(int32_t), "RunParams::inl_stat is [2]");
 constexpr size_t LM_STATS_BYTES = 6 * sizeof(unsigned long long); // mdrp_handle::lm_stats
 
 // Every entry point runs on the handle's device and puts the caller's current device back on return (the caller is
@@ -103,24 +131,25 @@ struct DeviceGuard {
 struct mdrp_handle {
     std::mutex mu; // one call at a time per handle (scratch, events and counters are per handle); different handles run concurrently
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
-    hipStream_t aux_stream = nullptr;  // the second chunk's sampler + solver run here, beside the first chunk's sweep
-    hipStream_t aux_stream2 = nullptr; // the sample tables and the super-chunk's LO launch run here
-    hipStream_t copy_stream = nullptr; // host-buffer calls: the H2D slices of the correspondences
-    hipEvent_t ev_copied = nullptr, ev_prepped = nullptr, ev_solved6 = nullptr;
+    hipStream_t stream = nullptr;      // the caller's (null: the device's legacy default stream) or own_stream
+    Stream own_stream;
+    Stream aux_stream;                 // the second chunk's sampler + solver run here, beside the first chunk's sweep
+    Stream aux_stream2;                // the sample tables and the super-chunk's LO launch run here
+    Stream copy_stream;                // host-buffer calls: the H2D slices of the correspondences
+    Event ev_copied, ev_prepped, ev_solved6;
     DevBuf fuse;                       // fused tail: control words (64 B) | done_cnt[batch] | fin_done[batch] | ready[batch]
     static constexpr int NC_MAX = 8; // chunks of a super-chunk
-    hipEvent_t ev_lo = nullptr, ev_tables = nullptr, ev_sampled[2] = {}, ev_solved[NC_MAX] = {}, ev_scanned[NC_MAX] = {};
+    Event ev_lo, ev_tables, ev_sampled[2], ev_solved[NC_MAX], ev_scanned[NC_MAX];
     int num_cu = 256;
     // persistent device buffers
-    DevBuf pts, dep, st, samples;
+    DevBuf pts, dep, st;
     DevBuf params;                     // per-call parameters in ONE upload: table states | cameras | table sizes | table of pair | n per pair
-    unsigned char *params_host = nullptr; // pinned staging of the same
+    Pinned<unsigned char> params_host; // staging of the same
     size_t params_host_cap = 0;
-    DevBuf models, slot_score, slot_inl, tags, model_count, triggers, work_pair, counters, results, mask, plan;
-    DevBuf tags_s, tags2_s; // survivor lists ordered by candidate density (k_sort_tags)
-    DevBuf tags2, model_count2, samples2; // odd chunks of a super-chunk (chunk c + 1 is solved beside the sweep of chunk c)
+    DevBuf models, slot_score, slot_inl, triggers, work_pair, counters, results, mask, plan;
+    // [c & 1]: chunk c of a super-chunk (chunk c + 1 is solved beside the sweep of chunk c)
+    DevBuf samples[2], tags[2], model_count[2];
+    DevBuf tags_sorted[2]; // survivor lists ordered by candidate density (k_sort_tags)
     DevBuf tags_v, surv_count; // survivors of k_count (unsorted, with density keys) and their number per pair
     DevBuf cand_stat; // [2 batch] u64: candidates | evaluations of the run's first chunk per pair (k_count's split point)
     DevBuf und_count; // k_count's two phases: hypotheses phase A left undecided, per pair (stride 2); the list itself and the partial counts alias the sorted tag lists
@@ -128,23 +157,23 @@ struct mdrp_handle {
     DevBuf cplan;              // work plan of k_count / k_bound
     DevBuf surv2_count;        // survivors of k_bound per pair
     DevBuf lo_mask;            // 5-point LO: inlier subset of the refined model, one row per LO workgroup
-    DevBuf red5;               // 5-point solver: the Reduce5 blocks between its kernels, [pair][ceil(chunk / 64)][76][64] doubles, + a region for the first chunk (run_pass)
+    DevBuf red5;               // 5-point solver: the Reduce5 blocks between its kernels, [pair][ceil(chunk / 64)][76][64] doubles, + a region for the first chunk (PassScratch)
     DevBuf lm_stats;                  // six u64: correspondences evaluated by the LM cost / accumulate sweeps of the LO kernel | of the final kernel |
                                       // fused tail: gate time-outs | final-refinement wait time-outs
-    unsigned long long *lm_stats_host = nullptr; // pinned copy, valid after finish_timing
+    Pinned<unsigned long long> lm_stats_host; // copy, valid after finish_timing
     int64_t fuse_gate_timeouts = 0, fuse_wait_timeouts = 0; // of the last call
     int64_t first_chunk = 0;                                // of the last call (mdrp_stats::first_chunk)
     double seen_wish[3] = {-1.0, -1.0, -1.0};               // per monodepth estimator: mean first_chunk_wish over the results of its last call that measured it
-    int32_t *wish_host = nullptr; hipEvent_t ev_wish = nullptr; // unfused runs: the two sums are copied behind the final refinements and read by the next call
+    Pinned<int32_t> wish_host; Event ev_wish;               // unfused runs: the two sums are copied behind the final refinements and read by the next call
     int wish_kind = -1;                                     // ... of this estimator, once ev_wish has completed (-1: nothing pending)
     bool fuse_disabled = false;       // a bounded wait of the fused tail expired on this handle: streams do not overlap here, run unfused ...
     int fuse_retry_in = 0;            // ... for this many API calls, then try the fused tail again (a busy moment on a shared GPU is not a profiler)
     int fuse_backoff = 64;            // ... doubled after every consecutive expired wait (capped), reset by a call whose fused tail ran through
     DevBuf in_x1, in_x2, in_d1, in_d2; // staging when the caller passes host memory
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
-    Progress *progress_host = nullptr; // pinned
+    Pinned<Progress> progress_host;
     // sweep timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<Event, Event>> ev_pool;
     std::vector<int> ev_what; // 0 = k_score (fp64 sweep), 1 = k_count (MFMA), 2 = LO, 3 = final refinement, 4 = k_bound, 5 = minimal solver
     size_t ev_used = 0;
     double sweep_ms = 0.0, count_ms = 0.0;
@@ -232,10 +261,10 @@ size_t lm_final_list_bytes(int n_max) { return (size_t)(2 + lm_mask_index_on(n_m
 
 int get_events(mdrp_handle *h, hipEvent_t *a, hipEvent_t *b, int what = 0) {
     if (h->ev_used == h->ev_pool.size()) {
-        hipEvent_t x, y;
-        HIPCHK(hipEventCreate(&x));
-        HIPCHK(hipEventCreate(&y));
-        h->ev_pool.emplace_back(x, y);
+        Event x, y;
+        HIPCHK(hipEventCreate(&x.v));
+        HIPCHK(hipEventCreate(&y.v));
+        h->ev_pool.emplace_back(std::move(x), std::move(y));
         h->ev_what.push_back(0);
     }
     h->ev_what[h->ev_used] = what;
@@ -250,6 +279,75 @@ int solver_for(int kind, int est_shift) {
     return kind == MDRP_SHARED_FOCAL ? SOLVER_SHARED : SOLVER_VARYING;
 }
 
+int model_slots(int kind) { return kind == MDRP_RELPOSE_5PT ? 12 : (kind == MDRP_SHARED_6PT ? 16 : 4); } // model slots per sample
+int sample_size(int kind) { return kind == MDRP_RELPOSE_5PT ? 5 : (kind == MDRP_SHARED_6PT ? 6 : (kind == MDRP_FUNDAMENTAL_7PT ? 7 : 3)); }
+
+// MDRP_CHUNKS: the leading chunk lengths of a run's first super-chunk, its positive entries (at most NC_MAX - 1).  False where it is
+// not set: run_pass chooses them.
+bool env_chunks(std::vector<uint64_t> &lead) {
+    lead.clear();
+    const char *e = getenv("MDRP_CHUNKS");
+    if (!e) return false;
+    const std::string spec = e;
+    size_t pos = 0;
+    while (pos < spec.size() && (int)lead.size() < mdrp_handle::NC_MAX - 1) {
+        const size_t q = spec.find(',', pos);
+        const long v = atol(spec.substr(pos, q == std::string::npos ? std::string::npos : q - pos).c_str());
+        if (v > 0) lead.push_back((uint64_t)v);
+        if (q == std::string::npos) break;
+        pos = q + 1;
+    }
+    return true;
+}
+
+// Every buffer of handle h that a pass allocates, with its bytes: run_pass ensures exactly these, estimate_device sizes its passes from them.
+// `lead`: the leading chunks of the run's first super-chunk.
+struct PassScratch {
+    std::vector<std::pair<DevBuf *, size_t>> bufs;
+    size_t fuse; // (ensured by the super-chunk that runs the fused tail)
+    // `params`: table states | cameras 1 | cameras 2 | table sizes | table of pair | n per pair
+    size_t params, off_cam1, off_cam2, off_tn, off_tof, off_nper;
+    // Reduce5 blocks of the 5-point solver (issue_solve): [pair][ceil(len / 64)] blocks of RED5_STRIDE x 64 doubles per solve, in two regions.
+    // The first chunk of a super-chunk of several chunks is solved on the main stream while the second chunk's solver may run on `aux` (the
+    // sliced host-buffer front: the main stream waits for a slice's k_prep only, not for the solver issued behind it), so it gets a region of
+    // its own behind the shared one.  Its length is a leading chunk that leaves at least as much again behind it: at most lead[0] and
+    // chunk_cap / 2 iterations.
+    size_t red5_blocks, red5_first_blocks; // per pair
+    size_t total() const {
+        size_t t = fuse;
+        for (const auto &b : bufs) t += b.second;
+        return t;
+    }
+};
+
+PassScratch pass_scratch(mdrp_handle *h, int kind, int batch, int n_max, int n_tables, int chunk_cap, const std::vector<uint64_t> &lead) {
+    const size_t b = (size_t)batch, n = (size_t)n_max, t = (size_t)n_tables, slots = b * chunk_cap * model_slots(kind);
+    PassScratch z;
+    z.fuse = 64 + 3 * sizeof(int32_t) * b;
+    z.off_cam1 = sizeof(uint64_t) * t; z.off_cam2 = z.off_cam1 + sizeof(CamDev) * b; z.off_tn = z.off_cam2 + sizeof(CamDev) * b;
+    z.off_tof = z.off_tn + sizeof(int32_t) * t; z.off_nper = z.off_tof + sizeof(int32_t) * b; z.params = z.off_nper + sizeof(int32_t) * b;
+    z.red5_blocks = ((size_t)chunk_cap + 63) / 64;
+    z.red5_first_blocks = (std::min<uint64_t>(lead.empty() ? 0 : lead[0], (uint64_t)chunk_cap / 2) + 63) / 64;
+    const size_t samples = sizeof(uint32_t) * sample_size(kind) * t * chunk_cap, tags = sizeof(uint32_t) * slots, pair2 = sizeof(int32_t) * 2 * b;
+    z.bufs = { // (in the order of allocation: params_host is allocated behind params)
+        {&h->pts, sizeof(double) * PT_STRIDE * b * n}, {&h->dep, kind >= MDRP_RELPOSE_5PT ? 0 : sizeof(double) * 2 * b * n}, {&h->st, sizeof(PairState) * b},
+        {&h->samples[0], samples}, {&h->params, z.params},
+        {&h->models, sizeof(Model) * slots}, {&h->slot_score, sizeof(double) * slots}, {&h->slot_inl, sizeof(int32_t) * slots},
+        {&h->tags[0], tags}, {&h->model_count[0], pair2}, {&h->model_count[1], pair2}, {&h->tags[1], tags}, {&h->tags_sorted[0], tags},
+        {&h->tags_sorted[1], tags}, {&h->samples[1], samples}, {&h->tags_v, tags},
+        {&h->surv_count, sizeof(int32_t) * b}, {&h->cand_stat, sizeof(unsigned long long) * 2 * b}, {&h->und_count, pair2},
+        {&h->cplan, sizeof(int32_t) * (b + 1)}, {&h->surv2_count, sizeof(int32_t) * b},
+        {&h->rfrag, std::max<size_t>(1024, b * ((n + 15) / 16) * 1024)},
+        {&h->triggers, sizeof(Trigger) * b * chunk_cap},     // worst case: every iteration triggers
+        {&h->work_pair, sizeof(int32_t) * (3 * b + 2)},      // LO plan of a super-chunk: prefix | begin | end | total
+        {&h->counters, sizeof(Counters)},
+        {&h->plan, sizeof(int32_t) * (2 * b + 2 + 4 + 16)}, // k_plan's two prefix arrays (batch + 1 each) | its totals {dense, total, head} | spare
+        // the 5- and 6-point LO keeps the inlier subset of the model it refines: one row per LO workgroup (kc_lo launches num_cu * (8 | 2) of them)
+        {&h->lo_mask, (kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT) ? (size_t)h->num_cu * 8 * std::max<size_t>(n, 1) : 0},
+        {&h->red5, kind == MDRP_RELPOSE_5PT ? sizeof(double) * b * (z.red5_blocks + z.red5_first_blocks) * RED5_STRIDE * 64 : 0}};
+    return z;
+}
+
 // one pass = a contiguous range of pairs that fits the scratch budget
 // `host` (or null): the caller's HOST buffers of this pass; x1 ... d2 are then the handle's device staging buffers, still to be filled
 struct HostSrc { const double *x1, *x2, *d1, *d2; };
@@ -261,8 +359,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     hipStream_t s = h->stream;
     const int est_shift = (kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0;
     const bool classic = kind >= MDRP_RELPOSE_5PT;              // non-monodepth baselines (mdrp_classic.h)
-    const int mps = kind == MDRP_RELPOSE_5PT ? 12 : (kind == MDRP_SHARED_6PT ? 16 : 4); // model slots per sample
-    const int ssz = kind == MDRP_RELPOSE_5PT ? 5 : (kind == MDRP_SHARED_6PT ? 6 : (kind == MDRP_FUNDAMENTAL_7PT ? 7 : 3)); // sample size
+    const int mps = model_slots(kind), ssz = sample_size(kind);
 
     // ---- group pairs by correspondence count: one sample table per distinct N
     std::vector<int32_t> table_of(batch), tab_n;
@@ -277,63 +374,82 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     const int n_tables = (int)tab_n.size();
     std::vector<uint64_t> tab_state(n_tables, ro->seed);
 
-    const size_t slots = (size_t)batch * chunk_cap * mps;
+    // iterations that certainly run: the reference cannot stop before min_iterations + 1 (or max_iterations)
+    const uint64_t certain = ro->max_iterations == 0 ? 1 : std::min<uint64_t>(ro->max_iterations, ro->min_iterations + 1);
+    // A SUPER-CHUNK is a range of iterations that shares one LO + walk pass and one host read-back; it is swept in one or
+    // more CHUNKS (solve / count / bound / score / scan launch trains).  Inside the certain range nothing can stop, so the
+    // first super-chunk is split into a short chunk (128 iterations) that establishes the records and the rest, whose
+    // hypotheses are retired against those records by k_count (MFMA) and k_bound (fp32) unless they might break one.
+    // Beyond the certain range a super-chunk is one chunk sized by the largest remaining dynamic_max_iter.
+    // leading chunk lengths of the first super-chunk; the last chunk takes the rest.  The first chunk has no records to
+    // retire anything against, so it is scored exactly in full: keep it short.  Every later chunk goes through k_count /
+    // k_bound against the records of the chunks before it.  Measured on the benchmark shape: "128" 84.5 k pairs/s, "64" 82 k,
+    // "256" 82.5 k, "512" 82 k, "256,768" 79 k (every chunk costs ~10 launches and a solver hand-over).  The 7-point estimator gets a second leading
+    // chunk: at 50 % outliers one sample in 128 is outlier-free, so the records after 128 iterations are often those of a poor model and the rest of
+    // the run would be counted and bounded against a bar that retires little (round 6: k_bound 5.7 ms of a 16.4 ms step; with "128,1024" the bar
+    // the last 8848 iterations meet is that of 1152: 62.3 -> 87.3 k pairs/s; "128,512" 86.6 k, "256,1024" 87.6 k, "128,3300,3300" 78.3 k)
+    std::vector<uint64_t> lead;
+    const bool chunks_set = env_chunks(lead);
+    if (h->wish_kind >= 0 && hipEventQuery(h->ev_wish) == hipSuccess) { // an unfused run's sums have arrived
+        if (h->wish_host[1] > 0) h->seen_wish[h->wish_kind] = (double)h->wish_host[0] / (double)h->wish_host[1];
+        h->wish_kind = -1;
+    }
+    if (!chunks_set) {
+        // Round 6, with the two-phase count: at 50 % outliers the step is flat in the first chunk's length from 128 to 512 iterations (calibrated P3P
+        // 8.45-8.49 / 8.44-8.55 / 8.40-8.41 / 8.51-8.66 ms at 128 / 256 / 384 / 512; shared focal 8.05 -> 7.99 at 256 or 384) — what a longer first
+        // chunk costs in exact scoring it returns as a tighter bar — but NOT at other outlier ratios: one 3-point sample in 64 is outlier-free at
+        // 75 % outliers, one in 300 at 85 %, and a pair whose first chunk holds none sends the whole rest of its run through the fp32 bound and the
+        // exact sweep: 75 % outliers 124 k pairs/s with 128, 142 k with 256, 147 k with 384; 85 %: 78 k / 93 k / 104 k (136 k with 1024).  The
+        // outlier-free shape pays for it the other way round (every hypothesis of the first chunk is a good one and is scored in full: 72.3 k with
+        // 128, 71.1 k with 256, 69.5 k with 384).  Default: 256 for the 3-point estimators where the run is long enough to pay for it (a sixteenth of
+        // the iterations that certainly run, between 128 and 256), up to 512 for the 5-point one by the same rule (solver-bound: flat), 128,1024 for the 7-point one
+        // (above), 128 for the 6-point one; MDRP_CHUNKS=384 or 128,1024 for data with fewer than one inlier in four.
+        if (kind == MDRP_FUNDAMENTAL_7PT) lead = {128, 1024};
+        else if (kind == MDRP_SHARED_6PT) lead = {128};
+        else if (kind == MDRP_RELPOSE_5PT) lead = {std::min<uint64_t>(512, std::max<uint64_t>(128, certain / 16 / 64 * 64))};
+        else {
+            lead = {std::min<uint64_t>(256, std::max<uint64_t>(128, certain / 16 / 64 * 64))};
+            // ... and where the handle's previous call with this estimator (kind 0..2 here) has results to go by: the mean over its pairs of what each
+            // would have liked (first_chunk_wish, mdrp_kernels.h: 6 / r^3 iterations for the pair's inlier ratio r, between 256 and 1024; 128 for nearly
+            // outlier-free pairs) — the lengths the sweeps above found best at 0, 50, 75 and 85 % outliers, and for a batch that mixes them (20 / 50 / 70 /
+            // 85 % by pair: 93.7 k pairs/s at 128, 101 k at 256, 105 k at 384-512, 104 k at 1024).  A long run only (the first chunk stays under an
+            // eighth of it).
+            if (h->seen_wish[kind] >= 0.0 && certain >= 8192)
+                lead[0] = (uint64_t)std::min(1024.0, std::max(128.0, std::ceil(h->seen_wish[kind] / 64.0) * 64.0));
+        }
+    }
+
+    const PassScratch sz = pass_scratch(h, kind, batch, n_max, n_tables, chunk_cap, lead);
     int rc;
-    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * batch * n_max))) return rc;
-    if (!classic && (rc = h->dep.ensure(sizeof(double) * 2 * batch * n_max))) return rc;
-    if ((rc = h->st.ensure(sizeof(PairState) * batch))) return rc;
-    if ((rc = h->samples.ensure(sizeof(uint32_t) * ssz * (size_t)n_tables * chunk_cap))) return rc;
-    // the small per-call inputs travel as one block (six pageable copies cost ~60 us of an idle GPU in front of k_prep)
-    const size_t off_state = 0, off_cam1 = off_state + sizeof(uint64_t) * (size_t)n_tables, off_cam2 = off_cam1 + sizeof(CamDev) * (size_t)batch,
-                 off_tn = off_cam2 + sizeof(CamDev) * (size_t)batch, off_tof = off_tn + sizeof(int32_t) * (size_t)n_tables,
-                 off_nper = off_tof + sizeof(int32_t) * (size_t)batch, params_bytes = off_nper + sizeof(int32_t) * (size_t)batch;
-    if ((rc = h->params.ensure(params_bytes))) return rc;
-    if (h->params_host_cap < params_bytes) {
-        if (h->params_host) (void)hipHostFree(h->params_host);
-        h->params_host = nullptr; h->params_host_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&h->params_host, params_bytes + params_bytes / 2, hipHostMallocDefault));
-        h->params_host_cap = params_bytes + params_bytes / 2;
+    for (const auto &b : sz.bufs) {
+        if ((rc = b.first->ensure(b.second))) return rc; // (0 bytes: nothing to allocate)
+        // the small per-call inputs travel as one block (six pageable copies cost ~60 us of an idle GPU in front of k_prep)
+        if (b.first == &h->params && h->params_host_cap < sz.params) {
+            h->params_host.reset(); h->params_host_cap = 0;
+            HIPCHK(hipHostMalloc((void **)&h->params_host.v, sz.params + sz.params / 2, hipHostMallocDefault));
+            h->params_host_cap = sz.params + sz.params / 2;
+        }
     }
     unsigned char *pd = h->params.as<unsigned char>();
-    uint64_t *d_table_state = reinterpret_cast<uint64_t *>(pd + off_state);
-    CamDev *d_cams1 = reinterpret_cast<CamDev *>(pd + off_cam1), *d_cams2 = reinterpret_cast<CamDev *>(pd + off_cam2);
-    int32_t *d_table_n = reinterpret_cast<int32_t *>(pd + off_tn), *d_table_of = reinterpret_cast<int32_t *>(pd + off_tof),
-            *d_nper = reinterpret_cast<int32_t *>(pd + off_nper);
-    if ((rc = h->models.ensure(sizeof(Model) * slots))) return rc;
-    if ((rc = h->slot_score.ensure(sizeof(double) * slots))) return rc;
-    if ((rc = h->slot_inl.ensure(sizeof(int32_t) * slots))) return rc;
-    if ((rc = h->tags.ensure(sizeof(uint32_t) * slots))) return rc;
-    if ((rc = h->model_count.ensure(sizeof(int32_t) * 2 * batch))) return rc;
-    if ((rc = h->model_count2.ensure(sizeof(int32_t) * 2 * batch))) return rc;
-    if ((rc = h->tags2.ensure(sizeof(uint32_t) * slots))) return rc;
-    if ((rc = h->tags_s.ensure(sizeof(uint32_t) * slots))) return rc;
-    if ((rc = h->tags2_s.ensure(sizeof(uint32_t) * slots))) return rc;
-    if ((rc = h->samples2.ensure(sizeof(uint32_t) * ssz * (size_t)n_tables * chunk_cap))) return rc;
-    if ((rc = h->tags_v.ensure(sizeof(uint32_t) * slots))) return rc;
-    if ((rc = h->surv_count.ensure(sizeof(int32_t) * batch))) return rc;
-    if ((rc = h->cand_stat.ensure(sizeof(unsigned long long) * 2 * batch))) return rc;
-    if ((rc = h->und_count.ensure(sizeof(int32_t) * 2 * batch))) return rc;
-    if ((rc = h->cplan.ensure(sizeof(int32_t) * ((size_t)batch + 1)))) return rc;
-    if ((rc = h->surv2_count.ensure(sizeof(int32_t) * batch))) return rc;
+    uint64_t *d_table_state = reinterpret_cast<uint64_t *>(pd);
+    CamDev *d_cams1 = reinterpret_cast<CamDev *>(pd + sz.off_cam1), *d_cams2 = reinterpret_cast<CamDev *>(pd + sz.off_cam2);
+    int32_t *d_table_n = reinterpret_cast<int32_t *>(pd + sz.off_tn), *d_table_of = reinterpret_cast<int32_t *>(pd + sz.off_tof),
+            *d_nper = reinterpret_cast<int32_t *>(pd + sz.off_nper);
+    Counters *cnt = h->counters.as<Counters>();
     const size_t groups_max = ((size_t)n_max + 15) / 16;
-    if ((rc = h->rfrag.ensure(std::max<size_t>(1024, (size_t)batch * groups_max * 1024)))) return rc;
     const int trig_cap = chunk_cap;
-    if ((rc = h->triggers.ensure(sizeof(Trigger) * (size_t)batch * trig_cap))) return rc;
-    if ((rc = h->work_pair.ensure(sizeof(int32_t) * (3 * (size_t)batch + 2)))) return rc; // LO plan of a super-chunk: prefix | begin | end | total
-    if ((rc = h->counters.ensure(COUNTERS_BYTES))) return rc;
-    if ((rc = h->plan.ensure(sizeof(int32_t) * (2 * (size_t)batch + 2 + 4 + 16)))) return rc; // two prefix arrays + {dense, total, head} // [2] n_active, [4..5] max_needed (u64), [6..7] evals (u64), [8], [9] LO queue heads of the two chunks
 
     {
         unsigned char *ph = h->params_host; // free: the previous call on this handle ended with a stream synchronisation
-        std::memcpy(ph + off_state, tab_state.data(), sizeof(uint64_t) * n_tables);
+        std::memcpy(ph, tab_state.data(), sizeof(uint64_t) * n_tables);
         const bool cams = kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT;
         // MDRP_SHARED_6PT reads the principal point from cam1 only (include/mdrp.h): cam2 may be NULL there
-        if (cams) { std::memcpy(ph + off_cam1, cam1, sizeof(CamDev) * batch); std::memcpy(ph + off_cam2, cam2 ? cam2 : cam1, sizeof(CamDev) * batch); }
-        else std::memset(ph + off_cam1, 0, 2 * sizeof(CamDev) * (size_t)batch);
-        std::memcpy(ph + off_tn, tab_n.data(), sizeof(int32_t) * n_tables);
-        std::memcpy(ph + off_tof, table_of.data(), sizeof(int32_t) * batch);
-        std::memcpy(ph + off_nper, n_host, sizeof(int32_t) * batch);
-        HIPCHK(hipMemcpyAsync(pd, ph, params_bytes, hipMemcpyHostToDevice, s));
+        if (cams) { std::memcpy(ph + sz.off_cam1, cam1, sizeof(CamDev) * batch); std::memcpy(ph + sz.off_cam2, cam2 ? cam2 : cam1, sizeof(CamDev) * batch); }
+        else std::memset(ph + sz.off_cam1, 0, 2 * sizeof(CamDev) * (size_t)batch);
+        std::memcpy(ph + sz.off_tn, tab_n.data(), sizeof(int32_t) * n_tables);
+        std::memcpy(ph + sz.off_tof, table_of.data(), sizeof(int32_t) * batch);
+        std::memcpy(ph + sz.off_nper, n_host, sizeof(int32_t) * batch);
+        HIPCHK(hipMemcpyAsync(pd, ph, sz.params, hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipEventRecord(h->ev_tables, s)); // sample tables can be drawn from here on
 
@@ -367,6 +483,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         launch_prep(0, batch, s);
         HIPCHK(hipGetLastError());
     }
+    rp.inl_stat = classic ? nullptr : &cnt->progress.wish_sum;
 
     // Run-time knobs (DESIGN.md 10 lists all of them): the stream pipeline, the fp32 bound stage, lanes per LM problem.
     const bool lo_overlap = env_int("MDRP_LO_OVERLAP", 1) != 0; // three-stream pipeline; 0 = every kernel on the handle's stream
@@ -393,76 +510,21 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     // (fuse_disabled / fuse_retry_in are advanced once per API call in estimate_device, not per pass)
     const bool fuse_env = env_int("MDRP_FUSE_TAIL", ((kind == MDRP_CALIB && est_shift) || h->fuse_disabled) ? 0 : 1) != 0;
     bool final_done = false;
-    // the 5-point LO keeps the inlier subset of the model it refines: one row per LO workgroup and chunk (LOs of two chunks overlap)
-    const size_t lo_mask_rows = (size_t)h->num_cu * 8; // kc_lo launches num_cu * (8 | 2) workgroups
-    if ((kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT) && (rc = h->lo_mask.ensure(lo_mask_rows * (size_t)std::max(n_max, 1)))) return rc;
-    int32_t *cnt = h->counters.as<int32_t>();
-    rp.inl_stat = classic ? nullptr : cnt + CNT_INL_STAT;
+    // the final refinements of the pass's pairs on the main stream; the fused tail's (ready list, done flags, wait ticks, time-out counter), or
+    // (null, pairs to skip or null, 0, null)
+    auto launch_final = [&](const int32_t *ready, int32_t *fin_done, unsigned long long ticks, unsigned long long *timeouts) {
+        if (classic)
+            MDRP_CLASSIC_LM_DISPATCH(kc_final, final_threads, kind, dim3(batch), clm_list_bytes, s, rp, h->st.as<PairState>(), h->pts.as<double>(), mask_dev, results_dev,
+                                     ready, fin_done, ticks, timeouts, clm_list_stride);
+        else
+            MDRP_FINAL_DISPATCH(final_threads, rp.final_loss, kind, est_shift, dim3(batch), (mask_index ? lm_final_list_bytes(n_max) : lm_list_bytes(n_max)), s, rp,
+                                h->st.as<PairState>(), h->pts.as<double>(), h->dep.as<double>(), mask_dev, results_dev, lm_list_stride(n_max), mask_index,
+                                h->lm_stats.as<unsigned long long>() + 2, ready, fin_done, ticks, timeouts);
+    };
     const size_t tile_bytes = SCORE_TILE_BYTES;
 
     uint64_t it0 = 0;
-    // iterations that certainly run: the reference cannot stop before min_iterations + 1 (or max_iterations)
-    const uint64_t certain = ro->max_iterations == 0 ? 1 : std::min<uint64_t>(ro->max_iterations, ro->min_iterations + 1);
-    // A SUPER-CHUNK is a range of iterations that shares one LO + walk pass and one host read-back; it is swept in one or
-    // more CHUNKS (solve / count / bound / score / scan launch trains).  Inside the certain range nothing can stop, so the
-    // first super-chunk is split into a short chunk (128 iterations) that establishes the records and the rest, whose
-    // hypotheses are retired against those records by k_count (MFMA) and k_bound (fp32) unless they might break one.
-    // Beyond the certain range a super-chunk is one chunk sized by the largest remaining dynamic_max_iter.
-    // leading chunk lengths of the first super-chunk; the last chunk takes the rest.  The first chunk has no records to
-    // retire anything against, so it is scored exactly in full: keep it short.  Every later chunk goes through k_count /
-    // k_bound against the records of the chunks before it.  Measured on the benchmark shape: "128" 84.5 k pairs/s, "64" 82 k,
-    // "256" 82.5 k, "512" 82 k, "256,768" 79 k (every chunk costs ~10 launches and a solver hand-over).  The 7-point estimator gets a second leading
-    // chunk: at 50 % outliers one sample in 128 is outlier-free, so the records after 128 iterations are often those of a poor model and the rest of
-    // the run would be counted and bounded against a bar that retires little (round 6: k_bound 5.7 ms of a 16.4 ms step; with "128,1024" the bar
-    // the last 8848 iterations meet is that of 1152: 62.3 -> 87.3 k pairs/s; "128,512" 86.6 k, "256,1024" 87.6 k, "128,3300,3300" 78.3 k)
-    std::vector<uint64_t> lead;
-    {
-        const char *e = getenv("MDRP_CHUNKS");
-        // Round 6, with the two-phase count: at 50 % outliers the step is flat in the first chunk's length from 128 to 512 iterations (calibrated P3P
-        // 8.45-8.49 / 8.44-8.55 / 8.40-8.41 / 8.51-8.66 ms at 128 / 256 / 384 / 512; shared focal 8.05 -> 7.99 at 256 or 384) — what a longer first
-        // chunk costs in exact scoring it returns as a tighter bar — but NOT at other outlier ratios: one 3-point sample in 64 is outlier-free at
-        // 75 % outliers, one in 300 at 85 %, and a pair whose first chunk holds none sends the whole rest of its run through the fp32 bound and the
-        // exact sweep: 75 % outliers 124 k pairs/s with 128, 142 k with 256, 147 k with 384; 85 %: 78 k / 93 k / 104 k (136 k with 1024).  The
-        // outlier-free shape pays for it the other way round (every hypothesis of the first chunk is a good one and is scored in full: 72.3 k with
-        // 128, 71.1 k with 256, 69.5 k with 384).  Default: 256 for the 3-point estimators where the run is long enough to pay for it (a sixteenth of
-        // the iterations that certainly run, between 128 and 256), up to 512 for the 5-point one by the same rule (solver-bound: flat), 128,1024 for the 7-point one
-        // (above); MDRP_CHUNKS=384 or 128,1024 for data with fewer than one inlier in four.
-        std::string spec = e ? e : (kind == MDRP_FUNDAMENTAL_7PT ? "128,1024" : "128");
-        size_t pos = 0;
-        while (pos < spec.size() && (int)lead.size() < mdrp_handle::NC_MAX - 1) {
-            const size_t q = spec.find(',', pos);
-            const long v = atol(spec.substr(pos, q == std::string::npos ? std::string::npos : q - pos).c_str());
-            if (v > 0) lead.push_back((uint64_t)v);
-            if (q == std::string::npos) break;
-            pos = q + 1;
-        }
-        if (h->wish_kind >= 0 && hipEventQuery(h->ev_wish) == hipSuccess) { // an unfused run's sums have arrived
-            if (h->wish_host[1] > 0) h->seen_wish[h->wish_kind] = (double)h->wish_host[0] / (double)h->wish_host[1];
-            h->wish_kind = -1;
-        }
-        if (!e && kind == MDRP_RELPOSE_5PT) lead.assign(1, std::min<uint64_t>(512, std::max<uint64_t>(128, certain / 16 / 64 * 64)));
-        if (!e && !classic) {
-            lead.assign(1, std::min<uint64_t>(256, std::max<uint64_t>(128, certain / 16 / 64 * 64)));
-            // ... and where the handle's previous call with this estimator (kind 0..2 here) has results to go by: the mean over its pairs of what each
-            // would have liked (first_chunk_wish, mdrp_kernels.h: 6 / r^3 iterations for the pair's inlier ratio r, between 256 and 1024; 128 for nearly
-            // outlier-free pairs) — the lengths the sweeps above found best at 0, 50, 75 and 85 % outliers, and for a batch that mixes them (20 / 50 / 70 /
-            // 85 % by pair: 93.7 k pairs/s at 128, 101 k at 256, 105 k at 384-512, 104 k at 1024).  A long run only (the first chunk stays under an
-            // eighth of it).
-            if (h->seen_wish[kind] >= 0.0 && certain >= 8192)
-                lead[0] = (uint64_t)std::min(1024.0, std::max(128.0, std::ceil(h->seen_wish[kind] / 64.0) * 64.0));
-        }
-    }
-    // Reduce5 blocks of the 5-point solver (issue_solve): [pair][ceil(len / 64)] blocks of RED5_STRIDE x 64 doubles per solve, in two regions.
-    // The first chunk of a super-chunk of several chunks is solved on the main stream while the second chunk's solver may run on `aux` (the
-    // sliced host-buffer front: the main stream waits for a slice's k_prep only, not for the solver issued behind it), so it gets a region of
-    // its own behind the shared one.  Its length is a leading chunk that leaves at least as much again behind it: at most lead[0] and
-    // chunk_cap / 2 iterations (red5_first_blocks; the budget in estimate_device reserves the same).
-    const size_t red5_blocks = ((size_t)chunk_cap + 63) / 64;
-    const size_t red5_first_blocks = (std::min<uint64_t>(lead.empty() ? 0 : lead[0], (uint64_t)chunk_cap / 2) + 63) / 64;
-    if (kind == MDRP_RELPOSE_5PT &&
-        (rc = h->red5.ensure(sizeof(double) * (size_t)batch * (red5_blocks + red5_first_blocks) * RED5_STRIDE * 64))) return rc;
     uint64_t max_needed = 0;
-    rp.slot_stride = chunk_cap * mps;
     while (true) {
         uint64_t lens[mdrp_handle::NC_MAX] = {0};
         int n_chunks = 1;
@@ -483,7 +545,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         for (int c = 0; c < n_chunks; ++c) super_len += lens[c];
         if (it0 == 0) h->first_chunk = (int64_t)lens[0];
         rp.chunk_start = it0; rp.super_len = (int)super_len;
-        HIPCHK(hipMemsetAsync(h->counters.p, 0, COUNTERS_BYTES, s));
+        HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
         if (it0 == 0) HIPCHK(hipMemsetAsync(h->cand_stat.p, 0, sizeof(unsigned long long) * 2 * batch, s));
         // Three-stream pipeline over the chunks of a super-chunk (the benchmark shape: 128 | 9872 iterations):
         //   main:  prep solve0 count0 sort0 score0 scan0 | (wait solve1) count1 bound1 sort1 score1 scan1 | gate, final refinements (fused tail) | walk
@@ -496,7 +558,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         const bool fuse_tail = fuse_env && piped && it0 + super_len >= ro->max_iterations;
         int32_t *fz_ctl = nullptr, *fz_done = nullptr, *fz_fin = nullptr, *fz_ready = nullptr;
         if (fuse_tail) {
-            if ((rc = h->fuse.ensure(64 + 3 * sizeof(int32_t) * (size_t)batch))) return rc;
+            if ((rc = h->fuse.ensure(sz.fuse))) return rc;
             fz_ctl = h->fuse.as<int32_t>(); fz_done = fz_ctl + 16; fz_fin = fz_done + batch; fz_ready = fz_fin + batch;
         }
         hipStream_t aux = piped ? h->aux_stream : s, aux2 = piped ? h->aux_stream2 : s;
@@ -515,7 +577,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         if (piped && it0 == 0) {
             HIPCHK(hipStreamWaitEvent(aux2, h->ev_tables, 0));
             for (int c = 0; c < 2 && c < n_chunks; ++c) {
-                launch_samples(aux2, (int)lens[c], ((c & 1) ? h->samples2 : h->samples).as<uint32_t>());
+                launch_samples(aux2, (int)lens[c], h->samples[c & 1].as<uint32_t>());
                 HIPCHK(hipEventRecord(h->ev_sampled[c], aux2));
                 presampled[c] = true;
             }
@@ -526,11 +588,10 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         auto issue_solve = [&](int c, hipStream_t st_, int p0, int pc) -> int {
             RunParams r = rp;
             r.chunk_len = (int)lens[c]; r.chunk_off = offs[c]; r.batch = pc;
-            const bool odd = c & 1;
             const size_t so = (size_t)p0 * rp.slot_stride;
-            uint32_t *tg = (odd ? h->tags2 : h->tags).as<uint32_t>() + so;
-            uint32_t *smp = (odd ? h->samples2 : h->samples).as<uint32_t>();
-            int32_t *mc = (odd ? h->model_count2 : h->model_count).as<int32_t>() + 2 * (size_t)p0;
+            uint32_t *tg = h->tags[c & 1].as<uint32_t>() + so;
+            uint32_t *smp = h->samples[c & 1].as<uint32_t>();
+            int32_t *mc = h->model_count[c & 1].as<int32_t>() + 2 * (size_t)p0;
             HIPCHK(hipMemsetAsync(mc, 0, sizeof(int32_t) * 2 * pc, st_));
             if (c < 2 && presampled[c]) HIPCHK(hipStreamWaitEvent(st_, h->ev_sampled[c], 0));
             else launch_samples(st_, r.chunk_len, smp);
@@ -554,8 +615,8 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                     // beside another chunk's solver (the sliced front: chunk 0 on `s`, chunk 1 on `aux`): it alone uses the second region.  Every
                     // other solve is ordered behind the previous one by its stream or by ev_solved.
                     const bool first_region = c == 0 && n_chunks > 1;
-                    if (first_region && (size_t)sgrid.x > red5_first_blocks) { g_err = "5-point first chunk longer than its Reduce5 region"; return MDRP_ERR_INVALID; }
-                    double *red5 = h->red5.as<double>() + ((first_region ? (size_t)batch * red5_blocks : 0) + (size_t)p0 * sgrid.x) * RED5_STRIDE * 64;
+                    if (first_region && (size_t)sgrid.x > sz.red5_first_blocks) { g_err = "5-point first chunk longer than its Reduce5 region"; return MDRP_ERR_INVALID; }
+                    double *red5 = h->red5.as<double>() + ((first_region ? (size_t)batch * sz.red5_blocks : 0) + (size_t)p0 * sgrid.x) * RED5_STRIDE * 64;
                     hipLaunchKernelGGL(kc_solve5_null, sgrid, dim3(64), SOLVE5N_LDS_BYTES, st_, r, st_p, smp, pts_p, red5);
                     hipLaunchKernelGGL(kc_solve5_reduce, sgrid, dim3(64), SOLVE5_LDS_BYTES, st_, r, st_p, red5);
                     hipLaunchKernelGGL(kc_solve5_roots, sgrid, dim3(64), SOLVE5B_LDS_BYTES, st_, r, st_p, smp, pts_p, red5, models_p, inl_p, tg, mc);
@@ -586,16 +647,16 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
             PairState *st_p = h->st.as<PairState>() + p0;
             const double *pts_p = h->pts.as<double>() + (size_t)p0 * n_max * PT_STRIDE;
             const Model *models_p = h->models.as<Model>() + so;
-            uint32_t *tags_sc = (odd ? h->tags2_s : h->tags_s).as<uint32_t>() + so;
-            int32_t *mcount_c = (odd ? h->model_count2 : h->model_count).as<int32_t>() + 2 * (size_t)p0;
-            uint32_t *tags_c = (odd ? h->tags2 : h->tags).as<uint32_t>() + so;
+            uint32_t *tags_sc = h->tags_sorted[odd].as<uint32_t>() + so;
+            int32_t *mcount_c = h->model_count[odd].as<int32_t>() + 2 * (size_t)p0;
+            uint32_t *tags_c = h->tags[odd].as<uint32_t>() + so;
             uint32_t *tags_v = h->tags_v.as<uint32_t>() + so;
             int32_t *surv1 = h->surv_count.as<int32_t>() + p0, *surv2 = h->surv2_count.as<int32_t>() + p0;
             hipEvent_t e0, e1;
             int rc_;
             if ((rc_ = get_events(h, &e0, &e1, 0))) return rc_;
             // candidate counts on the matrix cores against the records of the chunks before this one; survivors only go on
-            unsigned long long *cstats = reinterpret_cast<unsigned long long *>(cnt + 6);
+            unsigned long long *cstats = &cnt->progress.evals; // (and evals_mfma)
             {
                 hipEvent_t c0, c1;
                 if ((rc_ = get_events(h, &c0, &c1, 1))) return rc_;
@@ -606,7 +667,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                 // The undecided list lives where this chunk's SORTED list will be written once the counts are done (k_sort_tags, below), the partial counts
                 // in the other parity's sorted list, whose last reader was the previous chunk's exact sweep: no scratch of their own.
                 uint32_t *tags_u = tags_sc;
-                int32_t *und_part = reinterpret_cast<int32_t *>((odd ? h->tags_s : h->tags2_s).as<uint32_t>() + so), *und_cnt = h->und_count.as<int32_t>() + 2 * (size_t)p0;
+                int32_t *und_part = reinterpret_cast<int32_t *>(h->tags_sorted[!odd].as<uint32_t>() + so), *und_cnt = h->und_count.as<int32_t>() + 2 * (size_t)p0;
                 const uint4 *rfrag_p = h->rfrag.as<uint4>() + (size_t)p0 * groups_max * 64;
                 hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, st_p, mcount_c, 2, CNT_WG_MODELS, h->cplan.as<int32_t>(),
                                    surv1, (const int32_t *)nullptr, two_phase ? und_cnt : (int32_t *)nullptr); // (also clears the counters k_count appends to)
@@ -633,7 +694,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                 // fp32 lower bound of the score for k_count's survivors; its survivors go back into the chunk's tag list
                 hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, st_p, surv1, 1, BND_THREADS, h->cplan.as<int32_t>(), surv2, (const int32_t *)nullptr);
                 const dim3 bgrid((unsigned)pc * (unsigned)((len * mps + BND_THREADS - 1) / BND_THREADS));
-                unsigned long long *bstats = reinterpret_cast<unsigned long long *>(cnt + 12);
+                unsigned long long *bstats = &cnt->progress.evals_bound;
                 hipEvent_t b0, b1;
                 if ((rc_ = get_events(h, &b0, &b1, 4))) return rc_;
                 HIPCHK(hipEventRecord(b0, s));
@@ -662,7 +723,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
             HIPCHK(hipEventRecord(e1, s));
             h->sweep_launches++;
             Trigger *trig_p = h->triggers.as<Trigger>() + (size_t)p0 * trig_cap;
-            unsigned long long *scan_stats = reinterpret_cast<unsigned long long *>(cnt + 10);
+            unsigned long long *scan_stats = &cnt->progress.evals_sweep;
             // (four iterations per lane where the chunk is long: a 9872-iteration chunk is 39 steps of one wavefront instead of 154)
 #define MDRP_SCAN(M, I) hipLaunchKernelGGL((k_scan<M, I>), dim3(pc), dim3(64), 0, s, r, st_p, h->slot_score.as<double>() + so, h->slot_inl.as<int32_t>() + so, trig_p, trig_cap, mcount_c, scan_stats)
             if (mps == 16) MDRP_SCAN(16, 1);
@@ -749,18 +810,18 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
             const int lo_blocks = h->num_cu * (lo_threads == 64 ? 8 : 2);
             const FuseTail fz = fuse_tail ? FuseTail{fz_done, fz_ready, fz_ctl, h->st.as<PairState>()} : FuseTail{nullptr, nullptr, nullptr, nullptr};
             unsigned long long *lm_stats = h->lm_stats.as<unsigned long long>();
-            int32_t *xheads = cnt + CNT_XCD_HEAD; // one LO queue per XCD (lo_take)
+            int32_t *xheads = cnt->xcd_head; // one LO queue per XCD (lo_take)
             hipEvent_t l0, l1; // HIP events on the stream the LO runs on (mdrp_stats::lo_ms)
             if ((rc = get_events(h, &l0, &l1, 2))) return rc;
             HIPCHK(hipEventRecord(l0, aux2));
             if (classic)
                 MDRP_CLASSIC_LM_DISPATCH(kc_lo, lo_threads, kind, dim3(lo_blocks), clm_list_bytes, aux2, rp, h->st.as<PairState>(), h->pts.as<double>(),
-                                         h->models.as<Model>(), h->triggers.as<Trigger>(), trig_cap, lo_plan, cnt + CNT_LO_HEAD, xheads,
+                                         h->models.as<Model>(), h->triggers.as<Trigger>(), trig_cap, lo_plan, cnt->lo_head, xheads,
                                          h->lo_mask.as<uint8_t>(), clm_list_stride, fz);
             else
                 MDRP_LM_DISPATCH(k_lo, lo_threads, kind, est_shift, dim3(lo_blocks), lm_list_bytes(n_max), aux2, rp,
                                  h->st.as<PairState>(), h->pts.as<double>(), h->dep.as<double>(), h->models.as<Model>(), h->triggers.as<Trigger>(),
-                                 trig_cap, lo_plan, cnt + CNT_LO_HEAD, xheads, lm_list_stride(n_max), lm_stats, fz);
+                                 trig_cap, lo_plan, cnt->lo_head, xheads, lm_list_stride(n_max), lm_stats, fz);
             HIPCHK(hipEventRecord(l1, aux2));
         }
         if (fuse_tail) { // final refinements on the main stream, released when the last LO launch's queue is empty
@@ -773,39 +834,25 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
             const long long n_scale = std::max(1, (n_max + 1999) / 2000);
             const unsigned long long gate_ticks = 100ull * (unsigned long long)env_int("MDRP_FUSE_GATE_US", (int)std::min<long long>((50000 + 40ll * batch) * n_scale, 200000));
             const unsigned long long wait_ticks = 100ull * (unsigned long long)env_int("MDRP_FUSE_WAIT_US", (int)std::min<long long>((20000 + 4ll * batch) * n_scale, 100000));
-            hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, s, (const int32_t *)(cnt + CNT_LO_HEAD), plan_l + 3 * (size_t)batch + 1,
+            hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, s, (const int32_t *)cnt->lo_head, plan_l + 3 * (size_t)batch + 1,
                                (const int32_t *)fz_ctl, lo_blocks_l, gate_ticks, h->lm_stats.as<unsigned long long>() + 4);
             hipEvent_t g0, g1;
             if ((rc = get_events(h, &g0, &g1, 3))) return rc;
             HIPCHK(hipEventRecord(g0, s));
-            if (classic)
-                MDRP_CLASSIC_LM_DISPATCH(kc_final, final_threads, kind, dim3(batch), clm_list_bytes, s, rp, h->st.as<PairState>(), h->pts.as<double>(), mask_dev, results_dev,
-                                         (const int32_t *)fz_ready, fz_fin, wait_ticks, h->lm_stats.as<unsigned long long>() + 5, clm_list_stride);
-            else
-                MDRP_FINAL_DISPATCH(final_threads, rp.final_loss, kind, est_shift, dim3(batch), (mask_index ? lm_final_list_bytes(n_max) : lm_list_bytes(n_max)), s, rp, h->st.as<PairState>(),
-                                 h->pts.as<double>(), h->dep.as<double>(), mask_dev, results_dev, lm_list_stride(n_max), mask_index,
-                                 h->lm_stats.as<unsigned long long>() + 2, (const int32_t *)fz_ready, fz_fin, wait_ticks,
-                                 h->lm_stats.as<unsigned long long>() + 5);
+            launch_final(fz_ready, fz_fin, wait_ticks, h->lm_stats.as<unsigned long long>() + 5);
             HIPCHK(hipEventRecord(g1, s));
             final_done = true;
         }
         if (piped) { HIPCHK(hipEventRecord(h->ev_lo, aux2)); HIPCHK(hipStreamWaitEvent(s, h->ev_lo, 0)); }
-        if (fuse_tail) { // behind the LO launch: the pairs a bounded wait gave up on (none in a healthy run: 1024 workgroups that read a flag)
-            if (classic)
-                MDRP_CLASSIC_LM_DISPATCH(kc_final, final_threads, kind, dim3(batch), clm_list_bytes, s, rp, h->st.as<PairState>(), h->pts.as<double>(), mask_dev, results_dev,
-                                         (const int32_t *)nullptr, fz_fin, 0ull, (unsigned long long *)nullptr, clm_list_stride);
-            else
-                MDRP_FINAL_DISPATCH(final_threads, rp.final_loss, kind, est_shift, dim3(batch), (mask_index ? lm_final_list_bytes(n_max) : lm_list_bytes(n_max)), s, rp, h->st.as<PairState>(),
-                                 h->pts.as<double>(), h->dep.as<double>(), mask_dev, results_dev, lm_list_stride(n_max), mask_index,
-                                 h->lm_stats.as<unsigned long long>() + 2, (const int32_t *)nullptr, fz_fin, 0ull, (unsigned long long *)nullptr);
-        }
+        if (fuse_tail) // behind the LO launch: the pairs a bounded wait gave up on (none in a healthy run: 1024 workgroups that read a flag)
+            launch_final(nullptr, fz_fin, 0, nullptr);
         if (!fuse_tail)
             hipLaunchKernelGGL(k_walk, dim3((batch + 63) / 64), dim3(64), 0, s, rp, h->st.as<PairState>(), h->models.as<Model>(),
-                               h->triggers.as<Trigger>(), trig_cap, cnt + 2, reinterpret_cast<unsigned long long *>(cnt + 4),
+                               h->triggers.as<Trigger>(), trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed,
                                (const int32_t *)nullptr, 0, 0, 0);
         HIPCHK(hipGetLastError());
         // progress record: pairs still iterating, iterations they still need, evaluations swept (sum over pairs of models * n)
-        HIPCHK(hipMemcpyAsync(h->progress_host, cnt + 2, sizeof(Progress), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h->progress_host, &cnt->progress, sizeof(Progress), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         h->sweep_evals += (int64_t)h->progress_host->evals;
         h->mfma_evals += (int64_t)h->progress_host->evals_mfma;
@@ -827,14 +874,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     hipEvent_t f0, f1;
     if ((rc = get_events(h, &f0, &f1, 3))) return rc;
     HIPCHK(hipEventRecord(f0, s));
-    if (classic)
-        MDRP_CLASSIC_LM_DISPATCH(kc_final, final_threads, kind, dim3(batch), clm_list_bytes, s, rp, h->st.as<PairState>(), h->pts.as<double>(), mask_dev, results_dev,
-                                 (const int32_t *)nullptr, (int32_t *)nullptr, 0ull, (unsigned long long *)nullptr, clm_list_stride);
-    else {
-        MDRP_FINAL_DISPATCH(final_threads, rp.final_loss, kind, est_shift, dim3(batch), (mask_index ? lm_final_list_bytes(n_max) : lm_list_bytes(n_max)), s, rp, h->st.as<PairState>(),
-                         h->pts.as<double>(), h->dep.as<double>(), mask_dev, results_dev, lm_list_stride(n_max), mask_index,
-                         h->lm_stats.as<unsigned long long>() + 2, (const int32_t *)nullptr, (int32_t *)nullptr, 0ull, (unsigned long long *)nullptr);
-    }
+    launch_final(nullptr, nullptr, 0, nullptr);
     HIPCHK(hipEventRecord(f1, s));
     if (rp.inl_stat && h->wish_kind < 0) { // (the fused tail's sums came with the progress record; these arrive when the stream gets here: the next call looks)
         HIPCHK(hipMemcpyAsync(h->wish_host, rp.inl_stat, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -843,22 +883,6 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     }
     HIPCHK(hipGetLastError());
     return MDRP_OK;
-}
-
-// longest first chunk of the 5-point estimator that is solved beside the second one (run_pass: the second Reduce5 region): the first leading
-// chunk (MDRP_CHUNKS, default at most 512 iterations), at most half the chunk capacity
-size_t red5_first_len(int chunk_cap) {
-    uint64_t first = 512;
-    if (const char *e = getenv("MDRP_CHUNKS")) {
-        first = 0;
-        for (const char *q = e; *q; ++q) { // the first positive entry, as run_pass parses the list
-            const long v = atol(q);
-            if (v > 0) { first = (uint64_t)v; break; }
-            while (*q && *q != ',') ++q;
-            if (!*q) break;
-        }
-    }
-    return (size_t)std::min<uint64_t>(first, (uint64_t)chunk_cap / 2);
 }
 
 int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
@@ -872,7 +896,6 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     // RansacOptions switches of the reference that are not built are refused, never ignored (the reference would return different results)
     if (ro->progressive_sampling) { g_err = "progressive_sampling (PROSAC, RandomSampler::initialize_prosac) is not built"; return MDRP_ERR_UNSUPPORTED; }
     if (ro->real_focal_check && (kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT)) { g_err = "real_focal_check is not built"; return MDRP_ERR_UNSUPPORTED; }
-    const int mps = kind == MDRP_RELPOSE_5PT ? 12 : (kind == MDRP_SHARED_6PT ? 16 : 4);
     if (h->fuse_disabled && --h->fuse_retry_in <= 0) h->fuse_disabled = false; // once per API call (not per pass): the handle tries the fused tail again
     h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
     int rc;
@@ -896,12 +919,14 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     const int chunk_cap = (int)chunk_cap64;
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t per_pair = (size_t)chunk_cap * mps * (sizeof(Model) + sizeof(double) + 2 * sizeof(int32_t) + 4 * sizeof(uint32_t) /*tag lists*/) +
-                            (size_t)chunk_cap * (sizeof(Trigger) + 8) + (size_t)n_max * (PT_STRIDE + 2) * sizeof(double) + 1024;
-    const size_t per_pair_all = per_pair + (size_t)chunk_cap * mps * sizeof(uint32_t) /*tags_v*/ + ((size_t)n_max + 15) / 16 * 1024 /*rfrag*/ +
-                                (kind == MDRP_RELPOSE_5PT ? (((size_t)chunk_cap + 63) / 64 + (red5_first_len(chunk_cap) + 63) / 64) * RED5_STRIDE * 64 * sizeof(double) : 0) /*red5*/;
+    // What one more pair adds to a pass's scratch (every buffer of a pass grows linearly with its pairs and its sample tables), with one sample table
+    // per pair (a ragged batch may have as many).  Of the leading chunks, only the 5-point solver's second Reduce5 region depends on them: the
+    // default first chunk of that estimator is at most 512 iterations (run_pass).
+    std::vector<uint64_t> lead;
+    if (!env_chunks(lead)) lead.assign(1, 512);
+    const size_t per_pair = pass_scratch(h, kind, 2, n_max, 2, chunk_cap, lead).total() - pass_scratch(h, kind, 1, n_max, 1, chunk_cap, lead).total();
     size_t budget = std::min<size_t>((size_t)(0.5 * (double)free_b), (size_t)96 << 30);
-    int per_pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, budget / per_pair_all));
+    int per_pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, budget / per_pair));
     per_pass = std::min(per_pass, 65535); // k_solve / k_probe put the pair index on grid.y
     per_pass = std::max(1, std::min(per_pass, env_int("MDRP_PAIRS_PER_PASS", per_pass))); // (tests: several passes on a small batch)
     for (int p0 = 0; p0 < batch; p0 += per_pass) {
@@ -1002,35 +1027,30 @@ static int create_handle(int device, hipStream_t stream, bool own_stream, mdrp_h
     }
     DeviceGuard guard_(device);
     if (!guard_.ok) { g_err = "hipSetDevice failed"; return MDRP_ERR_HIP; }
-    mdrp_handle *h = new mdrp_handle();
+    std::unique_ptr<mdrp_handle> h(new mdrp_handle()); // (a failed step below releases what the steps before it made)
     h->device = device;
-    if (!own_stream) { h->stream = stream; h->owns_stream = false; } // NULL here = the device's legacy default stream
-    else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->owns_stream = true; }
+    if (own_stream) HIPCHK(hipStreamCreateWithFlags(&h->own_stream.v, hipStreamNonBlocking));
+    h->stream = own_stream ? h->own_stream.v : stream; // NULL here = the device's legacy default stream
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIPCHK(hipHostMalloc((void **)&h->progress_host, sizeof(Progress), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&h->lm_stats_host, LM_STATS_BYTES, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&h->wish_host, 2 * sizeof(int32_t), hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_wish, hipEventDisableTiming));
+    HIPCHK(hipHostMalloc((void **)&h->progress_host.v, sizeof(Progress), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&h->lm_stats_host.v, LM_STATS_BYTES, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&h->wish_host.v, 2 * sizeof(int32_t), hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_wish.v, hipEventDisableTiming));
     std::memset(h->lm_stats_host, 0, LM_STATS_BYTES);
     {   // high priority: the few long LO wavefronts should be placed first, the sweeps fill the remaining slots
         int prio_lo = 0, prio_hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        HIPCHK(hipStreamCreateWithPriority(&h->aux_stream, hipStreamNonBlocking, prio_hi));
-        HIPCHK(hipStreamCreateWithPriority(&h->aux_stream2, hipStreamNonBlocking, prio_hi));
+        HIPCHK(hipStreamCreateWithPriority(&h->aux_stream.v, hipStreamNonBlocking, prio_hi));
+        HIPCHK(hipStreamCreateWithPriority(&h->aux_stream2.v, hipStreamNonBlocking, prio_hi));
     }
-    HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_copied, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_prepped, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_solved6, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_lo, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_tables, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_sampled[0], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_sampled[1], hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithFlags(&h->copy_stream.v, hipStreamNonBlocking));
+    for (Event *e : {&h->ev_copied, &h->ev_prepped, &h->ev_solved6, &h->ev_lo, &h->ev_tables, &h->ev_sampled[0], &h->ev_sampled[1]})
+        HIPCHK(hipEventCreateWithFlags(&e->v, hipEventDisableTiming));
     for (int i = 0; i < mdrp_handle::NC_MAX; ++i) {
-        HIPCHK(hipEventCreateWithFlags(&h->ev_solved[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_scanned[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&h->ev_solved[i].v, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&h->ev_scanned[i].v, hipEventDisableTiming));
     }
     const int tile_bytes = (int)SCORE_TILE_BYTES;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_score<true>), hipFuncAttributeMaxDynamicSharedMemorySize, tile_bytes));
@@ -1038,8 +1058,38 @@ static int create_handle(int device, hipStream_t stream, bool own_stream, mdrp_h
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_score<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, tile_bytes));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kc_solve5_reduce), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SOLVE5_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kc_solver_unit<CLASSIC_RELPOSE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SOLVE5_LDS_BYTES));
-    *out = h;
+    *out = h.release();
     return MDRP_OK;
+}
+
+// the single-pair entry points (mdrp_score_models, mdrp_count_candidates, mdrp_bound_models): hypotheses 0 .. count - 1 in `tags` ...
+static int upload_iota(hipStream_t s, void *tags, int count) {
+    std::vector<uint32_t> iota(count);
+    for (int i = 0; i < count; ++i) iota[i] = (uint32_t)i;
+    HIPCHK(hipMemcpyAsync(tags, iota.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, s));
+    return MDRP_OK;
+}
+// ... and one pair without records (nothing is pruned or retired: every model sees every correspondence): its state, its correspondences packed
+// into h->pts from the device copies x1, x2, and their box
+static int stage_unit_pair(mdrp_handle *h, const double *x1, const double *x2, int n, double sq_threshold) {
+    hipStream_t s = h->stream;
+    PairState ps;
+    std::memset(&ps, 0, sizeof ps);
+    ps.n = n; ps.active = 1; ps.sq_thr = sq_threshold; ps.eps = std::sqrt(sq_threshold);
+    ps.best_min_score = DBL_MAX;
+    HIPCHK(hipMemcpyAsync(h->st.p, &ps, sizeof ps, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, x1, x2, (const double *)nullptr,
+                       (const double *)nullptr, h->pts.as<double>(), (double *)nullptr);
+    hipLaunchKernelGGL(k_box_unit, dim3(1), dim3(256), 0, s, n, h->pts.as<double>(), h->st.as<PairState>());
+    return MDRP_OK;
+}
+
+static LmOpt lm_opt(const mdrp_bundle_opt *opt) {
+    LmOpt o;
+    o.max_it = (int)std::min<uint64_t>(opt->max_iterations, 1u << 30); o.loss = opt->loss_type; o.loss_scale = opt->loss_scale;
+    o.grad_tol = opt->gradient_tol; o.step_tol = opt->step_tol; o.lambda0 = opt->initial_lambda;
+    o.lambda_min = opt->min_lambda; o.lambda_max = opt->max_lambda;
+    return o;
 }
 
 extern "C" {
@@ -1047,33 +1097,9 @@ extern "C" {
 void mdrp_destroy(mdrp_handle *h) {
     if (!h) return;
     DeviceGuard guard_(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    DevBuf *bufs[] = {&h->pts, &h->dep, &h->st, &h->samples, &h->params, &h->fuse, &h->models, &h->slot_score, &h->slot_inl, &h->tags, &h->model_count, &h->triggers, &h->work_pair,
-                      &h->counters, &h->results, &h->mask, &h->in_x1, &h->in_x2, &h->in_d1, &h->in_d2, &h->unit_a,
-                      &h->unit_b, &h->unit_c, &h->unit_d, &h->unit_e, &h->unit_f, &h->plan, &h->tags2, &h->model_count2, &h->samples2, &h->tags_s, &h->tags2_s,
-                      &h->tags_v, &h->surv_count, &h->und_count, &h->cand_stat, &h->red5, &h->rfrag, &h->cplan, &h->surv2_count, &h->lo_mask,
-                      &h->lm_stats};
-    for (DevBuf *b : bufs) b->release();
-    for (auto &e : h->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    if (h->progress_host) (void)hipHostFree(h->progress_host);
-    if (h->wish_host) (void)hipHostFree(h->wish_host);
-    if (h->ev_wish) (void)hipEventDestroy(h->ev_wish);
-    if (h->lm_stats_host) (void)hipHostFree(h->lm_stats_host);
-    if (h->params_host) (void)hipHostFree(h->params_host);
-    if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
-    if (h->aux_stream2) { (void)hipStreamSynchronize(h->aux_stream2); (void)hipStreamDestroy(h->aux_stream2); }
-    if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
-    if (h->ev_copied) (void)hipEventDestroy(h->ev_copied);
-    if (h->ev_prepped) (void)hipEventDestroy(h->ev_prepped);
-    if (h->ev_solved6) (void)hipEventDestroy(h->ev_solved6);
-    if (h->ev_lo) (void)hipEventDestroy(h->ev_lo);
-    if (h->ev_tables) (void)hipEventDestroy(h->ev_tables);
-    for (int i = 0; i < 2; ++i) if (h->ev_sampled[i]) (void)hipEventDestroy(h->ev_sampled[i]);
-    for (int i = 0; i < mdrp_handle::NC_MAX; ++i) {
-        if (h->ev_solved[i]) (void)hipEventDestroy(h->ev_solved[i]);
-        if (h->ev_scanned[i]) (void)hipEventDestroy(h->ev_scanned[i]);
-    }
-    if (h->owns_stream) (void)hipStreamDestroy(h->stream);
+    // no kernel or copy of the handle may still run when its memory goes: every stream first, then the handle, whose members free themselves
+    // (a caller's stream is not the handle's to destroy)
+    for (hipStream_t st : {h->stream, (hipStream_t)h->aux_stream, (hipStream_t)h->aux_stream2, (hipStream_t)h->copy_stream}) (void)hipStreamSynchronize(st);
     delete h;
 }
 
@@ -1235,8 +1261,8 @@ int mdrp_score_models(mdrp_handle *h, int kind, int mem_space, const mdrp_model 
     int rc;
     if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * std::max(n, 1))) || (rc = h->st.ensure(sizeof(PairState))) ||
         (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_score.ensure(sizeof(double) * slots)) ||
-        (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) || (rc = h->tags.ensure(sizeof(uint32_t) * slots)) ||
-        (rc = h->model_count.ensure(2 * sizeof(int32_t))))
+        (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) || (rc = h->tags[0].ensure(sizeof(uint32_t) * slots)) ||
+        (rc = h->model_count[0].ensure(2 * sizeof(int32_t))))
         return rc;
     const double *x1d = x1, *x2d = x2;
     const Model *md = reinterpret_cast<const Model *>(models);
@@ -1251,19 +1277,10 @@ int mdrp_score_models(mdrp_handle *h, int kind, int mem_space, const mdrp_model 
         HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyDeviceToDevice, s));
         md = h->models.as<Model>();
     }
-    std::vector<uint32_t> tags(num_models);
-    for (int i = 0; i < num_models; ++i) tags[i] = (uint32_t)i;
-    HIPCHK(hipMemcpyAsync(h->tags.p, tags.data(), sizeof(uint32_t) * num_models, hipMemcpyHostToDevice, s));
+    if ((rc = upload_iota(s, h->tags[0].p, num_models))) return rc;
     const int32_t counts2[2] = {num_models, 0};
-    HIPCHK(hipMemcpyAsync(h->model_count.p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    PairState ps;
-    std::memset(&ps, 0, sizeof ps);
-    ps.n = n; ps.active = 1; ps.sq_thr = sq_threshold; ps.eps = std::sqrt(sq_threshold);
-    ps.best_min_score = DBL_MAX; // no records: nothing is pruned
-    HIPCHK(hipMemcpyAsync(h->st.p, &ps, sizeof ps, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, x1d, x2d, (const double *)nullptr,
-                       (const double *)nullptr, h->pts.as<double>(), (double *)nullptr);
-    hipLaunchKernelGGL(k_box_unit, dim3(1), dim3(256), 0, s, n, h->pts.as<double>(), h->st.as<PairState>());
+    HIPCHK(hipMemcpyAsync(h->model_count[0].p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if ((rc = stage_unit_pair(h, x1d, x2d, n, sq_threshold))) return rc;
     RunParams rp;
     std::memset(&rp, 0, sizeof rp);
     rp.kind = kind; rp.batch = 1; rp.n_max = std::max(n, 1); rp.chunk_len = chunk; rp.chunk_off = 0; rp.slot_stride = chunk * 4; rp.super_len = chunk;
@@ -1271,14 +1288,14 @@ int mdrp_score_models(mdrp_handle *h, int kind, int mem_space, const mdrp_model 
     const size_t tile_bytes = SCORE_TILE_BYTES;
     if ((rc = h->plan.ensure(sizeof(int32_t) * 8))) return rc;
     int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 4;
-    hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->model_count.as<int32_t>(), plan, totals);
+    hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->model_count[0].as<int32_t>(), plan, totals);
     const dim3 grid((unsigned)std::min(h->num_cu * 4, (num_models + SCORE_THREADS - 1) / SCORE_THREADS));
     h->ev_used = 0; h->sweep_launches = 1; h->sweep_evals = (int64_t)num_models * n;
     hipEvent_t e0, e1;
     if ((rc = get_events(h, &e0, &e1))) return rc;
     HIPCHK(hipEventRecord(e0, s));
     MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), tile_bytes, s, rp, h->st.as<PairState>(), h->pts.as<double>(), md,
-                        h->tags.as<uint32_t>(), h->model_count.as<int32_t>(), h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan, totals);
+                        h->tags[0].as<uint32_t>(), h->model_count[0].as<int32_t>(), h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan, totals);
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipGetLastError());
     const hipMemcpyKind back = mem_space == MDRP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -1298,8 +1315,8 @@ int mdrp_count_candidates(mdrp_handle *h, int kind, const mdrp_model *models, in
     int rc;
     if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * nn)) || (rc = h->st.ensure(sizeof(PairState))) ||
         (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) ||
-        (rc = h->tags.ensure(sizeof(uint32_t) * slots)) || (rc = h->tags_v.ensure(sizeof(uint32_t) * slots)) ||
-        (rc = h->model_count.ensure(2 * sizeof(int32_t))) || (rc = h->surv_count.ensure(sizeof(int32_t))) ||
+        (rc = h->tags[0].ensure(sizeof(uint32_t) * slots)) || (rc = h->tags_v.ensure(sizeof(uint32_t) * slots)) ||
+        (rc = h->model_count[0].ensure(2 * sizeof(int32_t))) || (rc = h->surv_count.ensure(sizeof(int32_t))) ||
         (rc = h->cplan.ensure(2 * sizeof(int32_t))) || (rc = h->rfrag.ensure((size_t)((nn + 15) / 16) * 1024)) ||
         (rc = h->unit_f.ensure(sizeof(int32_t) * slots)) || (rc = h->in_x1.ensure(sizeof(double) * 2 * nn)) ||
         (rc = h->in_x2.ensure(sizeof(double) * 2 * nn)))
@@ -1307,29 +1324,20 @@ int mdrp_count_candidates(mdrp_handle *h, int kind, const mdrp_model *models, in
     HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
-    std::vector<uint32_t> tags(num_models);
-    for (int i = 0; i < num_models; ++i) tags[i] = (uint32_t)i;
-    HIPCHK(hipMemcpyAsync(h->tags.p, tags.data(), sizeof(uint32_t) * num_models, hipMemcpyHostToDevice, s));
+    if ((rc = upload_iota(s, h->tags[0].p, num_models))) return rc;
     const int32_t counts2[2] = {num_models, 0};
-    HIPCHK(hipMemcpyAsync(h->model_count.p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->model_count[0].p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(h->surv_count.p, 0, sizeof(int32_t), s));
-    PairState ps;
-    std::memset(&ps, 0, sizeof ps);
-    ps.n = n; ps.active = 1; ps.sq_thr = sq_threshold; ps.eps = std::sqrt(sq_threshold);
-    ps.best_min_score = DBL_MAX; // no records: nothing is retired
-    HIPCHK(hipMemcpyAsync(h->st.p, &ps, sizeof ps, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, h->in_x1.as<double>(), h->in_x2.as<double>(),
-                       (const double *)nullptr, (const double *)nullptr, h->pts.as<double>(), (double *)nullptr);
-    hipLaunchKernelGGL(k_box_unit, dim3(1), dim3(256), 0, s, n, h->pts.as<double>(), h->st.as<PairState>());
+    if ((rc = stage_unit_pair(h, h->in_x1.as<double>(), h->in_x2.as<double>(), n, sq_threshold))) return rc;
     hipLaunchKernelGGL(k_frag_unit, dim3((n + 16 + 255) / 256), dim3(256), 0, s, n, h->pts.as<double>(), h->rfrag.as<uint4>());
     RunParams rp;
     std::memset(&rp, 0, sizeof rp);
     rp.kind = kind; rp.batch = 1; rp.n_max = nn; rp.slot_stride = num_models; rp.mps = 4; rp.sample_sz = 3;
-    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->st.as<PairState>(), h->model_count.as<int32_t>(), 2, CNT_WG_MODELS, h->cplan.as<int32_t>(),
+    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->st.as<PairState>(), h->model_count[0].as<int32_t>(), 2, CNT_WG_MODELS, h->cplan.as<int32_t>(),
                        (int32_t *)nullptr);
     const dim3 grid((unsigned)((num_models + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
     MDRP_SWEEP_DISPATCH(k_count, kind, grid, dim3(CNT_THREADS), 0, s, rp, h->st.as<PairState>(), h->rfrag.as<uint4>(), h->models.as<Model>(),
-                        h->tags.as<uint32_t>(), h->model_count.as<int32_t>(), h->cplan.as<int32_t>(),
+                        h->tags[0].as<uint32_t>(), h->model_count[0].as<int32_t>(), h->cplan.as<int32_t>(),
                         h->tags_v.as<uint32_t>(), h->surv_count.as<int32_t>(), (unsigned long long *)nullptr, h->unit_f.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(candidates, h->unit_f.p, sizeof(int32_t) * num_models, hipMemcpyDeviceToHost, s));
@@ -1348,7 +1356,7 @@ int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
     int rc;
     if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * nn)) || (rc = h->st.ensure(sizeof(PairState))) ||
         (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) ||
-        (rc = h->tags.ensure(sizeof(uint32_t) * slots)) || (rc = h->tags_v.ensure(sizeof(uint32_t) * slots)) ||
+        (rc = h->tags[0].ensure(sizeof(uint32_t) * slots)) || (rc = h->tags_v.ensure(sizeof(uint32_t) * slots)) ||
         (rc = h->surv_count.ensure(sizeof(int32_t))) || (rc = h->surv2_count.ensure(sizeof(int32_t))) ||
         (rc = h->cplan.ensure(2 * sizeof(int32_t))) || (rc = h->unit_a.ensure(sizeof(double) * slots)) ||
         (rc = h->unit_f.ensure(sizeof(int32_t) * slots)) || (rc = h->in_x1.ensure(sizeof(double) * 2 * nn)) ||
@@ -1357,20 +1365,11 @@ int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
     HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
-    std::vector<uint32_t> tags(num_models);
-    for (int i = 0; i < num_models; ++i) tags[i] = (uint32_t)i;
-    HIPCHK(hipMemcpyAsync(h->tags_v.p, tags.data(), sizeof(uint32_t) * num_models, hipMemcpyHostToDevice, s));
+    if ((rc = upload_iota(s, h->tags_v.p, num_models))) return rc;
     HIPCHK(hipMemcpyAsync(h->surv_count.p, &num_models, sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(h->unit_a.p, 0, sizeof(double) * slots, s));
     HIPCHK(hipMemsetAsync(h->unit_f.p, 0, sizeof(int32_t) * slots, s));
-    PairState ps;
-    std::memset(&ps, 0, sizeof ps);
-    ps.n = n; ps.active = 1; ps.sq_thr = sq_threshold; ps.eps = std::sqrt(sq_threshold);
-    ps.best_min_score = DBL_MAX; // no records: nothing is retired, every model sees every correspondence
-    HIPCHK(hipMemcpyAsync(h->st.p, &ps, sizeof ps, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, h->in_x1.as<double>(), h->in_x2.as<double>(),
-                       (const double *)nullptr, (const double *)nullptr, h->pts.as<double>(), (double *)nullptr);
-    hipLaunchKernelGGL(k_box_unit, dim3(1), dim3(256), 0, s, n, h->pts.as<double>(), h->st.as<PairState>());
+    if ((rc = stage_unit_pair(h, h->in_x1.as<double>(), h->in_x2.as<double>(), n, sq_threshold))) return rc;
     RunParams rp;
     std::memset(&rp, 0, sizeof rp);
     rp.kind = kind; rp.batch = 1; rp.n_max = nn; rp.slot_stride = num_models; rp.mps = 4; rp.sample_sz = 3;
@@ -1379,7 +1378,7 @@ int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
     const dim3 grid((unsigned)((num_models + BND_THREADS - 1) / BND_THREADS));
     MDRP_SWEEP_DISPATCH(k_bound, kind, grid, dim3(BND_THREADS), 0, s, rp, h->st.as<PairState>(), h->pts.as<double>(), h->models.as<Model>(),
                         h->tags_v.as<uint32_t>(), h->surv_count.as<int32_t>(), h->cplan.as<int32_t>(),
-                        h->tags.as<uint32_t>(), h->surv2_count.as<int32_t>(), (unsigned long long *)nullptr, h->unit_a.as<double>(), h->unit_f.as<int32_t>());
+                        h->tags[0].as<uint32_t>(), h->surv2_count.as<int32_t>(), (unsigned long long *)nullptr, h->unit_a.as<double>(), h->unit_f.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(score_lb, h->unit_a.p, sizeof(double) * num_models, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(count_ub, h->unit_f.p, sizeof(int32_t) * num_models, hipMemcpyDeviceToHost, s));
@@ -1406,12 +1405,8 @@ int mdrp_refine_models(mdrp_handle *h, int kind, mdrp_model *models, int count, 
         HIPCHK(hipMemcpyAsync(h->unit_e.p, models, sizeof(Model) * count, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, h->in_x1.as<double>(), h->in_x2.as<double>(),
                            (const double *)nullptr, (const double *)nullptr, h->pts.as<double>(), (double *)nullptr);
-        LmOpt o;
-        o.max_it = (int)std::min<uint64_t>(opt->max_iterations, 1u << 30); o.loss = opt->loss_type; o.loss_scale = opt->loss_scale;
-        o.grad_tol = opt->gradient_tol; o.step_tol = opt->step_tol; o.lambda0 = opt->initial_lambda;
-        o.lambda_min = opt->min_lambda; o.lambda_max = opt->max_lambda;
         MDRP_CLASSIC_LM_DISPATCH(kc_refine_unit, (count >= 2048 ? 64 : 256), kind, dim3(count), 0, s, count, h->unit_e.as<Model>(),
-                                 h->pts.as<double>(), n, o, h->unit_a.as<double>());
+                                 h->pts.as<double>(), n, lm_opt(opt), h->unit_a.as<double>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(models, h->unit_e.p, sizeof(Model) * count, hipMemcpyDeviceToHost, s));
         if (final_cost) HIPCHK(hipMemcpyAsync(final_cost, h->unit_a.p, sizeof(double) * count, hipMemcpyDeviceToHost, s));
@@ -1430,12 +1425,8 @@ int mdrp_refine_models(mdrp_handle *h, int kind, mdrp_model *models, int count, 
     HIPCHK(hipMemcpyAsync(h->unit_e.p, models, sizeof(Model) * count, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, h->in_x1.as<double>(), h->in_x2.as<double>(),
                        h->in_d1.as<double>(), h->in_d2.as<double>(), h->pts.as<double>(), h->dep.as<double>());
-    LmOpt o;
-    o.max_it = (int)std::min<uint64_t>(opt->max_iterations, 1u << 30); o.loss = opt->loss_type; o.loss_scale = opt->loss_scale;
-    o.grad_tol = opt->gradient_tol; o.step_tol = opt->step_tol; o.lambda0 = opt->initial_lambda;
-    o.lambda_min = opt->min_lambda; o.lambda_max = opt->max_lambda;
     MDRP_LM_DISPATCH(k_refine_unit, (count >= 2048 ? 64 : 256), kind, (kind == MDRP_CALIB && estimate_shift), dim3(count), lm_list_bytes(n), s,
-                     count, h->unit_e.as<Model>(), h->pts.as<double>(), h->dep.as<double>(), n, scale_reproj, weight_sampson, o,
+                     count, h->unit_e.as<Model>(), h->pts.as<double>(), h->dep.as<double>(), n, scale_reproj, weight_sampson, lm_opt(opt),
                      h->unit_a.as<double>(), lm_list_stride(n));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(models, h->unit_e.p, sizeof(Model) * count, hipMemcpyDeviceToHost, s));
