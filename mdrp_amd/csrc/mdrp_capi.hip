@@ -488,6 +488,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     // Run-time knobs (DESIGN.md 10 lists all of them): the stream pipeline, the fp32 bound stage, lanes per LM problem.
     const bool lo_overlap = env_int("MDRP_LO_OVERLAP", 1) != 0; // three-stream pipeline; 0 = every kernel on the handle's stream
     const bool use_bound = env_int("MDRP_BOUND", 1) != 0;       // fp32 lower-bound stage between k_count and the fp64 sweep
+    const bool score_split = env_int("MDRP_SCORE_SPLIT", 1) != 0; // exact sweeps after a run's first chunk: k_score_split; 0 = k_score
     // lanes per LO problem: one wavefront when there are many short problems; four when the batch is small or the pairs are large (N = 5000:
     // a one-wavefront problem is 4 ms long and the launch ends with its stragglers — 45.6 against 43.9 ms per 1024 varying-focal pairs)
     // (chosen from the CALL's batch, not this pass's: the lane count fixes the LM's summation tree, and how a call is cut into passes depends on the
@@ -712,9 +713,20 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                 const dim3 grid((unsigned)std::min<long long>(ub, (long long)h->num_cu * 32));
                 MDRP_SWEEP_DISPATCH(k_score_w, kind, grid, dim3(SCW_THREADS), 0, s, r, st_p, pts_p, models_p, tags_sc, mcount_c,
                                     h->slot_score.as<double>() + so, h->slot_inl.as<int32_t>() + so, plan);
+            } else if (score_split && !(it0 == 0 && c == 0)) {
+                // the survivors of k_bound (~93 per pair): 64 hypotheses per workgroup, each wavefront a quarter of the records (k_score_split).  A run's
+                // first chunk keeps k_score: its sweep runs beside the second chunk's solver, where more and smaller sweep workgroups only wait longer
+                hipLaunchKernelGGL(k_sort_tags, dim3(pc), dim3(256), 0, s, r, st_p, mcount_c, surv_cnt, surv_tags, tags_sc);
+                hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, mcount_c, plan, totals, SPLIT_HYP);
+                HIPCHK(hipEventRecord(e0, s));
+                // items: at most ceil(sparse / 64) + ceil(dense / 64) per pair; surplus workgroups exit at once, a shortfall is taken by the item loop
+                const long long ub = (long long)pc * ((len * mps + SPLIT_HYP - 1) / SPLIT_HYP + 1);
+                const dim3 grid((unsigned)std::min<long long>(ub, (long long)h->num_cu * 32));
+                MDRP_SWEEP_DISPATCH(k_score_split, kind, grid, dim3(SPLIT_THREADS), 0, s, r, st_p, pts_p, models_p, tags_sc, mcount_c,
+                                    h->slot_score.as<double>() + so, h->slot_inl.as<int32_t>() + so, plan, totals);
             } else {
                 hipLaunchKernelGGL(k_sort_tags, dim3(pc), dim3(256), 0, s, r, st_p, mcount_c, surv_cnt, surv_tags, tags_sc);
-                hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, mcount_c, plan, totals);
+                hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, mcount_c, plan, totals, SCORE_THREADS);
                 HIPCHK(hipEventRecord(e0, s));
                 const dim3 grid((unsigned)pc * (unsigned)((len * mps + SCORE_THREADS - 1) / SCORE_THREADS));
                 MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), tile_bytes, s, r, st_p, pts_p, models_p, tags_sc, mcount_c,
@@ -1288,7 +1300,7 @@ int mdrp_score_models(mdrp_handle *h, int kind, int mem_space, const mdrp_model 
     const size_t tile_bytes = SCORE_TILE_BYTES;
     if ((rc = h->plan.ensure(sizeof(int32_t) * 8))) return rc;
     int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 4;
-    hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->model_count[0].as<int32_t>(), plan, totals);
+    hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->model_count[0].as<int32_t>(), plan, totals, SCORE_THREADS);
     const dim3 grid((unsigned)std::min(h->num_cu * 4, (num_models + SCORE_THREADS - 1) / SCORE_THREADS));
     h->ev_used = 0; h->sweep_launches = 1; h->sweep_evals = (int64_t)num_models * n;
     hipEvent_t e0, e1;

@@ -13,6 +13,7 @@
 //   k_plan     one wavefront                 work items of the sweep (workgroups per pair and class)
 //   k_score    one lane per hypothesis       Sampson/MSAC (+cheirality) sweep over all N correspondences,
 //                                            correspondences staged through LDS, broadcast reads            (a-7)  HOT
+//              (k_score_split: the same sums, 64 hypotheses per workgroup, each wavefront a quarter of the records: chunks after the first)
 //   k_scan     one wavefront per pair        ordered prefix scan of (count,score) records -> LO triggers     (a-2)
 //   k_lo_plan  one wavefront                 this chunk's trigger range per pair, frozen (later scans only append)
 //   k_lo       one wavefront (or workgroup)  LM refinement (<=25 it, TRUNCATED) + rescoring, per trigger     (a-8)
@@ -575,34 +576,42 @@ __global__ __launch_bounds__(solve_threads(SOLVER), MDRP_SOLVE_MINWAVES) void k_
 //   * bail-out against the records of earlier chunks (struct Prune): exact, skips ~30 % of the sparse work at 50 % outliers
 //     and nearly all of it on clean data.
 //   * v_fma_f64 with a loop-invariant addend goes through inline asm (fma3): hipcc picks v_fmac_f64 + v_mov_b64 otherwise.
-// exact inlier test + accumulation for one record (compute_sampson_msac_score @0x4f61d0 body, check_cheirality @0x1dce00)
+// exact inlier test of one record (compute_sampson_msac_score @0x4f61d0 body, check_cheirality @0x1dce00): true and the record's r^2
+// for an inlier.  score_point (k_score's phase 2, k_score_w, block_score) and k_score_split go through it; score_tile_dense spells out
+// the same expressions.
 template <bool POSE>
-__device__ __forceinline__ void score_point(const double *__restrict__ rec, const double E[9], const double R[9], const double t[3],
-                                            double thr, double &score, int &cnt) {
+__device__ __forceinline__ bool record_inlier(const double *__restrict__ rec, const double E[9], const double R[9], const double t[3],
+                                              double thr, double &r2) {
     const double2 *P = reinterpret_cast<const double2 *>(rec);
     const double2 p01 = P[0], p23 = P[1];
     const double a = p01.x, b = p01.y, c = p23.x, d = p23.y;
     const SampsonTerms s = sampson_terms(E, a, b, c, d);
-    if (!(s.C2 < thr * (1.0 + 1e-12) * s.den)) return; // not even a candidate (phase 1 may hand over a superset)
-    const double r2 = s.C2 / s.den;
-    if (r2 < thr) {
-        bool ok = true;
-        if (POSE) { // unit bearings via the precomputed inverse norms, min depth 0.01
-            const double2 p45 = P[2];
-            const double u0 = fma(R[0], a, fma(R[1], b, R[2]));
-            const double u1 = fma(R[3], a, fma(R[4], b, R[5]));
-            const double u2 = fma(R[6], a, fma(R[7], b, R[8]));
-            const double uh = fma(u0, c, fma(u1, d, u2));
-            const double ut = fma(u0, t[0], fma(u1, t[1], u2 * t[2]));
-            const double ht = fma(c, t[0], fma(d, t[1], t[2]));
-            const double A = -uh * p45.x * p45.y;
-            const double b1 = -ut * p45.x, b2 = ht * p45.y;
-            const double l1 = fma(-A, b2, b1), l2 = fma(-A, b1, b2);
-            const double md = 0.01 * fma(-A, A, 1.0);
-            ok = (l1 > md) && (l2 > md);
-        }
-        if (ok) { score += r2; ++cnt; }
+    if (!(s.C2 < thr * (1.0 + 1e-12) * s.den)) return false; // not even a candidate (phase 1 may hand over a superset)
+    r2 = s.C2 / s.den;
+    if (!(r2 < thr)) return false;
+    if (POSE) { // unit bearings via the precomputed inverse norms, min depth 0.01
+        const double2 p45 = P[2];
+        const double u0 = fma(R[0], a, fma(R[1], b, R[2]));
+        const double u1 = fma(R[3], a, fma(R[4], b, R[5]));
+        const double u2 = fma(R[6], a, fma(R[7], b, R[8]));
+        const double uh = fma(u0, c, fma(u1, d, u2));
+        const double ut = fma(u0, t[0], fma(u1, t[1], u2 * t[2]));
+        const double ht = fma(c, t[0], fma(d, t[1], t[2]));
+        const double A = -uh * p45.x * p45.y;
+        const double b1 = -ut * p45.x, b2 = ht * p45.y;
+        const double l1 = fma(-A, b2, b1), l2 = fma(-A, b1, b2);
+        const double md = 0.01 * fma(-A, A, 1.0);
+        return (l1 > md) && (l2 > md);
     }
+    return true;
+}
+
+// exact inlier test + accumulation for one record
+template <bool POSE>
+__device__ __forceinline__ void score_point(const double *__restrict__ rec, const double E[9], const double R[9], const double t[3],
+                                            double thr, double &score, int &cnt) {
+    double r2;
+    if (record_inlier<POSE>(rec, E, R, t, thr, r2)) { score += r2; ++cnt; }
 }
 
 // `recs` may be an LDS tile (broadcast ds_reads) or the pair's records in global memory (wave-uniform addresses ->
@@ -1418,10 +1427,10 @@ MDRP_GLOBAL __launch_bounds__(256) void k_sort_tags(RunParams rp, const PairStat
     if (tid == 0) { model_count[2 * pair] = cnt - s_dense; model_count[2 * pair + 1] = s_dense; }
 }
 
-// Work plan of one sweep launch: the workgroups a pair needs (ceil(count / SCORE_THREADS) per density class).
-// One wavefront, 64 pairs per step.  plan[0..B] = prefix sum of blocks per pair, plan[B+1 .. 2B] = sparse blocks of the pair.
+// Work plan of one sweep launch: the workgroups a pair needs (ceil(count / per_wg) per density class; per_wg: SCORE_THREADS hypotheses per
+// k_score workgroup, SPLIT_HYP per k_score_split workgroup).  plan[0..B] = prefix sum of blocks per pair, plan[B+1 .. 2B] = sparse blocks of the pair.
 MDRP_GLOBAL __launch_bounds__(PLAN_THREADS) void k_plan(int batch, const int32_t *__restrict__ model_count, int32_t *__restrict__ plan,
-                                                       int32_t *__restrict__ totals /*[0] dense, [1] dense + sparse, [2] queue head*/) {
+                                                       int32_t *__restrict__ totals /*[0] dense, [1] dense + sparse, [2] queue head*/, int per_wg) {
     __shared__ int s_w[PLAN_THREADS / 64 + 1];
     int run_d = 0, run_s = 0;
     int32_t *pd = plan, *psp = plan + batch + 1;
@@ -1429,8 +1438,8 @@ MDRP_GLOBAL __launch_bounds__(PLAN_THREADS) void k_plan(int batch, const int32_t
         const int p = p0 + threadIdx.x;
         int bd = 0, bs = 0;
         if (p < batch) {
-            bs = (model_count[2 * p] + SCORE_THREADS - 1) / SCORE_THREADS;
-            bd = (model_count[2 * p + 1] + SCORE_THREADS - 1) / SCORE_THREADS;
+            bs = (model_count[2 * p] + per_wg - 1) / per_wg;
+            bd = (model_count[2 * p + 1] + per_wg - 1) / per_wg;
         }
         int tot_d, tot_s;
         const int ed = plan_block_scan(bd, tot_d, s_w), es = plan_block_scan(bs, tot_s, s_w);
@@ -1611,6 +1620,184 @@ __global__ __launch_bounds__(SCW_THREADS) void k_score_w(RunParams rp, const Pai
             slot_inl[slot_base + slot] = pruned ? -2 : cnt;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ score, a pair's records split over the workgroup
+// The exact sweep of every chunk after a run's first, in calls of more than SCORE_WAVE_MAX_PAIRS pairs (round 7).  There ~93 hypotheses per pair
+// survive k_bound, and k_score gives each a LANE that walks all N records in a serial loop: ~1 500 wavefronts on 1 024 SIMDs, and the launch lasts
+// as long as the slowest walk (headline: 0.70 ms at 0.39 VALU-active).  Here a workgroup owns up to 64 hypotheses of one density class of one pair
+// (lane l of every wavefront = hypothesis l, in k_sort_tags' order) and takes the records SPLIT_STEP at a time: wavefront q evaluates records
+// [SPLIT_Q q, SPLIT_Q (q + 1)) of every step for all 64 hypotheses with k_score's arithmetic (record_inlier; the sparse class behind the same
+// packed-fp32 phase 1) and leaves, per record and hypothesis, r^2 of an inlier or +0 in an LDS slot, plus its inlier counts.  Wavefront 0 owns
+// the sums: one step behind the evaluation (the slots are double-buffered), each of its lanes adds the step's SPLIT_STEP slots in record order,
+// one after the other.  A score is a sum of non-negative terms from +0, and adding +0 to it changes no bit, so every sum is k_score's serial sum
+// of the inliers' r^2 — no partial sums.  The owner applies k_score's bail-out (Prune) where k_score's dense path does (every 128 records and at
+// the end; the test is monotone in the records consumed, so any set of positions that includes the end decides alike), publishes the dead lanes
+// through LDS, the other wavefronts skip them, and the workgroup stops once all are out.  Slots are written as k_score writes them.
+// The records of a step come through LDS as in k_score (each wavefront stages its own SPLIT_Q, with their fp32 copy, one step ahead).
+constexpr int SPLIT_THREADS = 256;
+constexpr int SPLIT_WAVES = SPLIT_THREADS / 64;
+constexpr int SPLIT_HYP = 64;                        // hypotheses per workgroup
+constexpr int SPLIT_Q = 8;                           // records per wavefront and step
+constexpr int SPLIT_STEP = SPLIT_WAVES * SPLIT_Q;    // records per step
+static_assert(128 % SPLIT_STEP == 0, "the bail-out positions (every 128 records) must be step boundaries");
+template <bool POSE, bool RAWF = false>
+__global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_split(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ pts,
+                                                               const Model *__restrict__ models, const uint32_t *__restrict__ tags /*sorted: k_sort_tags*/,
+                                                               const int32_t *__restrict__ model_count, double *__restrict__ slot_score,
+                                                               int32_t *__restrict__ slot_inl, const int32_t *__restrict__ plan /*k_plan, SPLIT_HYP per workgroup*/,
+                                                               const int32_t *__restrict__ totals) {
+    __shared__ double s_rec[2][SPLIT_WAVES][SPLIT_Q * PT_STRIDE]; // each wavefront's records of a step
+    __shared__ float4 s_rec32[2][SPLIT_WAVES][SPLIT_Q];           // their fp32 coordinates (store_rec32 layout)
+    __shared__ double s_r2[2][SPLIT_STEP][SPLIT_HYP];             // [record of the step][hypothesis]: r^2 of an inlier, else +0
+    __shared__ int32_t s_cnt[2][SPLIT_WAVES][SPLIT_HYP];          // inliers per wavefront's records and hypothesis
+    __shared__ unsigned long long s_dead[2];                      // the owner's dead lanes (not live included)
+    const int total = totals[1];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int w = blockIdx.x; w < total; w += gridDim.x) {
+        const int pair = plan_find(plan, rp.batch, w);
+        const int blk_sparse = plan[rp.batch + 1 + pair];
+        const int bi = w - plan[pair];
+        const bool dense = bi >= blk_sparse;
+        const int blk = dense ? bi - blk_sparse : bi;
+        const int cnt_sparse = model_count[2 * pair], cnt_dense = model_count[2 * pair + 1];
+        const PairState &ps = st[pair];
+        const int n = ps.n;
+        const double thr = ps.sq_thr;
+        const size_t slot_base = (size_t)pair * rp.slot_stride;
+        const int i = blk * SPLIT_HYP + lane;
+        const bool live = i < (dense ? cnt_dense : cnt_sparse);
+        uint32_t slot = 0;
+        if (live) slot = tags[slot_base + (dense ? rp.slot_stride - 1 - i : i)];
+        double E[9], R[9], t[3] = {0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < 9; ++q) { E[q] = 0; R[q] = 0; }
+        if (live) { // (k_score_w's setup: R is kept for the cheirality test)
+            const Model m = models[slot_base + slot];
+            if (RAWF) {
+#pragma unroll
+                for (int q = 0; q < 9; ++q) E[q] = reinterpret_cast<const double *>(&m)[q];
+            } else {
+                double Em[9];
+                quat_to_R(m.q, R);
+                essential_from_Rt(R, m.t, Em);
+                t[0] = m.t[0]; t[1] = m.t[1]; t[2] = m.t[2];
+                if (POSE) {
+#pragma unroll
+                    for (int q = 0; q < 9; ++q) E[q] = Em[q];
+                } else fundamental_from_E(Em, m.f1, m.f2, E);
+            }
+        }
+        double thr_dmax;
+        float Ef[9], tb;
+        bound_setup(E, ps, thr, Ef, tb, thr_dmax);
+        const long long rec_cnt = (long long)ps.best_min_cnt;
+        const double rec_score = ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX;
+        const double *gp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
+        const int steps = (n + SPLIT_STEP - 1) / SPLIT_STEP;
+        // lanes 0 .. 3 SPLIT_Q - 1 of a wavefront load a third of one of its records of the next step each (16 B) into registers, and store it
+        // (and the fp32 copy of its coordinates) once the step before is evaluated
+        double2 nx = {0, 0};
+        auto fetch = [&](int j) {
+            const int r = j * SPLIT_STEP + wave * SPLIT_Q + lane / 3;
+            if (lane < 3 * SPLIT_Q && r < n) nx = reinterpret_cast<const double2 *>(gp + (size_t)r * PT_STRIDE)[lane % 3];
+        };
+        auto stage = [&](int j) {
+            const int k = lane / 3, part = lane % 3;
+            if (lane < 3 * SPLIT_Q && j * SPLIT_STEP + wave * SPLIT_Q + k < n) {
+                reinterpret_cast<double2 *>(s_rec[j & 1][wave])[lane] = nx;
+                float *q = reinterpret_cast<float *>(s_rec32[j & 1][wave]) + (k >> 1) * 8 + (k & 1); // store_rec32's layout: a, b | c, d
+                if (part == 0) { q[0] = (float)nx.x; q[2] = (float)nx.y; }
+                else if (part == 1) { q[4] = (float)nx.x; q[6] = (float)nx.y; }
+            }
+        };
+        fetch(0);
+        stage(0);
+        __syncthreads(); // (also: the previous item's owner has read its last slots)
+        double score = 0;
+        int cnt = 0;
+        bool dead = !live;   // the owner's bail-out state (wavefront 0)
+        bool skip = !live;   // lanes this wavefront does not evaluate
+        for (int j = 0; j <= steps; ++j) {
+            if (j > 0) {
+                const unsigned long long dm = s_dead[(j - 1) & 1];
+                if (dm == ~0ull) break; // every hypothesis is out (all wavefronts read the same word)
+                skip = (dm >> lane) & 1;
+            }
+            if (wave == 0) {
+                if (j > 0) { // step j - 1: its slots in record order, its counts, the bail-out where k_score tests it
+                    const int b = (j - 1) & 1;
+                    if (!dead) {
+#pragma unroll 1
+                        for (int q = 0; q < SPLIT_WAVES; ++q) {
+#pragma unroll
+                            for (int r = 0; r < SPLIT_Q; ++r) score += s_r2[b][q * SPLIT_Q + r][lane];
+                            cnt += s_cnt[b][q][lane];
+                        }
+                    }
+                    const int processed = min(j * SPLIT_STEP, n);
+                    if (rec_score < DBL_MAX && ((processed & 127) == 0 || processed == n))
+                        dead = dead || (((long long)cnt + (long long)(n - processed) <= rec_cnt) &&
+                                        (score + thr * (double)(processed - cnt) >= rec_score));
+                }
+                if (j < steps) {
+                    const unsigned long long dm = __ballot(dead);
+                    if (lane == 0) s_dead[j & 1] = dm;
+                }
+                skip = dead;
+            }
+            if (j == steps) break;
+            if (j + 1 < steps) fetch(j + 1);
+            const int b = j & 1;
+            const int valid = min(SPLIT_Q, n - (j * SPLIT_STEP + wave * SPLIT_Q)); // (wave-uniform; <= 0 past the end)
+            const double *rec = s_rec[b][wave];
+            double *out = &s_r2[b][wave * SPLIT_Q][lane];
+            int found = 0;
+            if (dense) { // one pass, the per-record branch is coherent (score_tile_dense)
+#pragma unroll 2
+                for (int jj = 0; jj < SPLIT_Q; ++jj) {
+                    double v = 0.0, r2;
+                    if (jj < valid && !skip && record_inlier<POSE>(rec + jj * PT_STRIDE, E, R, t, thr, r2)) { v = r2; ++found; }
+                    out[jj * SPLIT_HYP] = v;
+                }
+            } else { // phase 1 in packed fp32 (score_tile_f32: keep unless |C32| > tb), the exact test on what it keeps
+#pragma unroll
+                for (int jj = 0; jj < SPLIT_Q; ++jj) out[jj * SPLIT_HYP] = 0.0;
+                const float4 *b32 = s_rec32[b][wave];
+                f32x2 Ev[9];
+#pragma unroll
+                for (int q = 0; q < 9; ++q) Ev[q] = (f32x2)(Ef[q]);
+                uint32_t mask = 0;
+#pragma unroll
+                for (int jj = 0; jj < SPLIT_Q; jj += 2) {
+                    const float4 ab = b32[jj], cd = b32[jj + 1];
+                    const f32x2 a = {ab.x, ab.y}, bb = {ab.z, ab.w}, c = {cd.x, cd.y}, d = {cd.z, cd.w};
+                    const f32x2 e0 = __builtin_elementwise_fma(Ev[0], a, __builtin_elementwise_fma(Ev[1], bb, Ev[2]));
+                    const f32x2 e1 = __builtin_elementwise_fma(Ev[3], a, __builtin_elementwise_fma(Ev[4], bb, Ev[5]));
+                    const f32x2 e2 = __builtin_elementwise_fma(Ev[6], a, __builtin_elementwise_fma(Ev[7], bb, Ev[8]));
+                    const f32x2 C = __builtin_elementwise_fma(c, e0, __builtin_elementwise_fma(d, e1, e2));
+                    mask |= (!(fabsf(C.x) > tb) ? 1u : 0u) << jj;
+                    mask |= (!(fabsf(C.y) > tb) ? 1u : 0u) << (jj + 1);
+                }
+                mask &= valid >= SPLIT_Q ? 0xFFu : (valid > 0 ? (1u << valid) - 1u : 0u); // records past the end hold stale LDS
+                if (skip) mask = 0;
+                while (mask) { // ascending record order
+                    const int jj = __ffs(mask) - 1;
+                    mask &= mask - 1;
+                    double r2;
+                    if (record_inlier<POSE>(rec + jj * PT_STRIDE, E, R, t, thr, r2)) { out[jj * SPLIT_HYP] = r2; ++found; }
+                }
+            }
+            s_cnt[b][wave][lane] = found;
+            if (j + 1 < steps) stage(j + 1);
+            __syncthreads();
+        }
+        if (wave == 0 && live) {
+            slot_score[slot_base + slot] = dead ? DBL_MAX : score + thr * (double)(n - cnt);
+            slot_inl[slot_base + slot] = dead ? -2 : cnt;
+        }
+    } // item loop
 }
 
 // ------------------------------------------------------------------------------------------------ scan
