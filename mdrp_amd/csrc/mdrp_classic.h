@@ -755,18 +755,9 @@ template <int CK, int T>
 __device__ void cblock_score(const Model &m, const double *__restrict__ pts, int n, double thr, double *scratch, double &score_out,
                              int &cnt_out, uint8_t *__restrict__ mask_out) {
     double R[9], E[9];
-    if (CK == CLASSIC_FUND) {
 #pragma unroll
-        for (int i = 0; i < 9; ++i) { E[i] = model_F(m)[i]; R[i] = 0.0; }
-    } else {
-        double Em[9];
-        quat_to_R(m.q, R);
-        essential_from_Rt(R, m.t, Em);
-        if (CK == CLASSIC_RELPOSE) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) E[i] = Em[i];
-        } else fundamental_from_E(Em, m.f1, m.f2, E);
-    }
+    for (int i = 0; i < 9; ++i) R[i] = 0.0; // (the fundamental matrix has no pose; its score tests no cheirality)
+    model_matrix<CK == CLASSIC_RELPOSE, CK == CLASSIC_FUND>(m, E, R);
     double score = 0;
     int cnt = 0;
     for (int i = threadIdx.x; i < n; i += T) {

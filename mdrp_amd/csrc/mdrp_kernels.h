@@ -48,7 +48,6 @@ constexpr int PT_STRIDE = 6;       // doubles per correspondence record
 constexpr int TILE_PTS = MDRP_TILE_PTS; // correspondences per LDS tile (48 B each)
 constexpr size_t SCORE_TILE_BYTES = (size_t)TILE_PTS * (PT_STRIDE * sizeof(double) + 4 * sizeof(float)); // + fp32 coordinates
 #define MDRP_P1F_UNROLL 8
-#define MDRP_P1_UNROLL 4
 constexpr int PRUNE_EVERY = 4;     // bail-out test every PRUNE_EVERY groups of 32 records (power of two)
 #define MDRP_DENSE_KEY 40 // of 64 probe records
 #define MDRP_SOLVE_MINWAVES 2
@@ -456,8 +455,42 @@ __device__ __forceinline__ SampsonTerms sampson_terms(const double E[9], double 
 }
 
 // Conservative fp32 phase-1 filter of the sweep for one hypothesis: mdrp_math.h filter_setup / filter_keeps
-__device__ __forceinline__ void bound_setup(const double E[9], const PairState &ps, double thr, float Ef[9], float &tb, double &thr_dmax) {
+__device__ __forceinline__ void bound_setup(const double E[9], const PairState &ps, double thr, float Ef[9], float &tb) {
+    double thr_dmax; // (Dmax itself: no kernel reads it)
     filter_setup(E, ps.box, thr, Ef, tb, thr_dmax);
+}
+
+// E (or F) of a model as the scoring sweeps see it, and the rotation it was built from (RAWF: R is left as it is)
+template <bool POSE, bool RAWF>
+__device__ __forceinline__ void model_matrix(const Model &m, double E[9], double R[9]) {
+    if (RAWF) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) E[q] = reinterpret_cast<const double *>(&m)[q];
+    } else {
+        double Em[9];
+        quat_to_R(m.q, R);
+        essential_from_Rt(R, m.t, Em);
+        if (POSE) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) E[q] = Em[q];
+        } else fundamental_from_E(Em, m.f1, m.f2, E);
+    }
+}
+template <bool POSE, bool RAWF>
+__device__ __forceinline__ void model_matrix(const Model &m, double E[9]) {
+    double R[9];
+    model_matrix<POSE, RAWF>(m, E, R);
+}
+
+// the pose of a model, for the cheirality test of phase 2 (nothing for the focal estimators: they do not test it)
+template <bool POSE>
+__device__ __forceinline__ void model_pose(const Model *__restrict__ mp, double R[9], double t[3]) {
+    if (POSE) {
+        double q[4];
+        q[0] = mp->q[0]; q[1] = mp->q[1]; q[2] = mp->q[2]; q[3] = mp->q[3];
+        t[0] = mp->t[0]; t[1] = mp->t[1]; t[2] = mp->t[2];
+        quat_to_R(q, R);
+    }
 }
 
 // fp32 record layout of the phase-1 filter: two records per 32 B, component-major (a0 a1 b0 b1)(c0 c1 d0 d1)
@@ -573,12 +606,19 @@ __global__ __launch_bounds__(solve_threads(SOLVER), MDRP_SOLVE_MINWAVES) void k_
 //     is the largest candidate count of any lane of the wavefront — hence the sort: similar hypotheses share a workgroup.
 //   * DENSE: candidate sets of the 64 lanes nearly coincide (the true inliers), so the plain per-record branch is coherent:
 //     one pass, no recomputation.
-//   * bail-out against the records of earlier chunks (struct Prune): exact, skips ~30 % of the sparse work at 50 % outliers
+//   * bail-out against the records of earlier chunks (struct Bar / Prune): exact, skips ~30 % of the sparse work at 50 % outliers
 //     and nearly all of it on clean data.
 //   * v_fma_f64 with a loop-invariant addend goes through inline asm (fma3): hipcc picks v_fmac_f64 + v_mov_b64 otherwise.
+// The three exact sweeps (k_score here; k_score_w and k_score_split further down) differ only in how they hand records to lanes.  What they
+// compute is written once, and a change to it is a change to one of these:
+//     model_matrix, model_pose     a model's E (or F), and its pose for the cheirality test
+//     record_inlier, score_point   the exact test of one record, and its accumulation
+//     numerator2                   phase 1: the packed-fp32 numerator of two records
+//     Bar, Prune::advance          the bar of a pair and the bail-out predicate (the one explanation is in front of struct Bar)
+//     sweep_item, write_slot       work item -> hypothesis, and the slot a hypothesis leaves behind
 // exact inlier test of one record (compute_sampson_msac_score @0x4f61d0 body, check_cheirality @0x1dce00): true and the record's r^2
-// for an inlier.  score_point (k_score's phase 2, k_score_w, block_score) and k_score_split go through it; score_tile_dense spells out
-// the same expressions.
+// for an inlier.  Every exact sweep goes through it: k_score (both classes), k_score_w and block_score by way of score_point, k_score_split
+// directly.
 template <bool POSE>
 __device__ __forceinline__ bool record_inlier(const double *__restrict__ rec, const double E[9], const double R[9], const double t[3],
                                               double thr, double &r2) {
@@ -616,7 +656,7 @@ __device__ __forceinline__ void score_point(const double *__restrict__ rec, cons
 
 // `recs` may be an LDS tile (broadcast ds_reads) or the pair's records in global memory (wave-uniform addresses ->
 // scalar loads into SGPRs, which v_fma_f64 takes directly as an operand).  The pose (R,t) is only needed by phase 2,
-// so it is rebuilt from the model's quaternion when a group has candidates instead of living in 24 VGPRs.
+// so it is rebuilt from the model's quaternion (model_pose) when a group has candidates instead of living in 24 VGPRs.
 // Bail-out against the pair's records from EARLIER chunks (exact): a hypothesis only matters if it beats a running
 // record of the minimal models (score_models<> @0x22ebc0: more inliers OR better score than any earlier minimal model).
 // Records only improve over a run, so the records at the end of the previous chunk are a valid (weaker) bar for every
@@ -625,14 +665,42 @@ __device__ __forceinline__ void score_point(const double *__restrict__ rec, cons
 //     score + thr (processed - cnt) >= rec_score   (all remaining terms are >= 0: cannot end with a better score).
 // Its slot is then written as "not a record" (count -2); k_scan treats it like an empty slot, so the trajectory is
 // identical to scoring everything.  A wavefront stops computing once all of its lanes are out.
-struct Prune {
+// Bar: the bar of a pair, as every retirement stage (k_count, k_bound, the exact sweeps) reads it from the pair's state.
+struct Bar {
     long long rec_cnt;
-    double rec_score; // already inflated by 1e-12 relative; DBL_MAX disables pruning
+    double rec_score; // already inflated by 1e-12 relative; DBL_MAX: no record yet, nothing can be retired
+    __device__ __forceinline__ explicit Bar(const PairState &ps)
+        : rec_cnt((long long)ps.best_min_cnt), rec_score(ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX) {}
+    __device__ __forceinline__ bool armed() const { return rec_score < DBL_MAX; }
+    // the bail-out predicate above, for a hypothesis with `cnt` inliers and the sum `score` after `processed` of the pair's n records
+    __device__ __forceinline__ bool out(int n, double thr, int processed, double score, int cnt) const {
+        return ((long long)cnt + (long long)(n - processed) <= rec_cnt) && (score + thr * (double)(processed - cnt) >= rec_score);
+    }
+};
+// Prune: the bail-out state of k_score's lanes
+struct Prune : Bar {
     int n;            // correspondences of the pair
     int processed;    // records consumed so far (all tiles)
     bool dead;        // this lane is out
     bool wave_dead;
+    __device__ __forceinline__ Prune(const PairState &ps, bool live) : Bar(ps), n(ps.n), processed(0), dead(!live), wave_dead(false) {}
+    // g more records are consumed: tests the bail-out; true when every lane of the wavefront is out
+    __device__ __forceinline__ bool advance(int g, double thr, double score, int cnt) {
+        processed += g;
+        if (armed()) {
+            dead = dead || out(n, thr, processed, score, cnt);
+            if (__all(dead)) { wave_dead = true; return true; }
+        }
+        return false;
+    }
 };
+
+// result of a hypothesis, as k_scan reads it: the MSAC score and the inlier count, or "not a record" for one the bail-out retired
+__device__ __forceinline__ void write_slot(double *__restrict__ slot_score, int32_t *__restrict__ slot_inl, size_t at, bool pruned,
+                                           double score, int cnt, int n, double thr) {
+    slot_score[at] = pruned ? DBL_MAX : score + thr * (double)(n - cnt);
+    slot_inl[at] = pruned ? -2 : cnt;
+}
 
 // Dense hypotheses (all 64 lanes close to the true model): their candidate sets nearly coincide (the true inliers), so
 // the plain per-record branch is coherent across the wavefront and the Sampson terms need not be recomputed in a second
@@ -640,129 +708,17 @@ struct Prune {
 template <bool POSE>
 __device__ __forceinline__ void score_tile_dense(const double *__restrict__ recs, int npts, const double E[9], const Model *__restrict__ mp,
                                                  double thr, double &score, int &cnt, Prune &pr) {
-    const double thr_hi = thr * (1.0 + 1e-12);
     double R[9], t[3] = {0, 0, 0};
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = 0;
-    if (POSE) {
-        double q[4];
-        q[0] = mp->q[0]; q[1] = mp->q[1]; q[2] = mp->q[2]; q[3] = mp->q[3];
-        t[0] = mp->t[0]; t[1] = mp->t[1]; t[2] = mp->t[2];
-        quat_to_R(q, R);
-    }
+    model_pose<POSE>(mp, R, t);
     for (int p0 = 0; p0 < npts; p0 += 32 * PRUNE_EVERY) {
         const int g = min(32 * PRUNE_EVERY, npts - p0);
         if (!pr.dead) {
 #pragma unroll 2
-            for (int j = 0; j < g; ++j) {
-                const double2 *P = reinterpret_cast<const double2 *>(recs + (size_t)(p0 + j) * PT_STRIDE);
-                const double2 p01 = P[0], p23 = P[1];
-                const double a = p01.x, b = p01.y, c = p23.x, d = p23.y;
-                const SampsonTerms s = sampson_terms(E, a, b, c, d);
-                if (s.C2 < thr_hi * s.den) {
-                    const double r2 = s.C2 / s.den;
-                    if (r2 < thr) {
-                        bool ok = true;
-                        if (POSE) {
-                            const double2 p45 = P[2];
-                            const double u0 = fma(R[0], a, fma(R[1], b, R[2]));
-                            const double u1 = fma(R[3], a, fma(R[4], b, R[5]));
-                            const double u2 = fma(R[6], a, fma(R[7], b, R[8]));
-                            const double uh = fma(u0, c, fma(u1, d, u2));
-                            const double ut = fma(u0, t[0], fma(u1, t[1], u2 * t[2]));
-                            const double ht = fma(c, t[0], fma(d, t[1], t[2]));
-                            const double A = -uh * p45.x * p45.y;
-                            const double b1 = -ut * p45.x, b2 = ht * p45.y;
-                            const double l1 = fma(-A, b2, b1), l2 = fma(-A, b1, b2);
-                            const double md = 0.01 * fma(-A, A, 1.0);
-                            ok = (l1 > md) && (l2 > md);
-                        }
-                        if (ok) { score += r2; ++cnt; }
-                    }
-                }
-            }
+            for (int j = 0; j < g; ++j) score_point<POSE>(recs + (size_t)(p0 + j) * PT_STRIDE, E, R, t, thr, score, cnt);
         }
-        pr.processed += g;
-        if (pr.rec_score < DBL_MAX) {
-            pr.dead = pr.dead || (((long long)cnt + (long long)(pr.n - pr.processed) <= pr.rec_cnt) &&
-                                  (score + thr * (double)(pr.processed - cnt) >= pr.rec_score));
-            if (__all(pr.dead)) { pr.wave_dead = true; return; }
-        }
-    }
-}
-
-// numerator C = x2' E x1 only (8 FMA); true when C^2 < thr * Dmax, i.e. the record MAY be an inlier.  12 ops instead of 22.
-// (Keeping the exact (E x1) half of the denominator and bounding only the (E' x2) half measured slower: +3 ops per
-// evaluation cost more than the fewer false candidates saved.)
-__device__ __forceinline__ bool sampson_maybe(const double E[9], double a, double b, double c, double d, double thr_hi, double dmax) {
-    const double e0 = fma(E[0], a, fma3(E[1], b, E[2]));
-    const double e1 = fma(E[3], a, fma3(E[4], b, E[5]));
-    const double e2 = fma(E[6], a, fma3(E[7], b, E[8]));
-    const double C = fma(c, e0, fma(d, e1, e2));
-    return C * C < thr_hi * dmax;
-}
-
-// BOUND (sparse hypotheses): phase 1 compares the numerator against thr * Dmax, where Dmax >= den for every record of
-// the pair (per-hypothesis bound over the pair's coordinate box).  C^2 >= thr * Dmax >= thr * den proves an outlier
-// with 12 instead of 22 ops; the few records that survive (a superset of the true candidates, ~1 %) get the exact test
-// in phase 2.  Dense hypotheses keep the exact denominator in phase 1 (the bound would send most records to phase 2).
-template <bool POSE, bool BOUND>
-__device__ __forceinline__ void score_tile(const double *__restrict__ recs, int npts, const double E[9], const Model *__restrict__ mp,
-                                           double thr, double thr_dmax, double &score, int &cnt, Prune &pr) {
-    const double thr_hi = thr * (1.0 + 1e-12);
-    for (int p0 = 0; p0 < npts; p0 += 32) {
-        const int g = min(32, npts - p0);
-        const double *base = recs + (size_t)p0 * PT_STRIDE;
-        uint32_t mask = 0;
-        if (g == 32) {
-#pragma unroll 1
-            for (int j0 = 0; j0 < 32; j0 += MDRP_P1_UNROLL) {
-#pragma unroll
-                for (int jj = 0; jj < MDRP_P1_UNROLL; ++jj) {
-                    const int j = j0 + jj;
-                    const double2 *P = reinterpret_cast<const double2 *>(base + j * PT_STRIDE);
-                    const double2 p01 = P[0], p23 = P[1];
-                    if (BOUND) {
-                        mask |= sampson_maybe(E, p01.x, p01.y, p23.x, p23.y, thr_hi, thr_dmax) ? (1u << j) : 0u;
-                    } else {
-                        const SampsonTerms s = sampson_terms(E, p01.x, p01.y, p23.x, p23.y);
-                        mask |= (s.C2 < thr_hi * s.den) ? (1u << j) : 0u;
-                    }
-                }
-            }
-        } else {
-            for (int j = 0; j < g; ++j) {
-                const double2 *P = reinterpret_cast<const double2 *>(base + j * PT_STRIDE);
-                const double2 p01 = P[0], p23 = P[1];
-                if (BOUND) {
-                    mask |= sampson_maybe(E, p01.x, p01.y, p23.x, p23.y, thr_hi, thr_dmax) ? (1u << j) : 0u;
-                } else {
-                    const SampsonTerms s = sampson_terms(E, p01.x, p01.y, p23.x, p23.y);
-                    mask |= (s.C2 < thr_hi * s.den) ? (1u << j) : 0u;
-                }
-            }
-        }
-        if (pr.dead) mask = 0;
-        if (mask) {
-            double R[9], t[3];
-            if (POSE) {
-                double q[4];
-                q[0] = mp->q[0]; q[1] = mp->q[1]; q[2] = mp->q[2]; q[3] = mp->q[3];
-                t[0] = mp->t[0]; t[1] = mp->t[1]; t[2] = mp->t[2];
-                quat_to_R(q, R);
-            }
-            while (mask) { // per-lane candidates, ascending record order (same accumulation order as the CPU loop)
-                const int j = __ffs(mask) - 1;
-                mask &= mask - 1;
-                score_point<POSE>(base + j * PT_STRIDE, E, R, t, thr, score, cnt);
-            }
-        }
-        pr.processed += g;
-        if (pr.rec_score < DBL_MAX && ((p0 >> 5) & (PRUNE_EVERY - 1)) == PRUNE_EVERY - 1) {
-            pr.dead = pr.dead || (((long long)cnt + (long long)(pr.n - pr.processed) <= pr.rec_cnt) &&
-                                  (score + thr * (double)(pr.processed - cnt) >= pr.rec_score));
-            if (__all(pr.dead)) { pr.wave_dead = true; return; }
-        }
+        if (pr.advance(g, thr, score, cnt)) return;
     }
 }
 
@@ -773,11 +729,20 @@ __device__ __forceinline__ void score_tile(const double *__restrict__ recs, int 
 //   keep the record unless |C32| > tb,  tb >= T + 2e-6 * M  (5x margin on 7u = 4.2e-7); NaN keeps; tb = inf keeps all.
 // Survivors (~1-2 % of the records) are re-tested and scored exactly in fp64 by phase 2, so results are bit-identical.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+// numerator C = x2' E x1 of two records in packed fp32 (mdrp_math.h filter_keeps, two at a time); ab, cd: the records in store_rec32's
+// layout (a0 a1 b0 b1)(c0 c1 d0 d1) -> v_pk_fma_f32 without shuffles.  e0, e1: the first two rows of E x1 (k_bound's denominator wants them too).
+__device__ __forceinline__ f32x2 numerator2(const f32x2 Ev[9], const float4 ab, const float4 cd, f32x2 &e0, f32x2 &e1) {
+    const f32x2 a = {ab.x, ab.y}, b = {ab.z, ab.w}, c = {cd.x, cd.y}, d = {cd.z, cd.w};
+    e0 = __builtin_elementwise_fma(Ev[0], a, __builtin_elementwise_fma(Ev[1], b, Ev[2]));
+    e1 = __builtin_elementwise_fma(Ev[3], a, __builtin_elementwise_fma(Ev[4], b, Ev[5]));
+    const f32x2 e2 = __builtin_elementwise_fma(Ev[6], a, __builtin_elementwise_fma(Ev[7], b, Ev[8]));
+    return __builtin_elementwise_fma(c, e0, __builtin_elementwise_fma(d, e1, e2));
+}
+
 template <bool POSE>
 __device__ __forceinline__ void score_tile_f32(const double *__restrict__ recs, const float4 *__restrict__ recs32, int npts,
                                                const double E[9], const float Ef[9], float tb, const Model *__restrict__ mp,
                                                double thr, double &score, int &cnt, Prune &pr) {
-    // recs32: two records per 32 B, component-major: (a0 a1 b0 b1)(c0 c1 d0 d1) -> v_pk_fma_f32 without shuffles.
     // Phase 1 fills the candidate mask of a 64-record window before phase 2 runs: phase 2 is a per-lane loop, the
     // wavefront pays the MAXIMUM candidate count over its lanes, and max / mean falls with the window length (windows of
     // 128 / 256 records measured equal / slower: the multi-word bit bookkeeping eats the gain).
@@ -801,12 +766,8 @@ __device__ __forceinline__ void score_tile_f32(const double *__restrict__ recs, 
 #pragma unroll
                     for (int jj = 0; jj < MDRP_P1F_UNROLL; jj += 2) {
                         const int j = j0 + jj;
-                        const float4 ab = b32[j], cd = b32[j + 1];
-                        const f32x2 a = {ab.x, ab.y}, b = {ab.z, ab.w}, c = {cd.x, cd.y}, d = {cd.z, cd.w};
-                        const f32x2 e0 = __builtin_elementwise_fma(Ev[0], a, __builtin_elementwise_fma(Ev[1], b, Ev[2]));
-                        const f32x2 e1 = __builtin_elementwise_fma(Ev[3], a, __builtin_elementwise_fma(Ev[4], b, Ev[5]));
-                        const f32x2 e2 = __builtin_elementwise_fma(Ev[6], a, __builtin_elementwise_fma(Ev[7], b, Ev[8]));
-                        const f32x2 C = __builtin_elementwise_fma(c, e0, __builtin_elementwise_fma(d, e1, e2));
+                        f32x2 e0, e1;
+                        const f32x2 C = numerator2(Ev, b32[j], b32[j + 1], e0, e1);
                         // mask = 2 * mask + keep: compare into an SGPR pair, add-with-carry shifts it in (2 instructions per
                         // record instead of compare + select + constant move + or); record j lands in bit 31 - j
                         const float cx = C.x, cy = C.y;
@@ -827,24 +788,14 @@ __device__ __forceinline__ void score_tile_f32(const double *__restrict__ recs, 
         if (pr.dead) m = 0;
         if (m) {
             double R[9], t[3];
-            if (POSE) {
-                double q[4];
-                q[0] = mp->q[0]; q[1] = mp->q[1]; q[2] = mp->q[2]; q[3] = mp->q[3];
-                t[0] = mp->t[0]; t[1] = mp->t[1]; t[2] = mp->t[2];
-                quat_to_R(q, R);
-            }
+            model_pose<POSE>(mp, R, t);
             while (m) { // per-lane candidates, ascending record order (same accumulation order as the CPU loop)
                 const int j = __ffsll((unsigned long long)m) - 1;
                 m &= m - 1;
                 score_point<POSE>(base + j * PT_STRIDE, E, R, t, thr, score, cnt);
             }
         }
-        pr.processed += g;
-        if (pr.rec_score < DBL_MAX) {
-            pr.dead = pr.dead || (((long long)cnt + (long long)(pr.n - pr.processed) <= pr.rec_cnt) &&
-                                  (score + thr * (double)(pr.processed - cnt) >= pr.rec_score));
-            if (__all(pr.dead)) { pr.wave_dead = true; return; }
-        }
+        if (pr.advance(g, thr, score, cnt)) return;
     }
 }
 
@@ -856,6 +807,25 @@ __device__ __forceinline__ int plan_find(const int32_t *__restrict__ prefix, int
         if (prefix[mid] <= w) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// Work item w of k_plan's plan, for the sweeps that give a workgroup per_wg hypotheses of one density class of one pair: the pair, the
+// class, and hypothesis idx of the workgroup — its slot, from the pair's sorted tag list (k_sort_tags: sparse hypotheses from the front,
+// dense ones from the back), or not live past the end of the class.
+struct SweepItem { int pair; bool dense, live; uint32_t slot; size_t slot_base; };
+__device__ __forceinline__ SweepItem sweep_item(const RunParams &rp, const int32_t *__restrict__ plan, const int32_t *__restrict__ model_count,
+                                                const uint32_t *__restrict__ tags, int w, int per_wg, int idx) {
+    SweepItem it;
+    it.pair = plan_find(plan, rp.batch, w);
+    const int blk_sparse = plan[rp.batch + 1 + it.pair];
+    const int bi = w - plan[it.pair];
+    it.dense = bi >= blk_sparse;
+    const int i = (it.dense ? bi - blk_sparse : bi) * per_wg + idx;
+    it.slot_base = (size_t)it.pair * rp.slot_stride;
+    const int cnt_sparse = model_count[2 * it.pair], cnt_dense = model_count[2 * it.pair + 1];
+    it.live = i < (it.dense ? cnt_dense : cnt_sparse);
+    it.slot = it.live ? tags[it.slot_base + (it.dense ? rp.slot_stride - 1 - i : i)] : 0;
+    return it;
 }
 
 // ------------------------------------------------------------------------------------------------ count (MFMA)
@@ -989,7 +959,7 @@ __global__ __launch_bounds__(CNT_THREADS, 4) void k_count(RunParams rp, const Pa
     // are issued before the arithmetic of the first (tag -> model is a dependent pair of L2 round trips)
     uint32_t slot_r[CNT_ROUNDS] = {};
     int part_r[CNT_ROUNDS] = {}; // phase B: candidates counted by phase A
-    double mq[CNT_ROUNDS][4], mt[CNT_ROUNDS][3], mf[CNT_ROUNDS][2], ms[CNT_ROUNDS][2];
+    Model mr[CNT_ROUNDS]; // (the fields model_matrix reads)
 #pragma unroll
     for (int r = 0; r < CNT_ROUNDS; ++r) {
         const int i = m0 + 64 * r + lane;
@@ -1000,10 +970,10 @@ __global__ __launch_bounds__(CNT_THREADS, 4) void k_count(RunParams rp, const Pa
         const Model *mp = models + slot_base + slot_r[r]; // slot 0 of the pair for idle lanes: a valid address
         const double2 *P = reinterpret_cast<const double2 *>(mp);
         const double2 q01 = P[0], q23 = P[1], t01 = P[2], t2s = P[3], f12 = P[5];
-        mq[r][0] = q01.x; mq[r][1] = q01.y; mq[r][2] = q23.x; mq[r][3] = q23.y;
-        mt[r][0] = t01.x; mt[r][1] = t01.y; mt[r][2] = t2s.x;
-        mf[r][0] = f12.x; mf[r][1] = f12.y;
-        ms[r][0] = t2s.y; ms[r][1] = RAWF ? P[4].x : 0.0;
+        mr[r].q[0] = q01.x; mr[r].q[1] = q01.y; mr[r].q[2] = q23.x; mr[r].q[3] = q23.y;
+        mr[r].t[0] = t01.x; mr[r].t[1] = t01.y; mr[r].t[2] = t2s.x;
+        mr[r].f1 = f12.x; mr[r].f2 = f12.y;
+        mr[r].scale = t2s.y; mr[r].shift1 = RAWF ? P[4].x : 0.0;
     }
 #pragma unroll
     for (int r = 0; r < CNT_ROUNDS; ++r) {
@@ -1014,19 +984,8 @@ __global__ __launch_bounds__(CNT_THREADS, 4) void k_count(RunParams rp, const Pa
         for (int j = 0; j < 8; ++j) { eh[j] = 0; el[j] = 0; }
         e8[0] = e8[1] = e8[2] = 0;
         if (i < cnt) {
-            double R[9], Em[9], E[9];
-            if (RAWF) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) E[q] = mq[r][q];
-                E[4] = mt[r][0]; E[5] = mt[r][1]; E[6] = mt[r][2]; E[7] = ms[r][0]; E[8] = ms[r][1];
-            } else {
-                quat_to_R(mq[r], R);
-                essential_from_Rt(R, mt[r], Em);
-                if (POSE) {
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) E[q] = Em[q];
-                } else fundamental_from_E(Em, mf[r][0], mf[r][1], E);
-            }
+            double E[9];
+            model_matrix<POSE, RAWF>(mr[r], E);
             count_setup_scaled(E, ps.box, thr, eh, el, e8, tb);
         }
         uint4 *dst = s_frag[wave][64 * r + lane];
@@ -1160,20 +1119,19 @@ __global__ __launch_bounds__(CNT_THREADS, 4) void k_count(RunParams rp, const Pa
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const long long rec_cnt = (long long)ps.best_min_cnt;
-    const double rec_score = ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX;
+    const Bar bar(ps);
 #pragma unroll
     for (int r = 0; r < CNT_ROUNDS; ++r) {
         const int i = m0 + 64 * r + lane;
         const bool live = i < cnt;
         const int cnd_here = live ? (int)s_out[64 * r + lane] + part_r[r] : 0;
         const int cnd = cnd_here + rest; // phase A of a split pair: the most the total can still become
-        if (cand_stat && phase == 1 && !split_a && rec_cnt == 0 && !(ps.best_min_score < DBL_MAX)) { // the run's first chunk (no record yet): the pair's candidate statistics
+        if (cand_stat && phase == 1 && !split_a && bar.rec_cnt == 0 && !(ps.best_min_score < DBL_MAX)) { // (the raw record, not !bar.armed(): through the inflated score this test costs the kernel two more SGPRs) // the run's first chunk (no record yet): the pair's candidate statistics
             const int tot = wave_sum_i(cnd_here), lv = __popcll(__ballot(live));
             if (lane == 0 && lv) { atomicAdd(&cand_stat[2 * pair], (unsigned long long)tot); atomicAdd(&cand_stat[2 * pair + 1], (unsigned long long)lv * (unsigned long long)n); }
         }
         if (cand_out && live) cand_out[i] = cnd;
-        const bool surv = live && ((long long)cnd > rec_cnt || thr * (double)(n - cnd) < rec_score); // else: its slot keeps k_solve's -2
+        const bool surv = live && ((long long)cnd > bar.rec_cnt || thr * (double)(n - cnd) < bar.rec_score); // else: its slot keeps k_solve's -2
         const unsigned long long ball = __ballot(surv);
         if (ball) {
             int base = 0;
@@ -1206,23 +1164,6 @@ __global__ __launch_bounds__(CNT_THREADS, 4) void k_count(RunParams rp, const Pa
 constexpr int BND_THREADS = 256;
 #define MDRP_BND_TILE 256
 constexpr int BND_TILE = MDRP_BND_TILE; // correspondences per LDS tile (16 B each, fp32); early-exit test and compaction per tile
-
-// E (or F) of a model as the scoring sweeps see it
-template <bool POSE, bool RAWF>
-__device__ __forceinline__ void model_matrix(const Model &m, double E[9]) {
-    if (RAWF) {
-#pragma unroll
-        for (int q = 0; q < 9; ++q) E[q] = reinterpret_cast<const double *>(&m)[q];
-    } else {
-        double R[9], Em[9];
-        quat_to_R(m.q, R);
-        essential_from_Rt(R, m.t, Em);
-        if (POSE) {
-#pragma unroll
-            for (int q = 0; q < 9; ++q) E[q] = Em[q];
-        } else fundamental_from_E(Em, m.f1, m.f2, E);
-    }
-}
 
 // Both proofs are monotone in the records seen so far (the terms of the score bound are >= 0; unseen records can add at most
 // their number to the inlier bound), so after every tile a model whose partial sums already prove it irrelevant leaves; the
@@ -1276,8 +1217,7 @@ __global__ __launch_bounds__(BND_THREADS, 4) void k_bound(RunParams rp, const Pa
     const float thr_cnt = (float)(thr * (1.0 + 1e-5)) * (1.0f + 1e-6f); // q may exceed r^2 by its own roundings (<= 8u)
     const float BIG = 1.2089258e24f; // 2^80
     const f32x2 nbig = {-BIG, -BIG}, kcnt = {thr_cnt * BIG, thr_cnt * BIG};
-    const long long rec_cnt = (long long)ps.best_min_cnt;
-    const double rec_score = ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX;
+    const Bar bar(ps);
     float4 *s_pair = s_rec; // two correspondences per 32 B, component-major: (a0 a1 b0 b1)(c0 c1 d0 d1)
     const double *gp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
     for (int t0 = 0; t0 < n; t0 += BND_TILE) {
@@ -1301,13 +1241,11 @@ __global__ __launch_bounds__(BND_THREADS, 4) void k_bound(RunParams rp, const Pa
 #pragma unroll 2
                 for (int j = 0; j < je; ++j) {
                     const float4 ab = s_pair[2 * (j0 + j)], cd = s_pair[2 * (j0 + j) + 1];
-                    const f32x2 a = {ab.x, ab.y}, b = {ab.z, ab.w}, c = {cd.x, cd.y}, d = {cd.z, cd.w};
-                    const f32x2 e0 = __builtin_elementwise_fma(Ev[0], a, __builtin_elementwise_fma(Ev[1], b, Ev[2]));
-                    const f32x2 e1 = __builtin_elementwise_fma(Ev[3], a, __builtin_elementwise_fma(Ev[4], b, Ev[5]));
-                    const f32x2 e2 = __builtin_elementwise_fma(Ev[6], a, __builtin_elementwise_fma(Ev[7], b, Ev[8]));
+                    const f32x2 c = {cd.x, cd.y}, d = {cd.z, cd.w};
+                    f32x2 e0, e1;
+                    const f32x2 C = numerator2(Ev, ab, cd, e0, e1);
                     const f32x2 g0 = __builtin_elementwise_fma(Ev[0], c, __builtin_elementwise_fma(Ev[3], d, Ev[6]));
                     const f32x2 g1 = __builtin_elementwise_fma(Ev[1], c, __builtin_elementwise_fma(Ev[4], d, Ev[7]));
-                    const f32x2 C = __builtin_elementwise_fma(c, e0, __builtin_elementwise_fma(d, e1, e2));
                     const f32x2 den = __builtin_elementwise_fma(e0, e0, __builtin_elementwise_fma(e1, e1, __builtin_elementwise_fma(g0, g0, __builtin_elementwise_fma(g1, g1, eDv))));
                     const f32x2 t = {fmaxf(fabsf(C.x) - eC, 0.0f), fmaxf(fabsf(C.y) - eC, 0.0f)};
                     const f32x2 rc = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)}; // v_rcp_f32: 1 ulp, inside BOUND_SLACK
@@ -1332,7 +1270,7 @@ __global__ __launch_bounds__(BND_THREADS, 4) void k_bound(RunParams rp, const Pa
         const int seen = t0 + npts;
         if (open && sane) {
             const long long cnt_ub = (long long)(cnt2.x + cnt2.y) + 1 + (long long)(n - seen); // + 1: the clamped sum may carry a fraction
-            if (cnt_ub <= rec_cnt && total_lb * (1.0 - BOUND_SLACK) >= rec_score) open = false; // its slot keeps k_solve's -2
+            if (cnt_ub <= bar.rec_cnt && total_lb * (1.0 - BOUND_SLACK) >= bar.rec_score) open = false; // its slot keeps k_solve's -2
         }
         if (seen >= n) break;
         // pack the open models into as few wavefronts as they need
@@ -1469,53 +1407,22 @@ __global__ __launch_bounds__(SCORE_THREADS, MDRP_SCORE_MINWAVES) void k_score(Ru
     const int total = totals[1];
     const int tid = threadIdx.x;
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
-    const int pair = plan_find(plan, rp.batch, w);
-    const int blk_sparse = plan[rp.batch + 1 + pair];
-    const int bi = w - plan[pair];
-    const bool dense = bi >= blk_sparse;
-    const int blk = dense ? bi - blk_sparse : bi;
-    const int cnt_sparse = model_count[2 * pair], cnt_dense = model_count[2 * pair + 1];
+    const SweepItem item = sweep_item(rp, plan, model_count, tags, w, SCORE_THREADS, tid);
+    const int pair = item.pair;
+    const bool dense = item.dense, live = item.live;
     const PairState &ps = st[pair];
     const int n = ps.n;
     const double thr = ps.sq_thr;
-    const size_t slot_base = (size_t)pair * rp.slot_stride;
-    const int cap = rp.slot_stride;
-    bool live;
-    uint32_t slot = 0;
-    { // sorted tag list of the pair: sparse hypotheses from the front, dense ones from the back (k_sort_tags)
-        const int i = blk * SCORE_THREADS + tid;
-        live = i < (dense ? cnt_dense : cnt_sparse);
-        if (live) slot = tags[slot_base + (dense ? cap - 1 - i : i)];
-    }
-    double E[9], thr_dmax;
+    double E[9];
     float tb, Ef[9];
-    const Model *mp = models + slot_base + slot;
+    const Model *mp = models + item.slot_base + item.slot;
 #pragma unroll
     for (int i = 0; i < 9; ++i) E[i] = 0;
-    if (live) {
-        const Model m = *mp;
-        double R[9], Em[9];
-        if (RAWF) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) E[i] = reinterpret_cast<const double *>(&m)[i];
-        } else {
-            quat_to_R(m.q, R);
-            essential_from_Rt(R, m.t, Em);
-            if (POSE) {
-#pragma unroll
-                for (int i = 0; i < 9; ++i) E[i] = Em[i];
-            } else {
-                fundamental_from_E(Em, m.f1, m.f2, E);
-            }
-        }
-    }
-    bound_setup(E, ps, thr, Ef, tb, thr_dmax);
+    if (live) model_matrix<POSE, RAWF>(*mp, E);
+    bound_setup(E, ps, thr, Ef, tb);
     double score = 0;
     int cnt = 0;
-    Prune pr;
-    pr.rec_cnt = (long long)ps.best_min_cnt;
-    pr.rec_score = ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX;
-    pr.n = n; pr.processed = 0; pr.dead = !live; pr.wave_dead = false;
+    Prune pr(ps, live);
     const double *gp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
     for (int t0 = 0; t0 < n; t0 += TILE_PTS) {
         const int npts = min(TILE_PTS, n - t0);
@@ -1535,21 +1442,17 @@ __global__ __launch_bounds__(SCORE_THREADS, MDRP_SCORE_MINWAVES) void k_score(Ru
             else score_tile_f32<POSE>(tile, tile32, npts, E, Ef, tb, mp, thr, score, cnt, pr);
         }
     }
-    if (live) {
-        const bool pruned = pr.dead;
-        slot_score[slot_base + slot] = pruned ? DBL_MAX : score + thr * (double)(n - cnt);
-        slot_inl[slot_base + slot] = pruned ? -2 : cnt;
-    }
+    if (live) write_slot(slot_score, slot_inl, item.slot_base + item.slot, pr.dead, score, cnt, n, thr);
     } // item loop
 }
 
 // ------------------------------------------------------------------------------------------------ score, one wavefront per hypothesis
 // Small batches (round 6).  k_score gives every hypothesis a LANE that walks the pair's records in a serial loop: ~0.3 ms for N = 2000 whatever
-// the number of hypotheses — with one image pair per call (what /root/reference/eval.py does) the two exact sweeps of a run were 0.6 of its 1.7 ms,
+// the number of hypotheses — with one image pair per call (what the reference's eval.py does) the two exact sweeps of a run were 0.6 of its 1.7 ms,
 // on a chip that was 99 % idle.  Here a WAVEFRONT owns a hypothesis and its lanes take 64 records per trip (coalesced 48-byte loads, the same
 // score_point arithmetic per record).  The MSAC score is a sum in RECORD ORDER (compute_sampson_msac_score @0x4f61d0 adds as it goes, and scores
 // are compared with `<`): the inliers' r^2 of a trip are compacted in lane order into LDS and added one after the other, so the sum — and the
-// early exit against the records of earlier chunks (struct Prune) — is k_score's bit for bit.  Twice the instructions per hypothesis, none of the
+// early exit against the records of earlier chunks (Bar::out, the predicate k_score tests) — is k_score's bit for bit.  Twice the instructions per hypothesis, none of the
 // latency: used where the hypotheses would not fill the chip anyway (mdrp_capi.hip: calls of at most SCORE_WAVE_MAX_PAIRS pairs).
 constexpr int SCORE_WAVE_MAX_PAIRS = 128;
 constexpr int SCW_THREADS = 256; // four hypotheses per workgroup
@@ -1576,20 +1479,8 @@ __global__ __launch_bounds__(SCW_THREADS) void k_score_w(RunParams rp, const Pai
         double E[9], R[9], t[3] = {m.t[0], m.t[1], m.t[2]};
 #pragma unroll
         for (int q = 0; q < 9; ++q) R[q] = 0;
-        if (RAWF) {
-#pragma unroll
-            for (int q = 0; q < 9; ++q) E[q] = reinterpret_cast<const double *>(&m)[q];
-        } else {
-            double Em[9];
-            quat_to_R(m.q, R);
-            essential_from_Rt(R, m.t, Em);
-            if (POSE) {
-#pragma unroll
-                for (int q = 0; q < 9; ++q) E[q] = Em[q];
-            } else fundamental_from_E(Em, m.f1, m.f2, E);
-        }
-        const long long rec_cnt = (long long)ps.best_min_cnt;
-        const double rec_score = ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX;
+        model_matrix<POSE, RAWF>(m, E, R);
+        const Bar bar(ps);
         const double *gp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
         double score = 0;
         int cnt = 0;
@@ -1610,15 +1501,11 @@ __global__ __launch_bounds__(SCW_THREADS) void k_score_w(RunParams rp, const Pai
                 cnt += k;
                 __builtin_amdgcn_wave_barrier(); // (the next trip overwrites the buffer)
             }
-            // k_score's bail-out (Prune), tested where its dense path tests it: after every 128 records and at the end of a 512-record tile
+            // k_score's bail-out, tested where its dense path tests it: after every 128 records and at the end of a 512-record tile
             const int processed = min(t0 + 64, n);
-            if (rec_score < DBL_MAX && ((processed & 127) == 0 || processed == n) &&
-                (long long)cnt + (long long)(n - processed) <= rec_cnt && score + thr * (double)(processed - cnt) >= rec_score) { pruned = true; break; }
+            if (bar.armed() && ((processed & 127) == 0 || processed == n) && bar.out(n, thr, processed, score, cnt)) { pruned = true; break; }
         }
-        if (lane == 0) {
-            slot_score[slot_base + slot] = pruned ? DBL_MAX : score + thr * (double)(n - cnt);
-            slot_inl[slot_base + slot] = pruned ? -2 : cnt;
-        }
+        if (lane == 0) write_slot(slot_score, slot_inl, slot_base + slot, pruned, score, cnt, n, thr);
     }
 }
 
@@ -1628,12 +1515,12 @@ __global__ __launch_bounds__(SCW_THREADS) void k_score_w(RunParams rp, const Pai
 // as long as the slowest walk (headline: 0.70 ms at 0.39 VALU-active).  Here a workgroup owns up to 64 hypotheses of one density class of one pair
 // (lane l of every wavefront = hypothesis l, in k_sort_tags' order) and takes the records SPLIT_STEP at a time: wavefront q evaluates records
 // [SPLIT_Q q, SPLIT_Q (q + 1)) of every step for all 64 hypotheses with k_score's arithmetic (record_inlier; the sparse class behind the same
-// packed-fp32 phase 1) and leaves, per record and hypothesis, r^2 of an inlier or +0 in an LDS slot, plus its inlier counts.  Wavefront 0 owns
+// packed-fp32 phase 1, numerator2) and leaves, per record and hypothesis, r^2 of an inlier or +0 in an LDS slot, plus its inlier counts.  Wavefront 0 owns
 // the sums: one step behind the evaluation (the slots are double-buffered), each of its lanes adds the step's SPLIT_STEP slots in record order,
 // one after the other.  A score is a sum of non-negative terms from +0, and adding +0 to it changes no bit, so every sum is k_score's serial sum
-// of the inliers' r^2 — no partial sums.  The owner applies k_score's bail-out (Prune) where k_score's dense path does (every 128 records and at
+// of the inliers' r^2 — no partial sums.  The owner applies k_score's bail-out (Bar::out) where k_score's dense path does (every 128 records and at
 // the end; the test is monotone in the records consumed, so any set of positions that includes the end decides alike), publishes the dead lanes
-// through LDS, the other wavefronts skip them, and the workgroup stops once all are out.  Slots are written as k_score writes them.
+// through LDS, the other wavefronts skip them, and the workgroup stops once all are out.  Work items are k_score's (sweep_item) and so are the slots it leaves (write_slot).
 // The records of a step come through LDS as in k_score (each wavefront stages its own SPLIT_Q, with their fp32 copy, one step ahead).
 constexpr int SPLIT_THREADS = 256;
 constexpr int SPLIT_WAVES = SPLIT_THREADS / 64;
@@ -1656,44 +1543,23 @@ __global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_sp
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
-        const int pair = plan_find(plan, rp.batch, w);
-        const int blk_sparse = plan[rp.batch + 1 + pair];
-        const int bi = w - plan[pair];
-        const bool dense = bi >= blk_sparse;
-        const int blk = dense ? bi - blk_sparse : bi;
-        const int cnt_sparse = model_count[2 * pair], cnt_dense = model_count[2 * pair + 1];
+        const SweepItem item = sweep_item(rp, plan, model_count, tags, w, SPLIT_HYP, lane);
+        const int pair = item.pair;
+        const bool dense = item.dense, live = item.live;
         const PairState &ps = st[pair];
         const int n = ps.n;
         const double thr = ps.sq_thr;
-        const size_t slot_base = (size_t)pair * rp.slot_stride;
-        const int i = blk * SPLIT_HYP + lane;
-        const bool live = i < (dense ? cnt_dense : cnt_sparse);
-        uint32_t slot = 0;
-        if (live) slot = tags[slot_base + (dense ? rp.slot_stride - 1 - i : i)];
         double E[9], R[9], t[3] = {0, 0, 0};
 #pragma unroll
         for (int q = 0; q < 9; ++q) { E[q] = 0; R[q] = 0; }
-        if (live) { // (k_score_w's setup: R is kept for the cheirality test)
-            const Model m = models[slot_base + slot];
-            if (RAWF) {
-#pragma unroll
-                for (int q = 0; q < 9; ++q) E[q] = reinterpret_cast<const double *>(&m)[q];
-            } else {
-                double Em[9];
-                quat_to_R(m.q, R);
-                essential_from_Rt(R, m.t, Em);
-                t[0] = m.t[0]; t[1] = m.t[1]; t[2] = m.t[2];
-                if (POSE) {
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) E[q] = Em[q];
-                } else fundamental_from_E(Em, m.f1, m.f2, E);
-            }
+        if (live) { // (R and t are kept for the cheirality test)
+            const Model m = models[item.slot_base + item.slot];
+            model_matrix<POSE, RAWF>(m, E, R);
+            if (!RAWF) { t[0] = m.t[0]; t[1] = m.t[1]; t[2] = m.t[2]; }
         }
-        double thr_dmax;
         float Ef[9], tb;
-        bound_setup(E, ps, thr, Ef, tb, thr_dmax);
-        const long long rec_cnt = (long long)ps.best_min_cnt;
-        const double rec_score = ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX;
+        bound_setup(E, ps, thr, Ef, tb);
+        const Bar bar(ps);
         const double *gp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
         const int steps = (n + SPLIT_STEP - 1) / SPLIT_STEP;
         // lanes 0 .. 3 SPLIT_Q - 1 of a wavefront load a third of one of its records of the next step each (16 B) into registers, and store it
@@ -1737,9 +1603,7 @@ __global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_sp
                         }
                     }
                     const int processed = min(j * SPLIT_STEP, n);
-                    if (rec_score < DBL_MAX && ((processed & 127) == 0 || processed == n))
-                        dead = dead || (((long long)cnt + (long long)(n - processed) <= rec_cnt) &&
-                                        (score + thr * (double)(processed - cnt) >= rec_score));
+                    if (bar.armed() && ((processed & 127) == 0 || processed == n)) dead = dead || bar.out(n, thr, processed, score, cnt);
                 }
                 if (j < steps) {
                     const unsigned long long dm = __ballot(dead);
@@ -1771,12 +1635,8 @@ __global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_sp
                 uint32_t mask = 0;
 #pragma unroll
                 for (int jj = 0; jj < SPLIT_Q; jj += 2) {
-                    const float4 ab = b32[jj], cd = b32[jj + 1];
-                    const f32x2 a = {ab.x, ab.y}, bb = {ab.z, ab.w}, c = {cd.x, cd.y}, d = {cd.z, cd.w};
-                    const f32x2 e0 = __builtin_elementwise_fma(Ev[0], a, __builtin_elementwise_fma(Ev[1], bb, Ev[2]));
-                    const f32x2 e1 = __builtin_elementwise_fma(Ev[3], a, __builtin_elementwise_fma(Ev[4], bb, Ev[5]));
-                    const f32x2 e2 = __builtin_elementwise_fma(Ev[6], a, __builtin_elementwise_fma(Ev[7], bb, Ev[8]));
-                    const f32x2 C = __builtin_elementwise_fma(c, e0, __builtin_elementwise_fma(d, e1, e2));
+                    f32x2 e0, e1;
+                    const f32x2 C = numerator2(Ev, b32[jj], b32[jj + 1], e0, e1);
                     mask |= (!(fabsf(C.x) > tb) ? 1u : 0u) << jj;
                     mask |= (!(fabsf(C.y) > tb) ? 1u : 0u) << (jj + 1);
                 }
@@ -1793,10 +1653,7 @@ __global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_sp
             if (j + 1 < steps) stage(j + 1);
             __syncthreads();
         }
-        if (wave == 0 && live) {
-            slot_score[slot_base + slot] = dead ? DBL_MAX : score + thr * (double)(n - cnt);
-            slot_inl[slot_base + slot] = dead ? -2 : cnt;
-        }
+        if (wave == 0 && live) write_slot(slot_score, slot_inl, item.slot_base + item.slot, dead, score, cnt, n, thr);
     } // item loop
 }
 
@@ -2350,13 +2207,9 @@ __device__ __forceinline__ void lm_refine(Model &m, const double *__restrict__ p
 template <int T>
 __device__ __forceinline__ void block_score(int kind, const Model &m, const double *__restrict__ pts, int n, double thr, double *scratch,
                             double &score_out, int &cnt_out, uint8_t *__restrict__ mask_out) {
-    double R[9], E[9], Em[9];
-    quat_to_R(m.q, R);
-    essential_from_Rt(R, m.t, Em);
-    if (kind == 0) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) E[i] = Em[i];
-    } else fundamental_from_E(Em, m.f1, m.f2, E);
+    double R[9], E[9];
+    if (kind == 0) model_matrix<true, false>(m, E, R);
+    else model_matrix<false, false>(m, E, R);
     double score = 0;
     int cnt = 0;
     // one record of look-ahead (all 48 bytes, unconditional loads from a clamped index): round 4 loaded a record, waited for it, and loaded

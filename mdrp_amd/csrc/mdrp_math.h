@@ -856,7 +856,7 @@ MDRP_HD double loss_weight(int type, double thr, double r2, double mu = 0.5) {
 // M = sum |E_ij| |x2_i|max |x1_j|max.  filter_keeps() drops a record only if |C32| > tb with
 // tb = (T + 2e-6 M)(1 + 1e-6) + 1e-30 (5x margin on 7u = 4.2e-7; the absolute term covers flushed denormals).
 // NaN keeps; M >= 1e30 or non-finite (fp32 overflow possible) -> tb = inf, keeps everything.
-// thr_dmax = Dmax * (1 + 1e-9) is returned for the fp64 variant of the same bound.
+// thr_dmax = Dmax * (1 + 1e-9), the denominator bound T is built from, is handed back as well (the sweeps do not read it).
 MDRP_HD void filter_setup(const double E[9], const double box[4], double thr, float Ef[9], float &tb, double &thr_dmax) {
     const double ax = box[0], ay = box[1], cx = box[2], cy = box[3];
     const double e0 = fabs(E[0]) * ax + fabs(E[1]) * ay + fabs(E[2]), e1 = fabs(E[3]) * ax + fabs(E[4]) * ay + fabs(E[5]);
