@@ -139,12 +139,13 @@ int mdrp_create_on_stream_(int device, void *stream, mdrp_handle **out, int abi_
 void mdrp_destroy(mdrp_handle *h);
 const char *mdrp_last_error(void);
 /* "mdrp-hip <ver> (gfx950) MDRP_SRC_HASH=<16 hex digits>": the hash covers mdrp_capi.hip, mdrp_kernels.h, mdrp_math.h,
- * mdrp_classic.h, mdrp_classic_math.h and this header as they were when the library was built (mdrp_amd/build.py source_hash()) */
+ * mdrp_classic.h, mdrp_classic_math.h, mdrp_frontend.h and this header as they were when the library was built (mdrp_amd/build.py source_hash()) */
 const char *mdrp_version(void);
-/* ABI 0.5: (major << 16) | minor of the structs and entry points in this header = 0x00000005.  mdrp_ransac_opt grew from 72 to 88 bytes in
- * 0.4; 0.5 makes the version check involuntary: handles are created through mdrp_create_ / mdrp_create_on_stream_, which take the host's
- * MDRP_ABI_VERSION and sizeof(mdrp_ransac_opt) (the macros above pass them) and refuse another ABI. */
-#define MDRP_ABI_VERSION 0x00000005
+/* (major << 16) | minor of the structs and entry points in this header = 0x00000006.  mdrp_ransac_opt grew from 72 to 88 bytes in
+ * 0.4; 0.5 made the version check involuntary: handles are created through mdrp_create_ / mdrp_create_on_stream_, which take the host's
+ * MDRP_ABI_VERSION and sizeof(mdrp_ransac_opt) (the macros above pass them) and refuse another ABI.  0.6 adds the device front end at the
+ * end of this header (the mdrp_matches descriptor and its two entry points); no existing struct or entry point changed. */
+#define MDRP_ABI_VERSION 0x00000006
 int mdrp_abi_version(void);
 /* HIP_VERSION (major * 10^7 + minor * 10^5 + patch) of the toolchain the library was compiled with.  The library carries no HIP
  * runtime of its own (it binds to the host process's libamdhip64 when it is loaded): a host compares this with
@@ -270,6 +271,51 @@ int mdrp_last_stats_sized(mdrp_handle *h, mdrp_stats *out, size_t out_size);
  * With the fused tail, lo_ms and final_ms are overlapping intervals on two streams and final_ms includes the final refinements' wait
  * for their pairs: read them as one phase (lo_ms + final_ms is an upper bound of it), not as two kernel durations. */
 int mdrp_last_stats(mdrp_handle *h, mdrp_stats *out);
+
+/* ---- ABI 0.6: the device front end — estimate straight from a matcher's output and two depth maps ----
+ * What every caller of the reference does on the host before the estimator (make_pair.py:96-106, make_video.py:265-275): gather the matched
+ * keypoints, read each keypoint's depth at the truncated pixel, drop the correspondences whose depths are both infinite.  Here the same
+ * happens on the device, so extractor, matcher and depth network outputs never leave it.  For pair b and match row m = (i, j), in row order:
+ *   1. the row is padding and dropped when i < 0 or j < 0 (LightGlue's -1; no counts go in), dropped as well when i >= k1 or j >= k2;
+ *   2. p1 = kp1[b][i], p2 = kp2[b][j]; the row is dropped unless x > -1 && x < w && y > -1 && y < h in its image (tested on the floating
+ *      value: -0.5 is pixel 0, w - 0.001 is pixel w - 1; -1, w, NaN and +-inf are dropped); the pixel is the coordinate truncated toward zero;
+ *   3. d1 = depth1[b][yi1][xi1], d2 = depth2[b][yi2][xi2], widened to double;
+ *   4. filter MDRP_FILTER_BOTH_INF drops the row iff both depths are infinite (the scripts' rule: a NaN or a one-sided infinity is kept);
+ *      MDRP_FILTER_FINITE keeps it only when both depths are finite;
+ *   5. kept rows go, IN MATCH ORDER, to slots s = 0, 1, ...: x1[b][s] = (double)p1 - center1[b] (centres optional, subtracted in double: the
+ *      focal estimators take principal-point-centred pixels), x2 likewise, d1[b][s], d2[b][s]; slot[b][m] = s, -1 for a dropped row; n[b]
+ *      is the number of kept rows; slots >= n[b] are filled with x = 0, d = 1.
+ * Every pointer of the descriptor is DEVICE memory. */
+enum { MDRP_F32 = 0, MDRP_F64 = 1 };                        /* kp_type, depth_type */
+enum { MDRP_FILTER_BOTH_INF = 0, MDRP_FILTER_FINITE = 1 };  /* filter */
+typedef struct {
+    const void *kp1, *kp2;         /* [B][k1][2], [B][k2][2] keypoints (x, y) in pixels of their depth map */
+    int32_t kp_type;               /* MDRP_F32 | MDRP_F64 */
+    int32_t k1, k2;                /* keypoints per image */
+    const int32_t *matches;        /* [B][m_max][2] index pairs (i into kp1, j into kp2); a negative index marks a padding row */
+    int32_t m_max;                 /* match rows per pair */
+    const void *depth1, *depth2;   /* [B][h1][w1], [B][h2][w2] depth maps */
+    int32_t depth_type;            /* MDRP_F32 | MDRP_F64 */
+    int32_t h1, w1, h2, w2;
+    const double *center1, *center2; /* [B][2] or NULL */
+    int32_t filter;                /* MDRP_FILTER_BOTH_INF | MDRP_FILTER_FINITE */
+} mdrp_matches;
+
+/* The front end alone.  x1, x2: [B][m_max][2], d1, d2: [B][m_max], slot: [B][m_max] — DEVICE memory of the caller; n_host: [B] kept rows per
+ * pair, HOST memory.  Queued on the handle's stream; returns after the counts have arrived (one stream synchronisation).
+ * MDRP_ERR_INVALID: a NULL buffer, a negative size, an unknown type or filter. */
+int mdrp_gather_matches(mdrp_handle *h, const mdrp_matches *mm, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
+                        int32_t *n_host);
+
+/* Front end + estimator.  Gathers into buffers of the handle, copies the B counts to pinned host memory and synchronises the stream ONCE (the
+ * host scheduler sizes its sample tables and passes from the counts; the estimator itself synchronises once per super-chunk anyway), then
+ * runs exactly what mdrp_estimate_batch_async runs on (x1, x2, d1, d2, n_max = m_max, n_per_pair = the counts): same records, same option
+ * refusals.  Results are read with mdrp_fetch_results / mdrp_copy_results_device.  kind: MDRP_CALIB, MDRP_SHARED_FOCAL or MDRP_VARYING_FOCAL
+ * (the estimators that take depths; any other kind is MDRP_ERR_INVALID).  match_mask_dev: [B][m_max] bytes in DEVICE memory or NULL — 1 where
+ * the row was kept and is an inlier of the result; n_used_host: [B] in HOST memory or NULL — the counts. */
+int mdrp_estimate_matches_async(mdrp_handle *h, int kind, const mdrp_matches *mm, int batch, const mdrp_camera *cam1_host,
+                                const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                uint8_t *match_mask_dev, int32_t *n_used_host);
 
 #ifdef __cplusplus
 }

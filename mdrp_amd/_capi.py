@@ -21,7 +21,10 @@ EXPORTS = (
     "mdrp_create_", "mdrp_create_on_stream_", "mdrp_destroy", "mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version", "mdrp_synchronize", "mdrp_estimate_batch",
     "mdrp_estimate_batch_async", "mdrp_fetch_results", "mdrp_copy_results_device", "mdrp_solver_batch", "mdrp_score_models", "mdrp_count_candidates", "mdrp_bound_models", "mdrp_refine_models",
     "mdrp_last_sweep_stats", "mdrp_last_stats", "mdrp_last_stats_sized", "mdrp_classic_solver_batch",
+    "mdrp_gather_matches", "mdrp_estimate_matches_async",
 )
+F32, F64 = 0, 1  # mdrp_matches.kp_type / depth_type
+FILTERS = {"both_inf": 0, "finite": 1}  # mdrp_matches.filter (include/mdrp.h MDRP_FILTER_*)
 
 
 class Model(C.Structure):
@@ -55,6 +58,14 @@ class Stats(C.Structure):
                 ("lm_cost_evals", C.c_int64), ("lm_accum_evals", C.c_int64), ("final_cost_evals", C.c_int64), ("final_accum_evals", C.c_int64),
                 ("fuse_gate_timeouts", C.c_int64), ("fuse_wait_timeouts", C.c_int64),  # ABI 0.3 (mdrp_last_stats_sized)
                 ("first_chunk", C.c_int64)]  # ABI 0.5
+
+
+class Matches(C.Structure):
+    """mdrp_matches (ABI 0.6): a matcher's output and two depth maps, every pointer in device memory"""
+    _fields_ = [("kp1", C.c_void_p), ("kp2", C.c_void_p), ("kp_type", C.c_int32), ("k1", C.c_int32), ("k2", C.c_int32),
+                ("matches", C.c_void_p), ("m_max", C.c_int32), ("depth1", C.c_void_p), ("depth2", C.c_void_p), ("depth_type", C.c_int32),
+                ("h1", C.c_int32), ("w1", C.c_int32), ("h2", C.c_int32), ("w2", C.c_int32), ("center1", C.c_void_p), ("center2", C.c_void_p),
+                ("filter", C.c_int32)]
 
 
 class Result(C.Structure):
@@ -117,11 +128,13 @@ def load_library():
         lib.mdrp_last_stats.argtypes = [vp, C.POINTER(Stats)]
         lib.mdrp_last_stats_sized.argtypes = [vp, C.POINTER(Stats), C.c_size_t]
         lib.mdrp_classic_solver_batch.argtypes = [vp, C.c_int, dp, dp, C.c_int, vp, vp]
+        lib.mdrp_gather_matches.argtypes = [vp, C.POINTER(Matches), C.c_int, dp, dp, dp, dp, ip, ip]
+        lib.mdrp_estimate_matches_async.argtypes = [vp, C.c_int, C.POINTER(Matches), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
         _lib = lib
         return lib
 
 
-ABI_VERSION = 0x00000005  # include/mdrp.h MDRP_ABI_VERSION
+ABI_VERSION = 0x00000006  # include/mdrp.h MDRP_ABI_VERSION
 ERR_UNSUPPORTED = 4  # include/mdrp.h MDRP_ERR_UNSUPPORTED: a reference option that selects behaviour the library does not build
 
 
@@ -315,6 +328,24 @@ class Handle:
                                                               C.c_void_p(d1_ptr) if d1_ptr else None, C.c_void_p(d2_ptr) if d2_ptr else None, int(batch), int(n_max),
                                                               _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
                                                               C.c_void_p(mask_ptr) if mask_ptr else None))
+
+    # ---- device front end: a Matches descriptor of device pointers
+    def gather_matches(self, mm, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
+        """k_gather alone into the caller's device buffers; returns the kept rows per pair (numpy int32).  Synchronises the stream once."""
+        n = np.zeros(int(batch), dtype=np.int32)
+        _check(self._lib, self._lib.mdrp_gather_matches(self._h, C.byref(mm), int(batch), C.c_void_p(x1_ptr), C.c_void_p(x2_ptr), C.c_void_p(d1_ptr),
+                                                        C.c_void_p(d2_ptr), C.c_void_p(slot_ptr), _ptr(n)))
+        return n
+
+    def estimate_matches_device(self, kind, mm, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
+        """front end + estimator on the handle's stream; results stay on the device (fetch_results / copy_results_device).  Returns the kept rows
+        per pair (numpy int32)."""
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        n = np.zeros(int(batch), dtype=np.int32)
+        _check(self._lib, self._lib.mdrp_estimate_matches_async(self._h, int(kind), C.byref(mm), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                                C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
+        return n
 
     def fetch_results(self, batch):
         out = np.zeros(batch, dtype=RESULT_DTYPE)

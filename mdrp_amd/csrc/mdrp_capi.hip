@@ -4,6 +4,7 @@
 #include "../../include/mdrp.h"
 #include "mdrp_kernels.h"
 #include "mdrp_classic.h"
+#include "mdrp_frontend.h"
 // MDRP_SPLIT_TU (the default build): the k_final family and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -170,6 +171,9 @@ struct mdrp_handle {
     int fuse_retry_in = 0;            // ... for this many API calls, then try the fused tail again (a busy moment on a shared GPU is not a profiler)
     int fuse_backoff = 64;            // ... doubled after every consecutive expired wait (capped), reset by a call whose fused tail ran through
     DevBuf in_x1, in_x2, in_d1, in_d2; // staging when the caller passes host memory
+    DevBuf fe_x1, fe_x2, fe_d1, fe_d2, fe_slot, fe_n; // device front end (mdrp_estimate_matches_async): gathered correspondences | slot of every match row | kept rows per pair
+    Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
+    size_t fe_n_host_cap = 0;
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
     Pinned<Progress> progress_host;
     // sweep timing
@@ -1004,7 +1008,7 @@ extern "C" {
 const char *mdrp_last_error(void) { return g_err.c_str(); }
 // the build embeds a hash of the source files (mdrp_amd/build.py) so that a stale prebuilt library can be told from the tree
 int mdrp_abi_version(void) { return MDRP_ABI_VERSION; }
-const char *mdrp_version(void) { return "mdrp-hip 0.5 (gfx950) MDRP_SRC_HASH=" MDRP_SRC_HASH; }
+const char *mdrp_version(void) { return "mdrp-hip 0.6 (gfx950) MDRP_SRC_HASH=" MDRP_SRC_HASH; }
 
 // HIP_VERSION of the toolchain this library was compiled with (the runtime is bound at load time: mdrp_amd/_capi.py compares the two)
 int mdrp_hip_build_version(void) { return HIP_VERSION; }
@@ -1177,6 +1181,105 @@ int mdrp_estimate_batch(mdrp_handle *h, int kind, int mem_space, const double *x
         HIPCHK(hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, h->stream));
     return fetch_results_locked(h, out, batch);
 }
+
+} // extern "C"
+
+// ---- device front end (mdrp_frontend.h)
+static int check_matches(const mdrp_matches *mm, int batch) {
+    const char *why = nullptr;
+    if (!mm || batch < 0) why = "invalid argument";
+    else if ((mm->kp_type != MDRP_F32 && mm->kp_type != MDRP_F64) || (mm->depth_type != MDRP_F32 && mm->depth_type != MDRP_F64)) why = "kp_type / depth_type must be MDRP_F32 or MDRP_F64";
+    else if (mm->filter != MDRP_FILTER_BOTH_INF && mm->filter != MDRP_FILTER_FINITE) why = "unknown filter";
+    else if (mm->k1 < 0 || mm->k2 < 0 || mm->m_max < 0 || mm->h1 < 0 || mm->w1 < 0 || mm->h2 < 0 || mm->w2 < 0) why = "negative size";
+    else if (batch > 0 && mm->m_max > 0 &&
+             (!mm->matches || (mm->k1 > 0 && !mm->kp1) || (mm->k2 > 0 && !mm->kp2) || (mm->h1 > 0 && mm->w1 > 0 && !mm->depth1) ||
+              (mm->h2 > 0 && mm->w2 > 0 && !mm->depth2)))
+        why = "NULL keypoints, matches or depth map";
+    if (why) { g_err = std::string("mdrp_matches: ") + why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+// k_gather on the handle's stream (the descriptor has passed check_matches); n_dev: [batch] on the device
+static int gather_device(mdrp_handle *h, const mdrp_matches *mm, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot, int32_t *n_dev) {
+    if (batch == 0) return MDRP_OK;
+#define MDRP_GATHER(KT, DT)                                                                                                                \
+    hipLaunchKernelGGL((k_gather<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)mm->kp1, (const KT *)mm->kp2, mm->k1, mm->k2,  \
+                       mm->matches, mm->m_max, (const DT *)mm->depth1, (const DT *)mm->depth2, mm->h1, mm->w1, mm->h2, mm->w2, mm->center1,      \
+                       mm->center2, mm->filter, x1, x2, d1, d2, slot, n_dev)
+    if (mm->kp_type == MDRP_F32 && mm->depth_type == MDRP_F32) MDRP_GATHER(float, float);
+    else if (mm->kp_type == MDRP_F32) MDRP_GATHER(float, double);
+    else if (mm->depth_type == MDRP_F32) MDRP_GATHER(double, float);
+    else MDRP_GATHER(double, double);
+#undef MDRP_GATHER
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+// the counts of the last gather into the handle's pinned block: the one stream synchronisation of the front end
+static int fetch_counts(mdrp_handle *h, int batch) {
+    if (batch == 0) return MDRP_OK;
+    if ((size_t)batch > h->fe_n_host_cap) {
+        h->fe_n_host.reset();
+        h->fe_n_host_cap = 0;
+        HIPCHK(hipHostMalloc((void **)&h->fe_n_host.v, sizeof(int32_t) * ((size_t)batch + batch / 8 + 64), hipHostMallocDefault));
+        h->fe_n_host_cap = (size_t)batch + batch / 8 + 64;
+    }
+    HIPCHK(hipMemcpyAsync(h->fe_n_host, h->fe_n.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MDRP_OK;
+}
+
+extern "C" {
+
+int mdrp_gather_matches(mdrp_handle *h, const mdrp_matches *mm, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
+                        int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_matches(mm, batch)) return rc;
+    if (batch > 0 && (!n_host || (mm->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_matches: NULL output"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1)))) return rc;
+    if ((rc = gather_device(h, mm, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>()))) return rc;
+    if ((rc = fetch_counts(h, batch))) return rc;
+    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
+    return MDRP_OK;
+}
+
+int mdrp_estimate_matches_async(mdrp_handle *h, int kind, const mdrp_matches *mm, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) {
+        g_err = "mdrp_estimate_matches_async: only the monodepth estimators (kind 0..2) take depth maps";
+        return MDRP_ERR_INVALID;
+    }
+    if (int rc = check_matches(mm, batch)) return rc;
+    MDRP_ENTER(h);
+    const size_t rows = (size_t)batch * mm->m_max;
+    int rc;
+    if ((rc = h->fe_x1.ensure(sizeof(double) * 2 * rows + 16)) || (rc = h->fe_x2.ensure(sizeof(double) * 2 * rows + 16)) ||
+        (rc = h->fe_d1.ensure(sizeof(double) * rows + 16)) || (rc = h->fe_d2.ensure(sizeof(double) * rows + 16)) ||
+        (rc = h->fe_slot.ensure(sizeof(int32_t) * rows + 16)) || (rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))))
+        return rc;
+    if ((rc = gather_device(h, mm, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
+                            h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>())))
+        return rc;
+    if ((rc = fetch_counts(h, batch))) return rc;
+    // from here on: the resident estimator on the gathered buffers, with the handle's own inlier mask (by slot)
+    rc = estimate_device(h, kind, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(), batch, mm->m_max,
+                         batch > 0 ? h->fe_n_host.v : nullptr, cam1, cam2, ropt, bopt, nullptr);
+    if (rc) return rc;
+    if (match_mask_dev && rows > 0) {
+        hipLaunchKernelGGL(k_match_mask, dim3((unsigned)((rows + FE_THREADS - 1) / FE_THREADS)), dim3(FE_THREADS), 0, h->stream, h->fe_slot.as<int32_t>(),
+                           h->mask.as<uint8_t>(), mm->m_max, rows, match_mask_dev);
+        HIPCHK(hipGetLastError());
+    }
+    if (n_used_host && batch > 0) std::memcpy(n_used_host, h->fe_n_host, sizeof(int32_t) * batch);
+    return MDRP_OK;
+}
+
+} // extern "C"
+
+extern "C" {
 
 int mdrp_last_sweep_stats(mdrp_handle *h, double *sweep_ms, int64_t *launches, int64_t *evaluations) {
     if (!h) return MDRP_ERR_INVALID;

@@ -1,0 +1,88 @@
+"""The device front end's definition, in plain NumPy for one image pair.
+
+`poselib.gather_matches_torch` / `poselib.estimate_matches_torch` turn a matcher's output (two keypoint tables, index pairs) and two
+depth maps into the estimators' correspondences on the GPU (mdrp_amd/csrc/mdrp_frontend.h).  This module states what they compute; it is
+written from the definition in include/mdrp.h (ABI 0.6), it is the yardstick of the tests, and it is not used by the product path.
+
+For match row m = (i, j), in row order:
+
+1. the row is padding and dropped when i < 0 or j < 0; it is dropped as well when i >= K1 or j >= K2;
+2. p1 = keypoints1[i], p2 = keypoints2[j]; the row is dropped unless x > -1, x < W, y > -1 and y < H hold for the floating value in its
+   image (-0.5 is pixel 0, W - 0.001 is pixel W - 1; -1, W, NaN and +-inf are dropped); the pixel is the coordinate truncated toward zero;
+3. d1 = depth_map1[yi1, xi1], d2 = depth_map2[yi2, xi2], widened to float64;
+4. filter "both_inf" drops the row iff both depths are infinite (a NaN or a one-sided infinity is kept); "finite" keeps it only when
+   both depths are finite;
+5. kept rows, in match order, give x1 = float64(p1) - center1, x2 = float64(p2) - center2, d1, d2; slot[m] is the position of row m
+   among the kept rows, -1 for a dropped row.
+"""
+import numpy as np
+
+FILTERS = ("both_inf", "finite")
+
+
+def pixel_index(x, y, width, height):
+    """(in range, xi, yi) of float32 / float64 coordinates in a width x height map (rule 2); xi = yi = 0 where out of range"""
+    x = np.asarray(x).astype(np.float64)
+    y = np.asarray(y).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        inside = (x > -1.0) & (x < float(width)) & (y > -1.0) & (y < float(height))
+    xi = np.trunc(np.where(inside, x, 0.0)).astype(np.int64)
+    yi = np.trunc(np.where(inside, y, 0.0)).astype(np.int64)
+    return inside, xi, yi
+
+
+def keep_depths(d1, d2, filter="both_inf"):
+    """the depth filter (rule 4) on float64 depths"""
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {FILTERS}, not {filter!r}")
+    d1 = np.asarray(d1, dtype=np.float64)
+    d2 = np.asarray(d2, dtype=np.float64)
+    if filter == "finite":
+        return np.isfinite(d1) & np.isfinite(d2)
+    return ~(np.isinf(d1) & np.isinf(d2))
+
+
+def _table(a, what):
+    a = np.asarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        raise ValueError(f"{what} must be float32 or float64")
+    return a
+
+
+def gather_matches_numpy(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1=None, center2=None, filter="both_inf"):
+    """One pair: keypoints (K, 2) and depth maps (H, W) in float32 / float64, matches (M, 2) integers (taken as int32).
+    Returns (x1 (n, 2), x2 (n, 2), d1 (n,), d2 (n,), slot (M,) int32), the first four float64; n = len(d1)."""
+    kp1, kp2 = _table(keypoints1, "keypoints"), _table(keypoints2, "keypoints")
+    dm1, dm2 = _table(depth_map1, "depth maps"), _table(depth_map2, "depth maps")
+    if kp1.ndim != 2 or kp1.shape[1] != 2 or kp2.ndim != 2 or kp2.shape[1] != 2 or dm1.ndim != 2 or dm2.ndim != 2:
+        raise ValueError("expected keypoints (K, 2) and depth maps (H, W)")
+    m = np.asarray(matches).astype(np.int32).reshape(-1, 2).astype(np.int64)
+    i, j = m[:, 0], m[:, 1]
+    ok = (i >= 0) & (j >= 0) & (i < len(kp1)) & (j < len(kp2))                           # rule 1
+    p1 = np.zeros((len(m), 2)); p2 = np.zeros((len(m), 2))
+    p1[ok] = kp1[i[ok]].astype(np.float64); p2[ok] = kp2[j[ok]].astype(np.float64)
+    in1, xi1, yi1 = pixel_index(p1[:, 0], p1[:, 1], dm1.shape[1], dm1.shape[0])       # rule 2 (float -> double is exact: the test is the same)
+    in2, xi2, yi2 = pixel_index(p2[:, 0], p2[:, 1], dm2.shape[1], dm2.shape[0])
+    ok &= in1 & in2
+    d1 = np.zeros(len(m)); d2 = np.zeros(len(m))
+    d1[ok] = dm1[yi1[ok], xi1[ok]].astype(np.float64)                                    # rule 3
+    d2[ok] = dm2[yi2[ok], xi2[ok]].astype(np.float64)
+    ok &= keep_depths(d1, d2, filter)                                                    # rule 4
+    slot = np.where(ok, np.cumsum(ok) - 1, -1).astype(np.int32)                          # rule 5
+    c1 = np.zeros(2) if center1 is None else np.asarray(center1, dtype=np.float64).reshape(2)
+    c2 = np.zeros(2) if center2 is None else np.asarray(center2, dtype=np.float64).reshape(2)
+    return p1[ok] - c1, p2[ok] - c2, d1[ok], d2[ok], slot
+
+
+def pad_pairs(gathered, m_max):
+    """per-pair results of gather_matches_numpy -> the padded buffers the device front end writes: x1, x2 (B, m_max, 2), d1, d2 (B, m_max),
+    n (B,) int32, slot (B, m_max) int32; slots past n hold x = 0, d = 1"""
+    B = len(gathered)
+    x1 = np.zeros((B, m_max, 2)); x2 = np.zeros((B, m_max, 2)); d1 = np.ones((B, m_max)); d2 = np.ones((B, m_max))
+    n = np.zeros(B, dtype=np.int32)
+    slot = np.full((B, m_max), -1, dtype=np.int32)
+    for b, (a1, a2, e1, e2, s) in enumerate(gathered):
+        n[b] = len(e1)
+        x1[b, :n[b]] = a1; x2[b, :n[b]] = a2; d1[b, :n[b]] = e1; d2[b, :n[b]] = e2
+        slot[b, :len(s)] = s
+    return x1, x2, d1, d2, n, slot

@@ -666,3 +666,109 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
                                 mask.data_ptr())
         res = h.fetch_results(B)
     return res, mask
+
+
+# ------------------------------------------------------------------------------------------------ device front end
+# What the reference's callers do in NumPy before the estimator (make_pair.py:96-106, make_video.py:265-275) — gather the matched
+# keypoints, read their depths at the truncated pixel, drop the rows whose depths are both infinite — on the device, so that extractor,
+# matcher and depth-network outputs go in as they are.  mdrp_amd/frontend.py states the semantics in NumPy (include/mdrp.h, ABI 0.6).
+def _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter):
+    """validated mdrp_matches descriptor of torch tensors on one ROCm device -> (descriptor, tensors it points into, B, M, device)"""
+    import torch
+    if filter not in _capi.FILTERS:
+        raise ValueError(f"filter must be one of {tuple(_capi.FILTERS)}, not {filter!r}")
+    named = {"keypoints1": keypoints1, "keypoints2": keypoints2, "matches": matches, "depth_map1": depth_map1, "depth_map2": depth_map2}
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+        if t.device != keypoints1.device:
+            raise ValueError("all tensors must live on the same device")
+    dev = keypoints1.device
+    kp1, kp2 = (t.unsqueeze(0) if t.dim() == 2 else t for t in (keypoints1, keypoints2))
+    mt = matches.unsqueeze(0) if matches.dim() == 2 and kp1.shape[0] == 1 else matches
+    dm1, dm2 = (t.unsqueeze(0) if t.dim() == 2 and kp1.shape[0] == 1 else t for t in (depth_map1, depth_map2))
+    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
+    if kp1.dtype not in ftypes or kp2.dtype != kp1.dtype:
+        raise ValueError("keypoints must both be float32 or both float64")
+    if dm1.dtype not in ftypes or dm2.dtype != dm1.dtype:
+        raise ValueError("depth maps must both be float32 or both float64")
+    if mt.dtype not in (torch.int32, torch.int64):
+        raise ValueError("matches must be int32 or int64")
+    if kp1.dim() != 3 or kp1.shape[2] != 2 or kp2.dim() != 3 or kp2.shape[2] != 2:
+        raise ValueError("keypoints must have shape (B, K, 2) or (K, 2)")
+    B = kp1.shape[0]
+    if kp2.shape[0] != B or mt.dim() != 3 or mt.shape[0] != B or mt.shape[2] != 2:
+        raise ValueError("matches must have shape (B, M, 2) with the keypoints' B")
+    if dm1.dim() != 3 or dm2.dim() != 3 or dm1.shape[0] != B or dm2.shape[0] != B:
+        raise ValueError("depth maps must have shape (B, H, W) with the keypoints' B")
+    if mt.dtype == torch.int64:
+        mt = mt.to(torch.int32)  # narrowed on the device, on the current stream: no synchronisation
+    kp1, kp2, mt, dm1, dm2 = (t.contiguous() for t in (kp1, kp2, mt, dm1, dm2))
+
+    def center(c):
+        if c is None:
+            return None
+        c = torch.as_tensor(c, dtype=torch.float64).to(dev)
+        if c.numel() == 2:
+            c = c.reshape(1, 2).expand(B, 2)
+        if c.shape != (B, 2):
+            raise ValueError("centers must have shape (B, 2) or (2,)")
+        return c.contiguous()
+
+    c1, c2 = center(center1), center(center2)
+    mm = _capi.Matches(kp1.data_ptr(), kp2.data_ptr(), ftypes[kp1.dtype], kp1.shape[1], kp2.shape[1], mt.data_ptr(), mt.shape[1],
+                       dm1.data_ptr(), dm2.data_ptr(), ftypes[dm1.dtype], dm1.shape[1], dm1.shape[2], dm2.shape[1], dm2.shape[2],
+                       None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr(), _capi.FILTERS[filter])
+    return mm, (kp1, kp2, mt, dm1, dm2, c1, c2), B, int(mt.shape[1]), dev
+
+
+def gather_matches_torch(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1=None, center2=None, filter="both_inf"):
+    """The front end alone, on the device's current torch stream.  keypoints (B, K, 2) float32 | float64 (a (K, 2) tensor is B = 1), matches
+    (B, M, 2) int32 | int64 with -1 rows as padding, depth maps (B, H, W) float32 | float64 (the two images may differ in size), all on one
+    ROCm device; center1 / center2: optional (B, 2) or (2,) principal points, subtracted in float64; filter: "both_inf" (the reference
+    scripts' rule) | "finite".  Returns (x1, x2 (B, M, 2), d1, d2 (B, M): float64 device tensors, kept rows first, in match order, the
+    rest x = 0, d = 1; n_per_pair: numpy int32; slot (B, M): int32 device tensor, the position of every match row, -1 if dropped).
+    One stream synchronisation (the counts)."""
+    import torch
+    mm, keep, B, M, dev = _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        x1 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        x2 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        d1 = torch.empty((B, M), dtype=torch.float64, device=dev)
+        d2 = torch.empty((B, M), dtype=torch.float64, device=dev)
+        slot = torch.empty((B, M), dtype=torch.int32, device=dev)
+        n = h.gather_matches(mm, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
+    del keep
+    return x1, x2, d1, d2, n, slot
+
+
+def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, depth_map2, cameras1=None, cameras2=None, ransac_opt=None,
+                           bundle_opt=None, center1=None, center2=None, filter="both_inf"):
+    """estimate_batch_torch straight from a matcher's output and two depth maps (inputs as gather_matches_torch): the correspondences are
+    gathered on the device into buffers of the handle and handed to the same estimator — records identical to gathering with
+    mdrp_amd.frontend.gather_matches_numpy and calling estimate_batch_torch with its n_per_pair.  kind: "calibrated" | "shared_focal" |
+    "varying_focal" (pass center1 / center2 for the focal estimators: they take principal-point-centred pixels).  Queued on the device's
+    current torch stream; the B kept-row counts cross to the host behind one stream synchronisation, then the 136-byte result records.
+    Returns (records, match_mask: (B, M) uint8 device tensor — 1 where the row was kept and is an inlier —, n_used: numpy int32)."""
+    import torch
+    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
+    if isinstance(kind, str) and kind not in kinds:
+        raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
+    k = kinds[kind] if isinstance(kind, str) else int(kind)
+    if k not in kinds.values():
+        raise ValueError("only the monodepth estimators (calibrated, shared_focal, varying_focal) take depth maps")
+    mm, keep, B, M, dev = _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter)
+    cams1 = cams2 = None
+    if k == _capi.CALIB:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
+        n_used = h.estimate_matches_device(k, mm, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        res = h.fetch_results(B)
+    del keep
+    return res, match_mask, n_used

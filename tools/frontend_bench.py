@@ -1,0 +1,187 @@
+#!/usr/bin/env python3
+"""What the device front end costs and saves at the headline shape (B = 1024 pairs, M = 2000 match rows, 10^4 RANSAC iterations, calibrated
+estimator): float32 keypoints (B, 2048, 2), float32 depth maps (B, 480, 640) and int64 matches, resident on the GPU, seeded from synth.
+
+Three routes, warmed and alternated in one process, each timed with the host clock around a call that ends in the fetched result records:
+  (a) torch_front_end + poselib.estimate_batch_torch — the route a user has without the front end, in torch ops: gathers, masks, an ordered
+      compaction by cumulative sum + scatter, casts to float64, the count copied to the host, and the inlier mask mapped back onto the rows;
+  (b) poselib.estimate_matches_torch;
+  (c) poselib.estimate_batch_torch alone on input gathered beforehand — the floor.
+Reports the median of the repetitions and their spread, checks that (a) and (b) return the same records, and writes profiles/frontend_bench.json.
+
+    python tools/frontend_bench.py [--batch 1024] [--rows 2000] [--iters 10000] [--reps 21] [--out profiles/frontend_bench.json]
+The front end's own kernel time comes from a separate run under the profiler, folded into the same file afterwards:
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/frontend_bench.py --only b --reps 3 --out /dev/null
+    python tools/frontend_bench.py --kernel-stats <dir>/**/*_kernel_stats.csv --out profiles/frontend_bench.json
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W, K = 480, 640, 2048
+A, C = 0.38, (320.0, 240.0)  # map pixel = A * synth pixel + C: a camera with focal A * 800 and principal point C
+CAM = {"model": "SIMPLE_PINHOLE", "width": W, "height": H, "params": [A * 800.0, *C]}
+BO = {"loss_type": "TRUNCATED_CAUCHY"}
+
+
+def make_inputs(batch, rows, dev):
+    """matcher-shaped inputs on the device: keypoint tables with the correspondences scattered through a permutation, their depths painted
+    into the maps, a tail of -1 padding rows of a different length per pair (LightGlue pads ragged match lists that way)"""
+    import torch
+    from mdrp_amd import synth
+    rng = np.random.default_rng(5)
+    b = synth.make_batch(0, batch, rows, noise_px=0.5, depth_noise=0.02, outlier_frac=0.5)
+    kp1 = np.stack([rng.uniform(0, W, (batch, K)), rng.uniform(0, H, (batch, K))], 2)
+    kp2 = kp1.copy()
+    matches = np.full((batch, rows, 2), -1, dtype=np.int64)
+    pt1 = A * b["x1"] + np.array(C)
+    pt2 = A * b["x2"] + np.array(C)
+    live = rows - rng.integers(0, rows // 20 + 1, batch)  # up to 5 % padding rows
+    for k in range(batch):
+        p1, p2 = rng.permutation(K)[:rows], rng.permutation(K)[:rows]
+        kp1[k, p1] = pt1[k]; kp2[k, p2] = pt2[k]
+        matches[k, :live[k], 0] = p1[:live[k]]; matches[k, :live[k], 1] = p2[:live[k]]
+    g = torch.Generator(device=dev); g.manual_seed(5)
+    dm1 = torch.rand((batch, H, W), device=dev, generator=g) * 5 + 1
+    dm2 = torch.rand((batch, H, W), device=dev, generator=g) * 5 + 1
+    for dm, pt, d in ((dm1, pt1, b["d1"]), (dm2, pt2, b["d2"])):
+        inside = (pt[..., 0] > -1) & (pt[..., 0] < W) & (pt[..., 1] > -1) & (pt[..., 1] < H)
+        bi, mi = np.nonzero(inside)
+        dm[torch.from_numpy(bi).to(dev), torch.from_numpy(pt[bi, mi, 1].astype(np.int64)).to(dev),
+           torch.from_numpy(pt[bi, mi, 0].astype(np.int64)).to(dev)] = torch.from_numpy(d[bi, mi].astype(np.float32)).to(dev)
+    dm1[:, ::7, ::5] = float("inf")   # a depth network's invalid pixels, in both maps: some rows have both depths infinite
+    dm2[:, ::3, ::5] = float("inf")
+    return (torch.from_numpy(kp1.astype(np.float32)).to(dev), torch.from_numpy(kp2.astype(np.float32)).to(dev), torch.from_numpy(matches).to(dev), dm1, dm2)
+
+
+def torch_front_end(kp1, kp2, matches, dm1, dm2):
+    """the reference scripts' preparation (gather, depth at the truncated pixel, drop inf & inf) in batched torch ops, order preserved"""
+    import torch
+    B, M, _ = matches.shape
+    i, j = matches[..., 0], matches[..., 1]
+    valid = (i >= 0) & (j >= 0) & (i < kp1.shape[1]) & (j < kp2.shape[1])
+    p1 = torch.gather(kp1, 1, i.clamp(0, kp1.shape[1] - 1).unsqueeze(-1).expand(-1, -1, 2))
+    p2 = torch.gather(kp2, 1, j.clamp(0, kp2.shape[1] - 1).unsqueeze(-1).expand(-1, -1, 2))
+
+    def depth(p, dm):
+        h, w = dm.shape[1:]
+        x, y = p[..., 0], p[..., 1]
+        inside = (x > -1) & (x < w) & (y > -1) & (y < h)
+        flat = torch.where(inside, y.long() * w + x.long(), 0)
+        return inside, torch.gather(dm.reshape(B, -1), 1, flat)
+
+    in1, d1 = depth(p1, dm1)
+    in2, d2 = depth(p2, dm2)
+    keep = valid & in1 & in2 & ~(torch.isinf(d1) & torch.isinf(d2))
+    count = torch.cumsum(keep, dim=1)
+    n = count[:, -1].to(torch.int32)
+    slot = torch.where(keep, count - 1, M)  # dropped rows land in a spare column
+    x1 = torch.zeros((B, M + 1, 2), dtype=torch.float64, device=kp1.device); x2 = torch.zeros_like(x1)
+    e1 = torch.ones((B, M + 1), dtype=torch.float64, device=kp1.device); e2 = torch.ones_like(e1)
+    s2 = slot.unsqueeze(-1).expand(-1, -1, 2)
+    x1.scatter_(1, s2, p1.double()); x2.scatter_(1, s2, p2.double())
+    e1.scatter_(1, slot, d1.double()); e2.scatter_(1, slot, d2.double())
+    x1[:, M] = 0.0; x2[:, M] = 0.0  # (not read: n <= M)
+    return x1[:, :M].contiguous(), x2[:, :M].contiguous(), e1[:, :M].contiguous(), e2[:, :M].contiguous(), n, slot, keep
+
+
+def route_a(poselib, t, ro):
+    import torch
+    x1, x2, d1, d2, n, slot, keep = torch_front_end(*t)
+    res, mask = poselib.estimate_batch_torch("calibrated", x1, x2, d1, d2, CAM, CAM, ro, BO, n_per_pair=n.cpu().numpy())
+    match_mask = torch.where(keep, torch.gather(mask, 1, slot.clamp(max=mask.shape[1] - 1)), 0).to(torch.uint8)
+    return res, match_mask
+
+
+def route_b(poselib, t, ro):
+    res, match_mask, _ = poselib.estimate_matches_torch("calibrated", *t, CAM, CAM, ro, BO)
+    return res, match_mask
+
+
+def fold_kernel_stats(paths, out):
+    """average duration of the front end's kernels from rocprofv3's kernel statistics into the result file"""
+    rows = {}
+    for p in paths:
+        for r in csv.DictReader(open(p)):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key in ("k_gather", "k_match_mask"):
+                if key in name:
+                    rows[key] = {"name": name, "calls": int(r["Calls"]), "average_us": float(r["AverageNs"]) / 1e3, "min_us": float(r["MinNs"]) / 1e3,
+                                 "max_us": float(r["MaxNs"]) / 1e3}
+    doc = json.load(open(out)) if os.path.exists(out) else {}
+    doc["front_end_kernels"] = rows
+    json.dump(doc, open(out, "w"), indent=1)
+    print(json.dumps(rows))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--rows", type=int, default=2000)
+    ap.add_argument("--iters", type=int, default=10000)
+    ap.add_argument("--reps", type=int, default=21)
+    ap.add_argument("--only", choices=["a", "b", "c"], default=None, help="run one route alone (profiler runs)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.json"))
+    ap.add_argument("--kernel-stats", nargs="+", default=None, help="rocprofv3 *_kernel_stats.csv files (globs allowed) to fold into --out")
+    a = ap.parse_args()
+    if a.kernel_stats:
+        return fold_kernel_stats([p for g in a.kernel_stats for p in glob.glob(g, recursive=True)], a.out)
+    import torch
+    import mdrp_amd.poselib as poselib
+    from mdrp_amd import frontend
+    dev = torch.device("cuda", 0)
+    ro = {"max_iterations": a.iters, "min_iterations": a.iters, "max_epipolar_error": 2.0 * A, "max_reproj_error": 16.0 * A}
+    t = make_inputs(a.batch, a.rows, dev)
+    gx1, gx2, gd1, gd2, gn, _ = poselib.gather_matches_torch(*t)
+    routes = {"a": lambda: route_a(poselib, t, ro), "b": lambda: route_b(poselib, t, ro),
+              "c": lambda: poselib.estimate_batch_torch("calibrated", gx1, gx2, gd1, gd2, CAM, CAM, ro, BO, n_per_pair=gn)}
+    if a.only:
+        routes = {a.only: routes[a.only]}
+    else:  # the two front ends agree, and both agree with the NumPy statement on the first pairs
+        ta = torch_front_end(*t)
+        assert np.array_equal(ta[4].cpu().numpy(), gn) and torch.equal(ta[0], gx1) and torch.equal(ta[3], gd2)
+        for k in range(2):
+            ref = frontend.gather_matches_numpy(*(v[k].cpu().numpy() for v in t))
+            assert len(ref[2]) == gn[k] and gx2[k, :gn[k]].cpu().numpy().tobytes() == ref[1].tobytes()
+    times = {k: [] for k in routes}
+    last = {}
+    for rep in range(a.reps + 2):  # two warm-up rounds
+        for k, fn in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[k] = fn()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                times[k].append(time.perf_counter() - t0)
+    if not a.only:
+        assert last["a"][0].tobytes() == last["b"][0].tobytes() == last["c"][0].tobytes(), "the routes' records differ"
+        assert torch.equal(last["a"][1], last["b"][1])
+    doc = {"shape": {"batch": a.batch, "match_rows": a.rows, "keypoints": K, "depth_map": [H, W], "iterations": a.iters, "repetitions": a.reps,
+                     "kept_rows_mean": float(gn.mean()), "estimator": "calibrated"},
+           "routes": {"a": "torch-op front end + estimate_batch_torch", "b": "estimate_matches_torch", "c": "estimate_batch_torch on gathered input"}}
+    for k, v in times.items():
+        v = np.array(v)
+        doc[k] = {"pairs_per_s_median": a.batch / float(np.median(v)), "ms_median": 1e3 * float(np.median(v)), "ms_min": 1e3 * float(v.min()),
+                  "ms_max": 1e3 * float(v.max()), "spread_rel": float((v.max() - v.min()) / np.median(v))}
+    if not a.only:
+        doc["front_end_ms"] = {"a_minus_c": doc["a"]["ms_median"] - doc["c"]["ms_median"], "b_minus_c": doc["b"]["ms_median"] - doc["c"]["ms_median"]}
+    if a.out != "/dev/null":
+        old = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        if "front_end_kernels" in old:
+            doc["front_end_kernels"] = old["front_end_kernels"]
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(doc, open(a.out, "w"), indent=1)
+    print(json.dumps(doc))
+
+
+if __name__ == "__main__":
+    main()
