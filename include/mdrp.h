@@ -317,6 +317,29 @@ int mdrp_estimate_matches_async(mdrp_handle *h, int kind, const mdrp_matches *mm
                                 const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
                                 uint8_t *match_mask_dev, int32_t *n_used_host);
 
+/* ---- Iteration budgets: the result at every budget of a list in ONE run (added within ABI 0.6: new symbols only).
+ * budgets: n_budgets integers in HOST memory, each >= 1, strictly increasing, at most MDRP_MAX_BUDGETS of them, and ropt->max_iterations must
+ * equal the last one.  Record and mask c are bit for bit what a separate call with max_iterations = budgets[c] and every other option unchanged
+ * returns: the sample sequence depends on (seed, N) alone and a run's bookkeeping on earlier iterations alone, so the run with budget K is a
+ * prefix of every longer run.  A pair that the dynamic stopping rule ended before a budget reports its stopped state there.
+ * MDRP_ERR_INVALID, before any device work: an empty list, a zero budget, a list that does not increase, more than MDRP_MAX_BUDGETS, a last
+ * budget other than ropt->max_iterations.  Every other argument, error and option refusal is mdrp_estimate_batch's.
+ * out: [n_budgets][batch] records; inlier_mask: [n_budgets][batch][n_max] bytes or NULL (host or device memory as mem_space says). */
+#define MDRP_MAX_BUDGETS 16
+int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
+                                const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
+                                const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets,
+                                int n_budgets, mdrp_result *out, uint8_t *inlier_mask);
+/* Device-resident variant (as mdrp_estimate_batch_async): inlier_mask_dev is [n_budgets][batch][n_max] bytes in DEVICE memory or NULL.  The
+ * records stay on the device until mdrp_fetch_budget_results / mdrp_copy_budget_results_device ([n_budgets][batch] records; n_budgets and
+ * batch are the call's); mdrp_fetch_results / mdrp_copy_results_device return the last budget's. */
+int mdrp_estimate_batch_budgets_async(mdrp_handle *h, int kind, const double *x1_dev, const double *x2_dev, const double *d1_dev,
+                                      const double *d2_dev, int batch, int n_max, const int32_t *n_per_pair_host, const mdrp_camera *cam1_host,
+                                      const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                      const uint64_t *budgets, int n_budgets, uint8_t *inlier_mask_dev);
+int mdrp_fetch_budget_results(mdrp_handle *h, mdrp_result *out_host, int n_budgets, int batch);
+int mdrp_copy_budget_results_device(mdrp_handle *h, void *dst_dev, int n_budgets, int batch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,9 @@ EXPORTS = (
     "mdrp_estimate_batch_async", "mdrp_fetch_results", "mdrp_copy_results_device", "mdrp_solver_batch", "mdrp_score_models", "mdrp_count_candidates", "mdrp_bound_models", "mdrp_refine_models",
     "mdrp_last_sweep_stats", "mdrp_last_stats", "mdrp_last_stats_sized", "mdrp_classic_solver_batch",
     "mdrp_gather_matches", "mdrp_estimate_matches_async",
+    "mdrp_estimate_batch_budgets", "mdrp_estimate_batch_budgets_async", "mdrp_fetch_budget_results", "mdrp_copy_budget_results_device",
 )
+MAX_BUDGETS = 16  # include/mdrp.h MDRP_MAX_BUDGETS
 F32, F64 = 0, 1  # mdrp_matches.kp_type / depth_type
 FILTERS = {"both_inf": 0, "finite": 1}  # mdrp_matches.filter (include/mdrp.h MDRP_FILTER_*)
 
@@ -130,6 +132,13 @@ def load_library():
         lib.mdrp_classic_solver_batch.argtypes = [vp, C.c_int, dp, dp, C.c_int, vp, vp]
         lib.mdrp_gather_matches.argtypes = [vp, C.POINTER(Matches), C.c_int, dp, dp, dp, dp, ip, ip]
         lib.mdrp_estimate_matches_async.argtypes = [vp, C.c_int, C.POINTER(Matches), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
+        if hasattr(lib, "mdrp_estimate_batch_budgets"):  # (an older ABI-0.6 library through MDRP_LIB has no budgets entry points: Handle._budgets_fn raises)
+            lib.mdrp_estimate_batch_budgets.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                        C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp]
+            lib.mdrp_estimate_batch_budgets_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp]
+            lib.mdrp_fetch_budget_results.argtypes = [vp, vp, C.c_int, C.c_int]
+            lib.mdrp_copy_budget_results_device.argtypes = [vp, vp, C.c_int, C.c_int]
         _lib = lib
         return lib
 
@@ -176,6 +185,30 @@ def bundle_opt_from_dict(d=None):
     return BundleOpt(int(d.get("max_iterations", 100)), int(lt), float(d.get("loss_scale", 1.0)),
                      float(d.get("gradient_tol", 1e-10)), float(d.get("step_tol", 1e-8)), float(d.get("initial_lambda", 1e-3)),
                      float(d.get("min_lambda", 1e-10)), float(d.get("max_lambda", 1e10)))
+
+
+def budget_list(budgets, ransac_opt=None):
+    """An iteration-budget list as the library takes it (mdrp_estimate_batch_budgets): integers >= 1, strictly increasing, at most MAX_BUDGETS.
+    Returns (uint64 array, ransac option dict with max_iterations = the last budget).  ValueError for an invalid list, and where the dict
+    already holds another max_iterations.  Needs no library."""
+    try:
+        ks = [int(k) for k in budgets]
+        exact = all(k == b for k, b in zip(ks, budgets))
+    except (TypeError, ValueError):
+        raise ValueError("budgets must be a sequence of integers") from None
+    if not ks:
+        raise ValueError("budgets: an empty list")
+    if not exact:
+        raise ValueError("budgets must be integers")
+    if len(ks) > MAX_BUDGETS:
+        raise ValueError(f"budgets: more than {MAX_BUDGETS}")
+    if ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError("budgets must be >= 1 and strictly increasing")
+    ro = dict(ransac_opt or {})
+    if "max_iterations" in ro and int(ro["max_iterations"]) != ks[-1]:
+        raise ValueError(f"ransac_opt['max_iterations'] = {ro['max_iterations']} differs from the last budget {ks[-1]}")
+    ro["max_iterations"] = ks[-1]
+    return np.asarray(ks, dtype=np.uint64), ro
 
 
 def library_version():
@@ -328,6 +361,59 @@ class Handle:
                                                               C.c_void_p(d1_ptr) if d1_ptr else None, C.c_void_p(d2_ptr) if d2_ptr else None, int(batch), int(n_max),
                                                               _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
                                                               C.c_void_p(mask_ptr) if mask_ptr else None))
+
+    # ---- every budget of a list in one run (include/mdrp.h: iteration budgets).  The list goes to the library as it is: the library checks it.
+    def _budgets_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the budgets entry points (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    def estimate_batch_budgets(self, kind, x1, x2, d1, d2, ropt, bopt, budgets, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
+        """estimate_batch at every budget: records (C, B) and masks (C, B, N), C = len(budgets)"""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+            raise ValueError("expected x1,x2 (B,N,2)")
+        if kind >= RELPOSE_5PT:
+            d1 = d2 = None
+        else:
+            d1 = np.ascontiguousarray(d1, dtype=np.float64)
+            d2 = np.ascontiguousarray(d2, dtype=np.float64)
+            if d1.shape != x1.shape[:2] or d2.shape != d1.shape:
+                raise ValueError("expected d1,d2 (B,N)")
+        B, N = x1.shape[:2]
+        ks = np.ascontiguousarray(budgets, dtype=np.uint64).reshape(-1)
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        out = np.zeros((len(ks), B), dtype=RESULT_DTYPE)
+        mask = np.zeros((len(ks), B, N), dtype=np.uint8) if want_mask else None
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        _check(self._lib, self._budgets_fn("mdrp_estimate_batch_budgets")(self._h, kind, MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N,
+                                                                _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                                _ptr(ks), len(ks), _ptr(out), _ptr(mask)))
+        return out, mask
+
+    def estimate_batch_budgets_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ropt, bopt, budgets, n_per_pair=None,
+                                      cam1=None, cam2=None, mask_ptr=None):
+        """estimate_batch_device at every budget; mask_ptr: (C, batch, n_max) bytes on the device.  Records: fetch_budget_results."""
+        ks = np.ascontiguousarray(budgets, dtype=np.uint64).reshape(-1)
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        _check(self._lib, self._budgets_fn("mdrp_estimate_batch_budgets_async")(self._h, kind, C.c_void_p(x1_ptr), C.c_void_p(x2_ptr),
+                                                                      C.c_void_p(d1_ptr) if d1_ptr else None, C.c_void_p(d2_ptr) if d2_ptr else None,
+                                                                      int(batch), int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                                      _ptr(ks), len(ks), C.c_void_p(mask_ptr) if mask_ptr else None))
+
+    def fetch_budget_results(self, n_budgets, batch):
+        out = np.zeros((int(n_budgets), int(batch)), dtype=RESULT_DTYPE)
+        _check(self._lib, self._budgets_fn("mdrp_fetch_budget_results")(self._h, _ptr(out), int(n_budgets), int(batch)))
+        return out
+
+    def copy_budget_results_device(self, dst_ptr, n_budgets, batch):
+        """the records of the last budgets call into device memory at dst_ptr (n_budgets x batch x 136 bytes)"""
+        _check(self._lib, self._budgets_fn("mdrp_copy_budget_results_device")(self._h, C.c_void_p(dst_ptr), int(n_budgets), int(batch)))
 
     # ---- device front end: a Matches descriptor of device pointers
     def gather_matches(self, mm, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):

@@ -170,6 +170,10 @@ struct mdrp_handle {
     bool fuse_disabled = false;       // a bounded wait of the fused tail expired on this handle: streams do not overlap here, run unfused ...
     int fuse_retry_in = 0;            // ... for this many API calls, then try the fused tail again (a busy moment on a shared GPU is not a profiler)
     int fuse_backoff = 64;            // ... doubled after every consecutive expired wait (capped), reset by a call whose fused tail ran through
+    // budgets call (mdrp_estimate_batch_budgets): per pass the checkpoint states [C][pairs] and problem list | representatives | done flags
+    // ([C][pairs] int32 each); per call the result planes [C][batch] and, where the caller gives no device mask, the mask planes [C][batch][n_max]
+    DevBuf ckpt, ck_list, bresults, bmask;
+    int last_budgets = 0;              // budgets of the last call (0: it had none)
     DevBuf in_x1, in_x2, in_d1, in_d2; // staging when the caller passes host memory
     DevBuf fe_x1, fe_x2, fe_d1, fe_d2, fe_slot, fe_n; // device front end (mdrp_estimate_matches_async): gathered correspondences | slot of every match row | kept rows per pair
     Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
@@ -309,8 +313,8 @@ bool env_chunks(std::vector<uint64_t> &lead) {
 struct PassScratch {
     std::vector<std::pair<DevBuf *, size_t>> bufs;
     size_t fuse; // (ensured by the super-chunk that runs the fused tail)
-    // `params`: table states | cameras 1 | cameras 2 | table sizes | table of pair | n per pair
-    size_t params, off_cam1, off_cam2, off_tn, off_tof, off_nper;
+    // `params`: table states | cameras 1 | cameras 2 | table sizes | table of pair | n per pair | budgets (a budgets call: MAX_BUDGETS u64)
+    size_t params, off_cam1, off_cam2, off_tn, off_tof, off_nper, off_bud;
     // Reduce5 blocks of the 5-point solver (issue_solve): [pair][ceil(len / 64)] blocks of RED5_STRIDE x 64 doubles per solve, in two regions.
     // The first chunk of a super-chunk of several chunks is solved on the main stream while the second chunk's solver may run on `aux` (the
     // sliced host-buffer front: the main stream waits for a slice's k_prep only, not for the solver issued behind it), so it gets a region of
@@ -324,12 +328,13 @@ struct PassScratch {
     }
 };
 
-PassScratch pass_scratch(mdrp_handle *h, int kind, int batch, int n_max, int n_tables, int chunk_cap, const std::vector<uint64_t> &lead) {
+PassScratch pass_scratch(mdrp_handle *h, int kind, int batch, int n_max, int n_tables, int chunk_cap, const std::vector<uint64_t> &lead, int n_budgets = 0) {
     const size_t b = (size_t)batch, n = (size_t)n_max, t = (size_t)n_tables, slots = b * chunk_cap * model_slots(kind);
     PassScratch z;
     z.fuse = 64 + 3 * sizeof(int32_t) * b;
     z.off_cam1 = sizeof(uint64_t) * t; z.off_cam2 = z.off_cam1 + sizeof(CamDev) * b; z.off_tn = z.off_cam2 + sizeof(CamDev) * b;
-    z.off_tof = z.off_tn + sizeof(int32_t) * t; z.off_nper = z.off_tof + sizeof(int32_t) * b; z.params = z.off_nper + sizeof(int32_t) * b;
+    z.off_tof = z.off_tn + sizeof(int32_t) * t; z.off_nper = z.off_tof + sizeof(int32_t) * b;
+    z.off_bud = (z.off_nper + sizeof(int32_t) * b + 7) / 8 * 8; z.params = n_budgets ? z.off_bud + sizeof(uint64_t) * MAX_BUDGETS : z.off_nper + sizeof(int32_t) * b;
     z.red5_blocks = ((size_t)chunk_cap + 63) / 64;
     z.red5_first_blocks = (std::min<uint64_t>(lead.empty() ? 0 : lead[0], (uint64_t)chunk_cap / 2) + 63) / 64;
     const size_t samples = sizeof(uint32_t) * sample_size(kind) * t * chunk_cap, tags = sizeof(uint32_t) * slots, pair2 = sizeof(int32_t) * 2 * b;
@@ -348,18 +353,36 @@ PassScratch pass_scratch(mdrp_handle *h, int kind, int batch, int n_max, int n_t
         {&h->plan, sizeof(int32_t) * (2 * b + 2 + 4 + 16)}, // k_plan's two prefix arrays (batch + 1 each) | its totals {dense, total, head} | spare
         // the 5- and 6-point LO keeps the inlier subset of the model it refines: one row per LO workgroup (kc_lo launches num_cu * (8 | 2) of them)
         {&h->lo_mask, (kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT) ? (size_t)h->num_cu * 8 * std::max<size_t>(n, 1) : 0},
-        {&h->red5, kind == MDRP_RELPOSE_5PT ? sizeof(double) * b * (z.red5_blocks + z.red5_first_blocks) * RED5_STRIDE * 64 : 0}};
+        {&h->red5, kind == MDRP_RELPOSE_5PT ? sizeof(double) * b * (z.red5_blocks + z.red5_first_blocks) * RED5_STRIDE * 64 : 0},
+        {&h->ckpt, sizeof(PairState) * b * n_budgets}, {&h->ck_list, sizeof(int32_t) * 3 * b * n_budgets}};
     return z;
 }
 
 // one pass = a contiguous range of pairs that fits the scratch budget
 // `host` (or null): the caller's HOST buffers of this pass; x1 ... d2 are then the handle's device staging buffers, still to be filled
 struct HostSrc { const double *x1, *x2, *d1, *d2; };
+// a budgets call: the budgets and, for this pass, row 0 of its pairs in the result and mask planes ([n][plane] records, [n][plane][n_max] bytes)
+struct BudgetOut { const uint64_t *budgets; int n; ResultDev *results; uint8_t *mask; int plane; };
+
+// strictly increasing budgets >= 1, at most MAX_BUDGETS, the last one the run's max_iterations: checked before any device work
+int check_budgets(const mdrp_ransac_opt *ro, const uint64_t *budgets, int n_budgets) {
+    const char *why = nullptr;
+    if (!ro || !budgets || n_budgets < 1) why = "budgets: an empty list";
+    else if (n_budgets > MAX_BUDGETS) why = "budgets: more than MDRP_MAX_BUDGETS";
+    else {
+        for (int c = 0; c < n_budgets && !why; ++c)
+            if (budgets[c] < 1 || (c > 0 && budgets[c] <= budgets[c - 1])) why = "budgets: must be >= 1 and strictly increasing";
+        if (!why && budgets[n_budgets - 1] != ro->max_iterations) why = "budgets: ransac_opt.max_iterations must equal the last budget";
+    }
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
 constexpr int HOST_SLICE_PAIRS = 256; // pairs per H2D slice of a host-buffer call (24.6 MB at N = 2000: ~0.5 ms of PCIe per slice)
 
 int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
              int n_max, const int32_t *n_host, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
-             const mdrp_bundle_opt *bo, int chunk_cap, uint8_t *mask_dev, ResultDev *results_dev, const HostSrc *host, int batch_call) {
+             const mdrp_bundle_opt *bo, int chunk_cap, uint8_t *mask_dev, ResultDev *results_dev, const HostSrc *host, int batch_call,
+             const BudgetOut *bud = nullptr) {
     hipStream_t s = h->stream;
     const int est_shift = (kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0;
     const bool classic = kind >= MDRP_RELPOSE_5PT;              // non-monodepth baselines (mdrp_classic.h)
@@ -423,7 +446,8 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         }
     }
 
-    const PassScratch sz = pass_scratch(h, kind, batch, n_max, n_tables, chunk_cap, lead);
+    const int n_bud = bud ? bud->n : 0;
+    const PassScratch sz = pass_scratch(h, kind, batch, n_max, n_tables, chunk_cap, lead, n_bud);
     int rc;
     for (const auto &b : sz.bufs) {
         if ((rc = b.first->ensure(b.second))) return rc; // (0 bytes: nothing to allocate)
@@ -453,6 +477,7 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         std::memcpy(ph + sz.off_tn, tab_n.data(), sizeof(int32_t) * n_tables);
         std::memcpy(ph + sz.off_tof, table_of.data(), sizeof(int32_t) * batch);
         std::memcpy(ph + sz.off_nper, n_host, sizeof(int32_t) * batch);
+        if (bud) std::memcpy(ph + sz.off_bud, bud->budgets, sizeof(uint64_t) * n_bud);
         HIPCHK(hipMemcpyAsync(pd, ph, sz.params, hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipEventRecord(h->ev_tables, s)); // sample tables can be drawn from here on
@@ -513,18 +538,24 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     // After a bounded wait expired on this handle (kernels of two streams do not run side by side here: serialising profiler,
     // AMD_SERIALIZE_KERNEL, a busy shared GPU) the handle stays unfused, unless MDRP_FUSE_TAIL is set explicitly.
     // (fuse_disabled / fuse_retry_in are advanced once per API call in estimate_device, not per pass)
-    const bool fuse_env = env_int("MDRP_FUSE_TAIL", ((kind == MDRP_CALIB && est_shift) || h->fuse_disabled) ? 0 : 1) != 0;
+    // (a budgets call runs its tail unfused: the checkpoints are taken by the walk kernel, and their refinements are one launch of their own)
+    const bool fuse_env = !bud && env_int("MDRP_FUSE_TAIL", ((kind == MDRP_CALIB && est_shift) || h->fuse_disabled) ? 0 : 1) != 0;
     bool final_done = false;
     // the final refinements of the pass's pairs on the main stream; the fused tail's (ready list, done flags, wait ticks, time-out counter), or
     // (null, pairs to skip or null, 0, null)
-    auto launch_final = [&](const int32_t *ready, int32_t *fin_done, unsigned long long ticks, unsigned long long *timeouts) {
+    // `problems` workgroups over the states `st_f` (run parameters `rf`): the pass's pairs, or the checkpoint problems of a budgets call
+    auto launch_final_of = [&](const RunParams &rf, int problems, PairState *st_f, uint8_t *mask_f, ResultDev *results_f, const int32_t *ready, int32_t *fin_done,
+                               unsigned long long ticks, unsigned long long *timeouts) {
         if (classic)
-            MDRP_CLASSIC_LM_DISPATCH(kc_final, final_threads, kind, dim3(batch), clm_list_bytes, s, rp, h->st.as<PairState>(), h->pts.as<double>(), mask_dev, results_dev,
+            MDRP_CLASSIC_LM_DISPATCH(kc_final, final_threads, kind, dim3(problems), clm_list_bytes, s, rf, st_f, h->pts.as<double>(), mask_f, results_f,
                                      ready, fin_done, ticks, timeouts, clm_list_stride);
         else
-            MDRP_FINAL_DISPATCH(final_threads, rp.final_loss, kind, est_shift, dim3(batch), (mask_index ? lm_final_list_bytes(n_max) : lm_list_bytes(n_max)), s, rp,
-                                h->st.as<PairState>(), h->pts.as<double>(), h->dep.as<double>(), mask_dev, results_dev, lm_list_stride(n_max), mask_index,
+            MDRP_FINAL_DISPATCH(final_threads, rf.final_loss, kind, est_shift, dim3(problems), (mask_index ? lm_final_list_bytes(n_max) : lm_list_bytes(n_max)), s, rf,
+                                st_f, h->pts.as<double>(), h->dep.as<double>(), mask_f, results_f, lm_list_stride(n_max), mask_index,
                                 h->lm_stats.as<unsigned long long>() + 2, ready, fin_done, ticks, timeouts);
+    };
+    auto launch_final = [&](const int32_t *ready, int32_t *fin_done, unsigned long long ticks, unsigned long long *timeouts) {
+        launch_final_of(rp, batch, h->st.as<PairState>(), mask_dev, results_dev, ready, fin_done, ticks, timeouts);
     };
     const size_t tile_bytes = SCORE_TILE_BYTES;
 
@@ -862,7 +893,11 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
         if (piped) { HIPCHK(hipEventRecord(h->ev_lo, aux2)); HIPCHK(hipStreamWaitEvent(s, h->ev_lo, 0)); }
         if (fuse_tail) // behind the LO launch: the pairs a bounded wait gave up on (none in a healthy run: 1024 workgroups that read a flag)
             launch_final(nullptr, fz_fin, 0, nullptr);
-        if (!fuse_tail)
+        if (bud)
+            hipLaunchKernelGGL(k_walk_ckpt, dim3((batch + WALK_CKPT_THREADS - 1) / WALK_CKPT_THREADS), dim3(WALK_CKPT_THREADS), 0, s, rp, h->st.as<PairState>(), h->models.as<Model>(),
+                               h->triggers.as<Trigger>(), trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed,
+                               reinterpret_cast<const uint64_t *>(pd + sz.off_bud), n_bud, h->ckpt.as<PairState>());
+        else if (!fuse_tail)
             hipLaunchKernelGGL(k_walk, dim3((batch + 63) / 64), dim3(64), 0, s, rp, h->st.as<PairState>(), h->models.as<Model>(),
                                h->triggers.as<Trigger>(), trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed,
                                (const int32_t *)nullptr, 0, 0, 0);
@@ -890,7 +925,20 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     hipEvent_t f0, f1;
     if ((rc = get_events(h, &f0, &f1, 3))) return rc;
     HIPCHK(hipEventRecord(f0, s));
-    launch_final(nullptr, nullptr, 0, nullptr);
+    if (bud) {
+        // the distinct checkpoint states of every pair in ONE launch over the compact list (k_ckpt_plan); every other checkpoint is filled from its
+        // representative.  A pair that stops early, or whose best model does not change between two budgets, is refined once for all of them.
+        const int problems = n_bud * batch;
+        int32_t *list = h->ck_list.as<int32_t>(), *rep = list + problems, *done = rep + problems;
+        hipLaunchKernelGGL(k_ckpt_plan, dim3(1), dim3(PLAN_THREADS), 0, s, batch, n_bud, h->ckpt.as<PairState>(), list, rep);
+        RunParams rf = rp;
+        rf.ck_pairs = batch; rf.ck_plane = bud->plane;
+        rf.inl_stat = nullptr; // (the last budget's results alone feed the next call's first chunk: k_ckpt_fill)
+        launch_final_of(rf, problems, h->ckpt.as<PairState>(), bud->mask, bud->results, list, done, 0, nullptr);
+        rf.inl_stat = rp.inl_stat;
+        hipLaunchKernelGGL(k_ckpt_fill, dim3(problems), dim3(CKPT_FILL_THREADS), 0, s, rf, n_bud, h->ckpt.as<PairState>(), rep, bud->results, bud->mask);
+    } else
+        launch_final(nullptr, nullptr, 0, nullptr);
     HIPCHK(hipEventRecord(f1, s));
     if (rp.inl_stat && h->wish_kind < 0) { // (the fused tail's sums came with the progress record; these arrive when the stream gets here: the next call looks)
         HIPCHK(hipMemcpyAsync(h->wish_host, rp.inl_stat, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -903,7 +951,8 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
 
 int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
                     int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                    const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr) {
+                    const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr,
+                    const uint64_t *budgets = nullptr, int n_budgets = 0) {
     const bool known_kind = kind >= 0 && kind <= 5;
     if (!h || batch < 0 || n_max < 0 || !known_kind || !ro || !bo) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (kind == MDRP_SHARED_6PT && batch > 0 && !cam1) { g_err = "the 6-point estimator needs the principal point in cam1"; return MDRP_ERR_INVALID; }
@@ -912,6 +961,7 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     // RansacOptions switches of the reference that are not built are refused, never ignored (the reference would return different results)
     if (ro->progressive_sampling) { g_err = "progressive_sampling (PROSAC, RandomSampler::initialize_prosac) is not built"; return MDRP_ERR_UNSUPPORTED; }
     if (ro->real_focal_check && (kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT)) { g_err = "real_focal_check is not built"; return MDRP_ERR_UNSUPPORTED; }
+    h->last_budgets = n_budgets;
     if (h->fuse_disabled && --h->fuse_retry_in <= 0) h->fuse_disabled = false; // once per API call (not per pass): the handle tries the fused tail again
     h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
     int rc;
@@ -926,9 +976,12 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     }
     uint8_t *mask = mask_dev;
     if (!mask) {
-        if ((rc = h->mask.ensure((size_t)batch * std::max(n_max, 1)))) return rc;
-        mask = h->mask.as<uint8_t>();
+        if ((rc = (budgets ? h->bmask : h->mask).ensure((size_t)std::max(n_budgets, 1) * batch * std::max(n_max, 1)))) return rc;
+        mask = (budgets ? h->bmask : h->mask).as<uint8_t>();
     }
+    // a budgets call: `mask` is [n_budgets][batch][n_max], the records go to the planes of `bresults` (allocated before the pass budget is taken
+    // from the free memory below); the last plane is copied to `results` behind the passes
+    if (budgets && (rc = h->bresults.ensure(sizeof(ResultDev) * n_budgets * batch))) return rc;
     // chunk capacity and pairs per pass from the scratch budget
     uint64_t chunk_cap64 = std::min<uint64_t>(std::max<uint64_t>(ro->max_iterations, 1), std::max<uint64_t>(ro->min_iterations + 1, 4096));
     chunk_cap64 = std::min<uint64_t>(chunk_cap64, 16384);
@@ -940,7 +993,7 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     // default first chunk of that estimator is at most 512 iterations (run_pass).
     std::vector<uint64_t> lead;
     if (!env_chunks(lead)) lead.assign(1, 512);
-    const size_t per_pair = pass_scratch(h, kind, 2, n_max, 2, chunk_cap, lead).total() - pass_scratch(h, kind, 1, n_max, 1, chunk_cap, lead).total();
+    const size_t per_pair = pass_scratch(h, kind, 2, n_max, 2, chunk_cap, lead, n_budgets).total() - pass_scratch(h, kind, 1, n_max, 1, chunk_cap, lead, n_budgets).total();
     size_t budget = std::min<size_t>((size_t)(0.5 * (double)free_b), (size_t)96 << 30);
     int per_pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, budget / per_pair));
     per_pass = std::min(per_pass, 65535); // k_solve / k_probe put the pair index on grid.y
@@ -950,11 +1003,15 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
         HostSrc hs{};
         if (host) hs = HostSrc{host->x1 + (size_t)2 * p0 * n_max, host->x2 + (size_t)2 * p0 * n_max, host->d1 ? host->d1 + (size_t)p0 * n_max : nullptr,
                                host->d2 ? host->d2 + (size_t)p0 * n_max : nullptr};
+        const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + (size_t)p0 * n_max, batch};
         rc = run_pass(h, kind, x1 + (size_t)2 * p0 * n_max, x2 + (size_t)2 * p0 * n_max, d1 ? d1 + (size_t)p0 * n_max : nullptr,
                       d2 ? d2 + (size_t)p0 * n_max : nullptr, nb,
                       n_max, n_host.data() + p0, cam1 ? cam1 + p0 : nullptr, cam2 ? cam2 + p0 : nullptr, ro, bo, chunk_cap,
-                      mask + (size_t)p0 * n_max, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch);
+                      mask + (size_t)p0 * n_max, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch, budgets ? &bud : nullptr);
         if (rc) return rc;
+    }
+    if (budgets) {
+        HIPCHK(hipMemcpyAsync(h->results.p, h->bresults.as<ResultDev>() + (size_t)(n_budgets - 1) * batch, sizeof(ResultDev) * batch, hipMemcpyDeviceToDevice, h->stream));
     }
     return MDRP_OK;
 }
@@ -1180,6 +1237,80 @@ int mdrp_estimate_batch(mdrp_handle *h, int kind, int mem_space, const double *x
     if (mem_space == MDRP_MEM_HOST && inlier_mask && np > 0)
         HIPCHK(hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, h->stream));
     return fetch_results_locked(h, out, batch);
+}
+
+// ---- iteration budgets
+static_assert(MDRP_MAX_BUDGETS == MAX_BUDGETS, "budget limit of the header and of the kernels");
+
+// an error behind the first device work: nothing of the call stays in flight on the caller's buffers
+static int drain_and_return(mdrp_handle *h, int rc) {
+    for (hipStream_t st : {h->stream, (hipStream_t)h->aux_stream, (hipStream_t)h->aux_stream2, (hipStream_t)h->copy_stream}) (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+static int budget_results_locked(mdrp_handle *h, void *dst, int n_budgets, int batch, hipMemcpyKind where) {
+    if (!dst || batch < 0 || n_budgets < 1 || n_budgets != h->last_budgets || batch != h->last_batch) {
+        g_err = "budget results: n_budgets and batch must be those of the handle's last budgets call";
+        return MDRP_ERR_INVALID;
+    }
+    if (batch > 0) HIPCHK(hipMemcpyAsync(dst, h->bresults.p, sizeof(ResultDev) * n_budgets * batch, where, h->stream));
+    return finish_timing(h);
+}
+
+int mdrp_estimate_batch_budgets_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2,
+                                      int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                      const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets, int n_budgets,
+                                      uint8_t *inlier_mask_dev) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
+    MDRP_ENTER(h);
+    const int rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, budgets, n_budgets);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_fetch_budget_results(mdrp_handle *h, mdrp_result *out, int n_budgets, int batch) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    return budget_results_locked(h, out, n_budgets, batch, hipMemcpyDeviceToHost);
+}
+
+int mdrp_copy_budget_results_device(mdrp_handle *h, void *dst_dev, int n_budgets, int batch) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    return budget_results_locked(h, dst_dev, n_budgets, batch, hipMemcpyDeviceToDevice); // (waits for the handle's stream, as mdrp_copy_results_device)
+}
+
+int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
+                                const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
+                                const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets,
+                                int n_budgets, mdrp_result *out, uint8_t *inlier_mask) {
+    if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
+    MDRP_ENTER(h);
+    const size_t np = (size_t)batch * n_max;
+    int rc;
+    uint8_t *mask_dev = inlier_mask;
+    HostSrc hsrc{};
+    bool use_host = false;
+    if (mem_space == MDRP_MEM_HOST) { // (staging as in mdrp_estimate_batch: the copies are issued by run_pass)
+        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
+            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)))
+            return rc;
+        hsrc = HostSrc{x1, x2, (d1 && d2) ? d1 : nullptr, (d1 && d2) ? d2 : nullptr};
+        if (d1 && d2) { d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>(); }
+        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
+        use_host = true;
+        mask_dev = nullptr; // handle-owned device mask planes, copied back below
+    }
+    rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, mask_dev, use_host ? &hsrc : nullptr, budgets, n_budgets);
+    if (rc) return drain_and_return(h, rc);
+    if (mem_space == MDRP_MEM_HOST && inlier_mask && np > 0 &&
+        hipMemcpyAsync(inlier_mask, h->bmask.p, np * n_budgets, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+        g_err = "copy of the inlier masks failed";
+        return drain_and_return(h, MDRP_ERR_HIP);
+    }
+    rc = budget_results_locked(h, out, n_budgets, batch, hipMemcpyDeviceToHost);
+    return rc ? drain_and_return(h, rc) : rc;
 }
 
 } // extern "C"

@@ -850,13 +850,14 @@ __device__ void cfinal_pair(const RunParams &rp, const PairState &ps, const doub
     res.model = ps.best;
     res.refinements = ps.refinements; res.iterations = ps.iterations; res.num_inliers = ps.num_inliers;
     res.inlier_ratio = ps.inlier_ratio; res.model_score = ps.model_score;
-    uint8_t *mask = mask_all + (size_t)pair * rp.n_max;
+    const FinalRows row = final_rows(rp, pair);
+    uint8_t *mask = mask_all + (size_t)row.out * rp.n_max;
     if (ps.n < ClassicTraits<CK>::K) {
         for (int i = threadIdx.x; i < rp.n_max; i += T) mask[i] = 0;
-        if (threadIdx.x == 0) results[pair] = res;
+        if (threadIdx.x == 0) results[row.out] = res;
         return;
     }
-    const double *pp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
+    const double *pp = pts + (size_t)row.rec * rp.n_max * PT_STRIDE;
     Model m = ps.best;
     for (int i = ps.n + threadIdx.x; i < rp.n_max; i += T) mask[i] = 0;
     clm_lo<CK, T>(m, ps, pp, mask, scratch, cl); // the output mask doubles as the LO's subset mask
@@ -892,7 +893,7 @@ __device__ void cfinal_pair(const RunParams &rp, const PairState &ps, const doub
     }
     if (CK == CLASSIC_SHARED) { best.f1 *= ps.norm; best.f2 *= ps.norm; } // back to pixels
     res.model = best;
-    if (threadIdx.x == 0) results[pair] = res;
+    if (threadIdx.x == 0) results[row.out] = res;
 }
 template <int CK, int T>
 __global__ __launch_bounds__(T, 2) void kc_final(RunParams rp, PairState *__restrict__ st, const double *__restrict__ pts,

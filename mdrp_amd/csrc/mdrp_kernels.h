@@ -111,7 +111,20 @@ struct RunParams {
     int final_max_it, final_loss;
     double grad_tol, step_tol, lambda0, lambda_min, lambda_max;
     int32_t *inl_stat;  // [2]: sum over the pairs of first_chunk_wish(inlier ratio of the result), and their number — the host sizes the NEXT call's first chunk from the mean
+    // checkpoint refinements of a budgets call (0 in every other launch): the final kernels' problem e is checkpoint e / ck_pairs of
+    // pair e % ck_pairs — its state is st[e], its records are that pair's, its result and mask row go to row (e / ck_pairs) * ck_plane + e % ck_pairs
+    int ck_pairs, ck_plane;
 };
+
+// iteration budgets of one call (mdrp_estimate_batch_budgets): strictly increasing, at most MAX_BUDGETS
+constexpr int MAX_BUDGETS = 16;
+// where a final refinement reads its records (`rec`) and writes its result and mask row (`out`)
+struct FinalRows { int rec, out; };
+__device__ __forceinline__ FinalRows final_rows(const RunParams &rp, int problem) {
+    if (!rp.ck_pairs) return {problem, problem};
+    const int c = problem / rp.ck_pairs, p = problem - c * rp.ck_pairs;
+    return {p, c * rp.ck_plane + p};
+}
 
 // ------------------------------------------------------------------------------------------------ reductions: cross-lane sums (gfx950)
 template <int CTRL>
@@ -2293,9 +2306,14 @@ __device__ __forceinline__ uint64_t f64_to_u64_x86(double d) {
     }
     return d >= -t63 ? (uint64_t)(int64_t)d : 0x8000000000000000ull; // (NaN fails both comparisons: cvttsd2si's "integer indefinite")
 }
-template <bool COHERENT = false>
+// SNAP (a budgets call's k_walk_ckpt only): the pair's state as it is when `iterations` reaches budget K_c — or the pair stops, if that
+// comes first — is copied into ck[c * ck_plane], with iterations = min(K_c, stop) and active = 0: what a run with max_iterations = K_c leaves behind,
+// since nothing but `it` changes between two triggers and the stop test cannot fire differently before K_c.  The copy is taken BEFORE a trigger at an
+// absolute iteration >= K_c is executed and before `it` passes K_c in a trigger-free stretch, at a stop or at the end of the super-chunk.
+template <bool COHERENT = false, bool SNAP = false>
 __device__ bool walk_pair(const RunParams &rp, PairState &ps, const Model *__restrict__ models, const Trigger *trig /*of this pair*/,
-                          size_t slot_base, uint64_t &need) {
+                          size_t slot_base, uint64_t &need, const uint64_t *__restrict__ budgets = nullptr, int n_budgets = 0,
+                          PairState *__restrict__ ck = nullptr /*this pair's row of checkpoint 0*/, size_t ck_plane = 0) {
     need = 0;
     if (!ps.active) return true;
     // max_iterations = 0: the reference's loop head ends the search before a sample is drawn (ransac<>: iterations < max_iterations) — no record, no
@@ -2304,6 +2322,18 @@ __device__ bool walk_pair(const RunParams &rp, PairState &ps, const Model *__res
     const uint64_t c0 = rp.chunk_start, c1 = rp.chunk_start + (uint64_t)rp.super_len;
     uint64_t it = c0; // iterations completed so far
     bool stopped = false;
+    int nc = 0; // SNAP: the first checkpoint still open (those up to the super-chunk's start were filled by the super-chunks before)
+    if constexpr (SNAP) while (nc < n_budgets && budgets[nc] <= c0) ++nc;
+    // SNAP: every open checkpoint with K_c <= upto takes the state as it is, at min(K_c, at) iterations
+    auto snap = [&](uint64_t upto, uint64_t at) {
+        if constexpr (SNAP)
+            for (; nc < n_budgets && budgets[nc] <= upto; ++nc) {
+                PairState &d = ck[(size_t)nc * ck_plane];
+                d = ps;
+                d.iterations = budgets[nc] < at ? budgets[nc] : at;
+                d.active = 0;
+            }
+    };
     // stop test applied after each completed iteration: it >= max -> stop; it > min && it > dyn -> stop
     auto first_stop = [&](uint64_t lo /*first candidate value of it*/) -> uint64_t {
         uint64_t s = lo;
@@ -2321,6 +2351,7 @@ __device__ bool walk_pair(const RunParams &rp, PairState &ps, const Model *__res
             const uint64_t s = first_stop(it + 1);
             if (s <= ti) { it = s; stopped = true; break; }
         }
+        snap(ti, ~0ull); // (iterations it .. ti - 1 changed nothing: the state at K_c <= ti is this one)
         // execute iteration ti
         if (tr.k_min >= 0 && tr.score_min < ps.model_score) {
             ps.model_score = tr.score_min;
@@ -2361,6 +2392,7 @@ __device__ bool walk_pair(const RunParams &rp, PairState &ps, const Model *__res
             if (s <= c1) { it = s; stopped = true; } else it = c1;
         }
     }
+    snap(stopped ? ~0ull : c1, stopped ? it : ~0ull); // stopped: every checkpoint still open reports the stopped state
     ps.iterations = it;
     if (stopped) { ps.active = 0; return true; }
     need = first_stop(it + 1) - it; // iterations still certainly needed with the current dyn_max_iter
@@ -2384,6 +2416,57 @@ MDRP_GLOBAL void k_walk(RunParams rp, PairState *__restrict__ st, const Model *_
         atomicAdd(n_active, 1);
         atomicMax(max_needed, (unsigned long long)need);
     }
+}
+
+// The walk of a budgets call: k_walk that also fills the pair's checkpoints, ckpt[c * rp.batch + pair] for budget c.  Pairs that never
+// iterate (fewer correspondences than a sample) report the state k_prep gave them at every budget.
+constexpr int WALK_CKPT_THREADS = 64; // (the launch bound lets a lane hold a whole PairState in registers while it copies it: no scratch)
+MDRP_GLOBAL __launch_bounds__(WALK_CKPT_THREADS) void k_walk_ckpt(RunParams rp, PairState *__restrict__ st, const Model *__restrict__ models, const Trigger *__restrict__ triggers,
+                            int trig_cap, int32_t *__restrict__ n_active, unsigned long long *__restrict__ max_needed,
+                            const uint64_t *__restrict__ budgets, int n_budgets, PairState *__restrict__ ckpt) {
+    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pair >= rp.batch) return;
+    PairState &ps = st[pair];
+    if (!ps.active) {
+        if (rp.chunk_start == 0)
+            for (int c = 0; c < n_budgets; ++c) ckpt[(size_t)c * rp.batch + pair] = ps;
+        return;
+    }
+    uint64_t need;
+    if (!walk_pair<false, true>(rp, ps, models, triggers + (size_t)pair * trig_cap, (size_t)pair * rp.slot_stride, need, budgets, n_budgets,
+                                ckpt + pair, (size_t)rp.batch)) {
+        atomicAdd(n_active, 1);
+        atomicMax(max_needed, (unsigned long long)need);
+    }
+}
+
+// Only distinct states are refined: `refinements` grows whenever a pair's state changes, so two checkpoints of a pair with equal `refinements` differ
+// in `iterations` at most.  One workgroup: per pair, the first checkpoint of every run of equal `refinements` goes on `list` (problems c * batch +
+// pair, ordered by pair, then budget; the unused tail is -1: surplus workgroups of the final launch leave at once), and rep[c * batch + pair] names
+// the problem whose result every checkpoint shares.
+MDRP_GLOBAL __launch_bounds__(PLAN_THREADS) void k_ckpt_plan(int batch, int n_budgets, const PairState *__restrict__ ckpt, int32_t *__restrict__ list,
+                                                            int32_t *__restrict__ rep) {
+    __shared__ int s_w[PLAN_THREADS / 64 + 1];
+    int run = 0;
+    for (int p0 = 0; p0 < batch; p0 += PLAN_THREADS) {
+        const int p = p0 + threadIdx.x;
+        int kept = 0;
+        if (p < batch)
+            for (int c = 0; c < n_budgets; ++c)
+                kept += c == 0 || ckpt[(size_t)c * batch + p].refinements != ckpt[(size_t)(c - 1) * batch + p].refinements;
+        int tot;
+        const int ex = plan_block_scan(kept, tot, s_w);
+        if (p < batch) {
+            int w = run + ex, r = 0;
+            for (int c = 0; c < n_budgets; ++c) {
+                const int e = c * batch + p;
+                if (c == 0 || ckpt[e].refinements != ckpt[e - batch].refinements) { r = e; list[w++] = e; }
+                rep[e] = r;
+            }
+        }
+        run += tot;
+    }
+    for (int i = run + threadIdx.x; i < n_budgets * batch; i += PLAN_THREADS) list[i] = -1;
 }
 
 // Fused tail (the LAST LO launch of a run whose end is known): the workgroup that refines the last open trigger of a
@@ -2527,7 +2610,8 @@ template <int KIND, bool SHIFT, int T, int FLOSS>
 __device__ __forceinline__ void final_pair(const RunParams &rp, const PairState &ps, const double *__restrict__ pts, const double *__restrict__ dep,
                                            uint8_t *__restrict__ mask_all, ResultDev *__restrict__ results, int pair, LmShared &sh) {
     double *scratch = sh.scratch;
-    uint8_t *mask = mask_all + (size_t)pair * rp.n_max;
+    const FinalRows row = final_rows(rp, pair);
+    uint8_t *mask = mask_all + (size_t)row.out * rp.n_max;
     if (ps.n < 3) {
         for (int i = threadIdx.x; i < rp.n_max; i += T) mask[i] = 0;
         if (threadIdx.x == 0) {
@@ -2535,12 +2619,12 @@ __device__ __forceinline__ void final_pair(const RunParams &rp, const PairState 
             res.model = ps.best;
             res.refinements = ps.refinements; res.iterations = ps.iterations; res.num_inliers = ps.num_inliers;
             res.inlier_ratio = ps.inlier_ratio; res.model_score = ps.model_score;
-            results[pair] = res;
+            results[row.out] = res;
         }
         return;
     }
-    const double *pp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
-    const double *dd = dep + (size_t)pair * rp.n_max * 2;
+    const double *pp = pts + (size_t)row.rec * rp.n_max * PT_STRIDE;
+    const double *dd = dep + (size_t)row.rec * rp.n_max * 2;
     // ransac<>'s last LO from the best model: 25 iterations, TRUNCATED, all records
     Model x = ps.best;
     {
@@ -2575,7 +2659,7 @@ __device__ __forceinline__ void final_pair(const RunParams &rp, const PairState 
         res.model = x;
         res.refinements = ps.refinements + 1; res.iterations = ps.iterations; res.num_inliers = num_inliers;
         res.inlier_ratio = ps.inlier_ratio; res.model_score = ps.model_score;
-        results[pair] = res;
+        results[row.out] = res;
         if (rp.inl_stat) { // what this pair would have liked as the run's first chunk: ~6 outlier-free samples expected in it (first_chunk_wish)
             atomicAdd(&rp.inl_stat[0], first_chunk_wish((double)num_inliers / (double)ps.n, 3));
             atomicAdd(&rp.inl_stat[1], 1);
@@ -2629,6 +2713,29 @@ __global__ __launch_bounds__(T, MDRP_LM_MINWAVES) void k_final(RunParams rp, Pai
     __syncthreads();
     final_pair<KIND, SHIFT, T, FLOSS>(rp, *reinterpret_cast<const PairState *>(s_ps), pts, dep, mask_all, results, s_pair, sh);
     if (ready && threadIdx.x == 0) fin_done[s_pair] = 1;
+}
+
+// Budgets call (k_ckpt_plan): behind the final refinements every other checkpoint takes its representative's record and mask row, with its own `iterations`.  One workgroup
+// per (budget, pair); rows as final_rows.  The last budget's results feed rp.inl_stat, as the final refinements of a call without budgets do.
+constexpr int CKPT_FILL_THREADS = 256;
+MDRP_GLOBAL __launch_bounds__(CKPT_FILL_THREADS) void k_ckpt_fill(RunParams rp, int n_budgets, const PairState *__restrict__ ckpt,
+                                                                 const int32_t *__restrict__ rep, ResultDev *__restrict__ results,
+                                                                 uint8_t *__restrict__ mask_all) {
+    const int e = blockIdx.x, r = rep[e];
+    const FinalRows dst = final_rows(rp, e), src = final_rows(rp, r);
+    if (r != e) {
+        const uint8_t *from = mask_all + (size_t)src.out * rp.n_max;
+        uint8_t *to = mask_all + (size_t)dst.out * rp.n_max;
+        for (int i = threadIdx.x; i < rp.n_max; i += CKPT_FILL_THREADS) to[i] = from[i];
+    }
+    if (threadIdx.x == 0) {
+        ResultDev res = results[src.out];
+        if (r != e) { res.iterations = ckpt[e].iterations; results[dst.out] = res; }
+        if (rp.inl_stat && e / rp.ck_pairs == n_budgets - 1 && ckpt[e].n >= 3) {
+            atomicAdd(&rp.inl_stat[0], first_chunk_wish((double)res.num_inliers / (double)ckpt[e].n, 3));
+            atomicAdd(&rp.inl_stat[1], 1);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ unit-parity kernels

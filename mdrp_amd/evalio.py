@@ -123,21 +123,46 @@ CORE_RANSAC_KEYS = ("max_iterations", "min_iterations", "dyn_num_trials_mult", "
                     "seed", "progressive_sampling", "max_prosac_iterations", "real_focal_check", "score_initial_model")
 
 
+def _graph_budgets(iterations_list):
+    """eval.py:290-294 graph mode: the iteration budgets of one run, checked (ValueError) before anything is loaded"""
+    if iterations_list is None:
+        return None
+    return [int(k) for k in _capi.budget_list(iterations_list)[0]]
+
+
+def _per_budget_results(budgets, out, infos, ms):
+    """(budget or None, objects, infos, runtime) per emitted batch of records: the call's, or one per budget with the call's time shared out"""
+    if budgets is None:
+        return [(None, out, infos, ms)]
+    return [(k, out[c], infos[c], ms / len(budgets)) for c, k in enumerate(budgets)]
+
+
 def evaluate_calibrated(h5, experiments, iters=None, threshold=1.0, reproj_threshold=16.0, first=None, batch=4096,
-                        estimate_batch=None, device=0, estimate_5pt_batch=None):
+                        estimate_batch=None, device=0, estimate_5pt_batch=None, iterations_list=None):
     """eval.py:316-359 for the calibrated estimator, batched: every experiment's pairs go to the GPU `batch` at a time.
     `estimate_batch(kp1s, kp2s, d1s, d2s, cams1, cams2, ransac_opt, bundle_opt)` defaults to the accelerated
     `poselib.estimate_monodepth_relative_pose_batch` (injectable for tests).  Experiment names with '5p' are the 5-point
     baseline row (eval.py:134-137: `poselib.estimate_relative_pose`, which reads only the upstream RansacOptions keys of the
     dict) and go to `poselib.estimate_relative_pose_batch`.  Pairs with fewer than 5 correspondences are skipped as in the
-    reference.  `info['runtime']` is the batch wall time divided by the batch size, in ms."""
+    reference.  `info['runtime']` is the batch wall time divided by the batch size, in ms.
+
+    iterations_list (the reference's graph mode, eval.py:290-294: [10, 20, 50, 100, 200, 500, 1000]): every batch runs ONCE, with
+    min_iterations = max_iterations = the last entry as `experiment_options` sets them and the list as the call's budgets
+    (`poselib.*_batch(..., budgets=...)`), and yields one record per pair and budget, budget innermost.  Each record is what the separate run
+    with that budget returns; its `info['iterations']` is the budget, and its `info['runtime']` is the call's time per pair divided by the
+    number of budgets — the one run is shared by all of them; a separate run per budget is not timed.  The estimators are then called with a
+    `budgets=` keyword and return lists over the budgets; without a list they are called as before."""
     from . import poselib
+    budgets = _graph_budgets(iterations_list)
+    if budgets is not None:
+        iters = budgets[-1]
+    kw = {} if budgets is None else {"budgets": budgets}
     if estimate_batch is None:
-        def estimate_batch(k1, k2, a, b, c1, c2, ro, bo):
-            return poselib.estimate_monodepth_relative_pose_batch(k1, k2, a, b, c1, c2, ro, bo, device=device)
+        def estimate_batch(k1, k2, a, b, c1, c2, ro, bo, **kw_):
+            return poselib.estimate_monodepth_relative_pose_batch(k1, k2, a, b, c1, c2, ro, bo, device=device, **kw_)
     if estimate_5pt_batch is None:
-        def estimate_5pt_batch(k1, k2, c1, c2, ro, bo):
-            return poselib.estimate_relative_pose_batch(k1, k2, c1, c2, ro, bo, device=device)
+        def estimate_5pt_batch(k1, k2, c1, c2, ro, bo, **kw_):
+            return poselib.estimate_relative_pose_batch(k1, k2, c1, c2, ro, bo, device=device, **kw_)
     pairs = list_pairs(h5, first)
     results = []
     for experiment in experiments:
@@ -155,17 +180,21 @@ def evaluate_calibrated(h5, experiments, iters=None, threshold=1.0, reproj_thres
             t0 = time.perf_counter()
             if five_point:
                 geoms, infos = estimate_5pt_batch([p["kp1"] for p in chunk], [p["kp2"] for p in chunk], [_pinhole(p["K1"]) for p in chunk],
-                                                  [_pinhole(p["K2"]) for p in chunk], ro, bo)
+                                                  [_pinhole(p["K2"]) for p in chunk], ro, bo, **kw)
             else:
                 geoms, infos = estimate_batch([p["kp1"] for p in chunk], [p["kp2"] for p in chunk], [p["d"][:, 0] for p in chunk],
                                               [p["d"][:, 1] for p in chunk], [_pinhole(p["K1"]) for p in chunk],
-                                              [_pinhole(p["K2"]) for p in chunk], ro, bo)
+                                              [_pinhole(p["K2"]) for p in chunk], ro, bo, **kw)
             ms = 1000.0 * (time.perf_counter() - t0) / max(len(chunk), 1)
-            for p, g, info in zip(chunk, geoms, infos):
-                info = dict(info)
-                info["runtime"] = ms
-                pose = g if five_point else g.pose   # estimate_relative_pose returns the CameraPose itself
-                results.append(result_record(experiment, info, pose.R, pose.t, p["R_gt"], p["t_gt"]))
+            planes = _per_budget_results(budgets, geoms, infos, ms)
+            for i, p in enumerate(chunk):
+                for k, gs, fs, ms_k in planes:
+                    info = dict(fs[i])
+                    info["runtime"] = ms_k
+                    if k is not None:
+                        info["iterations"] = k
+                    pose = gs[i] if five_point else gs[i].pose   # estimate_relative_pose returns the CameraPose itself
+                    results.append(result_record(experiment, info, pose.R, pose.t, p["R_gt"], p["t_gt"]))
     return results
 
 
@@ -251,15 +280,21 @@ def result_record_focal(experiment, info, pair, R_gt, t_gt, f1_gt, f2_gt):
 
 
 def evaluate_focal(h5, experiments, shared=True, iters=None, threshold=1.0, reproj_threshold=16.0, first=None, batch=4096,
-                   estimate_batch=None, device=0):
+                   estimate_batch=None, device=0, iterations_list=None):
     """eval_shared_f.py / eval_varying_f.py main loop for the monodepth focal estimators, batched.  Pairs with fewer than
-    6 (shared) / 7 (varying) correspondences are skipped as in the reference."""
+    6 (shared) / 7 (varying) correspondences are skipped as in the reference.  iterations_list: the graph mode, as in
+    `evaluate_calibrated` (one run per batch, one record per pair and budget, budget innermost; `info['runtime']` is the call's time
+    per pair divided by the number of budgets)."""
     from . import poselib
+    budgets = _graph_budgets(iterations_list)
+    if budgets is not None:
+        iters = budgets[-1]
+    kw = {} if budgets is None else {"budgets": budgets}
     if estimate_batch is None:
         fn = poselib.estimate_monodepth_shared_focal_relative_pose_batch if shared else poselib.estimate_monodepth_varying_focal_relative_pose_batch
 
-        def estimate_batch(k1, k2, a, b, ro, bo):
-            return fn(k1, k2, a, b, ro, bo, device=device)
+        def estimate_batch(k1, k2, a, b, ro, bo, **kw_):
+            return fn(k1, k2, a, b, ro, bo, device=device, **kw_)
     min_n = 6 if shared else 7
     pairs = list_pairs(h5, first)
     results = []
@@ -275,17 +310,21 @@ def evaluate_focal(h5, experiments, shared=True, iters=None, threshold=1.0, repr
             t0 = time.perf_counter()
             if six_point:
                 out, infos = poselib.estimate_shared_focal_relative_pose_batch([p["kp1"] for p in chunk], [p["kp2"] for p in chunk], None, ro, bo,
-                                                                               device=device)
+                                                                               device=device, **kw)
             else:
                 out, infos = estimate_batch([p["kp1"] for p in chunk], [p["kp2"] for p in chunk], [p["d"][:, 0] for p in chunk],
-                                            [p["d"][:, 1] for p in chunk], ro, bo)
+                                            [p["d"][:, 1] for p in chunk], ro, bo, **kw)
             ms = 1000.0 * (time.perf_counter() - t0) / max(len(chunk), 1)
-            for p, ip, info in zip(chunk, out, infos):
-                info = dict(info)
-                info["runtime"] = ms
+            planes = _per_budget_results(budgets, out, infos, ms)
+            for i, p in enumerate(chunk):
                 f1_gt = (p["K1"][0, 0] + p["K1"][1, 1]) / 2
                 f2_gt = (p["K2"][0, 0] + p["K2"][1, 1]) / 2
-                results.append(result_record_focal(experiment, info, ip, p["R_gt"], p["t_gt"], f1_gt, f2_gt))
+                for k, ips, fs, ms_k in planes:
+                    info = dict(fs[i])
+                    info["runtime"] = ms_k
+                    if k is not None:
+                        info["iterations"] = k
+                    results.append(result_record_focal(experiment, info, ips[i], p["R_gt"], p["t_gt"], f1_gt, f2_gt))
     return results
 
 

@@ -37,20 +37,27 @@ class BatchPipeline:
                 self._handles.append(h)
         return h
 
-    def submit(self, kind, x1, x2, d1, d2, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
-        """host (numpy) buffers; returns a Future of (records, mask) exactly as Handle.estimate_batch returns them"""
+    def submit(self, kind, x1, x2, d1, d2, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True, budgets=None):
+        """host (numpy) buffers; returns a Future of (records, mask) exactly as Handle.estimate_batch returns them (budgets: as
+        Handle.estimate_batch_budgets)"""
         ro = ropt if isinstance(ropt, _capi.RansacOpt) else _capi.ransac_opt_from_dict(ropt)
         bo = bopt if isinstance(bopt, _capi.BundleOpt) else _capi.bundle_opt_from_dict(bopt)
+        if budgets is not None:
+            return self._pool.submit(lambda: self._handle().estimate_batch_budgets(kind, x1, x2, d1, d2, ro, bo, budgets, n_per_pair, cam1, cam2, want_mask))
         return self._pool.submit(lambda: self._handle().estimate_batch(kind, x1, x2, d1, d2, ro, bo, n_per_pair, cam1, cam2, want_mask))
 
     def submit_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ropt, bopt, n_per_pair=None, cam1=None, cam2=None,
-                      mask_ptr=None):
-        """device pointers (e.g. torch tensors' data_ptr()); returns a Future of the result records (numpy)"""
+                      mask_ptr=None, budgets=None):
+        """device pointers (e.g. torch tensors' data_ptr()); returns a Future of the result records (numpy).  budgets: records (C, batch); mask_ptr
+        is then (C, batch, n_max) bytes of this batch alone."""
         ropt = _capi.ransac_opt_from_dict(ropt) if isinstance(ropt, dict) else ropt  # as submit() does
         bopt = _capi.bundle_opt_from_dict(bopt) if isinstance(bopt, dict) else bopt
 
         def run():
             h = self._handle()
+            if budgets is not None:
+                h.estimate_batch_budgets_device(kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ropt, bopt, budgets, n_per_pair, cam1, cam2, mask_ptr)
+                return h.fetch_budget_results(len(budgets), batch)
             h.estimate_batch_device(kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ropt, bopt, n_per_pair, cam1, cam2, mask_ptr)
             return h.fetch_results(batch)
         return self._pool.submit(run)
@@ -137,30 +144,38 @@ def close_auto_pipelines():
         p.close()
 
 
-def estimate_host(kind, x1, x2, d1, d2, ro, bo, n_per_pair=None, cam1=None, cam2=None, device=0, want_mask=True):
+def estimate_host(kind, x1, x2, d1, d2, ro, bo, n_per_pair=None, cam1=None, cam2=None, device=0, want_mask=True, budgets=None):
     """Handle.estimate_batch for a batch of any size (host buffers): one call up to PIPELINE_MIN pairs, pipelined chunks beyond.
-    Returns (records, mask) in pair order."""
+    Returns (records, mask) in pair order.  budgets (a list of iteration budgets, _capi.budget_list): records (C, B) and masks (C, B, N) — the
+    result at every budget from one run (Handle.estimate_batch_budgets); the chunks' slices are joined along the pair axis."""
     B = len(x1)
     bounds = chunk_bounds(B)
+    if len(bounds) == 1 and budgets is not None:
+        return _capi.default_handle(device).estimate_batch_budgets(kind, x1, x2, d1, d2, ro, bo, budgets, n_per_pair, cam1, cam2, want_mask)
     if len(bounds) == 1:
         return _capi.default_handle(device).estimate_batch(kind, x1, x2, d1, d2, ro, bo, n_per_pair, cam1, cam2, want_mask)
     pipe = _auto_pipe(device)
 
     def cut(a, lo, hi):
         return None if a is None else a[lo:hi]
-    futs = [pipe.submit(kind, x1[lo:hi], x2[lo:hi], cut(d1, lo, hi), cut(d2, lo, hi), ro, bo, cut(n_per_pair, lo, hi), cut(cam1, lo, hi), cut(cam2, lo, hi), want_mask)
+    futs = [pipe.submit(kind, x1[lo:hi], x2[lo:hi], cut(d1, lo, hi), cut(d2, lo, hi), ro, bo, cut(n_per_pair, lo, hi), cut(cam1, lo, hi), cut(cam2, lo, hi), want_mask, budgets)
             for lo, hi in bounds]
     parts = [f.result() for f in futs]
-    res = np.concatenate([p[0] for p in parts])
-    mask = np.concatenate([p[1] for p in parts]) if want_mask else None
+    axis = 0 if budgets is None else 1  # (with budgets a chunk's records are (C, pairs))
+    res = np.concatenate([p[0] for p in parts], axis=axis)
+    mask = np.concatenate([p[1] for p in parts], axis=axis) if want_mask else None
     return res, mask
 
 
-def estimate_device(kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ro, bo, n_per_pair=None, cam1=None, cam2=None, mask_ptr=None, device=0):
+def estimate_device(kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ro, bo, n_per_pair=None, cam1=None, cam2=None, mask_ptr=None, device=0,
+                    budgets=None):
     """The same on device pointers ([batch][n_max][2] / [batch][n_max] float64, mask [batch][n_max] bytes): chunks are pointer offsets into the
     caller's buffers.  Only called for batches beyond PIPELINE_MIN; the caller has made sure the inputs are complete (stream synchronised).
-    Returns the records (numpy) in pair order."""
+    Returns the records (numpy) in pair order.  budgets: records (C, batch) and a mask of (C, batch, n_max) bytes, whose planes a chunk cannot
+    reach by a pointer offset: the batch is then ONE call on a handle of the pipeline."""
     pipe = _auto_pipe(device)
+    if budgets is not None:
+        return pipe.submit_device(kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ro, bo, n_per_pair, cam1, cam2, mask_ptr, budgets).result()
 
     def cut(a, lo, hi):
         return None if a is None else a[lo:hi]

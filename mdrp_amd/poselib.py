@@ -191,6 +191,27 @@ def _camera_records(c, B):
 
 
 # ------------------------------------------------------------------------------------------------ batch API
+# budgets=[K_0 < ... < K_{C-1}] on a *_batch entry point: the result at every iteration budget from ONE run (include/mdrp.h), each bit
+# for bit what the call with max_iterations = K_c returns.  ransac_opt['max_iterations'] is set to the last budget when absent and must equal it
+# when present (ValueError, as for an invalid list: checked before anything else).  The return value gains a leading budget axis: the two lists
+# become lists over the budgets of today's lists (geometries[c][i], infos[c][i]); as_arrays and the torch form return records (C, B) and masks
+# (C, B, N).
+def _budget_args(ransac_opt, budgets):
+    """(ransac option dict, uint64 budgets or None)"""
+    if budgets is None:
+        return ransac_opt, None
+    ks, ro = _capi.budget_list(budgets, ransac_opt)
+    return ro, ks
+
+
+def _per_budget(budgets, res, mask, build):
+    """build(records (B,), masks (B, N)) -> (objects, infos): once, or per budget plane"""
+    if budgets is None:
+        return build(res, mask)
+    parts = [build(res[c], mask[c]) for c in range(len(res))]
+    return [p[0] for p in parts], [p[1] for p in parts]
+
+
 def _stack(points1, points2, depth1, depth2):
     """list of ragged pairs or already-stacked arrays -> padded (B,N,2),(B,N,2),(B,N),(B,N), n_per_pair"""
     if isinstance(points1, np.ndarray) and points1.ndim == 3:
@@ -209,13 +230,14 @@ def _stack(points1, points2, depth1, depth2):
 
 
 def estimate_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, cameras1, cameras2, ransac_opt=None,
-                                           bundle_opt=None, device=0, as_arrays=False):
+                                           bundle_opt=None, device=0, as_arrays=False, budgets=None):
     """B calibrated pairs at once.  cameras1/2: one Camera|dict for all pairs, or a list of B.  Returns
     (list[MonoDepthTwoViewGeometry], list[info dict]) — or, with as_arrays=True, (records, inlier masks, n_per_pair) as numpy arrays
     (_capi.RESULT_DTYPE; (B, N) uint8): building B Python objects and B lists of N bools costs more than the estimate itself beyond
     a few thousand pairs.  A host batch is ONE call whatever its size: the C side copies the correspondences in 256-pair slices on a copy stream
     beside the first kernels of the slices before them (MDRP_PIPELINE_MIN=<pairs> brings back the chunked two-in-flight path of rounds 4-5,
-    mdrp_amd.pipeline; results identical to sequential chunk calls)."""
+    mdrp_amd.pipeline; results identical to sequential chunk calls).  budgets: see _budget_args above."""
+    ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     x1, x2, d1, d2, ns = _stack(points2D_1, points2D_2, depth_1, depth_2)
     B = len(ns)
 
@@ -223,28 +245,30 @@ def estimate_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, dept
         return _camera_records(c, B)
 
     res, mask = pipeline.estimate_host(_capi.CALIB, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, cams(cameras1), cams(cameras2), device)
+                                       _capi.bundle_opt_from_dict(bundle_opt), ns, cams(cameras1), cams(cameras2), device, budgets=budgets)
     if as_arrays:
         return res, mask, ns
-    return [_geometry_from_model(r["model"]) for r in res], [_info(res[i], mask[i], ns[i]) for i in range(B)]
+    return _per_budget(budgets, res, mask, lambda r, m: ([_geometry_from_model(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(B)]))
 
 
-def _focal_batch(kind, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays=False):
+def _focal_batch(kind, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays=False, budgets=None):
+    ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     x1, x2, d1, d2, ns = _stack(points2D_1, points2D_2, depth_1, depth_2)
-    res, mask = pipeline.estimate_host(kind, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), ns, None, None, device)
+    res, mask = pipeline.estimate_host(kind, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), ns, None, None, device,
+                                       budgets=budgets)
     if as_arrays:
         return res, mask, ns
-    return [_pair_from_model(r["model"]) for r in res], [_info(res[i], mask[i], ns[i]) for i in range(len(ns))]
+    return _per_budget(budgets, res, mask, lambda r, m: ([_pair_from_model(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(len(ns))]))
 
 
 def estimate_monodepth_shared_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, ransac_opt=None,
-                                                        bundle_opt=None, device=0, as_arrays=False):
-    return _focal_batch(_capi.SHARED_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays)
+                                                        bundle_opt=None, device=0, as_arrays=False, budgets=None):
+    return _focal_batch(_capi.SHARED_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets)
 
 
 def estimate_monodepth_varying_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, ransac_opt=None,
-                                                         bundle_opt=None, device=0, as_arrays=False):
-    return _focal_batch(_capi.VARYING_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays)
+                                                         bundle_opt=None, device=0, as_arrays=False, budgets=None):
+    return _focal_batch(_capi.VARYING_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets)
 
 
 # ------------------------------------------------------------------------------------------------ reference signatures
@@ -483,8 +507,9 @@ def _check_baseline_options(ransac_opt):
         raise NotImplementedError("real_focal_check (FundamentalEstimator drops models without real focal lengths) is not built")
 
 
-def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ransac_opt=None, bundle_opt=None, device=0):
-    """B calibrated pairs through the 5-point estimator.  Returns (list[CameraPose], list[info dict])."""
+def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ransac_opt=None, bundle_opt=None, device=0, budgets=None):
+    """B calibrated pairs through the 5-point estimator.  Returns (list[CameraPose], list[info dict]).  budgets: see _budget_args."""
+    ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     _check_baseline_options(ransac_opt)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
     B = len(ns)
@@ -493,17 +518,19 @@ def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ran
         return _camera_records(c, B)
 
     res, mask = pipeline.estimate_host(_capi.RELPOSE_5PT, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, cams(cameras1), cams(cameras2), device)
-    return [CameraPose(r["model"]["q"].copy(), r["model"]["t"].copy()) for r in res], [_info(res[i], mask[i], ns[i]) for i in range(B)]
+                                       _capi.bundle_opt_from_dict(bundle_opt), ns, cams(cameras1), cams(cameras2), device, budgets=budgets)
+    return _per_budget(budgets, res, mask, lambda r, m: ([CameraPose(q["model"]["q"].copy(), q["model"]["t"].copy()) for q in r],
+                                                         [_info(r[i], m[i], ns[i]) for i in range(B)]))
 
 
-def estimate_fundamental_batch(points2D_1, points2D_2, ransac_opt=None, bundle_opt=None, device=0):
-    """B pairs through the 7-point estimator.  Returns (list[3 x 3 ndarray], list[info dict])."""
+def estimate_fundamental_batch(points2D_1, points2D_2, ransac_opt=None, bundle_opt=None, device=0, budgets=None):
+    """B pairs through the 7-point estimator.  Returns (list[3 x 3 ndarray], list[info dict]).  budgets: see _budget_args."""
+    ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     _check_baseline_options(ransac_opt)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
     res, mask = pipeline.estimate_host(_capi.FUNDAMENTAL_7PT, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, None, None, device)
-    return [_capi.model_to_fundamental(r["model"]) for r in res], [_info(res[i], mask[i], ns[i]) for i in range(len(ns))]
+                                       _capi.bundle_opt_from_dict(bundle_opt), ns, None, None, device, budgets=budgets)
+    return _per_budget(budgets, res, mask, lambda r, m: ([_capi.model_to_fundamental(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(len(ns))]))
 
 
 def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, ransac_opt={}, bundle_opt={}, initial_pose=None):
@@ -564,21 +591,25 @@ def _pp_records(pp, B):
     return rec, pp
 
 
-def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, ransac_opt=None, bundle_opt=None, device=0):
+def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, ransac_opt=None, bundle_opt=None, device=0, budgets=None):
     """B pairs through the 6-point shared-focal estimator.  pp: one principal point for all pairs or (B, 2).
-    Returns (list[ImagePair], list[info dict])."""
+    Returns (list[ImagePair], list[info dict]).  budgets: see _budget_args."""
+    ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     _check_baseline_options(ransac_opt)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
     B = len(ns)
     rec, ppb = _pp_records(pp, B)
     res, mask = pipeline.estimate_host(_capi.SHARED_6PT, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, rec, rec, device)
-    out = []
-    for i, r in enumerate(res):
-        f = float(r["model"]["f1"])
-        cam = Camera("SIMPLE_PINHOLE", [f, float(ppb[i, 0]), float(ppb[i, 1])])
-        out.append(ImagePair(CameraPose(r["model"]["q"].copy(), r["model"]["t"].copy()), cam, Camera("SIMPLE_PINHOLE", [f, float(ppb[i, 0]), float(ppb[i, 1])])))
-    return out, [_info(res[i], mask[i], ns[i]) for i in range(B)]
+                                       _capi.bundle_opt_from_dict(bundle_opt), ns, rec, rec, device, budgets=budgets)
+
+    def build(res, mask):
+        out = []
+        for i, r in enumerate(res):
+            f = float(r["model"]["f1"])
+            cam = Camera("SIMPLE_PINHOLE", [f, float(ppb[i, 0]), float(ppb[i, 1])])
+            out.append(ImagePair(CameraPose(r["model"]["q"].copy(), r["model"]["t"].copy()), cam, Camera("SIMPLE_PINHOLE", [f, float(ppb[i, 0]), float(ppb[i, 1])])))
+        return out, [_info(res[i], mask[i], ns[i]) for i in range(B)]
+    return _per_budget(budgets, res, mask, build)
 
 
 def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp=None, ransac_opt={}, bundle_opt={}, initial_image_pair=None):
@@ -631,14 +662,15 @@ def _torch_handle(dev, stream_ptr):
 
 
 def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras1=None, cameras2=None, ransac_opt=None,
-                         bundle_opt=None, n_per_pair=None):
+                         bundle_opt=None, n_per_pair=None, budgets=None):
     """Batch that already lives on the GPU (e.g. matcher output): `points2D_*` (B, N, 2) and `depth_*` (B, N) float64 torch
     tensors on a ROCm device; the work is queued on that device's CURRENT torch stream — including torch's default
     (null) stream — so it is ordered after whatever produced the inputs there and before later consumers of the mask;
     nothing crosses PCIe except the 136-byte result records.  kind: "calibrated" | "shared_focal" | "varying_focal".
     Returns (records: numpy structured array with `model`, `refinements`, `iterations`, `num_inliers`, `inlier_ratio`,
     `model_score`; inlier mask: (B, N) uint8 tensor on the device).  Ragged batches: pad and pass `n_per_pair`
-    (sequence, numpy array or tensor on any device)."""
+    (sequence, numpy array or tensor on any device).  budgets (see _budget_args): records (C, B) and a (C, B, N) mask tensor."""
+    ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     import torch
     kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
     k = kinds[kind] if isinstance(kind, str) else int(kind)
@@ -660,6 +692,12 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
     if k == _capi.CALIB:
         cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
     with torch.cuda.device(x1.device):
+        if budgets is not None:
+            mask = torch.zeros((len(budgets), B, N), dtype=torch.uint8, device=x1.device)
+            h.estimate_batch_budgets_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), B, N,
+                                            _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), budgets, n_per_pair, cams1, cams2,
+                                            mask.data_ptr())
+            return h.fetch_budget_results(len(budgets), B), mask
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
         h.estimate_batch_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), B, N,
                                 _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), n_per_pair, cams1, cams2,
