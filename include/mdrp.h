@@ -139,7 +139,7 @@ int mdrp_create_on_stream_(int device, void *stream, mdrp_handle **out, int abi_
 void mdrp_destroy(mdrp_handle *h);
 const char *mdrp_last_error(void);
 /* "mdrp-hip <ver> (gfx950) MDRP_SRC_HASH=<16 hex digits>": the hash covers mdrp_capi.hip, mdrp_kernels.h, mdrp_math.h,
- * mdrp_classic.h, mdrp_classic_math.h, mdrp_frontend.h and this header as they were when the library was built (mdrp_amd/build.py source_hash()) */
+ * mdrp_classic.h, mdrp_classic_math.h, mdrp_frontend.h, mdrp_schedule.h and this header as they were when the library was built (mdrp_amd/build.py source_hash()) */
 const char *mdrp_version(void);
 /* (major << 16) | minor of the structs and entry points in this header = 0x00000006.  mdrp_ransac_opt grew from 72 to 88 bytes in
  * 0.4; 0.5 made the version check involuntary: handles are created through mdrp_create_ / mdrp_create_on_stream_, which take the host's

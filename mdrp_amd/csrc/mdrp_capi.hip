@@ -5,6 +5,7 @@
 #include "mdrp_kernels.h"
 #include "mdrp_classic.h"
 #include "mdrp_frontend.h"
+#include "mdrp_schedule.h"
 // MDRP_SPLIT_TU (the default build): the k_final family and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -139,8 +140,7 @@ struct mdrp_handle {
     Stream copy_stream;                // host-buffer calls: the H2D slices of the correspondences
     Event ev_copied, ev_prepped, ev_solved6;
     DevBuf fuse;                       // fused tail: control words (64 B) | done_cnt[batch] | fin_done[batch] | ready[batch]
-    static constexpr int NC_MAX = 8; // chunks of a super-chunk
-    Event ev_lo, ev_tables, ev_sampled[2], ev_solved[NC_MAX], ev_scanned[NC_MAX];
+    Event ev_lo, ev_tables, ev_sampled[2], ev_solved[sched::NC_MAX], ev_scanned[sched::NC_MAX]; // per chunk of a super-chunk
     int num_cu = 256;
     // persistent device buffers
     DevBuf pts, dep, st;
@@ -287,38 +287,17 @@ int solver_for(int kind, int est_shift) {
     return kind == MDRP_SHARED_FOCAL ? SOLVER_SHARED : SOLVER_VARYING;
 }
 
-int model_slots(int kind) { return kind == MDRP_RELPOSE_5PT ? 12 : (kind == MDRP_SHARED_6PT ? 16 : 4); } // model slots per sample
-int sample_size(int kind) { return kind == MDRP_RELPOSE_5PT ? 5 : (kind == MDRP_SHARED_6PT ? 6 : (kind == MDRP_FUNDAMENTAL_7PT ? 7 : 3)); }
-
-// MDRP_CHUNKS: the leading chunk lengths of a run's first super-chunk, its positive entries (at most NC_MAX - 1).  False where it is
-// not set: run_pass chooses them.
-bool env_chunks(std::vector<uint64_t> &lead) {
-    lead.clear();
-    const char *e = getenv("MDRP_CHUNKS");
-    if (!e) return false;
-    const std::string spec = e;
-    size_t pos = 0;
-    while (pos < spec.size() && (int)lead.size() < mdrp_handle::NC_MAX - 1) {
-        const size_t q = spec.find(',', pos);
-        const long v = atol(spec.substr(pos, q == std::string::npos ? std::string::npos : q - pos).c_str());
-        if (v > 0) lead.push_back((uint64_t)v);
-        if (q == std::string::npos) break;
-        pos = q + 1;
-    }
-    return true;
-}
-
-// Every buffer of handle h that a pass allocates, with its bytes: run_pass ensures exactly these, estimate_device sizes its passes from them.
-// `lead`: the leading chunks of the run's first super-chunk.
+// Every buffer of handle h that a pass allocates, with its bytes: a Pass ensures exactly these, estimate_device sizes its passes from them.
+// `lead0`: the first leading chunk of the run's first super-chunk (0: none).
 struct PassScratch {
     std::vector<std::pair<DevBuf *, size_t>> bufs;
     size_t fuse; // (ensured by the super-chunk that runs the fused tail)
     // `params`: table states | cameras 1 | cameras 2 | table sizes | table of pair | n per pair | budgets (a budgets call: MAX_BUDGETS u64)
     size_t params, off_cam1, off_cam2, off_tn, off_tof, off_nper, off_bud;
-    // Reduce5 blocks of the 5-point solver (issue_solve): [pair][ceil(len / 64)] blocks of RED5_STRIDE x 64 doubles per solve, in two regions.
+    // Reduce5 blocks of the 5-point solver (Pass::solve): [pair][ceil(len / 64)] blocks of RED5_STRIDE x 64 doubles per solve, in two regions.
     // The first chunk of a super-chunk of several chunks is solved on the main stream while the second chunk's solver may run on `aux` (the
     // sliced host-buffer front: the main stream waits for a slice's k_prep only, not for the solver issued behind it), so it gets a region of
-    // its own behind the shared one.  Its length is a leading chunk that leaves at least as much again behind it: at most lead[0] and
+    // its own behind the shared one.  Its length is a leading chunk that leaves at least as much again behind it: at most lead0 and
     // chunk_cap / 2 iterations.
     size_t red5_blocks, red5_first_blocks; // per pair
     size_t total() const {
@@ -328,16 +307,16 @@ struct PassScratch {
     }
 };
 
-PassScratch pass_scratch(mdrp_handle *h, int kind, int batch, int n_max, int n_tables, int chunk_cap, const std::vector<uint64_t> &lead, int n_budgets = 0) {
-    const size_t b = (size_t)batch, n = (size_t)n_max, t = (size_t)n_tables, slots = b * chunk_cap * model_slots(kind);
+PassScratch pass_scratch(mdrp_handle *h, int kind, int batch, int n_max, int n_tables, int chunk_cap, uint64_t lead0, int n_budgets = 0) {
+    const size_t b = (size_t)batch, n = (size_t)n_max, t = (size_t)n_tables, slots = b * chunk_cap * sched::model_slots(kind);
     PassScratch z;
     z.fuse = 64 + 3 * sizeof(int32_t) * b;
     z.off_cam1 = sizeof(uint64_t) * t; z.off_cam2 = z.off_cam1 + sizeof(CamDev) * b; z.off_tn = z.off_cam2 + sizeof(CamDev) * b;
     z.off_tof = z.off_tn + sizeof(int32_t) * t; z.off_nper = z.off_tof + sizeof(int32_t) * b;
     z.off_bud = (z.off_nper + sizeof(int32_t) * b + 7) / 8 * 8; z.params = n_budgets ? z.off_bud + sizeof(uint64_t) * MAX_BUDGETS : z.off_nper + sizeof(int32_t) * b;
     z.red5_blocks = ((size_t)chunk_cap + 63) / 64;
-    z.red5_first_blocks = (std::min<uint64_t>(lead.empty() ? 0 : lead[0], (uint64_t)chunk_cap / 2) + 63) / 64;
-    const size_t samples = sizeof(uint32_t) * sample_size(kind) * t * chunk_cap, tags = sizeof(uint32_t) * slots, pair2 = sizeof(int32_t) * 2 * b;
+    z.red5_first_blocks = (std::min<uint64_t>(lead0, (uint64_t)chunk_cap / 2) + 63) / 64;
+    const size_t samples = sizeof(uint32_t) * sched::sample_size(kind) * t * chunk_cap, tags = sizeof(uint32_t) * slots, pair2 = sizeof(int32_t) * 2 * b;
     z.bufs = { // (in the order of allocation: params_host is allocated behind params)
         {&h->pts, sizeof(double) * PT_STRIDE * b * n}, {&h->dep, kind >= MDRP_RELPOSE_5PT ? 0 : sizeof(double) * 2 * b * n}, {&h->st, sizeof(PairState) * b},
         {&h->samples[0], samples}, {&h->params, z.params},
@@ -358,8 +337,7 @@ PassScratch pass_scratch(mdrp_handle *h, int kind, int batch, int n_max, int n_t
     return z;
 }
 
-// one pass = a contiguous range of pairs that fits the scratch budget
-// `host` (or null): the caller's HOST buffers of this pass; x1 ... d2 are then the handle's device staging buffers, still to be filled
+// the caller's HOST buffers of a pass
 struct HostSrc { const double *x1, *x2, *d1, *d2; };
 // a budgets call: the budgets and, for this pass, row 0 of its pairs in the result and mask planes ([n][plane] records, [n][plane][n_max] bytes)
 struct BudgetOut { const uint64_t *budgets; int n; ResultDev *results; uint8_t *mask; int plane; };
@@ -379,151 +357,59 @@ int check_budgets(const mdrp_ransac_opt *ro, const uint64_t *budgets, int n_budg
 }
 constexpr int HOST_SLICE_PAIRS = 256; // pairs per H2D slice of a host-buffer call (24.6 MB at N = 2000: ~0.5 ms of PCIe per slice)
 
-int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
-             int n_max, const int32_t *n_host, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
-             const mdrp_bundle_opt *bo, int chunk_cap, uint8_t *mask_dev, ResultDev *results_dev, const HostSrc *host, int batch_call,
-             const BudgetOut *bud = nullptr) {
-    hipStream_t s = h->stream;
-    const int est_shift = (kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0;
-    const bool classic = kind >= MDRP_RELPOSE_5PT;              // non-monodepth baselines (mdrp_classic.h)
-    const int mps = model_slots(kind), ssz = sample_size(kind);
+// one pass = a contiguous range of pairs that fits the scratch budget: what estimate_device hands run_pass (pointers offset to the pass's first pair)
+struct PassIn {
+    int kind;
+    const double *x1, *x2, *d1, *d2; // device memory; with `host`, the handle's staging buffers, still to be filled
+    int batch, n_max;
+    const int32_t *n_host;
+    const mdrp_camera *cam1, *cam2;
+    const mdrp_ransac_opt *ro;
+    const mdrp_bundle_opt *bo;
+    int chunk_cap;
+    uint8_t *mask_dev;
+    ResultDev *results_dev;
+    const HostSrc *host;  // (or null)
+    int batch_call;       // pairs of the whole API call
+    const BudgetOut *bud; // (or null)
+};
 
-    // ---- group pairs by correspondence count: one sample table per distinct N
-    std::vector<int32_t> table_of(batch), tab_n;
-    {
-        std::map<int32_t, int32_t> ids;
-        for (int i = 0; i < batch; ++i) {
-            auto it = ids.find(n_host[i]);
-            if (it == ids.end()) { it = ids.emplace(n_host[i], (int32_t)tab_n.size()).first; tab_n.push_back(n_host[i]); }
-            table_of[i] = it->second;
-        }
-    }
-    const int n_tables = (int)tab_n.size();
-    std::vector<uint64_t> tab_state(n_tables, ro->seed);
+// Chunk c of the super-chunk under way, for the pairs [p0, p0 + pc).  Every kernel of the front indexes its per-pair arrays as base[pair]: a RANGE
+// of pairs is the same launch on offset bases with r.batch = pc (the plans are per-launch scratch).  The whole batch is the range [0, batch); the
+// host-buffer front runs the first chunk and the second chunk's solver slice by slice while later slices are still on their way over PCIe.
+// Chunks alternate between two sets of tag lists / model counters / sample tables ([c & 1]); slots and triggers of different chunks are disjoint.
+struct ChunkView {
+    int c, p0, pc;
+    bool first_of_run; // no records yet: nothing to retire against
+    RunParams r;       // the pass's, with chunk_len, chunk_off and batch of this view
+    PairState *st;
+    double *pts, *dep, *slot_score;
+    Model *models;
+    int32_t *slot_inl, *model_count, *surv1, *surv2, *und_count;
+    uint32_t *samples, *tags, *tags_sorted, *tags_sorted_other, *tags_v;
+    unsigned long long *cand_stat;
+    uint4 *rfrag;
+    Trigger *trig;
+};
+// what goes on to a chunk's exact sweep: k_count's survivors, or k_bound's
+struct Survivors { const uint32_t *tags; const int32_t *count; };
 
-    // iterations that certainly run: the reference cannot stop before min_iterations + 1 (or max_iterations)
-    const uint64_t certain = ro->max_iterations == 0 ? 1 : std::min<uint64_t>(ro->max_iterations, ro->min_iterations + 1);
-    // A SUPER-CHUNK is a range of iterations that shares one LO + walk pass and one host read-back; it is swept in one or
-    // more CHUNKS (solve / count / bound / score / scan launch trains).  Inside the certain range nothing can stop, so the
-    // first super-chunk is split into a short chunk (128 iterations) that establishes the records and the rest, whose
-    // hypotheses are retired against those records by k_count (MFMA) and k_bound (fp32) unless they might break one.
-    // Beyond the certain range a super-chunk is one chunk sized by the largest remaining dynamic_max_iter.
-    // leading chunk lengths of the first super-chunk; the last chunk takes the rest.  The first chunk has no records to
-    // retire anything against, so it is scored exactly in full: keep it short.  Every later chunk goes through k_count /
-    // k_bound against the records of the chunks before it.  Measured on the benchmark shape: "128" 84.5 k pairs/s, "64" 82 k,
-    // "256" 82.5 k, "512" 82 k, "256,768" 79 k (every chunk costs ~10 launches and a solver hand-over).  The 7-point estimator gets a second leading
-    // chunk: at 50 % outliers one sample in 128 is outlier-free, so the records after 128 iterations are often those of a poor model and the rest of
-    // the run would be counted and bounded against a bar that retires little (round 6: k_bound 5.7 ms of a 16.4 ms step; with "128,1024" the bar
-    // the last 8848 iterations meet is that of 1152: 62.3 -> 87.3 k pairs/s; "128,512" 86.6 k, "256,1024" 87.6 k, "128,3300,3300" 78.3 k)
-    std::vector<uint64_t> lead;
-    const bool chunks_set = env_chunks(lead);
-    if (h->wish_kind >= 0 && hipEventQuery(h->ev_wish) == hipSuccess) { // an unfused run's sums have arrived
-        if (h->wish_host[1] > 0) h->seen_wish[h->wish_kind] = (double)h->wish_host[0] / (double)h->wish_host[1];
-        h->wish_kind = -1;
-    }
-    if (!chunks_set) {
-        // Round 6, with the two-phase count: at 50 % outliers the step is flat in the first chunk's length from 128 to 512 iterations (calibrated P3P
-        // 8.45-8.49 / 8.44-8.55 / 8.40-8.41 / 8.51-8.66 ms at 128 / 256 / 384 / 512; shared focal 8.05 -> 7.99 at 256 or 384) — what a longer first
-        // chunk costs in exact scoring it returns as a tighter bar — but NOT at other outlier ratios: one 3-point sample in 64 is outlier-free at
-        // 75 % outliers, one in 300 at 85 %, and a pair whose first chunk holds none sends the whole rest of its run through the fp32 bound and the
-        // exact sweep: 75 % outliers 124 k pairs/s with 128, 142 k with 256, 147 k with 384; 85 %: 78 k / 93 k / 104 k (136 k with 1024).  The
-        // outlier-free shape pays for it the other way round (every hypothesis of the first chunk is a good one and is scored in full: 72.3 k with
-        // 128, 71.1 k with 256, 69.5 k with 384).  Default: 256 for the 3-point estimators where the run is long enough to pay for it (a sixteenth of
-        // the iterations that certainly run, between 128 and 256), up to 512 for the 5-point one by the same rule (solver-bound: flat), 128,1024 for the 7-point one
-        // (above), 128 for the 6-point one; MDRP_CHUNKS=384 or 128,1024 for data with fewer than one inlier in four.
-        if (kind == MDRP_FUNDAMENTAL_7PT) lead = {128, 1024};
-        else if (kind == MDRP_SHARED_6PT) lead = {128};
-        else if (kind == MDRP_RELPOSE_5PT) lead = {std::min<uint64_t>(512, std::max<uint64_t>(128, certain / 16 / 64 * 64))};
-        else {
-            lead = {std::min<uint64_t>(256, std::max<uint64_t>(128, certain / 16 / 64 * 64))};
-            // ... and where the handle's previous call with this estimator (kind 0..2 here) has results to go by: the mean over its pairs of what each
-            // would have liked (first_chunk_wish, mdrp_kernels.h: 6 / r^3 iterations for the pair's inlier ratio r, between 256 and 1024; 128 for nearly
-            // outlier-free pairs) — the lengths the sweeps above found best at 0, 50, 75 and 85 % outliers, and for a batch that mixes them (20 / 50 / 70 /
-            // 85 % by pair: 93.7 k pairs/s at 128, 101 k at 256, 105 k at 384-512, 104 k at 1024).  A long run only (the first chunk stays under an
-            // eighth of it).
-            if (h->seen_wish[kind] >= 0.0 && certain >= 8192)
-                lead[0] = (uint64_t)std::min(1024.0, std::max(128.0, std::ceil(h->seen_wish[kind] / 64.0) * 64.0));
-        }
-    }
-
-    const int n_bud = bud ? bud->n : 0;
-    const PassScratch sz = pass_scratch(h, kind, batch, n_max, n_tables, chunk_cap, lead, n_bud);
-    int rc;
-    for (const auto &b : sz.bufs) {
-        if ((rc = b.first->ensure(b.second))) return rc; // (0 bytes: nothing to allocate)
-        // the small per-call inputs travel as one block (six pageable copies cost ~60 us of an idle GPU in front of k_prep)
-        if (b.first == &h->params && h->params_host_cap < sz.params) {
-            h->params_host.reset(); h->params_host_cap = 0;
-            HIPCHK(hipHostMalloc((void **)&h->params_host.v, sz.params + sz.params / 2, hipHostMallocDefault));
-            h->params_host_cap = sz.params + sz.params / 2;
-        }
-    }
-    unsigned char *pd = h->params.as<unsigned char>();
-    uint64_t *d_table_state = reinterpret_cast<uint64_t *>(pd);
-    CamDev *d_cams1 = reinterpret_cast<CamDev *>(pd + sz.off_cam1), *d_cams2 = reinterpret_cast<CamDev *>(pd + sz.off_cam2);
-    int32_t *d_table_n = reinterpret_cast<int32_t *>(pd + sz.off_tn), *d_table_of = reinterpret_cast<int32_t *>(pd + sz.off_tof),
-            *d_nper = reinterpret_cast<int32_t *>(pd + sz.off_nper);
-    Counters *cnt = h->counters.as<Counters>();
-    const size_t groups_max = ((size_t)n_max + 15) / 16;
-    const int trig_cap = chunk_cap;
-
-    {
-        unsigned char *ph = h->params_host; // free: the previous call on this handle ended with a stream synchronisation
-        std::memcpy(ph, tab_state.data(), sizeof(uint64_t) * n_tables);
-        const bool cams = kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT;
-        // MDRP_SHARED_6PT reads the principal point from cam1 only (include/mdrp.h): cam2 may be NULL there
-        if (cams) { std::memcpy(ph + sz.off_cam1, cam1, sizeof(CamDev) * batch); std::memcpy(ph + sz.off_cam2, cam2 ? cam2 : cam1, sizeof(CamDev) * batch); }
-        else std::memset(ph + sz.off_cam1, 0, 2 * sizeof(CamDev) * (size_t)batch);
-        std::memcpy(ph + sz.off_tn, tab_n.data(), sizeof(int32_t) * n_tables);
-        std::memcpy(ph + sz.off_tof, table_of.data(), sizeof(int32_t) * batch);
-        std::memcpy(ph + sz.off_nper, n_host, sizeof(int32_t) * batch);
-        if (bud) std::memcpy(ph + sz.off_bud, bud->budgets, sizeof(uint64_t) * n_bud);
-        HIPCHK(hipMemcpyAsync(pd, ph, sz.params, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(hipEventRecord(h->ev_tables, s)); // sample tables can be drawn from here on
-
-    RunParams rp;
-    std::memset(&rp, 0, sizeof rp);
-    rp.kind = kind; rp.solver = solver_for(kind, est_shift); rp.est_shift = est_shift;
-    rp.score_initial = ro->score_initial_model ? 1 : 0;
-    rp.batch = batch; rp.n_max = n_max;
-    rp.max_iterations = ro->max_iterations; rp.min_iterations = ro->min_iterations;
-    rp.dyn_mult = ro->dyn_num_trials_mult; rp.log_prob_missing = std::log(1.0 - ro->success_prob);
-    rp.weight_sampson = ro->monodepth_weight_sampson > 0.0f ? (double)ro->monodepth_weight_sampson : 0.0; // the wrappers hand max(ws, 0) on (@0x2246e6)
-    rp.final_max_it = (int)std::min<uint64_t>(bo->max_iterations, 1u << 30); rp.final_loss = bo->loss_type;
-    rp.grad_tol = bo->gradient_tol; rp.step_tol = bo->step_tol; rp.lambda0 = bo->initial_lambda;
-    rp.lambda_min = bo->min_lambda; rp.lambda_max = bo->max_lambda;
-    rp.chunk_len = chunk_cap; rp.chunk_off = 0; rp.slot_stride = chunk_cap * mps; rp.super_len = chunk_cap; rp.chunk_start = 0;
-    rp.mps = mps; rp.sample_sz = ssz;
-
-    // normalisation, record layout, MFMA fragments and pair states of the pairs [p0, p0 + pc) (one workgroup per pair, bases offset by p0)
-    auto launch_prep = [&](int p0, int pc, hipStream_t ps_) {
-        const size_t o2 = (size_t)2 * p0 * n_max, o1 = (size_t)p0 * n_max;
-        double *pts_p = h->pts.as<double>() + o1 * PT_STRIDE;
-        uint4 *rfrag_p = h->rfrag.as<uint4>() + (size_t)p0 * groups_max * 64;
-        if (classic)
-            hipLaunchKernelGGL(kc_prep, dim3(pc), dim3(256), 0, ps_, rp, x1 + o2, x2 + o2, d_nper + p0, d_table_of + p0, d_cams1 + p0, d_cams2 + p0,
-                               ro->max_epipolar_error, bo->loss_scale, pts_p, h->st.as<PairState>() + p0, rfrag_p);
-        else
-            hipLaunchKernelGGL(k_prep, dim3(pc), dim3(256), 0, ps_, rp, x1 + o2, x2 + o2, d1 + o1, d2 + o1, d_nper + p0, d_table_of + p0, d_cams1 + p0, d_cams2 + p0,
-                               ro->max_epipolar_error, ro->max_reproj_error, bo->loss_scale, pts_p, h->dep.as<double>() + 2 * o1, h->st.as<PairState>() + p0, rfrag_p);
-    };
-    if (!host) { // device-resident inputs: everything is there (host buffers: the copies and k_prep are issued slice by slice below)
-        launch_prep(0, batch, s);
-        HIPCHK(hipGetLastError());
-    }
-    rp.inl_stat = classic ? nullptr : &cnt->progress.wish_sum;
-
-    // Run-time knobs (DESIGN.md 10 lists all of them): the stream pipeline, the fp32 bound stage, lanes per LM problem.
-    const bool lo_overlap = env_int("MDRP_LO_OVERLAP", 1) != 0; // three-stream pipeline; 0 = every kernel on the handle's stream
-    const bool use_bound = env_int("MDRP_BOUND", 1) != 0;       // fp32 lower-bound stage between k_count and the fp64 sweep
-    const bool score_split = env_int("MDRP_SCORE_SPLIT", 1) != 0; // exact sweeps after a run's first chunk: k_score_split; 0 = k_score
-    // lanes per LO problem: one wavefront when there are many short problems; four when the batch is small or the pairs are large (N = 5000:
-    // a one-wavefront problem is 4 ms long and the launch ends with its stragglers — 45.6 against 43.9 ms per 1024 varying-focal pairs)
-    // (chosen from the CALL's batch, not this pass's: the lane count fixes the LM's summation tree, and how a call is cut into passes depends on the
-    // memory that happens to be free — a pair must get the same record whatever pass it falls into)
-    const int lo_threads = env_int("MDRP_LO_THREADS", (batch_call >= 128 && n_max < 4096) ? 64 : 256);
-    const int final_threads = env_int("MDRP_FINAL_THREADS", batch_call >= 4096 ? 64 : 256);
+// A pass and the stages run_pass strings together.  Stages only issue work (launches, copies, memsets, events) on the stream they name; who waits for
+// whom is run_pass's business.
+struct Pass : PassIn {
+    mdrp_handle *const h;
+    const hipStream_t s; // the main stream
+    const int est_shift;
+    const bool classic; // non-monodepth baselines (mdrp_classic.h)
+    const int mps, ssz;
+    // Run-time knobs (DESIGN.md 10 lists all of them; defaults that depend on the call's shape: mdrp_schedule.h)
+    const bool lo_overlap = env_int("MDRP_LO_OVERLAP", 1) != 0;     // three-stream pipeline; 0 = every kernel on the handle's stream
+    const bool use_bound = env_int("MDRP_BOUND", 1) != 0;           // fp32 lower-bound stage between k_count and the fp64 sweep
+    const bool score_split = env_int("MDRP_SCORE_SPLIT", 1) != 0;   // exact sweeps after a run's first chunk: k_score_split; 0 = k_score
+    const int lo_threads = env_int("MDRP_LO_THREADS", sched::lo_lanes(batch_call, n_max));
+    const int final_threads = env_int("MDRP_FINAL_THREADS", sched::final_lanes(batch_call));
+    const int samp_threads = env_int("MDRP_SAMPLE_THREADS", ssz == 3 ? SAMP_THREADS : (ssz == 5 ? 512 : 256)); // ~ samples between two rejections
+    const int lo_blocks = h->num_cu * (lo_threads == 64 ? 8 : 2);
     // the inlier-only final refinement walks a compacted index of the inliers instead of masking every record (where the three lists fit 32 KiB of LDS)
     const int mask_index = lm_mask_index_on(n_max);
     // work lists of the classic LM (mdrp_classic.h ClmList)
@@ -540,12 +426,389 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
     // (fuse_disabled / fuse_retry_in are advanced once per API call in estimate_device, not per pass)
     // (a budgets call runs its tail unfused: the checkpoints are taken by the walk kernel, and their refinements are one launch of their own)
     const bool fuse_env = !bud && env_int("MDRP_FUSE_TAIL", ((kind == MDRP_CALIB && est_shift) || h->fuse_disabled) ? 0 : 1) != 0;
-    bool final_done = false;
-    // the final refinements of the pass's pairs on the main stream; the fused tail's (ready list, done flags, wait ticks, time-out counter), or
-    // (null, pairs to skip or null, 0, null)
-    // `problems` workgroups over the states `st_f` (run parameters `rf`): the pass's pairs, or the checkpoint problems of a budgets call
-    auto launch_final_of = [&](const RunParams &rf, int problems, PairState *st_f, uint8_t *mask_f, ResultDev *results_f, const int32_t *ready, int32_t *fin_done,
-                               unsigned long long ticks, unsigned long long *timeouts) {
+    const int n_bud = bud ? bud->n : 0;
+    const int trig_cap = chunk_cap;
+    const size_t groups_max = ((size_t)n_max + 15) / 16;
+
+    std::vector<int32_t> table_of, tab_n;
+    int n_tables = 0;
+    uint64_t certain = 0;
+    sched::Lead lead;
+    PassScratch sz;
+    RunParams rp;
+    // the `params` block on the device, and the counter block
+    unsigned char *pd = nullptr;
+    uint64_t *d_table_state = nullptr;
+    CamDev *d_cams1 = nullptr, *d_cams2 = nullptr;
+    int32_t *d_table_n = nullptr, *d_table_of = nullptr, *d_nper = nullptr;
+    Counters *cnt = nullptr;
+    // the super-chunk under way
+    uint64_t it0 = 0;
+    sched::Layout lay;
+    bool piped = false, fuse_tail = false, presampled[2] = {false, false};
+    hipStream_t aux = nullptr, aux2 = nullptr; // the handle's, or `s` where the super-chunk is not pipelined
+    int32_t *fz_ctl = nullptr, *fz_done = nullptr, *fz_fin = nullptr, *fz_ready = nullptr;
+    bool final_done = false; // the fused tail has run the final refinements
+
+    Pass(mdrp_handle *h_, const PassIn &in)
+        : PassIn(in), h(h_), s(h_->stream), est_shift((kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0), classic(kind >= MDRP_RELPOSE_5PT),
+          mps(sched::model_slots(kind)), ssz(sched::sample_size(kind)) {}
+
+    // sample tables, leading chunks and scratch of the pass
+    int plan_and_allocate() {
+        sched::group_tables(n_host, batch, table_of, tab_n);
+        n_tables = (int)tab_n.size();
+        certain = sched::certain_iterations(ro->max_iterations, ro->min_iterations);
+        const bool chunks_set = sched::parse_chunks(getenv("MDRP_CHUNKS"), lead);
+        if (h->wish_kind >= 0 && hipEventQuery(h->ev_wish) == hipSuccess) { // an unfused run's sums have arrived
+            if (h->wish_host[1] > 0) h->seen_wish[h->wish_kind] = (double)h->wish_host[0] / (double)h->wish_host[1];
+            h->wish_kind = -1;
+        }
+        if (!chunks_set) lead = sched::default_lead(kind, certain, kind <= MDRP_VARYING_FOCAL ? h->seen_wish[kind] : -1.0);
+        sz = pass_scratch(h, kind, batch, n_max, n_tables, chunk_cap, lead.first(), n_bud);
+        for (const auto &b : sz.bufs) {
+            if (int rc = b.first->ensure(b.second)) return rc; // (0 bytes: nothing to allocate)
+            // the small per-call inputs travel as one block (six pageable copies cost ~60 us of an idle GPU in front of k_prep)
+            if (b.first == &h->params && h->params_host_cap < sz.params) {
+                h->params_host.reset(); h->params_host_cap = 0;
+                HIPCHK(hipHostMalloc((void **)&h->params_host.v, sz.params + sz.params / 2, hipHostMallocDefault));
+                h->params_host_cap = sz.params + sz.params / 2;
+            }
+        }
+        pd = h->params.as<unsigned char>();
+        d_table_state = reinterpret_cast<uint64_t *>(pd);
+        d_cams1 = reinterpret_cast<CamDev *>(pd + sz.off_cam1); d_cams2 = reinterpret_cast<CamDev *>(pd + sz.off_cam2);
+        d_table_n = reinterpret_cast<int32_t *>(pd + sz.off_tn); d_table_of = reinterpret_cast<int32_t *>(pd + sz.off_tof);
+        d_nper = reinterpret_cast<int32_t *>(pd + sz.off_nper);
+        cnt = h->counters.as<Counters>();
+        return MDRP_OK;
+    }
+
+    // the per-call parameters in one H2D copy on the main stream, and the run parameters every kernel takes by value
+    int upload_params() {
+        unsigned char *ph = h->params_host; // free: the previous call on this handle ended with a stream synchronisation
+        const std::vector<uint64_t> tab_state(n_tables, ro->seed);
+        std::memcpy(ph, tab_state.data(), sizeof(uint64_t) * n_tables);
+        const bool cams = kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT;
+        // MDRP_SHARED_6PT reads the principal point from cam1 only (include/mdrp.h): cam2 may be NULL there
+        if (cams) { std::memcpy(ph + sz.off_cam1, cam1, sizeof(CamDev) * batch); std::memcpy(ph + sz.off_cam2, cam2 ? cam2 : cam1, sizeof(CamDev) * batch); }
+        else std::memset(ph + sz.off_cam1, 0, 2 * sizeof(CamDev) * (size_t)batch);
+        std::memcpy(ph + sz.off_tn, tab_n.data(), sizeof(int32_t) * n_tables);
+        std::memcpy(ph + sz.off_tof, table_of.data(), sizeof(int32_t) * batch);
+        std::memcpy(ph + sz.off_nper, n_host, sizeof(int32_t) * batch);
+        if (bud) std::memcpy(ph + sz.off_bud, bud->budgets, sizeof(uint64_t) * n_bud);
+        HIPCHK(hipMemcpyAsync(pd, ph, sz.params, hipMemcpyHostToDevice, s));
+
+        std::memset(&rp, 0, sizeof rp);
+        rp.kind = kind; rp.solver = solver_for(kind, est_shift); rp.est_shift = est_shift;
+        rp.score_initial = ro->score_initial_model ? 1 : 0;
+        rp.batch = batch; rp.n_max = n_max;
+        rp.max_iterations = ro->max_iterations; rp.min_iterations = ro->min_iterations;
+        rp.dyn_mult = ro->dyn_num_trials_mult; rp.log_prob_missing = std::log(1.0 - ro->success_prob);
+        rp.weight_sampson = ro->monodepth_weight_sampson > 0.0f ? (double)ro->monodepth_weight_sampson : 0.0; // the wrappers hand max(ws, 0) on (@0x2246e6)
+        rp.final_max_it = (int)std::min<uint64_t>(bo->max_iterations, 1u << 30); rp.final_loss = bo->loss_type;
+        rp.grad_tol = bo->gradient_tol; rp.step_tol = bo->step_tol; rp.lambda0 = bo->initial_lambda;
+        rp.lambda_min = bo->min_lambda; rp.lambda_max = bo->max_lambda;
+        rp.chunk_len = chunk_cap; rp.chunk_off = 0; rp.slot_stride = chunk_cap * mps; rp.super_len = chunk_cap; rp.chunk_start = 0;
+        rp.mps = mps; rp.sample_sz = ssz;
+        return MDRP_OK;
+    }
+
+    // normalisation, record layout, MFMA fragments and pair states of the pairs [p0, p0 + pc) (one workgroup per pair, bases offset by p0)
+    void prep(int p0, int pc, hipStream_t st_) {
+        const size_t o2 = (size_t)2 * p0 * n_max, o1 = (size_t)p0 * n_max;
+        double *pts_p = h->pts.as<double>() + o1 * PT_STRIDE;
+        uint4 *rfrag_p = h->rfrag.as<uint4>() + (size_t)p0 * groups_max * 64;
+        if (classic)
+            hipLaunchKernelGGL(kc_prep, dim3(pc), dim3(256), 0, st_, rp, x1 + o2, x2 + o2, d_nper + p0, d_table_of + p0, d_cams1 + p0, d_cams2 + p0,
+                               ro->max_epipolar_error, bo->loss_scale, pts_p, h->st.as<PairState>() + p0, rfrag_p);
+        else
+            hipLaunchKernelGGL(k_prep, dim3(pc), dim3(256), 0, st_, rp, x1 + o2, x2 + o2, d1 + o1, d2 + o1, d_nper + p0, d_table_of + p0, d_cams1 + p0, d_cams2 + p0,
+                               ro->max_epipolar_error, ro->max_reproj_error, bo->loss_scale, pts_p, h->dep.as<double>() + 2 * o1, h->st.as<PairState>() + p0, rfrag_p);
+    }
+
+    // the chunks of the super-chunk at it0, its cleared counters, and whether it is pipelined over the streams and ends with the fused tail
+    int begin_super_chunk(uint64_t max_needed) {
+        lay = sched::super_chunk_layout(it0, certain, chunk_cap, lead, max_needed, ro->max_iterations);
+        if (it0 == 0) h->first_chunk = (int64_t)lay.lens[0];
+        rp.chunk_start = it0; rp.super_len = (int)lay.super_len;
+        HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
+        if (it0 == 0) HIPCHK(hipMemsetAsync(h->cand_stat.p, 0, sizeof(unsigned long long) * 2 * batch, s));
+        piped = lay.n_chunks > 1 && lo_overlap;
+        fuse_tail = fuse_env && piped && it0 + lay.super_len >= ro->max_iterations;
+        if (fuse_tail) {
+            if (int rc = h->fuse.ensure(sz.fuse)) return rc;
+            fz_ctl = h->fuse.as<int32_t>(); fz_done = fz_ctl + 16; fz_fin = fz_done + batch; fz_ready = fz_fin + batch;
+        }
+        aux = piped ? h->aux_stream : s; aux2 = piped ? h->aux_stream2 : s;
+        presampled[0] = presampled[1] = false;
+        return MDRP_OK;
+    }
+
+    void samples(hipStream_t st_, int len_, uint32_t *smp_) {
+        if (ssz == 6) hipLaunchKernelGGL(kc_samples<6>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
+        else if (ssz == 5) hipLaunchKernelGGL(kc_samples<5>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
+        else if (ssz == 7) hipLaunchKernelGGL(kc_samples<7>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
+        else hipLaunchKernelGGL(k_samples, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
+    }
+    // The sample tables of a run's first two chunks do not depend on anything but (seed, N): they are drawn on the (still idle)
+    // LO stream while k_prep runs, so the one-workgroup-per-table sampler (0.18 ms for 10^4 samples) is off the solver's path.
+    int presample() {
+        HIPCHK(hipStreamWaitEvent(aux2, h->ev_tables, 0));
+        for (int c = 0; c < 2 && c < lay.n_chunks; ++c) {
+            samples(aux2, (int)lay.lens[c], h->samples[c & 1].as<uint32_t>());
+            HIPCHK(hipEventRecord(h->ev_sampled[c], aux2));
+            presampled[c] = true;
+        }
+        return MDRP_OK;
+    }
+
+    ChunkView view(int c, int p0, int pc) const {
+        ChunkView v;
+        const bool odd = c & 1;
+        const size_t so = (size_t)p0 * rp.slot_stride, o1 = (size_t)p0 * n_max, q = (size_t)p0;
+        v.c = c; v.p0 = p0; v.pc = pc; v.first_of_run = it0 == 0 && c == 0;
+        v.r = rp; v.r.chunk_len = (int)lay.lens[c]; v.r.chunk_off = lay.offs[c]; v.r.batch = pc;
+        v.st = h->st.as<PairState>() + q; v.pts = h->pts.as<double>() + o1 * PT_STRIDE; v.dep = classic ? nullptr : h->dep.as<double>() + o1 * 2;
+        v.models = h->models.as<Model>() + so; v.slot_score = h->slot_score.as<double>() + so; v.slot_inl = h->slot_inl.as<int32_t>() + so;
+        v.samples = h->samples[odd].as<uint32_t>(); v.tags = h->tags[odd].as<uint32_t>() + so; v.tags_v = h->tags_v.as<uint32_t>() + so;
+        v.tags_sorted = h->tags_sorted[odd].as<uint32_t>() + so; v.tags_sorted_other = h->tags_sorted[!odd].as<uint32_t>() + so;
+        v.model_count = h->model_count[odd].as<int32_t>() + 2 * q; v.und_count = h->und_count.as<int32_t>() + 2 * q;
+        v.surv1 = h->surv_count.as<int32_t>() + q; v.surv2 = h->surv2_count.as<int32_t>() + q;
+        v.cand_stat = h->cand_stat.as<unsigned long long>() + 2 * q;
+        v.rfrag = h->rfrag.as<uint4>() + q * groups_max * 64; v.trig = h->triggers.as<Trigger>() + q * trig_cap;
+        return v;
+    }
+
+    // sample table (unless presampled) and minimal solver of the view on stream st_
+    int solve(const ChunkView &v, hipStream_t st_) {
+        const RunParams &r = v.r;
+        const int pc = v.pc;
+        HIPCHK(hipMemsetAsync(v.model_count, 0, sizeof(int32_t) * 2 * pc, st_));
+        if (v.c < 2 && presampled[v.c]) HIPCHK(hipStreamWaitEvent(st_, h->ev_sampled[v.c], 0));
+        else samples(st_, r.chunk_len, v.samples);
+        hipEvent_t v0, v1;
+        if (int rc = get_events(h, &v0, &v1, 5)) return rc;
+        HIPCHK(hipEventRecord(v0, st_));
+        struct Stop { hipEvent_t e; hipStream_t s; ~Stop() { (void)hipEventRecord(e, s); } } stop_{v1, st_}; // after the solver launch below
+        if (classic) {
+            const dim3 sgrid((r.chunk_len + 63) / 64, pc);
+            if (kind == MDRP_SHARED_6PT)
+                hipLaunchKernelGGL(kc_solve<CLASSIC_SHARED>, sgrid, dim3(64), 0, st_, r, v.st, v.samples, v.pts, v.models, v.slot_inl, v.tags, v.model_count);
+            else if (kind == MDRP_RELPOSE_5PT) {
+                // three kernels (mdrp_classic.h): null space and roots + poses at six wavefronts per CU, the elimination between them at three
+                // Invariant: two solves that may run at the same time never share a Reduce5 block.  A chunk's solve writes blocks
+                // [p0 * sgrid.x, (p0 + pc) * sgrid.x) of its region, and only the first chunk of a super-chunk of several chunks is ever solved
+                // beside another chunk's solver (the sliced front: chunk 0 on `s`, chunk 1 on `aux`): it alone uses the second region.  Every
+                // other solve is ordered behind the previous one by its stream or by ev_solved.
+                const bool first_region = v.c == 0 && lay.n_chunks > 1;
+                if (first_region && (size_t)sgrid.x > sz.red5_first_blocks) { g_err = "5-point first chunk longer than its Reduce5 region"; return MDRP_ERR_INVALID; }
+                double *red5 = h->red5.as<double>() + ((first_region ? (size_t)batch * sz.red5_blocks : 0) + (size_t)v.p0 * sgrid.x) * RED5_STRIDE * 64;
+                hipLaunchKernelGGL(kc_solve5_null, sgrid, dim3(64), SOLVE5N_LDS_BYTES, st_, r, v.st, v.samples, v.pts, red5);
+                hipLaunchKernelGGL(kc_solve5_reduce, sgrid, dim3(64), SOLVE5_LDS_BYTES, st_, r, v.st, red5);
+                hipLaunchKernelGGL(kc_solve5_roots, sgrid, dim3(64), SOLVE5B_LDS_BYTES, st_, r, v.st, v.samples, v.pts, red5, v.models, v.slot_inl, v.tags, v.model_count);
+            }
+            else
+                hipLaunchKernelGGL(kc_solve<CLASSIC_FUND>, sgrid, dim3(64), SOLVE7_LDS_BYTES, st_, r, v.st, v.samples, v.pts, v.models, v.slot_inl, v.tags, v.model_count);
+            return MDRP_OK;
+        }
+#define MDRP_SOLVE_LAUNCH(S)                                                                                                   \
+    hipLaunchKernelGGL(k_solve<S>, dim3((r.chunk_len + solve_threads(S) - 1) / solve_threads(S), pc), dim3(solve_threads(S)), 0, st_, r, v.st, v.samples, v.pts, v.dep, v.models, v.slot_inl, v.tags, v.model_count, 0, r.chunk_len)
+        switch (r.solver) {
+        case SOLVER_P3P: MDRP_SOLVE_LAUNCH(SOLVER_P3P); break;
+        case SOLVER_SHIFT: MDRP_SOLVE_LAUNCH(SOLVER_SHIFT); break;
+        case SOLVER_SHARED: MDRP_SOLVE_LAUNCH(SOLVER_SHARED); break;
+        default: MDRP_SOLVE_LAUNCH(SOLVER_VARYING); break;
+        }
+#undef MDRP_SOLVE_LAUNCH
+        return MDRP_OK;
+    }
+
+    // candidate counts on the matrix cores against the records of the chunks before this one; survivors only go on (tags_v, surv1)
+    int count(const ChunkView &v) {
+        unsigned long long *cstats = &cnt->progress.evals; // (and evals_mfma)
+        hipEvent_t c0, c1;
+        if (int rc = get_events(h, &c0, &c1, 1)) return rc;
+        // phase A: every hypothesis over the pair's leading tiles (all tiles where the records do not allow a split); phase B: the undecided
+        // ones over the rest (k_count, mdrp_kernels.h).  A run's first chunk has no record: phase A is the whole count, no phase B.
+        const bool two_phase = !v.first_of_run;
+        // The undecided list lives where this chunk's SORTED list will be written once the counts are done (k_sort_tags, below), the partial counts
+        // in the other parity's sorted list, whose last reader was the previous chunk's exact sweep: no scratch of their own.
+        uint32_t *tags_u = v.tags_sorted;
+        int32_t *und_part = reinterpret_cast<int32_t *>(v.tags_sorted_other), *cplan = h->cplan.as<int32_t>();
+        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.model_count, 2, CNT_WG_MODELS, cplan,
+                           v.surv1, (const int32_t *)nullptr, two_phase ? v.und_count : (int32_t *)nullptr); // (also clears the counters k_count appends to)
+        const dim3 cgrid((unsigned)v.pc * (unsigned)((v.r.chunk_len * mps + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
+        HIPCHK(hipEventRecord(c0, s));
+        MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, v.r, v.st, v.rfrag, v.models,
+                            v.tags, v.model_count, cplan, v.tags_v, v.surv1, cstats, (int32_t *)nullptr, (const int32_t *)nullptr,
+                            1, tags_u, und_part, v.und_count, (const int32_t *)nullptr, v.cand_stat);
+        if (two_phase) {
+            hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.und_count, 2, CNT_WG_MODELS, cplan,
+                               (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
+            MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, v.r, v.st, v.rfrag, v.models,
+                                tags_u, v.und_count, cplan, v.tags_v, v.surv1, cstats, (int32_t *)nullptr, (const int32_t *)nullptr,
+                                2, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, und_part, v.cand_stat);
+            h->count_launches++; // (mdrp_stats::count_launches counts kernel launches: a rocprof summary shows the same number)
+        }
+        HIPCHK(hipEventRecord(c1, s));
+        h->count_launches++;
+        return MDRP_OK;
+    }
+
+    // fp32 lower bound of the score for k_count's survivors; its survivors go back into the chunk's tag list
+    // (calls of a few pairs skip the stage: its lane-per-hypothesis record loop is 0.1 ms of latency, and k_score_w takes k_count's survivors at once;
+    // a run's first chunk has no records yet: nothing to retire)
+    int bound(const ChunkView &v, Survivors &sv) {
+        sv = Survivors{v.tags_v, v.surv1};
+        if (!(use_bound && batch_call > 16 && !v.first_of_run)) return MDRP_OK;
+        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.surv1, 1, BND_THREADS, h->cplan.as<int32_t>(), v.surv2, (const int32_t *)nullptr);
+        const dim3 bgrid((unsigned)v.pc * (unsigned)((v.r.chunk_len * mps + BND_THREADS - 1) / BND_THREADS));
+        unsigned long long *bstats = &cnt->progress.evals_bound;
+        hipEvent_t b0, b1;
+        if (int rc = get_events(h, &b0, &b1, 4)) return rc;
+        HIPCHK(hipEventRecord(b0, s));
+        MDRP_SWEEP_DISPATCH(k_bound, kind, bgrid, dim3(BND_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_v, v.surv1, h->cplan.as<int32_t>(), v.tags, v.surv2, bstats);
+        HIPCHK(hipEventRecord(b1, s));
+        sv = Survivors{v.tags, v.surv2};
+        return MDRP_OK;
+    }
+
+    // sort by candidate density, plan, exact fp64 sweep of the survivors between the events e0 and e1:
+    //   k_score_w      calls of few pairs: one WAVEFRONT per hypothesis — a lane per hypothesis is a 0.3 ms serial record loop however few there are
+    //   k_score_split  the survivors of k_bound (~93 per pair): 64 hypotheses per workgroup, each wavefront a quarter of the records
+    //   k_score        a run's first chunk: its sweep runs beside the second chunk's solver, where more and smaller sweep workgroups only wait longer
+    int score(const ChunkView &v, const Survivors &sv, hipEvent_t e0, hipEvent_t e1) {
+        const bool wave = batch_call <= SCORE_WAVE_MAX_PAIRS, split = !wave && score_split && !v.first_of_run;
+        const int models = v.r.chunk_len * mps;
+        int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * (size_t)batch + 2; // (the slice's plan uses the head of the buffer, `totals` stays where it is)
+        if (wave) hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, sv.count, 1, SCW_THREADS / 64, plan, (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
+        hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, sv.count, sv.tags, v.tags_sorted);
+        if (!wave) hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.model_count, plan, totals, split ? SPLIT_HYP : SCORE_THREADS);
+        HIPCHK(hipEventRecord(e0, s));
+        const long long capped = (long long)h->num_cu * 32; // k_score_w, k_score_split: surplus workgroups exit at once, a shortfall is taken by the item loop
+        if (wave) {
+            const long long ub = (long long)v.pc * ((models + SCW_THREADS / 64 - 1) / (SCW_THREADS / 64));
+            MDRP_SWEEP_DISPATCH(k_score_w, kind, dim3((unsigned)std::min(ub, capped)), dim3(SCW_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
+                                v.slot_score, v.slot_inl, plan);
+        } else if (split) {
+            const long long ub = (long long)v.pc * ((models + SPLIT_HYP - 1) / SPLIT_HYP + 1); // items: at most ceil(sparse / 64) + ceil(dense / 64) per pair
+            MDRP_SWEEP_DISPATCH(k_score_split, kind, dim3((unsigned)std::min(ub, capped)), dim3(SPLIT_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
+                                v.slot_score, v.slot_inl, plan, totals);
+        } else {
+            const dim3 grid((unsigned)v.pc * (unsigned)((models + SCORE_THREADS - 1) / SCORE_THREADS));
+            MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), SCORE_TILE_BYTES, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
+                                v.slot_score, v.slot_inl, plan, totals);
+        }
+        HIPCHK(hipEventRecord(e1, s));
+        h->sweep_launches++;
+        return MDRP_OK;
+    }
+
+    // ordered prefix over the iterations: LO triggers (four iterations per lane where the chunk is long: a 9872-iteration chunk is 39 steps of one
+    // wavefront instead of 154)
+    void scan(const ChunkView &v) {
+        unsigned long long *scan_stats = &cnt->progress.evals_sweep;
+#define MDRP_SCAN(M, I) hipLaunchKernelGGL((k_scan<M, I>), dim3(v.pc), dim3(64), 0, s, v.r, v.st, v.slot_score, v.slot_inl, v.trig, trig_cap, v.model_count, scan_stats)
+        if (mps == 16) MDRP_SCAN(16, 1);
+        else if (mps == 12) MDRP_SCAN(12, 1);
+        else if (v.r.chunk_len >= 1024) MDRP_SCAN(4, 4);
+        else MDRP_SCAN(4, 1);
+#undef MDRP_SCAN
+    }
+
+    // count -> bound -> sort -> plan -> exact score -> scan of the view, on the main stream
+    int sweep(const ChunkView &v) {
+        hipEvent_t e0, e1;
+        Survivors sv;
+        int rc;
+        if ((rc = get_events(h, &e0, &e1, 0)) || (rc = count(v)) || (rc = bound(v, sv)) || (rc = score(v, sv, e0, e1))) return rc;
+        scan(v);
+        return MDRP_OK;
+    }
+
+    // The first chunk of pairs [q0, q0 + qc) of the sliced front.  The 6-point solver (11.5 KB of scratch per lane) solves it on the solver stream
+    // too, behind the second chunk's slices: two of its dispatches at once on two queues need two whole-device scratch areas (~6 GB each) at the same
+    // time, and the runtime aborts the queue (out of resources) when it cannot have the second one.  The main stream sweeps behind that solve.
+    int first_chunk_of(int q0, int qc) {
+        const ChunkView v = view(0, q0, qc);
+        int rc;
+        if (kind != MDRP_SHARED_6PT) { if ((rc = solve(v, s))) return rc; }
+        else {
+            if ((rc = solve(v, aux))) return rc;
+            HIPCHK(hipEventRecord(h->ev_solved6, aux));
+            HIPCHK(hipStreamWaitEvent(s, h->ev_solved6, 0));
+        }
+        return sweep(v);
+    }
+    // Host buffers (MDRP_MEM_HOST) of a run's first super-chunk: the correspondences arrive slice by slice on the copy stream; k_prep and the second
+    // chunk's solver (the long one: 1.6 ms per 1024 pairs) of slice i run while slice i + 1 is on its way over PCIe.
+    // solved1: the second chunk's solver has been issued; swept0: pairs whose first chunk has been swept already.
+    int host_front(bool &solved1, int &swept0) {
+        int rc;
+        const bool sliced = piped && lay.n_chunks >= 2 && batch >= 2 * HOST_SLICE_PAIRS;
+        const int sl = sliced ? HOST_SLICE_PAIRS : batch;
+        for (int p0 = 0; p0 < batch; p0 += sl) {
+            const int pc = std::min(sl, batch - p0);
+            const size_t o2 = (size_t)2 * p0 * n_max, o1 = (size_t)p0 * n_max, n2 = sizeof(double) * 2 * (size_t)pc * n_max, n1 = sizeof(double) * (size_t)pc * n_max;
+            hipStream_t cs = sliced ? h->copy_stream : s;
+            HIPCHK(hipMemcpyAsync(const_cast<double *>(x1) + o2, host->x1 + o2, n2, hipMemcpyHostToDevice, cs));
+            HIPCHK(hipMemcpyAsync(const_cast<double *>(x2) + o2, host->x2 + o2, n2, hipMemcpyHostToDevice, cs));
+            if (host->d1 && host->d2) {
+                HIPCHK(hipMemcpyAsync(const_cast<double *>(d1) + o1, host->d1 + o1, n1, hipMemcpyHostToDevice, cs));
+                HIPCHK(hipMemcpyAsync(const_cast<double *>(d2) + o1, host->d2 + o1, n1, hipMemcpyHostToDevice, cs));
+            }
+            if (!sliced) { prep(p0, pc, s); break; }
+            // k_prep and the long solver of the slice on the solver stream, beside the next slices' copies (the main stream sweeps the first chunk)
+            HIPCHK(hipEventRecord(h->ev_copied, cs)); HIPCHK(hipStreamWaitEvent(aux, h->ev_copied, 0));
+            if (p0 == 0) HIPCHK(hipStreamWaitEvent(aux, h->ev_tables, 0)); // (the per-call parameters were uploaded on the main stream)
+            prep(p0, pc, aux);
+            HIPCHK(hipEventRecord(h->ev_prepped, aux));
+            if ((rc = solve(view(1, p0, pc), aux))) return rc;
+            // The first chunk is swept in TWO parts only: everything but the last slice as soon as the last-but-one slice is prepared (beside the
+            // last slice's copy), the last slice behind its own k_prep.  (Its exact sweep is a fixed ~0.5 ms of serial record loops per workgroup
+            // whatever the number of pairs: one sweep per slice cost four times that on the main stream, 10.3 ms per step against 10.0.)
+            const bool last = p0 + sl >= batch, last_but_one = !last && p0 + 2 * sl >= batch;
+            if (last_but_one || last) HIPCHK(hipStreamWaitEvent(s, h->ev_prepped, 0)); // (the prep of this slice and, by stream order, of every slice before it)
+            if (last_but_one) { swept0 = p0 + pc; if ((rc = first_chunk_of(0, swept0))) return rc; }
+            if (last) { if ((rc = first_chunk_of(swept0, batch - swept0))) return rc; swept0 = batch; }
+        }
+        if (sliced) { HIPCHK(hipEventRecord(h->ev_solved[1], aux)); solved1 = true; }
+        return MDRP_OK;
+    }
+
+    // Behind the super-chunk's last scan (chunk c): the LO of ALL its triggers, one persistent launch on aux2 (round 5: two launches, each with
+    // its own tail of long problems, cost 4.3 ms where one costs 2.7; LO problems are independent of each other, so results are bit-identical).
+    int lo(int c) {
+        int32_t *lo_plan = h->work_pair.as<int32_t>();
+        hipLaunchKernelGGL(k_lo_plan, dim3(1), dim3(PLAN_THREADS), 0, s, batch, h->st.as<PairState>(), (const int32_t *)nullptr, lo_plan);
+        if (fuse_tail) {
+            HIPCHK(hipMemsetAsync(fz_ctl, 0, 64 + 2 * sizeof(int32_t) * (size_t)batch, s));
+            HIPCHK(hipMemsetAsync(fz_ready, 0xFF, sizeof(int32_t) * (size_t)batch, s));
+        }
+        if (piped) { HIPCHK(hipEventRecord(h->ev_scanned[c], s)); HIPCHK(hipStreamWaitEvent(aux2, h->ev_scanned[c], 0)); }
+        const FuseTail fz = fuse_tail ? FuseTail{fz_done, fz_ready, fz_ctl, h->st.as<PairState>()} : FuseTail{nullptr, nullptr, nullptr, nullptr};
+        unsigned long long *lm_stats = h->lm_stats.as<unsigned long long>();
+        int32_t *xheads = cnt->xcd_head; // one LO queue per XCD (lo_take)
+        hipEvent_t l0, l1; // HIP events on the stream the LO runs on (mdrp_stats::lo_ms)
+        if (int rc = get_events(h, &l0, &l1, 2)) return rc;
+        HIPCHK(hipEventRecord(l0, aux2));
+        if (classic)
+            MDRP_CLASSIC_LM_DISPATCH(kc_lo, lo_threads, kind, dim3(lo_blocks), clm_list_bytes, aux2, rp, h->st.as<PairState>(), h->pts.as<double>(),
+                                     h->models.as<Model>(), h->triggers.as<Trigger>(), trig_cap, lo_plan, cnt->lo_head, xheads,
+                                     h->lo_mask.as<uint8_t>(), clm_list_stride, fz);
+        else
+            MDRP_LM_DISPATCH(k_lo, lo_threads, kind, est_shift, dim3(lo_blocks), lm_list_bytes(n_max), aux2, rp,
+                             h->st.as<PairState>(), h->pts.as<double>(), h->dep.as<double>(), h->models.as<Model>(), h->triggers.as<Trigger>(),
+                             trig_cap, lo_plan, cnt->lo_head, xheads, lm_list_stride(n_max), lm_stats, fz);
+        HIPCHK(hipEventRecord(l1, aux2));
+        return MDRP_OK;
+    }
+
+    // `problems` final refinements on the main stream over the states `st_f` (run parameters `rf`): the pass's pairs, or the checkpoint problems of
+    // a budgets call; the fused tail's (ready list, done flags, wait ticks, time-out counter), or (null, pairs to skip or null, 0, null)
+    void final_of(const RunParams &rf, int problems, PairState *st_f, uint8_t *mask_f, ResultDev *results_f, const int32_t *ready, int32_t *fin_done,
+                  unsigned long long ticks, unsigned long long *timeouts) {
         if (classic)
             MDRP_CLASSIC_LM_DISPATCH(kc_final, final_threads, kind, dim3(problems), clm_list_bytes, s, rf, st_f, h->pts.as<double>(), mask_f, results_f,
                                      ready, fin_done, ticks, timeouts, clm_list_stride);
@@ -553,346 +816,29 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
             MDRP_FINAL_DISPATCH(final_threads, rf.final_loss, kind, est_shift, dim3(problems), (mask_index ? lm_final_list_bytes(n_max) : lm_list_bytes(n_max)), s, rf,
                                 st_f, h->pts.as<double>(), h->dep.as<double>(), mask_f, results_f, lm_list_stride(n_max), mask_index,
                                 h->lm_stats.as<unsigned long long>() + 2, ready, fin_done, ticks, timeouts);
-    };
-    auto launch_final = [&](const int32_t *ready, int32_t *fin_done, unsigned long long ticks, unsigned long long *timeouts) {
-        launch_final_of(rp, batch, h->st.as<PairState>(), mask_dev, results_dev, ready, fin_done, ticks, timeouts);
-    };
-    const size_t tile_bytes = SCORE_TILE_BYTES;
+    }
+    void final_pairs(const int32_t *ready, int32_t *fin_done, unsigned long long ticks, unsigned long long *timeouts) {
+        final_of(rp, batch, h->st.as<PairState>(), mask_dev, results_dev, ready, fin_done, ticks, timeouts);
+    }
 
-    uint64_t it0 = 0;
-    uint64_t max_needed = 0;
-    while (true) {
-        uint64_t lens[mdrp_handle::NC_MAX] = {0};
-        int n_chunks = 1;
-        if (it0 < certain) {
-            const uint64_t span = std::min<uint64_t>(certain - it0, (uint64_t)chunk_cap);
-            uint64_t used = 0;
-            n_chunks = 0;
-            if (it0 == 0)
-                for (uint64_t l : lead) { // a leading chunk only while at least as much again remains behind it
-                    if (used + 2 * l > span) break;
-                    lens[n_chunks++] = l; used += l;
-                }
-            lens[n_chunks++] = span - used;
-        } else {
-            lens[0] = std::min<uint64_t>(std::min<uint64_t>(std::max<uint64_t>(max_needed, 256), ro->max_iterations - it0), (uint64_t)chunk_cap);
-        }
-        uint64_t super_len = 0;
-        for (int c = 0; c < n_chunks; ++c) super_len += lens[c];
-        if (it0 == 0) h->first_chunk = (int64_t)lens[0];
-        rp.chunk_start = it0; rp.super_len = (int)super_len;
-        HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
-        if (it0 == 0) HIPCHK(hipMemsetAsync(h->cand_stat.p, 0, sizeof(unsigned long long) * 2 * batch, s));
-        // Three-stream pipeline over the chunks of a super-chunk (the benchmark shape: 128 | 9872 iterations):
-        //   main:  prep solve0 count0 sort0 score0 scan0 | (wait solve1) count1 bound1 sort1 score1 scan1 | gate, final refinements (fused tail) | walk
-        //   aux :       (after solve0) solve1 ...
-        //   aux2:  samples0 samples1 (beside prep)                                                        | (after the last scan) LO: ALL triggers of the super-chunk
-        // Chunk c + 1 is solved while chunk c is swept.  Chunks alternate between two sets of tag lists / model counters / sample tables; slots
-        // and triggers of different chunks are disjoint.  A super-chunk has ONE LO launch, behind its last scan (round 5: two launches, each with
-        // its own tail of long problems, cost 4.3 ms where one costs 2.7; LO problems are independent of each other, so results are bit-identical).
-        const bool piped = n_chunks > 1 && lo_overlap;
-        const bool fuse_tail = fuse_env && piped && it0 + super_len >= ro->max_iterations;
-        int32_t *fz_ctl = nullptr, *fz_done = nullptr, *fz_fin = nullptr, *fz_ready = nullptr;
-        if (fuse_tail) {
-            if ((rc = h->fuse.ensure(sz.fuse))) return rc;
-            fz_ctl = h->fuse.as<int32_t>(); fz_done = fz_ctl + 16; fz_fin = fz_done + batch; fz_ready = fz_fin + batch;
-        }
-        hipStream_t aux = piped ? h->aux_stream : s, aux2 = piped ? h->aux_stream2 : s;
-        int offs[mdrp_handle::NC_MAX] = {0};
-        for (int c = 1; c < n_chunks; ++c) offs[c] = offs[c - 1] + (int)lens[c - 1];
-        // The sample tables of the first two chunks do not depend on anything but (seed, N): they are drawn on the (still idle)
-        // LO stream while k_prep runs, so the one-workgroup-per-table sampler (0.18 ms for 10^4 samples) is off the solver's path.
-        const int samp_threads = env_int("MDRP_SAMPLE_THREADS", ssz == 3 ? SAMP_THREADS : (ssz == 5 ? 512 : 256)); // ~ samples between two rejections
-        auto launch_samples = [&](hipStream_t st_, int len_, uint32_t *smp_) {
-            if (ssz == 6) hipLaunchKernelGGL(kc_samples<6>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
-            else if (ssz == 5) hipLaunchKernelGGL(kc_samples<5>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
-            else if (ssz == 7) hipLaunchKernelGGL(kc_samples<7>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
-            else hipLaunchKernelGGL(k_samples, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
-        };
-        bool presampled[2] = {false, false};
-        if (piped && it0 == 0) {
-            HIPCHK(hipStreamWaitEvent(aux2, h->ev_tables, 0));
-            for (int c = 0; c < 2 && c < n_chunks; ++c) {
-                launch_samples(aux2, (int)lens[c], h->samples[c & 1].as<uint32_t>());
-                HIPCHK(hipEventRecord(h->ev_sampled[c], aux2));
-                presampled[c] = true;
-            }
-        }
-        // Every kernel of the front indexes its per-pair arrays as base[pair]: a RANGE of pairs [p0, p0 + pc) is the same launch on offset bases
-        // with rp.batch = pc (the plans are per-launch scratch).  The whole batch is the range [0, batch); the host-buffer path below runs the
-        // first chunk and the second chunk's solver slice by slice while later slices are still on their way over PCIe.
-        auto issue_solve = [&](int c, hipStream_t st_, int p0, int pc) -> int {
-            RunParams r = rp;
-            r.chunk_len = (int)lens[c]; r.chunk_off = offs[c]; r.batch = pc;
-            const size_t so = (size_t)p0 * rp.slot_stride;
-            uint32_t *tg = h->tags[c & 1].as<uint32_t>() + so;
-            uint32_t *smp = h->samples[c & 1].as<uint32_t>();
-            int32_t *mc = h->model_count[c & 1].as<int32_t>() + 2 * (size_t)p0;
-            HIPCHK(hipMemsetAsync(mc, 0, sizeof(int32_t) * 2 * pc, st_));
-            if (c < 2 && presampled[c]) HIPCHK(hipStreamWaitEvent(st_, h->ev_sampled[c], 0));
-            else launch_samples(st_, r.chunk_len, smp);
-            hipEvent_t v0, v1;
-            int rc_;
-            if ((rc_ = get_events(h, &v0, &v1, 5))) return rc_;
-            HIPCHK(hipEventRecord(v0, st_));
-            struct Stop { hipEvent_t e; hipStream_t s; ~Stop() { (void)hipEventRecord(e, s); } } stop_{v1, st_}; // after the solver launch below
-            PairState *st_p = h->st.as<PairState>() + p0;
-            double *pts_p = h->pts.as<double>() + (size_t)p0 * n_max * PT_STRIDE;
-            Model *models_p = h->models.as<Model>() + so;
-            int32_t *inl_p = h->slot_inl.as<int32_t>() + so;
-            if (classic) {
-                const dim3 sgrid((r.chunk_len + 63) / 64, pc);
-                if (kind == MDRP_SHARED_6PT)
-                    hipLaunchKernelGGL(kc_solve<CLASSIC_SHARED>, sgrid, dim3(64), 0, st_, r, st_p, smp, pts_p, models_p, inl_p, tg, mc);
-                else if (kind == MDRP_RELPOSE_5PT) {
-                    // three kernels (mdrp_classic.h): null space and roots + poses at six wavefronts per CU, the elimination between them at three
-                    // Invariant: two solves that may run at the same time never share a Reduce5 block.  A chunk's solve writes blocks
-                    // [p0 * sgrid.x, (p0 + pc) * sgrid.x) of its region, and only the first chunk of a super-chunk of several chunks is ever solved
-                    // beside another chunk's solver (the sliced front: chunk 0 on `s`, chunk 1 on `aux`): it alone uses the second region.  Every
-                    // other solve is ordered behind the previous one by its stream or by ev_solved.
-                    const bool first_region = c == 0 && n_chunks > 1;
-                    if (first_region && (size_t)sgrid.x > sz.red5_first_blocks) { g_err = "5-point first chunk longer than its Reduce5 region"; return MDRP_ERR_INVALID; }
-                    double *red5 = h->red5.as<double>() + ((first_region ? (size_t)batch * sz.red5_blocks : 0) + (size_t)p0 * sgrid.x) * RED5_STRIDE * 64;
-                    hipLaunchKernelGGL(kc_solve5_null, sgrid, dim3(64), SOLVE5N_LDS_BYTES, st_, r, st_p, smp, pts_p, red5);
-                    hipLaunchKernelGGL(kc_solve5_reduce, sgrid, dim3(64), SOLVE5_LDS_BYTES, st_, r, st_p, red5);
-                    hipLaunchKernelGGL(kc_solve5_roots, sgrid, dim3(64), SOLVE5B_LDS_BYTES, st_, r, st_p, smp, pts_p, red5, models_p, inl_p, tg, mc);
-                }
-                else
-                    hipLaunchKernelGGL(kc_solve<CLASSIC_FUND>, sgrid, dim3(64), SOLVE7_LDS_BYTES, st_, r, st_p, smp, pts_p, models_p, inl_p, tg, mc);
-                return MDRP_OK;
-            }
-            double *dep_p = h->dep.as<double>() + (size_t)p0 * n_max * 2;
-#define MDRP_SOLVE_LAUNCH(S)                                                                                                   \
-    hipLaunchKernelGGL(k_solve<S>, dim3((r.chunk_len + solve_threads(S) - 1) / solve_threads(S), pc), dim3(solve_threads(S)), 0, st_, r, st_p, smp, pts_p, dep_p, models_p, inl_p, tg, mc, 0, r.chunk_len)
-            switch (r.solver) {
-            case SOLVER_P3P: MDRP_SOLVE_LAUNCH(SOLVER_P3P); break;
-            case SOLVER_SHIFT: MDRP_SOLVE_LAUNCH(SOLVER_SHIFT); break;
-            case SOLVER_SHARED: MDRP_SOLVE_LAUNCH(SOLVER_SHARED); break;
-            default: MDRP_SOLVE_LAUNCH(SOLVER_VARYING); break;
-            }
-#undef MDRP_SOLVE_LAUNCH
-            return MDRP_OK;
-        };
-        // count -> bound -> sort -> plan -> exact score -> scan of chunk c for the pairs [p0, p0 + pc), on the main stream
-        auto sweep_chunk = [&](int c, int p0, int pc) -> int {
-            RunParams r = rp;
-            r.chunk_len = (int)lens[c]; r.chunk_off = offs[c]; r.batch = pc;
-            const int len = r.chunk_len;
-            const bool odd = c & 1;
-            const size_t so = (size_t)p0 * rp.slot_stride;
-            PairState *st_p = h->st.as<PairState>() + p0;
-            const double *pts_p = h->pts.as<double>() + (size_t)p0 * n_max * PT_STRIDE;
-            const Model *models_p = h->models.as<Model>() + so;
-            uint32_t *tags_sc = h->tags_sorted[odd].as<uint32_t>() + so;
-            int32_t *mcount_c = h->model_count[odd].as<int32_t>() + 2 * (size_t)p0;
-            uint32_t *tags_c = h->tags[odd].as<uint32_t>() + so;
-            uint32_t *tags_v = h->tags_v.as<uint32_t>() + so;
-            int32_t *surv1 = h->surv_count.as<int32_t>() + p0, *surv2 = h->surv2_count.as<int32_t>() + p0;
-            hipEvent_t e0, e1;
-            int rc_;
-            if ((rc_ = get_events(h, &e0, &e1, 0))) return rc_;
-            // candidate counts on the matrix cores against the records of the chunks before this one; survivors only go on
-            unsigned long long *cstats = &cnt->progress.evals; // (and evals_mfma)
-            {
-                hipEvent_t c0, c1;
-                if ((rc_ = get_events(h, &c0, &c1, 1))) return rc_;
-                // phase A: every hypothesis over the pair's leading tiles (all tiles where the records do not allow a split); phase B: the undecided
-                // ones over the rest (k_count, mdrp_kernels.h).  A run's first chunk has no record: phase A is the whole count, no phase B.
-                const bool two_phase = !(it0 == 0 && c == 0);
-                unsigned long long *cand_stat = h->cand_stat.as<unsigned long long>() + 2 * (size_t)p0;
-                // The undecided list lives where this chunk's SORTED list will be written once the counts are done (k_sort_tags, below), the partial counts
-                // in the other parity's sorted list, whose last reader was the previous chunk's exact sweep: no scratch of their own.
-                uint32_t *tags_u = tags_sc;
-                int32_t *und_part = reinterpret_cast<int32_t *>(h->tags_sorted[!odd].as<uint32_t>() + so), *und_cnt = h->und_count.as<int32_t>() + 2 * (size_t)p0;
-                const uint4 *rfrag_p = h->rfrag.as<uint4>() + (size_t)p0 * groups_max * 64;
-                hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, st_p, mcount_c, 2, CNT_WG_MODELS, h->cplan.as<int32_t>(),
-                                   surv1, (const int32_t *)nullptr, two_phase ? und_cnt : (int32_t *)nullptr); // (also clears the counters k_count appends to)
-                const dim3 cgrid((unsigned)pc * (unsigned)((len * mps + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
-                HIPCHK(hipEventRecord(c0, s));
-                MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, r, st_p, rfrag_p, models_p,
-                                    tags_c, mcount_c, h->cplan.as<int32_t>(), tags_v, surv1, cstats, (int32_t *)nullptr, (const int32_t *)nullptr,
-                                    1, tags_u, und_part, und_cnt, (const int32_t *)nullptr, cand_stat);
-                if (two_phase) {
-                    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, st_p, und_cnt, 2, CNT_WG_MODELS, h->cplan.as<int32_t>(),
-                                       (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
-                    MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, r, st_p, rfrag_p, models_p,
-                                        tags_u, und_cnt, h->cplan.as<int32_t>(), tags_v, surv1, cstats, (int32_t *)nullptr, (const int32_t *)nullptr,
-                                        2, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, und_part, cand_stat);
-                    h->count_launches++; // (mdrp_stats::count_launches counts kernel launches: a rocprof summary shows the same number)
-                }
-                HIPCHK(hipEventRecord(c1, s));
-                h->count_launches++;
-            }
-            const uint32_t *surv_tags = tags_v;
-            const int32_t *surv_cnt = surv1;
-            // (calls of a few pairs skip the fp32 stage: its lane-per-hypothesis record loop is 0.1 ms of latency, and k_score_w takes k_count's survivors at once)
-            if (use_bound && batch_call > 16 && !(it0 == 0 && c == 0)) { // a run's first chunk has no records yet: nothing to retire
-                // fp32 lower bound of the score for k_count's survivors; its survivors go back into the chunk's tag list
-                hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, st_p, surv1, 1, BND_THREADS, h->cplan.as<int32_t>(), surv2, (const int32_t *)nullptr);
-                const dim3 bgrid((unsigned)pc * (unsigned)((len * mps + BND_THREADS - 1) / BND_THREADS));
-                unsigned long long *bstats = &cnt->progress.evals_bound;
-                hipEvent_t b0, b1;
-                if ((rc_ = get_events(h, &b0, &b1, 4))) return rc_;
-                HIPCHK(hipEventRecord(b0, s));
-                MDRP_SWEEP_DISPATCH(k_bound, kind, bgrid, dim3(BND_THREADS), 0, s, r, st_p, pts_p, models_p, tags_v, surv1, h->cplan.as<int32_t>(), tags_c, surv2, bstats);
-                HIPCHK(hipEventRecord(b1, s));
-                surv_tags = tags_c; surv_cnt = surv2;
-            }
-            int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * (size_t)batch + 2; // (the slice's plan uses the head of the buffer, `totals` stays where it is)
-            if (batch_call <= SCORE_WAVE_MAX_PAIRS) {
-                // few pairs: one WAVEFRONT per hypothesis (k_score_w) — a lane per hypothesis is a 0.3 ms serial record loop however few there are
-                hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, st_p, surv_cnt, 1, SCW_THREADS / 64, plan, (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
-                hipLaunchKernelGGL(k_sort_tags, dim3(pc), dim3(256), 0, s, r, st_p, mcount_c, surv_cnt, surv_tags, tags_sc);
-                HIPCHK(hipEventRecord(e0, s));
-                const long long ub = (long long)pc * ((len * mps + SCW_THREADS / 64 - 1) / (SCW_THREADS / 64));
-                const dim3 grid((unsigned)std::min<long long>(ub, (long long)h->num_cu * 32));
-                MDRP_SWEEP_DISPATCH(k_score_w, kind, grid, dim3(SCW_THREADS), 0, s, r, st_p, pts_p, models_p, tags_sc, mcount_c,
-                                    h->slot_score.as<double>() + so, h->slot_inl.as<int32_t>() + so, plan);
-            } else if (score_split && !(it0 == 0 && c == 0)) {
-                // the survivors of k_bound (~93 per pair): 64 hypotheses per workgroup, each wavefront a quarter of the records (k_score_split).  A run's
-                // first chunk keeps k_score: its sweep runs beside the second chunk's solver, where more and smaller sweep workgroups only wait longer
-                hipLaunchKernelGGL(k_sort_tags, dim3(pc), dim3(256), 0, s, r, st_p, mcount_c, surv_cnt, surv_tags, tags_sc);
-                hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, mcount_c, plan, totals, SPLIT_HYP);
-                HIPCHK(hipEventRecord(e0, s));
-                // items: at most ceil(sparse / 64) + ceil(dense / 64) per pair; surplus workgroups exit at once, a shortfall is taken by the item loop
-                const long long ub = (long long)pc * ((len * mps + SPLIT_HYP - 1) / SPLIT_HYP + 1);
-                const dim3 grid((unsigned)std::min<long long>(ub, (long long)h->num_cu * 32));
-                MDRP_SWEEP_DISPATCH(k_score_split, kind, grid, dim3(SPLIT_THREADS), 0, s, r, st_p, pts_p, models_p, tags_sc, mcount_c,
-                                    h->slot_score.as<double>() + so, h->slot_inl.as<int32_t>() + so, plan, totals);
-            } else {
-                hipLaunchKernelGGL(k_sort_tags, dim3(pc), dim3(256), 0, s, r, st_p, mcount_c, surv_cnt, surv_tags, tags_sc);
-                hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, pc, mcount_c, plan, totals, SCORE_THREADS);
-                HIPCHK(hipEventRecord(e0, s));
-                const dim3 grid((unsigned)pc * (unsigned)((len * mps + SCORE_THREADS - 1) / SCORE_THREADS));
-                MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), tile_bytes, s, r, st_p, pts_p, models_p, tags_sc, mcount_c,
-                                    h->slot_score.as<double>() + so, h->slot_inl.as<int32_t>() + so, plan, totals);
-            }
-            HIPCHK(hipEventRecord(e1, s));
-            h->sweep_launches++;
-            Trigger *trig_p = h->triggers.as<Trigger>() + (size_t)p0 * trig_cap;
-            unsigned long long *scan_stats = &cnt->progress.evals_sweep;
-            // (four iterations per lane where the chunk is long: a 9872-iteration chunk is 39 steps of one wavefront instead of 154)
-#define MDRP_SCAN(M, I) hipLaunchKernelGGL((k_scan<M, I>), dim3(pc), dim3(64), 0, s, r, st_p, h->slot_score.as<double>() + so, h->slot_inl.as<int32_t>() + so, trig_p, trig_cap, mcount_c, scan_stats)
-            if (mps == 16) MDRP_SCAN(16, 1);
-            else if (mps == 12) MDRP_SCAN(12, 1);
-            else if (len >= 1024) MDRP_SCAN(4, 4);
-            else MDRP_SCAN(4, 1);
-#undef MDRP_SCAN
-            return MDRP_OK;
-        };
-        // ---- host buffers (MDRP_MEM_HOST): the correspondences arrive slice by slice on the copy stream; k_prep and the second chunk's solver (the
-        // long one: 1.6 ms per 1024 pairs) of slice i run while slice i + 1 is on its way over PCIe
-        bool solved1 = false; // the second chunk's solver has been issued (slice by slice)
-        int swept0 = 0;       // pairs whose first chunk the sliced front has swept already
-        if (host && it0 == 0) {
-            const bool sliced = piped && n_chunks >= 2 && batch >= 2 * HOST_SLICE_PAIRS;
-            const int sl = sliced ? HOST_SLICE_PAIRS : batch;
-            for (int p0 = 0; p0 < batch; p0 += sl) {
-                const int pc = std::min(sl, batch - p0);
-                const size_t o2 = (size_t)2 * p0 * n_max, o1 = (size_t)p0 * n_max, n2 = sizeof(double) * 2 * (size_t)pc * n_max, n1 = sizeof(double) * (size_t)pc * n_max;
-                hipStream_t cs = sliced ? h->copy_stream : s;
-                HIPCHK(hipMemcpyAsync(const_cast<double *>(x1) + o2, host->x1 + o2, n2, hipMemcpyHostToDevice, cs));
-                HIPCHK(hipMemcpyAsync(const_cast<double *>(x2) + o2, host->x2 + o2, n2, hipMemcpyHostToDevice, cs));
-                if (host->d1 && host->d2) {
-                    HIPCHK(hipMemcpyAsync(const_cast<double *>(d1) + o1, host->d1 + o1, n1, hipMemcpyHostToDevice, cs));
-                    HIPCHK(hipMemcpyAsync(const_cast<double *>(d2) + o1, host->d2 + o1, n1, hipMemcpyHostToDevice, cs));
-                }
-                if (!sliced) { launch_prep(p0, pc, s); break; }
-                // k_prep and the long solver of the slice on the solver stream, beside the next slices' copies (the main stream sweeps the first chunk)
-                HIPCHK(hipEventRecord(h->ev_copied, cs)); HIPCHK(hipStreamWaitEvent(aux, h->ev_copied, 0));
-                if (p0 == 0) HIPCHK(hipStreamWaitEvent(aux, h->ev_tables, 0)); // (the per-call parameters were uploaded on the main stream)
-                launch_prep(p0, pc, aux);
-                HIPCHK(hipEventRecord(h->ev_prepped, aux));
-                if ((rc = issue_solve(1, aux, p0, pc))) return rc;
-                // The first chunk is swept in TWO parts only: everything but the last slice as soon as the last-but-one slice is prepared (beside the
-                // last slice's copy), the last slice behind its own k_prep.  (Its exact sweep is a fixed ~0.5 ms of serial record loops per workgroup
-                // whatever the number of pairs: one sweep per slice cost four times that on the main stream, 10.3 ms per step against 10.0.)
-                const bool last = p0 + sl >= batch, last_but_one = !last && p0 + 2 * sl >= batch;
-                if (last_but_one || last) HIPCHK(hipStreamWaitEvent(s, h->ev_prepped, 0)); // (the prep of this slice and, by stream order, of every slice before it)
-                // The 6-point solver (11.5 KB of scratch per lane) solves the first chunk on the solver stream too, behind the second chunk's slices:
-                // two of its dispatches at once on two queues need two whole-device scratch areas (~6 GB each) at the same time, and the runtime
-                // aborts the queue (out of resources) when it cannot have the second one.  The main stream sweeps behind that solve.
-                auto solve_first = [&](int q0, int qc) -> int {
-                    if (kind != MDRP_SHARED_6PT) return issue_solve(0, s, q0, qc);
-                    int rc_ = issue_solve(0, aux, q0, qc);
-                    if (rc_) return rc_;
-                    HIPCHK(hipEventRecord(h->ev_solved6, aux));
-                    HIPCHK(hipStreamWaitEvent(s, h->ev_solved6, 0));
-                    return MDRP_OK;
-                };
-                if (last_but_one) { swept0 = p0 + pc; if ((rc = solve_first(0, swept0)) || (rc = sweep_chunk(0, 0, swept0))) return rc; }
-                if (last) { if ((rc = solve_first(swept0, batch - swept0)) || (rc = sweep_chunk(0, swept0, batch - swept0))) return rc; swept0 = batch; }
-            }
-            if (sliced) { HIPCHK(hipEventRecord(h->ev_solved[1], aux)); solved1 = true; }
-        }
-        if (swept0 < batch && (rc = issue_solve(0, s, 0, batch))) return rc;
-        if (piped) HIPCHK(hipEventRecord(h->ev_solved[0], s));
-        for (int c = 0; c < n_chunks; ++c) {
-            rp.chunk_len = (int)lens[c]; rp.chunk_off = offs[c];
-            if (c == 0 && swept0 >= batch) { // (the sliced front has swept the first chunk already)
-                if (piped) HIPCHK(hipEventRecord(h->ev_scanned[0], s));
-                continue;
-            }
-            if (piped && c + 1 < n_chunks && !(c == 0 && solved1)) {
-                // the sampler tables advance in chunk order; chunk c + 1 reuses the lists chunk c - 1 was swept from
-                HIPCHK(hipStreamWaitEvent(aux, c == 0 ? h->ev_solved[0] : h->ev_scanned[c - 1], 0));
-                if ((rc = issue_solve(c + 1, aux, 0, batch))) return rc;
-                HIPCHK(hipEventRecord(h->ev_solved[c + 1], aux));
-            }
-            if (piped && c > 0) HIPCHK(hipStreamWaitEvent(s, h->ev_solved[c], 0));
-            if (!piped && c > 0 && (rc = issue_solve(c, s, 0, batch))) return rc;
-            if ((rc = sweep_chunk(c, 0, batch))) return rc;
-            if (c + 1 < n_chunks) { // (the solver of chunk c + 2 waits for this chunk's scan: it reuses this chunk's lists)
-                if (piped) HIPCHK(hipEventRecord(h->ev_scanned[c], s));
-                continue;
-            }
-            // ---- behind the super-chunk's last scan: the LO of ALL its triggers, one persistent launch
-            int32_t *lo_plan = h->work_pair.as<int32_t>();
-            hipLaunchKernelGGL(k_lo_plan, dim3(1), dim3(PLAN_THREADS), 0, s, batch, h->st.as<PairState>(), (const int32_t *)nullptr, lo_plan);
-            if (fuse_tail) {
-                HIPCHK(hipMemsetAsync(fz_ctl, 0, 64 + 2 * sizeof(int32_t) * (size_t)batch, s));
-                HIPCHK(hipMemsetAsync(fz_ready, 0xFF, sizeof(int32_t) * (size_t)batch, s));
-            }
-            if (piped) { HIPCHK(hipEventRecord(h->ev_scanned[c], s)); HIPCHK(hipStreamWaitEvent(aux2, h->ev_scanned[c], 0)); }
-            const int lo_blocks = h->num_cu * (lo_threads == 64 ? 8 : 2);
-            const FuseTail fz = fuse_tail ? FuseTail{fz_done, fz_ready, fz_ctl, h->st.as<PairState>()} : FuseTail{nullptr, nullptr, nullptr, nullptr};
-            unsigned long long *lm_stats = h->lm_stats.as<unsigned long long>();
-            int32_t *xheads = cnt->xcd_head; // one LO queue per XCD (lo_take)
-            hipEvent_t l0, l1; // HIP events on the stream the LO runs on (mdrp_stats::lo_ms)
-            if ((rc = get_events(h, &l0, &l1, 2))) return rc;
-            HIPCHK(hipEventRecord(l0, aux2));
-            if (classic)
-                MDRP_CLASSIC_LM_DISPATCH(kc_lo, lo_threads, kind, dim3(lo_blocks), clm_list_bytes, aux2, rp, h->st.as<PairState>(), h->pts.as<double>(),
-                                         h->models.as<Model>(), h->triggers.as<Trigger>(), trig_cap, lo_plan, cnt->lo_head, xheads,
-                                         h->lo_mask.as<uint8_t>(), clm_list_stride, fz);
-            else
-                MDRP_LM_DISPATCH(k_lo, lo_threads, kind, est_shift, dim3(lo_blocks), lm_list_bytes(n_max), aux2, rp,
-                                 h->st.as<PairState>(), h->pts.as<double>(), h->dep.as<double>(), h->models.as<Model>(), h->triggers.as<Trigger>(),
-                                 trig_cap, lo_plan, cnt->lo_head, xheads, lm_list_stride(n_max), lm_stats, fz);
-            HIPCHK(hipEventRecord(l1, aux2));
-        }
-        if (fuse_tail) { // final refinements on the main stream, released when the last LO launch's queue is empty
-            const int32_t *plan_l = h->work_pair.as<int32_t>();
-            const int lo_blocks_l = h->num_cu * (lo_threads == 64 ? 8 : 2); // = lo_blocks of the launch above
-            // bounded waits (k_gate): far beyond anything a healthy run needs (the LO queue of 1024 pairs is empty after ~1 ms)
-            // ... and scaled with the problem size: one LO problem is ~0.4 ms at N = 2000 and grows linearly with N (4 ms at 5000 on one wavefront)
-            // ... capped at 200 ms / 100 ms: under persistently serialised dispatch (rocprofv3 --pmc, AMD_SERIALIZE_KERNEL, a debugger) every re-try of the
-            // fused tail pays these in full (3.3 s at N = 70001 before the cap)
-            const long long n_scale = std::max(1, (n_max + 1999) / 2000);
-            const unsigned long long gate_ticks = 100ull * (unsigned long long)env_int("MDRP_FUSE_GATE_US", (int)std::min<long long>((50000 + 40ll * batch) * n_scale, 200000));
-            const unsigned long long wait_ticks = 100ull * (unsigned long long)env_int("MDRP_FUSE_WAIT_US", (int)std::min<long long>((20000 + 4ll * batch) * n_scale, 100000));
-            hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, s, (const int32_t *)cnt->lo_head, plan_l + 3 * (size_t)batch + 1,
-                               (const int32_t *)fz_ctl, lo_blocks_l, gate_ticks, h->lm_stats.as<unsigned long long>() + 4);
-            hipEvent_t g0, g1;
-            if ((rc = get_events(h, &g0, &g1, 3))) return rc;
-            HIPCHK(hipEventRecord(g0, s));
-            launch_final(fz_ready, fz_fin, wait_ticks, h->lm_stats.as<unsigned long long>() + 5);
-            HIPCHK(hipEventRecord(g1, s));
-            final_done = true;
-        }
-        if (piped) { HIPCHK(hipEventRecord(h->ev_lo, aux2)); HIPCHK(hipStreamWaitEvent(s, h->ev_lo, 0)); }
-        if (fuse_tail) // behind the LO launch: the pairs a bounded wait gave up on (none in a healthy run: 1024 workgroups that read a flag)
-            launch_final(nullptr, fz_fin, 0, nullptr);
+    // fused tail: the final refinements on the main stream, released by k_gate when the last LO launch's queue is empty (bounded waits: mdrp_schedule.h)
+    int gate_and_final() {
+        const int32_t *plan_l = h->work_pair.as<int32_t>();
+        const unsigned long long gate_ticks = 100ull * (unsigned long long)env_int("MDRP_FUSE_GATE_US", sched::fuse_gate_us(batch, n_max));
+        const unsigned long long wait_ticks = 100ull * (unsigned long long)env_int("MDRP_FUSE_WAIT_US", sched::fuse_wait_us(batch, n_max));
+        hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, s, (const int32_t *)cnt->lo_head, plan_l + 3 * (size_t)batch + 1,
+                           (const int32_t *)fz_ctl, lo_blocks, gate_ticks, h->lm_stats.as<unsigned long long>() + 4);
+        hipEvent_t g0, g1;
+        if (int rc = get_events(h, &g0, &g1, 3)) return rc;
+        HIPCHK(hipEventRecord(g0, s));
+        final_pairs(fz_ready, fz_fin, wait_ticks, h->lm_stats.as<unsigned long long>() + 5);
+        HIPCHK(hipEventRecord(g1, s));
+        final_done = true;
+        return MDRP_OK;
+    }
+
+    // replay of score_models / ransac bookkeeping over the ordered triggers (the fused tail's LO launch has done it; a budgets call takes its checkpoints here)
+    int walk() {
         if (bud)
             hipLaunchKernelGGL(k_walk_ckpt, dim3((batch + WALK_CKPT_THREADS - 1) / WALK_CKPT_THREADS), dim3(WALK_CKPT_THREADS), 0, s, rp, h->st.as<PairState>(), h->models.as<Model>(),
                                h->triggers.as<Trigger>(), trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed,
@@ -902,51 +848,121 @@ int run_pass(mdrp_handle *h, int kind, const double *x1, const double *x2, const
                                h->triggers.as<Trigger>(), trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed,
                                (const int32_t *)nullptr, 0, 0, 0);
         HIPCHK(hipGetLastError());
-        // progress record: pairs still iterating, iterations they still need, evaluations swept (sum over pairs of models * n)
-        HIPCHK(hipMemcpyAsync(h->progress_host, &cnt->progress, sizeof(Progress), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        h->sweep_evals += (int64_t)h->progress_host->evals;
-        h->mfma_evals += (int64_t)h->progress_host->evals_mfma;
-        h->fp64_evals += (int64_t)h->progress_host->evals_sweep;
-        h->bound_evals += (int64_t)h->progress_host->evals_bound;
-        if (final_done && h->progress_host->wish_pairs > 0) // (fused tail: the final refinements are behind this read-back; otherwise they are still to come)
-            h->seen_wish[kind] = (double)h->progress_host->wish_sum / (double)h->progress_host->wish_pairs;
-        if (getenv("MDRP_DEBUG"))
-            fprintf(stderr, "[mdrp] super-chunk start %llu len %llu (%d chunks): evals %llu (mfma %llu, fp32 bound %llu, fp64 sweep %llu = %.2f %%) active %d max_needed %llu\n",
-                    (unsigned long long)it0, (unsigned long long)super_len, n_chunks, h->progress_host->evals, h->progress_host->evals_mfma,
-                    h->progress_host->evals_bound, h->progress_host->evals_sweep, 100.0 * (double)h->progress_host->evals_sweep / (double)std::max<unsigned long long>(1, h->progress_host->evals),
-                    h->progress_host->n_active, h->progress_host->max_needed);
-        it0 += super_len;
-        if (h->progress_host->n_active == 0 || it0 >= ro->max_iterations) break;
-        max_needed = h->progress_host->max_needed;
+        return MDRP_OK;
     }
 
-    if (final_done) return MDRP_OK; // fused tail: the final refinements ran beside the last LO launch
-    hipEvent_t f0, f1;
-    if ((rc = get_events(h, &f0, &f1, 3))) return rc;
-    HIPCHK(hipEventRecord(f0, s));
-    if (bud) {
-        // the distinct checkpoint states of every pair in ONE launch over the compact list (k_ckpt_plan); every other checkpoint is filled from its
-        // representative.  A pair that stops early, or whose best model does not change between two budgets, is refined once for all of them.
-        const int problems = n_bud * batch;
-        int32_t *list = h->ck_list.as<int32_t>(), *rep = list + problems, *done = rep + problems;
-        hipLaunchKernelGGL(k_ckpt_plan, dim3(1), dim3(PLAN_THREADS), 0, s, batch, n_bud, h->ckpt.as<PairState>(), list, rep);
-        RunParams rf = rp;
-        rf.ck_pairs = batch; rf.ck_plane = bud->plane;
-        rf.inl_stat = nullptr; // (the last budget's results alone feed the next call's first chunk: k_ckpt_fill)
-        launch_final_of(rf, problems, h->ckpt.as<PairState>(), bud->mask, bud->results, list, done, 0, nullptr);
-        rf.inl_stat = rp.inl_stat;
-        hipLaunchKernelGGL(k_ckpt_fill, dim3(problems), dim3(CKPT_FILL_THREADS), 0, s, rf, n_bud, h->ckpt.as<PairState>(), rep, bud->results, bud->mask);
-    } else
-        launch_final(nullptr, nullptr, 0, nullptr);
-    HIPCHK(hipEventRecord(f1, s));
-    if (rp.inl_stat && h->wish_kind < 0) { // (the fused tail's sums came with the progress record; these arrive when the stream gets here: the next call looks)
-        HIPCHK(hipMemcpyAsync(h->wish_host, rp.inl_stat, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(h->ev_wish, s));
-        h->wish_kind = kind;
+    // progress record: pairs still iterating, iterations they still need, evaluations swept (sum over pairs of models * n); the one host wait of a super-chunk
+    int read_progress() {
+        const Progress *pr = h->progress_host;
+        HIPCHK(hipMemcpyAsync(h->progress_host, &cnt->progress, sizeof(Progress), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        h->sweep_evals += (int64_t)pr->evals;
+        h->mfma_evals += (int64_t)pr->evals_mfma;
+        h->fp64_evals += (int64_t)pr->evals_sweep;
+        h->bound_evals += (int64_t)pr->evals_bound;
+        if (final_done && pr->wish_pairs > 0) // (fused tail: the final refinements are behind this read-back; otherwise they are still to come)
+            h->seen_wish[kind] = (double)pr->wish_sum / (double)pr->wish_pairs;
+        if (getenv("MDRP_DEBUG"))
+            fprintf(stderr, "[mdrp] super-chunk start %llu len %llu (%d chunks): evals %llu (mfma %llu, fp32 bound %llu, fp64 sweep %llu = %.2f %%) active %d max_needed %llu\n",
+                    (unsigned long long)it0, (unsigned long long)lay.super_len, lay.n_chunks, pr->evals, pr->evals_mfma, pr->evals_bound, pr->evals_sweep,
+                    100.0 * (double)pr->evals_sweep / (double)std::max<unsigned long long>(1, pr->evals), pr->n_active, pr->max_needed);
+        return MDRP_OK;
     }
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
+
+    // unfused: the final refinements of the pass's pairs, or of a budgets call's checkpoints, behind the last super-chunk
+    int final_refinements() {
+        hipEvent_t f0, f1;
+        if (int rc = get_events(h, &f0, &f1, 3)) return rc;
+        HIPCHK(hipEventRecord(f0, s));
+        if (bud) {
+            // the distinct checkpoint states of every pair in ONE launch over the compact list (k_ckpt_plan); every other checkpoint is filled from its
+            // representative.  A pair that stops early, or whose best model does not change between two budgets, is refined once for all of them.
+            const int problems = n_bud * batch;
+            int32_t *list = h->ck_list.as<int32_t>(), *rep = list + problems, *done = rep + problems;
+            hipLaunchKernelGGL(k_ckpt_plan, dim3(1), dim3(PLAN_THREADS), 0, s, batch, n_bud, h->ckpt.as<PairState>(), list, rep);
+            RunParams rf = rp;
+            rf.ck_pairs = batch; rf.ck_plane = bud->plane;
+            rf.inl_stat = nullptr; // (the last budget's results alone feed the next call's first chunk: k_ckpt_fill)
+            final_of(rf, problems, h->ckpt.as<PairState>(), bud->mask, bud->results, list, done, 0, nullptr);
+            rf.inl_stat = rp.inl_stat;
+            hipLaunchKernelGGL(k_ckpt_fill, dim3(problems), dim3(CKPT_FILL_THREADS), 0, s, rf, n_bud, h->ckpt.as<PairState>(), rep, bud->results, bud->mask);
+        } else
+            final_pairs(nullptr, nullptr, 0, nullptr);
+        HIPCHK(hipEventRecord(f1, s));
+        if (rp.inl_stat && h->wish_kind < 0) { // (the fused tail's sums came with the progress record; these arrive when the stream gets here: the next call looks)
+            HIPCHK(hipMemcpyAsync(h->wish_host, rp.inl_stat, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipEventRecord(h->ev_wish, s));
+            h->wish_kind = kind;
+        }
+        HIPCHK(hipGetLastError());
+        return MDRP_OK;
+    }
+};
+
+// The stream schedule of a pass.  A super-chunk of several chunks is pipelined over three streams (the benchmark shape: 256 | 9744
+// iterations); chunk c + 1 is solved while chunk c is swept, and the super-chunk has ONE LO launch, behind its last scan:
+//   main:  prep solve0 count0 sort0 score0 scan0 | (wait solve1) count1 bound1 sort1 score1 scan1 | gate, final refinements (fused tail) | walk
+//   aux :       (after solve0) solve1 ...
+//   aux2:  samples0 samples1 (beside prep)                                                        | (after the last scan) LO: ALL triggers of the super-chunk
+// Host buffers of 512 pairs or more arrive in slices on a fourth stream (Pass::host_front):
+//   copy:  slice0 slice1 slice2 slice3
+//   aux :         prep0 solve1[0]  prep1 solve1[1]  prep2 solve1[2]  prep3 solve1[3]
+//   main:                                          solve0 + sweep of chunk 0 [slices 0-2]   | solve0 + sweep of chunk 0 [slice 3] | count1 ...
+// Otherwise (one chunk, or MDRP_LO_OVERLAP=0) aux and aux2 are the main stream and everything runs in the order it is issued.
+int run_pass(mdrp_handle *h, const PassIn &in) {
+    Pass p(h, in);
+    hipStream_t s = p.s;
+    int rc;
+    if ((rc = p.plan_and_allocate()) || (rc = p.upload_params())) return rc;
+    HIPCHK(hipEventRecord(h->ev_tables, s)); // sample tables can be drawn from here on
+    if (!p.host) { // device-resident inputs: everything is there (host buffers: the copies and k_prep are issued slice by slice by host_front)
+        p.prep(0, p.batch, s);
+        HIPCHK(hipGetLastError());
+    }
+    p.rp.inl_stat = p.classic ? nullptr : &p.cnt->progress.wish_sum;
+
+    uint64_t max_needed = 0;
+    while (true) {
+        if ((rc = p.begin_super_chunk(max_needed))) return rc;
+        const int n_chunks = p.lay.n_chunks;
+        const bool piped = p.piped;
+        if (piped && p.it0 == 0 && (rc = p.presample())) return rc;
+        bool solved1 = false; // the second chunk's solver has been issued (slice by slice)
+        int swept0 = 0;       // pairs whose first chunk the sliced front has swept already
+        if (p.host && p.it0 == 0 && (rc = p.host_front(solved1, swept0))) return rc;
+        if (swept0 < p.batch && (rc = p.solve(p.view(0, 0, p.batch), s))) return rc;
+        if (piped) HIPCHK(hipEventRecord(h->ev_solved[0], s));
+        for (int c = 0; c < n_chunks; ++c) {
+            p.rp.chunk_len = (int)p.lay.lens[c]; p.rp.chunk_off = p.lay.offs[c];
+            if (c == 0 && swept0 >= p.batch) { // (the sliced front has swept the first chunk already)
+                if (piped) HIPCHK(hipEventRecord(h->ev_scanned[0], s));
+                continue;
+            }
+            if (piped && c + 1 < n_chunks && !(c == 0 && solved1)) {
+                // the sampler tables advance in chunk order; chunk c + 1 reuses the lists chunk c - 1 was swept from
+                HIPCHK(hipStreamWaitEvent(p.aux, c == 0 ? h->ev_solved[0] : h->ev_scanned[c - 1], 0));
+                if ((rc = p.solve(p.view(c + 1, 0, p.batch), p.aux))) return rc;
+                HIPCHK(hipEventRecord(h->ev_solved[c + 1], p.aux));
+            }
+            if (piped && c > 0) HIPCHK(hipStreamWaitEvent(s, h->ev_solved[c], 0));
+            if (!piped && c > 0 && (rc = p.solve(p.view(c, 0, p.batch), s))) return rc;
+            if ((rc = p.sweep(p.view(c, 0, p.batch)))) return rc;
+            if (c + 1 < n_chunks) { // (the solver of chunk c + 2 waits for this chunk's scan: it reuses this chunk's lists)
+                if (piped) HIPCHK(hipEventRecord(h->ev_scanned[c], s));
+                continue;
+            }
+            if ((rc = p.lo(c))) return rc; // (records ev_scanned[c]; aux2 waits for it)
+        }
+        if (p.fuse_tail && (rc = p.gate_and_final())) return rc;
+        if (piped) { HIPCHK(hipEventRecord(h->ev_lo, p.aux2)); HIPCHK(hipStreamWaitEvent(s, h->ev_lo, 0)); }
+        if (p.fuse_tail) // behind the LO launch: the pairs a bounded wait gave up on (none in a healthy run: 1024 workgroups that read a flag)
+            p.final_pairs(nullptr, p.fz_fin, 0, nullptr);
+        if ((rc = p.walk()) || (rc = p.read_progress())) return rc;
+        p.it0 += p.lay.super_len;
+        if (h->progress_host->n_active == 0 || p.it0 >= p.ro->max_iterations) break;
+        max_needed = h->progress_host->max_needed;
+    }
+    return p.final_done ? MDRP_OK : p.final_refinements(); // (fused tail: the final refinements ran beside the last LO launch)
 }
 
 int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
@@ -983,32 +999,26 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     // from the free memory below); the last plane is copied to `results` behind the passes
     if (budgets && (rc = h->bresults.ensure(sizeof(ResultDev) * n_budgets * batch))) return rc;
     // chunk capacity and pairs per pass from the scratch budget
-    uint64_t chunk_cap64 = std::min<uint64_t>(std::max<uint64_t>(ro->max_iterations, 1), std::max<uint64_t>(ro->min_iterations + 1, 4096));
-    chunk_cap64 = std::min<uint64_t>(chunk_cap64, 16384);
-    const int chunk_cap = (int)chunk_cap64;
+    const int chunk_cap = sched::chunk_capacity(ro->max_iterations, ro->min_iterations);
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     // What one more pair adds to a pass's scratch (every buffer of a pass grows linearly with its pairs and its sample tables), with one sample table
-    // per pair (a ragged batch may have as many).  Of the leading chunks, only the 5-point solver's second Reduce5 region depends on them: the
-    // default first chunk of that estimator is at most 512 iterations (run_pass).
-    std::vector<uint64_t> lead;
-    if (!env_chunks(lead)) lead.assign(1, 512);
-    const size_t per_pair = pass_scratch(h, kind, 2, n_max, 2, chunk_cap, lead, n_budgets).total() - pass_scratch(h, kind, 1, n_max, 1, chunk_cap, lead, n_budgets).total();
-    size_t budget = std::min<size_t>((size_t)(0.5 * (double)free_b), (size_t)96 << 30);
-    int per_pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, budget / per_pair));
-    per_pass = std::min(per_pass, 65535); // k_solve / k_probe put the pair index on grid.y
+    // per pair (a ragged batch may have as many).  Of the leading chunks, only the 5-point solver's second Reduce5 region depends on them.
+    sched::Lead lead;
+    const uint64_t lead0 = sched::parse_chunks(getenv("MDRP_CHUNKS"), lead) ? lead.first() : sched::LEAD_BUDGET;
+    const size_t per_pair = pass_scratch(h, kind, 2, n_max, 2, chunk_cap, lead0, n_budgets).total() - pass_scratch(h, kind, 1, n_max, 1, chunk_cap, lead0, n_budgets).total();
+    int per_pass = sched::pairs_per_pass(free_b, per_pair, batch);
     per_pass = std::max(1, std::min(per_pass, env_int("MDRP_PAIRS_PER_PASS", per_pass))); // (tests: several passes on a small batch)
     for (int p0 = 0; p0 < batch; p0 += per_pass) {
         const int nb = std::min(per_pass, batch - p0);
+        const size_t o1 = (size_t)p0 * n_max, o2 = 2 * o1;
         HostSrc hs{};
-        if (host) hs = HostSrc{host->x1 + (size_t)2 * p0 * n_max, host->x2 + (size_t)2 * p0 * n_max, host->d1 ? host->d1 + (size_t)p0 * n_max : nullptr,
-                               host->d2 ? host->d2 + (size_t)p0 * n_max : nullptr};
-        const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + (size_t)p0 * n_max, batch};
-        rc = run_pass(h, kind, x1 + (size_t)2 * p0 * n_max, x2 + (size_t)2 * p0 * n_max, d1 ? d1 + (size_t)p0 * n_max : nullptr,
-                      d2 ? d2 + (size_t)p0 * n_max : nullptr, nb,
-                      n_max, n_host.data() + p0, cam1 ? cam1 + p0 : nullptr, cam2 ? cam2 + p0 : nullptr, ro, bo, chunk_cap,
-                      mask + (size_t)p0 * n_max, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch, budgets ? &bud : nullptr);
-        if (rc) return rc;
+        if (host) hs = HostSrc{host->x1 + o2, host->x2 + o2, host->d1 ? host->d1 + o1 : nullptr, host->d2 ? host->d2 + o1 : nullptr};
+        const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + o1, batch};
+        const PassIn in{kind, x1 + o2, x2 + o2, d1 ? d1 + o1 : nullptr, d2 ? d2 + o1 : nullptr, nb, n_max, n_host.data() + p0, cam1 ? cam1 + p0 : nullptr,
+                        cam2 ? cam2 + p0 : nullptr, ro, bo, chunk_cap, mask + o1, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch,
+                        budgets ? &bud : nullptr};
+        if ((rc = run_pass(h, in))) return rc;
     }
     if (budgets) {
         HIPCHK(hipMemcpyAsync(h->results.p, h->bresults.as<ResultDev>() + (size_t)(n_budgets - 1) * batch, sizeof(ResultDev) * batch, hipMemcpyDeviceToDevice, h->stream));
@@ -1121,7 +1131,7 @@ static int create_handle(int device, hipStream_t stream, bool own_stream, mdrp_h
     HIPCHK(hipStreamCreateWithFlags(&h->copy_stream.v, hipStreamNonBlocking));
     for (Event *e : {&h->ev_copied, &h->ev_prepped, &h->ev_solved6, &h->ev_lo, &h->ev_tables, &h->ev_sampled[0], &h->ev_sampled[1]})
         HIPCHK(hipEventCreateWithFlags(&e->v, hipEventDisableTiming));
-    for (int i = 0; i < mdrp_handle::NC_MAX; ++i) {
+    for (int i = 0; i < sched::NC_MAX; ++i) {
         HIPCHK(hipEventCreateWithFlags(&h->ev_solved[i].v, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&h->ev_scanned[i].v, hipEventDisableTiming));
     }
@@ -1183,12 +1193,26 @@ int mdrp_synchronize(mdrp_handle *h) {
     return MDRP_OK;
 }
 
+// an error behind the first device work: nothing of the call stays in flight on the caller's buffers
+static int drain_and_return(mdrp_handle *h, int rc) {
+    for (hipStream_t st : {h->stream, (hipStream_t)h->aux_stream, (hipStream_t)h->aux_stream2, (hipStream_t)h->copy_stream}) (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// the asynchronous calls, plain (budgets null) and with budgets
+static int estimate_async_locked(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
+                                 const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                 const mdrp_bundle_opt *bopt, const uint64_t *budgets, int n_budgets, uint8_t *inlier_mask_dev) {
+    const int rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, budgets, n_budgets);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
 int mdrp_estimate_batch_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2,
                               int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
                               const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
     if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     MDRP_ENTER(h);
-    return estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev);
+    return estimate_async_locked(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, nullptr, 0, inlier_mask_dev);
 }
 
 static int fetch_results_locked(mdrp_handle *h, mdrp_result *out, int batch) {
@@ -1210,43 +1234,8 @@ int mdrp_fetch_results(mdrp_handle *h, mdrp_result *out, int batch) {
     return fetch_results_locked(h, out, batch);
 }
 
-int mdrp_estimate_batch(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
-                        const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
-                        const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out,
-                        uint8_t *inlier_mask) {
-    if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    const size_t np = (size_t)batch * n_max;
-    int rc;
-    uint8_t *mask_dev = inlier_mask;
-    HostSrc hsrc{};
-    bool use_host = false;
-    if (mem_space == MDRP_MEM_HOST) {
-        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
-            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)))
-            return rc;
-        // the copies are issued by run_pass, slice by slice on the handle's copy stream, beside the first kernels of the slices before them
-        hsrc = HostSrc{x1, x2, (d1 && d2) ? d1 : nullptr, (d1 && d2) ? d2 : nullptr};
-        if (d1 && d2) { d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>(); }
-        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
-        use_host = true;
-        mask_dev = nullptr; // handle-owned device mask, copied back below
-    }
-    rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, mask_dev, use_host ? &hsrc : nullptr);
-    if (rc) return rc;
-    if (mem_space == MDRP_MEM_HOST && inlier_mask && np > 0)
-        HIPCHK(hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, h->stream));
-    return fetch_results_locked(h, out, batch);
-}
-
 // ---- iteration budgets
 static_assert(MDRP_MAX_BUDGETS == MAX_BUDGETS, "budget limit of the header and of the kernels");
-
-// an error behind the first device work: nothing of the call stays in flight on the caller's buffers
-static int drain_and_return(mdrp_handle *h, int rc) {
-    for (hipStream_t st : {h->stream, (hipStream_t)h->aux_stream, (hipStream_t)h->aux_stream2, (hipStream_t)h->copy_stream}) (void)hipStreamSynchronize(st);
-    return rc;
-}
 
 static int budget_results_locked(mdrp_handle *h, void *dst, int n_budgets, int batch, hipMemcpyKind where) {
     if (!dst || batch < 0 || n_budgets < 1 || n_budgets != h->last_budgets || batch != h->last_batch) {
@@ -1264,8 +1253,7 @@ int mdrp_estimate_batch_budgets_async(mdrp_handle *h, int kind, const double *x1
     if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
     MDRP_ENTER(h);
-    const int rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, budgets, n_budgets);
-    return rc ? drain_and_return(h, rc) : rc;
+    return estimate_async_locked(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, budgets, n_budgets, inlier_mask_dev);
 }
 
 int mdrp_fetch_budget_results(mdrp_handle *h, mdrp_result *out, int n_budgets, int batch) {
@@ -1280,6 +1268,45 @@ int mdrp_copy_budget_results_device(mdrp_handle *h, void *dst_dev, int n_budgets
     return budget_results_locked(h, dst_dev, n_budgets, batch, hipMemcpyDeviceToDevice); // (waits for the handle's stream, as mdrp_copy_results_device)
 }
 
+// The blocking calls, plain (budgets null) and with budgets: host buffers are staged in the handle's device buffers (the copies are issued by
+// run_pass, slice by slice on the handle's copy stream, beside the first kernels of the slices before them) and their masks copied back from the
+// handle's; then the records are fetched.
+static int estimate_batch_locked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
+                                 int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                 const mdrp_bundle_opt *bopt, const uint64_t *budgets, int n_budgets, mdrp_result *out, uint8_t *inlier_mask) {
+    const size_t np = (size_t)batch * n_max;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
+    int rc;
+    HostSrc hsrc{};
+    if (use_host) {
+        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
+            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)))
+            return rc;
+        hsrc = HostSrc{x1, x2, (d1 && d2) ? d1 : nullptr, (d1 && d2) ? d2 : nullptr};
+        if (d1 && d2) { d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>(); }
+        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
+    }
+    // (host call: a handle-owned device mask, or its planes, copied back below)
+    rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask, use_host ? &hsrc : nullptr, budgets, n_budgets);
+    if (rc) return drain_and_return(h, rc);
+    if (use_host && inlier_mask && np > 0 &&
+        hipMemcpyAsync(inlier_mask, (budgets ? h->bmask : h->mask).p, np * (budgets ? n_budgets : 1), hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+        g_err = "copy of the inlier masks failed";
+        return drain_and_return(h, MDRP_ERR_HIP);
+    }
+    rc = budgets ? budget_results_locked(h, out, n_budgets, batch, hipMemcpyDeviceToHost) : fetch_results_locked(h, out, batch);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_estimate_batch(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
+                        const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
+                        const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out,
+                        uint8_t *inlier_mask) {
+    if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    return estimate_batch_locked(h, kind, mem_space, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, nullptr, 0, out, inlier_mask);
+}
+
 int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
                                 const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
                                 const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets,
@@ -1287,30 +1314,7 @@ int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const d
     if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
     MDRP_ENTER(h);
-    const size_t np = (size_t)batch * n_max;
-    int rc;
-    uint8_t *mask_dev = inlier_mask;
-    HostSrc hsrc{};
-    bool use_host = false;
-    if (mem_space == MDRP_MEM_HOST) { // (staging as in mdrp_estimate_batch: the copies are issued by run_pass)
-        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
-            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)))
-            return rc;
-        hsrc = HostSrc{x1, x2, (d1 && d2) ? d1 : nullptr, (d1 && d2) ? d2 : nullptr};
-        if (d1 && d2) { d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>(); }
-        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
-        use_host = true;
-        mask_dev = nullptr; // handle-owned device mask planes, copied back below
-    }
-    rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, mask_dev, use_host ? &hsrc : nullptr, budgets, n_budgets);
-    if (rc) return drain_and_return(h, rc);
-    if (mem_space == MDRP_MEM_HOST && inlier_mask && np > 0 &&
-        hipMemcpyAsync(inlier_mask, h->bmask.p, np * n_budgets, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-        g_err = "copy of the inlier masks failed";
-        return drain_and_return(h, MDRP_ERR_HIP);
-    }
-    rc = budget_results_locked(h, out, n_budgets, batch, hipMemcpyDeviceToHost);
-    return rc ? drain_and_return(h, rc) : rc;
+    return estimate_batch_locked(h, kind, mem_space, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, budgets, n_budgets, out, inlier_mask);
 }
 
 } // extern "C"

@@ -88,7 +88,7 @@ class BatchPipeline:
 #       inside a large call).
 #   pageable host buffers (estimate_*_batch):  rounds 4-5 cut batches beyond 6144 pairs into 1024-pair chunks, two in flight, to hide the H2D
 #       copies (110-115 k pairs/s at 8192-16384 against 109 k for one call then).  Since round 6 a host-buffer call copies in 256-pair slices on
-#       its own copy stream beside the first kernels of the slices before (mdrp_capi.hip run_pass): ONE call is ahead there as well - 124.8 k
+#       its own copy stream beside the first kernels of the slices before (mdrp_capi.hip Pass::host_front): ONE call is ahead there as well - 124.8 k
 #       against 110.4 k at 8192 pairs, 120.9 k against 114.7 k at 16384.  The automatic chunking is therefore OFF by default
 #       (PIPELINE_MIN = 0: never); MDRP_PIPELINE_MIN=<pairs> switches it on for batches beyond that size, BatchPipeline stays for callers that
 #       have several independent batches to keep in flight.

@@ -228,7 +228,7 @@ def test_batches_larger_than_one_pass(monkeypatch):
 
 def test_host_buffer_call_in_h2d_slices_equals_the_resident_call():
     """a host-buffer call of >= 512 pairs copies the correspondences in 256-pair slices on the handle's copy stream and runs k_prep,
-    the first chunk and the second chunk's solver of each slice beside the next slice's copy (mdrp_capi.hip run_pass).  Pairs are independent units:
+    the first chunk and the second chunk's solver of each slice beside the next slice's copy (mdrp_capi.hip Pass::host_front).  Pairs are independent units:
     records and masks must equal those of the SAME batch resident on the device bit for bit — ragged counts (incl. pairs below the sample size), per-pair
     cameras, a last slice that is short (600 = 256 + 256 + 88), for all six estimators (tests/test_gpu_schedules.py: the shapes where the 5-point
     solver's first and second chunk used to share Reduce5 scratch)."""
@@ -271,7 +271,7 @@ def test_host_buffer_call_in_h2d_slices_equals_the_resident_call():
 
 def test_first_chunk_follows_the_inlier_ratio_of_the_previous_call_and_changes_no_result():
     """The first chunk of a run (scored exactly in full: no bar yet) is sized from the results of the handle's previous call with the same estimator
-    (mdrp_capi.hip run_pass; mdrp_stats::first_chunk): 256 iterations on a fresh handle; afterwards the mean over the previous call's pairs of
+    (mdrp_schedule.h default_lead; mdrp_stats::first_chunk): 256 iterations on a fresh handle; afterwards the mean over the previous call's pairs of
     6 / r^3 (r: the pair's inlier ratio; between 256 and 1024, 128 for a nearly outlier-free pair) — 80 % outliers: ~750; 50 %: 256; none: 128 — for
     runs of at least 8192 certain iterations, per estimator, never under MDRP_CHUNKS.  Records and masks of the same batch are identical whatever
     the length was."""

@@ -1,4 +1,4 @@
-"""Every schedule of run_pass (mdrp_capi.hip) must give the same records and masks, for all six estimators: one chunk on one stream (the plain
+"""Every schedule of run_pass (mdrp_capi.hip; the chunk rules: mdrp_schedule.h) must give the same records and masks, for all six estimators: one chunk on one stream (the plain
 sequential schedule), the three-stream chunk pipeline, the fused tail, and the sliced host-buffer front (a host-buffer call of >= 2 x HOST_SLICE_PAIRS
 pairs copies the correspondences in 256-pair slices; k_prep and the second chunk's solver of each slice run on the aux stream while the main stream
 solves and sweeps the first chunk).  The sequential schedule itself is anchored to the CPU oracle on the pairs around the slice edges."""
