@@ -139,7 +139,7 @@ int mdrp_create_on_stream_(int device, void *stream, mdrp_handle **out, int abi_
 void mdrp_destroy(mdrp_handle *h);
 const char *mdrp_last_error(void);
 /* "mdrp-hip <ver> (gfx950) MDRP_SRC_HASH=<16 hex digits>": the hash covers mdrp_capi.hip, mdrp_kernels.h, mdrp_math.h,
- * mdrp_classic.h, mdrp_classic_math.h, mdrp_frontend.h, mdrp_schedule.h and this header as they were when the library was built (mdrp_amd/build.py source_hash()) */
+ * mdrp_classic.h, mdrp_classic_math.h, mdrp_frontend.h, mdrp_schedule.h, mdrp_from_model.h and this header as they were when the library was built (mdrp_amd/build.py source_hash()) */
 const char *mdrp_version(void);
 /* (major << 16) | minor of the structs and entry points in this header = 0x00000006.  mdrp_ransac_opt grew from 72 to 88 bytes in
  * 0.4; 0.5 made the version check involuntary: handles are created through mdrp_create_ / mdrp_create_on_stream_, which take the host's
@@ -339,6 +339,47 @@ int mdrp_estimate_batch_budgets_async(mdrp_handle *h, int kind, const double *x1
                                       const uint64_t *budgets, int n_budgets, uint8_t *inlier_mask_dev);
 int mdrp_fetch_budget_results(mdrp_handle *h, mdrp_result *out_host, int n_budgets, int batch);
 int mdrp_copy_budget_results_device(mdrp_handle *h, void *dst_dev, int n_budgets, int batch);
+
+/* ---- Refine and verify caller-supplied models (added within ABI 0.6: new symbols only).
+ * One model per pair goes in, and the call runs exactly what the estimator runs from the moment RANSAC has picked its winner: the tail of
+ * ransac<> plus the wrapper's inlier-only refinement.  Nothing is sampled.  For pair b with n = n_per_pair[b] correspondences, the caller's
+ * model M0 (an mdrp_model in the caller's units, as the estimators return it: focals in pixels for the two focal kinds) and `stages`:
+ *   1. Prep, exactly the estimator's: unproject by the cameras (MDRP_CALIB) or divide by the normalisation scale (focal kinds; M0's focals are
+ *      divided by it as well); thresholds and loss scales as the estimator computes them from max_epipolar_error, max_reproj_error,
+ *      monodepth_weight_sampson (through float, clamped at 0), monodepth_estimate_shift (MDRP_CALIB only) and the caller's BundleOptions.
+ *      Every other RansacOptions field is ignored — iterations, seed, stopping rule, sampler switches: nothing samples, so nothing is refused.
+ *   2. S0, C0 = MSAC score and inlier count of M0 at the squared threshold: the estimator's exact fp64 sweep in record order (pose scoring
+ *      with cheirality for MDRP_CALIB, F from pose and focals for the focal kinds).
+ *   3. MDRP_STAGE_LO, unless M0.q[0] is NaN: M1 = LM from M0 over all n records (TRUNCATED loss at the LO's loss scale, 25 iterations, the LO's
+ *      fixed tolerances: ransac<>'s LO).  M1 is adopted with its own (S1, C1) iff S1 < S0; otherwise M0 stays with (S0, C0).  (The
+ *      estimator's record keeps the old score there, a reference quirk; here the adopted model's own score is reported.)
+ *   4. mask = get_inliers of the model kept so far; bytes at or past n are 0.
+ *   5. MDRP_STAGE_INLIERS, when the count exceeds 3 (MDRP_CALIB, MDRP_SHARED_FOCAL) or 7 (MDRP_VARYING_FOCAL): LM over the masked records with
+ *      the caller's BundleOptions at the estimator's final loss scale — the wrappers' inlier-only refinement.
+ *   6. Record: model = the final model, focals multiplied by the normalisation scale; model_score, num_inliers, inlier_ratio = count / n and
+ *      the mask describe the model that ENTERED stage 5 (the estimator's convention; call again with stages = 0 for the numbers of the returned
+ *      model); iterations = 0; refinements = LM runs executed (0 to 2).
+ *   7. initial_score[b] = S0, initial_inliers[b] = C0 (both optional).  A pair no LM ran on — stages = 0 (verification only), a NaN start
+ *      model — returns the caller's model BIT FOR BIT, without a focal round trip.  n < 3: the caller's model bit for bit, zeroed stats,
+ *      model_score = S0 = DBL_MAX, a zero mask (the estimators' rule).  A NaN start model scores n * threshold^2 with 0 inliers.
+ * The default stages = MDRP_STAGE_LO | MDRP_STAGE_INLIERS is the estimator's tail; MDRP_STAGE_INLIERS alone, started from ransac<>'s winner,
+ * gives the estimator's result.
+ * kind: MDRP_CALIB, MDRP_SHARED_FOCAL or MDRP_VARYING_FOCAL (any other kind is MDRP_ERR_INVALID).  MDRP_ERR_INVALID, before any device work:
+ * a NULL required buffer, a negative size, n_per_pair out of range, stages outside 0..3.
+ * x1, x2, d1, d2, models ([B]) and inlier_mask ([B][n_max] bytes or NULL) live in mem_space; n_per_pair, cameras, out ([B]), initial_score
+ * and initial_inliers ([B] each, or NULL) in HOST memory.  The call runs on the handle's stream, replaces the handle's last results and is
+ * synchronous with respect to `out`. */
+enum { MDRP_STAGE_LO = 1, MDRP_STAGE_INLIERS = 2 };
+int mdrp_refine_batch(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
+                      int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                      const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const mdrp_model *models, int stages, mdrp_result *out,
+                      uint8_t *inlier_mask, double *initial_score, int32_t *initial_inliers);
+/* Device-resident variant: nothing is copied back and the call does not wait.  The records stay in the handle's device buffers until
+ * mdrp_fetch_results / mdrp_copy_results_device; initial_score_dev / initial_inliers_dev are [B] in DEVICE memory or NULL. */
+int mdrp_refine_batch_async(mdrp_handle *h, int kind, const double *x1_dev, const double *x2_dev, const double *d1_dev, const double *d2_dev,
+                            int batch, int n_max, const int32_t *n_per_pair_host, const mdrp_camera *cam1_host, const mdrp_camera *cam2_host,
+                            const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const mdrp_model *models_dev, int stages,
+                            uint8_t *inlier_mask_dev, double *initial_score_dev, int32_t *initial_inliers_dev);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,9 @@ EXPORTS = (
     "mdrp_last_sweep_stats", "mdrp_last_stats", "mdrp_last_stats_sized", "mdrp_classic_solver_batch",
     "mdrp_gather_matches", "mdrp_estimate_matches_async",
     "mdrp_estimate_batch_budgets", "mdrp_estimate_batch_budgets_async", "mdrp_fetch_budget_results", "mdrp_copy_budget_results_device",
+    "mdrp_refine_batch", "mdrp_refine_batch_async",
 )
+STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
 MAX_BUDGETS = 16  # include/mdrp.h MDRP_MAX_BUDGETS
 F32, F64 = 0, 1  # mdrp_matches.kp_type / depth_type
 FILTERS = {"both_inf": 0, "finite": 1}  # mdrp_matches.filter (include/mdrp.h MDRP_FILTER_*)
@@ -139,6 +141,11 @@ def load_library():
                                                               C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp]
             lib.mdrp_fetch_budget_results.argtypes = [vp, vp, C.c_int, C.c_int]
             lib.mdrp_copy_budget_results_device.argtypes = [vp, vp, C.c_int, C.c_int]
+        if hasattr(lib, "mdrp_refine_batch"):  # (an older ABI-0.6 library through MDRP_LIB has no refine entry points: Handle._refine_fn raises)
+            lib.mdrp_refine_batch.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp, dp, ip]
+            lib.mdrp_refine_batch_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                    C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, dp, ip]
         _lib = lib
         return lib
 
@@ -414,6 +421,52 @@ class Handle:
     def copy_budget_results_device(self, dst_ptr, n_budgets, batch):
         """the records of the last budgets call into device memory at dst_ptr (n_budgets x batch x 136 bytes)"""
         _check(self._lib, self._budgets_fn("mdrp_copy_budget_results_device")(self._h, C.c_void_p(dst_ptr), int(n_budgets), int(batch)))
+
+    # ---- refine and verify caller-supplied models (include/mdrp.h: mdrp_refine_batch).  Arguments go to the library as they are: the library checks them.
+    def _refine_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the refine entry points (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    def refine_batch(self, kind, x1, x2, d1, d2, models, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
+        """B models (MODEL_DTYPE) against B pairs, host (numpy) buffers: (records, masks (B, N) uint8 or None, initial score (B,) float64,
+        initial inlier count (B,) int32)"""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+            raise ValueError("expected x1,x2 (B,N,2)")
+        d1 = np.ascontiguousarray(d1, dtype=np.float64)
+        d2 = np.ascontiguousarray(d2, dtype=np.float64)
+        if d1.shape != x1.shape[:2] or d2.shape != d1.shape:
+            raise ValueError("expected d1,d2 (B,N)")
+        B, N = x1.shape[:2]
+        models = None if models is None else np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
+        if models is not None and len(models) != B:
+            raise ValueError(f"expected {B} models, got {len(models)}")
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        out = np.zeros(B, dtype=RESULT_DTYPE)
+        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        score0, inl0 = np.zeros(B), np.zeros(B, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        _check(self._lib, self._refine_fn("mdrp_refine_batch")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
+                                                               C.byref(ropt), C.byref(bopt), _ptr(models), int(stages), _ptr(out), _ptr(mask), _ptr(score0), _ptr(inl0)))
+        return out, mask, score0, inl0
+
+    def refine_batch_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, models_ptr, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None,
+                            cam1=None, cam2=None, mask_ptr=None, initial_score_ptr=None, initial_inliers_ptr=None):
+        """the same on device pointers (ints), queued on the handle's stream; models_ptr: batch x 96 bytes; initial_score_ptr / initial_inliers_ptr:
+        batch float64 / int32 on the device, or None.  Records: fetch_results / copy_results_device."""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _check(self._lib, self._refine_fn("mdrp_refine_batch_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), int(batch), int(n_max),
+                                                                     _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(models_ptr), int(stages),
+                                                                     vp(mask_ptr), vp(initial_score_ptr), vp(initial_inliers_ptr)))
 
     # ---- device front end: a Matches descriptor of device pointers
     def gather_matches(self, mm, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):

@@ -6,7 +6,8 @@
 #include "mdrp_classic.h"
 #include "mdrp_frontend.h"
 #include "mdrp_schedule.h"
-// MDRP_SPLIT_TU (the default build): the k_final family and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
+#include "mdrp_from_model.h"
+// MDRP_SPLIT_TU (the default build): the k_final family, k_from_model and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
 #define MDRP_INST extern
@@ -15,6 +16,7 @@ namespace mdrp {
 MDRP_INSTANCES_FINAL_64
 MDRP_INSTANCES_FINAL_256
 MDRP_INSTANCES_CLASSIC
+MDRP_INSTANCES_FROM_MODEL
 }
 #endif
 
@@ -175,6 +177,7 @@ struct mdrp_handle {
     DevBuf ckpt, ck_list, bresults, bmask;
     int last_budgets = 0;              // budgets of the last call (0: it had none)
     DevBuf in_x1, in_x2, in_d1, in_d2; // staging when the caller passes host memory
+    DevBuf fm_models, fm_init;         // mdrp_refine_batch: the caller's models when they come from host memory | start-model scores [batch] f64, counts [batch] i32
     DevBuf fe_x1, fe_x2, fe_d1, fe_d2, fe_slot, fe_n; // device front end (mdrp_estimate_matches_async): gathered correspondences | slot of every match row | kept rows per pair
     Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
     size_t fe_n_host_cap = 0;
@@ -1315,6 +1318,146 @@ int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const d
     if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
     MDRP_ENTER(h);
     return estimate_batch_locked(h, kind, mem_space, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, budgets, n_budgets, out, inlier_mask);
+}
+
+} // extern "C"
+
+// ---- refine and verify caller-supplied models (include/mdrp.h; mdrp_from_model.h)
+// k_prep as the estimators launch it (no MFMA fragments, no sample tables, score_initial = 0), then ONE launch of k_from_model on the handle's stream:
+// nothing else of a pass is allocated or run.  Pointers are device memory, `models` included; initial_* may be null.
+static int refine_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
+                         const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
+                         const Model *models, int stages, uint8_t *mask_dev, double *init_score, int32_t *init_inl) {
+    hipStream_t s = h->stream;
+    const int est_shift = (kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0;
+    h->last_budgets = 0;
+    h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
+    int rc;
+    if ((rc = h->results.ensure(sizeof(ResultDev) * std::max(batch, 1))) || (rc = h->lm_stats.ensure(LM_STATS_BYTES))) return rc;
+    HIPCHK(hipMemsetAsync(h->lm_stats.p, 0, LM_STATS_BYTES, s));
+    if (batch == 0) return MDRP_OK;
+    const size_t b = (size_t)batch, n = (size_t)n_max;
+    // per-call parameters in one block: cameras 1 | cameras 2 | table of pair (zeros: there are no sample tables) | n per pair.  Staged in pageable
+    // memory (the copy has left it when hipMemcpyAsync returns): an asynchronous call may be followed by the next one before the stream has drained
+    const size_t off_cam2 = sizeof(CamDev) * b, off_tof = 2 * sizeof(CamDev) * b, off_nper = off_tof + sizeof(int32_t) * b, bytes = off_nper + sizeof(int32_t) * b;
+    std::vector<unsigned char> params(bytes, 0);
+    if (kind == MDRP_CALIB) { std::memcpy(params.data(), cam1, sizeof(CamDev) * b); std::memcpy(params.data() + off_cam2, cam2, sizeof(CamDev) * b); }
+    int32_t *nper = reinterpret_cast<int32_t *>(params.data() + off_nper);
+    for (int i = 0; i < batch; ++i) nper[i] = n_per_pair ? n_per_pair[i] : n_max;
+    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * b * n)) || (rc = h->dep.ensure(sizeof(double) * 2 * b * n)) || (rc = h->st.ensure(sizeof(PairState) * b)) ||
+        (rc = h->params.ensure(bytes)))
+        return rc;
+    uint8_t *mask = mask_dev;
+    if (!mask) {
+        if ((rc = h->mask.ensure(b * std::max(n_max, 1)))) return rc;
+        mask = h->mask.as<uint8_t>();
+    }
+    unsigned char *pd = h->params.as<unsigned char>();
+    HIPCHK(hipMemcpyAsync(pd, params.data(), bytes, hipMemcpyHostToDevice, s));
+
+    RunParams rp;
+    std::memset(&rp, 0, sizeof rp);
+    rp.kind = kind; rp.solver = solver_for(kind, est_shift); rp.est_shift = est_shift;
+    rp.batch = batch; rp.n_max = n_max;
+    rp.weight_sampson = ro->monodepth_weight_sampson > 0.0f ? (double)ro->monodepth_weight_sampson : 0.0;
+    rp.final_max_it = (int)std::min<uint64_t>(bo->max_iterations, 1u << 30); rp.final_loss = bo->loss_type;
+    rp.grad_tol = bo->gradient_tol; rp.step_tol = bo->step_tol; rp.lambda0 = bo->initial_lambda;
+    rp.lambda_min = bo->min_lambda; rp.lambda_max = bo->max_lambda;
+    hipLaunchKernelGGL(k_prep, dim3(batch), dim3(256), 0, s, rp, x1, x2, d1, d2, reinterpret_cast<const int32_t *>(pd + off_nper),
+                       reinterpret_cast<const int32_t *>(pd + off_tof), reinterpret_cast<const CamDev *>(pd), reinterpret_cast<const CamDev *>(pd + off_cam2),
+                       ro->max_epipolar_error, ro->max_reproj_error, bo->loss_scale, h->pts.as<double>(), h->dep.as<double>(), h->st.as<PairState>(),
+                       (uint4 *)nullptr);
+    hipEvent_t f0, f1; // reported as the final refinement's time (mdrp_stats::final_ms / final_launches)
+    if ((rc = get_events(h, &f0, &f1, 3))) return rc;
+    HIPCHK(hipEventRecord(f0, s));
+    const size_t smem = lm_final_list_bytes(n_max);
+    const int stride = lm_list_stride(n_max), midx = lm_mask_index_on(n_max);
+#define MDRP_FROM_MODEL_LAUNCH(K, S)                                                                                                                      \
+    hipLaunchKernelGGL((k_from_model<K, S>), dim3(batch), dim3(FROM_MODEL_THREADS), smem, s, rp, (const PairState *)h->st.as<PairState>(),                \
+                       (const double *)h->pts.as<double>(), (const double *)h->dep.as<double>(), models, stages, mask, h->results.as<ResultDev>(), init_score, \
+                       init_inl, stride, midx, h->lm_stats.as<unsigned long long>() + 2)
+    if (kind == MDRP_CALIB && est_shift) MDRP_FROM_MODEL_LAUNCH(0, true);
+    else if (kind == MDRP_CALIB) MDRP_FROM_MODEL_LAUNCH(0, false);
+    else if (kind == MDRP_SHARED_FOCAL) MDRP_FROM_MODEL_LAUNCH(1, false);
+    else MDRP_FROM_MODEL_LAUNCH(2, false);
+#undef MDRP_FROM_MODEL_LAUNCH
+    HIPCHK(hipEventRecord(f1, s));
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+// what both entry points refuse before any device work
+static int check_refine_args(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
+                             const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
+                             const mdrp_model *models, int stages) {
+    const char *why = nullptr;
+    if (!h || !ro || !bo) why = "invalid argument";
+    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "refine: only the monodepth estimators' models (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL)";
+    else if (batch < 0 || n_max < 0) why = "refine: a negative size";
+    else if (stages < 0 || stages > (MDRP_STAGE_LO | MDRP_STAGE_INLIERS)) why = "refine: stages must be a combination of MDRP_STAGE_LO and MDRP_STAGE_INLIERS";
+    else if (batch > 0 && !models) why = "refine: models is NULL";
+    else if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) why = "refine: correspondences and depths are required";
+    else if (kind == MDRP_CALIB && batch > 0 && (!cam1 || !cam2)) why = "calibrated estimator needs cameras";
+    for (int i = 0; !why && n_per_pair && i < batch; ++i)
+        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+extern "C" {
+
+static_assert(MDRP_STAGE_LO == STAGE_LO && MDRP_STAGE_INLIERS == STAGE_INLIERS, "stage flags of the header and of the kernel");
+
+int mdrp_refine_batch_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
+                            const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                            const mdrp_bundle_opt *bopt, const mdrp_model *models_dev, int stages, uint8_t *inlier_mask_dev, double *initial_score_dev,
+                            int32_t *initial_inliers_dev) {
+    if (int rc = check_refine_args(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev, stages)) return rc;
+    MDRP_ENTER(h);
+    const int rc = refine_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, reinterpret_cast<const Model *>(models_dev), stages,
+                                 inlier_mask_dev, initial_score_dev, initial_inliers_dev);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_refine_batch(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
+                      const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                      const mdrp_model *models, int stages, mdrp_result *out, uint8_t *inlier_mask, double *initial_score, int32_t *initial_inliers) {
+    if (int rc = check_refine_args(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models, stages)) return rc;
+    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
+    hipStream_t s = h->stream;
+    int rc;
+    const Model *models_dev = reinterpret_cast<const Model *>(models);
+    if (use_host && batch > 0) { // plain copies on the handle's stream
+        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
+            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)) || (rc = h->fm_models.ensure(sizeof(Model) * b)))
+            return rc;
+        if (np > 0) {
+            HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
+        }
+        HIPCHK(hipMemcpyAsync(h->fm_models.p, models, sizeof(Model) * b, hipMemcpyHostToDevice, s));
+        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>(); d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
+        models_dev = h->fm_models.as<Model>();
+    }
+    // the start-model scores are host outputs whatever mem_space says: a buffer of the handle, copied back
+    const size_t off_inl = sizeof(double) * b;
+    if ((initial_score || initial_inliers) && (rc = h->fm_init.ensure(off_inl + sizeof(int32_t) * b + 16))) return rc;
+    double *is_dev = initial_score ? h->fm_init.as<double>() : nullptr;
+    int32_t *ii_dev = initial_inliers ? reinterpret_cast<int32_t *>(h->fm_init.as<unsigned char>() + off_inl) : nullptr;
+    rc = refine_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev, stages, use_host ? nullptr : inlier_mask, is_dev, ii_dev);
+    if (rc) return drain_and_return(h, rc);
+    hipError_t e = hipSuccess;
+    if (use_host && inlier_mask && np > 0) e = hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && is_dev && batch > 0) e = hipMemcpyAsync(initial_score, is_dev, sizeof(double) * b, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && ii_dev && batch > 0) e = hipMemcpyAsync(initial_inliers, ii_dev, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) { g_err = "copy of the masks or start-model scores failed"; return drain_and_return(h, MDRP_ERR_HIP); }
+    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
+    return rc ? drain_and_return(h, rc) : rc;
 }
 
 } // extern "C"

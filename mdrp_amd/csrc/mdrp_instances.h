@@ -2,6 +2,7 @@
 // mdrp_capi.hip declares them `extern template`).  MDRP_INST is `extern` in the declaring unit and empty in the defining one.
 //   group 1 / 2: k_final<KIND, SHIFT, T = 64 / 256, FLOSS> for the four LM estimators x the six loss types of BundleOptions
 //   group 3:     the kernels of the 5- / 6- / 7-point baselines (mdrp_classic.h)
+//   group 4:     k_from_model<KIND, SHIFT> for the four LM estimators (mdrp_from_model.h)
 #pragma once
 namespace mdrp {
 #define MDRP_FINAL_PARAMS RunParams, PairState *, const double *, const double *, uint8_t *, ResultDev *, int, int, unsigned long long *, const int32_t *, int32_t *, \
@@ -19,6 +20,10 @@ namespace mdrp {
 #define MDRP_KC_SOLVE_ONE(CK) MDRP_INST template __global__ void kc_solve<CK>(RunParams, const PairState *, const uint32_t *, const double *, Model *, int32_t *, uint32_t *, int32_t *);
 #define MDRP_KC_UNIT_ONE(CK) MDRP_INST template __global__ void kc_solver_unit<CK>(int, const double *, const double *, Model *, int32_t *);
 #define MDRP_KC_SAMPLES_ONE(K) MDRP_INST template __global__ void kc_samples<K>(int, const int32_t *, uint64_t *, int, uint32_t *);
+
+#define MDRP_FROM_MODEL_ONE(K, S) MDRP_INST template __global__ void k_from_model<K, S>(RunParams, const PairState *, const double *, const double *, const Model *, int, \
+                                                                                      uint8_t *, ResultDev *, double *, int32_t *, int, int, unsigned long long *);
+#define MDRP_INSTANCES_FROM_MODEL MDRP_FROM_MODEL_ONE(0, false) MDRP_FROM_MODEL_ONE(0, true) MDRP_FROM_MODEL_ONE(1, false) MDRP_FROM_MODEL_ONE(2, false)
 
 #define MDRP_INSTANCES_FINAL_64 MDRP_FINAL_KINDS(MDRP_FINAL_ONE, 64)
 #define MDRP_INSTANCES_FINAL_256 MDRP_FINAL_KINDS(MDRP_FINAL_ONE, 256)

@@ -3,6 +3,7 @@
 #define MDRP_SECONDARY_TU 1
 #include "mdrp_kernels.h"
 #include "mdrp_classic.h"
+#include "mdrp_from_model.h"
 #define MDRP_INST
 #include "mdrp_instances.h"
 namespace mdrp {
@@ -12,7 +13,9 @@ MDRP_INSTANCES_FINAL_64
 MDRP_INSTANCES_FINAL_256
 #elif MDRP_TU == 3
 MDRP_INSTANCES_CLASSIC
+#elif MDRP_TU == 4
+MDRP_INSTANCES_FROM_MODEL
 #else
-#error "MDRP_TU must be 1 (k_final, 64 lanes), 2 (k_final, 256 lanes) or 3 (5- / 6- / 7-point baselines)"
+#error "MDRP_TU must be 1 (k_final, 64 lanes), 2 (k_final, 256 lanes), 3 (5- / 6- / 7-point baselines) or 4 (k_from_model)"
 #endif
 } // namespace mdrp

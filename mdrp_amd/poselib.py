@@ -810,3 +810,155 @@ def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, de
         res = h.fetch_results(B)
     del keep
     return res, match_mask, n_used
+
+
+# ------------------------------------------------------------------------------------------------ refine / verify caller-supplied models
+# The counterpart of PoseLib's refine_relative_pose for the three monodepth estimators (include/mdrp.h mdrp_refine_batch): one model
+# per pair goes in and the estimator's tail runs on it — score, LO, inlier mask, inlier-only refinement — without a single sample.  A pose from the
+# previous video frame, an SfM database or a coarse first pass is refined for the price of the tail; stages=() only counts its inliers with the
+# estimator's thresholds, normalisation and cheirality rule.  Of ransac_opt only max_epipolar_error, max_reproj_error, monodepth_weight_sampson and
+# monodepth_estimate_shift are read; nothing is refused.
+_STAGES = {"lo": _capi.STAGE_LO, "inliers": _capi.STAGE_INLIERS}
+
+
+def _stage_flags(stages):
+    """("lo", "inliers") | a subset | () | the integer flags themselves -> MDRP_STAGE_* flags"""
+    if isinstance(stages, (int, np.integer)) and not isinstance(stages, bool):
+        return int(stages)
+    if isinstance(stages, str):
+        stages = (stages,)
+    flags = 0
+    for s in stages:
+        if s not in _STAGES:
+            raise ValueError(f"stages must be drawn from {tuple(_STAGES)}, not {s!r}")
+        flags |= _STAGES[s]
+    return flags
+
+
+def _model_records(initial, kind):
+    """list of MonoDepthTwoViewGeometry (calibrated) / MonoDepthImagePair (focal kinds; focals from the two cameras), or a ready MODEL_DTYPE array"""
+    if isinstance(initial, np.ndarray) and initial.dtype == _capi.MODEL_DTYPE:
+        return np.ascontiguousarray(initial).reshape(-1)
+    out = np.zeros(len(initial), dtype=_capi.MODEL_DTYPE)
+    for i, obj in enumerate(initial):
+        g = getattr(obj, "geometry", obj)
+        out[i]["q"] = g.pose.q; out[i]["t"] = g.pose.t
+        out[i]["scale"], out[i]["shift1"], out[i]["shift2"] = g.scale, g.shift1, g.shift2
+        focal = kind != _capi.CALIB and hasattr(obj, "camera1")
+        out[i]["f1"] = obj.camera1.focal() if focal else 1.0
+        out[i]["f2"] = obj.camera2.focal() if focal else 1.0
+    return out
+
+
+def _refine_info(res, mask_row, n, score0, inl0):
+    info = _info(res, mask_row, n)
+    info["initial_score"], info["initial_inliers"] = float(score0), int(inl0)
+    return info
+
+
+def _refine_host(kind, points2D_1, points2D_2, depth_1, depth_2, initial, cameras1, cameras2, ransac_opt, bundle_opt, device, stages, as_arrays):
+    x1, x2, d1, d2, ns = _stack(points2D_1, points2D_2, depth_1, depth_2)
+    B = len(ns)
+    models = _model_records(initial, kind)
+    if len(models) != B:
+        raise ValueError(f"expected {B} initial models, got {len(models)}")
+    cams1 = cams2 = None
+    if kind == _capi.CALIB:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    res, mask, score0, inl0 = _capi.default_handle(device).refine_batch(kind, x1, x2, d1, d2, models, _capi.ransac_opt_from_dict(ransac_opt),
+                                                                        _capi.bundle_opt_from_dict(bundle_opt), _stage_flags(stages), ns, cams1, cams2)
+    if as_arrays:
+        return res, mask, ns, score0, inl0
+    wrap = _geometry_from_model if kind == _capi.CALIB else _pair_from_model
+    return [wrap(r["model"]) for r in res], [_refine_info(res[i], mask[i], ns[i], score0[i], inl0[i]) for i in range(B)]
+
+
+def refine_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, cameras1, cameras2, geometries, ransac_opt=None, bundle_opt=None,
+                                         device=0, stages=("lo", "inliers"), as_arrays=False):
+    """B calibrated pairs, each with a MonoDepthTwoViewGeometry to start from (or a MODEL_DTYPE array).  Returns (list[MonoDepthTwoViewGeometry],
+    list[info dict]): the estimators' info keys describing the model that entered the inlier-only refinement, plus `initial_score` and
+    `initial_inliers` of the model handed in.  as_arrays=True: (records, masks, n_per_pair, initial scores, initial inlier counts)."""
+    return _refine_host(_capi.CALIB, points2D_1, points2D_2, depth_1, depth_2, geometries, cameras1, cameras2, ransac_opt, bundle_opt, device, stages, as_arrays)
+
+
+def refine_monodepth_shared_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, image_pairs, ransac_opt=None, bundle_opt=None,
+                                                      device=0, stages=("lo", "inliers"), as_arrays=False):
+    """B pairs of principal-point-centred pixels, each with a MonoDepthImagePair to start from (focals: camera1 / camera2 .focal(), in pixels)"""
+    return _refine_host(_capi.SHARED_FOCAL, points2D_1, points2D_2, depth_1, depth_2, image_pairs, None, None, ransac_opt, bundle_opt, device, stages, as_arrays)
+
+
+def refine_monodepth_varying_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, image_pairs, ransac_opt=None, bundle_opt=None,
+                                                       device=0, stages=("lo", "inliers"), as_arrays=False):
+    return _refine_host(_capi.VARYING_FOCAL, points2D_1, points2D_2, depth_1, depth_2, image_pairs, None, None, ransac_opt, bundle_opt, device, stages, as_arrays)
+
+
+def _need_initial(initial, what):
+    if initial is None:
+        raise ValueError(f"{what} is required: there is nothing to refine without a model to start from")
+    return [initial]
+
+
+def refine_monodepth_relative_pose(points2D_1, points2D_2, depth_1, depth_2, camera1, camera2, ransac_opt={}, bundle_opt={}, initial_pose=None,
+                                   stages=("lo", "inliers")):
+    """estimate_monodepth_relative_pose's arguments; initial_pose (a MonoDepthTwoViewGeometry) is READ here.  Returns (geometry, info)."""
+    g, i = refine_monodepth_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1], [depth_2], camera1, camera2,
+                                                _need_initial(initial_pose, "initial_pose"), ransac_opt, bundle_opt, stages=stages)
+    return g[0], i[0]
+
+
+def refine_monodepth_shared_focal_relative_pose(points2D_1, points2D_2, depth_1, depth_2, ransac_opt={}, bundle_opt={}, initial_image_pair=None,
+                                                stages=("lo", "inliers")):
+    p, i = refine_monodepth_shared_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1], [depth_2],
+                                                             _need_initial(initial_image_pair, "initial_image_pair"), ransac_opt, bundle_opt, stages=stages)
+    return p[0], i[0]
+
+
+def refine_monodepth_varying_focal_relative_pose(points2D_1, points2D_2, depth_1, depth_2, ransac_opt={}, bundle_opt={}, initial_image_pair=None,
+                                                 stages=("lo", "inliers")):
+    p, i = refine_monodepth_varying_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1], [depth_2],
+                                                              _need_initial(initial_image_pair, "initial_image_pair"), ransac_opt, bundle_opt, stages=stages)
+    return p[0], i[0]
+
+
+def refine_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, models, cameras1=None, cameras2=None, ransac_opt=None, bundle_opt=None,
+                       n_per_pair=None, stages=("lo", "inliers")):
+    """The same on a batch that already lives on the GPU (inputs as estimate_batch_torch), queued on the device's current torch stream.
+    models: one per pair — a device tensor holding B records of 96 bytes (uint8 (B, 96), or float64 (B, 12): q t scale shift1 shift2 f1 f2; e.g.
+    written by a torch op just before the call), or a numpy array of _capi.MODEL_DTYPE, which is uploaded on that stream.  Returns (records,
+    inlier mask: (B, N) uint8 device tensor, initial: {"score": (B,) float64, "inliers": (B,) int32} numpy arrays of the models handed in)."""
+    import torch
+    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
+    k = kinds[kind] if isinstance(kind, str) else int(kind)
+    flags = _stage_flags(stages)
+    x1, x2, d1, d2 = (t.contiguous() for t in (points2D_1, points2D_2, depth_1, depth_2))
+    for t in (x1, x2, d1, d2):
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise ValueError("refine_batch_torch needs float64 tensors on the GPU")
+        if t.device != x1.device:
+            raise ValueError("all tensors must live on the same device")
+    B, N = d1.shape
+    if x1.shape != (B, N, 2) or x2.shape != (B, N, 2) or d2.shape != (B, N):
+        raise ValueError("shapes must be (B, N, 2), (B, N, 2), (B, N), (B, N)")
+    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
+    if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
+        n_per_pair = n_per_pair.detach().cpu().numpy()
+    cams1 = cams2 = None
+    if k == _capi.CALIB:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    with torch.cuda.device(x1.device):
+        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        if isinstance(models, np.ndarray):
+            models = torch.from_numpy(np.ascontiguousarray(models, dtype=_capi.MODEL_DTYPE).reshape(-1).view(np.uint8).copy()).to(x1.device)
+        if not (isinstance(models, torch.Tensor) and models.is_cuda and models.device == x1.device and models.dtype in (torch.uint8, torch.float64)):
+            raise ValueError("models must be a uint8 / float64 tensor on the inputs' device or a numpy array of _capi.MODEL_DTYPE")
+        models = models.contiguous()
+        if models.numel() * models.element_size() != B * _capi.MODEL_DTYPE.itemsize:
+            raise ValueError(f"models must hold {B} records of {_capi.MODEL_DTYPE.itemsize} bytes")
+        mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
+        score0 = torch.zeros(B, dtype=torch.float64, device=x1.device)
+        inl0 = torch.zeros(B, dtype=torch.int32, device=x1.device)
+        h.refine_batch_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), B, N, models.data_ptr(), _capi.ransac_opt_from_dict(ransac_opt),
+                              _capi.bundle_opt_from_dict(bundle_opt), flags, n_per_pair, cams1, cams2, mask.data_ptr(), score0.data_ptr(), inl0.data_ptr())
+        res = h.fetch_results(B)  # (waits for the stream: the two small tensors below are complete)
+        initial = {"score": score0.cpu().numpy(), "inliers": inl0.cpu().numpy()}
+    return res, mask, initial
