@@ -340,6 +340,42 @@ int mdrp_estimate_batch_budgets_async(mdrp_handle *h, int kind, const double *x1
 int mdrp_fetch_budget_results(mdrp_handle *h, mdrp_result *out_host, int n_budgets, int batch);
 int mdrp_copy_budget_results_device(mdrp_handle *h, void *dst_dev, int n_budgets, int batch);
 
+/* ---- The device front end on per-image tables (added within ABI 0.6: new symbols only).
+ * A batch of pairs as its producer holds it: a video matches every frame against one anchor, an SfM front end matches each image against
+ * many others — an image's keypoints and its depth map exist ONCE, and pair b is two indices (a, c) = pairs[b] into the image set.
+ * mdrp_matches wants every image's tables copied once per pair the image takes part in; this descriptor does not.
+ * For pair b: if a or c is outside [0, n_images), every row of the pair is dropped — n[b] = 0, every slot is -1, the buffers hold the
+ * filler (x = 0, d = 1) — and nothing is read through the bad index.  Otherwise rules 1-5 of mdrp_matches apply unchanged with
+ *   kp1 = kp[a], k1 = kp_count[a], depth1 = depth[a], (h1, w1) = size[a], center1 = center[a]
+ * and the same from c for image 2.  a == c and repeated pairs are legal.  Every pointer of the descriptor is DEVICE memory. */
+typedef struct {
+    const void *kp;                /* [I][k_max][2] keypoints (x, y) in pixels of their image's depth map */
+    int32_t kp_type;               /* MDRP_F32 | MDRP_F64 */
+    int32_t k_max;                 /* keypoint rows allocated per image */
+    const int32_t *kp_count;       /* [I] valid keypoints of each image, clamped to [0, k_max]; NULL = k_max for all */
+    const void *depth;             /* [I][h_max][w_max] depth maps: the row stride is always w_max */
+    int32_t depth_type;            /* MDRP_F32 | MDRP_F64 */
+    int32_t h_max, w_max;          /* rows and columns allocated per map */
+    const int32_t *size;           /* [I][2] (h, w): valid region of each map, clamped to [0, h_max] x [0, w_max]; NULL = the full map */
+    const double *center;          /* [I][2] or NULL */
+    int32_t n_images;              /* I */
+    const int32_t *pairs;          /* [B][2] image indices (a, c) */
+    const int32_t *matches;        /* [B][m_max][2] index pairs (i into kp[a], j into kp[c]); a negative index marks a padding row */
+    int32_t m_max;                 /* match rows per pair */
+    int32_t filter;                /* MDRP_FILTER_BOTH_INF | MDRP_FILTER_FINITE */
+} mdrp_image_pairs;
+
+/* Shaped exactly like mdrp_gather_matches and mdrp_estimate_matches_async: same outputs, same one stream synchronisation (the counts), then
+ * the resident estimator on the gathered buffers with n_max = m_max and the counts.  Cameras stay ONE RECORD PER PAIR ([B], host memory): a
+ * caller with per-image cameras expands them by pairs.  MDRP_ERR_INVALID, before any device work: a NULL descriptor, an unknown type or
+ * filter, a negative size or n_images, batch > 0 and m_max > 0 with pairs or matches NULL, kp NULL with n_images > 0 and k_max > 0, depth NULL
+ * with n_images > 0, h_max > 0 and w_max > 0; a kind other than MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL. */
+int mdrp_gather_image_pairs(mdrp_handle *h, const mdrp_image_pairs *ip, int batch, double *x1, double *x2, double *d1, double *d2,
+                            int32_t *slot, int32_t *n_host);
+int mdrp_estimate_image_pairs_async(mdrp_handle *h, int kind, const mdrp_image_pairs *ip, int batch, const mdrp_camera *cam1_host,
+                                    const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                    uint8_t *match_mask_dev, int32_t *n_used_host);
+
 /* ---- Refine and verify caller-supplied models (added within ABI 0.6: new symbols only).
  * One model per pair goes in, and the call runs exactly what the estimator runs from the moment RANSAC has picked its winner: the tail of
  * ransac<> plus the wrapper's inlier-only refinement.  Nothing is sampled.  For pair b with n = n_per_pair[b] correspondences, the caller's

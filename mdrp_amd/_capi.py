@@ -24,6 +24,7 @@ EXPORTS = (
     "mdrp_gather_matches", "mdrp_estimate_matches_async",
     "mdrp_estimate_batch_budgets", "mdrp_estimate_batch_budgets_async", "mdrp_fetch_budget_results", "mdrp_copy_budget_results_device",
     "mdrp_refine_batch", "mdrp_refine_batch_async",
+    "mdrp_gather_image_pairs", "mdrp_estimate_image_pairs_async",
 )
 STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
 MAX_BUDGETS = 16  # include/mdrp.h MDRP_MAX_BUDGETS
@@ -70,6 +71,13 @@ class Matches(C.Structure):
                 ("matches", C.c_void_p), ("m_max", C.c_int32), ("depth1", C.c_void_p), ("depth2", C.c_void_p), ("depth_type", C.c_int32),
                 ("h1", C.c_int32), ("w1", C.c_int32), ("h2", C.c_int32), ("w2", C.c_int32), ("center1", C.c_void_p), ("center2", C.c_void_p),
                 ("filter", C.c_int32)]
+
+
+class ImagePairs(C.Structure):
+    """mdrp_image_pairs (within ABI 0.6): per-image keypoint tables and depth maps, pairs as image indices, every pointer in device memory"""
+    _fields_ = [("kp", C.c_void_p), ("kp_type", C.c_int32), ("k_max", C.c_int32), ("kp_count", C.c_void_p), ("depth", C.c_void_p),
+                ("depth_type", C.c_int32), ("h_max", C.c_int32), ("w_max", C.c_int32), ("size", C.c_void_p), ("center", C.c_void_p),
+                ("n_images", C.c_int32), ("pairs", C.c_void_p), ("matches", C.c_void_p), ("m_max", C.c_int32), ("filter", C.c_int32)]
 
 
 class Result(C.Structure):
@@ -146,6 +154,9 @@ def load_library():
                                               C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp, dp, ip]
             lib.mdrp_refine_batch_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                     C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, dp, ip]
+        if hasattr(lib, "mdrp_gather_image_pairs"):  # (an older ABI-0.6 library through MDRP_LIB has no image-pairs entry points: Handle._image_pairs_fn raises)
+            lib.mdrp_gather_image_pairs.argtypes = [vp, C.POINTER(ImagePairs), C.c_int, dp, dp, dp, dp, ip, ip]
+            lib.mdrp_estimate_image_pairs_async.argtypes = [vp, C.c_int, C.POINTER(ImagePairs), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
         _lib = lib
         return lib
 
@@ -484,6 +495,30 @@ class Handle:
         n = np.zeros(int(batch), dtype=np.int32)
         _check(self._lib, self._lib.mdrp_estimate_matches_async(self._h, int(kind), C.byref(mm), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
                                                                 C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
+        return n
+
+    # ---- the same on per-image tables: an ImagePairs descriptor of device pointers
+    def _image_pairs_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: rebuild (mdrp_amd/build.py)")
+        return fn
+
+    def gather_image_pairs(self, ip, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
+        """k_gather_images alone into the caller's device buffers; returns the kept rows per pair (numpy int32).  Synchronises the stream once."""
+        n = np.zeros(int(batch), dtype=np.int32)
+        _check(self._lib, self._image_pairs_fn("mdrp_gather_image_pairs")(self._h, C.byref(ip), int(batch), C.c_void_p(x1_ptr), C.c_void_p(x2_ptr),
+                                                                          C.c_void_p(d1_ptr), C.c_void_p(d2_ptr), C.c_void_p(slot_ptr), _ptr(n)))
+        return n
+
+    def estimate_image_pairs_device(self, kind, ip, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
+        """front end on per-image tables + estimator on the handle's stream; cam1 / cam2 are per PAIR; results stay on the device (fetch_results /
+        copy_results_device).  Returns the kept rows per pair (numpy int32)."""
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        n = np.zeros(int(batch), dtype=np.int32)
+        _check(self._lib, self._image_pairs_fn("mdrp_estimate_image_pairs_async")(self._h, int(kind), C.byref(ip), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt),
+                                                                                  C.byref(bopt), C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
         return n
 
     def fetch_results(self, batch):

@@ -1493,6 +1493,41 @@ static int gather_device(mdrp_handle *h, const mdrp_matches *mm, int batch, doub
     return MDRP_OK;
 }
 
+// the same for mdrp_image_pairs
+static int check_image_pairs(const mdrp_image_pairs *ip, int batch) {
+    const char *why = nullptr;
+    if (!ip || batch < 0) why = "invalid argument";
+    else if ((ip->kp_type != MDRP_F32 && ip->kp_type != MDRP_F64) || (ip->depth_type != MDRP_F32 && ip->depth_type != MDRP_F64)) why = "kp_type / depth_type must be MDRP_F32 or MDRP_F64";
+    else if (ip->filter != MDRP_FILTER_BOTH_INF && ip->filter != MDRP_FILTER_FINITE) why = "unknown filter";
+    else if (ip->k_max < 0 || ip->m_max < 0 || ip->h_max < 0 || ip->w_max < 0 || ip->n_images < 0) why = "negative size";
+    else if (batch > 0 && ip->m_max > 0 && (!ip->pairs || !ip->matches)) why = "NULL pairs or matches";
+    else if (ip->n_images > 0 && ip->k_max > 0 && !ip->kp) why = "NULL keypoints";
+    else if (ip->n_images > 0 && ip->h_max > 0 && ip->w_max > 0 && !ip->depth) why = "NULL depth maps";
+    if (why) { g_err = std::string("mdrp_image_pairs: ") + why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+// k_gather_images on the handle's stream (the descriptor has passed check_image_pairs); n_dev: [batch] on the device
+static int gather_images_device(mdrp_handle *h, const mdrp_image_pairs *ip, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
+                                int32_t *n_dev) {
+    if (batch == 0) return MDRP_OK;
+    if (ip->m_max == 0) { // no rows, and pairs may be NULL: the counts are all there is to write
+        HIPCHK(hipMemsetAsync(n_dev, 0, sizeof(int32_t) * batch, h->stream));
+        return MDRP_OK;
+    }
+#define MDRP_GATHER(KT, DT)                                                                                                                \
+    hipLaunchKernelGGL((k_gather_images<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)ip->kp, ip->kp_count, ip->k_max,  \
+                       (const DT *)ip->depth, ip->size, ip->h_max, ip->w_max, ip->center, ip->n_images, ip->pairs, ip->matches, ip->m_max,  \
+                       ip->filter, x1, x2, d1, d2, slot, n_dev)
+    if (ip->kp_type == MDRP_F32 && ip->depth_type == MDRP_F32) MDRP_GATHER(float, float);
+    else if (ip->kp_type == MDRP_F32) MDRP_GATHER(float, double);
+    else if (ip->depth_type == MDRP_F32) MDRP_GATHER(double, float);
+    else MDRP_GATHER(double, double);
+#undef MDRP_GATHER
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
 // the counts of the last gather into the handle's pinned block: the one stream synchronisation of the front end
 static int fetch_counts(mdrp_handle *h, int batch) {
     if (batch == 0) return MDRP_OK;
@@ -1504,6 +1539,42 @@ static int fetch_counts(mdrp_handle *h, int batch) {
     }
     HIPCHK(hipMemcpyAsync(h->fe_n_host, h->fe_n.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return MDRP_OK;
+}
+
+static int check_front_end_kind(int kind, const char *who) {
+    if (kind == MDRP_CALIB || kind == MDRP_SHARED_FOCAL || kind == MDRP_VARYING_FOCAL) return MDRP_OK;
+    g_err = std::string(who) + ": only the monodepth estimators (kind 0..2) take depth maps";
+    return MDRP_ERR_INVALID;
+}
+
+// the handle's gather buffers for batch pairs of m_max rows
+static int ensure_gather_buffers(mdrp_handle *h, int batch, int m_max) {
+    const size_t rows = (size_t)batch * m_max;
+    int rc;
+    if ((rc = h->fe_x1.ensure(sizeof(double) * 2 * rows + 16)) || (rc = h->fe_x2.ensure(sizeof(double) * 2 * rows + 16)) ||
+        (rc = h->fe_d1.ensure(sizeof(double) * rows + 16)) || (rc = h->fe_d2.ensure(sizeof(double) * rows + 16)) ||
+        (rc = h->fe_slot.ensure(sizeof(int32_t) * rows + 16)) || (rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))))
+        return rc;
+    return MDRP_OK;
+}
+
+// behind a gather into the handle's buffers: the counts (one stream synchronisation), the resident estimator on the gathered buffers with the
+// handle's own inlier mask (by slot), then that mask back onto the match rows
+static int estimate_gathered(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                             const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+    const size_t rows = (size_t)batch * m_max;
+    int rc;
+    if ((rc = fetch_counts(h, batch))) return rc;
+    rc = estimate_device(h, kind, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(), batch, m_max,
+                         batch > 0 ? h->fe_n_host.v : nullptr, cam1, cam2, ropt, bopt, nullptr);
+    if (rc) return rc;
+    if (match_mask_dev && rows > 0) {
+        hipLaunchKernelGGL(k_match_mask, dim3((unsigned)((rows + FE_THREADS - 1) / FE_THREADS)), dim3(FE_THREADS), 0, h->stream, h->fe_slot.as<int32_t>(),
+                           h->mask.as<uint8_t>(), m_max, rows, match_mask_dev);
+        HIPCHK(hipGetLastError());
+    }
+    if (n_used_host && batch > 0) std::memcpy(n_used_host, h->fe_n_host, sizeof(int32_t) * batch);
     return MDRP_OK;
 }
 
@@ -1526,33 +1597,43 @@ int mdrp_gather_matches(mdrp_handle *h, const mdrp_matches *mm, int batch, doubl
 int mdrp_estimate_matches_async(mdrp_handle *h, int kind, const mdrp_matches *mm, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
                                 const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
     if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) {
-        g_err = "mdrp_estimate_matches_async: only the monodepth estimators (kind 0..2) take depth maps";
-        return MDRP_ERR_INVALID;
-    }
+    if (int rc = check_front_end_kind(kind, "mdrp_estimate_matches_async")) return rc;
     if (int rc = check_matches(mm, batch)) return rc;
     MDRP_ENTER(h);
-    const size_t rows = (size_t)batch * mm->m_max;
     int rc;
-    if ((rc = h->fe_x1.ensure(sizeof(double) * 2 * rows + 16)) || (rc = h->fe_x2.ensure(sizeof(double) * 2 * rows + 16)) ||
-        (rc = h->fe_d1.ensure(sizeof(double) * rows + 16)) || (rc = h->fe_d2.ensure(sizeof(double) * rows + 16)) ||
-        (rc = h->fe_slot.ensure(sizeof(int32_t) * rows + 16)) || (rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))))
-        return rc;
+    if ((rc = ensure_gather_buffers(h, batch, mm->m_max))) return rc;
     if ((rc = gather_device(h, mm, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
                             h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>())))
         return rc;
+    return estimate_gathered(h, kind, batch, mm->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
+}
+
+int mdrp_gather_image_pairs(mdrp_handle *h, const mdrp_image_pairs *ip, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
+                            int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_image_pairs(ip, batch)) return rc;
+    if (batch > 0 && (!n_host || (ip->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_image_pairs: NULL output"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1)))) return rc;
+    if ((rc = gather_images_device(h, ip, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>()))) return rc;
     if ((rc = fetch_counts(h, batch))) return rc;
-    // from here on: the resident estimator on the gathered buffers, with the handle's own inlier mask (by slot)
-    rc = estimate_device(h, kind, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(), batch, mm->m_max,
-                         batch > 0 ? h->fe_n_host.v : nullptr, cam1, cam2, ropt, bopt, nullptr);
-    if (rc) return rc;
-    if (match_mask_dev && rows > 0) {
-        hipLaunchKernelGGL(k_match_mask, dim3((unsigned)((rows + FE_THREADS - 1) / FE_THREADS)), dim3(FE_THREADS), 0, h->stream, h->fe_slot.as<int32_t>(),
-                           h->mask.as<uint8_t>(), mm->m_max, rows, match_mask_dev);
-        HIPCHK(hipGetLastError());
-    }
-    if (n_used_host && batch > 0) std::memcpy(n_used_host, h->fe_n_host, sizeof(int32_t) * batch);
+    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
     return MDRP_OK;
+}
+
+int mdrp_estimate_image_pairs_async(mdrp_handle *h, int kind, const mdrp_image_pairs *ip, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                    const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_front_end_kind(kind, "mdrp_estimate_image_pairs_async")) return rc;
+    if (int rc = check_image_pairs(ip, batch)) return rc;
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = ensure_gather_buffers(h, batch, ip->m_max))) return rc;
+    if ((rc = gather_images_device(h, ip, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
+                                   h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>())))
+        return rc;
+    return estimate_gathered(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
 }
 
 } // extern "C"

@@ -14,6 +14,10 @@ For match row m = (i, j), in row order:
    both depths are finite;
 5. kept rows, in match order, give x1 = float64(p1) - center1, x2 = float64(p2) - center2, d1, d2; slot[m] is the position of row m
    among the kept rows, -1 for a dropped row.
+
+`poselib.gather_image_pairs_torch` / `estimate_image_pairs_torch` take the batch as its producer holds it: keypoints and depth maps once per
+image, pairs as image indices (include/mdrp.h mdrp_image_pairs).  `gather_image_pairs_numpy` below states them as a loop over the pairs that
+calls `gather_matches_numpy` on the two images' valid tables: that reduction is the definition.
 """
 import numpy as np
 
@@ -86,3 +90,51 @@ def pad_pairs(gathered, m_max):
         x1[b, :n[b]] = a1; x2[b, :n[b]] = a2; d1[b, :n[b]] = e1; d2[b, :n[b]] = e2
         slot[b, :len(s)] = s
     return x1, x2, d1, d2, n, slot
+
+
+# ---- per-image tables (include/mdrp.h mdrp_image_pairs): keypoints and depth maps exist once per image, a pair is two image indices
+def image_valid(a, n_images):
+    """an image index addresses the set: a in [0, n_images)"""
+    a = np.asarray(a, dtype=np.int64)
+    return (a >= 0) & (a < int(n_images))
+
+
+def clamp_extent(v, maximum):
+    """a per-image extent (a kp_count, the h or w of a size) against the allocated one: clamped to [0, maximum]"""
+    return np.clip(np.asarray(v, dtype=np.int64), 0, int(maximum))
+
+
+def gather_image_pairs_numpy(keypoints, depth_maps, pairs, matches, centers=None, sizes=None, kp_counts=None, filter="both_inf"):
+    """keypoints (I, K, 2) and depth_maps (I, H, W) in float32 / float64, pairs (B, 2) image indices (a, c), matches (B, M, 2) integers.
+    sizes (I, 2) (h, w) and kp_counts (I,): the valid part of each image's map and table, clamped to the allocation, None = all of it;
+    centers (I, 2) or (2,).  Pair b is gather_matches_numpy on image a's and image c's valid tables; a pair with an index outside [0, I) is
+    empty.  Returns pad_pairs of the per-pair results: x1, x2 (B, M, 2), d1, d2 (B, M), n (B,) int32, slot (B, M) int32."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {FILTERS}, not {filter!r}")
+    kp, dm = _table(keypoints, "keypoints"), _table(depth_maps, "depth maps")
+    if kp.ndim != 3 or kp.shape[2] != 2 or dm.ndim != 3 or len(dm) != len(kp):
+        raise ValueError("expected keypoints (I, K, 2) and depth maps (I, H, W)")
+    I, K = kp.shape[:2]
+    H, W = dm.shape[1:]
+    pairs = np.asarray(pairs).astype(np.int32).reshape(-1, 2)
+    matches = np.asarray(matches)
+    if matches.ndim != 3 or len(matches) != len(pairs) or matches.shape[2] != 2:
+        raise ValueError("expected matches (B, M, 2) with the pairs' B")
+    M = matches.shape[1]
+    counts = np.full(I, K, dtype=np.int64) if kp_counts is None else clamp_extent(np.asarray(kp_counts).reshape(I), K)
+    hw = np.tile(np.array([H, W], dtype=np.int64), (I, 1)) if sizes is None else np.asarray(sizes).reshape(I, 2)
+    hs, ws = clamp_extent(hw[:, 0], H), clamp_extent(hw[:, 1], W)
+    cs = None if centers is None else np.asarray(centers, dtype=np.float64)
+    if cs is not None and cs.size == 2:
+        cs = np.tile(cs.reshape(1, 2), (I, 1))
+    if cs is not None and cs.shape != (I, 2):
+        raise ValueError("centers must have shape (I, 2) or (2,)")
+    empty = (np.zeros((0, 2)), np.zeros((0, 2)), np.zeros(0), np.zeros(0), np.full(M, -1, dtype=np.int32))
+    gathered = []
+    for b, (a, c) in enumerate(pairs):
+        if not (image_valid(a, I) and image_valid(c, I)):
+            gathered.append(empty)
+            continue
+        gathered.append(gather_matches_numpy(kp[a][:counts[a]], kp[c][:counts[c]], matches[b], dm[a][:hs[a], :ws[a]], dm[c][:hs[c], :ws[c]],
+                                             None if cs is None else cs[a], None if cs is None else cs[c], filter))
+    return pad_pairs(gathered, M)

@@ -812,6 +812,134 @@ def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, de
     return res, match_mask, n_used
 
 
+# ---- the same for a batch held per IMAGE (include/mdrp.h mdrp_image_pairs): keypoint tables and depth maps exist once per image
+# and the pairs are index pairs into the image set — every frame of a video against one anchor, each image of an SfM set against many
+# others — so nothing is copied once per pair.  mdrp_amd/frontend.py gather_image_pairs_numpy states the semantics.
+def _host_pairs(pairs):
+    """(B, 2) image indices as a contiguous host int32 array, from a sequence, a NumPy array or a tensor on any device"""
+    if hasattr(pairs, "detach"):
+        pairs = pairs.detach().cpu().numpy()
+    pairs = np.asarray(pairs)
+    if pairs.size == 0:
+        return np.zeros((0, 2), dtype=np.int32)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+        raise ValueError("pairs must be (B, 2) integer image indices")
+    return np.ascontiguousarray(np.clip(pairs, -1, 2 ** 31 - 1).astype(np.int32))  # (an index past int32 stays out of range instead of wrapping into it)
+
+
+def _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, sizes, kp_counts, filter, need_host_pairs):
+    """validated mdrp_image_pairs descriptor of torch tensors on one ROCm device -> (descriptor, tensors it points into, host pairs, B, M, I, device);
+    host pairs is None where they were not asked for and pairs already lives on the device (no copy back, no synchronisation)"""
+    import torch
+    if filter not in _capi.FILTERS:
+        raise ValueError(f"filter must be one of {tuple(_capi.FILTERS)}, not {filter!r}")
+    for name, t in {"keypoints": keypoints, "depth_maps": depth_maps, "matches": matches}.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+        if t.device != keypoints.device:
+            raise ValueError("all tensors must live on the same device")
+    dev = keypoints.device
+    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
+    if keypoints.dtype not in ftypes or depth_maps.dtype not in ftypes:
+        raise ValueError("keypoints and depth maps must be float32 or float64")
+    if matches.dtype not in (torch.int32, torch.int64):
+        raise ValueError("matches must be int32 or int64")
+    if keypoints.dim() != 3 or keypoints.shape[2] != 2:
+        raise ValueError("keypoints must have shape (I, K, 2)")
+    I = keypoints.shape[0]
+    if depth_maps.dim() != 3 or depth_maps.shape[0] != I:
+        raise ValueError("depth maps must have shape (I, H, W) with the keypoints' I")
+    on_device = isinstance(pairs, torch.Tensor) and pairs.device == dev
+    if on_device and (pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype.is_floating_point):
+        raise ValueError("pairs must be (B, 2) integer image indices")
+    host_pairs = _host_pairs(pairs) if need_host_pairs or not on_device else None
+    B = pairs.shape[0] if host_pairs is None else len(host_pairs)
+    if matches.dim() != 3 or matches.shape[0] != B or matches.shape[2] != 2:
+        raise ValueError("matches must have shape (B, M, 2) with the pairs' B")
+    mt = matches.to(torch.int32) if matches.dtype == torch.int64 else matches  # narrowed on the device, on the current stream: no synchronisation
+    kp, dm, mt = keypoints.contiguous(), depth_maps.contiguous(), mt.contiguous()
+
+    def per_image(v, dtype, shape, what):
+        """an optional per-image table -> contiguous device tensor of that dtype and shape (uploaded on the current stream when it is on the host)"""
+        if v is None:
+            return None
+        v = (v if isinstance(v, torch.Tensor) else torch.tensor(np.asarray(v))).to(device=dev, dtype=dtype)
+        if what == "centers" and v.numel() == 2:
+            v = v.reshape(1, 2).expand(I, 2)
+        if tuple(v.shape) != shape:
+            raise ValueError(f"{what} must have shape {shape}" + (" or (2,)" if what == "centers" else ""))
+        return v.contiguous()
+
+    cs = per_image(centers, torch.float64, (I, 2), "centers")
+    sz = per_image(sizes, torch.int32, (I, 2), "sizes")
+    kc = per_image(kp_counts, torch.int32, (I,), "kp_counts")
+    pr = pairs.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous() if on_device else torch.from_numpy(host_pairs).to(dev)  # (host_pairs is this call's own copy)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+    ip = _capi.ImagePairs(kp.data_ptr(), ftypes[kp.dtype], kp.shape[1], ptr(kc), dm.data_ptr(), ftypes[dm.dtype], dm.shape[1], dm.shape[2], ptr(sz), ptr(cs), I,
+                          pr.data_ptr(), mt.data_ptr(), mt.shape[1], _capi.FILTERS[filter])
+    return ip, (kp, dm, mt, cs, sz, kc, pr), host_pairs, B, int(mt.shape[1]), I, dev
+
+
+def gather_image_pairs_torch(keypoints, depth_maps, pairs, matches, centers=None, sizes=None, kp_counts=None, filter="both_inf"):
+    """gather_matches_torch for pairs given as image indices.  keypoints (I, K, 2) and depth_maps (I, H, W) float32 | float64, matches (B, M, 2)
+    int32 | int64 with -1 rows as padding, all on one ROCm device; pairs (B, 2) image indices (a, c) as a sequence, NumPy array or tensor on any
+    device (a pair with an index outside [0, I) is empty: n = 0, slots -1, filler).  sizes (I, 2) (h, w) and kp_counts (I,): the valid part of
+    each image's map and table (clamped to H, W and K; None = all); centers (I, 2) or (2,), subtracted in float64.  Returns what
+    gather_matches_torch returns, on the device's current torch stream, behind one stream synchronisation (the counts)."""
+    import torch
+    ip, keep, _, B, M, _, dev = _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, sizes, kp_counts, filter, False)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        x1 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        x2 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        d1 = torch.empty((B, M), dtype=torch.float64, device=dev)
+        d2 = torch.empty((B, M), dtype=torch.float64, device=dev)
+        slot = torch.empty((B, M), dtype=torch.int32, device=dev)
+        n = h.gather_image_pairs(ip, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
+    del keep
+    return x1, x2, d1, d2, n, slot
+
+
+def _pair_cameras(cameras, host_pairs, I):
+    """per-image cameras (one for all | a list of I | a CAMERA_DTYPE array of I) -> two [B] per-pair record arrays.  A pair with an image index
+    outside [0, I) gets record 0 (a zero record when I == 0): it has n = 0, no correspondence is read against its camera."""
+    rec = _camera_records(cameras, I) if I > 0 else np.zeros(1, dtype=_capi.CAMERA_DTYPE)
+    idx = np.where((host_pairs >= 0) & (host_pairs < I), host_pairs, 0)
+    return np.ascontiguousarray(rec[idx[:, 0]]), np.ascontiguousarray(rec[idx[:, 1]])
+
+
+def estimate_image_pairs_torch(kind, keypoints, depth_maps, pairs, matches, cameras=None, ransac_opt=None, bundle_opt=None, centers=None, sizes=None,
+                               kp_counts=None, filter="both_inf"):
+    """estimate_matches_torch for pairs given as image indices (inputs as gather_image_pairs_torch): records identical to gathering with
+    mdrp_amd.frontend.gather_image_pairs_numpy and calling estimate_batch_torch with its n_per_pair and the per-pair cameras.  cameras
+    (calibrated only) are per IMAGE — one Camera | dict for all, a list of I, or a CAMERA_DTYPE array of I records — and expanded to per-pair
+    records by pairs on the host.  kind: "calibrated" | "shared_focal" | "varying_focal" (pass centers for the focal estimators).
+    Returns (records, match_mask: (B, M) uint8 device tensor, n_used: numpy int32), stream behaviour as estimate_matches_torch."""
+    import torch
+    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
+    if isinstance(kind, str) and kind not in kinds:
+        raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
+    k = kinds[kind] if isinstance(kind, str) else int(kind)
+    if k not in kinds.values():
+        raise ValueError("only the monodepth estimators (calibrated, shared_focal, varying_focal) take depth maps")
+    ip, keep, host_pairs, B, M, I, dev = _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, sizes, kp_counts, filter, True)
+    cams1 = cams2 = None
+    if k == _capi.CALIB:
+        cams1, cams2 = _pair_cameras(cameras, host_pairs, I)
+    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
+        n_used = h.estimate_image_pairs_device(k, ip, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        res = h.fetch_results(B)
+    del keep
+    return res, match_mask, n_used
+
+
 # ------------------------------------------------------------------------------------------------ refine / verify caller-supplied models
 # The counterpart of PoseLib's refine_relative_pose for the three monodepth estimators (include/mdrp.h mdrp_refine_batch, DESIGN.md 7b): one model
 # per pair goes in and the estimator's tail runs on it — score, LO, inlier mask, inlier-only refinement — without a single sample.  A pose from the

@@ -13,6 +13,11 @@ Reports the median of the repetitions and their spread, checks that (a) and (b) 
 The front end's own kernel time comes from a separate run under the profiler, folded into the same file afterwards:
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/frontend_bench.py --only b --reps 3 --out /dev/null
     python tools/frontend_bench.py --kernel-stats <dir>/**/*_kernel_stats.csv --out profiles/frontend_bench.json
+
+--image-pairs: the same 1024-pair batch as its producer holds it — 46 images (1035 possible pairs), one keypoint table and one depth map per
+image, the pairs as image indices — through poselib.estimate_image_pairs_torch (route "i"), against the unchanged estimate_matches_torch on the
+per-pair expansion of the same data (route "e": every image's tables copied once per pair it takes part in, built before the clock starts).
+Checks that both return the same records, records the bytes of input each route holds, and writes under the key "image_pairs" of the same file.
 """
 import argparse
 import csv
@@ -107,6 +112,92 @@ def route_b(poselib, t, ro):
     return res, match_mask
 
 
+def make_image_inputs(n_images, batch, rows, dev):
+    """one scene seen by n_images cameras: K world points projected into every image (each image's table in an order of its own), the depth
+    of every visible point painted into that image's one map, and for the first `batch` of the image pairs a match list over `rows` of the
+    points, half of the rows mismatched, with a tail of -1 padding rows.  Returns the device tensors (keypoints (I, K, 2) float32, depth maps
+    (I, H, W) float32, pairs (B, 2) int32 on the host, matches (B, rows, 2) int64)."""
+    import itertools
+    import torch
+    rng = np.random.default_rng(6)
+    f = A * 800.0
+    world = np.stack([rng.uniform(-2.2, 2.2, K), rng.uniform(-1.6, 1.6, K), rng.uniform(3.0, 8.0, K)], 1)
+    kp = np.zeros((n_images, K, 2))
+    order = np.zeros((n_images, K), dtype=np.int64)  # order[i][p]: where point p sits in image i's table
+    g = torch.Generator(device=dev); g.manual_seed(6)
+    dm = torch.rand((n_images, H, W), device=dev, generator=g) * 5 + 1
+    for i in range(n_images):
+        w = rng.normal(0, 0.05, 3)  # a small rotation (Rodrigues) and a small translation per camera
+        th = np.linalg.norm(w)
+        kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / th
+        rot = np.eye(3) + np.sin(th) * kx + (1 - np.cos(th)) * kx @ kx
+        cam = world @ rot.T + rng.normal(0, 0.3, 3)
+        px = f * cam[:, :2] / cam[:, 2:] + np.array(C) + rng.normal(0, 0.5, (K, 2))
+        order[i] = rng.permutation(K)
+        kp[i, order[i]] = px
+        inside = (px[:, 0] > -1) & (px[:, 0] < W) & (px[:, 1] > -1) & (px[:, 1] < H)
+        dm[i, torch.from_numpy(px[inside, 1].astype(np.int64)).to(dev), torch.from_numpy(px[inside, 0].astype(np.int64)).to(dev)] = \
+            torch.from_numpy((cam[inside, 2] * (1 + rng.normal(0, 0.02, int(inside.sum())))).astype(np.float32)).to(dev)
+    dm[:, ::7, ::5] = float("inf")  # a depth network's invalid pixels
+    pairs = np.array(list(itertools.combinations(range(n_images), 2))[:batch], dtype=np.int32)
+    assert len(pairs) == batch, f"{n_images} images give {n_images * (n_images - 1) // 2} pairs, fewer than {batch}"
+    matches = np.full((batch, rows, 2), -1, dtype=np.int64)
+    live = rows - rng.integers(0, rows // 20 + 1, batch)  # up to 5 % padding rows
+    for b, (i, j) in enumerate(pairs):
+        pts = rng.permutation(K)[:rows]
+        other = pts.copy()
+        wrong = rng.random(rows) < 0.5
+        other[wrong] = rng.permutation(pts[wrong])  # outliers: a point matched to another point's keypoint
+        matches[b, :live[b], 0] = order[i][pts[:live[b]]]
+        matches[b, :live[b], 1] = order[j][other[:live[b]]]
+    return torch.from_numpy(kp.astype(np.float32)).to(dev), dm, pairs, torch.from_numpy(matches).to(dev)
+
+
+def tensor_bytes(*tensors):
+    return int(sum(t.numel() * t.element_size() for t in tensors))
+
+
+def run_image_pairs(a):
+    """route "i" (estimate_image_pairs_torch on the per-image tables) against route "e" (estimate_matches_torch on their per-pair expansion)"""
+    import torch
+    import mdrp_amd.poselib as poselib
+    dev = torch.device("cuda", 0)
+    ro = {"max_iterations": a.iters, "min_iterations": a.iters, "max_epipolar_error": 2.0 * A, "max_reproj_error": 16.0 * A}
+    kp, dm, pairs, matches = make_image_inputs(a.images, a.batch, a.rows, dev)
+    pairs_dev = torch.from_numpy(pairs).to(dev)
+    ia, ic = pairs_dev[:, 0].long(), pairs_dev[:, 1].long()
+    expanded = (kp[ia], kp[ic], matches, dm[ia], dm[ic])  # what a caller of estimate_matches_torch has to build and hold
+    routes = {"i": lambda: poselib.estimate_image_pairs_torch("calibrated", kp, dm, pairs, matches, CAM, ro, BO),
+              "e": lambda: poselib.estimate_matches_torch("calibrated", *expanded, CAM, CAM, ro, BO)}
+    times = {k: [] for k in routes}
+    last = {}
+    for rep in range(a.reps + 2):  # two warm-up rounds
+        for k, fn in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[k] = fn()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                times[k].append(time.perf_counter() - t0)
+    assert last["i"][0].tobytes() == last["e"][0].tobytes(), "the routes' records differ"
+    assert torch.equal(last["i"][1], last["e"][1]) and np.array_equal(last["i"][2], last["e"][2])
+    doc = {"shape": {"images": a.images, "batch": a.batch, "match_rows": a.rows, "keypoints": K, "depth_map": [H, W], "iterations": a.iters,
+                     "repetitions": a.reps, "kept_rows_mean": float(last["i"][2].mean()), "inlier_ratio_mean": float(last["i"][0]["inlier_ratio"].mean()),
+                     "estimator": "calibrated"},
+           "routes": {"i": "estimate_image_pairs_torch on per-image tables", "e": "estimate_matches_torch on the per-pair expansion (built beforehand)"},
+           "input_bytes": {"i": tensor_bytes(kp, dm, pairs_dev, matches), "e": tensor_bytes(*expanded)}}
+    for k, v in times.items():
+        v = np.array(v)
+        doc[k] = {"pairs_per_s_median": a.batch / float(np.median(v)), "ms_median": 1e3 * float(np.median(v)), "ms_min": 1e3 * float(v.min()),
+                  "ms_max": 1e3 * float(v.max()), "spread_rel": float((v.max() - v.min()) / np.median(v))}
+    if a.out != "/dev/null":
+        whole = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        whole["image_pairs"] = doc
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(whole, open(a.out, "w"), indent=1)
+    print(json.dumps({"image_pairs": doc}))
+
+
 def fold_kernel_stats(paths, out):
     """average duration of the front end's kernels from rocprofv3's kernel statistics into the result file"""
     rows = {}
@@ -130,11 +221,15 @@ def main():
     ap.add_argument("--iters", type=int, default=10000)
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--only", choices=["a", "b", "c"], default=None, help="run one route alone (profiler runs)")
+    ap.add_argument("--image-pairs", action="store_true", help="the batch as pairs of image indices into --images images (see above)")
+    ap.add_argument("--images", type=int, default=46)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.json"))
     ap.add_argument("--kernel-stats", nargs="+", default=None, help="rocprofv3 *_kernel_stats.csv files (globs allowed) to fold into --out")
     a = ap.parse_args()
     if a.kernel_stats:
         return fold_kernel_stats([p for g in a.kernel_stats for p in glob.glob(g, recursive=True)], a.out)
+    if a.image_pairs:
+        return run_image_pairs(a)
     import torch
     import mdrp_amd.poselib as poselib
     from mdrp_amd import frontend
