@@ -417,6 +417,42 @@ int mdrp_refine_batch_async(mdrp_handle *h, int kind, const double *x1_dev, cons
                             const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const mdrp_model *models_dev, int stages,
                             uint8_t *inlier_mask_dev, double *initial_score_dev, int32_t *initial_inliers_dev);
 
+/* ---- Estimate with a prior (added within ABI 0.6: new symbols only).
+ * mdrp_estimate_batch with one model per pair that the search starts from: the LO-RANSAC run unchanged, with the caller's model scored and
+ * LO-refined first, exactly as ransac<> treats an initial model under score_initial_model — and NOT reset to the identity, as the reference's
+ * wrappers reset it.  A good prior retires garbage hypotheses from the first chunk on and lowers the dynamic iteration bound at once; a bad
+ * prior costs one LM and changes nothing else; a wrong prior cannot give a wrong answer, because everything is still sampled
+ * (mdrp_refine_batch is the call that trusts the model).  For pair b with n = n_per_pair[b] correspondences and prior P (an mdrp_model in the
+ * caller's units, as the estimators return it: focals in pixels for the two focal kinds):
+ *   - n < 3: the estimators' record (identity model, zero stats, model_score = DBL_MAX).  P is not read.
+ *   - P.q[0] is NaN: the pair has no prior and behaves as in mdrp_estimate_batch, ropt->score_initial_model included.
+ *   - otherwise the pair ignores ropt->score_initial_model, and its state before iteration 0 is:
+ *       1. focal kinds: P.f1, P.f2 divided by the pair's normalisation scale.
+ *       2. (S0, C0) = exact MSAC score and inlier count of P at the squared threshold, in record order.
+ *       3. more = C0 > 0, better = S0 < DBL_MAX.  Neither (a NaN score): nothing changes, no LM.  Otherwise the records of the minimal
+ *          models become best_minimal_inlier_count = C0 (if more) and best_minimal_msac_score = S0 (if better), and P is the best model
+ *          with model_score = S0 and num_inliers = C0.
+ *       4. LO: the 25-iteration TRUNCATED LM at the LO's loss scale from P over all records gives M1 with (S1, C1); refinements = 1.  M1 is
+ *          adopted with its score and count iff S1 < model_score.  The LO never touches the records of the minimal models.
+ *       5. inlier_ratio = num_inliers / n, and the dynamic iteration bound follows from it by ransac<>'s rule.
+ *       6. This is not an iteration: iterations stays 0 and no stop test runs.  With max_iterations = 0 the loop ends here, and the closing LO,
+ *          the mask and the inlier-only refinement run on this state.
+ *   - everything behind that — sampling, scoring, LO triggers, stopping, closing LO, get_inliers, inlier-only refinement, focal
+ *     un-normalisation, the record — is mdrp_estimate_batch's, unchanged.  The state a prior leaves does not depend on the batch.
+ * kind: MDRP_CALIB, MDRP_SHARED_FOCAL or MDRP_VARYING_FOCAL.  MDRP_ERR_INVALID, before any device work: any other kind, batch > 0 with a NULL
+ * prior, and everything mdrp_estimate_batch refuses; the option refusals (progressive_sampling: MDRP_ERR_UNSUPPORTED) are the estimator's own.
+ * x1, x2, d1, d2, prior ([B]) and inlier_mask ([B][n_max] bytes or NULL) live in mem_space; n_per_pair, cameras and out ([B]) in HOST memory.
+ * Host buffers are copied in one piece on the handle's stream before the run (no sliced front).  Iteration budgets do not combine with priors. */
+int mdrp_estimate_batch_prior(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
+                              int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                              const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const mdrp_model *prior, mdrp_result *out,
+                              uint8_t *inlier_mask);
+/* Device-resident variant, as mdrp_estimate_batch_async: results through mdrp_fetch_results / mdrp_copy_results_device. */
+int mdrp_estimate_batch_prior_async(mdrp_handle *h, int kind, const double *x1_dev, const double *x2_dev, const double *d1_dev,
+                                    const double *d2_dev, int batch, int n_max, const int32_t *n_per_pair_host, const mdrp_camera *cam1_host,
+                                    const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                    const mdrp_model *prior_dev, uint8_t *inlier_mask_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ EXPORTS = (
     "mdrp_estimate_batch_budgets", "mdrp_estimate_batch_budgets_async", "mdrp_fetch_budget_results", "mdrp_copy_budget_results_device",
     "mdrp_refine_batch", "mdrp_refine_batch_async",
     "mdrp_gather_image_pairs", "mdrp_estimate_image_pairs_async",
+    "mdrp_estimate_batch_prior", "mdrp_estimate_batch_prior_async",
 )
 STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
 MAX_BUDGETS = 16  # include/mdrp.h MDRP_MAX_BUDGETS
@@ -157,6 +158,11 @@ def load_library():
         if hasattr(lib, "mdrp_gather_image_pairs"):  # (an older ABI-0.6 library through MDRP_LIB has no image-pairs entry points: Handle._image_pairs_fn raises)
             lib.mdrp_gather_image_pairs.argtypes = [vp, C.POINTER(ImagePairs), C.c_int, dp, dp, dp, dp, ip, ip]
             lib.mdrp_estimate_image_pairs_async.argtypes = [vp, C.c_int, C.POINTER(ImagePairs), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
+        if hasattr(lib, "mdrp_estimate_batch_prior"):  # (an older ABI-0.6 library through MDRP_LIB has no prior entry points: Handle._prior_fn raises)
+            lib.mdrp_estimate_batch_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                      C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
+            lib.mdrp_estimate_batch_prior_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                            C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
         _lib = lib
         return lib
 
@@ -478,6 +484,48 @@ class Handle:
         _check(self._lib, self._refine_fn("mdrp_refine_batch_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), int(batch), int(n_max),
                                                                      _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(models_ptr), int(stages),
                                                                      vp(mask_ptr), vp(initial_score_ptr), vp(initial_inliers_ptr)))
+
+    # ---- estimate with a prior (include/mdrp.h: mdrp_estimate_batch_prior).  Arguments go to the library as they are: the library checks them.
+    def _prior_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the prior entry points (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    def estimate_batch_prior(self, kind, x1, x2, d1, d2, priors, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
+        """estimate_batch with one prior (MODEL_DTYPE; a NaN q[0]: none) per pair, host (numpy) buffers: (records, masks (B, N) uint8 or None)"""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+            raise ValueError("expected x1,x2 (B,N,2)")
+        d1 = None if d1 is None else np.ascontiguousarray(d1, dtype=np.float64)
+        d2 = None if d2 is None else np.ascontiguousarray(d2, dtype=np.float64)
+        if d1 is not None and d2 is not None and (d1.shape != x1.shape[:2] or d2.shape != d1.shape):
+            raise ValueError("expected d1,d2 (B,N)")
+        B, N = x1.shape[:2]
+        priors = None if priors is None else np.ascontiguousarray(priors, dtype=MODEL_DTYPE).reshape(-1)
+        if priors is not None and len(priors) != B:
+            raise ValueError(f"expected {B} priors, got {len(priors)}")
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        out = np.zeros(B, dtype=RESULT_DTYPE)
+        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        _check(self._lib, self._prior_fn("mdrp_estimate_batch_prior")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N, _ptr(npp),
+                                                                      _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(priors), _ptr(out), _ptr(mask)))
+        return out, mask
+
+    def estimate_batch_prior_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, priors_ptr, ropt, bopt, n_per_pair=None, cam1=None, cam2=None,
+                                    mask_ptr=None):
+        """the same on device pointers (ints), queued on the handle's stream; priors_ptr: batch x 96 bytes.  Records: fetch_results / copy_results_device."""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _check(self._lib, self._prior_fn("mdrp_estimate_batch_prior_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), int(batch), int(n_max),
+                                                                            _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(priors_ptr), vp(mask_ptr)))
 
     # ---- device front end: a Matches descriptor of device pointers
     def gather_matches(self, mm, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):

@@ -7,7 +7,8 @@
 #include "mdrp_frontend.h"
 #include "mdrp_schedule.h"
 #include "mdrp_from_model.h"
-// MDRP_SPLIT_TU (the default build): the k_final family, k_from_model and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
+#include "mdrp_prior.h"
+// MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
 #define MDRP_INST extern
@@ -17,6 +18,7 @@ MDRP_INSTANCES_FINAL_64
 MDRP_INSTANCES_FINAL_256
 MDRP_INSTANCES_CLASSIC
 MDRP_INSTANCES_FROM_MODEL
+MDRP_INSTANCES_PRIOR
 }
 #endif
 
@@ -177,7 +179,7 @@ struct mdrp_handle {
     DevBuf ckpt, ck_list, bresults, bmask;
     int last_budgets = 0;              // budgets of the last call (0: it had none)
     DevBuf in_x1, in_x2, in_d1, in_d2; // staging when the caller passes host memory
-    DevBuf fm_models, fm_init;         // mdrp_refine_batch: the caller's models when they come from host memory | start-model scores [batch] f64, counts [batch] i32
+    DevBuf fm_models, fm_init;         // mdrp_refine_batch (and mdrp_estimate_batch_prior: the priors): the caller's models when they come from host memory | start-model scores [batch] f64, counts [batch] i32
     DevBuf fe_x1, fe_x2, fe_d1, fe_d2, fe_slot, fe_n; // device front end (mdrp_estimate_matches_async): gathered correspondences | slot of every match row | kept rows per pair
     Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
     size_t fe_n_host_cap = 0;
@@ -375,6 +377,7 @@ struct PassIn {
     const HostSrc *host;  // (or null)
     int batch_call;       // pairs of the whole API call
     const BudgetOut *bud; // (or null)
+    const Model *priors;  // device memory, one per pair of the pass, or null (mdrp_estimate_batch_prior; never with `host` or `bud`)
 };
 
 // Chunk c of the super-chunk under way, for the pairs [p0, p0 + pc).  Every kernel of the front indexes its per-pair arrays as base[pair]: a RANGE
@@ -528,6 +531,20 @@ struct Pass : PassIn {
         else
             hipLaunchKernelGGL(k_prep, dim3(pc), dim3(256), 0, st_, rp, x1 + o2, x2 + o2, d1 + o1, d2 + o1, d_nper + p0, d_table_of + p0, d_cams1 + p0, d_cams2 + p0,
                                ro->max_epipolar_error, ro->max_reproj_error, bo->loss_scale, pts_p, h->dep.as<double>() + 2 * o1, h->st.as<PairState>() + p0, rfrag_p);
+    }
+
+    // a call with priors: every pair that has one starts from the state ransac<> is in after scoring and LO-refining it (k_prior, mdrp_prior.h).
+    // On the main stream behind k_prep: every reader of the pair states is ordered behind this stream's first solver launch.
+    void prior() {
+#define MDRP_PRIOR_LAUNCH(K, S)                                                                                                                  \
+    hipLaunchKernelGGL((k_prior<K, S>), dim3(batch), dim3(PRIOR_THREADS), lm_list_bytes(n_max), s, rp, h->st.as<PairState>(),                     \
+                       (const double *)h->pts.as<double>(), (const double *)h->dep.as<double>(), priors, lm_list_stride(n_max),                  \
+                       h->lm_stats.as<unsigned long long>())
+        if (kind == MDRP_CALIB && est_shift) MDRP_PRIOR_LAUNCH(0, true);
+        else if (kind == MDRP_CALIB) MDRP_PRIOR_LAUNCH(0, false);
+        else if (kind == MDRP_SHARED_FOCAL) MDRP_PRIOR_LAUNCH(1, false);
+        else MDRP_PRIOR_LAUNCH(2, false);
+#undef MDRP_PRIOR_LAUNCH
     }
 
     // the chunks of the super-chunk at it0, its cleared counters, and whether it is pipelined over the streams and ends with the fused tail
@@ -920,6 +937,7 @@ int run_pass(mdrp_handle *h, const PassIn &in) {
     HIPCHK(hipEventRecord(h->ev_tables, s)); // sample tables can be drawn from here on
     if (!p.host) { // device-resident inputs: everything is there (host buffers: the copies and k_prep are issued slice by slice by host_front)
         p.prep(0, p.batch, s);
+        if (p.priors) p.prior();
         HIPCHK(hipGetLastError());
     }
     p.rp.inl_stat = p.classic ? nullptr : &p.cnt->progress.wish_sum;
@@ -968,10 +986,9 @@ int run_pass(mdrp_handle *h, const PassIn &in) {
     return p.final_done ? MDRP_OK : p.final_refinements(); // (fused tail: the final refinements ran beside the last LO launch)
 }
 
-int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
-                    int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                    const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr,
-                    const uint64_t *budgets = nullptr, int n_budgets = 0) {
+// what every estimator call refuses before any device work
+int estimate_refusals(mdrp_handle *h, int kind, const double *d1, const double *d2, int batch, int n_max, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                      const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo) {
     const bool known_kind = kind >= 0 && kind <= 5;
     if (!h || batch < 0 || n_max < 0 || !known_kind || !ro || !bo) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (kind == MDRP_SHARED_6PT && batch > 0 && !cam1) { g_err = "the 6-point estimator needs the principal point in cam1"; return MDRP_ERR_INVALID; }
@@ -980,6 +997,15 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
     // RansacOptions switches of the reference that are not built are refused, never ignored (the reference would return different results)
     if (ro->progressive_sampling) { g_err = "progressive_sampling (PROSAC, RandomSampler::initialize_prosac) is not built"; return MDRP_ERR_UNSUPPORTED; }
     if (ro->real_focal_check && (kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT)) { g_err = "real_focal_check is not built"; return MDRP_ERR_UNSUPPORTED; }
+    return MDRP_OK;
+}
+
+int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
+                    int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                    const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr,
+                    const uint64_t *budgets = nullptr, int n_budgets = 0, const Model *priors = nullptr /*[batch] in device memory*/) {
+    if (int rc = estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, ro, bo)) return rc;
+    if (priors && (host || budgets || kind > MDRP_VARYING_FOCAL)) { g_err = "priors: device-resident monodepth calls without budgets only"; return MDRP_ERR_INVALID; }
     h->last_budgets = n_budgets;
     if (h->fuse_disabled && --h->fuse_retry_in <= 0) h->fuse_disabled = false; // once per API call (not per pass): the handle tries the fused tail again
     h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
@@ -1020,7 +1046,7 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
         const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + o1, batch};
         const PassIn in{kind, x1 + o2, x2 + o2, d1 ? d1 + o1 : nullptr, d2 ? d2 + o1 : nullptr, nb, n_max, n_host.data() + p0, cam1 ? cam1 + p0 : nullptr,
                         cam2 ? cam2 + p0 : nullptr, ro, bo, chunk_cap, mask + o1, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch,
-                        budgets ? &bud : nullptr};
+                        budgets ? &bud : nullptr, priors ? priors + p0 : nullptr};
         if ((rc = run_pass(h, in))) return rc;
     }
     if (budgets) {
@@ -1318,6 +1344,73 @@ int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const d
     if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
     MDRP_ENTER(h);
     return estimate_batch_locked(h, kind, mem_space, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, budgets, n_budgets, out, inlier_mask);
+}
+
+} // extern "C"
+
+// ---- estimate with a prior (include/mdrp.h; mdrp_prior.h)
+// what both entry points refuse before any device work, beyond what estimate_device refuses for every estimator call
+static int check_prior_args(mdrp_handle *h, int kind, const double *d1, const double *d2, int batch, int n_max, const int32_t *n_per_pair,
+                            const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, const mdrp_model *prior) {
+    const char *why = nullptr;
+    if (!h) why = "invalid argument";
+    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "prior: only the monodepth estimators (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL)";
+    else if (batch < 0 || n_max < 0) why = "prior: a negative size";
+    else if (batch > 0 && !prior) why = "prior: prior is NULL";
+    for (int i = 0; !why && n_per_pair && i < batch; ++i)
+        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    return estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, ro, bo); // (the option refusals are the estimator's own)
+}
+
+extern "C" {
+
+int mdrp_estimate_batch_prior_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
+                                    const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                    const mdrp_bundle_opt *bopt, const mdrp_model *prior_dev, uint8_t *inlier_mask_dev) {
+    if (int rc = check_prior_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior_dev)) return rc;
+    MDRP_ENTER(h);
+    const int rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, nullptr, 0,
+                                   reinterpret_cast<const Model *>(prior_dev));
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+// The blocking form.  Host buffers are copied in plainly on the handle's stream and the call then runs the device-resident path (mdrp_refine_batch does
+// the same): the sliced host front prepares and solves slices on other streams, which a kernel between k_prep and the first solver cannot follow.
+int mdrp_estimate_batch_prior(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
+                              int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                              const mdrp_bundle_opt *bopt, const mdrp_model *prior, mdrp_result *out, uint8_t *inlier_mask) {
+    if (int rc = check_prior_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior)) return rc;
+    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) { g_err = "monodepth estimator needs correspondences and depths"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
+    hipStream_t s = h->stream;
+    int rc;
+    const Model *prior_dev = reinterpret_cast<const Model *>(prior);
+    if (use_host && batch > 0) {
+        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
+            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)) || (rc = h->fm_models.ensure(sizeof(Model) * b)))
+            return rc;
+        if (np > 0) {
+            HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
+        }
+        HIPCHK(hipMemcpyAsync(h->fm_models.p, prior, sizeof(Model) * b, hipMemcpyHostToDevice, s));
+        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>(); d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
+        prior_dev = h->fm_models.as<Model>();
+    }
+    rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask, nullptr, nullptr, 0, prior_dev);
+    if (rc) return drain_and_return(h, rc);
+    if (use_host && inlier_mask && np > 0 && hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s) != hipSuccess) {
+        g_err = "copy of the inlier masks failed";
+        return drain_and_return(h, MDRP_ERR_HIP);
+    }
+    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
+    return rc ? drain_and_return(h, rc) : rc;
 }
 
 } // extern "C"

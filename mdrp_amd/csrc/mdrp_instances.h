@@ -3,6 +3,7 @@
 //   group 1 / 2: k_final<KIND, SHIFT, T = 64 / 256, FLOSS> for the four LM estimators x the six loss types of BundleOptions
 //   group 3:     the kernels of the 5- / 6- / 7-point baselines (mdrp_classic.h)
 //   group 4:     k_from_model<KIND, SHIFT> for the four LM estimators (mdrp_from_model.h)
+//   group 5:     k_prior<KIND, SHIFT> for the four LM estimators (mdrp_prior.h)
 #pragma once
 namespace mdrp {
 #define MDRP_FINAL_PARAMS RunParams, PairState *, const double *, const double *, uint8_t *, ResultDev *, int, int, unsigned long long *, const int32_t *, int32_t *, \
@@ -24,6 +25,9 @@ namespace mdrp {
 #define MDRP_FROM_MODEL_ONE(K, S) MDRP_INST template __global__ void k_from_model<K, S>(RunParams, const PairState *, const double *, const double *, const Model *, int, \
                                                                                       uint8_t *, ResultDev *, double *, int32_t *, int, int, unsigned long long *);
 #define MDRP_INSTANCES_FROM_MODEL MDRP_FROM_MODEL_ONE(0, false) MDRP_FROM_MODEL_ONE(0, true) MDRP_FROM_MODEL_ONE(1, false) MDRP_FROM_MODEL_ONE(2, false)
+
+#define MDRP_PRIOR_ONE(K, S) MDRP_INST template __global__ void k_prior<K, S>(RunParams, PairState *, const double *, const double *, const Model *, int, unsigned long long *);
+#define MDRP_INSTANCES_PRIOR MDRP_PRIOR_ONE(0, false) MDRP_PRIOR_ONE(0, true) MDRP_PRIOR_ONE(1, false) MDRP_PRIOR_ONE(2, false)
 
 #define MDRP_INSTANCES_FINAL_64 MDRP_FINAL_KINDS(MDRP_FINAL_ONE, 64)
 #define MDRP_INSTANCES_FINAL_256 MDRP_FINAL_KINDS(MDRP_FINAL_ONE, 256)

@@ -2306,6 +2306,14 @@ __device__ __forceinline__ uint64_t f64_to_u64_x86(double d) {
     }
     return d >= -t63 ? (uint64_t)(int64_t)d : 0x8000000000000000ull; // (NaN fails both comparisons: cvttsd2si's "integer indefinite")
 }
+// ransac<>'s dynamic iteration bound behind a refinement, from the inlier ratio of the best model so far (walk_pair; k_prior, mdrp_prior.h)
+__device__ __forceinline__ uint64_t dyn_max_iter_of(const RunParams &rp, double inlier_ratio) {
+    if (inlier_ratio >= 0.9999) return rp.min_iterations;
+    if (inlier_ratio <= 0.0001) return rp.max_iterations;
+    // pow(ratio, sample size) of the reference: x * x * x for 3 (pinned against the binary), libm pow otherwise
+    const double prob_outlier = 1.0 - (rp.sample_sz == 3 ? inlier_ratio * inlier_ratio * inlier_ratio : pow(inlier_ratio, (double)rp.sample_sz));
+    return f64_to_u64_x86(ceil(rp.log_prob_missing / log(prob_outlier) * rp.dyn_mult));
+}
 // SNAP (a budgets call's k_walk_ckpt only): the pair's state as it is when `iterations` reaches budget K_c — or the pair stops, if that
 // comes first — is copied into ck[c * ck_plane], with iterations = min(K_c, stop) and active = 0: what a run with max_iterations = K_c leaves behind,
 // since nothing but `it` changes between two triggers and the stop test cannot fire differently before K_c.  The copy is taken BEFORE a trigger at an
@@ -2375,13 +2383,7 @@ __device__ bool walk_pair(const RunParams &rp, PairState &ps, const Model *__res
             }
         }
         ps.inlier_ratio = (double)ps.num_inliers / (double)ps.n;
-        if (ps.inlier_ratio >= 0.9999) ps.dyn_max_iter = rp.min_iterations;
-        else if (ps.inlier_ratio <= 0.0001) ps.dyn_max_iter = rp.max_iterations;
-        else {
-            // pow(ratio, sample size) of the reference: x * x * x for 3 (pinned against the binary), libm pow otherwise
-            const double prob_outlier = 1.0 - (rp.sample_sz == 3 ? ps.inlier_ratio * ps.inlier_ratio * ps.inlier_ratio : pow(ps.inlier_ratio, (double)rp.sample_sz));
-            ps.dyn_max_iter = f64_to_u64_x86(ceil(rp.log_prob_missing / log(prob_outlier) * rp.dyn_mult));
-        }
+        ps.dyn_max_iter = dyn_max_iter_of(rp, ps.inlier_ratio);
         it = ti + 1;
         if (it >= rp.max_iterations || (it > rp.min_iterations && it > ps.dyn_max_iter)) { stopped = true; break; }
     }

@@ -4,6 +4,7 @@
 #include "mdrp_kernels.h"
 #include "mdrp_classic.h"
 #include "mdrp_from_model.h"
+#include "mdrp_prior.h"
 #define MDRP_INST
 #include "mdrp_instances.h"
 namespace mdrp {
@@ -15,7 +16,9 @@ MDRP_INSTANCES_FINAL_256
 MDRP_INSTANCES_CLASSIC
 #elif MDRP_TU == 4
 MDRP_INSTANCES_FROM_MODEL
+#elif MDRP_TU == 5
+MDRP_INSTANCES_PRIOR
 #else
-#error "MDRP_TU must be 1 (k_final, 64 lanes), 2 (k_final, 256 lanes), 3 (5- / 6- / 7-point baselines) or 4 (k_from_model)"
+#error "MDRP_TU must be 1 (k_final, 64 lanes), 2 (k_final, 256 lanes), 3 (5- / 6- / 7-point baselines), 4 (k_from_model) or 5 (k_prior)"
 #endif
 } // namespace mdrp

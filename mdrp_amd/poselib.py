@@ -212,6 +212,42 @@ def _per_budget(budgets, res, mask, build):
     return [p[0] for p in parts], [p[1] for p in parts]
 
 
+# priors=[...] on a monodepth *_batch entry point (prior= on the single-pair forms): the search of each pair STARTS from the caller's model — scored
+# and LO-refined first, as ransac<> treats an initial model under score_initial_model, and not reset to the identity (include/mdrp.h:
+# mdrp_estimate_batch_prior).  Everything is still sampled, so a wrong prior costs one LM and cannot give a wrong answer.  An entry that
+# is None (a NaN quaternion in a record array) is a pair without a prior.  Not with budgets.  initial_pose / initial_image_pair keep the
+# reference's semantics (_with_initial): that model is reset, never read.
+def _prior_records(priors, kind, B):
+    """list of MonoDepthTwoViewGeometry / MonoDepthImagePair / None, or a MODEL_DTYPE array -> [B] MODEL_DTYPE records (None: a NaN record)"""
+    if isinstance(priors, np.ndarray):
+        if priors.dtype != _capi.MODEL_DTYPE:
+            raise ValueError("priors: a numpy array must have dtype _capi.MODEL_DTYPE")
+        rec = np.ascontiguousarray(priors).reshape(-1)
+    else:
+        priors = list(priors)
+        rec = np.zeros(len(priors), dtype=_capi.MODEL_DTYPE)
+        have = [i for i, p in enumerate(priors) if p is not None]
+        rec["q"] = np.nan
+        rec["scale"] = rec["f1"] = rec["f2"] = 1.0
+        if have:
+            rec[have] = _model_records([priors[i] for i in have], kind)
+    if len(rec) != B:
+        raise ValueError(f"priors: expected {B} models, got {len(rec)}")
+    return rec
+
+
+def _no_budgets_with_priors(priors, budgets):
+    if priors is not None and budgets is not None:
+        raise ValueError("priors and budgets do not combine: run the budgets without priors, or one call per budget")
+
+
+def _prior_host(kind, x1, x2, d1, d2, ns, priors, cams1, cams2, ransac_opt, bundle_opt, device):
+    """(records, masks) of a host batch with priors: one blocking call on the device's default handle"""
+    rec = _prior_records(priors, kind, len(ns))  # (checked before anything touches the device)
+    return _capi.default_handle(device).estimate_batch_prior(kind, x1, x2, d1, d2, rec, _capi.ransac_opt_from_dict(ransac_opt),
+                                                             _capi.bundle_opt_from_dict(bundle_opt), ns, cams1, cams2)
+
+
 def _stack(points1, points2, depth1, depth2):
     """list of ragged pairs or already-stacked arrays -> padded (B,N,2),(B,N,2),(B,N),(B,N), n_per_pair"""
     if isinstance(points1, np.ndarray) and points1.ndim == 3:
@@ -230,13 +266,15 @@ def _stack(points1, points2, depth1, depth2):
 
 
 def estimate_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, cameras1, cameras2, ransac_opt=None,
-                                           bundle_opt=None, device=0, as_arrays=False, budgets=None):
+                                           bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None):
     """B calibrated pairs at once.  cameras1/2: one Camera|dict for all pairs, or a list of B.  Returns
     (list[MonoDepthTwoViewGeometry], list[info dict]) — or, with as_arrays=True, (records, inlier masks, n_per_pair) as numpy arrays
     (_capi.RESULT_DTYPE; (B, N) uint8): building B Python objects and B lists of N bools costs more than the estimate itself beyond
     a few thousand pairs.  A host batch is ONE call whatever its size: the C side copies the correspondences in 256-pair slices on a copy stream
     beside the first kernels of the slices before them (MDRP_PIPELINE_MIN=<pairs> brings back the chunked two-in-flight path of rounds 4-5,
-    mdrp_amd.pipeline; results identical to sequential chunk calls).  budgets: see _budget_args above."""
+    mdrp_amd.pipeline; results identical to sequential chunk calls).  budgets: see _budget_args above.  priors: a list of B
+    MonoDepthTwoViewGeometry | None (or a MODEL_DTYPE array) each pair's search starts from, see _prior_records above."""
+    _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     x1, x2, d1, d2, ns = _stack(points2D_1, points2D_2, depth_1, depth_2)
     B = len(ns)
@@ -244,57 +282,70 @@ def estimate_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, dept
     def cams(c):
         return _camera_records(c, B)
 
-    res, mask = pipeline.estimate_host(_capi.CALIB, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, cams(cameras1), cams(cameras2), device, budgets=budgets)
+    if priors is not None:
+        res, mask = _prior_host(_capi.CALIB, x1, x2, d1, d2, ns, priors, cams(cameras1), cams(cameras2), ransac_opt, bundle_opt, device)
+    else:
+        res, mask = pipeline.estimate_host(_capi.CALIB, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt),
+                                           _capi.bundle_opt_from_dict(bundle_opt), ns, cams(cameras1), cams(cameras2), device, budgets=budgets)
     if as_arrays:
         return res, mask, ns
     return _per_budget(budgets, res, mask, lambda r, m: ([_geometry_from_model(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(B)]))
 
 
-def _focal_batch(kind, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays=False, budgets=None):
+def _focal_batch(kind, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays=False, budgets=None, priors=None):
+    _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     x1, x2, d1, d2, ns = _stack(points2D_1, points2D_2, depth_1, depth_2)
-    res, mask = pipeline.estimate_host(kind, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), ns, None, None, device,
-                                       budgets=budgets)
+    if priors is not None:
+        res, mask = _prior_host(kind, x1, x2, d1, d2, ns, priors, None, None, ransac_opt, bundle_opt, device)
+    else:
+        res, mask = pipeline.estimate_host(kind, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), ns, None, None,
+                                           device, budgets=budgets)
     if as_arrays:
         return res, mask, ns
     return _per_budget(budgets, res, mask, lambda r, m: ([_pair_from_model(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(len(ns))]))
 
 
 def estimate_monodepth_shared_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, ransac_opt=None,
-                                                        bundle_opt=None, device=0, as_arrays=False, budgets=None):
-    return _focal_batch(_capi.SHARED_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets)
+                                                        bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None):
+    """priors: a list of B MonoDepthImagePair | None (focals: camera1 / camera2 .focal(), in pixels), see _prior_records"""
+    return _focal_batch(_capi.SHARED_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets, priors)
 
 
 def estimate_monodepth_varying_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, ransac_opt=None,
-                                                         bundle_opt=None, device=0, as_arrays=False, budgets=None):
-    return _focal_batch(_capi.VARYING_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets)
+                                                         bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None):
+    return _focal_batch(_capi.VARYING_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets, priors)
 
 
 # ------------------------------------------------------------------------------------------------ reference signatures
 def estimate_monodepth_relative_pose(points2D_1, points2D_2, depth_1, depth_2, camera1, camera2, ransac_opt={},
-                                     bundle_opt={}, initial_pose=None):
-    """Pose estimation using depth estimates with non-linear refinement (_core.pyi:446-475)."""
+                                     bundle_opt={}, initial_pose=None, prior=None):
+    """Pose estimation using depth estimates with non-linear refinement (_core.pyi:446-475).  prior (not in the reference): a
+    MonoDepthTwoViewGeometry the search starts from (_prior_records); initial_pose keeps the reference's reset semantics."""
     g, i = estimate_monodepth_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1], [depth_2],
-                                                  camera1, camera2, _with_initial(initial_pose, ransac_opt), bundle_opt)
+                                                  camera1, camera2, _with_initial(initial_pose, ransac_opt), bundle_opt,
+                                                  priors=None if prior is None else [prior])
     return _initial_fallback(initial_pose, g[0]), i[0]
 
 
 def estimate_monodepth_shared_focal_relative_pose(points2D_1, points2D_2, depth_1, depth_2, ransac_opt={}, bundle_opt={},
-                                                  initial_image_pair=None):
-    """Unknown equal focal lengths; points principal-point-centred (_core.pyi:477-488, README.md:88-90)."""
+                                                  initial_image_pair=None, prior=None):
+    """Unknown equal focal lengths; points principal-point-centred (_core.pyi:477-488, README.md:88-90).  prior: a MonoDepthImagePair the
+    search starts from (_prior_records)."""
     p, i = estimate_monodepth_shared_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1],
-                                                               [depth_2], _with_initial(initial_image_pair, ransac_opt), bundle_opt)
+                                                               [depth_2], _with_initial(initial_image_pair, ransac_opt), bundle_opt,
+                                                               priors=None if prior is None else [prior])
     _initial_fallback(initial_image_pair, p[0].geometry)
     return p[0], i[0]
 
 
 def estimate_monodepth_varying_focal_relative_pose(points2D_1, points2D_2, depth_1, depth_2, ransac_opt={}, bundle_opt={},
-                                                   initial_image_pair=None):
+                                                   initial_image_pair=None, prior=None):
     """Two unknown focal lengths (_core.pyi:490-501, README.md:94-96).  `monodepth_estimate_shift` is ignored here
-    exactly like in the reference."""
+    exactly like in the reference.  prior: a MonoDepthImagePair the search starts from (_prior_records)."""
     p, i = estimate_monodepth_varying_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1],
-                                                                [depth_2], _with_initial(initial_image_pair, ransac_opt), bundle_opt)
+                                                                [depth_2], _with_initial(initial_image_pair, ransac_opt), bundle_opt,
+                                                                priors=None if prior is None else [prior])
     _initial_fallback(initial_image_pair, p[0].geometry)
     return p[0], i[0]
 
@@ -662,16 +713,27 @@ def _torch_handle(dev, stream_ptr):
 
 
 def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras1=None, cameras2=None, ransac_opt=None,
-                         bundle_opt=None, n_per_pair=None, budgets=None):
+                         bundle_opt=None, n_per_pair=None, budgets=None, priors=None):
     """Batch that already lives on the GPU (e.g. matcher output): `points2D_*` (B, N, 2) and `depth_*` (B, N) float64 torch
     tensors on a ROCm device; the work is queued on that device's CURRENT torch stream — including torch's default
     (null) stream — so it is ordered after whatever produced the inputs there and before later consumers of the mask;
     nothing crosses PCIe except the 136-byte result records.  kind: "calibrated" | "shared_focal" | "varying_focal".
     Returns (records: numpy structured array with `model`, `refinements`, `iterations`, `num_inliers`, `inlier_ratio`,
     `model_score`; inlier mask: (B, N) uint8 tensor on the device).  Ragged batches: pad and pass `n_per_pair`
-    (sequence, numpy array or tensor on any device).  budgets (see _budget_args): records (C, B) and a (C, B, N) mask tensor."""
+    (sequence, numpy array or tensor on any device).  budgets (see _budget_args): records (C, B) and a (C, B, N) mask tensor.
+    priors (see _prior_records; not with budgets): one model per pair the search starts from — a device tensor holding B records of 96 bytes
+    (uint8 (B, 96), or float64 (B, 12): q t scale shift1 shift2 f1 f2, a NaN q[0] for a pair without one), or a numpy array of _capi.MODEL_DTYPE,
+    which is uploaded on the stream."""
+    _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     import torch
+    if priors is not None:  # (checked before anything touches the device)
+        if isinstance(priors, np.ndarray):
+            priors = _prior_records(priors, None, int(depth_1.shape[0]))
+        elif not (isinstance(priors, torch.Tensor) and priors.dtype in (torch.uint8, torch.float64)):
+            raise ValueError("priors must be a uint8 / float64 tensor on the inputs' device or a numpy array of _capi.MODEL_DTYPE")
+        elif priors.numel() * priors.element_size() != int(depth_1.shape[0]) * _capi.MODEL_DTYPE.itemsize:
+            raise ValueError(f"priors must hold {int(depth_1.shape[0])} records of {_capi.MODEL_DTYPE.itemsize} bytes")
     kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
     k = kinds[kind] if isinstance(kind, str) else int(kind)
     x1, x2, d1, d2 = (t.contiguous() for t in (points2D_1, points2D_2, depth_1, depth_2))
@@ -699,9 +761,19 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
                                             mask.data_ptr())
             return h.fetch_budget_results(len(budgets), B), mask
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
-        h.estimate_batch_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), B, N,
-                                _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), n_per_pair, cams1, cams2,
-                                mask.data_ptr())
+        if priors is not None:
+            if isinstance(priors, np.ndarray):
+                priors = torch.from_numpy(priors.view(np.uint8).copy()).to(x1.device)
+            if not (priors.is_cuda and priors.device == x1.device):
+                raise ValueError("priors must live on the inputs' device")
+            priors = priors.contiguous()
+            h.estimate_batch_prior_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), B, N, priors.data_ptr(),
+                                          _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), n_per_pair, cams1, cams2,
+                                          mask.data_ptr())
+        else:
+            h.estimate_batch_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), B, N,
+                                    _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), n_per_pair, cams1, cams2,
+                                    mask.data_ptr())
         res = h.fetch_results(B)
     return res, mask
 
