@@ -213,6 +213,25 @@ int mdrp_count_candidates(mdrp_handle *h, int kind, const mdrp_model *models, in
 int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
                       int n, double sq_threshold, double *score_lb, int32_t *count_ub);
 
+/* The three retirement stages ARMED, as the scheduler strings them together for a chunk behind the run's first, on ONE pair (within ABI
+ * 0.6): k_count (one launch, or phase A + phase B) -> k_bound (optional) -> sort -> plan -> one of the three exact sweeps, against the
+ * records (rec_cnt, rec_score) written into the pair's state as best_min_cnt / best_min_score.  rec_score >= DBL_MAX: no record (nothing may
+ * be retired).  cand_stat_in[2]: the pair's candidate statistics (candidates, evaluations) from which a two-phase count takes its split
+ * point; {0, 0}: the pair is never split.  Host memory.
+ *   scores, counts [num_models]  the slots: a model the stages retired keeps count -2 (and score DBL_MAX)
+ *   left_at [num_models]         1 retired by k_count, 2 retired by k_bound, 3 reached the exact sweep (which may still bail out: count -2)
+ *   info [3]                     hypotheses phase A left undecided | survivors of the count | survivors of the bound (= of the count without it)
+ *   cand_stat_out [2]            the statistics after the run (a count without records adds its candidates and evaluations to them)
+ * tests/test_gpu_retirement.py pins every decision to the record test on the unarmed stages' own numbers. */
+#define MDRP_RETIRE_TWO_PHASE 1   /* count: phase A over the leading tiles + phase B over the undecided (else one armed launch that sweeps every tile) */
+#define MDRP_RETIRE_BOUND 2       /* run k_bound between the count and the exact sweep */
+#define MDRP_RETIRE_SWEEP_SCORE 0 /* exact sweep: k_score (a lane per hypothesis) */
+#define MDRP_RETIRE_SWEEP_SPLIT 4 /*   k_score_split (records split over the workgroup) */
+#define MDRP_RETIRE_SWEEP_WAVE 8  /*   k_score_w (a wavefront per hypothesis) */
+int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
+                       int n, double sq_threshold, uint64_t rec_cnt, double rec_score, const uint64_t *cand_stat_in, int flags,
+                       double *scores, int32_t *counts, int32_t *left_at, int32_t *info, uint64_t *cand_stat_out);
+
 /* Hybrid LM refinement of `count` models, each over the correspondences of ONE pair (refine_monodepth_*relpose
  * @0x261030/@0x2592e0/@0x260fa0).  Host memory.  models in/out.  For MDRP_RELPOSE_5PT / MDRP_FUNDAMENTAL_7PT: the Sampson-only
  * refine_relpose @0x258f50 / refine_fundamental @0x2590d0 (d1, d2, scale_reproj, weight_sampson, estimate_shift ignored). */

@@ -26,7 +26,10 @@ EXPORTS = (
     "mdrp_refine_batch", "mdrp_refine_batch_async",
     "mdrp_gather_image_pairs", "mdrp_estimate_image_pairs_async",
     "mdrp_estimate_batch_prior", "mdrp_estimate_batch_prior_async",
+    "mdrp_retire_models",
 )
+# include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
+RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
 STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
 MAX_BUDGETS = 16  # include/mdrp.h MDRP_MAX_BUDGETS
 F32, F64 = 0, 1  # mdrp_matches.kp_type / depth_type
@@ -163,6 +166,9 @@ def load_library():
                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
             lib.mdrp_estimate_batch_prior_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                             C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
+        if hasattr(lib, "mdrp_retire_models"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.retire_models raises)
+            lib.mdrp_retire_models.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_uint64, C.c_double, vp, C.c_int,
+                                               vp, vp, vp, vp, vp]
         _lib = lib
         return lib
 
@@ -647,6 +653,28 @@ class Handle:
         _check(self._lib, self._lib.mdrp_bound_models(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1),
                                                       float(sq_threshold), _ptr(lb), _ptr(ub)))
         return lb, ub
+
+    def retire_models(self, kind, models, x1, x2, sq_threshold, rec_cnt, rec_score, cand_stat=(0, 0), flags=0):
+        """the armed retirement stages on one pair (mdrp_retire_models): k_count (RETIRE_TWO_PHASE: phase A + B) -> k_bound (RETIRE_BOUND) -> the
+        exact sweep RETIRE_SWEEP_*, against the records (rec_cnt, rec_score); rec_score None or inf: no record.  Returns (scores, counts, left_at,
+        info, cand_stat): the slots (count -2: retired), 1 / 2 / 3 = left at k_count / at k_bound / reached the sweep, info = (undecided after
+        phase A, survivors of the count, survivors of the bound), and the pair's candidate statistics after the run"""
+        if not hasattr(self._lib, "mdrp_retire_models"):
+            raise MdrpError(f"{LIB_PATH} has no mdrp_retire_models: rebuild (mdrp_amd/build.py)")
+        models = np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        scores = np.zeros(len(models))
+        counts = np.zeros(len(models), dtype=np.int32)
+        left_at = np.zeros(len(models), dtype=np.int32)
+        info = np.zeros(3, dtype=np.int32)
+        cs_in = np.array([int(cand_stat[0]), int(cand_stat[1])], dtype=np.uint64)
+        cs_out = np.zeros(2, dtype=np.uint64)
+        score = np.finfo(np.float64).max if rec_score is None or not rec_score < np.finfo(np.float64).max else float(rec_score)
+        _check(self._lib, self._lib.mdrp_retire_models(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1), float(sq_threshold),
+                                                       int(rec_cnt), score, _ptr(cs_in), int(flags), _ptr(scores), _ptr(counts), _ptr(left_at),
+                                                       _ptr(info), _ptr(cs_out)))
+        return scores, counts, left_at, info, cs_out
 
     def score_models_device(self, kind, models_ptr, num_models, x1_ptr, x2_ptr, n, sq_threshold, scores_ptr, counts_ptr):
         _check(self._lib, self._lib.mdrp_score_models(self._h, int(kind), MEM_DEVICE, C.c_void_p(models_ptr), int(num_models),

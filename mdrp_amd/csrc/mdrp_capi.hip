@@ -1182,13 +1182,14 @@ static int upload_iota(hipStream_t s, void *tags, int count) {
     return MDRP_OK;
 }
 // ... and one pair without records (nothing is pruned or retired: every model sees every correspondence): its state, its correspondences packed
-// into h->pts from the device copies x1, x2, and their box
-static int stage_unit_pair(mdrp_handle *h, const double *x1, const double *x2, int n, double sq_threshold) {
+// into h->pts from the device copies x1, x2, and their box.  mdrp_retire_models alone stages records (rec_cnt, rec_score < DBL_MAX).
+static int stage_unit_pair(mdrp_handle *h, const double *x1, const double *x2, int n, double sq_threshold, uint64_t rec_cnt = 0,
+                           double rec_score = DBL_MAX) {
     hipStream_t s = h->stream;
     PairState ps;
     std::memset(&ps, 0, sizeof ps);
     ps.n = n; ps.active = 1; ps.sq_thr = sq_threshold; ps.eps = std::sqrt(sq_threshold);
-    ps.best_min_score = DBL_MAX;
+    ps.best_min_cnt = rec_cnt; ps.best_min_score = rec_score < DBL_MAX ? rec_score : DBL_MAX; // (a NaN score is no record either)
     HIPCHK(hipMemcpyAsync(h->st.p, &ps, sizeof ps, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, x1, x2, (const double *)nullptr,
                        (const double *)nullptr, h->pts.as<double>(), (double *)nullptr);
@@ -1950,6 +1951,137 @@ int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
     HIPCHK(hipMemcpyAsync(score_lb, h->unit_a.p, sizeof(double) * num_models, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(count_ub, h->unit_f.p, sizeof(int32_t) * num_models, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return MDRP_OK;
+}
+
+// The armed stage train of one chunk on one pair: Pass::count, Pass::bound and Pass::score launch for launch, with the scheduler's buffer roles
+// (undecided list in the chunk's sorted list, partial counts in the other parity's, k_count's survivors in tags_v, k_bound's back in tags).
+int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
+                       int n, double sq_threshold, uint64_t rec_cnt, double rec_score, const uint64_t *cand_stat_in, int flags,
+                       double *scores, int32_t *counts, int32_t *left_at, int32_t *info, uint64_t *cand_stat_out) {
+    const int sweep = flags & (MDRP_RETIRE_SWEEP_SPLIT | MDRP_RETIRE_SWEEP_WAVE);
+    if (!h || num_models < 0 || num_models > 0xFFFFFF || n < 0 || kind < 0 || kind > 5 || !models || !cand_stat_in || !scores || !counts || !left_at ||
+        !info || !cand_stat_out || (flags & ~15) || sweep == (MDRP_RETIRE_SWEEP_SPLIT | MDRP_RETIRE_SWEEP_WAVE)) {
+        g_err = "invalid argument"; return MDRP_ERR_INVALID;
+    }
+    if (num_models == 0) return MDRP_OK;
+    MDRP_ENTER(h);
+    hipStream_t s = h->stream;
+    const int nn = std::max(n, 1);
+    const size_t slots = (size_t)num_models, tag_bytes = sizeof(uint32_t) * slots; // slot_stride = num_models: k_sort_tags writes the dense class from the back
+    const bool armed = rec_score < DBL_MAX, two_phase = (flags & MDRP_RETIRE_TWO_PHASE) && armed; // (a run's first chunk has no record: no phase B)
+    int rc;
+    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * nn)) || (rc = h->st.ensure(sizeof(PairState))) ||
+        (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_score.ensure(sizeof(double) * slots)) ||
+        (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) || (rc = h->tags[0].ensure(tag_bytes)) || (rc = h->tags_v.ensure(tag_bytes)) ||
+        (rc = h->tags_sorted[0].ensure(tag_bytes)) || (rc = h->tags_sorted[1].ensure(tag_bytes)) ||
+        (rc = h->model_count[0].ensure(2 * sizeof(int32_t))) || (rc = h->und_count.ensure(2 * sizeof(int32_t))) ||
+        (rc = h->surv_count.ensure(sizeof(int32_t))) || (rc = h->surv2_count.ensure(sizeof(int32_t))) ||
+        (rc = h->cand_stat.ensure(2 * sizeof(unsigned long long))) || (rc = h->cplan.ensure(2 * sizeof(int32_t))) ||
+        (rc = h->plan.ensure(sizeof(int32_t) * (2 + 2 + 4 + 16))) || (rc = h->rfrag.ensure((size_t)((nn + 15) / 16) * 1024)) ||
+        (rc = h->in_x1.ensure(sizeof(double) * 2 * nn)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * nn)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
+    if ((rc = upload_iota(s, h->tags[0].p, num_models))) return rc;
+    {   // every slot as k_solve leaves a live one: "no record" until an exact sweep writes it
+        const std::vector<double> sc0(slots, DBL_MAX);
+        const std::vector<int32_t> in0(slots, -2);
+        HIPCHK(hipMemcpyAsync(h->slot_score.p, sc0.data(), sizeof(double) * slots, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->slot_inl.p, in0.data(), sizeof(int32_t) * slots, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s)); // (the vectors go out of scope)
+    }
+    const int32_t counts2[2] = {num_models, 0};
+    const unsigned long long cs_in[2] = {cand_stat_in[0], cand_stat_in[1]};
+    HIPCHK(hipMemcpyAsync(h->model_count[0].p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->cand_stat.p, cs_in, sizeof cs_in, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->und_count.p, 0, 2 * sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(h->surv_count.p, 0, sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(h->surv2_count.p, 0, sizeof(int32_t), s));
+    if ((rc = stage_unit_pair(h, h->in_x1.as<double>(), h->in_x2.as<double>(), n, sq_threshold, rec_cnt, rec_score))) return rc;
+    hipLaunchKernelGGL(k_frag_unit, dim3((n + 16 + 255) / 256), dim3(256), 0, s, n, h->pts.as<double>(), h->rfrag.as<uint4>());
+    RunParams rp;
+    std::memset(&rp, 0, sizeof rp);
+    rp.kind = kind; rp.batch = 1; rp.n_max = nn; rp.chunk_len = (num_models + 3) / 4; rp.super_len = rp.chunk_len; rp.slot_stride = num_models; rp.mps = 4; rp.sample_sz = 3;
+    PairState *st = h->st.as<PairState>();
+    const Model *md = h->models.as<Model>();
+    uint32_t *tags = h->tags[0].as<uint32_t>(), *tags_v = h->tags_v.as<uint32_t>(), *tags_sorted = h->tags_sorted[0].as<uint32_t>();
+    int32_t *model_count = h->model_count[0].as<int32_t>(), *und_count = h->und_count.as<int32_t>(), *surv1 = h->surv_count.as<int32_t>(),
+            *surv2 = h->surv2_count.as<int32_t>(), *cplan = h->cplan.as<int32_t>();
+    // ---- Pass::count
+    {
+        unsigned long long *cand_stat = (flags & MDRP_RETIRE_TWO_PHASE) ? h->cand_stat.as<unsigned long long>() : nullptr; // null: the pair is never split
+        uint32_t *tags_u = tags_sorted;
+        int32_t *und_part = h->tags_sorted[1].as<int32_t>();
+        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, model_count, 2, CNT_WG_MODELS, cplan, surv1, (const int32_t *)nullptr,
+                           two_phase ? und_count : (int32_t *)nullptr);
+        const dim3 cgrid((unsigned)((num_models + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
+        MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, rp, st, h->rfrag.as<uint4>(), md, tags, model_count, cplan, tags_v, surv1,
+                            (unsigned long long *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr, 1, tags_u, und_part, und_count,
+                            (const int32_t *)nullptr, cand_stat);
+        if (two_phase) {
+            hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, und_count, 2, CNT_WG_MODELS, cplan, (int32_t *)nullptr,
+                               (const int32_t *)nullptr, (int32_t *)nullptr);
+            MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, rp, st, h->rfrag.as<uint4>(), md, tags_u, und_count, cplan, tags_v, surv1,
+                                (unsigned long long *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr, 2, (uint32_t *)nullptr, (int32_t *)nullptr,
+                                (int32_t *)nullptr, und_part, cand_stat);
+        }
+    }
+    // ---- Pass::bound
+    const uint32_t *sv_tags = tags_v;
+    const int32_t *sv_count = surv1;
+    if (flags & MDRP_RETIRE_BOUND) {
+        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, surv1, 1, BND_THREADS, cplan, surv2, (const int32_t *)nullptr);
+        const dim3 bgrid((unsigned)((num_models + BND_THREADS - 1) / BND_THREADS));
+        MDRP_SWEEP_DISPATCH(k_bound, kind, bgrid, dim3(BND_THREADS), 0, s, rp, st, h->pts.as<double>(), md, tags_v, surv1, cplan, tags, surv2,
+                            (unsigned long long *)nullptr);
+        sv_tags = tags; sv_count = surv2;
+    }
+    // ---- Pass::score
+    {
+        const bool wave = sweep == MDRP_RETIRE_SWEEP_WAVE, split = sweep == MDRP_RETIRE_SWEEP_SPLIT;
+        int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * 1 + 2;
+        if (wave) hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, sv_count, 1, SCW_THREADS / 64, plan, (int32_t *)nullptr,
+                                     (const int32_t *)nullptr, (int32_t *)nullptr);
+        hipLaunchKernelGGL(k_sort_tags, dim3(1), dim3(256), 0, s, rp, st, model_count, sv_count, sv_tags, tags_sorted);
+        if (!wave) hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, model_count, plan, totals, split ? SPLIT_HYP : SCORE_THREADS);
+        const long long capped = (long long)h->num_cu * 32;
+        if (wave) {
+            const long long ub = (num_models + SCW_THREADS / 64 - 1) / (SCW_THREADS / 64);
+            MDRP_SWEEP_DISPATCH(k_score_w, kind, dim3((unsigned)std::min(ub, capped)), dim3(SCW_THREADS), 0, s, rp, st, h->pts.as<double>(), md, tags_sorted,
+                                model_count, h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan);
+        } else if (split) {
+            const long long ub = (num_models + SPLIT_HYP - 1) / SPLIT_HYP + 1;
+            MDRP_SWEEP_DISPATCH(k_score_split, kind, dim3((unsigned)std::min(ub, capped)), dim3(SPLIT_THREADS), 0, s, rp, st, h->pts.as<double>(), md,
+                                tags_sorted, model_count, h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan, totals);
+        } else {
+            const dim3 grid((unsigned)((num_models + SCORE_THREADS - 1) / SCORE_THREADS));
+            MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), SCORE_TILE_BYTES, s, rp, st, h->pts.as<double>(), md, tags_sorted, model_count,
+                                h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan, totals);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    // ---- the slots, and who left where: from the survivor lists of the two stages (tags_v and tags are not written behind the bound)
+    std::vector<uint32_t> list1(slots), list2(slots);
+    int32_t n_und[2] = {0, 0}, n1 = 0, n2 = 0;
+    unsigned long long cs_out[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(scores, h->slot_score.p, sizeof(double) * slots, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(counts, h->slot_inl.p, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(list1.data(), tags_v, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(list2.data(), tags, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_und, und_count, sizeof n_und, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&n1, surv1, sizeof n1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&n2, surv2, sizeof n2, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cs_out, h->cand_stat.p, sizeof cs_out, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const bool bound = (flags & MDRP_RETIRE_BOUND) != 0;
+    if (n1 < 0 || n1 > num_models || n2 < 0 || n2 > n1) { g_err = "retire_models: survivor counts out of range"; return MDRP_ERR_INVALID; }
+    for (int k = 0; k < num_models; ++k) left_at[k] = 1;
+    for (int i = 0; i < n1; ++i) left_at[list1[i] & 0xFFFFFFu] = bound ? 2 : 3;
+    if (bound) for (int i = 0; i < n2; ++i) left_at[list2[i] & 0xFFFFFFu] = 3;
+    info[0] = n_und[0]; info[1] = n1; info[2] = bound ? n2 : n1;
+    cand_stat_out[0] = cs_out[0]; cand_stat_out[1] = cs_out[1];
     return MDRP_OK;
 }
 
