@@ -232,6 +232,66 @@ int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int n
                        int n, double sq_threshold, uint64_t rec_cnt, double rec_score, const uint64_t *cand_stat_in, int flags,
                        double *scores, int32_t *counts, int32_t *left_at, int32_t *info, uint64_t *cand_stat_out);
 
+/* The bookkeeping train of ONE super-chunk on caller-given slot tables (within ABI 0.6): what the scheduler issues behind the exact sweeps, launch
+ * for launch and with its buffer roles — one k_scan per chunk (the instantiation chosen by the scheduler's own rule from mps and the chunk's
+ * length; chunk_off and chunk_len from chunk_lens), k_lo_plan, then k_walk, or k_walk_ckpt when budgets are given.  Nothing is solved, scored or
+ * refined: k_lo does not run.  Between k_lo_plan and the walk the triggers are read back, and each one's LO result (ref_score, ref_cnt, refined) is
+ * filled from the three lo_* tables at the trigger's slot iter * mps + k_ref: "the LO result of the minimal model in this slot".
+ * `batch` pairs start from `states` (the bookkeeping fields of a pair's state; every other field is zero) and end in them: feeding the states —
+ * and, with budgets, the checkpoints — of one call into the next with chunk_start advanced by super_len runs several super-chunks.
+ * super_len = the sum of chunk_lens; slots per pair = super_len * mps; the trigger list of a pair holds super_len entries (trig_cap).
+ * Slot counts: >= 0 a model's inlier count, -1 an empty slot, -2 "no record" (a retired hypothesis), -3 in slot 0 of an iteration the NaN model
+ * of the reference's P3P: (0 inliers, n * sq_thr).  Scores of slots with a negative count are not read as records.
+ * Host memory throughout.  MDRP_ERR_INVALID: mps other than 4, 12, 16; sample_sz other than 3, 5, 7; batch < 1; no chunk, more than 8, a chunk
+ * length < 1 or more than 2^20 iterations in all; budgets that are not >= 1, strictly increasing, at most MDRP_MAX_BUDGETS and at most
+ * ropt->max_iterations; a NULL buffer; a trigger that names a slot outside the tables.  Of ropt only max_iterations, min_iterations,
+ * dyn_num_trials_mult and success_prob are read.  tests/test_gpu_replay.py pins the train to the sequential loop. */
+typedef struct {
+    int32_t n, active;
+    double sq_thr;
+    uint64_t best_min_cnt;
+    double best_min_score;
+    uint64_t dyn_max_iter, iterations, refinements, num_inliers;
+    double inlier_ratio, model_score;
+    mdrp_model best;
+} mdrp_replay_state;
+typedef struct {
+    uint32_t iter;    /* iteration inside the super-chunk */
+    int32_t k_ref;    /* slot the LO refines: the last record breaker of the iteration */
+    int32_t k_min;    /* slot that set a new best minimal score in the iteration, or -1 */
+    int32_t cnt_min;
+    double score_min;
+    int32_t cnt_ref;
+    int32_t pad_;
+} mdrp_replay_trigger;
+typedef struct {
+    /* in */
+    int32_t mps, sample_sz, batch, n_chunks;
+    uint64_t chunk_start;            /* absolute iteration of the super-chunk's first iteration */
+    const int32_t *chunk_lens;       /* [n_chunks] */
+    const double *slot_score;        /* [batch][super_len * mps] */
+    const int32_t *slot_inl;
+    const mdrp_model *models;
+    const double *lo_score;          /* the LO tables, same shape */
+    const int32_t *lo_cnt;
+    const mdrp_model *lo_models;
+    const uint64_t *budgets;         /* [n_budgets] or NULL */
+    int32_t n_budgets, pad_;
+    /* in and out */
+    mdrp_replay_state *states;       /* [batch] */
+    mdrp_replay_state *checkpoints;  /* [n_budgets][batch] (budgets only): budgets <= chunk_start keep what an earlier call wrote */
+    /* out */
+    mdrp_replay_trigger *triggers;   /* [batch][super_len]: pair p's first n_triggers[n_chunks - 1][p] entries, in iteration order */
+    int32_t *n_triggers;             /* [n_chunks][batch]: after each chunk's scan */
+    uint64_t *scan_cnt;              /* [n_chunks][batch]: best_min_cnt after each chunk's scan */
+    double *scan_score;              /* [n_chunks][batch]: best_min_score after each chunk's scan */
+    int32_t *scan_inst;              /* [n_chunks]: 10 * MPS + IPL of the k_scan instantiation launched */
+    int32_t *lo_plan;                /* [3 * batch + 2]: prefix[batch + 1] | begin[batch] | end[batch] | total */
+    int32_t *n_active;               /* [1] pairs still iterating */
+    uint64_t *max_needed;            /* [1] most iterations any of them still certainly needs */
+} mdrp_replay;
+int mdrp_replay_slots(mdrp_handle *h, const mdrp_ransac_opt *ropt, mdrp_replay *io);
+
 /* Hybrid LM refinement of `count` models, each over the correspondences of ONE pair (refine_monodepth_*relpose
  * @0x261030/@0x2592e0/@0x260fa0).  Host memory.  models in/out.  For MDRP_RELPOSE_5PT / MDRP_FUNDAMENTAL_7PT: the Sampson-only
  * refine_relpose @0x258f50 / refine_fundamental @0x2590d0 (d1, d2, scale_reproj, weight_sampson, estimate_shift ignored). */

@@ -26,7 +26,7 @@ EXPORTS = (
     "mdrp_refine_batch", "mdrp_refine_batch_async",
     "mdrp_gather_image_pairs", "mdrp_estimate_image_pairs_async",
     "mdrp_estimate_batch_prior", "mdrp_estimate_batch_prior_async",
-    "mdrp_retire_models",
+    "mdrp_retire_models", "mdrp_replay_slots",
 )
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
@@ -94,6 +94,23 @@ RESULT_DTYPE = np.dtype([("model", MODEL_DTYPE), ("refinements", "u8"), ("iterat
                          ("inlier_ratio", "f8"), ("model_score", "f8")])
 CAMERA_DTYPE = np.dtype([("model_id", "i4"), ("pad_", "i4"), ("params", "f8", 4)])
 assert MODEL_DTYPE.itemsize == C.sizeof(Model) and RESULT_DTYPE.itemsize == C.sizeof(Result) and CAMERA_DTYPE.itemsize == C.sizeof(Camera)
+
+# mdrp_replay_state / mdrp_replay_trigger / mdrp_replay (include/mdrp.h): the bookkeeping train of one super-chunk on caller-given slot tables
+REPLAY_STATE_DTYPE = np.dtype([("n", "i4"), ("active", "i4"), ("sq_thr", "f8"), ("best_min_cnt", "u8"), ("best_min_score", "f8"), ("dyn_max_iter", "u8"),
+                               ("iterations", "u8"), ("refinements", "u8"), ("num_inliers", "u8"), ("inlier_ratio", "f8"), ("model_score", "f8"),
+                               ("best", MODEL_DTYPE)])
+REPLAY_TRIGGER_DTYPE = np.dtype([("iter", "u4"), ("k_ref", "i4"), ("k_min", "i4"), ("cnt_min", "i4"), ("score_min", "f8"), ("cnt_ref", "i4"), ("pad_", "i4")])
+
+
+class Replay(C.Structure):
+    _fields_ = [("mps", C.c_int32), ("sample_sz", C.c_int32), ("batch", C.c_int32), ("n_chunks", C.c_int32), ("chunk_start", C.c_uint64),
+                ("chunk_lens", C.c_void_p), ("slot_score", C.c_void_p), ("slot_inl", C.c_void_p), ("models", C.c_void_p), ("lo_score", C.c_void_p),
+                ("lo_cnt", C.c_void_p), ("lo_models", C.c_void_p), ("budgets", C.c_void_p), ("n_budgets", C.c_int32), ("pad_", C.c_int32),
+                ("states", C.c_void_p), ("checkpoints", C.c_void_p), ("triggers", C.c_void_p), ("n_triggers", C.c_void_p), ("scan_cnt", C.c_void_p),
+                ("scan_score", C.c_void_p), ("scan_inst", C.c_void_p), ("lo_plan", C.c_void_p), ("n_active", C.c_void_p), ("max_needed", C.c_void_p)]
+
+
+assert REPLAY_STATE_DTYPE.itemsize == 176 and REPLAY_TRIGGER_DTYPE.itemsize == 32 and C.sizeof(Replay) == 176
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -169,6 +186,8 @@ def load_library():
         if hasattr(lib, "mdrp_retire_models"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.retire_models raises)
             lib.mdrp_retire_models.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_uint64, C.c_double, vp, C.c_int,
                                                vp, vp, vp, vp, vp]
+        if hasattr(lib, "mdrp_replay_slots"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.replay_slots raises)
+            lib.mdrp_replay_slots.argtypes = [vp, C.POINTER(RansacOpt), C.POINTER(Replay)]
         _lib = lib
         return lib
 
@@ -675,6 +694,36 @@ class Handle:
                                                        int(rec_cnt), score, _ptr(cs_in), int(flags), _ptr(scores), _ptr(counts), _ptr(left_at),
                                                        _ptr(info), _ptr(cs_out)))
         return scores, counts, left_at, info, cs_out
+
+    def replay_slots(self, mps, sample_sz, chunk_start, chunk_lens, ropt, states, slot_score, slot_inl, models, lo_score, lo_cnt, lo_models, budgets=None,
+                     checkpoints=None):
+        """the bookkeeping train of one super-chunk on caller-given tables (mdrp_replay_slots): k_scan per chunk -> k_lo_plan -> k_walk (k_walk_ckpt
+        with budgets), the LO results taken from the lo_* tables.  states: REPLAY_STATE_DTYPE [batch]; the six tables [batch][super_len * mps]
+        (models: MODEL_DTYPE); checkpoints: REPLAY_STATE_DTYPE [n_budgets][batch] of the call before, or None.  Returns dict(states, triggers: one
+        REPLAY_TRIGGER_DTYPE array per pair, n_triggers / scan_cnt / scan_score [n_chunks][batch] behind each scan, scan_inst [n_chunks], prefix,
+        begin, end, total of the LO plan, n_active, max_needed, checkpoints)"""
+        if not hasattr(self._lib, "mdrp_replay_slots"):
+            raise MdrpError(f"{LIB_PATH} has no mdrp_replay_slots: rebuild (mdrp_amd/build.py)")
+        lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
+        states = np.array(states, dtype=REPLAY_STATE_DTYPE).reshape(-1)  # (a copy: in and out)
+        batch, nc, slots = len(states), len(lens), int(lens.sum()) * int(mps)
+        tabs = [np.ascontiguousarray(a, dtype=dt).reshape(batch, -1) for a, dt in ((slot_score, np.float64), (slot_inl, np.int32), (models, MODEL_DTYPE),
+                                                                                  (lo_score, np.float64), (lo_cnt, np.int32), (lo_models, MODEL_DTYPE))]
+        for a in tabs:
+            if a.shape[1] != slots:
+                raise ValueError(f"replay_slots: a table of {a.shape[1]} slots per pair, expected {slots}")
+        bud = None if budgets is None else np.ascontiguousarray(budgets, dtype=np.uint64).reshape(-1)
+        nb = 0 if bud is None else len(bud)
+        ck = np.zeros((nb, batch), dtype=REPLAY_STATE_DTYPE) if checkpoints is None else np.array(checkpoints, dtype=REPLAY_STATE_DTYPE).reshape(nb, batch)
+        trig = np.zeros((batch, int(lens.sum())), dtype=REPLAY_TRIGGER_DTYPE)
+        ntr, scnt, ssc = np.zeros((nc, batch), np.int32), np.zeros((nc, batch), np.uint64), np.zeros((nc, batch), np.float64)
+        inst, plan, nact, need = np.zeros(nc, np.int32), np.zeros(3 * batch + 2, np.int32), np.zeros(1, np.int32), np.zeros(1, np.uint64)
+        io = Replay(int(mps), int(sample_sz), batch, nc, int(chunk_start), _ptr(lens), *[_ptr(a) for a in tabs], _ptr(bud), nb, 0, _ptr(states),
+                    _ptr(ck) if nb else None, _ptr(trig), _ptr(ntr), _ptr(scnt), _ptr(ssc), _ptr(inst), _ptr(plan), _ptr(nact), _ptr(need))
+        _check(self._lib, self._lib.mdrp_replay_slots(self._h, C.byref(ropt), C.byref(io)))
+        return dict(states=states, triggers=[trig[p, :ntr[-1, p]] for p in range(batch)], n_triggers=ntr, scan_cnt=scnt, scan_score=ssc, scan_inst=inst,
+                    prefix=plan[:batch + 1], begin=plan[batch + 1:2 * batch + 1], end=plan[2 * batch + 1:3 * batch + 1], total=int(plan[3 * batch + 1]),
+                    n_active=int(nact[0]), max_needed=int(need[0]), checkpoints=ck)
 
     def score_models_device(self, kind, models_ptr, num_models, x1_ptr, x2_ptr, n, sq_threshold, scores_ptr, counts_ptr):
         _check(self._lib, self._lib.mdrp_score_models(self._h, int(kind), MEM_DEVICE, C.c_void_p(models_ptr), int(num_models),

@@ -380,6 +380,23 @@ struct PassIn {
     const Model *priors;  // device memory, one per pair of the pass, or null (mdrp_estimate_batch_prior; never with `host` or `bud`)
 };
 
+// The k_scan instantiation of a chunk, by the model slots per sample and the chunk's length (four iterations per lane where a 4-slot chunk is
+// long: a 9872-iteration chunk is 39 steps of one wavefront instead of 154).  The scheduler (Pass::scan) and mdrp_replay_slots both launch through
+// here.  Returns 10 * MPS + IPL of the instantiation it launched.
+int launch_scan(hipStream_t s, int mps, int pairs, const RunParams &r, PairState *st, const double *slot_score, const int32_t *slot_inl, Trigger *trig,
+                int trig_cap, const int32_t *model_count, unsigned long long *scan_stats) {
+#define MDRP_SCAN(M, I)                                                                                                                            \
+    do {                                                                                                                                           \
+        hipLaunchKernelGGL((k_scan<M, I>), dim3(pairs), dim3(64), 0, s, r, st, slot_score, slot_inl, trig, trig_cap, model_count, scan_stats);      \
+        return 10 * M + I;                                                                                                                         \
+    } while (0)
+    if (mps == 16) MDRP_SCAN(16, 1);
+    if (mps == 12) MDRP_SCAN(12, 1);
+    if (r.chunk_len >= 1024) MDRP_SCAN(4, 4);
+    MDRP_SCAN(4, 1);
+#undef MDRP_SCAN
+}
+
 // Chunk c of the super-chunk under way, for the pairs [p0, p0 + pc).  Every kernel of the front indexes its per-pair arrays as base[pair]: a RANGE
 // of pairs is the same launch on offset bases with r.batch = pc (the plans are per-launch scratch).  The whole batch is the range [0, batch); the
 // host-buffer front runs the first chunk and the second chunk's solver slice by slice while later slices are still on their way over PCIe.
@@ -725,16 +742,9 @@ struct Pass : PassIn {
         return MDRP_OK;
     }
 
-    // ordered prefix over the iterations: LO triggers (four iterations per lane where the chunk is long: a 9872-iteration chunk is 39 steps of one
-    // wavefront instead of 154)
+    // ordered prefix over the iterations: LO triggers
     void scan(const ChunkView &v) {
-        unsigned long long *scan_stats = &cnt->progress.evals_sweep;
-#define MDRP_SCAN(M, I) hipLaunchKernelGGL((k_scan<M, I>), dim3(v.pc), dim3(64), 0, s, v.r, v.st, v.slot_score, v.slot_inl, v.trig, trig_cap, v.model_count, scan_stats)
-        if (mps == 16) MDRP_SCAN(16, 1);
-        else if (mps == 12) MDRP_SCAN(12, 1);
-        else if (v.r.chunk_len >= 1024) MDRP_SCAN(4, 4);
-        else MDRP_SCAN(4, 1);
-#undef MDRP_SCAN
+        (void)launch_scan(s, mps, v.pc, v.r, v.st, v.slot_score, v.slot_inl, v.trig, trig_cap, v.model_count, &cnt->progress.evals_sweep);
     }
 
     // count -> bound -> sort -> plan -> exact score -> scan of the view, on the main stream
@@ -2082,6 +2092,139 @@ int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int n
     if (bound) for (int i = 0; i < n2; ++i) left_at[list2[i] & 0xFFFFFFu] = 3;
     info[0] = n_und[0]; info[1] = n1; info[2] = bound ? n2 : n1;
     cand_stat_out[0] = cs_out[0]; cand_stat_out[1] = cs_out[1];
+    return MDRP_OK;
+}
+
+// The bookkeeping train of one super-chunk on caller-given slot tables: Pass::scan per chunk, Pass::lo's plan and Pass::walk launch for launch, with
+// the scheduler's buffer roles (slots of chunk c at chunk_off * mps in the pair's slot row, triggers appended to the pair's list, the LO plan in
+// work_pair, the progress record in the counter block, budgets in the params block, checkpoints in ckpt).  k_lo's part is played by the host.
+int mdrp_replay_slots(mdrp_handle *h, const mdrp_ransac_opt *ro, mdrp_replay *io) {
+    if (!h || !ro || !io) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    const int mps = io->mps, batch = io->batch, n_chunks = io->n_chunks, n_bud = io->budgets ? io->n_budgets : 0;
+    const char *why = nullptr;
+    long long super_ll = 0;
+    if (mps != 4 && mps != 12 && mps != 16) why = "replay_slots: mps must be 4, 12 or 16";
+    else if (io->sample_sz != 3 && io->sample_sz != 5 && io->sample_sz != 7) why = "replay_slots: sample_sz must be 3, 5 or 7";
+    else if (batch < 1 || n_chunks < 1 || n_chunks > sched::NC_MAX || !io->chunk_lens) why = "replay_slots: batch >= 1 and 1 to 8 chunks";
+    else {
+        for (int c = 0; c < n_chunks; ++c) { if (io->chunk_lens[c] < 1) why = "replay_slots: a chunk length < 1"; super_ll += io->chunk_lens[c]; }
+        if (!why && super_ll > (1 << 20)) why = "replay_slots: more than 2^20 iterations";
+    }
+    if (!why && (!io->slot_score || !io->slot_inl || !io->models || !io->lo_score || !io->lo_cnt || !io->lo_models || !io->states || !io->triggers ||
+                 !io->n_triggers || !io->scan_cnt || !io->scan_score || !io->scan_inst || !io->lo_plan || !io->n_active || !io->max_needed ||
+                 (n_bud && !io->checkpoints)))
+        why = "replay_slots: a NULL buffer";
+    if (!why && (io->n_budgets < 0 || n_bud > MAX_BUDGETS)) why = "replay_slots: more than MDRP_MAX_BUDGETS";
+    for (int c = 0; c < n_bud && !why; ++c)
+        if (io->budgets[c] < 1 || (c > 0 && io->budgets[c] <= io->budgets[c - 1]) || io->budgets[c] > ro->max_iterations)
+            why = "replay_slots: budgets must be >= 1, strictly increasing and at most max_iterations";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    hipStream_t s = h->stream;
+    const int super_len = (int)super_ll, trig_cap = super_len;
+    const size_t b = (size_t)batch, slots = b * super_len * mps, plan_ints = 3 * b + 2;
+    int rc;
+    if ((rc = h->st.ensure(sizeof(PairState) * b)) || (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_score.ensure(sizeof(double) * slots)) ||
+        (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) || (rc = h->triggers.ensure(sizeof(Trigger) * b * trig_cap)) ||
+        (rc = h->work_pair.ensure(sizeof(int32_t) * plan_ints)) || (rc = h->counters.ensure(sizeof(Counters))) ||
+        (rc = h->model_count[0].ensure(sizeof(int32_t) * 2 * b)) || (rc = h->model_count[1].ensure(sizeof(int32_t) * 2 * b)) ||
+        (rc = h->params.ensure(sizeof(uint64_t) * MAX_BUDGETS)) || (rc = h->ckpt.ensure(sizeof(PairState) * b * std::max(n_bud, 1))))
+        return rc;
+    std::vector<PairState> st_host(b), ck_host(b * n_bud);
+    const auto stage = [](const mdrp_replay_state &z) {
+        PairState ps;
+        std::memset(&ps, 0, sizeof ps);
+        ps.n = z.n; ps.active = z.active; ps.sq_thr = z.sq_thr; ps.eps = std::sqrt(z.sq_thr);
+        ps.best_min_cnt = z.best_min_cnt; ps.best_min_score = z.best_min_score; ps.dyn_max_iter = z.dyn_max_iter; ps.iterations = z.iterations;
+        ps.refinements = z.refinements; ps.num_inliers = z.num_inliers; ps.inlier_ratio = z.inlier_ratio; ps.model_score = z.model_score;
+        std::memcpy(&ps.best, &z.best, sizeof(Model));
+        return ps;
+    };
+    const auto unstage = [](const PairState &ps, mdrp_replay_state &z) {
+        z.n = ps.n; z.active = ps.active; z.sq_thr = ps.sq_thr; z.best_min_cnt = ps.best_min_cnt; z.best_min_score = ps.best_min_score;
+        z.dyn_max_iter = ps.dyn_max_iter; z.iterations = ps.iterations; z.refinements = ps.refinements; z.num_inliers = ps.num_inliers;
+        z.inlier_ratio = ps.inlier_ratio; z.model_score = ps.model_score;
+        std::memcpy(&z.best, &ps.best, sizeof(Model));
+    };
+    for (size_t p = 0; p < b; ++p) st_host[p] = stage(io->states[p]);
+    for (size_t e = 0; e < ck_host.size(); ++e) ck_host[e] = stage(io->checkpoints[e]);
+    PairState *st = h->st.as<PairState>();
+    Trigger *trig = h->triggers.as<Trigger>();
+    int32_t *lo_plan = h->work_pair.as<int32_t>();
+    Counters *cnt = h->counters.as<Counters>();
+    HIPCHK(hipMemcpyAsync(st, st_host.data(), sizeof(PairState) * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->models.p, io->models, sizeof(Model) * slots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->slot_score.p, io->slot_score, sizeof(double) * slots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->slot_inl.p, io->slot_inl, sizeof(int32_t) * slots, hipMemcpyHostToDevice, s));
+    if (n_bud) {
+        HIPCHK(hipMemcpyAsync(h->params.p, io->budgets, sizeof(uint64_t) * n_bud, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->ckpt.p, ck_host.data(), sizeof(PairState) * ck_host.size(), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemsetAsync(h->model_count[0].p, 0, sizeof(int32_t) * 2 * b, s));
+    HIPCHK(hipMemsetAsync(h->model_count[1].p, 0, sizeof(int32_t) * 2 * b, s));
+    HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s)); // (begin_super_chunk)
+    RunParams rp;
+    std::memset(&rp, 0, sizeof rp);
+    rp.batch = batch; rp.n_max = 1; rp.mps = mps; rp.sample_sz = io->sample_sz; rp.slot_stride = super_len * mps; rp.super_len = super_len;
+    rp.chunk_start = io->chunk_start; rp.max_iterations = ro->max_iterations; rp.min_iterations = ro->min_iterations;
+    rp.dyn_mult = ro->dyn_num_trials_mult; rp.log_prob_missing = std::log(1.0 - ro->success_prob);
+    // ---- Pass::scan, chunk by chunk; the pair states behind each scan travel back for the records and trigger counts
+    std::vector<PairState> scanned(b * n_chunks);
+    int off = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+        RunParams r = rp;
+        r.chunk_len = io->chunk_lens[c]; r.chunk_off = off;
+        io->scan_inst[c] = launch_scan(s, mps, batch, r, st, h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), trig, trig_cap,
+                                       h->model_count[c & 1].as<int32_t>(), &cnt->progress.evals_sweep);
+        HIPCHK(hipMemcpyAsync(scanned.data() + b * c, st, sizeof(PairState) * b, hipMemcpyDeviceToHost, s));
+        off += io->chunk_lens[c];
+    }
+    rp.chunk_len = io->chunk_lens[n_chunks - 1]; rp.chunk_off = off - rp.chunk_len; // (as run_pass leaves them behind its chunk loop)
+    // ---- Pass::lo: the plan; the LO itself is the caller's tables
+    hipLaunchKernelGGL(k_lo_plan, dim3(1), dim3(PLAN_THREADS), 0, s, batch, st, (const int32_t *)nullptr, lo_plan);
+    HIPCHK(hipGetLastError());
+    std::vector<Trigger> trig_host(b * trig_cap);
+    HIPCHK(hipMemcpyAsync(trig_host.data(), trig, sizeof(Trigger) * trig_host.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->lo_plan, lo_plan, sizeof(int32_t) * plan_ints, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int c = 0; c < n_chunks; ++c)
+        for (size_t p = 0; p < b; ++p) {
+            const PairState &ps = scanned[b * c + p];
+            io->n_triggers[b * c + p] = ps.n_triggers; io->scan_cnt[b * c + p] = ps.best_min_cnt; io->scan_score[b * c + p] = ps.best_min_score;
+        }
+    for (size_t p = 0; p < b; ++p) {
+        const int nt = scanned[b * (n_chunks - 1) + p].n_triggers;
+        if (nt < 0 || nt > trig_cap) { g_err = "replay_slots: a trigger count outside the list"; return MDRP_ERR_INVALID; }
+        for (int k = 0; k < nt; ++k) {
+            Trigger &tr = trig_host[p * trig_cap + k];
+            if (tr.iter >= (uint32_t)super_len || tr.k_ref < 0 || tr.k_ref >= mps || tr.k_min < -1 || tr.k_min >= mps) {
+                g_err = "replay_slots: a trigger names a slot outside the tables"; return MDRP_ERR_INVALID;
+            }
+            const size_t slot = p * (size_t)rp.slot_stride + (size_t)tr.iter * mps + tr.k_ref;
+            tr.ref_score = io->lo_score[slot]; tr.ref_cnt = io->lo_cnt[slot];
+            std::memcpy(&tr.refined, &io->lo_models[slot], sizeof(Model));
+            mdrp_replay_trigger &o = io->triggers[p * trig_cap + k];
+            o.iter = tr.iter; o.k_ref = tr.k_ref; o.k_min = tr.k_min; o.cnt_min = tr.cnt_min; o.score_min = tr.score_min; o.cnt_ref = tr.cnt_ref; o.pad_ = 0;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(trig, trig_host.data(), sizeof(Trigger) * trig_host.size(), hipMemcpyHostToDevice, s));
+    // ---- Pass::walk
+    if (n_bud)
+        hipLaunchKernelGGL(k_walk_ckpt, dim3((batch + WALK_CKPT_THREADS - 1) / WALK_CKPT_THREADS), dim3(WALK_CKPT_THREADS), 0, s, rp, st, h->models.as<Model>(), trig,
+                           trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed, h->params.as<uint64_t>(), n_bud, h->ckpt.as<PairState>());
+    else
+        hipLaunchKernelGGL(k_walk, dim3((batch + 63) / 64), dim3(64), 0, s, rp, st, h->models.as<Model>(), trig, trig_cap, &cnt->progress.n_active,
+                           &cnt->progress.max_needed, (const int32_t *)nullptr, 0, 0, 0);
+    HIPCHK(hipGetLastError());
+    // ---- Pass::read_progress, and the states
+    Progress pr;
+    HIPCHK(hipMemcpyAsync(&pr, &cnt->progress, sizeof pr, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(st_host.data(), st, sizeof(PairState) * b, hipMemcpyDeviceToHost, s));
+    if (n_bud) HIPCHK(hipMemcpyAsync(ck_host.data(), h->ckpt.p, sizeof(PairState) * ck_host.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *io->n_active = pr.n_active; *io->max_needed = pr.max_needed;
+    for (size_t p = 0; p < b; ++p) unstage(st_host[p], io->states[p]);
+    for (size_t e = 0; e < ck_host.size(); ++e) unstage(ck_host[e], io->checkpoints[e]);
     return MDRP_OK;
 }
 

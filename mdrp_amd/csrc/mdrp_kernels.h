@@ -2343,10 +2343,13 @@ __device__ bool walk_pair(const RunParams &rp, PairState &ps, const Model *__res
             }
     };
     // stop test applied after each completed iteration: it >= max -> stop; it > min && it > dyn -> stop
+    // (+ 1 saturates: a bound of 2^64 - 1 — the reference's (uint64_t) of a dynamic bound in (-2, -1], dyn_num_trials_mult < 0 — is never exceeded, and
+    // the sum must not wrap to 0 and end the run at min_iterations + 1; max_iterations then caps the saturated value, and it >= max_iterations stops)
+    auto next_of = [](uint64_t v) -> uint64_t { return v == ~0ull ? v : v + 1; };
     auto first_stop = [&](uint64_t lo /*first candidate value of it*/) -> uint64_t {
         uint64_t s = lo;
-        if (s < ps.dyn_max_iter + 1) s = ps.dyn_max_iter + 1;
-        if (s < rp.min_iterations + 1) s = rp.min_iterations + 1;
+        if (s < next_of(ps.dyn_max_iter)) s = next_of(ps.dyn_max_iter);
+        if (s < next_of(rp.min_iterations)) s = next_of(rp.min_iterations);
         if (s > rp.max_iterations) s = rp.max_iterations;
         if (lo > s) s = lo;
         return s;

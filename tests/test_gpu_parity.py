@@ -618,6 +618,26 @@ def test_dynamic_stopping_chunks(handle, capi, po):
         assert int(res["num_inliers"]) == st.num_inliers and int(res["refinements"]) == st.refinements and (mask == mk).all(), of
 
 
+def test_a_dynamic_bound_of_2_to_the_64_minus_1_is_never_exceeded(handle, capi, po):
+    """dyn_num_trials_mult = -1 and success_prob = 0.5 on pairs with 73 % inliers: log(0.5) / log(1 - 0.73^3) * -1 = -1.4, ceil gives -1 and the
+    reference's (uint64_t) 2^64 - 1.  `iterations > dynamic_max_iter` is then never true and the run ends at max_iterations.  Checked here on the
+    CPU: the oracle's final inlier ratio gives that bound (it holds from the run's last LO on) and the oracle ran all 400 iterations although
+    min_iterations is 10.  walk_pair's trigger-free stretches once computed dyn_max_iter + 1 in uint64_t, which wrapped to 0: the device stopped
+    at iteration 11 (tests/test_gpu_replay.py has the unit cases)."""
+    import prior_ref
+    from mdrp_amd import synth
+    kw = dict(max_iterations=400, min_iterations=10, dyn_num_trials_mult=-1.0, success_prob=0.5, max_epipolar_error=2.0, max_reproj_error=16.0)
+    for idx in (81, 82, 83):
+        p = synth.make_pair(idx, 300, noise_px=0.5, depth_noise=0.02, outlier_frac=0.27)
+        cam = np.array([0, 3, 800.0, 0.0, 0.0, 0.0])
+        oro = po.ransac_opt(**kw)
+        m, st, mk = po.estimate(po.CALIB, p["x1"], p["x2"], p["d1"], p["d2"], oro, po.bundle_opt(loss_type=4), po.cam_flat(0, [800.0, 0, 0]), po.cam_flat(0, [800.0, 0, 0]))
+        assert prior_ref.dyn_max_iter(st.inlier_ratio, oro, np.log(0.5)) == 2 ** 64 - 1 and st.iterations == 400, (idx, st.inlier_ratio, st.iterations)
+        res, mask = _run_estimate(capi, handle, 0, p["x1"], p["x2"], p["d1"], p["d2"], kw, {"loss_type": "TRUNCATED_CAUCHY"}, cam, cam)
+        assert int(res["iterations"]) == st.iterations, (idx, int(res["iterations"]), st.iterations)
+        assert int(res["num_inliers"]) == st.num_inliers and int(res["refinements"]) == st.refinements and (mask == mk).all(), idx
+
+
 def test_poselib_signatures(po):
     """the drop-in module: same call shape and info keys as the reference demo (make_pair.py:111, notebook cell 16)"""
     import mdrp_amd.poselib as poselib
