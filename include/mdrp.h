@@ -79,11 +79,11 @@ typedef struct {
                                        * (0, N eps^2) and `refinements` at 1 (tests/golden/initial.npz). */
     /* ---- ABI 0.4: the remaining RansacOptions fields of the reference (+0x38 progressive_sampling,
      * +0x40 max_prosac_iterations, +0x48 real_focal_check), so that a host can hand its options over unabridged.
-     * PROSAC (RandomSampler::initialize_prosac @0x4f8a20) is not built — every caller in the reference passes
-     * progressive_sampling = False (eval.py:99, make_video.py:192): a non-zero value is refused with MDRP_ERR_UNSUPPORTED
-     * on every estimator.  (This field sits where ABI 0.3 had a zero `reserved_` word.) */
+     * PROSAC (RandomSampler::initialize_prosac @0x4f8a20) needs the records in quality order, so it is built behind entry points of its own
+     * that take the scores: mdrp_estimate_batch_ranked / _async, below.  Every other estimator entry point refuses a non-zero value
+     * with MDRP_ERR_UNSUPPORTED, as before.  (This field sits where ABI 0.3 had a zero `reserved_` word.) */
     int32_t progressive_sampling;    /* 0 */
-    uint64_t max_prosac_iterations;  /* 100000; read only with progressive_sampling, i.e. never */
+    uint64_t max_prosac_iterations;  /* 100000; read by the ranked entry points only */
     int32_t real_focal_check;        /* 0.  Only the 6- / 7-point baselines look at it in the reference; refused there when set */
     int32_t reserved_;
 } mdrp_ransac_opt;
@@ -531,6 +531,46 @@ int mdrp_estimate_batch_prior_async(mdrp_handle *h, int kind, const double *x1_d
                                     const double *d2_dev, int batch, int n_max, const int32_t *n_per_pair_host, const mdrp_camera *cam1_host,
                                     const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
                                     const mdrp_model *prior_dev, uint8_t *inlier_mask_dev);
+
+/* ---- Estimate in match-score order: PROSAC (added within ABI 0.6: new symbols only).
+ * mdrp_estimate_batch on the records of every pair taken in descending score order, with the sample sequence of the reference's
+ * RansacOptions::progressive_sampling (RandomSampler::initialize_prosac / generate_sample) in place of the uniform one.  For a pair with n records
+ * and scores s[0..n), higher is better:
+ *   - order = stable argsort of -key, key = s with NaN replaced by -inf; -0.0 and +0.0 tie; ties go by ascending caller index.  order[r] is the
+ *     caller index of the record at rank r.  scores == NULL: the records are in quality order already, nothing is ranked or permuted.
+ *   - the sampler (sample size K = 3), with M = ropt->max_prosac_iterations, all in fp64 and in exactly this order of operations:
+ *       growth[0..max(n,K)):  T = (double)M;  for i in 0..K-1: T *= (double)(K-i) / (double)(n-i);  Tp = 1;  growth[0..K) = 1;
+ *                             for i in K..n-1: Tn = T*(i+1.0)/(i+1.0-K); Tp += ceil(Tn - T); growth[i] = Tp; T = Tn
+ *       state:   rng = ropt->seed, k = 1, sub = K
+ *       sample:  if k < M: K-1 distinct indices from [0, sub-1) by the estimators' splitmix64 draw (redraw on a duplicate, same modulo rule), then
+ *                index K-1 := sub-1;  k += 1;  if k < M and k > growth[sub-1]: sub = min(sub+1, n)
+ *                else: the estimators' uniform draw of K from n
+ *     M <= 1 is uniform sampling from the first sample on: the call then equals mdrp_estimate_batch on the pre-sorted records bit for bit.
+ *   - everything else runs on the ordered records and is mdrp_estimate_batch's, unchanged: normalisation sums, the MSAC sums in record order, LO,
+ *     stopping, closing LO, get_inliers, the inlier-only refinement, the record.  inlier_mask[order[r]] = mask of rank r: the mask is in the
+ *     caller's order; bytes at or past n are 0.
+ * These entry points are what progressive_sampling selects in the reference, so they sample progressively whether ropt->progressive_sampling is 0
+ * or 1 (a reference caller's options pass unabridged); every other entry point still refuses the switch.  kind: MDRP_CALIB, MDRP_SHARED_FOCAL or
+ * MDRP_VARYING_FOCAL; any other kind is MDRP_ERR_INVALID, as is everything mdrp_estimate_batch refuses (NULL depths, n_per_pair out of range, ...).
+ * A refusal leaves the handle usable.  x1, x2, d1, d2, scores ([B][n_max] doubles or NULL) and inlier_mask ([B][n_max] bytes or NULL) live in
+ * mem_space; n_per_pair, cameras and out ([B]) in HOST memory.  Host buffers are copied in one piece on the handle's stream (no sliced front).
+ * Iteration budgets and priors do not combine with scores.  The ordered copies of the correspondences are the handle's and are allocated before
+ * the passes are sized from the free memory. */
+int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
+                               const double *scores, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
+                               const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out,
+                               uint8_t *inlier_mask);
+/* Device-resident variant, as mdrp_estimate_batch_async: results through mdrp_fetch_results / mdrp_copy_results_device. */
+int mdrp_estimate_batch_ranked_async(mdrp_handle *h, int kind, const double *x1_dev, const double *x2_dev, const double *d1_dev,
+                                     const double *d2_dev, const double *scores_dev, int batch, int n_max, const int32_t *n_per_pair_host,
+                                     const mdrp_camera *cam1_host, const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt,
+                                     const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev);
+/* Inspection: the device sampler alone for one table of n records, drawn chunk by chunk (chunk_lens[n_chunks], each >= 1) through the launch the
+ * scheduler uses, its state carried on the device between chunks.  out: [sum of chunk_lens][3] uint32 in HOST memory; n < 3 writes nothing. */
+int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks,
+                        uint32_t *out);
+/* Inspection: the ranking kernel alone.  scores [B][n_max] doubles and order [B][n_max] int32 live in mem_space; order[b][r] = -1 for r >= n. */
+int mdrp_rank_scores(mdrp_handle *h, int mem_space, const double *scores, int batch, int n_max, const int32_t *n_per_pair, int32_t *order);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ EXPORTS = (
     "mdrp_gather_image_pairs", "mdrp_estimate_image_pairs_async",
     "mdrp_estimate_batch_prior", "mdrp_estimate_batch_prior_async",
     "mdrp_retire_models", "mdrp_replay_slots",
+    "mdrp_estimate_batch_ranked", "mdrp_estimate_batch_ranked_async", "mdrp_prosac_samples", "mdrp_rank_scores",
 )
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
@@ -178,6 +179,13 @@ def load_library():
         if hasattr(lib, "mdrp_gather_image_pairs"):  # (an older ABI-0.6 library through MDRP_LIB has no image-pairs entry points: Handle._image_pairs_fn raises)
             lib.mdrp_gather_image_pairs.argtypes = [vp, C.POINTER(ImagePairs), C.c_int, dp, dp, dp, dp, ip, ip]
             lib.mdrp_estimate_image_pairs_async.argtypes = [vp, C.c_int, C.POINTER(ImagePairs), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
+        if hasattr(lib, "mdrp_estimate_batch_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked entry points: Handle._ranked_fn raises)
+            lib.mdrp_estimate_batch_ranked.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
+            lib.mdrp_estimate_batch_ranked_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                             C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
+            lib.mdrp_prosac_samples.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint64, ip, C.c_int, vp]
+            lib.mdrp_rank_scores.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, ip, vp]
         if hasattr(lib, "mdrp_estimate_batch_prior"):  # (an older ABI-0.6 library through MDRP_LIB has no prior entry points: Handle._prior_fn raises)
             lib.mdrp_estimate_batch_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
@@ -551,6 +559,73 @@ class Handle:
             return C.c_void_p(p) if p else None
         _check(self._lib, self._prior_fn("mdrp_estimate_batch_prior_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), int(batch), int(n_max),
                                                                             _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(priors_ptr), vp(mask_ptr)))
+
+    # ---- estimate in match-score order (include/mdrp.h: mdrp_estimate_batch_ranked).  Arguments go to the library as they are: the library checks them.
+    def _ranked_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the ranked entry points (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    def estimate_batch_ranked(self, kind, x1, x2, d1, d2, scores, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
+        """estimate_batch in score order with the progressive sampler, host (numpy) buffers; scores (B, N), higher is better, or None: the records
+        are in quality order already.  (records, masks (B, N) uint8 in the caller's order or None)"""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+            raise ValueError("expected x1,x2 (B,N,2)")
+        d1 = None if d1 is None else np.ascontiguousarray(d1, dtype=np.float64)
+        d2 = None if d2 is None else np.ascontiguousarray(d2, dtype=np.float64)
+        if d1 is not None and d2 is not None and (d1.shape != x1.shape[:2] or d2.shape != d1.shape):
+            raise ValueError("expected d1,d2 (B,N)")
+        B, N = x1.shape[:2]
+        scores = None if scores is None else np.ascontiguousarray(scores, dtype=np.float64)
+        if scores is not None and scores.shape != (B, N):
+            raise ValueError(f"expected scores ({B},{N}), got {scores.shape}")
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        out = np.zeros(B, dtype=RESULT_DTYPE)
+        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        _check(self._lib, self._ranked_fn("mdrp_estimate_batch_ranked")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), _ptr(scores), B, N,
+                                                                        _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(out), _ptr(mask)))
+        return out, mask
+
+    def estimate_batch_ranked_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, scores_ptr, batch, n_max, ropt, bopt, n_per_pair=None, cam1=None, cam2=None,
+                                     mask_ptr=None):
+        """the same on device pointers (ints), queued on the handle's stream; scores_ptr: batch x n_max float64, or None / 0 for records in quality
+        order.  Records: fetch_results / copy_results_device."""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _check(self._lib, self._ranked_fn("mdrp_estimate_batch_ranked_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), vp(scores_ptr),
+                                                                              int(batch), int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                                              vp(mask_ptr)))
+
+    def prosac_samples(self, seed, n, max_prosac_iterations, chunk_lens, fill=0):
+        """the device's progressive sampler for one table of n records, drawn chunk by chunk: (sum(chunk_lens), 3) uint32 (`fill` where n < 3:
+        nothing is written)"""
+        lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
+        out = np.full((int(lens.sum()), 3), fill, dtype=np.uint32)
+        _check(self._lib, self._ranked_fn("mdrp_prosac_samples")(self._h, int(seed), int(n), int(max_prosac_iterations), _ptr(lens), len(lens), _ptr(out)))
+        return out
+
+    def rank_scores(self, scores, n_per_pair=None):
+        """k_rank on host scores (B, N): order (B, N) int32, -1 at and past n"""
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        B, N = scores.shape
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        order = np.full((B, N), -2, dtype=np.int32)
+        _check(self._lib, self._ranked_fn("mdrp_rank_scores")(self._h, MEM_HOST, _ptr(scores), B, N, _ptr(npp), _ptr(order)))
+        return order
+
+    def rank_scores_device(self, scores_ptr, batch, n_max, order_ptr, n_per_pair=None):
+        """k_rank on device pointers (ints): scores batch x n_max float64, order batch x n_max int32.  Synchronous."""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        _check(self._lib, self._ranked_fn("mdrp_rank_scores")(self._h, MEM_DEVICE, C.c_void_p(scores_ptr), int(batch), int(n_max), _ptr(npp), C.c_void_p(order_ptr)))
 
     # ---- device front end: a Matches descriptor of device pointers
     def gather_matches(self, mm, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):

@@ -8,6 +8,7 @@
 #include "mdrp_schedule.h"
 #include "mdrp_from_model.h"
 #include "mdrp_prior.h"
+#include "mdrp_prosac.h"
 // MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -180,6 +181,9 @@ struct mdrp_handle {
     int last_budgets = 0;              // budgets of the last call (0: it had none)
     DevBuf in_x1, in_x2, in_d1, in_d2; // staging when the caller passes host memory
     DevBuf fm_models, fm_init;         // mdrp_refine_batch (and mdrp_estimate_batch_prior: the priors): the caller's models when they come from host memory | start-model scores [batch] f64, counts [batch] i32
+    // ranked calls (mdrp_estimate_batch_ranked): the correspondences in score order | order [batch][n_max] int32 | the mask in that order |
+    // scores and n per pair when they come from host memory | per pass: sample index per table (u64) | schedule offsets (u64, tables + 1) | subset sizes (u32)
+    DevBuf pr_x1, pr_x2, pr_d1, pr_d2, pr_order, pr_mask, pr_scores, pr_nper, pr_tab;
     DevBuf fe_x1, fe_x2, fe_d1, fe_d2, fe_slot, fe_n; // device front end (mdrp_estimate_matches_async): gathered correspondences | slot of every match row | kept rows per pair
     Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
     size_t fe_n_host_cap = 0;
@@ -378,7 +382,35 @@ struct PassIn {
     int batch_call;       // pairs of the whole API call
     const BudgetOut *bud; // (or null)
     const Model *priors;  // device memory, one per pair of the pass, or null (mdrp_estimate_batch_prior; never with `host` or `bud`)
+    const uint64_t *prosac; // ranked call: max_prosac_iterations of the progressive sampler (mdrp_prosac.h), or null: the uniform sampler
 };
+
+// The progressive sampler's launch: Pass::samples and mdrp_prosac_samples both go through here.  `tab`: sample index per table | schedule offsets |
+// subset sizes (prosac_tables).
+struct ProsacTab { uint64_t *k; const uint64_t *off; const uint32_t *sub; };
+void launch_samples_prosac(hipStream_t st, int threads, int n_tables, const int32_t *d_table_n, uint64_t *d_table_state, const ProsacTab &tab,
+                           uint64_t max_prosac, int len, uint32_t *smp) {
+    hipLaunchKernelGGL(k_samples_prosac, dim3(n_tables), dim3(threads), 0, st, n_tables, d_table_n, d_table_state, tab.k, tab.off, tab.sub,
+                       prosac::prosac_samples(max_prosac), len, smp);
+}
+// the tables of a run of at most `count` samples, one schedule per sample table, uploaded on `s` (pageable staging: the copy has left it on return)
+int prosac_tables(mdrp_handle *h, hipStream_t s, const int32_t *tab_n, int n_tables, uint64_t max_prosac, uint64_t count, ProsacTab &tab) {
+    std::vector<uint64_t> head(2 * (size_t)n_tables + 1, 0); // k = 0 per table | offsets
+    std::vector<uint32_t> sub;
+    for (int t = 0; t < n_tables; ++t) {
+        const std::vector<uint32_t> one = prosac::subset_schedule((uint64_t)std::max(tab_n[t], 0), max_prosac, count, true);
+        head[n_tables + t] = sub.size();
+        sub.insert(sub.end(), one.begin(), one.end());
+    }
+    head[2 * (size_t)n_tables] = sub.size();
+    const size_t hb = sizeof(uint64_t) * head.size(), sb = sizeof(uint32_t) * sub.size();
+    if (int rc = h->pr_tab.ensure(hb + sb + 16)) return rc;
+    unsigned char *d = h->pr_tab.as<unsigned char>();
+    HIPCHK(hipMemcpyAsync(d, head.data(), hb, hipMemcpyHostToDevice, s));
+    if (sb) HIPCHK(hipMemcpyAsync(d + hb, sub.data(), sb, hipMemcpyHostToDevice, s));
+    tab.k = reinterpret_cast<uint64_t *>(d); tab.off = tab.k + n_tables; tab.sub = reinterpret_cast<const uint32_t *>(d + hb);
+    return MDRP_OK;
+}
 
 // The k_scan instantiation of a chunk, by the model slots per sample and the chunk's length (four iterations per lane where a 4-slot chunk is
 // long: a 9872-iteration chunk is 39 steps of one wavefront instead of 154).  The scheduler (Pass::scan) and mdrp_replay_slots both launch through
@@ -472,6 +504,7 @@ struct Pass : PassIn {
     hipStream_t aux = nullptr, aux2 = nullptr; // the handle's, or `s` where the super-chunk is not pipelined
     int32_t *fz_ctl = nullptr, *fz_done = nullptr, *fz_fin = nullptr, *fz_ready = nullptr;
     bool final_done = false; // the fused tail has run the final refinements
+    ProsacTab ptab{nullptr, nullptr, nullptr}; // ranked call: the progressive sampler's tables
 
     Pass(mdrp_handle *h_, const PassIn &in)
         : PassIn(in), h(h_), s(h_->stream), est_shift((kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0), classic(kind >= MDRP_RELPOSE_5PT),
@@ -521,6 +554,7 @@ struct Pass : PassIn {
         std::memcpy(ph + sz.off_nper, n_host, sizeof(int32_t) * batch);
         if (bud) std::memcpy(ph + sz.off_bud, bud->budgets, sizeof(uint64_t) * n_bud);
         HIPCHK(hipMemcpyAsync(pd, ph, sz.params, hipMemcpyHostToDevice, s));
+        if (prosac) { if (int rc = prosac_tables(h, s, tab_n.data(), n_tables, *prosac, ro->max_iterations, ptab)) return rc; }
 
         std::memset(&rp, 0, sizeof rp);
         rp.kind = kind; rp.solver = solver_for(kind, est_shift); rp.est_shift = est_shift;
@@ -583,7 +617,8 @@ struct Pass : PassIn {
     }
 
     void samples(hipStream_t st_, int len_, uint32_t *smp_) {
-        if (ssz == 6) hipLaunchKernelGGL(kc_samples<6>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
+        if (prosac) launch_samples_prosac(st_, samp_threads, n_tables, d_table_n, d_table_state, ptab, *prosac, len_, smp_);
+        else if (ssz == 6) hipLaunchKernelGGL(kc_samples<6>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
         else if (ssz == 5) hipLaunchKernelGGL(kc_samples<5>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
         else if (ssz == 7) hipLaunchKernelGGL(kc_samples<7>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
         else hipLaunchKernelGGL(k_samples, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
@@ -1005,7 +1040,7 @@ int estimate_refusals(mdrp_handle *h, int kind, const double *d1, const double *
     if ((kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT) && batch > 0 && (!cam1 || !cam2)) { g_err = "calibrated estimator needs cameras"; return MDRP_ERR_INVALID; }
     if (kind <= 2 && batch > 0 && n_max > 0 && (!d1 || !d2)) { g_err = "monodepth estimator needs depths"; return MDRP_ERR_INVALID; }
     // RansacOptions switches of the reference that are not built are refused, never ignored (the reference would return different results)
-    if (ro->progressive_sampling) { g_err = "progressive_sampling (PROSAC, RandomSampler::initialize_prosac) is not built"; return MDRP_ERR_UNSUPPORTED; }
+    if (ro->progressive_sampling) { g_err = "progressive_sampling (PROSAC, RandomSampler::initialize_prosac) is not built on this entry point: it needs the match scores, mdrp_estimate_batch_ranked (scores= in Python) takes them"; return MDRP_ERR_UNSUPPORTED; }
     if (ro->real_focal_check && (kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT)) { g_err = "real_focal_check is not built"; return MDRP_ERR_UNSUPPORTED; }
     return MDRP_OK;
 }
@@ -1013,9 +1048,11 @@ int estimate_refusals(mdrp_handle *h, int kind, const double *d1, const double *
 int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
                     int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
                     const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr,
-                    const uint64_t *budgets = nullptr, int n_budgets = 0, const Model *priors = nullptr /*[batch] in device memory*/) {
+                    const uint64_t *budgets = nullptr, int n_budgets = 0, const Model *priors = nullptr /*[batch] in device memory*/,
+                    const uint64_t *prosac = nullptr /*ranked call: max_prosac_iterations*/) {
     if (int rc = estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, ro, bo)) return rc;
     if (priors && (host || budgets || kind > MDRP_VARYING_FOCAL)) { g_err = "priors: device-resident monodepth calls without budgets only"; return MDRP_ERR_INVALID; }
+    if (prosac && (host || budgets || priors || kind > MDRP_VARYING_FOCAL)) { g_err = "ranked: device-resident monodepth calls without budgets or priors only"; return MDRP_ERR_INVALID; }
     h->last_budgets = n_budgets;
     if (h->fuse_disabled && --h->fuse_retry_in <= 0) h->fuse_disabled = false; // once per API call (not per pass): the handle tries the fused tail again
     h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
@@ -1056,7 +1093,7 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
         const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + o1, batch};
         const PassIn in{kind, x1 + o2, x2 + o2, d1 ? d1 + o1 : nullptr, d2 ? d2 + o1 : nullptr, nb, n_max, n_host.data() + p0, cam1 ? cam1 + p0 : nullptr,
                         cam2 ? cam2 + p0 : nullptr, ro, bo, chunk_cap, mask + o1, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch,
-                        budgets ? &bud : nullptr, priors ? priors + p0 : nullptr};
+                        budgets ? &bud : nullptr, priors ? priors + p0 : nullptr, prosac};
         if ((rc = run_pass(h, in))) return rc;
     }
     if (budgets) {
@@ -2274,6 +2311,181 @@ int mdrp_refine_models(mdrp_handle *h, int kind, mdrp_model *models, int count, 
     HIPCHK(hipMemcpyAsync(models, h->unit_e.p, sizeof(Model) * count, hipMemcpyDeviceToHost, s));
     if (final_cost) HIPCHK(hipMemcpyAsync(final_cost, h->unit_a.p, sizeof(double) * count, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return MDRP_OK;
+}
+
+} // extern "C"
+
+// ---- estimate in match-score order (include/mdrp.h; mdrp_prosac.h)
+// what the ranked entry points refuse before any device work: check_prior_args' list without the prior, with the estimator's own refusals taken on
+// the options as the estimator will see them (progressive_sampling is what these entry points build: it is not handed on)
+static int check_ranked_args(mdrp_handle *h, int kind, const double *d1, const double *d2, int batch, int n_max, const int32_t *n_per_pair,
+                             const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo) {
+    const char *why = nullptr;
+    if (!h || !ro || !bo) why = "invalid argument";
+    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "ranked: only the monodepth estimators (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL)";
+    else if (batch < 0 || n_max < 0) why = "ranked: a negative size";
+    for (int i = 0; !why && n_per_pair && i < batch; ++i)
+        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    mdrp_ransac_opt plain = *ro;
+    plain.progressive_sampling = 0;
+    return estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, &plain, bo);
+}
+
+// n per pair on the device for the ranking kernels (pr_nper), and scores -> order (pr_order, or `order_dev`) on the handle's stream
+static int rank_device(mdrp_handle *h, const double *scores_dev, int batch, int n_max, const int32_t *n_per_pair, int32_t *order_dev) {
+    hipStream_t s = h->stream;
+    std::vector<int32_t> n_host(batch);
+    for (int i = 0; i < batch; ++i) n_host[i] = n_per_pair ? n_per_pair[i] : n_max;
+    if (int rc = h->pr_nper.ensure(sizeof(int32_t) * (size_t)batch)) return rc;
+    HIPCHK(hipMemcpyAsync(h->pr_nper.p, n_host.data(), sizeof(int32_t) * (size_t)batch, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_rank, dim3(batch), dim3(RANK_THREADS), 0, s, scores_dev, (const int32_t *)h->pr_nper.as<int32_t>(), n_max, order_dev);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+// All pointers device memory; scores_dev null: the records are in quality order already.  Ranks, gathers into the handle's ordered copies (allocated
+// before estimate_device takes the pass budget from the free memory), runs the unchanged estimator with the progressive sampler on them, and
+// scatters the mask into the caller's order: mask_dev, or the handle's mask where that is null.
+static int ranked_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, const double *scores_dev, int batch,
+                         int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
+                         const mdrp_bundle_opt *bo, uint8_t *mask_dev) {
+    mdrp_ransac_opt plain = *ro;
+    plain.progressive_sampling = 0;
+    const uint64_t max_prosac = ro->max_prosac_iterations;
+    const size_t np = (size_t)batch * n_max;
+    if (!scores_dev || np == 0)
+        return estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, &plain, bo, mask_dev, nullptr, nullptr, 0, nullptr, &max_prosac);
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = h->pr_x1.ensure(sizeof(double) * 2 * np)) || (rc = h->pr_x2.ensure(sizeof(double) * 2 * np)) || (rc = h->pr_d1.ensure(sizeof(double) * np)) ||
+        (rc = h->pr_d2.ensure(sizeof(double) * np)) || (rc = h->pr_order.ensure(sizeof(int32_t) * np)) || (rc = h->pr_mask.ensure(np)))
+        return rc;
+    uint8_t *mask = mask_dev;
+    if (!mask) {
+        if ((rc = h->mask.ensure(np))) return rc;
+        mask = h->mask.as<uint8_t>();
+    }
+    int32_t *order = h->pr_order.as<int32_t>();
+    if ((rc = rank_device(h, scores_dev, batch, n_max, n_per_pair, order))) return rc;
+    const dim3 rgrid((unsigned)batch, (unsigned)((n_max + 255) / 256));
+    const int32_t *nper = h->pr_nper.as<int32_t>();
+    hipLaunchKernelGGL(k_rank_gather, rgrid, dim3(256), 0, s, (const int32_t *)order, nper, n_max, x1, x2, d1, d2, h->pr_x1.as<double>(), h->pr_x2.as<double>(),
+                       h->pr_d1.as<double>(), h->pr_d2.as<double>());
+    HIPCHK(hipGetLastError());
+    if ((rc = estimate_device(h, kind, h->pr_x1.as<double>(), h->pr_x2.as<double>(), h->pr_d1.as<double>(), h->pr_d2.as<double>(), batch, n_max, n_per_pair,
+                              cam1, cam2, &plain, bo, h->pr_mask.as<uint8_t>(), nullptr, nullptr, 0, nullptr, &max_prosac)))
+        return rc;
+    hipLaunchKernelGGL(k_rank_scatter, rgrid, dim3(256), 0, s, (const int32_t *)order, nper, n_max, (const uint8_t *)h->pr_mask.as<uint8_t>(), mask);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+extern "C" {
+
+int mdrp_estimate_batch_ranked_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, const double *scores_dev,
+                                     int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                     const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
+    if (int rc = check_ranked_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
+    MDRP_ENTER(h);
+    const int rc = ranked_device(h, kind, x1, x2, d1, d2, scores_dev, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+// The blocking form.  Host buffers are copied in plainly on the handle's stream (as mdrp_estimate_batch_prior does): no sliced front.
+int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
+                               const double *scores, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                               const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
+    if (int rc = check_ranked_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
+    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) { g_err = "monodepth estimator needs correspondences and depths"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    const size_t np = (size_t)batch * n_max;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
+    hipStream_t s = h->stream;
+    int rc;
+    if (use_host && np > 0) {
+        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
+            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)) ||
+            (scores && (rc = h->pr_scores.ensure(sizeof(double) * np))))
+            return rc;
+        HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
+        if (scores) { HIPCHK(hipMemcpyAsync(h->pr_scores.p, scores, sizeof(double) * np, hipMemcpyHostToDevice, s)); scores = h->pr_scores.as<double>(); }
+        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>(); d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
+    }
+    rc = ranked_device(h, kind, x1, x2, d1, d2, scores, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask);
+    if (rc) return drain_and_return(h, rc);
+    if (use_host && inlier_mask && np > 0 && hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s) != hipSuccess) {
+        g_err = "copy of the inlier masks failed";
+        return drain_and_return(h, MDRP_ERR_HIP);
+    }
+    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+// k_rank alone: order [batch][n_max] int32 in mem_space (-1 at and past n).  Synchronous.
+int mdrp_rank_scores(mdrp_handle *h, int mem_space, const double *scores, int batch, int n_max, const int32_t *n_per_pair, int32_t *order) {
+    const char *why = nullptr;
+    if (!h || batch < 0 || n_max < 0 || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) why = "invalid argument";
+    else if ((size_t)batch * n_max > 0 && (!scores || !order)) why = "rank_scores: scores or order is NULL";
+    for (int i = 0; !why && n_per_pair && i < batch; ++i)
+        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    const size_t np = (size_t)batch * n_max;
+    if (np == 0) return MDRP_OK;
+    MDRP_ENTER(h);
+    hipStream_t s = h->stream;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
+    int rc;
+    int32_t *order_dev = order;
+    if (use_host) {
+        if ((rc = h->pr_scores.ensure(sizeof(double) * np)) || (rc = h->pr_order.ensure(sizeof(int32_t) * np))) return rc;
+        HIPCHK(hipMemcpyAsync(h->pr_scores.p, scores, sizeof(double) * np, hipMemcpyHostToDevice, s));
+        scores = h->pr_scores.as<double>(); order_dev = h->pr_order.as<int32_t>();
+    }
+    if ((rc = rank_device(h, scores, batch, n_max, n_per_pair, order_dev))) return drain_and_return(h, rc);
+    if (use_host) HIPCHK(hipMemcpyAsync(order, order_dev, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MDRP_OK;
+}
+
+// The progressive sampler alone, for one table of n records: chunk by chunk through the launch the scheduler uses (launch_samples_prosac), the
+// (RNG state, sample index) carried on the device from chunk to chunk.  out: [sum of chunk_lens][3] uint32 in host memory; n < 3 writes nothing.
+int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks, uint32_t *out) {
+    const char *why = nullptr;
+    long long total = 0, longest = 0;
+    if (!h || n < 0 || n_chunks < 0 || (n_chunks > 0 && (!chunk_lens || !out))) why = "invalid argument";
+    for (int c = 0; !why && c < n_chunks; ++c) {
+        if (chunk_lens[c] < 1) why = "prosac_samples: a chunk length < 1";
+        else { total += chunk_lens[c]; longest = std::max<long long>(longest, chunk_lens[c]); }
+    }
+    if (!why && total > (1 << 24)) why = "prosac_samples: more than 2^24 samples";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    if (n < 3 || n_chunks == 0) return MDRP_OK;
+    MDRP_ENTER(h);
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = h->params.ensure(16)) || (rc = h->samples[0].ensure(sizeof(uint32_t) * 3 * (size_t)longest))) return rc;
+    uint64_t *d_state = h->params.as<uint64_t>();
+    int32_t *d_n = reinterpret_cast<int32_t *>(d_state + 1);
+    const int32_t n32 = n;
+    HIPCHK(hipMemcpyAsync(d_state, &seed, sizeof seed, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_n, &n32, sizeof n32, hipMemcpyHostToDevice, s));
+    ProsacTab tab{nullptr, nullptr, nullptr};
+    if ((rc = prosac_tables(h, s, &n32, 1, max_prosac_iterations, (uint64_t)total, tab))) return drain_and_return(h, rc);
+    const int threads = env_int("MDRP_SAMPLE_THREADS", SAMP_THREADS);
+    size_t done = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+        launch_samples_prosac(s, threads, 1, d_n, d_state, tab, max_prosac_iterations, chunk_lens[c], h->samples[0].as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + 3 * done, h->samples[0].p, sizeof(uint32_t) * 3 * (size_t)chunk_lens[c], hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s)); // (pageable destination: the next chunk overwrites the table)
+        done += (size_t)chunk_lens[c];
+    }
     return MDRP_OK;
 }
 

@@ -241,6 +241,47 @@ def _no_budgets_with_priors(priors, budgets):
         raise ValueError("priors and budgets do not combine: run the budgets without priors, or one call per budget")
 
 
+# scores=... on a monodepth *_batch entry point, on the single-pair forms and on estimate_batch_torch: the estimate in match-score order with the
+# reference's progressive sampler (PROSAC; include/mdrp.h mdrp_estimate_batch_ranked).  One score per correspondence, higher is better
+# (a matcher's confidence), or the string "presorted" for records that are in quality order already.  progressive_sampling in ransac_opt may be
+# absent, False or True: scores= is what asks for the sampler; max_prosac_iterations is read.  Masks and info["inliers"] stay in the caller's order.
+# Not with budgets or priors.
+PRESORTED = "presorted"
+
+
+def _no_scores_with(scores, budgets, priors):
+    if scores is not None and (budgets is not None or priors is not None):
+        raise ValueError("scores do not combine with budgets or priors: rank without them, or run them without scores")
+
+
+def _score_rows(scores, ns, N):
+    """scores of a host batch -> (B, N) float64 padded with -inf, or None for "presorted"; checked against the pairs' sizes"""
+    if isinstance(scores, str):
+        if scores != PRESORTED:
+            raise ValueError(f'scores: the only string is "{PRESORTED}", not {scores!r}')
+        return None
+    B = len(ns)
+    if isinstance(scores, np.ndarray) and scores.ndim == 2:
+        rows = [scores[i] for i in range(scores.shape[0])]
+    else:
+        rows = [np.asarray(r).reshape(-1) for r in scores]
+    if len(rows) != B:
+        raise ValueError(f"scores: expected {B} rows, got {len(rows)}")
+    out = np.full((B, N), -np.inf)
+    for i, r in enumerate(rows):
+        if len(r) != ns[i] and len(r) != N:
+            raise ValueError(f"scores: pair {i} has {ns[i]} correspondences and {len(r)} scores")
+        out[i, :ns[i]] = np.asarray(r, dtype=np.float64)[:ns[i]]
+    return out
+
+
+def _ranked_host(kind, x1, x2, d1, d2, ns, scores, cams1, cams2, ransac_opt, bundle_opt, device):
+    """(records, masks) of a host batch in score order: one blocking call on the device's default handle"""
+    rows = _score_rows(scores, ns, x1.shape[1])  # (checked before anything touches the device)
+    return _capi.default_handle(device).estimate_batch_ranked(kind, x1, x2, d1, d2, rows, _capi.ransac_opt_from_dict(ransac_opt),
+                                                              _capi.bundle_opt_from_dict(bundle_opt), ns, cams1, cams2)
+
+
 def _prior_host(kind, x1, x2, d1, d2, ns, priors, cams1, cams2, ransac_opt, bundle_opt, device):
     """(records, masks) of a host batch with priors: one blocking call on the device's default handle"""
     rec = _prior_records(priors, kind, len(ns))  # (checked before anything touches the device)
@@ -266,14 +307,16 @@ def _stack(points1, points2, depth1, depth2):
 
 
 def estimate_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, cameras1, cameras2, ransac_opt=None,
-                                           bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None):
+                                           bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None, scores=None):
     """B calibrated pairs at once.  cameras1/2: one Camera|dict for all pairs, or a list of B.  Returns
     (list[MonoDepthTwoViewGeometry], list[info dict]) — or, with as_arrays=True, (records, inlier masks, n_per_pair) as numpy arrays
     (_capi.RESULT_DTYPE; (B, N) uint8): building B Python objects and B lists of N bools costs more than the estimate itself beyond
     a few thousand pairs.  A host batch is ONE call whatever its size: the C side copies the correspondences in 256-pair slices on a copy stream
     beside the first kernels of the slices before them (MDRP_PIPELINE_MIN=<pairs> brings back the chunked two-in-flight path of rounds 4-5,
     mdrp_amd.pipeline; results identical to sequential chunk calls).  budgets: see _budget_args above.  priors: a list of B
-    MonoDepthTwoViewGeometry | None (or a MODEL_DTYPE array) each pair's search starts from, see _prior_records above."""
+    MonoDepthTwoViewGeometry | None (or a MODEL_DTYPE array) each pair's search starts from, see _prior_records above.  scores: one score per
+    correspondence (a (B, N) array or a list of B arrays) or "presorted": the estimate in score order with the progressive sampler, see PRESORTED above."""
+    _no_scores_with(scores, budgets, priors)
     _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     x1, x2, d1, d2, ns = _stack(points2D_1, points2D_2, depth_1, depth_2)
@@ -282,7 +325,9 @@ def estimate_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, dept
     def cams(c):
         return _camera_records(c, B)
 
-    if priors is not None:
+    if scores is not None:
+        res, mask = _ranked_host(_capi.CALIB, x1, x2, d1, d2, ns, scores, cams(cameras1), cams(cameras2), ransac_opt, bundle_opt, device)
+    elif priors is not None:
         res, mask = _prior_host(_capi.CALIB, x1, x2, d1, d2, ns, priors, cams(cameras1), cams(cameras2), ransac_opt, bundle_opt, device)
     else:
         res, mask = pipeline.estimate_host(_capi.CALIB, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt),
@@ -292,11 +337,14 @@ def estimate_monodepth_relative_pose_batch(points2D_1, points2D_2, depth_1, dept
     return _per_budget(budgets, res, mask, lambda r, m: ([_geometry_from_model(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(B)]))
 
 
-def _focal_batch(kind, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays=False, budgets=None, priors=None):
+def _focal_batch(kind, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays=False, budgets=None, priors=None, scores=None):
+    _no_scores_with(scores, budgets, priors)
     _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     x1, x2, d1, d2, ns = _stack(points2D_1, points2D_2, depth_1, depth_2)
-    if priors is not None:
+    if scores is not None:
+        res, mask = _ranked_host(kind, x1, x2, d1, d2, ns, scores, None, None, ransac_opt, bundle_opt, device)
+    elif priors is not None:
         res, mask = _prior_host(kind, x1, x2, d1, d2, ns, priors, None, None, ransac_opt, bundle_opt, device)
     else:
         res, mask = pipeline.estimate_host(kind, x1, x2, d1, d2, _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), ns, None, None,
@@ -307,45 +355,50 @@ def _focal_batch(kind, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bun
 
 
 def estimate_monodepth_shared_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, ransac_opt=None,
-                                                        bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None):
-    """priors: a list of B MonoDepthImagePair | None (focals: camera1 / camera2 .focal(), in pixels), see _prior_records"""
-    return _focal_batch(_capi.SHARED_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets, priors)
+                                                        bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None, scores=None):
+    """priors: a list of B MonoDepthImagePair | None (focals: camera1 / camera2 .focal(), in pixels), see _prior_records; scores: see PRESORTED"""
+    return _focal_batch(_capi.SHARED_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets, priors, scores)
 
 
 def estimate_monodepth_varying_focal_relative_pose_batch(points2D_1, points2D_2, depth_1, depth_2, ransac_opt=None,
-                                                         bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None):
-    return _focal_batch(_capi.VARYING_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets, priors)
+                                                         bundle_opt=None, device=0, as_arrays=False, budgets=None, priors=None, scores=None):
+    return _focal_batch(_capi.VARYING_FOCAL, points2D_1, points2D_2, depth_1, depth_2, ransac_opt, bundle_opt, device, as_arrays, budgets, priors, scores)
 
 
 # ------------------------------------------------------------------------------------------------ reference signatures
+def _one_scores(scores):
+    """scores= of a single-pair form (not in the reference): an array of one score per correspondence, or "presorted" -> the batch forms' argument"""
+    return scores if scores is None or isinstance(scores, str) else [np.asarray(scores).reshape(-1)]
+
+
 def estimate_monodepth_relative_pose(points2D_1, points2D_2, depth_1, depth_2, camera1, camera2, ransac_opt={},
-                                     bundle_opt={}, initial_pose=None, prior=None):
+                                     bundle_opt={}, initial_pose=None, prior=None, scores=None):
     """Pose estimation using depth estimates with non-linear refinement (_core.pyi:446-475).  prior (not in the reference): a
     MonoDepthTwoViewGeometry the search starts from (_prior_records); initial_pose keeps the reference's reset semantics."""
     g, i = estimate_monodepth_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1], [depth_2],
                                                   camera1, camera2, _with_initial(initial_pose, ransac_opt), bundle_opt,
-                                                  priors=None if prior is None else [prior])
+                                                  priors=None if prior is None else [prior], scores=_one_scores(scores))
     return _initial_fallback(initial_pose, g[0]), i[0]
 
 
 def estimate_monodepth_shared_focal_relative_pose(points2D_1, points2D_2, depth_1, depth_2, ransac_opt={}, bundle_opt={},
-                                                  initial_image_pair=None, prior=None):
+                                                  initial_image_pair=None, prior=None, scores=None):
     """Unknown equal focal lengths; points principal-point-centred (_core.pyi:477-488, README.md:88-90).  prior: a MonoDepthImagePair the
     search starts from (_prior_records)."""
     p, i = estimate_monodepth_shared_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1],
                                                                [depth_2], _with_initial(initial_image_pair, ransac_opt), bundle_opt,
-                                                               priors=None if prior is None else [prior])
+                                                               priors=None if prior is None else [prior], scores=_one_scores(scores))
     _initial_fallback(initial_image_pair, p[0].geometry)
     return p[0], i[0]
 
 
 def estimate_monodepth_varying_focal_relative_pose(points2D_1, points2D_2, depth_1, depth_2, ransac_opt={}, bundle_opt={},
-                                                   initial_image_pair=None, prior=None):
+                                                   initial_image_pair=None, prior=None, scores=None):
     """Two unknown focal lengths (_core.pyi:490-501, README.md:94-96).  `monodepth_estimate_shift` is ignored here
     exactly like in the reference.  prior: a MonoDepthImagePair the search starts from (_prior_records)."""
     p, i = estimate_monodepth_varying_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], [depth_1],
                                                                 [depth_2], _with_initial(initial_image_pair, ransac_opt), bundle_opt,
-                                                                priors=None if prior is None else [prior])
+                                                                priors=None if prior is None else [prior], scores=_one_scores(scores))
     _initial_fallback(initial_image_pair, p[0].geometry)
     return p[0], i[0]
 
@@ -713,7 +766,7 @@ def _torch_handle(dev, stream_ptr):
 
 
 def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras1=None, cameras2=None, ransac_opt=None,
-                         bundle_opt=None, n_per_pair=None, budgets=None, priors=None):
+                         bundle_opt=None, n_per_pair=None, budgets=None, priors=None, scores=None):
     """Batch that already lives on the GPU (e.g. matcher output): `points2D_*` (B, N, 2) and `depth_*` (B, N) float64 torch
     tensors on a ROCm device; the work is queued on that device's CURRENT torch stream — including torch's default
     (null) stream — so it is ordered after whatever produced the inputs there and before later consumers of the mask;
@@ -723,7 +776,10 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
     (sequence, numpy array or tensor on any device).  budgets (see _budget_args): records (C, B) and a (C, B, N) mask tensor.
     priors (see _prior_records; not with budgets): one model per pair the search starts from — a device tensor holding B records of 96 bytes
     (uint8 (B, 96), or float64 (B, 12): q t scale shift1 shift2 f1 f2, a NaN q[0] for a pair without one), or a numpy array of _capi.MODEL_DTYPE,
-    which is uploaded on the stream."""
+    which is uploaded on the stream.  scores (see PRESORTED; not with budgets or priors): a (B, N) float32 / float64 tensor on the inputs' device, one
+    score per correspondence, higher is better, or "presorted": the estimate in score order with the progressive sampler; the mask stays in the
+    caller's order."""
+    _no_scores_with(scores, budgets, priors)
     _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     import torch
@@ -734,6 +790,11 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
             raise ValueError("priors must be a uint8 / float64 tensor on the inputs' device or a numpy array of _capi.MODEL_DTYPE")
         elif priors.numel() * priors.element_size() != int(depth_1.shape[0]) * _capi.MODEL_DTYPE.itemsize:
             raise ValueError(f"priors must hold {int(depth_1.shape[0])} records of {_capi.MODEL_DTYPE.itemsize} bytes")
+    if scores is not None and not (isinstance(scores, str) and scores == PRESORTED):  # (checked before anything touches the device)
+        if not (isinstance(scores, torch.Tensor) and scores.dtype in (torch.float32, torch.float64)):
+            raise ValueError('scores must be a float32 / float64 tensor on the inputs\' device or "presorted"')
+        if tuple(scores.shape) != tuple(depth_1.shape):
+            raise ValueError(f"scores must be {tuple(depth_1.shape)}, one per correspondence, not {tuple(scores.shape)}")
     kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
     k = kinds[kind] if isinstance(kind, str) else int(kind)
     x1, x2, d1, d2 = (t.contiguous() for t in (points2D_1, points2D_2, depth_1, depth_2))
@@ -761,7 +822,16 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
                                             mask.data_ptr())
             return h.fetch_budget_results(len(budgets), B), mask
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
-        if priors is not None:
+        if scores is not None:
+            sc = None
+            if not isinstance(scores, str):
+                if not (scores.is_cuda and scores.device == x1.device):
+                    raise ValueError("scores must live on the inputs' device")
+                sc = scores.to(torch.float64).contiguous()  # (float32 -> float64 is exact: the order is the caller's)
+            h.estimate_batch_ranked_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), None if sc is None else sc.data_ptr(), B, N,
+                                           _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), n_per_pair, cams1, cams2,
+                                           mask.data_ptr())
+        elif priors is not None:
             if isinstance(priors, np.ndarray):
                 priors = torch.from_numpy(priors.view(np.uint8).copy()).to(x1.device)
             if not (priors.is_cuda and priors.device == x1.device):
