@@ -550,7 +550,7 @@ int mdrp_estimate_batch_prior_async(mdrp_handle *h, int kind, const double *x1_d
  *     stopping, closing LO, get_inliers, the inlier-only refinement, the record.  inlier_mask[order[r]] = mask of rank r: the mask is in the
  *     caller's order; bytes at or past n are 0.
  * These entry points are what progressive_sampling selects in the reference, so they sample progressively whether ropt->progressive_sampling is 0
- * or 1 (a reference caller's options pass unabridged); every other entry point still refuses the switch.  kind: MDRP_CALIB, MDRP_SHARED_FOCAL or
+ * or 1 (a reference caller's options pass unabridged); every other entry point but the ranked front end (below) still refuses the switch.  kind: MDRP_CALIB, MDRP_SHARED_FOCAL or
  * MDRP_VARYING_FOCAL; any other kind is MDRP_ERR_INVALID, as is everything mdrp_estimate_batch refuses (NULL depths, n_per_pair out of range, ...).
  * A refusal leaves the handle usable.  x1, x2, d1, d2, scores ([B][n_max] doubles or NULL) and inlier_mask ([B][n_max] bytes or NULL) live in
  * mem_space; n_per_pair, cameras and out ([B]) in HOST memory.  Host buffers are copied in one piece on the handle's stream (no sliced front).
@@ -571,6 +571,39 @@ int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosa
                         uint32_t *out);
 /* Inspection: the ranking kernel alone.  scores [B][n_max] doubles and order [B][n_max] int32 live in mem_space; order[b][r] = -1 for r >= n. */
 int mdrp_rank_scores(mdrp_handle *h, int mem_space, const double *scores, int batch, int n_max, const int32_t *n_per_pair, int32_t *order);
+
+/* ---- The device front end with match scores: PROSAC from a matcher's confidences (added within ABI 0.6: new symbols only).
+ * mdrp_gather_matches / mdrp_gather_image_pairs and the two front-end estimates, with one score per MATCH ROW, higher is better:
+ * scores_dev is [B][m_max] in DEVICE memory, floats or doubles as score_type says (MDRP_F32 | MDRP_F64; float widens exactly).  For pair b:
+ *   - rules 1-4 of mdrp_matches, for mdrp_image_pairs behind the image-index rule, decide which rows are kept, exactly as without scores.  A row's
+ *     score plays no part in whether it is kept, and the score of a dropped row is never looked at.
+ *   - key(m) = (double)scores[b][m] with NaN (either sign) replaced by -inf; -0.0 and +0.0 tie.
+ *   - rank(m) = #{m' kept : key(m') > key(m), or key(m') == key(m) and m' < m}: the order of mdrp_estimate_batch_ranked on the kept rows' scores in
+ *     match order (a stable descending sort).
+ *   - slot[b][m] = rank(m) for a kept row, -1 for a dropped one; the record of row m (rule 5's x1, x2, d1, d2) is at index rank(m) of pair b's
+ *     buffers; n[b] = kept rows; slots >= n[b] hold the filler (x = 0, d = 1).
+ * The estimates then run exactly what mdrp_estimate_batch_ranked_async runs with scores == NULL (records in quality order already) on those buffers
+ * with n_max = m_max and n_per_pair = the counts: the progressive sampler, whether ropt->progressive_sampling is 0 or 1; max_prosac_iterations <= 1
+ * is the uniform sampler on the ordered records.  That is, bit for bit, mdrp_estimate_batch_ranked on the unranked gather with the kept rows' scores.
+ * match_mask_dev[b][m] = 1 iff row m was kept and its correspondence is an inlier; n_used_host: the counts.  Each kept row is written once, at its
+ * rank: no order buffer, no ordered copy, no scatter of the mask.  The handle holds one 8-byte key per match row for the call.
+ * scores_dev == NULL: the match rows are in quality order already — the unranked gather (score_type is not read), followed in the estimates by the
+ * progressive sampler.
+ * MDRP_ERR_INVALID, before any device work: everything mdrp_gather_matches / mdrp_gather_image_pairs / the front-end estimates refuse (descriptor,
+ * kind), a score_type other than MDRP_F32 / MDRP_F64 with scores_dev != NULL, and the estimator's own refusals taken with progressive_sampling
+ * cleared (cameras for MDRP_CALIB; MDRP_ERR_UNSUPPORTED for an option that is not built).  A refusal leaves the handle usable; an error behind the
+ * first device work returns after the handle's streams have drained.  Same stream behaviour as the unranked forms: one synchronisation (the
+ * counts).  Iteration budgets and priors do not combine with scores. */
+int mdrp_gather_matches_ranked(mdrp_handle *h, const mdrp_matches *mm, const void *scores_dev, int score_type, int batch, double *x1, double *x2,
+                               double *d1, double *d2, int32_t *slot, int32_t *n_host);
+int mdrp_estimate_matches_ranked_async(mdrp_handle *h, int kind, const mdrp_matches *mm, const void *scores_dev, int score_type, int batch,
+                                       const mdrp_camera *cam1_host, const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt,
+                                       const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host);
+int mdrp_gather_image_pairs_ranked(mdrp_handle *h, const mdrp_image_pairs *ip, const void *scores_dev, int score_type, int batch, double *x1,
+                                   double *x2, double *d1, double *d2, int32_t *slot, int32_t *n_host);
+int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_image_pairs *ip, const void *scores_dev, int score_type, int batch,
+                                           const mdrp_camera *cam1_host, const mdrp_camera *cam2_host, const mdrp_ransac_opt *ropt,
+                                           const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@ EXPORTS = (
     "mdrp_estimate_batch_prior", "mdrp_estimate_batch_prior_async",
     "mdrp_retire_models", "mdrp_replay_slots",
     "mdrp_estimate_batch_ranked", "mdrp_estimate_batch_ranked_async", "mdrp_prosac_samples", "mdrp_rank_scores",
+    "mdrp_gather_matches_ranked", "mdrp_estimate_matches_ranked_async", "mdrp_gather_image_pairs_ranked", "mdrp_estimate_image_pairs_ranked_async",
 )
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
@@ -186,6 +187,13 @@ def load_library():
                                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
             lib.mdrp_prosac_samples.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint64, ip, C.c_int, vp]
             lib.mdrp_rank_scores.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, ip, vp]
+        if hasattr(lib, "mdrp_gather_matches_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked front end: Handle._ranked_front_end_fn raises)
+            lib.mdrp_gather_matches_ranked.argtypes = [vp, C.POINTER(Matches), vp, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
+            lib.mdrp_estimate_matches_ranked_async.argtypes = [vp, C.c_int, C.POINTER(Matches), vp, C.c_int, C.c_int, vp, vp, C.POINTER(RansacOpt),
+                                                               C.POINTER(BundleOpt), vp, ip]
+            lib.mdrp_gather_image_pairs_ranked.argtypes = [vp, C.POINTER(ImagePairs), vp, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
+            lib.mdrp_estimate_image_pairs_ranked_async.argtypes = [vp, C.c_int, C.POINTER(ImagePairs), vp, C.c_int, C.c_int, vp, vp, C.POINTER(RansacOpt),
+                                                                   C.POINTER(BundleOpt), vp, ip]
         if hasattr(lib, "mdrp_estimate_batch_prior"):  # (an older ABI-0.6 library through MDRP_LIB has no prior entry points: Handle._prior_fn raises)
             lib.mdrp_estimate_batch_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
@@ -668,6 +676,48 @@ class Handle:
         _check(self._lib, self._image_pairs_fn("mdrp_estimate_image_pairs_async")(self._h, int(kind), C.byref(ip), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt),
                                                                                   C.byref(bopt), C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
         return n
+
+    # ---- the front end with match scores (include/mdrp.h: mdrp_gather_matches_ranked ...): scores_ptr is a device pointer to batch x m_max scores of
+    # score_type (F32 | F64), or None / 0 for match rows that are in quality order already.  Arguments go to the library as they are: the library checks them.
+    def _ranked_front_end_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the ranked front end (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    def _gather_ranked(self, name, desc, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
+        n = np.zeros(int(batch), dtype=np.int32)
+        _check(self._lib, self._ranked_front_end_fn(name)(self._h, C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type), int(batch),
+                                                           C.c_void_p(x1_ptr), C.c_void_p(x2_ptr), C.c_void_p(d1_ptr), C.c_void_p(d2_ptr), C.c_void_p(slot_ptr),
+                                                           _ptr(n)))
+        return n
+
+    def _estimate_ranked(self, name, kind, desc, scores_ptr, score_type, batch, ropt, bopt, cam1, cam2, match_mask_ptr):
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        n = np.zeros(int(batch), dtype=np.int32)
+        _check(self._lib, self._ranked_front_end_fn(name)(self._h, int(kind), C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type),
+                                                           int(batch), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                           C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
+        return n
+
+    def gather_matches_ranked(self, mm, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
+        """k_gather_ranked alone into the caller's device buffers: the kept rows at their ranks; returns the kept rows per pair (numpy int32).
+        Synchronises the stream once."""
+        return self._gather_ranked("mdrp_gather_matches_ranked", mm, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr)
+
+    def estimate_matches_ranked_device(self, kind, mm, scores_ptr, score_type, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
+        """ranked front end + estimator with the progressive sampler on the handle's stream; results stay on the device (fetch_results /
+        copy_results_device).  Returns the kept rows per pair (numpy int32)."""
+        return self._estimate_ranked("mdrp_estimate_matches_ranked_async", kind, mm, scores_ptr, score_type, batch, ropt, bopt, cam1, cam2, match_mask_ptr)
+
+    def gather_image_pairs_ranked(self, ip, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
+        """gather_matches_ranked on per-image tables (k_gather_images_ranked)"""
+        return self._gather_ranked("mdrp_gather_image_pairs_ranked", ip, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr)
+
+    def estimate_image_pairs_ranked_device(self, kind, ip, scores_ptr, score_type, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
+        """estimate_matches_ranked_device on per-image tables; cam1 / cam2 are per PAIR"""
+        return self._estimate_ranked("mdrp_estimate_image_pairs_ranked_async", kind, ip, scores_ptr, score_type, batch, ropt, bopt, cam1, cam2, match_mask_ptr)
 
     def fetch_results(self, batch):
         out = np.zeros(batch, dtype=RESULT_DTYPE)

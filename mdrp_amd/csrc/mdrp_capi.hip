@@ -184,6 +184,7 @@ struct mdrp_handle {
     // ranked calls (mdrp_estimate_batch_ranked): the correspondences in score order | order [batch][n_max] int32 | the mask in that order |
     // scores and n per pair when they come from host memory | per pass: sample index per table (u64) | schedule offsets (u64, tables + 1) | subset sizes (u32)
     DevBuf pr_x1, pr_x2, pr_d1, pr_d2, pr_order, pr_mask, pr_scores, pr_nper, pr_tab;
+    DevBuf fe_key;                     // ranked front end (k_gather_ranked): the key of every match row, [batch][m_max] uint64
     DevBuf fe_x1, fe_x2, fe_d1, fe_d2, fe_slot, fe_n; // device front end (mdrp_estimate_matches_async): gathered correspondences | slot of every match row | kept rows per pair
     Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
     size_t fe_n_host_cap = 0;
@@ -1618,9 +1619,27 @@ static int check_matches(const mdrp_matches *mm, int batch) {
     return MDRP_OK;
 }
 
-// k_gather on the handle's stream (the descriptor has passed check_matches); n_dev: [batch] on the device
-static int gather_device(mdrp_handle *h, const mdrp_matches *mm, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot, int32_t *n_dev) {
+// the ranked front end's key scratch (one key per match row), a buffer of the handle
+static int ensure_key_scratch(mdrp_handle *h, int batch, int m_max) { return h->fe_key.ensure(sizeof(uint64_t) * (size_t)batch * m_max + 16); }
+
+// k_gather on the handle's stream (the descriptor has passed check_matches); n_dev: [batch] on the device.  With scores ([batch][m_max] of
+// score_type, device memory): k_gather_ranked, the kept rows at their ranks; the handle's key scratch has been sized (ensure_key_scratch).
+static int gather_device(mdrp_handle *h, const mdrp_matches *mm, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot, int32_t *n_dev,
+                         const void *scores = nullptr, int score_type = MDRP_F64) {
     if (batch == 0) return MDRP_OK;
+    if (scores) {
+#define MDRP_GATHER(KT, DT)                                                                                                                       \
+    hipLaunchKernelGGL((k_gather_ranked<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)mm->kp1, (const KT *)mm->kp2, mm->k1,  \
+                       mm->k2, mm->matches, mm->m_max, (const DT *)mm->depth1, (const DT *)mm->depth2, mm->h1, mm->w1, mm->h2, mm->w2,            \
+                       mm->center1, mm->center2, mm->filter, scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, d1, d2, slot, n_dev)
+        if (mm->kp_type == MDRP_F32 && mm->depth_type == MDRP_F32) MDRP_GATHER(float, float);
+        else if (mm->kp_type == MDRP_F32) MDRP_GATHER(float, double);
+        else if (mm->depth_type == MDRP_F32) MDRP_GATHER(double, float);
+        else MDRP_GATHER(double, double);
+#undef MDRP_GATHER
+        HIPCHK(hipGetLastError());
+        return MDRP_OK;
+    }
 #define MDRP_GATHER(KT, DT)                                                                                                                \
     hipLaunchKernelGGL((k_gather<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)mm->kp1, (const KT *)mm->kp2, mm->k1, mm->k2,  \
                        mm->matches, mm->m_max, (const DT *)mm->depth1, (const DT *)mm->depth2, mm->h1, mm->w1, mm->h2, mm->w2, mm->center1,      \
@@ -1650,10 +1669,23 @@ static int check_image_pairs(const mdrp_image_pairs *ip, int batch) {
 
 // k_gather_images on the handle's stream (the descriptor has passed check_image_pairs); n_dev: [batch] on the device
 static int gather_images_device(mdrp_handle *h, const mdrp_image_pairs *ip, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
-                                int32_t *n_dev) {
+                                int32_t *n_dev, const void *scores = nullptr, int score_type = MDRP_F64) {
     if (batch == 0) return MDRP_OK;
     if (ip->m_max == 0) { // no rows, and pairs may be NULL: the counts are all there is to write
         HIPCHK(hipMemsetAsync(n_dev, 0, sizeof(int32_t) * batch, h->stream));
+        return MDRP_OK;
+    }
+    if (scores) { // k_gather_images_ranked, as gather_device
+#define MDRP_GATHER(KT, DT)                                                                                                                           \
+    hipLaunchKernelGGL((k_gather_images_ranked<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)ip->kp, ip->kp_count, ip->k_max,    \
+                       (const DT *)ip->depth, ip->size, ip->h_max, ip->w_max, ip->center, ip->n_images, ip->pairs, ip->matches, ip->m_max, ip->filter, \
+                       scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, d1, d2, slot, n_dev)
+        if (ip->kp_type == MDRP_F32 && ip->depth_type == MDRP_F32) MDRP_GATHER(float, float);
+        else if (ip->kp_type == MDRP_F32) MDRP_GATHER(float, double);
+        else if (ip->depth_type == MDRP_F32) MDRP_GATHER(double, float);
+        else MDRP_GATHER(double, double);
+#undef MDRP_GATHER
+        HIPCHK(hipGetLastError());
         return MDRP_OK;
     }
 #define MDRP_GATHER(KT, DT)                                                                                                                \
@@ -1702,13 +1734,14 @@ static int ensure_gather_buffers(mdrp_handle *h, int batch, int m_max) {
 
 // behind a gather into the handle's buffers: the counts (one stream synchronisation), the resident estimator on the gathered buffers with the
 // handle's own inlier mask (by slot), then that mask back onto the match rows
+// (prosac: the gathered buffers are in quality order and the progressive sampler draws from them, as in a ranked call)
 static int estimate_gathered(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                             const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+                             const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host, const uint64_t *prosac = nullptr) {
     const size_t rows = (size_t)batch * m_max;
     int rc;
     if ((rc = fetch_counts(h, batch))) return rc;
     rc = estimate_device(h, kind, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(), batch, m_max,
-                         batch > 0 ? h->fe_n_host.v : nullptr, cam1, cam2, ropt, bopt, nullptr);
+                         batch > 0 ? h->fe_n_host.v : nullptr, cam1, cam2, ropt, bopt, nullptr, nullptr, nullptr, 0, nullptr, prosac);
     if (rc) return rc;
     if (match_mask_dev && rows > 0) {
         hipLaunchKernelGGL(k_match_mask, dim3((unsigned)((rows + FE_THREADS - 1) / FE_THREADS)), dim3(FE_THREADS), 0, h->stream, h->fe_slot.as<int32_t>(),
@@ -1775,6 +1808,103 @@ int mdrp_estimate_image_pairs_async(mdrp_handle *h, int kind, const mdrp_image_p
                                    h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>())))
         return rc;
     return estimate_gathered(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
+}
+
+} // extern "C"
+
+// ---- the front end with match scores (include/mdrp.h; k_gather_ranked, mdrp_frontend.h)
+static int check_score_type(const void *scores, int score_type) {
+    if (!scores || score_type == MDRP_F32 || score_type == MDRP_F64) return MDRP_OK;
+    g_err = "score_type must be MDRP_F32 or MDRP_F64";
+    return MDRP_ERR_INVALID;
+}
+
+// What the ranked front-end estimates refuse before any device work, behind the descriptor's own checks: the estimator's refusals on the options as
+// the estimator will see them (check_ranked_args' rule: progressive_sampling is what these entry points build, it is not handed on).  The depths are
+// buffers of the handle: `own` stands for them.
+static int check_ranked_front_end(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
+                                  const mdrp_bundle_opt *bo) {
+    static const double own = 0.0;
+    mdrp_ransac_opt plain = *ro;
+    plain.progressive_sampling = 0;
+    return estimate_refusals(h, kind, &own, &own, batch, m_max, cam1, cam2, &plain, bo);
+}
+
+// behind a gather into the handle's buffers in quality order: estimate_gathered with the progressive sampler
+static int estimate_gathered_ranked(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                    const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+    mdrp_ransac_opt plain = *ropt;
+    plain.progressive_sampling = 0;
+    const uint64_t max_prosac = ropt->max_prosac_iterations;
+    return estimate_gathered(h, kind, batch, m_max, cam1, cam2, &plain, bopt, match_mask_dev, n_used_host, &max_prosac);
+}
+
+extern "C" {
+
+int mdrp_gather_matches_ranked(mdrp_handle *h, const mdrp_matches *mm, const void *scores_dev, int score_type, int batch, double *x1, double *x2, double *d1,
+                               double *d2, int32_t *slot, int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_matches(mm, batch)) return rc;
+    if (int rc = check_score_type(scores_dev, score_type)) return rc;
+    if (batch > 0 && (!n_host || (mm->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_matches_ranked: NULL output"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))) || (scores_dev && (rc = ensure_key_scratch(h, batch, mm->m_max)))) return rc;
+    if ((rc = gather_device(h, mm, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>(), scores_dev, score_type))) return drain_and_return(h, rc);
+    if ((rc = fetch_counts(h, batch))) return drain_and_return(h, rc);
+    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
+    return MDRP_OK;
+}
+
+int mdrp_estimate_matches_ranked_async(mdrp_handle *h, int kind, const mdrp_matches *mm, const void *scores_dev, int score_type, int batch,
+                                       const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                       uint8_t *match_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_front_end_kind(kind, "mdrp_estimate_matches_ranked_async")) return rc;
+    if (int rc = check_matches(mm, batch)) return rc;
+    if (int rc = check_score_type(scores_dev, score_type)) return rc;
+    if (int rc = check_ranked_front_end(h, kind, batch, mm->m_max, cam1, cam2, ropt, bopt)) return rc;
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = ensure_gather_buffers(h, batch, mm->m_max)) || (scores_dev && (rc = ensure_key_scratch(h, batch, mm->m_max)))) return rc;
+    if ((rc = gather_device(h, mm, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
+                            h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>(), scores_dev, score_type)))
+        return drain_and_return(h, rc);
+    rc = estimate_gathered_ranked(h, kind, batch, mm->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_gather_image_pairs_ranked(mdrp_handle *h, const mdrp_image_pairs *ip, const void *scores_dev, int score_type, int batch, double *x1, double *x2,
+                                   double *d1, double *d2, int32_t *slot, int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_image_pairs(ip, batch)) return rc;
+    if (int rc = check_score_type(scores_dev, score_type)) return rc;
+    if (batch > 0 && (!n_host || (ip->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_image_pairs_ranked: NULL output"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))) || (scores_dev && (rc = ensure_key_scratch(h, batch, ip->m_max)))) return rc;
+    if ((rc = gather_images_device(h, ip, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>(), scores_dev, score_type))) return drain_and_return(h, rc);
+    if ((rc = fetch_counts(h, batch))) return drain_and_return(h, rc);
+    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
+    return MDRP_OK;
+}
+
+int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_image_pairs *ip, const void *scores_dev, int score_type, int batch,
+                                           const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                           uint8_t *match_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_front_end_kind(kind, "mdrp_estimate_image_pairs_ranked_async")) return rc;
+    if (int rc = check_image_pairs(ip, batch)) return rc;
+    if (int rc = check_score_type(scores_dev, score_type)) return rc;
+    if (int rc = check_ranked_front_end(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt)) return rc;
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = ensure_gather_buffers(h, batch, ip->m_max)) || (scores_dev && (rc = ensure_key_scratch(h, batch, ip->m_max)))) return rc;
+    if ((rc = gather_images_device(h, ip, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
+                                   h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>(), scores_dev, score_type)))
+        return drain_and_return(h, rc);
+    rc = estimate_gathered_ranked(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
+    return rc ? drain_and_return(h, rc) : rc;
 }
 
 } // extern "C"

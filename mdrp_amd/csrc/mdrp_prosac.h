@@ -5,7 +5,8 @@
 // sample max_prosac_iterations on it is the uniform draw of K from n.  The sequence is a pure function of (seed, n, max_prosac_iterations), and
 // the subset size of a sample does not depend on the RNG at all: the host builds one schedule per distinct n (subset_schedule below) and
 // k_samples_prosac reads it.  Everything else of a ranked call is the unchanged estimator, run on the records in descending score order:
-//   k_rank              scores -> order (one workgroup per pair, rank by counting, scores tiled through LDS: one path for every n)
+//   k_rank              scores -> order (one workgroup per pair, rank by counting, scores tiled through LDS: one path for every n; rank_key and
+//                       rank_count are shared with the ranked front end, k_gather_ranked / k_gather_images_ranked of mdrp_frontend.h)
 //   k_rank_gather       x1, x2, d1, d2 -> handle-owned copies in that order, in front of the unchanged estimate_device
 //   k_samples_prosac    the wave-speculative sampler (samples_block, mdrp_kernels.h) with a variable number of raw draws per sample
 //   k_rank_scatter      the inlier mask back into the caller's order, behind the run
@@ -63,6 +64,28 @@ inline std::vector<uint32_t> subset_schedule(uint64_t n, uint64_t max_prosac_ite
     }
     return sub_of;
 }
+
+// ------------------------------------------------------------------------------------------------ ranking key
+#if defined(__HIPCC__)
+#define MDRP_PROSAC_HD __host__ __device__ __forceinline__
+#else
+#define MDRP_PROSAC_HD inline
+#endif
+
+// The key of a score as an unsigned integer that orders like the definition: NaN -> -inf, -0.0 -> +0.0, then the usual monotone map of the
+// IEEE bits (negative: all bits flipped; otherwise: the sign bit set).  Larger key = better score.  The smallest key is that of -inf,
+// 0x000fffffffffffff: 0 is below every key (the ranked front end, mdrp_frontend.h, gives it to the rows it drops).  Host and device
+// (tests/hostmath/rank_key_host.cpp pins it on the CPU); the bits are taken through a union, as mdrp_frontend.h takes them.
+MDRP_PROSAC_HD uint64_t rank_key(double s) {
+    union { double f; uint64_t u; } v;
+    v.f = s;
+    uint64_t b = v.u;
+    const uint64_t mag = b & 0x7fffffffffffffffULL;
+    if (mag > 0x7ff0000000000000ULL) b = 0xfff0000000000000ULL; // NaN (either sign, any payload) -> -inf
+    else if (mag == 0) b = 0;                                    // -0.0 -> +0.0
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
+}
+constexpr uint64_t RANK_KEY_DROPPED = 0; // below rank_key(-inf)
 
 } // namespace prosac
 } // namespace mdrp
@@ -136,17 +159,28 @@ MDRP_GLOBAL __launch_bounds__(SAMP_THREADS) void k_samples_prosac(int n_tables, 
 }
 
 // ------------------------------------------------------------------------------------------------ ranking
-// The key of a score as an unsigned integer that orders like the definition: NaN -> -inf, -0.0 -> +0.0, then the usual monotone map of the
-// IEEE bits (negative: all bits flipped; otherwise: the sign bit set).  Larger key = better score.
-__device__ __forceinline__ uint64_t rank_key(double s) {
-    uint64_t b = (uint64_t)__double_as_longlong(s);
-    const uint64_t mag = b & 0x7fffffffffffffffULL;
-    if (mag > 0x7ff0000000000000ULL) b = 0xfff0000000000000ULL; // NaN (either sign, any payload) -> -inf
-    else if (mag == 0) b = 0;                                    // -0.0 -> +0.0
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
+using prosac::rank_key;
 
 constexpr int RANK_THREADS = 256, RANK_PER_THREAD = 4, RANK_TILE = 2048;
+
+// The counting loop of k_rank and of the ranked front end (k_gather_ranked, mdrp_frontend.h): cnt[q] += #{j in [0, n) : key_j > key[q], or
+// key_j == key[q] and j < idx[q]} for the RANK_PER_THREAD records a thread holds, key_j = load(j) read by the workgroup into LDS tiles of
+// RANK_TILE and broadcast from there.  Every thread of the workgroup calls it with the same n: the barriers are the tile's.
+template <typename Load>
+__device__ __forceinline__ void rank_count(uint64_t *s_key /*LDS, RANK_TILE*/, int n, int tid, const Load &load, const uint64_t (&key)[RANK_PER_THREAD],
+                                           const int (&idx)[RANK_PER_THREAD], int (&cnt)[RANK_PER_THREAD]) {
+    for (int t0 = 0; t0 < n; t0 += RANK_TILE) {
+        const int tl = min(RANK_TILE, n - t0);
+        __syncthreads(); // the tile's readers of the previous round are done
+        for (int j = tid; j < tl; j += RANK_THREADS) s_key[j] = load(t0 + j);
+        __syncthreads();
+        for (int j = 0; j < tl; ++j) {
+            const uint64_t kj = s_key[j];
+#pragma unroll
+            for (int q = 0; q < RANK_PER_THREAD; ++q) cnt[q] += (kj > key[q] || (kj == key[q] && t0 + j < idx[q])) ? 1 : 0;
+        }
+    }
+}
 
 // One workgroup per pair.  rank of record i = records that come before it = #{j : key_j > key_i, or key_j == key_i and j < i} (a stable descending
 // sort); order[rank] = i.  Each thread ranks RANK_PER_THREAD records per pass against all n keys, read as LDS broadcasts from tiles of RANK_TILE
@@ -168,17 +202,7 @@ MDRP_GLOBAL __launch_bounds__(RANK_THREADS) void k_rank(const double *__restrict
             key[q] = idx[q] < n ? rank_key(sc[idx[q]]) : 0;
             cnt[q] = 0;
         }
-        for (int t0 = 0; t0 < n; t0 += RANK_TILE) {
-            const int tl = min(RANK_TILE, n - t0);
-            __syncthreads(); // the tile's readers of the previous round are done
-            for (int j = tid; j < tl; j += RANK_THREADS) s_key[j] = rank_key(sc[t0 + j]);
-            __syncthreads();
-            for (int j = 0; j < tl; ++j) {
-                const uint64_t kj = s_key[j];
-#pragma unroll
-                for (int q = 0; q < RANK_PER_THREAD; ++q) cnt[q] += (kj > key[q] || (kj == key[q] && t0 + j < idx[q])) ? 1 : 0;
-            }
-        }
+        rank_count(s_key, n, tid, [sc](int j) { return rank_key(sc[j]); }, key, idx, cnt);
 #pragma unroll
         for (int q = 0; q < RANK_PER_THREAD; ++q)
             if (idx[q] < n) ord[cnt[q]] = idx[q]; // (cnt < n: a permutation of [0, n))

@@ -15,6 +15,13 @@ For match row m = (i, j), in row order:
 5. kept rows, in match order, give x1 = float64(p1) - center1, x2 = float64(p2) - center2, d1, d2; slot[m] is the position of row m
    among the kept rows, -1 for a dropped row.
 
+With `scores` (one per match row, higher is better: a matcher's confidence) the kept rows leave in QUALITY order instead of match order, the order
+the progressive sampler (PROSAC) wants.  Rules 1-4 decide what is kept exactly as above: a score never drops or keeps a row.  Then
+
+6. key(m) = float64(scores[m]) with NaN replaced by -inf; -0.0 and +0.0 are one key; rank(m) = the number of kept rows m' with key(m') > key(m), or
+   key(m') == key(m) and m' < m: a stable descending sort of the kept rows' scores in match order (`score_order`).  slot[m] = rank(m), -1 for a
+   dropped row, and the record of row m sits at index rank(m).
+
 `poselib.gather_image_pairs_torch` / `estimate_image_pairs_torch` take the batch as its producer holds it: keypoints and depth maps once per
 image, pairs as image indices (include/mdrp.h mdrp_image_pairs).  `gather_image_pairs_numpy` below states them as a loop over the pairs that
 calls `gather_matches_numpy` on the two images' valid tables: that reduction is the definition.
@@ -53,9 +60,29 @@ def _table(a, what):
     return a
 
 
-def gather_matches_numpy(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1=None, center2=None, filter="both_inf"):
+def score_order(scores):
+    """rule 6 on the scores of the kept rows, in match order: the position (among the kept rows) of the row at every rank — descending key, NaN as
+    -inf, -0.0 = +0.0, ties by ascending position"""
+    with np.errstate(invalid="ignore"):  # (a signalling NaN widens to a quiet one: NaN either way)
+        key = np.array(scores, dtype=np.float64).reshape(-1)  # (a copy; float32 widens exactly)
+    key[np.isnan(key)] = -np.inf
+    key = key + 0.0  # -0.0 + 0.0 = +0.0
+    return np.argsort(-key, kind="stable")
+
+
+def _row_scores(scores, rows):
+    s = np.asarray(scores)
+    if s.dtype not in (np.float32, np.float64):
+        raise ValueError("scores must be float32 or float64")
+    if s.size != rows or s.ndim > 2 or (s.ndim == 2 and s.shape[0] != 1):
+        raise ValueError(f"scores: expected one per match row ({rows}), got shape {s.shape}")
+    return s.reshape(-1)
+
+
+def gather_matches_numpy(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1=None, center2=None, filter="both_inf", scores=None):
     """One pair: keypoints (K, 2) and depth maps (H, W) in float32 / float64, matches (M, 2) integers (taken as int32).
-    Returns (x1 (n, 2), x2 (n, 2), d1 (n,), d2 (n,), slot (M,) int32), the first four float64; n = len(d1)."""
+    Returns (x1 (n, 2), x2 (n, 2), d1 (n,), d2 (n,), slot (M,) int32), the first four float64; n = len(d1).
+    scores: (M,) float32 / float64, one per match row, higher is better — the kept rows in rank order (rule 6), slot[m] the rank of row m."""
     kp1, kp2 = _table(keypoints1, "keypoints"), _table(keypoints2, "keypoints")
     dm1, dm2 = _table(depth_map1, "depth maps"), _table(depth_map2, "depth maps")
     if kp1.ndim != 2 or kp1.shape[1] != 2 or kp2.ndim != 2 or kp2.shape[1] != 2 or dm1.ndim != 2 or dm2.ndim != 2:
@@ -75,7 +102,14 @@ def gather_matches_numpy(keypoints1, keypoints2, matches, depth_map1, depth_map2
     slot = np.where(ok, np.cumsum(ok) - 1, -1).astype(np.int32)                          # rule 5
     c1 = np.zeros(2) if center1 is None else np.asarray(center1, dtype=np.float64).reshape(2)
     c2 = np.zeros(2) if center2 is None else np.asarray(center2, dtype=np.float64).reshape(2)
-    return p1[ok] - c1, p2[ok] - c2, d1[ok], d2[ok], slot
+    x1, x2, e1, e2 = p1[ok] - c1, p2[ok] - c2, d1[ok], d2[ok]
+    if scores is None:
+        return x1, x2, e1, e2, slot
+    o = score_order(_row_scores(scores, len(m))[ok])                                    # rule 6: o[r] = kept position of the row at rank r
+    rank = np.empty(len(o), dtype=np.int32)
+    rank[o] = np.arange(len(o), dtype=np.int32)
+    slot[ok] = rank
+    return x1[o], x2[o], e1[o], e2[o], slot
 
 
 def pad_pairs(gathered, m_max):
@@ -104,11 +138,12 @@ def clamp_extent(v, maximum):
     return np.clip(np.asarray(v, dtype=np.int64), 0, int(maximum))
 
 
-def gather_image_pairs_numpy(keypoints, depth_maps, pairs, matches, centers=None, sizes=None, kp_counts=None, filter="both_inf"):
+def gather_image_pairs_numpy(keypoints, depth_maps, pairs, matches, centers=None, sizes=None, kp_counts=None, filter="both_inf", scores=None):
     """keypoints (I, K, 2) and depth_maps (I, H, W) in float32 / float64, pairs (B, 2) image indices (a, c), matches (B, M, 2) integers.
     sizes (I, 2) (h, w) and kp_counts (I,): the valid part of each image's map and table, clamped to the allocation, None = all of it;
     centers (I, 2) or (2,).  Pair b is gather_matches_numpy on image a's and image c's valid tables; a pair with an index outside [0, I) is
-    empty.  Returns pad_pairs of the per-pair results: x1, x2 (B, M, 2), d1, d2 (B, M), n (B,) int32, slot (B, M) int32."""
+    empty.  Returns pad_pairs of the per-pair results: x1, x2 (B, M, 2), d1, d2 (B, M), n (B,) int32, slot (B, M) int32.
+    scores: (B, M) float32 / float64, one per match row — every pair in rank order (gather_matches_numpy's rule 6)."""
     if filter not in FILTERS:
         raise ValueError(f"filter must be one of {FILTERS}, not {filter!r}")
     kp, dm = _table(keypoints, "keypoints"), _table(depth_maps, "depth maps")
@@ -121,6 +156,10 @@ def gather_image_pairs_numpy(keypoints, depth_maps, pairs, matches, centers=None
     if matches.ndim != 3 or len(matches) != len(pairs) or matches.shape[2] != 2:
         raise ValueError("expected matches (B, M, 2) with the pairs' B")
     M = matches.shape[1]
+    if scores is not None:
+        scores = np.asarray(scores)
+        if scores.dtype not in (np.float32, np.float64) or scores.shape != (len(pairs), M):
+            raise ValueError("scores must be (B, M) float32 or float64, one per match row")
     counts = np.full(I, K, dtype=np.int64) if kp_counts is None else clamp_extent(np.asarray(kp_counts).reshape(I), K)
     hw = np.tile(np.array([H, W], dtype=np.int64), (I, 1)) if sizes is None else np.asarray(sizes).reshape(I, 2)
     hs, ws = clamp_extent(hw[:, 0], H), clamp_extent(hw[:, 1], W)
@@ -136,5 +175,6 @@ def gather_image_pairs_numpy(keypoints, depth_maps, pairs, matches, centers=None
             gathered.append(empty)
             continue
         gathered.append(gather_matches_numpy(kp[a][:counts[a]], kp[c][:counts[c]], matches[b], dm[a][:hs[a], :ws[a]], dm[c][:hs[c], :ws[c]],
-                                             None if cs is None else cs[a], None if cs is None else cs[c], filter))
+                                             None if cs is None else cs[a], None if cs is None else cs[c], filter,
+                                             None if scores is None else scores[b]))
     return pad_pairs(gathered, M)

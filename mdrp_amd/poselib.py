@@ -241,7 +241,8 @@ def _no_budgets_with_priors(priors, budgets):
         raise ValueError("priors and budgets do not combine: run the budgets without priors, or one call per budget")
 
 
-# scores=... on a monodepth *_batch entry point, on the single-pair forms and on estimate_batch_torch: the estimate in match-score order with the
+# scores=... on a monodepth *_batch entry point, on the single-pair forms, on estimate_batch_torch and on the device front end (one score per MATCH
+# ROW there: gather_matches_torch, estimate_matches_torch and the image-pairs forms rank inside the gather): the estimate in match-score order with the
 # reference's progressive sampler (PROSAC; include/mdrp.h mdrp_estimate_batch_ranked).  One score per correspondence, higher is better
 # (a matcher's confidence), or the string "presorted" for records that are in quality order already.  progressive_sampling in ransac_opt may be
 # absent, False or True: scores= is what asks for the sampler; max_prosac_iterations is read.  Masks and info["inliers"] stay in the caller's order.
@@ -902,14 +903,50 @@ def _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2,
     return mm, (kp1, kp2, mt, dm1, dm2, c1, c2), B, int(mt.shape[1]), dev
 
 
-def gather_matches_torch(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1=None, center2=None, filter="both_inf"):
+def _front_end_scores(scores, matches):
+    """scores= of a front-end entry point -> (ranked call?, score tensor shaped like matches' rows or None for rows in quality order already).
+    Checked against `matches` as the caller passed it, before anything touches the device."""
+    import torch
+    if scores is None:
+        return False, None
+    if isinstance(scores, str):
+        if scores != PRESORTED:
+            raise ValueError(f'scores: the only string is "{PRESORTED}", not {scores!r}')
+        return True, None
+    if not (isinstance(scores, torch.Tensor) and scores.dtype in (torch.float32, torch.float64)):
+        raise ValueError('scores must be a float32 / float64 tensor on the inputs\' device or "presorted"')
+    if not (isinstance(matches, torch.Tensor) and matches.dim() in (2, 3)):
+        raise ValueError("matches must have shape (B, M, 2)")
+    if scores.device != matches.device:
+        raise ValueError("scores must live on the inputs' device")
+    rows = tuple(matches.shape[:-1])
+    if tuple(scores.shape) != rows and not (len(rows) == 2 and rows[0] == 1 and tuple(scores.shape) == rows[1:]):
+        raise ValueError(f"scores must be {rows}, one per match row, not {tuple(scores.shape)}")
+    return True, scores
+
+
+def _score_args(sc):
+    """(device pointer or None, score_type, the tensor to keep alive) of a checked score tensor: float32 goes in as it is, nothing is widened"""
+    import torch
+    if sc is None:
+        return None, _capi.F64, None
+    sc = sc.contiguous()
+    return sc.data_ptr(), _capi.F32 if sc.dtype == torch.float32 else _capi.F64, sc
+
+
+def gather_matches_torch(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1=None, center2=None, filter="both_inf", scores=None):
     """The front end alone, on the device's current torch stream.  keypoints (B, K, 2) float32 | float64 (a (K, 2) tensor is B = 1), matches
     (B, M, 2) int32 | int64 with -1 rows as padding, depth maps (B, H, W) float32 | float64 (the two images may differ in size), all on one
     ROCm device; center1 / center2: optional (B, 2) or (2,) principal points, subtracted in float64; filter: "both_inf" (the reference
     scripts' rule) | "finite".  Returns (x1, x2 (B, M, 2), d1, d2 (B, M): float64 device tensors, kept rows first, in match order, the
     rest x = 0, d = 1; n_per_pair: numpy int32; slot (B, M): int32 device tensor, the position of every match row, -1 if dropped).
-    One stream synchronisation (the counts)."""
+    One stream synchronisation (the counts).
+    scores: a (B, M) float32 | float64 tensor on the inputs' device ((M,) for B = 1), one per match row, higher is better (a matcher's
+    confidence) — the kept rows come in QUALITY order instead (mdrp_amd/frontend.py rule 6): slot is the rank of every match row,
+    the buffers are what estimate_batch_torch(..., scores="presorted") takes.  A score never drops a row.  "presorted": the rows are in quality
+    order already, which for the gather alone is no scores at all."""
     import torch
+    ranked, sc = _front_end_scores(scores, matches)
     mm, keep, B, M, dev = _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter)
     index = dev.index if dev.index is not None else torch.cuda.current_device()
     h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
@@ -919,20 +956,28 @@ def gather_matches_torch(keypoints1, keypoints2, matches, depth_map1, depth_map2
         d1 = torch.empty((B, M), dtype=torch.float64, device=dev)
         d2 = torch.empty((B, M), dtype=torch.float64, device=dev)
         slot = torch.empty((B, M), dtype=torch.int32, device=dev)
-        n = h.gather_matches(mm, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
-    del keep
+        if ranked:
+            sp, st, sc = _score_args(sc)
+            n = h.gather_matches_ranked(mm, sp, st, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
+        else:
+            n = h.gather_matches(mm, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
+    del keep, sc
     return x1, x2, d1, d2, n, slot
 
 
 def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, depth_map2, cameras1=None, cameras2=None, ransac_opt=None,
-                           bundle_opt=None, center1=None, center2=None, filter="both_inf"):
+                           bundle_opt=None, center1=None, center2=None, filter="both_inf", scores=None):
     """estimate_batch_torch straight from a matcher's output and two depth maps (inputs as gather_matches_torch): the correspondences are
     gathered on the device into buffers of the handle and handed to the same estimator — records identical to gathering with
     mdrp_amd.frontend.gather_matches_numpy and calling estimate_batch_torch with its n_per_pair.  kind: "calibrated" | "shared_focal" |
     "varying_focal" (pass center1 / center2 for the focal estimators: they take principal-point-centred pixels).  Queued on the device's
     current torch stream; the B kept-row counts cross to the host behind one stream synchronisation, then the 136-byte result records.
-    Returns (records, match_mask: (B, M) uint8 device tensor — 1 where the row was kept and is an inlier —, n_used: numpy int32)."""
+    Returns (records, match_mask: (B, M) uint8 device tensor — 1 where the row was kept and is an inlier —, n_used: numpy int32).
+    scores (see PRESORTED and gather_matches_torch): one score per match row or "presorted" — the estimate in score order with the progressive
+    sampler, bit for bit estimate_batch_torch(scores=the kept rows' scores) on the unranked gather; the gather itself ranks, each kept row is
+    written once.  progressive_sampling in ransac_opt may be absent, False or True; without scores it is refused as before."""
     import torch
+    ranked, sc = _front_end_scores(scores, matches)
     kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
     if isinstance(kind, str) and kind not in kinds:
         raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
@@ -948,9 +993,13 @@ def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, de
     h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
     with torch.cuda.device(dev):
         match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
-        n_used = h.estimate_matches_device(k, mm, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        if ranked:
+            sp, st, sc = _score_args(sc)
+            n_used = h.estimate_matches_ranked_device(k, mm, sp, st, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        else:
+            n_used = h.estimate_matches_device(k, mm, B, ro, bo, cams1, cams2, match_mask.data_ptr())
         res = h.fetch_results(B)
-    del keep
+    del keep, sc
     return res, match_mask, n_used
 
 
@@ -1024,13 +1073,15 @@ def _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, size
     return ip, (kp, dm, mt, cs, sz, kc, pr), host_pairs, B, int(mt.shape[1]), I, dev
 
 
-def gather_image_pairs_torch(keypoints, depth_maps, pairs, matches, centers=None, sizes=None, kp_counts=None, filter="both_inf"):
+def gather_image_pairs_torch(keypoints, depth_maps, pairs, matches, centers=None, sizes=None, kp_counts=None, filter="both_inf", scores=None):
     """gather_matches_torch for pairs given as image indices.  keypoints (I, K, 2) and depth_maps (I, H, W) float32 | float64, matches (B, M, 2)
     int32 | int64 with -1 rows as padding, all on one ROCm device; pairs (B, 2) image indices (a, c) as a sequence, NumPy array or tensor on any
     device (a pair with an index outside [0, I) is empty: n = 0, slots -1, filler).  sizes (I, 2) (h, w) and kp_counts (I,): the valid part of
     each image's map and table (clamped to H, W and K; None = all); centers (I, 2) or (2,), subtracted in float64.  Returns what
-    gather_matches_torch returns, on the device's current torch stream, behind one stream synchronisation (the counts)."""
+    gather_matches_torch returns, on the device's current torch stream, behind one stream synchronisation (the counts).  scores: as
+    gather_matches_torch's, (B, M)."""
     import torch
+    ranked, sc = _front_end_scores(scores, matches)
     ip, keep, _, B, M, _, dev = _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, sizes, kp_counts, filter, False)
     index = dev.index if dev.index is not None else torch.cuda.current_device()
     h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
@@ -1040,8 +1091,12 @@ def gather_image_pairs_torch(keypoints, depth_maps, pairs, matches, centers=None
         d1 = torch.empty((B, M), dtype=torch.float64, device=dev)
         d2 = torch.empty((B, M), dtype=torch.float64, device=dev)
         slot = torch.empty((B, M), dtype=torch.int32, device=dev)
-        n = h.gather_image_pairs(ip, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
-    del keep
+        if ranked:
+            sp, st, sc = _score_args(sc)
+            n = h.gather_image_pairs_ranked(ip, sp, st, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
+        else:
+            n = h.gather_image_pairs(ip, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
+    del keep, sc
     return x1, x2, d1, d2, n, slot
 
 
@@ -1054,13 +1109,15 @@ def _pair_cameras(cameras, host_pairs, I):
 
 
 def estimate_image_pairs_torch(kind, keypoints, depth_maps, pairs, matches, cameras=None, ransac_opt=None, bundle_opt=None, centers=None, sizes=None,
-                               kp_counts=None, filter="both_inf"):
+                               kp_counts=None, filter="both_inf", scores=None):
     """estimate_matches_torch for pairs given as image indices (inputs as gather_image_pairs_torch): records identical to gathering with
     mdrp_amd.frontend.gather_image_pairs_numpy and calling estimate_batch_torch with its n_per_pair and the per-pair cameras.  cameras
     (calibrated only) are per IMAGE — one Camera | dict for all, a list of I, or a CAMERA_DTYPE array of I records — and expanded to per-pair
     records by pairs on the host.  kind: "calibrated" | "shared_focal" | "varying_focal" (pass centers for the focal estimators).
-    Returns (records, match_mask: (B, M) uint8 device tensor, n_used: numpy int32), stream behaviour as estimate_matches_torch."""
+    Returns (records, match_mask: (B, M) uint8 device tensor, n_used: numpy int32), stream behaviour as estimate_matches_torch.  scores: as
+    estimate_matches_torch's, (B, M)."""
     import torch
+    ranked, sc = _front_end_scores(scores, matches)
     kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
     if isinstance(kind, str) and kind not in kinds:
         raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
@@ -1076,9 +1133,13 @@ def estimate_image_pairs_torch(kind, keypoints, depth_maps, pairs, matches, came
     h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
     with torch.cuda.device(dev):
         match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
-        n_used = h.estimate_image_pairs_device(k, ip, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        if ranked:
+            sp, st, sc = _score_args(sc)
+            n_used = h.estimate_image_pairs_ranked_device(k, ip, sp, st, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        else:
+            n_used = h.estimate_image_pairs_device(k, ip, B, ro, bo, cams1, cams2, match_mask.data_ptr())
         res = h.fetch_results(B)
-    del keep
+    del keep, sc
     return res, match_mask, n_used
 
 

@@ -38,13 +38,16 @@ CAM = {"model": "SIMPLE_PINHOLE", "width": W, "height": H, "params": [A * 800.0,
 BO = {"loss_type": "TRUNCATED_CAUCHY"}
 
 
-def make_inputs(batch, rows, dev):
+def make_inputs(batch, rows, dev, outlier_frac=0.5, outlier_flags=None):
     """matcher-shaped inputs on the device: keypoint tables with the correspondences scattered through a permutation, their depths painted
-    into the maps, a tail of -1 padding rows of a different length per pair (LightGlue pads ragged match lists that way)"""
+    into the maps, a tail of -1 padding rows of a different length per pair (LightGlue pads ragged match lists that way).  outlier_flags: a
+    list that receives the (batch, rows) outlier flags of the match rows (tools/frontend_ranked_bench.py makes its scores from them)."""
     import torch
     from mdrp_amd import synth
     rng = np.random.default_rng(5)
-    b = synth.make_batch(0, batch, rows, noise_px=0.5, depth_noise=0.02, outlier_frac=0.5)
+    b = synth.make_batch(0, batch, rows, noise_px=0.5, depth_noise=0.02, outlier_frac=outlier_frac)
+    if outlier_flags is not None:
+        outlier_flags.append(np.stack([g["is_outlier"] for g in b["gt"]]))
     kp1 = np.stack([rng.uniform(0, W, (batch, K)), rng.uniform(0, H, (batch, K))], 2)
     kp2 = kp1.copy()
     matches = np.full((batch, rows, 2), -1, dtype=np.int64)
@@ -112,10 +115,10 @@ def route_b(poselib, t, ro):
     return res, match_mask
 
 
-def make_image_inputs(n_images, batch, rows, dev):
+def make_image_inputs(n_images, batch, rows, dev, outlier_frac=0.5, outlier_flags=None):
     """one scene seen by n_images cameras: K world points projected into every image (each image's table in an order of its own), the depth
     of every visible point painted into that image's one map, and for the first `batch` of the image pairs a match list over `rows` of the
-    points, half of the rows mismatched, with a tail of -1 padding rows.  Returns the device tensors (keypoints (I, K, 2) float32, depth maps
+    points, half of the rows (outlier_frac) mismatched, with a tail of -1 padding rows; outlier_flags as in make_inputs.  Returns the device tensors (keypoints (I, K, 2) float32, depth maps
     (I, H, W) float32, pairs (B, 2) int32 on the host, matches (B, rows, 2) int64)."""
     import itertools
     import torch
@@ -146,7 +149,9 @@ def make_image_inputs(n_images, batch, rows, dev):
     for b, (i, j) in enumerate(pairs):
         pts = rng.permutation(K)[:rows]
         other = pts.copy()
-        wrong = rng.random(rows) < 0.5
+        wrong = rng.random(rows) < outlier_frac
+        if outlier_flags is not None:
+            outlier_flags.append(wrong)
         other[wrong] = rng.permutation(pts[wrong])  # outliers: a point matched to another point's keypoint
         matches[b, :live[b], 0] = order[i][pts[:live[b]]]
         matches[b, :live[b], 1] = order[j][other[:live[b]]]
