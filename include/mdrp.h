@@ -154,6 +154,16 @@ int mdrp_hip_build_version(void);
 /* block the calling thread until all work queued on the handle's stream is done */
 int mdrp_synchronize(mdrp_handle *h);
 
+/* The handle's history.  A handle keeps its scratch buffers (they only grow and are never cleared), the first-chunk length it learnt from its last
+ * call (mdrp_stats::first_chunk) and the fused tail's back-off (mdrp_stats::fuse_*_timeouts) from one call to the next.  All of it may change how the
+ * next call is SCHEDULED and none of it what the call RETURNS: every entry point below defines its outputs from its own arguments alone, bit for bit,
+ * whatever the handle ran before — another estimator, a larger or smaller batch, a call under other MDRP_* schedule settings, a refused call
+ * (tests/test_gpu_history.py).
+ * Calls on one handle may follow each other without mdrp_synchronize or a fetch in between, the *_async ones included: a call queues its work behind
+ * the previous call's on the handle's stream and stages its per-call parameters in memory the previous call has finished reading.  What the earlier
+ * call wrote into CALLER-owned device buffers (inlier masks, initial_score / initial_inliers) is complete once the stream has drained; its result
+ * records live in the handle and are replaced by the later call's — fetch or copy them first if they are wanted. */
+
 /* Batched estimators.  x1,x2: [B][n_max][2] pixel coordinates; d1,d2: [B][n_max] depths; n_per_pair: [B] valid
  * correspondences per pair (host memory always; NULL = all n_max).  cam1/cam2: [B] cameras (host memory; calibrated
  * estimator only — the focal estimators take principal-point-centred pixels, README.md:88-96).  out: [B] results

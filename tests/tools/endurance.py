@@ -1,39 +1,52 @@
-import sys, os, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+"""The long soak (not collected by pytest): handles created and destroyed, then one handle walked over every call of tests/history_cases.py for many
+laps, every probe checked against its fresh-handle bytes, with the device memory still free reported as it goes.  python tests/tools/endurance.py [laps]"""
+import os
+import sys
+import time
+
+TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for path in (TESTS, os.path.dirname(TESTS)):
+    if path not in sys.path:
+        sys.path.insert(0, path)
 import numpy as np, torch
-from mdrp_amd import _capi as capi, synth
+import history_cases as hc
+from mdrp_amd import _capi as capi
+
+laps = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+setenv, delenv = hc.environ_setters()
+
+
+def run(call, h):
+    hc.apply_env(call.env, setenv, delenv)
+    try:
+        return call.run(h)
+    finally:
+        hc.apply_env(None, setenv, delenv)
+
+
+def free_mb():
+    return (free0 - torch.cuda.mem_get_info()[0]) / 2**20
+
+
 free0 = torch.cuda.mem_get_info()[0]
-b = synth.make_batch(0, 64, 500, noise_px=0.5, depth_noise=0.02, outlier_frac=0.4)
-cams = np.zeros(64, dtype=capi.CAMERA_DTYPE); cams["params"][:, 0] = 800.0
-ro = capi.ransac_opt_from_dict({"max_epipolar_error": 2.0, "max_reproj_error": 16.0})
-bo = capi.bundle_opt_from_dict({"loss_type": "TRUNCATED_CAUCHY"})
-ref = None
+fresh = {}
 t0 = time.time()
-for it in range(40):                      # create / use / destroy
-    h = capi.Handle(0, None)
-    res, mask = h.estimate_batch(0, b["x1"], b["x2"], b["d1"], b["d2"], ro, bo, None, cams, cams)
-    if ref is None: ref = (res.tobytes(), mask.tobytes())
-    assert (res.tobytes(), mask.tobytes()) == ref, it
-    del h
-print("create/destroy x40 ok, %.1f s" % (time.time() - t0), "free delta MB", (free0 - torch.cuda.mem_get_info()[0]) / 2**20)
+for p in hc.probes():                     # create / use / destroy: the fresh-handle bytes, twice
+    for it in range(2):
+        h = capi.Handle(0, None)
+        out = run(p, h)
+        assert fresh.setdefault(p.name, out) == out, (p, it)
+        h.close()
+print("create/destroy x%d ok, %.1f s" % (2 * len(fresh), time.time() - t0), "free delta MB", free_mb())
+calls = hc.predecessors()
+rng = np.random.default_rng(0)
 h = capi.Handle(0, None)
 t0 = time.time()
-for it in range(400):                     # same handle, alternating shapes
-    n = 64 if it % 2 else 17
-    res, mask = h.estimate_batch(0, b["x1"][:n], b["x2"][:n], b["d1"][:n], b["d2"][:n], ro, bo, None, cams[:n], cams[:n])
-    if n == 64: assert (res.tobytes(), mask.tobytes()) == ref, it
-print("400 calls ok, %.1f s" % (time.time() - t0), "free delta MB", (free0 - torch.cuda.mem_get_info()[0]) / 2**20)
-# the non-monodepth baselines interleaved with the monodepth estimator on one handle: determinism and no growth
-refs = {}
-t0 = time.time()
-for it in range(300):
-    kind = (3, 5, 0)[it % 3]
-    n = (64, 17, 40)[it % 3]
-    if kind == 0:
-        res, mask = h.estimate_batch(0, b["x1"][:n], b["x2"][:n], b["d1"][:n], b["d2"][:n], ro, bo, None, cams[:n], cams[:n])
-    else:
-        res, mask = h.estimate_batch(kind, b["x1"][:n], b["x2"][:n], None, None, ro, bo, None, cams[:n] if kind == 3 else None, cams[:n] if kind == 3 else None)
-    key = (kind, n)
-    if key not in refs: refs[key] = (res.tobytes(), mask.tobytes())
-    assert (res.tobytes(), mask.tobytes()) == refs[key], (it, key)
-print("300 interleaved baseline / monodepth calls ok, %.1f s" % (time.time() - t0), "free delta MB", (free0 - torch.cuda.mem_get_info()[0]) / 2**20)
+for lap in range(laps):                   # same handle, every call in another order each lap
+    for at in rng.permutation(len(calls)):
+        out = run(calls[at], h)
+        if calls[at].probe:
+            bad = hc.mismatches(f"lap {lap}", calls[at], out, fresh[calls[at].name])
+            assert not bad, bad
+    print("lap %d ok, %d calls, %.1f s" % (lap, (lap + 1) * len(calls), time.time() - t0), "free delta MB", free_mb(), flush=True)
+h.close()
