@@ -196,6 +196,13 @@ int mdrp_copy_results_device(mdrp_handle *h, void *dst_dev, int batch);
 int mdrp_solver_batch(mdrp_handle *h, int solver, const double *x1h, const double *x2h, const double *d1,
                       const double *d2, int count, mdrp_model *out, int32_t *n_out);
 
+/* Inspection, no kernel runs: how many one-wavefront workgroups of the minimal solver (`solver` as above) the runtime's occupancy query places on
+ * a compute unit of `device` when each reserves the dynamic LDS the scheduler's rule grants for `resident_per_simd` solver wavefronts per SIMD with
+ * `keep_free_bytes` of the unit's LDS left out of their reach (sched::solver_reservation).  reserve_bytes = 0: the rule grants no cap
+ * and workgroups_per_cu is what registers alone allow. */
+int mdrp_solver_residency(int device, int solver, int resident_per_simd, uint64_t keep_free_bytes, uint64_t *lds_per_cu,
+                          uint64_t *reserve_bytes, int *workgroups_per_cu);
+
 /* The baselines' minimal solvers (relpose_5pt @0x14ae80, relpose_7pt @0x4ff2e0) on `count` independent problems, host memory.
  * x1h, x2h: [count][K][3] unit bearings, K = 5 / 7.  out: [count][M] models, M = 10 / 3 (solutions in the reference's order);
  * n_out: [count]. */

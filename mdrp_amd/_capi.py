@@ -20,7 +20,7 @@ SOLVER_P3P, SOLVER_SHIFT, SOLVER_SHARED, SOLVER_VARYING = 0, 1, 2, 3
 EXPORTS = (
     "mdrp_create_", "mdrp_create_on_stream_", "mdrp_destroy", "mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version", "mdrp_synchronize", "mdrp_estimate_batch",
     "mdrp_estimate_batch_async", "mdrp_fetch_results", "mdrp_copy_results_device", "mdrp_solver_batch", "mdrp_score_models", "mdrp_count_candidates", "mdrp_bound_models", "mdrp_refine_models",
-    "mdrp_last_sweep_stats", "mdrp_last_stats", "mdrp_last_stats_sized", "mdrp_classic_solver_batch",
+    "mdrp_last_sweep_stats", "mdrp_last_stats", "mdrp_last_stats_sized", "mdrp_classic_solver_batch", "mdrp_solver_residency",
     "mdrp_gather_matches", "mdrp_estimate_matches_async",
     "mdrp_estimate_batch_budgets", "mdrp_estimate_batch_budgets_async", "mdrp_fetch_budget_results", "mdrp_copy_budget_results_device",
     "mdrp_refine_batch", "mdrp_refine_batch_async",
@@ -204,6 +204,8 @@ def load_library():
                                                vp, vp, vp, vp, vp]
         if hasattr(lib, "mdrp_replay_slots"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.replay_slots raises)
             lib.mdrp_replay_slots.argtypes = [vp, C.POINTER(RansacOpt), C.POINTER(Replay)]
+        if hasattr(lib, "mdrp_solver_residency"):  # (an older ABI-0.6 library through MDRP_LIB has none: solver_residency raises)
+            lib.mdrp_solver_residency.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         _lib = lib
         return lib
 
@@ -274,6 +276,17 @@ def budget_list(budgets, ransac_opt=None):
         raise ValueError(f"ransac_opt['max_iterations'] = {ro['max_iterations']} differs from the last budget {ks[-1]}")
     ro["max_iterations"] = ks[-1]
     return np.asarray(ks, dtype=np.uint64), ro
+
+
+def solver_residency(solver, resident_per_simd, keep_free_bytes=0, device=0):
+    """(LDS bytes of a compute unit, dynamic LDS the scheduler's rule reserves per one-wavefront solver workgroup or 0, workgroups per compute unit
+    the runtime's occupancy query reports for that reservation): mdrp_solver_residency — no kernel runs"""
+    lib = load_library()
+    if not hasattr(lib, "mdrp_solver_residency"):
+        raise MdrpError("this library has no mdrp_solver_residency")
+    lds, reserve, wgs = C.c_uint64(), C.c_uint64(), C.c_int()
+    _check(lib, lib.mdrp_solver_residency(int(device), int(solver), int(resident_per_simd), int(keep_free_bytes), C.byref(lds), C.byref(reserve), C.byref(wgs)))
+    return lds.value, reserve.value, wgs.value
 
 
 def library_version():

@@ -147,6 +147,7 @@ struct mdrp_handle {
     DevBuf fuse;                       // fused tail: control words (64 B) | done_cnt[batch] | fin_done[batch] | ready[batch]
     Event ev_lo, ev_tables, ev_sampled[2], ev_solved[sched::NC_MAX], ev_scanned[sched::NC_MAX]; // per chunk of a super-chunk
     int num_cu = 256;
+    size_t lds_per_cu = 65536; // LDS of a compute unit, from the device properties (sched::solver_reservation)
     // persistent device buffers
     DevBuf pts, dep, st;
     DevBuf params;                     // per-call parameters in ONE upload: table states | cameras | table sizes | table of pair | n per pair
@@ -462,6 +463,10 @@ struct Pass : PassIn {
     const bool lo_overlap = env_int("MDRP_LO_OVERLAP", 1) != 0;     // three-stream pipeline; 0 = every kernel on the handle's stream
     const bool use_bound = env_int("MDRP_BOUND", 1) != 0;           // fp32 lower-bound stage between k_count and the fp64 sweep
     const bool score_split = env_int("MDRP_SCORE_SPLIT", 1) != 0;   // exact sweeps after a run's first chunk: k_score_split; 0 = k_score
+    // a run's first chunk: hypotheses scored first, whose prefix records retire most of the others (k_first_*); 0 = the whole chunk is scored as before
+    const int first_pick = sched::first_pick(kind, batch_call, SCORE_WAVE_MAX_PAIRS, env_int("MDRP_FIRST_PICK", -1));
+    // solver wavefronts per SIMD beside a first chunk's sweeps (sched::solver_reservation); set: that R with no LDS kept free, 0 = uncapped
+    const int solve_resident = env_int("MDRP_SOLVE_RESIDENT", -1);
     const int lo_threads = env_int("MDRP_LO_THREADS", sched::lo_lanes(batch_call, n_max));
     const int final_threads = env_int("MDRP_FINAL_THREADS", sched::final_lanes(batch_call));
     const int samp_threads = env_int("MDRP_SAMPLE_THREADS", ssz == 3 ? SAMP_THREADS : (ssz == 5 ? 512 : 256)); // ~ samples between two rejections
@@ -653,6 +658,17 @@ struct Pass : PassIn {
         return v;
     }
 
+    // Dynamic LDS each solver workgroup of the view reserves (and never touches), or 0: no cap.  Only the long solver that shares the chip with a
+    // first chunk's prefix retirement (P3P and shift solvers: the focal ones sit at two wavefronts per SIMD by their registers) is ever capped.
+    // Unset, MDRP_SOLVE_RESIDENT means sched::SOLVE_RESIDENT with two of the front's largest sweep workgroups kept free.
+    size_t solve_reserve(const ChunkView &v) const {
+        const bool beside_front = piped && it0 == 0 && v.c == 1 && kind == MDRP_CALIB;
+        if (!beside_front || solve_resident == 0 || (solve_resident < 0 && first_pick == 0)) return 0;
+        const size_t sweep_wg = std::max<size_t>(SPLIT_LDS_BYTES, std::max<size_t>(SCORE_TILE_BYTES, CNT_LDS_BYTES));
+        return solve_resident > 0 ? sched::solver_reservation(h->lds_per_cu, solve_resident, 0)
+                                  : sched::solver_reservation(h->lds_per_cu, sched::SOLVE_RESIDENT, 2 * sweep_wg);
+    }
+
     // sample table (unless presampled) and minimal solver of the view on stream st_
     int solve(const ChunkView &v, hipStream_t st_) {
         const RunParams &r = v.r;
@@ -685,8 +701,14 @@ struct Pass : PassIn {
                 hipLaunchKernelGGL(kc_solve<CLASSIC_FUND>, sgrid, dim3(64), SOLVE7_LDS_BYTES, st_, r, v.st, v.samples, v.pts, v.models, v.slot_inl, v.tags, v.model_count);
             return MDRP_OK;
         }
+        // One-wavefront workgroups at a capped residency for the solver that runs beside a first chunk's sweeps, where the rule grants a cap
+        // (solve_reserve); four-wavefront workgroups for the calibrated solvers otherwise (solve_threads, mdrp_kernels.h)
+        const size_t reserve = solve_reserve(v);
 #define MDRP_SOLVE_LAUNCH(S)                                                                                                   \
-    hipLaunchKernelGGL(k_solve<S>, dim3((r.chunk_len + solve_threads(S) - 1) / solve_threads(S), pc), dim3(solve_threads(S)), 0, st_, r, v.st, v.samples, v.pts, v.dep, v.models, v.slot_inl, v.tags, v.model_count, 0, r.chunk_len)
+    do {                                                                                                                       \
+        const int threads_ = reserve ? 64 : solve_threads(S);                                                                  \
+        hipLaunchKernelGGL(k_solve<S>, dim3((r.chunk_len + threads_ - 1) / threads_, pc), dim3(threads_), reserve, st_, r, v.st, v.samples, v.pts, v.dep, v.models, v.slot_inl, v.tags, v.model_count, 0, r.chunk_len); \
+    } while (0)
         switch (r.solver) {
         case SOLVER_P3P: MDRP_SOLVE_LAUNCH(SOLVER_P3P); break;
         case SOLVER_SHIFT: MDRP_SOLVE_LAUNCH(SOLVER_SHIFT); break;
@@ -747,6 +769,31 @@ struct Pass : PassIn {
         return MDRP_OK;
     }
 
+    // A run's first chunk in calls of more than SCORE_WAVE_MAX_PAIRS pairs (3-point estimators): prefix retirement (mdrp_kernels.h, "first chunk").
+    // In: k_count's survivors — every live hypothesis, or what a prior's records left.  The picked ones are scored here; what their prefix records
+    // do not retire is back on (tags_v, surv1) for score().  The picked list uses the chunk's solver-order tag list (k_count has consumed it), the
+    // rest list the other parity's sorted list (free until the next chunk's count), their counters surv2 and und_count (idle in a first chunk).
+    int front(const ChunkView &v, Survivors &sv) {
+        if (!(v.first_of_run && first_pick > 0)) return MDRP_OK;
+        uint32_t *tags_pick = v.tags, *tags_rest = v.tags_sorted_other;
+        int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * (size_t)batch + 2;
+        hipLaunchKernelGGL(k_first_pick, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, sv.count, sv.tags, first_pick, tags_pick, v.surv2, tags_rest, v.und_count);
+        hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, v.surv2, tags_pick, v.tags_sorted);
+        hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.model_count, plan, totals, SPLIT_HYP);
+        hipEvent_t f0, f1;
+        if (int rc = get_events(h, &f0, &f1, 0)) return rc;
+        HIPCHK(hipEventRecord(f0, s));
+        const long long ub = 2ll * v.pc; // at most FIRST_PICK_MAX + 1 hypotheses per pair, in two density classes: two workgroups of SPLIT_HYP
+        MDRP_SWEEP_DISPATCH(k_first_score, kind, dim3((unsigned)std::min(ub, (long long)h->num_cu * 32)), dim3(SPLIT_THREADS), 0, s, v.r, v.st, v.pts, v.models,
+                            v.tags_sorted, v.model_count, v.slot_score, v.slot_inl, plan, totals);
+        HIPCHK(hipEventRecord(f1, s));
+        h->sweep_launches++;
+        hipLaunchKernelGGL(k_first_filter, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, v.slot_score, v.slot_inl, tags_pick, v.surv2, tags_rest, v.und_count,
+                           v.tags_v, v.surv1, &cnt->progress.evals_sweep);
+        sv = Survivors{v.tags_v, v.surv1};
+        return MDRP_OK;
+    }
+
     // sort by candidate density, plan, exact fp64 sweep of the survivors between the events e0 and e1:
     //   k_score_w      calls of few pairs: one WAVEFRONT per hypothesis — a lane per hypothesis is a 0.3 ms serial record loop however few there are
     //   k_score_split  the survivors of k_bound (~93 per pair): 64 hypotheses per workgroup, each wavefront a quarter of the records
@@ -788,7 +835,7 @@ struct Pass : PassIn {
         hipEvent_t e0, e1;
         Survivors sv;
         int rc;
-        if ((rc = get_events(h, &e0, &e1, 0)) || (rc = count(v)) || (rc = bound(v, sv)) || (rc = score(v, sv, e0, e1))) return rc;
+        if ((rc = get_events(h, &e0, &e1, 0)) || (rc = count(v)) || (rc = bound(v, sv)) || (rc = front(v, sv)) || (rc = score(v, sv, e0, e1))) return rc;
         scan(v);
         return MDRP_OK;
     }
@@ -1194,6 +1241,7 @@ static int create_handle(int device, hipStream_t stream, bool own_stream, mdrp_h
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (prop.maxSharedMemoryPerMultiProcessor > 0) h->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
     HIPCHK(hipHostMalloc((void **)&h->progress_host.v, sizeof(Progress), hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void **)&h->lm_stats_host.v, LM_STATS_BYTES, hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void **)&h->wish_host.v, 2 * sizeof(int32_t), hipHostMallocDefault));
@@ -1963,6 +2011,23 @@ int mdrp_solver_batch(mdrp_handle *h, int solver, const double *x1h, const doubl
     HIPCHK(hipMemcpyAsync(out, h->unit_e.p, sizeof(Model) * 4 * count, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(n_out, h->unit_f.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return MDRP_OK;
+}
+
+int mdrp_solver_residency(int device, int solver, int resident_per_simd, uint64_t keep_free_bytes, uint64_t *lds_per_cu, uint64_t *reserve_bytes,
+                          int *workgroups_per_cu) {
+    if (!lds_per_cu || !reserve_bytes || !workgroups_per_cu || solver < SOLVER_P3P || solver > SOLVER_VARYING) { g_err = "mdrp_solver_residency: bad argument"; return MDRP_ERR_INVALID; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { g_err = "no usable HIP device"; return MDRP_ERR_NO_DEVICE; }
+    DeviceGuard guard_(device);
+    if (!guard_.ok) { g_err = "hipSetDevice failed"; return MDRP_ERR_HIP; }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    *lds_per_cu = (uint64_t)prop.maxSharedMemoryPerMultiProcessor;
+    *reserve_bytes = (uint64_t)sched::solver_reservation((size_t)*lds_per_cu, resident_per_simd, (size_t)keep_free_bytes);
+    const void *fn = solver == SOLVER_P3P ? reinterpret_cast<const void *>(k_solve<SOLVER_P3P>) : solver == SOLVER_SHIFT ? reinterpret_cast<const void *>(k_solve<SOLVER_SHIFT>)
+                   : solver == SOLVER_SHARED ? reinterpret_cast<const void *>(k_solve<SOLVER_SHARED>) : reinterpret_cast<const void *>(k_solve<SOLVER_VARYING>);
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, fn, 64, (size_t)*reserve_bytes));
     return MDRP_OK;
 }
 

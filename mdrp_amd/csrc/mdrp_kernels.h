@@ -9,6 +9,7 @@
 //   k_count    one wavefront per 128 models  MFMA: candidate COUNT of every model over all correspondences (the Sampson
 //                                            numerator is a [models x 9].[9 x correspondences] product); models that provably
 //                                            cannot break a running record are retired here, the rest go on as survivors
+//   k_first_*  one workgroup per pair        a run's first chunk: a few hypotheses scored first, the others retired by their prefix records
 //   k_sort_tags one workgroup per pair       survivors: dense / sparse class by candidate density, sparse counting-sorted by it
 //   k_plan     one wavefront                 work items of the sweep (workgroups per pair and class)
 //   k_score    one lane per hypothesis       Sampson/MSAC (+cheirality) sweep over all N correspondences,
@@ -29,6 +30,7 @@
 #include <float.h>
 #include "mdrp_logtab.h"
 #include "mdrp_math.h"
+#include "mdrp_front.h"
 
 // The library is built from several translation units compiled in parallel (mdrp_amd/build.py): mdrp_capi.hip (host API and most kernels) and
 // mdrp_tu.hip compiled once per group of large kernel instantiations (mdrp_instances.h).  Kernel TEMPLATES are instantiated explicitly in
@@ -524,6 +526,8 @@ constexpr int PROBE_PTS = 64; // scale of the candidate-density key: key = candi
 // that nothing shortens) get going: A/B on one box, three runs each — shared focal 8.05-8.27 -> 7.82-7.95 ms per step, shift solver 8.72-8.86 ->
 // 8.81-8.89, calibrated P3P 8.33-8.49 -> 8.49-8.74 (its first sweep then ends 0.6 ms after the solver instead of inside it; stream priorities
 // change nothing).  So: one wavefront per workgroup for the focal solvers, four for the calibrated ones.
+// The workgroup size is the launch's (blockDim.x): Pass::solve (mdrp_capi.hip) launches solve_threads(SOLVER), or one-wavefront workgroups with an LDS
+// reservation where sched::solver_reservation grants a cap on their residency (on 160 KiB of LDS it grants none by default).
 constexpr int solve_threads(int solver) { return solver == SOLVER_P3P || solver == SOLVER_SHIFT ? 256 : 64; }
 template <int SOLVER> // one solver per kernel (host dispatch): a runtime switch made every launch carry the registers of the largest
 __global__ __launch_bounds__(solve_threads(SOLVER), MDRP_SOLVE_MINWAVES) void k_solve(RunParams rp, const PairState *__restrict__ st, const uint32_t *__restrict__ samples,
@@ -531,8 +535,11 @@ __global__ __launch_bounds__(solve_threads(SOLVER), MDRP_SOLVE_MINWAVES) void k_
                                                Model *__restrict__ models, int32_t *__restrict__ slot_inl,
                                                uint32_t *__restrict__ tags, int32_t *__restrict__ model_count,
                                                int it_begin, int it_end /*iterations [it_begin, it_end) of the chunk: one launch solves a sub-range*/) {
+    // (never touched: a launch of one-wavefront workgroups reserves dynamic LDS through it, which is what limits how many of them share a CU —
+    // sched::solver_reservation, mdrp_schedule.h)
+    extern __shared__ unsigned char solve_reserved[];
     const int pair = blockIdx.y;
-    const int it = it_begin + blockIdx.x * solve_threads(SOLVER) + threadIdx.x;
+    const int it = it_begin + blockIdx.x * blockDim.x + threadIdx.x; // blockDim.x: solve_threads(SOLVER), or 64 (Pass::solve)
     const PairState &ps = st[pair];
     if (!ps.active) return;
     const bool live = it < it_end;
@@ -679,16 +686,8 @@ __device__ __forceinline__ void score_point(const double *__restrict__ rec, cons
 // Its slot is then written as "not a record" (count -2); k_scan treats it like an empty slot, so the trajectory is
 // identical to scoring everything.  A wavefront stops computing once all of its lanes are out.
 // Bar: the bar of a pair, as every retirement stage (k_count, k_bound, the exact sweeps) reads it from the pair's state.
-struct Bar {
-    long long rec_cnt;
-    double rec_score; // already inflated by 1e-12 relative; DBL_MAX: no record yet, nothing can be retired
-    __device__ __forceinline__ explicit Bar(const PairState &ps)
-        : rec_cnt((long long)ps.best_min_cnt), rec_score(ps.best_min_score < DBL_MAX ? ps.best_min_score * (1.0 + 1e-12) : DBL_MAX) {}
-    __device__ __forceinline__ bool armed() const { return rec_score < DBL_MAX; }
-    // the bail-out predicate above, for a hypothesis with `cnt` inliers and the sum `score` after `processed` of the pair's n records
-    __device__ __forceinline__ bool out(int n, double thr, int processed, double score, int cnt) const {
-        return ((long long)cnt + (long long)(n - processed) <= rec_cnt) && (score + thr * (double)(processed - cnt) >= rec_score);
-    }
+struct Bar : RecordBar { // (the predicates: mdrp_front.h)
+    __device__ __forceinline__ explicit Bar(const PairState &ps) : RecordBar((long long)ps.best_min_cnt, ps.best_min_score) {}
 };
 // Prune: the bail-out state of k_score's lanes
 struct Prune : Bar {
@@ -1144,7 +1143,7 @@ __global__ __launch_bounds__(CNT_THREADS, 4) void k_count(RunParams rp, const Pa
             if (lane == 0 && lv) { atomicAdd(&cand_stat[2 * pair], (unsigned long long)tot); atomicAdd(&cand_stat[2 * pair + 1], (unsigned long long)lv * (unsigned long long)n); }
         }
         if (cand_out && live) cand_out[i] = cnd;
-        const bool surv = live && ((long long)cnd > bar.rec_cnt || thr * (double)(n - cnd) < bar.rec_score); // else: its slot keeps k_solve's -2
+        const bool surv = live && !bar.retires(n, thr, cnd); // else: its slot keeps k_solve's -2
         const unsigned long long ball = __ballot(surv);
         if (ball) {
             int base = 0;
@@ -1417,6 +1416,9 @@ __global__ __launch_bounds__(SCORE_THREADS, MDRP_SCORE_MINWAVES) void k_score(Ru
                                                          int32_t *__restrict__ totals) {
     extern __shared__ double tile[]; // TILE_PTS * PT_STRIDE doubles, then TILE_PTS float4 (fp32 coordinates)
     float4 *tile32 = reinterpret_cast<float4 *>(tile + TILE_PTS * PT_STRIDE);
+    // In calls of more than SCORE_WAVE_MAX_PAIRS pairs this kernel sweeps a run's first chunk, beside the second chunk's solver: at equal priority
+    // its wavefronts get a quarter of the issue slots of a SIMD they share with three solver wavefronts.  Restored before the end.
+    __builtin_amdgcn_s_setprio(3);
     const int total = totals[1];
     const int tid = threadIdx.x;
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
@@ -1457,6 +1459,7 @@ __global__ __launch_bounds__(SCORE_THREADS, MDRP_SCORE_MINWAVES) void k_score(Ru
     }
     if (live) write_slot(slot_score, slot_inl, item.slot_base + item.slot, pr.dead, score, cnt, n, thr);
     } // item loop
+    __builtin_amdgcn_s_setprio(0);
 }
 
 // ------------------------------------------------------------------------------------------------ score, one wavefront per hypothesis
@@ -1540,13 +1543,17 @@ constexpr int SPLIT_WAVES = SPLIT_THREADS / 64;
 constexpr int SPLIT_HYP = 64;                        // hypotheses per workgroup
 constexpr int SPLIT_Q = 8;                           // records per wavefront and step
 constexpr int SPLIT_STEP = SPLIT_WAVES * SPLIT_Q;    // records per step
+// static LDS of a split-sweep workgroup (the arrays of score_split_items) and of a k_count workgroup (two A-fragment tiles): what the host reckons with
+constexpr size_t SPLIT_LDS_BYTES = 2 * SPLIT_WAVES * SPLIT_Q * (PT_STRIDE * sizeof(double) + sizeof(float4)) + 2 * SPLIT_STEP * SPLIT_HYP * sizeof(double) +
+                                   2 * SPLIT_WAVES * SPLIT_HYP * sizeof(int32_t) + 2 * sizeof(unsigned long long);
+constexpr size_t CNT_LDS_BYTES = 2 * 16 * 64 * sizeof(uint4);
 static_assert(128 % SPLIT_STEP == 0, "the bail-out positions (every 128 records) must be step boundaries");
-template <bool POSE, bool RAWF = false>
-__global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_split(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ pts,
-                                                               const Model *__restrict__ models, const uint32_t *__restrict__ tags /*sorted: k_sort_tags*/,
-                                                               const int32_t *__restrict__ model_count, double *__restrict__ slot_score,
-                                                               int32_t *__restrict__ slot_inl, const int32_t *__restrict__ plan /*k_plan, SPLIT_HYP per workgroup*/,
-                                                               const int32_t *__restrict__ totals) {
+template <bool POSE, bool RAWF>
+__device__ __forceinline__ void score_split_items(const RunParams &rp, const PairState *__restrict__ st, const double *__restrict__ pts,
+                                                  const Model *__restrict__ models, const uint32_t *__restrict__ tags /*sorted: k_sort_tags*/,
+                                                  const int32_t *__restrict__ model_count, double *__restrict__ slot_score,
+                                                  int32_t *__restrict__ slot_inl, const int32_t *__restrict__ plan /*k_plan, SPLIT_HYP per workgroup*/,
+                                                  const int32_t *__restrict__ totals) {
     __shared__ double s_rec[2][SPLIT_WAVES][SPLIT_Q * PT_STRIDE]; // each wavefront's records of a step
     __shared__ float4 s_rec32[2][SPLIT_WAVES][SPLIT_Q];           // their fp32 coordinates (store_rec32 layout)
     __shared__ double s_r2[2][SPLIT_STEP][SPLIT_HYP];             // [record of the step][hypothesis]: r^2 of an inlier, else +0
@@ -1668,6 +1675,136 @@ __global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_sp
         }
         if (wave == 0 && live) write_slot(slot_score, slot_inl, item.slot_base + item.slot, dead, score, cnt, n, thr);
     } // item loop
+}
+template <bool POSE, bool RAWF = false>
+__global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_score_split(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ pts,
+                                                               const Model *__restrict__ models, const uint32_t *__restrict__ tags,
+                                                               const int32_t *__restrict__ model_count, double *__restrict__ slot_score,
+                                                               int32_t *__restrict__ slot_inl, const int32_t *__restrict__ plan,
+                                                               const int32_t *__restrict__ totals) {
+    score_split_items<POSE, RAWF>(rp, st, pts, models, tags, model_count, slot_score, slot_inl, plan, totals);
+}
+
+// ------------------------------------------------------------------------------------------------ first chunk: prefix retirement
+// A run's first chunk has no record to retire against, and scoring all of it exactly was 63 % of the step's exact evaluations — most of them for
+// hypotheses from samples with an outlier, which cannot change the trajectory once an earlier, better hypothesis is known.  So, behind the first
+// chunk's k_count (calls of more than SCORE_WAVE_MAX_PAIRS pairs, 3-point estimators: Pass::front, mdrp_capi.hip):
+//   k_first_pick    one workgroup per pair: the `pick` hypotheses with the highest candidate density (ties: the earliest slots) and the pair's
+//                   earliest hypothesis go on the picked list P, every other one on the rest list — both keep k_count's keys
+//   k_first_score   P through k_sort_tags / k_plan / the split sweep (score_split_items: k_score_split's body, at raised wave priority)
+//   k_first_filter  one workgroup per pair: a hypothesis of the rest list that the records P reaches at STRICTLY EARLIER iterations retire
+//                   (prefix_bar / RecordBar::retires, mdrp_front.h — the test k_count applies against a chunk-start bar) keeps k_solve's -2;
+//                   the others go back on the survivor list, with their keys, for the usual sort / plan / k_score
+// Exact: the true running records at an iteration are at least as good as those of any subset of the hypotheses before it, and k_scan skips -2
+// slots.  The candidate count is taken from the key (cand_of_key: an upper bound, at most n / 64 above k_count's count).  NaN-model slots (-3) are
+// on no list.  All three run beside the second chunk's solver, hence the wave priority; each restores it before it ends.
+constexpr int FIRST_THREADS = 256;
+constexpr int FIRST_PICK_MAX = 64; // (and the earliest hypothesis: at most FIRST_PICK_MAX + 1 entries of P)
+MDRP_GLOBAL __launch_bounds__(FIRST_THREADS) void k_first_pick(RunParams rp, const PairState *__restrict__ st, const int32_t *__restrict__ surv_count,
+                                                              const uint32_t *__restrict__ tags_in /*k_count's survivors: slot | key << 24*/, int pick,
+                                                              uint32_t *__restrict__ tags_pick, int32_t *__restrict__ pick_count /*[batch]*/,
+                                                              uint32_t *__restrict__ tags_rest, int32_t *__restrict__ rest_count /*[2 batch], stride 2*/) {
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    if (!st[pair].active) return;
+    __builtin_amdgcn_s_setprio(3);
+    __shared__ int s_hist[256];
+    __shared__ int s_key, s_need, s_prefix, s_first, s_np, s_nr;
+    const int cnt = surv_count[pair];
+    const size_t slot_base = (size_t)pair * rp.slot_stride;
+    const uint32_t *src = tags_in + slot_base;
+    // the key T at which the picked set is full: every hypothesis above it is picked, s_need of those at it
+    s_hist[tid] = 0;
+    if (tid == 0) { s_first = 0x7FFFFFFF; s_np = 0; s_nr = 0; }
+    __syncthreads();
+    for (int i = tid; i < cnt; i += FIRST_THREADS) {
+        const uint32_t t = src[i];
+        atomicAdd(&s_hist[min(t >> 24, (uint32_t)PROBE_PTS)], 1);
+        atomicMin(&s_first, (int)(t & 0xFFFFFFu));
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int key = -1, above = 0;
+        if (cnt > pick)
+            for (key = PROBE_PTS; key > 0 && above + s_hist[key] < pick; --key) above += s_hist[key];
+        s_key = key; s_need = pick - above; s_prefix = 0;
+    }
+    __syncthreads();
+    const int key_t = s_key;
+    // ... and of those at T the s_need earliest: the slot S below which (inclusive) there are exactly that many, eight bits of it per round
+    for (int shift = 16; shift >= 0 && key_t >= 0; shift -= 8) {
+        s_hist[tid] = 0;
+        __syncthreads();
+        const int prefix = s_prefix;
+        for (int i = tid; i < cnt; i += FIRST_THREADS) {
+            const uint32_t t = src[i], slot = t & 0xFFFFFFu;
+            if ((int)min(t >> 24, (uint32_t)PROBE_PTS) == key_t && (int)(slot >> (shift + 8)) == prefix) atomicAdd(&s_hist[(slot >> shift) & 255u], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int b = 0, acc = 0;
+            for (; b < 255 && acc + s_hist[b] < s_need; ++b) acc += s_hist[b];
+            s_need -= acc; s_prefix = (prefix << 8) | b;
+        }
+        __syncthreads();
+    }
+    const uint32_t slot_s = (uint32_t)s_prefix, first = (uint32_t)s_first;
+    uint32_t *dp = tags_pick + slot_base, *dr = tags_rest + slot_base;
+    for (int i = tid; i < cnt; i += FIRST_THREADS) {
+        const uint32_t t = src[i], slot = t & 0xFFFFFFu;
+        const int key = (int)min(t >> 24, (uint32_t)PROBE_PTS);
+        if (key > key_t || (key == key_t && slot <= slot_s) || slot == first) dp[atomicAdd(&s_np, 1)] = t;
+        else dr[atomicAdd(&s_nr, 1)] = t;
+    }
+    __syncthreads();
+    if (tid == 0) { pick_count[pair] = s_np; rest_count[2 * pair] = s_nr; }
+    __builtin_amdgcn_s_setprio(0);
+}
+
+template <bool POSE, bool RAWF = false>
+__global__ __launch_bounds__(SPLIT_THREADS, MDRP_SCORE_MINWAVES) void k_first_score(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ pts,
+                                                               const Model *__restrict__ models, const uint32_t *__restrict__ tags,
+                                                               const int32_t *__restrict__ model_count, double *__restrict__ slot_score,
+                                                               int32_t *__restrict__ slot_inl, const int32_t *__restrict__ plan,
+                                                               const int32_t *__restrict__ totals) {
+    __builtin_amdgcn_s_setprio(3);
+    score_split_items<POSE, RAWF>(rp, st, pts, models, tags, model_count, slot_score, slot_inl, plan, totals);
+    __builtin_amdgcn_s_setprio(0);
+}
+
+MDRP_GLOBAL __launch_bounds__(FIRST_THREADS) void k_first_filter(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ slot_score,
+                                                                const int32_t *__restrict__ slot_inl, const uint32_t *__restrict__ tags_pick,
+                                                                const int32_t *__restrict__ pick_count, const uint32_t *__restrict__ tags_rest,
+                                                                const int32_t *__restrict__ rest_count /*stride 2*/, uint32_t *__restrict__ tags_out,
+                                                                int32_t *__restrict__ surv_count, unsigned long long *__restrict__ evals) {
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    const PairState &ps = st[pair];
+    if (!ps.active) return;
+    __builtin_amdgcn_s_setprio(3);
+    __shared__ int32_t s_iter[FIRST_PICK_MAX + 1], s_cnt[FIRST_PICK_MAX + 1];
+    __shared__ double s_score[FIRST_PICK_MAX + 1];
+    __shared__ int s_kept;
+    const int n = ps.n, np = min(pick_count[pair], FIRST_PICK_MAX + 1), nr = rest_count[2 * pair];
+    const double thr = ps.sq_thr;
+    const size_t slot_base = (size_t)pair * rp.slot_stride;
+    if (tid < np) {
+        const uint32_t slot = tags_pick[slot_base + tid] & 0xFFFFFFu;
+        s_iter[tid] = (int32_t)(slot / (uint32_t)rp.mps);
+        s_cnt[tid] = slot_inl[slot_base + slot];
+        s_score[tid] = slot_score[slot_base + slot];
+    }
+    if (tid == 0) s_kept = 0;
+    __syncthreads();
+    for (int i = tid; i < nr; i += FIRST_THREADS) {
+        const uint32_t t = tags_rest[slot_base + i], slot = t & 0xFFFFFFu;
+        const RecordBar bar = prefix_bar(s_iter, s_cnt, s_score, np, (int)(slot / (uint32_t)rp.mps));
+        if (!bar.retires(n, thr, cand_of_key((int)min(t >> 24, (uint32_t)PROBE_PTS), n))) tags_out[slot_base + atomicAdd(&s_kept, 1)] = t; // else: its slot keeps k_solve's -2
+    }
+    __syncthreads();
+    if (tid == 0) {
+        surv_count[pair] = s_kept;
+        if (evals) atomicAdd(evals, (unsigned long long)np * (unsigned long long)n); // (k_scan adds the survivors of the second sweep)
+    }
+    __builtin_amdgcn_s_setprio(0);
 }
 
 // ------------------------------------------------------------------------------------------------ scan

@@ -60,7 +60,8 @@ inline bool parse_chunks(const char *spec_or_null, Lead &lead) {
 // first super-chunk is split into a short chunk (128 iterations) that establishes the records and the rest, whose
 // hypotheses are retired against those records by k_count (MFMA) and k_bound (fp32) unless they might break one.
 // Beyond the certain range a super-chunk is one chunk sized by the largest remaining dynamic_max_iter.
-// The first chunk has no records to retire anything against, so it is scored exactly in full: keep it short.  Every later chunk goes
+// The first chunk has no records of a chunk before it to retire anything against (what the 3-point estimators retire inside it, by the prefix
+// records of a few hypotheses scored first, is first_pick's business below): keep it short.  Every later chunk goes
 // through k_count / k_bound against the records of the chunks before it.  Measured on the benchmark shape: "128" 84.5 k pairs/s, "64" 82 k,
 // "256" 82.5 k, "512" 82 k, "256,768" 79 k (every chunk costs ~10 launches and a solver hand-over).  The 7-point estimator gets a second leading
 // chunk: at 50 % outliers one sample in 128 is outlier-free, so the records after 128 iterations are often those of a poor model and the rest of
@@ -152,6 +153,34 @@ inline int pairs_per_pass(size_t free_bytes, size_t per_pair, int batch) {
 // memory that happens to be free — a pair must get the same record whatever pass it falls into.
 inline int lo_lanes(int batch_call, int n_max) { return (batch_call >= 128 && n_max < 4096) ? 64 : 256; }
 inline int final_lanes(int batch_call) { return batch_call >= 4096 ? 64 : 256; }
+
+// The first chunk's prefix retirement (k_first_pick / k_first_score / k_first_filter, mdrp_kernels.h): hypotheses picked per pair, 0 = the stage is
+// off and the whole chunk goes to the exact sweep as before.  On for the 3-point estimators in calls that do not score by wavefront (`wave_max_pairs`:
+// SCORE_WAVE_MAX_PAIRS); the 5-, 6- and 7-point estimators keep their front.  `knob`: MDRP_FIRST_PICK, or negative where it is not set.
+constexpr int FIRST_PICK = 48, FIRST_PICK_LIMIT = 64;
+inline int first_pick(int kind, int batch_call, int wave_max_pairs, int knob) {
+    if (kind > MDRP_VARYING_FOCAL || batch_call <= wave_max_pairs) return 0;
+    return knob < 0 ? FIRST_PICK : std::min(knob, FIRST_PICK_LIMIT);
+}
+
+// The solver beside a first chunk's sweeps.  A solver wavefront shares nothing with its neighbours, so one-wavefront workgroups refill a freed slot at
+// once and the kernel alone is a quarter shorter (mdrp_kernels.h, k_solve) — but the 3-point calibrated solvers hold 152 VGPRs, three wavefronts per
+// SIMD, and a 128-VGPR sweep wavefront finds no room beside three of them.  What a launch can still decide is its dynamic LDS: workgroups that each
+// reserve `bytes` of it (never touched) fit floor(lds_per_cu / bytes) to a CU.  The rule: the bytes per solver workgroup at which exactly 4 R of them
+// fit (R per SIMD) while `keep_free` bytes of the CU's LDS stay out of their reach — or 0, "uncapped", where R is not positive or no such size
+// exists.  Both conditions at once need  lds / (4 R + 1) < bytes <= (lds - keep_free) / (4 R),  that is keep_free < lds / (4 R + 1): a solver capped
+// through LDS takes at least 4 R / (4 R + 1) of it.  On 160 KiB and R = 2 that leaves 17.7 KiB, less than any sweep workgroup of the front needs
+// (32 - 39 KiB), so with the sweeps' LDS kept free the rule answers "uncapped" there and the long solver keeps its four-wavefront workgroups;
+// MDRP_SOLVE_RESIDENT = R asks for the cap without keeping anything free (DESIGN.md 4 has what that measures).
+constexpr size_t LDS_GRANULE = 2560; // sizes are rounded down to a multiple of both LDS allocation granularities (512 B; 1280 B on parts with 160 KiB)
+inline size_t solver_reservation(size_t lds_per_cu, int resident_per_simd, size_t keep_free) {
+    if (resident_per_simd <= 0 || keep_free >= lds_per_cu) return 0;
+    const size_t wgs = 4 * (size_t)resident_per_simd;
+    const size_t bytes = (lds_per_cu - keep_free) / wgs / LDS_GRANULE * LDS_GRANULE;
+    if (bytes == 0 || (wgs + 1) * bytes <= lds_per_cu) return 0; // one more would fit: no cap at this size
+    return bytes;
+}
+constexpr int SOLVE_RESIDENT = 2; // R of the 3-point calibrated solvers where the first chunk's prefix retirement is on
 
 // Bounded waits of the fused tail (k_gate, k_final), microseconds: far beyond anything a healthy run needs (the LO queue of 1024 pairs is empty
 // after ~1 ms), scaled with the problem size (one LO problem is ~0.4 ms at N = 2000 and grows linearly with N: 4 ms at 5000 on one wavefront) and
