@@ -309,6 +309,57 @@ typedef struct {
 } mdrp_replay;
 int mdrp_replay_slots(mdrp_handle *h, const mdrp_ransac_opt *ropt, mdrp_replay *io);
 
+/* The pick and the filter of a run's first chunk on caller-given lists (within ABI 0.6): k_first_pick, then k_first_filter, one workgroup per pair,
+ * with the scheduler's buffer roles and strides and nothing solved or scored between them — the caller's slot tables stand in for k_first_score.
+ * Four slots per iteration (the 3-point estimators): a hypothesis in slot s belongs to iteration s / 4.
+ * A pair's survivor list holds count tags  slot | key << 24  (k_count's candidate density key, read as min(key, 64)), every slot at most once.
+ *   pick    the `pick` hypotheses with the highest key, ties by the lowest slot, and the list's lowest slot go on the picked list P (at most
+ *           pick + 1 entries); every other one on the rest list.  Both keep the tags.
+ *   filter  a hypothesis of the rest list is retired when the records of P's entries at STRICTLY EARLIER iterations — (max count, min score) over
+ *           slot_inl / slot_score at the picked slots with a count >= 0 — rule it out with cand = (key * n) >> 6:
+ *           cand <= rec_cnt  and  sq_thr (n - cand) >= rec_score (1 + 1e-12).  The others go on the kept list.  evals: += |P| * n per active pair.
+ * Lists are filled through atomics: their order is not defined.  A pair with active == 0 leaves every output as the caller initialised it.
+ * Host memory throughout.  MDRP_ERR_INVALID, before any device work: batch < 1; slots < 4, no multiple of 4 or above 2^24; pick outside 1..64; a
+ * NULL buffer; a negative n; a list longer than the table; a tag whose slot is outside the table.  tests/test_gpu_first_front.py pins both kernels
+ * to the restatement in tests/first_front_ref.py. */
+typedef struct {
+    /* in */
+    int32_t batch, slots;            /* pairs; slots per pair (4 per iteration) */
+    int32_t pick, pad_;
+    const int32_t *n;                /* [batch] correspondences */
+    const int32_t *active;           /* [batch] */
+    const double *sq_thr;            /* [batch] */
+    const int32_t *count;            /* [batch] length of the survivor list */
+    const uint32_t *tags;            /* [batch][slots]: the pair's first count[p] entries */
+    const double *slot_score;        /* [batch][slots]: read at the picked slots only */
+    const int32_t *slot_inl;
+    /* in and out */
+    uint32_t *tags_pick;             /* [batch][slots]: the first pick_count[p] entries */
+    uint32_t *tags_rest;             /* [batch][slots]: the first rest_count[2 p] entries */
+    uint32_t *tags_out;              /* [batch][slots]: the kept list, surv_count[p] entries */
+    int32_t *pick_count;             /* [batch] */
+    int32_t *rest_count;             /* [2 batch]: pair p's at 2 p; the odd entries are not touched */
+    int32_t *surv_count;             /* [batch] */
+    /* out */
+    uint64_t *evals;                 /* [1] */
+} mdrp_front_tables;
+int mdrp_front_lists(mdrp_handle *h, mdrp_front_tables *io);
+
+/* The train of a run's FIRST chunk on ONE pair with caller-given models (within ABI 0.6), as the scheduler strings it together for the 3-point
+ * estimators in calls of more than 128 pairs: k_count in one launch — without records, or against (rec_cnt, rec_score) the way a prior arms it;
+ * rec_score >= DBL_MAX: no record — then the prefix retirement through the function the estimator launches it with (k_first_pick, sort, plan,
+ * k_first_score, k_first_filter), then sort, plan and k_score on what is left.  Models in slot order, four per iteration.  A model with a NaN in q
+ * or t is what the solver's NaN model is: slot count -3, on no list.  kind: MDRP_CALIB, MDRP_SHARED_FOCAL or MDRP_VARYING_FOCAL; pick in 1..64.
+ *   scores, counts [num_models]  the slots: a retired model keeps count -2 (and score DBL_MAX)
+ *   left_at [num_models]         0 on no list (a NaN model), 1 retired by k_count, 4 picked (scored by k_first_score), 5 retired by
+ *                                k_first_filter, 3 kept by it and scored by k_score
+ *   info [5]                     survivors of the count | entries of P | of the rest list | of the kept list | hypotheses k_first_filter
+ *                                reports as evaluated (its evals increment / n)
+ * Host memory.  tests/test_gpu_first_front.py. */
+int mdrp_front_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2, int n,
+                      double sq_threshold, uint64_t rec_cnt, double rec_score, int pick, double *scores, int32_t *counts, int32_t *left_at,
+                      int32_t *info);
+
 /* Hybrid LM refinement of `count` models, each over the correspondences of ONE pair (refine_monodepth_*relpose
  * @0x261030/@0x2592e0/@0x260fa0).  Host memory.  models in/out.  For MDRP_RELPOSE_5PT / MDRP_FUNDAMENTAL_7PT: the Sampson-only
  * refine_relpose @0x258f50 / refine_fundamental @0x2590d0 (d1, d2, scale_reproj, weight_sampson, estimate_shift ignored). */

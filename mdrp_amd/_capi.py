@@ -26,7 +26,7 @@ EXPORTS = (
     "mdrp_refine_batch", "mdrp_refine_batch_async",
     "mdrp_gather_image_pairs", "mdrp_estimate_image_pairs_async",
     "mdrp_estimate_batch_prior", "mdrp_estimate_batch_prior_async",
-    "mdrp_retire_models", "mdrp_replay_slots",
+    "mdrp_retire_models", "mdrp_replay_slots", "mdrp_front_lists", "mdrp_front_models",
     "mdrp_estimate_batch_ranked", "mdrp_estimate_batch_ranked_async", "mdrp_prosac_samples", "mdrp_rank_scores",
     "mdrp_gather_matches_ranked", "mdrp_estimate_matches_ranked_async", "mdrp_gather_image_pairs_ranked", "mdrp_estimate_image_pairs_ranked_async",
 )
@@ -113,6 +113,18 @@ class Replay(C.Structure):
 
 
 assert REPLAY_STATE_DTYPE.itemsize == 176 and REPLAY_TRIGGER_DTYPE.itemsize == 32 and C.sizeof(Replay) == 176
+
+
+class FrontTables(C.Structure):
+    """mdrp_front_tables (include/mdrp.h): the first chunk's pick and filter on caller-given lists"""
+    _fields_ = [("batch", C.c_int32), ("slots", C.c_int32), ("pick", C.c_int32), ("pad_", C.c_int32), ("n", C.c_void_p), ("active", C.c_void_p),
+                ("sq_thr", C.c_void_p), ("count", C.c_void_p), ("tags", C.c_void_p), ("slot_score", C.c_void_p), ("slot_inl", C.c_void_p),
+                ("tags_pick", C.c_void_p), ("tags_rest", C.c_void_p), ("tags_out", C.c_void_p), ("pick_count", C.c_void_p), ("rest_count", C.c_void_p),
+                ("surv_count", C.c_void_p), ("evals", C.c_void_p)]
+
+
+assert C.sizeof(FrontTables) == 128
+FRONT_PICK_LIMIT = 64  # mdrp_schedule.h sched::FIRST_PICK_LIMIT
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -204,6 +216,9 @@ def load_library():
                                                vp, vp, vp, vp, vp]
         if hasattr(lib, "mdrp_replay_slots"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.replay_slots raises)
             lib.mdrp_replay_slots.argtypes = [vp, C.POINTER(RansacOpt), C.POINTER(Replay)]
+        if hasattr(lib, "mdrp_front_lists"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.front_lists / front_models raise)
+            lib.mdrp_front_lists.argtypes = [vp, C.POINTER(FrontTables)]
+            lib.mdrp_front_models.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_uint64, C.c_double, C.c_int, vp, vp, vp, vp]
         if hasattr(lib, "mdrp_solver_residency"):  # (an older ABI-0.6 library through MDRP_LIB has none: solver_residency raises)
             lib.mdrp_solver_residency.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         _lib = lib
@@ -862,6 +877,60 @@ class Handle:
         return dict(states=states, triggers=[trig[p, :ntr[-1, p]] for p in range(batch)], n_triggers=ntr, scan_cnt=scnt, scan_score=ssc, scan_inst=inst,
                     prefix=plan[:batch + 1], begin=plan[batch + 1:2 * batch + 1], end=plan[2 * batch + 1:3 * batch + 1], total=int(plan[3 * batch + 1]),
                     n_active=int(nact[0]), max_needed=int(need[0]), checkpoints=ck)
+
+    def front_lists(self, n, sq_thr, active, lists, pick, slot_score, slot_inl, fill=None):
+        """k_first_pick -> k_first_filter on caller-given lists (mdrp_front_lists), one pair per entry of `lists`: uint32 arrays of tags
+        slot | key << 24.  slot_score, slot_inl: [batch][slots].  fill: dict of initial values of the outputs (tag lists: uint32, counters: int32),
+        which an inactive pair keeps.  Returns dict(picked, rest, kept: one uint32 array per pair, in the kernels' order; pick_count, rest_count
+        [2 batch], surv_count; evals; tags_pick, tags_rest, tags_out: the whole buffers)"""
+        if not hasattr(self._lib, "mdrp_front_lists"):
+            raise MdrpError(f"{LIB_PATH} has no mdrp_front_lists: rebuild (mdrp_amd/build.py)")
+        slot_score = np.ascontiguousarray(slot_score, dtype=np.float64)
+        slot_inl = np.ascontiguousarray(slot_inl, dtype=np.int32)
+        batch, slots = slot_inl.shape
+        if slot_score.shape != (batch, slots) or len(lists) != batch:
+            raise ValueError("front_lists: one list per pair and two tables [batch][slots]")
+        n = np.ascontiguousarray(n, dtype=np.int32).reshape(batch)
+        thr = np.ascontiguousarray(sq_thr, dtype=np.float64).reshape(batch)
+        act = np.ascontiguousarray(active, dtype=np.int32).reshape(batch)
+        count = np.array([len(t) for t in lists], dtype=np.int32)
+        if count.max(initial=0) > slots:
+            raise MdrpError("front_lists: a list longer than the table")
+        tags = np.zeros((batch, slots), dtype=np.uint32)
+        for p, t in enumerate(lists):
+            tags[p, :len(t)] = t
+        fill = fill or {}
+        bufs = {k: np.full((batch, slots), fill.get(k, 0xFFFFFFFF), dtype=np.uint32) for k in ("tags_pick", "tags_rest", "tags_out")}
+        cnts = {k: np.full(batch * w, fill.get(k, -7), dtype=np.int32) for k, w in (("pick_count", 1), ("rest_count", 2), ("surv_count", 1))}
+        evals = np.zeros(1, dtype=np.uint64)
+        io = FrontTables(batch, slots, int(pick), 0, _ptr(n), _ptr(act), _ptr(thr), _ptr(count), _ptr(tags), _ptr(slot_score), _ptr(slot_inl),
+                         _ptr(bufs["tags_pick"]), _ptr(bufs["tags_rest"]), _ptr(bufs["tags_out"]), _ptr(cnts["pick_count"]), _ptr(cnts["rest_count"]),
+                         _ptr(cnts["surv_count"]), _ptr(evals))
+        _check(self._lib, self._lib.mdrp_front_lists(self._h, C.byref(io)))
+
+        def cut(buf, lens):
+            return [buf[p, :max(0, min(int(lens[p]), slots))].copy() for p in range(batch)]
+        return dict(picked=cut(bufs["tags_pick"], cnts["pick_count"]), rest=cut(bufs["tags_rest"], cnts["rest_count"][0::2]),
+                    kept=cut(bufs["tags_out"], cnts["surv_count"]), evals=int(evals[0]), **bufs, **cnts)
+
+    def front_models(self, kind, models, x1, x2, sq_threshold, pick, rec_cnt=0, rec_score=None):
+        """the first chunk's train on one pair (mdrp_front_models): k_count (armed with (rec_cnt, rec_score) unless rec_score is None or inf) -> the
+        prefix retirement -> k_score.  Returns (scores, counts, left_at, info): the slots (count -2: retired, -3: a NaN model), 0 / 1 / 4 / 5 / 3 =
+        on no list / retired by k_count / picked / retired by k_first_filter / kept and scored, info = (survivors of the count, entries of P, of
+        the rest list, of the kept list, hypotheses the filter reports as evaluated)"""
+        if not hasattr(self._lib, "mdrp_front_models"):
+            raise MdrpError(f"{LIB_PATH} has no mdrp_front_models: rebuild (mdrp_amd/build.py)")
+        models = np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        scores = np.zeros(len(models))
+        counts = np.zeros(len(models), dtype=np.int32)
+        left_at = np.zeros(len(models), dtype=np.int32)
+        info = np.zeros(5, dtype=np.int32)
+        score = np.finfo(np.float64).max if rec_score is None or not rec_score < np.finfo(np.float64).max else float(rec_score)
+        _check(self._lib, self._lib.mdrp_front_models(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1), float(sq_threshold),
+                                                      int(rec_cnt), score, int(pick), _ptr(scores), _ptr(counts), _ptr(left_at), _ptr(info)))
+        return scores, counts, left_at, info
 
     def score_models_device(self, kind, models_ptr, num_models, x1_ptr, x2_ptr, n, sq_threshold, scores_ptr, counts_ptr):
         _check(self._lib, self._lib.mdrp_score_models(self._h, int(kind), MEM_DEVICE, C.c_void_p(models_ptr), int(num_models),

@@ -451,6 +451,31 @@ struct ChunkView {
 // what goes on to a chunk's exact sweep: k_count's survivors, or k_bound's
 struct Survivors { const uint32_t *tags; const int32_t *count; };
 
+// A run's first chunk in calls of more than SCORE_WAVE_MAX_PAIRS pairs (3-point estimators): prefix retirement (mdrp_kernels.h, "first chunk").
+// In: k_count's survivors — every live hypothesis, or what a prior's records left.  The picked ones are scored here; what their prefix records
+// do not retire is back on (tags_v, surv1) for the exact sweep.  The picked list uses the chunk's solver-order tag list (k_count has consumed it), the
+// rest list the other parity's sorted list (free until the next chunk's count), their counters surv2 and und_count (idle in a first chunk).
+// The scheduler (Pass::front) and mdrp_front_models both launch through here.
+int launch_front(mdrp_handle *h, hipStream_t s, int kind, const ChunkView &v, int first_pick, int32_t *plan, int32_t *totals,
+                 unsigned long long *evals, Survivors &sv) {
+    uint32_t *tags_pick = v.tags, *tags_rest = v.tags_sorted_other;
+    hipLaunchKernelGGL(k_first_pick, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, sv.count, sv.tags, first_pick, tags_pick, v.surv2, tags_rest, v.und_count);
+    hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, v.surv2, tags_pick, v.tags_sorted);
+    hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.model_count, plan, totals, SPLIT_HYP);
+    hipEvent_t f0, f1;
+    if (int rc = get_events(h, &f0, &f1, 0)) return rc;
+    HIPCHK(hipEventRecord(f0, s));
+    const long long ub = 2ll * v.pc; // at most FIRST_PICK_MAX + 1 hypotheses per pair, in two density classes: two workgroups of SPLIT_HYP
+    MDRP_SWEEP_DISPATCH(k_first_score, kind, dim3((unsigned)std::min(ub, (long long)h->num_cu * 32)), dim3(SPLIT_THREADS), 0, s, v.r, v.st, v.pts, v.models,
+                        v.tags_sorted, v.model_count, v.slot_score, v.slot_inl, plan, totals);
+    HIPCHK(hipEventRecord(f1, s));
+    h->sweep_launches++;
+    hipLaunchKernelGGL(k_first_filter, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, v.slot_score, v.slot_inl, tags_pick, v.surv2, tags_rest, v.und_count,
+                       v.tags_v, v.surv1, evals);
+    sv = Survivors{v.tags_v, v.surv1};
+    return MDRP_OK;
+}
+
 // A pass and the stages run_pass strings together.  Stages only issue work (launches, copies, memsets, events) on the stream they name; who waits for
 // whom is run_pass's business.
 struct Pass : PassIn {
@@ -769,29 +794,11 @@ struct Pass : PassIn {
         return MDRP_OK;
     }
 
-    // A run's first chunk in calls of more than SCORE_WAVE_MAX_PAIRS pairs (3-point estimators): prefix retirement (mdrp_kernels.h, "first chunk").
-    // In: k_count's survivors — every live hypothesis, or what a prior's records left.  The picked ones are scored here; what their prefix records
-    // do not retire is back on (tags_v, surv1) for score().  The picked list uses the chunk's solver-order tag list (k_count has consumed it), the
-    // rest list the other parity's sorted list (free until the next chunk's count), their counters surv2 and und_count (idle in a first chunk).
+    // A run's first chunk in calls of more than SCORE_WAVE_MAX_PAIRS pairs (3-point estimators): prefix retirement (launch_front, above)
     int front(const ChunkView &v, Survivors &sv) {
         if (!(v.first_of_run && first_pick > 0)) return MDRP_OK;
-        uint32_t *tags_pick = v.tags, *tags_rest = v.tags_sorted_other;
         int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * (size_t)batch + 2;
-        hipLaunchKernelGGL(k_first_pick, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, sv.count, sv.tags, first_pick, tags_pick, v.surv2, tags_rest, v.und_count);
-        hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, v.surv2, tags_pick, v.tags_sorted);
-        hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.model_count, plan, totals, SPLIT_HYP);
-        hipEvent_t f0, f1;
-        if (int rc = get_events(h, &f0, &f1, 0)) return rc;
-        HIPCHK(hipEventRecord(f0, s));
-        const long long ub = 2ll * v.pc; // at most FIRST_PICK_MAX + 1 hypotheses per pair, in two density classes: two workgroups of SPLIT_HYP
-        MDRP_SWEEP_DISPATCH(k_first_score, kind, dim3((unsigned)std::min(ub, (long long)h->num_cu * 32)), dim3(SPLIT_THREADS), 0, s, v.r, v.st, v.pts, v.models,
-                            v.tags_sorted, v.model_count, v.slot_score, v.slot_inl, plan, totals);
-        HIPCHK(hipEventRecord(f1, s));
-        h->sweep_launches++;
-        hipLaunchKernelGGL(k_first_filter, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, v.slot_score, v.slot_inl, tags_pick, v.surv2, tags_rest, v.und_count,
-                           v.tags_v, v.surv1, &cnt->progress.evals_sweep);
-        sv = Survivors{v.tags_v, v.surv1};
-        return MDRP_OK;
+        return launch_front(h, s, kind, v, first_pick, plan, totals, &cnt->progress.evals_sweep, sv);
     }
 
     // sort by candidate density, plan, exact fp64 sweep of the survivors between the events e0 and e1:
@@ -2198,15 +2205,15 @@ int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
 
 // The armed stage train of one chunk on one pair: Pass::count, Pass::bound and Pass::score launch for launch, with the scheduler's buffer roles
 // (undecided list in the chunk's sorted list, partial counts in the other parity's, k_count's survivors in tags_v, k_bound's back in tags).
-int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
-                       int n, double sq_threshold, uint64_t rec_cnt, double rec_score, const uint64_t *cand_stat_in, int flags,
-                       double *scores, int32_t *counts, int32_t *left_at, int32_t *info, uint64_t *cand_stat_out) {
+// front_pick > 0 (mdrp_front_models): the train of a run's FIRST chunk instead — one count launch, no bound, the prefix retirement between the
+// count and the sweep (launch_front), k_score.  Models with a NaN in their pose are then what k_solve's NaN model is: slot state -3, on no list.
+static int retire_train(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
+                        int n, double sq_threshold, uint64_t rec_cnt, double rec_score, const uint64_t *cand_stat_in, int flags, int front_pick,
+                        double *scores, int32_t *counts, int32_t *left_at, int32_t *info, uint64_t *cand_stat_out) {
     const int sweep = flags & (MDRP_RETIRE_SWEEP_SPLIT | MDRP_RETIRE_SWEEP_WAVE);
-    if (!h || num_models < 0 || num_models > 0xFFFFFF || n < 0 || kind < 0 || kind > 5 || !models || !cand_stat_in || !scores || !counts || !left_at ||
-        !info || !cand_stat_out || (flags & ~15) || sweep == (MDRP_RETIRE_SWEEP_SPLIT | MDRP_RETIRE_SWEEP_WAVE)) {
-        g_err = "invalid argument"; return MDRP_ERR_INVALID;
-    }
-    if (num_models == 0) return MDRP_OK;
+    const auto nan_pose = [](const mdrp_model &m) {
+        return m.q[0] != m.q[0] || m.q[1] != m.q[1] || m.q[2] != m.q[2] || m.q[3] != m.q[3] || m.t[0] != m.t[0] || m.t[1] != m.t[1] || m.t[2] != m.t[2];
+    };
     MDRP_ENTER(h);
     hipStream_t s = h->stream;
     const int nn = std::max(n, 1);
@@ -2226,15 +2233,25 @@ int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int n
     HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
-    if ((rc = upload_iota(s, h->tags[0].p, num_models))) return rc;
+    int listed = num_models;
     {   // every slot as k_solve leaves a live one: "no record" until an exact sweep writes it
         const std::vector<double> sc0(slots, DBL_MAX);
-        const std::vector<int32_t> in0(slots, -2);
+        std::vector<int32_t> in0(slots, -2);
+        std::vector<uint32_t> list(slots);
+        if (front_pick > 0) {
+            listed = 0;
+            for (int k = 0; k < num_models; ++k) {
+                if (nan_pose(models[k])) in0[k] = -3;
+                else list[listed++] = (uint32_t)k;
+            }
+        } else
+            for (int k = 0; k < num_models; ++k) list[k] = (uint32_t)k;
+        HIPCHK(hipMemcpyAsync(h->tags[0].p, list.data(), tag_bytes, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(h->slot_score.p, sc0.data(), sizeof(double) * slots, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(h->slot_inl.p, in0.data(), sizeof(int32_t) * slots, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s)); // (the vectors go out of scope)
     }
-    const int32_t counts2[2] = {num_models, 0};
+    const int32_t counts2[2] = {listed, 0};
     const unsigned long long cs_in[2] = {cand_stat_in[0], cand_stat_in[1]};
     HIPCHK(hipMemcpyAsync(h->model_count[0].p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->cand_stat.p, cs_in, sizeof cs_in, hipMemcpyHostToDevice, s));
@@ -2280,6 +2297,21 @@ int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int n
                             (unsigned long long *)nullptr);
         sv_tags = tags; sv_count = surv2;
     }
+    // ---- Pass::front
+    if (front_pick > 0) {
+        ChunkView v;
+        std::memset(&v, 0, sizeof v);
+        v.pc = 1; v.first_of_run = true; v.r = rp; v.st = st; v.pts = h->pts.as<double>(); v.models = h->models.as<Model>();
+        v.slot_score = h->slot_score.as<double>(); v.slot_inl = h->slot_inl.as<int32_t>(); v.model_count = model_count; v.surv1 = surv1; v.surv2 = surv2;
+        v.und_count = und_count; v.tags = tags; v.tags_sorted = tags_sorted; v.tags_sorted_other = h->tags_sorted[1].as<uint32_t>(); v.tags_v = tags_v;
+        Survivors sv{sv_tags, sv_count};
+        h->ev_used = 0; h->sweep_launches = 0;
+        if ((rc = h->counters.ensure(sizeof(Counters)))) return rc;
+        HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
+        int32_t *plan = h->plan.as<int32_t>();
+        if ((rc = launch_front(h, s, kind, v, front_pick, plan, plan + 2 * 1 + 2, &h->counters.as<Counters>()->progress.evals_sweep, sv))) return rc;
+        sv_tags = sv.tags; sv_count = sv.count;
+    }
     // ---- Pass::score
     {
         const bool wave = sweep == MDRP_RETIRE_SWEEP_WAVE, split = sweep == MDRP_RETIRE_SWEEP_SPLIT;
@@ -2318,6 +2350,23 @@ int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int n
     HIPCHK(hipMemcpyAsync(cs_out, h->cand_stat.p, sizeof cs_out, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const bool bound = (flags & MDRP_RETIRE_BOUND) != 0;
+    if (front_pick > 0) {
+        // the front's lists are where it left them: P in the solver-order list (list2), the rest list in the other parity's sorted list, the kept
+        // list back in tags_v (list1); their counters in surv2 (n2), und_count (n_und[0]) and surv1 (n1)
+        std::vector<uint32_t> rest(slots);
+        unsigned long long evals = 0;
+        HIPCHK(hipMemcpyAsync(rest.data(), h->tags_sorted[1].p, tag_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&evals, &h->counters.as<Counters>()->progress.evals_sweep, sizeof evals, hipMemcpyDeviceToHost, s));
+        if ((rc = finish_timing(h))) return rc;
+        const int np = n2, nr = n_und[0];
+        if (np < 0 || np > FIRST_PICK_MAX + 1 || nr < 0 || np + nr > listed || n1 < 0 || n1 > nr) { g_err = "front_models: list counts out of range"; return MDRP_ERR_INVALID; }
+        for (int k = 0; k < num_models; ++k) left_at[k] = nan_pose(models[k]) ? 0 : 1; // (NaN models were on no list)
+        for (int i = 0; i < nr; ++i) left_at[rest[i] & 0xFFFFFFu] = 5;
+        for (int i = 0; i < n1; ++i) left_at[list1[i] & 0xFFFFFFu] = 3;
+        for (int i = 0; i < np; ++i) left_at[list2[i] & 0xFFFFFFu] = 4;
+        info[0] = np + nr; info[1] = np; info[2] = nr; info[3] = n1; info[4] = (int32_t)(evals / (unsigned long long)std::max(n, 1));
+        return MDRP_OK;
+    }
     if (n1 < 0 || n1 > num_models || n2 < 0 || n2 > n1) { g_err = "retire_models: survivor counts out of range"; return MDRP_ERR_INVALID; }
     for (int k = 0; k < num_models; ++k) left_at[k] = 1;
     for (int i = 0; i < n1; ++i) left_at[list1[i] & 0xFFFFFFu] = bound ? 2 : 3;
@@ -2325,6 +2374,34 @@ int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int n
     info[0] = n_und[0]; info[1] = n1; info[2] = bound ? n2 : n1;
     cand_stat_out[0] = cs_out[0]; cand_stat_out[1] = cs_out[1];
     return MDRP_OK;
+}
+
+int mdrp_retire_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
+                       int n, double sq_threshold, uint64_t rec_cnt, double rec_score, const uint64_t *cand_stat_in, int flags,
+                       double *scores, int32_t *counts, int32_t *left_at, int32_t *info, uint64_t *cand_stat_out) {
+    const int sweep = flags & (MDRP_RETIRE_SWEEP_SPLIT | MDRP_RETIRE_SWEEP_WAVE);
+    if (!h || num_models < 0 || num_models > 0xFFFFFF || n < 0 || kind < 0 || kind > 5 || !models || !cand_stat_in || !scores || !counts || !left_at ||
+        !info || !cand_stat_out || (flags & ~15) || sweep == (MDRP_RETIRE_SWEEP_SPLIT | MDRP_RETIRE_SWEEP_WAVE)) {
+        g_err = "invalid argument"; return MDRP_ERR_INVALID;
+    }
+    if (num_models == 0) return MDRP_OK;
+    return retire_train(h, kind, models, num_models, x1, x2, n, sq_threshold, rec_cnt, rec_score, cand_stat_in, flags, 0, scores, counts, left_at, info,
+                        cand_stat_out);
+}
+
+// The first chunk's train on one pair (include/mdrp.h): retire_train with the front between the count and k_score.
+int mdrp_front_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2, int n,
+                      double sq_threshold, uint64_t rec_cnt, double rec_score, int pick, double *scores, int32_t *counts, int32_t *left_at,
+                      int32_t *info) {
+    if (!h || num_models < 0 || num_models > 0xFFFFFF || n < 0 || kind < MDRP_CALIB || kind > MDRP_VARYING_FOCAL || !models || !x1 || !x2 || !scores ||
+        !counts || !left_at || !info || pick < 1 || pick > sched::FIRST_PICK_LIMIT) {
+        g_err = "front_models: a 3-point estimator, pick in 1..64 and no NULL buffer"; return MDRP_ERR_INVALID;
+    }
+    if (num_models == 0) return MDRP_OK;
+    const uint64_t no_stat[2] = {0, 0};
+    uint64_t stat_out[2];
+    return retire_train(h, kind, models, num_models, x1, x2, n, sq_threshold, rec_cnt, rec_score, no_stat, MDRP_RETIRE_SWEEP_SCORE, pick, scores, counts,
+                        left_at, info, stat_out);
 }
 
 // The bookkeeping train of one super-chunk on caller-given slot tables: Pass::scan per chunk, Pass::lo's plan and Pass::walk launch for launch, with
@@ -2457,6 +2534,79 @@ int mdrp_replay_slots(mdrp_handle *h, const mdrp_ransac_opt *ro, mdrp_replay *io
     *io->n_active = pr.n_active; *io->max_needed = pr.max_needed;
     for (size_t p = 0; p < b; ++p) unstage(st_host[p], io->states[p]);
     for (size_t e = 0; e < ck_host.size(); ++e) unstage(ck_host[e], io->checkpoints[e]);
+    return MDRP_OK;
+}
+
+// k_first_pick and k_first_filter alone on caller-given survivor lists and slot tables, with Pass::front's buffer roles: the survivors and the kept
+// list share tags_v and their counters surv1 (the filter overwrites what the pick has consumed), P in the solver-order list with its counter in surv2,
+// the rest list in the other parity's sorted list with its counter at stride 2 in und_count.  k_first_score's part is played by the caller's tables.
+static_assert(FIRST_PICK_MAX == sched::FIRST_PICK_LIMIT, "k_first_filter's LDS tables hold what the scheduler may pick");
+int mdrp_front_lists(mdrp_handle *h, mdrp_front_tables *io) {
+    if (!h || !io) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    const int batch = io->batch, slots = io->slots;
+    const char *why = nullptr;
+    if (batch < 1 || slots < 4 || slots % 4 || slots > (1 << 24)) why = "front_lists: batch >= 1 and 4 .. 2^24 slots per pair, a multiple of 4";
+    else if (io->pick < 1 || io->pick > sched::FIRST_PICK_LIMIT) why = "front_lists: pick must be 1 .. 64";
+    else if (!io->n || !io->active || !io->sq_thr || !io->count || !io->tags || !io->slot_score || !io->slot_inl || !io->tags_pick || !io->tags_rest ||
+             !io->tags_out || !io->pick_count || !io->rest_count || !io->surv_count || !io->evals)
+        why = "front_lists: a NULL buffer";
+    for (int p = 0; p < batch && !why; ++p) {
+        if (io->n[p] < 0 || io->count[p] < 0 || io->count[p] > slots) why = "front_lists: n or a list length out of range";
+        for (int i = 0; !why && i < io->count[p]; ++i)
+            if ((io->tags[(size_t)p * slots + i] & 0xFFFFFFu) >= (uint32_t)slots) why = "front_lists: a tag names a slot outside the table";
+    }
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    hipStream_t s = h->stream;
+    const size_t b = (size_t)batch, all = b * (size_t)slots, tag_bytes = sizeof(uint32_t) * all;
+    int rc;
+    if ((rc = h->st.ensure(sizeof(PairState) * b)) || (rc = h->slot_score.ensure(sizeof(double) * all)) || (rc = h->slot_inl.ensure(sizeof(int32_t) * all)) ||
+        (rc = h->tags[0].ensure(tag_bytes)) || (rc = h->tags_v.ensure(tag_bytes)) || (rc = h->tags_sorted[1].ensure(tag_bytes)) ||
+        (rc = h->surv_count.ensure(sizeof(int32_t) * b)) || (rc = h->surv2_count.ensure(sizeof(int32_t) * b)) ||
+        (rc = h->und_count.ensure(sizeof(int32_t) * 2 * b)) || (rc = h->counters.ensure(sizeof(Counters))))
+        return rc;
+    std::vector<PairState> st_host(b);
+    int n_max = 1;
+    for (size_t p = 0; p < b; ++p) {
+        PairState &ps = st_host[p];
+        std::memset(&ps, 0, sizeof ps);
+        ps.n = io->n[p]; ps.active = io->active[p]; ps.sq_thr = io->sq_thr[p]; ps.eps = std::sqrt(io->sq_thr[p]); ps.best_min_score = DBL_MAX;
+        n_max = std::max(n_max, ps.n);
+    }
+    PairState *st = h->st.as<PairState>();
+    uint32_t *tags_pick = h->tags[0].as<uint32_t>(), *tags_rest = h->tags_sorted[1].as<uint32_t>(), *tags_v = h->tags_v.as<uint32_t>();
+    int32_t *surv1 = h->surv_count.as<int32_t>(), *surv2 = h->surv2_count.as<int32_t>(), *und_count = h->und_count.as<int32_t>();
+    unsigned long long *evals = &h->counters.as<Counters>()->progress.evals_sweep;
+    HIPCHK(hipMemcpyAsync(st, st_host.data(), sizeof(PairState) * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->slot_score.p, io->slot_score, sizeof(double) * all, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->slot_inl.p, io->slot_inl, sizeof(int32_t) * all, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(tags_v, io->tags, tag_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(surv1, io->count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(tags_pick, io->tags_pick, tag_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(tags_rest, io->tags_rest, tag_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(surv2, io->pick_count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(und_count, io->rest_count, sizeof(int32_t) * 2 * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
+    RunParams rp;
+    std::memset(&rp, 0, sizeof rp);
+    rp.batch = batch; rp.n_max = n_max; rp.chunk_len = slots / 4; rp.super_len = rp.chunk_len; rp.slot_stride = slots; rp.mps = 4; rp.sample_sz = 3;
+    hipLaunchKernelGGL(k_first_pick, dim3(batch), dim3(FIRST_THREADS), 0, s, rp, st, surv1, tags_v, io->pick, tags_pick, surv2, tags_rest, und_count);
+    // the pick has consumed the survivors: what the caller put into the kept list and its counter takes their place, so that an inactive pair's stay
+    HIPCHK(hipMemcpyAsync(tags_v, io->tags_out, tag_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(surv1, io->surv_count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_first_filter, dim3(batch), dim3(FIRST_THREADS), 0, s, rp, st, h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), tags_pick, surv2,
+                       tags_rest, und_count, tags_v, surv1, evals);
+    HIPCHK(hipGetLastError());
+    unsigned long long ev = 0;
+    HIPCHK(hipMemcpyAsync(io->tags_pick, tags_pick, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->tags_rest, tags_rest, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->tags_out, tags_v, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->pick_count, surv2, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->rest_count, und_count, sizeof(int32_t) * 2 * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->surv_count, surv1, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *io->evals = ev;
     return MDRP_OK;
 }
 

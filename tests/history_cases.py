@@ -577,6 +577,21 @@ def _run_replay(h, capi, c):
             np.array([r["total"], r["n_active"], r["max_needed"]], dtype=np.int64))
 
 
+def _front_lists_case():
+    """part of one group of tests/first_front_cases.py (pick 3): the margin cases, the ties, ten random tables and the inactive pair"""
+    import first_front_cases as ffc
+    cases = [c for c in ffc.groups()[(3, ffc.SMALL)] if c.name.startswith(("margin", "table 30", "inactive", "ties"))]
+    return dict(n=np.array([c.n for c in cases], dtype=np.int32), thr=np.array([c.thr for c in cases]), active=np.array([c.active for c in cases], dtype=np.int32),
+                tags=[c.tags for c in cases], lens=np.array([len(c.tags) for c in cases], dtype=np.int32), slot_score=np.stack([c.slot_score for c in cases]),
+                slot_inl=np.stack([c.slot_inl for c in cases]))
+
+
+def _run_front_lists(h, capi, d):
+    r = h.front_lists(d["n"], d["thr"], d["active"], d["tags"], 3, d["slot_score"], d["slot_inl"])
+    return (np.concatenate([np.sort(t) for t in r["picked"]]), np.concatenate([np.sort(t) for t in r["rest"]]), np.concatenate([np.sort(t) for t in r["kept"]]),
+            r["pick_count"], r["rest_count"], r["surv_count"], np.array([r["evals"]], dtype=np.uint64))
+
+
 def _refine_problem():
     import from_models_cases as fc
     p = synth.make_pair(9107, 130, noise_px=1.0, depth_noise=0.05, outlier_frac=0.7)
@@ -611,6 +626,12 @@ def _units():
              ("scores", "counts", "left at", "info", "candidate statistics"), mods),
         Unit("replay_slots", ["mdrp_replay_slots"], _replay_case, _run_replay,
              ("states", "triggers", "n_triggers", "scan_cnt", "scan_score", "scan_inst", "prefix", "begin", "end", "total | n_active | max_needed"), _replay_digest),
+        Unit("front_lists", ["mdrp_front_lists"], _front_lists_case, _run_front_lists,
+             ("picked (sorted)", "rest (sorted)", "kept (sorted)", "pick_count", "rest_count", "surv_count", "evals"),
+             lambda d: [d["n"], d["thr"], d["active"], np.concatenate(d["tags"]), d["lens"], d["slot_score"], d["slot_inl"]]),
+        Unit("front_models", ["mdrp_front_models"], _retirement_pair,
+             lambda h, capi, d: h.front_models(1, M(capi, d), d["x1"], d["x2"], d["thr"], 48, d["rec_cnt"], d["rec_score"]),
+             ("scores", "counts", "left at", "info"), mods),
         Unit("refine_models", ["mdrp_refine_models"], _refine_problem,
              lambda h, capi, d: h.refine_models(0, M(capi, d), d["x1"], d["x2"], d["d1"], d["d2"], 1 / 64.0, 1.0, capi.bundle_opt_from_dict({"loss_type": LOSS})),
              ("models", "costs"), lambda d: [d["x1"], d["x2"], d["d1"], d["d2"], d["models"]]),

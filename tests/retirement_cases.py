@@ -10,6 +10,8 @@ import math
 import numpy as np
 
 NS = (3, 64, 257, 513, 1000, 1024, 1025, 2000, 2049)
+FRONT_NS = (40, 257, 600)  # tests/test_gpu_first_front.py (the sizes of tests/test_gpu_first_filter.py above one sample)
+_SEED_NS = NS + tuple(n for n in FRONT_NS if n not in NS)
 PAIRS = ((0.05, 1.0), (0.4, 1.0), (0.6, 1.0), (0.0, 0.5))  # (outlier fraction, noise in pixels)
 NUM_MODELS = 1100  # three k_count workgroups of 512 (the last one ragged), five k_bound workgroups of 256
 NAN_SLOT, INF_SLOT, ZEROQ_SLOT = 7, 8, 9
@@ -49,7 +51,7 @@ def pair_case(n, pi):
     from mdrp_amd import synth
     from oracle import pyorc as po
     frac, noise = PAIRS[pi]
-    p = synth.make_pair(61000 + 4 * NS.index(n) + pi, n, noise_px=noise, outlier_frac=frac)
+    p = synth.make_pair(61000 + 4 * _SEED_NS.index(n) + pi, n, noise_px=noise, outlier_frac=frac)
     x1, x2 = np.ascontiguousarray(p["x1"] / 800.0), np.ascontiguousarray(p["x2"] / 800.0)
     rng = np.random.default_rng(7000 + 10 * n + pi)
     ms = np.zeros((NUM_MODELS, 12))

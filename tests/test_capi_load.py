@@ -33,6 +33,7 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_capi.RansacOpt) == 88 and C.sizeof(_capi.BundleOpt) == 64  # ABI 0.4: + progressive_sampling, max_prosac_iterations, real_focal_check
     assert _capi.RansacOpt.progressive_sampling.offset == 68 and _capi.RansacOpt.max_prosac_iterations.offset == 72 and _capi.RansacOpt.real_focal_check.offset == 80
     assert _capi.REPLAY_STATE_DTYPE.itemsize == 176 and _capi.REPLAY_TRIGGER_DTYPE.itemsize == 32 and C.sizeof(_capi.Replay) == 176  # mdrp_replay_slots
+    assert C.sizeof(_capi.FrontTables) == 128 and _capi.FrontTables.n.offset == 16 and _capi.FrontTables.evals.offset == 120  # mdrp_front_lists
     hdr0 = open(os.path.join(ROOT, "include", "mdrp.h")).read()
     assert int(re.search(r"#define MDRP_ABI_VERSION (0x[0-9a-fA-F]+)", hdr0).group(1), 16) == _capi.ABI_VERSION == _capi.load_library().mdrp_abi_version()
     # mdrp_stats: every field is 8 bytes; the binding's field list must be the header's, in order

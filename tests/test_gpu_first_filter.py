@@ -125,3 +125,154 @@ def test_front_stage_under_dynamic_stopping(monkeypatch):
     assert np.array_equal(mask_on, mask_off)
     its = on["iterations"][[i for i in range(B) if i != TWO]]
     assert int(its.min()) >= 101 and int(its.max()) == 2000 and len(set(its.tolist())) > 2  # pairs stop at their own iterations
+
+
+# ---- the stage behind the other entry points: priors (an ARMED count in the first chunk), PROSAC, budgets, and the longest first chunk
+BUDGETS = [10, 50, 128, 200, 600]   # two budgets inside the first chunk of 128 iterations, one on its last iteration, two behind it
+LONG = 16384                        # sched::chunk_capacity: with MDRP_CHUNKS set empty the first chunk is the whole first super-chunk
+N_LONG = 257
+
+
+@functools.lru_cache(maxsize=None)
+def _priors(kind):
+    """by pair index modulo 3: the pair's true model | a hopeless one | NaN (no prior); focals in pixels, 1 for the calibrated kind"""
+    from mdrp_amd import _capi, synth
+    import from_models_cases as fmc
+    ns = _inputs(kind)[0]
+    rng = np.random.default_rng(77500 + kind)
+    rows = np.zeros((B, 12))
+    for i in range(B):
+        p = synth.make_pair(77000 + 1000 * kind + i, max(int(ns[i]), 3), noise_px=0.5, depth_noise=0.02, outlier_frac=OUTLIERS[i % 3], random_focal=RF.get(kind))
+        f = (1.0, 1.0) if kind == 0 else (p["f1"], p["f2"])
+        R, t, scale = (p["R"], p["t"], p["scale"]) if i % 3 != 1 else (synth.rodrigues(rng.normal(0.0, 1.5, 3)), rng.normal(0.0, 0.5, 3), 1.0)
+        rows[i] = np.r_[fmc.rotmat_to_quat(R), t, scale, 0.0, 0.0, f]
+        if i % 3 == 2:
+            rows[i, :4] = np.nan
+    return _capi.array_to_models(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def _scores(kind):
+    """match scores a matcher might give: inliers mostly above outliers, rounded so that they tie"""
+    from mdrp_amd import synth
+    ns = _inputs(kind)[0]
+    out = np.zeros((B, NMAX))
+    rng = np.random.default_rng(77600 + kind)
+    for i in range(B):
+        n = int(ns[i])
+        p = synth.make_pair(77000 + 1000 * kind + i, max(n, 3), noise_px=0.5, depth_noise=0.02, outlier_frac=OUTLIERS[i % 3], random_focal=RF.get(kind))
+        out[i, :n] = -(p["is_outlier"][:n] + rng.normal(0.0, 0.6, n)).round(1)
+    return out
+
+
+def _call(h, monkeypatch, kind, env, how, max_it=ITS, min_it=ITS, n_cap=NMAX):
+    """one estimate of the 130 pairs through the entry point `how`: (records, masks, statistics); n_cap: correspondences per pair at most"""
+    from mdrp_amd import _capi
+    ns, x1, x2, d1, d2, cams = _inputs(kind)
+    ns = np.minimum(ns, n_cap).astype(np.int32)
+    x1, x2, d1, d2 = (np.ascontiguousarray(a[:, :n_cap]) for a in (x1, x2, d1, d2))
+    c = cams if kind == 0 else None
+    ro = _capi.ransac_opt_from_dict(dict(RO, max_iterations=max_it, min_iterations=min_it))
+    bo = _capi.bundle_opt_from_dict(BO)
+    _env(monkeypatch, env)
+    if how == "plain":
+        res, mask = h.estimate_batch(kind, x1, x2, d1, d2, ro, bo, ns, c, c)
+    elif how == "priors" or how == "no priors":
+        pr = _priors(kind).copy()
+        if how == "no priors":
+            pr["q"][:] = np.nan
+        res, mask = h.estimate_batch_prior(kind, x1, x2, d1, d2, pr, ro, bo, ns, c, c)
+    elif how == "scores":
+        res, mask = h.estimate_batch_ranked(kind, x1, x2, d1, d2, np.ascontiguousarray(_scores(kind)[:, :n_cap]), ro, bo, ns, c, c)
+    else:
+        assert how == "budgets"
+        res, mask = h.estimate_batch_budgets(kind, x1, x2, d1, d2, ro, bo, BUDGETS, ns, c, c)
+    return res.copy(), mask.copy(), h.last_stats()
+
+
+def _on_off(monkeypatch, kind, how, **kw):
+    from mdrp_amd import _capi
+    h = _capi.Handle(0)
+    try:
+        on = _call(h, monkeypatch, kind, {"MDRP_FIRST_PICK": "48"}, how, **kw)
+        off = _call(h, monkeypatch, kind, {"MDRP_FIRST_PICK": "0"}, how, **kw)
+    finally:
+        h.close()
+    assert on[2]["sweep_launches"] == off[2]["sweep_launches"] + 1, (how, on[2]["sweep_launches"], off[2]["sweep_launches"])  # the stage ran
+    assert on[2]["first_chunk"] == off[2]["first_chunk"]
+    flat_on, flat_off = on[0].reshape(-1), off[0].reshape(-1)
+    assert on[0].tobytes() == off[0].tobytes(), (kind, how, [i for i in range(len(flat_on)) if flat_on[i:i + 1].tobytes() != flat_off[i:i + 1].tobytes()][:16])
+    assert np.array_equal(on[1], off[1]), (kind, how)
+    assert int(on[0]["num_inliers"].max()) > 100
+    return on, off
+
+
+def test_the_inputs_of_the_other_entry_points():
+    """(no GPU) a third of the pairs each with a true, a hopeless and no prior, at every n; scores that tie and tell inliers from outliers"""
+    ns = _inputs(0)[0]
+    pr = _priors(0)
+    nan = np.isnan(pr["q"][:, 0])
+    assert [int(nan[i::3].sum()) for i in range(3)] == [0, 0, len(range(2, B, 3))] and np.isfinite(pr["t"]).all()
+    assert {int(ns[i]) for i in range(0, B, 3)} >= {40, 257, 600} and {int(ns[i]) for i in range(1, B, 3)} >= {40, 257, 600}
+    sc = _scores(0)
+    assert len(np.unique(sc[1, :257])) < 100 and BUDGETS[-1] == ITS and sorted(BUDGETS) == BUDGETS and sum(b < 128 for b in BUDGETS) == 2 and 128 in BUDGETS
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", [0, 1, 2])
+def test_front_stage_behind_priors(monkeypatch, kind):
+    """a good prior arms the first chunk's count: the stage runs on what the prior's records left.  A NaN prior is no prior."""
+    on, off = _on_off(monkeypatch, kind, "priors")
+    assert on[2]["first_chunk"] == 128
+    bare, _ = _on_off(monkeypatch, kind, "no priors")
+    assert on[2]["evals_fp64"] < bare[2]["evals_fp64"], ("the good priors retired nothing in the first chunk", on[2]["evals_fp64"], bare[2]["evals_fp64"])
+    nan = np.flatnonzero(np.isnan(_priors(kind)["q"][:, 0]))
+    from mdrp_amd import _capi
+    h = _capi.Handle(0)
+    try:
+        plain = _call(h, monkeypatch, kind, {"MDRP_FIRST_PICK": "48"}, "plain")
+    finally:
+        h.close()
+    assert bare[0].tobytes() == plain[0].tobytes() and on[0][nan].tobytes() == plain[0][nan].tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", [0, 2])
+def test_front_stage_behind_prosac(monkeypatch, kind):
+    """a first chunk full of near-best hypotheses: the progressive sampler draws from the best-scored matches first"""
+    on, _ = _on_off(monkeypatch, kind, "scores")
+    assert on[2]["first_chunk"] == 128
+    ns = _inputs(kind)[0]
+    half = [i for i in range(B) if i % 3 == 1 and ns[i] >= 40 and i not in (TWO, DEGENERATE)]  # the pairs at 50 % outliers with more than one sample
+    assert len(half) > 20 and (on[0]["num_inliers"][half] > 0).all()
+
+
+@pytest.mark.gpu
+def test_front_stage_with_budgets_inside_the_first_chunk(monkeypatch):
+    from mdrp_amd import _capi
+    on, _ = _on_off(monkeypatch, 0, "budgets")
+    assert on[2]["first_chunk"] == 128 and on[0].shape == (len(BUDGETS), B)
+    h = _capi.Handle(0)
+    try:
+        for c, k in enumerate(BUDGETS):  # each budget's record is the separate call's with max_iterations = the budget (tests/test_gpu_budgets.py)
+            res, mask, st = _call(h, monkeypatch, 0, {"MDRP_FIRST_PICK": "48"}, "plain", max_it=k)
+            assert on[0][c].tobytes() == res.tobytes(), (k, [i for i in range(B) if on[0][c][i:i + 1].tobytes() != res[i:i + 1].tobytes()][:16])
+            assert np.array_equal(on[1][c], mask), k
+    finally:
+        h.close()
+
+
+@pytest.mark.gpu
+def test_front_stage_on_the_longest_first_chunk(monkeypatch):
+    """MDRP_CHUNKS set empty and 16384 certain iterations: the first chunk is its whole super-chunk, 65536 slots per pair (n <= 257: a short call)"""
+    from mdrp_amd import _capi
+    h = _capi.Handle(0)
+    try:
+        on = _call(h, monkeypatch, 0, {"MDRP_FIRST_PICK": "48", "MDRP_CHUNKS": ""}, "plain", max_it=LONG, min_it=LONG, n_cap=N_LONG)
+        off = _call(h, monkeypatch, 0, {"MDRP_FIRST_PICK": "0", "MDRP_CHUNKS": ""}, "plain", max_it=LONG, min_it=LONG, n_cap=N_LONG)
+    finally:
+        h.close()
+    assert on[2]["first_chunk"] == off[2]["first_chunk"] == LONG and on[2]["sweep_launches"] == off[2]["sweep_launches"] + 1
+    assert on[2]["evals_fp64"] < off[2]["evals_fp64"], (on[2]["evals_fp64"], off[2]["evals_fp64"])
+    assert on[0].tobytes() == off[0].tobytes(), [i for i in range(B) if on[0][i:i + 1].tobytes() != off[0][i:i + 1].tobytes()][:16]
+    assert np.array_equal(on[1], off[1]) and int(on[0]["iterations"].max()) == LONG
