@@ -619,7 +619,7 @@ int mdrp_estimate_batch_prior_async(mdrp_handle *h, int kind, const double *x1_d
  *     caller's order; bytes at or past n are 0.
  * These entry points are what progressive_sampling selects in the reference, so they sample progressively whether ropt->progressive_sampling is 0
  * or 1 (a reference caller's options pass unabridged); every other entry point but the ranked front end (below) still refuses the switch.  kind: MDRP_CALIB, MDRP_SHARED_FOCAL or
- * MDRP_VARYING_FOCAL; any other kind is MDRP_ERR_INVALID, as is everything mdrp_estimate_batch refuses (NULL depths, n_per_pair out of range, ...).
+ * MDRP_VARYING_FOCAL; any other kind is MDRP_ERR_INVALID (the baselines have mdrp_estimate_classic_ranked, below), as is everything mdrp_estimate_batch refuses (NULL depths, n_per_pair out of range, ...).
  * A refusal leaves the handle usable.  x1, x2, d1, d2, scores ([B][n_max] doubles or NULL) and inlier_mask ([B][n_max] bytes or NULL) live in
  * mem_space; n_per_pair, cameras and out ([B]) in HOST memory.  Host buffers are copied in one piece on the handle's stream (no sliced front).
  * Iteration budgets and priors do not combine with scores.  The ordered copies of the correspondences are the handle's and are allocated before
@@ -639,6 +639,10 @@ int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosa
                         uint32_t *out);
 /* Inspection: the ranking kernel alone.  scores [B][n_max] doubles and order [B][n_max] int32 live in mem_space; order[b][r] = -1 for r >= n. */
 int mdrp_rank_scores(mdrp_handle *h, int mem_space, const double *scores, int batch, int n_max, const int32_t *n_per_pair, int32_t *order);
+
+/* ---- The 5- / 6- / 7-point baselines in match-score order (added within ABI 0.6: new symbols only) are declared and documented in
+ * mdrp_classic_ranked.h, which this header includes at its end: the ranked estimate for kinds 3 - 5, blocking and device-resident, and the
+ * progressive sampler alone for a sample size of 3, 5, 6 or 7. */
 
 /* ---- The device front end with match scores: PROSAC from a matcher's confidences (added within ABI 0.6: new symbols only).
  * mdrp_gather_matches / mdrp_gather_image_pairs and the two front-end estimates, with one score per MATCH ROW, higher is better:
@@ -676,4 +680,5 @@ int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_
 #ifdef __cplusplus
 }
 #endif
+#include "mdrp_classic_ranked.h"
 #endif

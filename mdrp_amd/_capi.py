@@ -30,6 +30,8 @@ EXPORTS = (
     "mdrp_estimate_batch_ranked", "mdrp_estimate_batch_ranked_async", "mdrp_prosac_samples", "mdrp_rank_scores",
     "mdrp_gather_matches_ranked", "mdrp_estimate_matches_ranked_async", "mdrp_gather_image_pairs_ranked", "mdrp_estimate_image_pairs_ranked_async",
 )
+# the entry points of include/mdrp_classic_ranked.h, the extension header mdrp.h includes (EXPORTS above is mdrp.h's own list)
+EXPORTS_CLASSIC_RANKED = ("mdrp_estimate_classic_ranked", "mdrp_estimate_classic_ranked_async", "mdrp_prosac_samples_k")
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
 STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
@@ -199,6 +201,12 @@ def load_library():
                                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
             lib.mdrp_prosac_samples.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint64, ip, C.c_int, vp]
             lib.mdrp_rank_scores.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, ip, vp]
+        if hasattr(lib, "mdrp_estimate_classic_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked baselines: Handle._classic_ranked_fn raises)
+            lib.mdrp_estimate_classic_ranked.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                         C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
+            lib.mdrp_estimate_classic_ranked_async.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                               C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
+            lib.mdrp_prosac_samples_k.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, ip, C.c_int, vp]
         if hasattr(lib, "mdrp_gather_matches_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked front end: Handle._ranked_front_end_fn raises)
             lib.mdrp_gather_matches_ranked.argtypes = [vp, C.POINTER(Matches), vp, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
             lib.mdrp_estimate_matches_ranked_async.argtypes = [vp, C.c_int, C.POINTER(Matches), vp, C.c_int, C.c_int, vp, vp, C.POINTER(RansacOpt),
@@ -647,6 +655,54 @@ class Handle:
         lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
         out = np.full((int(lens.sum()), 3), fill, dtype=np.uint32)
         _check(self._lib, self._ranked_fn("mdrp_prosac_samples")(self._h, int(seed), int(n), int(max_prosac_iterations), _ptr(lens), len(lens), _ptr(out)))
+        return out
+
+    # ---- the 5- / 6- / 7-point baselines in match-score order (include/mdrp.h: mdrp_estimate_classic_ranked): no depths
+    def _classic_ranked_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the ranked baselines (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    def estimate_classic_ranked(self, kind, x1, x2, scores, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
+        """estimate_batch of a baseline (kind 3, 4, 5) in score order with the progressive sampler, host (numpy) buffers; scores (B, N), higher is
+        better, or None: the records are in quality order already.  (records, masks (B, N) uint8 in the caller's order or None)"""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+            raise ValueError("expected x1,x2 (B,N,2)")
+        B, N = x1.shape[:2]
+        scores = None if scores is None else np.ascontiguousarray(scores, dtype=np.float64)
+        if scores is not None and scores.shape != (B, N):
+            raise ValueError(f"expected scores ({B},{N}), got {scores.shape}")
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        out = np.zeros(B, dtype=RESULT_DTYPE)
+        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        _check(self._lib, self._classic_ranked_fn("mdrp_estimate_classic_ranked")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(scores), B, N, _ptr(npp),
+                                                                                  _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(out), _ptr(mask)))
+        return out, mask
+
+    def estimate_classic_ranked_device(self, kind, x1_ptr, x2_ptr, scores_ptr, batch, n_max, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, mask_ptr=None):
+        """the same on device pointers (ints), queued on the handle's stream; scores_ptr: batch x n_max float64, or None / 0 for records in quality
+        order.  Records: fetch_results / copy_results_device."""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _check(self._lib, self._classic_ranked_fn("mdrp_estimate_classic_ranked_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(scores_ptr), int(batch),
+                                                                                        int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                                                        vp(mask_ptr)))
+
+    def prosac_samples_k(self, seed, n, sample_size, max_prosac_iterations, chunk_lens, fill=0):
+        """prosac_samples for samples of sample_size records (3, 5, 6 or 7): (sum(chunk_lens), sample_size) uint32"""
+        lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
+        out = np.full((int(lens.sum()), int(sample_size)), fill, dtype=np.uint32)
+        _check(self._lib, self._classic_ranked_fn("mdrp_prosac_samples_k")(self._h, int(seed), int(n), int(sample_size), int(max_prosac_iterations), _ptr(lens),
+                                                                           len(lens), _ptr(out)))
         return out
 
     def rank_scores(self, scores, n_per_pair=None):

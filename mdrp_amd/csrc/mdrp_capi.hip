@@ -387,20 +387,26 @@ struct PassIn {
     const uint64_t *prosac; // ranked call: max_prosac_iterations of the progressive sampler (mdrp_prosac.h), or null: the uniform sampler
 };
 
-// The progressive sampler's launch: Pass::samples and mdrp_prosac_samples both go through here.  `tab`: sample index per table | schedule offsets |
-// subset sizes (prosac_tables).
+// The progressive sampler's launch for samples of `ssz` records (3, or the baselines' 5 / 6 / 7): Pass::samples and mdrp_prosac_samples[_k] both go
+// through here.  `tab`: sample index per table | schedule offsets | subset sizes (prosac_tables).
 struct ProsacTab { uint64_t *k; const uint64_t *off; const uint32_t *sub; };
-void launch_samples_prosac(hipStream_t st, int threads, int n_tables, const int32_t *d_table_n, uint64_t *d_table_state, const ProsacTab &tab,
+void launch_samples_prosac(hipStream_t st, int ssz, int threads, int n_tables, const int32_t *d_table_n, uint64_t *d_table_state, const ProsacTab &tab,
                            uint64_t max_prosac, int len, uint32_t *smp) {
-    hipLaunchKernelGGL(k_samples_prosac, dim3(n_tables), dim3(threads), 0, st, n_tables, d_table_n, d_table_state, tab.k, tab.off, tab.sub,
-                       prosac::prosac_samples(max_prosac), len, smp);
+#define MDRP_PROSAC_LAUNCH(KERNEL)                                                                                                                \
+    hipLaunchKernelGGL(KERNEL, dim3(n_tables), dim3(threads), 0, st, n_tables, d_table_n, d_table_state, tab.k, tab.off, tab.sub,                  \
+                       prosac::prosac_samples(max_prosac), len, smp)
+    if (ssz == 5) MDRP_PROSAC_LAUNCH(kc_samples_prosac<5>);
+    else if (ssz == 6) MDRP_PROSAC_LAUNCH(kc_samples_prosac<6>);
+    else if (ssz == 7) MDRP_PROSAC_LAUNCH(kc_samples_prosac<7>);
+    else MDRP_PROSAC_LAUNCH(k_samples_prosac);
+#undef MDRP_PROSAC_LAUNCH
 }
 // the tables of a run of at most `count` samples, one schedule per sample table, uploaded on `s` (pageable staging: the copy has left it on return)
-int prosac_tables(mdrp_handle *h, hipStream_t s, const int32_t *tab_n, int n_tables, uint64_t max_prosac, uint64_t count, ProsacTab &tab) {
+int prosac_tables(mdrp_handle *h, hipStream_t s, int ssz, const int32_t *tab_n, int n_tables, uint64_t max_prosac, uint64_t count, ProsacTab &tab) {
     std::vector<uint64_t> head(2 * (size_t)n_tables + 1, 0); // k = 0 per table | offsets
     std::vector<uint32_t> sub;
     for (int t = 0; t < n_tables; ++t) {
-        const std::vector<uint32_t> one = prosac::subset_schedule((uint64_t)std::max(tab_n[t], 0), max_prosac, count, true);
+        const std::vector<uint32_t> one = prosac::subset_schedule((uint64_t)std::max(tab_n[t], 0), max_prosac, count, true, ssz);
         head[n_tables + t] = sub.size();
         sub.insert(sub.end(), one.begin(), one.end());
     }
@@ -585,7 +591,7 @@ struct Pass : PassIn {
         std::memcpy(ph + sz.off_nper, n_host, sizeof(int32_t) * batch);
         if (bud) std::memcpy(ph + sz.off_bud, bud->budgets, sizeof(uint64_t) * n_bud);
         HIPCHK(hipMemcpyAsync(pd, ph, sz.params, hipMemcpyHostToDevice, s));
-        if (prosac) { if (int rc = prosac_tables(h, s, tab_n.data(), n_tables, *prosac, ro->max_iterations, ptab)) return rc; }
+        if (prosac) { if (int rc = prosac_tables(h, s, ssz, tab_n.data(), n_tables, *prosac, ro->max_iterations, ptab)) return rc; }
 
         std::memset(&rp, 0, sizeof rp);
         rp.kind = kind; rp.solver = solver_for(kind, est_shift); rp.est_shift = est_shift;
@@ -648,7 +654,7 @@ struct Pass : PassIn {
     }
 
     void samples(hipStream_t st_, int len_, uint32_t *smp_) {
-        if (prosac) launch_samples_prosac(st_, samp_threads, n_tables, d_table_n, d_table_state, ptab, *prosac, len_, smp_);
+        if (prosac) launch_samples_prosac(st_, ssz, samp_threads, n_tables, d_table_n, d_table_state, ptab, *prosac, len_, smp_);
         else if (ssz == 6) hipLaunchKernelGGL(kc_samples<6>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
         else if (ssz == 5) hipLaunchKernelGGL(kc_samples<5>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
         else if (ssz == 7) hipLaunchKernelGGL(kc_samples<7>, dim3(n_tables), dim3(samp_threads), 0, st_, n_tables, d_table_n, d_table_state, len_, smp_);
@@ -1107,7 +1113,7 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
                     const uint64_t *prosac = nullptr /*ranked call: max_prosac_iterations*/) {
     if (int rc = estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, ro, bo)) return rc;
     if (priors && (host || budgets || kind > MDRP_VARYING_FOCAL)) { g_err = "priors: device-resident monodepth calls without budgets only"; return MDRP_ERR_INVALID; }
-    if (prosac && (host || budgets || priors || kind > MDRP_VARYING_FOCAL)) { g_err = "ranked: device-resident monodepth calls without budgets or priors only"; return MDRP_ERR_INVALID; }
+    if (prosac && (host || budgets || priors)) { g_err = "ranked: device-resident calls without budgets or priors only"; return MDRP_ERR_INVALID; }
     h->last_budgets = n_budgets;
     if (h->fuse_disabled && --h->fuse_retry_in <= 0) h->fuse_disabled = false; // once per API call (not per pass): the handle tries the fused tail again
     h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
@@ -2668,7 +2674,7 @@ static int check_ranked_args(mdrp_handle *h, int kind, const double *d1, const d
                              const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo) {
     const char *why = nullptr;
     if (!h || !ro || !bo) why = "invalid argument";
-    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "ranked: only the monodepth estimators (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL)";
+    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "ranked: only the monodepth estimators (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL); the 5- / 6- / 7-point baselines have no depths: mdrp_estimate_classic_ranked takes them";
     else if (batch < 0 || n_max < 0) why = "ranked: a negative size";
     for (int i = 0; !why && n_per_pair && i < batch; ++i)
         if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
@@ -2704,9 +2710,11 @@ static int ranked_device(mdrp_handle *h, int kind, const double *x1, const doubl
         return estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, &plain, bo, mask_dev, nullptr, nullptr, 0, nullptr, &max_prosac);
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = h->pr_x1.ensure(sizeof(double) * 2 * np)) || (rc = h->pr_x2.ensure(sizeof(double) * 2 * np)) || (rc = h->pr_d1.ensure(sizeof(double) * np)) ||
-        (rc = h->pr_d2.ensure(sizeof(double) * np)) || (rc = h->pr_order.ensure(sizeof(int32_t) * np)) || (rc = h->pr_mask.ensure(np)))
+    const bool depths = kind <= MDRP_VARYING_FOCAL; // (a baseline call: d1 / d2 are null, no ordered copies of them)
+    if ((rc = h->pr_x1.ensure(sizeof(double) * 2 * np)) || (rc = h->pr_x2.ensure(sizeof(double) * 2 * np)) || (depths && (rc = h->pr_d1.ensure(sizeof(double) * np))) ||
+        (depths && (rc = h->pr_d2.ensure(sizeof(double) * np))) || (rc = h->pr_order.ensure(sizeof(int32_t) * np)) || (rc = h->pr_mask.ensure(np)))
         return rc;
+    double *d1o = depths ? h->pr_d1.as<double>() : nullptr, *d2o = depths ? h->pr_d2.as<double>() : nullptr;
     uint8_t *mask = mask_dev;
     if (!mask) {
         if ((rc = h->mask.ensure(np))) return rc;
@@ -2717,9 +2725,9 @@ static int ranked_device(mdrp_handle *h, int kind, const double *x1, const doubl
     const dim3 rgrid((unsigned)batch, (unsigned)((n_max + 255) / 256));
     const int32_t *nper = h->pr_nper.as<int32_t>();
     hipLaunchKernelGGL(k_rank_gather, rgrid, dim3(256), 0, s, (const int32_t *)order, nper, n_max, x1, x2, d1, d2, h->pr_x1.as<double>(), h->pr_x2.as<double>(),
-                       h->pr_d1.as<double>(), h->pr_d2.as<double>());
+                       d1o, d2o);
     HIPCHK(hipGetLastError());
-    if ((rc = estimate_device(h, kind, h->pr_x1.as<double>(), h->pr_x2.as<double>(), h->pr_d1.as<double>(), h->pr_d2.as<double>(), batch, n_max, n_per_pair,
+    if ((rc = estimate_device(h, kind, h->pr_x1.as<double>(), h->pr_x2.as<double>(), d1o, d2o, batch, n_max, n_per_pair,
                               cam1, cam2, &plain, bo, h->pr_mask.as<uint8_t>(), nullptr, nullptr, 0, nullptr, &max_prosac)))
         return rc;
     hipLaunchKernelGGL(k_rank_scatter, rgrid, dim3(256), 0, s, (const int32_t *)order, nper, n_max, (const uint8_t *)h->pr_mask.as<uint8_t>(), mask);
@@ -2738,13 +2746,11 @@ int mdrp_estimate_batch_ranked_async(mdrp_handle *h, int kind, const double *x1,
     return rc ? drain_and_return(h, rc) : rc;
 }
 
-// The blocking form.  Host buffers are copied in plainly on the handle's stream (as mdrp_estimate_batch_prior does): no sliced front.
-int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
-                               const double *scores, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                               const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
-    if (int rc = check_ranked_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
-    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) { g_err = "monodepth estimator needs correspondences and depths"; return MDRP_ERR_INVALID; }
+// The blocking forms behind their argument checks.  Host buffers are copied in plainly, in one piece, on the handle's stream (as
+// mdrp_estimate_batch_prior does): no sliced front.  d1 / d2 null: a baseline call, no depths.
+static int ranked_blocking(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, const double *scores,
+                           int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                           const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
     MDRP_ENTER(h);
     const size_t np = (size_t)batch * n_max;
     const bool use_host = mem_space == MDRP_MEM_HOST;
@@ -2752,15 +2758,18 @@ int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const do
     int rc;
     if (use_host && np > 0) {
         if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
-            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)) ||
+            (d1 && ((rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)))) ||
             (scores && (rc = h->pr_scores.ensure(sizeof(double) * np))))
-            return rc;
+            return drain_and_return(h, rc);
         HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
+        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
+        if (d1) {
+            HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
+            d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
+        }
         if (scores) { HIPCHK(hipMemcpyAsync(h->pr_scores.p, scores, sizeof(double) * np, hipMemcpyHostToDevice, s)); scores = h->pr_scores.as<double>(); }
-        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>(); d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
     }
     rc = ranked_device(h, kind, x1, x2, d1, d2, scores, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask);
     if (rc) return drain_and_return(h, rc);
@@ -2770,6 +2779,48 @@ int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const do
     }
     rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
     return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
+                               const double *scores, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                               const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
+    if (int rc = check_ranked_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
+    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) { g_err = "monodepth estimator needs correspondences and depths"; return MDRP_ERR_INVALID; }
+    return ranked_blocking(h, kind, mem_space, x1, x2, d1, d2, scores, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, out, inlier_mask);
+}
+
+// ---- the 5- / 6- / 7-point baselines in match-score order (include/mdrp.h): check_ranked_args' rule on kinds 3-5, no depths
+static int check_classic_ranked_args(mdrp_handle *h, int kind, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                     const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo) {
+    const char *why = nullptr;
+    if (!h || !ro || !bo) why = "invalid argument";
+    else if (kind != MDRP_RELPOSE_5PT && kind != MDRP_SHARED_6PT && kind != MDRP_FUNDAMENTAL_7PT) why = "classic_ranked: only the baselines (MDRP_RELPOSE_5PT, MDRP_SHARED_6PT, MDRP_FUNDAMENTAL_7PT); mdrp_estimate_batch_ranked takes the monodepth estimators";
+    else if (batch < 0 || n_max < 0) why = "classic_ranked: a negative size";
+    for (int i = 0; !why && n_per_pair && i < batch; ++i)
+        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    mdrp_ransac_opt plain = *ro;
+    plain.progressive_sampling = 0;
+    return estimate_refusals(h, kind, nullptr, nullptr, batch, n_max, cam1, cam2, &plain, bo);
+}
+
+int mdrp_estimate_classic_ranked_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *scores_dev, int batch, int n_max,
+                                       const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                       const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
+    if (int rc = check_classic_ranked_args(h, kind, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
+    MDRP_ENTER(h);
+    const int rc = ranked_device(h, kind, x1, x2, nullptr, nullptr, scores_dev, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_estimate_classic_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *scores, int batch, int n_max,
+                                 const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                 const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
+    if (int rc = check_classic_ranked_args(h, kind, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
+    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (batch > 0 && n_max > 0 && (!x1 || !x2)) { g_err = "classic_ranked: correspondences are NULL"; return MDRP_ERR_INVALID; }
+    return ranked_blocking(h, kind, mem_space, x1, x2, nullptr, nullptr, scores, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, out, inlier_mask);
 }
 
 // k_rank alone: order [batch][n_max] int32 in mem_space (-1 at and past n).  Synchronous.
@@ -2798,40 +2849,48 @@ int mdrp_rank_scores(mdrp_handle *h, int mem_space, const double *scores, int ba
     return MDRP_OK;
 }
 
-// The progressive sampler alone, for one table of n records: chunk by chunk through the launch the scheduler uses (launch_samples_prosac), the
-// (RNG state, sample index) carried on the device from chunk to chunk.  out: [sum of chunk_lens][3] uint32 in host memory; n < 3 writes nothing.
-int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks, uint32_t *out) {
+// The progressive sampler alone, for one table of n records and samples of sample_size records (3, 5, 6 or 7): chunk by chunk through the launch
+// the scheduler uses (launch_samples_prosac), the (RNG state, sample index) carried on the device from chunk to chunk.
+// out: [sum of chunk_lens][sample_size] uint32 in host memory; n < sample_size writes nothing.
+int mdrp_prosac_samples_k(mdrp_handle *h, uint64_t seed, int n, int sample_size, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks,
+                          uint32_t *out) {
     const char *why = nullptr;
     long long total = 0, longest = 0;
+    const int K = sample_size;
     if (!h || n < 0 || n_chunks < 0 || (n_chunks > 0 && (!chunk_lens || !out))) why = "invalid argument";
+    else if (K != 3 && K != 5 && K != 6 && K != 7) why = "prosac_samples: sample_size is 3, 5, 6 or 7";
     for (int c = 0; !why && c < n_chunks; ++c) {
         if (chunk_lens[c] < 1) why = "prosac_samples: a chunk length < 1";
         else { total += chunk_lens[c]; longest = std::max<long long>(longest, chunk_lens[c]); }
     }
     if (!why && total > (1 << 24)) why = "prosac_samples: more than 2^24 samples";
     if (why) { g_err = why; return MDRP_ERR_INVALID; }
-    if (n < 3 || n_chunks == 0) return MDRP_OK;
+    if (n < K || n_chunks == 0) return MDRP_OK;
     MDRP_ENTER(h);
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = h->params.ensure(16)) || (rc = h->samples[0].ensure(sizeof(uint32_t) * 3 * (size_t)longest))) return rc;
+    if ((rc = h->params.ensure(16)) || (rc = h->samples[0].ensure(sizeof(uint32_t) * K * (size_t)longest))) return rc;
     uint64_t *d_state = h->params.as<uint64_t>();
     int32_t *d_n = reinterpret_cast<int32_t *>(d_state + 1);
     const int32_t n32 = n;
     HIPCHK(hipMemcpyAsync(d_state, &seed, sizeof seed, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_n, &n32, sizeof n32, hipMemcpyHostToDevice, s));
     ProsacTab tab{nullptr, nullptr, nullptr};
-    if ((rc = prosac_tables(h, s, &n32, 1, max_prosac_iterations, (uint64_t)total, tab))) return drain_and_return(h, rc);
-    const int threads = env_int("MDRP_SAMPLE_THREADS", SAMP_THREADS);
+    if ((rc = prosac_tables(h, s, K, &n32, 1, max_prosac_iterations, (uint64_t)total, tab))) return drain_and_return(h, rc);
+    const int threads = env_int("MDRP_SAMPLE_THREADS", K == 3 ? SAMP_THREADS : (K == 5 ? 512 : 256)); // (the scheduler's defaults: Pass::samp_threads)
     size_t done = 0;
     for (int c = 0; c < n_chunks; ++c) {
-        launch_samples_prosac(s, threads, 1, d_n, d_state, tab, max_prosac_iterations, chunk_lens[c], h->samples[0].as<uint32_t>());
+        launch_samples_prosac(s, K, threads, 1, d_n, d_state, tab, max_prosac_iterations, chunk_lens[c], h->samples[0].as<uint32_t>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out + 3 * done, h->samples[0].p, sizeof(uint32_t) * 3 * (size_t)chunk_lens[c], hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out + K * done, h->samples[0].p, sizeof(uint32_t) * K * (size_t)chunk_lens[c], hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s)); // (pageable destination: the next chunk overwrites the table)
         done += (size_t)chunk_lens[c];
     }
     return MDRP_OK;
+}
+
+int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks, uint32_t *out) {
+    return mdrp_prosac_samples_k(h, seed, n, 3, max_prosac_iterations, chunk_lens, n_chunks, out);
 }
 
 } // extern "C"

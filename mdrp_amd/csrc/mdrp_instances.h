@@ -1,7 +1,7 @@
 // Kernel instantiations that live in their own translation units (compiled in parallel by mdrp_amd/build.py; mdrp_tu.hip defines them,
 // mdrp_capi.hip declares them `extern template`).  MDRP_INST is `extern` in the declaring unit and empty in the defining one.
 //   group 1 / 2: k_final<KIND, SHIFT, T = 64 / 256, FLOSS> for the four LM estimators x the six loss types of BundleOptions
-//   group 3:     the kernels of the 5- / 6- / 7-point baselines (mdrp_classic.h)
+//   group 3:     the kernels of the 5- / 6- / 7-point baselines (mdrp_classic.h), their progressive sampler included (mdrp_prosac.h)
 //   group 4:     k_from_model<KIND, SHIFT> for the four LM estimators (mdrp_from_model.h)
 //   group 5:     k_prior<KIND, SHIFT> for the four LM estimators (mdrp_prior.h)
 #pragma once
@@ -21,6 +21,8 @@ namespace mdrp {
 #define MDRP_KC_SOLVE_ONE(CK) MDRP_INST template __global__ void kc_solve<CK>(RunParams, const PairState *, const uint32_t *, const double *, Model *, int32_t *, uint32_t *, int32_t *);
 #define MDRP_KC_UNIT_ONE(CK) MDRP_INST template __global__ void kc_solver_unit<CK>(int, const double *, const double *, Model *, int32_t *);
 #define MDRP_KC_SAMPLES_ONE(K) MDRP_INST template __global__ void kc_samples<K>(int, const int32_t *, uint64_t *, int, uint32_t *);
+#define MDRP_KS_PROSAC_ONE(K) MDRP_INST template __global__ void kc_samples_prosac<K>(int, const int32_t *, uint64_t *, uint64_t *, const uint64_t *, const uint32_t *, \
+                                                                                     uint64_t, int, uint32_t *);
 
 #define MDRP_FROM_MODEL_ONE(K, S) MDRP_INST template __global__ void k_from_model<K, S>(RunParams, const PairState *, const double *, const double *, const Model *, int, \
                                                                                       uint8_t *, ResultDev *, double *, int32_t *, int, int, unsigned long long *);
@@ -37,5 +39,6 @@ namespace mdrp {
     MDRP_CLASSIC_KINDS_T(MDRP_KC_REFINE_ONE, 64) MDRP_CLASSIC_KINDS_T(MDRP_KC_REFINE_ONE, 256)                                      \
     MDRP_KC_SOLVE_ONE(CLASSIC_SHARED) MDRP_KC_SOLVE_ONE(CLASSIC_FUND) /* (the 5-point solver: kc_solve5_reduce + kc_solve5_roots, main unit) */ \
     MDRP_KC_UNIT_ONE(CLASSIC_RELPOSE) MDRP_KC_UNIT_ONE(CLASSIC_SHARED) MDRP_KC_UNIT_ONE(CLASSIC_FUND)                               \
-    MDRP_KC_SAMPLES_ONE(5) MDRP_KC_SAMPLES_ONE(6) MDRP_KC_SAMPLES_ONE(7)
+    MDRP_KC_SAMPLES_ONE(5) MDRP_KC_SAMPLES_ONE(6) MDRP_KC_SAMPLES_ONE(7)                                                            \
+    MDRP_KS_PROSAC_ONE(5) MDRP_KS_PROSAC_ONE(6) MDRP_KS_PROSAC_ONE(7) /* (mdrp_prosac.h; K = 3 is the main unit's k_samples_prosac) */
 } // namespace mdrp

@@ -2,12 +2,14 @@
 //
 // PROSAC as the reference's RandomSampler draws it (initialize_prosac @0x4f8a20, generate_sample): while sample index k < max_prosac_iterations
 // a sample is K - 1 distinct draws from the first subset - 1 records plus record subset - 1, and the subset grows by the growth table; from
-// sample max_prosac_iterations on it is the uniform draw of K from n.  The sequence is a pure function of (seed, n, max_prosac_iterations), and
+// sample max_prosac_iterations on it is the uniform draw of K from n (K = 3 for the monodepth estimators, 5 / 6 / 7 for the baselines of
+// mdrp_classic.h: the sample size is a parameter of everything below).  The sequence is a pure function of (seed, n, K, max_prosac_iterations), and
 // the subset size of a sample does not depend on the RNG at all: the host builds one schedule per distinct n (subset_schedule below) and
 // k_samples_prosac reads it.  Everything else of a ranked call is the unchanged estimator, run on the records in descending score order:
 //   k_rank              scores -> order (one workgroup per pair, rank by counting, scores tiled through LDS: one path for every n; rank_key and
 //                       rank_count are shared with the ranked front end, k_gather_ranked / k_gather_images_ranked of mdrp_frontend.h)
-//   k_rank_gather       x1, x2, d1, d2 -> handle-owned copies in that order, in front of the unchanged estimate_device
+//   k_rank_gather       x1, x2, d1, d2 -> handle-owned copies in that order, in front of the unchanged estimate_device (a baseline has no depths:
+//                       the depth pointers are null and nothing of them is read or written)
 //   k_samples_prosac    the wave-speculative sampler (samples_block, mdrp_kernels.h) with a variable number of raw draws per sample
 //   k_rank_scatter      the inlier mask back into the caller's order, behind the run
 //
@@ -21,22 +23,22 @@
 namespace mdrp {
 namespace prosac {
 
-constexpr int K = 3; // sample size of the monodepth estimators
+constexpr int K = 3; // sample size of the monodepth estimators; the 5- / 6- / 7-point baselines pass theirs (mdrp_estimate_classic_ranked)
 
-// RandomSampler::initialize_prosac: growth[i] = samples after which the subset may grow past i + 1 records.  fp64, one operation per step, in
-// this order (no contraction: there is no multiply-add pair here to contract).
-inline std::vector<uint64_t> growth_table(uint64_t n, uint64_t max_prosac_iterations) {
-    std::vector<uint64_t> growth(std::max<uint64_t>(n, K), 1);
-    if (n < (uint64_t)K) return growth;
+// RandomSampler::initialize_prosac: growth[i] = samples after which the subset may grow past i + 1 records, for samples of `ssz` records.  fp64, one
+// operation per step, in this order (no contraction: there is no multiply-add pair here to contract).
+inline std::vector<uint64_t> growth_table(uint64_t n, uint64_t max_prosac_iterations, int ssz = K) {
+    std::vector<uint64_t> growth(std::max<uint64_t>(n, (uint64_t)ssz), 1);
+    if (n < (uint64_t)ssz) return growth;
     double T = (double)max_prosac_iterations;
-    for (int i = 0; i < K; ++i) {
-        const double ratio = (double)(K - i) / (double)(n - (uint64_t)i);
+    for (int i = 0; i < ssz; ++i) {
+        const double ratio = (double)(ssz - i) / (double)(n - (uint64_t)i);
         T = T * ratio;
     }
     uint64_t Tp = 1;
-    for (uint64_t i = K; i < n; ++i) {
+    for (uint64_t i = (uint64_t)ssz; i < n; ++i) {
         const double num = T * ((double)i + 1.0);
-        const double Tn = num / ((double)i + 1.0 - (double)K);
+        const double Tn = num / ((double)i + 1.0 - (double)ssz);
         const double step = std::ceil(Tn - T);
         Tp = (uint64_t)((double)Tp + step);
         growth[i] = Tp;
@@ -51,11 +53,11 @@ inline uint64_t prosac_samples(uint64_t max_prosac_iterations) { return max_pros
 
 // subset size of sample j for j = 0 .. min(count, prosac_samples) - 1, by replaying generate_sample's bookkeeping (at most one growth step per
 // sample).  With `truncate` the table ends where the subset has reached n: every progressive sample behind the table's end draws from all n.
-inline std::vector<uint32_t> subset_schedule(uint64_t n, uint64_t max_prosac_iterations, uint64_t count, bool truncate) {
+inline std::vector<uint32_t> subset_schedule(uint64_t n, uint64_t max_prosac_iterations, uint64_t count, bool truncate, int ssz = K) {
     std::vector<uint32_t> sub_of;
-    if (n < (uint64_t)K) return sub_of;
-    const std::vector<uint64_t> growth = growth_table(n, max_prosac_iterations);
-    uint64_t k = 1, sub = K;
+    if (n < (uint64_t)ssz) return sub_of;
+    const std::vector<uint64_t> growth = growth_table(n, max_prosac_iterations, ssz);
+    uint64_t k = 1, sub = (uint64_t)ssz;
     for (uint64_t j = 0; j < count && k < max_prosac_iterations; ++j) {
         if (truncate && sub >= n) break;
         sub_of.push_back((uint32_t)sub);
@@ -92,52 +94,57 @@ constexpr uint64_t RANK_KEY_DROPPED = 0; // below rank_key(-inf)
 
 #if defined(__HIPCC__)
 #include "mdrp_kernels.h"
+#include "mdrp_classic.h"
 
 namespace mdrp {
 
 // ------------------------------------------------------------------------------------------------ sampler
-// samples_block with K - 1 raw draws per progressive sample and K per uniform one.  Sample j of the table is progressive iff j < n_prosac; with P
-// progressive samples left at the start of a step, thread i speculates that its sample starts (K-1) min(i, P) + K max(0, i - P) draws behind the
-// workgroup's state.  Threads up to and including the first one that redrew a duplicate are right, the step commits those.  The table carries
-// (RNG state, sample index) across chunks: table_state, table_k.
-MDRP_GLOBAL __launch_bounds__(SAMP_THREADS) void k_samples_prosac(int n_tables, const int32_t *__restrict__ table_n, uint64_t *__restrict__ table_state,
-                                                                 uint64_t *__restrict__ table_k, const uint64_t *__restrict__ sub_off /*[n_tables + 1]*/,
-                                                                 const uint32_t *__restrict__ sub_of, uint64_t n_prosac, int chunk_len,
-                                                                 uint32_t *__restrict__ samples /*[n_tables][chunk_len][3]*/) {
+// samples_block with K - 1 raw draws per progressive sample and K per uniform one.  One body for every sample size: k_samples_prosac is its K = 3
+// kernel (the monodepth estimators, main unit; tests/test_prosac_resources.py reads its budget by that name), kc_samples_prosac<K> its kernels for the
+// baselines' K = 5, 6, 7, instantiated with their other kernels (mdrp_instances.h).  Sample j of the table is progressive iff j < n_prosac; with P progressive samples
+// left at the start of a step, thread i speculates that its sample starts (K-1) min(i, P) + K max(0, i - P) draws behind the workgroup's state.
+// Threads up to and including the first one that redrew a duplicate are right, the step commits those.  The table carries (RNG state, sample
+// index) across chunks: table_state, table_k.  A progressive sample is K - 1 distinct draws from the first sub - 1 records (draw_sample_k's
+// duplicate rule) and record sub - 1.  While the subset is barely larger than K almost every sample redraws and a step commits few samples: the
+// first ~60 samples of a table cost about as many steps (DESIGN.md 7e gives the measured time).
+template <int K>
+__device__ __forceinline__ void samples_prosac_tables(int n_tables, const int32_t *__restrict__ table_n, uint64_t *__restrict__ table_state,
+                                                      uint64_t *__restrict__ table_k, const uint64_t *__restrict__ sub_off /*[n_tables + 1]*/,
+                                                      const uint32_t *__restrict__ sub_of, uint64_t n_prosac, int chunk_len,
+                                                      uint32_t *__restrict__ samples /*[n_tables][chunk_len][K]*/) {
     __shared__ int s_first[SAMP_THREADS / 64];
     __shared__ unsigned long long s_state;
     const uint64_t GAMMA = 0x9e3779b97f4a7c15ULL;
     const int t = blockIdx.x;
     if (t >= n_tables) return;
     const uint64_t n = (uint64_t)table_n[t];
-    if (n < 3) return;
+    if (n < (uint64_t)K) return;
     uint64_t state = table_state[t];
     const uint64_t j0 = table_k[t];
     __syncthreads(); // every thread holds the state before thread 0 advances it
     const uint32_t *tab = sub_of + sub_off[t];
     const uint64_t tab_len = sub_off[t + 1] - sub_off[t];
-    uint32_t *out = samples + (size_t)t * chunk_len * 3;
+    uint32_t *out = samples + (size_t)t * chunk_len * K;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x, nwaves = nthreads >> 6;
     int done = 0;
     while (done < chunk_len) {
         const uint64_t jb = j0 + (uint64_t)done;               // sample index of thread 0
         const uint64_t P = jb < n_prosac ? n_prosac - jb : 0;  // progressive samples left
         const uint64_t i = (uint64_t)tid, pre = i < P ? i : P;
-        uint64_t s = state + (2 * pre + 3 * (i - pre)) * GAMMA;
+        uint64_t s = state + ((uint64_t)(K - 1) * pre + (uint64_t)K * (i - pre)) * GAMMA;
         const uint64_t s0 = s;
-        uint32_t smp[3];
+        uint32_t smp[K];
         uint64_t expect;
         if (i < P) {
             const uint64_t j = jb + i;
-            const uint64_t sub = j < tab_len ? (uint64_t)tab[j] : n; // (>= 3: the first sub - 1 >= 2 records hold two distinct indices)
+            const uint64_t sub = j < tab_len ? (uint64_t)tab[j] : n; // (>= K: the first sub - 1 >= K - 1 records hold K - 1 distinct indices)
             const uint64_t m = sub - 1;
-            smp[0] = (uint32_t)((uint64_t)(int64_t)splitmix_int(s) % m);
-            do { smp[1] = (uint32_t)((uint64_t)(int64_t)splitmix_int(s) % m); } while (smp[1] == smp[0]);
-            smp[2] = (uint32_t)m;
-            expect = 2;
+            draw_sample_k<K - 1>(m, s, smp);
+            smp[K - 1] = (uint32_t)m;
+            expect = K - 1;
         } else {
-            draw_sample3(n, s, smp[0], smp[1], smp[2]);
-            expect = 3;
+            draw_sample_k<K>(n, s, smp);
+            expect = K;
         }
         const bool rejected = (s - s0) != expect * GAMMA;
         const unsigned long long ball = __ballot(rejected);
@@ -148,7 +155,7 @@ MDRP_GLOBAL __launch_bounds__(SAMP_THREADS) void k_samples_prosac(int n_tables, 
         const int nvalid = min(first + 1, chunk_len - done);
         if (tid < nvalid) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) out[(size_t)3 * (done + tid) + k] = smp[k];
+            for (int k = 0; k < K; ++k) out[(size_t)K * (done + tid) + k] = smp[k];
         }
         if (tid == nvalid - 1) s_state = s;
         __syncthreads();
@@ -156,6 +163,19 @@ MDRP_GLOBAL __launch_bounds__(SAMP_THREADS) void k_samples_prosac(int n_tables, 
         done += nvalid;
     }
     if (tid == 0) { table_state[t] = state; table_k[t] = j0 + (uint64_t)chunk_len; }
+}
+MDRP_GLOBAL __launch_bounds__(SAMP_THREADS) void k_samples_prosac(int n_tables, const int32_t *__restrict__ table_n, uint64_t *__restrict__ table_state,
+                                                                 uint64_t *__restrict__ table_k, const uint64_t *__restrict__ sub_off,
+                                                                 const uint32_t *__restrict__ sub_of, uint64_t n_prosac, int chunk_len,
+                                                                 uint32_t *__restrict__ samples /*[n_tables][chunk_len][3]*/) {
+    samples_prosac_tables<3>(n_tables, table_n, table_state, table_k, sub_off, sub_of, n_prosac, chunk_len, samples);
+}
+template <int K>
+__global__ __launch_bounds__(SAMP_THREADS) void kc_samples_prosac(int n_tables, const int32_t *__restrict__ table_n, uint64_t *__restrict__ table_state,
+                                                                  uint64_t *__restrict__ table_k, const uint64_t *__restrict__ sub_off,
+                                                                  const uint32_t *__restrict__ sub_of, uint64_t n_prosac, int chunk_len,
+                                                                  uint32_t *__restrict__ samples /*[n_tables][chunk_len][K]*/) {
+    samples_prosac_tables<K>(n_tables, table_n, table_state, table_k, sub_off, sub_of, n_prosac, chunk_len, samples);
 }
 
 // ------------------------------------------------------------------------------------------------ ranking
@@ -209,7 +229,7 @@ MDRP_GLOBAL __launch_bounds__(RANK_THREADS) void k_rank(const double *__restrict
     }
 }
 
-// records of pair blockIdx.x in rank order into the ordered copies; rows at or past n are zero
+// records of pair blockIdx.x in rank order into the ordered copies; rows at or past n are zero.  d1o null (a baseline call): no depths, d1 / d2 / d2o are not touched
 MDRP_GLOBAL __launch_bounds__(256) void k_rank_gather(const int32_t *__restrict__ order, const int32_t *__restrict__ n_per_pair, int n_max,
                                                      const double *__restrict__ x1, const double *__restrict__ x2, const double *__restrict__ d1,
                                                      const double *__restrict__ d2, double *__restrict__ x1o, double *__restrict__ x2o,
@@ -224,11 +244,11 @@ MDRP_GLOBAL __launch_bounds__(256) void k_rank_gather(const int32_t *__restrict_
         const int src = order[o + r];
         if (src >= 0 && src < n) {
             a = reinterpret_cast<const double2 *>(x1)[o + src]; b = reinterpret_cast<const double2 *>(x2)[o + src];
-            u = d1[o + src]; v = d2[o + src];
+            if (d1o) { u = d1[o + src]; v = d2[o + src]; }
         }
     }
     reinterpret_cast<double2 *>(x1o)[o + r] = a; reinterpret_cast<double2 *>(x2o)[o + r] = b;
-    d1o[o + r] = u; d2o[o + r] = v;
+    if (d1o) { d1o[o + r] = u; d2o[o + r] = v; }
 }
 
 // mask[order[r]] = mask_ranked[r] for r < n; bytes at or past n are zero.  order is a permutation of [0, n): every byte is written once.

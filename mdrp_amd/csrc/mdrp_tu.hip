@@ -5,6 +5,7 @@
 #include "mdrp_classic.h"
 #include "mdrp_from_model.h"
 #include "mdrp_prior.h"
+#include "mdrp_prosac.h"
 #define MDRP_INST
 #include "mdrp_instances.h"
 namespace mdrp {

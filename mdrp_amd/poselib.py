@@ -272,6 +272,8 @@ def _score_rows(scores, ns, N):
     for i, r in enumerate(rows):
         if len(r) != ns[i] and len(r) != N:
             raise ValueError(f"scores: pair {i} has {ns[i]} correspondences and {len(r)} scores")
+        if np.asarray(r).dtype.kind not in "fiub":
+            raise ValueError(f"scores: pair {i} has dtype {np.asarray(r).dtype}, not real numbers")
         out[i, :ns[i]] = np.asarray(r, dtype=np.float64)[:ns[i]]
     return out
 
@@ -603,56 +605,71 @@ def _stack2(points1, points2):
     return x1, x2, ns
 
 
-def _check_baseline_options(ransac_opt):
-    """options of upstream RansacOptions that change what the baseline estimators do and are not built here"""
+def _check_baseline_options(ransac_opt, scores=None):
+    """options of upstream RansacOptions that change what the baseline estimators do and are not built here.  progressive_sampling needs the match
+    scores: with scores= it may be absent, False or True (see PRESORTED), without them it is refused."""
     ro = ransac_opt or {}
-    if ro.get("progressive_sampling"):
-        raise NotImplementedError("progressive_sampling (PROSAC) is not built (DESIGN.md 9)")
+    if ro.get("progressive_sampling") and scores is None:
+        raise NotImplementedError("progressive_sampling (PROSAC) needs the match scores: pass scores= (DESIGN.md 7e)")
     if ro.get("real_focal_check"):
         raise NotImplementedError("real_focal_check (FundamentalEstimator drops models without real focal lengths) is not built")
 
 
-def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ransac_opt=None, bundle_opt=None, device=0, budgets=None):
-    """B calibrated pairs through the 5-point estimator.  Returns (list[CameraPose], list[info dict]).  budgets: see _budget_args."""
+def _baseline_host(kind, x1, x2, ns, scores, cams1, cams2, ransac_opt, bundle_opt, device, budgets):
+    """(records, masks) of a baseline's host batch: pipeline.estimate_host, or with scores (see PRESORTED) one blocking ranked call on the device's
+    default handle (include/mdrp.h mdrp_estimate_classic_ranked)"""
+    if scores is None:
+        return pipeline.estimate_host(kind, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), ns, cams1, cams2,
+                                      device, budgets=budgets)
+    rows = _score_rows(scores, ns, x1.shape[1])  # (checked before anything touches the device)
+    return _capi.default_handle(device).estimate_classic_ranked(kind, x1, x2, rows, _capi.ransac_opt_from_dict(ransac_opt),
+                                                                _capi.bundle_opt_from_dict(bundle_opt), ns, cams1, cams2)
+
+
+def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None):
+    """B calibrated pairs through the 5-point estimator.  Returns (list[CameraPose], list[info dict]).  budgets: see _budget_args; scores: see
+    PRESORTED (not with budgets)."""
+    _no_scores_with(scores, budgets, None)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
-    _check_baseline_options(ransac_opt)
+    _check_baseline_options(ransac_opt, scores)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
     B = len(ns)
 
     def cams(c):
         return _camera_records(c, B)
 
-    res, mask = pipeline.estimate_host(_capi.RELPOSE_5PT, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, cams(cameras1), cams(cameras2), device, budgets=budgets)
+    res, mask = _baseline_host(_capi.RELPOSE_5PT, x1, x2, ns, scores, cams(cameras1), cams(cameras2), ransac_opt, bundle_opt, device, budgets)
     return _per_budget(budgets, res, mask, lambda r, m: ([CameraPose(q["model"]["q"].copy(), q["model"]["t"].copy()) for q in r],
                                                          [_info(r[i], m[i], ns[i]) for i in range(B)]))
 
 
-def estimate_fundamental_batch(points2D_1, points2D_2, ransac_opt=None, bundle_opt=None, device=0, budgets=None):
-    """B pairs through the 7-point estimator.  Returns (list[3 x 3 ndarray], list[info dict]).  budgets: see _budget_args."""
+def estimate_fundamental_batch(points2D_1, points2D_2, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None):
+    """B pairs through the 7-point estimator.  Returns (list[3 x 3 ndarray], list[info dict]).  budgets: see _budget_args; scores: see PRESORTED
+    (not with budgets)."""
+    _no_scores_with(scores, budgets, None)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
-    _check_baseline_options(ransac_opt)
+    _check_baseline_options(ransac_opt, scores)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
-    res, mask = pipeline.estimate_host(_capi.FUNDAMENTAL_7PT, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, None, None, device, budgets=budgets)
+    res, mask = _baseline_host(_capi.FUNDAMENTAL_7PT, x1, x2, ns, scores, None, None, ransac_opt, bundle_opt, device, budgets)
     return _per_budget(budgets, res, mask, lambda r, m: ([_capi.model_to_fundamental(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(len(ns))]))
 
 
-def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, ransac_opt={}, bundle_opt={}, initial_pose=None):
+def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, ransac_opt={}, bundle_opt={}, initial_pose=None, scores=None):
     """Relative pose estimation with non-linear refinement (_core.pyi:504-529; eval.py:136 — the 5-point baseline).  As in the
-    monodepth estimators, an initial pose only sets score_initial_model: ransac_relpose resets the pose itself."""
+    monodepth estimators, an initial pose only sets score_initial_model: ransac_relpose resets the pose itself.  scores (not in the reference): see
+    PRESORTED."""
     poses, infos = estimate_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], camera1, camera2,
-                                                _with_initial(initial_pose, ransac_opt), bundle_opt)
+                                                _with_initial(initial_pose, ransac_opt), bundle_opt, scores=_one_scores(scores))
     return poses[0], infos[0]
 
 
-def estimate_fundamental(points2D_1, points2D_2, ransac_opt={}, bundle_opt={}, initial_F=None):
-    """Fundamental matrix estimation with non-linear refinement (_core.pyi:309-323; the 7-point baseline)."""
+def estimate_fundamental(points2D_1, points2D_2, ransac_opt={}, bundle_opt={}, initial_F=None, scores=None):
+    """Fundamental matrix estimation with non-linear refinement (_core.pyi:309-323; the 7-point baseline).  scores (not in the reference): see PRESORTED."""
     if initial_F is not None:
         # unlike ransac_*relpose, which reset the model they are handed (an initial pose only sets score_initial_model), the reference's
         # ransac_fundamental scores the caller's F itself (DESIGN.md §9): not expressible through the flag, and no caller in the reference uses it
         raise NotImplementedError("estimate_fundamental with initial_F (score_initial_model on a caller's F) is not built")
-    Fs, infos = estimate_fundamental_batch([_as_points(points2D_1)], [_as_points(points2D_2)], ransac_opt, bundle_opt)
+    Fs, infos = estimate_fundamental_batch([_as_points(points2D_1)], [_as_points(points2D_2)], ransac_opt, bundle_opt, scores=_one_scores(scores))
     return Fs[0], infos[0]
 
 
@@ -696,16 +713,16 @@ def _pp_records(pp, B):
     return rec, pp
 
 
-def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, ransac_opt=None, bundle_opt=None, device=0, budgets=None):
+def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None):
     """B pairs through the 6-point shared-focal estimator.  pp: one principal point for all pairs or (B, 2).
-    Returns (list[ImagePair], list[info dict]).  budgets: see _budget_args."""
+    Returns (list[ImagePair], list[info dict]).  budgets: see _budget_args; scores: see PRESORTED (not with budgets)."""
+    _no_scores_with(scores, budgets, None)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
-    _check_baseline_options(ransac_opt)
+    _check_baseline_options(ransac_opt, scores)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
     B = len(ns)
     rec, ppb = _pp_records(pp, B)
-    res, mask = pipeline.estimate_host(_capi.SHARED_6PT, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt),
-                                       _capi.bundle_opt_from_dict(bundle_opt), ns, rec, rec, device, budgets=budgets)
+    res, mask = _baseline_host(_capi.SHARED_6PT, x1, x2, ns, scores, rec, rec, ransac_opt, bundle_opt, device, budgets)
 
     def build(res, mask):
         out = []
@@ -717,15 +734,15 @@ def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, r
     return _per_budget(budgets, res, mask, build)
 
 
-def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp=None, ransac_opt={}, bundle_opt={}, initial_image_pair=None):
+def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp=None, ransac_opt={}, bundle_opt={}, initial_image_pair=None, scores=None):
     """Relative pose with one unknown focal length shared by both images, 6-point solver + non-linear refinement
     (_core.pyi:531-543; /root/reference/eval_shared_f.py:161, where the fork's signature has no `pp` and the points are
     already centred: a dict in the third position is taken as ransac_opt).  An initial image pair only sets
-    score_initial_model, like the initial pose of the other estimators."""
+    score_initial_model, like the initial pose of the other estimators.  scores (not in the reference): see PRESORTED."""
     if isinstance(pp, dict):  # fork call shape: (kp1, kp2, ransac_dict, bundle_dict)
         pp, ransac_opt, bundle_opt = None, pp, (ransac_opt if ransac_opt else bundle_opt)
     pairs, infos = estimate_shared_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], pp,
-                                                             _with_initial(initial_image_pair, ransac_opt), bundle_opt)
+                                                             _with_initial(initial_image_pair, ransac_opt), bundle_opt, scores=_one_scores(scores))
     return pairs[0], infos[0]
 
 
@@ -845,6 +862,67 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
             h.estimate_batch_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), B, N,
                                     _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), n_per_pair, cams1, cams2,
                                     mask.data_ptr())
+        res = h.fetch_results(B)
+    return res, mask
+
+
+BASELINE_KINDS = {"relpose_5pt": _capi.RELPOSE_5PT, "shared_focal_6pt": _capi.SHARED_6PT, "fundamental_7pt": _capi.FUNDAMENTAL_7PT}
+
+
+def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, cameras2=None, pp=None, ransac_opt=None, bundle_opt=None, n_per_pair=None,
+                                  scores=None):
+    """estimate_batch_torch for the comparison rows, which have no depths: `points2D_*` (B, N, 2) float64 torch tensors on a ROCm device, queued on
+    that device's current torch stream.  kind: "relpose_5pt" (cameras1 / cameras2) | "shared_focal_6pt" (pp: one principal point or (B, 2); None is
+    (0, 0)) | "fundamental_7pt".  Returns (records, (B, N) uint8 mask tensor on the device) as estimate_batch_torch does.  scores (see PRESORTED): a
+    (B, N) float32 / float64 tensor on the inputs' device, one per correspondence, higher is better, or "presorted": the estimate in score order with
+    the progressive sampler of the estimator's sample size; the mask stays in the caller's order.  Without scores it is the plain estimator."""
+    import torch
+    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
+        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
+    k = BASELINE_KINDS[kind]
+    _check_baseline_options(ransac_opt, scores)
+    # (everything down to the handle is checked before anything touches the device)
+    if not (isinstance(points2D_1, torch.Tensor) and isinstance(points2D_2, torch.Tensor)):
+        raise ValueError("estimate_baseline_batch_torch needs float64 tensors on the GPU")
+    if points2D_1.ndim != 3 or points2D_1.shape[2] != 2 or points2D_2.shape != points2D_1.shape:
+        raise ValueError("shapes must be (B, N, 2), (B, N, 2)")
+    B, N = int(points2D_1.shape[0]), int(points2D_1.shape[1])
+    if isinstance(scores, str):
+        if scores != PRESORTED:
+            raise ValueError(f'scores: the only string is "{PRESORTED}", not {scores!r}')
+    elif scores is not None:
+        if not (isinstance(scores, torch.Tensor) and scores.dtype in (torch.float32, torch.float64)):
+            raise ValueError('scores must be a float32 / float64 tensor on the inputs\' device or "presorted"')
+        if tuple(scores.shape) != (B, N):
+            raise ValueError(f"scores must be {(B, N)}, one per correspondence, not {tuple(scores.shape)}")
+    x1, x2 = points2D_1.contiguous(), points2D_2.contiguous()
+    for t in (x1, x2):
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise ValueError("estimate_baseline_batch_torch needs float64 tensors on the GPU")
+        if t.device != x1.device:
+            raise ValueError("all tensors must live on the same device")
+    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
+    h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+    if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
+        n_per_pair = n_per_pair.detach().cpu().numpy()
+    cams1 = cams2 = None
+    if k == _capi.RELPOSE_5PT:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    elif k == _capi.SHARED_6PT:
+        cams1 = cams2 = _pp_records(pp, B)[0]
+    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
+    with torch.cuda.device(x1.device):
+        mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
+        if scores is None:
+            h.estimate_batch_device(k, x1.data_ptr(), x2.data_ptr(), None, None, B, N, ro, bo, n_per_pair, cams1, cams2, mask.data_ptr())
+        else:
+            sc = None
+            if not isinstance(scores, str):
+                if not (scores.is_cuda and scores.device == x1.device):
+                    raise ValueError("scores must live on the inputs' device")
+                sc = scores.to(torch.float64).contiguous()  # (float32 -> float64 is exact: the order is the caller's)
+            h.estimate_classic_ranked_device(k, x1.data_ptr(), x2.data_ptr(), None if sc is None else sc.data_ptr(), B, N, ro, bo, n_per_pair, cams1, cams2,
+                                             mask.data_ptr())
         res = h.fetch_results(B)
     return res, mask
 
