@@ -681,4 +681,5 @@ int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_
 }
 #endif
 #include "mdrp_classic_ranked.h"
+#include "mdrp_classic_models.h"
 #endif

@@ -32,6 +32,8 @@ EXPORTS = (
 )
 # the entry points of include/mdrp_classic_ranked.h, the extension header mdrp.h includes (EXPORTS above is mdrp.h's own list)
 EXPORTS_CLASSIC_RANKED = ("mdrp_estimate_classic_ranked", "mdrp_estimate_classic_ranked_async", "mdrp_prosac_samples_k")
+# the entry points of include/mdrp_classic_models.h, the second extension header mdrp.h includes: the baselines from a caller's model
+EXPORTS_CLASSIC_MODELS = ("mdrp_refine_classic", "mdrp_refine_classic_async", "mdrp_estimate_classic_prior", "mdrp_estimate_classic_prior_async")
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
 STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
@@ -207,6 +209,15 @@ def load_library():
             lib.mdrp_estimate_classic_ranked_async.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                                C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
             lib.mdrp_prosac_samples_k.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, ip, C.c_int, vp]
+        if hasattr(lib, "mdrp_refine_classic"):  # (an older ABI-0.6 library through MDRP_LIB has no baselines from a model: Handle._classic_models_fn raises)
+            lib.mdrp_refine_classic.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp, dp, ip]
+            lib.mdrp_refine_classic_async.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                      C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, dp, ip]
+            lib.mdrp_estimate_classic_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                        C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp]
+            lib.mdrp_estimate_classic_prior_async.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
+                                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp]
         if hasattr(lib, "mdrp_gather_matches_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked front end: Handle._ranked_front_end_fn raises)
             lib.mdrp_gather_matches_ranked.argtypes = [vp, C.POINTER(Matches), vp, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
             lib.mdrp_estimate_matches_ranked_async.argtypes = [vp, C.c_int, C.POINTER(Matches), vp, C.c_int, C.c_int, vp, vp, C.POINTER(RansacOpt),
@@ -704,6 +715,79 @@ class Handle:
         _check(self._lib, self._classic_ranked_fn("mdrp_prosac_samples_k")(self._h, int(seed), int(n), int(sample_size), int(max_prosac_iterations), _ptr(lens),
                                                                            len(lens), _ptr(out)))
         return out
+
+    # ---- the 5- / 6- / 7-point baselines from a caller's model (include/mdrp_classic_models.h).  Arguments go to the library as they are: the library checks them.
+    def _classic_models_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the baselines took models (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    @staticmethod
+    def _classic_host_args(x1, x2, models, n_per_pair, cam1, cam2, what):
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+            raise ValueError("expected x1,x2 (B,N,2)")
+        B = x1.shape[0]
+        models = None if models is None else np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
+        if models is not None and len(models) != B:
+            raise ValueError(f"expected {B} {what}, got {len(models)}")
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        return x1, x2, models, npp, c1, c2
+
+    def refine_classic(self, kind, x1, x2, models, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
+        """refine_batch for a baseline (kind 3, 4, 5): B models (MODEL_DTYPE, in the caller's units; a fundamental matrix in the first nine doubles)
+        against B pairs, host (numpy) buffers: (records, masks (B, N) uint8 or None, initial score (B,) float64, initial inlier count (B,) int32)"""
+        x1, x2, models, npp, c1, c2 = self._classic_host_args(x1, x2, models, n_per_pair, cam1, cam2, "models")
+        B, N = x1.shape[:2]
+        out = np.zeros(B, dtype=RESULT_DTYPE)
+        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        score0, inl0 = np.zeros(B), np.zeros(B, dtype=np.int32)
+        _check(self._lib, self._classic_models_fn("mdrp_refine_classic")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
+                                                                         C.byref(ropt), C.byref(bopt), _ptr(models), int(stages), _ptr(out), _ptr(mask),
+                                                                         _ptr(score0), _ptr(inl0)))
+        return out, mask, score0, inl0
+
+    def refine_classic_device(self, kind, x1_ptr, x2_ptr, batch, n_max, models_ptr, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None, cam1=None,
+                              cam2=None, mask_ptr=None, initial_score_ptr=None, initial_inliers_ptr=None):
+        """the same on device pointers (ints), queued on the handle's stream; models_ptr: batch x 96 bytes; initial_score_ptr / initial_inliers_ptr:
+        batch float64 / int32 on the device, or None.  Records: fetch_results / copy_results_device."""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _check(self._lib, self._classic_models_fn("mdrp_refine_classic_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), int(batch), int(n_max), _ptr(npp), _ptr(c1),
+                                                                               _ptr(c2), C.byref(ropt), C.byref(bopt), vp(models_ptr), int(stages), vp(mask_ptr),
+                                                                               vp(initial_score_ptr), vp(initial_inliers_ptr)))
+
+    def estimate_classic_prior(self, kind, x1, x2, priors, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True, prior_space=0):
+        """estimate_batch of a baseline (kind 3, 4, 5) with one prior (MODEL_DTYPE; a NaN first double: none) per pair, host (numpy) buffers;
+        prior_space 0: the caller's units, 1: the estimator's normalised coordinates.  (records, masks (B, N) uint8 or None)"""
+        x1, x2, priors, npp, c1, c2 = self._classic_host_args(x1, x2, priors, n_per_pair, cam1, cam2, "priors")
+        B, N = x1.shape[:2]
+        out = np.zeros(B, dtype=RESULT_DTYPE)
+        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        _check(self._lib, self._classic_models_fn("mdrp_estimate_classic_prior")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
+                                                                                 C.byref(ropt), C.byref(bopt), _ptr(priors), int(prior_space), _ptr(out), _ptr(mask)))
+        return out, mask
+
+    def estimate_classic_prior_device(self, kind, x1_ptr, x2_ptr, batch, n_max, priors_ptr, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, mask_ptr=None,
+                                      prior_space=0):
+        """the same on device pointers (ints), queued on the handle's stream; priors_ptr: batch x 96 bytes.  Records: fetch_results / copy_results_device."""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _check(self._lib, self._classic_models_fn("mdrp_estimate_classic_prior_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), int(batch), int(n_max), _ptr(npp),
+                                                                                       _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(priors_ptr),
+                                                                                       int(prior_space), vp(mask_ptr)))
 
     def rank_scores(self, scores, n_per_pair=None):
         """k_rank on host scores (B, N): order (B, N) int32, -1 at and past n"""

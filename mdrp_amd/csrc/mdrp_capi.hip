@@ -9,7 +9,8 @@
 #include "mdrp_from_model.h"
 #include "mdrp_prior.h"
 #include "mdrp_prosac.h"
-// MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
+#include "mdrp_classic_models.h"
+// MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior, kc_from_model, kc_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
 #define MDRP_INST extern
@@ -20,6 +21,7 @@ MDRP_INSTANCES_FINAL_256
 MDRP_INSTANCES_CLASSIC
 MDRP_INSTANCES_FROM_MODEL
 MDRP_INSTANCES_PRIOR
+MDRP_INSTANCES_CLASSIC_MODELS
 }
 #endif
 
@@ -383,7 +385,8 @@ struct PassIn {
     const HostSrc *host;  // (or null)
     int batch_call;       // pairs of the whole API call
     const BudgetOut *bud; // (or null)
-    const Model *priors;  // device memory, one per pair of the pass, or null (mdrp_estimate_batch_prior; never with `host` or `bud`)
+    const Model *priors;  // device memory, one per pair of the pass, or null (mdrp_estimate_batch_prior, mdrp_estimate_classic_prior; never with `host` or `bud`)
+    int prior_space;      // the baselines' priors: 0 = the caller's units, 1 = the estimator's normalised coordinates (include/mdrp_classic_models.h)
     const uint64_t *prosac; // ranked call: max_prosac_iterations of the progressive sampler (mdrp_prosac.h), or null: the uniform sampler
 };
 
@@ -624,6 +627,16 @@ struct Pass : PassIn {
     // a call with priors: every pair that has one starts from the state ransac<> is in after scoring and LO-refining it (k_prior, mdrp_prior.h).
     // On the main stream behind k_prep: every reader of the pair states is ordered behind this stream's first solver launch.
     void prior() {
+        if (classic) { // kc_prior (mdrp_classic_models.h); the pass's output mask is clm_lo's subset mask: kc_final rewrites every byte of it
+#define MDRP_KC_PRIOR_LAUNCH(CK)                                                                                                          \
+    hipLaunchKernelGGL((kc_prior<CK>), dim3(batch), dim3(CLASSIC_MODEL_THREADS), clm_list_bytes, s, rp, h->st.as<PairState>(),            \
+                       (const double *)h->pts.as<double>(), priors, prior_space, mask_dev, clm_list_stride)
+            if (kind == MDRP_RELPOSE_5PT) MDRP_KC_PRIOR_LAUNCH(CLASSIC_RELPOSE);
+            else if (kind == MDRP_SHARED_6PT) MDRP_KC_PRIOR_LAUNCH(CLASSIC_SHARED);
+            else MDRP_KC_PRIOR_LAUNCH(CLASSIC_FUND);
+#undef MDRP_KC_PRIOR_LAUNCH
+            return;
+        }
 #define MDRP_PRIOR_LAUNCH(K, S)                                                                                                                  \
     hipLaunchKernelGGL((k_prior<K, S>), dim3(batch), dim3(PRIOR_THREADS), lm_list_bytes(n_max), s, rp, h->st.as<PairState>(),                     \
                        (const double *)h->pts.as<double>(), (const double *)h->dep.as<double>(), priors, lm_list_stride(n_max),                  \
@@ -1110,9 +1123,9 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
                     int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
                     const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr,
                     const uint64_t *budgets = nullptr, int n_budgets = 0, const Model *priors = nullptr /*[batch] in device memory*/,
-                    const uint64_t *prosac = nullptr /*ranked call: max_prosac_iterations*/) {
+                    const uint64_t *prosac = nullptr /*ranked call: max_prosac_iterations*/, int prior_space = 0 /*the baselines' priors*/) {
     if (int rc = estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, ro, bo)) return rc;
-    if (priors && (host || budgets || kind > MDRP_VARYING_FOCAL)) { g_err = "priors: device-resident monodepth calls without budgets only"; return MDRP_ERR_INVALID; }
+    if (priors && (host || budgets)) { g_err = "priors: device-resident calls without budgets only"; return MDRP_ERR_INVALID; }
     if (prosac && (host || budgets || priors)) { g_err = "ranked: device-resident calls without budgets or priors only"; return MDRP_ERR_INVALID; }
     h->last_budgets = n_budgets;
     if (h->fuse_disabled && --h->fuse_retry_in <= 0) h->fuse_disabled = false; // once per API call (not per pass): the handle tries the fused tail again
@@ -1154,7 +1167,7 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
         const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + o1, batch};
         const PassIn in{kind, x1 + o2, x2 + o2, d1 ? d1 + o1 : nullptr, d2 ? d2 + o1 : nullptr, nb, n_max, n_host.data() + p0, cam1 ? cam1 + p0 : nullptr,
                         cam2 ? cam2 + p0 : nullptr, ro, bo, chunk_cap, mask + o1, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch,
-                        budgets ? &bud : nullptr, priors ? priors + p0 : nullptr, prosac};
+                        budgets ? &bud : nullptr, priors ? priors + p0 : nullptr, prior_space, prosac};
         if ((rc = run_pass(h, in))) return rc;
     }
     if (budgets) {
@@ -1526,13 +1539,20 @@ int mdrp_estimate_batch_prior(mdrp_handle *h, int kind, int mem_space, const dou
 } // extern "C"
 
 // ---- refine and verify caller-supplied models (include/mdrp.h; mdrp_from_model.h)
-// k_prep as the estimators launch it (no MFMA fragments, no sample tables, score_initial = 0), then ONE launch of k_from_model on the handle's stream:
-// nothing else of a pass is allocated or run.  Pointers are device memory, `models` included; initial_* may be null.
-static int refine_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
-                         const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
-                         const Model *models, int stages, uint8_t *mask_dev, double *init_score, int32_t *init_inl) {
+// What mdrp_refine_batch and mdrp_refine_classic share in front of their one kernel: the handle's counters and result buffers, the per-call parameters
+// in one block, the record / state buffers, the mask (the caller's or the handle's), the run parameters, and the events around the launch.
+struct RefineStage {
+    const int32_t *nper, *table_of;
+    const CamDev *cam1, *cam2;
+    uint8_t *mask;
+    RunParams rp;
+    hipEvent_t f0, f1; // reported as the final refinement's time (mdrp_stats::final_ms / final_launches)
+};
+// returns MDRP_OK with st.mask == nullptr for an empty batch (nothing to launch)
+static int refine_stage(mdrp_handle *h, int kind, int est_shift, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                        const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, RefineStage &st) {
     hipStream_t s = h->stream;
-    const int est_shift = (kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0;
+    st.mask = nullptr;
     h->last_budgets = 0;
     h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
     int rc;
@@ -1540,39 +1560,59 @@ static int refine_device(mdrp_handle *h, int kind, const double *x1, const doubl
     HIPCHK(hipMemsetAsync(h->lm_stats.p, 0, LM_STATS_BYTES, s));
     if (batch == 0) return MDRP_OK;
     const size_t b = (size_t)batch, n = (size_t)n_max;
+    const bool mono = kind <= MDRP_VARYING_FOCAL;
     // per-call parameters in one block: cameras 1 | cameras 2 | table of pair (zeros: there are no sample tables) | n per pair.  Staged in pageable
     // memory (the copy has left it when hipMemcpyAsync returns): an asynchronous call may be followed by the next one before the stream has drained
     const size_t off_cam2 = sizeof(CamDev) * b, off_tof = 2 * sizeof(CamDev) * b, off_nper = off_tof + sizeof(int32_t) * b, bytes = off_nper + sizeof(int32_t) * b;
     std::vector<unsigned char> params(bytes, 0);
-    if (kind == MDRP_CALIB) { std::memcpy(params.data(), cam1, sizeof(CamDev) * b); std::memcpy(params.data() + off_cam2, cam2, sizeof(CamDev) * b); }
+    if (kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT) { // MDRP_SHARED_6PT reads the principal point from cam1 only: cam2 may be NULL there
+        std::memcpy(params.data(), cam1, sizeof(CamDev) * b);
+        std::memcpy(params.data() + off_cam2, cam2 ? cam2 : cam1, sizeof(CamDev) * b);
+    }
     int32_t *nper = reinterpret_cast<int32_t *>(params.data() + off_nper);
     for (int i = 0; i < batch; ++i) nper[i] = n_per_pair ? n_per_pair[i] : n_max;
-    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * b * n)) || (rc = h->dep.ensure(sizeof(double) * 2 * b * n)) || (rc = h->st.ensure(sizeof(PairState) * b)) ||
-        (rc = h->params.ensure(bytes)))
+    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * b * std::max<size_t>(n, 1))) || (mono && (rc = h->dep.ensure(sizeof(double) * 2 * b * n))) ||
+        (rc = h->st.ensure(sizeof(PairState) * b)) || (rc = h->params.ensure(bytes)))
         return rc;
     uint8_t *mask = mask_dev;
-    if (!mask) {
+    if (!mask) { // (the baselines' kernel uses the mask as its LO's subset mask as well)
         if ((rc = h->mask.ensure(b * std::max(n_max, 1)))) return rc;
         mask = h->mask.as<uint8_t>();
     }
     unsigned char *pd = h->params.as<unsigned char>();
     HIPCHK(hipMemcpyAsync(pd, params.data(), bytes, hipMemcpyHostToDevice, s));
-
-    RunParams rp;
+    st.nper = reinterpret_cast<const int32_t *>(pd + off_nper); st.table_of = reinterpret_cast<const int32_t *>(pd + off_tof);
+    st.cam1 = reinterpret_cast<const CamDev *>(pd); st.cam2 = reinterpret_cast<const CamDev *>(pd + off_cam2);
+    RunParams &rp = st.rp;
     std::memset(&rp, 0, sizeof rp);
     rp.kind = kind; rp.solver = solver_for(kind, est_shift); rp.est_shift = est_shift;
     rp.batch = batch; rp.n_max = n_max;
-    rp.weight_sampson = ro->monodepth_weight_sampson > 0.0f ? (double)ro->monodepth_weight_sampson : 0.0;
+    if (!mono) { rp.mps = sched::model_slots(kind); rp.sample_sz = sched::sample_size(kind); } // (kc_prep: a pair of fewer records than the sample size is empty)
+    rp.weight_sampson = (mono && ro->monodepth_weight_sampson > 0.0f) ? (double)ro->monodepth_weight_sampson : 0.0;
     rp.final_max_it = (int)std::min<uint64_t>(bo->max_iterations, 1u << 30); rp.final_loss = bo->loss_type;
     rp.grad_tol = bo->gradient_tol; rp.step_tol = bo->step_tol; rp.lambda0 = bo->initial_lambda;
     rp.lambda_min = bo->min_lambda; rp.lambda_max = bo->max_lambda;
-    hipLaunchKernelGGL(k_prep, dim3(batch), dim3(256), 0, s, rp, x1, x2, d1, d2, reinterpret_cast<const int32_t *>(pd + off_nper),
-                       reinterpret_cast<const int32_t *>(pd + off_tof), reinterpret_cast<const CamDev *>(pd), reinterpret_cast<const CamDev *>(pd + off_cam2),
+    if ((rc = get_events(h, &st.f0, &st.f1, 3))) return rc;
+    st.mask = mask;
+    return MDRP_OK;
+}
+
+// k_prep as the estimators launch it (no MFMA fragments, no sample tables, score_initial = 0), then ONE launch of k_from_model on the handle's stream:
+// nothing else of a pass is allocated or run.  Pointers are device memory, `models` included; initial_* may be null.
+static int refine_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
+                         const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
+                         const Model *models, int stages, uint8_t *mask_dev, double *init_score, int32_t *init_inl) {
+    hipStream_t s = h->stream;
+    const int est_shift = (kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0;
+    RefineStage st;
+    if (int rc = refine_stage(h, kind, est_shift, batch, n_max, n_per_pair, cam1, cam2, ro, bo, mask_dev, st)) return rc;
+    if (!st.mask) return MDRP_OK;
+    const RunParams &rp = st.rp;
+    uint8_t *mask = st.mask;
+    hipLaunchKernelGGL(k_prep, dim3(batch), dim3(256), 0, s, rp, x1, x2, d1, d2, st.nper, st.table_of, st.cam1, st.cam2,
                        ro->max_epipolar_error, ro->max_reproj_error, bo->loss_scale, h->pts.as<double>(), h->dep.as<double>(), h->st.as<PairState>(),
                        (uint4 *)nullptr);
-    hipEvent_t f0, f1; // reported as the final refinement's time (mdrp_stats::final_ms / final_launches)
-    if ((rc = get_events(h, &f0, &f1, 3))) return rc;
-    HIPCHK(hipEventRecord(f0, s));
+    HIPCHK(hipEventRecord(st.f0, s));
     const size_t smem = lm_final_list_bytes(n_max);
     const int stride = lm_list_stride(n_max), midx = lm_mask_index_on(n_max);
 #define MDRP_FROM_MODEL_LAUNCH(K, S)                                                                                                                      \
@@ -1584,7 +1624,7 @@ static int refine_device(mdrp_handle *h, int kind, const double *x1, const doubl
     else if (kind == MDRP_SHARED_FOCAL) MDRP_FROM_MODEL_LAUNCH(1, false);
     else MDRP_FROM_MODEL_LAUNCH(2, false);
 #undef MDRP_FROM_MODEL_LAUNCH
-    HIPCHK(hipEventRecord(f1, s));
+    HIPCHK(hipEventRecord(st.f1, s));
     HIPCHK(hipGetLastError());
     return MDRP_OK;
 }
@@ -2891,6 +2931,165 @@ int mdrp_prosac_samples_k(mdrp_handle *h, uint64_t seed, int n, int sample_size,
 
 int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks, uint32_t *out) {
     return mdrp_prosac_samples_k(h, seed, n, 3, max_prosac_iterations, chunk_lens, n_chunks, out);
+}
+
+} // extern "C"
+
+// ---- the baselines from a caller's model (include/mdrp_classic_models.h; mdrp_classic_models.h)
+static const char *classic_models_kind(int kind) {
+    return (kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT)
+               ? nullptr
+               : "classic models: only the baselines (MDRP_RELPOSE_5PT, MDRP_SHARED_6PT, MDRP_FUNDAMENTAL_7PT); mdrp_refine_batch and mdrp_estimate_batch_prior take the monodepth estimators";
+}
+
+// kc_prep as the estimators launch it (no MFMA fragments, no sample tables, score_initial = 0), then ONE launch of kc_from_model on the handle's stream
+// (refine_device's shape, through the same refine_stage).  Pointers are device memory, `models` included; initial_* may be null.
+static int refine_classic_device(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                 const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, const Model *models,
+                                 int stages, uint8_t *mask_dev, double *init_score, int32_t *init_inl) {
+    hipStream_t s = h->stream;
+    RefineStage st;
+    if (int rc = refine_stage(h, kind, 0, batch, n_max, n_per_pair, cam1, cam2, ro, bo, mask_dev, st)) return rc;
+    if (!st.mask) return MDRP_OK;
+    const RunParams &rp = st.rp;
+    uint8_t *mask = st.mask;
+    hipLaunchKernelGGL(kc_prep, dim3(batch), dim3(256), 0, s, rp, x1, x2, st.nper, st.table_of, st.cam1, st.cam2, ro->max_epipolar_error, bo->loss_scale,
+                       h->pts.as<double>(), h->st.as<PairState>(), (uint4 *)nullptr);
+    HIPCHK(hipEventRecord(st.f0, s));
+    const int stride = lm_list_stride(n_max);
+    const size_t smem = (size_t)2 * stride * sizeof(uint16_t);
+#define MDRP_KC_FROM_MODEL_LAUNCH(CK)                                                                                                                   \
+    hipLaunchKernelGGL((kc_from_model<CK>), dim3(batch), dim3(CLASSIC_MODEL_THREADS), smem, s, rp, (const PairState *)h->st.as<PairState>(),            \
+                       (const double *)h->pts.as<double>(), models, stages, mask, h->results.as<ResultDev>(), init_score, init_inl, stride)
+    if (kind == MDRP_RELPOSE_5PT) MDRP_KC_FROM_MODEL_LAUNCH(CLASSIC_RELPOSE);
+    else if (kind == MDRP_SHARED_6PT) MDRP_KC_FROM_MODEL_LAUNCH(CLASSIC_SHARED);
+    else MDRP_KC_FROM_MODEL_LAUNCH(CLASSIC_FUND);
+#undef MDRP_KC_FROM_MODEL_LAUNCH
+    HIPCHK(hipEventRecord(st.f1, s));
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+// what the four entry points refuse before any device work (`who`: "refine_classic" / "classic_prior")
+static int check_classic_models_args(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                     const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
+                                     const mdrp_model *models) {
+    const char *why = nullptr;
+    if (!h || !ro || !bo) why = "invalid argument";
+    else if ((why = classic_models_kind(kind))) {}
+    else if (batch < 0 || n_max < 0) why = "classic models: a negative size";
+    else if (batch > 0 && !models) why = "classic models: models / prior is NULL";
+    else if (batch > 0 && n_max > 0 && (!x1 || !x2)) why = "classic models: correspondences are NULL";
+    else if (kind == MDRP_RELPOSE_5PT && batch > 0 && (!cam1 || !cam2)) why = "calibrated estimator needs cameras";
+    else if (kind == MDRP_SHARED_6PT && batch > 0 && !cam1) why = "the 6-point estimator needs the principal point in cam1";
+    for (int i = 0; !why && n_per_pair && i < batch; ++i)
+        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+static int check_stages(int stages) {
+    if (stages < 0 || stages > (MDRP_STAGE_LO | MDRP_STAGE_INLIERS)) { g_err = "refine: stages must be a combination of MDRP_STAGE_LO and MDRP_STAGE_INLIERS"; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+// host buffers of a blocking call: plain copies on the handle's stream into the handle's staging buffers (mdrp_refine_batch)
+static int stage_classic_host(mdrp_handle *h, const double *&x1, const double *&x2, const Model *&models, int batch, int n_max) {
+    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->fm_models.ensure(sizeof(Model) * b))) return rc;
+    if (np > 0) {
+        HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(h->fm_models.p, models, sizeof(Model) * b, hipMemcpyHostToDevice, s));
+    x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
+    models = h->fm_models.as<Model>();
+    return MDRP_OK;
+}
+
+extern "C" {
+
+int mdrp_refine_classic_async(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                              const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                              const mdrp_model *models_dev, int stages, uint8_t *inlier_mask_dev, double *initial_score_dev, int32_t *initial_inliers_dev) {
+    if (int rc = check_classic_models_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev)) return rc;
+    if (int rc = check_stages(stages)) return rc;
+    MDRP_ENTER(h);
+    const int rc = refine_classic_device(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, reinterpret_cast<const Model *>(models_dev), stages,
+                                         inlier_mask_dev, initial_score_dev, initial_inliers_dev);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_refine_classic(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                        const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const mdrp_model *models,
+                        int stages, mdrp_result *out, uint8_t *inlier_mask, double *initial_score, int32_t *initial_inliers) {
+    if (int rc = check_classic_models_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models)) return rc;
+    if (int rc = check_stages(stages)) return rc;
+    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
+    hipStream_t s = h->stream;
+    int rc;
+    const Model *models_dev = reinterpret_cast<const Model *>(models);
+    if (use_host && batch > 0 && (rc = stage_classic_host(h, x1, x2, models_dev, batch, n_max))) return drain_and_return(h, rc);
+    // the start-model scores are host outputs whatever mem_space says: a buffer of the handle, copied back
+    const size_t off_inl = sizeof(double) * b;
+    if ((initial_score || initial_inliers) && (rc = h->fm_init.ensure(off_inl + sizeof(int32_t) * b + 16))) return rc;
+    double *is_dev = initial_score ? h->fm_init.as<double>() : nullptr;
+    int32_t *ii_dev = initial_inliers ? reinterpret_cast<int32_t *>(h->fm_init.as<unsigned char>() + off_inl) : nullptr;
+    rc = refine_classic_device(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev, stages, use_host ? nullptr : inlier_mask, is_dev, ii_dev);
+    if (rc) return drain_and_return(h, rc);
+    hipError_t e = hipSuccess;
+    if (use_host && inlier_mask && np > 0) e = hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && is_dev && batch > 0) e = hipMemcpyAsync(initial_score, is_dev, sizeof(double) * b, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && ii_dev && batch > 0) e = hipMemcpyAsync(initial_inliers, ii_dev, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) { g_err = "copy of the masks or start-model scores failed"; return drain_and_return(h, MDRP_ERR_HIP); }
+    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+// the estimator's own refusals for the kind come behind the argument checks (estimate_refusals: real_focal_check, progressive_sampling)
+static int check_classic_prior_args(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                    const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
+                                    const mdrp_model *prior, int prior_space) {
+    if (int rc = check_classic_models_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ro, bo, prior)) return rc;
+    if (prior_space != 0 && prior_space != 1) { g_err = "classic_prior: prior_space must be 0 (the caller's units) or 1 (the estimator's normalised coordinates)"; return MDRP_ERR_INVALID; }
+    return estimate_refusals(h, kind, nullptr, nullptr, batch, n_max, cam1, cam2, ro, bo);
+}
+
+int mdrp_estimate_classic_prior_async(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                      const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                      const mdrp_model *prior_dev, int prior_space, uint8_t *inlier_mask_dev) {
+    if (int rc = check_classic_prior_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior_dev, prior_space)) return rc;
+    MDRP_ENTER(h);
+    const int rc = estimate_device(h, kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, nullptr, 0,
+                                   reinterpret_cast<const Model *>(prior_dev), nullptr, prior_space);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+int mdrp_estimate_classic_prior(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                const mdrp_model *prior, int prior_space, mdrp_result *out, uint8_t *inlier_mask) {
+    if (int rc = check_classic_prior_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior, prior_space)) return rc;
+    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    const size_t np = (size_t)batch * n_max;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
+    int rc;
+    const Model *prior_dev = reinterpret_cast<const Model *>(prior);
+    if (use_host && batch > 0 && (rc = stage_classic_host(h, x1, x2, prior_dev, batch, n_max))) return drain_and_return(h, rc);
+    rc = estimate_device(h, kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask, nullptr, nullptr, 0,
+                         prior_dev, nullptr, prior_space);
+    if (rc) return drain_and_return(h, rc);
+    if (use_host && inlier_mask && np > 0 && hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+        g_err = "copy of the inlier masks failed";
+        return drain_and_return(h, MDRP_ERR_HIP);
+    }
+    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
+    return rc ? drain_and_return(h, rc) : rc;
 }
 
 } // extern "C"

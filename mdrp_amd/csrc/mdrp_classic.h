@@ -841,6 +841,30 @@ __global__ __launch_bounds__(T, 2) void kc_lo(RunParams rp, const PairState *__r
 }
 
 // ------------------------------------------------------------------------------------------------ final
+// the estimators' way out of their normalised coordinates (cfinal_pair; kc_from_model, mdrp_classic_models.h): the focal back to pixels,
+// the fundamental matrix back to pixel coordinates with unit Frobenius norm
+template <int CK>
+__device__ __forceinline__ void classic_unnormalize(Model &best, const PairState &ps) {
+    if (CK == CLASSIC_FUND) { // F <- T2' F T1, T = [1/s 0 -cx/s; 0 1/s -cy/s; 0 0 1], unit Frobenius norm
+        double *F = model_F(best);
+        const double is = 1.0 / ps.norm;
+        const double T1[9] = {is, 0, -ps.cen[0] * is, 0, is, -ps.cen[1] * is, 0, 0, 1}, T2[9] = {is, 0, -ps.cen[2] * is, 0, is, -ps.cen[3] * is, 0, 0, 1};
+        double M[9], O[9], nrm = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) M[3 * i + j] = F[3 * i] * T1[j] + F[3 * i + 1] * T1[3 + j] + F[3 * i + 2] * T1[6 + j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { O[3 * i + j] = T2[i] * M[j] + T2[3 + i] * M[3 + j] + T2[6 + i] * M[6 + j]; nrm += O[3 * i + j] * O[3 * i + j]; }
+        nrm = 1.0 / sqrt(nrm);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) F[i] = O[i] * nrm;
+    }
+    if (CK == CLASSIC_SHARED) { best.f1 *= ps.norm; best.f2 *= ps.norm; } // back to pixels
+}
+
 // ransac<> tail + get_inliers + the estimator's inlier-only refinement with the user's BundleOptions (estimate_relative_pose
 // @0x21f800: if more than 5 inliers; estimate_fundamental @0x221a00: more than 7, then F <- T2' F T1 / |.|)
 template <int CK, int T>
@@ -874,24 +898,7 @@ __device__ void cfinal_pair(const RunParams &rp, const PairState &ps, const doub
         f.grad_tol = rp.grad_tol; f.step_tol = rp.step_tol; f.lambda0 = rp.lambda0; f.lambda_min = rp.lambda_min; f.lambda_max = rp.lambda_max;
         clm_refine<CK, T>(best, pp, ps.n, mask, f, scratch, cl);
     }
-    if (CK == CLASSIC_FUND) { // F <- T2' F T1, T = [1/s 0 -cx/s; 0 1/s -cy/s; 0 0 1], unit Frobenius norm
-        double *F = model_F(best);
-        const double is = 1.0 / ps.norm;
-        const double T1[9] = {is, 0, -ps.cen[0] * is, 0, is, -ps.cen[1] * is, 0, 0, 1}, T2[9] = {is, 0, -ps.cen[2] * is, 0, is, -ps.cen[3] * is, 0, 0, 1};
-        double M[9], O[9], nrm = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) M[3 * i + j] = F[3 * i] * T1[j] + F[3 * i + 1] * T1[3 + j] + F[3 * i + 2] * T1[6 + j];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { O[3 * i + j] = T2[i] * M[j] + T2[3 + i] * M[3 + j] + T2[6 + i] * M[6 + j]; nrm += O[3 * i + j] * O[3 * i + j]; }
-        nrm = 1.0 / sqrt(nrm);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) F[i] = O[i] * nrm;
-    }
-    if (CK == CLASSIC_SHARED) { best.f1 *= ps.norm; best.f2 *= ps.norm; } // back to pixels
+    classic_unnormalize<CK>(best, ps);
     res.model = best;
     if (threadIdx.x == 0) results[row.out] = res;
 }

@@ -4,6 +4,7 @@
 //   group 3:     the kernels of the 5- / 6- / 7-point baselines (mdrp_classic.h), their progressive sampler included (mdrp_prosac.h)
 //   group 4:     k_from_model<KIND, SHIFT> for the four LM estimators (mdrp_from_model.h)
 //   group 5:     k_prior<KIND, SHIFT> for the four LM estimators (mdrp_prior.h)
+//   group 6:     kc_from_model<CK> and kc_prior<CK> for the three baselines (mdrp_classic_models.h)
 #pragma once
 namespace mdrp {
 #define MDRP_FINAL_PARAMS RunParams, PairState *, const double *, const double *, uint8_t *, ResultDev *, int, int, unsigned long long *, const int32_t *, int32_t *, \
@@ -30,6 +31,13 @@ namespace mdrp {
 
 #define MDRP_PRIOR_ONE(K, S) MDRP_INST template __global__ void k_prior<K, S>(RunParams, PairState *, const double *, const double *, const Model *, int, unsigned long long *);
 #define MDRP_INSTANCES_PRIOR MDRP_PRIOR_ONE(0, false) MDRP_PRIOR_ONE(0, true) MDRP_PRIOR_ONE(1, false) MDRP_PRIOR_ONE(2, false)
+
+#define MDRP_KC_FROM_MODEL_ONE(CK) MDRP_INST template __global__ void kc_from_model<CK>(RunParams, const PairState *, const double *, const Model *, int, uint8_t *, ResultDev *, \
+                                                                                        double *, int32_t *, int);
+#define MDRP_KC_PRIOR_ONE(CK) MDRP_INST template __global__ void kc_prior<CK>(RunParams, PairState *, const double *, const Model *, int, uint8_t *, int);
+#define MDRP_INSTANCES_CLASSIC_MODELS                                                                                    \
+    MDRP_KC_FROM_MODEL_ONE(CLASSIC_RELPOSE) MDRP_KC_FROM_MODEL_ONE(CLASSIC_SHARED) MDRP_KC_FROM_MODEL_ONE(CLASSIC_FUND) \
+    MDRP_KC_PRIOR_ONE(CLASSIC_RELPOSE) MDRP_KC_PRIOR_ONE(CLASSIC_SHARED) MDRP_KC_PRIOR_ONE(CLASSIC_FUND)
 
 #define MDRP_INSTANCES_FINAL_64 MDRP_FINAL_KINDS(MDRP_FINAL_ONE, 64)
 #define MDRP_INSTANCES_FINAL_256 MDRP_FINAL_KINDS(MDRP_FINAL_ONE, 256)

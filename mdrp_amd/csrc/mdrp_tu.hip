@@ -6,6 +6,7 @@
 #include "mdrp_from_model.h"
 #include "mdrp_prior.h"
 #include "mdrp_prosac.h"
+#include "mdrp_classic_models.h"
 #define MDRP_INST
 #include "mdrp_instances.h"
 namespace mdrp {
@@ -19,7 +20,9 @@ MDRP_INSTANCES_CLASSIC
 MDRP_INSTANCES_FROM_MODEL
 #elif MDRP_TU == 5
 MDRP_INSTANCES_PRIOR
+#elif MDRP_TU == 6
+MDRP_INSTANCES_CLASSIC_MODELS
 #else
-#error "MDRP_TU must be 1 (k_final, 64 lanes), 2 (k_final, 256 lanes), 3 (5- / 6- / 7-point baselines), 4 (k_from_model) or 5 (k_prior)"
+#error "MDRP_TU must be 1 (k_final, 64 lanes), 2 (k_final, 256 lanes), 3 (5- / 6- / 7-point baselines), 4 (k_from_model), 5 (k_prior) or 6 (kc_from_model, kc_prior)"
 #endif
 } // namespace mdrp

@@ -615,9 +615,50 @@ def _check_baseline_options(ransac_opt, scores=None):
         raise NotImplementedError("real_focal_check (FundamentalEstimator drops models without real focal lengths) is not built")
 
 
-def _baseline_host(kind, x1, x2, ns, scores, cams1, cams2, ransac_opt, bundle_opt, device, budgets):
+# priors=[...] on a baseline's *_batch entry point (prior= on the single-pair forms): _prior_records' semantics for the 5-, 6- and 7-point estimators
+# (include/mdrp_classic_models.h: mdrp_estimate_classic_prior).  A prior is what the estimator returns: a CameraPose (5-point), an
+# ImagePair (6-point; the focal is camera1's, in pixels) or a 3 x 3 fundamental matrix for pixel coordinates (7-point); None is a pair without one.
+def _baseline_model_records(models, kind, B, what):
+    """list of CameraPose / ImagePair / 3 x 3 arrays (None: a NaN record), or a MODEL_DTYPE array -> [B] MODEL_DTYPE records in the caller's units"""
+    if isinstance(models, np.ndarray) and models.dtype == _capi.MODEL_DTYPE:
+        rec = np.ascontiguousarray(models).reshape(-1)
+    else:
+        if kind == _capi.FUNDAMENTAL_7PT and isinstance(models, np.ndarray) and models.ndim == 3:
+            models = [models[i] for i in range(models.shape[0])]
+        if isinstance(models, (np.ndarray, str)) or not hasattr(models, "__len__"):
+            raise ValueError(f"{what}: a list with one model per pair, or a numpy array of _capi.MODEL_DTYPE")
+        models = list(models)
+        rec = np.zeros(len(models), dtype=_capi.MODEL_DTYPE)
+        rec["q"] = np.nan
+        rec["scale"] = rec["f1"] = rec["f2"] = 1.0
+        for i, m in enumerate(models):
+            if m is None:
+                continue
+            if kind == _capi.FUNDAMENTAL_7PT:
+                if isinstance(m, (CameraPose, ImagePair)) or np.asarray(m).shape != (3, 3) or np.asarray(m).dtype.kind not in "fiu":
+                    raise ValueError(f"{what}: pair {i} needs a 3 x 3 fundamental matrix, not {type(m).__name__}")
+                rec[i] = _capi.fundamental_to_model(m)
+            elif kind == _capi.SHARED_6PT:
+                if not isinstance(m, ImagePair):
+                    raise ValueError(f"{what}: pair {i} needs an ImagePair, not {type(m).__name__}")
+                rec[i]["q"] = m.pose.q; rec[i]["t"] = m.pose.t
+                rec[i]["f1"] = rec[i]["f2"] = m.camera1.focal()
+            else:
+                if not isinstance(m, CameraPose):
+                    raise ValueError(f"{what}: pair {i} needs a CameraPose, not {type(m).__name__}")
+                rec[i]["q"] = m.q; rec[i]["t"] = m.t
+    if len(rec) != B:
+        raise ValueError(f"{what}: expected {B} models, got {len(rec)}")
+    return rec
+
+
+def _baseline_host(kind, x1, x2, ns, scores, cams1, cams2, ransac_opt, bundle_opt, device, budgets, priors=None, prior_space=0):
     """(records, masks) of a baseline's host batch: pipeline.estimate_host, or with scores (see PRESORTED) one blocking ranked call on the device's
-    default handle (include/mdrp.h mdrp_estimate_classic_ranked)"""
+    default handle (include/mdrp.h mdrp_estimate_classic_ranked), or with priors one blocking call of mdrp_estimate_classic_prior"""
+    if priors is not None:
+        rec = _baseline_model_records(priors, kind, len(ns), "priors")  # (checked before anything touches the device)
+        return _capi.default_handle(device).estimate_classic_prior(kind, x1, x2, rec, _capi.ransac_opt_from_dict(ransac_opt),
+                                                                   _capi.bundle_opt_from_dict(bundle_opt), ns, cams1, cams2, prior_space=prior_space)
     if scores is None:
         return pipeline.estimate_host(kind, x1, x2, None, None, _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), ns, cams1, cams2,
                                       device, budgets=budgets)
@@ -626,10 +667,12 @@ def _baseline_host(kind, x1, x2, ns, scores, cams1, cams2, ransac_opt, bundle_op
                                                                 _capi.bundle_opt_from_dict(bundle_opt), ns, cams1, cams2)
 
 
-def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None):
+def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None,
+                                 priors=None):
     """B calibrated pairs through the 5-point estimator.  Returns (list[CameraPose], list[info dict]).  budgets: see _budget_args; scores: see
-    PRESORTED (not with budgets)."""
-    _no_scores_with(scores, budgets, None)
+    PRESORTED (not with budgets); priors: see _baseline_model_records (not with budgets or scores)."""
+    _no_scores_with(scores, budgets, priors)
+    _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     _check_baseline_options(ransac_opt, scores)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
@@ -638,38 +681,47 @@ def estimate_relative_pose_batch(points2D_1, points2D_2, cameras1, cameras2, ran
     def cams(c):
         return _camera_records(c, B)
 
-    res, mask = _baseline_host(_capi.RELPOSE_5PT, x1, x2, ns, scores, cams(cameras1), cams(cameras2), ransac_opt, bundle_opt, device, budgets)
+    res, mask = _baseline_host(_capi.RELPOSE_5PT, x1, x2, ns, scores, cams(cameras1), cams(cameras2), ransac_opt, bundle_opt, device, budgets, priors)
     return _per_budget(budgets, res, mask, lambda r, m: ([CameraPose(q["model"]["q"].copy(), q["model"]["t"].copy()) for q in r],
                                                          [_info(r[i], m[i], ns[i]) for i in range(B)]))
 
 
-def estimate_fundamental_batch(points2D_1, points2D_2, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None):
+def estimate_fundamental_batch(points2D_1, points2D_2, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None, priors=None):
     """B pairs through the 7-point estimator.  Returns (list[3 x 3 ndarray], list[info dict]).  budgets: see _budget_args; scores: see PRESORTED
-    (not with budgets)."""
-    _no_scores_with(scores, budgets, None)
+    (not with budgets); priors: see _baseline_model_records (not with budgets or scores)."""
+    _no_scores_with(scores, budgets, priors)
+    _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     _check_baseline_options(ransac_opt, scores)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
-    res, mask = _baseline_host(_capi.FUNDAMENTAL_7PT, x1, x2, ns, scores, None, None, ransac_opt, bundle_opt, device, budgets)
+    res, mask = _baseline_host(_capi.FUNDAMENTAL_7PT, x1, x2, ns, scores, None, None, ransac_opt, bundle_opt, device, budgets, priors)
     return _per_budget(budgets, res, mask, lambda r, m: ([_capi.model_to_fundamental(q["model"]) for q in r], [_info(r[i], m[i], ns[i]) for i in range(len(ns))]))
 
 
-def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, ransac_opt={}, bundle_opt={}, initial_pose=None, scores=None):
+def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, ransac_opt={}, bundle_opt={}, initial_pose=None, scores=None, prior=None):
     """Relative pose estimation with non-linear refinement (_core.pyi:504-529; eval.py:136 — the 5-point baseline).  As in the
     monodepth estimators, an initial pose only sets score_initial_model: ransac_relpose resets the pose itself.  scores (not in the reference): see
-    PRESORTED."""
+    PRESORTED.  prior (not in the reference): a CameraPose the search STARTS from, see _baseline_model_records."""
     poses, infos = estimate_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], camera1, camera2,
-                                                _with_initial(initial_pose, ransac_opt), bundle_opt, scores=_one_scores(scores))
+                                                _with_initial(initial_pose, ransac_opt), bundle_opt, scores=_one_scores(scores),
+                                                priors=None if prior is None else [prior])
     return poses[0], infos[0]
 
 
-def estimate_fundamental(points2D_1, points2D_2, ransac_opt={}, bundle_opt={}, initial_F=None, scores=None):
-    """Fundamental matrix estimation with non-linear refinement (_core.pyi:309-323; the 7-point baseline).  scores (not in the reference): see PRESORTED."""
+def estimate_fundamental(points2D_1, points2D_2, ransac_opt={}, bundle_opt={}, initial_F=None, scores=None, prior=None):
+    """Fundamental matrix estimation with non-linear refinement (_core.pyi:309-323; the 7-point baseline).  scores (not in the reference): see PRESORTED.
+    initial_F: as the reference reads it — scored and LO-refined first, not reset.  prior (not in the reference): the same under another name, a 3 x 3 F
+    for pixel coordinates the search STARTS from, see _baseline_model_records."""
     if initial_F is not None:
         # unlike ransac_*relpose, which reset the model they are handed (an initial pose only sets score_initial_model), the reference's
-        # ransac_fundamental scores the caller's F itself (DESIGN.md §9): not expressible through the flag, and no caller in the reference uses it
-        raise NotImplementedError("estimate_fundamental with initial_F (score_initial_model on a caller's F) is not built")
-    Fs, infos = estimate_fundamental_batch([_as_points(points2D_1)], [_as_points(points2D_2)], ransac_opt, bundle_opt, scores=_one_scores(scores))
+        # ransac_fundamental scores the caller's F itself, converted into its normalised coordinates, once the binding has set score_initial_model:
+        # the state a prior in the caller's units leaves (mdrp_estimate_classic_prior, prior_space = 0; DESIGN.md 9, pinned in
+        # tests/golden/classic_initial_F_ref.npz from the binary)
+        if prior is not None:
+            raise ValueError("initial_F and prior both start the search from a matrix: pass one of them")
+        prior = np.asarray(initial_F, dtype=np.float64)
+    Fs, infos = estimate_fundamental_batch([_as_points(points2D_1)], [_as_points(points2D_2)], ransac_opt, bundle_opt, scores=_one_scores(scores),
+                                           priors=None if prior is None else [prior])
     return Fs[0], infos[0]
 
 
@@ -713,16 +765,19 @@ def _pp_records(pp, B):
     return rec, pp
 
 
-def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None):
+def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, ransac_opt=None, bundle_opt=None, device=0, budgets=None, scores=None,
+                                              priors=None):
     """B pairs through the 6-point shared-focal estimator.  pp: one principal point for all pairs or (B, 2).
-    Returns (list[ImagePair], list[info dict]).  budgets: see _budget_args; scores: see PRESORTED (not with budgets)."""
-    _no_scores_with(scores, budgets, None)
+    Returns (list[ImagePair], list[info dict]).  budgets: see _budget_args; scores: see PRESORTED (not with budgets); priors: see
+    _baseline_model_records (not with budgets or scores)."""
+    _no_scores_with(scores, budgets, priors)
+    _no_budgets_with_priors(priors, budgets)
     ransac_opt, budgets = _budget_args(ransac_opt, budgets)
     _check_baseline_options(ransac_opt, scores)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
     B = len(ns)
     rec, ppb = _pp_records(pp, B)
-    res, mask = _baseline_host(_capi.SHARED_6PT, x1, x2, ns, scores, rec, rec, ransac_opt, bundle_opt, device, budgets)
+    res, mask = _baseline_host(_capi.SHARED_6PT, x1, x2, ns, scores, rec, rec, ransac_opt, bundle_opt, device, budgets, priors)
 
     def build(res, mask):
         out = []
@@ -734,15 +789,17 @@ def estimate_shared_focal_relative_pose_batch(points2D_1, points2D_2, pp=None, r
     return _per_budget(budgets, res, mask, build)
 
 
-def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp=None, ransac_opt={}, bundle_opt={}, initial_image_pair=None, scores=None):
+def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp=None, ransac_opt={}, bundle_opt={}, initial_image_pair=None, scores=None, prior=None):
     """Relative pose with one unknown focal length shared by both images, 6-point solver + non-linear refinement
     (_core.pyi:531-543; /root/reference/eval_shared_f.py:161, where the fork's signature has no `pp` and the points are
     already centred: a dict in the third position is taken as ransac_opt).  An initial image pair only sets
-    score_initial_model, like the initial pose of the other estimators.  scores (not in the reference): see PRESORTED."""
+    score_initial_model, like the initial pose of the other estimators.  scores (not in the reference): see PRESORTED.  prior (not in the reference):
+    an ImagePair the search STARTS from, see _baseline_model_records."""
     if isinstance(pp, dict):  # fork call shape: (kp1, kp2, ransac_dict, bundle_dict)
         pp, ransac_opt, bundle_opt = None, pp, (ransac_opt if ransac_opt else bundle_opt)
     pairs, infos = estimate_shared_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], pp,
-                                                             _with_initial(initial_image_pair, ransac_opt), bundle_opt, scores=_one_scores(scores))
+                                                             _with_initial(initial_image_pair, ransac_opt), bundle_opt, scores=_one_scores(scores),
+                                                             priors=None if prior is None else [prior])
     return pairs[0], infos[0]
 
 
@@ -869,24 +926,146 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
 BASELINE_KINDS = {"relpose_5pt": _capi.RELPOSE_5PT, "shared_focal_6pt": _capi.SHARED_6PT, "fundamental_7pt": _capi.FUNDAMENTAL_7PT}
 
 
-def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, cameras2=None, pp=None, ransac_opt=None, bundle_opt=None, n_per_pair=None,
-                                  scores=None):
-    """estimate_batch_torch for the comparison rows, which have no depths: `points2D_*` (B, N, 2) float64 torch tensors on a ROCm device, queued on
-    that device's current torch stream.  kind: "relpose_5pt" (cameras1 / cameras2) | "shared_focal_6pt" (pp: one principal point or (B, 2); None is
-    (0, 0)) | "fundamental_7pt".  Returns (records, (B, N) uint8 mask tensor on the device) as estimate_batch_torch does.  scores (see PRESORTED): a
-    (B, N) float32 / float64 tensor on the inputs' device, one per correspondence, higher is better, or "presorted": the estimate in score order with
-    the progressive sampler of the estimator's sample size; the mask stays in the caller's order.  Without scores it is the plain estimator."""
+def _model_tensor(models, B, device, what):
+    """one model record per pair on `device`: a uint8 (B, 96) / float64 (B, 12) tensor there, or a numpy array of _capi.MODEL_DTYPE (uploaded on the
+    current stream)"""
+    import torch
+    if isinstance(models, np.ndarray):
+        if models.dtype != _capi.MODEL_DTYPE:
+            raise ValueError(f"{what}: a numpy array must have dtype _capi.MODEL_DTYPE")
+        models = torch.from_numpy(np.ascontiguousarray(models).reshape(-1).view(np.uint8).copy()).to(device)
+    if not (isinstance(models, torch.Tensor) and models.is_cuda and models.device == device and models.dtype in (torch.uint8, torch.float64)):
+        raise ValueError(f"{what} must be a uint8 / float64 tensor on the inputs' device or a numpy array of _capi.MODEL_DTYPE")
+    models = models.contiguous()
+    if models.numel() * models.element_size() != B * _capi.MODEL_DTYPE.itemsize:
+        raise ValueError(f"{what} must hold {B} records of {_capi.MODEL_DTYPE.itemsize} bytes")
+    return models
+
+
+def _baseline_points_shape(who, points2D_1, points2D_2):
+    """(B, N) of two (B, N, 2) tensors"""
+    import torch
+    if not (isinstance(points2D_1, torch.Tensor) and isinstance(points2D_2, torch.Tensor)):
+        raise ValueError(f"{who} needs float64 tensors on the GPU")
+    if points2D_1.ndim != 3 or points2D_1.shape[2] != 2 or points2D_2.shape != points2D_1.shape:
+        raise ValueError("shapes must be (B, N, 2), (B, N, 2)")
+    return int(points2D_1.shape[0]), int(points2D_1.shape[1])
+
+
+def _baseline_torch_args(who, kind, points2D_1, points2D_2, cameras1, cameras2, pp, n_per_pair):
+    """what the baselines' resident entry points check before anything touches the device: (kind id, x1, x2, B, N, device index, n_per_pair, cams1, cams2)"""
     import torch
     if not (isinstance(kind, str) and kind in BASELINE_KINDS):
         raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
     k = BASELINE_KINDS[kind]
+    B, N = _baseline_points_shape(who, points2D_1, points2D_2)
+    x1, x2 = points2D_1.contiguous(), points2D_2.contiguous()
+    for t in (x1, x2):
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise ValueError(f"{who} needs float64 tensors on the GPU")
+        if t.device != x1.device:
+            raise ValueError("all tensors must live on the same device")
+    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
+    if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
+        n_per_pair = n_per_pair.detach().cpu().numpy()
+    cams1 = cams2 = None
+    if k == _capi.RELPOSE_5PT:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    elif k == _capi.SHARED_6PT:
+        cams1 = cams2 = _pp_records(pp, B)[0]
+    return k, x1, x2, B, N, dev, n_per_pair, cams1, cams2
+
+
+def refine_baseline_batch_torch(kind, points2D_1, points2D_2, models, cameras1=None, cameras2=None, pp=None, ransac_opt=None, bundle_opt=None,
+                                n_per_pair=None, stages=("lo", "inliers")):
+    """refine_batch_torch for the comparison rows (include/mdrp_classic_models.h: mdrp_refine_classic): one model per pair goes in and the baseline's
+    own tail runs on it without a sample.  kind, points, cameras and pp as in estimate_baseline_batch_torch; models as in refine_batch_torch, in the
+    caller's units (5-point: q, t; 6-point: q, t and f1 = f2 in pixels; 7-point: F for pixel coordinates in the first nine doubles; a NaN first double:
+    no model).  Of ransac_opt only max_epipolar_error is read.  Returns (records, (B, N) uint8 mask tensor on the device, initial: {"score",
+    "inliers"} numpy arrays of the models handed in)."""
+    import torch
+    k, x1, x2, B, N, dev, n_per_pair, cams1, cams2 = _baseline_torch_args("refine_baseline_batch_torch", kind, points2D_1, points2D_2, cameras1, cameras2, pp,
+                                                                          n_per_pair)
+    flags = _stage_flags(stages)
+    with torch.cuda.device(x1.device):
+        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        models = _model_tensor(models, B, x1.device, "models")
+        mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
+        score0 = torch.zeros(B, dtype=torch.float64, device=x1.device)
+        inl0 = torch.zeros(B, dtype=torch.int32, device=x1.device)
+        h.refine_classic_device(k, x1.data_ptr(), x2.data_ptr(), B, N, models.data_ptr(), _capi.ransac_opt_from_dict(ransac_opt),
+                                _capi.bundle_opt_from_dict(bundle_opt), flags, n_per_pair, cams1, cams2, mask.data_ptr(), score0.data_ptr(), inl0.data_ptr())
+        res = h.fetch_results(B)  # (waits for the stream: the two small tensors below are complete)
+        initial = {"score": score0.cpu().numpy(), "inliers": inl0.cpu().numpy()}
+    return res, mask, initial
+
+
+# The names refine_relative_pose / refine_fundamental are NOT defined here: upstream gives them another meaning (a plain LM over all the points
+# handed in, no threshold, no LO, no mask), and a function of that name with the estimator's tail would not be a drop-in (DESIGN.md 7b).
+def refine_baseline_batch(kind, points2D_1, points2D_2, models, cameras1=None, cameras2=None, pp=None, ransac_opt=None, bundle_opt=None, device=0,
+                          stages=("lo", "inliers"), as_arrays=False):
+    """B pairs, each with a model to start from, through the baseline's tail (refine_monodepth_*_batch for the comparison rows).  kind: see
+    BASELINE_KINDS; models: list[CameraPose] (5-point), list[ImagePair] (6-point) or 3 x 3 arrays (7-point), or a MODEL_DTYPE array.  Returns
+    (list of the same type, list[info dict] as _refine_info builds them); as_arrays=True: (records, masks, n_per_pair, initial scores, initial
+    inlier counts)."""
+    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
+        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
+    k = BASELINE_KINDS[kind]
+    flags = _stage_flags(stages)  # (everything is checked before anything touches the device)
+    x1, x2, ns = _stack2(points2D_1, points2D_2)
+    B = len(ns)
+    rec = _baseline_model_records(models, k, B, "models")
+    if np.isnan(rec["q"][:, 0]).any() and not (isinstance(models, np.ndarray) and models.dtype == _capi.MODEL_DTYPE):
+        raise ValueError("models: every pair needs a model to start from (None is for priors)")
+    cams1 = cams2 = None
+    ppb = None
+    if k == _capi.RELPOSE_5PT:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    elif k == _capi.SHARED_6PT:
+        cams1, ppb = _pp_records(pp, B)
+        cams2 = cams1
+    res, mask, score0, inl0 = _capi.default_handle(device).refine_classic(k, x1, x2, rec, _capi.ransac_opt_from_dict(ransac_opt),
+                                                                          _capi.bundle_opt_from_dict(bundle_opt), flags, ns, cams1, cams2)
+    if as_arrays:
+        return res, mask, ns, score0, inl0
+    if k == _capi.RELPOSE_5PT:
+        out = [CameraPose(r["model"]["q"].copy(), r["model"]["t"].copy()) for r in res]
+    elif k == _capi.FUNDAMENTAL_7PT:
+        out = [_capi.model_to_fundamental(r["model"]) for r in res]
+    else:
+        out = []
+        for i, r in enumerate(res):
+            f = float(r["model"]["f1"])
+            out.append(ImagePair(CameraPose(r["model"]["q"].copy(), r["model"]["t"].copy()), Camera("SIMPLE_PINHOLE", [f, float(ppb[i, 0]), float(ppb[i, 1])]),
+                                 Camera("SIMPLE_PINHOLE", [f, float(ppb[i, 0]), float(ppb[i, 1])])))
+    return out, [_refine_info(res[i], mask[i], ns[i], score0[i], inl0[i]) for i in range(B)]
+
+
+def refine_baseline(kind, points2D_1, points2D_2, model, camera1=None, camera2=None, pp=None, ransac_opt={}, bundle_opt={}, stages=("lo", "inliers")):
+    """refine_baseline_batch for one pair.  Returns (model, info)."""
+    if model is None:
+        raise ValueError("model is required: there is nothing to refine without a model to start from")
+    m, i = refine_baseline_batch(kind, [_as_points(points2D_1)], [_as_points(points2D_2)], [model], camera1, camera2, pp, ransac_opt, bundle_opt, stages=stages)
+    return m[0], i[0]
+
+
+def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, cameras2=None, pp=None, ransac_opt=None, bundle_opt=None, n_per_pair=None,
+                                  scores=None, priors=None, prior_space=0):
+    """estimate_batch_torch for the comparison rows, which have no depths: `points2D_*` (B, N, 2) float64 torch tensors on a ROCm device, queued on
+    that device's current torch stream.  kind: "relpose_5pt" (cameras1 / cameras2) | "shared_focal_6pt" (pp: one principal point or (B, 2); None is
+    (0, 0)) | "fundamental_7pt".  Returns (records, (B, N) uint8 mask tensor on the device) as estimate_batch_torch does.  scores (see PRESORTED): a
+    (B, N) float32 / float64 tensor on the inputs' device, one per correspondence, higher is better, or "presorted": the estimate in score order with
+    the progressive sampler of the estimator's sample size; the mask stays in the caller's order.  Without scores it is the plain estimator.
+    priors (not with scores): one model per pair as in refine_baseline_batch_torch, a NaN first double meaning none — the search of each pair starts
+    from it (include/mdrp_classic_models.h: mdrp_estimate_classic_prior); prior_space 1: the records are in the estimator's normalised coordinates."""
+    import torch
+    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
+        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
+    k = BASELINE_KINDS[kind]
+    _no_scores_with(scores, None, priors)
     _check_baseline_options(ransac_opt, scores)
     # (everything down to the handle is checked before anything touches the device)
-    if not (isinstance(points2D_1, torch.Tensor) and isinstance(points2D_2, torch.Tensor)):
-        raise ValueError("estimate_baseline_batch_torch needs float64 tensors on the GPU")
-    if points2D_1.ndim != 3 or points2D_1.shape[2] != 2 or points2D_2.shape != points2D_1.shape:
-        raise ValueError("shapes must be (B, N, 2), (B, N, 2)")
-    B, N = int(points2D_1.shape[0]), int(points2D_1.shape[1])
+    B, N = _baseline_points_shape("estimate_baseline_batch_torch", points2D_1, points2D_2)
     if isinstance(scores, str):
         if scores != PRESORTED:
             raise ValueError(f'scores: the only string is "{PRESORTED}", not {scores!r}')
@@ -895,25 +1074,17 @@ def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, c
             raise ValueError('scores must be a float32 / float64 tensor on the inputs\' device or "presorted"')
         if tuple(scores.shape) != (B, N):
             raise ValueError(f"scores must be {(B, N)}, one per correspondence, not {tuple(scores.shape)}")
-    x1, x2 = points2D_1.contiguous(), points2D_2.contiguous()
-    for t in (x1, x2):
-        if not (t.is_cuda and t.dtype == torch.float64):
-            raise ValueError("estimate_baseline_batch_torch needs float64 tensors on the GPU")
-        if t.device != x1.device:
-            raise ValueError("all tensors must live on the same device")
-    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
+    k, x1, x2, B, N, dev, n_per_pair, cams1, cams2 = _baseline_torch_args("estimate_baseline_batch_torch", kind, points2D_1, points2D_2, cameras1, cameras2, pp,
+                                                                          n_per_pair)
     h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
-    if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
-        n_per_pair = n_per_pair.detach().cpu().numpy()
-    cams1 = cams2 = None
-    if k == _capi.RELPOSE_5PT:
-        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
-    elif k == _capi.SHARED_6PT:
-        cams1 = cams2 = _pp_records(pp, B)[0]
     ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
     with torch.cuda.device(x1.device):
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
-        if scores is None:
+        if priors is not None:
+            pr = _model_tensor(priors, B, x1.device, "priors")
+            h.estimate_classic_prior_device(k, x1.data_ptr(), x2.data_ptr(), B, N, pr.data_ptr(), ro, bo, n_per_pair, cams1, cams2, mask.data_ptr(),
+                                            prior_space=prior_space)
+        elif scores is None:
             h.estimate_batch_device(k, x1.data_ptr(), x2.data_ptr(), None, None, B, N, ro, bo, n_per_pair, cams1, cams2, mask.data_ptr())
         else:
             sc = None
