@@ -34,6 +34,10 @@ EXPORTS = (
 EXPORTS_CLASSIC_RANKED = ("mdrp_estimate_classic_ranked", "mdrp_estimate_classic_ranked_async", "mdrp_prosac_samples_k")
 # the entry points of include/mdrp_classic_models.h, the second extension header mdrp.h includes: the baselines from a caller's model
 EXPORTS_CLASSIC_MODELS = ("mdrp_refine_classic", "mdrp_refine_classic_async", "mdrp_estimate_classic_prior", "mdrp_estimate_classic_prior_async")
+# the entry points of include/mdrp_classic_frontend.h, the third extension header mdrp.h includes: the baselines' device front end (no depth maps)
+EXPORTS_CLASSIC_FRONTEND = ("mdrp_gather_point_matches", "mdrp_gather_point_matches_ranked", "mdrp_gather_point_image_pairs",
+                            "mdrp_gather_point_image_pairs_ranked", "mdrp_estimate_classic_matches_async", "mdrp_estimate_classic_matches_ranked_async",
+                            "mdrp_estimate_classic_image_pairs_async", "mdrp_estimate_classic_image_pairs_ranked_async")
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
 STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
@@ -88,6 +92,18 @@ class ImagePairs(C.Structure):
     _fields_ = [("kp", C.c_void_p), ("kp_type", C.c_int32), ("k_max", C.c_int32), ("kp_count", C.c_void_p), ("depth", C.c_void_p),
                 ("depth_type", C.c_int32), ("h_max", C.c_int32), ("w_max", C.c_int32), ("size", C.c_void_p), ("center", C.c_void_p),
                 ("n_images", C.c_int32), ("pairs", C.c_void_p), ("matches", C.c_void_p), ("m_max", C.c_int32), ("filter", C.c_int32)]
+
+
+class PointMatches(C.Structure):
+    """mdrp_point_matches (include/mdrp_classic_frontend.h): a matcher's output without depth maps, every pointer in device memory"""
+    _fields_ = [("kp1", C.c_void_p), ("kp2", C.c_void_p), ("kp_type", C.c_int32), ("k1", C.c_int32), ("k2", C.c_int32),
+                ("matches", C.c_void_p), ("m_max", C.c_int32), ("center1", C.c_void_p), ("center2", C.c_void_p)]
+
+
+class PointImagePairs(C.Structure):
+    """mdrp_point_image_pairs (include/mdrp_classic_frontend.h): per-image keypoint tables, pairs as image indices, every pointer in device memory"""
+    _fields_ = [("kp", C.c_void_p), ("kp_type", C.c_int32), ("k_max", C.c_int32), ("kp_count", C.c_void_p), ("center", C.c_void_p),
+                ("n_images", C.c_int32), ("pairs", C.c_void_p), ("matches", C.c_void_p), ("m_max", C.c_int32)]
 
 
 class Result(C.Structure):
@@ -225,6 +241,14 @@ def load_library():
             lib.mdrp_gather_image_pairs_ranked.argtypes = [vp, C.POINTER(ImagePairs), vp, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
             lib.mdrp_estimate_image_pairs_ranked_async.argtypes = [vp, C.c_int, C.POINTER(ImagePairs), vp, C.c_int, C.c_int, vp, vp, C.POINTER(RansacOpt),
                                                                    C.POINTER(BundleOpt), vp, ip]
+        if hasattr(lib, "mdrp_gather_point_matches"):  # (an older ABI-0.6 library through MDRP_LIB has no front end for the baselines: Handle._classic_front_end_fn raises)
+            for desc, stem in ((PointMatches, "matches"), (PointImagePairs, "image_pairs")):
+                getattr(lib, f"mdrp_gather_point_{stem}").argtypes = [vp, C.POINTER(desc), C.c_int, dp, dp, ip, ip]
+                getattr(lib, f"mdrp_gather_point_{stem}_ranked").argtypes = [vp, C.POINTER(desc), vp, C.c_int, C.c_int, dp, dp, ip, ip]
+                getattr(lib, f"mdrp_estimate_classic_{stem}_async").argtypes = [vp, C.c_int, C.POINTER(desc), C.c_int, vp, vp, C.POINTER(RansacOpt),
+                                                                                C.POINTER(BundleOpt), vp, ip]
+                getattr(lib, f"mdrp_estimate_classic_{stem}_ranked_async").argtypes = [vp, C.c_int, C.POINTER(desc), vp, C.c_int, C.c_int, vp, vp,
+                                                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
         if hasattr(lib, "mdrp_estimate_batch_prior"):  # (an older ABI-0.6 library through MDRP_LIB has no prior entry points: Handle._prior_fn raises)
             lib.mdrp_estimate_batch_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
@@ -886,6 +910,44 @@ class Handle:
     def estimate_image_pairs_ranked_device(self, kind, ip, scores_ptr, score_type, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
         """estimate_matches_ranked_device on per-image tables; cam1 / cam2 are per PAIR"""
         return self._estimate_ranked("mdrp_estimate_image_pairs_ranked_async", kind, ip, scores_ptr, score_type, batch, ropt, bopt, cam1, cam2, match_mask_ptr)
+
+    # ---- the baselines' front end (include/mdrp_classic_frontend.h): a PointMatches / PointImagePairs descriptor of device pointers, no depths.
+    # scores_ptr as in the ranked front end above; ranked=False is the unranked entry point.  Arguments go to the library as they are.
+    def _classic_front_end_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the baselines' front end (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    @staticmethod
+    def _point_stem(desc):
+        return "image_pairs" if isinstance(desc, PointImagePairs) else "matches"
+
+    def gather_points(self, desc, batch, x1_ptr, x2_ptr, slot_ptr, scores_ptr=None, score_type=F64, ranked=False):
+        """k_gather_points* alone into the caller's device buffers (no depths); returns the kept rows per pair (numpy int32).  Synchronises the
+        stream once."""
+        n = np.zeros(int(batch), dtype=np.int32)
+        out = (C.c_void_p(x1_ptr), C.c_void_p(x2_ptr), C.c_void_p(slot_ptr), _ptr(n))
+        if ranked:
+            fn = self._classic_front_end_fn(f"mdrp_gather_point_{self._point_stem(desc)}_ranked")
+            _check(self._lib, fn(self._h, C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type), int(batch), *out))
+        else:
+            _check(self._lib, self._classic_front_end_fn(f"mdrp_gather_point_{self._point_stem(desc)}")(self._h, C.byref(desc), int(batch), *out))
+        return n
+
+    def estimate_points_device(self, kind, desc, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None, scores_ptr=None, score_type=F64, ranked=False):
+        """front end without depths + a baseline (kind 3, 4, 5) on the handle's stream; cam1 / cam2 are per PAIR; results stay on the device
+        (fetch_results / copy_results_device).  Returns the kept rows per pair (numpy int32)."""
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        n = np.zeros(int(batch), dtype=np.int32)
+        tail = (int(batch), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n))
+        if ranked:
+            fn = self._classic_front_end_fn(f"mdrp_estimate_classic_{self._point_stem(desc)}_ranked_async")
+            _check(self._lib, fn(self._h, int(kind), C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type), *tail))
+        else:
+            _check(self._lib, self._classic_front_end_fn(f"mdrp_estimate_classic_{self._point_stem(desc)}_async")(self._h, int(kind), C.byref(desc), *tail))
+        return n
 
     def fetch_results(self, batch):
         out = np.zeros(batch, dtype=RESULT_DTYPE)

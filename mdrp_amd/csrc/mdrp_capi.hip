@@ -1823,11 +1823,12 @@ static int check_front_end_kind(int kind, const char *who) {
 }
 
 // the handle's gather buffers for batch pairs of m_max rows
-static int ensure_gather_buffers(mdrp_handle *h, int batch, int m_max) {
+// (depths false: the front end of the baselines, which has no d1 / d2 and leaves fe_d1 / fe_d2 as they are)
+static int ensure_gather_buffers(mdrp_handle *h, int batch, int m_max, bool depths = true) {
     const size_t rows = (size_t)batch * m_max;
     int rc;
     if ((rc = h->fe_x1.ensure(sizeof(double) * 2 * rows + 16)) || (rc = h->fe_x2.ensure(sizeof(double) * 2 * rows + 16)) ||
-        (rc = h->fe_d1.ensure(sizeof(double) * rows + 16)) || (rc = h->fe_d2.ensure(sizeof(double) * rows + 16)) ||
+        (depths && ((rc = h->fe_d1.ensure(sizeof(double) * rows + 16)) || (rc = h->fe_d2.ensure(sizeof(double) * rows + 16)))) ||
         (rc = h->fe_slot.ensure(sizeof(int32_t) * rows + 16)) || (rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))))
         return rc;
     return MDRP_OK;
@@ -1837,11 +1838,11 @@ static int ensure_gather_buffers(mdrp_handle *h, int batch, int m_max) {
 // handle's own inlier mask (by slot), then that mask back onto the match rows
 // (prosac: the gathered buffers are in quality order and the progressive sampler draws from them, as in a ranked call)
 static int estimate_gathered(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                             const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host, const uint64_t *prosac = nullptr) {
+                             const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host, const uint64_t *prosac = nullptr, bool depths = true) {
     const size_t rows = (size_t)batch * m_max;
     int rc;
     if ((rc = fetch_counts(h, batch))) return rc;
-    rc = estimate_device(h, kind, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(), batch, m_max,
+    rc = estimate_device(h, kind, h->fe_x1.as<double>(), h->fe_x2.as<double>(), depths ? h->fe_d1.as<double>() : nullptr, depths ? h->fe_d2.as<double>() : nullptr, batch, m_max,
                          batch > 0 ? h->fe_n_host.v : nullptr, cam1, cam2, ropt, bopt, nullptr, nullptr, nullptr, 0, nullptr, prosac);
     if (rc) return rc;
     if (match_mask_dev && rows > 0) {
@@ -2006,6 +2007,197 @@ int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_
         return drain_and_return(h, rc);
     rc = estimate_gathered_ranked(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
     return rc ? drain_and_return(h, rc) : rc;
+}
+
+} // extern "C"
+
+// ---- the device front end of the 5- / 6- / 7-point baselines (include/mdrp_classic_frontend.h; k_gather_points*, mdrp_frontend.h):
+// check_matches / check_image_pairs without the depth clauses, the gathers without d1 / d2, the estimator with d1 = d2 = NULL on the handle's buffers
+static int check_point_matches(const mdrp_point_matches *pm, int batch) {
+    const char *why = nullptr;
+    if (!pm || batch < 0) why = "invalid argument";
+    else if (pm->kp_type != MDRP_F32 && pm->kp_type != MDRP_F64) why = "kp_type must be MDRP_F32 or MDRP_F64";
+    else if (pm->k1 < 0 || pm->k2 < 0 || pm->m_max < 0) why = "negative size";
+    else if (batch > 0 && pm->m_max > 0 && (!pm->matches || (pm->k1 > 0 && !pm->kp1) || (pm->k2 > 0 && !pm->kp2))) why = "NULL keypoints or matches";
+    if (why) { g_err = std::string("mdrp_point_matches: ") + why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+static int check_point_image_pairs(const mdrp_point_image_pairs *pp, int batch) {
+    const char *why = nullptr;
+    if (!pp || batch < 0) why = "invalid argument";
+    else if (pp->kp_type != MDRP_F32 && pp->kp_type != MDRP_F64) why = "kp_type must be MDRP_F32 or MDRP_F64";
+    else if (pp->k_max < 0 || pp->m_max < 0 || pp->n_images < 0) why = "negative size";
+    else if (batch > 0 && pp->m_max > 0 && (!pp->pairs || !pp->matches)) why = "NULL pairs or matches";
+    else if (pp->n_images > 0 && pp->k_max > 0 && !pp->kp) why = "NULL keypoints";
+    if (why) { g_err = std::string("mdrp_point_image_pairs: ") + why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+static int check_classic_front_end_kind(int kind, const char *who) {
+    if (kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT) return MDRP_OK;
+    g_err = std::string(who) + ": only the baselines (MDRP_RELPOSE_5PT, MDRP_SHARED_6PT, MDRP_FUNDAMENTAL_7PT); the monodepth estimators need depth maps: mdrp_estimate_matches_async takes them";
+    return MDRP_ERR_INVALID;
+}
+
+// What the baselines' front-end estimates refuse before any device work, behind the descriptor's own checks: the estimator's refusals on the options
+// as the estimator will see them (ranked: progressive_sampling is what the entry point builds, it is not handed on).
+static int check_classic_front_end(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
+                                   const mdrp_bundle_opt *bo, bool ranked) {
+    mdrp_ransac_opt seen = *ro;
+    if (ranked) seen.progressive_sampling = 0;
+    return estimate_refusals(h, kind, nullptr, nullptr, batch, m_max, cam1, cam2, &seen, bo);
+}
+
+// k_gather_points / k_gather_points_ranked on the handle's stream (the descriptor has passed check_point_matches); n_dev: [batch] on the device
+static int gather_points_device(mdrp_handle *h, const mdrp_point_matches *pm, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_dev,
+                                const void *scores = nullptr, int score_type = MDRP_F64) {
+    if (batch == 0) return MDRP_OK;
+    if (pm->m_max == 0) { // no rows: the counts are all there is to write
+        HIPCHK(hipMemsetAsync(n_dev, 0, sizeof(int32_t) * batch, h->stream));
+        return MDRP_OK;
+    }
+    if (scores) {
+#define MDRP_GATHER(KT)                                                                                                                                \
+    hipLaunchKernelGGL((k_gather_points_ranked<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pm->kp1, (const KT *)pm->kp2, pm->k1, pm->k2, \
+                       pm->matches, pm->m_max, pm->center1, pm->center2, scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, slot, n_dev)
+        if (pm->kp_type == MDRP_F32) MDRP_GATHER(float);
+        else MDRP_GATHER(double);
+#undef MDRP_GATHER
+    } else {
+#define MDRP_GATHER(KT)                                                                                                                         \
+    hipLaunchKernelGGL((k_gather_points<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pm->kp1, (const KT *)pm->kp2, pm->k1, pm->k2, \
+                       pm->matches, pm->m_max, pm->center1, pm->center2, x1, x2, slot, n_dev)
+        if (pm->kp_type == MDRP_F32) MDRP_GATHER(float);
+        else MDRP_GATHER(double);
+#undef MDRP_GATHER
+    }
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+// the same for mdrp_point_image_pairs
+static int gather_point_images_device(mdrp_handle *h, const mdrp_point_image_pairs *pp, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_dev,
+                                      const void *scores = nullptr, int score_type = MDRP_F64) {
+    if (batch == 0) return MDRP_OK;
+    if (pp->m_max == 0) { // no rows, and pairs may be NULL
+        HIPCHK(hipMemsetAsync(n_dev, 0, sizeof(int32_t) * batch, h->stream));
+        return MDRP_OK;
+    }
+    if (scores) {
+#define MDRP_GATHER(KT)                                                                                                                                  \
+    hipLaunchKernelGGL((k_gather_points_images_ranked<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pp->kp, pp->kp_count, pp->k_max,     \
+                       pp->center, pp->n_images, pp->pairs, pp->matches, pp->m_max, scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, slot, n_dev)
+        if (pp->kp_type == MDRP_F32) MDRP_GATHER(float);
+        else MDRP_GATHER(double);
+#undef MDRP_GATHER
+    } else {
+#define MDRP_GATHER(KT)                                                                                                                           \
+    hipLaunchKernelGGL((k_gather_points_images<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pp->kp, pp->kp_count, pp->k_max,     \
+                       pp->center, pp->n_images, pp->pairs, pp->matches, pp->m_max, x1, x2, slot, n_dev)
+        if (pp->kp_type == MDRP_F32) MDRP_GATHER(float);
+        else MDRP_GATHER(double);
+#undef MDRP_GATHER
+    }
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+// the gathers alone into the caller's buffers, behind the descriptor's check: the counts cross to n_host behind one stream synchronisation
+template <typename Desc, typename Gather>
+static int gather_points_alone(mdrp_handle *h, const Desc *desc, const void *scores_dev, int score_type, int batch, double *x1, double *x2, int32_t *slot,
+                               int32_t *n_host, const char *who, Gather gather) {
+    if (int rc = check_score_type(scores_dev, score_type)) return rc;
+    if (batch > 0 && (!n_host || (desc->m_max > 0 && (!x1 || !x2 || !slot)))) { g_err = std::string(who) + ": NULL output"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))) || (scores_dev && (rc = ensure_key_scratch(h, batch, desc->m_max)))) return rc;
+    if ((rc = gather(h, desc, batch, x1, x2, slot, h->fe_n.as<int32_t>(), scores_dev, score_type))) return drain_and_return(h, rc);
+    if ((rc = fetch_counts(h, batch))) return drain_and_return(h, rc);
+    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
+    return MDRP_OK;
+}
+
+// gather into the handle's buffers (no depth buffers), then estimate_gathered with d1 = d2 = NULL; ranked: with the progressive sampler
+template <typename Desc, typename Gather>
+static int estimate_points(mdrp_handle *h, int kind, const Desc *desc, const void *scores_dev, int score_type, bool ranked, int batch, const mdrp_camera *cam1,
+                           const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host,
+                           Gather gather) {
+    if (int rc = check_score_type(scores_dev, score_type)) return rc;
+    if (int rc = check_classic_front_end(h, kind, batch, desc->m_max, cam1, cam2, ropt, bopt, ranked)) return rc;
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = ensure_gather_buffers(h, batch, desc->m_max, false)) || (scores_dev && (rc = ensure_key_scratch(h, batch, desc->m_max)))) return rc;
+    if ((rc = gather(h, desc, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>(), scores_dev, score_type)))
+        return drain_and_return(h, rc);
+    mdrp_ransac_opt plain = *ropt;
+    const uint64_t max_prosac = ropt->max_prosac_iterations;
+    if (ranked) plain.progressive_sampling = 0;
+    rc = estimate_gathered(h, kind, batch, desc->m_max, cam1, cam2, &plain, bopt, match_mask_dev, n_used_host, ranked ? &max_prosac : nullptr, false);
+    return rc ? drain_and_return(h, rc) : rc;
+}
+
+extern "C" {
+
+int mdrp_gather_point_matches(mdrp_handle *h, const mdrp_point_matches *pm, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_point_matches(pm, batch)) return rc;
+    return gather_points_alone(h, pm, nullptr, MDRP_F64, batch, x1, x2, slot, n_host, "mdrp_gather_point_matches", gather_points_device);
+}
+
+int mdrp_gather_point_matches_ranked(mdrp_handle *h, const mdrp_point_matches *pm, const void *scores_dev, int score_type, int batch, double *x1, double *x2,
+                                     int32_t *slot, int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_point_matches(pm, batch)) return rc;
+    return gather_points_alone(h, pm, scores_dev, score_type, batch, x1, x2, slot, n_host, "mdrp_gather_point_matches_ranked", gather_points_device);
+}
+
+int mdrp_gather_point_image_pairs(mdrp_handle *h, const mdrp_point_image_pairs *pp, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_point_image_pairs(pp, batch)) return rc;
+    return gather_points_alone(h, pp, nullptr, MDRP_F64, batch, x1, x2, slot, n_host, "mdrp_gather_point_image_pairs", gather_point_images_device);
+}
+
+int mdrp_gather_point_image_pairs_ranked(mdrp_handle *h, const mdrp_point_image_pairs *pp, const void *scores_dev, int score_type, int batch, double *x1,
+                                         double *x2, int32_t *slot, int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_point_image_pairs(pp, batch)) return rc;
+    return gather_points_alone(h, pp, scores_dev, score_type, batch, x1, x2, slot, n_host, "mdrp_gather_point_image_pairs_ranked", gather_point_images_device);
+}
+
+int mdrp_estimate_classic_matches_async(mdrp_handle *h, int kind, const mdrp_point_matches *pm, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                        const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_matches_async")) return rc;
+    if (int rc = check_point_matches(pm, batch)) return rc;
+    return estimate_points(h, kind, pm, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_points_device);
+}
+
+int mdrp_estimate_classic_matches_ranked_async(mdrp_handle *h, int kind, const mdrp_point_matches *pm, const void *scores_dev, int score_type, int batch,
+                                               const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                               uint8_t *match_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_matches_ranked_async")) return rc;
+    if (int rc = check_point_matches(pm, batch)) return rc;
+    return estimate_points(h, kind, pm, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_points_device);
+}
+
+int mdrp_estimate_classic_image_pairs_async(mdrp_handle *h, int kind, const mdrp_point_image_pairs *pp, int batch, const mdrp_camera *cam1,
+                                            const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev,
+                                            int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_image_pairs_async")) return rc;
+    if (int rc = check_point_image_pairs(pp, batch)) return rc;
+    return estimate_points(h, kind, pp, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_point_images_device);
+}
+
+int mdrp_estimate_classic_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_point_image_pairs *pp, const void *scores_dev, int score_type,
+                                                   int batch, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                                   const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_image_pairs_ranked_async")) return rc;
+    if (int rc = check_point_image_pairs(pp, batch)) return rc;
+    return estimate_points(h, kind, pp, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_point_images_device);
 }
 
 } // extern "C"

@@ -9,6 +9,8 @@
 // image indices); its per-image rules (fe_image_valid, fe_clamp_extent, the table offsets) are pinned by tests/hostmath/image_pairs_host.cpp.
 // k_gather_ranked / k_gather_images_ranked are the same two front ends with one score per match row: a kept row goes to its RANK
 // among the kept rows of its pair, so that the progressive sampler (mdrp_prosac.h) runs on the gathered buffers as they are.
+// k_gather_points* are the four again without depth maps, for the 5- / 6- / 7-point baselines: the row rule is fe_point_row
+// (tests/hostmath/points_host.cpp), the compactions are shared through the row functors' HAS_DEPTH.
 // Like mdrp_math.h, the header compiles with a plain host C++ compiler (the kernels are left out there); that build is test scaffolding.
 #pragma once
 #include <math.h>
@@ -75,17 +77,27 @@ MDRP_HD size_t fe_depth_offset(int a, int h_max, int w_max, int yi, int xi) {
     return ((size_t)a * (size_t)h_max + (size_t)yi) * (size_t)w_max + (size_t)xi; // the row stride is w_max, whatever the valid width
 }
 
-#if defined(__HIPCC__)
-
-constexpr int FE_THREADS = 256; // one workgroup per pair, four wavefronts
-
 // Rules 1-4 for one match row, once for every kernel of the front end: what a kept row gathers, and whether it is kept.
 struct FeRow {
     double p1x = 0.0, p1y = 0.0, p2x = 0.0, p2y = 0.0, e1 = 0.0, e2 = 0.0; // centred keypoints, depths
 };
 
+// ---- the front end without depth maps (include/mdrp_classic_frontend.h): the 5- / 6- / 7-point baselines take correspondences alone
+// A row of valid indices is kept iff its four coordinates are finite: there is no map to be inside of and no depth to filter on.
+template <typename KpT> MDRP_HD bool fe_point_row(const KpT *q1, const KpT *q2, double c1x, double c1y, double c2x, double c2y, FeRow &r) {
+    const double a1x = (double)q1[0], a1y = (double)q1[1], a2x = (double)q2[0], a2y = (double)q2[1];
+    r.p1x = a1x - c1x; r.p1y = a1y - c1y;
+    r.p2x = a2x - c2x; r.p2y = a2y - c2y;
+    return fe_isfinite(a1x) && fe_isfinite(a1y) && fe_isfinite(a2x) && fe_isfinite(a2y);
+}
+
+#if defined(__HIPCC__)
+
+constexpr int FE_THREADS = 256; // one workgroup per pair, four wavefronts
+
 // the rows of pair b of an mdrp_matches batch
 template <typename KpT, typename DepthT> struct FeMatchRows {
+    static constexpr bool HAS_DEPTH = true; // the row carries depths: fe_gather_ordered / fe_gather_ranked write d1, d2
     const KpT *kp1, *kp2;
     int k1, k2;
     const int32_t *matches;
@@ -116,6 +128,7 @@ template <typename KpT, typename DepthT> struct FeMatchRows {
 
 // the rows of pair (a, c) of an mdrp_image_pairs batch; a pair with an index outside the image set keeps no row and loads nothing
 template <typename KpT, typename DepthT> struct FeImageRows {
+    static constexpr bool HAS_DEPTH = true;
     const KpT *kp;
     const DepthT *depth;
     const int32_t *matches;
@@ -165,7 +178,54 @@ template <typename KpT, typename DepthT> struct FeImageRows {
     }
 };
 
-// the ordered compaction of k_gather / k_gather_images for the rows of one pair
+// the rows of pair b of an mdrp_point_matches batch: FeMatchRows without the maps
+template <typename KpT> struct FePointMatchRows {
+    static constexpr bool HAS_DEPTH = false; // no depth buffer is written or read: d1 = d2 = nullptr
+    const KpT *kp1, *kp2;
+    int k1, k2;
+    const int32_t *matches;
+    double c1x, c1y, c2x, c2y;
+    size_t b, row0;
+    __device__ __forceinline__ bool operator()(int m, FeRow &r) const { // m in [0, m_max)
+        const int i = matches[2 * (row0 + m)], j = matches[2 * (row0 + m) + 1];
+        if (!fe_row_valid(i, j, k1, k2)) return false;
+        return fe_point_row(kp1 + 2 * (b * (size_t)k1 + (size_t)i), kp2 + 2 * (b * (size_t)k2 + (size_t)j), c1x, c1y, c2x, c2y, r);
+    }
+};
+
+// the rows of pair (a, c) of an mdrp_point_image_pairs batch: FeImageRows without the maps
+template <typename KpT> struct FePointImageRows {
+    static constexpr bool HAS_DEPTH = false;
+    const KpT *kp;
+    const int32_t *matches;
+    int k_max, a, c;
+    bool pair_ok;
+    int k1 = 0, k2 = 0;
+    double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0;
+    size_t row0;
+    __device__ __forceinline__ FePointImageRows(const KpT *kp_, const int32_t *kp_count, int k_max_, const double *center, int n_images, const int32_t *pairs,
+                                                const int32_t *matches_, size_t b, size_t row0_)
+        : kp(kp_), matches(matches_), k_max(k_max_), a(pairs[2 * b]), c(pairs[2 * b + 1]),
+          pair_ok(fe_image_valid(a, n_images) && fe_image_valid(c, n_images)) /*uniform over the workgroup*/, row0(row0_) {
+        if (pair_ok) {
+            k1 = kp_count ? fe_clamp_extent(kp_count[a], k_max) : k_max;
+            k2 = kp_count ? fe_clamp_extent(kp_count[c], k_max) : k_max;
+            if (center) {
+                c1x = center[2 * (size_t)a]; c1y = center[2 * (size_t)a + 1];
+                c2x = center[2 * (size_t)c]; c2y = center[2 * (size_t)c + 1];
+            }
+        }
+    }
+    __device__ __forceinline__ bool operator()(int m, FeRow &r) const { // m in [0, m_max)
+        if (!pair_ok) return false; // nothing is loaded, not even the match row
+        const int i = matches[2 * (row0 + m)], j = matches[2 * (row0 + m) + 1];
+        if (!fe_row_valid(i, j, k1, k2)) return false; // i < k1 <= k_max, j < k2 <= k_max
+        return fe_point_row(kp + fe_kp_offset(a, k_max, i), kp + fe_kp_offset(c, k_max, j), c1x, c1y, c2x, c2y, r);
+    }
+};
+
+// the ordered compaction of k_gather / k_gather_images / k_gather_points / k_gather_points_images for the rows of one pair
+// (Rows::HAS_DEPTH false: d1 and d2 are not touched, they may be null)
 template <typename Rows>
 __device__ __forceinline__ void fe_gather_ordered(const Rows &rows, int *s_wave /*LDS, FE_THREADS / 64*/, size_t b, int m_max, double *__restrict__ x1,
                                                   double *__restrict__ x2, double *__restrict__ d1, double *__restrict__ d2, int32_t *__restrict__ slot,
@@ -195,7 +255,7 @@ __device__ __forceinline__ void fe_gather_ordered(const Rows &rows, int *s_wave 
                 const size_t at = row0 + (size_t)s;
                 x1[2 * at] = r.p1x; x1[2 * at + 1] = r.p1y;
                 x2[2 * at] = r.p2x; x2[2 * at + 1] = r.p2y;
-                d1[at] = r.e1; d2[at] = r.e2;
+                if constexpr (Rows::HAS_DEPTH) { d1[at] = r.e1; d2[at] = r.e2; }
             }
         }
         base += total;
@@ -205,7 +265,7 @@ __device__ __forceinline__ void fe_gather_ordered(const Rows &rows, int *s_wave 
         const size_t at = row0 + (size_t)s;
         x1[2 * at] = 0.0; x1[2 * at + 1] = 0.0;
         x2[2 * at] = 0.0; x2[2 * at + 1] = 0.0;
-        d1[at] = 1.0; d2[at] = 1.0;
+        if constexpr (Rows::HAS_DEPTH) { d1[at] = 1.0; d2[at] = 1.0; }
     }
     if (threadIdx.x == 0) n_out[b] = base;
 }
@@ -307,7 +367,7 @@ __device__ __forceinline__ void fe_gather_ranked(const Rows &rows, uint64_t *s_k
                 const size_t at = row0 + (size_t)cnt[q];
                 x1[2 * at] = r.p1x; x1[2 * at + 1] = r.p1y;
                 x2[2 * at] = r.p2x; x2[2 * at + 1] = r.p2y;
-                d1[at] = r.e1; d2[at] = r.e2;
+                if constexpr (Rows::HAS_DEPTH) { d1[at] = r.e1; d2[at] = r.e2; }
             }
         }
     }
@@ -315,7 +375,7 @@ __device__ __forceinline__ void fe_gather_ranked(const Rows &rows, uint64_t *s_k
         const size_t at = row0 + (size_t)s;
         x1[2 * at] = 0.0; x1[2 * at + 1] = 0.0;
         x2[2 * at] = 0.0; x2[2 * at + 1] = 0.0;
-        d1[at] = 1.0; d2[at] = 1.0;
+        if constexpr (Rows::HAS_DEPTH) { d1[at] = 1.0; d2[at] = 1.0; }
     }
     if (tid == 0) n_out[b] = n;
 }
@@ -352,6 +412,59 @@ __global__ __launch_bounds__(FE_THREADS) void k_gather_images_ranked(const KpT *
     const size_t b = blockIdx.x;
     const FeImageRows<KpT, DepthT> rows(kp, kp_count, k_max, depth, size, h_max, w_max, center, n_images, pairs, matches, filter, b, b * (size_t)m_max);
     fe_gather_ranked(rows, s_key, s_wave, b, m_max, scores, score_type, keys, x1, x2, d1, d2, slot, n_out);
+}
+
+// ---- the front end without depth maps: the four kernels above on FePointMatchRows / FePointImageRows.  One template parameter (the keypoint
+// type), no depth buffer: d1 = d2 = nullptr into the shared compactions, which do not touch them (Rows::HAS_DEPTH).
+template <typename KpT>
+__global__ __launch_bounds__(FE_THREADS) void k_gather_points(const KpT *__restrict__ kp1, const KpT *__restrict__ kp2, int k1, int k2,
+                                                              const int32_t *__restrict__ matches, int m_max, const double *__restrict__ center1,
+                                                              const double *__restrict__ center2, double *__restrict__ x1, double *__restrict__ x2,
+                                                              int32_t *__restrict__ slot, int32_t *__restrict__ n_out) {
+    __shared__ int s_wave[FE_THREADS / 64];
+    const size_t b = blockIdx.x;
+    const FePointMatchRows<KpT> rows{kp1, kp2, k1, k2, matches, center1 ? center1[2 * b] : 0.0, center1 ? center1[2 * b + 1] : 0.0,
+                                     center2 ? center2[2 * b] : 0.0, center2 ? center2[2 * b + 1] : 0.0, b, b * (size_t)m_max};
+    fe_gather_ordered(rows, s_wave, b, m_max, x1, x2, nullptr, nullptr, slot, n_out);
+}
+
+template <typename KpT>
+__global__ __launch_bounds__(FE_THREADS) void k_gather_points_images(const KpT *__restrict__ kp, const int32_t *__restrict__ kp_count, int k_max,
+                                                                     const double *__restrict__ center, int n_images, const int32_t *__restrict__ pairs,
+                                                                     const int32_t *__restrict__ matches, int m_max, double *__restrict__ x1,
+                                                                     double *__restrict__ x2, int32_t *__restrict__ slot, int32_t *__restrict__ n_out) {
+    __shared__ int s_wave[FE_THREADS / 64];
+    const size_t b = blockIdx.x;
+    const FePointImageRows<KpT> rows(kp, kp_count, k_max, center, n_images, pairs, matches, b, b * (size_t)m_max);
+    fe_gather_ordered(rows, s_wave, b, m_max, x1, x2, nullptr, nullptr, slot, n_out);
+}
+
+template <typename KpT>
+__global__ __launch_bounds__(FE_THREADS) void k_gather_points_ranked(const KpT *__restrict__ kp1, const KpT *__restrict__ kp2, int k1, int k2,
+                                                                     const int32_t *__restrict__ matches, int m_max, const double *__restrict__ center1,
+                                                                     const double *__restrict__ center2, const void *__restrict__ scores, int score_type,
+                                                                     uint64_t *keys, double *__restrict__ x1, double *__restrict__ x2,
+                                                                     int32_t *__restrict__ slot, int32_t *__restrict__ n_out) {
+    __shared__ uint64_t s_key[RANK_TILE];
+    __shared__ int s_wave[FE_THREADS / 64];
+    const size_t b = blockIdx.x;
+    const FePointMatchRows<KpT> rows{kp1, kp2, k1, k2, matches, center1 ? center1[2 * b] : 0.0, center1 ? center1[2 * b + 1] : 0.0,
+                                     center2 ? center2[2 * b] : 0.0, center2 ? center2[2 * b + 1] : 0.0, b, b * (size_t)m_max};
+    fe_gather_ranked(rows, s_key, s_wave, b, m_max, scores, score_type, keys, x1, x2, nullptr, nullptr, slot, n_out);
+}
+
+template <typename KpT>
+__global__ __launch_bounds__(FE_THREADS) void k_gather_points_images_ranked(const KpT *__restrict__ kp, const int32_t *__restrict__ kp_count, int k_max,
+                                                                            const double *__restrict__ center, int n_images,
+                                                                            const int32_t *__restrict__ pairs, const int32_t *__restrict__ matches, int m_max,
+                                                                            const void *__restrict__ scores, int score_type, uint64_t *keys,
+                                                                            double *__restrict__ x1, double *__restrict__ x2, int32_t *__restrict__ slot,
+                                                                            int32_t *__restrict__ n_out) {
+    __shared__ uint64_t s_key[RANK_TILE];
+    __shared__ int s_wave[FE_THREADS / 64];
+    const size_t b = blockIdx.x;
+    const FePointImageRows<KpT> rows(kp, kp_count, k_max, center, n_images, pairs, matches, b, b * (size_t)m_max);
+    fe_gather_ranked(rows, s_key, s_wave, b, m_max, scores, score_type, keys, x1, x2, nullptr, nullptr, slot, n_out);
 }
 
 // the estimator's inlier mask (one byte per kept correspondence, by slot) back onto the match rows: dropped rows are 0

@@ -25,6 +25,11 @@ the progressive sampler (PROSAC) wants.  Rules 1-4 decide wha
 `poselib.gather_image_pairs_torch` / `estimate_image_pairs_torch` take the batch as its producer holds it: keypoints and depth maps once per
 image, pairs as image indices (include/mdrp.h mdrp_image_pairs).  `gather_image_pairs_numpy` below states them as a loop over the pairs that
 calls `gather_matches_numpy` on the two images' valid tables: that reduction is the definition.
+
+`poselib.gather_point_matches_torch` / `estimate_baseline_matches_torch` and their per-image siblings are the front end of the 5- / 6- / 7-point
+baselines, which have no depths (include/mdrp_classic_frontend.h): `gather_point_matches_numpy` / `gather_point_image_pairs_numpy`
+state them.  Rule 1 is unchanged; rule 2 becomes "all four coordinates are finite" (no map to be inside of), rules 3 and 4 fall away, rules 5 and 6
+hold without d1 and d2.
 """
 import numpy as np
 
@@ -178,3 +183,78 @@ def gather_image_pairs_numpy(keypoints, depth_maps, pairs, matches, centers=None
                                              None if cs is None else cs[a], None if cs is None else cs[c], filter,
                                              None if scores is None else scores[b]))
     return pad_pairs(gathered, M)
+
+
+# ---- the front end without depth maps (include/mdrp_classic_frontend.h): the 5- / 6- / 7-point baselines take correspondences alone
+def gather_point_matches_numpy(keypoints1, keypoints2, matches, center1=None, center2=None, scores=None):
+    """One pair: keypoints (K, 2) in float32 / float64, matches (M, 2) integers (taken as int32).  A row is kept iff both indices address their
+    tables and the four coordinates are finite.  Returns (x1 (n, 2), x2 (n, 2) float64, slot (M,) int32): gather_matches_numpy's return minus the
+    depths.  scores: (M,) float32 / float64 — the kept rows in rank order (rule 6), slot[m] the rank of row m."""
+    kp1, kp2 = _table(keypoints1, "keypoints"), _table(keypoints2, "keypoints")
+    if kp1.ndim != 2 or kp1.shape[1] != 2 or kp2.ndim != 2 or kp2.shape[1] != 2:
+        raise ValueError("expected keypoints (K, 2)")
+    m = np.asarray(matches).astype(np.int32).reshape(-1, 2).astype(np.int64)
+    i, j = m[:, 0], m[:, 1]
+    ok = (i >= 0) & (j >= 0) & (i < len(kp1)) & (j < len(kp2))                           # rule 1
+    p1 = np.zeros((len(m), 2)); p2 = np.zeros((len(m), 2))
+    p1[ok] = kp1[i[ok]].astype(np.float64); p2[ok] = kp2[j[ok]].astype(np.float64)
+    ok &= np.isfinite(p1).all(axis=1) & np.isfinite(p2).all(axis=1)                      # rule 2 without a map: finite coordinates
+    slot = np.where(ok, np.cumsum(ok) - 1, -1).astype(np.int32)
+    c1 = np.zeros(2) if center1 is None else np.asarray(center1, dtype=np.float64).reshape(2)
+    c2 = np.zeros(2) if center2 is None else np.asarray(center2, dtype=np.float64).reshape(2)
+    x1, x2 = p1[ok] - c1, p2[ok] - c2
+    if scores is None:
+        return x1, x2, slot
+    o = score_order(_row_scores(scores, len(m))[ok])                                    # rule 6
+    rank = np.empty(len(o), dtype=np.int32)
+    rank[o] = np.arange(len(o), dtype=np.int32)
+    slot[ok] = rank
+    return x1[o], x2[o], slot
+
+
+def pad_point_pairs(gathered, m_max):
+    """pad_pairs without depths: per-pair results of gather_point_matches_numpy -> x1, x2 (B, m_max, 2), n (B,) int32, slot (B, m_max) int32;
+    slots past n hold x = 0"""
+    B = len(gathered)
+    x1 = np.zeros((B, m_max, 2)); x2 = np.zeros((B, m_max, 2))
+    n = np.zeros(B, dtype=np.int32)
+    slot = np.full((B, m_max), -1, dtype=np.int32)
+    for b, (a1, a2, s) in enumerate(gathered):
+        n[b] = len(a1)
+        x1[b, :n[b]] = a1; x2[b, :n[b]] = a2
+        slot[b, :len(s)] = s
+    return x1, x2, n, slot
+
+
+def gather_point_image_pairs_numpy(keypoints, pairs, matches, centers=None, kp_counts=None, scores=None):
+    """keypoints (I, K, 2) in float32 / float64, pairs (B, 2) image indices (a, c), matches (B, M, 2) integers; kp_counts (I,) clamped to [0, K],
+    None = K; centers (I, 2) or (2,).  Pair b is gather_point_matches_numpy on image a's and image c's valid tables; a pair with an index outside
+    [0, I) is empty.  Returns pad_point_pairs of the per-pair results: x1, x2 (B, M, 2), n (B,) int32, slot (B, M) int32.  scores: (B, M)."""
+    kp = _table(keypoints, "keypoints")
+    if kp.ndim != 3 or kp.shape[2] != 2:
+        raise ValueError("expected keypoints (I, K, 2)")
+    I, K = kp.shape[:2]
+    pairs = np.asarray(pairs).astype(np.int32).reshape(-1, 2)
+    matches = np.asarray(matches)
+    if matches.ndim != 3 or len(matches) != len(pairs) or matches.shape[2] != 2:
+        raise ValueError("expected matches (B, M, 2) with the pairs' B")
+    M = matches.shape[1]
+    if scores is not None:
+        scores = np.asarray(scores)
+        if scores.dtype not in (np.float32, np.float64) or scores.shape != (len(pairs), M):
+            raise ValueError("scores must be (B, M) float32 or float64, one per match row")
+    counts = np.full(I, K, dtype=np.int64) if kp_counts is None else clamp_extent(np.asarray(kp_counts).reshape(I), K)
+    cs = None if centers is None else np.asarray(centers, dtype=np.float64)
+    if cs is not None and cs.size == 2:
+        cs = np.tile(cs.reshape(1, 2), (I, 1))
+    if cs is not None and cs.shape != (I, 2):
+        raise ValueError("centers must have shape (I, 2) or (2,)")
+    empty = (np.zeros((0, 2)), np.zeros((0, 2)), np.full(M, -1, dtype=np.int32))
+    gathered = []
+    for b, (a, c) in enumerate(pairs):
+        if not (image_valid(a, I) and image_valid(c, I)):
+            gathered.append(empty)
+            continue
+        gathered.append(gather_point_matches_numpy(kp[a][:counts[a]], kp[c][:counts[c]], matches[b], None if cs is None else cs[a],
+                                                   None if cs is None else cs[c], None if scores is None else scores[b]))
+    return pad_point_pairs(gathered, M)

@@ -1392,6 +1392,208 @@ def estimate_image_pairs_torch(kind, keypoints, depth_maps, pairs, matches, came
     return res, match_mask, n_used
 
 
+# ---- the same two front ends for the comparison rows, which have no depths (include/mdrp_classic_frontend.h): keypoint tables and index
+# pairs go in, the 5- / 6- / 7-point baselines run on the gathered correspondences.  mdrp_amd/frontend.py gather_point_matches_numpy /
+# gather_point_image_pairs_numpy state the semantics: a row is kept iff its indices address their tables and its four coordinates are finite.
+def _baseline_kind(kind):
+    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
+        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
+    return BASELINE_KINDS[kind]
+
+
+def _point_matches_descriptor(keypoints1, keypoints2, matches, center1, center2):
+    """_matches_descriptor without the depth maps: validated mdrp_point_matches descriptor -> (descriptor, tensors it points into, B, M, device)"""
+    import torch
+    named = {"keypoints1": keypoints1, "keypoints2": keypoints2, "matches": matches}
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+    kp1, kp2 = (t.unsqueeze(0) if t.dim() == 2 else t for t in (keypoints1, keypoints2))
+    mt = matches.unsqueeze(0) if matches.dim() == 2 and kp1.shape[0] == 1 else matches
+    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
+    if kp1.dtype not in ftypes or kp2.dtype != kp1.dtype:
+        raise ValueError("keypoints must both be float32 or both float64")
+    if mt.dtype not in (torch.int32, torch.int64):
+        raise ValueError("matches must be int32 or int64")
+    if kp1.dim() != 3 or kp1.shape[2] != 2 or kp2.dim() != 3 or kp2.shape[2] != 2:
+        raise ValueError("keypoints must have shape (B, K, 2) or (K, 2)")
+    B = kp1.shape[0]
+    if kp2.shape[0] != B or mt.dim() != 3 or mt.shape[0] != B or mt.shape[2] != 2:
+        raise ValueError("matches must have shape (B, M, 2) with the keypoints' B")
+    for name, t in named.items():  # (types and shapes first: a caller who mixes both up hears about the tensors themselves)
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+        if t.device != keypoints1.device:
+            raise ValueError("all tensors must live on the same device")
+    dev = keypoints1.device
+    if mt.dtype == torch.int64:
+        mt = mt.to(torch.int32)  # narrowed on the device, on the current stream: no synchronisation
+    kp1, kp2, mt = (t.contiguous() for t in (kp1, kp2, mt))
+
+    def center(c):
+        if c is None:
+            return None
+        c = torch.as_tensor(c, dtype=torch.float64).to(dev)
+        if c.numel() == 2:
+            c = c.reshape(1, 2).expand(B, 2)
+        if c.shape != (B, 2):
+            raise ValueError("centers must have shape (B, 2) or (2,)")
+        return c.contiguous()
+
+    c1, c2 = center(center1), center(center2)
+    pm = _capi.PointMatches(kp1.data_ptr(), kp2.data_ptr(), ftypes[kp1.dtype], kp1.shape[1], kp2.shape[1], mt.data_ptr(), mt.shape[1],
+                            None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr())
+    return pm, (kp1, kp2, mt, c1, c2), B, int(mt.shape[1]), dev
+
+
+def _point_image_pairs_descriptor(keypoints, pairs, matches, centers, kp_counts, need_host_pairs):
+    """_image_pairs_descriptor without the depth maps: validated mdrp_point_image_pairs descriptor -> (descriptor, tensors it points into, host
+    pairs or None, B, M, I, device)"""
+    import torch
+    named = {"keypoints": keypoints, "matches": matches}
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+    dev = keypoints.device
+    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
+    if keypoints.dtype not in ftypes:
+        raise ValueError("keypoints must be float32 or float64")
+    if matches.dtype not in (torch.int32, torch.int64):
+        raise ValueError("matches must be int32 or int64")
+    if keypoints.dim() != 3 or keypoints.shape[2] != 2:
+        raise ValueError("keypoints must have shape (I, K, 2)")
+    I = keypoints.shape[0]
+    on_device = isinstance(pairs, torch.Tensor) and pairs.device == dev
+    if on_device and (pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype.is_floating_point):
+        raise ValueError("pairs must be (B, 2) integer image indices")
+    host_pairs = _host_pairs(pairs) if need_host_pairs or not on_device else None
+    B = pairs.shape[0] if host_pairs is None else len(host_pairs)
+    if matches.dim() != 3 or matches.shape[0] != B or matches.shape[2] != 2:
+        raise ValueError("matches must have shape (B, M, 2) with the pairs' B")
+    for name, t in named.items():  # (types and shapes first, as _point_matches_descriptor)
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+        if t.device != dev:
+            raise ValueError("all tensors must live on the same device")
+    mt = matches.to(torch.int32) if matches.dtype == torch.int64 else matches  # narrowed on the device, on the current stream: no synchronisation
+    kp, mt = keypoints.contiguous(), mt.contiguous()
+
+    def per_image(v, dtype, shape, what):
+        if v is None:
+            return None
+        v = (v if isinstance(v, torch.Tensor) else torch.tensor(np.asarray(v))).to(device=dev, dtype=dtype)
+        if what == "centers" and v.numel() == 2:
+            v = v.reshape(1, 2).expand(I, 2)
+        if tuple(v.shape) != shape:
+            raise ValueError(f"{what} must have shape {shape}" + (" or (2,)" if what == "centers" else ""))
+        return v.contiguous()
+
+    cs = per_image(centers, torch.float64, (I, 2), "centers")
+    kc = per_image(kp_counts, torch.int32, (I,), "kp_counts")
+    pr = pairs.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous() if on_device else torch.from_numpy(host_pairs).to(dev)  # (host_pairs is this call's own copy)
+    pp = _capi.PointImagePairs(kp.data_ptr(), ftypes[kp.dtype], kp.shape[1], None if kc is None else kc.data_ptr(), None if cs is None else cs.data_ptr(), I,
+                               pr.data_ptr(), mt.data_ptr(), mt.shape[1])
+    return pp, (kp, mt, cs, kc, pr), host_pairs, B, int(mt.shape[1]), I, dev
+
+
+def _gather_points(desc, B, M, dev, ranked, sc):
+    """the gather alone of either descriptor on the device's current torch stream: (x1, x2, n_per_pair, slot)"""
+    import torch
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        x1 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        x2 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        slot = torch.empty((B, M), dtype=torch.int32, device=dev)
+        sp, st, sc = _score_args(sc)
+        n = h.gather_points(desc, B, x1.data_ptr(), x2.data_ptr(), slot.data_ptr(), sp, st, ranked)
+    del sc
+    return x1, x2, n, slot
+
+
+def _estimate_points(k, desc, B, M, dev, ranked, sc, cams1, cams2, ransac_opt, bundle_opt):
+    """front end + baseline of either descriptor on the device's current torch stream: (records, match_mask, n_used)"""
+    import torch
+    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
+        sp, st, sc = _score_args(sc)
+        n_used = h.estimate_points_device(k, desc, B, ro, bo, cams1, cams2, match_mask.data_ptr(), sp, st, ranked)
+        res = h.fetch_results(B)
+    del sc
+    return res, match_mask, n_used
+
+
+def gather_point_matches_torch(keypoints1, keypoints2, matches, center1=None, center2=None, scores=None):
+    """gather_matches_torch without depth maps, for the 5- / 6- / 7-point baselines: keypoints (B, K, 2) float32 | float64 (a (K, 2) tensor is
+    B = 1), matches (B, M, 2) int32 | int64 with -1 rows as padding, all on one ROCm device; center1 / center2: optional (B, 2) or (2,), subtracted in
+    float64.  A row is kept iff its indices address their tables and its four coordinates are finite (mdrp_amd/frontend.py
+    gather_point_matches_numpy).  Returns (x1, x2 (B, M, 2): float64 device tensors, kept rows first, the rest 0; n_per_pair: numpy int32; slot
+    (B, M): int32 device tensor, -1 if dropped).  One stream synchronisation (the counts).  scores: as gather_matches_torch's — the kept rows in
+    QUALITY order, what estimate_baseline_batch_torch(..., scores="presorted") takes."""
+    ranked, sc = _front_end_scores(scores, matches)
+    pm, keep, B, M, dev = _point_matches_descriptor(keypoints1, keypoints2, matches, center1, center2)
+    out = _gather_points(pm, B, M, dev, ranked, sc)
+    del keep
+    return out
+
+
+def estimate_baseline_matches_torch(kind, keypoints1, keypoints2, matches, cameras1=None, cameras2=None, pp=None, ransac_opt=None, bundle_opt=None,
+                                    center1=None, center2=None, scores=None):
+    """estimate_baseline_batch_torch straight from a matcher's output (inputs as gather_point_matches_torch): records identical to gathering with
+    mdrp_amd.frontend.gather_point_matches_numpy and calling estimate_baseline_batch_torch with its n_per_pair.  kind: see BASELINE_KINDS
+    ("relpose_5pt": cameras1 / cameras2 per pair; "shared_focal_6pt": pp and principal-point-centred keypoints through center1 / center2;
+    "fundamental_7pt").  Returns (records, match_mask: (B, M) uint8 device tensor — 1 where the row was kept and is an inlier —, n_used: numpy
+    int32).  scores: one per match row or "presorted" — the estimate in score order with the progressive sampler, bit for bit
+    estimate_baseline_batch_torch(scores="presorted") on the ranked gather; progressive_sampling in ransac_opt may then be absent, False or True,
+    without scores it is refused."""
+    k = _baseline_kind(kind)
+    ranked, sc = _front_end_scores(scores, matches)
+    _check_baseline_options(ransac_opt, scores)
+    pm, keep, B, M, dev = _point_matches_descriptor(keypoints1, keypoints2, matches, center1, center2)
+    cams1 = cams2 = None
+    if k == _capi.RELPOSE_5PT:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    elif k == _capi.SHARED_6PT:
+        cams1 = cams2 = _pp_records(pp, B)[0]
+    out = _estimate_points(k, pm, B, M, dev, ranked, sc, cams1, cams2, ransac_opt, bundle_opt)
+    del keep
+    return out
+
+
+def gather_point_image_pairs_torch(keypoints, pairs, matches, centers=None, kp_counts=None, scores=None):
+    """gather_point_matches_torch for pairs given as image indices (gather_image_pairs_torch without depth maps): keypoints (I, K, 2), pairs
+    (B, 2) image indices as a sequence, NumPy array or tensor on any device (an index outside [0, I): an empty pair), matches (B, M, 2); kp_counts
+    (I,) clamped to K, centers (I, 2) or (2,).  Returns what gather_point_matches_torch returns.  scores: (B, M)."""
+    ranked, sc = _front_end_scores(scores, matches)
+    desc, keep, _, B, M, _, dev = _point_image_pairs_descriptor(keypoints, pairs, matches, centers, kp_counts, False)
+    out = _gather_points(desc, B, M, dev, ranked, sc)
+    del keep
+    return out
+
+
+def estimate_baseline_image_pairs_torch(kind, keypoints, pairs, matches, cameras=None, pp=None, ransac_opt=None, bundle_opt=None, centers=None,
+                                        kp_counts=None, scores=None):
+    """estimate_baseline_matches_torch for pairs given as image indices (inputs as gather_point_image_pairs_torch): records identical to
+    gathering with mdrp_amd.frontend.gather_point_image_pairs_numpy and calling estimate_baseline_batch_torch with its n_per_pair and the per-pair
+    cameras.  cameras ("relpose_5pt" only) are per IMAGE and expanded to per-pair records by pairs on the host; pp ("shared_focal_6pt") is one
+    principal point or one per PAIR (B, 2).  Returns (records, match_mask, n_used)."""
+    k = _baseline_kind(kind)
+    ranked, sc = _front_end_scores(scores, matches)
+    _check_baseline_options(ransac_opt, scores)
+    desc, keep, host_pairs, B, M, I, dev = _point_image_pairs_descriptor(keypoints, pairs, matches, centers, kp_counts, k == _capi.RELPOSE_5PT)
+    cams1 = cams2 = None
+    if k == _capi.RELPOSE_5PT:
+        cams1, cams2 = _pair_cameras(cameras, host_pairs, I)
+    elif k == _capi.SHARED_6PT:
+        cams1 = cams2 = _pp_records(pp, B)[0]
+    out = _estimate_points(k, desc, B, M, dev, ranked, sc, cams1, cams2, ransac_opt, bundle_opt)
+    del keep
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ refine / verify caller-supplied models
 # The counterpart of PoseLib's refine_relative_pose for the three monodepth estimators (include/mdrp.h mdrp_refine_batch, DESIGN.md 7b): one model
 # per pair goes in and the estimator's tail runs on it — score, LO, inlier mask, inlier-only refinement — without a single sample.  A pose from the

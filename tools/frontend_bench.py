@@ -18,6 +18,11 @@ The front end's own kernel time comes from a separate run under the profiler, fo
 image, the pairs as image indices — through poselib.estimate_image_pairs_torch (route "i"), against the unchanged estimate_matches_torch on the
 per-pair expansion of the same data (route "e": every image's tables copied once per pair it takes part in, built before the clock starts).
 Checks that both return the same records, records the bytes of input each route holds, and writes under the key "image_pairs" of the same file.
+
+--baseline KIND (relpose_5pt | shared_focal_6pt | fundamental_7pt): the same three routes for a comparison row, which has no depths (DESIGN.md
+7g) — (a) torch_point_front_end (torch indexing, the finite test, the ordered compaction, the count copied to the host) +
+estimate_baseline_batch_torch, (b) poselib.estimate_baseline_matches_torch, (c) estimate_baseline_batch_torch on input gathered beforehand.  No
+depth maps are made.  Writes under the key "baseline_<KIND>" of profiles/classic_frontend_bench.json unless --out says otherwise.
 """
 import argparse
 import csv
@@ -38,10 +43,11 @@ CAM = {"model": "SIMPLE_PINHOLE", "width": W, "height": H, "params": [A * 800.0,
 BO = {"loss_type": "TRUNCATED_CAUCHY"}
 
 
-def make_inputs(batch, rows, dev, outlier_frac=0.5, outlier_flags=None):
+def make_inputs(batch, rows, dev, outlier_frac=0.5, outlier_flags=None, depth_maps=True):
     """matcher-shaped inputs on the device: keypoint tables with the correspondences scattered through a permutation, their depths painted
     into the maps, a tail of -1 padding rows of a different length per pair (LightGlue pads ragged match lists that way).  outlier_flags: a
-    list that receives the (batch, rows) outlier flags of the match rows (tools/frontend_ranked_bench.py makes its scores from them)."""
+    list that receives the (batch, rows) outlier flags of the match rows (tools/frontend_ranked_bench.py makes its scores from them).
+    depth_maps=False: keypoints and matches alone (the baselines' front end)."""
     import torch
     from mdrp_amd import synth
     rng = np.random.default_rng(5)
@@ -58,6 +64,8 @@ def make_inputs(batch, rows, dev, outlier_frac=0.5, outlier_flags=None):
         p1, p2 = rng.permutation(K)[:rows], rng.permutation(K)[:rows]
         kp1[k, p1] = pt1[k]; kp2[k, p2] = pt2[k]
         matches[k, :live[k], 0] = p1[:live[k]]; matches[k, :live[k], 1] = p2[:live[k]]
+    if not depth_maps:
+        return torch.from_numpy(kp1.astype(np.float32)).to(dev), torch.from_numpy(kp2.astype(np.float32)).to(dev), torch.from_numpy(matches).to(dev)
     g = torch.Generator(device=dev); g.manual_seed(5)
     dm1 = torch.rand((batch, H, W), device=dev, generator=g) * 5 + 1
     dm2 = torch.rand((batch, H, W), device=dev, generator=g) * 5 + 1
@@ -113,6 +121,99 @@ def route_a(poselib, t, ro):
 def route_b(poselib, t, ro):
     res, match_mask, _ = poselib.estimate_matches_torch("calibrated", *t, CAM, CAM, ro, BO)
     return res, match_mask
+
+
+# ---- the comparison rows (5- / 6- / 7-point), which have no depths
+BASELINES = ("relpose_5pt", "shared_focal_6pt", "fundamental_7pt")
+
+
+def baseline_arguments(kind):
+    """(cameras1, cameras2, pp, centre) of a baseline on make_inputs' keypoints: cameras for the 5-point kind, principal-point-centred pixels and
+    pp = (0, 0) for the 6-point kind, nothing for the 7-point kind"""
+    if kind == "relpose_5pt":
+        return CAM, CAM, None, None
+    return None, None, ((0.0, 0.0) if kind == "shared_focal_6pt" else None), (C if kind == "shared_focal_6pt" else None)
+
+
+def torch_point_front_end(kp1, kp2, matches, centre=None):
+    """the baselines' preparation in batched torch ops, order preserved: kp[matches], drop padding, bad indices and non-finite coordinates, compact"""
+    import torch
+    B, M, _ = matches.shape
+    i, j = matches[..., 0], matches[..., 1]
+    valid = (i >= 0) & (j >= 0) & (i < kp1.shape[1]) & (j < kp2.shape[1])
+    p1 = torch.gather(kp1, 1, i.clamp(0, kp1.shape[1] - 1).unsqueeze(-1).expand(-1, -1, 2)).double()
+    p2 = torch.gather(kp2, 1, j.clamp(0, kp2.shape[1] - 1).unsqueeze(-1).expand(-1, -1, 2)).double()
+    keep = valid & torch.isfinite(p1).all(-1) & torch.isfinite(p2).all(-1)
+    if centre is not None:
+        c = torch.tensor(centre, dtype=torch.float64, device=kp1.device)
+        p1, p2 = p1 - c, p2 - c
+    count = torch.cumsum(keep, dim=1)
+    n = count[:, -1].to(torch.int32)
+    slot = torch.where(keep, count - 1, M)  # dropped rows land in a spare column
+    x1 = torch.zeros((B, M + 1, 2), dtype=torch.float64, device=kp1.device); x2 = torch.zeros_like(x1)
+    s2 = slot.unsqueeze(-1).expand(-1, -1, 2)
+    x1.scatter_(1, s2, p1); x2.scatter_(1, s2, p2)
+    x1[:, M] = 0.0; x2[:, M] = 0.0  # (not read: n <= M)
+    return x1[:, :M].contiguous(), x2[:, :M].contiguous(), n, slot, keep
+
+
+def time_routes(routes, reps):
+    """every route warmed twice, then alternated: ({route: seconds of every repetition}, {route: its last result})"""
+    import torch
+    times = {k: [] for k in routes}
+    last = {}
+    for rep in range(reps + 2):
+        for k, fn in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[k] = fn()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                times[k].append(time.perf_counter() - t0)
+    return times, last
+
+
+def run_baseline(a):
+    import torch
+    import mdrp_amd.poselib as poselib
+    from mdrp_amd import frontend
+    dev = torch.device("cuda", 0)
+    kind = a.baseline
+    cam1, cam2, pp, centre = baseline_arguments(kind)
+    ro = {"max_iterations": a.iters, "min_iterations": a.iters, "max_epipolar_error": 2.0 * A, "max_reproj_error": 16.0 * A}
+    t = make_inputs(a.batch, a.rows, dev, depth_maps=False)
+    gx1, gx2, gn, gslot = poselib.gather_point_matches_torch(*t, center1=centre, center2=centre)
+    ta = torch_point_front_end(*t, centre)  # the two front ends agree, and both agree with the NumPy statement on the first pairs
+    assert np.array_equal(ta[2].cpu().numpy(), gn) and torch.equal(ta[0], gx1) and torch.equal(ta[1], gx2)
+    for k in range(2):
+        ref = frontend.gather_point_matches_numpy(*(v[k].cpu().numpy() for v in t), centre, centre)
+        assert len(ref[0]) == gn[k] and gx2[k, :gn[k]].cpu().numpy().tobytes() == ref[1].tobytes() and gslot[k].cpu().numpy().tobytes() == ref[2].tobytes()
+
+    def route_a():
+        x1, x2, n, slot, keep = torch_point_front_end(*t, centre)
+        res, mask = poselib.estimate_baseline_batch_torch(kind, x1, x2, cam1, cam2, pp, ro, BO, n_per_pair=n.cpu().numpy())
+        return res, torch.where(keep, torch.gather(mask, 1, slot.clamp(max=mask.shape[1] - 1)), 0).to(torch.uint8)
+
+    routes = {"a": route_a, "b": lambda: poselib.estimate_baseline_matches_torch(kind, *t, cam1, cam2, pp, ro, BO, center1=centre, center2=centre)[:2],
+              "c": lambda: poselib.estimate_baseline_batch_torch(kind, gx1, gx2, cam1, cam2, pp, ro, BO, n_per_pair=gn)}
+    times, last = time_routes(routes, a.reps)
+    assert last["a"][0].tobytes() == last["b"][0].tobytes() == last["c"][0].tobytes(), "the routes' records differ"
+    assert torch.equal(last["a"][1], last["b"][1])
+    doc = {"shape": {"batch": a.batch, "match_rows": a.rows, "keypoints": K, "iterations": a.iters, "repetitions": a.reps, "kept_rows_mean": float(gn.mean()),
+                     "estimator": kind, "inliers_mean": float(last["b"][0]["num_inliers"].mean())},
+           "routes": {"a": "torch-op front end + estimate_baseline_batch_torch", "b": "estimate_baseline_matches_torch",
+                      "c": "estimate_baseline_batch_torch on gathered input"}}
+    for k, v in times.items():
+        v = np.array(v)
+        doc[k] = {"pairs_per_s_median": a.batch / float(np.median(v)), "ms_median": 1e3 * float(np.median(v)), "ms_min": 1e3 * float(v.min()),
+                  "ms_max": 1e3 * float(v.max()), "spread_rel": float((v.max() - v.min()) / np.median(v))}
+    doc["front_end_ms"] = {"a_minus_c": doc["a"]["ms_median"] - doc["c"]["ms_median"], "b_minus_c": doc["b"]["ms_median"] - doc["c"]["ms_median"]}
+    if a.out != "/dev/null":
+        whole = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        whole["baseline_" + kind] = doc
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(whole, open(a.out, "w"), indent=1)
+    print(json.dumps({"baseline_" + kind: doc}))
 
 
 def make_image_inputs(n_images, batch, rows, dev, outlier_frac=0.5, outlier_flags=None):
@@ -228,13 +329,17 @@ def main():
     ap.add_argument("--only", choices=["a", "b", "c"], default=None, help="run one route alone (profiler runs)")
     ap.add_argument("--image-pairs", action="store_true", help="the batch as pairs of image indices into --images images (see above)")
     ap.add_argument("--images", type=int, default=46)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_bench.json"))
+    ap.add_argument("--baseline", choices=BASELINES, default=None, help="the routes for a comparison row, without depth maps (see above)")
+    ap.add_argument("--out", default=None, help="default: profiles/frontend_bench.json (--baseline: profiles/classic_frontend_bench.json)")
     ap.add_argument("--kernel-stats", nargs="+", default=None, help="rocprofv3 *_kernel_stats.csv files (globs allowed) to fold into --out")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "classic_frontend_bench.json" if a.baseline else "frontend_bench.json")
     if a.kernel_stats:
         return fold_kernel_stats([p for g in a.kernel_stats for p in glob.glob(g, recursive=True)], a.out)
     if a.image_pairs:
         return run_image_pairs(a)
+    if a.baseline:
+        return run_baseline(a)
     import torch
     import mdrp_amd.poselib as poselib
     from mdrp_amd import frontend

@@ -16,6 +16,12 @@ estimate_image_pairs_torch, gather_image_pairs_torch).  Reports medians, the spr
 the spread of (b); writes profiles/frontend_ranked_bench.json.
 
     python tools/frontend_ranked_bench.py [--batch 1024] [--rows 2048] [--iters 10000] [--reps 21] [--out profiles/frontend_ranked_bench.json]
+
+--baseline KIND (relpose_5pt | shared_focal_6pt | fundamental_7pt): the three routes for a comparison row, which has no depths, on the
+matches form: (a) poselib.estimate_baseline_matches_torch(scores = S) — k_gather_points_ranked, the progressive sampler, k_match_mask; (b) what a
+caller writes without it — tools/frontend_bench.torch_point_front_end (torch indexing, the ordered compaction, the count copied to the host), S
+pushed through slot, estimate_baseline_batch_torch(scores =), the mask mapped back; (c) estimate_baseline_matches_torch without scores.  Writes
+under the key "baseline_<KIND>" of profiles/classic_frontend_ranked_bench.json unless --out says otherwise.
 """
 import argparse
 import json
@@ -75,6 +81,49 @@ def summarise(times, last, batch):
     return run
 
 
+def run_baseline(a):
+    import torch
+    import mdrp_amd.poselib as poselib
+    dev = torch.device("cuda", 0)
+    kind = a.baseline
+    cam1, cam2, pp, centre = fb.baseline_arguments(kind)
+    ro = {"max_iterations": a.iters, "min_iterations": a.iters, "max_epipolar_error": 2.0 * fb.A, "max_reproj_error": 16.0 * fb.A}
+    doc = {"shape": {"batch": a.batch, "match_rows": a.rows, "keypoints": fb.K, "iterations": a.iters, "repetitions": a.reps, "estimator": kind,
+                     "scores": "float32, -(outlier flag + N(0, 0.6)) per match row", "max_prosac_iterations": 100000},
+           "routes": {"a": "estimate_baseline_matches_torch, scores = tensor",
+                      "b": "torch-op front end with a host count, scores through slot, estimate_baseline_batch_torch(scores = tensor), mask through slot",
+                      "c": "estimate_baseline_matches_torch without scores"},
+           "runs": []}
+    for frac in a.outliers:
+        flags = []
+        rng = np.random.default_rng(9)
+        t = fb.make_inputs(a.batch, a.rows, dev, frac, flags, depth_maps=False)
+        scores = torch.from_numpy((-(flags[0].astype(np.float64) + rng.normal(0.0, 0.6, flags[0].shape))).astype(np.float32)).to(dev)
+        direct = lambda **kw: poselib.estimate_baseline_matches_torch(kind, *t, cam1, cam2, pp, ro, fb.BO, center1=centre, center2=centre, **kw)  # noqa: E731
+
+        def gather():
+            x1, x2, n, slot, keep = fb.torch_point_front_end(*t, centre)
+            return x1, x2, None, None, n.cpu().numpy(), torch.where(keep, slot, -1)
+
+        estimate = lambda x1, x2, d1, d2, n, sc: poselib.estimate_baseline_batch_torch(kind, x1, x2, cam1, cam2, pp, ro, fb.BO, n_per_pair=n, scores=sc)  # noqa: E731
+        routes = {"a": lambda: direct(scores=scores)[:2], "b": lambda: two_call_route(poselib, gather, estimate, scores), "c": lambda: direct()[:2]}
+        times, last = measure(routes, a.reps)
+        assert last["a"][0].tobytes() == last["b"][0].tobytes(), "the records of (a) and (b) differ"
+        assert torch.equal(last["a"][1], last["b"][1]), "the masks of (a) and (b) differ"
+        run = {"form": "matches", "outlier_frac": frac, "kept_rows_mean": float(direct()[2].mean())}
+        run.update(summarise(times, last, a.batch))
+        doc["runs"].append(run)
+        print(json.dumps(run), flush=True)
+        del routes, direct, scores, t
+        torch.cuda.empty_cache()
+    out = a.out or os.path.join(ROOT, "profiles", "classic_frontend_ranked_bench.json")
+    if out != "/dev/null":
+        whole = json.load(open(out)) if os.path.exists(out) else {}
+        whole["baseline_" + kind] = doc
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(whole, open(out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -84,8 +133,12 @@ def main():
     ap.add_argument("--outliers", type=float, nargs="+", default=[0.5, 0.85])
     ap.add_argument("--images", type=int, default=46)
     ap.add_argument("--forms", nargs="+", choices=["matches", "image_pairs"], default=["matches", "image_pairs"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_ranked_bench.json"))
+    ap.add_argument("--baseline", choices=fb.BASELINES, default=None, help="the routes for a comparison row, without depth maps (see above)")
+    ap.add_argument("--out", default=None, help="default: profiles/frontend_ranked_bench.json (--baseline: profiles/classic_frontend_ranked_bench.json)")
     a = ap.parse_args()
+    if a.baseline:
+        return run_baseline(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "frontend_ranked_bench.json")
     import torch
     import mdrp_amd.poselib as poselib
     dev = torch.device("cuda", 0)
