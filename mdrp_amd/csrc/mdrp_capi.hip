@@ -46,7 +46,15 @@ static_assert(sizeof(mdrp_result) == sizeof(ResultDev), "result layout");
 
 namespace {
 
-thread_local std::string g_err;
+// The thread's last error message.  Every failure of the library assigns it on its way out, and nothing else does: `raised` is how a call's scope
+// (MDRP_ENTER) knows that the call is failing, whichever return statement it leaves through.
+struct LastError {
+    std::string msg;
+    bool raised = false;
+    LastError &operator=(std::string m) { msg = std::move(m); raised = true; return *this; }
+    const char *c_str() const { return msg.c_str(); }
+};
+thread_local LastError g_err;
 
 #define HIPCHK(expr)                                                                                       \
     do {                                                                                                   \
@@ -204,6 +212,12 @@ struct mdrp_handle {
     int64_t count_launches = 0;
     int64_t sweep_launches = 0, sweep_evals = 0, mfma_evals = 0, fp64_evals = 0, bound_evals = 0;
     int last_batch = 0;
+    // the start of an estimator or refine call: what the fetch entry points will accept, and the counters of mdrp_last_stats at zero
+    void begin_call(int batch, int n_budgets) {
+        last_batch = batch; last_budgets = n_budgets;
+        ev_used = 0; sweep_ms = 0; count_ms = 0; sweep_launches = 0; count_launches = 0;
+        sweep_evals = 0; mfma_evals = 0; fp64_evals = 0; bound_evals = 0; lm_cost_evals = 0; lm_accum_evals = 0;
+    }
 };
 
 namespace {
@@ -368,6 +382,12 @@ int check_budgets(const mdrp_ransac_opt *ro, const uint64_t *budgets, int n_budg
     if (why) { g_err = why; return MDRP_ERR_INVALID; }
     return MDRP_OK;
 }
+// the one n_per_pair range check (n_per_pair null: n_max for every pair)
+const char *n_per_pair_out_of_range(const int32_t *n_per_pair, int batch, int n_max) {
+    for (int i = 0; n_per_pair && i < batch; ++i)
+        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) return "n_per_pair out of range";
+    return nullptr;
+}
 constexpr int HOST_SLICE_PAIRS = 256; // pairs per H2D slice of a host-buffer call (24.6 MB at N = 2000: ~0.5 ms of PCIe per slice)
 
 // one pass = a contiguous range of pairs that fits the scratch budget: what estimate_device hands run_pass (pointers offset to the pass's first pair)
@@ -389,6 +409,38 @@ struct PassIn {
     int prior_space;      // the baselines' priors: 0 = the caller's units, 1 = the estimator's normalised coordinates (include/mdrp_classic_models.h)
     const uint64_t *prosac; // ranked call: max_prosac_iterations of the progressive sampler (mdrp_prosac.h), or null: the uniform sampler
 };
+
+// One estimator call, as its entry point describes it to estimate_device (and, with the caller's models beside it, to the refine calls).  Every
+// default means "not used": an entry point names what it uses and nothing else.
+struct EstimateCall {
+    int kind = -1;
+    const double *x1 = nullptr, *x2 = nullptr, *d1 = nullptr, *d2 = nullptr; // device memory; with `host`, the handle's staging buffers, still to be filled
+    int batch = 0, n_max = 0;
+    const int32_t *n_per_pair = nullptr;          // host memory, or null: n_max for every pair
+    const mdrp_camera *cam1 = nullptr, *cam2 = nullptr;
+    const mdrp_ransac_opt *ro = nullptr;
+    const mdrp_bundle_opt *bo = nullptr;
+    uint8_t *mask_dev = nullptr;                  // the caller's device mask, or null: the handle's (its planes, in a budgets call)
+    const HostSrc *host = nullptr;                // the sliced host front (mdrp_estimate_batch[_budgets] on host buffers): run_pass issues the copies
+    const uint64_t *budgets = nullptr; int n_budgets = 0;
+    const Model *priors = nullptr; int prior_space = 0; // PassIn::priors, [batch] in device memory, and PassIn::prior_space
+    const uint64_t *prosac = nullptr;             // PassIn::prosac
+};
+
+// the pairs [p0, p0 + nb) of a call as a pass: every per-pair pointer offset by p0 (`n_host`, `mask`, `hs` and `bud` are the pass's already)
+PassIn pass_in(mdrp_handle *h, const EstimateCall &c, int p0, int nb, const int32_t *n_host, int chunk_cap, uint8_t *mask, const HostSrc *hs, const BudgetOut *bud) {
+    const size_t o1 = (size_t)p0 * c.n_max, o2 = 2 * o1;
+    PassIn in{};
+    in.kind = c.kind; in.batch = nb; in.n_max = c.n_max; in.batch_call = c.batch; in.chunk_cap = chunk_cap;
+    in.x1 = c.x1 + o2; in.x2 = c.x2 + o2; in.d1 = c.d1 ? c.d1 + o1 : nullptr; in.d2 = c.d2 ? c.d2 + o1 : nullptr;
+    in.n_host = n_host;
+    in.cam1 = c.cam1 ? c.cam1 + p0 : nullptr; in.cam2 = c.cam2 ? c.cam2 + p0 : nullptr;
+    in.ro = c.ro; in.bo = c.bo;
+    in.mask_dev = mask; in.results_dev = h->results.as<ResultDev>() + p0;
+    in.host = hs; in.bud = bud;
+    in.priors = c.priors ? c.priors + p0 : nullptr; in.prior_space = c.prior_space; in.prosac = c.prosac;
+    return in;
+}
 
 // The progressive sampler's launch for samples of `ssz` records (3, or the baselines' 5 / 6 / 7): Pass::samples and mdrp_prosac_samples[_k] both go
 // through here.  `tab`: sample index per table | schedule offsets | subset sizes (prosac_tables).
@@ -1106,41 +1158,44 @@ int run_pass(mdrp_handle *h, const PassIn &in) {
 }
 
 // what every estimator call refuses before any device work
-int estimate_refusals(mdrp_handle *h, int kind, const double *d1, const double *d2, int batch, int n_max, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                      const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo) {
-    const bool known_kind = kind >= 0 && kind <= 5;
-    if (!h || batch < 0 || n_max < 0 || !known_kind || !ro || !bo) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (kind == MDRP_SHARED_6PT && batch > 0 && !cam1) { g_err = "the 6-point estimator needs the principal point in cam1"; return MDRP_ERR_INVALID; }
-    if ((kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT) && batch > 0 && (!cam1 || !cam2)) { g_err = "calibrated estimator needs cameras"; return MDRP_ERR_INVALID; }
-    if (kind <= 2 && batch > 0 && n_max > 0 && (!d1 || !d2)) { g_err = "monodepth estimator needs depths"; return MDRP_ERR_INVALID; }
+// the cameras a kind cannot run without (MDRP_SHARED_6PT reads the principal point from cam1 only)
+const char *missing_cameras(int kind, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2) {
+    if (kind == MDRP_SHARED_6PT && batch > 0 && !cam1) return "the 6-point estimator needs the principal point in cam1";
+    if ((kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT) && batch > 0 && (!cam1 || !cam2)) return "calibrated estimator needs cameras";
+    return nullptr;
+}
+
+int estimate_refusals(mdrp_handle *h, const EstimateCall &c) {
+    const bool known_kind = c.kind >= 0 && c.kind <= 5;
+    if (!h || c.batch < 0 || c.n_max < 0 || !known_kind || !c.ro || !c.bo) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (const char *why = missing_cameras(c.kind, c.batch, c.cam1, c.cam2)) { g_err = why; return MDRP_ERR_INVALID; }
+    if (c.kind <= 2 && c.batch > 0 && c.n_max > 0 && (!c.d1 || !c.d2)) { g_err = "monodepth estimator needs depths"; return MDRP_ERR_INVALID; }
     // RansacOptions switches of the reference that are not built are refused, never ignored (the reference would return different results)
-    if (ro->progressive_sampling) { g_err = "progressive_sampling (PROSAC, RandomSampler::initialize_prosac) is not built on this entry point: it needs the match scores, mdrp_estimate_batch_ranked (scores= in Python) takes them"; return MDRP_ERR_UNSUPPORTED; }
-    if (ro->real_focal_check && (kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT)) { g_err = "real_focal_check is not built"; return MDRP_ERR_UNSUPPORTED; }
+    if (c.ro->progressive_sampling) { g_err = "progressive_sampling (PROSAC, RandomSampler::initialize_prosac) is not built on this entry point: it needs the match scores, mdrp_estimate_batch_ranked (scores= in Python) takes them"; return MDRP_ERR_UNSUPPORTED; }
+    if (c.ro->real_focal_check && (c.kind == MDRP_SHARED_6PT || c.kind == MDRP_FUNDAMENTAL_7PT)) { g_err = "real_focal_check is not built"; return MDRP_ERR_UNSUPPORTED; }
     return MDRP_OK;
 }
 
-int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
-                    int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                    const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, const HostSrc *host = nullptr,
-                    const uint64_t *budgets = nullptr, int n_budgets = 0, const Model *priors = nullptr /*[batch] in device memory*/,
-                    const uint64_t *prosac = nullptr /*ranked call: max_prosac_iterations*/, int prior_space = 0 /*the baselines' priors*/) {
-    if (int rc = estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, ro, bo)) return rc;
-    if (priors && (host || budgets)) { g_err = "priors: device-resident calls without budgets only"; return MDRP_ERR_INVALID; }
-    if (prosac && (host || budgets || priors)) { g_err = "ranked: device-resident calls without budgets or priors only"; return MDRP_ERR_INVALID; }
-    h->last_budgets = n_budgets;
+// Runs a call on the handle's streams: refusals, the handle's per-call state, the passes.  Returns with the work queued (a pass synchronises once per super-chunk).
+int estimate_device(mdrp_handle *h, const EstimateCall &c) {
+    const int kind = c.kind, batch = c.batch, n_max = c.n_max, n_budgets = c.n_budgets;
+    const int32_t *n_per_pair = c.n_per_pair;
+    const mdrp_ransac_opt *ro = c.ro;
+    const uint64_t *budgets = c.budgets;
+    if (int rc = estimate_refusals(h, c)) return rc;
+    if (c.priors && (c.host || budgets)) { g_err = "priors: device-resident calls without budgets only"; return MDRP_ERR_INVALID; }
+    if (c.prosac && (c.host || budgets || c.priors)) { g_err = "ranked: device-resident calls without budgets or priors only"; return MDRP_ERR_INVALID; }
+    h->begin_call(batch, n_budgets);
     if (h->fuse_disabled && --h->fuse_retry_in <= 0) h->fuse_disabled = false; // once per API call (not per pass): the handle tries the fused tail again
-    h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
     int rc;
     if ((rc = h->results.ensure(sizeof(ResultDev) * std::max(batch, 1)))) return rc;
     if ((rc = h->lm_stats.ensure(LM_STATS_BYTES))) return rc;
     HIPCHK(hipMemsetAsync(h->lm_stats.p, 0, LM_STATS_BYTES, h->stream));
     if (batch == 0) return MDRP_OK;
+    if (const char *why = n_per_pair_out_of_range(n_per_pair, batch, n_max)) { g_err = why; return MDRP_ERR_INVALID; } // (the plain entry points have no check before this one)
     std::vector<int32_t> n_host(batch);
-    for (int i = 0; i < batch; ++i) {
-        n_host[i] = n_per_pair ? n_per_pair[i] : n_max;
-        if (n_host[i] < 0 || n_host[i] > n_max) { g_err = "n_per_pair out of range"; return MDRP_ERR_INVALID; }
-    }
-    uint8_t *mask = mask_dev;
+    for (int i = 0; i < batch; ++i) n_host[i] = n_per_pair ? n_per_pair[i] : n_max;
+    uint8_t *mask = c.mask_dev;
     if (!mask) {
         if ((rc = (budgets ? h->bmask : h->mask).ensure((size_t)std::max(n_budgets, 1) * batch * std::max(n_max, 1)))) return rc;
         mask = (budgets ? h->bmask : h->mask).as<uint8_t>();
@@ -1163,12 +1218,9 @@ int estimate_device(mdrp_handle *h, int kind, const double *x1, const double *x2
         const int nb = std::min(per_pass, batch - p0);
         const size_t o1 = (size_t)p0 * n_max, o2 = 2 * o1;
         HostSrc hs{};
-        if (host) hs = HostSrc{host->x1 + o2, host->x2 + o2, host->d1 ? host->d1 + o1 : nullptr, host->d2 ? host->d2 + o1 : nullptr};
+        if (c.host) hs = HostSrc{c.host->x1 + o2, c.host->x2 + o2, c.host->d1 ? c.host->d1 + o1 : nullptr, c.host->d2 ? c.host->d2 + o1 : nullptr};
         const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + o1, batch};
-        const PassIn in{kind, x1 + o2, x2 + o2, d1 ? d1 + o1 : nullptr, d2 ? d2 + o1 : nullptr, nb, n_max, n_host.data() + p0, cam1 ? cam1 + p0 : nullptr,
-                        cam2 ? cam2 + p0 : nullptr, ro, bo, chunk_cap, mask + o1, h->results.as<ResultDev>() + p0, host ? &hs : nullptr, batch,
-                        budgets ? &bud : nullptr, priors ? priors + p0 : nullptr, prior_space, prosac};
-        if ((rc = run_pass(h, in))) return rc;
+        if ((rc = run_pass(h, pass_in(h, c, p0, nb, n_host.data() + p0, chunk_cap, mask + o1, c.host ? &hs : nullptr, budgets ? &bud : nullptr)))) return rc;
     }
     if (budgets) {
         HIPCHK(hipMemcpyAsync(h->results.p, h->bresults.as<ResultDev>() + (size_t)(n_budgets - 1) * batch, sizeof(ResultDev) * batch, hipMemcpyDeviceToDevice, h->stream));
@@ -1208,11 +1260,24 @@ int finish_timing(mdrp_handle *h) {
 
 } // namespace
 
-// serialise calls on one handle and run them on the handle's device; the caller's current device is restored on return
+// The one failure path behind MDRP_ENTER: a call that fails - a buffer that cannot grow, a HIP error, a helper's refusal - leaves through here whichever
+// `return` it takes, and nothing of it stays in flight on the caller's buffers or the handle's: every stream of the handle is drained before the error
+// is returned.  (A failure is what assigns g_err; a call that succeeds pays nothing.)
+struct DrainOnFailure {
+    mdrp_handle *const h;
+    explicit DrainOnFailure(mdrp_handle *h_) : h(h_) { g_err.raised = false; }
+    ~DrainOnFailure() {
+        if (!g_err.raised) return;
+        for (hipStream_t st : {h->stream, (hipStream_t)h->aux_stream, (hipStream_t)h->aux_stream2, (hipStream_t)h->copy_stream}) (void)hipStreamSynchronize(st);
+    }
+};
+
+// serialise calls on one handle and run them on the handle's device; the caller's current device is restored on return; a failing call drains the handle
 #define MDRP_ENTER(h)                                                                      \
     std::lock_guard<std::mutex> lock_((h)->mu);                                            \
     DeviceGuard guard_((h)->device);                                                       \
-    if (!guard_.ok) { g_err = "hipSetDevice failed"; return MDRP_ERR_HIP; }
+    if (!guard_.ok) { g_err = "hipSetDevice failed"; return MDRP_ERR_HIP; }                \
+    DrainOnFailure drain_(h);
 
 #ifndef MDRP_SRC_HASH
 #define MDRP_SRC_HASH "unknown"
@@ -1345,32 +1410,55 @@ int mdrp_synchronize(mdrp_handle *h) {
     return MDRP_OK;
 }
 
-// an error behind the first device work: nothing of the call stays in flight on the caller's buffers
-static int drain_and_return(mdrp_handle *h, int rc) {
-    for (hipStream_t st : {h->stream, (hipStream_t)h->aux_stream, (hipStream_t)h->aux_stream2, (hipStream_t)h->copy_stream}) (void)hipStreamSynchronize(st);
-    return rc;
-}
+} // extern "C"
 
-// the asynchronous calls, plain (budgets null) and with budgets
-static int estimate_async_locked(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
-                                 const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                                 const mdrp_bundle_opt *bopt, const uint64_t *budgets, int n_budgets, uint8_t *inlier_mask_dev) {
-    const int rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, budgets, n_budgets);
-    return rc ? drain_and_return(h, rc) : rc;
-}
+// The estimator, refine, gather and rank entry points.  Each one is: refuse | fill the call record by name | run (blocking: stage, run, finish); the pieces
+// are mdrp_capi_entry.h's.  A failure behind MDRP_ENTER drains the handle (DrainOnFailure): no entry point does it by hand.
+#include "mdrp_capi_entry.h"
 
+extern "C" {
+
+// ---- the estimators, plain and with iteration budgets
 int mdrp_estimate_batch_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2,
                               int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
                               const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
     if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.mask_dev = inlier_mask_dev;
     MDRP_ENTER(h);
-    return estimate_async_locked(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, nullptr, 0, inlier_mask_dev);
+    return estimate_device(h, c);
 }
 
-static int fetch_results_locked(mdrp_handle *h, mdrp_result *out, int batch) {
-    if (!out || batch < 0 || batch > h->last_batch) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    HIPCHK(hipMemcpyAsync(out, h->results.p, sizeof(ResultDev) * batch, hipMemcpyDeviceToHost, h->stream));
-    return finish_timing(h);
+int mdrp_estimate_batch_budgets_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2,
+                                      int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                      const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets, int n_budgets,
+                                      uint8_t *inlier_mask_dev) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.mask_dev = inlier_mask_dev; c.budgets = budgets; c.n_budgets = n_budgets;
+    MDRP_ENTER(h);
+    return estimate_device(h, c);
+}
+
+int mdrp_estimate_batch(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
+                        const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
+                        const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out,
+                        uint8_t *inlier_mask) {
+    if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    return estimate_batch_blocking(h, c, mem_space, out, inlier_mask);
+}
+
+int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
+                                const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
+                                const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets,
+                                int n_budgets, mdrp_result *out, uint8_t *inlier_mask) {
+    if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.budgets = budgets; c.n_budgets = n_budgets;
+    return estimate_batch_blocking(h, c, mem_space, out, inlier_mask);
 }
 
 int mdrp_copy_results_device(mdrp_handle *h, void *dst_dev, int batch) {
@@ -1386,28 +1474,6 @@ int mdrp_fetch_results(mdrp_handle *h, mdrp_result *out, int batch) {
     return fetch_results_locked(h, out, batch);
 }
 
-// ---- iteration budgets
-static_assert(MDRP_MAX_BUDGETS == MAX_BUDGETS, "budget limit of the header and of the kernels");
-
-static int budget_results_locked(mdrp_handle *h, void *dst, int n_budgets, int batch, hipMemcpyKind where) {
-    if (!dst || batch < 0 || n_budgets < 1 || n_budgets != h->last_budgets || batch != h->last_batch) {
-        g_err = "budget results: n_budgets and batch must be those of the handle's last budgets call";
-        return MDRP_ERR_INVALID;
-    }
-    if (batch > 0) HIPCHK(hipMemcpyAsync(dst, h->bresults.p, sizeof(ResultDev) * n_budgets * batch, where, h->stream));
-    return finish_timing(h);
-}
-
-int mdrp_estimate_batch_budgets_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2,
-                                      int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                                      const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets, int n_budgets,
-                                      uint8_t *inlier_mask_dev) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
-    MDRP_ENTER(h);
-    return estimate_async_locked(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, budgets, n_budgets, inlier_mask_dev);
-}
-
 int mdrp_fetch_budget_results(mdrp_handle *h, mdrp_result *out, int n_budgets, int batch) {
     if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     MDRP_ENTER(h);
@@ -1420,790 +1486,230 @@ int mdrp_copy_budget_results_device(mdrp_handle *h, void *dst_dev, int n_budgets
     return budget_results_locked(h, dst_dev, n_budgets, batch, hipMemcpyDeviceToDevice); // (waits for the handle's stream, as mdrp_copy_results_device)
 }
 
-// The blocking calls, plain (budgets null) and with budgets: host buffers are staged in the handle's device buffers (the copies are issued by
-// run_pass, slice by slice on the handle's copy stream, beside the first kernels of the slices before them) and their masks copied back from the
-// handle's; then the records are fetched.
-static int estimate_batch_locked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
-                                 int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                                 const mdrp_bundle_opt *bopt, const uint64_t *budgets, int n_budgets, mdrp_result *out, uint8_t *inlier_mask) {
-    const size_t np = (size_t)batch * n_max;
-    const bool use_host = mem_space == MDRP_MEM_HOST;
-    int rc;
-    HostSrc hsrc{};
-    if (use_host) {
-        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
-            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)))
-            return rc;
-        hsrc = HostSrc{x1, x2, (d1 && d2) ? d1 : nullptr, (d1 && d2) ? d2 : nullptr};
-        if (d1 && d2) { d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>(); }
-        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
-    }
-    // (host call: a handle-owned device mask, or its planes, copied back below)
-    rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask, use_host ? &hsrc : nullptr, budgets, n_budgets);
-    if (rc) return drain_and_return(h, rc);
-    if (use_host && inlier_mask && np > 0 &&
-        hipMemcpyAsync(inlier_mask, (budgets ? h->bmask : h->mask).p, np * (budgets ? n_budgets : 1), hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-        g_err = "copy of the inlier masks failed";
-        return drain_and_return(h, MDRP_ERR_HIP);
-    }
-    rc = budgets ? budget_results_locked(h, out, n_budgets, batch, hipMemcpyDeviceToHost) : fetch_results_locked(h, out, batch);
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-int mdrp_estimate_batch(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
-                        const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
-                        const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out,
-                        uint8_t *inlier_mask) {
-    if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    return estimate_batch_locked(h, kind, mem_space, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, nullptr, 0, out, inlier_mask);
-}
-
-int mdrp_estimate_batch_budgets(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1,
-                                const double *d2, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1,
-                                const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const uint64_t *budgets,
-                                int n_budgets, mdrp_result *out, uint8_t *inlier_mask) {
-    if (!h || !out || batch < 0 || n_max < 0) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_budgets(ropt, budgets, n_budgets)) return rc;
-    MDRP_ENTER(h);
-    return estimate_batch_locked(h, kind, mem_space, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, budgets, n_budgets, out, inlier_mask);
-}
-
-} // extern "C"
-
-// ---- estimate with a prior (include/mdrp.h; mdrp_prior.h)
-// what both entry points refuse before any device work, beyond what estimate_device refuses for every estimator call
-static int check_prior_args(mdrp_handle *h, int kind, const double *d1, const double *d2, int batch, int n_max, const int32_t *n_per_pair,
-                            const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, const mdrp_model *prior) {
-    const char *why = nullptr;
-    if (!h) why = "invalid argument";
-    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "prior: only the monodepth estimators (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL)";
-    else if (batch < 0 || n_max < 0) why = "prior: a negative size";
-    else if (batch > 0 && !prior) why = "prior: prior is NULL";
-    for (int i = 0; !why && n_per_pair && i < batch; ++i)
-        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
-    if (why) { g_err = why; return MDRP_ERR_INVALID; }
-    return estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, ro, bo); // (the option refusals are the estimator's own)
-}
-
-extern "C" {
-
+// ---- estimate with a prior
 int mdrp_estimate_batch_prior_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
                                     const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
                                     const mdrp_bundle_opt *bopt, const mdrp_model *prior_dev, uint8_t *inlier_mask_dev) {
-    if (int rc = check_prior_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior_dev)) return rc;
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.priors = reinterpret_cast<const Model *>(prior_dev); c.mask_dev = inlier_mask_dev;
+    if (int rc = refuse(REFUSE_PRIOR, h, c, resident_args(prior_dev))) return rc;
     MDRP_ENTER(h);
-    const int rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, nullptr, 0,
-                                   reinterpret_cast<const Model *>(prior_dev));
-    return rc ? drain_and_return(h, rc) : rc;
+    return estimate_device(h, c);
 }
 
-// The blocking form.  Host buffers are copied in plainly on the handle's stream and the call then runs the device-resident path (mdrp_refine_batch does
-// the same): the sliced host front prepares and solves slices on other streams, which a kernel between k_prep and the first solver cannot follow.
 int mdrp_estimate_batch_prior(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, int batch,
                               int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
                               const mdrp_bundle_opt *bopt, const mdrp_model *prior, mdrp_result *out, uint8_t *inlier_mask) {
-    if (int rc = check_prior_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior)) return rc;
-    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) { g_err = "monodepth estimator needs correspondences and depths"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
-    const bool use_host = mem_space == MDRP_MEM_HOST;
-    hipStream_t s = h->stream;
-    int rc;
-    const Model *prior_dev = reinterpret_cast<const Model *>(prior);
-    if (use_host && batch > 0) {
-        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
-            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)) || (rc = h->fm_models.ensure(sizeof(Model) * b)))
-            return rc;
-        if (np > 0) {
-            HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
-        }
-        HIPCHK(hipMemcpyAsync(h->fm_models.p, prior, sizeof(Model) * b, hipMemcpyHostToDevice, s));
-        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>(); d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
-        prior_dev = h->fm_models.as<Model>();
-    }
-    rc = estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask, nullptr, nullptr, 0, prior_dev);
-    if (rc) return drain_and_return(h, rc);
-    if (use_host && inlier_mask && np > 0 && hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s) != hipSuccess) {
-        g_err = "copy of the inlier masks failed";
-        return drain_and_return(h, MDRP_ERR_HIP);
-    }
-    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
-    return rc ? drain_and_return(h, rc) : rc;
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.priors = reinterpret_cast<const Model *>(prior);
+    if (int rc = refuse(REFUSE_PRIOR, h, c, blocking_args(mem_space, out, prior))) return rc;
+    return run_blocking(h, c, mem_space, &c.priors, nullptr, out, inlier_mask, nullptr, [&] { return estimate_device(h, c); });
 }
 
-} // extern "C"
-
-// ---- refine and verify caller-supplied models (include/mdrp.h; mdrp_from_model.h)
-// What mdrp_refine_batch and mdrp_refine_classic share in front of their one kernel: the handle's counters and result buffers, the per-call parameters
-// in one block, the record / state buffers, the mask (the caller's or the handle's), the run parameters, and the events around the launch.
-struct RefineStage {
-    const int32_t *nper, *table_of;
-    const CamDev *cam1, *cam2;
-    uint8_t *mask;
-    RunParams rp;
-    hipEvent_t f0, f1; // reported as the final refinement's time (mdrp_stats::final_ms / final_launches)
-};
-// returns MDRP_OK with st.mask == nullptr for an empty batch (nothing to launch)
-static int refine_stage(mdrp_handle *h, int kind, int est_shift, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                        const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, uint8_t *mask_dev, RefineStage &st) {
-    hipStream_t s = h->stream;
-    st.mask = nullptr;
-    h->last_budgets = 0;
-    h->ev_used = 0; h->sweep_ms = 0; h->sweep_launches = 0; h->sweep_evals = 0; h->mfma_evals = 0; h->fp64_evals = 0; h->bound_evals = 0; h->count_launches = 0; h->count_ms = 0; h->last_batch = batch; h->lm_cost_evals = 0; h->lm_accum_evals = 0;
-    int rc;
-    if ((rc = h->results.ensure(sizeof(ResultDev) * std::max(batch, 1))) || (rc = h->lm_stats.ensure(LM_STATS_BYTES))) return rc;
-    HIPCHK(hipMemsetAsync(h->lm_stats.p, 0, LM_STATS_BYTES, s));
-    if (batch == 0) return MDRP_OK;
-    const size_t b = (size_t)batch, n = (size_t)n_max;
-    const bool mono = kind <= MDRP_VARYING_FOCAL;
-    // per-call parameters in one block: cameras 1 | cameras 2 | table of pair (zeros: there are no sample tables) | n per pair.  Staged in pageable
-    // memory (the copy has left it when hipMemcpyAsync returns): an asynchronous call may be followed by the next one before the stream has drained
-    const size_t off_cam2 = sizeof(CamDev) * b, off_tof = 2 * sizeof(CamDev) * b, off_nper = off_tof + sizeof(int32_t) * b, bytes = off_nper + sizeof(int32_t) * b;
-    std::vector<unsigned char> params(bytes, 0);
-    if (kind == MDRP_CALIB || kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT) { // MDRP_SHARED_6PT reads the principal point from cam1 only: cam2 may be NULL there
-        std::memcpy(params.data(), cam1, sizeof(CamDev) * b);
-        std::memcpy(params.data() + off_cam2, cam2 ? cam2 : cam1, sizeof(CamDev) * b);
-    }
-    int32_t *nper = reinterpret_cast<int32_t *>(params.data() + off_nper);
-    for (int i = 0; i < batch; ++i) nper[i] = n_per_pair ? n_per_pair[i] : n_max;
-    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * b * std::max<size_t>(n, 1))) || (mono && (rc = h->dep.ensure(sizeof(double) * 2 * b * n))) ||
-        (rc = h->st.ensure(sizeof(PairState) * b)) || (rc = h->params.ensure(bytes)))
-        return rc;
-    uint8_t *mask = mask_dev;
-    if (!mask) { // (the baselines' kernel uses the mask as its LO's subset mask as well)
-        if ((rc = h->mask.ensure(b * std::max(n_max, 1)))) return rc;
-        mask = h->mask.as<uint8_t>();
-    }
-    unsigned char *pd = h->params.as<unsigned char>();
-    HIPCHK(hipMemcpyAsync(pd, params.data(), bytes, hipMemcpyHostToDevice, s));
-    st.nper = reinterpret_cast<const int32_t *>(pd + off_nper); st.table_of = reinterpret_cast<const int32_t *>(pd + off_tof);
-    st.cam1 = reinterpret_cast<const CamDev *>(pd); st.cam2 = reinterpret_cast<const CamDev *>(pd + off_cam2);
-    RunParams &rp = st.rp;
-    std::memset(&rp, 0, sizeof rp);
-    rp.kind = kind; rp.solver = solver_for(kind, est_shift); rp.est_shift = est_shift;
-    rp.batch = batch; rp.n_max = n_max;
-    if (!mono) { rp.mps = sched::model_slots(kind); rp.sample_sz = sched::sample_size(kind); } // (kc_prep: a pair of fewer records than the sample size is empty)
-    rp.weight_sampson = (mono && ro->monodepth_weight_sampson > 0.0f) ? (double)ro->monodepth_weight_sampson : 0.0;
-    rp.final_max_it = (int)std::min<uint64_t>(bo->max_iterations, 1u << 30); rp.final_loss = bo->loss_type;
-    rp.grad_tol = bo->gradient_tol; rp.step_tol = bo->step_tol; rp.lambda0 = bo->initial_lambda;
-    rp.lambda_min = bo->min_lambda; rp.lambda_max = bo->max_lambda;
-    if ((rc = get_events(h, &st.f0, &st.f1, 3))) return rc;
-    st.mask = mask;
-    return MDRP_OK;
-}
-
-// k_prep as the estimators launch it (no MFMA fragments, no sample tables, score_initial = 0), then ONE launch of k_from_model on the handle's stream:
-// nothing else of a pass is allocated or run.  Pointers are device memory, `models` included; initial_* may be null.
-static int refine_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
-                         const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
-                         const Model *models, int stages, uint8_t *mask_dev, double *init_score, int32_t *init_inl) {
-    hipStream_t s = h->stream;
-    const int est_shift = (kind == MDRP_CALIB && ro->monodepth_estimate_shift) ? 1 : 0;
-    RefineStage st;
-    if (int rc = refine_stage(h, kind, est_shift, batch, n_max, n_per_pair, cam1, cam2, ro, bo, mask_dev, st)) return rc;
-    if (!st.mask) return MDRP_OK;
-    const RunParams &rp = st.rp;
-    uint8_t *mask = st.mask;
-    hipLaunchKernelGGL(k_prep, dim3(batch), dim3(256), 0, s, rp, x1, x2, d1, d2, st.nper, st.table_of, st.cam1, st.cam2,
-                       ro->max_epipolar_error, ro->max_reproj_error, bo->loss_scale, h->pts.as<double>(), h->dep.as<double>(), h->st.as<PairState>(),
-                       (uint4 *)nullptr);
-    HIPCHK(hipEventRecord(st.f0, s));
-    const size_t smem = lm_final_list_bytes(n_max);
-    const int stride = lm_list_stride(n_max), midx = lm_mask_index_on(n_max);
-#define MDRP_FROM_MODEL_LAUNCH(K, S)                                                                                                                      \
-    hipLaunchKernelGGL((k_from_model<K, S>), dim3(batch), dim3(FROM_MODEL_THREADS), smem, s, rp, (const PairState *)h->st.as<PairState>(),                \
-                       (const double *)h->pts.as<double>(), (const double *)h->dep.as<double>(), models, stages, mask, h->results.as<ResultDev>(), init_score, \
-                       init_inl, stride, midx, h->lm_stats.as<unsigned long long>() + 2)
-    if (kind == MDRP_CALIB && est_shift) MDRP_FROM_MODEL_LAUNCH(0, true);
-    else if (kind == MDRP_CALIB) MDRP_FROM_MODEL_LAUNCH(0, false);
-    else if (kind == MDRP_SHARED_FOCAL) MDRP_FROM_MODEL_LAUNCH(1, false);
-    else MDRP_FROM_MODEL_LAUNCH(2, false);
-#undef MDRP_FROM_MODEL_LAUNCH
-    HIPCHK(hipEventRecord(st.f1, s));
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-// what both entry points refuse before any device work
-static int check_refine_args(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
-                             const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
-                             const mdrp_model *models, int stages) {
-    const char *why = nullptr;
-    if (!h || !ro || !bo) why = "invalid argument";
-    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "refine: only the monodepth estimators' models (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL)";
-    else if (batch < 0 || n_max < 0) why = "refine: a negative size";
-    else if (stages < 0 || stages > (MDRP_STAGE_LO | MDRP_STAGE_INLIERS)) why = "refine: stages must be a combination of MDRP_STAGE_LO and MDRP_STAGE_INLIERS";
-    else if (batch > 0 && !models) why = "refine: models is NULL";
-    else if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) why = "refine: correspondences and depths are required";
-    else if (kind == MDRP_CALIB && batch > 0 && (!cam1 || !cam2)) why = "calibrated estimator needs cameras";
-    for (int i = 0; !why && n_per_pair && i < batch; ++i)
-        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
-    if (why) { g_err = why; return MDRP_ERR_INVALID; }
-    return MDRP_OK;
-}
-
-extern "C" {
-
-static_assert(MDRP_STAGE_LO == STAGE_LO && MDRP_STAGE_INLIERS == STAGE_INLIERS, "stage flags of the header and of the kernel");
-
+// ---- refine and verify caller-supplied models
 int mdrp_refine_batch_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
                             const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
                             const mdrp_bundle_opt *bopt, const mdrp_model *models_dev, int stages, uint8_t *inlier_mask_dev, double *initial_score_dev,
                             int32_t *initial_inliers_dev) {
-    if (int rc = check_refine_args(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev, stages)) return rc;
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.mask_dev = inlier_mask_dev;
+    if (int rc = refuse(REFUSE_REFINE, h, c, resident_args(models_dev, stages))) return rc;
     MDRP_ENTER(h);
-    const int rc = refine_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, reinterpret_cast<const Model *>(models_dev), stages,
-                                 inlier_mask_dev, initial_score_dev, initial_inliers_dev);
-    return rc ? drain_and_return(h, rc) : rc;
+    return refine_device(h, c, reinterpret_cast<const Model *>(models_dev), stages, initial_score_dev, initial_inliers_dev);
 }
 
 int mdrp_refine_batch(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, int batch, int n_max,
                       const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
                       const mdrp_model *models, int stages, mdrp_result *out, uint8_t *inlier_mask, double *initial_score, int32_t *initial_inliers) {
-    if (int rc = check_refine_args(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models, stages)) return rc;
-    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
-    const bool use_host = mem_space == MDRP_MEM_HOST;
-    hipStream_t s = h->stream;
-    int rc;
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    if (int rc = refuse(REFUSE_REFINE, h, c, blocking_args(mem_space, out, models, stages))) return rc;
     const Model *models_dev = reinterpret_cast<const Model *>(models);
-    if (use_host && batch > 0) { // plain copies on the handle's stream
-        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
-            (rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)) || (rc = h->fm_models.ensure(sizeof(Model) * b)))
-            return rc;
-        if (np > 0) {
-            HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
-        }
-        HIPCHK(hipMemcpyAsync(h->fm_models.p, models, sizeof(Model) * b, hipMemcpyHostToDevice, s));
-        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>(); d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
-        models_dev = h->fm_models.as<Model>();
-    }
-    // the start-model scores are host outputs whatever mem_space says: a buffer of the handle, copied back
-    const size_t off_inl = sizeof(double) * b;
-    if ((initial_score || initial_inliers) && (rc = h->fm_init.ensure(off_inl + sizeof(int32_t) * b + 16))) return rc;
-    double *is_dev = initial_score ? h->fm_init.as<double>() : nullptr;
-    int32_t *ii_dev = initial_inliers ? reinterpret_cast<int32_t *>(h->fm_init.as<unsigned char>() + off_inl) : nullptr;
-    rc = refine_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev, stages, use_host ? nullptr : inlier_mask, is_dev, ii_dev);
-    if (rc) return drain_and_return(h, rc);
-    hipError_t e = hipSuccess;
-    if (use_host && inlier_mask && np > 0) e = hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && is_dev && batch > 0) e = hipMemcpyAsync(initial_score, is_dev, sizeof(double) * b, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && ii_dev && batch > 0) e = hipMemcpyAsync(initial_inliers, ii_dev, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) { g_err = "copy of the masks or start-model scores failed"; return drain_and_return(h, MDRP_ERR_HIP); }
-    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
-    return rc ? drain_and_return(h, rc) : rc;
+    StartOutputs start{initial_score, initial_inliers};
+    return run_blocking(h, c, mem_space, &models_dev, nullptr, out, inlier_mask, &start,
+                        [&] { return refine_device(h, c, models_dev, stages, start.score_dev, start.inl_dev); });
 }
 
-} // extern "C"
+// ---- the baselines from a caller's model
+int mdrp_refine_classic_async(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                              const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                              const mdrp_model *models_dev, int stages, uint8_t *inlier_mask_dev, double *initial_score_dev, int32_t *initial_inliers_dev) {
+    EstimateCall c = call_of(kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.mask_dev = inlier_mask_dev;
+    if (int rc = refuse(REFUSE_REFINE_CLASSIC, h, c, resident_args(models_dev, stages))) return rc;
+    MDRP_ENTER(h);
+    return refine_classic_device(h, c, reinterpret_cast<const Model *>(models_dev), stages, initial_score_dev, initial_inliers_dev);
+}
 
-// ---- device front end (mdrp_frontend.h)
-static int check_matches(const mdrp_matches *mm, int batch) {
+int mdrp_refine_classic(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                        const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const mdrp_model *models,
+                        int stages, mdrp_result *out, uint8_t *inlier_mask, double *initial_score, int32_t *initial_inliers) {
+    EstimateCall c = call_of(kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    if (int rc = refuse(REFUSE_REFINE_CLASSIC, h, c, blocking_args(mem_space, out, models, stages))) return rc;
+    const Model *models_dev = reinterpret_cast<const Model *>(models);
+    StartOutputs start{initial_score, initial_inliers};
+    return run_blocking(h, c, mem_space, &models_dev, nullptr, out, inlier_mask, &start,
+                        [&] { return refine_classic_device(h, c, models_dev, stages, start.score_dev, start.inl_dev); });
+}
+
+int mdrp_estimate_classic_prior_async(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                      const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                      const mdrp_model *prior_dev, int prior_space, uint8_t *inlier_mask_dev) {
+    EstimateCall c = call_of(kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.priors = reinterpret_cast<const Model *>(prior_dev); c.prior_space = prior_space; c.mask_dev = inlier_mask_dev;
+    if (int rc = refuse(REFUSE_CLASSIC_PRIOR, h, c, resident_args(prior_dev))) return rc;
+    MDRP_ENTER(h);
+    return estimate_device(h, c);
+}
+
+int mdrp_estimate_classic_prior(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
+                                const mdrp_model *prior, int prior_space, mdrp_result *out, uint8_t *inlier_mask) {
+    EstimateCall c = call_of(kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.priors = reinterpret_cast<const Model *>(prior); c.prior_space = prior_space;
+    if (int rc = refuse(REFUSE_CLASSIC_PRIOR, h, c, blocking_args(mem_space, out, prior))) return rc;
+    return run_blocking(h, c, mem_space, &c.priors, nullptr, out, inlier_mask, nullptr, [&] { return estimate_device(h, c); });
+}
+
+// ---- estimate in match-score order: the monodepth estimators, then the 5- / 6- / 7-point baselines (no depths)
+int mdrp_estimate_batch_ranked_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, const double *scores_dev,
+                                     int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                     const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.mask_dev = inlier_mask_dev;
+    if (int rc = refuse(REFUSE_RANKED, h, c, resident_args())) return rc;
+    MDRP_ENTER(h);
+    return ranked_device(h, c, scores_dev);
+}
+
+int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
+                               const double *scores, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                               const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
+    EstimateCall c = call_of(kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    if (int rc = refuse(REFUSE_RANKED, h, c, blocking_args(mem_space, out))) return rc;
+    return run_blocking(h, c, mem_space, nullptr, &scores, out, inlier_mask, nullptr, [&] { return ranked_device(h, c, scores); });
+}
+
+int mdrp_estimate_classic_ranked_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *scores_dev, int batch, int n_max,
+                                       const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                       const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
+    EstimateCall c = call_of(kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    c.mask_dev = inlier_mask_dev;
+    if (int rc = refuse(REFUSE_CLASSIC_RANKED, h, c, resident_args())) return rc;
+    MDRP_ENTER(h);
+    return ranked_device(h, c, scores_dev);
+}
+
+int mdrp_estimate_classic_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *scores, int batch, int n_max,
+                                 const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
+                                 const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
+    EstimateCall c = call_of(kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt);
+    if (int rc = refuse(REFUSE_CLASSIC_RANKED, h, c, blocking_args(mem_space, out))) return rc;
+    return run_blocking(h, c, mem_space, nullptr, &scores, out, inlier_mask, nullptr, [&] { return ranked_device(h, c, scores); });
+}
+
+// k_rank alone: order [batch][n_max] int32 in mem_space (-1 at and past n).  Synchronous.  (Not an estimator call: no record, its own three refusals.)
+int mdrp_rank_scores(mdrp_handle *h, int mem_space, const double *scores, int batch, int n_max, const int32_t *n_per_pair, int32_t *order) {
     const char *why = nullptr;
-    if (!mm || batch < 0) why = "invalid argument";
-    else if ((mm->kp_type != MDRP_F32 && mm->kp_type != MDRP_F64) || (mm->depth_type != MDRP_F32 && mm->depth_type != MDRP_F64)) why = "kp_type / depth_type must be MDRP_F32 or MDRP_F64";
-    else if (mm->filter != MDRP_FILTER_BOTH_INF && mm->filter != MDRP_FILTER_FINITE) why = "unknown filter";
-    else if (mm->k1 < 0 || mm->k2 < 0 || mm->m_max < 0 || mm->h1 < 0 || mm->w1 < 0 || mm->h2 < 0 || mm->w2 < 0) why = "negative size";
-    else if (batch > 0 && mm->m_max > 0 &&
-             (!mm->matches || (mm->k1 > 0 && !mm->kp1) || (mm->k2 > 0 && !mm->kp2) || (mm->h1 > 0 && mm->w1 > 0 && !mm->depth1) ||
-              (mm->h2 > 0 && mm->w2 > 0 && !mm->depth2)))
-        why = "NULL keypoints, matches or depth map";
-    if (why) { g_err = std::string("mdrp_matches: ") + why; return MDRP_ERR_INVALID; }
-    return MDRP_OK;
-}
-
-// the ranked front end's key scratch (one key per match row), a buffer of the handle
-static int ensure_key_scratch(mdrp_handle *h, int batch, int m_max) { return h->fe_key.ensure(sizeof(uint64_t) * (size_t)batch * m_max + 16); }
-
-// k_gather on the handle's stream (the descriptor has passed check_matches); n_dev: [batch] on the device.  With scores ([batch][m_max] of
-// score_type, device memory): k_gather_ranked, the kept rows at their ranks; the handle's key scratch has been sized (ensure_key_scratch).
-static int gather_device(mdrp_handle *h, const mdrp_matches *mm, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot, int32_t *n_dev,
-                         const void *scores = nullptr, int score_type = MDRP_F64) {
-    if (batch == 0) return MDRP_OK;
-    if (scores) {
-#define MDRP_GATHER(KT, DT)                                                                                                                       \
-    hipLaunchKernelGGL((k_gather_ranked<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)mm->kp1, (const KT *)mm->kp2, mm->k1,  \
-                       mm->k2, mm->matches, mm->m_max, (const DT *)mm->depth1, (const DT *)mm->depth2, mm->h1, mm->w1, mm->h2, mm->w2,            \
-                       mm->center1, mm->center2, mm->filter, scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, d1, d2, slot, n_dev)
-        if (mm->kp_type == MDRP_F32 && mm->depth_type == MDRP_F32) MDRP_GATHER(float, float);
-        else if (mm->kp_type == MDRP_F32) MDRP_GATHER(float, double);
-        else if (mm->depth_type == MDRP_F32) MDRP_GATHER(double, float);
-        else MDRP_GATHER(double, double);
-#undef MDRP_GATHER
-        HIPCHK(hipGetLastError());
-        return MDRP_OK;
-    }
-#define MDRP_GATHER(KT, DT)                                                                                                                \
-    hipLaunchKernelGGL((k_gather<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)mm->kp1, (const KT *)mm->kp2, mm->k1, mm->k2,  \
-                       mm->matches, mm->m_max, (const DT *)mm->depth1, (const DT *)mm->depth2, mm->h1, mm->w1, mm->h2, mm->w2, mm->center1,      \
-                       mm->center2, mm->filter, x1, x2, d1, d2, slot, n_dev)
-    if (mm->kp_type == MDRP_F32 && mm->depth_type == MDRP_F32) MDRP_GATHER(float, float);
-    else if (mm->kp_type == MDRP_F32) MDRP_GATHER(float, double);
-    else if (mm->depth_type == MDRP_F32) MDRP_GATHER(double, float);
-    else MDRP_GATHER(double, double);
-#undef MDRP_GATHER
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-// the same for mdrp_image_pairs
-static int check_image_pairs(const mdrp_image_pairs *ip, int batch) {
-    const char *why = nullptr;
-    if (!ip || batch < 0) why = "invalid argument";
-    else if ((ip->kp_type != MDRP_F32 && ip->kp_type != MDRP_F64) || (ip->depth_type != MDRP_F32 && ip->depth_type != MDRP_F64)) why = "kp_type / depth_type must be MDRP_F32 or MDRP_F64";
-    else if (ip->filter != MDRP_FILTER_BOTH_INF && ip->filter != MDRP_FILTER_FINITE) why = "unknown filter";
-    else if (ip->k_max < 0 || ip->m_max < 0 || ip->h_max < 0 || ip->w_max < 0 || ip->n_images < 0) why = "negative size";
-    else if (batch > 0 && ip->m_max > 0 && (!ip->pairs || !ip->matches)) why = "NULL pairs or matches";
-    else if (ip->n_images > 0 && ip->k_max > 0 && !ip->kp) why = "NULL keypoints";
-    else if (ip->n_images > 0 && ip->h_max > 0 && ip->w_max > 0 && !ip->depth) why = "NULL depth maps";
-    if (why) { g_err = std::string("mdrp_image_pairs: ") + why; return MDRP_ERR_INVALID; }
-    return MDRP_OK;
-}
-
-// k_gather_images on the handle's stream (the descriptor has passed check_image_pairs); n_dev: [batch] on the device
-static int gather_images_device(mdrp_handle *h, const mdrp_image_pairs *ip, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
-                                int32_t *n_dev, const void *scores = nullptr, int score_type = MDRP_F64) {
-    if (batch == 0) return MDRP_OK;
-    if (ip->m_max == 0) { // no rows, and pairs may be NULL: the counts are all there is to write
-        HIPCHK(hipMemsetAsync(n_dev, 0, sizeof(int32_t) * batch, h->stream));
-        return MDRP_OK;
-    }
-    if (scores) { // k_gather_images_ranked, as gather_device
-#define MDRP_GATHER(KT, DT)                                                                                                                           \
-    hipLaunchKernelGGL((k_gather_images_ranked<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)ip->kp, ip->kp_count, ip->k_max,    \
-                       (const DT *)ip->depth, ip->size, ip->h_max, ip->w_max, ip->center, ip->n_images, ip->pairs, ip->matches, ip->m_max, ip->filter, \
-                       scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, d1, d2, slot, n_dev)
-        if (ip->kp_type == MDRP_F32 && ip->depth_type == MDRP_F32) MDRP_GATHER(float, float);
-        else if (ip->kp_type == MDRP_F32) MDRP_GATHER(float, double);
-        else if (ip->depth_type == MDRP_F32) MDRP_GATHER(double, float);
-        else MDRP_GATHER(double, double);
-#undef MDRP_GATHER
-        HIPCHK(hipGetLastError());
-        return MDRP_OK;
-    }
-#define MDRP_GATHER(KT, DT)                                                                                                                \
-    hipLaunchKernelGGL((k_gather_images<KT, DT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)ip->kp, ip->kp_count, ip->k_max,  \
-                       (const DT *)ip->depth, ip->size, ip->h_max, ip->w_max, ip->center, ip->n_images, ip->pairs, ip->matches, ip->m_max,  \
-                       ip->filter, x1, x2, d1, d2, slot, n_dev)
-    if (ip->kp_type == MDRP_F32 && ip->depth_type == MDRP_F32) MDRP_GATHER(float, float);
-    else if (ip->kp_type == MDRP_F32) MDRP_GATHER(float, double);
-    else if (ip->depth_type == MDRP_F32) MDRP_GATHER(double, float);
-    else MDRP_GATHER(double, double);
-#undef MDRP_GATHER
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-// the counts of the last gather into the handle's pinned block: the one stream synchronisation of the front end
-static int fetch_counts(mdrp_handle *h, int batch) {
-    if (batch == 0) return MDRP_OK;
-    if ((size_t)batch > h->fe_n_host_cap) {
-        h->fe_n_host.reset();
-        h->fe_n_host_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&h->fe_n_host.v, sizeof(int32_t) * ((size_t)batch + batch / 8 + 64), hipHostMallocDefault));
-        h->fe_n_host_cap = (size_t)batch + batch / 8 + 64;
-    }
-    HIPCHK(hipMemcpyAsync(h->fe_n_host, h->fe_n.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MDRP_OK;
-}
-
-static int check_front_end_kind(int kind, const char *who) {
-    if (kind == MDRP_CALIB || kind == MDRP_SHARED_FOCAL || kind == MDRP_VARYING_FOCAL) return MDRP_OK;
-    g_err = std::string(who) + ": only the monodepth estimators (kind 0..2) take depth maps";
-    return MDRP_ERR_INVALID;
-}
-
-// the handle's gather buffers for batch pairs of m_max rows
-// (depths false: the front end of the baselines, which has no d1 / d2 and leaves fe_d1 / fe_d2 as they are)
-static int ensure_gather_buffers(mdrp_handle *h, int batch, int m_max, bool depths = true) {
-    const size_t rows = (size_t)batch * m_max;
+    if (!h || batch < 0 || n_max < 0 || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) why = "invalid argument";
+    else if ((size_t)batch * n_max > 0 && (!scores || !order)) why = "rank_scores: scores or order is NULL";
+    else why = n_per_pair_out_of_range(n_per_pair, batch, n_max);
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    const size_t np = (size_t)batch * n_max;
+    if (np == 0) return MDRP_OK;
+    MDRP_ENTER(h);
+    hipStream_t s = h->stream;
+    const bool use_host = mem_space == MDRP_MEM_HOST;
     int rc;
-    if ((rc = h->fe_x1.ensure(sizeof(double) * 2 * rows + 16)) || (rc = h->fe_x2.ensure(sizeof(double) * 2 * rows + 16)) ||
-        (depths && ((rc = h->fe_d1.ensure(sizeof(double) * rows + 16)) || (rc = h->fe_d2.ensure(sizeof(double) * rows + 16)))) ||
-        (rc = h->fe_slot.ensure(sizeof(int32_t) * rows + 16)) || (rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))))
-        return rc;
-    return MDRP_OK;
-}
-
-// behind a gather into the handle's buffers: the counts (one stream synchronisation), the resident estimator on the gathered buffers with the
-// handle's own inlier mask (by slot), then that mask back onto the match rows
-// (prosac: the gathered buffers are in quality order and the progressive sampler draws from them, as in a ranked call)
-static int estimate_gathered(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                             const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host, const uint64_t *prosac = nullptr, bool depths = true) {
-    const size_t rows = (size_t)batch * m_max;
-    int rc;
-    if ((rc = fetch_counts(h, batch))) return rc;
-    rc = estimate_device(h, kind, h->fe_x1.as<double>(), h->fe_x2.as<double>(), depths ? h->fe_d1.as<double>() : nullptr, depths ? h->fe_d2.as<double>() : nullptr, batch, m_max,
-                         batch > 0 ? h->fe_n_host.v : nullptr, cam1, cam2, ropt, bopt, nullptr, nullptr, nullptr, 0, nullptr, prosac);
-    if (rc) return rc;
-    if (match_mask_dev && rows > 0) {
-        hipLaunchKernelGGL(k_match_mask, dim3((unsigned)((rows + FE_THREADS - 1) / FE_THREADS)), dim3(FE_THREADS), 0, h->stream, h->fe_slot.as<int32_t>(),
-                           h->mask.as<uint8_t>(), m_max, rows, match_mask_dev);
-        HIPCHK(hipGetLastError());
+    int32_t *order_dev = order;
+    if (use_host) {
+        if ((rc = h->pr_scores.ensure(sizeof(double) * np)) || (rc = h->pr_order.ensure(sizeof(int32_t) * np))) return rc;
+        HIPCHK(hipMemcpyAsync(h->pr_scores.p, scores, sizeof(double) * np, hipMemcpyHostToDevice, s));
+        scores = h->pr_scores.as<double>(); order_dev = h->pr_order.as<int32_t>();
     }
-    if (n_used_host && batch > 0) std::memcpy(n_used_host, h->fe_n_host, sizeof(int32_t) * batch);
+    if ((rc = rank_device(h, scores, batch, n_max, n_per_pair, order_dev))) return rc;
+    if (use_host) HIPCHK(hipMemcpyAsync(order, order_dev, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return MDRP_OK;
 }
 
-extern "C" {
-
+// ---- the device front ends: sixteen entry points over four descriptors, each {gather | estimate} x {plain | ranked}
 int mdrp_gather_matches(mdrp_handle *h, const mdrp_matches *mm, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
                         int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_matches(mm, batch)) return rc;
-    if (batch > 0 && (!n_host || (mm->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_matches: NULL output"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1)))) return rc;
-    if ((rc = gather_device(h, mm, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>()))) return rc;
-    if ((rc = fetch_counts(h, batch))) return rc;
-    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
-    return MDRP_OK;
+    return gather_alone(h, FE_MATCHES, mm, nullptr, MDRP_F64, batch, x1, x2, d1, d2, slot, n_host, "mdrp_gather_matches");
+}
+int mdrp_gather_matches_ranked(mdrp_handle *h, const mdrp_matches *mm, const void *scores_dev, int score_type, int batch, double *x1, double *x2, double *d1,
+                               double *d2, int32_t *slot, int32_t *n_host) {
+    return gather_alone(h, FE_MATCHES, mm, scores_dev, score_type, batch, x1, x2, d1, d2, slot, n_host, "mdrp_gather_matches_ranked");
+}
+int mdrp_gather_image_pairs(mdrp_handle *h, const mdrp_image_pairs *ip, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
+                            int32_t *n_host) {
+    return gather_alone(h, FE_IMAGE_PAIRS, ip, nullptr, MDRP_F64, batch, x1, x2, d1, d2, slot, n_host, "mdrp_gather_image_pairs");
+}
+int mdrp_gather_image_pairs_ranked(mdrp_handle *h, const mdrp_image_pairs *ip, const void *scores_dev, int score_type, int batch, double *x1, double *x2,
+                                   double *d1, double *d2, int32_t *slot, int32_t *n_host) {
+    return gather_alone(h, FE_IMAGE_PAIRS, ip, scores_dev, score_type, batch, x1, x2, d1, d2, slot, n_host, "mdrp_gather_image_pairs_ranked");
+}
+int mdrp_gather_point_matches(mdrp_handle *h, const mdrp_point_matches *pm, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_host) {
+    return gather_alone(h, FE_POINT_MATCHES, pm, nullptr, MDRP_F64, batch, x1, x2, nullptr, nullptr, slot, n_host, "mdrp_gather_point_matches");
+}
+int mdrp_gather_point_matches_ranked(mdrp_handle *h, const mdrp_point_matches *pm, const void *scores_dev, int score_type, int batch, double *x1, double *x2,
+                                     int32_t *slot, int32_t *n_host) {
+    return gather_alone(h, FE_POINT_MATCHES, pm, scores_dev, score_type, batch, x1, x2, nullptr, nullptr, slot, n_host, "mdrp_gather_point_matches_ranked");
+}
+int mdrp_gather_point_image_pairs(mdrp_handle *h, const mdrp_point_image_pairs *pp, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_host) {
+    return gather_alone(h, FE_POINT_IMAGE_PAIRS, pp, nullptr, MDRP_F64, batch, x1, x2, nullptr, nullptr, slot, n_host, "mdrp_gather_point_image_pairs");
+}
+int mdrp_gather_point_image_pairs_ranked(mdrp_handle *h, const mdrp_point_image_pairs *pp, const void *scores_dev, int score_type, int batch, double *x1,
+                                         double *x2, int32_t *slot, int32_t *n_host) {
+    return gather_alone(h, FE_POINT_IMAGE_PAIRS, pp, scores_dev, score_type, batch, x1, x2, nullptr, nullptr, slot, n_host, "mdrp_gather_point_image_pairs_ranked");
 }
 
 int mdrp_estimate_matches_async(mdrp_handle *h, int kind, const mdrp_matches *mm, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
                                 const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_front_end_kind(kind, "mdrp_estimate_matches_async")) return rc;
-    if (int rc = check_matches(mm, batch)) return rc;
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = ensure_gather_buffers(h, batch, mm->m_max))) return rc;
-    if ((rc = gather_device(h, mm, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
-                            h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>())))
-        return rc;
-    return estimate_gathered(h, kind, batch, mm->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
+    return estimate_front(h, FE_MATCHES, kind, mm, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, "mdrp_estimate_matches_async");
 }
-
-int mdrp_gather_image_pairs(mdrp_handle *h, const mdrp_image_pairs *ip, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *slot,
-                            int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_image_pairs(ip, batch)) return rc;
-    if (batch > 0 && (!n_host || (ip->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_image_pairs: NULL output"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1)))) return rc;
-    if ((rc = gather_images_device(h, ip, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>()))) return rc;
-    if ((rc = fetch_counts(h, batch))) return rc;
-    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
-    return MDRP_OK;
-}
-
-int mdrp_estimate_image_pairs_async(mdrp_handle *h, int kind, const mdrp_image_pairs *ip, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                                    const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_front_end_kind(kind, "mdrp_estimate_image_pairs_async")) return rc;
-    if (int rc = check_image_pairs(ip, batch)) return rc;
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = ensure_gather_buffers(h, batch, ip->m_max))) return rc;
-    if ((rc = gather_images_device(h, ip, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
-                                   h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>())))
-        return rc;
-    return estimate_gathered(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
-}
-
-} // extern "C"
-
-// ---- the front end with match scores (include/mdrp.h; k_gather_ranked, mdrp_frontend.h)
-static int check_score_type(const void *scores, int score_type) {
-    if (!scores || score_type == MDRP_F32 || score_type == MDRP_F64) return MDRP_OK;
-    g_err = "score_type must be MDRP_F32 or MDRP_F64";
-    return MDRP_ERR_INVALID;
-}
-
-// What the ranked front-end estimates refuse before any device work, behind the descriptor's own checks: the estimator's refusals on the options as
-// the estimator will see them (check_ranked_args' rule: progressive_sampling is what these entry points build, it is not handed on).  The depths are
-// buffers of the handle: `own` stands for them.
-static int check_ranked_front_end(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
-                                  const mdrp_bundle_opt *bo) {
-    static const double own = 0.0;
-    mdrp_ransac_opt plain = *ro;
-    plain.progressive_sampling = 0;
-    return estimate_refusals(h, kind, &own, &own, batch, m_max, cam1, cam2, &plain, bo);
-}
-
-// behind a gather into the handle's buffers in quality order: estimate_gathered with the progressive sampler
-static int estimate_gathered_ranked(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                                    const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
-    mdrp_ransac_opt plain = *ropt;
-    plain.progressive_sampling = 0;
-    const uint64_t max_prosac = ropt->max_prosac_iterations;
-    return estimate_gathered(h, kind, batch, m_max, cam1, cam2, &plain, bopt, match_mask_dev, n_used_host, &max_prosac);
-}
-
-extern "C" {
-
-int mdrp_gather_matches_ranked(mdrp_handle *h, const mdrp_matches *mm, const void *scores_dev, int score_type, int batch, double *x1, double *x2, double *d1,
-                               double *d2, int32_t *slot, int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_matches(mm, batch)) return rc;
-    if (int rc = check_score_type(scores_dev, score_type)) return rc;
-    if (batch > 0 && (!n_host || (mm->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_matches_ranked: NULL output"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))) || (scores_dev && (rc = ensure_key_scratch(h, batch, mm->m_max)))) return rc;
-    if ((rc = gather_device(h, mm, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>(), scores_dev, score_type))) return drain_and_return(h, rc);
-    if ((rc = fetch_counts(h, batch))) return drain_and_return(h, rc);
-    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
-    return MDRP_OK;
-}
-
 int mdrp_estimate_matches_ranked_async(mdrp_handle *h, int kind, const mdrp_matches *mm, const void *scores_dev, int score_type, int batch,
                                        const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
                                        uint8_t *match_mask_dev, int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_front_end_kind(kind, "mdrp_estimate_matches_ranked_async")) return rc;
-    if (int rc = check_matches(mm, batch)) return rc;
-    if (int rc = check_score_type(scores_dev, score_type)) return rc;
-    if (int rc = check_ranked_front_end(h, kind, batch, mm->m_max, cam1, cam2, ropt, bopt)) return rc;
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = ensure_gather_buffers(h, batch, mm->m_max)) || (scores_dev && (rc = ensure_key_scratch(h, batch, mm->m_max)))) return rc;
-    if ((rc = gather_device(h, mm, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
-                            h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>(), scores_dev, score_type)))
-        return drain_and_return(h, rc);
-    rc = estimate_gathered_ranked(h, kind, batch, mm->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
-    return rc ? drain_and_return(h, rc) : rc;
+    return estimate_front(h, FE_MATCHES, kind, mm, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host,
+                          "mdrp_estimate_matches_ranked_async");
 }
-
-int mdrp_gather_image_pairs_ranked(mdrp_handle *h, const mdrp_image_pairs *ip, const void *scores_dev, int score_type, int batch, double *x1, double *x2,
-                                   double *d1, double *d2, int32_t *slot, int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_image_pairs(ip, batch)) return rc;
-    if (int rc = check_score_type(scores_dev, score_type)) return rc;
-    if (batch > 0 && (!n_host || (ip->m_max > 0 && (!x1 || !x2 || !d1 || !d2 || !slot)))) { g_err = "mdrp_gather_image_pairs_ranked: NULL output"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))) || (scores_dev && (rc = ensure_key_scratch(h, batch, ip->m_max)))) return rc;
-    if ((rc = gather_images_device(h, ip, batch, x1, x2, d1, d2, slot, h->fe_n.as<int32_t>(), scores_dev, score_type))) return drain_and_return(h, rc);
-    if ((rc = fetch_counts(h, batch))) return drain_and_return(h, rc);
-    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
-    return MDRP_OK;
+int mdrp_estimate_image_pairs_async(mdrp_handle *h, int kind, const mdrp_image_pairs *ip, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                                    const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
+    return estimate_front(h, FE_IMAGE_PAIRS, kind, ip, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host,
+                          "mdrp_estimate_image_pairs_async");
 }
-
 int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_image_pairs *ip, const void *scores_dev, int score_type, int batch,
                                            const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
                                            uint8_t *match_mask_dev, int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_front_end_kind(kind, "mdrp_estimate_image_pairs_ranked_async")) return rc;
-    if (int rc = check_image_pairs(ip, batch)) return rc;
-    if (int rc = check_score_type(scores_dev, score_type)) return rc;
-    if (int rc = check_ranked_front_end(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt)) return rc;
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = ensure_gather_buffers(h, batch, ip->m_max)) || (scores_dev && (rc = ensure_key_scratch(h, batch, ip->m_max)))) return rc;
-    if ((rc = gather_images_device(h, ip, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(),
-                                   h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>(), scores_dev, score_type)))
-        return drain_and_return(h, rc);
-    rc = estimate_gathered_ranked(h, kind, batch, ip->m_max, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host);
-    return rc ? drain_and_return(h, rc) : rc;
+    return estimate_front(h, FE_IMAGE_PAIRS, kind, ip, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host,
+                          "mdrp_estimate_image_pairs_ranked_async");
 }
-
-} // extern "C"
-
-// ---- the device front end of the 5- / 6- / 7-point baselines (include/mdrp_classic_frontend.h; k_gather_points*, mdrp_frontend.h):
-// check_matches / check_image_pairs without the depth clauses, the gathers without d1 / d2, the estimator with d1 = d2 = NULL on the handle's buffers
-static int check_point_matches(const mdrp_point_matches *pm, int batch) {
-    const char *why = nullptr;
-    if (!pm || batch < 0) why = "invalid argument";
-    else if (pm->kp_type != MDRP_F32 && pm->kp_type != MDRP_F64) why = "kp_type must be MDRP_F32 or MDRP_F64";
-    else if (pm->k1 < 0 || pm->k2 < 0 || pm->m_max < 0) why = "negative size";
-    else if (batch > 0 && pm->m_max > 0 && (!pm->matches || (pm->k1 > 0 && !pm->kp1) || (pm->k2 > 0 && !pm->kp2))) why = "NULL keypoints or matches";
-    if (why) { g_err = std::string("mdrp_point_matches: ") + why; return MDRP_ERR_INVALID; }
-    return MDRP_OK;
-}
-
-static int check_point_image_pairs(const mdrp_point_image_pairs *pp, int batch) {
-    const char *why = nullptr;
-    if (!pp || batch < 0) why = "invalid argument";
-    else if (pp->kp_type != MDRP_F32 && pp->kp_type != MDRP_F64) why = "kp_type must be MDRP_F32 or MDRP_F64";
-    else if (pp->k_max < 0 || pp->m_max < 0 || pp->n_images < 0) why = "negative size";
-    else if (batch > 0 && pp->m_max > 0 && (!pp->pairs || !pp->matches)) why = "NULL pairs or matches";
-    else if (pp->n_images > 0 && pp->k_max > 0 && !pp->kp) why = "NULL keypoints";
-    if (why) { g_err = std::string("mdrp_point_image_pairs: ") + why; return MDRP_ERR_INVALID; }
-    return MDRP_OK;
-}
-
-static int check_classic_front_end_kind(int kind, const char *who) {
-    if (kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT) return MDRP_OK;
-    g_err = std::string(who) + ": only the baselines (MDRP_RELPOSE_5PT, MDRP_SHARED_6PT, MDRP_FUNDAMENTAL_7PT); the monodepth estimators need depth maps: mdrp_estimate_matches_async takes them";
-    return MDRP_ERR_INVALID;
-}
-
-// What the baselines' front-end estimates refuse before any device work, behind the descriptor's own checks: the estimator's refusals on the options
-// as the estimator will see them (ranked: progressive_sampling is what the entry point builds, it is not handed on).
-static int check_classic_front_end(mdrp_handle *h, int kind, int batch, int m_max, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
-                                   const mdrp_bundle_opt *bo, bool ranked) {
-    mdrp_ransac_opt seen = *ro;
-    if (ranked) seen.progressive_sampling = 0;
-    return estimate_refusals(h, kind, nullptr, nullptr, batch, m_max, cam1, cam2, &seen, bo);
-}
-
-// k_gather_points / k_gather_points_ranked on the handle's stream (the descriptor has passed check_point_matches); n_dev: [batch] on the device
-static int gather_points_device(mdrp_handle *h, const mdrp_point_matches *pm, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_dev,
-                                const void *scores = nullptr, int score_type = MDRP_F64) {
-    if (batch == 0) return MDRP_OK;
-    if (pm->m_max == 0) { // no rows: the counts are all there is to write
-        HIPCHK(hipMemsetAsync(n_dev, 0, sizeof(int32_t) * batch, h->stream));
-        return MDRP_OK;
-    }
-    if (scores) {
-#define MDRP_GATHER(KT)                                                                                                                                \
-    hipLaunchKernelGGL((k_gather_points_ranked<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pm->kp1, (const KT *)pm->kp2, pm->k1, pm->k2, \
-                       pm->matches, pm->m_max, pm->center1, pm->center2, scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, slot, n_dev)
-        if (pm->kp_type == MDRP_F32) MDRP_GATHER(float);
-        else MDRP_GATHER(double);
-#undef MDRP_GATHER
-    } else {
-#define MDRP_GATHER(KT)                                                                                                                         \
-    hipLaunchKernelGGL((k_gather_points<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pm->kp1, (const KT *)pm->kp2, pm->k1, pm->k2, \
-                       pm->matches, pm->m_max, pm->center1, pm->center2, x1, x2, slot, n_dev)
-        if (pm->kp_type == MDRP_F32) MDRP_GATHER(float);
-        else MDRP_GATHER(double);
-#undef MDRP_GATHER
-    }
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-// the same for mdrp_point_image_pairs
-static int gather_point_images_device(mdrp_handle *h, const mdrp_point_image_pairs *pp, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_dev,
-                                      const void *scores = nullptr, int score_type = MDRP_F64) {
-    if (batch == 0) return MDRP_OK;
-    if (pp->m_max == 0) { // no rows, and pairs may be NULL
-        HIPCHK(hipMemsetAsync(n_dev, 0, sizeof(int32_t) * batch, h->stream));
-        return MDRP_OK;
-    }
-    if (scores) {
-#define MDRP_GATHER(KT)                                                                                                                                  \
-    hipLaunchKernelGGL((k_gather_points_images_ranked<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pp->kp, pp->kp_count, pp->k_max,     \
-                       pp->center, pp->n_images, pp->pairs, pp->matches, pp->m_max, scores, score_type, h->fe_key.as<uint64_t>(), x1, x2, slot, n_dev)
-        if (pp->kp_type == MDRP_F32) MDRP_GATHER(float);
-        else MDRP_GATHER(double);
-#undef MDRP_GATHER
-    } else {
-#define MDRP_GATHER(KT)                                                                                                                           \
-    hipLaunchKernelGGL((k_gather_points_images<KT>), dim3(batch), dim3(FE_THREADS), 0, h->stream, (const KT *)pp->kp, pp->kp_count, pp->k_max,     \
-                       pp->center, pp->n_images, pp->pairs, pp->matches, pp->m_max, x1, x2, slot, n_dev)
-        if (pp->kp_type == MDRP_F32) MDRP_GATHER(float);
-        else MDRP_GATHER(double);
-#undef MDRP_GATHER
-    }
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-// the gathers alone into the caller's buffers, behind the descriptor's check: the counts cross to n_host behind one stream synchronisation
-template <typename Desc, typename Gather>
-static int gather_points_alone(mdrp_handle *h, const Desc *desc, const void *scores_dev, int score_type, int batch, double *x1, double *x2, int32_t *slot,
-                               int32_t *n_host, const char *who, Gather gather) {
-    if (int rc = check_score_type(scores_dev, score_type)) return rc;
-    if (batch > 0 && (!n_host || (desc->m_max > 0 && (!x1 || !x2 || !slot)))) { g_err = std::string(who) + ": NULL output"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1))) || (scores_dev && (rc = ensure_key_scratch(h, batch, desc->m_max)))) return rc;
-    if ((rc = gather(h, desc, batch, x1, x2, slot, h->fe_n.as<int32_t>(), scores_dev, score_type))) return drain_and_return(h, rc);
-    if ((rc = fetch_counts(h, batch))) return drain_and_return(h, rc);
-    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
-    return MDRP_OK;
-}
-
-// gather into the handle's buffers (no depth buffers), then estimate_gathered with d1 = d2 = NULL; ranked: with the progressive sampler
-template <typename Desc, typename Gather>
-static int estimate_points(mdrp_handle *h, int kind, const Desc *desc, const void *scores_dev, int score_type, bool ranked, int batch, const mdrp_camera *cam1,
-                           const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host,
-                           Gather gather) {
-    if (int rc = check_score_type(scores_dev, score_type)) return rc;
-    if (int rc = check_classic_front_end(h, kind, batch, desc->m_max, cam1, cam2, ropt, bopt, ranked)) return rc;
-    MDRP_ENTER(h);
-    int rc;
-    if ((rc = ensure_gather_buffers(h, batch, desc->m_max, false)) || (scores_dev && (rc = ensure_key_scratch(h, batch, desc->m_max)))) return rc;
-    if ((rc = gather(h, desc, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_slot.as<int32_t>(), h->fe_n.as<int32_t>(), scores_dev, score_type)))
-        return drain_and_return(h, rc);
-    mdrp_ransac_opt plain = *ropt;
-    const uint64_t max_prosac = ropt->max_prosac_iterations;
-    if (ranked) plain.progressive_sampling = 0;
-    rc = estimate_gathered(h, kind, batch, desc->m_max, cam1, cam2, &plain, bopt, match_mask_dev, n_used_host, ranked ? &max_prosac : nullptr, false);
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-extern "C" {
-
-int mdrp_gather_point_matches(mdrp_handle *h, const mdrp_point_matches *pm, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_point_matches(pm, batch)) return rc;
-    return gather_points_alone(h, pm, nullptr, MDRP_F64, batch, x1, x2, slot, n_host, "mdrp_gather_point_matches", gather_points_device);
-}
-
-int mdrp_gather_point_matches_ranked(mdrp_handle *h, const mdrp_point_matches *pm, const void *scores_dev, int score_type, int batch, double *x1, double *x2,
-                                     int32_t *slot, int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_point_matches(pm, batch)) return rc;
-    return gather_points_alone(h, pm, scores_dev, score_type, batch, x1, x2, slot, n_host, "mdrp_gather_point_matches_ranked", gather_points_device);
-}
-
-int mdrp_gather_point_image_pairs(mdrp_handle *h, const mdrp_point_image_pairs *pp, int batch, double *x1, double *x2, int32_t *slot, int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_point_image_pairs(pp, batch)) return rc;
-    return gather_points_alone(h, pp, nullptr, MDRP_F64, batch, x1, x2, slot, n_host, "mdrp_gather_point_image_pairs", gather_point_images_device);
-}
-
-int mdrp_gather_point_image_pairs_ranked(mdrp_handle *h, const mdrp_point_image_pairs *pp, const void *scores_dev, int score_type, int batch, double *x1,
-                                         double *x2, int32_t *slot, int32_t *n_host) {
-    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_point_image_pairs(pp, batch)) return rc;
-    return gather_points_alone(h, pp, scores_dev, score_type, batch, x1, x2, slot, n_host, "mdrp_gather_point_image_pairs_ranked", gather_point_images_device);
-}
-
 int mdrp_estimate_classic_matches_async(mdrp_handle *h, int kind, const mdrp_point_matches *pm, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
                                         const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_matches_async")) return rc;
-    if (int rc = check_point_matches(pm, batch)) return rc;
-    return estimate_points(h, kind, pm, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_points_device);
+    return estimate_front(h, FE_POINT_MATCHES, kind, pm, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host,
+                          "mdrp_estimate_classic_matches_async");
 }
-
 int mdrp_estimate_classic_matches_ranked_async(mdrp_handle *h, int kind, const mdrp_point_matches *pm, const void *scores_dev, int score_type, int batch,
                                                const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
                                                uint8_t *match_mask_dev, int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_matches_ranked_async")) return rc;
-    if (int rc = check_point_matches(pm, batch)) return rc;
-    return estimate_points(h, kind, pm, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_points_device);
+    return estimate_front(h, FE_POINT_MATCHES, kind, pm, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host,
+                          "mdrp_estimate_classic_matches_ranked_async");
 }
-
 int mdrp_estimate_classic_image_pairs_async(mdrp_handle *h, int kind, const mdrp_point_image_pairs *pp, int batch, const mdrp_camera *cam1,
                                             const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev,
                                             int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_image_pairs_async")) return rc;
-    if (int rc = check_point_image_pairs(pp, batch)) return rc;
-    return estimate_points(h, kind, pp, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_point_images_device);
+    return estimate_front(h, FE_POINT_IMAGE_PAIRS, kind, pp, nullptr, MDRP_F64, false, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host,
+                          "mdrp_estimate_classic_image_pairs_async");
 }
-
 int mdrp_estimate_classic_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_point_image_pairs *pp, const void *scores_dev, int score_type,
                                                    int batch, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
                                                    const mdrp_bundle_opt *bopt, uint8_t *match_mask_dev, int32_t *n_used_host) {
-    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (int rc = check_classic_front_end_kind(kind, "mdrp_estimate_classic_image_pairs_ranked_async")) return rc;
-    if (int rc = check_point_image_pairs(pp, batch)) return rc;
-    return estimate_points(h, kind, pp, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host, gather_point_images_device);
+    return estimate_front(h, FE_POINT_IMAGE_PAIRS, kind, pp, scores_dev, score_type, true, batch, cam1, cam2, ropt, bopt, match_mask_dev, n_used_host,
+                          "mdrp_estimate_classic_image_pairs_ranked_async");
 }
 
-} // extern "C"
-
-extern "C" {
-
+// ---- statistics of the last call, and the unit entry points
 int mdrp_last_sweep_stats(mdrp_handle *h, double *sweep_ms, int64_t *launches, int64_t *evaluations) {
     if (!h) return MDRP_ERR_INVALID;
     std::lock_guard<std::mutex> lock_(h->mu);
@@ -2897,190 +2403,6 @@ int mdrp_refine_models(mdrp_handle *h, int kind, mdrp_model *models, int count, 
     return MDRP_OK;
 }
 
-} // extern "C"
-
-// ---- estimate in match-score order (include/mdrp.h; mdrp_prosac.h)
-// what the ranked entry points refuse before any device work: check_prior_args' list without the prior, with the estimator's own refusals taken on
-// the options as the estimator will see them (progressive_sampling is what these entry points build: it is not handed on)
-static int check_ranked_args(mdrp_handle *h, int kind, const double *d1, const double *d2, int batch, int n_max, const int32_t *n_per_pair,
-                             const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo) {
-    const char *why = nullptr;
-    if (!h || !ro || !bo) why = "invalid argument";
-    else if (kind != MDRP_CALIB && kind != MDRP_SHARED_FOCAL && kind != MDRP_VARYING_FOCAL) why = "ranked: only the monodepth estimators (MDRP_CALIB, MDRP_SHARED_FOCAL, MDRP_VARYING_FOCAL); the 5- / 6- / 7-point baselines have no depths: mdrp_estimate_classic_ranked takes them";
-    else if (batch < 0 || n_max < 0) why = "ranked: a negative size";
-    for (int i = 0; !why && n_per_pair && i < batch; ++i)
-        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
-    if (why) { g_err = why; return MDRP_ERR_INVALID; }
-    mdrp_ransac_opt plain = *ro;
-    plain.progressive_sampling = 0;
-    return estimate_refusals(h, kind, d1, d2, batch, n_max, cam1, cam2, &plain, bo);
-}
-
-// n per pair on the device for the ranking kernels (pr_nper), and scores -> order (pr_order, or `order_dev`) on the handle's stream
-static int rank_device(mdrp_handle *h, const double *scores_dev, int batch, int n_max, const int32_t *n_per_pair, int32_t *order_dev) {
-    hipStream_t s = h->stream;
-    std::vector<int32_t> n_host(batch);
-    for (int i = 0; i < batch; ++i) n_host[i] = n_per_pair ? n_per_pair[i] : n_max;
-    if (int rc = h->pr_nper.ensure(sizeof(int32_t) * (size_t)batch)) return rc;
-    HIPCHK(hipMemcpyAsync(h->pr_nper.p, n_host.data(), sizeof(int32_t) * (size_t)batch, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_rank, dim3(batch), dim3(RANK_THREADS), 0, s, scores_dev, (const int32_t *)h->pr_nper.as<int32_t>(), n_max, order_dev);
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-// All pointers device memory; scores_dev null: the records are in quality order already.  Ranks, gathers into the handle's ordered copies (allocated
-// before estimate_device takes the pass budget from the free memory), runs the unchanged estimator with the progressive sampler on them, and
-// scatters the mask into the caller's order: mask_dev, or the handle's mask where that is null.
-static int ranked_device(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, const double *scores_dev, int batch,
-                         int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro,
-                         const mdrp_bundle_opt *bo, uint8_t *mask_dev) {
-    mdrp_ransac_opt plain = *ro;
-    plain.progressive_sampling = 0;
-    const uint64_t max_prosac = ro->max_prosac_iterations;
-    const size_t np = (size_t)batch * n_max;
-    if (!scores_dev || np == 0)
-        return estimate_device(h, kind, x1, x2, d1, d2, batch, n_max, n_per_pair, cam1, cam2, &plain, bo, mask_dev, nullptr, nullptr, 0, nullptr, &max_prosac);
-    hipStream_t s = h->stream;
-    int rc;
-    const bool depths = kind <= MDRP_VARYING_FOCAL; // (a baseline call: d1 / d2 are null, no ordered copies of them)
-    if ((rc = h->pr_x1.ensure(sizeof(double) * 2 * np)) || (rc = h->pr_x2.ensure(sizeof(double) * 2 * np)) || (depths && (rc = h->pr_d1.ensure(sizeof(double) * np))) ||
-        (depths && (rc = h->pr_d2.ensure(sizeof(double) * np))) || (rc = h->pr_order.ensure(sizeof(int32_t) * np)) || (rc = h->pr_mask.ensure(np)))
-        return rc;
-    double *d1o = depths ? h->pr_d1.as<double>() : nullptr, *d2o = depths ? h->pr_d2.as<double>() : nullptr;
-    uint8_t *mask = mask_dev;
-    if (!mask) {
-        if ((rc = h->mask.ensure(np))) return rc;
-        mask = h->mask.as<uint8_t>();
-    }
-    int32_t *order = h->pr_order.as<int32_t>();
-    if ((rc = rank_device(h, scores_dev, batch, n_max, n_per_pair, order))) return rc;
-    const dim3 rgrid((unsigned)batch, (unsigned)((n_max + 255) / 256));
-    const int32_t *nper = h->pr_nper.as<int32_t>();
-    hipLaunchKernelGGL(k_rank_gather, rgrid, dim3(256), 0, s, (const int32_t *)order, nper, n_max, x1, x2, d1, d2, h->pr_x1.as<double>(), h->pr_x2.as<double>(),
-                       d1o, d2o);
-    HIPCHK(hipGetLastError());
-    if ((rc = estimate_device(h, kind, h->pr_x1.as<double>(), h->pr_x2.as<double>(), d1o, d2o, batch, n_max, n_per_pair,
-                              cam1, cam2, &plain, bo, h->pr_mask.as<uint8_t>(), nullptr, nullptr, 0, nullptr, &max_prosac)))
-        return rc;
-    hipLaunchKernelGGL(k_rank_scatter, rgrid, dim3(256), 0, s, (const int32_t *)order, nper, n_max, (const uint8_t *)h->pr_mask.as<uint8_t>(), mask);
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-extern "C" {
-
-int mdrp_estimate_batch_ranked_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *d1, const double *d2, const double *scores_dev,
-                                     int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                                     const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
-    if (int rc = check_ranked_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
-    MDRP_ENTER(h);
-    const int rc = ranked_device(h, kind, x1, x2, d1, d2, scores_dev, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev);
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-// The blocking forms behind their argument checks.  Host buffers are copied in plainly, in one piece, on the handle's stream (as
-// mdrp_estimate_batch_prior does): no sliced front.  d1 / d2 null: a baseline call, no depths.
-static int ranked_blocking(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2, const double *scores,
-                           int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                           const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
-    MDRP_ENTER(h);
-    const size_t np = (size_t)batch * n_max;
-    const bool use_host = mem_space == MDRP_MEM_HOST;
-    hipStream_t s = h->stream;
-    int rc;
-    if (use_host && np > 0) {
-        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) ||
-            (d1 && ((rc = h->in_d1.ensure(sizeof(double) * np + 16)) || (rc = h->in_d2.ensure(sizeof(double) * np + 16)))) ||
-            (scores && (rc = h->pr_scores.ensure(sizeof(double) * np))))
-            return drain_and_return(h, rc);
-        HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
-        if (d1) {
-            HIPCHK(hipMemcpyAsync(h->in_d1.p, d1, sizeof(double) * np, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(h->in_d2.p, d2, sizeof(double) * np, hipMemcpyHostToDevice, s));
-            d1 = h->in_d1.as<double>(); d2 = h->in_d2.as<double>();
-        }
-        if (scores) { HIPCHK(hipMemcpyAsync(h->pr_scores.p, scores, sizeof(double) * np, hipMemcpyHostToDevice, s)); scores = h->pr_scores.as<double>(); }
-    }
-    rc = ranked_device(h, kind, x1, x2, d1, d2, scores, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask);
-    if (rc) return drain_and_return(h, rc);
-    if (use_host && inlier_mask && np > 0 && hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s) != hipSuccess) {
-        g_err = "copy of the inlier masks failed";
-        return drain_and_return(h, MDRP_ERR_HIP);
-    }
-    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-int mdrp_estimate_batch_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *d1, const double *d2,
-                               const double *scores, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                               const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
-    if (int rc = check_ranked_args(h, kind, d1, d2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
-    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (batch > 0 && n_max > 0 && (!x1 || !x2 || !d1 || !d2)) { g_err = "monodepth estimator needs correspondences and depths"; return MDRP_ERR_INVALID; }
-    return ranked_blocking(h, kind, mem_space, x1, x2, d1, d2, scores, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, out, inlier_mask);
-}
-
-// ---- the 5- / 6- / 7-point baselines in match-score order (include/mdrp.h): check_ranked_args' rule on kinds 3-5, no depths
-static int check_classic_ranked_args(mdrp_handle *h, int kind, int batch, int n_max, const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2,
-                                     const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo) {
-    const char *why = nullptr;
-    if (!h || !ro || !bo) why = "invalid argument";
-    else if (kind != MDRP_RELPOSE_5PT && kind != MDRP_SHARED_6PT && kind != MDRP_FUNDAMENTAL_7PT) why = "classic_ranked: only the baselines (MDRP_RELPOSE_5PT, MDRP_SHARED_6PT, MDRP_FUNDAMENTAL_7PT); mdrp_estimate_batch_ranked takes the monodepth estimators";
-    else if (batch < 0 || n_max < 0) why = "classic_ranked: a negative size";
-    for (int i = 0; !why && n_per_pair && i < batch; ++i)
-        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
-    if (why) { g_err = why; return MDRP_ERR_INVALID; }
-    mdrp_ransac_opt plain = *ro;
-    plain.progressive_sampling = 0;
-    return estimate_refusals(h, kind, nullptr, nullptr, batch, n_max, cam1, cam2, &plain, bo);
-}
-
-int mdrp_estimate_classic_ranked_async(mdrp_handle *h, int kind, const double *x1, const double *x2, const double *scores_dev, int batch, int n_max,
-                                       const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                                       const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev) {
-    if (int rc = check_classic_ranked_args(h, kind, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
-    MDRP_ENTER(h);
-    const int rc = ranked_device(h, kind, x1, x2, nullptr, nullptr, scores_dev, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev);
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-int mdrp_estimate_classic_ranked(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, const double *scores, int batch, int n_max,
-                                 const int32_t *n_per_pair, const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt,
-                                 const mdrp_bundle_opt *bopt, mdrp_result *out, uint8_t *inlier_mask) {
-    if (int rc = check_classic_ranked_args(h, kind, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt)) return rc;
-    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    if (batch > 0 && n_max > 0 && (!x1 || !x2)) { g_err = "classic_ranked: correspondences are NULL"; return MDRP_ERR_INVALID; }
-    return ranked_blocking(h, kind, mem_space, x1, x2, nullptr, nullptr, scores, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, out, inlier_mask);
-}
-
-// k_rank alone: order [batch][n_max] int32 in mem_space (-1 at and past n).  Synchronous.
-int mdrp_rank_scores(mdrp_handle *h, int mem_space, const double *scores, int batch, int n_max, const int32_t *n_per_pair, int32_t *order) {
-    const char *why = nullptr;
-    if (!h || batch < 0 || n_max < 0 || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) why = "invalid argument";
-    else if ((size_t)batch * n_max > 0 && (!scores || !order)) why = "rank_scores: scores or order is NULL";
-    for (int i = 0; !why && n_per_pair && i < batch; ++i)
-        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
-    if (why) { g_err = why; return MDRP_ERR_INVALID; }
-    const size_t np = (size_t)batch * n_max;
-    if (np == 0) return MDRP_OK;
-    MDRP_ENTER(h);
-    hipStream_t s = h->stream;
-    const bool use_host = mem_space == MDRP_MEM_HOST;
-    int rc;
-    int32_t *order_dev = order;
-    if (use_host) {
-        if ((rc = h->pr_scores.ensure(sizeof(double) * np)) || (rc = h->pr_order.ensure(sizeof(int32_t) * np))) return rc;
-        HIPCHK(hipMemcpyAsync(h->pr_scores.p, scores, sizeof(double) * np, hipMemcpyHostToDevice, s));
-        scores = h->pr_scores.as<double>(); order_dev = h->pr_order.as<int32_t>();
-    }
-    if ((rc = rank_device(h, scores, batch, n_max, n_per_pair, order_dev))) return drain_and_return(h, rc);
-    if (use_host) HIPCHK(hipMemcpyAsync(order, order_dev, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MDRP_OK;
-}
-
 // The progressive sampler alone, for one table of n records and samples of sample_size records (3, 5, 6 or 7): chunk by chunk through the launch
 // the scheduler uses (launch_samples_prosac), the (RNG state, sample index) carried on the device from chunk to chunk.
 // out: [sum of chunk_lens][sample_size] uint32 in host memory; n < sample_size writes nothing.
@@ -3108,7 +2430,7 @@ int mdrp_prosac_samples_k(mdrp_handle *h, uint64_t seed, int n, int sample_size,
     HIPCHK(hipMemcpyAsync(d_state, &seed, sizeof seed, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_n, &n32, sizeof n32, hipMemcpyHostToDevice, s));
     ProsacTab tab{nullptr, nullptr, nullptr};
-    if ((rc = prosac_tables(h, s, K, &n32, 1, max_prosac_iterations, (uint64_t)total, tab))) return drain_and_return(h, rc);
+    if ((rc = prosac_tables(h, s, K, &n32, 1, max_prosac_iterations, (uint64_t)total, tab))) return rc;
     const int threads = env_int("MDRP_SAMPLE_THREADS", K == 3 ? SAMP_THREADS : (K == 5 ? 512 : 256)); // (the scheduler's defaults: Pass::samp_threads)
     size_t done = 0;
     for (int c = 0; c < n_chunks; ++c) {
@@ -3123,165 +2445,6 @@ int mdrp_prosac_samples_k(mdrp_handle *h, uint64_t seed, int n, int sample_size,
 
 int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks, uint32_t *out) {
     return mdrp_prosac_samples_k(h, seed, n, 3, max_prosac_iterations, chunk_lens, n_chunks, out);
-}
-
-} // extern "C"
-
-// ---- the baselines from a caller's model (include/mdrp_classic_models.h; mdrp_classic_models.h)
-static const char *classic_models_kind(int kind) {
-    return (kind == MDRP_RELPOSE_5PT || kind == MDRP_SHARED_6PT || kind == MDRP_FUNDAMENTAL_7PT)
-               ? nullptr
-               : "classic models: only the baselines (MDRP_RELPOSE_5PT, MDRP_SHARED_6PT, MDRP_FUNDAMENTAL_7PT); mdrp_refine_batch and mdrp_estimate_batch_prior take the monodepth estimators";
-}
-
-// kc_prep as the estimators launch it (no MFMA fragments, no sample tables, score_initial = 0), then ONE launch of kc_from_model on the handle's stream
-// (refine_device's shape, through the same refine_stage).  Pointers are device memory, `models` included; initial_* may be null.
-static int refine_classic_device(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
-                                 const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, const Model *models,
-                                 int stages, uint8_t *mask_dev, double *init_score, int32_t *init_inl) {
-    hipStream_t s = h->stream;
-    RefineStage st;
-    if (int rc = refine_stage(h, kind, 0, batch, n_max, n_per_pair, cam1, cam2, ro, bo, mask_dev, st)) return rc;
-    if (!st.mask) return MDRP_OK;
-    const RunParams &rp = st.rp;
-    uint8_t *mask = st.mask;
-    hipLaunchKernelGGL(kc_prep, dim3(batch), dim3(256), 0, s, rp, x1, x2, st.nper, st.table_of, st.cam1, st.cam2, ro->max_epipolar_error, bo->loss_scale,
-                       h->pts.as<double>(), h->st.as<PairState>(), (uint4 *)nullptr);
-    HIPCHK(hipEventRecord(st.f0, s));
-    const int stride = lm_list_stride(n_max);
-    const size_t smem = (size_t)2 * stride * sizeof(uint16_t);
-#define MDRP_KC_FROM_MODEL_LAUNCH(CK)                                                                                                                   \
-    hipLaunchKernelGGL((kc_from_model<CK>), dim3(batch), dim3(CLASSIC_MODEL_THREADS), smem, s, rp, (const PairState *)h->st.as<PairState>(),            \
-                       (const double *)h->pts.as<double>(), models, stages, mask, h->results.as<ResultDev>(), init_score, init_inl, stride)
-    if (kind == MDRP_RELPOSE_5PT) MDRP_KC_FROM_MODEL_LAUNCH(CLASSIC_RELPOSE);
-    else if (kind == MDRP_SHARED_6PT) MDRP_KC_FROM_MODEL_LAUNCH(CLASSIC_SHARED);
-    else MDRP_KC_FROM_MODEL_LAUNCH(CLASSIC_FUND);
-#undef MDRP_KC_FROM_MODEL_LAUNCH
-    HIPCHK(hipEventRecord(st.f1, s));
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
-}
-
-// what the four entry points refuse before any device work (`who`: "refine_classic" / "classic_prior")
-static int check_classic_models_args(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
-                                     const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
-                                     const mdrp_model *models) {
-    const char *why = nullptr;
-    if (!h || !ro || !bo) why = "invalid argument";
-    else if ((why = classic_models_kind(kind))) {}
-    else if (batch < 0 || n_max < 0) why = "classic models: a negative size";
-    else if (batch > 0 && !models) why = "classic models: models / prior is NULL";
-    else if (batch > 0 && n_max > 0 && (!x1 || !x2)) why = "classic models: correspondences are NULL";
-    else if (kind == MDRP_RELPOSE_5PT && batch > 0 && (!cam1 || !cam2)) why = "calibrated estimator needs cameras";
-    else if (kind == MDRP_SHARED_6PT && batch > 0 && !cam1) why = "the 6-point estimator needs the principal point in cam1";
-    for (int i = 0; !why && n_per_pair && i < batch; ++i)
-        if (n_per_pair[i] < 0 || n_per_pair[i] > n_max) why = "n_per_pair out of range";
-    if (why) { g_err = why; return MDRP_ERR_INVALID; }
-    return MDRP_OK;
-}
-
-static int check_stages(int stages) {
-    if (stages < 0 || stages > (MDRP_STAGE_LO | MDRP_STAGE_INLIERS)) { g_err = "refine: stages must be a combination of MDRP_STAGE_LO and MDRP_STAGE_INLIERS"; return MDRP_ERR_INVALID; }
-    return MDRP_OK;
-}
-
-// host buffers of a blocking call: plain copies on the handle's stream into the handle's staging buffers (mdrp_refine_batch)
-static int stage_classic_host(mdrp_handle *h, const double *&x1, const double *&x2, const Model *&models, int batch, int n_max) {
-    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
-    hipStream_t s = h->stream;
-    int rc;
-    if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->fm_models.ensure(sizeof(Model) * b))) return rc;
-    if (np > 0) {
-        HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(hipMemcpyAsync(h->fm_models.p, models, sizeof(Model) * b, hipMemcpyHostToDevice, s));
-    x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
-    models = h->fm_models.as<Model>();
-    return MDRP_OK;
-}
-
-extern "C" {
-
-int mdrp_refine_classic_async(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
-                              const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
-                              const mdrp_model *models_dev, int stages, uint8_t *inlier_mask_dev, double *initial_score_dev, int32_t *initial_inliers_dev) {
-    if (int rc = check_classic_models_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev)) return rc;
-    if (int rc = check_stages(stages)) return rc;
-    MDRP_ENTER(h);
-    const int rc = refine_classic_device(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, reinterpret_cast<const Model *>(models_dev), stages,
-                                         inlier_mask_dev, initial_score_dev, initial_inliers_dev);
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-int mdrp_refine_classic(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
-                        const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, const mdrp_model *models,
-                        int stages, mdrp_result *out, uint8_t *inlier_mask, double *initial_score, int32_t *initial_inliers) {
-    if (int rc = check_classic_models_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models)) return rc;
-    if (int rc = check_stages(stages)) return rc;
-    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    const size_t np = (size_t)batch * n_max, b = (size_t)batch;
-    const bool use_host = mem_space == MDRP_MEM_HOST;
-    hipStream_t s = h->stream;
-    int rc;
-    const Model *models_dev = reinterpret_cast<const Model *>(models);
-    if (use_host && batch > 0 && (rc = stage_classic_host(h, x1, x2, models_dev, batch, n_max))) return drain_and_return(h, rc);
-    // the start-model scores are host outputs whatever mem_space says: a buffer of the handle, copied back
-    const size_t off_inl = sizeof(double) * b;
-    if ((initial_score || initial_inliers) && (rc = h->fm_init.ensure(off_inl + sizeof(int32_t) * b + 16))) return rc;
-    double *is_dev = initial_score ? h->fm_init.as<double>() : nullptr;
-    int32_t *ii_dev = initial_inliers ? reinterpret_cast<int32_t *>(h->fm_init.as<unsigned char>() + off_inl) : nullptr;
-    rc = refine_classic_device(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, models_dev, stages, use_host ? nullptr : inlier_mask, is_dev, ii_dev);
-    if (rc) return drain_and_return(h, rc);
-    hipError_t e = hipSuccess;
-    if (use_host && inlier_mask && np > 0) e = hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && is_dev && batch > 0) e = hipMemcpyAsync(initial_score, is_dev, sizeof(double) * b, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && ii_dev && batch > 0) e = hipMemcpyAsync(initial_inliers, ii_dev, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) { g_err = "copy of the masks or start-model scores failed"; return drain_and_return(h, MDRP_ERR_HIP); }
-    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-// the estimator's own refusals for the kind come behind the argument checks (estimate_refusals: real_focal_check, progressive_sampling)
-static int check_classic_prior_args(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
-                                    const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo,
-                                    const mdrp_model *prior, int prior_space) {
-    if (int rc = check_classic_models_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ro, bo, prior)) return rc;
-    if (prior_space != 0 && prior_space != 1) { g_err = "classic_prior: prior_space must be 0 (the caller's units) or 1 (the estimator's normalised coordinates)"; return MDRP_ERR_INVALID; }
-    return estimate_refusals(h, kind, nullptr, nullptr, batch, n_max, cam1, cam2, ro, bo);
-}
-
-int mdrp_estimate_classic_prior_async(mdrp_handle *h, int kind, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
-                                      const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
-                                      const mdrp_model *prior_dev, int prior_space, uint8_t *inlier_mask_dev) {
-    if (int rc = check_classic_prior_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior_dev, prior_space)) return rc;
-    MDRP_ENTER(h);
-    const int rc = estimate_device(h, kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, inlier_mask_dev, nullptr, nullptr, 0,
-                                   reinterpret_cast<const Model *>(prior_dev), nullptr, prior_space);
-    return rc ? drain_and_return(h, rc) : rc;
-}
-
-int mdrp_estimate_classic_prior(mdrp_handle *h, int kind, int mem_space, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
-                                const mdrp_camera *cam1, const mdrp_camera *cam2, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt,
-                                const mdrp_model *prior, int prior_space, mdrp_result *out, uint8_t *inlier_mask) {
-    if (int rc = check_classic_prior_args(h, kind, x1, x2, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, prior, prior_space)) return rc;
-    if (!out || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    const size_t np = (size_t)batch * n_max;
-    const bool use_host = mem_space == MDRP_MEM_HOST;
-    int rc;
-    const Model *prior_dev = reinterpret_cast<const Model *>(prior);
-    if (use_host && batch > 0 && (rc = stage_classic_host(h, x1, x2, prior_dev, batch, n_max))) return drain_and_return(h, rc);
-    rc = estimate_device(h, kind, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, cam1, cam2, ropt, bopt, use_host ? nullptr : inlier_mask, nullptr, nullptr, 0,
-                         prior_dev, nullptr, prior_space);
-    if (rc) return drain_and_return(h, rc);
-    if (use_host && inlier_mask && np > 0 && hipMemcpyAsync(inlier_mask, h->mask.p, np, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-        g_err = "copy of the inlier masks failed";
-        return drain_and_return(h, MDRP_ERR_HIP);
-    }
-    rc = fetch_results_locked(h, out, batch); // (waits for the handle's stream)
-    return rc ? drain_and_return(h, rc) : rc;
 }
 
 } // extern "C"
