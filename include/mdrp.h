@@ -683,4 +683,5 @@ int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_
 #include "mdrp_classic_ranked.h"
 #include "mdrp_classic_models.h"
 #include "mdrp_classic_frontend.h" /* the device front end of the 5- / 6- / 7-point baselines: matcher output without depth maps */
+#include "mdrp_classic_focals.h"   /* the varying-focal baseline: focals and pose from the 7-point estimator's fundamental matrix */
 #endif

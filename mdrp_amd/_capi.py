@@ -38,6 +38,10 @@ EXPORTS_CLASSIC_MODELS = ("mdrp_refine_classic", "mdrp_refine_classic_async", "m
 EXPORTS_CLASSIC_FRONTEND = ("mdrp_gather_point_matches", "mdrp_gather_point_matches_ranked", "mdrp_gather_point_image_pairs",
                             "mdrp_gather_point_image_pairs_ranked", "mdrp_estimate_classic_matches_async", "mdrp_estimate_classic_matches_ranked_async",
                             "mdrp_estimate_classic_image_pairs_async", "mdrp_estimate_classic_image_pairs_ranked_async")
+# the entry points of include/mdrp_classic_focals.h, the fourth extension header mdrp.h includes: focals and pose from the 7-point estimator's F
+EXPORTS_CLASSIC_FOCALS = ("mdrp_focals_from_fundamental", "mdrp_pose_from_fundamental", "mdrp_pose_from_fundamental_async",
+                          "mdrp_estimate_fundamental_focals_async")
+FOCAL_NO_MODEL, FOCAL_F1_NOT_REAL, FOCAL_F2_NOT_REAL, FOCAL_NO_VOTERS = 1, 2, 4, 8  # include/mdrp_classic_focals.h MDRP_FOCAL_*: mdrp_focal_pose.status
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
 STAGE_LO, STAGE_INLIERS = 1, 2  # include/mdrp.h MDRP_STAGE_*: the stages of mdrp_refine_batch
@@ -115,6 +119,8 @@ MODEL_DTYPE = np.dtype([("q", "f8", 4), ("t", "f8", 3), ("scale", "f8"), ("shift
 RESULT_DTYPE = np.dtype([("model", MODEL_DTYPE), ("refinements", "u8"), ("iterations", "u8"), ("num_inliers", "u8"),
                          ("inlier_ratio", "f8"), ("model_score", "f8")])
 CAMERA_DTYPE = np.dtype([("model_id", "i4"), ("pad_", "i4"), ("params", "f8", 4)])
+# mdrp_focal_pose (include/mdrp_classic_focals.h), 128 bytes
+FOCAL_POSE_DTYPE = np.dtype([("model", MODEL_DTYPE), ("votes", "i4", 4), ("voters", "i4"), ("winner", "i4"), ("status", "i4"), ("pad_", "i4")])
 assert MODEL_DTYPE.itemsize == C.sizeof(Model) and RESULT_DTYPE.itemsize == C.sizeof(Result) and CAMERA_DTYPE.itemsize == C.sizeof(Camera)
 
 # mdrp_replay_state / mdrp_replay_trigger / mdrp_replay (include/mdrp.h): the bookkeeping train of one super-chunk on caller-given slot tables
@@ -249,6 +255,11 @@ def load_library():
                                                                                 C.POINTER(BundleOpt), vp, ip]
                 getattr(lib, f"mdrp_estimate_classic_{stem}_ranked_async").argtypes = [vp, C.c_int, C.POINTER(desc), vp, C.c_int, C.c_int, vp, vp,
                                                                                        C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
+        if hasattr(lib, "mdrp_focals_from_fundamental"):  # (an older ABI-0.6 library through MDRP_LIB has no focals from F: Handle._focals_fn raises)
+            lib.mdrp_focals_from_fundamental.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int, dp]
+            lib.mdrp_pose_from_fundamental.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, C.c_int, vp, dp, dp, vp]
+            lib.mdrp_pose_from_fundamental_async.argtypes = [vp, dp, dp, C.c_int, C.c_int, ip, vp, C.c_int, vp, dp, dp, vp]
+            lib.mdrp_estimate_fundamental_focals_async.argtypes = [vp, dp, dp, C.c_int, C.c_int, ip, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, dp, dp, vp]
         if hasattr(lib, "mdrp_estimate_batch_prior"):  # (an older ABI-0.6 library through MDRP_LIB has no prior entry points: Handle._prior_fn raises)
             lib.mdrp_estimate_batch_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
@@ -1150,6 +1161,71 @@ class Handle:
                                                        _ptr(d2), len(x1), float(scale_reproj), float(weight_sampson), C.byref(bopt),
                                                        int(bool(estimate_shift)), _ptr(cost)))
         return models, cost
+
+    # ---- the varying-focal baseline's tail: focals and pose from F (include/mdrp_classic_focals.h)
+    def _focals_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: rebuild (mdrp_amd/build.py)")
+        return fn
+
+    def focals_from_fundamental(self, F, pp1=None, pp2=None):
+        """F (B, 3, 3) or (B, 9) row-major, pp1 / pp2 (B, 2) or None (the origin) -> (B, 2) focals, NaN where not real (mdrp_focals_from_fundamental)"""
+        F = np.ascontiguousarray(F, dtype=np.float64).reshape(-1, 9)
+        B = len(F)
+        pp1 = None if pp1 is None else np.ascontiguousarray(pp1, dtype=np.float64).reshape(B, 2)
+        pp2 = None if pp2 is None else np.ascontiguousarray(pp2, dtype=np.float64).reshape(B, 2)
+        out = np.zeros((B, 2))
+        _check(self._lib, self._focals_fn("mdrp_focals_from_fundamental")(self._h, MEM_HOST, _ptr(F), _ptr(pp1), _ptr(pp2), B, _ptr(out)))
+        return out
+
+    def focals_from_fundamental_device(self, F_ptr, pp1_ptr, pp2_ptr, batch, out_ptr):
+        _check(self._lib, self._focals_fn("mdrp_focals_from_fundamental")(self._h, MEM_DEVICE, C.c_void_p(F_ptr), C.c_void_p(pp1_ptr) if pp1_ptr else None,
+                                                                          C.c_void_p(pp2_ptr) if pp2_ptr else None, int(batch), C.c_void_p(out_ptr)))
+
+    def pose_from_fundamental(self, x1, x2, models, n_per_pair=None, mask=None, pp1=None, pp2=None):
+        """host buffers: x1, x2 (B, N, 2); models: (B,) MODEL_DTYPE or RESULT_DTYPE records holding F (the record size is the stride); mask (B, N)
+        uint8 or None; pp1 / pp2 (B, 2) or None -> (B,) FOCAL_POSE_DTYPE (mdrp_pose_from_fundamental)"""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+            raise ValueError("expected x1,x2 (B,N,2)")
+        B, N = x1.shape[:2]
+        models = np.ascontiguousarray(models).reshape(-1)
+        if models.dtype not in (MODEL_DTYPE, RESULT_DTYPE) or len(models) != B:
+            raise ValueError(f"models: {B} records of _capi.MODEL_DTYPE or _capi.RESULT_DTYPE")
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(B, N)
+        pp1 = None if pp1 is None else np.ascontiguousarray(pp1, dtype=np.float64).reshape(B, 2)
+        pp2 = None if pp2 is None else np.ascontiguousarray(pp2, dtype=np.float64).reshape(B, 2)
+        out = np.zeros(B, dtype=FOCAL_POSE_DTYPE)
+        _check(self._lib, self._focals_fn("mdrp_pose_from_fundamental")(self._h, MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(models),
+                                                                        models.dtype.itemsize, _ptr(mask), _ptr(pp1), _ptr(pp2), _ptr(out)))
+        return out
+
+    def pose_from_fundamental_device(self, x1_ptr, x2_ptr, batch, n_max, models_ptr, stride, out_ptr, n_per_pair=None, mask_ptr=None, pp1_ptr=None,
+                                     pp2_ptr=None, blocking_out=None):
+        """device pointers (ints).  blocking_out None: mdrp_pose_from_fundamental_async into out_ptr (device); a FOCAL_POSE_DTYPE array: the blocking
+        call with mem_space = device, the records into that host array (out_ptr is not read)"""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        if blocking_out is None:
+            _check(self._lib, self._focals_fn("mdrp_pose_from_fundamental_async")(self._h, opt(x1_ptr), opt(x2_ptr), int(batch), int(n_max), _ptr(npp),
+                                                                                  opt(models_ptr), int(stride), opt(mask_ptr), opt(pp1_ptr), opt(pp2_ptr),
+                                                                                  opt(out_ptr)))
+        else:
+            _check(self._lib, self._focals_fn("mdrp_pose_from_fundamental")(self._h, MEM_DEVICE, opt(x1_ptr), opt(x2_ptr), int(batch), int(n_max), _ptr(npp),
+                                                                            opt(models_ptr), int(stride), opt(mask_ptr), opt(pp1_ptr), opt(pp2_ptr),
+                                                                            _ptr(blocking_out)))
+
+    def estimate_fundamental_focals_device(self, x1_ptr, x2_ptr, batch, n_max, ropt, bopt, out_ptr, n_per_pair=None, mask_ptr=None, pp1_ptr=None,
+                                           pp2_ptr=None):
+        """the 7-point estimate with the tail queued behind it (mdrp_estimate_fundamental_focals_async); the F records through fetch_results"""
+        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check(self._lib, self._focals_fn("mdrp_estimate_fundamental_focals_async")(self._h, opt(x1_ptr), opt(x2_ptr), int(batch), int(n_max), _ptr(npp),
+                                                                                    C.byref(ropt), C.byref(bopt), opt(mask_ptr), opt(pp1_ptr), opt(pp2_ptr),
+                                                                                    opt(out_ptr)))
 
 
 _default_tls = threading.local()

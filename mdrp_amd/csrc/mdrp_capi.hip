@@ -10,6 +10,7 @@
 #include "mdrp_prior.h"
 #include "mdrp_prosac.h"
 #include "mdrp_classic_models.h"
+#include "mdrp_classic_focals.h"
 // MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior, kc_from_model, kc_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -43,6 +44,10 @@ using namespace mdrp;
 static_assert(sizeof(mdrp_model) == sizeof(Model), "model layout");
 static_assert(sizeof(mdrp_camera) == sizeof(CamDev), "camera layout");
 static_assert(sizeof(mdrp_result) == sizeof(ResultDev), "result layout");
+static_assert(sizeof(mdrp_focal_pose) == sizeof(FocalPose) && offsetof(mdrp_focal_pose, votes) == offsetof(FocalPose, votes) &&
+              offsetof(mdrp_focal_pose, status) == offsetof(FocalPose, status), "focal pose layout");
+static_assert(MDRP_FOCAL_NO_MODEL == FOCAL_NO_MODEL && MDRP_FOCAL_F1_NOT_REAL == FOCAL_F1_NOT_REAL && MDRP_FOCAL_F2_NOT_REAL == FOCAL_F2_NOT_REAL &&
+              MDRP_FOCAL_NO_VOTERS == FOCAL_NO_VOTERS, "status bits of the header and of the kernel");
 
 namespace {
 
@@ -199,6 +204,7 @@ struct mdrp_handle {
     DevBuf fe_x1, fe_x2, fe_d1, fe_d2, fe_slot, fe_n; // device front end (mdrp_estimate_matches_async): gathered correspondences | slot of every match row | kept rows per pair
     Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
     size_t fe_n_host_cap = 0;
+    DevBuf fp_nper, fp_in, fp_out;     // focals and pose from F (include/mdrp_classic_focals.h): n per pair | a host call's models, mask and principal points | its records
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
     Pinned<Progress> progress_host;
     // sweep timing
@@ -2445,6 +2451,151 @@ int mdrp_prosac_samples_k(mdrp_handle *h, uint64_t seed, int n, int sample_size,
 
 int mdrp_prosac_samples(mdrp_handle *h, uint64_t seed, int n, uint64_t max_prosac_iterations, const int32_t *chunk_lens, int n_chunks, uint32_t *out) {
     return mdrp_prosac_samples_k(h, seed, n, 3, max_prosac_iterations, chunk_lens, n_chunks, out);
+}
+
+} // extern "C"
+
+// ---- the varying-focal baseline's tail: focals and pose from F (include/mdrp_classic_focals.h; mdrp_classic_focals.h)
+namespace {
+
+struct FocalPoseCall {
+    const double *x1, *x2;
+    int batch, n_max;
+    const int32_t *n_per_pair; // host
+    const void *models;
+    int stride;
+    const uint8_t *mask;
+    const double *pp1, *pp2;
+};
+
+// what the pose entry points refuse before any device work
+const char *focal_pose_refusal(const FocalPoseCall &c, const void *out) {
+    if (c.batch < 0 || c.n_max < 0) return "focal pose: a negative size";
+    if (c.batch > 0 && (!c.models || !out)) return "focal pose: models or out is NULL";
+    if (c.batch > 0 && c.n_max > 0 && (!c.x1 || !c.x2)) return "focal pose: correspondences are NULL";
+    if (const char *why = n_per_pair_out_of_range(c.n_per_pair, c.batch, c.n_max)) return why;
+    if (c.stride < (int)sizeof(mdrp_model) || c.stride % 8 != 0)
+        return "focal pose: model_stride_bytes must be a multiple of 8 and at least sizeof(mdrp_model) = 96 (sizeof(mdrp_result) = 136 reads result records)";
+    return nullptr;
+}
+
+// the counts up, then ONE launch of kc_focal_pose on the handle's stream; every pointer but n_per_pair is device memory
+int focal_pose_device(mdrp_handle *h, const FocalPoseCall &c, FocalPose *out_dev) {
+    if (c.batch == 0) return MDRP_OK;
+    hipStream_t s = h->stream;
+    if (int rc = h->fp_nper.ensure(sizeof(int32_t) * (size_t)c.batch)) return rc;
+    std::vector<int32_t> nper(c.batch); // pageable: the copy has left it when hipMemcpyAsync returns
+    for (int i = 0; i < c.batch; ++i) nper[i] = c.n_per_pair ? c.n_per_pair[i] : c.n_max;
+    HIPCHK(hipMemcpyAsync(h->fp_nper.p, nper.data(), sizeof(int32_t) * (size_t)c.batch, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(kc_focal_pose, dim3(c.batch), dim3(FOCAL_POSE_THREADS), 0, s, c.x1, c.x2, c.n_max, (const int32_t *)h->fp_nper.as<int32_t>(),
+                       reinterpret_cast<const unsigned char *>(c.models), c.stride, c.mask, c.pp1, c.pp2, out_dev);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+} // namespace
+
+extern "C" {
+
+int mdrp_focals_from_fundamental(mdrp_handle *h, int mem_space, const double *F, const double *pp1, const double *pp2, int batch, double *f1f2) {
+    if (!h || batch < 0 || (batch > 0 && (!F || !f1f2)) || (mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE)) {
+        g_err = "focals: invalid argument";
+        return MDRP_ERR_INVALID;
+    }
+    MDRP_ENTER(h);
+    if (batch == 0) return MDRP_OK;
+    hipStream_t s = h->stream;
+    const size_t b = (size_t)batch;
+    const double *dF = F, *d1 = pp1, *d2 = pp2;
+    double *dout = f1f2;
+    if (mem_space == MDRP_MEM_HOST) {
+        const size_t off1 = pad16(sizeof(double) * 9 * b), off2 = off1 + pad16(sizeof(double) * 2 * b);
+        int rc;
+        if ((rc = h->fp_in.ensure(off2 + sizeof(double) * 2 * b)) || (rc = h->fp_out.ensure(sizeof(double) * 2 * b))) return rc;
+        unsigned char *in = h->fp_in.as<unsigned char>();
+        HIPCHK(hipMemcpyAsync(in, F, sizeof(double) * 9 * b, hipMemcpyHostToDevice, s));
+        if (pp1) HIPCHK(hipMemcpyAsync(in + off1, pp1, sizeof(double) * 2 * b, hipMemcpyHostToDevice, s));
+        if (pp2) HIPCHK(hipMemcpyAsync(in + off2, pp2, sizeof(double) * 2 * b, hipMemcpyHostToDevice, s));
+        dF = reinterpret_cast<const double *>(in);
+        d1 = pp1 ? reinterpret_cast<const double *>(in + off1) : nullptr;
+        d2 = pp2 ? reinterpret_cast<const double *>(in + off2) : nullptr;
+        dout = h->fp_out.as<double>();
+    }
+    hipLaunchKernelGGL(kc_focals, dim3((batch + 255) / 256), dim3(256), 0, s, dF, d1, d2, batch, dout);
+    HIPCHK(hipGetLastError());
+    if (mem_space == MDRP_MEM_HOST) HIPCHK(hipMemcpyAsync(f1f2, dout, sizeof(double) * 2 * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MDRP_OK;
+}
+
+int mdrp_pose_from_fundamental_async(mdrp_handle *h, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair, const void *models,
+                                     int model_stride_bytes, const uint8_t *inlier_mask, const double *pp1, const double *pp2, mdrp_focal_pose *out_dev) {
+    const FocalPoseCall c{x1, x2, batch, n_max, n_per_pair, models, model_stride_bytes, inlier_mask, pp1, pp2};
+    const char *why = h ? focal_pose_refusal(c, out_dev) : "focal pose: invalid argument";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    return focal_pose_device(h, c, reinterpret_cast<FocalPose *>(out_dev));
+}
+
+int mdrp_pose_from_fundamental(mdrp_handle *h, int mem_space, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                               const void *models, int model_stride_bytes, const uint8_t *inlier_mask, const double *pp1, const double *pp2,
+                               mdrp_focal_pose *out) {
+    FocalPoseCall c{x1, x2, batch, n_max, n_per_pair, models, model_stride_bytes, inlier_mask, pp1, pp2};
+    const char *why = h ? focal_pose_refusal(c, out) : "focal pose: invalid argument";
+    if (!why && mem_space != MDRP_MEM_HOST && mem_space != MDRP_MEM_DEVICE) why = "focal pose: invalid argument";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    if (batch == 0) return MDRP_OK;
+    hipStream_t s = h->stream;
+    const size_t b = (size_t)batch, np = b * (size_t)n_max;
+    int rc;
+    if ((rc = h->fp_out.ensure(sizeof(FocalPose) * b))) return rc;
+    if (mem_space == MDRP_MEM_HOST) { // the inputs in one piece each on the handle's stream, as stage_host_call copies them
+        const size_t sz_models = pad16(b * (size_t)model_stride_bytes), sz_mask = pad16(np), sz_pp = pad16(sizeof(double) * 2 * b);
+        const size_t off_mask = sz_models, off_pp1 = off_mask + sz_mask, off_pp2 = off_pp1 + sz_pp;
+        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * np + 16)) || (rc = h->fp_in.ensure(off_pp2 + sz_pp)))
+            return rc;
+        unsigned char *in = h->fp_in.as<unsigned char>();
+        if (np > 0) {
+            HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s));
+        }
+        HIPCHK(hipMemcpyAsync(in, models, b * (size_t)model_stride_bytes, hipMemcpyHostToDevice, s));
+        if (inlier_mask && np > 0) HIPCHK(hipMemcpyAsync(in + off_mask, inlier_mask, np, hipMemcpyHostToDevice, s));
+        if (pp1) HIPCHK(hipMemcpyAsync(in + off_pp1, pp1, sizeof(double) * 2 * b, hipMemcpyHostToDevice, s));
+        if (pp2) HIPCHK(hipMemcpyAsync(in + off_pp2, pp2, sizeof(double) * 2 * b, hipMemcpyHostToDevice, s));
+        c.x1 = h->in_x1.as<double>(); c.x2 = h->in_x2.as<double>();
+        c.models = in;
+        c.mask = inlier_mask ? in + off_mask : nullptr;
+        c.pp1 = pp1 ? reinterpret_cast<const double *>(in + off_pp1) : nullptr;
+        c.pp2 = pp2 ? reinterpret_cast<const double *>(in + off_pp2) : nullptr;
+    }
+    if ((rc = focal_pose_device(h, c, h->fp_out.as<FocalPose>()))) return rc;
+    HIPCHK(hipMemcpyAsync(out, h->fp_out.p, sizeof(FocalPose) * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MDRP_OK;
+}
+
+int mdrp_estimate_fundamental_focals_async(mdrp_handle *h, const double *x1, const double *x2, int batch, int n_max, const int32_t *n_per_pair,
+                                           const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *inlier_mask_dev, const double *pp1,
+                                           const double *pp2, mdrp_focal_pose *out_dev) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    EstimateCall c = call_of(MDRP_FUNDAMENTAL_7PT, x1, x2, nullptr, nullptr, batch, n_max, n_per_pair, nullptr, nullptr, ropt, bopt);
+    c.mask_dev = inlier_mask_dev;
+    MDRP_ENTER(h);
+    if (int rc = estimate_refusals(h, c)) return rc; // (the estimator's own, first: its option refusals keep their codes)
+    const char *why = nullptr;
+    if (batch > 0 && !out_dev) why = "focal pose: models or out is NULL";
+    else if (batch > 0 && n_max > 0 && (!x1 || !x2)) why = "focal pose: correspondences are NULL";
+    else why = n_per_pair_out_of_range(n_per_pair, batch, n_max);
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    if (int rc = estimate_device(h, c)) return rc;
+    if (batch == 0) return MDRP_OK;
+    // the tail behind the estimator on the handle's stream: its records and its mask where they lie
+    const FocalPoseCall fc{x1, x2, batch, n_max, n_per_pair, h->results.p, (int)sizeof(ResultDev), inlier_mask_dev ? inlier_mask_dev : h->mask.as<uint8_t>(), pp1, pp2};
+    return focal_pose_device(h, fc, reinterpret_cast<FocalPose *>(out_dev));
 }
 
 } // extern "C"

@@ -281,7 +281,8 @@ def result_record_focal(experiment, info, pair, R_gt, t_gt, f1_gt, f2_gt):
 
 def evaluate_focal(h5, experiments, shared=True, iters=None, threshold=1.0, reproj_threshold=16.0, first=None, batch=4096,
                    estimate_batch=None, device=0, iterations_list=None):
-    """eval_shared_f.py / eval_varying_f.py main loop for the monodepth focal estimators, batched.  Pairs with fewer than
+    """eval_shared_f.py / eval_varying_f.py main loop for the monodepth focal estimators and their comparison rows (`6p` shared, `7p` varying),
+    batched.  Pairs with fewer than
     6 (shared) / 7 (varying) correspondences are skipped as in the reference.  iterations_list: the graph mode, as in
     `evaluate_calibrated` (one run per batch, one record per pair and budget, budget innermost; `info['runtime']` is the call's time
     per pair divided by the number of budgets)."""
@@ -302,7 +303,10 @@ def evaluate_focal(h5, experiments, shared=True, iters=None, threshold=1.0, repr
         depth = int(experiment.split("+")[1]) if "+" in experiment else None
         ro, bo = focal_options(experiment, iters, threshold, reproj_threshold, varying=not shared)
         six_point = shared and "6p" in experiment  # eval_shared_f.py:159-162: the non-monodepth 6-point row
-        ro = {k: v for k, v in ro.items() if k in CORE_RANSAC_KEYS} if six_point else \
+        seven_point = not shared and "7p" in experiment  # eval_varying_f.py:134: the non-monodepth row, 7-point F then focals and pose from it
+        if seven_point and budgets is not None:
+            raise NotImplementedError("iterations_list: the 7p row has no budgets form (DESIGN.md 7h)")
+        ro = {k: v for k, v in ro.items() if k in CORE_RANSAC_KEYS} if six_point or seven_point else \
             poselib._map_fork_options(ro, _capi.SHARED_FOCAL if shared else _capi.VARYING_FOCAL)
         loaded = [p for p in (load_pair_focal(h5, a, b, depth, shared) for a, b in pairs) if len(p["kp1"]) >= min_n]
         for s in range(0, len(loaded), batch):
@@ -311,6 +315,10 @@ def evaluate_focal(h5, experiments, shared=True, iters=None, threshold=1.0, repr
             if six_point:
                 out, infos = poselib.estimate_shared_focal_relative_pose_batch([p["kp1"] for p in chunk], [p["kp2"] for p in chunk], None, ro, bo,
                                                                                device=device, **kw)
+            elif seven_point:
+                out, infos = poselib.estimate_varying_focal_relative_pose_batch([p["kp1"] for p in chunk], [p["kp2"] for p in chunk], None, None, ro, bo,
+                                                                                device=device)
+                infos = [dict(f, F=np.asarray(f["F"]).tolist()) for f in infos]  # (the records are written as JSON)
             else:
                 out, infos = estimate_batch([p["kp1"] for p in chunk], [p["kp2"] for p in chunk], [p["d"][:, 0] for p in chunk],
                                             [p["d"][:, 1] for p in chunk], ro, bo, **kw)

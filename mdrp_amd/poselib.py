@@ -811,6 +811,94 @@ def relpose_6pt_shared_focal(x1, x2):
                       Camera("SIMPLE_PINHOLE", [float(m["f2"]), 0.0, 0.0])) for m in out[0][:n[0]]]
 
 
+# ------------------------------------------------------------------------------------------------ the varying-focal baseline (`7p`)
+# The 7-point fundamental matrix, then focals and a pose from it (include/mdrp_classic_focals.h): what the reference's varying-focal
+# tables compare the monodepth estimator with (/root/reference/eval_varying_f.py:134).
+def _focal_pp(pp, B, what):
+    """None, one principal point or one per pair -> (B, 2) float64, or None for the origin"""
+    if pp is None:
+        return None
+    a = np.asarray(pp, dtype=np.float64)
+    if a.size == 2:
+        a = a.reshape(1, 2)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] not in (1, B) or not np.isfinite(a).all():
+        raise ValueError(f"{what}: a finite principal point (2,) or one per pair ({B}, 2)")
+    return np.broadcast_to(a, (B, 2)).copy()
+
+
+def _focal_matrices(F):
+    a = np.asarray(F)
+    if a.dtype.kind not in "fiu" or a.ndim != 3 or a.shape[1:] != (3, 3):
+        raise ValueError("F: fundamental matrices (B, 3, 3)")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def focals_from_fundamental_batch(F, pp1=None, pp2=None, device=0):
+    """B fundamental matrices (B, 3, 3) for pixel coordinates and the principal points of the two images (one for all pairs, (B, 2), or None: the
+    origin) -> (list[Camera], list[Camera]) as focals_from_fundamental returns them."""
+    F = _focal_matrices(F)
+    B = len(F)
+    a, b = _focal_pp(pp1, B, "pp1"), _focal_pp(pp2, B, "pp2")  # (checked before anything touches the device)
+    f = _capi.default_handle(device).focals_from_fundamental(F, a, b)
+    za = np.zeros((B, 2)) if a is None else a
+    zb = np.zeros((B, 2)) if b is None else b
+    return ([Camera("SIMPLE_PINHOLE", [float(f[i, 0]), float(za[i, 0]), float(za[i, 1])]) for i in range(B)],
+            [Camera("SIMPLE_PINHOLE", [float(f[i, 1]), float(zb[i, 0]), float(zb[i, 1])]) for i in range(B)])
+
+
+def focals_from_fundamental(F, pp1, pp2):
+    """(_core.pyi: focals_from_fundamental(F, pp1, pp2) -> tuple[Camera, Camera]): the focal lengths of two cameras with known principal points from
+    their fundamental matrix, closed form.  Two SIMPLE_PINHOLE cameras [f, ppx, ppy] with width = height = -1, as the wheel returns them; a focal
+    whose square comes out negative is NaN."""
+    a = np.asarray(F)
+    if a.shape != (3, 3):
+        raise ValueError("F: a 3 x 3 fundamental matrix")
+    for name, pp in (("pp1", pp1), ("pp2", pp2)):
+        if pp is None or np.asarray(pp).size != 2:
+            raise ValueError(f"{name}: a principal point (2,)")
+    c1, c2 = focals_from_fundamental_batch(a[None], np.asarray(pp1, dtype=np.float64).reshape(2), np.asarray(pp2, dtype=np.float64).reshape(2))
+    return c1[0], c2[0]
+
+
+def _focal_pose_pairs(rec, ppa, ppb):
+    out = []
+    for i, r in enumerate(rec):
+        m = r["model"]
+        out.append(ImagePair(CameraPose(m["q"].copy(), m["t"].copy()), Camera("SIMPLE_PINHOLE", [float(m["f1"]), float(ppa[i, 0]), float(ppa[i, 1])]),
+                             Camera("SIMPLE_PINHOLE", [float(m["f2"]), float(ppb[i, 0]), float(ppb[i, 1])])))
+    return out
+
+
+def estimate_varying_focal_relative_pose_batch(points2D_1, points2D_2, pp1=None, pp2=None, ransac_opt=None, bundle_opt=None, device=0, scores=None,
+                                               priors=None):
+    """B pairs through the varying-focal baseline: the 7-point estimator (estimate_fundamental_batch, with its scores / priors), then the focals of
+    the two cameras from its F and the pose the inliers vote for (include/mdrp_classic_focals.h).  pp1 / pp2: the principal point of each image in the
+    points' coordinates, one for all pairs or (B, 2); None is the origin (centred points).  Returns (list[ImagePair], list[info dict]): the 7-point
+    info plus "F" (3 x 3), "votes" (4 ints), "winner" and "status" (0: a pose chosen by the inliers; _capi.FOCAL_* bits otherwise — a focal that is
+    not real is NaN and the pose is the identity)."""
+    _no_scores_with(scores, None, priors)
+    _check_baseline_options(ransac_opt, scores)
+    x1, x2, ns = _stack2(points2D_1, points2D_2)
+    B = len(ns)
+    a, b = _focal_pp(pp1, B, "pp1"), _focal_pp(pp2, B, "pp2")  # (checked before anything touches the device)
+    res, mask = _baseline_host(_capi.FUNDAMENTAL_7PT, x1, x2, ns, scores, None, None, ransac_opt, bundle_opt, device, None, priors)
+    rec = _capi.default_handle(device).pose_from_fundamental(x1, x2, res, ns, mask, a, b)
+    infos = []
+    for i in range(B):
+        info = _info(res[i], mask[i], ns[i])
+        info.update(F=_capi.model_to_fundamental(res[i]["model"]), votes=[int(v) for v in rec[i]["votes"]], winner=int(rec[i]["winner"]),
+                    status=int(rec[i]["status"]))
+        infos.append(info)
+    return _focal_pose_pairs(rec, np.zeros((B, 2)) if a is None else a, np.zeros((B, 2)) if b is None else b), infos
+
+
+def estimate_varying_focal_relative_pose(points2D_1, points2D_2, pp1=None, pp2=None, ransac_opt={}, bundle_opt={}, scores=None, prior=None):
+    """estimate_varying_focal_relative_pose_batch for one pair.  Returns (ImagePair, info)."""
+    pairs, infos = estimate_varying_focal_relative_pose_batch([_as_points(points2D_1)], [_as_points(points2D_2)], pp1, pp2, ransac_opt, bundle_opt,
+                                                              scores=_one_scores(scores), priors=None if prior is None else [prior])
+    return pairs[0], infos[0]
+
+
 # names the reference scripts also reach for: present so that a swapped import fails with a clear message at the call
 estimate_relative_pose_w_relative_depth = _not_on_path("estimate_relative_pose_w_relative_depth", "fork-only variant, eval.py:140 (commented out upstream)")
 
@@ -1096,6 +1184,83 @@ def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, c
                                              mask.data_ptr())
         res = h.fetch_results(B)
     return res, mask
+
+
+def _focal_pp_tensor(pp, B, device, what):
+    """a principal point for pose_from_fundamental_batch_torch: None (the origin), a float64 (B, 2) tensor on `device`, or what _focal_pp takes (uploaded)"""
+    import torch
+    if pp is None:
+        return None
+    if isinstance(pp, torch.Tensor):
+        if not (pp.is_cuda and pp.device == device and pp.dtype == torch.float64 and tuple(pp.shape) == (B, 2)):
+            raise ValueError(f"{what}: a float64 ({B}, 2) tensor on the inputs' device")
+        return pp.contiguous()
+    return torch.from_numpy(_focal_pp(pp, B, what)).to(device)
+
+
+def pose_from_fundamental_batch_torch(points2D_1, points2D_2, models, n_per_pair=None, inlier_mask=None, pp1=None, pp2=None):
+    """Focals and pose from a fundamental matrix per pair, on tensors that already live on the GPU (include/mdrp_classic_focals.h:
+    mdrp_pose_from_fundamental_async) — the tail to put behind any 7-point call (estimate_baseline_batch_torch("fundamental_7pt", ...) with or without
+    scores or priors, refine_baseline_batch_torch).  points2D_*: (B, N, 2) float64; models: B records holding F row-major in their first nine doubles —
+    a uint8 (B, 96) / float64 (B, 12) tensor of model records, a uint8 (B, 136) / float64 (B, 17) tensor of result records, or a numpy array of
+    _capi.MODEL_DTYPE / _capi.RESULT_DTYPE (uploaded on the current stream); inlier_mask: (B, N) uint8 tensor or None (every record votes);
+    pp1 / pp2: see _focal_pp_tensor.  Queued on the device's current torch stream.  Returns B records of _capi.FOCAL_POSE_DTYPE (numpy)."""
+    import torch
+    B, N = _baseline_points_shape("pose_from_fundamental_batch_torch", points2D_1, points2D_2)
+    x1, x2 = points2D_1.contiguous(), points2D_2.contiguous()
+    for t in (x1, x2):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.device == x1.device):
+            raise ValueError("pose_from_fundamental_batch_torch needs float64 tensors on one GPU")
+    if isinstance(models, np.ndarray):
+        if models.dtype not in (_capi.MODEL_DTYPE, _capi.RESULT_DTYPE):
+            raise ValueError("models: a numpy array must have dtype _capi.MODEL_DTYPE or _capi.RESULT_DTYPE")
+        models = torch.from_numpy(np.ascontiguousarray(models).reshape(-1).view(np.uint8).copy())
+        upload = True
+    else:
+        upload = False
+    if not (isinstance(models, torch.Tensor) and models.dtype in (torch.uint8, torch.float64)) or (not upload and not (models.is_cuda and models.device == x1.device)):
+        raise ValueError("models must be a uint8 / float64 tensor on the inputs' device or a numpy array of _capi.MODEL_DTYPE / _capi.RESULT_DTYPE")
+    nbytes = models.numel() * models.element_size()
+    if B > 0 and (nbytes % B != 0 or nbytes // B not in (_capi.MODEL_DTYPE.itemsize, _capi.RESULT_DTYPE.itemsize)):
+        raise ValueError(f"models must hold {B} records of {_capi.MODEL_DTYPE.itemsize} or {_capi.RESULT_DTYPE.itemsize} bytes")
+    stride = nbytes // B if B > 0 else _capi.MODEL_DTYPE.itemsize
+    if inlier_mask is not None and not (isinstance(inlier_mask, torch.Tensor) and inlier_mask.is_cuda and inlier_mask.device == x1.device
+                                        and inlier_mask.dtype == torch.uint8 and tuple(inlier_mask.shape) == (B, N)):
+        raise ValueError(f"inlier_mask: a uint8 ({B}, {N}) tensor on the inputs' device")
+    if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
+        n_per_pair = n_per_pair.detach().cpu().numpy()
+    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(x1.device):
+        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        a, b = _focal_pp_tensor(pp1, B, x1.device, "pp1"), _focal_pp_tensor(pp2, B, x1.device, "pp2")
+        models = models.to(x1.device).contiguous()
+        mk = None if inlier_mask is None else inlier_mask.contiguous()
+        out = torch.zeros((B, _capi.FOCAL_POSE_DTYPE.itemsize), dtype=torch.uint8, device=x1.device)
+        h.pose_from_fundamental_device(x1.data_ptr(), x2.data_ptr(), B, N, models.data_ptr(), stride, out.data_ptr(), n_per_pair,
+                                       None if mk is None else mk.data_ptr(), None if a is None else a.data_ptr(), None if b is None else b.data_ptr())
+        rec = out.cpu().numpy().reshape(-1).view(_capi.FOCAL_POSE_DTYPE).copy()  # (waits for the stream the kernel was queued on)
+    return rec
+
+
+def estimate_varying_focal_baseline_batch_torch(points2D_1, points2D_2, pp1=None, pp2=None, ransac_opt=None, bundle_opt=None, n_per_pair=None):
+    """The varying-focal baseline on tensors that already live on the GPU, in ONE call of the library (mdrp_estimate_fundamental_focals_async): the
+    7-point estimate of estimate_baseline_batch_torch("fundamental_7pt", ...) with pose_from_fundamental_batch_torch queued behind it on its result
+    records and its mask, which never leave the device.  Returns (B records of _capi.FOCAL_POSE_DTYPE, the 7-point records, (B, N) uint8 mask tensor)."""
+    import torch
+    _check_baseline_options(ransac_opt, None)
+    k, x1, x2, B, N, dev, n_per_pair, _, _ = _baseline_torch_args("estimate_varying_focal_baseline_batch_torch", "fundamental_7pt", points2D_1, points2D_2,
+                                                                  None, None, None, n_per_pair)
+    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
+    with torch.cuda.device(x1.device):
+        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        a, b = _focal_pp_tensor(pp1, B, x1.device, "pp1"), _focal_pp_tensor(pp2, B, x1.device, "pp2")
+        mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
+        out = torch.zeros((B, _capi.FOCAL_POSE_DTYPE.itemsize), dtype=torch.uint8, device=x1.device)
+        h.estimate_fundamental_focals_device(x1.data_ptr(), x2.data_ptr(), B, N, ro, bo, out.data_ptr(), n_per_pair, mask.data_ptr(),
+                                             None if a is None else a.data_ptr(), None if b is None else b.data_ptr())
+        res = h.fetch_results(B)  # (waits for the stream: the tail's records are complete)
+        rec = out.cpu().numpy().reshape(-1).view(_capi.FOCAL_POSE_DTYPE).copy()
+    return rec, res, mask
 
 
 # ------------------------------------------------------------------------------------------------ device front end
