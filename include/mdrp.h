@@ -684,4 +684,5 @@ int mdrp_estimate_image_pairs_ranked_async(mdrp_handle *h, int kind, const mdrp_
 #include "mdrp_classic_models.h"
 #include "mdrp_classic_frontend.h" /* the device front end of the 5- / 6- / 7-point baselines: matcher output without depth maps */
 #include "mdrp_classic_focals.h"   /* the varying-focal baseline: focals and pose from the 7-point estimator's fundamental matrix */
+#include "mdrp_dense.h"            /* the front end for dense matchers: a warp sampled by certainty on the device */
 #endif

@@ -41,6 +41,10 @@ EXPORTS_CLASSIC_FRONTEND = ("mdrp_gather_point_matches", "mdrp_gather_point_matc
 # the entry points of include/mdrp_classic_focals.h, the fourth extension header mdrp.h includes: focals and pose from the 7-point estimator's F
 EXPORTS_CLASSIC_FOCALS = ("mdrp_focals_from_fundamental", "mdrp_pose_from_fundamental", "mdrp_pose_from_fundamental_async",
                           "mdrp_estimate_fundamental_focals_async")
+# the entry points of include/mdrp_dense.h, the fifth extension header mdrp.h includes: the front end for dense matchers (a warp sampled by certainty)
+EXPORTS_DENSE = ("mdrp_sample_dense", "mdrp_estimate_dense_async")
+DENSE_COORDS = {"normalized": 0, "pixel": 1}  # mdrp_dense_matches.coords (include/mdrp_dense.h MDRP_DENSE_*)
+DENSE_MAX_ROWS, DENSE_MAX_STAGE1, DENSE_MAX_N, DENSE_MAX_GRID = 1 << 22, 65536, 16384, 8  # include/mdrp_dense.h MDRP_DENSE_MAX_*
 FOCAL_NO_MODEL, FOCAL_F1_NOT_REAL, FOCAL_F2_NOT_REAL, FOCAL_NO_VOTERS = 1, 2, 4, 8  # include/mdrp_classic_focals.h MDRP_FOCAL_*: mdrp_focal_pose.status
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
@@ -108,6 +112,16 @@ class PointImagePairs(C.Structure):
     """mdrp_point_image_pairs (include/mdrp_classic_frontend.h): per-image keypoint tables, pairs as image indices, every pointer in device memory"""
     _fields_ = [("kp", C.c_void_p), ("kp_type", C.c_int32), ("k_max", C.c_int32), ("kp_count", C.c_void_p), ("center", C.c_void_p),
                 ("n_images", C.c_int32), ("pairs", C.c_void_p), ("matches", C.c_void_p), ("m_max", C.c_int32)]
+
+
+class DenseMatches(C.Structure):
+    """mdrp_dense_matches (include/mdrp_dense.h): a dense matcher's warp and certainty, two depth maps and the sampler's arguments; every pointer in
+    device memory"""
+    _fields_ = [("warp", C.c_void_p), ("warp_type", C.c_int32), ("rows", C.c_int32), ("certainty", C.c_void_p), ("certainty_type", C.c_int32),
+                ("coords", C.c_int32), ("depth1", C.c_void_p), ("depth2", C.c_void_p), ("depth_type", C.c_int32), ("h1", C.c_int32), ("w1", C.c_int32),
+                ("h2", C.c_int32), ("w2", C.c_int32), ("filter", C.c_int32), ("center1", C.c_void_p), ("center2", C.c_void_p), ("n", C.c_int32),
+                ("balanced", C.c_int32), ("expansion", C.c_int32), ("grid", C.c_int32), ("min_count", C.c_int32), ("ranked", C.c_int32),
+                ("seed", C.c_uint64), ("threshold", C.c_double), ("rows_out", C.c_void_p), ("score_out", C.c_void_p)]
 
 
 class Result(C.Structure):
@@ -260,6 +274,9 @@ def load_library():
             lib.mdrp_pose_from_fundamental.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, C.c_int, vp, dp, dp, vp]
             lib.mdrp_pose_from_fundamental_async.argtypes = [vp, dp, dp, C.c_int, C.c_int, ip, vp, C.c_int, vp, dp, dp, vp]
             lib.mdrp_estimate_fundamental_focals_async.argtypes = [vp, dp, dp, C.c_int, C.c_int, ip, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, dp, dp, vp]
+        if hasattr(lib, "mdrp_sample_dense"):
+            lib.mdrp_sample_dense.argtypes = [vp, C.POINTER(DenseMatches), C.c_int, dp, dp, dp, dp, ip, dp, ip]
+            lib.mdrp_estimate_dense_async.argtypes = [vp, C.c_int, C.POINTER(DenseMatches), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
         if hasattr(lib, "mdrp_estimate_batch_prior"):  # (an older ABI-0.6 library through MDRP_LIB has no prior entry points: Handle._prior_fn raises)
             lib.mdrp_estimate_batch_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
@@ -1226,6 +1243,32 @@ class Handle:
         _check(self._lib, self._focals_fn("mdrp_estimate_fundamental_focals_async")(self._h, opt(x1_ptr), opt(x2_ptr), int(batch), int(n_max), _ptr(npp),
                                                                                     C.byref(ropt), C.byref(bopt), opt(mask_ptr), opt(pp1_ptr), opt(pp2_ptr),
                                                                                     opt(out_ptr)))
+
+    # ---- the front end for dense matchers (include/mdrp_dense.h): a DenseMatches descriptor of device pointers.  Arguments go to the library as they
+    # are: the library checks them.
+    def _dense_fn(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the dense front end (rebuild: mdrp_amd/build.py)")
+        return fn
+
+    def sample_dense(self, desc, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, rows_ptr, score_ptr):
+        """the sampler alone into the caller's device buffers ([batch][n]); returns the records per pair (numpy int32).  Synchronises the stream once."""
+        n = np.zeros(int(batch), dtype=np.int32)
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _check(self._lib, self._dense_fn("mdrp_sample_dense")(self._h, C.byref(desc), int(batch), opt(x1_ptr), opt(x2_ptr), opt(d1_ptr), opt(d2_ptr),
+                                                              opt(rows_ptr), opt(score_ptr), _ptr(n)))
+        return n
+
+    def estimate_dense_device(self, kind, desc, batch, ropt, bopt, cam1=None, cam2=None, record_mask_ptr=None):
+        """sampler + estimator on the handle's stream; results stay on the device (fetch_results / copy_results_device); desc.rows_out / score_out
+        receive the records' rows and certainties.  Returns the records per pair (numpy int32)."""
+        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
+        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        n = np.zeros(int(batch), dtype=np.int32)
+        _check(self._lib, self._dense_fn("mdrp_estimate_dense_async")(self._h, int(kind), C.byref(desc), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt),
+                                                                      C.byref(bopt), C.c_void_p(record_mask_ptr) if record_mask_ptr else None, _ptr(n)))
+        return n
 
 
 _default_tls = threading.local()

@@ -11,6 +11,7 @@
 #include "mdrp_prosac.h"
 #include "mdrp_classic_models.h"
 #include "mdrp_classic_focals.h"
+#include "mdrp_dense.h"
 // MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior, kc_from_model, kc_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -205,6 +206,7 @@ struct mdrp_handle {
     Pinned<int32_t> fe_n_host;         // the counts, read by the host scheduler
     size_t fe_n_host_cap = 0;
     DevBuf fp_nper, fp_in, fp_out;     // focals and pose from F (include/mdrp_classic_focals.h): n per pair | a host call's models, mask and principal points | its records
+    DevBuf dn_scratch, dn_score;       // dense front end (include/mdrp_dense.h): the sampler's scratch, carved per call (DenseScratch) | mdrp_estimate_dense_async: the records' certainties
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
     Pinned<Progress> progress_host;
     // sweep timing
@@ -2596,6 +2598,129 @@ int mdrp_estimate_fundamental_focals_async(mdrp_handle *h, const double *x1, con
     // the tail behind the estimator on the handle's stream: its records and its mask where they lie
     const FocalPoseCall fc{x1, x2, batch, n_max, n_per_pair, h->results.p, (int)sizeof(ResultDev), inlier_mask_dev ? inlier_mask_dev : h->mask.as<uint8_t>(), pp1, pp2};
     return focal_pose_device(h, fc, reinterpret_cast<FocalPose *>(out_dev));
+}
+
+} // extern "C"
+
+// ---- the front end for dense matchers: a warp sampled by certainty (include/mdrp_dense.h; mdrp_dense.h)
+namespace {
+
+static_assert(MDRP_DENSE_NORMALIZED == DENSE_NORMALIZED && MDRP_DENSE_PIXEL == DENSE_PIXEL && MDRP_DENSE_MAX_ROWS == DENSE_MAX_ROWS &&
+              MDRP_DENSE_MAX_STAGE1 == DENSE_MAX_STAGE1 && MDRP_DENSE_MAX_N == DENSE_MAX_N && MDRP_DENSE_MAX_GRID == DENSE_MAX_GRID, "limits of the header and of the kernels");
+static_assert(sizeof(mdrp_dense_matches) == 144 && offsetof(mdrp_dense_matches, seed) == 112 && offsetof(mdrp_dense_matches, rows_out) == 128, "descriptor layout");
+
+// what both entry points refuse of the descriptor before any device work
+const char *dense_refusal(const mdrp_dense_matches *d, int batch) {
+    const auto is_type = [](int t) { return t == MDRP_F32 || t == MDRP_F64; };
+    if (!d || batch < 0) return "invalid argument";
+    if (!is_type(d->warp_type) || !is_type(d->certainty_type) || !is_type(d->depth_type)) return "warp_type / certainty_type / depth_type must be MDRP_F32 or MDRP_F64";
+    if (d->coords != MDRP_DENSE_NORMALIZED && d->coords != MDRP_DENSE_PIXEL) return "coords must be MDRP_DENSE_NORMALIZED or MDRP_DENSE_PIXEL";
+    if (d->filter != MDRP_FILTER_BOTH_INF && d->filter != MDRP_FILTER_FINITE) return "unknown filter";
+    if (d->rows < 0 || d->h1 < 0 || d->w1 < 0 || d->h2 < 0 || d->w2 < 0) return "negative size";
+    if (d->rows > MDRP_DENSE_MAX_ROWS) return "rows above MDRP_DENSE_MAX_ROWS (2^22)";
+    if (d->n < 1 || d->n > MDRP_DENSE_MAX_N) return "n must be 1 .. MDRP_DENSE_MAX_N (16384)";
+    if (d->expansion < 1) return "expansion must be at least 1";
+    if ((int64_t)d->expansion * d->n > MDRP_DENSE_MAX_STAGE1) return "expansion * n above MDRP_DENSE_MAX_STAGE1 (65536)";
+    if (d->grid < 1 || d->grid > MDRP_DENSE_MAX_GRID) return "grid must be 1 .. MDRP_DENSE_MAX_GRID (8)";
+    if (d->min_count < 1) return "min_count must be at least 1";
+    if (batch > 0 && d->rows > 0 && (!d->warp || !d->certainty)) return "NULL warp or certainty";
+    if (batch > 0 && ((d->h1 > 0 && d->w1 > 0 && !d->depth1) || (d->h2 > 0 && d->w2 > 0 && !d->depth2))) return "NULL depth map";
+    return nullptr;
+}
+int check_dense(const mdrp_dense_matches *d, int batch) {
+    if (const char *why = dense_refusal(d, batch)) { g_err = std::string("mdrp_dense_matches: ") + why; return MDRP_ERR_INVALID; }
+    return MDRP_OK;
+}
+
+// The kernels of the sampler on the handle's stream; the outputs are device memory, [batch][n]; n_dev: [batch].  The scratch is one buffer of
+// the handle, carved for this call's sizes.
+int dense_sample_device(mdrp_handle *h, const mdrp_dense_matches *d, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *rows, double *score,
+                        int32_t *n_dev) {
+    if (batch == 0) return MDRP_OK;
+    hipStream_t s = h->stream;
+    DenseArgs a{};
+    a.warp = d->warp; a.cert = d->certainty; a.depth1 = d->depth1; a.depth2 = d->depth2; a.center1 = d->center1; a.center2 = d->center2;
+    a.warp_type = d->warp_type; a.cert_type = d->certainty_type; a.depth_type = d->depth_type; a.coords = d->coords; a.filter = d->filter;
+    a.rows = d->rows; a.h1 = d->h1; a.w1 = d->w1; a.h2 = d->h2; a.w2 = d->w2;
+    a.n = d->n; a.m1_max = d->balanced ? d->expansion * d->n : d->n; a.grid = d->grid; a.min_count = d->min_count; a.balanced = d->balanced ? 1 : 0;
+    a.ranked = d->ranked ? 1 : 0;
+    a.seed = (uint32_t)d->seed; a.threshold = d->threshold;
+    a.nblk = std::max(1, (d->rows + DENSE_BLOCK_ROWS - 1) / DENSE_BLOCK_ROWS); // (a warp without rows: one empty block)
+    a.ntile = (a.m1_max + DENSE_THREADS - 1) / DENSE_THREADS;
+    const size_t b = (size_t)batch, slots = (size_t)a.ntile * DENSE_THREADS;
+    size_t total = 0;
+    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
+    const size_t o_qpre = carve(sizeof(uint32_t) * b * std::max(a.rows, 1)), o_bpre = carve(sizeof(uint64_t) * b * a.nblk), o_bcnt = carve(sizeof(uint32_t) * b * a.nblk),
+                 o_meta = carve(sizeof(DenseMeta) * b), o_cand = carve(sizeof(int32_t) * b * slots), o_tcnt = carve(sizeof(int32_t) * b * a.ntile),
+                 o_p1 = carve(sizeof(int32_t) * b * a.m1_max), o_cell = carve(sizeof(int32_t) * b * a.m1_max), o_wpre = carve(sizeof(uint64_t) * b * a.m1_max),
+                 o_sel = carve(sizeof(int32_t) * b * a.n), o_rank = carve(sizeof(int32_t) * b * a.n);
+    if (int rc = h->dn_scratch.ensure(total)) return rc;
+    unsigned char *p = h->dn_scratch.as<unsigned char>();
+    DenseScratch z;
+    z.qpre = reinterpret_cast<uint32_t *>(p + o_qpre); z.bpre = reinterpret_cast<uint64_t *>(p + o_bpre); z.bcnt = reinterpret_cast<uint32_t *>(p + o_bcnt);
+    z.meta = reinterpret_cast<DenseMeta *>(p + o_meta); z.cand = reinterpret_cast<int32_t *>(p + o_cand); z.tcnt = reinterpret_cast<int32_t *>(p + o_tcnt);
+    z.p1 = reinterpret_cast<int32_t *>(p + o_p1); z.cell = reinterpret_cast<int32_t *>(p + o_cell); z.wpre = reinterpret_cast<uint64_t *>(p + o_wpre);
+    z.sel = reinterpret_cast<int32_t *>(p + o_sel); z.rank = reinterpret_cast<int32_t *>(p + o_rank);
+    hipLaunchKernelGGL(k_dense_weights, dim3(batch, a.nblk), dim3(DENSE_THREADS), 0, s, a, z.qpre, z.bpre, z.bcnt);
+    hipLaunchKernelGGL(k_dense_scan, dim3(batch), dim3(DENSE_THREADS), 0, s, a, z.bpre, (const uint32_t *)z.bcnt, z.meta);
+    hipLaunchKernelGGL(k_dense_pick, dim3(batch, a.ntile), dim3(DENSE_THREADS), 0, s, a, (const uint32_t *)z.qpre, (const uint64_t *)z.bpre, (const DenseMeta *)z.meta,
+                       z.cand, z.tcnt);
+    hipLaunchKernelGGL(k_dense_balance, dim3(batch), dim3(DENSE_BAL_THREADS), 0, s, a, (const int32_t *)z.cand, (const int32_t *)z.tcnt, z.p1, z.cell, z.wpre, z.sel, n_dev);
+    if (a.ranked)
+        hipLaunchKernelGGL(k_dense_rank, dim3(batch, (a.n + DENSE_EMIT_RECORDS - 1) / DENSE_EMIT_RECORDS), dim3(DENSE_THREADS), 0, s, a.cert, a.cert_type, a.rows, a.n,
+                           (const int32_t *)z.sel, (const int32_t *)n_dev, z.rank);
+    hipLaunchKernelGGL(k_dense_emit, dim3(batch, (a.n + DENSE_THREADS - 1) / DENSE_THREADS), dim3(DENSE_THREADS), 0, s, a, (const int32_t *)z.sel, (const int32_t *)n_dev,
+                       (const int32_t *)(a.ranked ? z.rank : nullptr), x1, x2, d1, d2, rows, score);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int mdrp_sample_dense(mdrp_handle *h, const mdrp_dense_matches *desc, int batch, double *x1, double *x2, double *d1, double *d2, int32_t *rows, double *score,
+                      int32_t *n_host) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_dense(desc, batch)) return rc;
+    if (batch > 0 && (!x1 || !x2 || !d1 || !d2 || !rows || !score || !n_host)) { g_err = "mdrp_sample_dense: NULL output"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    int rc;
+    if ((rc = h->fe_n.ensure(sizeof(int32_t) * std::max(batch, 1)))) return rc;
+    if ((rc = dense_sample_device(h, desc, batch, x1, x2, d1, d2, rows, score, h->fe_n.as<int32_t>()))) return rc;
+    if ((rc = fetch_counts(h, batch))) return rc;
+    if (batch > 0) std::memcpy(n_host, h->fe_n_host, sizeof(int32_t) * batch);
+    return MDRP_OK;
+}
+
+int mdrp_estimate_dense_async(mdrp_handle *h, int kind, const mdrp_dense_matches *desc, int batch, const mdrp_camera *cam1, const mdrp_camera *cam2,
+                              const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, uint8_t *record_mask_dev, int32_t *n_used_host) {
+    if (!h || !ropt || !bopt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (int rc = check_front_end_kind(kind, true, "mdrp_estimate_dense_async")) return rc;
+    if (int rc = check_dense(desc, batch)) return rc;
+    static const double own = 0.0; // the records are buffers of the handle, not yet sized: `own` stands for them in the refusals (as in estimate_front)
+    const bool ranked = desc->ranked != 0;
+    const int n = desc->n;
+    EstimateCall c = call_of(kind, nullptr, nullptr, &own, &own, batch, n, nullptr, cam1, cam2, ropt, bopt);
+    if (int rc = refusals_as_run(h, c, ranked)) return rc;
+    MDRP_ENTER(h);
+    const size_t recs = (size_t)batch * n;
+    int rc;
+    if ((rc = ensure_gather_buffers(h, batch, n, true)) || (!desc->score_out && (rc = h->dn_score.ensure(sizeof(double) * recs + 16)))) return rc;
+    int32_t *rows = desc->rows_out ? desc->rows_out : h->fe_slot.as<int32_t>();
+    double *score = desc->score_out ? desc->score_out : h->dn_score.as<double>();
+    c.x1 = h->fe_x1.as<double>(); c.x2 = h->fe_x2.as<double>(); c.d1 = h->fe_d1.as<double>(); c.d2 = h->fe_d2.as<double>();
+    if ((rc = dense_sample_device(h, desc, batch, h->fe_x1.as<double>(), h->fe_x2.as<double>(), h->fe_d1.as<double>(), h->fe_d2.as<double>(), rows, score,
+                                  h->fe_n.as<int32_t>())))
+        return rc;
+    if ((rc = fetch_counts(h, batch))) return rc;
+    c.n_per_pair = batch > 0 ? h->fe_n_host.v : nullptr;
+    c.mask_dev = record_mask_dev; // per sampled record, in the records' order: nothing to map back
+    const RankedRun rr(*ropt);
+    if (ranked) rr.apply(c); // the records are in quality order: the progressive sampler on them as they are
+    if ((rc = estimate_device(h, c))) return rc;
+    if (n_used_host && batch > 0) std::memcpy(n_used_host, h->fe_n_host, sizeof(int32_t) * batch);
+    return MDRP_OK;
 }
 
 } // extern "C"

@@ -30,6 +30,11 @@ calls `gather_matches_numpy` on the two images' valid tables: that reduction is 
 baselines, which have no depths (include/mdrp_classic_frontend.h): `gather_point_matches_numpy` / `gather_point_image_pairs_numpy`
 state them.  Rule 1 is unchanged; rule 2 becomes "all four coordinates are finite" (no map to be inside of), rules 3 and 4 fall away, rules 5 and 6
 hold without d1 and d2.
+
+`poselib.sample_dense_torch` / `estimate_dense_torch` are the front end for DENSE matchers (include/mdrp_dense.h): a warp of rows
+(xA, yA, xB, yB) and its certainty instead of keypoints and index pairs.  `sample_dense_numpy` at the end of this module is their definition, rules
+D1-D7 of the header: pixel coordinates, rules 2-4 above as the candidate test, integer weights from the certainty, a stratified draw, a
+density-balanced second draw, the records.  Every quantity that decides a pick is an integer, so the device equals it as bytes.
 """
 import numpy as np
 
@@ -258,3 +263,159 @@ def gather_point_image_pairs_numpy(keypoints, pairs, matches, centers=None, kp_c
         gathered.append(gather_point_matches_numpy(kp[a][:counts[a]], kp[c][:counts[c]], matches[b], None if cs is None else cs[a],
                                                    None if cs is None else cs[c], None if scores is None else scores[b]))
     return pad_point_pairs(gathered, M)
+
+
+# ---- the front end for dense matchers (include/mdrp_dense.h): a warp sampled by certainty.  Rules D1-D7 of the header, for one pair.
+# Every quantity that decides a pick is an integer (weights, the 24-bit stratum offsets, running sums, cell counts): the device result equals this
+# statement as bytes whatever order a parallel scan or an atomic adds in.
+COORDS = ("normalized", "pixel")
+DENSE_MAX_ROWS, DENSE_MAX_STAGE1, DENSE_MAX_N, DENSE_MAX_GRID = 1 << 22, 65536, 16384, 8
+_M32 = 0xFFFFFFFF
+
+
+def dense_pixel_coord(v, extent, coords="normalized"):
+    """D1: float64 pixel coordinate of float32 / float64 warp values in an image `extent` wide (or high)"""
+    if coords not in COORDS:
+        raise ValueError(f"coords must be one of {COORDS}, not {coords!r}")
+    with np.errstate(invalid="ignore"):
+        v = np.asarray(v).astype(np.float64)
+        return (v + 1.0) * (0.5 * float(extent)) if coords == "normalized" else v
+
+
+def dense_weight(certainty, threshold=0.05):
+    """D2 (the certainty's part) and D3: uint32 weights; 0 where the certainty is not finite or not above zero, otherwise
+    min(65536, max(1, floor(c' * 65536))) with c' = 1 above the threshold"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = np.asarray(certainty).astype(np.float64)
+        ok = np.isfinite(c) & (c > 0.0)
+        cp = np.where(c > float(threshold), 1.0, c)
+        f = np.floor(np.where(ok, cp, 0.0) * 65536.0)
+    q = np.minimum(65536.0, np.maximum(1.0, f)).astype(np.uint32)
+    return np.where(ok, q, np.uint32(0)).astype(np.uint32)
+
+
+def lowbias32(x):
+    """the 32-bit integer hash of D4 on uint32 values (array or scalar): uint32 array"""
+    x = np.atleast_1d(np.asarray(x, dtype=np.uint64)) & _M32  # (uint64 holds every 32 x 32-bit product)
+    x ^= x >> np.uint64(16); x = (x * np.uint64(0x7feb352d)) & _M32
+    x ^= x >> np.uint64(15); x = (x * np.uint64(0x846ca68b)) & _M32
+    x ^= x >> np.uint64(16)
+    return x.astype(np.uint32)
+
+
+def dense_u(seed, stage, k):
+    """D4: the 24-bit stratum offset of draw k (array) for a seed and a stage; only the seed's low 32 bits count"""
+    k = np.atleast_1d(np.asarray(k, dtype=np.uint64))
+    x = ((int(seed) & _M32) * 0x9E3779B1 + int(stage) * 0x85EBCA77) & _M32
+    return lowbias32((np.uint64(x) + k) & _M32) >> np.uint32(8)
+
+
+def dense_position(k, S, M, u):
+    """D4: P_k = (k * S + ((u_k * S) >> 24)) div M in uint64 (S <= 2^38, k < M <= 2^16, u < 2^24: below 2^63)"""
+    k = np.atleast_1d(np.asarray(k, dtype=np.uint64))
+    u = np.atleast_1d(np.asarray(u, dtype=np.uint64))
+    S, M = np.uint64(S), np.uint64(M)
+    return (k * S + ((u * S) >> np.uint64(24))) // M
+
+
+def stratified_draw(weights, M, stage, seed):
+    """D4: indices picked by the stratified draw of M from integer weights (sum > 0 unless M == 0), ascending, duplicates of the predecessor dropped"""
+    w = np.asarray(weights, dtype=np.uint64)
+    if M <= 0 or len(w) == 0:
+        return np.zeros(0, dtype=np.int64)
+    cum = np.cumsum(w, dtype=np.uint64)
+    k = np.arange(M, dtype=np.uint64)
+    P = dense_position(k, cum[-1], M, dense_u(seed, stage, k))
+    pick = np.searchsorted(cum, P, side="right").astype(np.int64)  # the smallest i whose inclusive running sum exceeds P
+    keep = np.ones(M, dtype=bool)
+    keep[1:] = pick[1:] != pick[:-1]
+    return pick[keep]
+
+
+def dense_cell(xi1, yi1, xi2, yi2, w1, h1, w2, h2, grid):
+    """D6: the 4-D cell of integer pixel indices as one index below grid^4"""
+    g = int(grid)
+    a, b = np.asarray(xi1, dtype=np.int64) * g // int(w1), np.asarray(yi1, dtype=np.int64) * g // int(h1)
+    c, d = np.asarray(xi2, dtype=np.int64) * g // int(w2), np.asarray(yi2, dtype=np.int64) * g // int(h2)
+    return ((a * g + b) * g + c) * g + d
+
+
+def dense_cell_weight(count, min_count=2):
+    """D6: (1 << 20) div count where count >= min_count, else 1"""
+    count = np.asarray(count, dtype=np.int64)
+    return np.where(count >= int(min_count), (1 << 20) // np.maximum(count, 1), 1).astype(np.uint64)
+
+
+def check_dense_arguments(rows, n, expansion, grid, min_count):
+    """the limits the host refuses (D4, D6)"""
+    if not 0 <= int(rows) <= DENSE_MAX_ROWS:
+        raise ValueError(f"a pair's warp has at most 2^22 rows, not {rows}")
+    if not 1 <= int(n) <= DENSE_MAX_N:
+        raise ValueError(f"n must be 1 .. {DENSE_MAX_N}, not {n}")
+    if int(expansion) < 1 or int(expansion) * int(n) > DENSE_MAX_STAGE1:
+        raise ValueError(f"expansion must be at least 1 and expansion * n at most {DENSE_MAX_STAGE1}")
+    if not 1 <= int(grid) <= DENSE_MAX_GRID:
+        raise ValueError(f"grid must be 1 .. {DENSE_MAX_GRID}, not {grid}")
+    if int(min_count) < 1:
+        raise ValueError("min_count must be at least 1")
+
+
+def dense_candidates(warp, certainty, depth_map1, depth_map2, coords="normalized", threshold=0.05, filter="both_inf"):
+    """D1-D3 for one pair: (q (R,) uint32 weights, 0 for a non-candidate; p1, p2 (R, 2) float64 pixel coordinates; pixel indices xi1, yi1, xi2, yi2;
+    d1, d2 (R,) float64 depths, 0 where the points are not inside)"""
+    wp, ct = _table(warp, "warp"), _table(certainty, "certainty")
+    dm1, dm2 = _table(depth_map1, "depth maps"), _table(depth_map2, "depth maps")
+    if dm1.ndim != 2 or dm2.ndim != 2 or wp.shape[-1] != 4 or wp.size != 4 * ct.size:
+        raise ValueError("expected warp (R, 4) or (Hc, Wc, 4), certainty with one value per row and depth maps (H, W)")
+    wp, ct = wp.reshape(-1, 4), ct.reshape(-1)
+    (h1, w1), (h2, w2) = dm1.shape, dm2.shape
+    p1 = np.stack([dense_pixel_coord(wp[:, 0], w1, coords), dense_pixel_coord(wp[:, 1], h1, coords)], axis=1)
+    p2 = np.stack([dense_pixel_coord(wp[:, 2], w2, coords), dense_pixel_coord(wp[:, 3], h2, coords)], axis=1)
+    in1, xi1, yi1 = pixel_index(p1[:, 0], p1[:, 1], w1, h1)                               # rule 2
+    in2, xi2, yi2 = pixel_index(p2[:, 0], p2[:, 1], w2, h2)
+    ok = in1 & in2 & bool(dm1.size > 0 and dm2.size > 0)                                 # (a map without pixels has no row inside)
+    d1 = np.zeros(len(ct)); d2 = np.zeros(len(ct))
+    d1[ok] = dm1[yi1[ok], xi1[ok]].astype(np.float64)                                    # rule 3
+    d2[ok] = dm2[yi2[ok], xi2[ok]].astype(np.float64)
+    ok &= keep_depths(d1, d2, filter)                                                    # rule 4
+    q = np.where(ok, dense_weight(ct, threshold), np.uint32(0)).astype(np.uint32)        # D2, D3
+    return q, p1, p2, (xi1, yi1, xi2, yi2), d1, d2
+
+
+def sample_dense_numpy(warp, certainty, depth_map1, depth_map2, n, seed=0, coords="normalized", threshold=0.05, balanced=True, expansion=4, grid=8,
+                       min_count=2, filter="both_inf", ranked=False, center1=None, center2=None):
+    """One pair: warp (R, 4) or (Hc, Wc, 4) rows (xA, yA, xB, yB), certainty (R,) or (Hc, Wc), depth maps (H, W), all float32 / float64.
+    Returns (x1 (m, 2), x2 (m, 2), d1 (m,), d2 (m,) float64, rows (m,) int32, score (m,) float64), m <= n: the records of the sampled rows in
+    ascending row order, or (ranked) in descending certainty with ties by ascending row.  This function is the definition (D1-D7)."""
+    ct = np.asarray(certainty).reshape(-1)
+    check_dense_arguments(ct.size, n, expansion, grid, min_count)
+    q, p1, p2, (xi1, yi1, xi2, yi2), d1, d2 = dense_candidates(warp, certainty, depth_map1, depth_map2, coords, threshold, filter)
+    K = int(np.count_nonzero(q))
+    M1 = min((int(expansion) if balanced else 1) * int(n), K)                             # D5
+    rows = stratified_draw(q, M1, 1, seed)
+    if balanced and len(rows):                                                            # D6
+        (h1, w1), (h2, w2) = np.asarray(depth_map1).shape, np.asarray(depth_map2).shape
+        cell = dense_cell(xi1[rows], yi1[rows], xi2[rows], yi2[rows], w1, h1, w2, h2, grid)
+        count = np.bincount(cell, minlength=int(grid) ** 4)[cell]
+        rows = rows[stratified_draw(dense_cell_weight(count, min_count), min(int(n), len(rows)), 2, seed)]
+    score = ct[rows].astype(np.float64)
+    if ranked:                                                                            # D7: rule 6's order on the raw certainty
+        o = score_order(score)
+        rows, score = rows[o], score[o]
+    c1 = np.zeros(2) if center1 is None else np.asarray(center1, dtype=np.float64).reshape(2)
+    c2 = np.zeros(2) if center2 is None else np.asarray(center2, dtype=np.float64).reshape(2)
+    return p1[rows] - c1, p2[rows] - c2, d1[rows], d2[rows], rows.astype(np.int32), score
+
+
+def pad_dense_pairs(sampled, n):
+    """per-pair results of sample_dense_numpy -> the padded buffers the device writes: x1, x2 (B, n, 2), d1, d2 (B, n), n_per_pair (B,) int32,
+    rows (B, n) int32, score (B, n); behind the count x = 0, d = 1, rows = -1, score = 0"""
+    B = len(sampled)
+    x1 = np.zeros((B, n, 2)); x2 = np.zeros((B, n, 2)); d1 = np.ones((B, n)); d2 = np.ones((B, n))
+    cnt = np.zeros(B, dtype=np.int32)
+    rows = np.full((B, n), -1, dtype=np.int32)
+    score = np.zeros((B, n))
+    for b, (a1, a2, e1, e2, r, s) in enumerate(sampled):
+        m = cnt[b] = len(r)
+        x1[b, :m] = a1; x2[b, :m] = a2; d1[b, :m] = e1; d2[b, :m] = e2; rows[b, :m] = r; score[b, :m] = s
+    return x1, x2, d1, d2, cnt, rows, score

@@ -1417,6 +1417,140 @@ def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, de
     return res, match_mask, n_used
 
 
+# ---- the front end for DENSE matchers (include/mdrp_dense.h): a warp and its certainty instead of keypoints and index pairs.  What the
+# reference's dense demo does between the matcher and the estimator (certainty-weighted sampling, a density-balanced re-sampling, pixel coordinates,
+# depths at the truncated pixel, the depth filter) on the device; mdrp_amd/frontend.py sample_dense_numpy is the definition, equal as bytes.
+def _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, threshold, balanced, expansion, grid, min_count, filter, ranked,
+                      center1, center2):
+    """validated mdrp_dense_matches descriptor of torch tensors on one ROCm device -> (descriptor, tensors it points into, B, device)"""
+    import torch
+    if filter not in _capi.FILTERS:
+        raise ValueError(f"filter must be one of {tuple(_capi.FILTERS)}, not {filter!r}")
+    if coords not in _capi.DENSE_COORDS:
+        raise ValueError(f"coords must be one of {tuple(_capi.DENSE_COORDS)}, not {coords!r}")
+    n, expansion, grid, min_count = (int(v) for v in (n, expansion, grid, min_count))
+    if not 1 <= n <= _capi.DENSE_MAX_N:
+        raise ValueError(f"n must be 1 .. {_capi.DENSE_MAX_N}, not {n}")
+    if expansion < 1 or expansion * n > _capi.DENSE_MAX_STAGE1:
+        raise ValueError(f"expansion must be at least 1 and expansion * n at most {_capi.DENSE_MAX_STAGE1}, not {expansion} * {n}")
+    if not 1 <= grid <= _capi.DENSE_MAX_GRID:
+        raise ValueError(f"grid must be 1 .. {_capi.DENSE_MAX_GRID}, not {grid}")
+    if min_count < 1:
+        raise ValueError(f"min_count must be at least 1, not {min_count}")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must fit 64 bits (its low 32 bits are used)")
+    threshold = float(threshold)
+    named = {"warp": warp, "certainty": certainty, "depth_map1": depth_map1, "depth_map2": depth_map2}
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+        if t.device != warp.device:
+            raise ValueError("all tensors must live on the same device")
+    dev = warp.device
+    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
+    if warp.dtype not in ftypes or certainty.dtype not in ftypes:
+        raise ValueError("warp and certainty must be float32 or float64")
+    if depth_map1.dtype not in ftypes or depth_map2.dtype != depth_map1.dtype:
+        raise ValueError("depth maps must both be float32 or both float64")
+    if warp.dim() not in (3, 4) or warp.shape[-1] != 4:
+        raise ValueError("warp must have shape (B, R, 4) or (B, Hc, Wc, 4)")
+    B = int(warp.shape[0])
+    R = int(warp[0].numel()) // 4 if B > 0 else 0
+    if certainty.dim() not in (2, 3) or certainty.shape[0] != B or tuple(certainty.shape[1:]) != tuple(warp.shape[1:-1]):
+        raise ValueError(f"certainty must have shape {tuple(warp.shape[:-1])}, one value per warp row, not {tuple(certainty.shape)}")
+    if R > _capi.DENSE_MAX_ROWS:
+        raise ValueError(f"a pair's warp has at most 2^22 rows, not {R}")
+    if depth_map1.dim() != 3 or depth_map2.dim() != 3 or depth_map1.shape[0] != B or depth_map2.shape[0] != B:
+        raise ValueError("depth maps must have shape (B, H, W) with the warp's B")
+    wp, ct, dm1, dm2 = (t.contiguous() for t in (warp, certainty, depth_map1, depth_map2))
+
+    def center(c):
+        if c is None:
+            return None
+        c = torch.as_tensor(c, dtype=torch.float64).to(dev)
+        if c.numel() == 2:
+            c = c.reshape(1, 2).expand(B, 2)
+        if c.shape != (B, 2):
+            raise ValueError("centers must have shape (B, 2) or (2,)")
+        return c.contiguous()
+
+    c1, c2 = center(center1), center(center2)
+    desc = _capi.DenseMatches(wp.data_ptr(), ftypes[wp.dtype], R, ct.data_ptr(), ftypes[ct.dtype], _capi.DENSE_COORDS[coords], dm1.data_ptr(), dm2.data_ptr(),
+                              ftypes[dm1.dtype], dm1.shape[1], dm1.shape[2], dm2.shape[1], dm2.shape[2], _capi.FILTERS[filter],
+                              None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr(), n, 1 if balanced else 0, expansion, grid,
+                              min_count, 1 if ranked else 0, seed, threshold, None, None)
+    return desc, (wp, ct, dm1, dm2, c1, c2), B, dev
+
+
+def sample_dense_torch(warp, certainty, depth_map1, depth_map2, n=5000, seed=0, coords="normalized", threshold=0.05, balanced=True, expansion=4, grid=8,
+                       min_count=2, filter="both_inf", ranked=False, center1=None, center2=None):
+    """A dense matcher's output to the estimators' records, on the device's current torch stream.  warp (B, R, 4) or (B, Hc, Wc, 4) float32 |
+    float64 rows (xA, yA, xB, yB) - several layouts such as symmetric halves concatenate along the rows -, certainty with one value per row, depth
+    maps (B, H, W) float32 | float64 of their images' sizes, all on one ROCm device.  coords: "normalized" ([-1, 1] over each image, as the matcher
+    emits them) | "pixel".  n records per pair are drawn by certainty (certainties above `threshold` count alike), from `expansion` times as many
+    when `balanced`, which then re-draws n of them with weights inverse to the number of draws in their cell of a grid^4 histogram over both images
+    (cells of fewer than min_count draws get the smallest weight); mdrp_amd.frontend.sample_dense_numpy states every rule, and the result equals it
+    as bytes.  threshold, expansion, grid and min_count are untuned defaults: their effect on pose accuracy has not been measured.  The result of a
+    pair depends on the pair and the seed, not on its batch.
+    Returns (x1, x2 (B, n, 2), d1, d2 (B, n): float64 device tensors, the records first - in ascending row order, or with ranked=True in descending
+    certainty, the order estimate_batch_torch(scores="presorted") takes -, the rest x = 0, d = 1; n_per_pair: numpy int32; rows (B, n): int32 device
+    tensor, the warp row of every record, -1 behind the count; score (B, n): float64 device tensor, its certainty).  One stream synchronisation."""
+    import torch
+    desc, keep, B, dev = _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, threshold, balanced, expansion, grid, min_count,
+                                           filter, ranked, center1, center2)
+    n = desc.n
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        x1 = torch.empty((B, n, 2), dtype=torch.float64, device=dev)
+        x2 = torch.empty((B, n, 2), dtype=torch.float64, device=dev)
+        d1 = torch.empty((B, n), dtype=torch.float64, device=dev)
+        d2 = torch.empty((B, n), dtype=torch.float64, device=dev)
+        rows = torch.empty((B, n), dtype=torch.int32, device=dev)
+        score = torch.empty((B, n), dtype=torch.float64, device=dev)
+        cnt = h.sample_dense(desc, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), rows.data_ptr(), score.data_ptr())
+    del keep
+    return x1, x2, d1, d2, cnt, rows, score
+
+
+def estimate_dense_torch(kind, warp, certainty, depth_map1, depth_map2, cameras1=None, cameras2=None, ransac_opt=None, bundle_opt=None, n=5000, seed=0,
+                         coords="normalized", threshold=0.05, balanced=True, expansion=4, grid=8, min_count=2, filter="both_inf", ranked=False,
+                         center1=None, center2=None):
+    """estimate_batch_torch straight from a dense matcher's output and two depth maps (inputs as sample_dense_torch): the records are sampled on the
+    device into buffers of the handle and handed to the same estimator - byte for byte estimate_batch_torch on sample_dense_torch's output with its
+    n_per_pair (ranked=True: with scores="presorted", the progressive sampler in descending certainty; progressive_sampling in ransac_opt may then
+    be absent, False or True, and without ranked it is refused as before).  kind: "calibrated" | "shared_focal" | "varying_focal" (pass center1 /
+    center2 for the focal estimators: they take principal-point-centred pixels).  Queued on the device's current torch stream; the B counts cross to
+    the host behind one stream synchronisation, then the 136-byte result records.
+    Returns (records, record_mask: (B, n) uint8 device tensor - 1 where the sampled record is an inlier -, n_used: numpy int32, rows: (B, n) int32
+    device tensor, the warp row of every record, -1 behind the count)."""
+    import torch
+    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
+    if isinstance(kind, str) and kind not in kinds:
+        raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
+    k = kinds[kind] if isinstance(kind, str) else int(kind)
+    if k not in kinds.values():
+        raise ValueError("only the monodepth estimators (calibrated, shared_focal, varying_focal) take depth maps")
+    desc, keep, B, dev = _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, threshold, balanced, expansion, grid, min_count,
+                                           filter, ranked, center1, center2)
+    n = desc.n
+    cams1 = cams2 = None
+    if k == _capi.CALIB:
+        cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
+    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    with torch.cuda.device(dev):
+        record_mask = torch.zeros((B, n), dtype=torch.uint8, device=dev)
+        rows = torch.empty((B, n), dtype=torch.int32, device=dev)
+        desc.rows_out = rows.data_ptr()
+        n_used = h.estimate_dense_device(k, desc, B, ro, bo, cams1, cams2, record_mask.data_ptr())
+        res = h.fetch_results(B)
+    del keep
+    return res, record_mask, n_used, rows
+
+
 # ---- the same for a batch held per IMAGE (include/mdrp.h mdrp_image_pairs, DESIGN.md 7c): keypoint tables and depth maps exist once per image
 # and the pairs are index pairs into the image set — every frame of a video against one anchor, each image of an SfM set against many
 # others — so nothing is copied once per pair.  mdrp_amd/frontend.py gather_image_pairs_numpy states the semantics.
