@@ -17,32 +17,6 @@ RELPOSE_5PT, SHARED_6PT, FUNDAMENTAL_7PT = 3, 4, 5  # non-monodepth baselines (d
 MEM_HOST, MEM_DEVICE = 0, 1
 SOLVER_P3P, SOLVER_SHIFT, SOLVER_SHARED, SOLVER_VARYING = 0, 1, 2, 3
 
-EXPORTS = (
-    "mdrp_create_", "mdrp_create_on_stream_", "mdrp_destroy", "mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version", "mdrp_synchronize", "mdrp_estimate_batch",
-    "mdrp_estimate_batch_async", "mdrp_fetch_results", "mdrp_copy_results_device", "mdrp_solver_batch", "mdrp_score_models", "mdrp_count_candidates", "mdrp_bound_models", "mdrp_refine_models",
-    "mdrp_last_sweep_stats", "mdrp_last_stats", "mdrp_last_stats_sized", "mdrp_classic_solver_batch", "mdrp_solver_residency",
-    "mdrp_gather_matches", "mdrp_estimate_matches_async",
-    "mdrp_estimate_batch_budgets", "mdrp_estimate_batch_budgets_async", "mdrp_fetch_budget_results", "mdrp_copy_budget_results_device",
-    "mdrp_refine_batch", "mdrp_refine_batch_async",
-    "mdrp_gather_image_pairs", "mdrp_estimate_image_pairs_async",
-    "mdrp_estimate_batch_prior", "mdrp_estimate_batch_prior_async",
-    "mdrp_retire_models", "mdrp_replay_slots", "mdrp_front_lists", "mdrp_front_models",
-    "mdrp_estimate_batch_ranked", "mdrp_estimate_batch_ranked_async", "mdrp_prosac_samples", "mdrp_rank_scores",
-    "mdrp_gather_matches_ranked", "mdrp_estimate_matches_ranked_async", "mdrp_gather_image_pairs_ranked", "mdrp_estimate_image_pairs_ranked_async",
-)
-# the entry points of include/mdrp_classic_ranked.h, the extension header mdrp.h includes (EXPORTS above is mdrp.h's own list)
-EXPORTS_CLASSIC_RANKED = ("mdrp_estimate_classic_ranked", "mdrp_estimate_classic_ranked_async", "mdrp_prosac_samples_k")
-# the entry points of include/mdrp_classic_models.h, the second extension header mdrp.h includes: the baselines from a caller's model
-EXPORTS_CLASSIC_MODELS = ("mdrp_refine_classic", "mdrp_refine_classic_async", "mdrp_estimate_classic_prior", "mdrp_estimate_classic_prior_async")
-# the entry points of include/mdrp_classic_frontend.h, the third extension header mdrp.h includes: the baselines' device front end (no depth maps)
-EXPORTS_CLASSIC_FRONTEND = ("mdrp_gather_point_matches", "mdrp_gather_point_matches_ranked", "mdrp_gather_point_image_pairs",
-                            "mdrp_gather_point_image_pairs_ranked", "mdrp_estimate_classic_matches_async", "mdrp_estimate_classic_matches_ranked_async",
-                            "mdrp_estimate_classic_image_pairs_async", "mdrp_estimate_classic_image_pairs_ranked_async")
-# the entry points of include/mdrp_classic_focals.h, the fourth extension header mdrp.h includes: focals and pose from the 7-point estimator's F
-EXPORTS_CLASSIC_FOCALS = ("mdrp_focals_from_fundamental", "mdrp_pose_from_fundamental", "mdrp_pose_from_fundamental_async",
-                          "mdrp_estimate_fundamental_focals_async")
-# the entry points of include/mdrp_dense.h, the fifth extension header mdrp.h includes: the front end for dense matchers (a warp sampled by certainty)
-EXPORTS_DENSE = ("mdrp_sample_dense", "mdrp_estimate_dense_async")
 DENSE_COORDS = {"normalized": 0, "pixel": 1}  # mdrp_dense_matches.coords (include/mdrp_dense.h MDRP_DENSE_*)
 DENSE_MAX_ROWS, DENSE_MAX_STAGE1, DENSE_MAX_N, DENSE_MAX_GRID = 1 << 22, 65536, 16384, 8  # include/mdrp_dense.h MDRP_DENSE_MAX_*
 FOCAL_NO_MODEL, FOCAL_F1_NOT_REAL, FOCAL_F2_NOT_REAL, FOCAL_NO_VOTERS = 1, 2, 4, 8  # include/mdrp_classic_focals.h MDRP_FOCAL_*: mdrp_focal_pose.status
@@ -166,6 +140,109 @@ class FrontTables(C.Structure):
 assert C.sizeof(FrontTables) == 128
 FRONT_PICK_LIMIT = 64  # mdrp_schedule.h sched::FIRST_PICK_LIMIT
 
+# ---- the prototypes: {header: {symbol: argtypes}}, what load_library() declares and what the EXPORTS* tuples below list.  A new entry point is a row
+# here, a method of Handle on the staging helpers below, and a case in tests/binding_cases.py.
+_i, _p, _u64, _f64 = C.c_int, C.c_void_p, C.c_uint64, C.c_double
+_XD = [_p, _p, _p, _p]  # x1, x2, d1, d2
+_TAB = [_i, _i, _p, _p, _p]  # batch, n_max, n_per_pair, cam1, cam2
+_OPT = [C.POINTER(RansacOpt), C.POINTER(BundleOpt)]
+
+
+def _gather_args(desc, outs, ranked):
+    """a front end's gather: descriptor, (scores, score_type), batch, `outs` device buffers, the counts"""
+    return [_p, C.POINTER(desc), *([_p, _i] if ranked else []), _i, *[_p] * outs, _p]
+
+
+def _front_args(desc, ranked):
+    """a front end + estimator: kind, descriptor, (scores, score_type), batch, cam1, cam2, options, mask, the counts"""
+    return [_p, _i, C.POINTER(desc), *([_p, _i] if ranked else []), _i, _p, _p, *_OPT, _p, _p]
+
+
+PROTOTYPES = {
+    "mdrp.h": {
+        "mdrp_create_": [_i, _p, C.POINTER(_p), _i, _i],
+        "mdrp_create_on_stream_": [_i, _p, C.POINTER(_p), _i, _i],
+        "mdrp_destroy": [_p],
+        "mdrp_synchronize": [_p],
+        "mdrp_estimate_batch": [_p, _i, _i, *_XD, *_TAB, *_OPT, _p, _p],
+        "mdrp_estimate_batch_async": [_p, _i, *_XD, *_TAB, *_OPT, _p],
+        "mdrp_fetch_results": [_p, _p, _i],
+        "mdrp_copy_results_device": [_p, _p, _i],
+        "mdrp_solver_batch": [_p, _i, *_XD, _i, _p, _p],
+        "mdrp_score_models": [_p, _i, _i, _p, _i, _p, _p, _i, _f64, _p, _p],
+        "mdrp_count_candidates": [_p, _i, _p, _i, _p, _p, _i, _f64, _p],
+        "mdrp_bound_models": [_p, _i, _p, _i, _p, _p, _i, _f64, _p, _p],
+        "mdrp_refine_models": [_p, _i, _p, _i, *_XD, _i, _f64, _f64, C.POINTER(BundleOpt), _i, _p],
+        "mdrp_last_sweep_stats": [_p, C.POINTER(_f64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+        "mdrp_last_stats": [_p, C.POINTER(Stats)],
+        "mdrp_last_stats_sized": [_p, C.POINTER(Stats), C.c_size_t],
+        "mdrp_classic_solver_batch": [_p, _i, _p, _p, _i, _p, _p],
+        "mdrp_solver_residency": [_i, _i, _i, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)],
+        "mdrp_gather_matches": _gather_args(Matches, 5, False),
+        "mdrp_estimate_matches_async": _front_args(Matches, False),
+        "mdrp_estimate_batch_budgets": [_p, _i, _i, *_XD, *_TAB, *_OPT, _p, _i, _p, _p],
+        "mdrp_estimate_batch_budgets_async": [_p, _i, *_XD, *_TAB, *_OPT, _p, _i, _p],
+        "mdrp_fetch_budget_results": [_p, _p, _i, _i],
+        "mdrp_copy_budget_results_device": [_p, _p, _i, _i],
+        "mdrp_refine_batch": [_p, _i, _i, *_XD, *_TAB, *_OPT, _p, _i, _p, _p, _p, _p],
+        "mdrp_refine_batch_async": [_p, _i, *_XD, *_TAB, *_OPT, _p, _i, _p, _p, _p],
+        "mdrp_gather_image_pairs": _gather_args(ImagePairs, 5, False),
+        "mdrp_estimate_image_pairs_async": _front_args(ImagePairs, False),
+        "mdrp_estimate_batch_prior": [_p, _i, _i, *_XD, *_TAB, *_OPT, _p, _p, _p],
+        "mdrp_estimate_batch_prior_async": [_p, _i, *_XD, *_TAB, *_OPT, _p, _p],
+        "mdrp_retire_models": [_p, _i, _p, _i, _p, _p, _i, _f64, _u64, _f64, _p, _i, _p, _p, _p, _p, _p],
+        "mdrp_replay_slots": [_p, C.POINTER(RansacOpt), C.POINTER(Replay)],
+        "mdrp_front_lists": [_p, C.POINTER(FrontTables)],
+        "mdrp_front_models": [_p, _i, _p, _i, _p, _p, _i, _f64, _u64, _f64, _i, _p, _p, _p, _p],
+        "mdrp_estimate_batch_ranked": [_p, _i, _i, *_XD, _p, *_TAB, *_OPT, _p, _p],
+        "mdrp_estimate_batch_ranked_async": [_p, _i, *_XD, _p, *_TAB, *_OPT, _p],
+        "mdrp_prosac_samples": [_p, _u64, _i, _u64, _p, _i, _p],
+        "mdrp_rank_scores": [_p, _i, _p, _i, _i, _p, _p],
+        "mdrp_gather_matches_ranked": _gather_args(Matches, 5, True),
+        "mdrp_estimate_matches_ranked_async": _front_args(Matches, True),
+        "mdrp_gather_image_pairs_ranked": _gather_args(ImagePairs, 5, True),
+        "mdrp_estimate_image_pairs_ranked_async": _front_args(ImagePairs, True),
+    },
+    "mdrp_classic_ranked.h": {  # the 5- / 6- / 7-point baselines in match-score order
+        "mdrp_estimate_classic_ranked": [_p, _i, _i, _p, _p, _p, *_TAB, *_OPT, _p, _p],
+        "mdrp_estimate_classic_ranked_async": [_p, _i, _p, _p, _p, *_TAB, *_OPT, _p],
+        "mdrp_prosac_samples_k": [_p, _u64, _i, _i, _u64, _p, _i, _p],
+    },
+    "mdrp_classic_models.h": {  # the baselines from a caller's model
+        "mdrp_refine_classic": [_p, _i, _i, _p, _p, *_TAB, *_OPT, _p, _i, _p, _p, _p, _p],
+        "mdrp_refine_classic_async": [_p, _i, _p, _p, *_TAB, *_OPT, _p, _i, _p, _p, _p],
+        "mdrp_estimate_classic_prior": [_p, _i, _i, _p, _p, *_TAB, *_OPT, _p, _i, _p, _p],
+        "mdrp_estimate_classic_prior_async": [_p, _i, _p, _p, *_TAB, *_OPT, _p, _i, _p],
+    },
+    "mdrp_classic_frontend.h": {  # the baselines' device front end (no depth maps)
+        "mdrp_gather_point_matches": _gather_args(PointMatches, 3, False),
+        "mdrp_gather_point_matches_ranked": _gather_args(PointMatches, 3, True),
+        "mdrp_gather_point_image_pairs": _gather_args(PointImagePairs, 3, False),
+        "mdrp_gather_point_image_pairs_ranked": _gather_args(PointImagePairs, 3, True),
+        "mdrp_estimate_classic_matches_async": _front_args(PointMatches, False),
+        "mdrp_estimate_classic_matches_ranked_async": _front_args(PointMatches, True),
+        "mdrp_estimate_classic_image_pairs_async": _front_args(PointImagePairs, False),
+        "mdrp_estimate_classic_image_pairs_ranked_async": _front_args(PointImagePairs, True),
+    },
+    "mdrp_classic_focals.h": {  # focals and pose from the 7-point estimator's F
+        "mdrp_focals_from_fundamental": [_p, _i, _p, _p, _p, _i, _p],
+        "mdrp_pose_from_fundamental": [_p, _i, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p],
+        "mdrp_pose_from_fundamental_async": [_p, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p],
+        "mdrp_estimate_fundamental_focals_async": [_p, _p, _p, _i, _i, _p, *_OPT, _p, _p, _p, _p],
+    },
+    "mdrp_dense.h": {  # the front end for dense matchers (a warp sampled by certainty)
+        "mdrp_sample_dense": _gather_args(DenseMatches, 6, False),
+        "mdrp_estimate_dense_async": _front_args(DenseMatches, False),
+    },
+}
+# what each header declares: mdrp.h's own list (with the four symbols that only get a restype), then its extension headers'
+EXPORTS = tuple(PROTOTYPES["mdrp.h"]) + ("mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version")
+EXPORTS_CLASSIC_RANKED = tuple(PROTOTYPES["mdrp_classic_ranked.h"])
+EXPORTS_CLASSIC_MODELS = tuple(PROTOTYPES["mdrp_classic_models.h"])
+EXPORTS_CLASSIC_FRONTEND = tuple(PROTOTYPES["mdrp_classic_frontend.h"])
+EXPORTS_CLASSIC_FOCALS = tuple(PROTOTYPES["mdrp_classic_focals.h"])
+EXPORTS_DENSE = tuple(PROTOTYPES["mdrp_dense.h"])
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -185,7 +262,6 @@ def load_library():
         _ensure_hip_runtime()  # the library binds its hip* symbols to the process's one runtime when it is loaded
         lib = C.CDLL(LIB_PATH)
         _check_hip_runtime_version(lib)
-        vp, dp, ip = C.c_void_p, C.c_void_p, C.c_void_p
         lib.mdrp_last_error.restype = C.c_char_p
         lib.mdrp_version.restype = C.c_char_p
         abi = getattr(lib, "mdrp_abi_version", None)  # (a library from before ABI 0.4, e.g. through MDRP_LIB, has no such symbol)
@@ -194,104 +270,11 @@ def load_library():
         abi.restype = C.c_int
         if abi() != ABI_VERSION:
             raise MdrpError(f"{LIB_PATH} speaks ABI {abi():#x}, this binding {ABI_VERSION:#x}: rebuild (mdrp_amd/build.py)")
-        lib.mdrp_create_.argtypes = [C.c_int, vp, C.POINTER(vp), C.c_int, C.c_int]
-        lib.mdrp_create_on_stream_.argtypes = [C.c_int, vp, C.POINTER(vp), C.c_int, C.c_int]
-        lib.mdrp_destroy.argtypes = [vp]
         lib.mdrp_destroy.restype = None
-        lib.mdrp_synchronize.argtypes = [vp]
-        lib.mdrp_estimate_batch.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                            C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
-        lib.mdrp_estimate_batch_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                  C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
-        lib.mdrp_fetch_results.argtypes = [vp, vp, C.c_int]
-        lib.mdrp_copy_results_device.argtypes = [vp, vp, C.c_int]
-        lib.mdrp_solver_batch.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, vp, vp]
-        lib.mdrp_score_models.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, vp, vp]
-        lib.mdrp_count_candidates.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, vp]
-        lib.mdrp_bound_models.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, vp, vp]
-        lib.mdrp_refine_models.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double,
-                                           C.POINTER(BundleOpt), C.c_int, vp]
-        lib.mdrp_last_sweep_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        lib.mdrp_last_stats.argtypes = [vp, C.POINTER(Stats)]
-        lib.mdrp_last_stats_sized.argtypes = [vp, C.POINTER(Stats), C.c_size_t]
-        lib.mdrp_classic_solver_batch.argtypes = [vp, C.c_int, dp, dp, C.c_int, vp, vp]
-        lib.mdrp_gather_matches.argtypes = [vp, C.POINTER(Matches), C.c_int, dp, dp, dp, dp, ip, ip]
-        lib.mdrp_estimate_matches_async.argtypes = [vp, C.c_int, C.POINTER(Matches), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
-        if hasattr(lib, "mdrp_estimate_batch_budgets"):  # (an older ABI-0.6 library through MDRP_LIB has no budgets entry points: Handle._budgets_fn raises)
-            lib.mdrp_estimate_batch_budgets.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                        C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp]
-            lib.mdrp_estimate_batch_budgets_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp]
-            lib.mdrp_fetch_budget_results.argtypes = [vp, vp, C.c_int, C.c_int]
-            lib.mdrp_copy_budget_results_device.argtypes = [vp, vp, C.c_int, C.c_int]
-        if hasattr(lib, "mdrp_refine_batch"):  # (an older ABI-0.6 library through MDRP_LIB has no refine entry points: Handle._refine_fn raises)
-            lib.mdrp_refine_batch.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp, dp, ip]
-            lib.mdrp_refine_batch_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                    C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, dp, ip]
-        if hasattr(lib, "mdrp_gather_image_pairs"):  # (an older ABI-0.6 library through MDRP_LIB has no image-pairs entry points: Handle._image_pairs_fn raises)
-            lib.mdrp_gather_image_pairs.argtypes = [vp, C.POINTER(ImagePairs), C.c_int, dp, dp, dp, dp, ip, ip]
-            lib.mdrp_estimate_image_pairs_async.argtypes = [vp, C.c_int, C.POINTER(ImagePairs), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
-        if hasattr(lib, "mdrp_estimate_batch_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked entry points: Handle._ranked_fn raises)
-            lib.mdrp_estimate_batch_ranked.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
-            lib.mdrp_estimate_batch_ranked_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                             C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
-            lib.mdrp_prosac_samples.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint64, ip, C.c_int, vp]
-            lib.mdrp_rank_scores.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, ip, vp]
-        if hasattr(lib, "mdrp_estimate_classic_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked baselines: Handle._classic_ranked_fn raises)
-            lib.mdrp_estimate_classic_ranked.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                         C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
-            lib.mdrp_estimate_classic_ranked_async.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                               C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp]
-            lib.mdrp_prosac_samples_k.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, ip, C.c_int, vp]
-        if hasattr(lib, "mdrp_refine_classic"):  # (an older ABI-0.6 library through MDRP_LIB has no baselines from a model: Handle._classic_models_fn raises)
-            lib.mdrp_refine_classic.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp, dp, ip]
-            lib.mdrp_refine_classic_async.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                      C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, dp, ip]
-            lib.mdrp_estimate_classic_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                        C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp, vp]
-            lib.mdrp_estimate_classic_prior_async.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                              C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, C.c_int, vp]
-        if hasattr(lib, "mdrp_gather_matches_ranked"):  # (an older ABI-0.6 library through MDRP_LIB has no ranked front end: Handle._ranked_front_end_fn raises)
-            lib.mdrp_gather_matches_ranked.argtypes = [vp, C.POINTER(Matches), vp, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
-            lib.mdrp_estimate_matches_ranked_async.argtypes = [vp, C.c_int, C.POINTER(Matches), vp, C.c_int, C.c_int, vp, vp, C.POINTER(RansacOpt),
-                                                               C.POINTER(BundleOpt), vp, ip]
-            lib.mdrp_gather_image_pairs_ranked.argtypes = [vp, C.POINTER(ImagePairs), vp, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
-            lib.mdrp_estimate_image_pairs_ranked_async.argtypes = [vp, C.c_int, C.POINTER(ImagePairs), vp, C.c_int, C.c_int, vp, vp, C.POINTER(RansacOpt),
-                                                                   C.POINTER(BundleOpt), vp, ip]
-        if hasattr(lib, "mdrp_gather_point_matches"):  # (an older ABI-0.6 library through MDRP_LIB has no front end for the baselines: Handle._classic_front_end_fn raises)
-            for desc, stem in ((PointMatches, "matches"), (PointImagePairs, "image_pairs")):
-                getattr(lib, f"mdrp_gather_point_{stem}").argtypes = [vp, C.POINTER(desc), C.c_int, dp, dp, ip, ip]
-                getattr(lib, f"mdrp_gather_point_{stem}_ranked").argtypes = [vp, C.POINTER(desc), vp, C.c_int, C.c_int, dp, dp, ip, ip]
-                getattr(lib, f"mdrp_estimate_classic_{stem}_async").argtypes = [vp, C.c_int, C.POINTER(desc), C.c_int, vp, vp, C.POINTER(RansacOpt),
-                                                                                C.POINTER(BundleOpt), vp, ip]
-                getattr(lib, f"mdrp_estimate_classic_{stem}_ranked_async").argtypes = [vp, C.c_int, C.POINTER(desc), vp, C.c_int, C.c_int, vp, vp,
-                                                                                       C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
-        if hasattr(lib, "mdrp_focals_from_fundamental"):  # (an older ABI-0.6 library through MDRP_LIB has no focals from F: Handle._focals_fn raises)
-            lib.mdrp_focals_from_fundamental.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int, dp]
-            lib.mdrp_pose_from_fundamental.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, ip, vp, C.c_int, vp, dp, dp, vp]
-            lib.mdrp_pose_from_fundamental_async.argtypes = [vp, dp, dp, C.c_int, C.c_int, ip, vp, C.c_int, vp, dp, dp, vp]
-            lib.mdrp_estimate_fundamental_focals_async.argtypes = [vp, dp, dp, C.c_int, C.c_int, ip, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, dp, dp, vp]
-        if hasattr(lib, "mdrp_sample_dense"):
-            lib.mdrp_sample_dense.argtypes = [vp, C.POINTER(DenseMatches), C.c_int, dp, dp, dp, dp, ip, dp, ip]
-            lib.mdrp_estimate_dense_async.argtypes = [vp, C.c_int, C.POINTER(DenseMatches), C.c_int, vp, vp, C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, ip]
-        if hasattr(lib, "mdrp_estimate_batch_prior"):  # (an older ABI-0.6 library through MDRP_LIB has no prior entry points: Handle._prior_fn raises)
-            lib.mdrp_estimate_batch_prior.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                      C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp, vp]
-            lib.mdrp_estimate_batch_prior_async.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int, ip, vp, vp,
-                                                            C.POINTER(RansacOpt), C.POINTER(BundleOpt), vp, vp]
-        if hasattr(lib, "mdrp_retire_models"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.retire_models raises)
-            lib.mdrp_retire_models.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_uint64, C.c_double, vp, C.c_int,
-                                               vp, vp, vp, vp, vp]
-        if hasattr(lib, "mdrp_replay_slots"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.replay_slots raises)
-            lib.mdrp_replay_slots.argtypes = [vp, C.POINTER(RansacOpt), C.POINTER(Replay)]
-        if hasattr(lib, "mdrp_front_lists"):  # (an older ABI-0.6 library through MDRP_LIB has none: Handle.front_lists / front_models raise)
-            lib.mdrp_front_lists.argtypes = [vp, C.POINTER(FrontTables)]
-            lib.mdrp_front_models.argtypes = [vp, C.c_int, vp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_uint64, C.c_double, C.c_int, vp, vp, vp, vp]
-        if hasattr(lib, "mdrp_solver_residency"):  # (an older ABI-0.6 library through MDRP_LIB has none: solver_residency raises)
-            lib.mdrp_solver_residency.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        for symbols in PROTOTYPES.values():
+            for name, argtypes in symbols.items():
+                if hasattr(lib, name):  # (an older ABI-0.6 library through MDRP_LIB lacks the later entry points: _fn raises where one is called)
+                    getattr(lib, name).argtypes = argtypes
         _lib = lib
         return lib
 
@@ -307,8 +290,67 @@ def _check(lib, rc):
         raise MdrpError(f"mdrp error {rc}: {lib.mdrp_last_error().decode(errors='replace')}")
 
 
+def _fn(lib, name):
+    """the entry point `name` of the loaded library, or MdrpError where an older library (through MDRP_LIB) does not have it"""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise MdrpError(f"{LIB_PATH} has no {name}: rebuild (mdrp_amd/build.py)")
+    return fn
+
+
 def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _dev(p):
+    """an optional device pointer (an int; None or 0: absent) as the library takes it"""
+    return C.c_void_p(p) if p else None
+
+
+def _tables(n_per_pair, cam1, cam2):
+    """the per-pair tables of an estimator call, each optional, as the host arrays the library reads: n_per_pair int32, cam1 / cam2 camera records"""
+    return (None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32),
+            None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE),
+            None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE))
+
+
+def _host_batch(x1, x2, d1=None, d2=None, depths="none"):
+    """The correspondences of a host (numpy) batch as the library reads them: (x1, x2 (B, N, 2) float64, d1, d2 (B, N) float64 or None, B, N).
+    depths: "required" (a monodepth estimator without them is refused here), "optional" (each may be None: the library decides) or "none" (a
+    baseline: whatever was passed is dropped)."""
+    x1 = np.ascontiguousarray(x1, dtype=np.float64)
+    x2 = np.ascontiguousarray(x2, dtype=np.float64)
+    if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
+        raise ValueError("expected x1,x2 (B,N,2)")
+    if depths == "none":
+        d1 = d2 = None
+    else:
+        d1 = None if d1 is None and depths == "optional" else np.ascontiguousarray(d1, dtype=np.float64)
+        d2 = None if d2 is None and depths == "optional" else np.ascontiguousarray(d2, dtype=np.float64)
+        if d1 is not None and d2 is not None and (d1.shape != x1.shape[:2] or d2.shape != d1.shape):
+            raise ValueError("expected d1,d2 (B,N)")
+    return x1, x2, d1, d2, x1.shape[0], x1.shape[1]
+
+
+def _host_models(models, B, what):
+    """one optional model record per pair of a host batch"""
+    models = None if models is None else np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
+    if models is not None and len(models) != B:
+        raise ValueError(f"expected {B} {what}, got {len(models)}")
+    return models
+
+
+def _host_scores(scores, B, N):
+    """one optional score per correspondence of a host batch"""
+    scores = None if scores is None else np.ascontiguousarray(scores, dtype=np.float64)
+    if scores is not None and scores.shape != (B, N):
+        raise ValueError(f"expected scores ({B},{N}), got {scores.shape}")
+    return scores
+
+
+def _results(B, N, want_mask, planes=()):
+    """the records and the inlier masks a blocking call fills, `planes`: the leading axes (one per budget)"""
+    return np.zeros((*planes, B), dtype=RESULT_DTYPE), np.zeros((*planes, B, N), dtype=np.uint8) if want_mask else None
 
 
 def ransac_opt_from_dict(d=None):
@@ -368,10 +410,8 @@ def solver_residency(solver, resident_per_simd, keep_free_bytes=0, device=0):
     """(LDS bytes of a compute unit, dynamic LDS the scheduler's rule reserves per one-wavefront solver workgroup or 0, workgroups per compute unit
     the runtime's occupancy query reports for that reservation): mdrp_solver_residency — no kernel runs"""
     lib = load_library()
-    if not hasattr(lib, "mdrp_solver_residency"):
-        raise MdrpError("this library has no mdrp_solver_residency")
     lds, reserve, wgs = C.c_uint64(), C.c_uint64(), C.c_int()
-    _check(lib, lib.mdrp_solver_residency(int(device), int(solver), int(resident_per_simd), int(keep_free_bytes), C.byref(lds), C.byref(reserve), C.byref(wgs)))
+    _check(lib, _fn(lib, "mdrp_solver_residency")(int(device), int(solver), int(resident_per_simd), int(keep_free_bytes), C.byref(lds), C.byref(reserve), C.byref(wgs)))
     return lds.value, reserve.value, wgs.value
 
 
@@ -472,7 +512,7 @@ class Handle:
         if stream is None:
             _check(self._lib, self._lib.mdrp_create_(int(device), None, C.byref(h), ABI_VERSION, C.sizeof(RansacOpt)))
         else:
-            _check(self._lib, self._lib.mdrp_create_on_stream_(int(device), C.c_void_p(int(stream)) if stream else None, C.byref(h), ABI_VERSION, C.sizeof(RansacOpt)))
+            _check(self._lib, self._lib.mdrp_create_on_stream_(int(device), _dev(int(stream)), C.byref(h), ABI_VERSION, C.sizeof(RansacOpt)))
         self._h = h
         self.device = int(device)
         self.stream = stream
@@ -493,23 +533,9 @@ class Handle:
 
     # ---- batched estimators, host (numpy) buffers
     def estimate_batch(self, kind, x1, x2, d1, d2, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        if kind >= RELPOSE_5PT:
-            d1 = d2 = None  # the non-monodepth baselines take no depths
-        else:
-            d1 = np.ascontiguousarray(d1, dtype=np.float64)
-            d2 = np.ascontiguousarray(d2, dtype=np.float64)
-            if d1.shape != x1.shape[:2] or d2.shape != d1.shape:
-                raise ValueError("expected d1,d2 (B,N)")
-        B, N = x1.shape[:2]
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        out = np.zeros(B, dtype=RESULT_DTYPE)
-        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
+        x1, x2, d1, d2, B, N = _host_batch(x1, x2, d1, d2, "none" if kind >= RELPOSE_5PT else "required")  # the non-monodepth baselines take no depths
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask)
         _check(self._lib, self._lib.mdrp_estimate_batch(self._h, kind, MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N,
                                                         _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
                                                         _ptr(out), _ptr(mask)))
@@ -518,464 +544,263 @@ class Handle:
     # ---- batched estimators, device pointers (ints), results fetched separately
     def estimate_batch_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ropt, bopt, n_per_pair=None,
                               cam1=None, cam2=None, mask_ptr=None):
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        _check(self._lib, self._lib.mdrp_estimate_batch_async(self._h, kind, C.c_void_p(x1_ptr), C.c_void_p(x2_ptr),
-                                                              C.c_void_p(d1_ptr) if d1_ptr else None, C.c_void_p(d2_ptr) if d2_ptr else None, int(batch), int(n_max),
-                                                              _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
-                                                              C.c_void_p(mask_ptr) if mask_ptr else None))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, self._lib.mdrp_estimate_batch_async(self._h, kind, _dev(x1_ptr), _dev(x2_ptr), _dev(d1_ptr), _dev(d2_ptr), int(batch), int(n_max),
+                                                              _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _dev(mask_ptr)))
 
     # ---- every budget of a list in one run (include/mdrp.h: iteration budgets).  The list goes to the library as it is: the library checks it.
-    def _budgets_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the budgets entry points (rebuild: mdrp_amd/build.py)")
-        return fn
-
     def estimate_batch_budgets(self, kind, x1, x2, d1, d2, ropt, bopt, budgets, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
         """estimate_batch at every budget: records (C, B) and masks (C, B, N), C = len(budgets)"""
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        if kind >= RELPOSE_5PT:
-            d1 = d2 = None
-        else:
-            d1 = np.ascontiguousarray(d1, dtype=np.float64)
-            d2 = np.ascontiguousarray(d2, dtype=np.float64)
-            if d1.shape != x1.shape[:2] or d2.shape != d1.shape:
-                raise ValueError("expected d1,d2 (B,N)")
-        B, N = x1.shape[:2]
+        x1, x2, d1, d2, B, N = _host_batch(x1, x2, d1, d2, "none" if kind >= RELPOSE_5PT else "required")
         ks = np.ascontiguousarray(budgets, dtype=np.uint64).reshape(-1)
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        out = np.zeros((len(ks), B), dtype=RESULT_DTYPE)
-        mask = np.zeros((len(ks), B, N), dtype=np.uint8) if want_mask else None
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        _check(self._lib, self._budgets_fn("mdrp_estimate_batch_budgets")(self._h, kind, MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N,
-                                                                _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
-                                                                _ptr(ks), len(ks), _ptr(out), _ptr(mask)))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask, (len(ks),))
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_batch_budgets")(self._h, kind, MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N,
+                                                                        _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                                        _ptr(ks), len(ks), _ptr(out), _ptr(mask)))
         return out, mask
 
     def estimate_batch_budgets_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, ropt, bopt, budgets, n_per_pair=None,
                                       cam1=None, cam2=None, mask_ptr=None):
         """estimate_batch_device at every budget; mask_ptr: (C, batch, n_max) bytes on the device.  Records: fetch_budget_results."""
         ks = np.ascontiguousarray(budgets, dtype=np.uint64).reshape(-1)
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        _check(self._lib, self._budgets_fn("mdrp_estimate_batch_budgets_async")(self._h, kind, C.c_void_p(x1_ptr), C.c_void_p(x2_ptr),
-                                                                      C.c_void_p(d1_ptr) if d1_ptr else None, C.c_void_p(d2_ptr) if d2_ptr else None,
-                                                                      int(batch), int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
-                                                                      _ptr(ks), len(ks), C.c_void_p(mask_ptr) if mask_ptr else None))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_batch_budgets_async")(self._h, kind, _dev(x1_ptr), _dev(x2_ptr), _dev(d1_ptr), _dev(d2_ptr),
+                                                                              int(batch), int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt),
+                                                                              C.byref(bopt), _ptr(ks), len(ks), _dev(mask_ptr)))
 
     def fetch_budget_results(self, n_budgets, batch):
         out = np.zeros((int(n_budgets), int(batch)), dtype=RESULT_DTYPE)
-        _check(self._lib, self._budgets_fn("mdrp_fetch_budget_results")(self._h, _ptr(out), int(n_budgets), int(batch)))
+        _check(self._lib, _fn(self._lib, "mdrp_fetch_budget_results")(self._h, _ptr(out), int(n_budgets), int(batch)))
         return out
 
     def copy_budget_results_device(self, dst_ptr, n_budgets, batch):
         """the records of the last budgets call into device memory at dst_ptr (n_budgets x batch x 136 bytes)"""
-        _check(self._lib, self._budgets_fn("mdrp_copy_budget_results_device")(self._h, C.c_void_p(dst_ptr), int(n_budgets), int(batch)))
+        _check(self._lib, _fn(self._lib, "mdrp_copy_budget_results_device")(self._h, _dev(dst_ptr), int(n_budgets), int(batch)))
 
     # ---- refine and verify caller-supplied models (include/mdrp.h: mdrp_refine_batch).  Arguments go to the library as they are: the library checks them.
-    def _refine_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the refine entry points (rebuild: mdrp_amd/build.py)")
-        return fn
-
     def refine_batch(self, kind, x1, x2, d1, d2, models, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
         """B models (MODEL_DTYPE) against B pairs, host (numpy) buffers: (records, masks (B, N) uint8 or None, initial score (B,) float64,
         initial inlier count (B,) int32)"""
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        d1 = np.ascontiguousarray(d1, dtype=np.float64)
-        d2 = np.ascontiguousarray(d2, dtype=np.float64)
-        if d1.shape != x1.shape[:2] or d2.shape != d1.shape:
-            raise ValueError("expected d1,d2 (B,N)")
-        B, N = x1.shape[:2]
-        models = None if models is None else np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
-        if models is not None and len(models) != B:
-            raise ValueError(f"expected {B} models, got {len(models)}")
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        out = np.zeros(B, dtype=RESULT_DTYPE)
-        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        x1, x2, d1, d2, B, N = _host_batch(x1, x2, d1, d2, "required")
+        models = _host_models(models, B, "models")
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask)
         score0, inl0 = np.zeros(B), np.zeros(B, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        _check(self._lib, self._refine_fn("mdrp_refine_batch")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
-                                                               C.byref(ropt), C.byref(bopt), _ptr(models), int(stages), _ptr(out), _ptr(mask), _ptr(score0), _ptr(inl0)))
+        _check(self._lib, _fn(self._lib, "mdrp_refine_batch")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N, _ptr(npp), _ptr(c1),
+                                                              _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(models), int(stages), _ptr(out), _ptr(mask),
+                                                              _ptr(score0), _ptr(inl0)))
         return out, mask, score0, inl0
 
     def refine_batch_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, models_ptr, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None,
                             cam1=None, cam2=None, mask_ptr=None, initial_score_ptr=None, initial_inliers_ptr=None):
         """the same on device pointers (ints), queued on the handle's stream; models_ptr: batch x 96 bytes; initial_score_ptr / initial_inliers_ptr:
         batch float64 / int32 on the device, or None.  Records: fetch_results / copy_results_device."""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _check(self._lib, self._refine_fn("mdrp_refine_batch_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), int(batch), int(n_max),
-                                                                     _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(models_ptr), int(stages),
-                                                                     vp(mask_ptr), vp(initial_score_ptr), vp(initial_inliers_ptr)))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, _fn(self._lib, "mdrp_refine_batch_async")(self._h, int(kind), _dev(x1_ptr), _dev(x2_ptr), _dev(d1_ptr), _dev(d2_ptr), int(batch),
+                                                                    int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _dev(models_ptr),
+                                                                    int(stages), _dev(mask_ptr), _dev(initial_score_ptr), _dev(initial_inliers_ptr)))
 
     # ---- estimate with a prior (include/mdrp.h: mdrp_estimate_batch_prior).  Arguments go to the library as they are: the library checks them.
-    def _prior_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the prior entry points (rebuild: mdrp_amd/build.py)")
-        return fn
-
     def estimate_batch_prior(self, kind, x1, x2, d1, d2, priors, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
         """estimate_batch with one prior (MODEL_DTYPE; a NaN q[0]: none) per pair, host (numpy) buffers: (records, masks (B, N) uint8 or None)"""
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        d1 = None if d1 is None else np.ascontiguousarray(d1, dtype=np.float64)
-        d2 = None if d2 is None else np.ascontiguousarray(d2, dtype=np.float64)
-        if d1 is not None and d2 is not None and (d1.shape != x1.shape[:2] or d2.shape != d1.shape):
-            raise ValueError("expected d1,d2 (B,N)")
-        B, N = x1.shape[:2]
-        priors = None if priors is None else np.ascontiguousarray(priors, dtype=MODEL_DTYPE).reshape(-1)
-        if priors is not None and len(priors) != B:
-            raise ValueError(f"expected {B} priors, got {len(priors)}")
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        out = np.zeros(B, dtype=RESULT_DTYPE)
-        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        _check(self._lib, self._prior_fn("mdrp_estimate_batch_prior")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N, _ptr(npp),
+        x1, x2, d1, d2, B, N = _host_batch(x1, x2, d1, d2, "optional")
+        priors = _host_models(priors, B, "priors")
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_batch_prior")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), B, N, _ptr(npp),
                                                                       _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(priors), _ptr(out), _ptr(mask)))
         return out, mask
 
     def estimate_batch_prior_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, batch, n_max, priors_ptr, ropt, bopt, n_per_pair=None, cam1=None, cam2=None,
                                     mask_ptr=None):
         """the same on device pointers (ints), queued on the handle's stream; priors_ptr: batch x 96 bytes.  Records: fetch_results / copy_results_device."""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _check(self._lib, self._prior_fn("mdrp_estimate_batch_prior_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), int(batch), int(n_max),
-                                                                            _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(priors_ptr), vp(mask_ptr)))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_batch_prior_async")(self._h, int(kind), _dev(x1_ptr), _dev(x2_ptr), _dev(d1_ptr), _dev(d2_ptr),
+                                                                            int(batch), int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt),
+                                                                            C.byref(bopt), _dev(priors_ptr), _dev(mask_ptr)))
 
     # ---- estimate in match-score order (include/mdrp.h: mdrp_estimate_batch_ranked).  Arguments go to the library as they are: the library checks them.
-    def _ranked_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the ranked entry points (rebuild: mdrp_amd/build.py)")
-        return fn
-
     def estimate_batch_ranked(self, kind, x1, x2, d1, d2, scores, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
         """estimate_batch in score order with the progressive sampler, host (numpy) buffers; scores (B, N), higher is better, or None: the records
         are in quality order already.  (records, masks (B, N) uint8 in the caller's order or None)"""
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        d1 = None if d1 is None else np.ascontiguousarray(d1, dtype=np.float64)
-        d2 = None if d2 is None else np.ascontiguousarray(d2, dtype=np.float64)
-        if d1 is not None and d2 is not None and (d1.shape != x1.shape[:2] or d2.shape != d1.shape):
-            raise ValueError("expected d1,d2 (B,N)")
-        B, N = x1.shape[:2]
-        scores = None if scores is None else np.ascontiguousarray(scores, dtype=np.float64)
-        if scores is not None and scores.shape != (B, N):
-            raise ValueError(f"expected scores ({B},{N}), got {scores.shape}")
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        out = np.zeros(B, dtype=RESULT_DTYPE)
-        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        _check(self._lib, self._ranked_fn("mdrp_estimate_batch_ranked")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), _ptr(scores), B, N,
-                                                                        _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(out), _ptr(mask)))
+        x1, x2, d1, d2, B, N = _host_batch(x1, x2, d1, d2, "optional")
+        scores = _host_scores(scores, B, N)
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_batch_ranked")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), _ptr(scores), B, N,
+                                                                       _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(out), _ptr(mask)))
         return out, mask
 
     def estimate_batch_ranked_device(self, kind, x1_ptr, x2_ptr, d1_ptr, d2_ptr, scores_ptr, batch, n_max, ropt, bopt, n_per_pair=None, cam1=None, cam2=None,
                                      mask_ptr=None):
         """the same on device pointers (ints), queued on the handle's stream; scores_ptr: batch x n_max float64, or None / 0 for records in quality
         order.  Records: fetch_results / copy_results_device."""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _check(self._lib, self._ranked_fn("mdrp_estimate_batch_ranked_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(d1_ptr), vp(d2_ptr), vp(scores_ptr),
-                                                                              int(batch), int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
-                                                                              vp(mask_ptr)))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_batch_ranked_async")(self._h, int(kind), _dev(x1_ptr), _dev(x2_ptr), _dev(d1_ptr), _dev(d2_ptr),
+                                                                             _dev(scores_ptr), int(batch), int(n_max), _ptr(npp), _ptr(c1), _ptr(c2),
+                                                                             C.byref(ropt), C.byref(bopt), _dev(mask_ptr)))
 
     def prosac_samples(self, seed, n, max_prosac_iterations, chunk_lens, fill=0):
         """the device's progressive sampler for one table of n records, drawn chunk by chunk: (sum(chunk_lens), 3) uint32 (`fill` where n < 3:
         nothing is written)"""
         lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
         out = np.full((int(lens.sum()), 3), fill, dtype=np.uint32)
-        _check(self._lib, self._ranked_fn("mdrp_prosac_samples")(self._h, int(seed), int(n), int(max_prosac_iterations), _ptr(lens), len(lens), _ptr(out)))
+        _check(self._lib, _fn(self._lib, "mdrp_prosac_samples")(self._h, int(seed), int(n), int(max_prosac_iterations), _ptr(lens), len(lens), _ptr(out)))
         return out
 
     # ---- the 5- / 6- / 7-point baselines in match-score order (include/mdrp.h: mdrp_estimate_classic_ranked): no depths
-    def _classic_ranked_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the ranked baselines (rebuild: mdrp_amd/build.py)")
-        return fn
-
     def estimate_classic_ranked(self, kind, x1, x2, scores, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
         """estimate_batch of a baseline (kind 3, 4, 5) in score order with the progressive sampler, host (numpy) buffers; scores (B, N), higher is
         better, or None: the records are in quality order already.  (records, masks (B, N) uint8 in the caller's order or None)"""
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        B, N = x1.shape[:2]
-        scores = None if scores is None else np.ascontiguousarray(scores, dtype=np.float64)
-        if scores is not None and scores.shape != (B, N):
-            raise ValueError(f"expected scores ({B},{N}), got {scores.shape}")
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        out = np.zeros(B, dtype=RESULT_DTYPE)
-        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        _check(self._lib, self._classic_ranked_fn("mdrp_estimate_classic_ranked")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(scores), B, N, _ptr(npp),
-                                                                                  _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(out), _ptr(mask)))
+        x1, x2, _, _, B, N = _host_batch(x1, x2)
+        scores = _host_scores(scores, B, N)
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_classic_ranked")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), _ptr(scores), B, N, _ptr(npp),
+                                                                         _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _ptr(out), _ptr(mask)))
         return out, mask
 
     def estimate_classic_ranked_device(self, kind, x1_ptr, x2_ptr, scores_ptr, batch, n_max, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, mask_ptr=None):
         """the same on device pointers (ints), queued on the handle's stream; scores_ptr: batch x n_max float64, or None / 0 for records in quality
         order.  Records: fetch_results / copy_results_device."""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _check(self._lib, self._classic_ranked_fn("mdrp_estimate_classic_ranked_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), vp(scores_ptr), int(batch),
-                                                                                        int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
-                                                                                        vp(mask_ptr)))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_classic_ranked_async")(self._h, int(kind), _dev(x1_ptr), _dev(x2_ptr), _dev(scores_ptr), int(batch),
+                                                                               int(n_max), _ptr(npp), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
+                                                                               _dev(mask_ptr)))
 
     def prosac_samples_k(self, seed, n, sample_size, max_prosac_iterations, chunk_lens, fill=0):
         """prosac_samples for samples of sample_size records (3, 5, 6 or 7): (sum(chunk_lens), sample_size) uint32"""
         lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
         out = np.full((int(lens.sum()), int(sample_size)), fill, dtype=np.uint32)
-        _check(self._lib, self._classic_ranked_fn("mdrp_prosac_samples_k")(self._h, int(seed), int(n), int(sample_size), int(max_prosac_iterations), _ptr(lens),
-                                                                           len(lens), _ptr(out)))
+        _check(self._lib, _fn(self._lib, "mdrp_prosac_samples_k")(self._h, int(seed), int(n), int(sample_size), int(max_prosac_iterations), _ptr(lens),
+                                                                  len(lens), _ptr(out)))
         return out
 
     # ---- the 5- / 6- / 7-point baselines from a caller's model (include/mdrp_classic_models.h).  Arguments go to the library as they are: the library checks them.
-    def _classic_models_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the baselines took models (rebuild: mdrp_amd/build.py)")
-        return fn
-
-    @staticmethod
-    def _classic_host_args(x1, x2, models, n_per_pair, cam1, cam2, what):
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        B = x1.shape[0]
-        models = None if models is None else np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
-        if models is not None and len(models) != B:
-            raise ValueError(f"expected {B} {what}, got {len(models)}")
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        return x1, x2, models, npp, c1, c2
-
     def refine_classic(self, kind, x1, x2, models, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None, cam1=None, cam2=None, want_mask=True):
         """refine_batch for a baseline (kind 3, 4, 5): B models (MODEL_DTYPE, in the caller's units; a fundamental matrix in the first nine doubles)
         against B pairs, host (numpy) buffers: (records, masks (B, N) uint8 or None, initial score (B,) float64, initial inlier count (B,) int32)"""
-        x1, x2, models, npp, c1, c2 = self._classic_host_args(x1, x2, models, n_per_pair, cam1, cam2, "models")
-        B, N = x1.shape[:2]
-        out = np.zeros(B, dtype=RESULT_DTYPE)
-        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
+        x1, x2, _, _, B, N = _host_batch(x1, x2)
+        models = _host_models(models, B, "models")
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask)
         score0, inl0 = np.zeros(B), np.zeros(B, dtype=np.int32)
-        _check(self._lib, self._classic_models_fn("mdrp_refine_classic")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
-                                                                         C.byref(ropt), C.byref(bopt), _ptr(models), int(stages), _ptr(out), _ptr(mask),
-                                                                         _ptr(score0), _ptr(inl0)))
+        _check(self._lib, _fn(self._lib, "mdrp_refine_classic")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
+                                                                C.byref(ropt), C.byref(bopt), _ptr(models), int(stages), _ptr(out), _ptr(mask),
+                                                                _ptr(score0), _ptr(inl0)))
         return out, mask, score0, inl0
 
     def refine_classic_device(self, kind, x1_ptr, x2_ptr, batch, n_max, models_ptr, ropt, bopt, stages=STAGE_LO | STAGE_INLIERS, n_per_pair=None, cam1=None,
                               cam2=None, mask_ptr=None, initial_score_ptr=None, initial_inliers_ptr=None):
         """the same on device pointers (ints), queued on the handle's stream; models_ptr: batch x 96 bytes; initial_score_ptr / initial_inliers_ptr:
         batch float64 / int32 on the device, or None.  Records: fetch_results / copy_results_device."""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _check(self._lib, self._classic_models_fn("mdrp_refine_classic_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), int(batch), int(n_max), _ptr(npp), _ptr(c1),
-                                                                               _ptr(c2), C.byref(ropt), C.byref(bopt), vp(models_ptr), int(stages), vp(mask_ptr),
-                                                                               vp(initial_score_ptr), vp(initial_inliers_ptr)))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, _fn(self._lib, "mdrp_refine_classic_async")(self._h, int(kind), _dev(x1_ptr), _dev(x2_ptr), int(batch), int(n_max), _ptr(npp), _ptr(c1),
+                                                                      _ptr(c2), C.byref(ropt), C.byref(bopt), _dev(models_ptr), int(stages), _dev(mask_ptr),
+                                                                      _dev(initial_score_ptr), _dev(initial_inliers_ptr)))
 
     def estimate_classic_prior(self, kind, x1, x2, priors, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, want_mask=True, prior_space=0):
         """estimate_batch of a baseline (kind 3, 4, 5) with one prior (MODEL_DTYPE; a NaN first double: none) per pair, host (numpy) buffers;
         prior_space 0: the caller's units, 1: the estimator's normalised coordinates.  (records, masks (B, N) uint8 or None)"""
-        x1, x2, priors, npp, c1, c2 = self._classic_host_args(x1, x2, priors, n_per_pair, cam1, cam2, "priors")
-        B, N = x1.shape[:2]
-        out = np.zeros(B, dtype=RESULT_DTYPE)
-        mask = np.zeros((B, N), dtype=np.uint8) if want_mask else None
-        _check(self._lib, self._classic_models_fn("mdrp_estimate_classic_prior")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
-                                                                                 C.byref(ropt), C.byref(bopt), _ptr(priors), int(prior_space), _ptr(out), _ptr(mask)))
+        x1, x2, _, _, B, N = _host_batch(x1, x2)
+        priors = _host_models(priors, B, "priors")
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        out, mask = _results(B, N, want_mask)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_classic_prior")(self._h, int(kind), MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(c1), _ptr(c2),
+                                                                        C.byref(ropt), C.byref(bopt), _ptr(priors), int(prior_space), _ptr(out), _ptr(mask)))
         return out, mask
 
     def estimate_classic_prior_device(self, kind, x1_ptr, x2_ptr, batch, n_max, priors_ptr, ropt, bopt, n_per_pair=None, cam1=None, cam2=None, mask_ptr=None,
                                       prior_space=0):
         """the same on device pointers (ints), queued on the handle's stream; priors_ptr: batch x 96 bytes.  Records: fetch_results / copy_results_device."""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _check(self._lib, self._classic_models_fn("mdrp_estimate_classic_prior_async")(self._h, int(kind), vp(x1_ptr), vp(x2_ptr), int(batch), int(n_max), _ptr(npp),
-                                                                                       _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), vp(priors_ptr),
-                                                                                       int(prior_space), vp(mask_ptr)))
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_classic_prior_async")(self._h, int(kind), _dev(x1_ptr), _dev(x2_ptr), int(batch), int(n_max), _ptr(npp),
+                                                                              _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), _dev(priors_ptr),
+                                                                              int(prior_space), _dev(mask_ptr)))
 
     def rank_scores(self, scores, n_per_pair=None):
         """k_rank on host scores (B, N): order (B, N) int32, -1 at and past n"""
         scores = np.ascontiguousarray(scores, dtype=np.float64)
         B, N = scores.shape
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        npp = _tables(n_per_pair, None, None)[0]
         order = np.full((B, N), -2, dtype=np.int32)
-        _check(self._lib, self._ranked_fn("mdrp_rank_scores")(self._h, MEM_HOST, _ptr(scores), B, N, _ptr(npp), _ptr(order)))
+        _check(self._lib, _fn(self._lib, "mdrp_rank_scores")(self._h, MEM_HOST, _ptr(scores), B, N, _ptr(npp), _ptr(order)))
         return order
 
     def rank_scores_device(self, scores_ptr, batch, n_max, order_ptr, n_per_pair=None):
         """k_rank on device pointers (ints): scores batch x n_max float64, order batch x n_max int32.  Synchronous."""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        _check(self._lib, self._ranked_fn("mdrp_rank_scores")(self._h, MEM_DEVICE, C.c_void_p(scores_ptr), int(batch), int(n_max), _ptr(npp), C.c_void_p(order_ptr)))
+        npp = _tables(n_per_pair, None, None)[0]
+        _check(self._lib, _fn(self._lib, "mdrp_rank_scores")(self._h, MEM_DEVICE, _dev(scores_ptr), int(batch), int(n_max), _ptr(npp), _dev(order_ptr)))
 
-    # ---- device front end: a Matches descriptor of device pointers
+    # ---- the device front ends: a descriptor of device pointers (Matches, ImagePairs; PointMatches, PointImagePairs without depth maps).  scores_ptr
+    # is a device pointer to batch x m_max scores of score_type (F32 | F64), or None / 0 for match rows that are in quality order already; a ranked call
+    # is the entry point `stem`_ranked.  Arguments go to the library as they are: the library checks them.
+    def _gather(self, stem, desc, batch, out_ptrs, scores_ptr=None, score_type=F64, ranked=False):
+        """a front end's gather alone into the caller's device buffers `out_ptrs`: the kept rows per pair"""
+        n = np.zeros(int(batch), dtype=np.int32)
+        scored = (_dev(scores_ptr), int(score_type)) if ranked else ()
+        _check(self._lib, _fn(self._lib, stem + "_ranked" if ranked else stem)(self._h, C.byref(desc), *scored, int(batch), *map(_dev, out_ptrs), _ptr(n)))
+        return n
+
+    def _estimate_front(self, stem, kind, desc, batch, ropt, bopt, cam1, cam2, mask_ptr, scores_ptr=None, score_type=F64, ranked=False):
+        """a front end + estimator on the handle's stream: the kept rows per pair"""
+        _, c1, c2 = _tables(None, cam1, cam2)
+        n = np.zeros(int(batch), dtype=np.int32)
+        scored = (_dev(scores_ptr), int(score_type)) if ranked else ()
+        _check(self._lib, _fn(self._lib, stem + ("_ranked_async" if ranked else "_async"))(self._h, int(kind), C.byref(desc), *scored, int(batch), _ptr(c1), _ptr(c2),
+                                                                                            C.byref(ropt), C.byref(bopt), _dev(mask_ptr), _ptr(n)))
+        return n
+
     def gather_matches(self, mm, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
         """k_gather alone into the caller's device buffers; returns the kept rows per pair (numpy int32).  Synchronises the stream once."""
-        n = np.zeros(int(batch), dtype=np.int32)
-        _check(self._lib, self._lib.mdrp_gather_matches(self._h, C.byref(mm), int(batch), C.c_void_p(x1_ptr), C.c_void_p(x2_ptr), C.c_void_p(d1_ptr),
-                                                        C.c_void_p(d2_ptr), C.c_void_p(slot_ptr), _ptr(n)))
-        return n
+        return self._gather("mdrp_gather_matches", mm, batch, (x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr))
 
     def estimate_matches_device(self, kind, mm, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
         """front end + estimator on the handle's stream; results stay on the device (fetch_results / copy_results_device).  Returns the kept rows
         per pair (numpy int32)."""
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        n = np.zeros(int(batch), dtype=np.int32)
-        _check(self._lib, self._lib.mdrp_estimate_matches_async(self._h, int(kind), C.byref(mm), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
-                                                                C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
-        return n
-
-    # ---- the same on per-image tables: an ImagePairs descriptor of device pointers
-    def _image_pairs_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: rebuild (mdrp_amd/build.py)")
-        return fn
+        return self._estimate_front("mdrp_estimate_matches", kind, mm, batch, ropt, bopt, cam1, cam2, match_mask_ptr)
 
     def gather_image_pairs(self, ip, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
         """k_gather_images alone into the caller's device buffers; returns the kept rows per pair (numpy int32).  Synchronises the stream once."""
-        n = np.zeros(int(batch), dtype=np.int32)
-        _check(self._lib, self._image_pairs_fn("mdrp_gather_image_pairs")(self._h, C.byref(ip), int(batch), C.c_void_p(x1_ptr), C.c_void_p(x2_ptr),
-                                                                          C.c_void_p(d1_ptr), C.c_void_p(d2_ptr), C.c_void_p(slot_ptr), _ptr(n)))
-        return n
+        return self._gather("mdrp_gather_image_pairs", ip, batch, (x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr))
 
     def estimate_image_pairs_device(self, kind, ip, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
         """front end on per-image tables + estimator on the handle's stream; cam1 / cam2 are per PAIR; results stay on the device (fetch_results /
         copy_results_device).  Returns the kept rows per pair (numpy int32)."""
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        n = np.zeros(int(batch), dtype=np.int32)
-        _check(self._lib, self._image_pairs_fn("mdrp_estimate_image_pairs_async")(self._h, int(kind), C.byref(ip), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt),
-                                                                                  C.byref(bopt), C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
-        return n
-
-    # ---- the front end with match scores (include/mdrp.h: mdrp_gather_matches_ranked ...): scores_ptr is a device pointer to batch x m_max scores of
-    # score_type (F32 | F64), or None / 0 for match rows that are in quality order already.  Arguments go to the library as they are: the library checks them.
-    def _ranked_front_end_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the ranked front end (rebuild: mdrp_amd/build.py)")
-        return fn
-
-    def _gather_ranked(self, name, desc, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
-        n = np.zeros(int(batch), dtype=np.int32)
-        _check(self._lib, self._ranked_front_end_fn(name)(self._h, C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type), int(batch),
-                                                           C.c_void_p(x1_ptr), C.c_void_p(x2_ptr), C.c_void_p(d1_ptr), C.c_void_p(d2_ptr), C.c_void_p(slot_ptr),
-                                                           _ptr(n)))
-        return n
-
-    def _estimate_ranked(self, name, kind, desc, scores_ptr, score_type, batch, ropt, bopt, cam1, cam2, match_mask_ptr):
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        n = np.zeros(int(batch), dtype=np.int32)
-        _check(self._lib, self._ranked_front_end_fn(name)(self._h, int(kind), C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type),
-                                                           int(batch), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt),
-                                                           C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n)))
-        return n
+        return self._estimate_front("mdrp_estimate_image_pairs", kind, ip, batch, ropt, bopt, cam1, cam2, match_mask_ptr)
 
     def gather_matches_ranked(self, mm, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
         """k_gather_ranked alone into the caller's device buffers: the kept rows at their ranks; returns the kept rows per pair (numpy int32).
         Synchronises the stream once."""
-        return self._gather_ranked("mdrp_gather_matches_ranked", mm, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr)
+        return self._gather("mdrp_gather_matches", mm, batch, (x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr), scores_ptr, score_type, True)
 
     def estimate_matches_ranked_device(self, kind, mm, scores_ptr, score_type, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
         """ranked front end + estimator with the progressive sampler on the handle's stream; results stay on the device (fetch_results /
         copy_results_device).  Returns the kept rows per pair (numpy int32)."""
-        return self._estimate_ranked("mdrp_estimate_matches_ranked_async", kind, mm, scores_ptr, score_type, batch, ropt, bopt, cam1, cam2, match_mask_ptr)
+        return self._estimate_front("mdrp_estimate_matches", kind, mm, batch, ropt, bopt, cam1, cam2, match_mask_ptr, scores_ptr, score_type, True)
 
     def gather_image_pairs_ranked(self, ip, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr):
         """gather_matches_ranked on per-image tables (k_gather_images_ranked)"""
-        return self._gather_ranked("mdrp_gather_image_pairs_ranked", ip, scores_ptr, score_type, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr)
+        return self._gather("mdrp_gather_image_pairs", ip, batch, (x1_ptr, x2_ptr, d1_ptr, d2_ptr, slot_ptr), scores_ptr, score_type, True)
 
     def estimate_image_pairs_ranked_device(self, kind, ip, scores_ptr, score_type, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None):
         """estimate_matches_ranked_device on per-image tables; cam1 / cam2 are per PAIR"""
-        return self._estimate_ranked("mdrp_estimate_image_pairs_ranked_async", kind, ip, scores_ptr, score_type, batch, ropt, bopt, cam1, cam2, match_mask_ptr)
+        return self._estimate_front("mdrp_estimate_image_pairs", kind, ip, batch, ropt, bopt, cam1, cam2, match_mask_ptr, scores_ptr, score_type, True)
 
-    # ---- the baselines' front end (include/mdrp_classic_frontend.h): a PointMatches / PointImagePairs descriptor of device pointers, no depths.
-    # scores_ptr as in the ranked front end above; ranked=False is the unranked entry point.  Arguments go to the library as they are.
-    def _classic_front_end_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the baselines' front end (rebuild: mdrp_amd/build.py)")
-        return fn
-
-    @staticmethod
-    def _point_stem(desc):
-        return "image_pairs" if isinstance(desc, PointImagePairs) else "matches"
-
+    # ---- the baselines' front end (include/mdrp_classic_frontend.h): a PointMatches / PointImagePairs descriptor, no depths; ranked=False is the
+    # unranked entry point
     def gather_points(self, desc, batch, x1_ptr, x2_ptr, slot_ptr, scores_ptr=None, score_type=F64, ranked=False):
         """k_gather_points* alone into the caller's device buffers (no depths); returns the kept rows per pair (numpy int32).  Synchronises the
         stream once."""
-        n = np.zeros(int(batch), dtype=np.int32)
-        out = (C.c_void_p(x1_ptr), C.c_void_p(x2_ptr), C.c_void_p(slot_ptr), _ptr(n))
-        if ranked:
-            fn = self._classic_front_end_fn(f"mdrp_gather_point_{self._point_stem(desc)}_ranked")
-            _check(self._lib, fn(self._h, C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type), int(batch), *out))
-        else:
-            _check(self._lib, self._classic_front_end_fn(f"mdrp_gather_point_{self._point_stem(desc)}")(self._h, C.byref(desc), int(batch), *out))
-        return n
+        stem = "image_pairs" if isinstance(desc, PointImagePairs) else "matches"
+        return self._gather(f"mdrp_gather_point_{stem}", desc, batch, (x1_ptr, x2_ptr, slot_ptr), scores_ptr, score_type, ranked)
 
     def estimate_points_device(self, kind, desc, batch, ropt, bopt, cam1=None, cam2=None, match_mask_ptr=None, scores_ptr=None, score_type=F64, ranked=False):
         """front end without depths + a baseline (kind 3, 4, 5) on the handle's stream; cam1 / cam2 are per PAIR; results stay on the device
         (fetch_results / copy_results_device).  Returns the kept rows per pair (numpy int32)."""
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        n = np.zeros(int(batch), dtype=np.int32)
-        tail = (int(batch), _ptr(c1), _ptr(c2), C.byref(ropt), C.byref(bopt), C.c_void_p(match_mask_ptr) if match_mask_ptr else None, _ptr(n))
-        if ranked:
-            fn = self._classic_front_end_fn(f"mdrp_estimate_classic_{self._point_stem(desc)}_ranked_async")
-            _check(self._lib, fn(self._h, int(kind), C.byref(desc), C.c_void_p(scores_ptr) if scores_ptr else None, int(score_type), *tail))
-        else:
-            _check(self._lib, self._classic_front_end_fn(f"mdrp_estimate_classic_{self._point_stem(desc)}_async")(self._h, int(kind), C.byref(desc), *tail))
-        return n
+        stem = "image_pairs" if isinstance(desc, PointImagePairs) else "matches"
+        return self._estimate_front(f"mdrp_estimate_classic_{stem}", kind, desc, batch, ropt, bopt, cam1, cam2, match_mask_ptr, scores_ptr, score_type, ranked)
 
     def fetch_results(self, batch):
         out = np.zeros(batch, dtype=RESULT_DTYPE)
@@ -984,7 +809,7 @@ class Handle:
 
     def copy_results_device(self, dst_ptr, batch):
         """the result records of the last device-resident estimate into device memory at dst_ptr (batch x 136 bytes)"""
-        _check(self._lib, self._lib.mdrp_copy_results_device(self._h, C.c_void_p(dst_ptr), int(batch)))
+        _check(self._lib, self._lib.mdrp_copy_results_device(self._h, _dev(dst_ptr), int(batch)))
 
     def last_sweep_stats(self):
         ms, launches, evals = C.c_double(0), C.c_int64(0), C.c_int64(0)
@@ -1061,8 +886,7 @@ class Handle:
         exact sweep RETIRE_SWEEP_*, against the records (rec_cnt, rec_score); rec_score None or inf: no record.  Returns (scores, counts, left_at,
         info, cand_stat): the slots (count -2: retired), 1 / 2 / 3 = left at k_count / at k_bound / reached the sweep, info = (undecided after
         phase A, survivors of the count, survivors of the bound), and the pair's candidate statistics after the run"""
-        if not hasattr(self._lib, "mdrp_retire_models"):
-            raise MdrpError(f"{LIB_PATH} has no mdrp_retire_models: rebuild (mdrp_amd/build.py)")
+        fn = _fn(self._lib, "mdrp_retire_models")
         models = np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
         x1 = np.ascontiguousarray(x1, dtype=np.float64)
         x2 = np.ascontiguousarray(x2, dtype=np.float64)
@@ -1073,9 +897,8 @@ class Handle:
         cs_in = np.array([int(cand_stat[0]), int(cand_stat[1])], dtype=np.uint64)
         cs_out = np.zeros(2, dtype=np.uint64)
         score = np.finfo(np.float64).max if rec_score is None or not rec_score < np.finfo(np.float64).max else float(rec_score)
-        _check(self._lib, self._lib.mdrp_retire_models(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1), float(sq_threshold),
-                                                       int(rec_cnt), score, _ptr(cs_in), int(flags), _ptr(scores), _ptr(counts), _ptr(left_at),
-                                                       _ptr(info), _ptr(cs_out)))
+        _check(self._lib, fn(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1), float(sq_threshold),
+                             int(rec_cnt), score, _ptr(cs_in), int(flags), _ptr(scores), _ptr(counts), _ptr(left_at), _ptr(info), _ptr(cs_out)))
         return scores, counts, left_at, info, cs_out
 
     def replay_slots(self, mps, sample_sz, chunk_start, chunk_lens, ropt, states, slot_score, slot_inl, models, lo_score, lo_cnt, lo_models, budgets=None,
@@ -1085,8 +908,7 @@ class Handle:
         (models: MODEL_DTYPE); checkpoints: REPLAY_STATE_DTYPE [n_budgets][batch] of the call before, or None.  Returns dict(states, triggers: one
         REPLAY_TRIGGER_DTYPE array per pair, n_triggers / scan_cnt / scan_score [n_chunks][batch] behind each scan, scan_inst [n_chunks], prefix,
         begin, end, total of the LO plan, n_active, max_needed, checkpoints)"""
-        if not hasattr(self._lib, "mdrp_replay_slots"):
-            raise MdrpError(f"{LIB_PATH} has no mdrp_replay_slots: rebuild (mdrp_amd/build.py)")
+        fn = _fn(self._lib, "mdrp_replay_slots")
         lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
         states = np.array(states, dtype=REPLAY_STATE_DTYPE).reshape(-1)  # (a copy: in and out)
         batch, nc, slots = len(states), len(lens), int(lens.sum()) * int(mps)
@@ -1103,7 +925,7 @@ class Handle:
         inst, plan, nact, need = np.zeros(nc, np.int32), np.zeros(3 * batch + 2, np.int32), np.zeros(1, np.int32), np.zeros(1, np.uint64)
         io = Replay(int(mps), int(sample_sz), batch, nc, int(chunk_start), _ptr(lens), *[_ptr(a) for a in tabs], _ptr(bud), nb, 0, _ptr(states),
                     _ptr(ck) if nb else None, _ptr(trig), _ptr(ntr), _ptr(scnt), _ptr(ssc), _ptr(inst), _ptr(plan), _ptr(nact), _ptr(need))
-        _check(self._lib, self._lib.mdrp_replay_slots(self._h, C.byref(ropt), C.byref(io)))
+        _check(self._lib, fn(self._h, C.byref(ropt), C.byref(io)))
         return dict(states=states, triggers=[trig[p, :ntr[-1, p]] for p in range(batch)], n_triggers=ntr, scan_cnt=scnt, scan_score=ssc, scan_inst=inst,
                     prefix=plan[:batch + 1], begin=plan[batch + 1:2 * batch + 1], end=plan[2 * batch + 1:3 * batch + 1], total=int(plan[3 * batch + 1]),
                     n_active=int(nact[0]), max_needed=int(need[0]), checkpoints=ck)
@@ -1113,8 +935,7 @@ class Handle:
         slot | key << 24.  slot_score, slot_inl: [batch][slots].  fill: dict of initial values of the outputs (tag lists: uint32, counters: int32),
         which an inactive pair keeps.  Returns dict(picked, rest, kept: one uint32 array per pair, in the kernels' order; pick_count, rest_count
         [2 batch], surv_count; evals; tags_pick, tags_rest, tags_out: the whole buffers)"""
-        if not hasattr(self._lib, "mdrp_front_lists"):
-            raise MdrpError(f"{LIB_PATH} has no mdrp_front_lists: rebuild (mdrp_amd/build.py)")
+        fn = _fn(self._lib, "mdrp_front_lists")
         slot_score = np.ascontiguousarray(slot_score, dtype=np.float64)
         slot_inl = np.ascontiguousarray(slot_inl, dtype=np.int32)
         batch, slots = slot_inl.shape
@@ -1136,7 +957,7 @@ class Handle:
         io = FrontTables(batch, slots, int(pick), 0, _ptr(n), _ptr(act), _ptr(thr), _ptr(count), _ptr(tags), _ptr(slot_score), _ptr(slot_inl),
                          _ptr(bufs["tags_pick"]), _ptr(bufs["tags_rest"]), _ptr(bufs["tags_out"]), _ptr(cnts["pick_count"]), _ptr(cnts["rest_count"]),
                          _ptr(cnts["surv_count"]), _ptr(evals))
-        _check(self._lib, self._lib.mdrp_front_lists(self._h, C.byref(io)))
+        _check(self._lib, fn(self._h, C.byref(io)))
 
         def cut(buf, lens):
             return [buf[p, :max(0, min(int(lens[p]), slots))].copy() for p in range(batch)]
@@ -1148,8 +969,7 @@ class Handle:
         prefix retirement -> k_score.  Returns (scores, counts, left_at, info): the slots (count -2: retired, -3: a NaN model), 0 / 1 / 4 / 5 / 3 =
         on no list / retired by k_count / picked / retired by k_first_filter / kept and scored, info = (survivors of the count, entries of P, of
         the rest list, of the kept list, hypotheses the filter reports as evaluated)"""
-        if not hasattr(self._lib, "mdrp_front_models"):
-            raise MdrpError(f"{LIB_PATH} has no mdrp_front_models: rebuild (mdrp_amd/build.py)")
+        fn = _fn(self._lib, "mdrp_front_models")
         models = np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1)
         x1 = np.ascontiguousarray(x1, dtype=np.float64)
         x2 = np.ascontiguousarray(x2, dtype=np.float64)
@@ -1158,14 +978,13 @@ class Handle:
         left_at = np.zeros(len(models), dtype=np.int32)
         info = np.zeros(5, dtype=np.int32)
         score = np.finfo(np.float64).max if rec_score is None or not rec_score < np.finfo(np.float64).max else float(rec_score)
-        _check(self._lib, self._lib.mdrp_front_models(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1), float(sq_threshold),
-                                                      int(rec_cnt), score, int(pick), _ptr(scores), _ptr(counts), _ptr(left_at), _ptr(info)))
+        _check(self._lib, fn(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1), float(sq_threshold),
+                             int(rec_cnt), score, int(pick), _ptr(scores), _ptr(counts), _ptr(left_at), _ptr(info)))
         return scores, counts, left_at, info
 
     def score_models_device(self, kind, models_ptr, num_models, x1_ptr, x2_ptr, n, sq_threshold, scores_ptr, counts_ptr):
-        _check(self._lib, self._lib.mdrp_score_models(self._h, int(kind), MEM_DEVICE, C.c_void_p(models_ptr), int(num_models),
-                                                      C.c_void_p(x1_ptr), C.c_void_p(x2_ptr), int(n), float(sq_threshold),
-                                                      C.c_void_p(scores_ptr), C.c_void_p(counts_ptr)))
+        _check(self._lib, self._lib.mdrp_score_models(self._h, int(kind), MEM_DEVICE, _dev(models_ptr), int(num_models), _dev(x1_ptr), _dev(x2_ptr), int(n),
+                                                      float(sq_threshold), _dev(scores_ptr), _dev(counts_ptr)))
 
     def refine_models(self, kind, models, x1, x2, d1, d2, scale_reproj, weight_sampson, bopt, estimate_shift=False):
         models = np.ascontiguousarray(models, dtype=MODEL_DTYPE).reshape(-1).copy()
@@ -1180,12 +999,6 @@ class Handle:
         return models, cost
 
     # ---- the varying-focal baseline's tail: focals and pose from F (include/mdrp_classic_focals.h)
-    def _focals_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: rebuild (mdrp_amd/build.py)")
-        return fn
-
     def focals_from_fundamental(self, F, pp1=None, pp2=None):
         """F (B, 3, 3) or (B, 9) row-major, pp1 / pp2 (B, 2) or None (the origin) -> (B, 2) focals, NaN where not real (mdrp_focals_from_fundamental)"""
         F = np.ascontiguousarray(F, dtype=np.float64).reshape(-1, 9)
@@ -1193,82 +1006,58 @@ class Handle:
         pp1 = None if pp1 is None else np.ascontiguousarray(pp1, dtype=np.float64).reshape(B, 2)
         pp2 = None if pp2 is None else np.ascontiguousarray(pp2, dtype=np.float64).reshape(B, 2)
         out = np.zeros((B, 2))
-        _check(self._lib, self._focals_fn("mdrp_focals_from_fundamental")(self._h, MEM_HOST, _ptr(F), _ptr(pp1), _ptr(pp2), B, _ptr(out)))
+        _check(self._lib, _fn(self._lib, "mdrp_focals_from_fundamental")(self._h, MEM_HOST, _ptr(F), _ptr(pp1), _ptr(pp2), B, _ptr(out)))
         return out
 
     def focals_from_fundamental_device(self, F_ptr, pp1_ptr, pp2_ptr, batch, out_ptr):
-        _check(self._lib, self._focals_fn("mdrp_focals_from_fundamental")(self._h, MEM_DEVICE, C.c_void_p(F_ptr), C.c_void_p(pp1_ptr) if pp1_ptr else None,
-                                                                          C.c_void_p(pp2_ptr) if pp2_ptr else None, int(batch), C.c_void_p(out_ptr)))
+        _check(self._lib, _fn(self._lib, "mdrp_focals_from_fundamental")(self._h, MEM_DEVICE, _dev(F_ptr), _dev(pp1_ptr), _dev(pp2_ptr), int(batch),
+                                                                         _dev(out_ptr)))
 
     def pose_from_fundamental(self, x1, x2, models, n_per_pair=None, mask=None, pp1=None, pp2=None):
         """host buffers: x1, x2 (B, N, 2); models: (B,) MODEL_DTYPE or RESULT_DTYPE records holding F (the record size is the stride); mask (B, N)
         uint8 or None; pp1 / pp2 (B, 2) or None -> (B,) FOCAL_POSE_DTYPE (mdrp_pose_from_fundamental)"""
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        x2 = np.ascontiguousarray(x2, dtype=np.float64)
-        if x1.ndim != 3 or x1.shape[2] != 2 or x2.shape != x1.shape:
-            raise ValueError("expected x1,x2 (B,N,2)")
-        B, N = x1.shape[:2]
+        x1, x2, _, _, B, N = _host_batch(x1, x2)
         models = np.ascontiguousarray(models).reshape(-1)
         if models.dtype not in (MODEL_DTYPE, RESULT_DTYPE) or len(models) != B:
             raise ValueError(f"models: {B} records of _capi.MODEL_DTYPE or _capi.RESULT_DTYPE")
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
+        npp = _tables(n_per_pair, None, None)[0]
         mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(B, N)
         pp1 = None if pp1 is None else np.ascontiguousarray(pp1, dtype=np.float64).reshape(B, 2)
         pp2 = None if pp2 is None else np.ascontiguousarray(pp2, dtype=np.float64).reshape(B, 2)
         out = np.zeros(B, dtype=FOCAL_POSE_DTYPE)
-        _check(self._lib, self._focals_fn("mdrp_pose_from_fundamental")(self._h, MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(models),
-                                                                        models.dtype.itemsize, _ptr(mask), _ptr(pp1), _ptr(pp2), _ptr(out)))
+        _check(self._lib, _fn(self._lib, "mdrp_pose_from_fundamental")(self._h, MEM_HOST, _ptr(x1), _ptr(x2), B, N, _ptr(npp), _ptr(models),
+                                                                       models.dtype.itemsize, _ptr(mask), _ptr(pp1), _ptr(pp2), _ptr(out)))
         return out
 
     def pose_from_fundamental_device(self, x1_ptr, x2_ptr, batch, n_max, models_ptr, stride, out_ptr, n_per_pair=None, mask_ptr=None, pp1_ptr=None,
                                      pp2_ptr=None, blocking_out=None):
         """device pointers (ints).  blocking_out None: mdrp_pose_from_fundamental_async into out_ptr (device); a FOCAL_POSE_DTYPE array: the blocking
         call with mem_space = device, the records into that host array (out_ptr is not read)"""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        npp = _tables(n_per_pair, None, None)[0]
+        args = (_dev(x1_ptr), _dev(x2_ptr), int(batch), int(n_max), _ptr(npp), _dev(models_ptr), int(stride), _dev(mask_ptr), _dev(pp1_ptr), _dev(pp2_ptr))
         if blocking_out is None:
-            _check(self._lib, self._focals_fn("mdrp_pose_from_fundamental_async")(self._h, opt(x1_ptr), opt(x2_ptr), int(batch), int(n_max), _ptr(npp),
-                                                                                  opt(models_ptr), int(stride), opt(mask_ptr), opt(pp1_ptr), opt(pp2_ptr),
-                                                                                  opt(out_ptr)))
+            _check(self._lib, _fn(self._lib, "mdrp_pose_from_fundamental_async")(self._h, *args, _dev(out_ptr)))
         else:
-            _check(self._lib, self._focals_fn("mdrp_pose_from_fundamental")(self._h, MEM_DEVICE, opt(x1_ptr), opt(x2_ptr), int(batch), int(n_max), _ptr(npp),
-                                                                            opt(models_ptr), int(stride), opt(mask_ptr), opt(pp1_ptr), opt(pp2_ptr),
-                                                                            _ptr(blocking_out)))
+            _check(self._lib, _fn(self._lib, "mdrp_pose_from_fundamental")(self._h, MEM_DEVICE, *args, _ptr(blocking_out)))
 
     def estimate_fundamental_focals_device(self, x1_ptr, x2_ptr, batch, n_max, ropt, bopt, out_ptr, n_per_pair=None, mask_ptr=None, pp1_ptr=None,
                                            pp2_ptr=None):
         """the 7-point estimate with the tail queued behind it (mdrp_estimate_fundamental_focals_async); the F records through fetch_results"""
-        npp = None if n_per_pair is None else np.ascontiguousarray(n_per_pair, dtype=np.int32)
-        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        _check(self._lib, self._focals_fn("mdrp_estimate_fundamental_focals_async")(self._h, opt(x1_ptr), opt(x2_ptr), int(batch), int(n_max), _ptr(npp),
-                                                                                    C.byref(ropt), C.byref(bopt), opt(mask_ptr), opt(pp1_ptr), opt(pp2_ptr),
-                                                                                    opt(out_ptr)))
+        npp = _tables(n_per_pair, None, None)[0]
+        _check(self._lib, _fn(self._lib, "mdrp_estimate_fundamental_focals_async")(self._h, _dev(x1_ptr), _dev(x2_ptr), int(batch), int(n_max), _ptr(npp),
+                                                                                   C.byref(ropt), C.byref(bopt), _dev(mask_ptr), _dev(pp1_ptr), _dev(pp2_ptr),
+                                                                                   _dev(out_ptr)))
 
     # ---- the front end for dense matchers (include/mdrp_dense.h): a DenseMatches descriptor of device pointers.  Arguments go to the library as they
     # are: the library checks them.
-    def _dense_fn(self, name):
-        fn = getattr(self._lib, name, None)
-        if fn is None:
-            raise MdrpError(f"{LIB_PATH} has no {name}: it was built before the dense front end (rebuild: mdrp_amd/build.py)")
-        return fn
-
     def sample_dense(self, desc, batch, x1_ptr, x2_ptr, d1_ptr, d2_ptr, rows_ptr, score_ptr):
         """the sampler alone into the caller's device buffers ([batch][n]); returns the records per pair (numpy int32).  Synchronises the stream once."""
-        n = np.zeros(int(batch), dtype=np.int32)
-        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        _check(self._lib, self._dense_fn("mdrp_sample_dense")(self._h, C.byref(desc), int(batch), opt(x1_ptr), opt(x2_ptr), opt(d1_ptr), opt(d2_ptr),
-                                                              opt(rows_ptr), opt(score_ptr), _ptr(n)))
-        return n
+        return self._gather("mdrp_sample_dense", desc, batch, (x1_ptr, x2_ptr, d1_ptr, d2_ptr, rows_ptr, score_ptr))
 
     def estimate_dense_device(self, kind, desc, batch, ropt, bopt, cam1=None, cam2=None, record_mask_ptr=None):
         """sampler + estimator on the handle's stream; results stay on the device (fetch_results / copy_results_device); desc.rows_out / score_out
         receive the records' rows and certainties.  Returns the records per pair (numpy int32)."""
-        c1 = None if cam1 is None else np.ascontiguousarray(cam1, dtype=CAMERA_DTYPE)
-        c2 = None if cam2 is None else np.ascontiguousarray(cam2, dtype=CAMERA_DTYPE)
-        n = np.zeros(int(batch), dtype=np.int32)
-        _check(self._lib, self._dense_fn("mdrp_estimate_dense_async")(self._h, int(kind), C.byref(desc), int(batch), _ptr(c1), _ptr(c2), C.byref(ropt),
-                                                                      C.byref(bopt), C.c_void_p(record_mask_ptr) if record_mask_ptr else None, _ptr(n)))
-        return n
+        return self._estimate_front("mdrp_estimate_dense", kind, desc, batch, ropt, bopt, cam1, cam2, record_mask_ptr)
 
 
 _default_tls = threading.local()

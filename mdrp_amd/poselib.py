@@ -928,6 +928,45 @@ def _torch_handle(dev, stream_ptr):
     return h
 
 
+def _handle_on(dev):
+    """the calling thread's handle on the current torch stream of the torch device `dev`"""
+    import torch
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    return _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+
+
+MONODEPTH_KINDS = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
+
+
+def _monodepth_kind(kind):
+    """the kind of an entry point that reads depth maps: a name of MONODEPTH_KINDS or its id"""
+    if isinstance(kind, str) and kind not in MONODEPTH_KINDS:
+        raise ValueError(f"kind must be one of {tuple(MONODEPTH_KINDS)}, not {kind!r}")
+    k = MONODEPTH_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if k not in MONODEPTH_KINDS.values():
+        raise ValueError("only the monodepth estimators (calibrated, shared_focal, varying_focal) take depth maps")
+    return k
+
+
+def _check_resident_scores(scores, shape):
+    """a score tensor of a resident batch, checked before anything touches the device: float32 / float64, one score per correspondence"""
+    import torch
+    if not (isinstance(scores, torch.Tensor) and scores.dtype in (torch.float32, torch.float64)):
+        raise ValueError('scores must be a float32 / float64 tensor on the inputs\' device or "presorted"')
+    if tuple(scores.shape) != tuple(shape):
+        raise ValueError(f"scores must be {tuple(shape)}, one per correspondence, not {tuple(scores.shape)}")
+
+
+def _resident_scores(scores, device):
+    """the checked scores as the ranked entry points read them: None for "presorted", else a contiguous float64 tensor the caller keeps alive"""
+    import torch
+    if isinstance(scores, str):
+        return None
+    if not (scores.is_cuda and scores.device == device):
+        raise ValueError("scores must live on the inputs' device")
+    return scores.to(torch.float64).contiguous()  # (float32 -> float64 is exact: the order is the caller's)
+
+
 def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras1=None, cameras2=None, ransac_opt=None,
                          bundle_opt=None, n_per_pair=None, budgets=None, priors=None, scores=None):
     """Batch that already lives on the GPU (e.g. matcher output): `points2D_*` (B, N, 2) and `depth_*` (B, N) float64 torch
@@ -954,12 +993,8 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
         elif priors.numel() * priors.element_size() != int(depth_1.shape[0]) * _capi.MODEL_DTYPE.itemsize:
             raise ValueError(f"priors must hold {int(depth_1.shape[0])} records of {_capi.MODEL_DTYPE.itemsize} bytes")
     if scores is not None and not (isinstance(scores, str) and scores == PRESORTED):  # (checked before anything touches the device)
-        if not (isinstance(scores, torch.Tensor) and scores.dtype in (torch.float32, torch.float64)):
-            raise ValueError('scores must be a float32 / float64 tensor on the inputs\' device or "presorted"')
-        if tuple(scores.shape) != tuple(depth_1.shape):
-            raise ValueError(f"scores must be {tuple(depth_1.shape)}, one per correspondence, not {tuple(scores.shape)}")
-    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
-    k = kinds[kind] if isinstance(kind, str) else int(kind)
+        _check_resident_scores(scores, depth_1.shape)
+    k = MONODEPTH_KINDS[kind] if isinstance(kind, str) else int(kind)
     x1, x2, d1, d2 = (t.contiguous() for t in (points2D_1, points2D_2, depth_1, depth_2))
     for t in (x1, x2, d1, d2):
         if not (t.is_cuda and t.dtype == torch.float64):
@@ -969,9 +1004,7 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
     B, N = d1.shape
     if x1.shape != (B, N, 2) or x2.shape != (B, N, 2) or d2.shape != (B, N):
         raise ValueError("shapes must be (B, N, 2), (B, N, 2), (B, N), (B, N)")
-    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(x1.device)
-    h = _torch_handle(dev, int(stream.cuda_stream))
+    h = _handle_on(x1.device)
     if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
         n_per_pair = n_per_pair.detach().cpu().numpy()
     cams1 = cams2 = None
@@ -986,11 +1019,7 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
             return h.fetch_budget_results(len(budgets), B), mask
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
         if scores is not None:
-            sc = None
-            if not isinstance(scores, str):
-                if not (scores.is_cuda and scores.device == x1.device):
-                    raise ValueError("scores must live on the inputs' device")
-                sc = scores.to(torch.float64).contiguous()  # (float32 -> float64 is exact: the order is the caller's)
+            sc = _resident_scores(scores, x1.device)
             h.estimate_batch_ranked_device(k, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), None if sc is None else sc.data_ptr(), B, N,
                                            _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt), n_per_pair, cams1, cams2,
                                            mask.data_ptr())
@@ -1012,6 +1041,12 @@ def estimate_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, cameras
 
 
 BASELINE_KINDS = {"relpose_5pt": _capi.RELPOSE_5PT, "shared_focal_6pt": _capi.SHARED_6PT, "fundamental_7pt": _capi.FUNDAMENTAL_7PT}
+
+
+def _baseline_kind(kind):
+    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
+        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
+    return BASELINE_KINDS[kind]
 
 
 def _model_tensor(models, B, device, what):
@@ -1041,11 +1076,9 @@ def _baseline_points_shape(who, points2D_1, points2D_2):
 
 
 def _baseline_torch_args(who, kind, points2D_1, points2D_2, cameras1, cameras2, pp, n_per_pair):
-    """what the baselines' resident entry points check before anything touches the device: (kind id, x1, x2, B, N, device index, n_per_pair, cams1, cams2)"""
+    """what the baselines' resident entry points check before anything touches the device: (kind id, x1, x2, B, N, n_per_pair, cams1, cams2)"""
     import torch
-    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
-        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
-    k = BASELINE_KINDS[kind]
+    k = _baseline_kind(kind)
     B, N = _baseline_points_shape(who, points2D_1, points2D_2)
     x1, x2 = points2D_1.contiguous(), points2D_2.contiguous()
     for t in (x1, x2):
@@ -1053,7 +1086,6 @@ def _baseline_torch_args(who, kind, points2D_1, points2D_2, cameras1, cameras2, 
             raise ValueError(f"{who} needs float64 tensors on the GPU")
         if t.device != x1.device:
             raise ValueError("all tensors must live on the same device")
-    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
     if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
         n_per_pair = n_per_pair.detach().cpu().numpy()
     cams1 = cams2 = None
@@ -1061,7 +1093,7 @@ def _baseline_torch_args(who, kind, points2D_1, points2D_2, cameras1, cameras2, 
         cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
     elif k == _capi.SHARED_6PT:
         cams1 = cams2 = _pp_records(pp, B)[0]
-    return k, x1, x2, B, N, dev, n_per_pair, cams1, cams2
+    return k, x1, x2, B, N, n_per_pair, cams1, cams2
 
 
 def refine_baseline_batch_torch(kind, points2D_1, points2D_2, models, cameras1=None, cameras2=None, pp=None, ransac_opt=None, bundle_opt=None,
@@ -1072,11 +1104,11 @@ def refine_baseline_batch_torch(kind, points2D_1, points2D_2, models, cameras1=N
     no model).  Of ransac_opt only max_epipolar_error is read.  Returns (records, (B, N) uint8 mask tensor on the device, initial: {"score",
     "inliers"} numpy arrays of the models handed in)."""
     import torch
-    k, x1, x2, B, N, dev, n_per_pair, cams1, cams2 = _baseline_torch_args("refine_baseline_batch_torch", kind, points2D_1, points2D_2, cameras1, cameras2, pp,
-                                                                          n_per_pair)
+    k, x1, x2, B, N, n_per_pair, cams1, cams2 = _baseline_torch_args("refine_baseline_batch_torch", kind, points2D_1, points2D_2, cameras1, cameras2, pp,
+                                                                     n_per_pair)
     flags = _stage_flags(stages)
     with torch.cuda.device(x1.device):
-        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        h = _handle_on(x1.device)
         models = _model_tensor(models, B, x1.device, "models")
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
         score0 = torch.zeros(B, dtype=torch.float64, device=x1.device)
@@ -1096,9 +1128,7 @@ def refine_baseline_batch(kind, points2D_1, points2D_2, models, cameras1=None, c
     BASELINE_KINDS; models: list[CameraPose] (5-point), list[ImagePair] (6-point) or 3 x 3 arrays (7-point), or a MODEL_DTYPE array.  Returns
     (list of the same type, list[info dict] as _refine_info builds them); as_arrays=True: (records, masks, n_per_pair, initial scores, initial
     inlier counts)."""
-    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
-        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
-    k = BASELINE_KINDS[kind]
+    k = _baseline_kind(kind)
     flags = _stage_flags(stages)  # (everything is checked before anything touches the device)
     x1, x2, ns = _stack2(points2D_1, points2D_2)
     B = len(ns)
@@ -1147,9 +1177,7 @@ def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, c
     priors (not with scores): one model per pair as in refine_baseline_batch_torch, a NaN first double meaning none — the search of each pair starts
     from it (include/mdrp_classic_models.h: mdrp_estimate_classic_prior); prior_space 1: the records are in the estimator's normalised coordinates."""
     import torch
-    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
-        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
-    k = BASELINE_KINDS[kind]
+    k = _baseline_kind(kind)
     _no_scores_with(scores, None, priors)
     _check_baseline_options(ransac_opt, scores)
     # (everything down to the handle is checked before anything touches the device)
@@ -1158,13 +1186,10 @@ def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, c
         if scores != PRESORTED:
             raise ValueError(f'scores: the only string is "{PRESORTED}", not {scores!r}')
     elif scores is not None:
-        if not (isinstance(scores, torch.Tensor) and scores.dtype in (torch.float32, torch.float64)):
-            raise ValueError('scores must be a float32 / float64 tensor on the inputs\' device or "presorted"')
-        if tuple(scores.shape) != (B, N):
-            raise ValueError(f"scores must be {(B, N)}, one per correspondence, not {tuple(scores.shape)}")
-    k, x1, x2, B, N, dev, n_per_pair, cams1, cams2 = _baseline_torch_args("estimate_baseline_batch_torch", kind, points2D_1, points2D_2, cameras1, cameras2, pp,
-                                                                          n_per_pair)
-    h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        _check_resident_scores(scores, (B, N))
+    k, x1, x2, B, N, n_per_pair, cams1, cams2 = _baseline_torch_args("estimate_baseline_batch_torch", kind, points2D_1, points2D_2, cameras1, cameras2, pp,
+                                                                     n_per_pair)
+    h = _handle_on(x1.device)
     ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
     with torch.cuda.device(x1.device):
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
@@ -1175,11 +1200,7 @@ def estimate_baseline_batch_torch(kind, points2D_1, points2D_2, cameras1=None, c
         elif scores is None:
             h.estimate_batch_device(k, x1.data_ptr(), x2.data_ptr(), None, None, B, N, ro, bo, n_per_pair, cams1, cams2, mask.data_ptr())
         else:
-            sc = None
-            if not isinstance(scores, str):
-                if not (scores.is_cuda and scores.device == x1.device):
-                    raise ValueError("scores must live on the inputs' device")
-                sc = scores.to(torch.float64).contiguous()  # (float32 -> float64 is exact: the order is the caller's)
+            sc = _resident_scores(scores, x1.device)
             h.estimate_classic_ranked_device(k, x1.data_ptr(), x2.data_ptr(), None if sc is None else sc.data_ptr(), B, N, ro, bo, n_per_pair, cams1, cams2,
                                              mask.data_ptr())
         res = h.fetch_results(B)
@@ -1229,9 +1250,8 @@ def pose_from_fundamental_batch_torch(points2D_1, points2D_2, models, n_per_pair
         raise ValueError(f"inlier_mask: a uint8 ({B}, {N}) tensor on the inputs' device")
     if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
         n_per_pair = n_per_pair.detach().cpu().numpy()
-    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
     with torch.cuda.device(x1.device):
-        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        h = _handle_on(x1.device)
         a, b = _focal_pp_tensor(pp1, B, x1.device, "pp1"), _focal_pp_tensor(pp2, B, x1.device, "pp2")
         models = models.to(x1.device).contiguous()
         mk = None if inlier_mask is None else inlier_mask.contiguous()
@@ -1248,11 +1268,11 @@ def estimate_varying_focal_baseline_batch_torch(points2D_1, points2D_2, pp1=None
     records and its mask, which never leave the device.  Returns (B records of _capi.FOCAL_POSE_DTYPE, the 7-point records, (B, N) uint8 mask tensor)."""
     import torch
     _check_baseline_options(ransac_opt, None)
-    k, x1, x2, B, N, dev, n_per_pair, _, _ = _baseline_torch_args("estimate_varying_focal_baseline_batch_torch", "fundamental_7pt", points2D_1, points2D_2,
-                                                                  None, None, None, n_per_pair)
+    k, x1, x2, B, N, n_per_pair, _, _ = _baseline_torch_args("estimate_varying_focal_baseline_batch_torch", "fundamental_7pt", points2D_1, points2D_2,
+                                                             None, None, None, n_per_pair)
     ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
     with torch.cuda.device(x1.device):
-        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        h = _handle_on(x1.device)
         a, b = _focal_pp_tensor(pp1, B, x1.device, "pp1"), _focal_pp_tensor(pp2, B, x1.device, "pp2")
         mask = torch.zeros((B, N), dtype=torch.uint8, device=x1.device)
         out = torch.zeros((B, _capi.FOCAL_POSE_DTYPE.itemsize), dtype=torch.uint8, device=x1.device)
@@ -1267,53 +1287,125 @@ def estimate_varying_focal_baseline_batch_torch(points2D_1, points2D_2, pp1=None
 # What the reference's callers do in NumPy before the estimator (make_pair.py:96-106, make_video.py:265-275) — gather the matched
 # keypoints, read their depths at the truncated pixel, drop the rows whose depths are both infinite — on the device, so that extractor,
 # matcher and depth-network outputs go in as they are.  mdrp_amd/frontend.py states the semantics in NumPy (include/mdrp.h, ABI 0.6).
-def _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter):
-    """validated mdrp_matches descriptor of torch tensors on one ROCm device -> (descriptor, tensors it points into, B, M, device)"""
+# The pieces the five descriptor builders below are made of.  Each builder calls them in its own order, which is the order its complaints come in: the
+# builders with depth maps complain about placement first, the point builders about types and shapes first.
+def _check_tensors(named):
     import torch
-    if filter not in _capi.FILTERS:
-        raise ValueError(f"filter must be one of {tuple(_capi.FILTERS)}, not {filter!r}")
-    named = {"keypoints1": keypoints1, "keypoints2": keypoints2, "matches": matches, "depth_map1": depth_map1, "depth_map2": depth_map2}
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor on the GPU")
+
+
+def _check_on_gpu(named):
+    """every named value is a torch tensor on the GPU, on the first one's device -> that device"""
+    import torch
     for name, t in named.items():
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f"{name} must be a torch tensor on the GPU")
-        if t.device != keypoints1.device:
+        if t.device != next(iter(named.values())).device:
             raise ValueError("all tensors must live on the same device")
-    dev = keypoints1.device
+    return next(iter(named.values())).device
+
+
+def _float_types():
+    import torch
+    return {torch.float32: _capi.F32, torch.float64: _capi.F64}
+
+
+def _check_float_pair(a, b, what):
+    if a.dtype not in _float_types() or b.dtype != a.dtype:
+        raise ValueError(f"{what} must both be float32 or both float64")
+
+
+def _check_match_dtype(matches):
+    import torch
+    if matches.dtype not in (torch.int32, torch.int64):
+        raise ValueError("matches must be int32 or int64")
+
+
+def _check_keypoint_tables(kp1, kp2):
+    if kp1.dim() != 3 or kp1.shape[2] != 2 or kp2.dim() != 3 or kp2.shape[2] != 2:
+        raise ValueError("keypoints must have shape (B, K, 2) or (K, 2)")
+
+
+def _check_match_rows(matches, B, whose, tables_agree=True):
+    if not tables_agree or matches.dim() != 3 or matches.shape[0] != B or matches.shape[2] != 2:
+        raise ValueError(f"matches must have shape (B, M, 2) with the {whose}' B")
+
+
+def _narrow_matches(matches):
+    import torch
+    return matches.to(torch.int32) if matches.dtype == torch.int64 else matches  # narrowed on the device, on the current stream: no synchronisation
+
+
+def _center(c, B, dev):
+    """an optional principal point, (2,) or (B, 2) -> contiguous float64 (B, 2) tensor on `dev`"""
+    import torch
+    if c is None:
+        return None
+    c = torch.as_tensor(c, dtype=torch.float64).to(dev)
+    if c.numel() == 2:
+        c = c.reshape(1, 2).expand(B, 2)
+    if c.shape != (B, 2):
+        raise ValueError("centers must have shape (B, 2) or (2,)")
+    return c.contiguous()
+
+
+def _per_image(v, dtype, shape, what, dev):
+    """an optional per-image table -> contiguous device tensor of that dtype and shape (uploaded on the current stream when it is on the host)"""
+    import torch
+    if v is None:
+        return None
+    v = (v if isinstance(v, torch.Tensor) else torch.tensor(np.asarray(v))).to(device=dev, dtype=dtype)
+    if what == "centers" and v.numel() == 2:
+        v = v.reshape(1, 2).expand(shape[0], 2)
+    if tuple(v.shape) != shape:
+        raise ValueError(f"{what} must have shape {shape}" + (" or (2,)" if what == "centers" else ""))
+    return v.contiguous()
+
+
+def _pairs_on_host(pairs, dev, need_host_pairs):
+    """(pairs already lives on `dev`?, host pairs or None where they were not asked for and pairs is on the device: no copy back, B)"""
+    import torch
+    on_device = isinstance(pairs, torch.Tensor) and pairs.device == dev
+    if on_device and (pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype.is_floating_point):
+        raise ValueError("pairs must be (B, 2) integer image indices")
+    host_pairs = _host_pairs(pairs) if need_host_pairs or not on_device else None
+    return on_device, host_pairs, pairs.shape[0] if host_pairs is None else len(host_pairs)
+
+
+def _pairs_on_device(pairs, on_device, host_pairs, dev):
+    """the pair table as the descriptors carry it: int32 (B, 2) on `dev` (host_pairs is this call's own copy)"""
+    import torch
+    return pairs.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous() if on_device else torch.from_numpy(host_pairs).to(dev)
+
+
+def _data_ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter):
+    """validated mdrp_matches descriptor of torch tensors on one ROCm device -> (descriptor, tensors it points into, B, M, device)"""
+    if filter not in _capi.FILTERS:
+        raise ValueError(f"filter must be one of {tuple(_capi.FILTERS)}, not {filter!r}")
+    dev = _check_on_gpu({"keypoints1": keypoints1, "keypoints2": keypoints2, "matches": matches, "depth_map1": depth_map1, "depth_map2": depth_map2})
     kp1, kp2 = (t.unsqueeze(0) if t.dim() == 2 else t for t in (keypoints1, keypoints2))
     mt = matches.unsqueeze(0) if matches.dim() == 2 and kp1.shape[0] == 1 else matches
     dm1, dm2 = (t.unsqueeze(0) if t.dim() == 2 and kp1.shape[0] == 1 else t for t in (depth_map1, depth_map2))
-    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
-    if kp1.dtype not in ftypes or kp2.dtype != kp1.dtype:
-        raise ValueError("keypoints must both be float32 or both float64")
-    if dm1.dtype not in ftypes or dm2.dtype != dm1.dtype:
-        raise ValueError("depth maps must both be float32 or both float64")
-    if mt.dtype not in (torch.int32, torch.int64):
-        raise ValueError("matches must be int32 or int64")
-    if kp1.dim() != 3 or kp1.shape[2] != 2 or kp2.dim() != 3 or kp2.shape[2] != 2:
-        raise ValueError("keypoints must have shape (B, K, 2) or (K, 2)")
+    _check_float_pair(kp1, kp2, "keypoints")
+    _check_float_pair(dm1, dm2, "depth maps")
+    _check_match_dtype(mt)
+    _check_keypoint_tables(kp1, kp2)
     B = kp1.shape[0]
-    if kp2.shape[0] != B or mt.dim() != 3 or mt.shape[0] != B or mt.shape[2] != 2:
-        raise ValueError("matches must have shape (B, M, 2) with the keypoints' B")
+    _check_match_rows(mt, B, "keypoints", kp2.shape[0] == B)
     if dm1.dim() != 3 or dm2.dim() != 3 or dm1.shape[0] != B or dm2.shape[0] != B:
         raise ValueError("depth maps must have shape (B, H, W) with the keypoints' B")
-    if mt.dtype == torch.int64:
-        mt = mt.to(torch.int32)  # narrowed on the device, on the current stream: no synchronisation
-    kp1, kp2, mt, dm1, dm2 = (t.contiguous() for t in (kp1, kp2, mt, dm1, dm2))
-
-    def center(c):
-        if c is None:
-            return None
-        c = torch.as_tensor(c, dtype=torch.float64).to(dev)
-        if c.numel() == 2:
-            c = c.reshape(1, 2).expand(B, 2)
-        if c.shape != (B, 2):
-            raise ValueError("centers must have shape (B, 2) or (2,)")
-        return c.contiguous()
-
-    c1, c2 = center(center1), center(center2)
+    kp1, kp2, mt, dm1, dm2 = (t.contiguous() for t in (kp1, kp2, _narrow_matches(mt), dm1, dm2))
+    c1, c2 = _center(center1, B, dev), _center(center2, B, dev)
+    ftypes = _float_types()
     mm = _capi.Matches(kp1.data_ptr(), kp2.data_ptr(), ftypes[kp1.dtype], kp1.shape[1], kp2.shape[1], mt.data_ptr(), mt.shape[1],
                        dm1.data_ptr(), dm2.data_ptr(), ftypes[dm1.dtype], dm1.shape[1], dm1.shape[2], dm2.shape[1], dm2.shape[2],
-                       None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr(), _capi.FILTERS[filter])
+                       _data_ptr(c1), _data_ptr(c2), _capi.FILTERS[filter])
     return mm, (kp1, kp2, mt, dm1, dm2, c1, c2), B, int(mt.shape[1]), dev
 
 
@@ -1348,6 +1440,44 @@ def _score_args(sc):
     return sc.data_ptr(), _capi.F32 if sc.dtype == torch.float32 else _capi.F64, sc
 
 
+def _gather_rows(stem, desc, B, M, dev, ranked, sc):
+    """the gather alone of a Matches ("matches") or ImagePairs ("image_pairs") descriptor on the device's current torch stream: (x1, x2, d1, d2,
+    n_per_pair, slot)"""
+    import torch
+    h = _handle_on(dev)
+    with torch.cuda.device(dev):
+        x1 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        x2 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+        d1 = torch.empty((B, M), dtype=torch.float64, device=dev)
+        d2 = torch.empty((B, M), dtype=torch.float64, device=dev)
+        slot = torch.empty((B, M), dtype=torch.int32, device=dev)
+        out = (x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
+        if ranked:
+            sp, st, sc = _score_args(sc)
+            n = getattr(h, f"gather_{stem}_ranked")(desc, sp, st, B, *out)
+        else:
+            n = getattr(h, f"gather_{stem}")(desc, B, *out)
+    del sc
+    return x1, x2, d1, d2, n, slot
+
+
+def _estimate_rows(stem, k, desc, B, M, dev, ranked, sc, cams1, cams2, ransac_opt, bundle_opt):
+    """front end + estimator of either descriptor with depth maps on the device's current torch stream: (records, match_mask, n_used)"""
+    import torch
+    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
+    h = _handle_on(dev)
+    with torch.cuda.device(dev):
+        match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
+        if ranked:
+            sp, st, sc = _score_args(sc)
+            n_used = getattr(h, f"estimate_{stem}_ranked_device")(k, desc, sp, st, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        else:
+            n_used = getattr(h, f"estimate_{stem}_device")(k, desc, B, ro, bo, cams1, cams2, match_mask.data_ptr())
+        res = h.fetch_results(B)
+    del sc
+    return res, match_mask, n_used
+
+
 def gather_matches_torch(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1=None, center2=None, filter="both_inf", scores=None):
     """The front end alone, on the device's current torch stream.  keypoints (B, K, 2) float32 | float64 (a (K, 2) tensor is B = 1), matches
     (B, M, 2) int32 | int64 with -1 rows as padding, depth maps (B, H, W) float32 | float64 (the two images may differ in size), all on one
@@ -1359,24 +1489,11 @@ def gather_matches_torch(keypoints1, keypoints2, matches, depth_map1, depth_map2
     confidence) — the kept rows come in QUALITY order instead (mdrp_amd/frontend.py rule 6): slot is the rank of every match row,
     the buffers are what estimate_batch_torch(..., scores="presorted") takes.  A score never drops a row.  "presorted": the rows are in quality
     order already, which for the gather alone is no scores at all."""
-    import torch
     ranked, sc = _front_end_scores(scores, matches)
     mm, keep, B, M, dev = _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        x1 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
-        x2 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
-        d1 = torch.empty((B, M), dtype=torch.float64, device=dev)
-        d2 = torch.empty((B, M), dtype=torch.float64, device=dev)
-        slot = torch.empty((B, M), dtype=torch.int32, device=dev)
-        if ranked:
-            sp, st, sc = _score_args(sc)
-            n = h.gather_matches_ranked(mm, sp, st, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
-        else:
-            n = h.gather_matches(mm, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
-    del keep, sc
-    return x1, x2, d1, d2, n, slot
+    out = _gather_rows("matches", mm, B, M, dev, ranked, sc)
+    del keep
+    return out
 
 
 def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, depth_map2, cameras1=None, cameras2=None, ransac_opt=None,
@@ -1390,31 +1507,15 @@ def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, de
     scores (see PRESORTED and gather_matches_torch): one score per match row or "presorted" — the estimate in score order with the progressive
     sampler, bit for bit estimate_batch_torch(scores=the kept rows' scores) on the unranked gather; the gather itself ranks, each kept row is
     written once.  progressive_sampling in ransac_opt may be absent, False or True; without scores it is refused as before."""
-    import torch
     ranked, sc = _front_end_scores(scores, matches)
-    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
-    if isinstance(kind, str) and kind not in kinds:
-        raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
-    k = kinds[kind] if isinstance(kind, str) else int(kind)
-    if k not in kinds.values():
-        raise ValueError("only the monodepth estimators (calibrated, shared_focal, varying_focal) take depth maps")
+    k = _monodepth_kind(kind)
     mm, keep, B, M, dev = _matches_descriptor(keypoints1, keypoints2, matches, depth_map1, depth_map2, center1, center2, filter)
     cams1 = cams2 = None
     if k == _capi.CALIB:
         cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
-    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
-        if ranked:
-            sp, st, sc = _score_args(sc)
-            n_used = h.estimate_matches_ranked_device(k, mm, sp, st, B, ro, bo, cams1, cams2, match_mask.data_ptr())
-        else:
-            n_used = h.estimate_matches_device(k, mm, B, ro, bo, cams1, cams2, match_mask.data_ptr())
-        res = h.fetch_results(B)
-    del keep, sc
-    return res, match_mask, n_used
+    out = _estimate_rows("matches", k, mm, B, M, dev, ranked, sc, cams1, cams2, ransac_opt, bundle_opt)
+    del keep
+    return out
 
 
 # ---- the front end for DENSE matchers (include/mdrp_dense.h, DESIGN.md 7i): a warp and its certainty instead of keypoints and index pairs.  What the
@@ -1423,7 +1524,6 @@ def estimate_matches_torch(kind, keypoints1, keypoints2, matches, depth_map1, de
 def _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, threshold, balanced, expansion, grid, min_count, filter, ranked,
                       center1, center2):
     """validated mdrp_dense_matches descriptor of torch tensors on one ROCm device -> (descriptor, tensors it points into, B, device)"""
-    import torch
     if filter not in _capi.FILTERS:
         raise ValueError(f"filter must be one of {tuple(_capi.FILTERS)}, not {filter!r}")
     if coords not in _capi.DENSE_COORDS:
@@ -1441,18 +1541,11 @@ def _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, 
     if not 0 <= seed < 1 << 64:
         raise ValueError("seed must fit 64 bits (its low 32 bits are used)")
     threshold = float(threshold)
-    named = {"warp": warp, "certainty": certainty, "depth_map1": depth_map1, "depth_map2": depth_map2}
-    for name, t in named.items():
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{name} must be a torch tensor on the GPU")
-        if t.device != warp.device:
-            raise ValueError("all tensors must live on the same device")
-    dev = warp.device
-    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
+    dev = _check_on_gpu({"warp": warp, "certainty": certainty, "depth_map1": depth_map1, "depth_map2": depth_map2})
+    ftypes = _float_types()
     if warp.dtype not in ftypes or certainty.dtype not in ftypes:
         raise ValueError("warp and certainty must be float32 or float64")
-    if depth_map1.dtype not in ftypes or depth_map2.dtype != depth_map1.dtype:
-        raise ValueError("depth maps must both be float32 or both float64")
+    _check_float_pair(depth_map1, depth_map2, "depth maps")
     if warp.dim() not in (3, 4) or warp.shape[-1] != 4:
         raise ValueError("warp must have shape (B, R, 4) or (B, Hc, Wc, 4)")
     B = int(warp.shape[0])
@@ -1464,21 +1557,10 @@ def _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, 
     if depth_map1.dim() != 3 or depth_map2.dim() != 3 or depth_map1.shape[0] != B or depth_map2.shape[0] != B:
         raise ValueError("depth maps must have shape (B, H, W) with the warp's B")
     wp, ct, dm1, dm2 = (t.contiguous() for t in (warp, certainty, depth_map1, depth_map2))
-
-    def center(c):
-        if c is None:
-            return None
-        c = torch.as_tensor(c, dtype=torch.float64).to(dev)
-        if c.numel() == 2:
-            c = c.reshape(1, 2).expand(B, 2)
-        if c.shape != (B, 2):
-            raise ValueError("centers must have shape (B, 2) or (2,)")
-        return c.contiguous()
-
-    c1, c2 = center(center1), center(center2)
+    c1, c2 = _center(center1, B, dev), _center(center2, B, dev)
     desc = _capi.DenseMatches(wp.data_ptr(), ftypes[wp.dtype], R, ct.data_ptr(), ftypes[ct.dtype], _capi.DENSE_COORDS[coords], dm1.data_ptr(), dm2.data_ptr(),
                               ftypes[dm1.dtype], dm1.shape[1], dm1.shape[2], dm2.shape[1], dm2.shape[2], _capi.FILTERS[filter],
-                              None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr(), n, 1 if balanced else 0, expansion, grid,
+                              _data_ptr(c1), _data_ptr(c2), n, 1 if balanced else 0, expansion, grid,
                               min_count, 1 if ranked else 0, seed, threshold, None, None)
     return desc, (wp, ct, dm1, dm2, c1, c2), B, dev
 
@@ -1500,8 +1582,7 @@ def sample_dense_torch(warp, certainty, depth_map1, depth_map2, n=5000, seed=0, 
     desc, keep, B, dev = _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, threshold, balanced, expansion, grid, min_count,
                                            filter, ranked, center1, center2)
     n = desc.n
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    h = _handle_on(dev)
     with torch.cuda.device(dev):
         x1 = torch.empty((B, n, 2), dtype=torch.float64, device=dev)
         x2 = torch.empty((B, n, 2), dtype=torch.float64, device=dev)
@@ -1526,12 +1607,7 @@ def estimate_dense_torch(kind, warp, certainty, depth_map1, depth_map2, cameras1
     Returns (records, record_mask: (B, n) uint8 device tensor - 1 where the sampled record is an inlier -, n_used: numpy int32, rows: (B, n) int32
     device tensor, the warp row of every record, -1 behind the count)."""
     import torch
-    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
-    if isinstance(kind, str) and kind not in kinds:
-        raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
-    k = kinds[kind] if isinstance(kind, str) else int(kind)
-    if k not in kinds.values():
-        raise ValueError("only the monodepth estimators (calibrated, shared_focal, varying_focal) take depth maps")
+    k = _monodepth_kind(kind)
     desc, keep, B, dev = _dense_descriptor(warp, certainty, depth_map1, depth_map2, n, seed, coords, threshold, balanced, expansion, grid, min_count,
                                            filter, ranked, center1, center2)
     n = desc.n
@@ -1539,8 +1615,7 @@ def estimate_dense_torch(kind, warp, certainty, depth_map1, depth_map2, cameras1
     if k == _capi.CALIB:
         cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
     ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    h = _handle_on(dev)
     with torch.cuda.device(dev):
         record_mask = torch.zeros((B, n), dtype=torch.uint8, device=dev)
         rows = torch.empty((B, n), dtype=torch.int32, device=dev)
@@ -1572,52 +1647,25 @@ def _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, size
     import torch
     if filter not in _capi.FILTERS:
         raise ValueError(f"filter must be one of {tuple(_capi.FILTERS)}, not {filter!r}")
-    for name, t in {"keypoints": keypoints, "depth_maps": depth_maps, "matches": matches}.items():
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{name} must be a torch tensor on the GPU")
-        if t.device != keypoints.device:
-            raise ValueError("all tensors must live on the same device")
-    dev = keypoints.device
-    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
+    dev = _check_on_gpu({"keypoints": keypoints, "depth_maps": depth_maps, "matches": matches})
+    ftypes = _float_types()
     if keypoints.dtype not in ftypes or depth_maps.dtype not in ftypes:
         raise ValueError("keypoints and depth maps must be float32 or float64")
-    if matches.dtype not in (torch.int32, torch.int64):
-        raise ValueError("matches must be int32 or int64")
+    _check_match_dtype(matches)
     if keypoints.dim() != 3 or keypoints.shape[2] != 2:
         raise ValueError("keypoints must have shape (I, K, 2)")
     I = keypoints.shape[0]
     if depth_maps.dim() != 3 or depth_maps.shape[0] != I:
         raise ValueError("depth maps must have shape (I, H, W) with the keypoints' I")
-    on_device = isinstance(pairs, torch.Tensor) and pairs.device == dev
-    if on_device and (pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype.is_floating_point):
-        raise ValueError("pairs must be (B, 2) integer image indices")
-    host_pairs = _host_pairs(pairs) if need_host_pairs or not on_device else None
-    B = pairs.shape[0] if host_pairs is None else len(host_pairs)
-    if matches.dim() != 3 or matches.shape[0] != B or matches.shape[2] != 2:
-        raise ValueError("matches must have shape (B, M, 2) with the pairs' B")
-    mt = matches.to(torch.int32) if matches.dtype == torch.int64 else matches  # narrowed on the device, on the current stream: no synchronisation
-    kp, dm, mt = keypoints.contiguous(), depth_maps.contiguous(), mt.contiguous()
-
-    def per_image(v, dtype, shape, what):
-        """an optional per-image table -> contiguous device tensor of that dtype and shape (uploaded on the current stream when it is on the host)"""
-        if v is None:
-            return None
-        v = (v if isinstance(v, torch.Tensor) else torch.tensor(np.asarray(v))).to(device=dev, dtype=dtype)
-        if what == "centers" and v.numel() == 2:
-            v = v.reshape(1, 2).expand(I, 2)
-        if tuple(v.shape) != shape:
-            raise ValueError(f"{what} must have shape {shape}" + (" or (2,)" if what == "centers" else ""))
-        return v.contiguous()
-
-    cs = per_image(centers, torch.float64, (I, 2), "centers")
-    sz = per_image(sizes, torch.int32, (I, 2), "sizes")
-    kc = per_image(kp_counts, torch.int32, (I,), "kp_counts")
-    pr = pairs.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous() if on_device else torch.from_numpy(host_pairs).to(dev)  # (host_pairs is this call's own copy)
-
-    def ptr(t):
-        return None if t is None else t.data_ptr()
-    ip = _capi.ImagePairs(kp.data_ptr(), ftypes[kp.dtype], kp.shape[1], ptr(kc), dm.data_ptr(), ftypes[dm.dtype], dm.shape[1], dm.shape[2], ptr(sz), ptr(cs), I,
-                          pr.data_ptr(), mt.data_ptr(), mt.shape[1], _capi.FILTERS[filter])
+    on_device, host_pairs, B = _pairs_on_host(pairs, dev, need_host_pairs)
+    _check_match_rows(matches, B, "pairs")
+    kp, dm, mt = keypoints.contiguous(), depth_maps.contiguous(), _narrow_matches(matches).contiguous()
+    cs = _per_image(centers, torch.float64, (I, 2), "centers", dev)
+    sz = _per_image(sizes, torch.int32, (I, 2), "sizes", dev)
+    kc = _per_image(kp_counts, torch.int32, (I,), "kp_counts", dev)
+    pr = _pairs_on_device(pairs, on_device, host_pairs, dev)
+    ip = _capi.ImagePairs(kp.data_ptr(), ftypes[kp.dtype], kp.shape[1], _data_ptr(kc), dm.data_ptr(), ftypes[dm.dtype], dm.shape[1], dm.shape[2], _data_ptr(sz),
+                          _data_ptr(cs), I, pr.data_ptr(), mt.data_ptr(), mt.shape[1], _capi.FILTERS[filter])
     return ip, (kp, dm, mt, cs, sz, kc, pr), host_pairs, B, int(mt.shape[1]), I, dev
 
 
@@ -1628,24 +1676,11 @@ def gather_image_pairs_torch(keypoints, depth_maps, pairs, matches, centers=None
     each image's map and table (clamped to H, W and K; None = all); centers (I, 2) or (2,), subtracted in float64.  Returns what
     gather_matches_torch returns, on the device's current torch stream, behind one stream synchronisation (the counts).  scores: as
     gather_matches_torch's, (B, M)."""
-    import torch
     ranked, sc = _front_end_scores(scores, matches)
     ip, keep, _, B, M, _, dev = _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, sizes, kp_counts, filter, False)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        x1 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
-        x2 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
-        d1 = torch.empty((B, M), dtype=torch.float64, device=dev)
-        d2 = torch.empty((B, M), dtype=torch.float64, device=dev)
-        slot = torch.empty((B, M), dtype=torch.int32, device=dev)
-        if ranked:
-            sp, st, sc = _score_args(sc)
-            n = h.gather_image_pairs_ranked(ip, sp, st, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
-        else:
-            n = h.gather_image_pairs(ip, B, x1.data_ptr(), x2.data_ptr(), d1.data_ptr(), d2.data_ptr(), slot.data_ptr())
-    del keep, sc
-    return x1, x2, d1, d2, n, slot
+    out = _gather_rows("image_pairs", ip, B, M, dev, ranked, sc)
+    del keep
+    return out
 
 
 def _pair_cameras(cameras, host_pairs, I):
@@ -1664,84 +1699,36 @@ def estimate_image_pairs_torch(kind, keypoints, depth_maps, pairs, matches, came
     records by pairs on the host.  kind: "calibrated" | "shared_focal" | "varying_focal" (pass centers for the focal estimators).
     Returns (records, match_mask: (B, M) uint8 device tensor, n_used: numpy int32), stream behaviour as estimate_matches_torch.  scores: as
     estimate_matches_torch's, (B, M)."""
-    import torch
     ranked, sc = _front_end_scores(scores, matches)
-    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
-    if isinstance(kind, str) and kind not in kinds:
-        raise ValueError(f"kind must be one of {tuple(kinds)}, not {kind!r}")
-    k = kinds[kind] if isinstance(kind, str) else int(kind)
-    if k not in kinds.values():
-        raise ValueError("only the monodepth estimators (calibrated, shared_focal, varying_focal) take depth maps")
+    k = _monodepth_kind(kind)
     ip, keep, host_pairs, B, M, I, dev = _image_pairs_descriptor(keypoints, depth_maps, pairs, matches, centers, sizes, kp_counts, filter, True)
     cams1 = cams2 = None
     if k == _capi.CALIB:
         cams1, cams2 = _pair_cameras(cameras, host_pairs, I)
-    ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
-        if ranked:
-            sp, st, sc = _score_args(sc)
-            n_used = h.estimate_image_pairs_ranked_device(k, ip, sp, st, B, ro, bo, cams1, cams2, match_mask.data_ptr())
-        else:
-            n_used = h.estimate_image_pairs_device(k, ip, B, ro, bo, cams1, cams2, match_mask.data_ptr())
-        res = h.fetch_results(B)
-    del keep, sc
-    return res, match_mask, n_used
+    out = _estimate_rows("image_pairs", k, ip, B, M, dev, ranked, sc, cams1, cams2, ransac_opt, bundle_opt)
+    del keep
+    return out
 
 
 # ---- the same two front ends for the comparison rows, which have no depths (include/mdrp_classic_frontend.h, DESIGN.md 7g): keypoint tables and index
 # pairs go in, the 5- / 6- / 7-point baselines run on the gathered correspondences.  mdrp_amd/frontend.py gather_point_matches_numpy /
 # gather_point_image_pairs_numpy state the semantics: a row is kept iff its indices address their tables and its four coordinates are finite.
-def _baseline_kind(kind):
-    if not (isinstance(kind, str) and kind in BASELINE_KINDS):
-        raise ValueError(f"kind: one of {sorted(BASELINE_KINDS)}, not {kind!r}")
-    return BASELINE_KINDS[kind]
-
-
 def _point_matches_descriptor(keypoints1, keypoints2, matches, center1, center2):
     """_matches_descriptor without the depth maps: validated mdrp_point_matches descriptor -> (descriptor, tensors it points into, B, M, device)"""
-    import torch
     named = {"keypoints1": keypoints1, "keypoints2": keypoints2, "matches": matches}
-    for name, t in named.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch tensor on the GPU")
+    _check_tensors(named)
     kp1, kp2 = (t.unsqueeze(0) if t.dim() == 2 else t for t in (keypoints1, keypoints2))
     mt = matches.unsqueeze(0) if matches.dim() == 2 and kp1.shape[0] == 1 else matches
-    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
-    if kp1.dtype not in ftypes or kp2.dtype != kp1.dtype:
-        raise ValueError("keypoints must both be float32 or both float64")
-    if mt.dtype not in (torch.int32, torch.int64):
-        raise ValueError("matches must be int32 or int64")
-    if kp1.dim() != 3 or kp1.shape[2] != 2 or kp2.dim() != 3 or kp2.shape[2] != 2:
-        raise ValueError("keypoints must have shape (B, K, 2) or (K, 2)")
+    _check_float_pair(kp1, kp2, "keypoints")
+    _check_match_dtype(mt)
+    _check_keypoint_tables(kp1, kp2)
     B = kp1.shape[0]
-    if kp2.shape[0] != B or mt.dim() != 3 or mt.shape[0] != B or mt.shape[2] != 2:
-        raise ValueError("matches must have shape (B, M, 2) with the keypoints' B")
-    for name, t in named.items():  # (types and shapes first: a caller who mixes both up hears about the tensors themselves)
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a torch tensor on the GPU")
-        if t.device != keypoints1.device:
-            raise ValueError("all tensors must live on the same device")
-    dev = keypoints1.device
-    if mt.dtype == torch.int64:
-        mt = mt.to(torch.int32)  # narrowed on the device, on the current stream: no synchronisation
-    kp1, kp2, mt = (t.contiguous() for t in (kp1, kp2, mt))
-
-    def center(c):
-        if c is None:
-            return None
-        c = torch.as_tensor(c, dtype=torch.float64).to(dev)
-        if c.numel() == 2:
-            c = c.reshape(1, 2).expand(B, 2)
-        if c.shape != (B, 2):
-            raise ValueError("centers must have shape (B, 2) or (2,)")
-        return c.contiguous()
-
-    c1, c2 = center(center1), center(center2)
-    pm = _capi.PointMatches(kp1.data_ptr(), kp2.data_ptr(), ftypes[kp1.dtype], kp1.shape[1], kp2.shape[1], mt.data_ptr(), mt.shape[1],
-                            None if c1 is None else c1.data_ptr(), None if c2 is None else c2.data_ptr())
+    _check_match_rows(mt, B, "keypoints", kp2.shape[0] == B)
+    dev = _check_on_gpu(named)  # (types and shapes first: a caller who mixes both up hears about the tensors themselves)
+    kp1, kp2, mt = (t.contiguous() for t in (kp1, kp2, _narrow_matches(mt)))
+    c1, c2 = _center(center1, B, dev), _center(center2, B, dev)
+    pm = _capi.PointMatches(kp1.data_ptr(), kp2.data_ptr(), _float_types()[kp1.dtype], kp1.shape[1], kp2.shape[1], mt.data_ptr(), mt.shape[1],
+                            _data_ptr(c1), _data_ptr(c2))
     return pm, (kp1, kp2, mt, c1, c2), B, int(mt.shape[1]), dev
 
 
@@ -1750,56 +1737,29 @@ def _point_image_pairs_descriptor(keypoints, pairs, matches, centers, kp_counts,
     pairs or None, B, M, I, device)"""
     import torch
     named = {"keypoints": keypoints, "matches": matches}
-    for name, t in named.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch tensor on the GPU")
+    _check_tensors(named)
     dev = keypoints.device
-    ftypes = {torch.float32: _capi.F32, torch.float64: _capi.F64}
-    if keypoints.dtype not in ftypes:
+    if keypoints.dtype not in _float_types():
         raise ValueError("keypoints must be float32 or float64")
-    if matches.dtype not in (torch.int32, torch.int64):
-        raise ValueError("matches must be int32 or int64")
+    _check_match_dtype(matches)
     if keypoints.dim() != 3 or keypoints.shape[2] != 2:
         raise ValueError("keypoints must have shape (I, K, 2)")
     I = keypoints.shape[0]
-    on_device = isinstance(pairs, torch.Tensor) and pairs.device == dev
-    if on_device and (pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype.is_floating_point):
-        raise ValueError("pairs must be (B, 2) integer image indices")
-    host_pairs = _host_pairs(pairs) if need_host_pairs or not on_device else None
-    B = pairs.shape[0] if host_pairs is None else len(host_pairs)
-    if matches.dim() != 3 or matches.shape[0] != B or matches.shape[2] != 2:
-        raise ValueError("matches must have shape (B, M, 2) with the pairs' B")
-    for name, t in named.items():  # (types and shapes first, as _point_matches_descriptor)
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a torch tensor on the GPU")
-        if t.device != dev:
-            raise ValueError("all tensors must live on the same device")
-    mt = matches.to(torch.int32) if matches.dtype == torch.int64 else matches  # narrowed on the device, on the current stream: no synchronisation
-    kp, mt = keypoints.contiguous(), mt.contiguous()
-
-    def per_image(v, dtype, shape, what):
-        if v is None:
-            return None
-        v = (v if isinstance(v, torch.Tensor) else torch.tensor(np.asarray(v))).to(device=dev, dtype=dtype)
-        if what == "centers" and v.numel() == 2:
-            v = v.reshape(1, 2).expand(I, 2)
-        if tuple(v.shape) != shape:
-            raise ValueError(f"{what} must have shape {shape}" + (" or (2,)" if what == "centers" else ""))
-        return v.contiguous()
-
-    cs = per_image(centers, torch.float64, (I, 2), "centers")
-    kc = per_image(kp_counts, torch.int32, (I,), "kp_counts")
-    pr = pairs.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous() if on_device else torch.from_numpy(host_pairs).to(dev)  # (host_pairs is this call's own copy)
-    pp = _capi.PointImagePairs(kp.data_ptr(), ftypes[kp.dtype], kp.shape[1], None if kc is None else kc.data_ptr(), None if cs is None else cs.data_ptr(), I,
-                               pr.data_ptr(), mt.data_ptr(), mt.shape[1])
+    on_device, host_pairs, B = _pairs_on_host(pairs, dev, need_host_pairs)
+    _check_match_rows(matches, B, "pairs")
+    _check_on_gpu(named)  # (types and shapes first, as _point_matches_descriptor)
+    kp, mt = keypoints.contiguous(), _narrow_matches(matches).contiguous()
+    cs = _per_image(centers, torch.float64, (I, 2), "centers", dev)
+    kc = _per_image(kp_counts, torch.int32, (I,), "kp_counts", dev)
+    pr = _pairs_on_device(pairs, on_device, host_pairs, dev)
+    pp = _capi.PointImagePairs(kp.data_ptr(), _float_types()[kp.dtype], kp.shape[1], _data_ptr(kc), _data_ptr(cs), I, pr.data_ptr(), mt.data_ptr(), mt.shape[1])
     return pp, (kp, mt, cs, kc, pr), host_pairs, B, int(mt.shape[1]), I, dev
 
 
 def _gather_points(desc, B, M, dev, ranked, sc):
     """the gather alone of either descriptor on the device's current torch stream: (x1, x2, n_per_pair, slot)"""
     import torch
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    h = _handle_on(dev)
     with torch.cuda.device(dev):
         x1 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
         x2 = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
@@ -1814,8 +1774,7 @@ def _estimate_points(k, desc, B, M, dev, ranked, sc, cams1, cams2, ransac_opt, b
     """front end + baseline of either descriptor on the device's current torch stream: (records, match_mask, n_used)"""
     import torch
     ro, bo = _capi.ransac_opt_from_dict(ransac_opt), _capi.bundle_opt_from_dict(bundle_opt)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _torch_handle(index, int(torch.cuda.current_stream(dev).cuda_stream))
+    h = _handle_on(dev)
     with torch.cuda.device(dev):
         match_mask = torch.zeros((B, M), dtype=torch.uint8, device=dev)
         sp, st, sc = _score_args(sc)
@@ -2008,8 +1967,7 @@ def refine_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, models, c
     written by a torch op just before the call), or a numpy array of _capi.MODEL_DTYPE, which is uploaded on that stream.  Returns (records,
     inlier mask: (B, N) uint8 device tensor, initial: {"score": (B,) float64, "inliers": (B,) int32} numpy arrays of the models handed in)."""
     import torch
-    kinds = {"calibrated": _capi.CALIB, "shared_focal": _capi.SHARED_FOCAL, "varying_focal": _capi.VARYING_FOCAL}
-    k = kinds[kind] if isinstance(kind, str) else int(kind)
+    k = MONODEPTH_KINDS[kind] if isinstance(kind, str) else int(kind)
     flags = _stage_flags(stages)
     x1, x2, d1, d2 = (t.contiguous() for t in (points2D_1, points2D_2, depth_1, depth_2))
     for t in (x1, x2, d1, d2):
@@ -2020,14 +1978,13 @@ def refine_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, models, c
     B, N = d1.shape
     if x1.shape != (B, N, 2) or x2.shape != (B, N, 2) or d2.shape != (B, N):
         raise ValueError("shapes must be (B, N, 2), (B, N, 2), (B, N), (B, N)")
-    dev = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
     if n_per_pair is not None and isinstance(n_per_pair, torch.Tensor):
         n_per_pair = n_per_pair.detach().cpu().numpy()
     cams1 = cams2 = None
     if k == _capi.CALIB:
         cams1, cams2 = _camera_records(cameras1, B), _camera_records(cameras2, B)
     with torch.cuda.device(x1.device):
-        h = _torch_handle(dev, int(torch.cuda.current_stream(x1.device).cuda_stream))
+        h = _handle_on(x1.device)
         if isinstance(models, np.ndarray):
             models = torch.from_numpy(np.ascontiguousarray(models, dtype=_capi.MODEL_DTYPE).reshape(-1).view(np.uint8).copy()).to(x1.device)
         if not (isinstance(models, torch.Tensor) and models.is_cuda and models.device == x1.device and models.dtype in (torch.uint8, torch.float64)):
