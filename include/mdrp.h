@@ -360,6 +360,58 @@ int mdrp_front_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
                       double sq_threshold, uint64_t rec_cnt, double rec_score, int pick, double *scores, int32_t *counts, int32_t *left_at,
                       int32_t *info);
 
+/* The stages IN FRONT of the sweeps, as the scheduler runs them for a batch (within ABI 0.6: a new symbol only): plan and scratch of one pass, the
+ * per-call parameters, k_prep / kc_prep, then for each chunk of the caller's list, in order, the sample tables (the first two drawn ahead beside the
+ * prep where the super-chunk is pipelined, as in an estimate) and the minimal solver of the whole batch — through the functions an estimate calls,
+ * and nothing behind the solver.  One super-chunk at iteration 0; MDRP_SAMPLE_THREADS, MDRP_SOLVE_RESIDENT, MDRP_LO_OVERLAP and MDRP_CHUNKS (which only
+ * sizes the 5-point solver's first-chunk scratch here) act as on an estimate.
+ * Before the first launch the records, the fragments, the slot tables, both sample tables and both tag lists are filled with the byte MDRP_FRONT_FILL; the sample table and tag
+ * list of a chunk that is not drawn ahead are filled again in front of it.  What no kernel writes keeps the pattern.
+ *   kind 0..5, cameras, depths and options as mdrp_estimate_batch takes them (host memory); ropt->monodepth_estimate_shift selects the shift solver
+ *   chunk_lens [n_chunks]   1 to 8 chunks of >= 1 iterations; super_len = their sum; chunk c starts at iteration off_c = the sum of those before it
+ *   slot_iters              iterations per pair the slot outputs hold: super_len <= slot_iters <= the pass's capacity (sched::chunk_capacity of the options)
+ * with K = the sample size (3, 5, 6, 7), MPS = the model slots per sample (4, 12, 16, 4), G = ceil(n_max / 16), S = slot_iters * MPS:
+ *   pts [batch][n_max][6], dep [batch][n_max][2] (monodepth kinds; NULL otherwise), rfrag [batch][G][64][4] u32, states [batch]: behind the prep
+ *   table_of_pair [batch], table_n [batch] (the first *n_tables entries)
+ *   samples [batch][super_len][K]    table t's chunk c at [t][off_c]: the chunks of a table side by side (rows from *n_tables on are not written)
+ *   slot_inl [n_chunks][batch][S]    the slot states behind each chunk's solver;  models [batch][S]: behind the last
+ *   tags [n_chunks][batch][S]        the chunk's tag list: pair p's first model_count[c][p][0] entries are its live slots, in no defined order
+ *   model_count [n_chunks][batch][2]
+ * MDRP_ERR_INVALID before any device work: what mdrp_estimate_batch refuses; batch or n_max < 1; a NULL output; no chunk, more than 8, a length < 1;
+ * slot_iters outside its range; for MDRP_RELPOSE_5PT with several chunks, a first chunk longer than the pass's first-chunk Reduce5 region.
+ * tests/test_gpu_front_stages.py pins every stage to tests/front_stages_ref.py. */
+#define MDRP_FRONT_FILL 0xA5
+typedef struct { /* what k_prep / kc_prep leave of a pair (field for field the kernels' pair state) */
+    int32_t n, table, active, n_triggers;
+    double eps, sq_thr, scale_reproj, lo_loss_scale, final_loss_scale, norm;
+    double box[4], cen[4];
+    uint64_t best_min_cnt;
+    double best_min_score;
+    uint64_t dyn_max_iter, iterations, refinements, num_inliers;
+    double inlier_ratio, model_score;
+    mdrp_model best;
+} mdrp_front_state;
+typedef struct {
+    /* in */
+    int32_t kind, batch, n_max, n_chunks;
+    int32_t slot_iters, pad_;
+    const double *x1, *x2, *d1, *d2;
+    const int32_t *n_per_pair;       /* [batch] or NULL */
+    const mdrp_camera *cam1, *cam2;
+    const int32_t *chunk_lens;
+    /* out */
+    double *pts, *dep;
+    uint32_t *rfrag;
+    mdrp_front_state *states;
+    int32_t *table_of_pair, *table_n, *n_tables;
+    uint32_t *samples;
+    int32_t *slot_inl;
+    mdrp_model *models;
+    uint32_t *tags;
+    int32_t *model_count;
+} mdrp_front_run;
+int mdrp_front_stages(mdrp_handle *h, const mdrp_ransac_opt *ropt, const mdrp_bundle_opt *bopt, mdrp_front_run *io);
+
 /* Hybrid LM refinement of `count` models, each over the correspondences of ONE pair (refine_monodepth_*relpose
  * @0x261030/@0x2592e0/@0x260fa0).  Host memory.  models in/out.  For MDRP_RELPOSE_5PT / MDRP_FUNDAMENTAL_7PT: the Sampson-only
  * refine_relpose @0x258f50 / refine_fundamental @0x2590d0 (d1, d2, scale_reproj, weight_sampson, estimate_shift ignored). */

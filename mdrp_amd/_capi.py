@@ -140,6 +140,28 @@ class FrontTables(C.Structure):
 assert C.sizeof(FrontTables) == 128
 FRONT_PICK_LIMIT = 64  # mdrp_schedule.h sched::FIRST_PICK_LIMIT
 
+# mdrp_front_state / mdrp_front_run (include/mdrp.h): the scheduler's own stages in front of the sweeps, on a caller's chunk list
+FRONT_STATE_DTYPE = np.dtype([("n", "i4"), ("table", "i4"), ("active", "i4"), ("n_triggers", "i4"), ("eps", "f8"), ("sq_thr", "f8"), ("scale_reproj", "f8"),
+                              ("lo_loss_scale", "f8"), ("final_loss_scale", "f8"), ("norm", "f8"), ("box", "f8", 4), ("cen", "f8", 4), ("best_min_cnt", "u8"),
+                              ("best_min_score", "f8"), ("dyn_max_iter", "u8"), ("iterations", "u8"), ("refinements", "u8"), ("num_inliers", "u8"),
+                              ("inlier_ratio", "f8"), ("model_score", "f8"), ("best", MODEL_DTYPE)])
+FRONT_FILL = 0xA5  # MDRP_FRONT_FILL: the byte every buffer of a front_stages run holds where no kernel wrote
+FRONT_FILL_I32 = int(np.frombuffer(bytes([FRONT_FILL] * 4), dtype=np.int32)[0])
+FRONT_FILL_U32 = int(np.frombuffer(bytes([FRONT_FILL] * 4), dtype=np.uint32)[0])
+SAMPLE_SIZE = {0: 3, 1: 3, 2: 3, 3: 5, 4: 6, 5: 7}    # mdrp_schedule.h sched::sample_size
+MODEL_SLOTS = {0: 4, 1: 4, 2: 4, 3: 12, 4: 16, 5: 4}  # mdrp_schedule.h sched::model_slots
+
+
+class FrontRun(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("batch", C.c_int32), ("n_max", C.c_int32), ("n_chunks", C.c_int32), ("slot_iters", C.c_int32), ("pad_", C.c_int32),
+                ("x1", C.c_void_p), ("x2", C.c_void_p), ("d1", C.c_void_p), ("d2", C.c_void_p), ("n_per_pair", C.c_void_p), ("cam1", C.c_void_p),
+                ("cam2", C.c_void_p), ("chunk_lens", C.c_void_p), ("pts", C.c_void_p), ("dep", C.c_void_p), ("rfrag", C.c_void_p), ("states", C.c_void_p),
+                ("table_of_pair", C.c_void_p), ("table_n", C.c_void_p), ("n_tables", C.c_void_p), ("samples", C.c_void_p), ("slot_inl", C.c_void_p),
+                ("models", C.c_void_p), ("tags", C.c_void_p), ("model_count", C.c_void_p)]
+
+
+assert FRONT_STATE_DTYPE.itemsize == 288 and C.sizeof(FrontRun) == 184
+
 # ---- the prototypes: {header: {symbol: argtypes}}, what load_library() declares and what the EXPORTS* tuples below list.  A new entry point is a row
 # here, a method of Handle on the staging helpers below, and a case in tests/binding_cases.py.
 _i, _p, _u64, _f64 = C.c_int, C.c_void_p, C.c_uint64, C.c_double
@@ -194,7 +216,8 @@ PROTOTYPES = {
         "mdrp_replay_slots": [_p, C.POINTER(RansacOpt), C.POINTER(Replay)],
         "mdrp_front_lists": [_p, C.POINTER(FrontTables)],
         "mdrp_front_models": [_p, _i, _p, _i, _p, _p, _i, _f64, _u64, _f64, _i, _p, _p, _p, _p],
-        "mdrp_estimate_batch_ranked": [_p, _i, _i, *_XD, _p, *_TAB, *_OPT, _p, _p],
+        "mdrp_front_stages": [_p, *_OPT, C.POINTER(FrontRun)],
+        "mdrp_estimate_batch_ranked":[_p, _i, _i, *_XD, _p, *_TAB, *_OPT, _p, _p],
         "mdrp_estimate_batch_ranked_async": [_p, _i, *_XD, _p, *_TAB, *_OPT, _p],
         "mdrp_prosac_samples": [_p, _u64, _i, _u64, _p, _i, _p],
         "mdrp_rank_scores": [_p, _i, _p, _i, _i, _p, _p],
@@ -981,6 +1004,39 @@ class Handle:
         _check(self._lib, fn(self._h, int(kind), _ptr(models), len(models), _ptr(x1), _ptr(x2), len(x1), float(sq_threshold),
                              int(rec_cnt), score, int(pick), _ptr(scores), _ptr(counts), _ptr(left_at), _ptr(info)))
         return scores, counts, left_at, info
+
+    def front_stages(self, kind, x1, x2, d1, d2, ropt, bopt, chunk_lens, n_per_pair=None, cam1=None, cam2=None, slot_iters=None):
+        """the scheduler's own stages in front of the sweeps (mdrp_front_stages): plan, parameters, k_prep / kc_prep, then the sample tables and the
+        minimal solver of every chunk of `chunk_lens`, in order.  slot_iters: iterations per pair the slot outputs hold (None: the chunks' sum).
+        Returns dict(pts (B, N, 6), dep (B, N, 2) or None, rfrag (B, ceil(N / 16), 64, 4) uint32, states FRONT_STATE_DTYPE (B,), table_of_pair (B,),
+        table_n (n_tables,), samples (n_tables, super_len, K), slot_inl (n_chunks, B, slot_iters, MPS), models (B, slot_iters, MPS),
+        tags (n_chunks, B, slot_iters * MPS), model_count (n_chunks, B, 2), chunk_off (n_chunks,)); what no kernel wrote holds FRONT_FILL bytes"""
+        fn = _fn(self._lib, "mdrp_front_stages")
+        x1, x2, d1, d2, B, N = _host_batch(x1, x2, d1, d2, "none" if kind >= RELPOSE_5PT else "optional")
+        npp, c1, c2 = _tables(n_per_pair, cam1, cam2)
+        lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
+        K, mps, nc, total = SAMPLE_SIZE.get(kind, 3), MODEL_SLOTS.get(kind, 4), len(lens), int(lens.sum())
+        iters = total if slot_iters is None else int(slot_iters)
+        S = max(iters, 0) * mps
+
+        def filled(shape, dtype):
+            a = np.empty(shape, dtype=dtype)
+            a.view(np.uint8).fill(FRONT_FILL)
+            return a
+        pts, dep = filled((B, N, 6), np.float64), filled((B, N, 2), np.float64) if kind < RELPOSE_5PT else None
+        rfrag, states = filled((B, (N + 15) // 16, 64, 4), np.uint32), filled(B, FRONT_STATE_DTYPE)
+        table_of, table_n, n_tables = filled(B, np.int32), filled(B, np.int32), np.zeros(1, dtype=np.int32)
+        samples = filled((B, max(total, 0), K), np.uint32)
+        slot_inl, models = filled((nc, B, S), np.int32), filled((B, S), MODEL_DTYPE)
+        tags, model_count = filled((nc, B, S), np.uint32), filled((nc, B, 2), np.int32)
+        io = FrontRun(int(kind), B, N, nc, iters, 0, _ptr(x1), _ptr(x2), _ptr(d1), _ptr(d2), _ptr(npp), _ptr(c1), _ptr(c2), _ptr(lens), _ptr(pts), _ptr(dep),
+                      _ptr(rfrag), _ptr(states), _ptr(table_of), _ptr(table_n), _ptr(n_tables), _ptr(samples), _ptr(slot_inl), _ptr(models), _ptr(tags),
+                      _ptr(model_count))
+        _check(self._lib, fn(self._h, C.byref(ropt), C.byref(bopt), C.byref(io)))
+        nt = int(n_tables[0])
+        return dict(pts=pts, dep=dep, rfrag=rfrag, states=states, table_of_pair=table_of, table_n=table_n[:nt], samples=samples[:nt],
+                    slot_inl=slot_inl.reshape(nc, B, iters, mps), models=models.reshape(B, iters, mps), tags=tags, model_count=model_count,
+                    chunk_off=np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64))
 
     def score_models_device(self, kind, models_ptr, num_models, x1_ptr, x2_ptr, n, sq_threshold, scores_ptr, counts_ptr):
         _check(self._lib, self._lib.mdrp_score_models(self._h, int(kind), MEM_DEVICE, _dev(models_ptr), int(num_models), _dev(x1_ptr), _dev(x2_ptr), int(n),

@@ -612,6 +612,11 @@ struct Pass : PassIn {
 
     // sample tables, leading chunks and scratch of the pass
     int plan_and_allocate() {
+        plan();
+        return allocate();
+    }
+    // ... the decisions alone: nothing is allocated or issued (mdrp_front_stages refuses a chunk list against them before any device work)
+    void plan() {
         sched::group_tables(n_host, batch, table_of, tab_n);
         n_tables = (int)tab_n.size();
         certain = sched::certain_iterations(ro->max_iterations, ro->min_iterations);
@@ -622,6 +627,8 @@ struct Pass : PassIn {
         }
         if (!chunks_set) lead = sched::default_lead(kind, certain, kind <= MDRP_VARYING_FOCAL ? h->seen_wish[kind] : -1.0);
         sz = pass_scratch(h, kind, batch, n_max, n_tables, chunk_cap, lead.first(), n_bud);
+    }
+    int allocate() {
         for (const auto &b : sz.bufs) {
             if (int rc = b.first->ensure(b.second)) return rc; // (0 bytes: nothing to allocate)
             // the small per-call inputs travel as one block (six pageable copies cost ~60 us of an idle GPU in front of k_prep)
@@ -710,7 +717,11 @@ struct Pass : PassIn {
 
     // the chunks of the super-chunk at it0, its cleared counters, and whether it is pipelined over the streams and ends with the fused tail
     int begin_super_chunk(uint64_t max_needed) {
-        lay = sched::super_chunk_layout(it0, certain, chunk_cap, lead, max_needed, ro->max_iterations);
+        return begin_super_chunk(sched::super_chunk_layout(it0, certain, chunk_cap, lead, max_needed, ro->max_iterations));
+    }
+    // ... with the chunks given (mdrp_front_stages: a caller's chunk list)
+    int begin_super_chunk(const sched::Layout &layout) {
+        lay = layout;
         if (it0 == 0) h->first_chunk = (int64_t)lay.lens[0];
         rp.chunk_start = it0; rp.super_len = (int)lay.super_len;
         HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
@@ -2359,6 +2370,113 @@ int mdrp_front_lists(mdrp_handle *h, mdrp_front_tables *io) {
     HIPCHK(hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     *io->evals = ev;
+    return MDRP_OK;
+}
+
+// The front of a pass up to and including each chunk's solver, stage for stage what run_pass issues for device-resident inputs: Pass::plan / allocate,
+// upload_params, prep, begin_super_chunk on the caller's chunks, presample where the super-chunk is pipelined, then Pass::solve on view(c, 0, batch) chunk
+// by chunk on the main stream.  Between the stages the handle's buffers are only filled with MDRP_FRONT_FILL and read back.
+static_assert(sizeof(mdrp_front_state) == sizeof(PairState) && offsetof(mdrp_front_state, norm) == offsetof(PairState, norm) &&
+                  offsetof(mdrp_front_state, cen) == offsetof(PairState, cen) && offsetof(mdrp_front_state, dyn_max_iter) == offsetof(PairState, dyn_max_iter) &&
+                  offsetof(mdrp_front_state, best) == offsetof(PairState, best),
+              "mdrp_front_state mirrors PairState");
+int mdrp_front_stages(mdrp_handle *h, const mdrp_ransac_opt *ro, const mdrp_bundle_opt *bo, mdrp_front_run *io) {
+    if (!h || !io) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    EstimateCall c = call_of(io->kind, io->x1, io->x2, io->d1, io->d2, io->batch, io->n_max, io->n_per_pair, io->cam1, io->cam2, ro, bo);
+    if (int rc = estimate_refusals(h, c)) return rc;
+    const int kind = io->kind, batch = io->batch, n_max = io->n_max, n_chunks = io->n_chunks;
+    const bool mono = kind <= MDRP_VARYING_FOCAL;
+    if (!mono) c.d1 = c.d2 = nullptr; // (a baseline takes no depths)
+    const char *why = nullptr;
+    long long super_ll = 0;
+    if (batch < 1 || n_max < 1 || !io->x1 || !io->x2) why = "front_stages: batch >= 1, n_max >= 1 and the correspondences";
+    else if (n_chunks < 1 || n_chunks > sched::NC_MAX || !io->chunk_lens) why = "front_stages: 1 to 8 chunks";
+    else if (!io->pts || (mono && !io->dep) || !io->rfrag || !io->states || !io->table_of_pair || !io->table_n || !io->n_tables || !io->samples ||
+             !io->slot_inl || !io->models || !io->tags || !io->model_count)
+        why = "front_stages: a NULL output";
+    else why = n_per_pair_out_of_range(io->n_per_pair, batch, n_max);
+    for (int k = 0; !why && k < n_chunks; ++k) { if (io->chunk_lens[k] < 1) why = "front_stages: a chunk length < 1"; super_ll += io->chunk_lens[k]; }
+    const int chunk_cap = why ? 0 : sched::chunk_capacity(ro->max_iterations, ro->min_iterations);
+    if (!why && (super_ll > chunk_cap || io->slot_iters < super_ll || io->slot_iters > chunk_cap))
+        why = "front_stages: the chunks and slot_iters must fit the pass's capacity (sched::chunk_capacity), slot_iters >= the sum of the chunks";
+    if (why) { g_err = why; return MDRP_ERR_INVALID; }
+    std::vector<int32_t> n_host(batch);
+    for (int i = 0; i < batch; ++i) n_host[i] = io->n_per_pair ? io->n_per_pair[i] : n_max;
+    sched::Layout lay;
+    lay.n_chunks = n_chunks;
+    for (int k = 0; k < n_chunks; ++k) { lay.lens[k] = (uint64_t)io->chunk_lens[k]; lay.super_len += lay.lens[k]; }
+    for (int k = 1; k < n_chunks; ++k) lay.offs[k] = lay.offs[k - 1] + (int)lay.lens[k - 1];
+    const int super_len = (int)super_ll;
+
+    MDRP_ENTER(h);
+    Pass p(h, pass_in(h, c, 0, batch, n_host.data(), chunk_cap, nullptr, nullptr, nullptr));
+    p.plan();
+    // what Pass::solve would refuse in the middle of the run
+    if (kind == MDRP_RELPOSE_5PT && n_chunks > 1 && (lay.lens[0] + 63) / 64 > p.sz.red5_first_blocks) {
+        g_err = "front_stages: 5-point first chunk longer than its Reduce5 region"; return MDRP_ERR_INVALID;
+    }
+    hipStream_t s = p.s;
+    int rc;
+    h->ev_used = 0;
+    if ((rc = stage_host_call(h, c, nullptr, nullptr))) return rc;
+    p.x1 = c.x1; p.x2 = c.x2; p.d1 = c.d1; p.d2 = c.d2;
+    if ((rc = p.allocate()) || (rc = p.upload_params())) return rc;
+    const size_t b = (size_t)batch, slots = b * p.rp.slot_stride, mps = (size_t)p.mps, ssz = (size_t)p.ssz;
+    const size_t smp_words = ssz * p.n_tables * chunk_cap;
+    const size_t np = b * n_max, frag_words = b * p.groups_max * 64 * 4;
+    HIPCHK(hipMemsetAsync(h->pts.p, MDRP_FRONT_FILL, sizeof(double) * PT_STRIDE * np, s));
+    if (mono) HIPCHK(hipMemsetAsync(h->dep.p, MDRP_FRONT_FILL, sizeof(double) * 2 * np, s));
+    HIPCHK(hipMemsetAsync(h->rfrag.p, MDRP_FRONT_FILL, sizeof(uint32_t) * frag_words, s));
+    HIPCHK(hipMemsetAsync(h->models.p, MDRP_FRONT_FILL, sizeof(Model) * slots, s));
+    HIPCHK(hipMemsetAsync(h->slot_inl.p, MDRP_FRONT_FILL, sizeof(int32_t) * slots, s));
+    for (int q = 0; q < 2; ++q) {
+        HIPCHK(hipMemsetAsync(h->samples[q].p, MDRP_FRONT_FILL, sizeof(uint32_t) * smp_words, s));
+        HIPCHK(hipMemsetAsync(h->tags[q].p, MDRP_FRONT_FILL, sizeof(uint32_t) * slots, s));
+    }
+    HIPCHK(hipEventRecord(h->ev_tables, s));
+    p.prep(0, batch, s);
+    HIPCHK(hipGetLastError());
+    // ---- behind the prep
+    std::vector<PairState> st_host(b);
+    HIPCHK(hipMemcpyAsync(io->pts, h->pts.p, sizeof(double) * PT_STRIDE * np, hipMemcpyDeviceToHost, s));
+    if (mono) HIPCHK(hipMemcpyAsync(io->dep, h->dep.p, sizeof(double) * 2 * np, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->rfrag, h->rfrag.p, sizeof(uint32_t) * frag_words, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(st_host.data(), h->st.p, sizeof(PairState) * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::memcpy(io->states, st_host.data(), sizeof(PairState) * b);
+    std::memcpy(io->table_of_pair, p.table_of.data(), sizeof(int32_t) * b);
+    std::memcpy(io->table_n, p.tab_n.data(), sizeof(int32_t) * p.n_tables);
+    *io->n_tables = p.n_tables;
+    // ---- the chunks
+    if ((rc = p.begin_super_chunk(lay))) return rc;
+    if (p.piped && (rc = p.presample())) return rc;
+    const size_t out_slots = (size_t)io->slot_iters * mps;
+    std::vector<uint32_t> smp_host(smp_words), tags_host(slots);
+    std::vector<int32_t> inl_host(slots);
+    for (int k = 0; k < n_chunks; ++k) {
+        const ChunkView v = p.view(k, 0, batch);
+        const size_t len = (size_t)lay.lens[k];
+        if (!(k < 2 && p.presampled[k])) HIPCHK(hipMemsetAsync(v.samples, MDRP_FRONT_FILL, sizeof(uint32_t) * smp_words, s));
+        if (k >= 2) HIPCHK(hipMemsetAsync(v.tags, MDRP_FRONT_FILL, sizeof(uint32_t) * slots, s));
+        if ((rc = p.solve(v, s))) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(smp_host.data(), v.samples, sizeof(uint32_t) * ssz * p.n_tables * len, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(tags_host.data(), v.tags, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(inl_host.data(), v.slot_inl, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(io->model_count + 2 * b * k, v.model_count, sizeof(int32_t) * 2 * b, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int t = 0; t < p.n_tables; ++t)
+            std::memcpy(io->samples + ((size_t)t * super_len + lay.offs[k]) * ssz, smp_host.data() + (size_t)t * len * ssz, sizeof(uint32_t) * len * ssz);
+        for (size_t q = 0; q < b; ++q) {
+            std::memcpy(io->tags + (b * k + q) * out_slots, tags_host.data() + q * p.rp.slot_stride, sizeof(uint32_t) * out_slots);
+            std::memcpy(io->slot_inl + (b * k + q) * out_slots, inl_host.data() + q * p.rp.slot_stride, sizeof(int32_t) * out_slots);
+        }
+    }
+    std::vector<Model> models_host(slots);
+    HIPCHK(hipMemcpyAsync(models_host.data(), h->models.p, sizeof(Model) * slots, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (hipStream_t st : {(hipStream_t)h->aux_stream, (hipStream_t)h->aux_stream2}) HIPCHK(hipStreamSynchronize(st));
+    for (size_t q = 0; q < b; ++q) std::memcpy(io->models + q * out_slots, models_host.data() + q * p.rp.slot_stride, sizeof(Model) * out_slots);
     return MDRP_OK;
 }
 

@@ -71,7 +71,8 @@ struct PairState {
     double final_loss_scale; // focal estimators: user bundle loss_scale, normalised; calibrated: half the normalised epipolar threshold (k_prep)
     double norm;        // un-normalisation factor of the focals (1 for calibrated)
     double box[4];      // max |x1.x|, |x1.y|, |x2.x|, |x2.y| of the normalised correspondences (k_score's denominator bound)
-    double cen[4];      // centroids subtracted by the 7-point baseline's normalisation (c1.x, c1.y, c2.x, c2.y); 0 otherwise
+    double cen[4];      // what the baselines' normalisation subtracted (c1.x, c1.y, c2.x, c2.y): the cameras' principal points (5-point), the caller's (6-point),
+                        // the centroids (7-point); 0 for the monodepth estimators
     uint64_t best_min_cnt;
     double best_min_score;
     uint64_t dyn_max_iter;

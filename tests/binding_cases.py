@@ -316,6 +316,8 @@ _front = lambda env: ([N, N], [1.0, 2.0], [1, 0], [np.array([1, 2], np.uint32), 
                       env.arr("slot_inl", np.ones((B, 3), np.int32)))
 case("front_lists")(lambda env: (_front(env), {}))
 case("front_lists[fill]")(lambda env: (_front(env), {"fill": {"tags_pick": 7, "rest_count": -1}}))
+case("front_stages")(lambda env: ((_capi.CALIB, *points(env), *depths(env), *opts(), env.arr("lens", np.array([2, 3], np.int32))), tables(env)))
+case("front_stages[no depths]")(lambda env: ((_capi.SHARED_6PT, *points(env), None, None, *opts(), [4]), {"cam1": cameras(env)["cam1"], "slot_iters": 6}))
 
 # ---------------------------------------------------------------------------------------------------- refusals that need no library
 REFUSALS = []  # (id, Handle method, build(env) -> (args, kwargs)): the exception's type and message are pinned, and that nothing was called
@@ -365,7 +367,7 @@ MISSING = {"mdrp_estimate_batch_budgets": "estimate_batch_budgets[kind0]", "mdrp
            "mdrp_estimate_image_pairs_async": "estimate_image_pairs_device[absent]", "mdrp_gather_matches_ranked": "gather_matches_ranked[absent]",
            "mdrp_gather_point_image_pairs_ranked": "gather_points[image_pairs, ranked=True, absent]", "mdrp_pose_from_fundamental": "pose_from_fundamental",
            "mdrp_estimate_dense_async": "estimate_dense_device[absent]", "mdrp_retire_models": "retire_models", "mdrp_replay_slots": "replay_slots",
-           "mdrp_front_lists": "front_lists", "mdrp_front_models": "front_models", "mdrp_solver_residency": "solver_residency"}
+           "mdrp_front_lists": "front_lists", "mdrp_front_models": "front_models", "mdrp_front_stages": "front_stages", "mdrp_solver_residency": "solver_residency"}
 
 
 # ---------------------------------------------------------------------------------------------------- running them

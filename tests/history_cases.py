@@ -592,6 +592,24 @@ def _run_front_lists(h, capi, d):
             r["pick_count"], r["rest_count"], r["surv_count"], np.array([r["evals"]], dtype=np.uint64))
 
 
+def _front_stages_case():
+    """a ragged calibrated batch (a pair below the sample size, an empty pair) and two chunks, the second ending inside a wavefront"""
+    d = estimator_batch(0, False, 5, 130, 9400)
+    return dict(d, lens=np.array([64, 41], dtype=np.int32))
+
+
+def _run_front_stages(h, capi, d):
+    ro = capi.ransac_opt_from_dict(dict(RO, max_iterations=110, min_iterations=110, seed=5))
+    r = h.front_stages(0, d["x1"], d["x2"], d["d1"], d["d2"], ro, capi.bundle_opt_from_dict({"loss_type": LOSS}), d["lens"], n_per_pair=d["n"],
+                       cam1=cameras(capi, 0, 5), cam2=cameras(capi, 0, 5), slot_iters=110)
+    tags = r["tags"].copy()  # (the order of a tag list is not defined: the live entries sorted, the untouched rest as it is)
+    for c in range(tags.shape[0]):
+        for p in range(tags.shape[1]):
+            k = max(0, min(int(r["model_count"][c, p, 0]), tags.shape[2]))
+            tags[c, p, :k] = np.sort(tags[c, p, :k])
+    return (r["pts"], r["dep"], r["rfrag"], r["states"], r["table_of_pair"], r["table_n"], r["samples"], r["slot_inl"], r["models"], tags, r["model_count"])
+
+
 def _refine_problem():
     import from_models_cases as fc
     p = synth.make_pair(9107, 130, noise_px=1.0, depth_noise=0.05, outlier_frac=0.7)
@@ -632,6 +650,9 @@ def _units():
         Unit("front_models", ["mdrp_front_models"], _retirement_pair,
              lambda h, capi, d: h.front_models(1, M(capi, d), d["x1"], d["x2"], d["thr"], 48, d["rec_cnt"], d["rec_score"]),
              ("scores", "counts", "left at", "info"), mods),
+        Unit("front_stages", ["mdrp_front_stages"], _front_stages_case, _run_front_stages,
+             ("pts", "dep", "rfrag", "states", "table_of_pair", "table_n", "samples", "slot_inl", "models", "tags (sorted)", "model_count"),
+             lambda d: [d["x1"], d["x2"], d["d1"], d["d2"], d["n"], d["lens"]]),
         Unit("refine_models", ["mdrp_refine_models"], _refine_problem,
              lambda h, capi, d: h.refine_models(0, M(capi, d), d["x1"], d["x2"], d["d1"], d["d2"], 1 / 64.0, 1.0, capi.bundle_opt_from_dict({"loss_type": LOSS})),
              ("models", "costs"), lambda d: [d["x1"], d["x2"], d["d1"], d["d2"], d["models"]]),
