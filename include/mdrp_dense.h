@@ -95,4 +95,6 @@ int mdrp_estimate_dense_async(mdrp_handle *h, int kind, const mdrp_dense_matches
 #ifdef __cplusplus
 }
 #endif
+
+#include "mdrp_reconstruct.h" /* the back end: fused two-view point clouds from models and depth maps; it subsamples with D4's hash */
 #endif

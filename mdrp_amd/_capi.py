@@ -19,6 +19,8 @@ SOLVER_P3P, SOLVER_SHIFT, SOLVER_SHARED, SOLVER_VARYING = 0, 1, 2, 3
 
 DENSE_COORDS = {"normalized": 0, "pixel": 1}  # mdrp_dense_matches.coords (include/mdrp_dense.h MDRP_DENSE_*)
 DENSE_MAX_ROWS, DENSE_MAX_STAGE1, DENSE_MAX_N, DENSE_MAX_GRID = 1 << 22, 65536, 16384, 8  # include/mdrp_dense.h MDRP_DENSE_MAX_*
+RECON_KEEP = {"not_inf": 0, "finite": 1}  # mdrp_reconstruct_opt.keep (include/mdrp_reconstruct.h MDRP_KEEP_*)
+RECON_MAX_EXTENT, RECON_ALL = 65536, 0xFFFFFFFF  # include/mdrp_reconstruct.h MDRP_RECON_MAX_EXTENT, MDRP_RECON_ALL
 FOCAL_NO_MODEL, FOCAL_F1_NOT_REAL, FOCAL_F2_NOT_REAL, FOCAL_NO_VOTERS = 1, 2, 4, 8  # include/mdrp_classic_focals.h MDRP_FOCAL_*: mdrp_focal_pose.status
 # include/mdrp.h MDRP_RETIRE_*: flags of mdrp_retire_models
 RETIRE_TWO_PHASE, RETIRE_BOUND, RETIRE_SWEEP_SCORE, RETIRE_SWEEP_SPLIT, RETIRE_SWEEP_WAVE = 1, 2, 0, 4, 8
@@ -96,6 +98,26 @@ class DenseMatches(C.Structure):
                 ("h2", C.c_int32), ("w2", C.c_int32), ("filter", C.c_int32), ("center1", C.c_void_p), ("center2", C.c_void_p), ("n", C.c_int32),
                 ("balanced", C.c_int32), ("expansion", C.c_int32), ("grid", C.c_int32), ("min_count", C.c_int32), ("ranked", C.c_int32),
                 ("seed", C.c_uint64), ("threshold", C.c_double), ("rows_out", C.c_void_p), ("score_out", C.c_void_p)]
+
+
+class DepthPairs(C.Structure):
+    """mdrp_depth_pairs (include/mdrp_reconstruct.h): two depth maps per pair, every pointer in device memory"""
+    _fields_ = [("depth1", C.c_void_p), ("depth2", C.c_void_p), ("depth_type", C.c_int32), ("h1", C.c_int32), ("w1", C.c_int32), ("h2", C.c_int32),
+                ("w2", C.c_int32), ("reserved_", C.c_int32), ("center1", C.c_void_p), ("center2", C.c_void_p)]
+
+
+class DepthImagePairs(C.Structure):
+    """mdrp_depth_image_pairs (include/mdrp_reconstruct.h): one depth map per image, pairs as image indices, every pointer in device memory"""
+    _fields_ = [("depth", C.c_void_p), ("depth_type", C.c_int32), ("h_max", C.c_int32), ("w_max", C.c_int32), ("n_images", C.c_int32),
+                ("size", C.c_void_p), ("center", C.c_void_p), ("pairs", C.c_void_p)]
+
+
+class ReconstructOpt(C.Structure):
+    """mdrp_reconstruct_opt (include/mdrp_reconstruct.h)"""
+    _fields_ = [("keep", C.c_int32), ("thr", C.c_uint32), ("seed", C.c_uint64), ("p_max", C.c_int32), ("reserved_", C.c_int32)]
+
+
+assert C.sizeof(DepthPairs) == 56 and C.sizeof(DepthImagePairs) == 48 and C.sizeof(ReconstructOpt) == 24
 
 
 class Result(C.Structure):
@@ -257,6 +279,10 @@ PROTOTYPES = {
         "mdrp_sample_dense": _gather_args(DenseMatches, 6, False),
         "mdrp_estimate_dense_async": _front_args(DenseMatches, False),
     },
+    "mdrp_reconstruct.h": {  # the back end: fused two-view point clouds from models and depth maps
+        "mdrp_reconstruct_pairs_async": [_p, _i, C.POINTER(DepthPairs), C.POINTER(ReconstructOpt), _i, _p, _i, _p, _p, _p, _p, _p],
+        "mdrp_reconstruct_image_pairs_async": [_p, _i, C.POINTER(DepthImagePairs), C.POINTER(ReconstructOpt), _i, _p, _i, _p, _p, _p, _p, _p],
+    },
 }
 # what each header declares: mdrp.h's own list (with the four symbols that only get a restype), then its extension headers'
 EXPORTS = tuple(PROTOTYPES["mdrp.h"]) + ("mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version")
@@ -265,6 +291,7 @@ EXPORTS_CLASSIC_MODELS = tuple(PROTOTYPES["mdrp_classic_models.h"])
 EXPORTS_CLASSIC_FRONTEND = tuple(PROTOTYPES["mdrp_classic_frontend.h"])
 EXPORTS_CLASSIC_FOCALS = tuple(PROTOTYPES["mdrp_classic_focals.h"])
 EXPORTS_DENSE = tuple(PROTOTYPES["mdrp_dense.h"])
+EXPORTS_RECONSTRUCT = tuple(PROTOTYPES["mdrp_reconstruct.h"])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -522,7 +549,28 @@ def _ensure_hip_runtime():
     raise MdrpError("no HIP runtime (libamdhip64) could be loaded: " + "; ".join(errs))
 
 
-class Handle:
+class _ReconstructCalls:
+    """The back end's two calls (include/mdrp_reconstruct.h), methods of Handle through this base: a DepthPairs / DepthImagePairs descriptor and a
+    ReconstructOpt of device pointers and plain values.  Arguments go to the library as they are: the library checks them."""
+
+    def reconstruct_pairs_device(self, kind, desc, opt, batch, models_ptr, model_stride, points_ptr, pixel_ptr, counts_ptr, cam1=None, cam2=None):
+        """fused two-view point clouds on the handle's stream into the caller's device buffers: points [batch][p_max][3] float32, pixel
+        [batch][p_max] int32, counts [batch][2] int32.  models_ptr: device records model_stride bytes apart (96: models, 136: what
+        copy_results_device wrote); cam1 / cam2: per PAIR, the calibrated kind alone.  Nothing synchronises."""
+        stem = "image_pairs" if isinstance(desc, DepthImagePairs) else "pairs"
+        _, c1, c2 = _tables(None, cam1, cam2)
+        _check(self._lib, _fn(self._lib, f"mdrp_reconstruct_{stem}_async")(self._h, int(kind), C.byref(desc), C.byref(opt), int(batch), _dev(models_ptr),
+                                                                          int(model_stride), _ptr(c1), _ptr(c2), _dev(points_ptr), _dev(pixel_ptr),
+                                                                          _dev(counts_ptr)))
+
+    def reconstruct_image_pairs_device(self, kind, desc, opt, batch, models_ptr, model_stride, points_ptr, pixel_ptr, counts_ptr, cam1=None, cam2=None):
+        """reconstruct_pairs_device for a DepthImagePairs descriptor"""
+        if not isinstance(desc, DepthImagePairs):
+            raise ValueError("reconstruct_image_pairs_device takes a DepthImagePairs descriptor")
+        self.reconstruct_pairs_device(kind, desc, opt, batch, models_ptr, model_stride, points_ptr, pixel_ptr, counts_ptr, cam1, cam2)
+
+
+class Handle(_ReconstructCalls):
     """One handle = one HIP device + one stream + its scratch buffers.  Calls on one handle are serialised inside the
     library; use one handle per host thread for concurrency (default_handle() does).
 

@@ -12,6 +12,7 @@
 #include "mdrp_classic_models.h"
 #include "mdrp_classic_focals.h"
 #include "mdrp_dense.h"
+#include "mdrp_reconstruct.h"
 // MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior, kc_from_model, kc_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -207,6 +208,7 @@ struct mdrp_handle {
     size_t fe_n_host_cap = 0;
     DevBuf fp_nper, fp_in, fp_out;     // focals and pose from F (include/mdrp_classic_focals.h): n per pair | a host call's models, mask and principal points | its records
     DevBuf dn_scratch, dn_score;       // dense front end (include/mdrp_dense.h): the sampler's scratch, carved per call (DenseScratch) | mdrp_estimate_dense_async: the records' certainties
+    DevBuf rc_scratch;                 // back end (include/mdrp_reconstruct.h): tile counts | the pairs' ReconPair | the two camera tables, carved per call
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
     Pinned<Progress> progress_host;
     // sweep timing
@@ -2839,6 +2841,120 @@ int mdrp_estimate_dense_async(mdrp_handle *h, int kind, const mdrp_dense_matches
     if ((rc = estimate_device(h, c))) return rc;
     if (n_used_host && batch > 0) std::memcpy(n_used_host, h->fe_n_host, sizeof(int32_t) * batch);
     return MDRP_OK;
+}
+
+} // extern "C"
+
+// ---- the back end: fused two-view point clouds from models and depth maps (include/mdrp_reconstruct.h; mdrp_reconstruct.h)
+namespace {
+
+static_assert(MDRP_KEEP_NOT_INF == RECON_KEEP_NOT_INF && MDRP_KEEP_FINITE == RECON_KEEP_FINITE && MDRP_RECON_MAX_EXTENT == RECON_MAX_EXTENT &&
+              MDRP_RECON_ALL == RECON_ALL && sizeof(mdrp_model) == RECON_MODEL_BYTES, "values of the header and of the kernels");
+static_assert(sizeof(mdrp_depth_pairs) == 56 && offsetof(mdrp_depth_pairs, center1) == 40 && sizeof(mdrp_depth_image_pairs) == 48 &&
+              offsetof(mdrp_depth_image_pairs, size) == 24 && sizeof(mdrp_reconstruct_opt) == 24 && offsetof(mdrp_reconstruct_opt, p_max) == 16, "descriptor layout");
+static_assert(sizeof(ReconCam) == sizeof(mdrp_camera) && offsetof(ReconCam, params) == offsetof(mdrp_camera, params), "camera layout");
+
+// one call of either entry point: the descriptor flattened (ReconArgs without its tile counts) and everything else the caller handed over
+struct ReconCall {
+    const char *who;
+    ReconArgs a;
+    int batch;
+    const mdrp_camera *cam1, *cam2; // host
+    float *points;
+    int32_t *pixel, *counts;
+};
+
+// what both entry points refuse before any device work (the descriptor's own NULLs are the entry points')
+const char *recon_refusal(const ReconCall &c, const mdrp_reconstruct_opt *o) {
+    const ReconArgs &a = c.a;
+    if (c.batch < 0) return "negative batch";
+    if (a.kind < MDRP_CALIB || a.kind > MDRP_VARYING_FOCAL) return "only the monodepth estimators' models (kind 0..2) have depths to unproject";
+    if (a.kind == MDRP_CALIB && c.batch > 0 && (!c.cam1 || !c.cam2)) return "MDRP_CALIB needs cam1_host and cam2_host, one record per pair";
+    if (a.kind != MDRP_CALIB && (c.cam1 || c.cam2)) return "cameras are MDRP_CALIB's: a focal kind unprojects with the model's focals (pass NULL)";
+    if (a.model_stride < RECON_MODEL_BYTES || a.model_stride % 8 != 0) return "model_stride must be at least 96 and a multiple of 8";
+    if (a.depth_type != MDRP_F32 && a.depth_type != MDRP_F64) return "depth_type must be MDRP_F32 or MDRP_F64";
+    if (o->keep != MDRP_KEEP_NOT_INF && o->keep != MDRP_KEEP_FINITE) return "keep must be MDRP_KEEP_NOT_INF or MDRP_KEEP_FINITE";
+    if (o->thr == 0) return "thr == 0 keeps nothing (1 .. MDRP_RECON_ALL)";
+    if (o->p_max < 0) return "negative p_max";
+    if (a.h1 < 0 || a.w1 < 0 || a.h2 < 0 || a.w2 < 0 || a.n_images < 0) return "negative size";
+    if (a.h1 > MDRP_RECON_MAX_EXTENT || a.w1 > MDRP_RECON_MAX_EXTENT || a.h2 > MDRP_RECON_MAX_EXTENT || a.w2 > MDRP_RECON_MAX_EXTENT)
+        return "extent above MDRP_RECON_MAX_EXTENT (65536)";
+    if ((int64_t)a.h1 * a.w1 > INT32_MAX || (int64_t)a.h2 * a.w2 > INT32_MAX) return "a map of 2^31 pixels or more";
+    if (c.batch == 0) return nullptr;
+    if (!a.models || !c.counts) return "NULL models_dev or counts";
+    if (o->p_max > 0 && (!c.points || !c.pixel)) return "NULL points or pixel";
+    if (((int64_t)a.h1 * a.w1 > 0 && !a.depth1) || ((int64_t)a.h2 * a.w2 > 0 && !a.depth2)) return "NULL depth map";
+    if (a.kind == MDRP_CALIB)
+        for (int i = 0; i < c.batch; ++i)
+            if ((c.cam1[i].model_id | 1) != 1 || (c.cam2[i].model_id | 1) != 1) return "only SIMPLE_PINHOLE (0) and PINHOLE (1) cameras unproject here";
+    return nullptr;
+}
+
+// The three kernels on the handle's stream.  The scratch is one buffer of the handle, carved for this call's sizes; every word of it that a kernel
+// reads was written by this call.
+int reconstruct_device(mdrp_handle *h, ReconCall &c, const mdrp_reconstruct_opt *o) {
+    ReconArgs &a = c.a;
+    a.keep = o->keep; a.thr = o->thr; a.seed = (uint32_t)o->seed; a.p_max = o->p_max;
+    const auto tiles = [](int hh, int ww) { return (int)std::max<int64_t>(1, ((int64_t)hh * ww + RECON_TILE - 1) / RECON_TILE); }; // (a map without pixels: one empty tile)
+    a.nt1 = tiles(a.h1, a.w1); a.nt2 = tiles(a.h2, a.w2); a.nfill = (a.p_max + RECON_TILE - 1) / RECON_TILE;
+    const size_t b = (size_t)c.batch, nt = (size_t)a.nt1 + a.nt2;
+    if (b * (nt + a.nfill) > (size_t)INT32_MAX) { g_err = std::string(c.who) + ": batch * tiles above 2^31 - 1: split the batch"; return MDRP_ERR_INVALID; }
+    if (c.batch == 0) return MDRP_OK;
+    size_t total = 0;
+    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
+    const size_t o_pair = carve(sizeof(ReconPair) * b), o_cam = carve(sizeof(ReconCam) * 2 * b), o_tcnt = carve(sizeof(uint32_t) * b * nt);
+    if (int rc = h->rc_scratch.ensure(total)) return rc;
+    unsigned char *p = h->rc_scratch.as<unsigned char>();
+    hipStream_t s = h->stream;
+    if (a.kind == MDRP_CALIB) { // pageable: the copies have left the caller's tables when hipMemcpyAsync returns
+        HIPCHK(hipMemcpyAsync(p + o_cam, c.cam1, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(p + o_cam + sizeof(ReconCam) * b, c.cam2, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
+        a.cam1 = reinterpret_cast<const ReconCam *>(p + o_cam); a.cam2 = a.cam1 + b;
+    }
+    ReconPair *rp = reinterpret_cast<ReconPair *>(p + o_pair);
+    uint32_t *tcnt = reinterpret_cast<uint32_t *>(p + o_tcnt);
+    hipLaunchKernelGGL(k_recon_count, dim3((unsigned)(b * nt)), dim3(RECON_THREADS), 0, s, a, tcnt);
+    hipLaunchKernelGGL(k_recon_scan, dim3(c.batch), dim3(RECON_THREADS), 0, s, a, tcnt, rp, c.counts);
+    if (a.p_max > 0)
+        hipLaunchKernelGGL(k_recon_emit, dim3((unsigned)(b * (nt + a.nfill))), dim3(RECON_THREADS), 0, s, a, (const uint32_t *)tcnt, (const ReconPair *)rp,
+                           (const int32_t *)c.counts, c.points, c.pixel);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+int reconstruct_call(mdrp_handle *h, ReconCall &c, const mdrp_reconstruct_opt *o) {
+    if (const char *why = recon_refusal(c, o)) { g_err = std::string(c.who) + ": " + why; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    return reconstruct_device(h, c, o);
+}
+
+} // namespace
+
+extern "C" {
+
+int mdrp_reconstruct_pairs_async(mdrp_handle *h, int kind, const mdrp_depth_pairs *dp, const mdrp_reconstruct_opt *opt, int batch, const void *models_dev,
+                                 int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, float *points, int32_t *pixel, int32_t *counts) {
+    if (!h || !dp || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    ReconCall c{"mdrp_reconstruct_pairs_async", {}, batch, cam1, cam2, points, pixel, counts};
+    ReconArgs &a = c.a;
+    a.depth1 = dp->depth1; a.depth2 = dp->depth2; a.center1 = dp->center1; a.center2 = dp->center2;
+    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = dp->depth_type; a.kind = kind;
+    a.h1 = dp->h1; a.w1 = dp->w1; a.h2 = dp->h2; a.w2 = dp->w2;
+    return reconstruct_call(h, c, opt);
+}
+
+int mdrp_reconstruct_image_pairs_async(mdrp_handle *h, int kind, const mdrp_depth_image_pairs *ip, const mdrp_reconstruct_opt *opt, int batch,
+                                       const void *models_dev, int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, float *points,
+                                       int32_t *pixel, int32_t *counts) {
+    if (!h || !ip || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (batch > 0 && !ip->pairs) { g_err = "mdrp_reconstruct_image_pairs_async: NULL pairs"; return MDRP_ERR_INVALID; }
+    ReconCall c{"mdrp_reconstruct_image_pairs_async", {}, batch, cam1, cam2, points, pixel, counts};
+    ReconArgs &a = c.a;
+    a.depth1 = a.depth2 = ip->n_images > 0 ? ip->depth : ip; // (an empty set: no map is read; the pointer only has to pass for one)
+    a.center1 = a.center2 = ip->center; a.size = ip->size; a.pairs = ip->pairs; a.n_images = ip->n_images;
+    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = ip->depth_type; a.kind = kind;
+    a.h1 = a.h2 = ip->h_max; a.w1 = a.w2 = ip->w_max;
+    return reconstruct_call(h, c, opt);
 }
 
 } // extern "C"

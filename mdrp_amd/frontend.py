@@ -35,6 +35,11 @@ hold without d1 and d2.
 (xA, yA, xB, yB) and its certainty instead of keypoints and index pairs.  `sample_dense_numpy` at the end of this module is their definition, rules
 D1-D7 of the header: pixel coordinates, rules 2-4 above as the candidate test, integer weights from the certainty, a stratified draw, a
 density-balanced second draw, the records.  Every quantity that decides a pick is an integer, so the device equals it as bytes.
+
+`poselib.reconstruct_pairs_torch` / `reconstruct_image_pairs_torch` are the BACK end (include/mdrp_reconstruct.h): from the estimators'
+models and the pairs' depth maps to the fused two-view point cloud in camera 2's frame.  `reconstruct_pair_numpy` and `reconstruct_image_pairs_numpy`
+at the end of this module are their definition, rules R1-R7 of the header: the usable-model rule, the pixel order, the integer subsample, the depth
+filter, the unprojection and the transform in float64 with one rounding per arithmetic sign, the rows and their truncation.
 """
 import numpy as np
 
@@ -419,3 +424,187 @@ def pad_dense_pairs(sampled, n):
         m = cnt[b] = len(r)
         x1[b, :m] = a1; x2[b, :m] = a2; d1[b, :m] = e1; d2[b, :m] = e2; rows[b, :m] = r; score[b, :m] = s
     return x1, x2, d1, d2, cnt, rows, score
+
+
+# ---- the back end (include/mdrp_reconstruct.h): the fused two-view point cloud of a pair from its model and its two depth maps.  Rules
+# R1-R7 of the header, for one pair.  Whether a pixel is kept is decided by integers (the hash of its coordinates against a threshold) and a test of
+# its depth; a kept pixel's point is a fixed sequence of float64 operations, one rounding per arithmetic sign, rounded once to float32: the device
+# result equals this statement as bytes.
+KINDS = ("calibrated", "shared_focal", "varying_focal")
+KEEPS = ("not_inf", "finite")
+RECON_ALL, RECON_MAX_EXTENT = 0xFFFFFFFF, 65536
+RECON_STAGES = (3, 4)  # D4's stage of image 1 | image 2 (1 and 2 are the dense sampler's)
+
+
+def recon_threshold(rate):
+    """R3: a rate to the integer threshold: floor(rate * 2^32) for 0 < rate < 1, "all" for rate >= 1; rate <= 0 or NaN is refused"""
+    rate = float(rate)
+    if not rate > 0.0:
+        raise ValueError(f"rate must be above 0, not {rate!r}")
+    return RECON_ALL if rate >= 1.0 else int(np.floor(rate * 4294967296.0))
+
+
+def recon_hash(seed, stage, v, u):
+    """R3: uint32 hash of pixels (v, u) (arrays) for a seed and a stage; only the seed's low 32 bits count"""
+    k = (np.asarray(v, dtype=np.uint64) << np.uint64(16)) | np.asarray(u, dtype=np.uint64)
+    x = ((int(seed) & _M32) * 0x9E3779B1 + int(stage) * 0x85EBCA77) & _M32
+    return lowbias32((np.uint64(x) + k) & _M32).reshape(np.shape(k))
+
+
+def recon_candidates(h, w, thr, seed, stage):
+    """R3: (h, w) bool, True where the pixel is a candidate"""
+    if h > RECON_MAX_EXTENT or w > RECON_MAX_EXTENT:
+        raise ValueError(f"a map extent is at most {RECON_MAX_EXTENT}")
+    if not 1 <= int(thr) <= RECON_ALL:
+        raise ValueError("thr must be 1 .. 0xFFFFFFFF")
+    if int(thr) == RECON_ALL or h * w == 0:
+        return np.ones((h, w), dtype=bool)
+    v, u = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    return recon_hash(seed, stage, v, u) < np.uint32(thr)
+
+
+def recon_keep(d, keep="not_inf"):
+    """R4 on float64 depths"""
+    if keep not in KEEPS:
+        raise ValueError(f"keep must be one of {KEEPS}, not {keep!r}")
+    return np.isfinite(d) if keep == "finite" else ~np.isinf(d)
+
+
+def recon_usable(m, kind):
+    """R1: the model (a MODEL_DTYPE scalar) can be reconstructed from"""
+    with np.errstate(invalid="ignore"):
+        ok = bool(np.isfinite(m["q"]).all() and np.isfinite(m["t"]).all() and np.isfinite([m["scale"], m["shift1"], m["shift2"]]).all() and m["scale"] != 0.0)
+        if kind != "calibrated":
+            ok = ok and bool(np.isfinite(m["f1"]) and np.isfinite(m["f2"]) and m["f1"] > 0.0 and m["f2"] > 0.0)
+    return ok
+
+
+def _recon_intrinsics(m, kind, side, camera):
+    """(1 / fx, 1 / fy, cx, cy) of R5 for image `side`: from the camera (a record or dict with model_id 0 {f, cx, cy} | 1 {fx, fy, cx, cy} and params)
+    for the calibrated kind, from the model's focal otherwise (the principal point is the centre's business there)"""
+    if kind != "calibrated":
+        f = np.float64(m["f2"] if side else m["f1"])
+        return np.float64(1.0) / f, np.float64(1.0) / f, np.float64(0.0), np.float64(0.0)
+    if camera is None:
+        raise ValueError("the calibrated kind needs both cameras")
+    mid, p = int(camera["model_id"]), np.asarray(camera["params"], dtype=np.float64)
+    if mid not in (0, 1):
+        raise ValueError("only SIMPLE_PINHOLE (0) and PINHOLE (1) cameras")
+    fx, fy, cx, cy = (p[0], p[1], p[2], p[3]) if mid == 1 else (p[0], p[0], p[1], p[2])
+    return np.float64(1.0) / fx, np.float64(1.0) / fy, cx, cy
+
+
+def _quat_rows(q):
+    """R6: R from q = (w, x, y, z), the expressions of poselib._quat_to_R as they are written there"""
+    w, x, y, z = (np.float64(v) for v in q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def reconstruct_side_numpy(model, kind, side, depth_map, center=None, camera=None, keep="not_inf", thr=RECON_ALL, seed=0):
+    """R2-R6 for one image of one pair whose model is usable: (points (n, 3) FLOAT64 in camera 2's frame, before R7's rounding; v (n,), u (n,) int64,
+    the kept pixels in row-major order).  side 0 is image 1 (transformed), side 1 is image 2 (as it stands)."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    dm = _table(depth_map, "depth maps")
+    if dm.ndim != 2:
+        raise ValueError("expected a depth map (H, W)")
+    h, w = dm.shape
+    m = np.asarray(model).reshape(())
+    with np.errstate(all="ignore"):
+        d_all = dm.astype(np.float64)                                                     # R4 (float -> double is exact)
+        kept = recon_candidates(h, w, thr, seed, RECON_STAGES[side]) & recon_keep(d_all, keep)
+        v, u = np.nonzero(kept)                                                           # R2: row-major
+        d = d_all[v, u]
+        c = np.zeros(2) if center is None else np.asarray(center, dtype=np.float64).reshape(2)
+        rx, ry, cx, cy = _recon_intrinsics(m, kind, side, camera)
+        x = u.astype(np.float64) - c[0]                                                   # R5: every line is one rounding per sign
+        y = v.astype(np.float64) - c[1]
+        xn = (x - cx) * rx
+        yn = (y - cy) * ry
+        z = d + np.float64(m["shift2"] if side else m["shift1"])
+        X = np.stack([xn * z, yn * z, z], axis=1)
+        if side == 0:                                                                     # R6
+            R, t, inv = _quat_rows(m["q"]), np.asarray(m["t"], dtype=np.float64), np.float64(1.0) / np.float64(m["scale"])
+            X = np.stack([inv * (((R[r, 0] * X[:, 0] + R[r, 1] * X[:, 1]) + R[r, 2] * X[:, 2]) + t[r]) for r in range(3)], axis=1)
+    return X.reshape(-1, 3), v.astype(np.int64), u.astype(np.int64)
+
+
+def reconstruct_rows_numpy(model, kind, depth_map1, depth_map2, center1=None, center2=None, camera1=None, camera2=None, keep="not_inf", thr=RECON_ALL,
+                           seed=0, w_alloc1=None, w_alloc2=None):
+    """R1-R6 and R7's rounding for one pair: ((points1 (n1, 3) float32, pixel1 (n1,) int32), (points2, pixel2)), every kept point of image 1 and of
+    image 2 in pixel order; both empty where the model is not usable"""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    if keep not in KEEPS:
+        raise ValueError(f"keep must be one of {KEEPS}, not {keep!r}")
+    m = np.asarray(model).reshape(())
+    sides = []
+    for side, (dm, c, cam, wa) in enumerate(((depth_map1, center1, camera1, w_alloc1), (depth_map2, center2, camera2, w_alloc2))):
+        wa = np.shape(dm)[1] if wa is None else int(wa)
+        if recon_usable(m, kind):                                                          # R1
+            X, v, u = reconstruct_side_numpy(m, kind, side, dm, c, cam, keep, thr, seed)
+        else:
+            X, v, u = np.zeros((0, 3)), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        with np.errstate(over="ignore", invalid="ignore"):
+            sides.append((X.astype(np.float32), (v * wa + u).astype(np.int32)))          # R7: one rounding, to nearest
+    return tuple(sides)
+
+
+def pack_rows(sides, p_max=None):
+    """R7's placement: the two images' kept rows -> (points (p_max, 3) float32, pixel (p_max,) int32, counts (2,) int32); p_max None = n1 + n2.
+    Rows are written while they fit, image 2's behind image 1's; the counts are the true ones; behind the last written row 0, 0, 0 and -1."""
+    n1, n2 = len(sides[0][1]), len(sides[1][1])
+    p_max = n1 + n2 if p_max is None else int(p_max)
+    if p_max < 0:
+        raise ValueError("p_max must not be negative")
+    points, pixel = np.zeros((p_max, 3), dtype=np.float32), np.full(p_max, -1, dtype=np.int32)
+    start = 0
+    for P, px in sides:
+        k = min(len(px), p_max - start)
+        points[start:start + k] = P[:k]; pixel[start:start + k] = px[:k]
+        start += k
+    return points, pixel, np.array([n1, n2], dtype=np.int32)
+
+
+def reconstruct_pair_numpy(model, kind, depth_map1, depth_map2, center1=None, center2=None, camera1=None, camera2=None, keep="not_inf", thr=RECON_ALL,
+                           seed=0, p_max=None, w_alloc1=None, w_alloc2=None):
+    """One pair: model (a MODEL_DTYPE scalar), depth maps (h, w) float32 / float64, centres (2,) or None, cameras (calibrated kind) as records or
+    dicts with model_id and params.  Returns (points (p_max, 3) float32, pixel (p_max,) int32, counts (2,) int32) by R1-R7; p_max None = n1 + n2;
+    w_alloc: the allocated row length `pixel` counts rows by, None = the map's width.  This function is the definition."""
+    return pack_rows(reconstruct_rows_numpy(model, kind, depth_map1, depth_map2, center1, center2, camera1, camera2, keep, thr, seed, w_alloc1, w_alloc2),
+                     p_max)
+
+
+def reconstruct_image_pairs_numpy(models, kind, depth_maps, pairs, p_max, centers=None, sizes=None, cameras1=None, cameras2=None, keep="not_inf",
+                                  thr=RECON_ALL, seed=0):
+    """models (B,) MODEL_DTYPE, depth_maps (I, H, W) float32 / float64, pairs (B, 2) image indices (a, c); sizes (I, 2) (h, w) clamped to the
+    allocation, None = all of it; centers (I, 2) or (2,); cameras1 / cameras2: one per PAIR (calibrated kind).  Pair b is reconstruct_pair_numpy on
+    the two images' valid regions with w_alloc = W; a pair with an index outside [0, I) is empty.  Returns (points (B, p_max, 3) float32, pixel
+    (B, p_max) int32, counts (B, 2) int32)."""
+    dm = _table(depth_maps, "depth maps")
+    if dm.ndim != 3:
+        raise ValueError("expected depth maps (I, H, W)")
+    I, H, W = dm.shape
+    pairs = np.asarray(pairs).astype(np.int32).reshape(-1, 2)
+    models = np.asarray(models).reshape(-1)
+    if len(models) != len(pairs):
+        raise ValueError("one model per pair")
+    hw = np.tile(np.array([H, W], dtype=np.int64), (I, 1)) if sizes is None else np.asarray(sizes).reshape(I, 2)
+    hs, ws = clamp_extent(hw[:, 0], H), clamp_extent(hw[:, 1], W)
+    cs = None if centers is None else np.asarray(centers, dtype=np.float64)
+    if cs is not None and cs.size == 2:
+        cs = np.tile(cs.reshape(1, 2), (I, 1))
+    if cs is not None and cs.shape != (I, 2):
+        raise ValueError("centers must have shape (I, 2) or (2,)")
+    B, p_max = len(pairs), int(p_max)
+    points, pixel = np.zeros((B, p_max, 3), dtype=np.float32), np.full((B, p_max), -1, dtype=np.int32)
+    counts = np.zeros((B, 2), dtype=np.int32)
+    for b, (a, c) in enumerate(pairs):
+        if not (image_valid(a, I) and image_valid(c, I)):
+            continue
+        points[b], pixel[b], counts[b] = reconstruct_pair_numpy(
+            models[b], kind, dm[a][:hs[a], :ws[a]], dm[c][:hs[c], :ws[c]], None if cs is None else cs[a], None if cs is None else cs[c],
+            None if cameras1 is None else cameras1[b], None if cameras2 is None else cameras2[b], keep, thr, seed, p_max, W, W)
+    return points, pixel, counts

@@ -2000,3 +2000,8 @@ def refine_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, models, c
         res = h.fetch_results(B)  # (waits for the stream: the two small tensors below are complete)
         initial = {"score": score0.cpu().numpy(), "inliers": inl0.cpu().numpy()}
     return res, mask, initial
+
+
+# ---- the back end (include/mdrp_reconstruct.h): fused two-view point clouds from models and depth maps.  mdrp_amd/reconstruct.py holds
+# the three entry points; they are found here, beside the estimators whose records they take.
+from .reconstruct import reconstruct_image_pairs_torch, reconstruct_pair, reconstruct_pairs_torch  # noqa: E402, F401
