@@ -519,32 +519,139 @@ struct ChunkView {
     uint4 *rfrag;
     Trigger *trig;
 };
-// what goes on to a chunk's exact sweep: k_count's survivors, or k_bound's
+// what goes on to a chunk's exact sweep: k_count's survivors, k_bound's, or what the first chunk's filter kept
 struct Survivors { const uint32_t *tags; const int32_t *count; };
+// the sweep plans' `totals`, behind a plan of the call's `batch` pairs (a slice's plan uses the head of the buffer, `totals` stays where it is)
+int32_t *plan_totals(int32_t *plan, int batch) { return plan + 2 * (size_t)batch + 2; }
+enum class Sweep { tile, split, wave }; // k_score, k_score_split, k_score_w
+
+// The stage launchers of a chunk's sweep.  The scheduler (Pass::count ... Pass::walk, which keep the decisions, the event pairs and the launch counters) and
+// the probes behind the kernel-pinning tests (mdrp_bound_models, mdrp_retire_models, mdrp_front_models, mdrp_front_lists, mdrp_replay_slots) all launch
+// through here: plan kernels, grids, argument order and buffer roles are written once.  A launcher only issues launches, and records its caller's
+// events, on the stream it is given.  Grids are upper bounds from the chunk's length: a workgroup beyond the plan exits at once (k_count, k_bound)
+// or finds its item loop empty (the exact sweeps).
+
+// Candidate counts on the matrix cores against the records of the chunks before this one: of (v.tags, v.model_count), survivors only go on
+// (v.tags_v, v.surv1).  Phase A: every hypothesis over the pair's leading tiles (all tiles where the records, or a null cand_stat, do not allow a
+// split); two_phase: phase B, the undecided ones over the rest (k_count, mdrp_kernels.h).  The undecided list lives where this chunk's SORTED list
+// will be written once the counts are done (k_sort_tags), the partial counts in the other parity's sorted list, whose last reader was the previous
+// chunk's exact sweep: no scratch of their own.  stats (or null): evaluations, [0] all and [1] on the matrix cores.
+int launch_count(mdrp_handle *h, hipStream_t s, int kind, const ChunkView &v, bool two_phase, unsigned long long *stats, unsigned long long *cand_stat,
+                 hipEvent_t c0, hipEvent_t c1) {
+    uint32_t *tags_u = v.tags_sorted;
+    int32_t *und_part = reinterpret_cast<int32_t *>(v.tags_sorted_other), *cplan = h->cplan.as<int32_t>();
+    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.model_count, 2, CNT_WG_MODELS, cplan,
+                       v.surv1, (const int32_t *)nullptr, two_phase ? v.und_count : (int32_t *)nullptr); // (also clears the counters k_count appends to)
+    const dim3 cgrid((unsigned)v.pc * (unsigned)((v.r.chunk_len * v.r.mps + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
+    HIPCHK(hipEventRecord(c0, s));
+    MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, v.r, v.st, v.rfrag, v.models,
+                        v.tags, v.model_count, cplan, v.tags_v, v.surv1, stats, (int32_t *)nullptr, (const int32_t *)nullptr,
+                        1, tags_u, und_part, v.und_count, (const int32_t *)nullptr, cand_stat);
+    if (two_phase) {
+        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.und_count, 2, CNT_WG_MODELS, cplan,
+                           (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
+        MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, v.r, v.st, v.rfrag, v.models,
+                            tags_u, v.und_count, cplan, v.tags_v, v.surv1, stats, (int32_t *)nullptr, (const int32_t *)nullptr,
+                            2, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, und_part, cand_stat);
+    }
+    HIPCHK(hipEventRecord(c1, s));
+    return MDRP_OK;
+}
+
+// fp32 lower bound of the score for k_count's survivors (v.tags_v, v.surv1); its survivors go back into the chunk's tag list (v.tags, v.surv2),
+// which k_count has consumed, and are what `sv` names afterwards.  dbg_lb / dbg_ub (or null): the two bounds of every model (mdrp_bound_models).
+int launch_bound(mdrp_handle *h, hipStream_t s, int kind, const ChunkView &v, unsigned long long *stats, double *dbg_lb, int32_t *dbg_ub,
+                 hipEvent_t b0, hipEvent_t b1, Survivors &sv) {
+    int32_t *cplan = h->cplan.as<int32_t>();
+    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.surv1, 1, BND_THREADS, cplan, v.surv2, (const int32_t *)nullptr);
+    const dim3 bgrid((unsigned)v.pc * (unsigned)((v.r.chunk_len * v.r.mps + BND_THREADS - 1) / BND_THREADS));
+    HIPCHK(hipEventRecord(b0, s));
+    MDRP_SWEEP_DISPATCH(k_bound, kind, bgrid, dim3(BND_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_v, v.surv1, cplan, v.tags, v.surv2, stats,
+                        dbg_lb, dbg_ub);
+    HIPCHK(hipEventRecord(b1, s));
+    sv = Survivors{v.tags, v.surv2};
+    return MDRP_OK;
+}
+
+// sort by candidate density, plan, exact fp64 sweep of the survivors between the events e0 and e1:
+//   k_score_w      calls of few pairs: one WAVEFRONT per hypothesis — a lane per hypothesis is a 0.3 ms serial record loop however few there are
+//   k_score_split  the survivors of k_bound (~93 per pair): 64 hypotheses per workgroup, each wavefront a quarter of the records
+//   k_score        a run's first chunk: its sweep runs beside the second chunk's solver, where more and smaller sweep workgroups only wait longer
+int launch_score(mdrp_handle *h, hipStream_t s, int kind, const ChunkView &v, const Survivors &sv, Sweep sweep, int32_t *plan, int32_t *totals,
+                 hipEvent_t e0, hipEvent_t e1) {
+    const bool wave = sweep == Sweep::wave, split = sweep == Sweep::split;
+    const int models = v.r.chunk_len * v.r.mps;
+    if (wave) hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, sv.count, 1, SCW_THREADS / 64, plan, (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
+    hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, sv.count, sv.tags, v.tags_sorted);
+    if (!wave) hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.model_count, plan, totals, split ? SPLIT_HYP : SCORE_THREADS);
+    HIPCHK(hipEventRecord(e0, s));
+    const long long capped = (long long)h->num_cu * 32; // k_score_w, k_score_split: surplus workgroups exit at once, a shortfall is taken by the item loop
+    if (wave) {
+        const long long ub = (long long)v.pc * ((models + SCW_THREADS / 64 - 1) / (SCW_THREADS / 64));
+        MDRP_SWEEP_DISPATCH(k_score_w, kind, dim3((unsigned)std::min(ub, capped)), dim3(SCW_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
+                            v.slot_score, v.slot_inl, plan);
+    } else if (split) {
+        const long long ub = (long long)v.pc * ((models + SPLIT_HYP - 1) / SPLIT_HYP + 1); // items: at most ceil(sparse / 64) + ceil(dense / 64) per pair
+        MDRP_SWEEP_DISPATCH(k_score_split, kind, dim3((unsigned)std::min(ub, capped)), dim3(SPLIT_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
+                            v.slot_score, v.slot_inl, plan, totals);
+    } else {
+        const dim3 grid((unsigned)v.pc * (unsigned)((models + SCORE_THREADS - 1) / SCORE_THREADS));
+        MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), SCORE_TILE_BYTES, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
+                            v.slot_score, v.slot_inl, plan, totals);
+    }
+    HIPCHK(hipEventRecord(e1, s));
+    return MDRP_OK;
+}
 
 // A run's first chunk in calls of more than SCORE_WAVE_MAX_PAIRS pairs (3-point estimators): prefix retirement (mdrp_kernels.h, "first chunk").
 // In: k_count's survivors — every live hypothesis, or what a prior's records left.  The picked ones are scored here; what their prefix records
-// do not retire is back on (tags_v, surv1) for the exact sweep.  The picked list uses the chunk's solver-order tag list (k_count has consumed it), the
+// do not retire is back on the kept list for the exact sweep.  The picked list uses the chunk's solver-order tag list (k_count has consumed it), the
 // rest list the other parity's sorted list (free until the next chunk's count), their counters surv2 and und_count (idle in a first chunk).
-// The scheduler (Pass::front) and mdrp_front_models both launch through here.
-int launch_front(mdrp_handle *h, hipStream_t s, int kind, const ChunkView &v, int first_pick, int32_t *plan, int32_t *totals,
-                 unsigned long long *evals, Survivors &sv) {
-    uint32_t *tags_pick = v.tags, *tags_rest = v.tags_sorted_other;
-    hipLaunchKernelGGL(k_first_pick, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, sv.count, sv.tags, first_pick, tags_pick, v.surv2, tags_rest, v.und_count);
-    hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, v.surv2, tags_pick, v.tags_sorted);
+struct FrontLists { uint32_t *pick, *rest, *kept; int32_t *n_pick, *n_rest /*stride 2*/, *n_kept; };
+FrontLists front_lists(const ChunkView &v) { return FrontLists{v.tags, v.tags_sorted_other, v.tags_v, v.surv2, v.und_count, v.surv1}; }
+// ... its three parts (mdrp_front_lists runs the first and the last around its caller's tables): the pick,
+void launch_front_pick(hipStream_t s, const ChunkView &v, const Survivors &sv, int first_pick) {
+    const FrontLists f = front_lists(v);
+    hipLaunchKernelGGL(k_first_pick, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, sv.count, sv.tags, first_pick, f.pick, f.n_pick, f.rest, f.n_rest);
+}
+// the picked hypotheses' exact scores between the events f0 and f1,
+int launch_front_score(mdrp_handle *h, hipStream_t s, int kind, const ChunkView &v, int32_t *plan, int32_t *totals, hipEvent_t f0, hipEvent_t f1) {
+    const FrontLists f = front_lists(v);
+    hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, f.n_pick, f.pick, v.tags_sorted);
     hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.model_count, plan, totals, SPLIT_HYP);
-    hipEvent_t f0, f1;
-    if (int rc = get_events(h, &f0, &f1, 0)) return rc;
     HIPCHK(hipEventRecord(f0, s));
     const long long ub = 2ll * v.pc; // at most FIRST_PICK_MAX + 1 hypotheses per pair, in two density classes: two workgroups of SPLIT_HYP
     MDRP_SWEEP_DISPATCH(k_first_score, kind, dim3((unsigned)std::min(ub, (long long)h->num_cu * 32)), dim3(SPLIT_THREADS), 0, s, v.r, v.st, v.pts, v.models,
                         v.tags_sorted, v.model_count, v.slot_score, v.slot_inl, plan, totals);
     HIPCHK(hipEventRecord(f1, s));
-    h->sweep_launches++;
-    hipLaunchKernelGGL(k_first_filter, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, v.slot_score, v.slot_inl, tags_pick, v.surv2, tags_rest, v.und_count,
-                       v.tags_v, v.surv1, evals);
-    sv = Survivors{v.tags_v, v.surv1};
     return MDRP_OK;
+}
+// and the filter of the rest list by their records (evals: the counter k_first_filter adds to), whose kept list is what goes on to the exact sweep.
+Survivors launch_front_filter(hipStream_t s, const ChunkView &v, unsigned long long *evals) {
+    const FrontLists f = front_lists(v);
+    hipLaunchKernelGGL(k_first_filter, dim3(v.pc), dim3(FIRST_THREADS), 0, s, v.r, v.st, v.slot_score, v.slot_inl, f.pick, f.n_pick, f.rest, f.n_rest,
+                       f.kept, f.n_kept, evals);
+    return Survivors{f.kept, f.n_kept};
+}
+// The scheduler (Pass::front) and mdrp_front_models run the three in a row.
+int launch_front(mdrp_handle *h, hipStream_t s, int kind, const ChunkView &v, int first_pick, int32_t *plan, int32_t *totals, unsigned long long *evals,
+                 hipEvent_t f0, hipEvent_t f1, Survivors &sv) {
+    launch_front_pick(s, v, sv, first_pick);
+    if (int rc = launch_front_score(h, s, kind, v, plan, totals, f0, f1)) return rc;
+    sv = launch_front_filter(s, v, evals);
+    return MDRP_OK;
+}
+
+// Replay of score_models / ransac bookkeeping over the ordered triggers of `batch` pairs; with budgets (n_bud of them, else null), the walk that
+// takes their checkpoints into ckpt.
+void launch_walk(hipStream_t s, int batch, const RunParams &r, PairState *st, const Model *models, const Trigger *trig, int trig_cap, Progress *progress,
+                 const uint64_t *budgets, int n_bud, PairState *ckpt) {
+    if (budgets)
+        hipLaunchKernelGGL(k_walk_ckpt, dim3((batch + WALK_CKPT_THREADS - 1) / WALK_CKPT_THREADS), dim3(WALK_CKPT_THREADS), 0, s, r, st, models, trig, trig_cap,
+                           &progress->n_active, &progress->max_needed, budgets, n_bud, ckpt);
+    else
+        hipLaunchKernelGGL(k_walk, dim3((batch + 63) / 64), dim3(64), 0, s, r, st, models, trig, trig_cap, &progress->n_active, &progress->max_needed,
+                           (const int32_t *)nullptr, 0, 0, 0);
 }
 
 // A pass and the stages run_pass strings together.  Stages only issue work (launches, copies, memsets, events) on the stream they name; who waits for
@@ -836,93 +943,45 @@ struct Pass : PassIn {
         return MDRP_OK;
     }
 
-    // candidate counts on the matrix cores against the records of the chunks before this one; survivors only go on (tags_v, surv1)
+    // The sweep stages: each decides whether and how its stage runs and keeps the call's accounting (the event pair and its `what` code, the launch
+    // counters); the launches themselves are the launchers' above.
+    // A run's first chunk has no record: phase A is the whole count, no phase B.
     int count(const ChunkView &v) {
-        unsigned long long *cstats = &cnt->progress.evals; // (and evals_mfma)
         hipEvent_t c0, c1;
         if (int rc = get_events(h, &c0, &c1, 1)) return rc;
-        // phase A: every hypothesis over the pair's leading tiles (all tiles where the records do not allow a split); phase B: the undecided
-        // ones over the rest (k_count, mdrp_kernels.h).  A run's first chunk has no record: phase A is the whole count, no phase B.
         const bool two_phase = !v.first_of_run;
-        // The undecided list lives where this chunk's SORTED list will be written once the counts are done (k_sort_tags, below), the partial counts
-        // in the other parity's sorted list, whose last reader was the previous chunk's exact sweep: no scratch of their own.
-        uint32_t *tags_u = v.tags_sorted;
-        int32_t *und_part = reinterpret_cast<int32_t *>(v.tags_sorted_other), *cplan = h->cplan.as<int32_t>();
-        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.model_count, 2, CNT_WG_MODELS, cplan,
-                           v.surv1, (const int32_t *)nullptr, two_phase ? v.und_count : (int32_t *)nullptr); // (also clears the counters k_count appends to)
-        const dim3 cgrid((unsigned)v.pc * (unsigned)((v.r.chunk_len * mps + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
-        HIPCHK(hipEventRecord(c0, s));
-        MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, v.r, v.st, v.rfrag, v.models,
-                            v.tags, v.model_count, cplan, v.tags_v, v.surv1, cstats, (int32_t *)nullptr, (const int32_t *)nullptr,
-                            1, tags_u, und_part, v.und_count, (const int32_t *)nullptr, v.cand_stat);
-        if (two_phase) {
-            hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.und_count, 2, CNT_WG_MODELS, cplan,
-                               (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
-            MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, v.r, v.st, v.rfrag, v.models,
-                                tags_u, v.und_count, cplan, v.tags_v, v.surv1, cstats, (int32_t *)nullptr, (const int32_t *)nullptr,
-                                2, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, und_part, v.cand_stat);
-            h->count_launches++; // (mdrp_stats::count_launches counts kernel launches: a rocprof summary shows the same number)
-        }
-        HIPCHK(hipEventRecord(c1, s));
-        h->count_launches++;
-        return MDRP_OK;
+        h->count_launches += two_phase ? 2 : 1; // (mdrp_stats::count_launches counts kernel launches: a rocprof summary shows the same number)
+        return launch_count(h, s, kind, v, two_phase, &cnt->progress.evals, v.cand_stat, c0, c1);
     }
 
-    // fp32 lower bound of the score for k_count's survivors; its survivors go back into the chunk's tag list
-    // (calls of a few pairs skip the stage: its lane-per-hypothesis record loop is 0.1 ms of latency, and k_score_w takes k_count's survivors at once;
+    // (calls of a few pairs skip the bound: its lane-per-hypothesis record loop is 0.1 ms of latency, and k_score_w takes k_count's survivors at once;
     // a run's first chunk has no records yet: nothing to retire)
     int bound(const ChunkView &v, Survivors &sv) {
         sv = Survivors{v.tags_v, v.surv1};
         if (!(use_bound && batch_call > 16 && !v.first_of_run)) return MDRP_OK;
-        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, v.surv1, 1, BND_THREADS, h->cplan.as<int32_t>(), v.surv2, (const int32_t *)nullptr);
-        const dim3 bgrid((unsigned)v.pc * (unsigned)((v.r.chunk_len * mps + BND_THREADS - 1) / BND_THREADS));
-        unsigned long long *bstats = &cnt->progress.evals_bound;
         hipEvent_t b0, b1;
         if (int rc = get_events(h, &b0, &b1, 4)) return rc;
-        HIPCHK(hipEventRecord(b0, s));
-        MDRP_SWEEP_DISPATCH(k_bound, kind, bgrid, dim3(BND_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_v, v.surv1, h->cplan.as<int32_t>(), v.tags, v.surv2, bstats);
-        HIPCHK(hipEventRecord(b1, s));
-        sv = Survivors{v.tags, v.surv2};
-        return MDRP_OK;
+        return launch_bound(h, s, kind, v, &cnt->progress.evals_bound, nullptr, nullptr, b0, b1, sv);
     }
 
-    // A run's first chunk in calls of more than SCORE_WAVE_MAX_PAIRS pairs (3-point estimators): prefix retirement (launch_front, above)
+    // A run's first chunk in calls of more than SCORE_WAVE_MAX_PAIRS pairs (3-point estimators): prefix retirement
     int front(const ChunkView &v, Survivors &sv) {
         if (!(v.first_of_run && first_pick > 0)) return MDRP_OK;
-        int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * (size_t)batch + 2;
-        return launch_front(h, s, kind, v, first_pick, plan, totals, &cnt->progress.evals_sweep, sv);
+        int32_t *plan = h->plan.as<int32_t>();
+        hipEvent_t f0, f1;
+        if (int rc = get_events(h, &f0, &f1, 0)) return rc;
+        h->sweep_launches++;
+        return launch_front(h, s, kind, v, first_pick, plan, plan_totals(plan, batch), &cnt->progress.evals_sweep, f0, f1, sv);
     }
 
-    // sort by candidate density, plan, exact fp64 sweep of the survivors between the events e0 and e1:
-    //   k_score_w      calls of few pairs: one WAVEFRONT per hypothesis — a lane per hypothesis is a 0.3 ms serial record loop however few there are
-    //   k_score_split  the survivors of k_bound (~93 per pair): 64 hypotheses per workgroup, each wavefront a quarter of the records
-    //   k_score        a run's first chunk: its sweep runs beside the second chunk's solver, where more and smaller sweep workgroups only wait longer
+    // the exact sweep between the events e0 and e1: by wavefronts in calls of few pairs, else split behind k_bound, by tiles in a run's first chunk
     int score(const ChunkView &v, const Survivors &sv, hipEvent_t e0, hipEvent_t e1) {
-        const bool wave = batch_call <= SCORE_WAVE_MAX_PAIRS, split = !wave && score_split && !v.first_of_run;
-        const int models = v.r.chunk_len * mps;
-        int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * (size_t)batch + 2; // (the slice's plan uses the head of the buffer, `totals` stays where it is)
-        if (wave) hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.st, sv.count, 1, SCW_THREADS / 64, plan, (int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr);
-        hipLaunchKernelGGL(k_sort_tags, dim3(v.pc), dim3(256), 0, s, v.r, v.st, v.model_count, sv.count, sv.tags, v.tags_sorted);
-        if (!wave) hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, v.pc, v.model_count, plan, totals, split ? SPLIT_HYP : SCORE_THREADS);
-        HIPCHK(hipEventRecord(e0, s));
-        const long long capped = (long long)h->num_cu * 32; // k_score_w, k_score_split: surplus workgroups exit at once, a shortfall is taken by the item loop
-        if (wave) {
-            const long long ub = (long long)v.pc * ((models + SCW_THREADS / 64 - 1) / (SCW_THREADS / 64));
-            MDRP_SWEEP_DISPATCH(k_score_w, kind, dim3((unsigned)std::min(ub, capped)), dim3(SCW_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
-                                v.slot_score, v.slot_inl, plan);
-        } else if (split) {
-            const long long ub = (long long)v.pc * ((models + SPLIT_HYP - 1) / SPLIT_HYP + 1); // items: at most ceil(sparse / 64) + ceil(dense / 64) per pair
-            MDRP_SWEEP_DISPATCH(k_score_split, kind, dim3((unsigned)std::min(ub, capped)), dim3(SPLIT_THREADS), 0, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
-                                v.slot_score, v.slot_inl, plan, totals);
-        } else {
-            const dim3 grid((unsigned)v.pc * (unsigned)((models + SCORE_THREADS - 1) / SCORE_THREADS));
-            MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), SCORE_TILE_BYTES, s, v.r, v.st, v.pts, v.models, v.tags_sorted, v.model_count,
-                                v.slot_score, v.slot_inl, plan, totals);
-        }
-        HIPCHK(hipEventRecord(e1, s));
+        const Sweep sweep = batch_call <= SCORE_WAVE_MAX_PAIRS ? Sweep::wave : (score_split && !v.first_of_run ? Sweep::split : Sweep::tile);
+        int32_t *plan = h->plan.as<int32_t>();
         h->sweep_launches++;
-        return MDRP_OK;
+        return launch_score(h, s, kind, v, sv, sweep, plan, plan_totals(plan, batch), e0, e1);
     }
+
 
     // ordered prefix over the iterations: LO triggers
     void scan(const ChunkView &v) {
@@ -1051,14 +1110,9 @@ struct Pass : PassIn {
 
     // replay of score_models / ransac bookkeeping over the ordered triggers (the fused tail's LO launch has done it; a budgets call takes its checkpoints here)
     int walk() {
-        if (bud)
-            hipLaunchKernelGGL(k_walk_ckpt, dim3((batch + WALK_CKPT_THREADS - 1) / WALK_CKPT_THREADS), dim3(WALK_CKPT_THREADS), 0, s, rp, h->st.as<PairState>(), h->models.as<Model>(),
-                               h->triggers.as<Trigger>(), trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed,
-                               reinterpret_cast<const uint64_t *>(pd + sz.off_bud), n_bud, h->ckpt.as<PairState>());
-        else if (!fuse_tail)
-            hipLaunchKernelGGL(k_walk, dim3((batch + 63) / 64), dim3(64), 0, s, rp, h->st.as<PairState>(), h->models.as<Model>(),
-                               h->triggers.as<Trigger>(), trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed,
-                               (const int32_t *)nullptr, 0, 0, 0);
+        if (bud || !fuse_tail)
+            launch_walk(s, batch, rp, h->st.as<PairState>(), h->models.as<Model>(), h->triggers.as<Trigger>(), trig_cap, &cnt->progress,
+                        bud ? reinterpret_cast<const uint64_t *>(pd + sz.off_bud) : nullptr, n_bud, h->ckpt.as<PairState>());
         HIPCHK(hipGetLastError());
         return MDRP_OK;
     }
@@ -1382,28 +1436,83 @@ static int create_handle(int device, hipStream_t stream, bool own_stream, mdrp_h
     return MDRP_OK;
 }
 
-// the single-pair entry points (mdrp_score_models, mdrp_count_candidates, mdrp_bound_models): hypotheses 0 .. count - 1 in `tags` ...
-static int upload_iota(hipStream_t s, void *tags, int count) {
-    std::vector<uint32_t> iota(count);
-    for (int i = 0; i < count; ++i) iota[i] = (uint32_t)i;
-    HIPCHK(hipMemcpyAsync(tags, iota.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, s));
-    return MDRP_OK;
+// A probe's whole batch (r.batch pairs) as chunk 0 of a run: the scheduler's buffers from their start, parity 0.  (first_of_run is an input of the
+// scheduler's decisions: no launcher reads it.)
+static ChunkView probe_view(mdrp_handle *h, const RunParams &r) {
+    ChunkView v;
+    std::memset(&v, 0, sizeof v);
+    v.pc = r.batch; v.r = r;
+    v.st = h->st.as<PairState>(); v.pts = h->pts.as<double>(); v.models = h->models.as<Model>();
+    v.slot_score = h->slot_score.as<double>(); v.slot_inl = h->slot_inl.as<int32_t>();
+    v.tags = h->tags[0].as<uint32_t>(); v.tags_v = h->tags_v.as<uint32_t>();
+    v.tags_sorted = h->tags_sorted[0].as<uint32_t>(); v.tags_sorted_other = h->tags_sorted[1].as<uint32_t>();
+    v.model_count = h->model_count[0].as<int32_t>(); v.und_count = h->und_count.as<int32_t>();
+    v.surv1 = h->surv_count.as<int32_t>(); v.surv2 = h->surv2_count.as<int32_t>();
+    v.cand_stat = h->cand_stat.as<unsigned long long>(); v.rfrag = h->rfrag.as<uint4>(); v.trig = h->triggers.as<Trigger>();
+    return v;
 }
-// ... and one pair without records (nothing is pruned or retired: every model sees every correspondence): its state, its correspondences packed
-// into h->pts from the device copies x1, x2, and their box.  mdrp_retire_models alone stages records (rec_cnt, rec_score < DBL_MAX).
-static int stage_unit_pair(mdrp_handle *h, const double *x1, const double *x2, int n, double sq_threshold, uint64_t rec_cnt = 0,
-                           double rec_score = DBL_MAX) {
+
+// The single-pair probes (mdrp_score_models, mdrp_count_candidates, mdrp_bound_models, retire_train) stage their pair as a one-pair chunk of `slots`
+// slots per pair (the run parameters' slot_stride; chunk_len = ceil(num_models / 4) sizes the launchers' grids) and get its view `v`:
+//   * the correspondences (host or device memory) packed into h->pts with their box, and the models;
+//   * the pair's state: no records (nothing is pruned or retired: every model sees every correspondence) unless rec_score < DBL_MAX (retire_train);
+//   * `listed` tags (`list`, or null: 0 .. num_models - 1) as the chunk's solver-order list with its count in model_count, or, as_survivors, as
+//     k_count's survivors (tags_v, surv1); the other list counters cleared;
+//   * frag: the records' MFMA fragments for k_count.
+static int stage_unit_chunk(mdrp_handle *h, int kind, int mem_space, const mdrp_model *models, int num_models, size_t slots, const double *x1,
+                            const double *x2, int n, double sq_threshold, const uint32_t *list, int listed, bool as_survivors, bool frag, ChunkView &v,
+                            uint64_t rec_cnt = 0, double rec_score = DBL_MAX) {
     hipStream_t s = h->stream;
+    const int nn = std::max(n, 1);
+    const size_t tag_bytes = sizeof(uint32_t) * slots;
+    const bool host = mem_space == MDRP_MEM_HOST;
+    int rc;
+    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * nn)) || (rc = h->st.ensure(sizeof(PairState))) ||
+        (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_score.ensure(sizeof(double) * slots)) ||
+        (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) || (rc = h->tags[0].ensure(tag_bytes)) || (rc = h->tags_v.ensure(tag_bytes)) ||
+        (rc = h->tags_sorted[0].ensure(tag_bytes)) || (rc = h->tags_sorted[1].ensure(tag_bytes)) ||
+        (rc = h->model_count[0].ensure(2 * sizeof(int32_t))) || (rc = h->und_count.ensure(2 * sizeof(int32_t))) ||
+        (rc = h->surv_count.ensure(sizeof(int32_t))) || (rc = h->surv2_count.ensure(sizeof(int32_t))) ||
+        (rc = h->cand_stat.ensure(2 * sizeof(unsigned long long))) || (rc = h->cplan.ensure(2 * sizeof(int32_t))) ||
+        (rc = h->plan.ensure(sizeof(int32_t) * (2 + 2 + 4 + 16))) || (rc = h->rfrag.ensure((size_t)((nn + 15) / 16) * 1024)) ||
+        (host && ((rc = h->in_x1.ensure(sizeof(double) * 2 * nn)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * nn)))))
+        return rc;
+    RunParams rp;
+    std::memset(&rp, 0, sizeof rp);
+    rp.kind = kind; rp.batch = 1; rp.n_max = nn; rp.chunk_len = (num_models + 3) / 4; rp.super_len = rp.chunk_len; rp.slot_stride = (int)slots;
+    rp.mps = 4; rp.sample_sz = 3;
+    v = probe_view(h, rp);
+    if (host) {
+        HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
+        x1 = h->in_x1.as<double>(); x2 = h->in_x2.as<double>();
+    }
+    HIPCHK(hipMemcpyAsync(v.models, models, sizeof(Model) * num_models, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    std::vector<uint32_t> iota;
+    if (!list) {
+        iota.resize(listed = num_models);
+        for (int i = 0; i < num_models; ++i) iota[i] = (uint32_t)i;
+        list = iota.data();
+    }
+    const int32_t counts2[2] = {listed, 0}, surv = as_survivors ? listed : 0;
+    HIPCHK(hipMemcpyAsync(as_survivors ? v.tags_v : v.tags, list, sizeof(uint32_t) * listed, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(v.model_count, counts2, sizeof counts2, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(v.surv1, &surv, sizeof surv, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(v.surv2, 0, sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(v.und_count, 0, 2 * sizeof(int32_t), s));
     PairState ps;
     std::memset(&ps, 0, sizeof ps);
     ps.n = n; ps.active = 1; ps.sq_thr = sq_threshold; ps.eps = std::sqrt(sq_threshold);
     ps.best_min_cnt = rec_cnt; ps.best_min_score = rec_score < DBL_MAX ? rec_score : DBL_MAX; // (a NaN score is no record either)
-    HIPCHK(hipMemcpyAsync(h->st.p, &ps, sizeof ps, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(v.st, &ps, sizeof ps, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_pack_unit, dim3((n + 255) / 256 + 1), dim3(256), 0, s, n, x1, x2, (const double *)nullptr,
-                       (const double *)nullptr, h->pts.as<double>(), (double *)nullptr);
-    hipLaunchKernelGGL(k_box_unit, dim3(1), dim3(256), 0, s, n, h->pts.as<double>(), h->st.as<PairState>());
+                       (const double *)nullptr, v.pts, (double *)nullptr);
+    hipLaunchKernelGGL(k_box_unit, dim3(1), dim3(256), 0, s, n, v.pts, v.st);
+    if (frag) hipLaunchKernelGGL(k_frag_unit, dim3((n + 16 + 255) / 256), dim3(256), 0, s, n, v.pts, v.rfrag);
+    HIPCHK(hipStreamSynchronize(s)); // (the staged host copies go out of scope)
     return MDRP_OK;
 }
+
 
 static LmOpt lm_opt(const mdrp_bundle_opt *opt) {
     LmOpt o;
@@ -1832,135 +1941,79 @@ int mdrp_classic_solver_batch(mdrp_handle *h, int kind, const double *x1h, const
     return MDRP_OK;
 }
 
+// Exact scores of a model list as it stands: the one probe with a sweep launch of its own (k_score over the UNSORTED list, every model in the
+// sparse class, on a grid capped at four workgroups per CU, so that the item loop runs), in slots padded to whole iterations of four.
 int mdrp_score_models(mdrp_handle *h, int kind, int mem_space, const mdrp_model *models, int num_models, const double *x1,
                       const double *x2, int n, double sq_threshold, double *scores, int32_t *counts) {
     if (!h || num_models < 0 || n < 0 || kind < 0 || kind > 5 || !scores || !counts) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (num_models == 0) return MDRP_OK;
     MDRP_ENTER(h);
     hipStream_t s = h->stream;
-    const int chunk = (num_models + 3) / 4;
-    const size_t slots = (size_t)chunk * 4;
+    ChunkView v;
     int rc;
-    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * std::max(n, 1))) || (rc = h->st.ensure(sizeof(PairState))) ||
-        (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_score.ensure(sizeof(double) * slots)) ||
-        (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) || (rc = h->tags[0].ensure(sizeof(uint32_t) * slots)) ||
-        (rc = h->model_count[0].ensure(2 * sizeof(int32_t))))
+    if ((rc = stage_unit_chunk(h, kind, mem_space, models, num_models, (size_t)4 * ((num_models + 3) / 4), x1, x2, n, sq_threshold, nullptr, 0, false, false, v)))
         return rc;
-    const double *x1d = x1, *x2d = x2;
-    const Model *md = reinterpret_cast<const Model *>(models);
-    if (mem_space == MDRP_MEM_HOST) {
-        if ((rc = h->in_x1.ensure(sizeof(double) * 2 * std::max(n, 1))) || (rc = h->in_x2.ensure(sizeof(double) * 2 * std::max(n, 1)))) return rc;
-        HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
-        x1d = h->in_x1.as<double>(); x2d = h->in_x2.as<double>();
-        md = h->models.as<Model>();
-    } else {
-        HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyDeviceToDevice, s));
-        md = h->models.as<Model>();
-    }
-    if ((rc = upload_iota(s, h->tags[0].p, num_models))) return rc;
-    const int32_t counts2[2] = {num_models, 0};
-    HIPCHK(hipMemcpyAsync(h->model_count[0].p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if ((rc = stage_unit_pair(h, x1d, x2d, n, sq_threshold))) return rc;
-    RunParams rp;
-    std::memset(&rp, 0, sizeof rp);
-    rp.kind = kind; rp.batch = 1; rp.n_max = std::max(n, 1); rp.chunk_len = chunk; rp.chunk_off = 0; rp.slot_stride = chunk * 4; rp.super_len = chunk;
-    rp.mps = 4; rp.sample_sz = 3;
-    const size_t tile_bytes = SCORE_TILE_BYTES;
-    if ((rc = h->plan.ensure(sizeof(int32_t) * 8))) return rc;
-    int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 4;
-    hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->model_count[0].as<int32_t>(), plan, totals, SCORE_THREADS);
+    int32_t *plan = h->plan.as<int32_t>(), *totals = plan_totals(plan, 1);
+    hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, v.model_count, plan, totals, SCORE_THREADS);
     const dim3 grid((unsigned)std::min(h->num_cu * 4, (num_models + SCORE_THREADS - 1) / SCORE_THREADS));
     h->ev_used = 0; h->sweep_launches = 1; h->sweep_evals = (int64_t)num_models * n;
     hipEvent_t e0, e1;
     if ((rc = get_events(h, &e0, &e1))) return rc;
     HIPCHK(hipEventRecord(e0, s));
-    MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), tile_bytes, s, rp, h->st.as<PairState>(), h->pts.as<double>(), md,
-                        h->tags[0].as<uint32_t>(), h->model_count[0].as<int32_t>(), h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan, totals);
+    MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), SCORE_TILE_BYTES, s, v.r, v.st, v.pts, v.models, v.tags, v.model_count, v.slot_score,
+                        v.slot_inl, plan, totals);
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipGetLastError());
     const hipMemcpyKind back = mem_space == MDRP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIPCHK(hipMemcpyAsync(scores, h->slot_score.p, sizeof(double) * num_models, back, s));
-    HIPCHK(hipMemcpyAsync(counts, h->slot_inl.p, sizeof(int32_t) * num_models, back, s));
+    HIPCHK(hipMemcpyAsync(scores, v.slot_score, sizeof(double) * num_models, back, s));
+    HIPCHK(hipMemcpyAsync(counts, v.slot_inl, sizeof(int32_t) * num_models, back, s));
     return finish_timing(h);
 }
 
+// k_count's candidate counts of every model: the kernel's phase 0, the whole count in one launch with cand_out and no undecided lists, which
+// no chunk of the scheduler runs: a launch of its own.
 int mdrp_count_candidates(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
                           int n, double sq_threshold, int32_t *candidates) {
     if (!h || num_models < 0 || n < 0 || kind < 0 || kind > 5 || !candidates || !models) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (num_models == 0) return MDRP_OK;
     MDRP_ENTER(h);
     hipStream_t s = h->stream;
-    const int nn = std::max(n, 1);
-    const size_t slots = (size_t)num_models;
+    ChunkView v;
     int rc;
-    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * nn)) || (rc = h->st.ensure(sizeof(PairState))) ||
-        (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) ||
-        (rc = h->tags[0].ensure(sizeof(uint32_t) * slots)) || (rc = h->tags_v.ensure(sizeof(uint32_t) * slots)) ||
-        (rc = h->model_count[0].ensure(2 * sizeof(int32_t))) || (rc = h->surv_count.ensure(sizeof(int32_t))) ||
-        (rc = h->cplan.ensure(2 * sizeof(int32_t))) || (rc = h->rfrag.ensure((size_t)((nn + 15) / 16) * 1024)) ||
-        (rc = h->unit_f.ensure(sizeof(int32_t) * slots)) || (rc = h->in_x1.ensure(sizeof(double) * 2 * nn)) ||
-        (rc = h->in_x2.ensure(sizeof(double) * 2 * nn)))
+    if ((rc = stage_unit_chunk(h, kind, MDRP_MEM_HOST, models, num_models, num_models, x1, x2, n, sq_threshold, nullptr, 0, false, true, v)) ||
+        (rc = h->unit_f.ensure(sizeof(int32_t) * num_models)))
         return rc;
-    HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
-    if ((rc = upload_iota(s, h->tags[0].p, num_models))) return rc;
-    const int32_t counts2[2] = {num_models, 0};
-    HIPCHK(hipMemcpyAsync(h->model_count[0].p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->surv_count.p, 0, sizeof(int32_t), s));
-    if ((rc = stage_unit_pair(h, h->in_x1.as<double>(), h->in_x2.as<double>(), n, sq_threshold))) return rc;
-    hipLaunchKernelGGL(k_frag_unit, dim3((n + 16 + 255) / 256), dim3(256), 0, s, n, h->pts.as<double>(), h->rfrag.as<uint4>());
-    RunParams rp;
-    std::memset(&rp, 0, sizeof rp);
-    rp.kind = kind; rp.batch = 1; rp.n_max = nn; rp.slot_stride = num_models; rp.mps = 4; rp.sample_sz = 3;
-    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->st.as<PairState>(), h->model_count[0].as<int32_t>(), 2, CNT_WG_MODELS, h->cplan.as<int32_t>(),
-                       (int32_t *)nullptr);
+    int32_t *cplan = h->cplan.as<int32_t>();
+    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, v.st, v.model_count, 2, CNT_WG_MODELS, cplan, (int32_t *)nullptr);
     const dim3 grid((unsigned)((num_models + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
-    MDRP_SWEEP_DISPATCH(k_count, kind, grid, dim3(CNT_THREADS), 0, s, rp, h->st.as<PairState>(), h->rfrag.as<uint4>(), h->models.as<Model>(),
-                        h->tags[0].as<uint32_t>(), h->model_count[0].as<int32_t>(), h->cplan.as<int32_t>(),
-                        h->tags_v.as<uint32_t>(), h->surv_count.as<int32_t>(), (unsigned long long *)nullptr, h->unit_f.as<int32_t>());
+    MDRP_SWEEP_DISPATCH(k_count, kind, grid, dim3(CNT_THREADS), 0, s, v.r, v.st, v.rfrag, v.models, v.tags, v.model_count, cplan, v.tags_v, v.surv1,
+                        (unsigned long long *)nullptr, h->unit_f.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(candidates, h->unit_f.p, sizeof(int32_t) * num_models, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return MDRP_OK;
 }
 
+// k_bound's two bounds of every model, the models as k_count's survivors, through the scheduler's launcher.
 int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
                       int n, double sq_threshold, double *score_lb, int32_t *count_ub) {
     if (!h || num_models < 0 || n < 0 || kind < 0 || kind > 5 || !score_lb || !count_ub || !models) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (num_models == 0) return MDRP_OK;
     MDRP_ENTER(h);
     hipStream_t s = h->stream;
-    const int nn = std::max(n, 1);
-    const size_t slots = (size_t)num_models;
+    ChunkView v;
+    Survivors sv;
+    hipEvent_t b0, b1;
     int rc;
-    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * nn)) || (rc = h->st.ensure(sizeof(PairState))) ||
-        (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) ||
-        (rc = h->tags[0].ensure(sizeof(uint32_t) * slots)) || (rc = h->tags_v.ensure(sizeof(uint32_t) * slots)) ||
-        (rc = h->surv_count.ensure(sizeof(int32_t))) || (rc = h->surv2_count.ensure(sizeof(int32_t))) ||
-        (rc = h->cplan.ensure(2 * sizeof(int32_t))) || (rc = h->unit_a.ensure(sizeof(double) * slots)) ||
-        (rc = h->unit_f.ensure(sizeof(int32_t) * slots)) || (rc = h->in_x1.ensure(sizeof(double) * 2 * nn)) ||
-        (rc = h->in_x2.ensure(sizeof(double) * 2 * nn)))
+    if ((rc = stage_unit_chunk(h, kind, MDRP_MEM_HOST, models, num_models, num_models, x1, x2, n, sq_threshold, nullptr, 0, true, false, v)) ||
+        (rc = h->unit_a.ensure(sizeof(double) * num_models)) || (rc = h->unit_f.ensure(sizeof(int32_t) * num_models)))
         return rc;
-    HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
-    if ((rc = upload_iota(s, h->tags_v.p, num_models))) return rc;
-    HIPCHK(hipMemcpyAsync(h->surv_count.p, &num_models, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->unit_a.p, 0, sizeof(double) * slots, s));
-    HIPCHK(hipMemsetAsync(h->unit_f.p, 0, sizeof(int32_t) * slots, s));
-    if ((rc = stage_unit_pair(h, h->in_x1.as<double>(), h->in_x2.as<double>(), n, sq_threshold))) return rc;
-    RunParams rp;
-    std::memset(&rp, 0, sizeof rp);
-    rp.kind = kind; rp.batch = 1; rp.n_max = nn; rp.slot_stride = num_models; rp.mps = 4; rp.sample_sz = 3;
-    hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, h->st.as<PairState>(), h->surv_count.as<int32_t>(), 1, BND_THREADS,
-                       h->cplan.as<int32_t>(), h->surv2_count.as<int32_t>());
-    const dim3 grid((unsigned)((num_models + BND_THREADS - 1) / BND_THREADS));
-    MDRP_SWEEP_DISPATCH(k_bound, kind, grid, dim3(BND_THREADS), 0, s, rp, h->st.as<PairState>(), h->pts.as<double>(), h->models.as<Model>(),
-                        h->tags_v.as<uint32_t>(), h->surv_count.as<int32_t>(), h->cplan.as<int32_t>(),
-                        h->tags[0].as<uint32_t>(), h->surv2_count.as<int32_t>(), (unsigned long long *)nullptr, h->unit_a.as<double>(), h->unit_f.as<int32_t>());
+    HIPCHK(hipMemsetAsync(h->unit_a.p, 0, sizeof(double) * num_models, s));
+    HIPCHK(hipMemsetAsync(h->unit_f.p, 0, sizeof(int32_t) * num_models, s));
+    h->ev_used = 0;
+    if ((rc = get_events(h, &b0, &b1, 4)) ||
+        (rc = launch_bound(h, s, kind, v, nullptr, h->unit_a.as<double>(), h->unit_f.as<int32_t>(), b0, b1, sv)))
+        return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(score_lb, h->unit_a.p, sizeof(double) * num_models, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(count_ub, h->unit_f.p, sizeof(int32_t) * num_models, hipMemcpyDeviceToHost, s));
@@ -1968,160 +2021,79 @@ int mdrp_bound_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
     return MDRP_OK;
 }
 
-// The armed stage train of one chunk on one pair: Pass::count, Pass::bound and Pass::score launch for launch, with the scheduler's buffer roles
-// (undecided list in the chunk's sorted list, partial counts in the other parity's, k_count's survivors in tags_v, k_bound's back in tags).
+// The armed stage train of one chunk on one pair, through the scheduler's own stage launchers (launch_count, launch_bound, launch_score) on the
+// one-pair view of the handle's buffers: what the flags choose is what Pass::count, Pass::bound and Pass::score decide in a run.
 // front_pick > 0 (mdrp_front_models): the train of a run's FIRST chunk instead — one count launch, no bound, the prefix retirement between the
 // count and the sweep (launch_front), k_score.  Models with a NaN in their pose are then what k_solve's NaN model is: slot state -3, on no list.
 static int retire_train(mdrp_handle *h, int kind, const mdrp_model *models, int num_models, const double *x1, const double *x2,
                         int n, double sq_threshold, uint64_t rec_cnt, double rec_score, const uint64_t *cand_stat_in, int flags, int front_pick,
                         double *scores, int32_t *counts, int32_t *left_at, int32_t *info, uint64_t *cand_stat_out) {
-    const int sweep = flags & (MDRP_RETIRE_SWEEP_SPLIT | MDRP_RETIRE_SWEEP_WAVE);
+    const Sweep sweep = (flags & MDRP_RETIRE_SWEEP_WAVE) ? Sweep::wave : ((flags & MDRP_RETIRE_SWEEP_SPLIT) ? Sweep::split : Sweep::tile);
     const auto nan_pose = [](const mdrp_model &m) {
         return m.q[0] != m.q[0] || m.q[1] != m.q[1] || m.q[2] != m.q[2] || m.q[3] != m.q[3] || m.t[0] != m.t[0] || m.t[1] != m.t[1] || m.t[2] != m.t[2];
     };
     MDRP_ENTER(h);
     hipStream_t s = h->stream;
-    const int nn = std::max(n, 1);
     const size_t slots = (size_t)num_models, tag_bytes = sizeof(uint32_t) * slots; // slot_stride = num_models: k_sort_tags writes the dense class from the back
     const bool armed = rec_score < DBL_MAX, two_phase = (flags & MDRP_RETIRE_TWO_PHASE) && armed; // (a run's first chunk has no record: no phase B)
+    // every slot as k_solve leaves a live one: "no record" until an exact sweep writes it
+    const std::vector<double> sc0(slots, DBL_MAX);
+    std::vector<int32_t> in0(slots, -2);
+    std::vector<uint32_t> list(slots);
+    int listed = 0;
+    for (int k = 0; k < num_models; ++k) {
+        if (front_pick > 0 && nan_pose(models[k])) in0[k] = -3;
+        else list[listed++] = (uint32_t)k;
+    }
+    ChunkView v;
     int rc;
-    if ((rc = h->pts.ensure(sizeof(double) * PT_STRIDE * nn)) || (rc = h->st.ensure(sizeof(PairState))) ||
-        (rc = h->models.ensure(sizeof(Model) * slots)) || (rc = h->slot_score.ensure(sizeof(double) * slots)) ||
-        (rc = h->slot_inl.ensure(sizeof(int32_t) * slots)) || (rc = h->tags[0].ensure(tag_bytes)) || (rc = h->tags_v.ensure(tag_bytes)) ||
-        (rc = h->tags_sorted[0].ensure(tag_bytes)) || (rc = h->tags_sorted[1].ensure(tag_bytes)) ||
-        (rc = h->model_count[0].ensure(2 * sizeof(int32_t))) || (rc = h->und_count.ensure(2 * sizeof(int32_t))) ||
-        (rc = h->surv_count.ensure(sizeof(int32_t))) || (rc = h->surv2_count.ensure(sizeof(int32_t))) ||
-        (rc = h->cand_stat.ensure(2 * sizeof(unsigned long long))) || (rc = h->cplan.ensure(2 * sizeof(int32_t))) ||
-        (rc = h->plan.ensure(sizeof(int32_t) * (2 + 2 + 4 + 16))) || (rc = h->rfrag.ensure((size_t)((nn + 15) / 16) * 1024)) ||
-        (rc = h->in_x1.ensure(sizeof(double) * 2 * nn)) || (rc = h->in_x2.ensure(sizeof(double) * 2 * nn)))
+    if ((rc = stage_unit_chunk(h, kind, MDRP_MEM_HOST, models, num_models, slots, x1, x2, n, sq_threshold, list.data(), listed, false, true, v, rec_cnt,
+                               rec_score)) ||
+        (rc = h->counters.ensure(sizeof(Counters))))
         return rc;
-    HIPCHK(hipMemcpyAsync(h->in_x1.p, x1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->in_x2.p, x2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->models.p, models, sizeof(Model) * num_models, hipMemcpyHostToDevice, s));
-    int listed = num_models;
-    {   // every slot as k_solve leaves a live one: "no record" until an exact sweep writes it
-        const std::vector<double> sc0(slots, DBL_MAX);
-        std::vector<int32_t> in0(slots, -2);
-        std::vector<uint32_t> list(slots);
-        if (front_pick > 0) {
-            listed = 0;
-            for (int k = 0; k < num_models; ++k) {
-                if (nan_pose(models[k])) in0[k] = -3;
-                else list[listed++] = (uint32_t)k;
-            }
-        } else
-            for (int k = 0; k < num_models; ++k) list[k] = (uint32_t)k;
-        HIPCHK(hipMemcpyAsync(h->tags[0].p, list.data(), tag_bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->slot_score.p, sc0.data(), sizeof(double) * slots, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->slot_inl.p, in0.data(), sizeof(int32_t) * slots, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s)); // (the vectors go out of scope)
-    }
-    const int32_t counts2[2] = {listed, 0};
     const unsigned long long cs_in[2] = {cand_stat_in[0], cand_stat_in[1]};
-    HIPCHK(hipMemcpyAsync(h->model_count[0].p, counts2, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->cand_stat.p, cs_in, sizeof cs_in, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->und_count.p, 0, 2 * sizeof(int32_t), s));
-    HIPCHK(hipMemsetAsync(h->surv_count.p, 0, sizeof(int32_t), s));
-    HIPCHK(hipMemsetAsync(h->surv2_count.p, 0, sizeof(int32_t), s));
-    if ((rc = stage_unit_pair(h, h->in_x1.as<double>(), h->in_x2.as<double>(), n, sq_threshold, rec_cnt, rec_score))) return rc;
-    hipLaunchKernelGGL(k_frag_unit, dim3((n + 16 + 255) / 256), dim3(256), 0, s, n, h->pts.as<double>(), h->rfrag.as<uint4>());
-    RunParams rp;
-    std::memset(&rp, 0, sizeof rp);
-    rp.kind = kind; rp.batch = 1; rp.n_max = nn; rp.chunk_len = (num_models + 3) / 4; rp.super_len = rp.chunk_len; rp.slot_stride = num_models; rp.mps = 4; rp.sample_sz = 3;
-    PairState *st = h->st.as<PairState>();
-    const Model *md = h->models.as<Model>();
-    uint32_t *tags = h->tags[0].as<uint32_t>(), *tags_v = h->tags_v.as<uint32_t>(), *tags_sorted = h->tags_sorted[0].as<uint32_t>();
-    int32_t *model_count = h->model_count[0].as<int32_t>(), *und_count = h->und_count.as<int32_t>(), *surv1 = h->surv_count.as<int32_t>(),
-            *surv2 = h->surv2_count.as<int32_t>(), *cplan = h->cplan.as<int32_t>();
-    // ---- Pass::count
-    {
-        unsigned long long *cand_stat = (flags & MDRP_RETIRE_TWO_PHASE) ? h->cand_stat.as<unsigned long long>() : nullptr; // null: the pair is never split
-        uint32_t *tags_u = tags_sorted;
-        int32_t *und_part = h->tags_sorted[1].as<int32_t>();
-        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, model_count, 2, CNT_WG_MODELS, cplan, surv1, (const int32_t *)nullptr,
-                           two_phase ? und_count : (int32_t *)nullptr);
-        const dim3 cgrid((unsigned)((num_models + CNT_WG_MODELS - 1) / CNT_WG_MODELS));
-        MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, rp, st, h->rfrag.as<uint4>(), md, tags, model_count, cplan, tags_v, surv1,
-                            (unsigned long long *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr, 1, tags_u, und_part, und_count,
-                            (const int32_t *)nullptr, cand_stat);
-        if (two_phase) {
-            hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, und_count, 2, CNT_WG_MODELS, cplan, (int32_t *)nullptr,
-                               (const int32_t *)nullptr, (int32_t *)nullptr);
-            MDRP_SWEEP_DISPATCH(k_count, kind, cgrid, dim3(CNT_THREADS), 0, s, rp, st, h->rfrag.as<uint4>(), md, tags_u, und_count, cplan, tags_v, surv1,
-                                (unsigned long long *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr, 2, (uint32_t *)nullptr, (int32_t *)nullptr,
-                                (int32_t *)nullptr, und_part, cand_stat);
-        }
-    }
-    // ---- Pass::bound
-    const uint32_t *sv_tags = tags_v;
-    const int32_t *sv_count = surv1;
-    if (flags & MDRP_RETIRE_BOUND) {
-        hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, surv1, 1, BND_THREADS, cplan, surv2, (const int32_t *)nullptr);
-        const dim3 bgrid((unsigned)((num_models + BND_THREADS - 1) / BND_THREADS));
-        MDRP_SWEEP_DISPATCH(k_bound, kind, bgrid, dim3(BND_THREADS), 0, s, rp, st, h->pts.as<double>(), md, tags_v, surv1, cplan, tags, surv2,
-                            (unsigned long long *)nullptr);
-        sv_tags = tags; sv_count = surv2;
-    }
-    // ---- Pass::front
+    unsigned long long *front_evals = &h->counters.as<Counters>()->progress.evals_sweep;
+    HIPCHK(hipMemcpyAsync(v.slot_score, sc0.data(), sizeof(double) * slots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(v.slot_inl, in0.data(), sizeof(int32_t) * slots, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(v.cand_stat, cs_in, sizeof cs_in, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
+    int32_t *plan = h->plan.as<int32_t>(), *totals = plan_totals(plan, 1);
+    Survivors sv{v.tags_v, v.surv1};
+    hipEvent_t c0, c1, b0, b1, f0, f1, e0, e1;
+    h->ev_used = 0;
+    // (a null cand_stat: the pair is never split)
+    if ((rc = get_events(h, &c0, &c1, 1)) ||
+        (rc = launch_count(h, s, kind, v, two_phase, nullptr, (flags & MDRP_RETIRE_TWO_PHASE) ? v.cand_stat : nullptr, c0, c1)))
+        return rc;
+    if ((flags & MDRP_RETIRE_BOUND) && ((rc = get_events(h, &b0, &b1, 4)) || (rc = launch_bound(h, s, kind, v, nullptr, nullptr, nullptr, b0, b1, sv))))
+        return rc;
     if (front_pick > 0) {
-        ChunkView v;
-        std::memset(&v, 0, sizeof v);
-        v.pc = 1; v.first_of_run = true; v.r = rp; v.st = st; v.pts = h->pts.as<double>(); v.models = h->models.as<Model>();
-        v.slot_score = h->slot_score.as<double>(); v.slot_inl = h->slot_inl.as<int32_t>(); v.model_count = model_count; v.surv1 = surv1; v.surv2 = surv2;
-        v.und_count = und_count; v.tags = tags; v.tags_sorted = tags_sorted; v.tags_sorted_other = h->tags_sorted[1].as<uint32_t>(); v.tags_v = tags_v;
-        Survivors sv{sv_tags, sv_count};
-        h->ev_used = 0; h->sweep_launches = 0;
-        if ((rc = h->counters.ensure(sizeof(Counters)))) return rc;
-        HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
-        int32_t *plan = h->plan.as<int32_t>();
-        if ((rc = launch_front(h, s, kind, v, front_pick, plan, plan + 2 * 1 + 2, &h->counters.as<Counters>()->progress.evals_sweep, sv))) return rc;
-        sv_tags = sv.tags; sv_count = sv.count;
+        h->sweep_launches = 1; // (mdrp_front_models reports the front's sweep)
+        if ((rc = get_events(h, &f0, &f1, 0)) || (rc = launch_front(h, s, kind, v, front_pick, plan, totals, front_evals, f0, f1, sv))) return rc;
     }
-    // ---- Pass::score
-    {
-        const bool wave = sweep == MDRP_RETIRE_SWEEP_WAVE, split = sweep == MDRP_RETIRE_SWEEP_SPLIT;
-        int32_t *plan = h->plan.as<int32_t>(), *totals = plan + 2 * 1 + 2;
-        if (wave) hipLaunchKernelGGL(k_count_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, st, sv_count, 1, SCW_THREADS / 64, plan, (int32_t *)nullptr,
-                                     (const int32_t *)nullptr, (int32_t *)nullptr);
-        hipLaunchKernelGGL(k_sort_tags, dim3(1), dim3(256), 0, s, rp, st, model_count, sv_count, sv_tags, tags_sorted);
-        if (!wave) hipLaunchKernelGGL(k_plan, dim3(1), dim3(PLAN_THREADS), 0, s, 1, model_count, plan, totals, split ? SPLIT_HYP : SCORE_THREADS);
-        const long long capped = (long long)h->num_cu * 32;
-        if (wave) {
-            const long long ub = (num_models + SCW_THREADS / 64 - 1) / (SCW_THREADS / 64);
-            MDRP_SWEEP_DISPATCH(k_score_w, kind, dim3((unsigned)std::min(ub, capped)), dim3(SCW_THREADS), 0, s, rp, st, h->pts.as<double>(), md, tags_sorted,
-                                model_count, h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan);
-        } else if (split) {
-            const long long ub = (num_models + SPLIT_HYP - 1) / SPLIT_HYP + 1;
-            MDRP_SWEEP_DISPATCH(k_score_split, kind, dim3((unsigned)std::min(ub, capped)), dim3(SPLIT_THREADS), 0, s, rp, st, h->pts.as<double>(), md,
-                                tags_sorted, model_count, h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan, totals);
-        } else {
-            const dim3 grid((unsigned)((num_models + SCORE_THREADS - 1) / SCORE_THREADS));
-            MDRP_SWEEP_DISPATCH(k_score, kind, grid, dim3(SCORE_THREADS), SCORE_TILE_BYTES, s, rp, st, h->pts.as<double>(), md, tags_sorted, model_count,
-                                h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), plan, totals);
-        }
-    }
+    if ((rc = get_events(h, &e0, &e1, 0)) || (rc = launch_score(h, s, kind, v, sv, sweep, plan, totals, e0, e1))) return rc;
     HIPCHK(hipGetLastError());
     // ---- the slots, and who left where: from the survivor lists of the two stages (tags_v and tags are not written behind the bound)
+    const FrontLists f = front_lists(v);
     std::vector<uint32_t> list1(slots), list2(slots);
     int32_t n_und[2] = {0, 0}, n1 = 0, n2 = 0;
     unsigned long long cs_out[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(scores, h->slot_score.p, sizeof(double) * slots, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(counts, h->slot_inl.p, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(list1.data(), tags_v, tag_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(list2.data(), tags, tag_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_und, und_count, sizeof n_und, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&n1, surv1, sizeof n1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&n2, surv2, sizeof n2, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(cs_out, h->cand_stat.p, sizeof cs_out, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(scores, v.slot_score, sizeof(double) * slots, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(counts, v.slot_inl, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(list1.data(), v.tags_v, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(list2.data(), v.tags, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_und, v.und_count, sizeof n_und, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&n1, v.surv1, sizeof n1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&n2, v.surv2, sizeof n2, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cs_out, v.cand_stat, sizeof cs_out, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const bool bound = (flags & MDRP_RETIRE_BOUND) != 0;
     if (front_pick > 0) {
-        // the front's lists are where it left them: P in the solver-order list (list2), the rest list in the other parity's sorted list, the kept
-        // list back in tags_v (list1); their counters in surv2 (n2), und_count (n_und[0]) and surv1 (n1)
+        // the front's lists are where it left them (front_lists): the picked list is list2, the kept list list1; their counters n2, n_und[0] and n1
         std::vector<uint32_t> rest(slots);
         unsigned long long evals = 0;
-        HIPCHK(hipMemcpyAsync(rest.data(), h->tags_sorted[1].p, tag_bytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&evals, &h->counters.as<Counters>()->progress.evals_sweep, sizeof evals, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(rest.data(), f.rest, tag_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&evals, front_evals, sizeof evals, hipMemcpyDeviceToHost, s));
         if ((rc = finish_timing(h))) return rc;
         const int np = n2, nr = n_und[0];
         if (np < 0 || np > FIRST_PICK_MAX + 1 || nr < 0 || np + nr > listed || n1 < 0 || n1 > nr) { g_err = "front_models: list counts out of range"; return MDRP_ERR_INVALID; }
@@ -2169,9 +2141,10 @@ int mdrp_front_models(mdrp_handle *h, int kind, const mdrp_model *models, int nu
                         left_at, info, stat_out);
 }
 
-// The bookkeeping train of one super-chunk on caller-given slot tables: Pass::scan per chunk, Pass::lo's plan and Pass::walk launch for launch, with
-// the scheduler's buffer roles (slots of chunk c at chunk_off * mps in the pair's slot row, triggers appended to the pair's list, the LO plan in
-// work_pair, the progress record in the counter block, budgets in the params block, checkpoints in ckpt).  k_lo's part is played by the host.
+// The bookkeeping train of one super-chunk on caller-given slot tables: the scan per chunk and the walk through the scheduler's own launchers
+// (launch_scan, launch_walk), Pass::lo's plan kernel between them, with the scheduler's buffer roles (slots of chunk c at chunk_off * mps in the
+// pair's slot row, triggers appended to the pair's list, the LO plan in work_pair, the progress record in the counter block, budgets in the params
+// block, checkpoints in ckpt).  k_lo's part is played by the host.
 int mdrp_replay_slots(mdrp_handle *h, const mdrp_ransac_opt *ro, mdrp_replay *io) {
     if (!h || !ro || !io) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     const int mps = io->mps, batch = io->batch, n_chunks = io->n_chunks, n_bud = io->budgets ? io->n_budgets : 0;
@@ -2283,12 +2256,8 @@ int mdrp_replay_slots(mdrp_handle *h, const mdrp_ransac_opt *ro, mdrp_replay *io
     }
     HIPCHK(hipMemcpyAsync(trig, trig_host.data(), sizeof(Trigger) * trig_host.size(), hipMemcpyHostToDevice, s));
     // ---- Pass::walk
-    if (n_bud)
-        hipLaunchKernelGGL(k_walk_ckpt, dim3((batch + WALK_CKPT_THREADS - 1) / WALK_CKPT_THREADS), dim3(WALK_CKPT_THREADS), 0, s, rp, st, h->models.as<Model>(), trig,
-                           trig_cap, &cnt->progress.n_active, &cnt->progress.max_needed, h->params.as<uint64_t>(), n_bud, h->ckpt.as<PairState>());
-    else
-        hipLaunchKernelGGL(k_walk, dim3((batch + 63) / 64), dim3(64), 0, s, rp, st, h->models.as<Model>(), trig, trig_cap, &cnt->progress.n_active,
-                           &cnt->progress.max_needed, (const int32_t *)nullptr, 0, 0, 0);
+    launch_walk(s, batch, rp, st, h->models.as<Model>(), trig, trig_cap, &cnt->progress, n_bud ? h->params.as<uint64_t>() : nullptr, n_bud,
+                h->ckpt.as<PairState>());
     HIPCHK(hipGetLastError());
     // ---- Pass::read_progress, and the states
     Progress pr;
@@ -2302,9 +2271,9 @@ int mdrp_replay_slots(mdrp_handle *h, const mdrp_ransac_opt *ro, mdrp_replay *io
     return MDRP_OK;
 }
 
-// k_first_pick and k_first_filter alone on caller-given survivor lists and slot tables, with Pass::front's buffer roles: the survivors and the kept
-// list share tags_v and their counters surv1 (the filter overwrites what the pick has consumed), P in the solver-order list with its counter in surv2,
-// the rest list in the other parity's sorted list with its counter at stride 2 in und_count.  k_first_score's part is played by the caller's tables.
+// The front's pick and filter alone (launch_front_pick, launch_front_filter: the scheduler's own) on caller-given survivor lists and slot tables, in
+// the front's lists (front_lists) of a view of the whole batch; the survivors arrive where the kept list will be (the filter overwrites what the
+// pick has consumed).  k_first_score's part is played by the caller's tables.
 static_assert(FIRST_PICK_MAX == sched::FIRST_PICK_LIMIT, "k_first_filter's LDS tables hold what the scheduler may pick");
 int mdrp_front_lists(mdrp_handle *h, mdrp_front_tables *io) {
     if (!h || !io) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
@@ -2338,37 +2307,35 @@ int mdrp_front_lists(mdrp_handle *h, mdrp_front_tables *io) {
         ps.n = io->n[p]; ps.active = io->active[p]; ps.sq_thr = io->sq_thr[p]; ps.eps = std::sqrt(io->sq_thr[p]); ps.best_min_score = DBL_MAX;
         n_max = std::max(n_max, ps.n);
     }
-    PairState *st = h->st.as<PairState>();
-    uint32_t *tags_pick = h->tags[0].as<uint32_t>(), *tags_rest = h->tags_sorted[1].as<uint32_t>(), *tags_v = h->tags_v.as<uint32_t>();
-    int32_t *surv1 = h->surv_count.as<int32_t>(), *surv2 = h->surv2_count.as<int32_t>(), *und_count = h->und_count.as<int32_t>();
-    unsigned long long *evals = &h->counters.as<Counters>()->progress.evals_sweep;
-    HIPCHK(hipMemcpyAsync(st, st_host.data(), sizeof(PairState) * b, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->slot_score.p, io->slot_score, sizeof(double) * all, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->slot_inl.p, io->slot_inl, sizeof(int32_t) * all, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(tags_v, io->tags, tag_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(surv1, io->count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(tags_pick, io->tags_pick, tag_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(tags_rest, io->tags_rest, tag_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(surv2, io->pick_count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(und_count, io->rest_count, sizeof(int32_t) * 2 * b, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
     RunParams rp;
     std::memset(&rp, 0, sizeof rp);
     rp.batch = batch; rp.n_max = n_max; rp.chunk_len = slots / 4; rp.super_len = rp.chunk_len; rp.slot_stride = slots; rp.mps = 4; rp.sample_sz = 3;
-    hipLaunchKernelGGL(k_first_pick, dim3(batch), dim3(FIRST_THREADS), 0, s, rp, st, surv1, tags_v, io->pick, tags_pick, surv2, tags_rest, und_count);
+    const ChunkView v = probe_view(h, rp);
+    const FrontLists f = front_lists(v);
+    unsigned long long *evals = &h->counters.as<Counters>()->progress.evals_sweep;
+    HIPCHK(hipMemcpyAsync(v.st, st_host.data(), sizeof(PairState) * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(v.slot_score, io->slot_score, sizeof(double) * all, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(v.slot_inl, io->slot_inl, sizeof(int32_t) * all, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f.kept, io->tags, tag_bytes, hipMemcpyHostToDevice, s)); // (k_count's survivors, where the kept list will be)
+    HIPCHK(hipMemcpyAsync(f.n_kept, io->count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f.pick, io->tags_pick, tag_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f.rest, io->tags_rest, tag_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f.n_pick, io->pick_count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f.n_rest, io->rest_count, sizeof(int32_t) * 2 * b, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
+    launch_front_pick(s, v, Survivors{f.kept, f.n_kept}, io->pick);
     // the pick has consumed the survivors: what the caller put into the kept list and its counter takes their place, so that an inactive pair's stay
-    HIPCHK(hipMemcpyAsync(tags_v, io->tags_out, tag_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(surv1, io->surv_count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_first_filter, dim3(batch), dim3(FIRST_THREADS), 0, s, rp, st, h->slot_score.as<double>(), h->slot_inl.as<int32_t>(), tags_pick, surv2,
-                       tags_rest, und_count, tags_v, surv1, evals);
+    HIPCHK(hipMemcpyAsync(f.kept, io->tags_out, tag_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f.n_kept, io->surv_count, sizeof(int32_t) * b, hipMemcpyHostToDevice, s));
+    (void)launch_front_filter(s, v, evals);
     HIPCHK(hipGetLastError());
     unsigned long long ev = 0;
-    HIPCHK(hipMemcpyAsync(io->tags_pick, tags_pick, tag_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(io->tags_rest, tags_rest, tag_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(io->tags_out, tags_v, tag_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(io->pick_count, surv2, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(io->rest_count, und_count, sizeof(int32_t) * 2 * b, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(io->surv_count, surv1, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->tags_pick, f.pick, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->tags_rest, f.rest, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->tags_out, f.kept, tag_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->pick_count, f.n_pick, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->rest_count, f.n_rest, sizeof(int32_t) * 2 * b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->surv_count, f.n_kept, sizeof(int32_t) * b, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     *io->evals = ev;
