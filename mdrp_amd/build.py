@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "mdrp_capi.hip")
 SRC_TU = os.path.join(HERE, "csrc", "mdrp_tu.hip")  # secondary translation units: one compile per group of kernel instantiations
 TU_GROUPS = (1, 2, 3, 4, 5, 6)                       # k_final at 64 lanes | k_final at 256 lanes | 5- / 6- / 7-point baselines | k_from_model | k_prior | kc_from_model, kc_prior (mdrp_instances.h)
-DEPS = [SRC, SRC_TU, os.path.join(HERE, "csrc", "mdrp_capi_entry.h"), os.path.join(HERE, "csrc", "mdrp_kernels.h"), os.path.join(HERE, "csrc", "mdrp_math.h"),
+DEPS = [SRC, SRC_TU, os.path.join(HERE, "csrc", "mdrp_capi_entry.h"), os.path.join(HERE, "csrc", "mdrp_kernels.h"), os.path.join(HERE, "csrc", "mdrp_tail.h"), os.path.join(HERE, "csrc", "mdrp_math.h"),
         os.path.join(HERE, "csrc", "mdrp_classic.h"), os.path.join(HERE, "csrc", "mdrp_classic_math.h"),
         os.path.join(HERE, "csrc", "mdrp_logtab.h"), os.path.join(HERE, "csrc", "mdrp_instances.h"),
         os.path.join(HERE, "csrc", "mdrp_frontend.h"), os.path.join(HERE, "csrc", "mdrp_schedule.h"),

@@ -4,10 +4,11 @@
 // The sampler, the three scoring sweeps (k_count on the matrix cores, k_bound, k_score), k_scan, k_lo_plan and k_walk are the
 // monodepth path's own kernels (a fundamental matrix travels in the first nine doubles of a Model: RAWF instantiations);
 // this file adds what differs: the normalisation (kc_prep), samples of K > 3 points (kc_samples), the minimal solvers
-// (kc_solve, mdrp_classic_math.h), and the Sampson-only LM of refine_relpose @0x258f50 / refine_fundamental @0x2590d0 with
-// the estimators' LO rules (kc_lo) and final stage (kc_final).
+// (kc_solve, mdrp_classic_math.h), the Sampson-only LM of refine_relpose @0x258f50 / refine_fundamental @0x2590d0 with the
+// estimators' LO rule (clm_lo), and the family's descriptor (ClassicFam) for the stage bodies of mdrp_tail.h, which kc_lo and
+// kc_final wrap.
 #pragma once
-#include "mdrp_kernels.h"
+#include "mdrp_tail.h"
 #include "mdrp_classic_math.h"
 
 namespace mdrp {
@@ -778,9 +779,7 @@ __device__ void cblock_score(const Model &m, const double *__restrict__ pts, int
 // kept only if more than the sample size), FundamentalEstimator on all correspondences; 25 iterations, TRUNCATED at eps
 template <int CK, int T>
 __device__ void clm_lo(Model &m, const PairState &ps, const double *__restrict__ pp, uint8_t *__restrict__ wg_mask, double *scratch, ClmList &cl) {
-    LmOpt o;
-    o.max_it = 25; o.loss = 1; o.loss_scale = ps.lo_loss_scale;
-    o.grad_tol = 1e-10; o.step_tol = 1e-8; o.lambda0 = 1e-3; o.lambda_min = 1e-10; o.lambda_max = 1e10;
+    const LmOpt o = lo_opt(ps);
     if (CK == CLASSIC_FUND) { clm_refine<CK, T>(m, pp, ps.n, nullptr, o, scratch, cl); return; }
     double sc;
     int ni;
@@ -789,60 +788,9 @@ __device__ void clm_lo(Model &m, const PairState &ps, const double *__restrict__
     __syncthreads(); // wg_mask is rewritten by the next problem
 }
 
-// ------------------------------------------------------------------------------------------------ LO
-template <int CK, int T>
-__global__ __launch_bounds__(T, 2) void kc_lo(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ pts,
-                                              const Model *__restrict__ models, Trigger *__restrict__ triggers, int trig_cap,
-                                              const int32_t *__restrict__ plan, int32_t *__restrict__ head /*zeroed*/,
-                                              int32_t *__restrict__ xheads /*zeroed, or null: lo_take (mdrp_kernels.h)*/,
-                                              uint8_t *__restrict__ lo_mask /*[gridDim.x][n_max]*/, int list_stride /*2 * list_stride u16 of dynamic LDS, or 0*/,
-                                              FuseTail fz /*ready == null: off*/) {
-    extern __shared__ uint16_t clm_dyn_list[];
-    __shared__ double scratch[4 * MAX_ACC];
-    __shared__ ClmList cl;
-    __shared__ int s_item;
-    if (threadIdx.x == 0) { cl.list = clm_dyn_list; cl.stride = list_stride; }
-    const int32_t *prefix = plan, *begin = plan + rp.batch + 1, *end = begin + rp.batch;
-    const int total = plan[3 * (size_t)rp.batch + 1];
-    uint8_t *wg_mask = lo_mask + (size_t)blockIdx.x * rp.n_max;
-    if (fz.ready && threadIdx.x == 0) { // fused tail (mdrp_kernels.h FuseTail): pairs without a trigger in this launch are ready as they are
-        for (int p = blockIdx.x; p < rp.batch; p += gridDim.x)
-            if (end[p] == begin[p]) fuse_publish(fz, rp, p, models, triggers, trig_cap);
-        atomicAdd(fz.ctl + 1, 1);
-    }
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_item = lo_take(head, xheads, total);
-        __syncthreads();
-        const int w = s_item;
-        if (w >= total) break;
-        const int pair = plan_find(prefix, rp.batch, w);
-        const int pos = begin[pair] + (w - prefix[pair]);
-        const PairState &ps = st[pair];
-        Trigger &tr = triggers[(size_t)pair * trig_cap + pos];
-        const size_t slot_base = (size_t)pair * rp.slot_stride;
-        Model m = models[slot_base + (size_t)tr.iter * rp.mps + tr.k_ref];
-        const double *pp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
-        clm_lo<CK, T>(m, ps, pp, wg_mask, scratch, cl);
-        double sc;
-        int cn;
-        cblock_score<CK, T>(m, pp, ps.n, ps.sq_thr, scratch, sc, cn, nullptr);
-        if (threadIdx.x == 0) {
-            tr.refined = m; tr.ref_score = sc; tr.ref_cnt = cn;
-            if (fz.ready) {
-                __threadfence(); // this trigger's results before the count
-                if (atomicAdd(fz.done_cnt + pair, 1) + 1 == end[pair] - begin[pair]) {
-                    __threadfence(); // the other triggers' results (written on other CUs / XCDs) before the replay reads them
-                    fuse_publish(fz, rp, pair, models, triggers, trig_cap);
-                }
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ final
-// the estimators' way out of their normalised coordinates (cfinal_pair; kc_from_model, mdrp_classic_models.h): the focal back to pixels,
-// the fundamental matrix back to pixel coordinates with unit Frobenius norm
+// ------------------------------------------------------------------------------------------------ the family's descriptor (mdrp_tail.h)
+// the estimators' way out of their normalised coordinates: the focal back to pixels, the fundamental matrix back to pixel coordinates with unit
+// Frobenius norm
 template <int CK>
 __device__ __forceinline__ void classic_unnormalize(Model &best, const PairState &ps) {
     if (CK == CLASSIC_FUND) { // F <- T2' F T1, T = [1/s 0 -cx/s; 0 1/s -cy/s; 0 0 1], unit Frobenius norm
@@ -865,43 +813,80 @@ __device__ __forceinline__ void classic_unnormalize(Model &best, const PairState
     if (CK == CLASSIC_SHARED) { best.f1 *= ps.norm; best.f2 *= ps.norm; } // back to pixels
 }
 
-// ransac<> tail + get_inliers + the estimator's inlier-only refinement with the user's BundleOptions (estimate_relative_pose
-// @0x21f800: if more than 5 inliers; estimate_fundamental @0x221a00: more than 7, then F <- T2' F T1 / |.|)
-template <int CK, int T>
-__device__ void cfinal_pair(const RunParams &rp, const PairState &ps, const double *__restrict__ pts, uint8_t *__restrict__ mask_all,
-                            ResultDev *__restrict__ results, int pair, double *scratch, ClmList &cl) {
-    ResultDev res;
-    res.model = ps.best;
-    res.refinements = ps.refinements; res.iterations = ps.iterations; res.num_inliers = ps.num_inliers;
-    res.inlier_ratio = ps.inlier_ratio; res.model_score = ps.model_score;
-    const FinalRows row = final_rows(rp, pair);
-    uint8_t *mask = mask_all + (size_t)row.out * rp.n_max;
-    if (ps.n < ClassicTraits<CK>::K) {
-        for (int i = threadIdx.x; i < rp.n_max; i += T) mask[i] = 0;
-        if (threadIdx.x == 0) results[row.out] = res;
-        return;
+// The caller's model in the estimator's units (the way in; classic_unnormalize is the way out).
+//   5-point: as it is (the cameras unproject the points; t is not renormalised)
+//   6-point: f / norm
+//   7-point: F_n = T2^-T (F T1^-1) with T^-1 = [s 0 cx; 0 s cy; 0 0 1] per image, s = norm: classic_unnormalize's loops on the inverse
+//            transforms, no rescaling
+// space 1: the record is in the estimator's normalised coordinates already and is taken as it stands.
+template <int CK>
+__device__ __forceinline__ Model classic_model_start(const Model *__restrict__ m0, const PairState &ps, int space) {
+    Model x = *m0;
+    if (space != 0) return x;
+    if (CK == CLASSIC_SHARED) { x.f1 /= ps.norm; x.f2 /= ps.norm; }
+    if (CK == CLASSIC_FUND) {
+        double *F = model_F(x);
+        const double s = ps.norm;
+        const double T1[9] = {s, 0, ps.cen[0], 0, s, ps.cen[1], 0, 0, 1}, T2[9] = {s, 0, ps.cen[2], 0, s, ps.cen[3], 0, 0, 1};
+        double M[9], O[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) M[3 * i + j] = F[3 * i] * T1[j] + F[3 * i + 1] * T1[3 + j] + F[3 * i + 2] * T1[6 + j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) O[3 * i + j] = T2[i] * M[j] + T2[3 + i] * M[3 + j] + T2[6 + i] * M[6 + j];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) F[i] = O[i];
     }
-    const double *pp = pts + (size_t)row.rec * rp.n_max * PT_STRIDE;
-    Model m = ps.best;
-    for (int i = ps.n + threadIdx.x; i < rp.n_max; i += T) mask[i] = 0;
-    clm_lo<CK, T>(m, ps, pp, mask, scratch, cl); // the output mask doubles as the LO's subset mask
-    res.refinements++;
-    double sc;
-    int cn;
-    cblock_score<CK, T>(m, pp, ps.n, ps.sq_thr, scratch, sc, cn, nullptr);
-    Model best = ps.best;
-    if (sc < ps.model_score) { best = m; res.num_inliers = (uint64_t)cn; } // score / ratio NOT updated (reference)
-    cblock_score<CK, T>(best, pp, ps.n, ps.sq_thr, scratch, sc, cn, mask);
-    if (res.num_inliers > (uint64_t)ClassicTraits<CK>::K) {
-        LmOpt f;
-        f.max_it = rp.final_max_it; f.loss = rp.final_loss; f.loss_scale = ps.final_loss_scale;
-        f.grad_tol = rp.grad_tol; f.step_tol = rp.step_tol; f.lambda0 = rp.lambda0; f.lambda_min = rp.lambda_min; f.lambda_max = rp.lambda_max;
-        clm_refine<CK, T>(best, pp, ps.n, mask, f, scratch, cl);
-    }
-    classic_unnormalize<CK>(best, ps);
-    res.model = best;
-    if (threadIdx.x == 0) results[row.out] = res;
+    return x;
 }
+
+struct ClmShared {
+    double scratch[4 * MAX_ACC];
+    ClmList cl; // cl.list: dynamic LDS, 2 * stride u16, or stride 0
+};
+// The baselines behind the stage bodies of mdrp_tail.h.  Inlier-only refinement: estimate_relative_pose @0x21f800 with more than 5 inliers,
+// estimate_fundamental @0x221a00 with more than 7 (then F <- T2' F T1 / |.|).  The LO always runs, on its subset mask (clm_lo), and always counts.
+template <int CK, int T_>
+struct ClassicFam {
+    static constexpr int T = T_, MIN_N = ClassicTraits<CK>::K, MIN_INLIERS = ClassicTraits<CK>::K;
+    using Lds = ClmShared;
+    const RunParams &rp;
+    const double *pts;
+    Lds &sh;
+    __device__ __forceinline__ const double *pp(int row) const { return pts + (size_t)row * rp.n_max * PT_STRIDE; }
+    __device__ __forceinline__ void score(const Model &m, int row, const PairState &ps, double &sc, int &cn, uint8_t *__restrict__ mask) const {
+        cblock_score<CK, T>(m, pp(row), ps.n, ps.sq_thr, sh.scratch, sc, cn, mask);
+    }
+    __device__ __forceinline__ void lo(Model &m, int row, const PairState &ps, uint8_t *__restrict__ subset) const {
+        clm_lo<CK, T>(m, ps, pp(row), subset, sh.scratch, sh.cl);
+    }
+    __device__ __forceinline__ bool lo_counts(const Model &) const { return true; } // (kc_from_model has returned for a record without a model)
+    __device__ __forceinline__ void refine_inliers(Model &m, int row, const PairState &ps, const uint8_t *__restrict__ mask, const LmOpt &o) const {
+        clm_refine<CK, T>(m, pp(row), ps.n, mask, o, sh.scratch, sh.cl);
+    }
+    __device__ __forceinline__ Model start(const Model *__restrict__ m0, const PairState &ps, int space) const { return classic_model_start<CK>(m0, ps, space); }
+    __device__ __forceinline__ void finish(Model &x, const PairState &ps) const { classic_unnormalize<CK>(x, ps); }
+    __device__ __forceinline__ void end_problem() const {}
+};
+
+// ------------------------------------------------------------------------------------------------ LO, final
+template <int CK, int T>
+__global__ __launch_bounds__(T, 2) void kc_lo(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ pts,
+                                              const Model *__restrict__ models, Trigger *__restrict__ triggers, int trig_cap,
+                                              const int32_t *__restrict__ plan, int32_t *__restrict__ head /*zeroed*/,
+                                              int32_t *__restrict__ xheads /*zeroed, or null: lo_take*/,
+                                              uint8_t *__restrict__ lo_mask /*[gridDim.x][n_max]*/, int list_stride /*2 * list_stride u16 of dynamic LDS, or 0*/,
+                                              FuseTail fz /*ready == null: off*/) {
+    extern __shared__ uint16_t clm_dyn_list[];
+    __shared__ ClmShared sh;
+    __shared__ int s_item;
+    if (threadIdx.x == 0) { sh.cl.list = clm_dyn_list; sh.cl.stride = list_stride; }
+    lo_queue(ClassicFam<CK, T>{rp, pts, sh}, rp, st, models, triggers, trig_cap, plan, head, xheads, lo_mask + (size_t)blockIdx.x * rp.n_max, fz, s_item);
+}
+
 template <int CK, int T>
 __global__ __launch_bounds__(T, 2) void kc_final(RunParams rp, PairState *__restrict__ st, const double *__restrict__ pts,
                                                  uint8_t *__restrict__ mask_all, ResultDev *__restrict__ results,
@@ -910,37 +895,19 @@ __global__ __launch_bounds__(T, 2) void kc_final(RunParams rp, PairState *__rest
                                                  unsigned long long ticks, unsigned long long *__restrict__ timeouts /*fused: expired bounded waits*/,
                                                  int list_stride /*2 * list_stride u16 of dynamic LDS, or 0*/) {
     extern __shared__ uint16_t clm_dyn_list[];
-    __shared__ double scratch[4 * MAX_ACC];
-    __shared__ ClmList cl;
+    __shared__ ClmShared sh;
     __shared__ int s_pair;
-    if (threadIdx.x == 0) { cl.list = clm_dyn_list; cl.stride = list_stride; }
-    __syncthreads();
-    __shared__ __attribute__((aligned(16))) unsigned int s_ps[(sizeof(PairState) + 3) / 4];
-    if (!ready) {
-        if (fin_done && fin_done[blockIdx.x]) return; // (uniform) the pass behind a fused tail: only what that left undone
-        cfinal_pair<CK, T>(rp, st[blockIdx.x], pts, mask_all, results, blockIdx.x, scratch, cl);
-        return;
-    }
-    if (threadIdx.x == 0) { // fused tail: the blockIdx-th pair to become ready, bounded wait (k_final / k_gate, mdrp_kernels.h)
-        int p;
-        const unsigned long long t0 = wall_clock64();
-        // polled RELAXED, one acquire fence when the pair is there (see k_final, mdrp_kernels.h)
-        while ((p = __hip_atomic_load(ready + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < 0 && wall_clock64() - t0 < ticks)
-            __builtin_amdgcn_s_sleep(16);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        if (p < 0 && timeouts) atomicAdd(timeouts, 1ull); // gave up: the pass behind the LO launch refines this pair (mdrp_stats.fuse_wait_timeouts)
-        __threadfence();
-        s_pair = p;
+    __shared__ __attribute__((aligned(16))) unsigned int s_ps[PAIR_STATE_WORDS];
+    if (threadIdx.x == 0) {
+        sh.cl.list = clm_dyn_list; sh.cl.stride = list_stride;
+        s_pair = final_take(ready, fin_done, ticks, timeouts);
     }
     __syncthreads();
     if (s_pair < 0) return;
-    {
-        const volatile unsigned int *src = reinterpret_cast<const volatile unsigned int *>(st + s_pair);
-        for (int i = threadIdx.x; i < (int)(sizeof(PairState) / 4); i += T) s_ps[i] = src[i];
-    }
+    stage_pair<T>(s_ps, st + s_pair);
     __syncthreads();
-    cfinal_pair<CK, T>(rp, *reinterpret_cast<const PairState *>(s_ps), pts, mask_all, results, s_pair, scratch, cl);
-    if (threadIdx.x == 0) fin_done[s_pair] = 1;
+    final_pair(ClassicFam<CK, T>{rp, pts, sh}, rp, *reinterpret_cast<const PairState *>(s_ps), mask_all, results, s_pair);
+    if (ready && threadIdx.x == 0) fin_done[s_pair] = 1;
 }
 
 // ------------------------------------------------------------------------------------------------ unit-parity kernels

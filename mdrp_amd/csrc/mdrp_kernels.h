@@ -2389,498 +2389,6 @@ __device__ __forceinline__ void block_score(int kind, const Model &m, const doub
     score_out = v[0] + thr * (double)(n - cnt_out);
 }
 
-// ------------------------------------------------------------------------------------------------ LO
-// Persistent workgroups pop (pair, trigger) items; each refines the triggering minimal model (refine_model
-// @0x4fa550/@0x4fad60/@0x4fb0a0: 25 it, TRUNCATED) and rescoring it.
-#define MDRP_LM_MINWAVES 2
-// LO work plan of one chunk: the triggers the chunk's scan appended to each pair's list, as a prefix sum over the pairs.
-// The plan is frozen when it is built (begin/end per pair), so k_lo of this chunk can run on a second stream while the
-// next chunk's scan keeps appending triggers — the LO of the first, short chunk (most of a run's LO work: records fall
-// fast at the start) hides behind the second chunk's sweep instead of leaving the chip to the tail of a launch whose
-// single problems take ~1 ms on one wavefront.
-// (Measured and dropped: longest-first ordering by inlier count — no change.  XCD-affine queues, pair p on XCD p mod 8: 2.8x less HBM
-// fetch, same time in round 2; as contiguous eighths of the plan with stealing (lo_take, round 4) 2-5 % of k_lo: the LO is bound by
-// instruction issue at 1-2 waves/SIMD, not by bandwidth or order.)
-// plan layout: prefix[B+1] | begin[B] | end[B] | total
-MDRP_GLOBAL __launch_bounds__(PLAN_THREADS) void k_lo_plan(int batch, const PairState *__restrict__ st, const int32_t *__restrict__ prev_plan /*or null*/,
-                                                          int32_t *__restrict__ plan) {
-    __shared__ int s_w[PLAN_THREADS / 64 + 1];
-    int32_t *prefix = plan, *begin = plan + batch + 1, *end = begin + batch;
-    const int32_t *prev_end = prev_plan ? prev_plan + 2 * (size_t)batch + 1 : nullptr;
-    int run = 0;
-    for (int p0 = 0; p0 < batch; p0 += PLAN_THREADS) {
-        const int p = p0 + threadIdx.x;
-        int b = 0, e = 0;
-        if (p < batch) { b = prev_end ? prev_end[p] : 0; e = st[p].n_triggers; if (e < b) e = b; }
-        int tot;
-        const int ex = plan_block_scan(e - b, tot, s_w);
-        if (p < batch) { prefix[p] = run + ex; begin[p] = b; end[p] = e; }
-        run += tot;
-    }
-    if (threadIdx.x == 0) { prefix[batch] = run; plan[3 * (size_t)batch + 1] = run; }
-}
-
-// ------------------------------------------------------------------------------------------------ walk
-// One lane per pair replays score_models<> / ransac<> bookkeeping (@0x22ebc0, @0x22f030) over the ordered triggers
-// and applies the dynamic stopping rule.
-// lo_plans / n_plans / lo_cap: the LM engine refines at most lo_cap triggers of a chunk per pass (its problem table is sized
-// before anyone knows how many triggers the scans will find); if a chunk found more, nothing is replayed yet — the flag
-// n_active[1] tells the host to run the remaining passes and launch the walk again.
-// Replay of one pair (one lane).  Returns true if the pair has stopped; otherwise `need` = iterations it still certainly needs.
-// COHERENT: the LO results in the triggers were written by other workgroups of the SAME launch (fused tail): they are read with
-// agent-scope atomic loads, which neither the compiler (restrict / invariance reasoning) nor the scalar cache can serve from
-// anything older than the acquire that preceded the call.
-__device__ __forceinline__ double coherent_f64(const double *p) {
-    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-// (uint64_t) of a double as the reference's x86-64 build computes it (comisd against 2^63; cvttsd2si; the high half via d - 2^63 and a flipped top
-// bit): what the dynamic iteration bound becomes when it leaves the range — success_prob = 1 gives +inf -> 0 (the search ends right after
-// min_iterations), NaN (success_prob > 1) gives 2^63 (never), a negative bound wraps.  v_cvt saturates instead.  tests/golden/edge_options_ref.npz
-__device__ __forceinline__ uint64_t f64_to_u64_x86(double d) {
-    const double t63 = 9223372036854775808.0;
-    if (d >= t63) {
-        const double e = d - t63;
-        return (e < t63 ? (uint64_t)(int64_t)e : 0x8000000000000000ull) ^ 0x8000000000000000ull;
-    }
-    return d >= -t63 ? (uint64_t)(int64_t)d : 0x8000000000000000ull; // (NaN fails both comparisons: cvttsd2si's "integer indefinite")
-}
-// ransac<>'s dynamic iteration bound behind a refinement, from the inlier ratio of the best model so far (walk_pair; k_prior, mdrp_prior.h)
-__device__ __forceinline__ uint64_t dyn_max_iter_of(const RunParams &rp, double inlier_ratio) {
-    if (inlier_ratio >= 0.9999) return rp.min_iterations;
-    if (inlier_ratio <= 0.0001) return rp.max_iterations;
-    // pow(ratio, sample size) of the reference: x * x * x for 3 (pinned against the binary), libm pow otherwise
-    const double prob_outlier = 1.0 - (rp.sample_sz == 3 ? inlier_ratio * inlier_ratio * inlier_ratio : pow(inlier_ratio, (double)rp.sample_sz));
-    return f64_to_u64_x86(ceil(rp.log_prob_missing / log(prob_outlier) * rp.dyn_mult));
-}
-// SNAP (a budgets call's k_walk_ckpt only): the pair's state as it is when `iterations` reaches budget K_c — or the pair stops, if that
-// comes first — is copied into ck[c * ck_plane], with iterations = min(K_c, stop) and active = 0: what a run with max_iterations = K_c leaves behind,
-// since nothing but `it` changes between two triggers and the stop test cannot fire differently before K_c.  The copy is taken BEFORE a trigger at an
-// absolute iteration >= K_c is executed and before `it` passes K_c in a trigger-free stretch, at a stop or at the end of the super-chunk.
-template <bool COHERENT = false, bool SNAP = false>
-__device__ bool walk_pair(const RunParams &rp, PairState &ps, const Model *__restrict__ models, const Trigger *trig /*of this pair*/,
-                          size_t slot_base, uint64_t &need, const uint64_t *__restrict__ budgets = nullptr, int n_budgets = 0,
-                          PairState *__restrict__ ck = nullptr /*this pair's row of checkpoint 0*/, size_t ck_plane = 0) {
-    need = 0;
-    if (!ps.active) return true;
-    // max_iterations = 0: the reference's loop head ends the search before a sample is drawn (ransac<>: iterations < max_iterations) — no record, no
-    // LO; the closing LO then runs on the reset identity model (tests/golden/edge_options_ref.npz)
-    if (rp.max_iterations == 0) { ps.iterations = 0; ps.active = 0; return true; }
-    const uint64_t c0 = rp.chunk_start, c1 = rp.chunk_start + (uint64_t)rp.super_len;
-    uint64_t it = c0; // iterations completed so far
-    bool stopped = false;
-    int nc = 0; // SNAP: the first checkpoint still open (those up to the super-chunk's start were filled by the super-chunks before)
-    if constexpr (SNAP) while (nc < n_budgets && budgets[nc] <= c0) ++nc;
-    // SNAP: every open checkpoint with K_c <= upto takes the state as it is, at min(K_c, at) iterations
-    auto snap = [&](uint64_t upto, uint64_t at) {
-        if constexpr (SNAP)
-            for (; nc < n_budgets && budgets[nc] <= upto; ++nc) {
-                PairState &d = ck[(size_t)nc * ck_plane];
-                d = ps;
-                d.iterations = budgets[nc] < at ? budgets[nc] : at;
-                d.active = 0;
-            }
-    };
-    // stop test applied after each completed iteration: it >= max -> stop; it > min && it > dyn -> stop
-    // (+ 1 saturates: a bound of 2^64 - 1 — the reference's (uint64_t) of a dynamic bound in (-2, -1], dyn_num_trials_mult < 0 — is never exceeded, and
-    // the sum must not wrap to 0 and end the run at min_iterations + 1; max_iterations then caps the saturated value, and it >= max_iterations stops)
-    auto next_of = [](uint64_t v) -> uint64_t { return v == ~0ull ? v : v + 1; };
-    auto first_stop = [&](uint64_t lo /*first candidate value of it*/) -> uint64_t {
-        uint64_t s = lo;
-        if (s < next_of(ps.dyn_max_iter)) s = next_of(ps.dyn_max_iter);
-        if (s < next_of(rp.min_iterations)) s = next_of(rp.min_iterations);
-        if (s > rp.max_iterations) s = rp.max_iterations;
-        if (lo > s) s = lo;
-        return s;
-    };
-    for (int k = 0; k < ps.n_triggers && !stopped; ++k) {
-        const Trigger &tr = trig[k];
-        const uint64_t ti = c0 + tr.iter; // absolute index of the triggering iteration
-        // iterations it .. ti-1 complete without bookkeeping changes; would the loop stop at a value in (it, ti] ?
-        if (ti > it) {
-            const uint64_t s = first_stop(it + 1);
-            if (s <= ti) { it = s; stopped = true; break; }
-        }
-        snap(ti, ~0ull); // (iterations it .. ti - 1 changed nothing: the state at K_c <= ti is this one)
-        // execute iteration ti
-        if (tr.k_min >= 0 && tr.score_min < ps.model_score) {
-            ps.model_score = tr.score_min;
-            ps.best = models[slot_base + (size_t)tr.iter * rp.mps + tr.k_min];
-            ps.num_inliers = (uint64_t)tr.cnt_min;
-        }
-        ps.refinements++;
-        const double ref_score = COHERENT ? coherent_f64(&tr.ref_score) : tr.ref_score;
-        if (ref_score < ps.model_score) {
-            ps.model_score = ref_score;
-            if (COHERENT) {
-                ps.num_inliers = (uint64_t)__hip_atomic_load(&tr.ref_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                static_assert(sizeof(Model) % 8 == 0, "Model is copied as doubles");
-                const double *src = reinterpret_cast<const double *>(&tr.refined);
-                double *dst = reinterpret_cast<double *>(&ps.best);
-#pragma unroll
-                for (int q = 0; q < (int)(sizeof(Model) / 8); ++q) dst[q] = coherent_f64(src + q);
-            } else {
-                ps.num_inliers = (uint64_t)tr.ref_cnt;
-                ps.best = tr.refined;
-            }
-        }
-        ps.inlier_ratio = (double)ps.num_inliers / (double)ps.n;
-        ps.dyn_max_iter = dyn_max_iter_of(rp, ps.inlier_ratio);
-        it = ti + 1;
-        if (it >= rp.max_iterations || (it > rp.min_iterations && it > ps.dyn_max_iter)) { stopped = true; break; }
-    }
-    if (!stopped) {
-        // remaining iterations of the chunk
-        if (c1 > it) {
-            const uint64_t s = first_stop(it + 1);
-            if (s <= c1) { it = s; stopped = true; } else it = c1;
-        }
-    }
-    snap(stopped ? ~0ull : c1, stopped ? it : ~0ull); // stopped: every checkpoint still open reports the stopped state
-    ps.iterations = it;
-    if (stopped) { ps.active = 0; return true; }
-    need = first_stop(it + 1) - it; // iterations still certainly needed with the current dyn_max_iter
-    return false;
-}
-
-MDRP_GLOBAL void k_walk(RunParams rp, PairState *__restrict__ st, const Model *__restrict__ models, const Trigger *__restrict__ triggers,
-                       int trig_cap, int32_t *__restrict__ n_active, unsigned long long *__restrict__ max_needed,
-                       const int32_t *__restrict__ lo_plans, int n_plans, int plan_stride, int lo_cap) {
-    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pair >= rp.batch) return;
-    for (int c = 0; c < n_plans; ++c)
-        if (lo_plans[(size_t)c * plan_stride + 3 * (size_t)rp.batch + 1] > lo_cap) {
-            if (pair == 0) n_active[1] = 1;
-            return;
-        }
-    PairState &ps = st[pair];
-    if (!ps.active) return;
-    uint64_t need;
-    if (!walk_pair<false>(rp, ps, models, triggers + (size_t)pair * trig_cap, (size_t)pair * rp.slot_stride, need)) {
-        atomicAdd(n_active, 1);
-        atomicMax(max_needed, (unsigned long long)need);
-    }
-}
-
-// The walk of a budgets call: k_walk that also fills the pair's checkpoints, ckpt[c * rp.batch + pair] for budget c.  Pairs that never
-// iterate (fewer correspondences than a sample) report the state k_prep gave them at every budget.
-constexpr int WALK_CKPT_THREADS = 64; // (the launch bound lets a lane hold a whole PairState in registers while it copies it: no scratch)
-MDRP_GLOBAL __launch_bounds__(WALK_CKPT_THREADS) void k_walk_ckpt(RunParams rp, PairState *__restrict__ st, const Model *__restrict__ models, const Trigger *__restrict__ triggers,
-                            int trig_cap, int32_t *__restrict__ n_active, unsigned long long *__restrict__ max_needed,
-                            const uint64_t *__restrict__ budgets, int n_budgets, PairState *__restrict__ ckpt) {
-    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pair >= rp.batch) return;
-    PairState &ps = st[pair];
-    if (!ps.active) {
-        if (rp.chunk_start == 0)
-            for (int c = 0; c < n_budgets; ++c) ckpt[(size_t)c * rp.batch + pair] = ps;
-        return;
-    }
-    uint64_t need;
-    if (!walk_pair<false, true>(rp, ps, models, triggers + (size_t)pair * trig_cap, (size_t)pair * rp.slot_stride, need, budgets, n_budgets,
-                                ckpt + pair, (size_t)rp.batch)) {
-        atomicAdd(n_active, 1);
-        atomicMax(max_needed, (unsigned long long)need);
-    }
-}
-
-// Only distinct states are refined: `refinements` grows whenever a pair's state changes, so two checkpoints of a pair with equal `refinements` differ
-// in `iterations` at most.  One workgroup: per pair, the first checkpoint of every run of equal `refinements` goes on `list` (problems c * batch +
-// pair, ordered by pair, then budget; the unused tail is -1: surplus workgroups of the final launch leave at once), and rep[c * batch + pair] names
-// the problem whose result every checkpoint shares.
-MDRP_GLOBAL __launch_bounds__(PLAN_THREADS) void k_ckpt_plan(int batch, int n_budgets, const PairState *__restrict__ ckpt, int32_t *__restrict__ list,
-                                                            int32_t *__restrict__ rep) {
-    __shared__ int s_w[PLAN_THREADS / 64 + 1];
-    int run = 0;
-    for (int p0 = 0; p0 < batch; p0 += PLAN_THREADS) {
-        const int p = p0 + threadIdx.x;
-        int kept = 0;
-        if (p < batch)
-            for (int c = 0; c < n_budgets; ++c)
-                kept += c == 0 || ckpt[(size_t)c * batch + p].refinements != ckpt[(size_t)(c - 1) * batch + p].refinements;
-        int tot;
-        const int ex = plan_block_scan(kept, tot, s_w);
-        if (p < batch) {
-            int w = run + ex, r = 0;
-            for (int c = 0; c < n_budgets; ++c) {
-                const int e = c * batch + p;
-                if (c == 0 || ckpt[e].refinements != ckpt[e - batch].refinements) { r = e; list[w++] = e; }
-                rep[e] = r;
-            }
-        }
-        run += tot;
-    }
-    for (int i = run + threadIdx.x; i < n_budgets * batch; i += PLAN_THREADS) list[i] = -1;
-}
-
-// Fused tail (the LAST LO launch of a run whose end is known): the workgroup that refines the last open trigger of a
-// pair replays the pair (walk_pair, instead of a k_walk launch) and appends it to `ready`.  When the LO queue is empty - its last
-// problems are in flight, most wavefront slots are already free - k_gate lets the final refinements start on another stream:
-// workgroup i of k_final takes the i-th ready pair.  The few whose pair is not ready yet wait for problems that resident LO
-// workgroups hold (nobody needs their slots: the queue is empty), so the wait cannot block anything.
-struct FuseTail {
-    int32_t *done_cnt;   // [batch] refined triggers of this launch per pair (zeroed)
-    int32_t *ready;      // [batch] pairs in the order they became ready (-1 = not yet)
-    int32_t *ctl;        // [0] entries of `ready`, [1] LO workgroups that have started (their trigger-less pairs are published)   (zeroed)
-    PairState *st;       // mutable alias of the pair states (only the walking lane writes)
-};
-// one lane: returns when every workgroup of the LO launch has started and every problem has been taken from its queue - from then
-// on whatever a final refinement may wait for is in the hands of a resident workgroup.
-// Both this wait and the final refinements' wait for their pair are BOUNDED (`ticks` of the 100 MHz clock): where kernels of
-// different streams cannot run side by side (rocprofv3 --pmc serialises dispatches, debuggers do) the LO launch may be stuck behind
-// the very kernels that wait for it.  Then the gate gives up, the final workgroups give up and leave their pairs undone, the LO
-// launch runs, and the ordinary k_final pass behind it (`skip`) refines what is left: slower, never stuck.
-// LO queue with XCD affinity.  The problems of a launch are sorted by pair (k_lo_plan) and every LM sweep re-reads its pair's records
-// (96 KB at N = 2000, 240 KB at N = 5000; ~18 sweeps per problem): with one queue the ~5 problems of a pair run on five different XCDs and
-// every sweep comes over the fabric.  Eight queues, one per XCD, each over a contiguous eighth of the plan: an XCD's wavefronts work on ~46
-// consecutive pairs at a time and the problems of a pair share its L2.  The LO is bound by instruction issue, not by the memory side
-// (DESIGN.md 4): this buys 2-5 % of k_lo, no more.  A workgroup whose own queue is empty takes from the others (the tail stays balanced);
-// which problem runs where changes nothing but speed.  `head` counts the tickets handed out (k_gate waits on it); xheads == null: one queue.
-constexpr int LO_XCD_STRIDE = 16; // int32 between two queue heads (their own 64-byte blocks)
-__device__ __forceinline__ int lo_xcc_id() {
-    int x;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-    return x & 7;
-}
-__device__ __forceinline__ int lo_take(int32_t *__restrict__ head, int32_t *__restrict__ xheads, int total) {
-    if (!xheads) return atomicAdd(head, 1);
-    const int x = lo_xcc_id();
-    for (int k = 0; k < 8; ++k) {
-        const int y = (x + k) & 7;
-        const int b = (int)((long long)total * y / 8), len = (int)((long long)total * (y + 1) / 8) - b;
-        if (len <= 0 || __hip_atomic_load(xheads + y * LO_XCD_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= len) continue;
-        const int t = atomicAdd(xheads + y * LO_XCD_STRIDE, 1);
-        if (t < len) { atomicAdd(head, 1); return b + t; }
-    }
-    return total;
-}
-
-MDRP_GLOBAL void k_gate(const int32_t *__restrict__ lo_head, const int32_t *__restrict__ plan_total, const int32_t *__restrict__ ctl, int lo_blocks,
-                       unsigned long long ticks, unsigned long long *__restrict__ timeouts /*[0] gate, [1] final waits: mdrp_stats.fuse_*_timeouts*/) {
-    const int total = *plan_total;
-    const unsigned long long t0 = wall_clock64();
-    bool open = false;
-    while (!(open = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= lo_blocks &&
-                    __hip_atomic_load(lo_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= total) && wall_clock64() - t0 < ticks)
-        __builtin_amdgcn_s_sleep(64);
-    if (!open && timeouts) atomicAdd(timeouts, 1ull);
-}
-__device__ __forceinline__ void fuse_publish(const FuseTail &fz, const RunParams &rp, int pair, const Model *__restrict__ models,
-                                             const Trigger *__restrict__ triggers, int trig_cap) {
-    uint64_t need;
-    walk_pair<true>(rp, fz.st[pair], models, triggers + (size_t)pair * trig_cap, (size_t)pair * rp.slot_stride, need);
-    __threadfence();
-    const int t = atomicAdd(fz.ctl, 1);
-    __hip_atomic_store(fz.ready + t, pair, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// LO of item w of the launch's plan (refine_model + score_model of the refined model), by the whole workgroup
-template <int KIND, bool SHIFT, int T>
-__device__ void lo_problem(const RunParams &rp, const PairState *__restrict__ st, const double *__restrict__ pts, const double *__restrict__ dep,
-                           const Model *__restrict__ models, Trigger *__restrict__ triggers, int trig_cap, const int32_t *__restrict__ plan, int w,
-                           LmShared &sh, const FuseTail &fz) {
-    const int32_t *prefix = plan, *begin = plan + rp.batch + 1, *end = begin + rp.batch;
-    const int pair = plan_find(prefix, rp.batch, w);
-    const int pos = begin[pair] + (w - prefix[pair]);
-    const PairState &ps = st[pair];
-    Trigger &tr = triggers[(size_t)pair * trig_cap + pos];
-    const size_t slot_base = (size_t)pair * rp.slot_stride;
-    Model m = models[slot_base + (size_t)tr.iter * rp.mps + tr.k_ref];
-    LmOpt o;
-    o.max_it = 25; o.loss = 1; o.loss_scale = ps.lo_loss_scale;
-    o.grad_tol = 1e-10; o.step_tol = 1e-8; o.lambda0 = 1e-3; o.lambda_min = 1e-10; o.lambda_max = 1e10;
-    const double *pp = pts + (size_t)pair * rp.n_max * PT_STRIDE;
-    const double *dd = dep + (size_t)pair * rp.n_max * 2;
-    // (a NaN model — the reference's P3P, k_solve — has a NaN cost: no step can be accepted, it comes back as it is)
-    if (m.q[0] == m.q[0]) lm_refine<KIND, SHIFT, T, 1>(m, pp, dd, ps.n, nullptr, ps.scale_reproj, rp.weight_sampson, o, sh); // refine_model: always TRUNCATED
-    double sc;
-    int cn;
-    block_score<T>(KIND, m, pp, ps.n, ps.sq_thr, sh.scratch, sc, cn, nullptr);
-    if (threadIdx.x == 0) {
-        tr.refined = m; tr.ref_score = sc; tr.ref_cnt = cn; lm_flush_stats(sh);
-        if (fz.ready) {
-            __threadfence(); // this trigger's results before the count
-            if (atomicAdd(fz.done_cnt + pair, 1) + 1 == end[pair] - begin[pair]) {
-                __threadfence(); // the other triggers' results (written on other CUs / XCDs) before the replay reads them
-                fuse_publish(fz, rp, pair, models, triggers, trig_cap);
-            }
-        }
-    }
-}
-
-template <int KIND, bool SHIFT, int T>
-__global__ __launch_bounds__(T, MDRP_LM_MINWAVES) void k_lo(RunParams rp, const PairState *__restrict__ st, const double *__restrict__ pts,
-                                                   const double *__restrict__ dep, const Model *__restrict__ models,
-                                                   Trigger *__restrict__ triggers, int trig_cap, const int32_t *__restrict__ plan,
-                                                   int32_t *__restrict__ head /*zeroed*/, int32_t *__restrict__ xheads /*zeroed, or null: lo_take*/,
-                                                   int list_stride, unsigned long long *__restrict__ lm_stats, FuseTail fz /*ready == null: off*/) {
-    extern __shared__ uint16_t lm_dyn_list[];
-    __shared__ LmShared sh;
-    __shared__ int s_item;
-    if (threadIdx.x == 0) { sh.list = lm_dyn_list; sh.stride = list_stride; sh.midx = 0; sh.stats = lm_stats; sh.ev[0] = 0; sh.ev[1] = 0; sh.logtab = nullptr; }
-    __syncthreads();
-    const int total = plan[3 * (size_t)rp.batch + 1];
-    if (fz.ready && threadIdx.x == 0) { // pairs without a trigger in this launch are ready as they are (earlier LO launches have ended: stream order)
-        const int32_t *begin = plan + rp.batch + 1, *end = begin + rp.batch;
-        for (int p = blockIdx.x; p < rp.batch; p += gridDim.x)
-            if (end[p] == begin[p]) fuse_publish(fz, rp, p, models, triggers, trig_cap);
-        atomicAdd(fz.ctl + 1, 1);
-    }
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_item = lo_take(head, xheads, total);
-        __syncthreads();
-        const int w = s_item;
-        if (w >= total) break;
-        lo_problem<KIND, SHIFT, T>(rp, st, pts, dep, models, triggers, trig_cap, plan, w, sh, fz);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ final
-// ransac<> tail (@0x22f1d0-0x22f295) + get_inliers (@0x4f7a10/@0x4f77f0) + the estimator's inlier-only refinement
-// (@0x2247c3 / @0x223815) + focal un-normalisation.
-struct ResultDev {
-    Model model;
-    uint64_t refinements, iterations, num_inliers;
-    double inlier_ratio, model_score;
-};
-
-// FLOSS: the user's loss type of the inlier-only refinement as a compile-time constant (rp.final_loss; -1 = read o.loss at run time).
-// Round 5: the two refinements of ransac<>'s tail are two call sites of lm_refine, each with its loss (and whether a record mask
-// exists) known to the compiler — the LO with TRUNCATED exactly as k_lo compiles it (unit-weight rows, no products by the weight), the
-// inlier-only refinement without the six-way loss switch in its sweeps.  Nothing but the model under refinement is live across an LM:
-// the round-4 kernel carried `best`, `m`, `x` and the result record (100 VGPRs) through both refinements and spilled 201-449 VGPRs.
-template <int KIND, bool SHIFT, int T, int FLOSS>
-__device__ __forceinline__ void final_pair(const RunParams &rp, const PairState &ps, const double *__restrict__ pts, const double *__restrict__ dep,
-                                           uint8_t *__restrict__ mask_all, ResultDev *__restrict__ results, int pair, LmShared &sh) {
-    double *scratch = sh.scratch;
-    const FinalRows row = final_rows(rp, pair);
-    uint8_t *mask = mask_all + (size_t)row.out * rp.n_max;
-    if (ps.n < 3) {
-        for (int i = threadIdx.x; i < rp.n_max; i += T) mask[i] = 0;
-        if (threadIdx.x == 0) {
-            ResultDev res;
-            res.model = ps.best;
-            res.refinements = ps.refinements; res.iterations = ps.iterations; res.num_inliers = ps.num_inliers;
-            res.inlier_ratio = ps.inlier_ratio; res.model_score = ps.model_score;
-            results[row.out] = res;
-        }
-        return;
-    }
-    const double *pp = pts + (size_t)row.rec * rp.n_max * PT_STRIDE;
-    const double *dd = dep + (size_t)row.rec * rp.n_max * 2;
-    // ransac<>'s last LO from the best model: 25 iterations, TRUNCATED, all records
-    Model x = ps.best;
-    {
-        LmOpt o;
-        o.max_it = 25; o.loss = 1; o.loss_scale = ps.lo_loss_scale;
-        o.grad_tol = 1e-10; o.step_tol = 1e-8; o.lambda0 = 1e-3; o.lambda_min = 1e-10; o.lambda_max = 1e10;
-        if (x.q[0] == x.q[0]) lm_refine<KIND, SHIFT, T, 1>(x, pp, dd, ps.n, nullptr, ps.scale_reproj, rp.weight_sampson, o, sh); // (NaN model: lo_problem)
-    }
-    uint64_t num_inliers = ps.num_inliers;
-    {
-        double sc;
-        int cn;
-        block_score<T>(KIND, x, pp, ps.n, ps.sq_thr, scratch, sc, cn, nullptr);
-        if (sc < ps.model_score) num_inliers = (uint64_t)cn; // the refined model is adopted; score / ratio NOT updated (reference)
-        else x = ps.best;                                    // (re-read: no second model is kept live across the LM)
-        for (int i = ps.n + threadIdx.x; i < rp.n_max; i += T) mask[i] = 0;
-        block_score<T>(KIND, x, pp, ps.n, ps.sq_thr, scratch, sc, cn, mask); // get_inliers of the winner
-        __syncthreads();
-    }
-    // the estimator's inlier-only refinement with the user's BundleOptions: with more than 3 inliers in the calibrated (@0x224434) and shared-focal
-    // (@0x2235e6) wrappers, with more than 7 in the varying-focal one (@0x223d16)
-    if (num_inliers > (KIND == 2 ? 7u : 3u)) {
-        LmOpt o;
-        o.max_it = rp.final_max_it; o.loss = FLOSS >= 0 ? FLOSS : rp.final_loss; o.loss_scale = ps.final_loss_scale;
-        o.grad_tol = rp.grad_tol; o.step_tol = rp.step_tol; o.lambda0 = rp.lambda0; o.lambda_min = rp.lambda_min; o.lambda_max = rp.lambda_max;
-        lm_refine<KIND, SHIFT, T, FLOSS>(x, pp, dd, ps.n, mask, ps.scale_reproj, rp.weight_sampson, o, sh);
-    }
-    if (KIND != 0) { x.f1 *= ps.norm; x.f2 *= ps.norm; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ResultDev res;
-        res.model = x;
-        res.refinements = ps.refinements + 1; res.iterations = ps.iterations; res.num_inliers = num_inliers;
-        res.inlier_ratio = ps.inlier_ratio; res.model_score = ps.model_score;
-        results[row.out] = res;
-        if (rp.inl_stat) { // what this pair would have liked as the run's first chunk: ~6 outlier-free samples expected in it (first_chunk_wish)
-            atomicAdd(&rp.inl_stat[0], first_chunk_wish((double)num_inliers / (double)ps.n, 3));
-            atomicAdd(&rp.inl_stat[1], 1);
-        }
-        lm_flush_stats(sh);
-    }
-}
-
-template <int KIND, bool SHIFT, int T, int FLOSS>
-__global__ __launch_bounds__(T, MDRP_LM_MINWAVES) void k_final(RunParams rp, PairState *__restrict__ st, const double *__restrict__ pts,
-                                                      const double *__restrict__ dep, uint8_t *__restrict__ mask_all,
-                                                      ResultDev *__restrict__ results, int list_stride, int mask_index /*1: 3 * list_stride entries of dynamic LDS*/,
-                                                      unsigned long long *__restrict__ lm_stats,
-                                                      const int32_t *__restrict__ ready /*or null: pair = blockIdx.x*/,
-                                                      int32_t *__restrict__ fin_done /*fused: set per refined pair; unfused: pairs to skip, or null*/,
-                                                      unsigned long long ticks, unsigned long long *__restrict__ timeouts /*fused: expired bounded waits*/) {
-    extern __shared__ uint16_t lm_dyn_list[];
-    __shared__ LmShared sh;
-    __shared__ int s_pair;
-    __shared__ __attribute__((aligned(16))) unsigned int s_ps[(sizeof(PairState) + 3) / 4];
-    __shared__ __attribute__((aligned(16))) double s_logtab[(FLOSS == 3 || FLOSS == 4 || FLOSS < 0) ? 2 * MDRP_LOGTAB_N : 2];
-    constexpr bool use_logtab = FLOSS == 3 || FLOSS == 4 || FLOSS < 0;
-    if (use_logtab) lm_logtab_load(s_logtab);
-    if (threadIdx.x == 0) {
-        sh.list = lm_dyn_list; sh.stride = list_stride; sh.midx = mask_index; sh.stats = lm_stats; sh.ev[0] = 0; sh.ev[1] = 0;
-        sh.logtab = use_logtab ? s_logtab : nullptr;
-        int p = blockIdx.x;
-        if (ready) { // fused tail: the blockIdx-th pair to become ready (bounded wait, see k_gate)
-            const unsigned long long t0 = wall_clock64();
-            // polled RELAXED, one acquire fence when the pair is there: an acquire LOAD is followed by an invalidate of the XCD's L2, and the few
-            // hundred workgroups waiting here did that every microsecond while the last LO problems were still sweeping.  (Found with an experimental
-            // queue-driven k_final whose idle workgroups polled the same way: the pairs still running took twice as long per iteration.)
-            while ((p = __hip_atomic_load(ready + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < 0 && wall_clock64() - t0 < ticks)
-                __builtin_amdgcn_s_sleep(16);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (p < 0 && timeouts) atomicAdd(timeouts, 1ull); // gave up: the pass behind the LO launch refines this pair
-            __threadfence(); // the replayed pair state (written on another CU / XCD) before anyone of this workgroup reads it
-        } else if (fin_done && fin_done[p]) p = -1; // the pass behind a fused tail: only what that left undone
-        s_pair = p;
-    }
-    __syncthreads();
-    if (s_pair < 0) return;
-    // The pair state is read ONCE, with vector loads, into LDS.  Fused: it was written DURING this launch (by the LO workgroup that replayed the
-    // pair); this kernel never writes `st`, so the compiler may fetch st[pair] through the scalar cache, which an acquire does not invalidate and
-    // which can hold the cache line that the previous pair's last field shares with this pair's head from BEFORE the replay.  Unfused: the same
-    // copy keeps ONE call site of final_pair (round 4 compiled the 17 k-instruction body twice) and the pair's fields re-readable from LDS.
-    {
-        const volatile unsigned int *src = reinterpret_cast<const volatile unsigned int *>(st + s_pair);
-        for (int i = threadIdx.x; i < (int)(sizeof(PairState) / 4); i += T) s_ps[i] = src[i];
-    }
-    __syncthreads();
-    final_pair<KIND, SHIFT, T, FLOSS>(rp, *reinterpret_cast<const PairState *>(s_ps), pts, dep, mask_all, results, s_pair, sh);
-    if (ready && threadIdx.x == 0) fin_done[s_pair] = 1;
-}
-
-// Budgets call (k_ckpt_plan): behind the final refinements every other checkpoint takes its representative's record and mask row, with its own `iterations`.  One workgroup
-// per (budget, pair); rows as final_rows.  The last budget's results feed rp.inl_stat, as the final refinements of a call without budgets do.
-constexpr int CKPT_FILL_THREADS = 256;
-MDRP_GLOBAL __launch_bounds__(CKPT_FILL_THREADS) void k_ckpt_fill(RunParams rp, int n_budgets, const PairState *__restrict__ ckpt,
-                                                                 const int32_t *__restrict__ rep, ResultDev *__restrict__ results,
-                                                                 uint8_t *__restrict__ mask_all) {
-    const int e = blockIdx.x, r = rep[e];
-    const FinalRows dst = final_rows(rp, e), src = final_rows(rp, r);
-    if (r != e) {
-        const uint8_t *from = mask_all + (size_t)src.out * rp.n_max;
-        uint8_t *to = mask_all + (size_t)dst.out * rp.n_max;
-        for (int i = threadIdx.x; i < rp.n_max; i += CKPT_FILL_THREADS) to[i] = from[i];
-    }
-    if (threadIdx.x == 0) {
-        ResultDev res = results[src.out];
-        if (r != e) { res.iterations = ckpt[e].iterations; results[dst.out] = res; }
-        if (rp.inl_stat && e / rp.ck_pairs == n_budgets - 1 && ckpt[e].n >= 3) {
-            atomicAdd(&rp.inl_stat[0], first_chunk_wish((double)res.num_inliers / (double)ckpt[e].n, 3));
-            atomicAdd(&rp.inl_stat[1], 1);
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ unit-parity kernels
 MDRP_GLOBAL void k_solver_unit(int solver, int count, const double *__restrict__ x1h, const double *__restrict__ x2h,
                               const double *__restrict__ d1, const double *__restrict__ d2, Model *__restrict__ out, int32_t *__restrict__ n_out) {

@@ -99,6 +99,49 @@ def batch(kind, n_list=RAGGED_N, first=None, start=tuple(RAGGED_START.items())):
     return dict(x1=x1, x2=x2, n=np.array(n_list, dtype=np.int32), models=models, cams=cameras(kind), pp=PP)
 
 
+EXACT_N = 40  # records per pair of exact_inlier_batch
+
+
+@functools.lru_cache(maxsize=None)
+def exact_inlier_batch(kind, counts, first=88000):
+    """from_models_cases.exact_inlier_batch for the baselines: one noise-free pair per entry of `counts` with c records that the pair's ground truth
+    counts as inliers (the yardstick's own mask picks them), the others gross outliers (the second image's point drawn anew until the yardstick
+    counts none of them — the 7-point kind's threshold moves with the points, so the mask is taken afresh each time), and the start model is that
+    ground truth: a model with exactly c inliers, all exact.  The 5-point kind's second image is rescaled to its PINHOLE camera's two focals."""
+    B, N = len(counts), EXACT_N
+    x1 = np.zeros((B, N, 2)); x2 = np.zeros((B, N, 2))
+    models = np.zeros((B, 12))
+    rng = np.random.default_rng(first + kind)
+    ro, bo = oracle_options("HUBER")  # (stages = 0: the loss is not looked at)
+    cams = cameras(kind)
+    c1, c2 = oracle_cams(dict(cams=cams))
+    for i, c in enumerate(counts):
+        p = synth.make_pair(first + i, N, f1=F, f2=F, pp=PP, noise_px=0.0, outlier_frac=0.0)
+        m = start_model(kind, p, "exact", rng)
+        a1, a2 = p["x1"], p["x2"].copy()
+        if kind == cm.FIVE:
+            a2 = (a2 - PP) / F * np.array(cams[1][1][:2]) + PP
+        mask = lambda a2: np.asarray(cm.refine_from_model_classic(kind, a1, a2, m, ro, bo, 0, c1, c2, PP)["mask"], dtype=bool)
+        assert mask(a2).all(), (kind, i)  # noise-free: every record fits the ground truth
+        lo, hi = a2.min(axis=0), a2.max(axis=0)
+        redo = np.arange(N) >= c
+        for _ in range(50):
+            a2[redo] = rng.uniform(lo, hi, (int(redo.sum()), 2))
+            redo = mask(a2) & (np.arange(N) >= c)
+            if not redo.any():
+                break
+        assert not redo.any() and mask(a2)[:c].all(), (kind, i)
+        x1[i], x2[i], models[i] = a1, a2, m
+    return dict(x1=x1, x2=x2, n=np.full(B, N, dtype=np.int32), models=models, cams=cams, pp=PP)
+
+
+def exact_inlier_yardstick(kind, loss, stages, counts):
+    b = exact_inlier_batch(kind, counts)
+    ro, bo = oracle_options(loss)
+    c1, c2 = oracle_cams(b)
+    return [cm.refine_from_model_classic(kind, b["x1"][i], b["x2"][i], b["models"][i], ro, bo, stages, c1, c2, b["pp"]) for i in range(len(counts))]
+
+
 def oracle_options(loss, max_iterations=0, min_iterations=0, score_initial=False, seed=3):
     return (po.ransac_opt(max_iterations=max_iterations, min_iterations=min_iterations, max_epipolar_error=THR, seed=seed, score_initial_model=score_initial),
             po.bundle_opt(max_iterations=100, loss_type=LOSSES[loss], loss_scale=1.0, gradient_tol=1e-10))

@@ -145,3 +145,47 @@ def branches(name, loss, **kw):
         else:
             seen.add("inliers_run")
     return seen
+
+
+EXACT_N = 40  # records per pair of exact_inlier_batch
+
+
+@functools.lru_cache(maxsize=None)
+def exact_inlier_batch(name, counts, first=75000):
+    """one noise-free pair per entry of `counts`: c records that the pair's ground truth counts as inliers (the yardstick's own get_inliers picks them), the
+    others gross outliers (the second image's point and depth drawn anew until the yardstick counts none of them), and the start model is that ground
+    truth — a model with exactly c inliers, all exact"""
+    kind, es, rf = helpers.OPTIONS_KINDS[name]
+    kw = dict(f1=F1, f2=F2, pp=PP) if kind == po.CALIB else {}
+    B, N = len(counts), EXACT_N
+    x1 = np.zeros((B, N, 2)); x2 = np.zeros((B, N, 2)); d1 = np.ones((B, N)); d2 = np.ones((B, N))
+    models = np.zeros((B, 12))
+    rng = np.random.default_rng(first)
+    ro, bo = oracle_options(name, "HUBER")  # (stages = 0: the loss is not looked at)
+    cams = cameras(kind)
+    c1, c2 = (po.cam_flat(*cams[0]), po.cam_flat(*cams[1])) if cams else (None, None)
+    for i, c in enumerate(counts):
+        p = synth.make_pair(first + i, N, noise_px=0.0, depth_noise=0.0, outlier_frac=0.0, random_focal=rf, shift1=0.2 if es else 0.0, shift2=-0.1 if es else 0.0, **kw)
+        m = start_model(name, p, "exact", rng)
+        mask = lambda a2, e2: np.asarray(fm.refine_from_model(kind, p["x1"], a2, p["d1"], e2, m, ro, bo, 0, c1, c2)["mask"], dtype=bool)
+        order = np.argsort(~mask(p["x2"], p["d2"]), kind="stable")  # the ground truth's inliers first
+        a1, a2, e1, e2 = p["x1"][order], p["x2"][order].copy(), p["d1"][order], p["d2"][order].copy()
+        p = dict(p, x1=a1, d1=e1)
+        lo, hi = a2.min(axis=0), a2.max(axis=0)
+        redo = np.arange(N) >= c
+        for _ in range(50):
+            a2[redo] = rng.uniform(lo, hi, (int(redo.sum()), 2))
+            e2[redo] = rng.uniform(e2.min(), e2.max(), int(redo.sum()))
+            redo = mask(a2, e2) & (np.arange(N) >= c)
+            if not redo.any():
+                break
+        x1[i], x2[i], d1[i], d2[i], models[i] = a1, a2, e1, e2, m
+    return dict(x1=x1, x2=x2, d1=d1, d2=d2, n=np.full(B, N, dtype=np.int32), models=models, cams=cams)
+
+
+def exact_inlier_yardstick(name, loss, stages, counts):
+    kind = helpers.OPTIONS_KINDS[name][0]
+    b = exact_inlier_batch(name, counts)
+    ro, bo = oracle_options(name, loss)
+    c1, c2 = (po.cam_flat(*b["cams"][0]), po.cam_flat(*b["cams"][1])) if b["cams"] else (None, None)
+    return [fm.refine_from_model(kind, b["x1"][i], b["x2"][i], b["d1"][i], b["d2"][i], b["models"][i], ro, bo, stages, c1, c2) for i in range(len(counts))]

@@ -75,6 +75,7 @@ def test_header_and_binding_agree():
         assert len(getattr(lib, name).argtypes) == len(_declaration(hdr, name)), name
     assert len(_declaration(hdr, "mdrp_refine_batch")) == 20 and len(_declaration(hdr, "mdrp_refine_batch_async")) == 18
     assert os.path.realpath(os.path.join(ROOT, "mdrp_amd", "csrc", "mdrp_from_model.h")) in [os.path.realpath(d) for d in build.DEPS]
+    assert os.path.realpath(os.path.join(ROOT, "mdrp_amd", "csrc", "mdrp_tail.h")) in [os.path.realpath(d) for d in build.DEPS]
 
 
 def test_kernel_family_and_resources():

@@ -299,6 +299,45 @@ def test_fused_tail_is_bit_identical(kind, monkeypatch):
     assert max(i["refinements"] for i in i0) > 3
 
 
+@pytest.mark.parametrize("lanes", ["64", "256"])
+def test_fused_tail_is_bit_identical_at_both_lane_counts(lanes, monkeypatch):
+    """MDRP_FUSE_TAIL = 0 against 1 with MDRP_LO_THREADS = MDRP_FINAL_THREADS = 64 and 256 for the 5-point baseline (kc_lo / kc_final at either width, the
+    pair taken from the ready list or by its index): records and masks bit for bit.  Eight small pairs, one with four records beside one with five."""
+    from mdrp_amd import _capi, synth
+    ns = [64, 60, 5, 4, 33, 64, 64, 50]
+    B, N = len(ns), 64
+    pairs = [synth.make_pair(9750 + k, n, f1=850.0, f2=850.0, pp=(640.0, 480.0), noise_px=0.6, outlier_frac=[0.4, 0.1][k % 2]) for k, n in enumerate(ns)]
+    n_per = np.array(ns, dtype=np.int32)
+    x1, x2 = np.zeros((B, N, 2)), np.zeros((B, N, 2))
+    for k, p in enumerate(pairs):
+        x1[k, : ns[k]], x2[k, : ns[k]] = p["x1"], p["x2"]
+    cams = np.zeros(B, dtype=_capi.CAMERA_DTYPE)  # SIMPLE_PINHOLE
+    cams["params"][:, :3] = (850.0, 640.0, 480.0)
+    ro = _capi.ransac_opt_from_dict({"max_iterations": 256, "min_iterations": 256, "max_epipolar_error": 1.5, "seed": 2})
+    bo = _capi.bundle_opt_from_dict({"loss_type": "TRUNCATED_CAUCHY", "loss_scale": 1.5})
+    monkeypatch.setenv("MDRP_LO_THREADS", lanes)
+    monkeypatch.setenv("MDRP_FINAL_THREADS", lanes)
+    h = _capi.Handle(0)  # (its own: an expired wait turns a handle's fused tail off for its next calls)
+    try:
+        out = []
+        # "giveup", last: the fused tail's bounded waits cut to 1 us.  Only the fused tail's waits can expire, so a count above zero shows that this shape
+        # at this width does take the fused path, which no other statistic tells apart (tests/test_gpu_wide.py does the same for k_lo / k_final)
+        for fuse in ("0", "1", "giveup"):
+            monkeypatch.setenv("MDRP_FUSE_TAIL", "0" if fuse == "0" else "1")
+            for k in ("MDRP_FUSE_GATE_US", "MDRP_FUSE_WAIT_US"):
+                monkeypatch.setenv(k, "1") if fuse == "giveup" else monkeypatch.delenv(k, raising=False)
+            res, mask = h.estimate_batch(_capi.RELPOSE_5PT, x1, x2, None, None, ro, bo, n_per, cams, cams)
+            assert (h.last_stats()["fuse_timeouts"] > 0) == (fuse == "giveup"), fuse
+            out.append((res.copy(), mask.copy()))
+        (r0, m0), (r1, m1), (r2, m2) = out
+        print(lanes, "refinements", r0["refinements"].tolist(), "inliers", r0["num_inliers"].tolist())
+        assert r0.tobytes() == r1.tobytes() and np.array_equal(m0, m1)
+        assert r0.tobytes() == r2.tobytes() and np.array_equal(m0, m2)
+        assert int(r0["refinements"].max()) > 1 and int(r0["refinements"][3]) == 0
+    finally:
+        h.close()
+
+
 # ---------------------------------------------------------------------------------------------- 6-point, shared focal
 def _six_rows(out, n):
     return [np.r_[m["q"], m["t"], m["f1"]] for m in out[:n]]

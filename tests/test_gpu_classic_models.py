@@ -88,6 +88,30 @@ def test_beyond_the_16_bit_work_lists(capi, handle):
     _refine_against_the_yardstick(capi, handle, cm.FIVE, LOSS, **BIG)
 
 
+@pytest.mark.parametrize("kind", cc.KINDS)
+def test_inliers_stage_alone_at_the_count_rule(capi, handle, kind):
+    """stages = INLIERS from a model with exactly K exact inliers among gross outliers, and with one more: the inlier-only refinement needs MORE than
+    K, so `refinements` is 0, then 1 (tests/classic_models_cases.exact_inlier_batch; the yardstick confirms both counts)"""
+    K = cm.K_OF[kind]
+    counts = (K, K + 1)
+    b = cc.exact_inlier_batch(kind, counts)
+    want = cc.exact_inlier_yardstick(kind, LOSS, cm.STAGE_INLIERS, counts)
+    assert [w["initial_inliers"] for w in want] == list(counts) and [w["refinements"] for w in want] == [0, 1]
+    assert min(cc.threshold_margin(kind, w) for w in want) > 1e-6
+    ro, bo = cc.library_options(LOSS, capi)
+    c1, c2 = cc.camera_records(kind, b, capi)
+    models = capi.array_to_models(b["models"])
+    res, mask, score0, inl0 = handle.refine_classic(kind, b["x1"], b["x2"], models, ro, bo, cm.STAGE_INLIERS, b["n"], c1, c2)
+    for i, w in enumerate(want):
+        got = capi.model_to_array(res[i]["model"])
+        print(kind, counts[i], "inliers", int(res[i]["num_inliers"]), int(inl0[i]), "LMs", int(res[i]["refinements"]), w["refinements"], "model diff",
+              cc.model_diff(kind, got, w["model"]))
+        assert int(inl0[i]) == counts[i] == int(res[i]["num_inliers"]) == int(mask[i].sum()) and np.array_equal(mask[i], w["mask"]), (kind, i)
+        assert int(res[i]["refinements"]) == w["refinements"] == (0 if counts[i] == K else 1), (kind, i)
+        assert cc.model_diff(kind, got, w["model"]) < 1e-6, (kind, i, got, w["model"])
+    assert res[0]["model"].tobytes() == models[0].tobytes()  # no LM ran: bit for bit
+
+
 def _torch_batch(first, B, N):
     import torch
     pairs = [cc.make_pair(first + i, N) for i in range(B)]

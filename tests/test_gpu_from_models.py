@@ -73,6 +73,30 @@ def test_beyond_the_16_bit_work_lists(capi, handle, loss):
     _against_the_yardstick(capi, handle, "varying", loss, **BIG)
 
 
+@pytest.mark.parametrize("name", helpers.OPTIONS_NAMES)
+def test_inliers_stage_alone_at_the_count_rule(capi, handle, name):
+    """stages = INLIERS from a model with exactly 3 (7: varying focal) exact inliers among gross outliers, and with one more: the inlier-only refinement
+    needs MORE than the rule's count, so `refinements` is 0, then 1 (tests/from_models_cases.exact_inlier_batch; the yardstick confirms both counts)"""
+    kind = helpers.OPTIONS_KINDS[name][0]
+    rule = 7 if kind == 2 else 3
+    counts = (rule, rule + 1)
+    b = fc.exact_inlier_batch(name, counts)
+    want = fc.exact_inlier_yardstick(name, "TRUNCATED_CAUCHY", fm.STAGE_INLIERS, counts)
+    assert [w["initial_inliers"] for w in want] == list(counts) and [w["refinements"] for w in want] == [0, 1]
+    assert min(fc.threshold_margin(kind, w) for w in want) > 1e-6
+    ro, bo = fc.library_options(name, "TRUNCATED_CAUCHY", capi)
+    c1, c2 = fc.camera_records(b, capi)
+    models = capi.array_to_models(b["models"])
+    res, mask, score0, inl0 = handle.refine_batch(kind, b["x1"], b["x2"], b["d1"], b["d2"], models, ro, bo, fm.STAGE_INLIERS, b["n"], c1, c2)
+    for i, w in enumerate(want):
+        print(name, counts[i], "inliers", int(res[i]["num_inliers"]), int(inl0[i]), "LMs", int(res[i]["refinements"]), w["refinements"])
+        assert int(inl0[i]) == counts[i] == int(res[i]["num_inliers"]) == int(mask[i].sum()) and np.array_equal(mask[i], w["mask"]), (name, i)
+        assert int(res[i]["refinements"]) == w["refinements"] == (0 if counts[i] == rule else 1), (name, i)
+        got = capi.model_to_array(res[i]["model"])
+        assert helpers.same_model(got, w["model"]), (name, i, got, w["model"])
+    assert res[0]["model"].tobytes() == models[0].tobytes()  # no LM ran: bit for bit
+
+
 def _torch_batch(name, first, B, N):
     import torch
     from mdrp_amd import synth

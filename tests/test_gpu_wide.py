@@ -201,3 +201,44 @@ def test_fused_tail_is_bit_identical(capi, monkeypatch, kind, es):
             assert int(r0["refinements"].max()) > 3
     finally:
         h.close()
+
+
+@pytest.mark.parametrize("lanes", ["64", "256"])
+def test_fused_tail_is_bit_identical_at_both_lane_counts(capi, monkeypatch, lanes):
+    """MDRP_FUSE_TAIL = 0 against 1 with MDRP_LO_THREADS = MDRP_FINAL_THREADS = 64 and 256 (k_lo / k_final at either width, the pair taken from the
+    ready list or by its index): records and masks bit for bit.  Eight small pairs, one with a record fewer than a sample beside one with exactly three."""
+    from mdrp_amd import synth
+    ns = [64, 63, 3, 2, 40, 64, 17, 64]
+    B, N = len(ns), 64
+    pairs = [synth.make_pair(8950 + i, n, noise_px=0.5, depth_noise=0.02, outlier_frac=[0.5, 0.2, 0.0][i % 3]) for i, n in enumerate(ns)]
+    n_per = np.array(ns, dtype=np.int32)
+    x1, x2 = np.zeros((B, N, 2)), np.zeros((B, N, 2))
+    d1, d2 = np.ones((B, N)), np.ones((B, N))
+    for i, p in enumerate(pairs):
+        x1[i, : ns[i]], x2[i, : ns[i]], d1[i, : ns[i]], d2[i, : ns[i]] = p["x1"], p["x2"], p["d1"], p["d2"]
+    cams = np.zeros(B, dtype=capi.CAMERA_DTYPE)
+    cams["params"][:, 0] = 800.0
+    ro = capi.ransac_opt_from_dict({"max_iterations": 256, "min_iterations": 256, "max_epipolar_error": 2.0, "max_reproj_error": 16.0})
+    bo = capi.bundle_opt_from_dict({"loss_type": "TRUNCATED_CAUCHY"})
+    monkeypatch.setenv("MDRP_LO_THREADS", lanes)
+    monkeypatch.setenv("MDRP_FINAL_THREADS", lanes)
+    h = capi.Handle(0)
+    try:
+        out = []
+        # "giveup" (last: an expired wait turns the handle's fused tail off for its next calls): the fused tail's bounded waits cut to 1 us, as in
+        # test_fused_tail_is_bit_identical.  The only waits that can expire are the fused tail's, so a count above zero shows that this shape at this
+        # width does take the fused path, which no other statistic tells apart
+        for fuse in ("0", "1", "giveup"):
+            monkeypatch.setenv("MDRP_FUSE_TAIL", "0" if fuse == "0" else "1")
+            for k in ("MDRP_FUSE_GATE_US", "MDRP_FUSE_WAIT_US"):
+                monkeypatch.setenv(k, "1") if fuse == "giveup" else monkeypatch.delenv(k, raising=False)
+            res, mask = h.estimate_batch(0, x1, x2, d1, d2, ro, bo, n_per, cams, cams)
+            assert (h.last_stats()["fuse_timeouts"] > 0) == (fuse == "giveup"), fuse
+            out.append((res.copy(), mask.copy()))
+        (r0, m0), (r1, m1), (r2, m2) = out
+        print(lanes, "refinements", r0["refinements"].tolist(), "inliers", r0["num_inliers"].tolist())
+        assert r0.tobytes() == r1.tobytes() and np.array_equal(m0, m1)
+        assert r0.tobytes() == r2.tobytes() and np.array_equal(m0, m2)
+        assert int(r0["refinements"].max()) > 1 and int(r0["refinements"][3]) == 0 and int(r0["refinements"][2]) >= 1
+    finally:
+        h.close()
