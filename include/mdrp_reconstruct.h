@@ -94,4 +94,6 @@ int mdrp_reconstruct_image_pairs_async(mdrp_handle *h, int kind, const mdrp_dept
 #ifdef __cplusplus
 }
 #endif
+
+#include "mdrp_scene.h" /* an image set: the pairs chained along a tree, one fused cloud per scene; it builds on the descriptors and rules above */
 #endif

@@ -120,6 +120,16 @@ class ReconstructOpt(C.Structure):
 assert C.sizeof(DepthPairs) == 56 and C.sizeof(DepthImagePairs) == 48 and C.sizeof(ReconstructOpt) == 24
 
 
+class SceneTransform(C.Structure):
+    """mdrp_scene_transform (include/mdrp_scene.h): a point X of the image is (R X + t) * (1 / s) in the frame of `root`; depth -1 = absent or detached"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("s", C.c_double), ("f", C.c_double), ("shift", C.c_double), ("root", C.c_int32),
+                ("depth", C.c_int32)]
+
+
+assert C.sizeof(SceneTransform) == 128
+SCENE_ABSENT, SCENE_EDGE, SCENE_ROOT = 0, 1, 2  # include/mdrp_scene.h MDRP_SCENE_*: tree[i][1]
+
+
 class Result(C.Structure):
     _fields_ = [("model", Model), ("refinements", C.c_uint64), ("iterations", C.c_uint64), ("num_inliers", C.c_uint64),
                 ("inlier_ratio", C.c_double), ("model_score", C.c_double)]
@@ -283,6 +293,10 @@ PROTOTYPES = {
         "mdrp_reconstruct_pairs_async": [_p, _i, C.POINTER(DepthPairs), C.POINTER(ReconstructOpt), _i, _p, _i, _p, _p, _p, _p, _p],
         "mdrp_reconstruct_image_pairs_async": [_p, _i, C.POINTER(DepthImagePairs), C.POINTER(ReconstructOpt), _i, _p, _i, _p, _p, _p, _p, _p],
     },
+    "mdrp_scene.h": {  # an image set: the pairs chained along a tree, one fused cloud per scene
+        "mdrp_scene_transforms_async": [_p, _i, _i, _p, _i, _p, _i, _p, _p],
+        "mdrp_reconstruct_scene_async": [_p, _i, C.POINTER(DepthImagePairs), C.POINTER(ReconstructOpt), _i, _p, _i, _p, _p, _p, _p, _p, _p],
+    },
 }
 # what each header declares: mdrp.h's own list (with the four symbols that only get a restype), then its extension headers'
 EXPORTS = tuple(PROTOTYPES["mdrp.h"]) + ("mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version")
@@ -292,6 +306,7 @@ EXPORTS_CLASSIC_FRONTEND = tuple(PROTOTYPES["mdrp_classic_frontend.h"])
 EXPORTS_CLASSIC_FOCALS = tuple(PROTOTYPES["mdrp_classic_focals.h"])
 EXPORTS_DENSE = tuple(PROTOTYPES["mdrp_dense.h"])
 EXPORTS_RECONSTRUCT = tuple(PROTOTYPES["mdrp_reconstruct.h"])
+EXPORTS_SCENE = tuple(PROTOTYPES["mdrp_scene.h"])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -570,7 +585,29 @@ class _ReconstructCalls:
         self.reconstruct_pairs_device(kind, desc, opt, batch, models_ptr, model_stride, points_ptr, pixel_ptr, counts_ptr, cam1, cam2)
 
 
-class Handle(_ReconstructCalls):
+class _SceneCalls:
+    """The two calls of include/mdrp_scene.h, methods of Handle through this base.  Arguments go to the library as they are: the library checks them."""
+
+    def scene_transforms_device(self, kind, batch, models_ptr, model_stride, pairs_ptr, n_images, tree_ptr, transforms_ptr):
+        """the accumulated transform of every image of a tree on the handle's stream into the caller's device buffer, [n_images] SceneTransform
+        records.  pairs_ptr: int32 [batch][2], tree_ptr: int32 [n_images][2] (pair, role), both on the device.  Nothing synchronises."""
+        _check(self._lib, _fn(self._lib, "mdrp_scene_transforms_async")(self._h, int(kind), int(batch), _dev(models_ptr), int(model_stride), _dev(pairs_ptr),
+                                                                        int(n_images), _dev(tree_ptr), _dev(transforms_ptr)))
+
+    def reconstruct_scene_device(self, kind, desc, opt, batch, models_ptr, model_stride, tree_ptr, points_ptr, pixel_ptr, offsets_ptr, cams=None,
+                                 transforms_ptr=None):
+        """the fused cloud of an image set on the handle's stream into the caller's device buffers: points [p_max][3] float32, pixel [p_max] int32,
+        offsets [n_images + 1] int64, and the [n_images] transform records where transforms_ptr is given.  desc: a DepthImagePairs; cams: per
+        IMAGE, the calibrated kind alone.  Nothing synchronises."""
+        if not isinstance(desc, DepthImagePairs):
+            raise ValueError("reconstruct_scene_device takes a DepthImagePairs descriptor")
+        _, c, _ = _tables(None, cams, None)
+        _check(self._lib, _fn(self._lib, "mdrp_reconstruct_scene_async")(self._h, int(kind), C.byref(desc), C.byref(opt), int(batch), _dev(models_ptr),
+                                                                         int(model_stride), _dev(tree_ptr), _ptr(c), _dev(transforms_ptr),
+                                                                         _dev(points_ptr), _dev(pixel_ptr), _dev(offsets_ptr)))
+
+
+class Handle(_ReconstructCalls, _SceneCalls):
     """One handle = one HIP device + one stream + its scratch buffers.  Calls on one handle are serialised inside the
     library; use one handle per host thread for concurrency (default_handle() does).
 

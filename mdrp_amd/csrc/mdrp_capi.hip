@@ -13,6 +13,7 @@
 #include "mdrp_classic_focals.h"
 #include "mdrp_dense.h"
 #include "mdrp_reconstruct.h"
+#include "mdrp_scene.h"
 // MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior, kc_from_model, kc_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -209,6 +210,7 @@ struct mdrp_handle {
     DevBuf fp_nper, fp_in, fp_out;     // focals and pose from F (include/mdrp_classic_focals.h): n per pair | a host call's models, mask and principal points | its records
     DevBuf dn_scratch, dn_score;       // dense front end (include/mdrp_dense.h): the sampler's scratch, carved per call (DenseScratch) | mdrp_estimate_dense_async: the records' certainties
     DevBuf rc_scratch;                 // back end (include/mdrp_reconstruct.h): tile counts | the pairs' ReconPair | the two camera tables, carved per call
+    DevBuf sc_scratch;                 // scenes (include/mdrp_scene.h): the images' records (where the caller takes none) | their SceneImage | the camera table | tile counts, carved per call
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
     Pinned<Progress> progress_host;
     // sweep timing
@@ -2922,6 +2924,113 @@ int mdrp_reconstruct_image_pairs_async(mdrp_handle *h, int kind, const mdrp_dept
     a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = ip->depth_type; a.kind = kind;
     a.h1 = a.h2 = ip->h_max; a.w1 = a.w2 = ip->w_max;
     return reconstruct_call(h, c, opt);
+}
+
+} // extern "C"
+
+// ---- scenes: an image set's pairs chained along a tree, one fused cloud per scene (include/mdrp_scene.h; mdrp_scene.h)
+namespace {
+
+static_assert(MDRP_SCENE_ABSENT == SCENE_ABSENT && MDRP_SCENE_EDGE == SCENE_EDGE && MDRP_SCENE_ROOT == SCENE_ROOT, "values of the header and of the kernels");
+static_assert(sizeof(mdrp_scene_transform) == 128 && sizeof(SceneTransform) == 128 && offsetof(mdrp_scene_transform, t) == offsetof(SceneTransform, t) &&
+              offsetof(mdrp_scene_transform, s) == offsetof(SceneTransform, s) && offsetof(mdrp_scene_transform, f) == offsetof(SceneTransform, f) &&
+              offsetof(mdrp_scene_transform, shift) == offsetof(SceneTransform, shift) && offsetof(mdrp_scene_transform, root) == offsetof(SceneTransform, root) &&
+              offsetof(mdrp_scene_transform, depth) == offsetof(SceneTransform, depth) && offsetof(mdrp_scene_transform, depth) == 124, "record layout");
+
+// what both entry points refuse of the tree and the models
+const char *scene_tree_refusal(const SceneTree &t) {
+    if (t.batch < 0) return "negative batch";
+    if (t.n_images < 0) return "negative n_images";
+    if (t.kind < MDRP_CALIB || t.kind > MDRP_VARYING_FOCAL) return "only the monodepth estimators' models (kind 0..2) have depths to unproject";
+    if (t.model_stride < RECON_MODEL_BYTES || t.model_stride % 8 != 0) return "model_stride must be at least 96 and a multiple of 8";
+    if (t.n_images > 0 && !t.tree) return "NULL tree_dev";
+    if (t.n_images > 0 && t.batch > 0 && (!t.models || !t.pairs)) return "NULL models_dev or pairs";
+    return nullptr;
+}
+
+void scene_chain_launch(hipStream_t s, const SceneTree &t, const ReconCam *cams, SceneTransform *T, SceneImage *im) {
+    hipLaunchKernelGGL(k_scene_chain, dim3((unsigned)((t.n_images + SCENE_CHAIN_THREADS - 1) / SCENE_CHAIN_THREADS)), dim3(SCENE_CHAIN_THREADS), 0, s, t, cams, T, im);
+}
+
+} // namespace
+
+extern "C" {
+
+int mdrp_scene_transforms_async(mdrp_handle *h, int kind, int batch, const void *models_dev, int model_stride, const int32_t *pairs_dev, int n_images,
+                                const int32_t *tree_dev, mdrp_scene_transform *transforms_dev) {
+    if (!h) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    const SceneTree t{static_cast<const unsigned char *>(models_dev), pairs_dev, tree_dev, model_stride, kind, batch, n_images};
+    const char *why = scene_tree_refusal(t);
+    if (!why && n_images > 0 && !transforms_dev) why = "NULL transforms_dev";
+    if (why) { g_err = std::string("mdrp_scene_transforms_async: ") + why; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    if (n_images == 0) return MDRP_OK;
+    scene_chain_launch(h->stream, t, nullptr, reinterpret_cast<SceneTransform *>(transforms_dev), nullptr);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+int mdrp_reconstruct_scene_async(mdrp_handle *h, int kind, const mdrp_depth_image_pairs *ip, const mdrp_reconstruct_opt *opt, int batch, const void *models_dev,
+                                 int model_stride, const int32_t *tree_dev, const mdrp_camera *cams_host, mdrp_scene_transform *transforms_dev, float *points,
+                                 int32_t *pixel, int64_t *offsets) {
+    if (!h || !ip || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    const int n = ip->n_images;
+    const SceneTree t{static_cast<const unsigned char *>(models_dev), ip->pairs, tree_dev, model_stride, kind, batch, n};
+    const int64_t px = (int64_t)ip->h_max * ip->w_max;
+    const auto refusal = [&]() -> const char * {
+        if (const char *why = scene_tree_refusal(t)) return why;
+        if (kind == MDRP_CALIB && n > 0 && !cams_host) return "MDRP_CALIB needs cams_host, one record per image";
+        if (kind != MDRP_CALIB && cams_host) return "cameras are MDRP_CALIB's: a focal kind unprojects with the model's focals (pass NULL)";
+        if (ip->depth_type != MDRP_F32 && ip->depth_type != MDRP_F64) return "depth_type must be MDRP_F32 or MDRP_F64";
+        if (opt->keep != MDRP_KEEP_NOT_INF && opt->keep != MDRP_KEEP_FINITE) return "keep must be MDRP_KEEP_NOT_INF or MDRP_KEEP_FINITE";
+        if (opt->thr == 0) return "thr == 0 keeps nothing (1 .. MDRP_RECON_ALL)";
+        if (opt->p_max < 0) return "negative p_max";
+        if (ip->h_max < 0 || ip->w_max < 0) return "negative size";
+        if (ip->h_max > MDRP_RECON_MAX_EXTENT || ip->w_max > MDRP_RECON_MAX_EXTENT) return "extent above MDRP_RECON_MAX_EXTENT (65536)";
+        if (px > INT32_MAX) return "a map of 2^31 pixels or more";
+        if (!offsets) return "NULL offsets";
+        if (opt->p_max > 0 && (!points || !pixel)) return "NULL points or pixel";
+        if (n > 0 && px > 0 && !ip->depth) return "NULL depth map";
+        if (kind == MDRP_CALIB)
+            for (int i = 0; i < n; ++i)
+                if ((cams_host[i].model_id | 1) != 1) return "only SIMPLE_PINHOLE (0) and PINHOLE (1) cameras unproject here";
+        return nullptr;
+    };
+    if (const char *why = refusal()) { g_err = std::string("mdrp_reconstruct_scene_async: ") + why; return MDRP_ERR_INVALID; }
+    SceneArgs a{};
+    a.depth = ip->depth; a.center = ip->center; a.size = ip->size; a.depth_type = ip->depth_type; a.keep = opt->keep; a.n_images = n;
+    a.h = ip->h_max; a.w = ip->w_max; a.thr = opt->thr; a.seed = (uint32_t)opt->seed; a.p_max = opt->p_max;
+    a.nt = (int)std::max<int64_t>(1, (px + RECON_TILE - 1) / RECON_TILE); // (a map without pixels: one empty tile)
+    const size_t tiles = (size_t)n * (size_t)a.nt, nfill = ((size_t)a.p_max + RECON_TILE - 1) / RECON_TILE;
+    if (tiles + nfill > (size_t)INT32_MAX) { g_err = "mdrp_reconstruct_scene_async: the scene's tiles above 2^31 - 1: split the scene"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    // The scratch is one buffer of the handle, carved for this call's sizes; every word of it that a kernel reads was written by this call.
+    size_t total = 0;
+    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
+    const size_t o_T = carve(transforms_dev ? 0 : sizeof(SceneTransform) * (size_t)n), o_im = carve(sizeof(SceneImage) * (size_t)n),
+                 o_cam = carve(kind == MDRP_CALIB ? sizeof(ReconCam) * (size_t)n : 0), o_tcnt = carve(sizeof(uint32_t) * tiles);
+    if (int rc = h->sc_scratch.ensure(std::max<size_t>(total, 16))) return rc;
+    unsigned char *p = h->sc_scratch.as<unsigned char>();
+    hipStream_t s = h->stream;
+    const ReconCam *cams = nullptr;
+    if (kind == MDRP_CALIB && n > 0) { // pageable: the copy has left the caller's table when hipMemcpyAsync returns
+        HIPCHK(hipMemcpyAsync(p + o_cam, cams_host, sizeof(ReconCam) * (size_t)n, hipMemcpyHostToDevice, s));
+        cams = reinterpret_cast<const ReconCam *>(p + o_cam);
+    }
+    SceneTransform *T = transforms_dev ? reinterpret_cast<SceneTransform *>(transforms_dev) : reinterpret_cast<SceneTransform *>(p + o_T);
+    SceneImage *im = reinterpret_cast<SceneImage *>(p + o_im);
+    uint32_t *tcnt = reinterpret_cast<uint32_t *>(p + o_tcnt);
+    if (n > 0) {
+        scene_chain_launch(s, t, cams, T, im);
+        hipLaunchKernelGGL(k_scene_count, dim3((unsigned)tiles), dim3(RECON_THREADS), 0, s, a, (const SceneTransform *)T, tcnt);
+        hipLaunchKernelGGL(k_scene_scan, dim3((unsigned)n), dim3(RECON_THREADS), 0, s, 0, n, a.nt, tcnt, offsets);
+    }
+    hipLaunchKernelGGL(k_scene_scan, dim3(1), dim3(RECON_THREADS), 0, s, 1, n, a.nt, tcnt, offsets);
+    if (a.p_max > 0)
+        hipLaunchKernelGGL(k_scene_emit, dim3((unsigned)(tiles + nfill)), dim3(RECON_THREADS), 0, s, a, (const uint32_t *)tcnt, (const SceneTransform *)T,
+                           (const SceneImage *)im, (const int64_t *)offsets, points, pixel);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
 }
 
 } // extern "C"

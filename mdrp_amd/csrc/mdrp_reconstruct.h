@@ -66,14 +66,20 @@ MDRP_HD double recon_mul(double a, double b) {
     return r;
 }
 
-// R5 and R6 for one kept pixel: every product and every sum is rounded on its own, as NumPy rounds them (a product that feeds a sum is a recon_mul).
-// (v, u): the pixel; (c0, c1): its image's centre; d: its depth.  out: the point in camera 2's frame, before the rounding to float32.
-MDRP_HD void recon_point(const ReconPair &p, int side, uint32_t v, uint32_t u, double c0, double c1, double d, double out[3]) {
-    const ReconSide &s = p.s[side];
+// R5 alone: the point of pixel (v, u) with depth d in its own camera's frame; (c0, c1): its image's centre (shared with the scene kernels, mdrp_scene.h)
+MDRP_HD void recon_unproject(const ReconSide &s, uint32_t v, uint32_t u, double c0, double c1, double d, double X[3]) {
     const double x = (double)u - c0, y = (double)v - c1;
     const double xn = (x - s.ox) * s.rx, yn = (y - s.oy) * s.ry;
     const double z = d + s.shift;
-    const double X0 = xn * z, X1 = yn * z;
+    X[0] = xn * z; X[1] = yn * z; X[2] = z;
+}
+
+// R5 and R6 for one kept pixel: every product and every sum is rounded on its own, as NumPy rounds them (a product that feeds a sum is a recon_mul).
+// (v, u): the pixel; (c0, c1): its image's centre; d: its depth.  out: the point in camera 2's frame, before the rounding to float32.
+MDRP_HD void recon_point(const ReconPair &p, int side, uint32_t v, uint32_t u, double c0, double c1, double d, double out[3]) {
+    double X[3];
+    recon_unproject(p.s[side], v, u, c0, c1, d, X);
+    const double X0 = X[0], X1 = X[1], z = X[2];
     if (side != 0) {
         out[0] = X0; out[1] = X1; out[2] = z;
         return;
@@ -99,16 +105,19 @@ MDRP_HD ReconSide recon_side(int kind, int id, const double *c, double f, double
     return s;
 }
 
-// the pair's record from its model and its two cameras (cam: model_id 0 {f, cx, cy}, 1 {fx, fy, cx, cy}; null for a focal kind).  R by the
-// expressions of poselib._quat_to_R as they are written there.
-MDRP_HD void recon_pair(const double *m, int kind, int id1, const double *cam1, int id2, const double *cam2, ReconPair &p) {
+// R6's rotation from the model's q = (w, x, y, z), by the expressions of poselib._quat_to_R as they are written there (shared with mdrp_scene.h)
+MDRP_HD void recon_rotation(const double *m, double R[9]) {
     const double w = m[0], x = m[1], y = m[2], z = m[3];
     const double xx = recon_mul(x, x), yy = recon_mul(y, y), zz = recon_mul(z, z), xy = recon_mul(x, y), xz = recon_mul(x, z), yz = recon_mul(y, z);
     const double wx = recon_mul(w, x), wy = recon_mul(w, y), wz = recon_mul(w, z);
     // (2 s is exact: 1 - 2 s rounds once, fused or not)
-    p.R[0] = 1.0 - 2.0 * (yy + zz); p.R[1] = 2.0 * (xy - wz); p.R[2] = 2.0 * (xz + wy);
-    p.R[3] = 2.0 * (xy + wz); p.R[4] = 1.0 - 2.0 * (xx + zz); p.R[5] = 2.0 * (yz - wx);
-    p.R[6] = 2.0 * (xz - wy); p.R[7] = 2.0 * (yz + wx); p.R[8] = 1.0 - 2.0 * (xx + yy);
+    R[0] = 1.0 - 2.0 * (yy + zz); R[1] = 2.0 * (xy - wz); R[2] = 2.0 * (xz + wy);
+    R[3] = 2.0 * (xy + wz); R[4] = 1.0 - 2.0 * (xx + zz); R[5] = 2.0 * (yz - wx);
+    R[6] = 2.0 * (xz - wy); R[7] = 2.0 * (yz + wx); R[8] = 1.0 - 2.0 * (xx + yy);
+}
+// the pair's record from its model and its two cameras (cam: model_id 0 {f, cx, cy}, 1 {fx, fy, cx, cy}; null for a focal kind)
+MDRP_HD void recon_pair(const double *m, int kind, int id1, const double *cam1, int id2, const double *cam2, ReconPair &p) {
+    recon_rotation(m, p.R);
     p.t[0] = m[4]; p.t[1] = m[5]; p.t[2] = m[6];
     p.inv = 1.0 / m[7];
     p.s[0] = recon_side(kind, id1, cam1, m[10], m[8]);
@@ -162,11 +171,11 @@ __device__ __forceinline__ ReconView recon_view(const ReconArgs &a, size_t b, in
 }
 
 // R2-R4 for the RECON_PER_LANE consecutive pixels of a lane that start at pixel p0 of a view with npix pixels: bit j of the result is set iff pixel
-// p0 + j is kept; d[j], vv[j], uu[j] are its depth and coordinates.  One division per lane.
+// p0 + j is kept; d[j], vv[j], uu[j] are its depth and coordinates.  One division per lane.  (own_stage: the scene kernels', mdrp_scene.h; 0 = the side's)
 __device__ __forceinline__ unsigned recon_lane(const ReconArgs &a, const ReconView &vw, int side, uint32_t npix, uint32_t p0, double d[RECON_PER_LANE],
-                                               uint32_t vv[RECON_PER_LANE], uint32_t uu[RECON_PER_LANE]) {
+                                               uint32_t vv[RECON_PER_LANE], uint32_t uu[RECON_PER_LANE], uint32_t own_stage = 0) {
     const void *map = side ? a.depth2 : a.depth1;
-    const uint32_t stage = side ? RECON_STAGE_2 : RECON_STAGE_1;
+    const uint32_t stage = own_stage ? own_stage : (side ? RECON_STAGE_2 : RECON_STAGE_1);
     unsigned kept = 0;
     if (p0 >= npix) return 0; // (npix > 0: w > 0)
     uint32_t v = p0 / (uint32_t)vw.w, u = p0 - v * (uint32_t)vw.w;

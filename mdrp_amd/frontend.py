@@ -40,6 +40,11 @@ density-balanced second draw, the records.  Every quantity that decides a pick i
 models and the pairs' depth maps to the fused two-view point cloud in camera 2's frame.  `reconstruct_pair_numpy` and `reconstruct_image_pairs_numpy`
 at the end of this module are their definition, rules R1-R7 of the header: the usable-model rule, the pixel order, the integer subsample, the depth
 filter, the unprojection and the transform in float64 with one rounding per arithmetic sign, the rows and their truncation.
+
+`poselib.scene_transforms_torch` / `reconstruct_scene_torch` chain an image set's pairs along a tree and fuse ONE cloud per scene
+(include/mdrp_scene.h).  `scene_transforms_numpy` and `reconstruct_scene_numpy` at the end of this module are their definition, rules
+S1-S6 of the header: the tree and its detached images, the accumulation leaf upward in float64 without a fused multiply-add, R3-R5 on a stage of
+their own with the image mixed into the seed, the rows in image order and the int64 offsets.
 """
 import numpy as np
 
@@ -502,6 +507,16 @@ def _quat_rows(q):
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
+def _recon_unproject(v, u, d, c, rx, ry, cx, cy, shift):
+    """R5 for kept pixels (v, u) with depths d: (n, 3) float64, every line one rounding per sign"""
+    x = u.astype(np.float64) - c[0]
+    y = v.astype(np.float64) - c[1]
+    xn = (x - cx) * rx
+    yn = (y - cy) * ry
+    z = d + shift
+    return np.stack([xn * z, yn * z, z], axis=1)
+
+
 def reconstruct_side_numpy(model, kind, side, depth_map, center=None, camera=None, keep="not_inf", thr=RECON_ALL, seed=0):
     """R2-R6 for one image of one pair whose model is usable: (points (n, 3) FLOAT64 in camera 2's frame, before R7's rounding; v (n,), u (n,) int64,
     the kept pixels in row-major order).  side 0 is image 1 (transformed), side 1 is image 2 (as it stands)."""
@@ -519,12 +534,7 @@ def reconstruct_side_numpy(model, kind, side, depth_map, center=None, camera=Non
         d = d_all[v, u]
         c = np.zeros(2) if center is None else np.asarray(center, dtype=np.float64).reshape(2)
         rx, ry, cx, cy = _recon_intrinsics(m, kind, side, camera)
-        x = u.astype(np.float64) - c[0]                                                   # R5: every line is one rounding per sign
-        y = v.astype(np.float64) - c[1]
-        xn = (x - cx) * rx
-        yn = (y - cy) * ry
-        z = d + np.float64(m["shift2"] if side else m["shift1"])
-        X = np.stack([xn * z, yn * z, z], axis=1)
+        X = _recon_unproject(v, u, d, c, rx, ry, cx, cy, np.float64(m["shift2"] if side else m["shift1"]))
         if side == 0:                                                                     # R6
             R, t, inv = _quat_rows(m["q"]), np.asarray(m["t"], dtype=np.float64), np.float64(1.0) / np.float64(m["scale"])
             X = np.stack([inv * (((R[r, 0] * X[:, 0] + R[r, 1] * X[:, 1]) + R[r, 2] * X[:, 2]) + t[r]) for r in range(3)], axis=1)
@@ -608,3 +618,181 @@ def reconstruct_image_pairs_numpy(models, kind, depth_maps, pairs, p_max, center
             models[b], kind, dm[a][:hs[a], :ws[a]], dm[c][:hs[c], :ws[c]], None if cs is None else cs[a], None if cs is None else cs[c],
             None if cameras1 is None else cameras1[b], None if cameras2 is None else cameras2[b], keep, thr, seed, p_max, W, W)
     return points, pixel, counts
+
+
+# ---- a scene (include/mdrp_scene.h): the pairs of an image set chained along a tree, every image unprojected once into the frame of
+# its root.  Rules S1-S6 of the header.  The tree is walked in a fixed order and every product and sum of the accumulation is rounded on its own, so
+# the transform records, and with them the points, are defined as bytes.
+SCENE_STAGE = 5          # R3's stage for a scene (3 and 4 are the two-view back end's)
+SCENE_ABSENT, SCENE_EDGE, SCENE_ROOT = 0, 1, 2  # tree[i][1], the role
+SCENE_SEED_MUL = 0xC2B2AE35
+SCENE_TRANSFORM_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("s", "<f8"), ("f", "<f8"), ("shift", "<f8"), ("root", "<i4"), ("depth", "<i4")])
+assert SCENE_TRANSFORM_DTYPE.itemsize == 128  # mdrp_scene_transform
+
+
+def scene_seed(seed, image):
+    """S3: the seed of image `image`: lowbias32(seed + 0xC2B2AE35 * (image + 1)) in uint32 arithmetic; R3's hash takes it in the seed's place"""
+    return int(lowbias32(((int(seed) & _M32) + SCENE_SEED_MUL * (int(image) + 1)) & _M32)[0])
+
+
+def _scene_edge(models, kind, pairs, tree, I, i):
+    """S1 for image i: None where it is absent or detached by its own entry, else (role, the other image of its pair or -1, R (3, 3), t (3,), s, the
+    image's own f, its own shift), the edge that takes a point of image i's camera to the other image's: (R X + t) / s"""
+    one, zero = np.float64(1.0), np.float64(0.0)
+    p, role = int(tree[i][0]), int(tree[i][1])
+    if role not in (SCENE_EDGE, SCENE_ROOT):
+        return None
+    if role == SCENE_ROOT and p == -1:
+        return (SCENE_ROOT, -1, np.eye(3), np.zeros(3), one, zero, zero) if kind == "calibrated" else None
+    if not 0 <= p < len(pairs):
+        return None
+    a, c = int(pairs[p][0]), int(pairs[p][1])
+    if a == c or i not in (a, c):
+        return None
+    other = c if i == a else a
+    if not image_valid(other, I):
+        return None
+    m = models[p]
+    if not recon_usable(m, kind):
+        return None
+    first = i == a
+    shift = np.float64(m["shift1"] if first else m["shift2"])
+    f = zero if kind == "calibrated" else np.float64(m["f1"] if first else m["f2"])
+    if role == SCENE_ROOT:
+        return SCENE_ROOT, other, np.eye(3), np.zeros(3), one, f, shift
+    R, t, scale = _quat_rows(m["q"]), np.asarray(m["t"], dtype=np.float64), np.float64(m["scale"])
+    if first:                                                                             # the model itself: X_c = (R X_a + t) / scale
+        return SCENE_EDGE, other, R, t, scale, f, shift
+    inv = one / scale                                                                     # its inverse: X_a = (R^T X_c - (R^T t) inv) / inv
+    ti = np.array([-(((R[0, r] * t[0] + R[1, r] * t[1]) + R[2, r] * t[2]) * inv) for r in range(3)])
+    return SCENE_EDGE, other, np.ascontiguousarray(R.T), ti, inv, f, shift
+
+
+def _scene_compose(Re, te, se, R, t, s):
+    """S2: the edge e behind the accumulated (R, t, s): R' = Re R with each sum taken left to right, t' = Re t + s te, s' = s se"""
+    Rn = np.array([[(Re[r, 0] * R[0, c] + Re[r, 1] * R[1, c]) + Re[r, 2] * R[2, c] for c in range(3)] for r in range(3)])
+    tn = np.array([((Re[r, 0] * t[0] + Re[r, 1] * t[1]) + Re[r, 2] * t[2]) + s * te[r] for r in range(3)])
+    return Rn, tn, s * se
+
+
+def scene_transforms_numpy(models, kind, pairs, tree, n_images):
+    """S1 and S2: models (B,) MODEL_DTYPE, pairs (B, 2) image indices (a, c), tree (I, 2) (pair, role) -> (I,) SCENE_TRANSFORM_DTYPE.  The record of
+    an absent or detached image is zeros with root = depth = -1.  This function is the definition."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    I = int(n_images)
+    pairs = np.asarray(pairs).astype(np.int64).reshape(-1, 2)
+    tree = np.asarray(tree).astype(np.int64).reshape(I, 2)
+    models = np.asarray(models).reshape(-1)
+    if len(models) != len(pairs):
+        raise ValueError("one model per pair")
+    out = np.zeros(I, dtype=SCENE_TRANSFORM_DTYPE)
+    out["root"] = out["depth"] = -1
+    with np.errstate(all="ignore"):
+        edges = [_scene_edge(models, kind, pairs, tree, I, i) for i in range(I)]
+        for i, e in enumerate(edges):
+            if e is None:
+                continue
+            role, node, R, t, s, f, shift = e
+            root, depth = (i, 0) if role == SCENE_ROOT else (-1, 1)
+            if role == SCENE_EDGE:
+                for _ in range(I):                                                        # the walk is cut after I steps: a cycle ends as detached
+                    en = edges[node]
+                    if en is None:
+                        break
+                    if en[0] == SCENE_ROOT:
+                        root = node
+                        break
+                    R, t, s = _scene_compose(en[2], en[3], en[4], R, t, s)
+                    depth += 1
+                    node = en[1]
+            if root < 0:
+                continue
+            out[i] = (R.reshape(9), t, s, f, shift, root, depth)
+    return out
+
+
+def scene_unproject(transform, kind, v, u, d, center=None, camera=None):
+    """S5: pixels (v, u) (arrays; an integer pixel is its own coordinate) with float64 depths d of an image with record `transform` -> (n, 3) float64
+    in the image's own camera frame, by R5's lines with the image's own focal and shift"""
+    T = np.asarray(transform).reshape(())
+    c = np.zeros(2) if center is None else np.asarray(center, dtype=np.float64).reshape(2)
+    rx, ry, cx, cy = _recon_intrinsics({"f1": T["f"], "f2": T["f"]}, kind, 0, camera)
+    return _recon_unproject(np.asarray(v), np.asarray(u), d, c, rx, ry, cx, cy, np.float64(T["shift"]))
+
+
+def scene_transform_points(transform, X):
+    """S6: points X (n, 3) float64 of an image's camera frame into its root's frame; a root's points are X as it stands"""
+    T = np.asarray(transform).reshape(())
+    if T["depth"] == 0:
+        return X
+    R, t, inv = T["R"].reshape(3, 3), T["t"], np.float64(1.0) / np.float64(T["s"])
+    return np.stack([(((R[r, 0] * X[:, 0] + R[r, 1] * X[:, 1]) + R[r, 2] * X[:, 2]) + t[r]) * inv for r in range(3)], axis=1).reshape(-1, 3)
+
+
+def scene_image_rows_numpy(transform, kind, image, depth_map, center=None, camera=None, keep="not_inf", thr=RECON_ALL, seed=0, w_alloc=None):
+    """S3-S6 for one attached image: (points (n, 3) float32 in its root's frame, pixel (n,) int32), every kept pixel in row-major order"""
+    dm = _table(depth_map, "depth maps")
+    h, w = dm.shape
+    T = np.asarray(transform).reshape(())
+    wa = w if w_alloc is None else int(w_alloc)
+    with np.errstate(all="ignore"):
+        d_all = dm.astype(np.float64)
+        kept = recon_candidates(h, w, thr, scene_seed(seed, image), SCENE_STAGE) & recon_keep(d_all, keep)      # S3, S4
+        v, u = np.nonzero(kept)
+        X = scene_transform_points(T, scene_unproject(T, kind, v, u, d_all[v, u], center, camera))
+        return X.reshape(-1, 3).astype(np.float32), (v * wa + u).astype(np.int32)                                # S6: one rounding
+
+
+def pack_scene_rows(rows, p_max=None):
+    """S6's placement: per image (points, pixel) or None -> (points (p_max, 3) float32, pixel (p_max,) int32, offsets (I + 1,) int64); p_max None =
+    every row.  Rows are written while they fit; the offsets are the true ones; behind the last written row 0, 0, 0 and -1."""
+    n = [0 if r is None else len(r[1]) for r in rows]
+    offsets = np.concatenate([[0], np.cumsum(n, dtype=np.int64)]).astype(np.int64)
+    p_max = int(offsets[-1]) if p_max is None else int(p_max)
+    if p_max < 0:
+        raise ValueError("p_max must not be negative")
+    points, pixel = np.zeros((p_max, 3), dtype=np.float32), np.full(p_max, -1, dtype=np.int32)
+    for r, start in zip(rows, offsets[:-1]):
+        if r is None or start >= p_max:
+            continue
+        k = min(len(r[1]), p_max - int(start))
+        points[start:start + k] = r[0][:k]; pixel[start:start + k] = r[1][:k]
+    return points, pixel, offsets
+
+
+def scene_rows_numpy(transforms, kind, depth_maps, centers=None, sizes=None, cameras=None, keep="not_inf", thr=RECON_ALL, seed=0):
+    """per image the kept rows of scene_image_rows_numpy on its valid region, None for an absent or detached image"""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    if keep not in KEEPS:
+        raise ValueError(f"keep must be one of {KEEPS}, not {keep!r}")
+    dm = _table(depth_maps, "depth maps")
+    if dm.ndim != 3:
+        raise ValueError("expected depth maps (I, H, W)")
+    I, H, W = dm.shape
+    if len(transforms) != I:
+        raise ValueError("one transform per image")
+    hw = np.tile(np.array([H, W], dtype=np.int64), (I, 1)) if sizes is None else np.asarray(sizes).reshape(I, 2)
+    hs, ws = clamp_extent(hw[:, 0], H), clamp_extent(hw[:, 1], W)
+    cs = None if centers is None else np.asarray(centers, dtype=np.float64)
+    if cs is not None and cs.size == 2:
+        cs = np.tile(cs.reshape(1, 2), (I, 1))
+    if cs is not None and cs.shape != (I, 2):
+        raise ValueError("centers must have shape (I, 2) or (2,)")
+    if kind == "calibrated" and (cameras is None or len(cameras) != I):
+        raise ValueError("the calibrated kind needs one camera per image")
+    return [None if transforms[i]["depth"] < 0 else
+            scene_image_rows_numpy(transforms[i], kind, i, dm[i][:hs[i], :ws[i]], None if cs is None else cs[i], None if cameras is None else cameras[i],
+                                   keep, thr, seed, W) for i in range(I)]
+
+
+def reconstruct_scene_numpy(models, kind, depth_maps, pairs, tree, p_max=None, centers=None, sizes=None, cameras=None, keep="not_inf", thr=RECON_ALL,
+                            seed=0):
+    """models (B,) MODEL_DTYPE, depth_maps (I, H, W) float32 / float64, pairs (B, 2), tree (I, 2) (pair, role); sizes (I, 2) clamped to the
+    allocation; centers (I, 2) or (2,); cameras: one per IMAGE (calibrated kind), records or dicts with model_id and params.  Returns (points
+    (p_max, 3) float32, pixel (p_max,) int32 = v * W + u, offsets (I + 1,) int64, transforms (I,) SCENE_TRANSFORM_DTYPE) by S1-S6; p_max None =
+    every row.  This function is the definition."""
+    I = np.shape(depth_maps)[0]
+    T = scene_transforms_numpy(models, kind, pairs, tree, I)
+    return (*pack_scene_rows(scene_rows_numpy(T, kind, depth_maps, centers, sizes, cameras, keep, thr, seed), p_max), T)

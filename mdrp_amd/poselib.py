@@ -2005,3 +2005,8 @@ def refine_batch_torch(kind, points2D_1, points2D_2, depth_1, depth_2, models, c
 # ---- the back end (include/mdrp_reconstruct.h): fused two-view point clouds from models and depth maps.  mdrp_amd/reconstruct.py holds
 # the three entry points; they are found here, beside the estimators whose records they take.
 from .reconstruct import reconstruct_image_pairs_torch, reconstruct_pair, reconstruct_pairs_torch  # noqa: E402, F401
+
+
+# ---- scenes (include/mdrp_scene.h): an image set's pairs chained along a tree, one fused cloud per scene.  mdrp_amd/scene.py holds the
+# entry points; they are found here, beside the estimators whose records they take.
+from .scene import reconstruct_scene, reconstruct_scene_torch, scene_transforms_torch, scene_tree, video_tree  # noqa: E402, F401
