@@ -298,6 +298,7 @@ int env_int(const char *name, int dflt) {
     const char *v = getenv(name);
     return v ? atoi(v) : dflt;
 }
+bool front_clear_on() { return env_int("MDRP_FRONT_CLEAR", 1) != 0; } // (read by estimate_device and by its passes)
 
 // LDS work lists: 2 buffers of u16 indices, stride = n_max rounded to 64 (0 disables the lists)
 int lm_list_stride(int n_max) { return n_max <= LM_LIST_MAX_N ? ((n_max + 63) / 64) * 64 : 0; }
@@ -420,6 +421,7 @@ struct PassIn {
     const Model *priors;  // device memory, one per pair of the pass, or null (mdrp_estimate_batch_prior, mdrp_estimate_classic_prior; never with `host` or `bud`)
     int prior_space;      // the baselines' priors: 0 = the caller's units, 1 = the estimator's normalised coordinates (include/mdrp_classic_models.h)
     const uint64_t *prosac; // ranked call: max_prosac_iterations of the progressive sampler (mdrp_prosac.h), or null: the uniform sampler
+    bool clear_lm_stats;    // the call's first pass, where estimate_device has left the LM statistics to the pass's front clear (Pass::clear_front)
 };
 
 // One estimator call, as its entry point describes it to estimate_device (and, with the caller's models beside it, to the refine calls).  Every
@@ -502,6 +504,19 @@ int launch_scan(hipStream_t s, int mps, int pairs, const RunParams &r, PairState
     if (r.chunk_len >= 1024) MDRP_SCAN(4, 4);
     MDRP_SCAN(4, 1);
 #undef MDRP_SCAN
+}
+// ... and of a chunk that was swept against a bar, from the sweep's sorted tag lists (k_scan_list; `list_cap` candidates per pair at most, pairs
+// with more are walked as above by the same instantiation)
+void launch_scan_list(hipStream_t s, int mps, int pairs, const RunParams &r, PairState *st, const double *slot_score, const int32_t *slot_inl, Trigger *trig,
+                      int trig_cap, const int32_t *model_count, const uint32_t *tags_sorted, int list_cap, unsigned long long *scan_stats) {
+    const int cap = std::min(std::max(list_cap, 0), SCAN_LIST_MAX);
+#define MDRP_SCAN_LIST(M, I) \
+    hipLaunchKernelGGL((k_scan_list<M, I>), dim3(pairs), dim3(SCAN_LIST_THREADS), 0, s, r, st, slot_score, slot_inl, trig, trig_cap, model_count, tags_sorted, cap, scan_stats)
+    if (mps == 16) MDRP_SCAN_LIST(16, 1);
+    else if (mps == 12) MDRP_SCAN_LIST(12, 1);
+    else if (r.chunk_len >= 1024) MDRP_SCAN_LIST(4, 4);
+    else MDRP_SCAN_LIST(4, 1);
+#undef MDRP_SCAN_LIST
 }
 
 // Chunk c of the super-chunk under way, for the pairs [p0, p0 + pc).  Every kernel of the front indexes its per-pair arrays as base[pair]: a RANGE
@@ -672,6 +687,14 @@ struct Pass : PassIn {
     const int first_pick = sched::first_pick(kind, batch_call, SCORE_WAVE_MAX_PAIRS, env_int("MDRP_FIRST_PICK", -1));
     // solver wavefronts per SIMD beside a first chunk's sweeps (sched::solver_reservation); set: that R with no LDS kept free, 0 = uncapped
     const int solve_resident = env_int("MDRP_SOLVE_RESIDENT", -1);
+    // a run's second chunk: its solver starts behind k_prep (sched::second_solver_after); 0 = behind the first chunk's solver
+    const int solve_behind_prep = env_int("MDRP_SOLVE_BEHIND_PREP", -1);
+    // the first super-chunk's small blocks are cleared by one kernel in front of k_prep (clear_front); 0 = one memset each where they are used
+    const bool front_clear = front_clear_on();
+    // the scan behind a chunk with a bar reads the exact sweep's lists (k_scan_list); 0 = it walks every slot.  The cap: candidates per pair the list
+    // scan takes (pairs with more are walked in full; the tests lower it to reach that path)
+    const bool scan_list = env_int("MDRP_SCAN_LIST", 1) != 0;
+    const int scan_list_cap = env_int("MDRP_SCAN_LIST_CAP", SCAN_LIST_MAX);
     const int lo_threads = env_int("MDRP_LO_THREADS", sched::lo_lanes(batch_call, n_max));
     const int final_threads = env_int("MDRP_FINAL_THREADS", sched::final_lanes(batch_call));
     const int samp_threads = env_int("MDRP_SAMPLE_THREADS", ssz == 3 ? SAMP_THREADS : (ssz == 5 ? 512 : 256)); // ~ samples between two rejections
@@ -712,6 +735,7 @@ struct Pass : PassIn {
     uint64_t it0 = 0;
     sched::Layout lay;
     bool piped = false, fuse_tail = false, presampled[2] = {false, false};
+    bool front_cleared = false, fuse_cleared = false; // clear_front has filled the first super-chunk's blocks (and the fused tail's)
     hipStream_t aux = nullptr, aux2 = nullptr; // the handle's, or `s` where the super-chunk is not pipelined
     int32_t *fz_ctl = nullptr, *fz_done = nullptr, *fz_fin = nullptr, *fz_ready = nullptr;
     bool final_done = false; // the fused tail has run the final refinements
@@ -789,6 +813,41 @@ struct Pass : PassIn {
         return MDRP_OK;
     }
 
+    // Device-resident inputs: what the run's first super-chunk starts from, filled by ONE kernel on the main stream in front of the parameter upload
+    // and k_prep, where the GPU has nothing else to do — the counters, the candidate statistics, the model counts of both chunk parities, the fused
+    // tail's block where that super-chunk will end with the fused tail, and (the call's first pass) the LM statistics.  begin_super_chunk, solve and
+    // lo then issue no memset for it; later super-chunks, the sliced host front and the stage-by-stage entry points keep theirs.
+    // Stream order covers every block: each is last read by the previous pass or call on the main stream or behind an event the main stream has
+    // waited for (the LO launch on aux2: ev_lo; the solvers on aux: ev_solved), and first written behind an event recorded on the main stream after
+    // this launch (the second chunk's solver on aux: ev_prepped or ev_solved[0]; the LO launch on aux2: ev_scanned).  The ready list of the fused tail
+    // (all ones) is read by the previous k_final on the main stream and published to by this pass's k_lo behind ev_scanned.
+    int clear_front() {
+        if (!front_clear || host) return MDRP_OK;
+        const sched::Layout l0 = sched::super_chunk_layout(0, certain, chunk_cap, lead, 0, ro->max_iterations);
+        const bool fuse0 = fuse_env && l0.n_chunks > 1 && lo_overlap && l0.super_len >= ro->max_iterations; // (begin_super_chunk's fuse_tail at it0 = 0)
+        ClearList cl{};
+        auto add = [&cl](void *p_, size_t bytes, uint32_t value) {
+            cl.p[cl.n] = static_cast<uint32_t *>(p_); cl.words[cl.n] = (uint32_t)(bytes / sizeof(uint32_t)); cl.value[cl.n] = value; cl.n++;
+        };
+        const size_t b = (size_t)batch;
+        add(h->counters.p, sizeof(Counters), 0);
+        add(h->cand_stat.p, sizeof(unsigned long long) * 2 * b, 0);
+        add(h->model_count[0].p, sizeof(int32_t) * 2 * b, 0);
+        add(h->model_count[1].p, sizeof(int32_t) * 2 * b, 0);
+        if (fuse0) {
+            if (int rc = h->fuse.ensure(sz.fuse)) return rc;
+            int32_t *ctl = h->fuse.as<int32_t>();
+            add(ctl, 64 + 2 * sizeof(int32_t) * b, 0);              // control words | done flags | final-refinement flags
+            add(ctl + 16 + 2 * b, sizeof(int32_t) * b, 0xFFFFFFFFu); // ready list
+        }
+        if (clear_lm_stats) add(h->lm_stats.p, LM_STATS_BYTES, 0);
+        static_assert(7 <= CLEAR_BLOCKS_MAX && sizeof(Counters) % 4 == 0 && LM_STATS_BYTES % 4 == 0, "clear list");
+        const int blocks = (int)std::min<size_t>(64, (4 * b + CLEAR_THREADS - 1) / CLEAR_THREADS);
+        hipLaunchKernelGGL(k_clear, dim3(std::max(blocks, 1)), dim3(CLEAR_THREADS), 0, s, cl);
+        front_cleared = true; fuse_cleared = fuse0;
+        return MDRP_OK;
+    }
+
     // normalisation, record layout, MFMA fragments and pair states of the pairs [p0, p0 + pc) (one workgroup per pair, bases offset by p0)
     void prep(int p0, int pc, hipStream_t st_) {
         const size_t o2 = (size_t)2 * p0 * n_max, o1 = (size_t)p0 * n_max;
@@ -835,8 +894,10 @@ struct Pass : PassIn {
         lay = layout;
         if (it0 == 0) h->first_chunk = (int64_t)lay.lens[0];
         rp.chunk_start = it0; rp.super_len = (int)lay.super_len;
-        HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
-        if (it0 == 0) HIPCHK(hipMemsetAsync(h->cand_stat.p, 0, sizeof(unsigned long long) * 2 * batch, s));
+        if (!(front_cleared && it0 == 0)) { // (clear_front has done both)
+            HIPCHK(hipMemsetAsync(h->counters.p, 0, sizeof(Counters), s));
+            if (it0 == 0) HIPCHK(hipMemsetAsync(h->cand_stat.p, 0, sizeof(unsigned long long) * 2 * batch, s));
+        }
         piped = lay.n_chunks > 1 && lo_overlap;
         fuse_tail = fuse_env && piped && it0 + lay.super_len >= ro->max_iterations;
         if (fuse_tail) {
@@ -899,7 +960,8 @@ struct Pass : PassIn {
     int solve(const ChunkView &v, hipStream_t st_) {
         const RunParams &r = v.r;
         const int pc = v.pc;
-        HIPCHK(hipMemsetAsync(v.model_count, 0, sizeof(int32_t) * 2 * pc, st_));
+        // (clear_front has cleared both parities for the first two chunks of the run; a third chunk takes the first one's over)
+        if (!(front_cleared && it0 == 0 && v.c < 2)) HIPCHK(hipMemsetAsync(v.model_count, 0, sizeof(int32_t) * 2 * pc, st_));
         if (v.c < 2 && presampled[v.c]) HIPCHK(hipStreamWaitEvent(st_, h->ev_sampled[v.c], 0));
         else samples(st_, r.chunk_len, v.samples);
         hipEvent_t v0, v1;
@@ -987,7 +1049,10 @@ struct Pass : PassIn {
 
     // ordered prefix over the iterations: LO triggers
     void scan(const ChunkView &v) {
-        (void)launch_scan(s, mps, v.pc, v.r, v.st, v.slot_score, v.slot_inl, v.trig, trig_cap, v.model_count, &cnt->progress.evals_sweep);
+        if (scan_list && !v.first_of_run) // (a first chunk's NaN-model slots are on no list, and most of its slots hold a result)
+            launch_scan_list(s, mps, v.pc, v.r, v.st, v.slot_score, v.slot_inl, v.trig, trig_cap, v.model_count, v.tags_sorted, scan_list_cap,
+                             &cnt->progress.evals_sweep);
+        else (void)launch_scan(s, mps, v.pc, v.r, v.st, v.slot_score, v.slot_inl, v.trig, trig_cap, v.model_count, &cnt->progress.evals_sweep);
     }
 
     // count -> bound -> sort -> plan -> exact score -> scan of the view, on the main stream
@@ -1055,7 +1120,7 @@ struct Pass : PassIn {
     int lo(int c) {
         int32_t *lo_plan = h->work_pair.as<int32_t>();
         hipLaunchKernelGGL(k_lo_plan, dim3(1), dim3(PLAN_THREADS), 0, s, batch, h->st.as<PairState>(), (const int32_t *)nullptr, lo_plan);
-        if (fuse_tail) {
+        if (fuse_tail && !(front_cleared && fuse_cleared && it0 == 0)) {
             HIPCHK(hipMemsetAsync(fz_ctl, 0, 64 + 2 * sizeof(int32_t) * (size_t)batch, s));
             HIPCHK(hipMemsetAsync(fz_ready, 0xFF, sizeof(int32_t) * (size_t)batch, s));
         }
@@ -1169,8 +1234,8 @@ struct Pass : PassIn {
 
 // The stream schedule of a pass.  A super-chunk of several chunks is pipelined over three streams (the benchmark shape: 256 | 9744
 // iterations); chunk c + 1 is solved while chunk c is swept, and the super-chunk has ONE LO launch, behind its last scan:
-//   main:  prep solve0 count0 sort0 score0 scan0 | (wait solve1) count1 bound1 sort1 score1 scan1 | gate, final refinements (fused tail) | walk
-//   aux :       (after solve0) solve1 ...
+//   main:  clear prep solve0 count0 sort0 score0 scan0 | (wait solve1) count1 bound1 sort1 score1 scan1 | gate, final refinements (fused tail) | walk
+//   aux :       (after prep; sched::second_solver_after) solve1 ...
 //   aux2:  samples0 samples1 (beside prep)                                                        | (after the last scan) LO: ALL triggers of the super-chunk
 // Host buffers of 512 pairs or more arrive in slices on a fourth stream (Pass::host_front):
 //   copy:  slice0 slice1 slice2 slice3
@@ -1181,12 +1246,13 @@ int run_pass(mdrp_handle *h, const PassIn &in) {
     Pass p(h, in);
     hipStream_t s = p.s;
     int rc;
-    if ((rc = p.plan_and_allocate()) || (rc = p.upload_params())) return rc;
+    if ((rc = p.plan_and_allocate()) || (rc = p.clear_front()) || (rc = p.upload_params())) return rc;
     HIPCHK(hipEventRecord(h->ev_tables, s)); // sample tables can be drawn from here on
     if (!p.host) { // device-resident inputs: everything is there (host buffers: the copies and k_prep are issued slice by slice by host_front)
         p.prep(0, p.batch, s);
         if (p.priors) p.prior();
         HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev_prepped, s)); // the records and pair states every solver reads are there from here on
     }
     p.rp.inl_stat = p.classic ? nullptr : &p.cnt->progress.wish_sum;
 
@@ -1209,7 +1275,10 @@ int run_pass(mdrp_handle *h, const PassIn &in) {
             }
             if (piped && c + 1 < n_chunks && !(c == 0 && solved1)) {
                 // the sampler tables advance in chunk order; chunk c + 1 reuses the lists chunk c - 1 was swept from
-                HIPCHK(hipStreamWaitEvent(p.aux, c == 0 ? h->ev_solved[0] : h->ev_scanned[c - 1], 0));
+                // (the second chunk's solver needs nothing of the first one's: behind k_prep where sched::second_solver_after says so)
+                const bool behind_prep = c == 0 && p.it0 == 0 &&
+                    sched::second_solver_after(p.kind, p.presampled[1], p.host != nullptr, n_chunks, p.solve_behind_prep) == sched::SolveAfter::prep;
+                HIPCHK(hipStreamWaitEvent(p.aux, c > 0 ? h->ev_scanned[c - 1] : (behind_prep ? h->ev_prepped : h->ev_solved[0]), 0));
                 if ((rc = p.solve(p.view(c + 1, 0, p.batch), p.aux))) return rc;
                 HIPCHK(hipEventRecord(h->ev_solved[c + 1], p.aux));
             }
@@ -1267,7 +1336,9 @@ int estimate_device(mdrp_handle *h, const EstimateCall &c) {
     int rc;
     if ((rc = h->results.ensure(sizeof(ResultDev) * std::max(batch, 1)))) return rc;
     if ((rc = h->lm_stats.ensure(LM_STATS_BYTES))) return rc;
-    HIPCHK(hipMemsetAsync(h->lm_stats.p, 0, LM_STATS_BYTES, h->stream));
+    // (device-resident inputs: the first pass clears the statistics with the rest of its front, Pass::clear_front)
+    const bool stats_in_pass = front_clear_on() && batch > 0 && !c.host && !n_per_pair_out_of_range(n_per_pair, batch, n_max);
+    if (!stats_in_pass) HIPCHK(hipMemsetAsync(h->lm_stats.p, 0, LM_STATS_BYTES, h->stream));
     if (batch == 0) return MDRP_OK;
     if (const char *why = n_per_pair_out_of_range(n_per_pair, batch, n_max)) { g_err = why; return MDRP_ERR_INVALID; } // (the plain entry points have no check before this one)
     std::vector<int32_t> n_host(batch);
@@ -1297,7 +1368,9 @@ int estimate_device(mdrp_handle *h, const EstimateCall &c) {
         HostSrc hs{};
         if (c.host) hs = HostSrc{c.host->x1 + o2, c.host->x2 + o2, c.host->d1 ? c.host->d1 + o1 : nullptr, c.host->d2 ? c.host->d2 + o1 : nullptr};
         const BudgetOut bud{budgets, n_budgets, h->bresults.as<ResultDev>() + p0, mask + o1, batch};
-        if ((rc = run_pass(h, pass_in(h, c, p0, nb, n_host.data() + p0, chunk_cap, mask + o1, c.host ? &hs : nullptr, budgets ? &bud : nullptr)))) return rc;
+        PassIn in = pass_in(h, c, p0, nb, n_host.data() + p0, chunk_cap, mask + o1, c.host ? &hs : nullptr, budgets ? &bud : nullptr);
+        in.clear_lm_stats = stats_in_pass && p0 == 0;
+        if ((rc = run_pass(h, in))) return rc;
     }
     if (budgets) {
         HIPCHK(hipMemcpyAsync(h->results.p, h->bresults.as<ResultDev>() + (size_t)(n_budgets - 1) * batch, sizeof(ResultDev) * batch, hipMemcpyDeviceToDevice, h->stream));

@@ -292,6 +292,22 @@ __device__ __forceinline__ void clear_record_fragment(uint4 *__restrict__ frag, 
     g[0] = z; g[16] = z; g[32] = z; g[48] = z;
 }
 
+// ------------------------------------------------------------------------------------------------ clear
+// The small per-call blocks a run's first super-chunk starts from (counters, candidate statistics, both chunk parities' model counts, the fused
+// tail's block, the LM statistics), filled in ONE launch in front of k_prep instead of one memset each in front of the solvers, the scan and the LO
+// (Pass::clear_front, mdrp_capi.hip).  Every block is a whole number of 32-bit words; `value` is the word stored (0, or ~0 for the ready list).
+constexpr int CLEAR_BLOCKS_MAX = 8, CLEAR_THREADS = 256;
+struct ClearList {
+    int n;
+    uint32_t *p[CLEAR_BLOCKS_MAX];
+    uint32_t words[CLEAR_BLOCKS_MAX], value[CLEAR_BLOCKS_MAX];
+};
+MDRP_GLOBAL __launch_bounds__(CLEAR_THREADS) void k_clear(ClearList cl) {
+    const uint32_t step = gridDim.x * CLEAR_THREADS;
+    for (int b = 0; b < cl.n; ++b)
+        for (uint32_t i = blockIdx.x * CLEAR_THREADS + threadIdx.x; i < cl.words[b]; i += step) cl.p[b][i] = cl.value[b];
+}
+
 // ------------------------------------------------------------------------------------------------ prep
 // One workgroup per pair: normalise the correspondences into the pts/dep records and set up the pair state.
 // calibrated: Camera::unproject + thresholds * (1/f1 + 1/f2)/2 (estimate_monodepth_relative_pose @0x2242bf-0x224348)
@@ -1813,11 +1829,12 @@ MDRP_GLOBAL __launch_bounds__(FIRST_THREADS) void k_first_filter(RunParams rp, c
 // local records -> wave exclusive prefix (max count, min score) -> per-lane replay against the true running records.
 // IPL (round 6): with one iteration per lane the 154 steps of a 9872-iteration chunk were 154 dependent memory round trips of one wavefront per
 // SIMD (0.13 ms, on the critical path in front of the LO launch); four iterations per lane keep four times the loads in flight per step.
-template <int MPS = 4, int IPL = 1>
-__global__ __launch_bounds__(64) void k_scan(RunParams rp, PairState *__restrict__ st, const double *__restrict__ slot_score,
-                                             const int32_t *__restrict__ slot_inl, Trigger *__restrict__ triggers,
-                                             int trig_cap, const int32_t *__restrict__ model_count,
-                                             unsigned long long *__restrict__ evals) {
+// (the walk of one pair by its wavefront: k_scan, and k_scan_list for the pairs it does not take from the sweep's lists)
+template <int MPS, int IPL>
+__device__ __forceinline__ void scan_walk(const RunParams &rp, PairState *__restrict__ st, const double *__restrict__ slot_score,
+                                          const int32_t *__restrict__ slot_inl, Trigger *__restrict__ triggers,
+                                          int trig_cap, const int32_t *__restrict__ model_count,
+                                          unsigned long long *__restrict__ evals) {
     const int pair = blockIdx.x, lane = threadIdx.x;
     PairState &ps = st[pair];
     if (!ps.active) { if (lane == 0) ps.n_triggers = 0; return; }
@@ -1928,6 +1945,160 @@ __global__ __launch_bounds__(64) void k_scan(RunParams rp, PairState *__restrict
     if (lane == 0) {
         ps.best_min_cnt = (uint64_t)(run_cnt < 0 ? 0 : run_cnt);
         ps.best_min_score = run_score;
+        ps.n_triggers = min(ntrig, trig_cap);
+    }
+}
+template <int MPS = 4, int IPL = 1>
+__global__ __launch_bounds__(64) void k_scan(RunParams rp, PairState *__restrict__ st, const double *__restrict__ slot_score,
+                                             const int32_t *__restrict__ slot_inl, Trigger *__restrict__ triggers,
+                                             int trig_cap, const int32_t *__restrict__ model_count,
+                                             unsigned long long *__restrict__ evals) {
+    scan_walk<MPS, IPL>(rp, st, slot_score, slot_inl, triggers, trig_cap, model_count, evals);
+}
+
+// The scan of a chunk that was swept against a bar (every chunk but a run's first).  There all but a few hundred slots of a pair hold k_solve's -2,
+// and the walk above spends its time skipping them, one dependent round trip per 64 * IPL iterations (0.10 ms for 9744 iterations, in front of the
+// LO launch).  The slots that hold anything else are those the exact sweep wrote, and it wrote exactly the slots on the pair's sorted tag list
+// (k_sort_tags: model_count[2p] sparse ones from the front, model_count[2p + 1] dense ones from the back).  One workgroup per pair reads that list
+// twice, SCAN_LIST_THREADS entries per trip, in whatever order it is in:
+//   pass 1  the CANDIDATES — slots with a count that beat a record the pair had when the chunk began, the only ones that can be a trigger or move a
+//           running record, since the running records never fall behind those — leave (max count, min score) in one of 64 bins by iteration (LDS
+//           atomics; slot = iteration * MPS + k is the sequential order), and one wavefront turns the bins into exclusive prefixes joined with the
+//           chunk-start records: the sequential loop's running records at the start of each bin;
+//   pass 2  a candidate that does not beat its bin's prefix changes nothing in the sequential loop (its running records are at least the prefix);
+//           the few that do — every real improvement, and what only beats an earlier candidate of its own bin — go on an LDS list.
+// That list is ordered by slot index and replayed like the walk replays a lane's iterations: the running records over it are the true ones (the
+// first slot to reach each new record is on it).  Same triggers in the same order, same records, same trigger count.
+// The pair is walked in full instead (scan_walk by the first wavefront: same result, found the slow way) where
+//  - the list would be longer than `list_cap` (at most SCAN_LIST_MAX; MDRP_SCAN_LIST_CAP lowers it for the tests),
+//  - the sweep's lists are longer than SCAN_LIST_WALK entries (a pair whose first chunk left a poor bar: two passes cost more than the walk), or
+//  - its score record does not yet reach N * thr, the score of k_solve's NaN models (slot state -3, on no list): only then can one be a trigger.
+constexpr int SCAN_LIST_MAX = 64, SCAN_LIST_THREADS = 256, SCAN_LIST_WALK = 8 * SCAN_LIST_THREADS;
+template <int MPS = 4, int IPL = 1>
+__global__ __launch_bounds__(SCAN_LIST_THREADS) void k_scan_list(RunParams rp, PairState *__restrict__ st, const double *__restrict__ slot_score,
+                                                                 const int32_t *__restrict__ slot_inl, Trigger *__restrict__ triggers,
+                                                                 int trig_cap, const int32_t *__restrict__ model_count,
+                                                                 const uint32_t *__restrict__ tags_sorted, int list_cap,
+                                                                 unsigned long long *__restrict__ evals) {
+    __shared__ uint32_t s_slot[SCAN_LIST_MAX];
+    __shared__ int s_cnt[SCAN_LIST_MAX], b_cnt[64], s_n;
+    __shared__ double s_score[SCAN_LIST_MAX];
+    __shared__ unsigned long long b_score[64]; // bit patterns of scores >= +0: ordered like the scores
+    const int pair = blockIdx.x, lane = threadIdx.x; // (`lane`: the thread of the workgroup)
+    PairState &ps = st[pair];
+    bool walk = !ps.active; // (the walk's own way out)
+    long long run_cnt = 0;
+    double run_score = 0;
+    int n_sparse = 0, total = 0;
+    if (!walk) {
+        run_cnt = (long long)ps.best_min_cnt;
+        run_score = ps.best_min_score;
+        n_sparse = model_count[2 * pair]; total = n_sparse + model_count[2 * pair + 1];
+        walk = !(run_score <= (double)ps.n * ps.sq_thr) || total > SCAN_LIST_WALK;
+    }
+    int m = 0;
+    if (!walk) {
+        const size_t row = (size_t)pair * rp.slot_stride;
+        const int bin_its = (rp.chunk_len + 63) / 64; // iterations per bin
+        if (lane < 64) { b_cnt[lane] = -1; b_score[lane] = (unsigned long long)__double_as_longlong(DBL_MAX); }
+        if (lane == 0) s_n = 0;
+        __syncthreads();
+        // one entry of the list: its slot, count and score, whether it is a candidate, and its bin
+        struct Entry { uint32_t slot; int c, bin; double s; bool cand; };
+        auto entry = [&](int i) {
+            Entry e{0, -1, 0, DBL_MAX, false};
+            if (i < total) {
+                e.slot = tags_sorted[row + (i < n_sparse ? i : rp.slot_stride - 1 - (i - n_sparse))];
+                e.c = slot_inl[row + e.slot];
+                if (e.c >= 0) { e.s = slot_score[row + e.slot]; e.cand = (long long)e.c > run_cnt || e.s < run_score; }
+                e.bin = min(max(((int)(e.slot / MPS) - rp.chunk_off) / bin_its, 0), 63);
+            }
+            return e;
+        };
+        for (int i0 = 0; i0 < total; i0 += SCAN_LIST_THREADS) {
+            const Entry e = entry(i0 + lane);
+            if (e.cand) {
+                atomicMax(&b_cnt[e.bin], e.c);
+                if (e.s < run_score) atomicMin(&b_score[e.bin], (unsigned long long)__double_as_longlong(e.s));
+            }
+        }
+        __syncthreads();
+        if (lane < 64) { // the bins' exclusive prefixes, joined with the chunk-start records
+            long long pc = b_cnt[lane];
+            double psn = __longlong_as_double((long long)b_score[lane]);
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const long long vc = __shfl_up(pc, o, 64);
+                const double vs = __shfl_up(psn, o, 64);
+                if (lane >= o) { pc = max(pc, vc); psn = fmin(psn, vs); }
+            }
+            long long ec = __shfl_up(pc, 1, 64);
+            double es = __shfl_up(psn, 1, 64);
+            if (lane == 0) { ec = -1; es = DBL_MAX; }
+            b_cnt[lane] = (int)max(run_cnt, ec); // (a count: fits, and run_cnt is at most the pair's N)
+            b_score[lane] = (unsigned long long)__double_as_longlong(fmin(run_score, es));
+        }
+        __syncthreads();
+        list_cap = min(list_cap, SCAN_LIST_MAX);
+        for (int i0 = 0; i0 < total; i0 += SCAN_LIST_THREADS) {
+            const Entry e = entry(i0 + lane);
+            if (e.cand && (e.c > b_cnt[e.bin] || e.s < __longlong_as_double((long long)b_score[e.bin]))) {
+                const int at = atomicAdd(&s_n, 1);
+                if (at < list_cap) { s_slot[at] = e.slot; s_cnt[at] = e.c; s_score[at] = e.s; }
+            }
+        }
+        __syncthreads();
+        m = s_n;
+        walk = m > list_cap;
+    }
+    if (walk) {
+        if (lane < 64) scan_walk<MPS, IPL>(rp, st, slot_score, slot_inl, triggers, trig_cap, model_count, evals);
+        return;
+    }
+    if (lane == 0 && evals) atomicAdd(evals, (unsigned long long)(model_count[2 * pair] + model_count[2 * pair + 1]) * (unsigned long long)ps.n);
+    // by slot index: rank by counting (slots are distinct)
+    __syncthreads();
+    uint32_t my_slot = 0;
+    int my_cnt = 0, rank = 0;
+    double my_score = 0;
+    if (lane < m) {
+        my_slot = s_slot[lane]; my_cnt = s_cnt[lane]; my_score = s_score[lane];
+        for (int j = 0; j < m; ++j) rank += s_slot[j] < my_slot;
+    }
+    __syncthreads();
+    if (lane < m) { s_slot[rank] = my_slot; s_cnt[rank] = my_cnt; s_score[rank] = my_score; }
+    __syncthreads();
+    if (lane >= 64) return;
+    // the replay, iteration by iteration and model by model against the running records (every lane the same; lane 0 writes)
+    int ntrig = rp.chunk_off > 0 ? ps.n_triggers : 0; // later chunks of a super-chunk append to its trigger list
+    long long bc = run_cnt;
+    double bs = run_score;
+    for (int i = 0; i < m;) {
+        const uint32_t iter = s_slot[i] / MPS;
+        int k_ref = -1, k_min = -1, cnt_min = 0, cnt_ref = 0;
+        double score_min = 0;
+        for (; i < m && s_slot[i] / MPS == iter; ++i) {
+            const int k = (int)(s_slot[i] % MPS), c = s_cnt[i];
+            const double s = s_score[i];
+            const bool more = (long long)c > bc, better = s < bs;
+            if (more || better) {
+                if (more) bc = c;
+                if (better) { bs = s; k_min = k; score_min = s; cnt_min = c; }
+                k_ref = k; cnt_ref = c;
+            }
+        }
+        if (k_ref >= 0) {
+            if (ntrig < trig_cap && lane == 0) {
+                Trigger &tr = triggers[(size_t)pair * trig_cap + ntrig];
+                tr.iter = iter; tr.k_ref = k_ref; tr.k_min = k_min; tr.cnt_min = cnt_min; tr.score_min = score_min;
+                tr.ref_score = DBL_MAX; tr.ref_cnt = 0; tr.cnt_ref = cnt_ref;
+            }
+            ++ntrig;
+        }
+    }
+    if (lane == 0) {
+        ps.best_min_cnt = (uint64_t)bc;
+        ps.best_min_score = bs;
         ps.n_triggers = min(ntrig, trig_cap);
     }
 }

@@ -182,6 +182,22 @@ inline size_t solver_reservation(size_t lds_per_cu, int resident_per_simd, size_
 }
 constexpr int SOLVE_RESIDENT = 2; // R of the 3-point calibrated solvers where the first chunk's prefix retirement is on
 
+// What the solver of a run's SECOND chunk (the long one, on the solver stream) waits for.  It reads the records and pair states k_prep (and a
+// prior's kernel) leave and its own sample table, and writes the models, tags and model counts of its own chunk parity (the 5-point solver: its own
+// Reduce5 region): nothing the first chunk's solver touches.  So it starts behind k_prep, beside the first chunk's solver (which is issued first and
+// takes the head of the dispatch order), where
+//  - the pass has device-resident inputs (the sliced host-buffer front issues that solver slice by slice itself),
+//  - the second chunk's sample table was drawn ahead on the LO stream (otherwise the sampler advances the tables in chunk order on the solver's stream),
+//  - the estimator is not the 6-point one: its solver takes 11.5 KB of scratch per lane, and two of its dispatches on two queues at once need two
+//    whole-device scratch areas (Pass::first_chunk_of, mdrp_capi.hip).
+// Otherwise, and with MDRP_SOLVE_BEHIND_PREP=0 (`knob`; negative: not set), it waits for the first chunk's solver as it always did.  The third and later
+// chunks wait for the scan of the chunk whose lists they reuse whatever this says.
+enum class SolveAfter { prep, first_solver };
+inline SolveAfter second_solver_after(int kind, bool presampled, bool host_buffers, int n_chunks, int knob) {
+    if (knob == 0 || host_buffers || !presampled || n_chunks < 2 || kind == MDRP_SHARED_6PT) return SolveAfter::first_solver;
+    return SolveAfter::prep;
+}
+
 // Bounded waits of the fused tail (k_gate, k_final), microseconds: far beyond anything a healthy run needs (the LO queue of 1024 pairs is empty
 // after ~1 ms), scaled with the problem size (one LO problem is ~0.4 ms at N = 2000 and grows linearly with N: 4 ms at 5000 on one wavefront) and
 // capped at 200 ms / 100 ms: under persistently serialised dispatch (rocprofv3 --pmc, AMD_SERIALIZE_KERNEL, a debugger) every re-try of the
