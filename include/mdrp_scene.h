@@ -88,4 +88,6 @@ int mdrp_reconstruct_scene_async(mdrp_handle *h, int kind, const mdrp_depth_imag
 #ifdef __cplusplus
 }
 #endif
+
+#include "mdrp_covis.h" /* co-visibility: dense depth-consistency counts per pair; it builds on the descriptors and rules of mdrp_reconstruct.h */
 #endif

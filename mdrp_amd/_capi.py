@@ -130,6 +130,16 @@ assert C.sizeof(SceneTransform) == 128
 SCENE_ABSENT, SCENE_EDGE, SCENE_ROOT = 0, 1, 2  # include/mdrp_scene.h MDRP_SCENE_*: tree[i][1]
 
 
+class CovisOpt(C.Structure):
+    """mdrp_covis_opt (include/mdrp_covis.h): the subsample (R3's threshold and seed) and the band lo * zt .. hi * zt a consistent depth lies in"""
+    _fields_ = [("thr", C.c_uint32), ("reserved_", C.c_int32), ("seed", C.c_uint64), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+assert C.sizeof(CovisOpt) == 32
+COVIS_SLOTS = 8  # include/mdrp_covis.h MDRP_COVIS_SLOTS: counters per direction
+COVIS_CLASSES = ("sampled", "front", "inside", "known", "consistent", "occluded", "violating")  # MDRP_COVIS_*: the slot of each class
+
+
 class Result(C.Structure):
     _fields_ = [("model", Model), ("refinements", C.c_uint64), ("iterations", C.c_uint64), ("num_inliers", C.c_uint64),
                 ("inlier_ratio", C.c_double), ("model_score", C.c_double)]
@@ -297,6 +307,10 @@ PROTOTYPES = {
         "mdrp_scene_transforms_async": [_p, _i, _i, _p, _i, _p, _i, _p, _p],
         "mdrp_reconstruct_scene_async": [_p, _i, C.POINTER(DepthImagePairs), C.POINTER(ReconstructOpt), _i, _p, _i, _p, _p, _p, _p, _p, _p],
     },
+    "mdrp_covis.h": {  # co-visibility: dense depth-consistency counts per pair
+        "mdrp_covisibility_pairs_async": [_p, _i, C.POINTER(DepthPairs), C.POINTER(CovisOpt), _i, _p, _i, _p, _p, _p],
+        "mdrp_covisibility_image_pairs_async": [_p, _i, C.POINTER(DepthImagePairs), C.POINTER(CovisOpt), _i, _p, _i, _p, _p, _p],
+    },
 }
 # what each header declares: mdrp.h's own list (with the four symbols that only get a restype), then its extension headers'
 EXPORTS = tuple(PROTOTYPES["mdrp.h"]) + ("mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version")
@@ -307,6 +321,7 @@ EXPORTS_CLASSIC_FOCALS = tuple(PROTOTYPES["mdrp_classic_focals.h"])
 EXPORTS_DENSE = tuple(PROTOTYPES["mdrp_dense.h"])
 EXPORTS_RECONSTRUCT = tuple(PROTOTYPES["mdrp_reconstruct.h"])
 EXPORTS_SCENE = tuple(PROTOTYPES["mdrp_scene.h"])
+EXPORTS_COVIS = tuple(PROTOTYPES["mdrp_covis.h"])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -607,7 +622,25 @@ class _SceneCalls:
                                                                          _dev(points_ptr), _dev(pixel_ptr), _dev(offsets_ptr)))
 
 
-class Handle(_ReconstructCalls, _SceneCalls):
+class _CovisCalls:
+    """The two calls of include/mdrp_covis.h, methods of Handle through this base.  Arguments go to the library as they are: the library checks them."""
+
+    def covisibility_pairs_device(self, kind, desc, opt, batch, models_ptr, model_stride, counts_ptr, cam1=None, cam2=None):
+        """the depth-consistency counts of a batch of pairs on the handle's stream into the caller's device buffer, counts [batch][2][8] int32.
+        desc: a DepthPairs or a DepthImagePairs; opt: a CovisOpt; models_ptr, cam1 / cam2 as reconstruct_pairs_device.  Nothing synchronises."""
+        stem = "image_pairs" if isinstance(desc, DepthImagePairs) else "pairs"
+        _, c1, c2 = _tables(None, cam1, cam2)
+        _check(self._lib, _fn(self._lib, f"mdrp_covisibility_{stem}_async")(self._h, int(kind), C.byref(desc), C.byref(opt), int(batch), _dev(models_ptr),
+                                                                           int(model_stride), _ptr(c1), _ptr(c2), _dev(counts_ptr)))
+
+    def covisibility_image_pairs_device(self, kind, desc, opt, batch, models_ptr, model_stride, counts_ptr, cam1=None, cam2=None):
+        """covisibility_pairs_device for a DepthImagePairs descriptor"""
+        if not isinstance(desc, DepthImagePairs):
+            raise ValueError("covisibility_image_pairs_device takes a DepthImagePairs descriptor")
+        self.covisibility_pairs_device(kind, desc, opt, batch, models_ptr, model_stride, counts_ptr, cam1, cam2)
+
+
+class Handle(_ReconstructCalls, _SceneCalls, _CovisCalls):
     """One handle = one HIP device + one stream + its scratch buffers.  Calls on one handle are serialised inside the
     library; use one handle per host thread for concurrency (default_handle() does).
 

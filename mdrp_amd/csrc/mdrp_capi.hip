@@ -14,6 +14,7 @@
 #include "mdrp_dense.h"
 #include "mdrp_reconstruct.h"
 #include "mdrp_scene.h"
+#include "mdrp_covis.h"
 // MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior, kc_from_model, kc_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -210,6 +211,7 @@ struct mdrp_handle {
     DevBuf fp_nper, fp_in, fp_out;     // focals and pose from F (include/mdrp_classic_focals.h): n per pair | a host call's models, mask and principal points | its records
     DevBuf dn_scratch, dn_score;       // dense front end (include/mdrp_dense.h): the sampler's scratch, carved per call (DenseScratch) | mdrp_estimate_dense_async: the records' certainties
     DevBuf rc_scratch;                 // back end (include/mdrp_reconstruct.h): tile counts | the pairs' ReconPair | the two camera tables, carved per call
+    DevBuf cv_scratch;                 // co-visibility (include/mdrp_covis.h): the pairs' CovisPair | the two camera tables, carved per call
     DevBuf sc_scratch;                 // scenes (include/mdrp_scene.h): the images' records (where the caller takes none) | their SceneImage | the camera table | tile counts, carved per call
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
     Pinned<Progress> progress_host;
@@ -3104,6 +3106,81 @@ int mdrp_reconstruct_scene_async(mdrp_handle *h, int kind, const mdrp_depth_imag
                            (const SceneImage *)im, (const int64_t *)offsets, points, pixel);
     HIPCHK(hipGetLastError());
     return MDRP_OK;
+}
+
+} // extern "C"
+
+// ---- co-visibility: dense depth-consistency counts per pair (include/mdrp_covis.h; mdrp_covis.h)
+namespace {
+
+static_assert(MDRP_COVIS_SAMPLED == COVIS_SAMPLED && MDRP_COVIS_FRONT == COVIS_FRONT && MDRP_COVIS_INSIDE == COVIS_INSIDE && MDRP_COVIS_KNOWN == COVIS_KNOWN &&
+              MDRP_COVIS_CONSISTENT == COVIS_CONSISTENT && MDRP_COVIS_OCCLUDED == COVIS_OCCLUDED && MDRP_COVIS_VIOLATING == COVIS_VIOLATING &&
+              MDRP_COVIS_SLOTS == COVIS_SLOTS, "values of the header and of the kernels");
+static_assert(sizeof(mdrp_covis_opt) == 32 && offsetof(mdrp_covis_opt, seed) == 8 && offsetof(mdrp_covis_opt, lo) == 16 && offsetof(mdrp_covis_opt, hi) == 24, "option layout");
+
+// Both entry points behind their descriptors: the back end's refusals (a cloud of no rows), the tolerance's, then the two kernels on the handle's
+// stream.  The scratch is one buffer of the handle, carved for this call's sizes; every word of it that a kernel reads was written by this call.
+int covis_call(mdrp_handle *h, ReconCall &c, const mdrp_covis_opt *o) {
+    const mdrp_reconstruct_opt ro{MDRP_KEEP_FINITE, o->thr, o->seed, 0, 0};
+    const char *why = recon_refusal(c, &ro);
+    if (!why && !(std::isfinite(o->lo) && std::isfinite(o->hi) && o->lo >= 0.0 && o->lo <= 1.0 && o->hi >= 1.0)) why = "lo and hi must be finite with 0 <= lo <= 1 <= hi";
+    ReconArgs &a = c.a;
+    a.keep = RECON_KEEP_FINITE; a.thr = o->thr; a.seed = (uint32_t)o->seed; a.p_max = 0; a.nfill = 0;
+    const auto tiles = [](int hh, int ww) { return (int)std::max<int64_t>(1, ((int64_t)hh * ww + RECON_TILE - 1) / RECON_TILE); }; // (a map without pixels: one empty tile)
+    const size_t b = (size_t)std::max(c.batch, 0);
+    size_t nt = 0;
+    if (!why) {
+        a.nt1 = tiles(a.h1, a.w1); a.nt2 = tiles(a.h2, a.w2);
+        nt = (size_t)a.nt1 + a.nt2;
+        if (b * nt > (size_t)INT32_MAX) why = "batch * tiles above 2^31 - 1: split the batch";
+    }
+    if (why) { g_err = std::string(c.who) + ": " + why; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    if (c.batch == 0) return MDRP_OK;
+    size_t total = 0;
+    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
+    const size_t o_pair = carve(sizeof(CovisPair) * b), o_cam = carve(a.kind == MDRP_CALIB ? sizeof(ReconCam) * 2 * b : 0);
+    if (int rc = h->cv_scratch.ensure(total)) return rc;
+    unsigned char *p = h->cv_scratch.as<unsigned char>();
+    hipStream_t s = h->stream;
+    if (a.kind == MDRP_CALIB) { // pageable: the copies have left the caller's tables when hipMemcpyAsync returns
+        HIPCHK(hipMemcpyAsync(p + o_cam, c.cam1, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(p + o_cam + sizeof(ReconCam) * b, c.cam2, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
+        a.cam1 = reinterpret_cast<const ReconCam *>(p + o_cam); a.cam2 = a.cam1 + b;
+    }
+    CovisPair *cp = reinterpret_cast<CovisPair *>(p + o_pair);
+    hipLaunchKernelGGL(k_covis_pair, dim3((unsigned)((b + COVIS_PAIR_THREADS - 1) / COVIS_PAIR_THREADS)), dim3(COVIS_PAIR_THREADS), 0, s, a, c.batch, cp, c.counts);
+    hipLaunchKernelGGL(k_covis_count, dim3((unsigned)(b * nt)), dim3(RECON_THREADS), 0, s, a, (const CovisPair *)cp, o->lo, o->hi, c.counts);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int mdrp_covisibility_pairs_async(mdrp_handle *h, int kind, const mdrp_depth_pairs *dp, const mdrp_covis_opt *opt, int batch, const void *models_dev,
+                                  int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, int32_t *counts) {
+    if (!h || !dp || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    ReconCall c{"mdrp_covisibility_pairs_async", {}, batch, cam1, cam2, nullptr, nullptr, counts};
+    ReconArgs &a = c.a;
+    a.depth1 = dp->depth1; a.depth2 = dp->depth2; a.center1 = dp->center1; a.center2 = dp->center2;
+    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = dp->depth_type; a.kind = kind;
+    a.h1 = dp->h1; a.w1 = dp->w1; a.h2 = dp->h2; a.w2 = dp->w2;
+    return covis_call(h, c, opt);
+}
+
+int mdrp_covisibility_image_pairs_async(mdrp_handle *h, int kind, const mdrp_depth_image_pairs *ip, const mdrp_covis_opt *opt, int batch,
+                                        const void *models_dev, int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, int32_t *counts) {
+    if (!h || !ip || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    if (batch > 0 && !ip->pairs) { g_err = "mdrp_covisibility_image_pairs_async: NULL pairs"; return MDRP_ERR_INVALID; }
+    ReconCall c{"mdrp_covisibility_image_pairs_async", {}, batch, cam1, cam2, nullptr, nullptr, counts};
+    ReconArgs &a = c.a;
+    a.depth1 = a.depth2 = ip->n_images > 0 ? ip->depth : ip; // (an empty set: no map is read; the pointer only has to pass for one)
+    a.center1 = a.center2 = ip->center; a.size = ip->size; a.pairs = ip->pairs; a.n_images = ip->n_images;
+    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = ip->depth_type; a.kind = kind;
+    a.h1 = a.h2 = ip->h_max; a.w1 = a.w2 = ip->w_max;
+    return covis_call(h, c, opt);
 }
 
 } // extern "C"

@@ -45,6 +45,11 @@ filter, the unprojection and the transform in float64 with one rounding per arit
 (include/mdrp_scene.h).  `scene_transforms_numpy` and `reconstruct_scene_numpy` at the end of this module are their definition, rules
 S1-S6 of the header: the tree and its detached images, the accumulation leaf upward in float64 without a fused multiply-add, R3-R5 on a stage of
 their own with the image mixed into the seed, the rows in image order and the int64 offsets.
+
+`poselib.covisibility_pairs_torch` / `covisibility_image_pairs_torch` judge a pair by its depth maps (include/mdrp_covis.h): 16 integer
+counts per pair.  `covisibility_pair_numpy` and `covisibility_image_pairs_numpy` at the end of this module are their definition, rules C1-C7 of the
+header: R3's subsample on two stages of its own, the point carried into the other camera's frame, the nearest target pixel, the three-way comparison
+of depths, all in float64 with one rounding per arithmetic sign.
 """
 import numpy as np
 
@@ -796,3 +801,144 @@ def reconstruct_scene_numpy(models, kind, depth_maps, pairs, tree, p_max=None, c
     I = np.shape(depth_maps)[0]
     T = scene_transforms_numpy(models, kind, pairs, tree, I)
     return (*pack_scene_rows(scene_rows_numpy(T, kind, depth_maps, centers, sizes, cameras, keep, thr, seed), p_max), T)
+
+
+# ---- co-visibility (include/mdrp_covis.h): how far a pair's two depth maps agree under its model.  Rules C1-C7 of the header.  A sampled
+# pixel of the source image is unprojected (R5), carried into the target camera's frame, projected to the nearest pixel of the target map, and its
+# depth there is compared with the target's own.  Every count is an integer and every quantity that decides one is a fixed sequence of float64
+# operations, one rounding per arithmetic sign: the device result equals this statement as bytes.
+COVIS_STAGES = (6, 7)  # C3: R3's stage of direction 0 | direction 1 (1 and 2: the dense sampler's, 3 and 4: the two-view cloud's, 5: the scene's)
+COVIS_SLOTS = 8
+COVIS_CLASSES = ("sampled", "front", "inside", "known", "consistent", "occluded", "violating")  # C7: the slot of each class, and its bit in a class mask
+
+
+def covis_band(tol):
+    """(lo, hi) = (1.0 - tol, 1.0 + tol) of C6, computed once here so that the device never derives them; 0 <= tol <= 1"""
+    tol = float(tol)
+    if not 0.0 <= tol <= 1.0:
+        raise ValueError(f"tol must be in [0, 1], not {tol!r}")
+    return 1.0 - tol, 1.0 + tol
+
+
+def _covis_check_band(lo, hi):
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo <= 1.0 <= hi):
+        raise ValueError(f"lo and hi must be finite with 0 <= lo <= 1 <= hi, not {lo!r}, {hi!r}")
+    return np.float64(lo), np.float64(hi)
+
+
+def _covis_focals(m, kind, side, camera):
+    """(fx, fy) a point is projected with into image `side` (C5): the camera's for the calibrated kind, the model's focal otherwise"""
+    if kind != "calibrated":
+        f = np.float64(m["f2"] if side else m["f1"])
+        return f, f
+    mid, p = int(camera["model_id"]), np.asarray(camera["params"], dtype=np.float64)
+    return (p[0], p[1]) if mid == 1 else (p[0], p[0])
+
+
+def covisibility_direction_numpy(model, kind, direction, depth_src, depth_tgt, center_src=None, center_tgt=None, camera_src=None, camera_tgt=None,
+                                 thr=RECON_ALL, seed=0, lo=0.95, hi=1.05):
+    """C3-C6 for one direction of one pair whose model is usable: (v (n,), u (n,) int64: the SAMPLED source pixels in row-major order; classes (n,)
+    uint8: bit k set iff the pixel is in class COVIS_CLASSES[k]; vt, ut (n,) int64: the target pixel of an INSIDE one, 0 elsewhere).  direction 0:
+    the source is image 1 and the target image 2; direction 1 the other way round."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    lo, hi = _covis_check_band(lo, hi)
+    src, tgt = _table(depth_src, "depth maps"), _table(depth_tgt, "depth maps")
+    if src.ndim != 2 or tgt.ndim != 2:
+        raise ValueError("expected depth maps (H, W)")
+    s, t = int(direction), 1 - int(direction)
+    m = np.asarray(model).reshape(())
+    (h, w), (ht, wt) = src.shape, tgt.shape
+    shift_s, shift_t = (np.float64(m["shift2"]), np.float64(m["shift1"])) if s else (np.float64(m["shift1"]), np.float64(m["shift2"]))
+    with np.errstate(all="ignore"):
+        d_all = src.astype(np.float64)
+        sampled = recon_candidates(h, w, thr, seed, COVIS_STAGES[s]) & np.isfinite(d_all) & (d_all + shift_s > 0.0)  # C3
+        v, u = np.nonzero(sampled)
+        d = d_all[v, u]
+        cs = np.zeros(2) if center_src is None else np.asarray(center_src, dtype=np.float64).reshape(2)
+        ct = np.zeros(2) if center_tgt is None else np.asarray(center_tgt, dtype=np.float64).reshape(2)
+        rx, ry, cx, cy = _recon_intrinsics(m, kind, s, camera_src)
+        X = _recon_unproject(v, u, d, cs, rx, ry, cx, cy, shift_s)
+        R, tr, scale = _quat_rows(m["q"]), np.asarray(m["t"], dtype=np.float64), np.float64(m["scale"])
+        if s == 0:                                                                            # C4: R6
+            inv = np.float64(1.0) / scale
+            P = [inv * (((R[r, 0] * X[:, 0] + R[r, 1] * X[:, 1]) + R[r, 2] * X[:, 2]) + tr[r]) for r in range(3)]
+        else:                                                                                 # C4: the inverse, sums left to right
+            Y = [scale * X[:, r] - tr[r] for r in range(3)]
+            P = [(R[0, r] * Y[0] + R[1, r] * Y[1]) + R[2, r] * Y[2] for r in range(3)]
+        front = np.isfinite(P[2]) & (P[2] > 0.0)
+        _, _, ox, oy = _recon_intrinsics(m, kind, t, camera_tgt)                              # C5
+        fx, fy = _covis_focals(m, kind, t, camera_tgt)
+        xo, yo = P[0] / P[2], P[1] / P[2]
+        px, py = (xo * fx + ox) + ct[0], (yo * fy + oy) + ct[1]
+        a, b = px + 0.5, py + 0.5
+        inside = front & (a >= 0.0) & (a < np.float64(wt)) & (b >= 0.0) & (b < np.float64(ht))
+        ut, vt = np.where(inside, a, 0.0).astype(np.int64), np.where(inside, b, 0.0).astype(np.int64)  # truncation
+        dt = np.zeros(len(v))
+        dt[inside] = tgt[vt[inside], ut[inside]].astype(np.float64)                           # C6: one read, of an INSIDE pixel alone
+        zt = dt + shift_t
+        known = inside & np.isfinite(dt) & (zt > 0.0)
+        l, hgh = lo * zt, hi * zt
+        consistent, occluded, violating = known & (P[2] >= l) & (P[2] <= hgh), known & (P[2] > hgh), known & (P[2] < l)
+    classes = np.zeros(len(v), dtype=np.uint8)
+    for k, member in enumerate((np.ones(len(v), dtype=bool), front, inside, known, consistent, occluded, violating)):
+        classes |= (member.astype(np.uint8) << np.uint8(k))
+    return v.astype(np.int64), u.astype(np.int64), classes, vt, ut
+
+
+def covis_counts(classes):
+    """C7: the (8,) int32 counters of one direction from its pixels' class masks"""
+    classes = np.asarray(classes, dtype=np.uint8)
+    return np.array([int(((classes >> k) & 1).sum()) for k in range(len(COVIS_CLASSES))] + [0], dtype=np.int32)
+
+
+def covisibility_pair_numpy(model, kind, depth_map1, depth_map2, center1=None, center2=None, camera1=None, camera2=None, thr=RECON_ALL, seed=0,
+                            lo=0.95, hi=1.05):
+    """One pair: model (a MODEL_DTYPE scalar), depth maps (h, w) float32 / float64, centres (2,) or None, cameras (calibrated kind) as records or
+    dicts with model_id and params; thr, seed: R3's; lo, hi: C6's band (covis_band(tol)).  Returns counts (2, 8) int32 by C1-C7: per direction
+    sampled, front, inside, known, consistent, occluded, violating, 0; all zero where the model is not usable.  This function is the definition."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    _covis_check_band(lo, hi)
+    m = np.asarray(model).reshape(())
+    counts = np.zeros((2, COVIS_SLOTS), dtype=np.int32)
+    if not recon_usable(m, kind):                                                             # C1
+        return counts
+    if kind == "calibrated" and (camera1 is None or camera2 is None):
+        raise ValueError("the calibrated kind needs both cameras")
+    sides = ((depth_map1, center1, camera1), (depth_map2, center2, camera2))
+    for direction in range(2):                                                                # C2
+        (ds, cs, ks), (dt, ct, kt) = sides[direction], sides[1 - direction]
+        counts[direction] = covis_counts(covisibility_direction_numpy(m, kind, direction, ds, dt, cs, ct, ks, kt, thr, seed, lo, hi)[2])
+    return counts
+
+
+def covisibility_image_pairs_numpy(models, kind, depth_maps, pairs, centers=None, sizes=None, cameras1=None, cameras2=None, thr=RECON_ALL, seed=0,
+                                   lo=0.95, hi=1.05):
+    """models (B,) MODEL_DTYPE, depth_maps (I, H, W) float32 / float64, pairs (B, 2) image indices (a, c); sizes (I, 2) (h, w) clamped to the
+    allocation, None = all of it; centers (I, 2) or (2,); cameras1 / cameras2: one per PAIR (calibrated kind).  Pair b is covisibility_pair_numpy on
+    the two images' valid regions; a pair with an index outside [0, I) has all counters zero.  Returns counts (B, 2, 8) int32."""
+    dm = _table(depth_maps, "depth maps")
+    if dm.ndim != 3:
+        raise ValueError("expected depth maps (I, H, W)")
+    I, H, W = dm.shape
+    pairs = np.asarray(pairs).astype(np.int32).reshape(-1, 2)
+    models = np.asarray(models).reshape(-1)
+    if len(models) != len(pairs):
+        raise ValueError("one model per pair")
+    hw = np.tile(np.array([H, W], dtype=np.int64), (I, 1)) if sizes is None else np.asarray(sizes).reshape(I, 2)
+    hs, ws = clamp_extent(hw[:, 0], H), clamp_extent(hw[:, 1], W)
+    cs = None if centers is None else np.asarray(centers, dtype=np.float64)
+    if cs is not None and cs.size == 2:
+        cs = np.tile(cs.reshape(1, 2), (I, 1))
+    if cs is not None and cs.shape != (I, 2):
+        raise ValueError("centers must have shape (I, 2) or (2,)")
+    counts = np.zeros((len(pairs), 2, COVIS_SLOTS), dtype=np.int32)
+    for b, (a, c) in enumerate(pairs):
+        if not (image_valid(a, I) and image_valid(c, I)):
+            continue
+        counts[b] = covisibility_pair_numpy(models[b], kind, dm[a][:hs[a], :ws[a]], dm[c][:hs[c], :ws[c]], None if cs is None else cs[a],
+                                            None if cs is None else cs[c], None if cameras1 is None else cameras1[b],
+                                            None if cameras2 is None else cameras2[b], thr, seed, lo, hi)
+    return counts

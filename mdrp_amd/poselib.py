@@ -2010,3 +2010,8 @@ from .reconstruct import reconstruct_image_pairs_torch, reconstruct_pair, recons
 # ---- scenes (include/mdrp_scene.h): an image set's pairs chained along a tree, one fused cloud per scene.  mdrp_amd/scene.py holds the
 # entry points; they are found here, beside the estimators whose records they take.
 from .scene import reconstruct_scene, reconstruct_scene_torch, scene_transforms_torch, scene_tree, video_tree  # noqa: E402, F401
+
+
+# ---- co-visibility (include/mdrp_covis.h): dense depth-consistency counts per pair.  mdrp_amd/covis.py holds the entry points; they are
+# found here, beside the estimators whose records they take.
+from .covis import covisibility_image_pairs_torch, covisibility_pair, covisibility_pairs_torch, covisibility_scores  # noqa: E402, F401

@@ -31,7 +31,9 @@ def video_tree(n):
 
 def scene_tree(pairs, weights, n_images, roots=None):
     """The maximum-weight spanning forest of the images under the pairs, as a `tree` array (n_images, 2) int32 of (pair, role).  Runs on the HOST, in
-    NumPy and plain Python (choosing the tree on the device is out of scope): fetch the weights - num_inliers of the records, say - first.
+    NumPy and plain Python (choosing the tree on the device is out of scope): fetch the weights first - num_inliers of the records, say, or better
+    covisibility_scores(covisibility_image_pairs_torch(...))["weight"], the number of pixels on which the pair's two depth maps agree under its model
+    (mdrp_amd/covis.py): 300 inliers on one poster no longer beat a pair whose maps agree over half the frame.
     pairs (B, 2) image indices, weights (B,): larger is better; a pair with a == c, an index outside [0, n_images) or a NaN weight is left out.
     Deterministic: Kruskal's algorithm over the pairs by descending weight, ties by the lower pair index.  roots: the image each component is rooted
     at - any number of images, at most one per component; a component without one is rooted at its lowest image.  A root takes the lowest-index

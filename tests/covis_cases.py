@@ -1,0 +1,175 @@
+"""Case builders for the co-visibility tests (include/mdrp_covis.h): models near the identity with full mantissas, so that most of an
+image lands inside the other and every class of C6 is populated; one model that throws every point behind the target, one that throws every point
+outside it, R1's unusable models; depth maps around one surface with outliers on both sides of it and planted +inf, -inf, NaN, 0 and negative
+depths, a whole row and a whole map of inf; cameras of both models; and the reference as the NumPy definition states it (mdrp_amd/frontend.py),
+computed once per pair and shared."""
+import functools
+
+import numpy as np
+
+from mdrp_amd import _capi, frontend
+
+KINDS = ("calibrated", "shared_focal", "varying_focal")
+# ((h1, w1), (h2, w2)): one pixel | fewer than a lane's run | 37 * 53 = 1961 pixels straddle a tile of 1024 and leave a run of 1 hanging | many tiles
+SIZES = (((1, 1), (1, 1)), ((3, 5), (2, 7)), ((37, 53), (41, 29)), ((130, 257), (67, 131)))
+BATCHES = (1, 3, 17)
+RATES = (1.0, 0.5, 0.05)
+TOLS = (0.0, 0.05)
+B_MAX = max(BATCHES)
+SEED = 0x1234ABCD5
+EMPTY = {1: "nan_q", 5: "zero_scale", 9: "bad_focal", 13: "inf_t"}  # C1's empty pairs, mixed into every batch of more than one pair
+BEHIND, OUTSIDE = 6, 7                                              # no sampled pixel is FRONT | every one is FRONT and none INSIDE
+INF_MAP = {0: 2, 1: 4}                                              # the map of image 1 | image 2 that is all +inf
+
+
+def models(kind, n=B_MAX, seed=41):
+    """n models near the identity whose every value has a full mantissa (a fused multiply-add would round differently somewhere)"""
+    rng = np.random.default_rng(seed)
+    m = np.zeros(n, dtype=_capi.MODEL_DTYPE)
+    q = np.concatenate([np.ones((n, 1)), rng.normal(size=(n, 3)) * 0.04], axis=1)
+    m["q"] = q / np.linalg.norm(q, axis=1, keepdims=True) * rng.uniform(0.99, 1.01, size=(n, 1))  # (nobody promised a unit quaternion)
+    m["t"] = rng.normal(size=(n, 3)) * 0.25
+    m["scale"] = rng.uniform(0.85, 1.2, size=n)
+    m["shift1"] = rng.normal(size=n) * 0.17
+    m["shift2"] = rng.normal(size=n) * 0.21
+    m["f1"] = rng.uniform(60.0, 140.0, size=n) if kind != "calibrated" else 1.0
+    m["f2"] = m["f1"] if kind == "shared_focal" else (rng.uniform(60.0, 140.0, size=n) if kind == "varying_focal" else 1.0)
+    for i, what in EMPTY.items():
+        if i >= n:
+            continue
+        if what == "nan_q":
+            m["q"][i, 0] = np.nan
+        elif what == "zero_scale":
+            m["scale"][i] = 0.0
+        elif what == "bad_focal":
+            if kind == "calibrated":
+                m["shift2"][i] = np.inf
+            else:
+                m["f1"][i] = -1.0
+        else:
+            m["t"][i, 1] = -np.inf
+    if n > BEHIND:
+        m["q"][BEHIND] = [0.0, 0.0, 1.0, 0.0]   # half a turn about y: z changes its sign, in both directions
+        m["t"][BEHIND] = [0.1, -0.1, -0.2]  # (z <= 0 on both sides: a positive z would bring the nearest points in front)
+    if n > OUTSIDE:
+        m["t"][OUTSIDE] = [1.0e4, 0.0, 0.3]     # far to the side, in both directions
+    return m
+
+
+def cameras(size, n=B_MAX, seed=42):
+    """two [n] camera tables with the principal points near the maps' middles: SIMPLE_PINHOLE and PINHOLE with fx != fy alternate"""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((2, n), dtype=_capi.CAMERA_DTYPE)
+    for s in range(2):
+        h, w = size[s]
+        for i in range(n):
+            cx, cy = w / 2.0 + rng.uniform(-2.0, 2.0), h / 2.0 + rng.uniform(-2.0, 2.0)
+            if (i + s) % 2:
+                out[s, i]["model_id"] = 1
+                out[s, i]["params"] = [rng.uniform(60, 140), rng.uniform(60, 140), cx, cy]
+            else:
+                out[s, i]["params"] = [rng.uniform(60, 140), cx, cy, 0.0]
+    return out[0], out[1]
+
+
+def centres(kind, size, n=B_MAX, seed=43):
+    """the focal kinds' principal points (near the middles); small offsets for the calibrated kind, whose cameras carry theirs"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for s in range(2):
+        h, w = size[s]
+        mid = np.zeros(2) if kind == "calibrated" else np.array([w / 2.0, h / 2.0])
+        out.append(mid + rng.uniform(-1.5, 1.5, size=(n, 2)))
+    return out
+
+
+def depth_maps(h, w, dtype, n=B_MAX, seed=44, whole_inf=2):
+    """(n, h, w) depths: a surface near 5 with a third of the pixels anywhere in 0.4 .. 23 (occluders and holes), planted +inf, -inf, NaN, 0 and
+    negatives; row 0 of every odd map is +inf where the map has more than one row; map `whole_inf` is all +inf"""
+    rng = np.random.default_rng(seed + 1000 * h + w)
+    d = 5.0 + 0.12 * rng.normal(size=(n, h, w))
+    wild = rng.uniform(size=(n, h, w)) < 0.33
+    d[wild] = rng.uniform(0.4, 23.0, size=int(wild.sum()))
+    plant = rng.integers(0, 40, size=(n, h, w))
+    d[plant == 0] = np.inf
+    d[plant == 1] = -np.inf
+    d[plant == 2] = np.nan
+    d[plant == 3] = 0.0
+    d[plant == 4] *= -1.0
+    if h > 1:
+        d[1::2, 0, :] = np.inf
+    if n > whole_inf:
+        d[whole_inf] = np.inf
+    return d.astype(dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(kind, dtype_name, size):
+    """everything a call of the per-pair form takes, for B_MAX pairs; a batch of B is the first B of each"""
+    (h1, w1), (h2, w2) = size
+    dtype = np.dtype(dtype_name)
+    cam1, cam2 = cameras(size) if kind == "calibrated" else (None, None)
+    c1, c2 = centres(kind, size)
+    return {"models": models(kind), "dm1": depth_maps(h1, w1, dtype, seed=44, whole_inf=INF_MAP[0]), "dm2": depth_maps(h2, w2, dtype, seed=45, whole_inf=INF_MAP[1]),
+            "c1": c1, "c2": c2, "cam1": cam1, "cam2": cam2}
+
+
+@functools.lru_cache(maxsize=None)
+def pair_counts(kind, dtype_name, size, rate, tol, b):
+    """the definition's (2, 8) counters of pair b: computed once, shared by every batch that holds the pair"""
+    x = inputs(kind, dtype_name, size)
+    lo, hi = frontend.covis_band(tol)
+    return frontend.covisibility_pair_numpy(x["models"][b], kind, x["dm1"][b], x["dm2"][b], x["c1"][b], x["c2"][b], None if x["cam1"] is None else x["cam1"][b],
+                                            None if x["cam2"] is None else x["cam2"][b], frontend.recon_threshold(rate), SEED, lo, hi)
+
+
+def reference(kind, dtype_name, size, rate, tol, B):
+    """counts (B, 2, 8) int32 by the definition"""
+    return np.stack([pair_counts(kind, dtype_name, size, rate, tol, b) for b in range(B)])
+
+
+def run(kind, dtype_name, size, rate, tol, B, device="cuda:0"):
+    """poselib.covisibility_pairs_torch on the first B pairs, as a NumPy array"""
+    import torch
+    from mdrp_amd import poselib
+    x = inputs(kind, dtype_name, size)
+    dev = torch.device(device)
+    out = poselib.covisibility_pairs_torch(kind, x["models"][:B], torch.from_numpy(x["dm1"][:B]).to(dev), torch.from_numpy(x["dm2"][:B]).to(dev),
+                                           None if x["cam1"] is None else x["cam1"][:B], None if x["cam2"] is None else x["cam2"][:B],
+                                           torch.from_numpy(x["c1"][:B]).to(dev), torch.from_numpy(x["c2"][:B]).to(dev), rate, SEED, tol)
+    return out.cpu().numpy()
+
+
+# ---- straight through a handle (refusals, history): the descriptor of the first B pairs of `inputs`, the call, the counters as a byte string
+def device_call(h, kind="varying_focal", dtype_name="float32", size=SIZES[2], B=3, rate=0.5, tol=0.05, stride=96, change=None, image_form=False):
+    """h.covisibility_pairs_device on the inputs of (kind, dtype, size); change(args) may overwrite any entry of the argument dict before the call
+    (desc, opt, kind, batch, models, stride, counts, cam1, cam2).  image_form: the same pairs through a DepthImagePairs descriptor whose image set is
+    the B maps of image 1 (image 2 of pair b is image (b + 1) % B)."""
+    import torch
+    from mdrp_amd import poselib
+    x = inputs(kind, dtype_name, size)
+    dev = torch.device("cuda:0")
+    k = poselib.MONODEPTH_KINDS[kind]
+    (h1, w1), (h2, w2) = size
+    dm1, dm2 = torch.from_numpy(x["dm1"][:B]).to(dev), torch.from_numpy(x["dm2"][:B]).to(dev)
+    c1, c2 = torch.from_numpy(x["c1"][:B]).to(dev), torch.from_numpy(x["c2"][:B]).to(dev)
+    rec = np.zeros(B, dtype=_capi.RESULT_DTYPE if stride == 136 else _capi.MODEL_DTYPE)
+    (rec["model"] if stride == 136 else rec)[...] = x["models"][:B]
+    models_dev = torch.from_numpy(rec.view(np.uint8).reshape(B, stride).copy()).to(dev)
+    ftype = _capi.F32 if dtype_name == "float32" else _capi.F64
+    if image_form:
+        pairs = torch.tensor([[b, (b + 1) % B] for b in range(B)], dtype=torch.int32, device=dev)
+        desc = _capi.DepthImagePairs(dm1.data_ptr(), ftype, h1, w1, B, None, c1.data_ptr(), pairs.data_ptr())
+    else:
+        desc = _capi.DepthPairs(dm1.data_ptr(), dm2.data_ptr(), ftype, h1, w1, h2, w2, 0, c1.data_ptr(), c2.data_ptr())
+    lo, hi = frontend.covis_band(tol)
+    opt = _capi.CovisOpt(frontend.recon_threshold(rate), 0, SEED, lo, hi)
+    counts = torch.full((B, 2, 8), 7, dtype=torch.int32, device=dev)
+    a = {"kind": k, "desc": desc, "opt": opt, "batch": B, "models": models_dev.data_ptr(), "stride": stride, "counts": counts.data_ptr(),
+         "cam1": None if x["cam1"] is None else x["cam1"][:B], "cam2": None if x["cam2"] is None else x["cam2"][:B]}
+    if change is not None:
+        change(a)
+    torch.cuda.synchronize()
+    h.covisibility_pairs_device(a["kind"], a["desc"], a["opt"], a["batch"], a["models"], a["stride"], a["counts"], a["cam1"], a["cam2"])
+    h.synchronize()
+    return (counts.cpu().numpy().tobytes(),)
