@@ -25,15 +25,13 @@ def _options(rate, seed, tol):
     return _capi.CovisOpt(thr, 0, seed, lo, hi)
 
 
-def _run(k, desc, opt, B, dev, models, cams1, cams2, keep_alive):
+def _counters(B, opt, dev):
     import torch
-    h = _pl._handle_on(dev)
-    with torch.cuda.device(dev):
-        rec, stride = reconstruct._models(models, B, dev, h)
-        counts = torch.empty((B, 2, _capi.COVIS_SLOTS), dtype=torch.int32, device=dev)
-        h.covisibility_pairs_device(k, desc, opt, B, rec.data_ptr(), stride, counts.data_ptr(), cams1, cams2)
-    del rec, keep_alive  # (queued on the current stream, where torch's allocator orders the reuse of their memory behind the call)
-    return counts
+    return (torch.empty((B, 2, _capi.COVIS_SLOTS), dtype=torch.int32, device=dev),)
+
+
+def _run(staged, models):
+    return reconstruct._run(staged, models, _counters, lambda h: h.covisibility_pairs_device)[0]
 
 
 def covisibility_pairs_torch(kind, models, depth_map1, depth_map2, cameras1=None, cameras2=None, center1=None, center2=None, rate=0.05, seed=0, tol=0.05):
@@ -45,53 +43,16 @@ def covisibility_pairs_torch(kind, models, depth_map1, depth_map2, cameras1=None
     sampled | front | inside | known | consistent | occluded | violating pixels and a 0 - each of the first four a subset of the one before it, the
     last three a partition of `known`.  `violating` points float in front of a surface the other camera saw: evidence against the model.  A pair
     whose model is not usable (a NaN pose, scale 0, a focal <= 0) has all counters 0.  covisibility_scores turns the counts into ratios and a weight."""
-    k = _pl._monodepth_kind(kind)
-    dev = _pl._check_on_gpu({"depth_map1": depth_map1, "depth_map2": depth_map2})
-    _pl._check_float_pair(depth_map1, depth_map2, "depth maps")
-    if depth_map1.dim() != 3 or depth_map2.dim() != 3 or depth_map1.shape[0] != depth_map2.shape[0]:
-        raise ValueError("depth maps must have shape (B, H, W) with one B")
-    B = int(depth_map1.shape[0])
-    (h1, w1), (h2, w2) = (int(v) for v in depth_map1.shape[1:]), (int(v) for v in depth_map2.shape[1:])
-    reconstruct._check_maps(h1, w1); reconstruct._check_maps(h2, w2)
-    opt = _options(rate, seed, tol)
-    cams1 = cams2 = None
-    if k == _capi.CALIB:
-        cams1, cams2 = _pl._camera_records(cameras1, B), _pl._camera_records(cameras2, B)
-    elif cameras1 is not None or cameras2 is not None:
-        raise ValueError("cameras are the calibrated kind's: a focal kind projects with the model's focals")
-    dm1, dm2 = depth_map1.contiguous(), depth_map2.contiguous()
-    c1, c2 = _pl._center(center1, B, dev), _pl._center(center2, B, dev)
-    desc = _capi.DepthPairs(dm1.data_ptr(), dm2.data_ptr(), _pl._float_types()[dm1.dtype], h1, w1, h2, w2, 0, _pl._data_ptr(c1), _pl._data_ptr(c2))
-    return _run(k, desc, opt, B, dev, models, cams1, cams2, (dm1, dm2, c1, c2))
+    staged = reconstruct._stage_pairs(kind, depth_map1, depth_map2, cameras1, cameras2, center1, center2, lambda pixels: _options(rate, seed, tol), "projects")
+    return _run(staged, models)
 
 
 def covisibility_image_pairs_torch(kind, models, depth_maps, pairs, cameras=None, centers=None, sizes=None, rate=0.05, seed=0, tol=0.05):
     """covisibility_pairs_torch for pairs given as image indices: depth_maps (I, H, W) exist once per image, pairs (B, 2) image indices (a, c) as a
     sequence, NumPy array or tensor on any device (a pair with an index outside [0, I) has all counters 0); sizes, centers and cameras per IMAGE, as
     reconstruct_image_pairs_torch takes them.  Returns counts (B, 2, 8) int32 on the device."""
-    import torch
-    k = _pl._monodepth_kind(kind)
-    dev = _pl._check_on_gpu({"depth_maps": depth_maps})
-    if depth_maps.dtype not in _pl._float_types():
-        raise ValueError("depth maps must be float32 or float64")
-    if depth_maps.dim() != 3:
-        raise ValueError("depth maps must have shape (I, H, W)")
-    I, H, W = (int(v) for v in depth_maps.shape)
-    reconstruct._check_maps(H, W)
-    on_device, host_pairs, B = _pl._pairs_on_host(pairs, dev, k == _capi.CALIB)
-    B = int(B)
-    opt = _options(rate, seed, tol)
-    cams1 = cams2 = None
-    if k == _capi.CALIB:
-        cams1, cams2 = _pl._pair_cameras(cameras, host_pairs, I)
-    elif cameras is not None:
-        raise ValueError("cameras are the calibrated kind's: a focal kind projects with the model's focals")
-    dm = depth_maps.contiguous()
-    cs = _pl._per_image(centers, torch.float64, (I, 2), "centers", dev)
-    sz = _pl._per_image(sizes, torch.int32, (I, 2), "sizes", dev)
-    pr = _pl._pairs_on_device(pairs, on_device, host_pairs, dev)
-    desc = _capi.DepthImagePairs(dm.data_ptr(), _pl._float_types()[dm.dtype], H, W, I, _pl._data_ptr(sz), _pl._data_ptr(cs), pr.data_ptr())
-    return _run(k, desc, opt, B, dev, models, cams1, cams2, (dm, cs, sz, pr))
+    staged = reconstruct._stage_image_pairs(kind, depth_maps, pairs, cameras, centers, sizes, lambda pixels: _options(rate, seed, tol), "projects")
+    return _run(staged, models)
 
 
 def covisibility_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1=None, camera2=None, center1=None, center2=None, rate=0.05, seed=0,
@@ -99,19 +60,7 @@ def covisibility_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1=No
     """One pair for NumPy users, over the same device call: a MonoDepthTwoViewGeometry with its two cameras (the calibrated kind), or a
     MonoDepthImagePair (its cameras' focals; pass center1 / center2, the principal points), and two (H, W) float32 | float64 depth maps.
     Returns counts (2, 8) int32 as a NumPy array."""
-    import torch
-    g = geometry_or_image_pair
-    focal = hasattr(g, "camera1") and hasattr(g, "geometry")
-    if not focal and (camera1 is None or camera2 is None):
-        raise ValueError("a MonoDepthTwoViewGeometry needs camera1 and camera2; a MonoDepthImagePair brings its focals")
-    if focal and (camera1 is not None or camera2 is not None):
-        raise ValueError("a MonoDepthImagePair brings its focals: pass no cameras")
-    kind = _capi.VARYING_FOCAL if focal else _capi.CALIB
-    rec = _pl._model_records([g], kind)
-    dev = torch.device("cuda", int(device))
-    maps = [torch.from_numpy(np.ascontiguousarray(frontend._table(d, "depth maps"))).to(dev).unsqueeze(0) for d in (depth_map1, depth_map2)]
-    if maps[0].dim() != 3 or maps[1].dim() != 3:
-        raise ValueError("expected depth maps (H, W)")
+    kind, rec, maps = reconstruct._single_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1, camera2, device)
     return covisibility_pairs_torch(kind, rec, maps[0], maps[1], camera1, camera2, center1, center2, rate, seed, tol).cpu().numpy()[0]
 
 

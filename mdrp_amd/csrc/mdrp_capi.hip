@@ -98,6 +98,19 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// One DevBuf carved into a call's blocks, each 16-byte aligned: take() every block's bytes, ensure() the buffer, then at<T>() a block.
+struct Carve {
+    size_t total = 0;
+    unsigned char *base = nullptr;
+    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; }
+    int ensure(DevBuf &buf, size_t least = 0) {
+        if (int rc = buf.ensure(std::max(total, least))) return rc;
+        base = buf.as<unsigned char>();
+        return MDRP_OK;
+    }
+    template <typename T> T *at(size_t offset) const { return reinterpret_cast<T *>(base + offset); }
+};
+
 // any other HIP object of a handle (stream, event, pinned host memory): destroyed with the handle, or when creating the handle fails half-way
 template <typename T, auto Destroy> struct Owned {
     T v = nullptr;
@@ -210,9 +223,11 @@ struct mdrp_handle {
     size_t fe_n_host_cap = 0;
     DevBuf fp_nper, fp_in, fp_out;     // focals and pose from F (include/mdrp_classic_focals.h): n per pair | a host call's models, mask and principal points | its records
     DevBuf dn_scratch, dn_score;       // dense front end (include/mdrp_dense.h): the sampler's scratch, carved per call (DenseScratch) | mdrp_estimate_dense_async: the records' certainties
-    DevBuf rc_scratch;                 // back end (include/mdrp_reconstruct.h): tile counts | the pairs' ReconPair | the two camera tables, carved per call
-    DevBuf cv_scratch;                 // co-visibility (include/mdrp_covis.h): the pairs' CovisPair | the two camera tables, carved per call
-    DevBuf sc_scratch;                 // scenes (include/mdrp_scene.h): the images' records (where the caller takes none) | their SceneImage | the camera table | tile counts, carved per call
+    // back end, carved per call (calls on a handle are serialised on one stream, and every word a kernel reads was written by its own call) -
+    // clouds (include/mdrp_reconstruct.h): the pairs' ReconPair | the two camera tables | tile counts; co-visibility (include/mdrp_covis.h): the pairs'
+    // CovisPair | the two camera tables; scenes (include/mdrp_scene.h): the images' records (where the caller takes none) | their SceneImage | the
+    // camera table | tile counts
+    DevBuf be_scratch;
     DevBuf unit_a, unit_b, unit_c, unit_d, unit_e, unit_f;
     Pinned<Progress> progress_host;
     // sweep timing
@@ -2812,19 +2827,17 @@ int dense_sample_device(mdrp_handle *h, const mdrp_dense_matches *d, int batch, 
     a.nblk = std::max(1, (d->rows + DENSE_BLOCK_ROWS - 1) / DENSE_BLOCK_ROWS); // (a warp without rows: one empty block)
     a.ntile = (a.m1_max + DENSE_THREADS - 1) / DENSE_THREADS;
     const size_t b = (size_t)batch, slots = (size_t)a.ntile * DENSE_THREADS;
-    size_t total = 0;
-    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
-    const size_t o_qpre = carve(sizeof(uint32_t) * b * std::max(a.rows, 1)), o_bpre = carve(sizeof(uint64_t) * b * a.nblk), o_bcnt = carve(sizeof(uint32_t) * b * a.nblk),
-                 o_meta = carve(sizeof(DenseMeta) * b), o_cand = carve(sizeof(int32_t) * b * slots), o_tcnt = carve(sizeof(int32_t) * b * a.ntile),
-                 o_p1 = carve(sizeof(int32_t) * b * a.m1_max), o_cell = carve(sizeof(int32_t) * b * a.m1_max), o_wpre = carve(sizeof(uint64_t) * b * a.m1_max),
-                 o_sel = carve(sizeof(int32_t) * b * a.n), o_rank = carve(sizeof(int32_t) * b * a.n);
-    if (int rc = h->dn_scratch.ensure(total)) return rc;
-    unsigned char *p = h->dn_scratch.as<unsigned char>();
+    Carve cv;
+    const size_t o_qpre = cv.take(sizeof(uint32_t) * b * std::max(a.rows, 1)), o_bpre = cv.take(sizeof(uint64_t) * b * a.nblk), o_bcnt = cv.take(sizeof(uint32_t) * b * a.nblk),
+                 o_meta = cv.take(sizeof(DenseMeta) * b), o_cand = cv.take(sizeof(int32_t) * b * slots), o_tcnt = cv.take(sizeof(int32_t) * b * a.ntile),
+                 o_p1 = cv.take(sizeof(int32_t) * b * a.m1_max), o_cell = cv.take(sizeof(int32_t) * b * a.m1_max), o_wpre = cv.take(sizeof(uint64_t) * b * a.m1_max),
+                 o_sel = cv.take(sizeof(int32_t) * b * a.n), o_rank = cv.take(sizeof(int32_t) * b * a.n);
+    if (int rc = cv.ensure(h->dn_scratch)) return rc;
     DenseScratch z;
-    z.qpre = reinterpret_cast<uint32_t *>(p + o_qpre); z.bpre = reinterpret_cast<uint64_t *>(p + o_bpre); z.bcnt = reinterpret_cast<uint32_t *>(p + o_bcnt);
-    z.meta = reinterpret_cast<DenseMeta *>(p + o_meta); z.cand = reinterpret_cast<int32_t *>(p + o_cand); z.tcnt = reinterpret_cast<int32_t *>(p + o_tcnt);
-    z.p1 = reinterpret_cast<int32_t *>(p + o_p1); z.cell = reinterpret_cast<int32_t *>(p + o_cell); z.wpre = reinterpret_cast<uint64_t *>(p + o_wpre);
-    z.sel = reinterpret_cast<int32_t *>(p + o_sel); z.rank = reinterpret_cast<int32_t *>(p + o_rank);
+    z.qpre = cv.at<uint32_t>(o_qpre); z.bpre = cv.at<uint64_t>(o_bpre); z.bcnt = cv.at<uint32_t>(o_bcnt);
+    z.meta = cv.at<DenseMeta>(o_meta); z.cand = cv.at<int32_t>(o_cand); z.tcnt = cv.at<int32_t>(o_tcnt);
+    z.p1 = cv.at<int32_t>(o_p1); z.cell = cv.at<int32_t>(o_cell); z.wpre = cv.at<uint64_t>(o_wpre);
+    z.sel = cv.at<int32_t>(o_sel); z.rank = cv.at<int32_t>(o_rank);
     hipLaunchKernelGGL(k_dense_weights, dim3(batch, a.nblk), dim3(DENSE_THREADS), 0, s, a, z.qpre, z.bpre, z.bcnt);
     hipLaunchKernelGGL(k_dense_scan, dim3(batch), dim3(DENSE_THREADS), 0, s, a, z.bpre, (const uint32_t *)z.bcnt, z.meta);
     hipLaunchKernelGGL(k_dense_pick, dim3(batch, a.ntile), dim3(DENSE_THREADS), 0, s, a, (const uint32_t *)z.qpre, (const uint64_t *)z.bpre, (const DenseMeta *)z.meta,
@@ -2898,7 +2911,8 @@ static_assert(sizeof(mdrp_depth_pairs) == 56 && offsetof(mdrp_depth_pairs, cente
               offsetof(mdrp_depth_image_pairs, size) == 24 && sizeof(mdrp_reconstruct_opt) == 24 && offsetof(mdrp_reconstruct_opt, p_max) == 16, "descriptor layout");
 static_assert(sizeof(ReconCam) == sizeof(mdrp_camera) && offsetof(ReconCam, params) == offsetof(mdrp_camera, params), "camera layout");
 
-// one call of either entry point: the descriptor flattened (ReconArgs without its tile counts) and everything else the caller handed over
+// one call of a two-view entry point (clouds or co-visibility): the descriptor and the options flattened (ReconArgs without its tile counts) and
+// everything else the caller handed over
 struct ReconCall {
     const char *who;
     ReconArgs a;
@@ -2907,56 +2921,112 @@ struct ReconCall {
     float *points;
     int32_t *pixel, *counts;
 };
+ReconCall recon_call(const char *who, int kind, int batch, const void *models_dev, int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, float *points,
+                     int32_t *pixel, int32_t *counts) {
+    ReconCall c{who, {}, batch, cam1, cam2, points, pixel, counts};
+    c.a.models = static_cast<const unsigned char *>(models_dev); c.a.model_stride = model_stride; c.a.kind = kind;
+    return c;
+}
+// the two descriptors into ReconArgs (struct ReconArgs, mdrp_reconstruct.h)
+void recon_flatten(ReconArgs &a, const mdrp_depth_pairs *dp) {
+    a.depth1 = dp->depth1; a.depth2 = dp->depth2; a.center1 = dp->center1; a.center2 = dp->center2;
+    a.depth_type = dp->depth_type;
+    a.h1 = dp->h1; a.w1 = dp->w1; a.h2 = dp->h2; a.w2 = dp->w2;
+}
+void recon_flatten(ReconArgs &a, const mdrp_depth_image_pairs *ip) {
+    a.depth1 = a.depth2 = ip->n_images > 0 ? ip->depth : ip; // (an empty set: no map is read; the pointer only has to pass for one)
+    a.center1 = a.center2 = ip->center; a.size = ip->size; a.pairs = ip->pairs; a.n_images = ip->n_images;
+    a.depth_type = ip->depth_type;
+    a.h1 = a.h2 = ip->h_max; a.w1 = a.w2 = ip->w_max;
+}
 
-// what both entry points refuse before any device work (the descriptor's own NULLs are the entry points')
-const char *recon_refusal(const ReconCall &c, const mdrp_reconstruct_opt *o) {
-    const ReconArgs &a = c.a;
-    if (c.batch < 0) return "negative batch";
-    if (a.kind < MDRP_CALIB || a.kind > MDRP_VARYING_FOCAL) return "only the monodepth estimators' models (kind 0..2) have depths to unproject";
-    if (a.kind == MDRP_CALIB && c.batch > 0 && (!c.cam1 || !c.cam2)) return "MDRP_CALIB needs cam1_host and cam2_host, one record per pair";
-    if (a.kind != MDRP_CALIB && (c.cam1 || c.cam2)) return "cameras are MDRP_CALIB's: a focal kind unprojects with the model's focals (pass NULL)";
-    if (a.model_stride < RECON_MODEL_BYTES || a.model_stride % 8 != 0) return "model_stride must be at least 96 and a multiple of 8";
-    if (a.depth_type != MDRP_F32 && a.depth_type != MDRP_F64) return "depth_type must be MDRP_F32 or MDRP_F64";
-    if (o->keep != MDRP_KEEP_NOT_INF && o->keep != MDRP_KEEP_FINITE) return "keep must be MDRP_KEEP_NOT_INF or MDRP_KEEP_FINITE";
-    if (o->thr == 0) return "thr == 0 keeps nothing (1 .. MDRP_RECON_ALL)";
-    if (o->p_max < 0) return "negative p_max";
-    if (a.h1 < 0 || a.w1 < 0 || a.h2 < 0 || a.w2 < 0 || a.n_images < 0) return "negative size";
-    if (a.h1 > MDRP_RECON_MAX_EXTENT || a.w1 > MDRP_RECON_MAX_EXTENT || a.h2 > MDRP_RECON_MAX_EXTENT || a.w2 > MDRP_RECON_MAX_EXTENT)
+// The runs of refusals that the back end's entry points share; each entry point composes them in its own order, which decides the message of a call
+// with two defects.
+const char *recon_kind_refusal(int kind) {
+    return kind < MDRP_CALIB || kind > MDRP_VARYING_FOCAL ? "only the monodepth estimators' models (kind 0..2) have depths to unproject" : nullptr;
+}
+const char *recon_stride_refusal(int model_stride) {
+    return model_stride < RECON_MODEL_BYTES || model_stride % 8 != 0 ? "model_stride must be at least 96 and a multiple of 8" : nullptr;
+}
+const char *recon_focal_cameras_refusal(int kind, bool cameras) {
+    return kind != MDRP_CALIB && cameras ? "cameras are MDRP_CALIB's: a focal kind unprojects with the model's focals (pass NULL)" : nullptr;
+}
+const char *recon_option_refusal(int depth_type, int keep, uint32_t thr, int p_max) {
+    if (depth_type != MDRP_F32 && depth_type != MDRP_F64) return "depth_type must be MDRP_F32 or MDRP_F64";
+    if (keep != MDRP_KEEP_NOT_INF && keep != MDRP_KEEP_FINITE) return "keep must be MDRP_KEEP_NOT_INF or MDRP_KEEP_FINITE";
+    if (thr == 0) return "thr == 0 keeps nothing (1 .. MDRP_RECON_ALL)";
+    if (p_max < 0) return "negative p_max";
+    return nullptr;
+}
+const char *recon_extent_refusal(int h1, int w1, int h2, int w2, int n_images) {
+    if (h1 < 0 || w1 < 0 || h2 < 0 || w2 < 0 || n_images < 0) return "negative size";
+    if (h1 > MDRP_RECON_MAX_EXTENT || w1 > MDRP_RECON_MAX_EXTENT || h2 > MDRP_RECON_MAX_EXTENT || w2 > MDRP_RECON_MAX_EXTENT)
         return "extent above MDRP_RECON_MAX_EXTENT (65536)";
-    if ((int64_t)a.h1 * a.w1 > INT32_MAX || (int64_t)a.h2 * a.w2 > INT32_MAX) return "a map of 2^31 pixels or more";
-    if (c.batch == 0) return nullptr;
-    if (!a.models || !c.counts) return "NULL models_dev or counts";
-    if (o->p_max > 0 && (!c.points || !c.pixel)) return "NULL points or pixel";
-    if (((int64_t)a.h1 * a.w1 > 0 && !a.depth1) || ((int64_t)a.h2 * a.w2 > 0 && !a.depth2)) return "NULL depth map";
-    if (a.kind == MDRP_CALIB)
-        for (int i = 0; i < c.batch; ++i)
-            if ((c.cam1[i].model_id | 1) != 1 || (c.cam2[i].model_id | 1) != 1) return "only SIMPLE_PINHOLE (0) and PINHOLE (1) cameras unproject here";
+    if ((int64_t)h1 * w1 > INT32_MAX || (int64_t)h2 * w2 > INT32_MAX) return "a map of 2^31 pixels or more";
+    return nullptr;
+}
+const char *recon_camera_models_refusal(const mdrp_camera *cams, int n) {
+    for (int i = 0; i < n; ++i)
+        if ((cams[i].model_id | 1) != 1) return "only SIMPLE_PINHOLE (0) and PINHOLE (1) cameras unproject here";
     return nullptr;
 }
 
-// The three kernels on the handle's stream.  The scratch is one buffer of the handle, carved for this call's sizes; every word of it that a kernel
-// reads was written by this call.
-int reconstruct_device(mdrp_handle *h, ReconCall &c, const mdrp_reconstruct_opt *o) {
+// what the two-view entry points refuse before any device work (the descriptor's own NULLs are the entry points')
+const char *recon_refusal(const ReconCall &c) {
+    const ReconArgs &a = c.a;
+    const char *why;
+    if (c.batch < 0) return "negative batch";
+    if ((why = recon_kind_refusal(a.kind))) return why;
+    if (a.kind == MDRP_CALIB && c.batch > 0 && (!c.cam1 || !c.cam2)) return "MDRP_CALIB needs cam1_host and cam2_host, one record per pair";
+    if ((why = recon_focal_cameras_refusal(a.kind, c.cam1 || c.cam2))) return why;
+    if ((why = recon_stride_refusal(a.model_stride))) return why;
+    if ((why = recon_option_refusal(a.depth_type, a.keep, a.thr, a.p_max))) return why;
+    if ((why = recon_extent_refusal(a.h1, a.w1, a.h2, a.w2, a.n_images))) return why;
+    if (c.batch == 0) return nullptr;
+    if (!a.models || !c.counts) return "NULL models_dev or counts";
+    if (a.p_max > 0 && (!c.points || !c.pixel)) return "NULL points or pixel";
+    if (((int64_t)a.h1 * a.w1 > 0 && !a.depth1) || ((int64_t)a.h2 * a.w2 > 0 && !a.depth2)) return "NULL depth map";
+    if (a.kind == MDRP_CALIB && ((why = recon_camera_models_refusal(c.cam1, c.batch)) || (why = recon_camera_models_refusal(c.cam2, c.batch)))) return why;
+    return nullptr;
+}
+
+int recon_tiles(int h, int w) { return (int)std::max<int64_t>(1, ((int64_t)h * w + RECON_TILE - 1) / RECON_TILE); } // (a map without pixels: one empty tile)
+
+// the call's tile counts from its extents and p_max; the refusal of a grid it cannot launch (batch >= 0)
+const char *recon_tile_counts(ReconCall &c) {
     ReconArgs &a = c.a;
-    a.keep = o->keep; a.thr = o->thr; a.seed = (uint32_t)o->seed; a.p_max = o->p_max;
-    const auto tiles = [](int hh, int ww) { return (int)std::max<int64_t>(1, ((int64_t)hh * ww + RECON_TILE - 1) / RECON_TILE); }; // (a map without pixels: one empty tile)
-    a.nt1 = tiles(a.h1, a.w1); a.nt2 = tiles(a.h2, a.w2); a.nfill = (a.p_max + RECON_TILE - 1) / RECON_TILE;
-    const size_t b = (size_t)c.batch, nt = (size_t)a.nt1 + a.nt2;
-    if (b * (nt + a.nfill) > (size_t)INT32_MAX) { g_err = std::string(c.who) + ": batch * tiles above 2^31 - 1: split the batch"; return MDRP_ERR_INVALID; }
+    a.nt1 = recon_tiles(a.h1, a.w1); a.nt2 = recon_tiles(a.h2, a.w2); a.nfill = (a.p_max + RECON_TILE - 1) / RECON_TILE;
+    return (size_t)c.batch * ((size_t)a.nt1 + a.nt2 + a.nfill) > (size_t)INT32_MAX ? "batch * tiles above 2^31 - 1: split the batch" : nullptr;
+}
+
+// The caller's camera table(s) of `count` records each into a carved block, the second behind the first.  Pageable: the copies have left the caller's
+// tables when hipMemcpyAsync returns.
+int upload_cameras(mdrp_handle *h, ReconCam *dst, const mdrp_camera *cams1, const mdrp_camera *cams2, size_t count) {
+    HIPCHK(hipMemcpyAsync(dst, cams1, sizeof(ReconCam) * count, hipMemcpyHostToDevice, h->stream));
+    if (cams2) HIPCHK(hipMemcpyAsync(dst + count, cams2, sizeof(ReconCam) * count, hipMemcpyHostToDevice, h->stream));
+    return MDRP_OK;
+}
+// ... of a calibrated two-view call, per pair
+int upload_pair_cameras(mdrp_handle *h, ReconCall &c, ReconCam *dst) {
+    if (c.a.kind != MDRP_CALIB) return MDRP_OK;
+    c.a.cam1 = dst; c.a.cam2 = dst + c.batch;
+    return upload_cameras(h, dst, c.cam1, c.cam2, (size_t)c.batch);
+}
+
+// The three kernels on the handle's stream.  The scratch is the back end's buffer of the handle, carved for this call's sizes; every word of it that
+// a kernel reads was written by this call.
+int reconstruct_device(mdrp_handle *h, ReconCall &c) {
+    ReconArgs &a = c.a;
+    if (const char *why = recon_tile_counts(c)) { g_err = std::string(c.who) + ": " + why; return MDRP_ERR_INVALID; }
     if (c.batch == 0) return MDRP_OK;
-    size_t total = 0;
-    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
-    const size_t o_pair = carve(sizeof(ReconPair) * b), o_cam = carve(sizeof(ReconCam) * 2 * b), o_tcnt = carve(sizeof(uint32_t) * b * nt);
-    if (int rc = h->rc_scratch.ensure(total)) return rc;
-    unsigned char *p = h->rc_scratch.as<unsigned char>();
+    const size_t b = (size_t)c.batch, nt = (size_t)a.nt1 + a.nt2;
+    Carve cv;
+    const size_t o_pair = cv.take(sizeof(ReconPair) * b), o_cam = cv.take(sizeof(ReconCam) * 2 * b), o_tcnt = cv.take(sizeof(uint32_t) * b * nt);
+    int rc;
+    if ((rc = cv.ensure(h->be_scratch)) || (rc = upload_pair_cameras(h, c, cv.at<ReconCam>(o_cam)))) return rc;
     hipStream_t s = h->stream;
-    if (a.kind == MDRP_CALIB) { // pageable: the copies have left the caller's tables when hipMemcpyAsync returns
-        HIPCHK(hipMemcpyAsync(p + o_cam, c.cam1, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(p + o_cam + sizeof(ReconCam) * b, c.cam2, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
-        a.cam1 = reinterpret_cast<const ReconCam *>(p + o_cam); a.cam2 = a.cam1 + b;
-    }
-    ReconPair *rp = reinterpret_cast<ReconPair *>(p + o_pair);
-    uint32_t *tcnt = reinterpret_cast<uint32_t *>(p + o_tcnt);
+    ReconPair *rp = cv.at<ReconPair>(o_pair);
+    uint32_t *tcnt = cv.at<uint32_t>(o_tcnt);
     hipLaunchKernelGGL(k_recon_count, dim3((unsigned)(b * nt)), dim3(RECON_THREADS), 0, s, a, tcnt);
     hipLaunchKernelGGL(k_recon_scan, dim3(c.batch), dim3(RECON_THREADS), 0, s, a, tcnt, rp, c.counts);
     if (a.p_max > 0)
@@ -2967,9 +3037,10 @@ int reconstruct_device(mdrp_handle *h, ReconCall &c, const mdrp_reconstruct_opt 
 }
 
 int reconstruct_call(mdrp_handle *h, ReconCall &c, const mdrp_reconstruct_opt *o) {
-    if (const char *why = recon_refusal(c, o)) { g_err = std::string(c.who) + ": " + why; return MDRP_ERR_INVALID; }
+    c.a.keep = o->keep; c.a.thr = o->thr; c.a.seed = (uint32_t)o->seed; c.a.p_max = o->p_max;
+    if (const char *why = recon_refusal(c)) { g_err = std::string(c.who) + ": " + why; return MDRP_ERR_INVALID; }
     MDRP_ENTER(h);
-    return reconstruct_device(h, c, o);
+    return reconstruct_device(h, c);
 }
 
 } // namespace
@@ -2979,11 +3050,8 @@ extern "C" {
 int mdrp_reconstruct_pairs_async(mdrp_handle *h, int kind, const mdrp_depth_pairs *dp, const mdrp_reconstruct_opt *opt, int batch, const void *models_dev,
                                  int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, float *points, int32_t *pixel, int32_t *counts) {
     if (!h || !dp || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    ReconCall c{"mdrp_reconstruct_pairs_async", {}, batch, cam1, cam2, points, pixel, counts};
-    ReconArgs &a = c.a;
-    a.depth1 = dp->depth1; a.depth2 = dp->depth2; a.center1 = dp->center1; a.center2 = dp->center2;
-    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = dp->depth_type; a.kind = kind;
-    a.h1 = dp->h1; a.w1 = dp->w1; a.h2 = dp->h2; a.w2 = dp->w2;
+    ReconCall c = recon_call("mdrp_reconstruct_pairs_async", kind, batch, models_dev, model_stride, cam1, cam2, points, pixel, counts);
+    recon_flatten(c.a, dp);
     return reconstruct_call(h, c, opt);
 }
 
@@ -2992,12 +3060,8 @@ int mdrp_reconstruct_image_pairs_async(mdrp_handle *h, int kind, const mdrp_dept
                                        int32_t *pixel, int32_t *counts) {
     if (!h || !ip || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (batch > 0 && !ip->pairs) { g_err = "mdrp_reconstruct_image_pairs_async: NULL pairs"; return MDRP_ERR_INVALID; }
-    ReconCall c{"mdrp_reconstruct_image_pairs_async", {}, batch, cam1, cam2, points, pixel, counts};
-    ReconArgs &a = c.a;
-    a.depth1 = a.depth2 = ip->n_images > 0 ? ip->depth : ip; // (an empty set: no map is read; the pointer only has to pass for one)
-    a.center1 = a.center2 = ip->center; a.size = ip->size; a.pairs = ip->pairs; a.n_images = ip->n_images;
-    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = ip->depth_type; a.kind = kind;
-    a.h1 = a.h2 = ip->h_max; a.w1 = a.w2 = ip->w_max;
+    ReconCall c = recon_call("mdrp_reconstruct_image_pairs_async", kind, batch, models_dev, model_stride, cam1, cam2, points, pixel, counts);
+    recon_flatten(c.a, ip);
     return reconstruct_call(h, c, opt);
 }
 
@@ -3016,8 +3080,8 @@ static_assert(sizeof(mdrp_scene_transform) == 128 && sizeof(SceneTransform) == 1
 const char *scene_tree_refusal(const SceneTree &t) {
     if (t.batch < 0) return "negative batch";
     if (t.n_images < 0) return "negative n_images";
-    if (t.kind < MDRP_CALIB || t.kind > MDRP_VARYING_FOCAL) return "only the monodepth estimators' models (kind 0..2) have depths to unproject";
-    if (t.model_stride < RECON_MODEL_BYTES || t.model_stride % 8 != 0) return "model_stride must be at least 96 and a multiple of 8";
+    if (const char *why = recon_kind_refusal(t.kind)) return why;
+    if (const char *why = recon_stride_refusal(t.model_stride)) return why;
     if (t.n_images > 0 && !t.tree) return "NULL tree_dev";
     if (t.n_images > 0 && t.batch > 0 && (!t.models || !t.pairs)) return "NULL models_dev or pairs";
     return nullptr;
@@ -3053,48 +3117,40 @@ int mdrp_reconstruct_scene_async(mdrp_handle *h, int kind, const mdrp_depth_imag
     const SceneTree t{static_cast<const unsigned char *>(models_dev), ip->pairs, tree_dev, model_stride, kind, batch, n};
     const int64_t px = (int64_t)ip->h_max * ip->w_max;
     const auto refusal = [&]() -> const char * {
-        if (const char *why = scene_tree_refusal(t)) return why;
+        const char *why;
+        if ((why = scene_tree_refusal(t))) return why;
         if (kind == MDRP_CALIB && n > 0 && !cams_host) return "MDRP_CALIB needs cams_host, one record per image";
-        if (kind != MDRP_CALIB && cams_host) return "cameras are MDRP_CALIB's: a focal kind unprojects with the model's focals (pass NULL)";
-        if (ip->depth_type != MDRP_F32 && ip->depth_type != MDRP_F64) return "depth_type must be MDRP_F32 or MDRP_F64";
-        if (opt->keep != MDRP_KEEP_NOT_INF && opt->keep != MDRP_KEEP_FINITE) return "keep must be MDRP_KEEP_NOT_INF or MDRP_KEEP_FINITE";
-        if (opt->thr == 0) return "thr == 0 keeps nothing (1 .. MDRP_RECON_ALL)";
-        if (opt->p_max < 0) return "negative p_max";
-        if (ip->h_max < 0 || ip->w_max < 0) return "negative size";
-        if (ip->h_max > MDRP_RECON_MAX_EXTENT || ip->w_max > MDRP_RECON_MAX_EXTENT) return "extent above MDRP_RECON_MAX_EXTENT (65536)";
-        if (px > INT32_MAX) return "a map of 2^31 pixels or more";
+        if ((why = recon_focal_cameras_refusal(kind, cams_host != nullptr))) return why;
+        if ((why = recon_option_refusal(ip->depth_type, opt->keep, opt->thr, opt->p_max))) return why;
+        if ((why = recon_extent_refusal(ip->h_max, ip->w_max, ip->h_max, ip->w_max, n))) return why; // (n >= 0: the tree's refusals)
         if (!offsets) return "NULL offsets";
         if (opt->p_max > 0 && (!points || !pixel)) return "NULL points or pixel";
         if (n > 0 && px > 0 && !ip->depth) return "NULL depth map";
-        if (kind == MDRP_CALIB)
-            for (int i = 0; i < n; ++i)
-                if ((cams_host[i].model_id | 1) != 1) return "only SIMPLE_PINHOLE (0) and PINHOLE (1) cameras unproject here";
-        return nullptr;
+        return kind == MDRP_CALIB ? recon_camera_models_refusal(cams_host, n) : nullptr;
     };
     if (const char *why = refusal()) { g_err = std::string("mdrp_reconstruct_scene_async: ") + why; return MDRP_ERR_INVALID; }
     SceneArgs a{};
     a.depth = ip->depth; a.center = ip->center; a.size = ip->size; a.depth_type = ip->depth_type; a.keep = opt->keep; a.n_images = n;
     a.h = ip->h_max; a.w = ip->w_max; a.thr = opt->thr; a.seed = (uint32_t)opt->seed; a.p_max = opt->p_max;
-    a.nt = (int)std::max<int64_t>(1, (px + RECON_TILE - 1) / RECON_TILE); // (a map without pixels: one empty tile)
+    a.nt = recon_tiles(a.h, a.w);
     const size_t tiles = (size_t)n * (size_t)a.nt, nfill = ((size_t)a.p_max + RECON_TILE - 1) / RECON_TILE;
     if (tiles + nfill > (size_t)INT32_MAX) { g_err = "mdrp_reconstruct_scene_async: the scene's tiles above 2^31 - 1: split the scene"; return MDRP_ERR_INVALID; }
     MDRP_ENTER(h);
-    // The scratch is one buffer of the handle, carved for this call's sizes; every word of it that a kernel reads was written by this call.
-    size_t total = 0;
-    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
-    const size_t o_T = carve(transforms_dev ? 0 : sizeof(SceneTransform) * (size_t)n), o_im = carve(sizeof(SceneImage) * (size_t)n),
-                 o_cam = carve(kind == MDRP_CALIB ? sizeof(ReconCam) * (size_t)n : 0), o_tcnt = carve(sizeof(uint32_t) * tiles);
-    if (int rc = h->sc_scratch.ensure(std::max<size_t>(total, 16))) return rc;
-    unsigned char *p = h->sc_scratch.as<unsigned char>();
+    // The scratch is the back end's buffer of the handle, carved for this call's sizes (at least 16 bytes: an empty scene still launches on it); every
+    // word of it that a kernel reads was written by this call.
+    Carve cv;
+    const size_t o_T = cv.take(transforms_dev ? 0 : sizeof(SceneTransform) * (size_t)n), o_im = cv.take(sizeof(SceneImage) * (size_t)n),
+                 o_cam = cv.take(kind == MDRP_CALIB ? sizeof(ReconCam) * (size_t)n : 0), o_tcnt = cv.take(sizeof(uint32_t) * tiles);
+    if (int rc = cv.ensure(h->be_scratch, 16)) return rc;
     hipStream_t s = h->stream;
     const ReconCam *cams = nullptr;
-    if (kind == MDRP_CALIB && n > 0) { // pageable: the copy has left the caller's table when hipMemcpyAsync returns
-        HIPCHK(hipMemcpyAsync(p + o_cam, cams_host, sizeof(ReconCam) * (size_t)n, hipMemcpyHostToDevice, s));
-        cams = reinterpret_cast<const ReconCam *>(p + o_cam);
+    if (kind == MDRP_CALIB && n > 0) {
+        if (int rc = upload_cameras(h, cv.at<ReconCam>(o_cam), cams_host, nullptr, (size_t)n)) return rc;
+        cams = cv.at<ReconCam>(o_cam);
     }
-    SceneTransform *T = transforms_dev ? reinterpret_cast<SceneTransform *>(transforms_dev) : reinterpret_cast<SceneTransform *>(p + o_T);
-    SceneImage *im = reinterpret_cast<SceneImage *>(p + o_im);
-    uint32_t *tcnt = reinterpret_cast<uint32_t *>(p + o_tcnt);
+    SceneTransform *T = transforms_dev ? reinterpret_cast<SceneTransform *>(transforms_dev) : cv.at<SceneTransform>(o_T);
+    SceneImage *im = cv.at<SceneImage>(o_im);
+    uint32_t *tcnt = cv.at<uint32_t>(o_tcnt);
     if (n > 0) {
         scene_chain_launch(s, t, cams, T, im);
         hipLaunchKernelGGL(k_scene_count, dim3((unsigned)tiles), dim3(RECON_THREADS), 0, s, a, (const SceneTransform *)T, tcnt);
@@ -3118,37 +3174,25 @@ static_assert(MDRP_COVIS_SAMPLED == COVIS_SAMPLED && MDRP_COVIS_FRONT == COVIS_F
               MDRP_COVIS_SLOTS == COVIS_SLOTS, "values of the header and of the kernels");
 static_assert(sizeof(mdrp_covis_opt) == 32 && offsetof(mdrp_covis_opt, seed) == 8 && offsetof(mdrp_covis_opt, lo) == 16 && offsetof(mdrp_covis_opt, hi) == 24, "option layout");
 
-// Both entry points behind their descriptors: the back end's refusals (a cloud of no rows), the tolerance's, then the two kernels on the handle's
-// stream.  The scratch is one buffer of the handle, carved for this call's sizes; every word of it that a kernel reads was written by this call.
+// Both entry points behind their descriptors: the two-view back end's refusals on this call's own values (a cloud of no rows that keeps the finite
+// depths), the tolerance's, then the two kernels on the handle's stream.  The scratch is the back end's buffer of the handle, carved for this call's
+// sizes; every word of it that a kernel reads was written by this call.
 int covis_call(mdrp_handle *h, ReconCall &c, const mdrp_covis_opt *o) {
-    const mdrp_reconstruct_opt ro{MDRP_KEEP_FINITE, o->thr, o->seed, 0, 0};
-    const char *why = recon_refusal(c, &ro);
-    if (!why && !(std::isfinite(o->lo) && std::isfinite(o->hi) && o->lo >= 0.0 && o->lo <= 1.0 && o->hi >= 1.0)) why = "lo and hi must be finite with 0 <= lo <= 1 <= hi";
     ReconArgs &a = c.a;
-    a.keep = RECON_KEEP_FINITE; a.thr = o->thr; a.seed = (uint32_t)o->seed; a.p_max = 0; a.nfill = 0;
-    const auto tiles = [](int hh, int ww) { return (int)std::max<int64_t>(1, ((int64_t)hh * ww + RECON_TILE - 1) / RECON_TILE); }; // (a map without pixels: one empty tile)
-    const size_t b = (size_t)std::max(c.batch, 0);
-    size_t nt = 0;
-    if (!why) {
-        a.nt1 = tiles(a.h1, a.w1); a.nt2 = tiles(a.h2, a.w2);
-        nt = (size_t)a.nt1 + a.nt2;
-        if (b * nt > (size_t)INT32_MAX) why = "batch * tiles above 2^31 - 1: split the batch";
-    }
+    a.keep = RECON_KEEP_FINITE; a.thr = o->thr; a.seed = (uint32_t)o->seed; a.p_max = 0;
+    const char *why = recon_refusal(c);
+    if (!why && !(std::isfinite(o->lo) && std::isfinite(o->hi) && o->lo >= 0.0 && o->lo <= 1.0 && o->hi >= 1.0)) why = "lo and hi must be finite with 0 <= lo <= 1 <= hi";
+    if (!why) why = recon_tile_counts(c);
     if (why) { g_err = std::string(c.who) + ": " + why; return MDRP_ERR_INVALID; }
     MDRP_ENTER(h);
     if (c.batch == 0) return MDRP_OK;
-    size_t total = 0;
-    const auto carve = [&total](size_t bytes) { const size_t at = total; total += (bytes + 15) & ~(size_t)15; return at; };
-    const size_t o_pair = carve(sizeof(CovisPair) * b), o_cam = carve(a.kind == MDRP_CALIB ? sizeof(ReconCam) * 2 * b : 0);
-    if (int rc = h->cv_scratch.ensure(total)) return rc;
-    unsigned char *p = h->cv_scratch.as<unsigned char>();
+    const size_t b = (size_t)c.batch, nt = (size_t)a.nt1 + a.nt2;
+    Carve cv;
+    const size_t o_pair = cv.take(sizeof(CovisPair) * b), o_cam = cv.take(a.kind == MDRP_CALIB ? sizeof(ReconCam) * 2 * b : 0);
+    int rc;
+    if ((rc = cv.ensure(h->be_scratch)) || (rc = upload_pair_cameras(h, c, cv.at<ReconCam>(o_cam)))) return rc;
     hipStream_t s = h->stream;
-    if (a.kind == MDRP_CALIB) { // pageable: the copies have left the caller's tables when hipMemcpyAsync returns
-        HIPCHK(hipMemcpyAsync(p + o_cam, c.cam1, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(p + o_cam + sizeof(ReconCam) * b, c.cam2, sizeof(ReconCam) * b, hipMemcpyHostToDevice, s));
-        a.cam1 = reinterpret_cast<const ReconCam *>(p + o_cam); a.cam2 = a.cam1 + b;
-    }
-    CovisPair *cp = reinterpret_cast<CovisPair *>(p + o_pair);
+    CovisPair *cp = cv.at<CovisPair>(o_pair);
     hipLaunchKernelGGL(k_covis_pair, dim3((unsigned)((b + COVIS_PAIR_THREADS - 1) / COVIS_PAIR_THREADS)), dim3(COVIS_PAIR_THREADS), 0, s, a, c.batch, cp, c.counts);
     hipLaunchKernelGGL(k_covis_count, dim3((unsigned)(b * nt)), dim3(RECON_THREADS), 0, s, a, (const CovisPair *)cp, o->lo, o->hi, c.counts);
     HIPCHK(hipGetLastError());
@@ -3162,11 +3206,8 @@ extern "C" {
 int mdrp_covisibility_pairs_async(mdrp_handle *h, int kind, const mdrp_depth_pairs *dp, const mdrp_covis_opt *opt, int batch, const void *models_dev,
                                   int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, int32_t *counts) {
     if (!h || !dp || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    ReconCall c{"mdrp_covisibility_pairs_async", {}, batch, cam1, cam2, nullptr, nullptr, counts};
-    ReconArgs &a = c.a;
-    a.depth1 = dp->depth1; a.depth2 = dp->depth2; a.center1 = dp->center1; a.center2 = dp->center2;
-    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = dp->depth_type; a.kind = kind;
-    a.h1 = dp->h1; a.w1 = dp->w1; a.h2 = dp->h2; a.w2 = dp->w2;
+    ReconCall c = recon_call("mdrp_covisibility_pairs_async", kind, batch, models_dev, model_stride, cam1, cam2, nullptr, nullptr, counts);
+    recon_flatten(c.a, dp);
     return covis_call(h, c, opt);
 }
 
@@ -3174,12 +3215,8 @@ int mdrp_covisibility_image_pairs_async(mdrp_handle *h, int kind, const mdrp_dep
                                         const void *models_dev, int model_stride, const mdrp_camera *cam1, const mdrp_camera *cam2, int32_t *counts) {
     if (!h || !ip || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
     if (batch > 0 && !ip->pairs) { g_err = "mdrp_covisibility_image_pairs_async: NULL pairs"; return MDRP_ERR_INVALID; }
-    ReconCall c{"mdrp_covisibility_image_pairs_async", {}, batch, cam1, cam2, nullptr, nullptr, counts};
-    ReconArgs &a = c.a;
-    a.depth1 = a.depth2 = ip->n_images > 0 ? ip->depth : ip; // (an empty set: no map is read; the pointer only has to pass for one)
-    a.center1 = a.center2 = ip->center; a.size = ip->size; a.pairs = ip->pairs; a.n_images = ip->n_images;
-    a.models = static_cast<const unsigned char *>(models_dev); a.model_stride = model_stride; a.depth_type = ip->depth_type; a.kind = kind;
-    a.h1 = a.h2 = ip->h_max; a.w1 = a.w2 = ip->w_max;
+    ReconCall c = recon_call("mdrp_covisibility_image_pairs_async", kind, batch, models_dev, model_stride, cam1, cam2, nullptr, nullptr, counts);
+    recon_flatten(c.a, ip);
     return covis_call(h, c, opt);
 }
 

@@ -8,7 +8,7 @@
 //   k_covis_pair    a thread per pair: the pair's CovisPair (the ReconPair of mdrp_reconstruct.h, the focals of both sides, the scale) and its 16
 //                   counters cleared.  Every word the count kernel reads or adds to is written here, by this call.
 //   k_covis_count   a workgroup per tile of RECON_TILE consecutive pixels of one SOURCE image of one pair (image 1: direction 0, image 2: direction 1),
-//                   a lane per RECON_PER_LANE consecutive pixels, through recon_view and recon_lane with the stages 6 and 7.  A sampled pixel runs
+//                   a lane per RECON_PER_LANE consecutive pixels, through recon_side_lane with the stages 6 and 7.  A sampled pixel runs
 //                   C4-C6 with one gathered load of the target map; the seven class counts of a wavefront come from ballots and popcounts, and go to
 //                   the pair's counters by one integer atomicAdd per wavefront and non-zero class (integer sums do not depend on their order).
 // Nothing is proportional to B * h * w: the scratch is the pairs' records and the camera tables.
@@ -107,16 +107,15 @@ MDRP_GLOBAL __launch_bounds__(RECON_THREADS) void k_covis_count(ReconArgs a, con
     const int nt = a.nt1 + a.nt2;
     const size_t b = blockIdx.x / (uint32_t)nt;
     const int tile = (int)(blockIdx.x % (uint32_t)nt), tid = threadIdx.x, lane = tid & 63;
-    const int dir = tile >= a.nt1 ? 1 : 0, ts = dir ? tile - a.nt1 : tile;
-    const ReconView vw = recon_view(a, b, dir), tw = recon_view(a, b, 1 - dir);
-    const bool usable = vw.ok && recon_usable(reinterpret_cast<const double *>(a.models + b * (size_t)a.model_stride), a.kind); // uniform over the workgroup
-    const uint32_t npix = usable ? (uint32_t)vw.h * (uint32_t)vw.w : 0u;
+    ReconSideTile t;
     double d[RECON_PER_LANE];
     uint32_t vv[RECON_PER_LANE], uu[RECON_PER_LANE];
-    const unsigned kept = recon_lane(a, vw, dir, npix, (uint32_t)ts * RECON_TILE + (uint32_t)tid * RECON_PER_LANE, d, vv, uu, dir ? COVIS_STAGE_2 : COVIS_STAGE_1);
+    const unsigned kept = recon_side_lane(a, b, tile, tid, COVIS_STAGE_1, COVIS_STAGE_2, t, d, vv, uu);
+    const int dir = t.side; // (the source image's side is the direction)
+    const ReconView tw = recon_view(a, b, 1 - dir);
     const CovisPair &cp = cps[b];
-    const double *sc = usable ? (dir ? a.center2 : a.center1) : nullptr, *tc = usable ? (dir ? a.center1 : a.center2) : nullptr; // (an empty set has no row 0)
-    const double c0 = sc ? sc[2 * (size_t)vw.image] : 0.0, c1 = sc ? sc[2 * (size_t)vw.image + 1] : 0.0;
+    const double *sc = t.usable ? (dir ? a.center2 : a.center1) : nullptr, *tc = t.usable ? (dir ? a.center1 : a.center2) : nullptr; // (an empty set has no row 0)
+    const double c0 = sc ? sc[2 * (size_t)t.vw.image] : 0.0, c1 = sc ? sc[2 * (size_t)t.vw.image + 1] : 0.0;
     const double tc0 = tc ? tc[2 * (size_t)tw.image] : 0.0, tc1 = tc ? tc[2 * (size_t)tw.image + 1] : 0.0;
     const void *tmap = dir ? a.depth1 : a.depth2;
     const double shift_s = cp.p.s[dir].shift, shift_t = cp.p.s[1 - dir].shift;

@@ -13,6 +13,13 @@
 //                   (lane order is pixel order) + its place among its lane's own; it is unprojected, transformed (image 1), rounded and written
 //                   while it fits.  The workgroups behind the tiles write the filler behind the last written row.
 // Nothing is proportional to B * h * w but the tile counts (4 bytes per 1024 pixels).
+//
+// The pieces of the tile walk are shared with the scene kernels (mdrp_scene.h) and the co-visibility kernels (mdrp_covis.h): ReconWalk and recon_lane
+// (R2-R4 for a lane), recon_side_lane (a pair's tile to its side, view and walk), recon_tile_total and recon_tile_rank (the compaction through one
+// LDS word per wavefront), recon_fill (the filler) and recon_write_rows (the rows, around a functor for the point).  Two pieces stay where they were
+// (profiles/backend_refactor_disasm.txt).  The "cameras of pair b, or null" selection in k_recon_scan and k_covis_pair: every shared form that was
+// tried changed those kernels' registers.  The three-step scans of k_recon_scan (uint32, a barrier behind each side) and k_scene_scan (int64, one body
+// whose every step branches on the phase): a shared helper would take k_scene_scan's phase 0 out of that body and so change its code.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -170,39 +177,58 @@ __device__ __forceinline__ ReconView recon_view(const ReconArgs &a, size_t b, in
     return v;
 }
 
+// what the lane walk reads of a call: the map, its element type, R4's filter and R3's threshold, seed and stage
+struct ReconWalk {
+    const void *map;
+    int depth_type, keep;
+    uint32_t thr, seed, stage;
+};
+// ... of one side (or direction) of a two-view call, whose stage is stage1 or stage2
+__device__ __forceinline__ ReconWalk recon_walk(const ReconArgs &a, int side, uint32_t stage1, uint32_t stage2) {
+    return {side ? a.depth2 : a.depth1, a.depth_type, a.keep, a.thr, a.seed, side ? stage2 : stage1};
+}
+
 // R2-R4 for the RECON_PER_LANE consecutive pixels of a lane that start at pixel p0 of a view with npix pixels: bit j of the result is set iff pixel
-// p0 + j is kept; d[j], vv[j], uu[j] are its depth and coordinates.  One division per lane.  (own_stage: the scene kernels', mdrp_scene.h; 0 = the side's)
-__device__ __forceinline__ unsigned recon_lane(const ReconArgs &a, const ReconView &vw, int side, uint32_t npix, uint32_t p0, double d[RECON_PER_LANE],
-                                               uint32_t vv[RECON_PER_LANE], uint32_t uu[RECON_PER_LANE], uint32_t own_stage = 0) {
-    const void *map = side ? a.depth2 : a.depth1;
-    const uint32_t stage = own_stage ? own_stage : (side ? RECON_STAGE_2 : RECON_STAGE_1);
+// p0 + j is kept; d[j], vv[j], uu[j] are its depth and coordinates.  One division per lane.
+__device__ __forceinline__ unsigned recon_lane(const ReconWalk &k, const ReconView &vw, uint32_t npix, uint32_t p0, double d[RECON_PER_LANE],
+                                               uint32_t vv[RECON_PER_LANE], uint32_t uu[RECON_PER_LANE]) {
+    const void *map = k.map; // (both as locals: read through k inside the loop, the stage's product with the hash's constant is no longer folded)
+    const uint32_t stage = k.stage;
     unsigned kept = 0;
     if (p0 >= npix) return 0; // (npix > 0: w > 0)
     uint32_t v = p0 / (uint32_t)vw.w, u = p0 - v * (uint32_t)vw.w;
 #pragma unroll
     for (int j = 0; j < RECON_PER_LANE; ++j) {
         vv[j] = v; uu[j] = u; d[j] = 0.0;
-        if (p0 + (uint32_t)j < npix && recon_candidate(a.thr, a.seed, stage, v, u)) {
-            d[j] = dense_ld(map, a.depth_type, vw.base + (size_t)v * (size_t)vw.stride + (size_t)u);
-            if (recon_keep(d[j], a.keep)) kept |= 1u << j;
+        if (p0 + (uint32_t)j < npix && recon_candidate(k.thr, k.seed, stage, v, u)) {
+            d[j] = dense_ld(map, k.depth_type, vw.base + (size_t)v * (size_t)vw.stride + (size_t)u);
+            if (recon_keep(d[j], k.keep)) kept |= 1u << j;
         }
         if (++u == (uint32_t)vw.w) { u = 0; ++v; }
     }
     return kept;
 }
 
-MDRP_GLOBAL __launch_bounds__(RECON_THREADS) void k_recon_count(ReconArgs a, uint32_t *__restrict__ tcnt) {
-    __shared__ uint32_t s_wave[RECON_THREADS / 64];
-    const int nt = a.nt1 + a.nt2;
-    const size_t b = blockIdx.x / (uint32_t)nt;
-    const int tile = (int)(blockIdx.x % (uint32_t)nt), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int side = tile >= a.nt1 ? 1 : 0, ts = side ? tile - a.nt1 : tile;
-    const ReconView vw = recon_view(a, b, side);
-    const bool usable = vw.ok && recon_usable(reinterpret_cast<const double *>(a.models + b * (size_t)a.model_stride), a.kind); // uniform over the workgroup
-    const uint32_t npix = usable ? (uint32_t)vw.h * (uint32_t)vw.w : 0u;
-    double d[RECON_PER_LANE];
-    uint32_t vv[RECON_PER_LANE], uu[RECON_PER_LANE];
-    const unsigned kept = recon_lane(a, vw, side, npix, (uint32_t)ts * RECON_TILE + (uint32_t)tid * RECON_PER_LANE, d, vv, uu);
+// Tile `tile` of pair b, of the pair's nt1 tiles of image 1 and nt2 of image 2: its side, its view, whether the pair emits at all (R1; uniform over
+// the workgroup), and this lane's walk of it under the side's stage.
+struct ReconSideTile {
+    int side;
+    ReconView vw;
+    bool usable;
+};
+__device__ __forceinline__ unsigned recon_side_lane(const ReconArgs &a, size_t b, int tile, int tid, uint32_t stage1, uint32_t stage2, ReconSideTile &t,
+                                                    double d[RECON_PER_LANE], uint32_t vv[RECON_PER_LANE], uint32_t uu[RECON_PER_LANE]) {
+    t.side = tile >= a.nt1 ? 1 : 0;
+    const int ts = t.side ? tile - a.nt1 : tile;
+    t.vw = recon_view(a, b, t.side);
+    t.usable = t.vw.ok && recon_usable(reinterpret_cast<const double *>(a.models + b * (size_t)a.model_stride), a.kind);
+    const uint32_t npix = t.usable ? (uint32_t)t.vw.h * (uint32_t)t.vw.w : 0u;
+    return recon_lane(recon_walk(a, t.side, stage1, stage2), t.vw, npix, (uint32_t)ts * RECON_TILE + (uint32_t)tid * RECON_PER_LANE, d, vv, uu);
+}
+
+// The kept pixels of a tile from its lanes' masks, through s_wave (one word per wavefront): the count kernels' tail.  Thread 0 writes the sum to *out.
+__device__ __forceinline__ void recon_tile_total(unsigned kept, int tid, uint32_t *s_wave /*LDS, RECON_THREADS / 64*/, uint32_t *out) {
+    const int lane = tid & 63, wave = tid >> 6;
     uint32_t c = 0;
 #pragma unroll
     for (int j = 0; j < RECON_PER_LANE; ++j) c += (uint32_t)__popcll(__ballot((kept >> j) & 1u));
@@ -212,8 +238,67 @@ MDRP_GLOBAL __launch_bounds__(RECON_THREADS) void k_recon_count(ReconArgs a, uin
         uint32_t total = 0;
 #pragma unroll
         for (int w = 0; w < RECON_THREADS / 64; ++w) total += s_wave[w];
-        tcnt[b * (size_t)nt + tile] = total;
+        *out = total;
     }
+}
+
+// The kept pixels of the tile before this lane's own, through s_wave: lanes take consecutive runs of pixels, so lane order is pixel order.
+__device__ __forceinline__ uint32_t recon_tile_rank(unsigned kept, int tid, uint32_t *s_wave /*LDS, RECON_THREADS / 64*/) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t before = 0, c = 0;
+#pragma unroll
+    for (int j = 0; j < RECON_PER_LANE; ++j) {
+        const unsigned long long ball = __ballot((kept >> j) & 1u);
+        before += (uint32_t)__popcll(ball & below);
+        c += (uint32_t)__popcll(ball);
+    }
+    if (lane == 0) s_wave[wave] = c;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < RECON_THREADS / 64; ++w) before += w < wave ? s_wave[w] : 0u;
+    return before;
+}
+
+// A filler workgroup: the RECON_TILE rows from `first` on that lie behind the last written row and inside the cloud
+__device__ __forceinline__ void recon_fill(int64_t first, int tid, int64_t written, int64_t p_max, float *pts, int32_t *pix) {
+#pragma unroll
+    for (int j = 0; j < RECON_PER_LANE; ++j) {
+        const int64_t r = first + (int64_t)j * RECON_THREADS + tid;
+        if (r >= written && r < p_max) {
+            pts[3 * r] = 0.0f; pts[3 * r + 1] = 0.0f; pts[3 * r + 2] = 0.0f;
+            pix[r] = -1;
+        }
+    }
+}
+
+// A lane's kept pixels to the rows from `row` on, written while they fit (the counts stay the true ones).  point(v, u, d, out[3]): R5 and R6 (or the
+// scene's S5 and S6) of one pixel, rounded here to float32; stride: the row stride of the pixel's map.
+template <typename Point>
+__device__ __forceinline__ void recon_write_rows(unsigned kept, int64_t row, int64_t p_max, const uint32_t vv[RECON_PER_LANE], const uint32_t uu[RECON_PER_LANE],
+                                                 const double d[RECON_PER_LANE], int stride, Point point, float *pts, int32_t *pix) {
+#pragma unroll
+    for (int j = 0; j < RECON_PER_LANE; ++j) {
+        if (!((kept >> j) & 1u)) continue;
+        if (row < p_max) {
+            double o[3];
+            point(vv[j], uu[j], d[j], o);
+            pts[3 * row] = (float)o[0]; pts[3 * row + 1] = (float)o[1]; pts[3 * row + 2] = (float)o[2];
+            pix[row] = (int32_t)(vv[j] * (uint32_t)stride + uu[j]);
+        }
+        ++row;
+    }
+}
+
+MDRP_GLOBAL __launch_bounds__(RECON_THREADS) void k_recon_count(ReconArgs a, uint32_t *__restrict__ tcnt) {
+    __shared__ uint32_t s_wave[RECON_THREADS / 64];
+    const int nt = a.nt1 + a.nt2;
+    const size_t b = blockIdx.x / (uint32_t)nt;
+    const int tile = (int)(blockIdx.x % (uint32_t)nt), tid = threadIdx.x;
+    ReconSideTile t;
+    double d[RECON_PER_LANE];
+    uint32_t vv[RECON_PER_LANE], uu[RECON_PER_LANE];
+    recon_tile_total(recon_side_lane(a, b, tile, tid, RECON_STAGE_1, RECON_STAGE_2, t, d, vv, uu), tid, s_wave, tcnt + (b * (size_t)nt + tile));
 }
 
 // One workgroup per pair.  Each image's tile counts to their exclusive running sum in place, as k_dense_scan sums its blocks: a thread sums its run
@@ -260,60 +345,29 @@ MDRP_GLOBAL __launch_bounds__(RECON_THREADS) void k_recon_emit(ReconArgs a, cons
                                                               const int32_t *__restrict__ counts, float *__restrict__ points, int32_t *__restrict__ pixel) {
     const int nt = a.nt1 + a.nt2, per_pair = nt + a.nfill;
     const size_t b = blockIdx.x / (uint32_t)per_pair;
-    const int tile = (int)(blockIdx.x % (uint32_t)per_pair), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = (int)(blockIdx.x % (uint32_t)per_pair), tid = threadIdx.x;
     const int64_t n1 = counts[2 * b], n2 = counts[2 * b + 1], p_max = a.p_max;
     const int64_t start2 = n1 < p_max ? n1 : p_max; // image 2's first row
     float *pts = points + b * (size_t)a.p_max * 3;
     int32_t *pix = pixel + b * (size_t)a.p_max;
     if (tile >= nt) { // the filler behind the last written row
-        const int64_t written = start2 + (n2 < p_max - start2 ? n2 : p_max - start2);
-#pragma unroll
-        for (int j = 0; j < RECON_PER_LANE; ++j) {
-            const int64_t r = (int64_t)(tile - nt) * RECON_TILE + (int64_t)j * RECON_THREADS + tid;
-            if (r >= written && r < p_max) {
-                pts[3 * r] = 0.0f; pts[3 * r + 1] = 0.0f; pts[3 * r + 2] = 0.0f;
-                pix[r] = -1;
-            }
-        }
+        recon_fill((int64_t)(tile - nt) * RECON_TILE, tid, start2 + (n2 < p_max - start2 ? n2 : p_max - start2), p_max, pts, pix);
         return;
     }
     __shared__ uint32_t s_wave[RECON_THREADS / 64];
-    const int side = tile >= a.nt1 ? 1 : 0, ts = side ? tile - a.nt1 : tile;
-    const ReconView vw = recon_view(a, b, side);
-    const bool usable = vw.ok && recon_usable(reinterpret_cast<const double *>(a.models + b * (size_t)a.model_stride), a.kind);
-    const uint32_t npix = usable ? (uint32_t)vw.h * (uint32_t)vw.w : 0u;
+    ReconSideTile t;
     double d[RECON_PER_LANE];
     uint32_t vv[RECON_PER_LANE], uu[RECON_PER_LANE];
-    const unsigned kept = recon_lane(a, vw, side, npix, (uint32_t)ts * RECON_TILE + (uint32_t)tid * RECON_PER_LANE, d, vv, uu);
-    // the kept pixels of the lower lanes: lanes take consecutive runs of pixels, so lane order is pixel order
-    const unsigned long long below = (1ull << lane) - 1ull;
-    uint32_t before = 0, c = 0;
-#pragma unroll
-    for (int j = 0; j < RECON_PER_LANE; ++j) {
-        const unsigned long long ball = __ballot((kept >> j) & 1u);
-        before += (uint32_t)__popcll(ball & below);
-        c += (uint32_t)__popcll(ball);
-    }
-    if (lane == 0) s_wave[wave] = c;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < RECON_THREADS / 64; ++w) before += w < wave ? s_wave[w] : 0u;
+    const unsigned kept = recon_side_lane(a, b, tile, tid, RECON_STAGE_1, RECON_STAGE_2, t, d, vv, uu);
+    const uint32_t before = recon_tile_rank(kept, tid, s_wave);
     if (!kept) return;
-    int64_t row = (side ? start2 : 0) + (int64_t)tcnt[b * (size_t)nt + tile] + (int64_t)before;
+    const int side = t.side;
+    const int64_t row = (side ? start2 : 0) + (int64_t)tcnt[b * (size_t)nt + tile] + (int64_t)before;
     const ReconPair &p = rp[b];
-    const double c0 = (side ? a.center2 : a.center1) ? (side ? a.center2 : a.center1)[2 * (size_t)vw.image] : 0.0;
-    const double c1 = (side ? a.center2 : a.center1) ? (side ? a.center2 : a.center1)[2 * (size_t)vw.image + 1] : 0.0;
-#pragma unroll
-    for (int j = 0; j < RECON_PER_LANE; ++j) {
-        if (!((kept >> j) & 1u)) continue;
-        if (row < p_max) { // rows are written while they fit; the counts stay the true ones
-            double o[3];
-            recon_point(p, side, vv[j], uu[j], c0, c1, d[j], o);
-            pts[3 * row] = (float)o[0]; pts[3 * row + 1] = (float)o[1]; pts[3 * row + 2] = (float)o[2];
-            pix[row] = (int32_t)(vv[j] * (uint32_t)vw.stride + uu[j]);
-        }
-        ++row;
-    }
+    const double *ctr = side ? a.center2 : a.center1;
+    const double c0 = ctr ? ctr[2 * (size_t)t.vw.image] : 0.0, c1 = ctr ? ctr[2 * (size_t)t.vw.image + 1] : 0.0;
+    const auto point = [&p, side, c0, c1](uint32_t v, uint32_t u, double dd, double o[3]) { recon_point(p, side, v, u, c0, c1, dd, o); };
+    recon_write_rows(kept, row, p_max, vv, uu, d, t.vw.stride, point, pts, pix);
 }
 
 #endif // __HIPCC__

@@ -177,7 +177,7 @@ MDRP_GLOBAL __launch_bounds__(SCENE_CHAIN_THREADS) void k_scene_chain(SceneTree 
     if (im) im[i] = scene_image(t, s.kind, cams ? cams + i : nullptr);
 }
 
-// the view of one image of the set (an image that emits nothing has no pixels) and the lane walk's arguments for it
+// the view of one image of the set (an image that emits nothing has no pixels)
 __device__ __forceinline__ ReconView scene_view(const SceneArgs &a, size_t image, bool attached) {
     ReconView v;
     v.ok = attached; v.image = (int)image; v.stride = a.w;
@@ -186,34 +186,22 @@ __device__ __forceinline__ ReconView scene_view(const SceneArgs &a, size_t image
     v.base = image * (size_t)a.h * (size_t)a.w;
     return v;
 }
-__device__ __forceinline__ ReconArgs scene_lane_args(const SceneArgs &a, size_t image) {
-    ReconArgs r = {};
-    r.depth1 = a.depth; r.depth_type = a.depth_type; r.keep = a.keep; r.thr = a.thr;
-    r.seed = scene_seed(a.seed, (uint32_t)image);
-    return r;
+// this lane's walk of tile `tile` of an image under S3's seed and the scene's stage; vw: the image's view
+__device__ __forceinline__ unsigned scene_lane(const SceneArgs &a, size_t image, int tile, int tid, bool attached, ReconView &vw, double d[RECON_PER_LANE],
+                                               uint32_t vv[RECON_PER_LANE], uint32_t uu[RECON_PER_LANE]) {
+    vw = scene_view(a, image, attached);
+    const ReconWalk k = {a.depth, a.depth_type, a.keep, a.thr, scene_seed(a.seed, (uint32_t)image), SCENE_STAGE};
+    return recon_lane(k, vw, (uint32_t)vw.h * (uint32_t)vw.w, (uint32_t)tile * RECON_TILE + (uint32_t)tid * RECON_PER_LANE, d, vv, uu);
 }
 
 MDRP_GLOBAL __launch_bounds__(RECON_THREADS) void k_scene_count(SceneArgs a, const SceneTransform *__restrict__ T, uint32_t *__restrict__ tcnt) {
     __shared__ uint32_t s_wave[RECON_THREADS / 64];
     const size_t image = blockIdx.x / (uint32_t)a.nt;
-    const int tile = (int)(blockIdx.x % (uint32_t)a.nt), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const ReconView vw = scene_view(a, image, T[image].depth >= 0); // uniform over the workgroup
-    const ReconArgs ra = scene_lane_args(a, image);
-    const uint32_t npix = (uint32_t)vw.h * (uint32_t)vw.w;
+    const int tile = (int)(blockIdx.x % (uint32_t)a.nt), tid = threadIdx.x;
+    ReconView vw;
     double d[RECON_PER_LANE];
     uint32_t vv[RECON_PER_LANE], uu[RECON_PER_LANE];
-    const unsigned kept = recon_lane(ra, vw, 0, npix, (uint32_t)tile * RECON_TILE + (uint32_t)tid * RECON_PER_LANE, d, vv, uu, SCENE_STAGE);
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < RECON_PER_LANE; ++j) c += (uint32_t)__popcll(__ballot((kept >> j) & 1u));
-    if (lane == 0) s_wave[wave] = c;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t total = 0;
-#pragma unroll
-        for (int w = 0; w < RECON_THREADS / 64; ++w) total += s_wave[w];
-        tcnt[blockIdx.x] = total;
-    }
+    recon_tile_total(scene_lane(a, image, tile, tid, T[image].depth >= 0, vw, d, vv, uu), tid, s_wave, tcnt + blockIdx.x); // (attached: uniform over the workgroup)
 }
 
 // The running sums, as k_recon_scan takes its tiles': a thread sums its run of consecutive values, thread 0 scans the run totals, the thread walks its
@@ -252,58 +240,28 @@ MDRP_GLOBAL __launch_bounds__(RECON_THREADS) void k_scene_emit(SceneArgs a, cons
                                                               const SceneImage *__restrict__ im, const int64_t *__restrict__ offsets,
                                                               float *__restrict__ points, int32_t *__restrict__ pixel) {
     const uint32_t tiles = (uint32_t)a.n_images * (uint32_t)a.nt; // (fits: the entry point checks the grid)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t p_max = a.p_max;
     if (blockIdx.x >= tiles) { // the filler behind the last written row
-        const int64_t all = offsets[a.n_images], written = all < p_max ? all : p_max;
-#pragma unroll
-        for (int j = 0; j < RECON_PER_LANE; ++j) {
-            const int64_t r = (int64_t)(blockIdx.x - tiles) * RECON_TILE + (int64_t)j * RECON_THREADS + tid;
-            if (r >= written && r < p_max) {
-                points[3 * r] = 0.0f; points[3 * r + 1] = 0.0f; points[3 * r + 2] = 0.0f;
-                pixel[r] = -1;
-            }
-        }
+        const int64_t all = offsets[a.n_images];
+        recon_fill((int64_t)(blockIdx.x - tiles) * RECON_TILE, tid, all < p_max ? all : p_max, p_max, points, pixel);
         return;
     }
     __shared__ uint32_t s_wave[RECON_THREADS / 64];
     const size_t image = blockIdx.x / (uint32_t)a.nt;
     const int tile = (int)(blockIdx.x % (uint32_t)a.nt);
     const SceneTransform &t = T[image];
-    const ReconView vw = scene_view(a, image, t.depth >= 0);
-    const ReconArgs ra = scene_lane_args(a, image);
-    const uint32_t npix = (uint32_t)vw.h * (uint32_t)vw.w;
+    ReconView vw;
     double d[RECON_PER_LANE];
     uint32_t vv[RECON_PER_LANE], uu[RECON_PER_LANE];
-    const unsigned kept = recon_lane(ra, vw, 0, npix, (uint32_t)tile * RECON_TILE + (uint32_t)tid * RECON_PER_LANE, d, vv, uu, SCENE_STAGE);
-    // the kept pixels of the lower lanes: lanes take consecutive runs of pixels, so lane order is pixel order
-    const unsigned long long below = (1ull << lane) - 1ull;
-    uint32_t before = 0, c = 0;
-#pragma unroll
-    for (int j = 0; j < RECON_PER_LANE; ++j) {
-        const unsigned long long ball = __ballot((kept >> j) & 1u);
-        before += (uint32_t)__popcll(ball & below);
-        c += (uint32_t)__popcll(ball);
-    }
-    if (lane == 0) s_wave[wave] = c;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < RECON_THREADS / 64; ++w) before += w < wave ? s_wave[w] : 0u;
+    const unsigned kept = scene_lane(a, image, tile, tid, t.depth >= 0, vw, d, vv, uu);
+    const uint32_t before = recon_tile_rank(kept, tid, s_wave);
     if (!kept) return;
-    int64_t row = offsets[image] + (int64_t)tcnt[blockIdx.x] + (int64_t)before;
+    const int64_t row = offsets[image] + (int64_t)tcnt[blockIdx.x] + (int64_t)before;
     const SceneImage &si = im[image];
     const double c0 = a.center ? a.center[2 * image] : 0.0, c1 = a.center ? a.center[2 * image + 1] : 0.0;
-#pragma unroll
-    for (int j = 0; j < RECON_PER_LANE; ++j) {
-        if (!((kept >> j) & 1u)) continue;
-        if (row < p_max) { // rows are written while they fit; the offsets stay the true ones
-            double o[3];
-            scene_point(t, si, vv[j], uu[j], c0, c1, d[j], o);
-            points[3 * row] = (float)o[0]; points[3 * row + 1] = (float)o[1]; points[3 * row + 2] = (float)o[2];
-            pixel[row] = (int32_t)(vv[j] * (uint32_t)vw.stride + uu[j]);
-        }
-        ++row;
-    }
+    const auto point = [&](uint32_t v, uint32_t u, double dd, double o[3]) { scene_point(t, si, v, u, c0, c1, dd, o); };
+    recon_write_rows(kept, row, p_max, vv, uu, d, vw.stride, point, points, pixel);
 }
 
 #endif // __HIPCC__

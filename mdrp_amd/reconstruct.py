@@ -67,17 +67,93 @@ def _models(models, B, dev, h):
     return _pl._model_tensor(models, B, dev, "models"), _capi.MODEL_DTYPE.itemsize
 
 
-def _run(k, desc, opt, B, dev, models, cams1, cams2, keep_alive):
+def _focal_kind_cameras(verb):
+    return ValueError(f"cameras are the calibrated kind's: a focal kind {verb} with the model's focals")
+
+
+def _stage_pairs(kind, depth_map1, depth_map2, cameras1, cameras2, center1, center2, options, verb="unprojects"):
+    """The per-pair form checked and staged: (k, desc, opt, B, dev, cams1, cams2, keep_alive).  options(pixels) -> the call's option record, made
+    between the checks of the maps and of the cameras; verb: what a focal kind does with its focals, for the exception."""
+    k = _pl._monodepth_kind(kind)
+    dev = _pl._check_on_gpu({"depth_map1": depth_map1, "depth_map2": depth_map2})
+    _pl._check_float_pair(depth_map1, depth_map2, "depth maps")
+    if depth_map1.dim() != 3 or depth_map2.dim() != 3 or depth_map1.shape[0] != depth_map2.shape[0]:
+        raise ValueError("depth maps must have shape (B, H, W) with one B")
+    B = int(depth_map1.shape[0])
+    (h1, w1), (h2, w2) = (int(v) for v in depth_map1.shape[1:]), (int(v) for v in depth_map2.shape[1:])
+    _check_maps(h1, w1); _check_maps(h2, w2)
+    opt = options(h1 * w1 + h2 * w2)
+    cams1 = cams2 = None
+    if k == _capi.CALIB:
+        cams1, cams2 = _pl._camera_records(cameras1, B), _pl._camera_records(cameras2, B)
+    elif cameras1 is not None or cameras2 is not None:
+        raise _focal_kind_cameras(verb)
+    dm1, dm2 = depth_map1.contiguous(), depth_map2.contiguous()
+    c1, c2 = _pl._center(center1, B, dev), _pl._center(center2, B, dev)
+    desc = _capi.DepthPairs(dm1.data_ptr(), dm2.data_ptr(), _pl._float_types()[dm1.dtype], h1, w1, h2, w2, 0, _pl._data_ptr(c1), _pl._data_ptr(c2))
+    return k, desc, opt, B, dev, cams1, cams2, (dm1, dm2, c1, c2)
+
+
+def _stage_images(depth_maps, centers, sizes, pairs_ptr):
+    """The image part of the per-image form staged - the checked maps, the centres and the sizes - around the pairs' device pointer:
+    (desc, keep_alive)"""
     import torch
+    dev = depth_maps.device
+    I, H, W = (int(v) for v in depth_maps.shape)
+    dm = depth_maps.contiguous()
+    cs = _pl._per_image(centers, torch.float64, (I, 2), "centers", dev)
+    sz = _pl._per_image(sizes, torch.int32, (I, 2), "sizes", dev)
+    desc = _capi.DepthImagePairs(dm.data_ptr(), _pl._float_types()[dm.dtype], H, W, I, _pl._data_ptr(sz), _pl._data_ptr(cs), pairs_ptr)
+    return desc, (dm, cs, sz)
+
+
+def _check_image_maps(depth_maps):
+    """(dev, I, H, W) of the per-image form's maps"""
+    dev = _pl._check_on_gpu({"depth_maps": depth_maps})
+    if depth_maps.dtype not in _pl._float_types():
+        raise ValueError("depth maps must be float32 or float64")
+    if depth_maps.dim() != 3:
+        raise ValueError("depth maps must have shape (I, H, W)")
+    I, H, W = (int(v) for v in depth_maps.shape)
+    _check_maps(H, W)
+    return dev, I, H, W
+
+
+def _stage_image_pairs(kind, depth_maps, pairs, cameras, centers, sizes, options, verb="unprojects"):
+    """_stage_pairs for the per-image form: the cameras are per image and expanded to per-pair records by pairs on the host."""
+    k = _pl._monodepth_kind(kind)
+    dev, I, H, W = _check_image_maps(depth_maps)
+    on_device, host_pairs, B = _pl._pairs_on_host(pairs, dev, k == _capi.CALIB)
+    B = int(B)
+    opt = options(2 * H * W)
+    cams1 = cams2 = None
+    if k == _capi.CALIB:
+        cams1, cams2 = _pl._pair_cameras(cameras, host_pairs, I)
+    elif cameras is not None:
+        raise _focal_kind_cameras(verb)
+    pr = _pl._pairs_on_device(pairs, on_device, host_pairs, dev)
+    desc, keep_alive = _stage_images(depth_maps, centers, sizes, pr.data_ptr())
+    return k, desc, opt, B, dev, cams1, cams2, keep_alive + (pr,)
+
+
+def _run(staged, models, outputs, method):
+    """One two-view device call on staged = what _stage_pairs returns.  outputs(B, opt, dev) -> the output tensors, allocated under the device;
+    method(handle) -> the handle's entry point, called with the tensors' pointers between the model records and the cameras."""
+    import torch
+    k, desc, opt, B, dev, cams1, cams2, keep_alive = staged
     h = _pl._handle_on(dev)
     with torch.cuda.device(dev):
         rec, stride = _models(models, B, dev, h)
-        points = torch.empty((B, opt.p_max, 3), dtype=torch.float32, device=dev)
-        pixel = torch.empty((B, opt.p_max), dtype=torch.int32, device=dev)
-        counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        h.reconstruct_pairs_device(k, desc, opt, B, rec.data_ptr(), stride, points.data_ptr(), pixel.data_ptr(), counts.data_ptr(), cams1, cams2)
-    del rec, keep_alive  # (queued on the current stream, where torch's allocator orders the reuse of their memory behind the call)
-    return points, pixel, counts
+        out = outputs(B, opt, dev)
+        method(h)(k, desc, opt, B, rec.data_ptr(), stride, *(t.data_ptr() for t in out), cams1, cams2)
+    del rec, keep_alive, staged  # (queued on the current stream, where torch's allocator orders the reuse of their memory behind the call)
+    return out
+
+
+def _cloud(B, opt, dev):
+    import torch
+    return (torch.empty((B, opt.p_max, 3), dtype=torch.float32, device=dev), torch.empty((B, opt.p_max), dtype=torch.int32, device=dev),
+            torch.empty((B, 2), dtype=torch.int32, device=dev))
 
 
 def reconstruct_pairs_torch(kind, models, depth_map1, depth_map2, cameras1=None, cameras2=None, center1=None, center2=None, rate=0.05, seed=0,
@@ -94,24 +170,8 @@ def reconstruct_pairs_torch(kind, models, depth_map1, depth_map2, cameras1=None,
     Returns (points (B, p_max, 3) float32: image 1's kept pixels in row-major order, in camera 2's frame, then image 2's; pixel (B, p_max) int32:
     v * W + u of every row in its own map, -1 behind the last row; counts (B, 2) int32: the TRUE kept numbers, n1 + n2 > p_max says truncated) as
     device tensors.  A pair whose model is not usable (a NaN pose, scale 0, a focal <= 0) is empty."""
-    k = _pl._monodepth_kind(kind)
-    dev = _pl._check_on_gpu({"depth_map1": depth_map1, "depth_map2": depth_map2})
-    _pl._check_float_pair(depth_map1, depth_map2, "depth maps")
-    if depth_map1.dim() != 3 or depth_map2.dim() != 3 or depth_map1.shape[0] != depth_map2.shape[0]:
-        raise ValueError("depth maps must have shape (B, H, W) with one B")
-    B = int(depth_map1.shape[0])
-    (h1, w1), (h2, w2) = (int(v) for v in depth_map1.shape[1:]), (int(v) for v in depth_map2.shape[1:])
-    _check_maps(h1, w1); _check_maps(h2, w2)
-    opt = _options(rate, seed, keep, p_max, h1 * w1 + h2 * w2)
-    cams1 = cams2 = None
-    if k == _capi.CALIB:
-        cams1, cams2 = _pl._camera_records(cameras1, B), _pl._camera_records(cameras2, B)
-    elif cameras1 is not None or cameras2 is not None:
-        raise ValueError("cameras are the calibrated kind's: a focal kind unprojects with the model's focals")
-    dm1, dm2 = depth_map1.contiguous(), depth_map2.contiguous()
-    c1, c2 = _pl._center(center1, B, dev), _pl._center(center2, B, dev)
-    desc = _capi.DepthPairs(dm1.data_ptr(), dm2.data_ptr(), _pl._float_types()[dm1.dtype], h1, w1, h2, w2, 0, _pl._data_ptr(c1), _pl._data_ptr(c2))
-    return _run(k, desc, opt, B, dev, models, cams1, cams2, (dm1, dm2, c1, c2))
+    staged = _stage_pairs(kind, depth_map1, depth_map2, cameras1, cameras2, center1, center2, lambda pixels: _options(rate, seed, keep, p_max, pixels))
+    return _run(staged, models, _cloud, lambda h: h.reconstruct_pairs_device)
 
 
 def reconstruct_image_pairs_torch(kind, models, depth_maps, pairs, cameras=None, centers=None, sizes=None, rate=0.05, seed=0, keep="not_inf", p_max=None):
@@ -120,36 +180,12 @@ def reconstruct_image_pairs_torch(kind, models, depth_maps, pairs, cameras=None,
     map, clamped to (H, W), None = all; centers (I, 2) or (2,); cameras (calibrated only) are per IMAGE - one for all, a list of I or a
     CAMERA_DTYPE array of I - and expanded to per-pair records by pairs on the host.  pixel is v * W + u with the ALLOCATED W, whatever the sizes.
     p_max None: default_p_max of 2 * H * W pixels.  Everything else, and what is returned, as reconstruct_pairs_torch."""
-    import torch
-    k = _pl._monodepth_kind(kind)
-    dev = _pl._check_on_gpu({"depth_maps": depth_maps})
-    if depth_maps.dtype not in _pl._float_types():
-        raise ValueError("depth maps must be float32 or float64")
-    if depth_maps.dim() != 3:
-        raise ValueError("depth maps must have shape (I, H, W)")
-    I, H, W = (int(v) for v in depth_maps.shape)
-    _check_maps(H, W)
-    on_device, host_pairs, B = _pl._pairs_on_host(pairs, dev, k == _capi.CALIB)
-    B = int(B)
-    opt = _options(rate, seed, keep, p_max, 2 * H * W)
-    cams1 = cams2 = None
-    if k == _capi.CALIB:
-        cams1, cams2 = _pl._pair_cameras(cameras, host_pairs, I)
-    elif cameras is not None:
-        raise ValueError("cameras are the calibrated kind's: a focal kind unprojects with the model's focals")
-    dm = depth_maps.contiguous()
-    cs = _pl._per_image(centers, torch.float64, (I, 2), "centers", dev)
-    sz = _pl._per_image(sizes, torch.int32, (I, 2), "sizes", dev)
-    pr = _pl._pairs_on_device(pairs, on_device, host_pairs, dev)
-    desc = _capi.DepthImagePairs(dm.data_ptr(), _pl._float_types()[dm.dtype], H, W, I, _pl._data_ptr(sz), _pl._data_ptr(cs), pr.data_ptr())
-    return _run(k, desc, opt, B, dev, models, cams1, cams2, (dm, cs, sz, pr))
+    staged = _stage_image_pairs(kind, depth_maps, pairs, cameras, centers, sizes, lambda pixels: _options(rate, seed, keep, p_max, pixels))
+    return _run(staged, models, _cloud, lambda h: h.reconstruct_pairs_device)
 
 
-def reconstruct_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1=None, camera2=None, center1=None, center2=None, rate=0.05, seed=0,
-                     keep="not_inf", p_max=None, device=0):
-    """One pair for NumPy users, over the same device call: a MonoDepthTwoViewGeometry with its two cameras (the calibrated kind), or a
-    MonoDepthImagePair (its cameras' focals; pass center1 / center2, the principal points), and two (H, W) float32 | float64 depth maps.
-    Returns (points (n, 3) float32 in camera 2's frame, pixel (n,) int32, counts (2,) int32) as NumPy arrays, n = the written rows."""
+def _single_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1, camera2, device):
+    """(kind, model records, the two maps as (1, H, W) device tensors) of one pair for NumPy users"""
     import torch
     g = geometry_or_image_pair
     focal = hasattr(g, "camera1") and hasattr(g, "geometry")
@@ -163,6 +199,15 @@ def reconstruct_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1=Non
     maps = [torch.from_numpy(np.ascontiguousarray(frontend._table(d, "depth maps"))).to(dev).unsqueeze(0) for d in (depth_map1, depth_map2)]
     if maps[0].dim() != 3 or maps[1].dim() != 3:
         raise ValueError("expected depth maps (H, W)")
+    return kind, rec, maps
+
+
+def reconstruct_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1=None, camera2=None, center1=None, center2=None, rate=0.05, seed=0,
+                     keep="not_inf", p_max=None, device=0):
+    """One pair for NumPy users, over the same device call: a MonoDepthTwoViewGeometry with its two cameras (the calibrated kind), or a
+    MonoDepthImagePair (its cameras' focals; pass center1 / center2, the principal points), and two (H, W) float32 | float64 depth maps.
+    Returns (points (n, 3) float32 in camera 2's frame, pixel (n,) int32, counts (2,) int32) as NumPy arrays, n = the written rows."""
+    kind, rec, maps = _single_pair(geometry_or_image_pair, depth_map1, depth_map2, camera1, camera2, device)
     points, pixel, counts = reconstruct_pairs_torch(kind, rec, maps[0], maps[1], camera1, camera2, center1, center2, rate, seed, keep, p_max)
     counts = counts.cpu().numpy()[0]
     n = min(int(counts.astype(np.int64).sum()), points.shape[1])

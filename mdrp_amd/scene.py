@@ -158,26 +158,17 @@ def reconstruct_scene_torch(kind, models, depth_maps, pairs, tree, cameras=None,
     A forest is allowed: every component is in its own root's frame (`root` of the records)."""
     import torch
     k = _pl._monodepth_kind(kind)
-    dev = _pl._check_on_gpu({"depth_maps": depth_maps})
-    if depth_maps.dtype not in _pl._float_types():
-        raise ValueError("depth maps must be float32 or float64")
-    if depth_maps.dim() != 3:
-        raise ValueError("depth maps must have shape (I, H, W)")
-    I, H, W = (int(v) for v in depth_maps.shape)
-    reconstruct._check_maps(H, W)
+    dev, I, H, W = reconstruct._check_image_maps(depth_maps)
     opt = reconstruct._options(rate, seed, keep, p_max, I * H * W)
     cams = None
     if k == _capi.CALIB:
         cams = _pl._camera_records(cameras, I) if I > 0 else None
     elif cameras is not None:
-        raise ValueError("cameras are the calibrated kind's: a focal kind unprojects with the model's focals")
+        raise reconstruct._focal_kind_cameras("unprojects")
     pr = _int_table(pairs, 2, "pairs", dev)
     tr = _tree_table(tree, I, dev)
     B = int(pr.shape[0])
-    dm = depth_maps.contiguous()
-    cs = _pl._per_image(centers, torch.float64, (I, 2), "centers", dev)
-    sz = _pl._per_image(sizes, torch.int32, (I, 2), "sizes", dev)
-    desc = _capi.DepthImagePairs(dm.data_ptr(), _pl._float_types()[dm.dtype], H, W, I, _pl._data_ptr(sz), _pl._data_ptr(cs), pr.data_ptr() if B else None)
+    desc, images = reconstruct._stage_images(depth_maps, centers, sizes, pr.data_ptr() if B else None)
     h = _pl._handle_on(dev)
     with torch.cuda.device(dev):
         rec, stride = reconstruct._models(models, B, dev, h)
@@ -187,7 +178,7 @@ def reconstruct_scene_torch(kind, models, depth_maps, pairs, tree, cameras=None,
         T = torch.empty((I, TRANSFORM_DTYPE.itemsize), dtype=torch.uint8, device=dev) if return_transforms else None
         h.reconstruct_scene_device(k, desc, opt, B, rec.data_ptr() if B else None, stride, tr.data_ptr() if I else None, points.data_ptr(),
                                    pixel.data_ptr(), offsets.data_ptr(), cams, T.data_ptr() if T is not None and I else None)
-    del rec, dm, cs, sz, pr, tr  # (queued on the current stream, where torch's allocator orders the reuse of their memory behind the call)
+    del rec, images, pr, tr  # (queued on the current stream, where torch's allocator orders the reuse of their memory behind the call)
     out = [points, pixel, offsets]
     if return_image:
         rows = torch.arange(opt.p_max, device=dev)

@@ -1,13 +1,14 @@
 """The history rule of include/mdrp.h for the entry points of include/mdrp_covis.h: each of them, called behind and in front of a larger call of its
-own kind, a refused call, a two-view cloud, a dense sample and a plain estimate on ONE handle, returns the bytes it returns on a fresh handle - and
-so do the calls around it.  Co-visibility has a scratch buffer of its own that is carved per call (the pairs' records, the camera tables), and it
-ADDS to the caller's counters: a call that did not clear them, or read a record of the call before it, would show here.  Every comparison is of
-bytes; the fresh answers are computed once."""
+own kind, a refused call, a two-view cloud, a scene, a dense sample and a plain estimate on ONE handle, returns the bytes it returns on a fresh
+handle - and so do the calls around it.  Co-visibility carves the back end's one scratch buffer per call (the pairs' records, the camera tables),
+as the two-view clouds and the scenes do, and it ADDS to the caller's counters: a call that did not clear them, or read a record of the call
+before it, would show here.  Every comparison is of bytes; the fresh answers are computed once."""
 import pytest
 
 import covis_cases as cc
 import dense_cases as dc
 import reconstruct_cases as rc
+import scene_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -38,6 +39,10 @@ def two_view_cloud(h, capi):
     return rc.device_call(h)
 
 
+def scene(h, capi):  # the scene's smallest good call: its records, images and tile counts lie where the pairs' records lay
+    return sc.device_call(h)
+
+
 def dense_sample(h, capi):
     return dc.sample_on(h, dc.tensors(*dc.as_seen(dc.batch("small"))), 100)
 
@@ -51,7 +56,7 @@ def larger_estimate(h, capi):
 
 
 NEW = {"pairs_small": pairs_small, "pairs_calibrated": pairs_calibrated, "image_pairs": image_pairs, "pairs_larger": pairs_larger}
-OLD = {"refused": refused, "two_view_cloud": two_view_cloud, "dense_sample": dense_sample, "larger_estimate": larger_estimate}
+OLD = {"refused": refused, "two_view_cloud": two_view_cloud, "scene": scene, "dense_sample": dense_sample, "larger_estimate": larger_estimate}
 ALL = {**NEW, **OLD}
 
 
