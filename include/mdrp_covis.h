@@ -70,4 +70,6 @@ int mdrp_covisibility_image_pairs_async(mdrp_handle *h, int kind, const mdrp_dep
 #ifdef __cplusplus
 }
 #endif
+
+#include "mdrp_fuse.h" /* the consistency filter of a scene: the scene's cloud gated by rules C5 and C6 against other images of the set */
 #endif

@@ -140,6 +140,16 @@ COVIS_SLOTS = 8  # include/mdrp_covis.h MDRP_COVIS_SLOTS: counters per direction
 COVIS_CLASSES = ("sampled", "front", "inside", "known", "consistent", "occluded", "violating")  # MDRP_COVIS_*: the slot of each class
 
 
+class FuseOpt(C.Structure):
+    """mdrp_fuse_opt (include/mdrp_fuse.h): the scene cloud's options, the number of view columns, C6's band and the gate"""
+    _fields_ = [("keep", C.c_int32), ("thr", C.c_uint32), ("seed", C.c_uint64), ("p_max", C.c_int32), ("n_views", C.c_int32), ("lo", C.c_double),
+                ("hi", C.c_double), ("min_consistent", C.c_int32), ("max_violating", C.c_int32)]
+
+
+assert C.sizeof(FuseOpt) == 48
+FUSE_MAX_VIEWS = 8  # include/mdrp_fuse.h MDRP_FUSE_MAX_VIEWS: columns of `views`
+
+
 class Result(C.Structure):
     _fields_ = [("model", Model), ("refinements", C.c_uint64), ("iterations", C.c_uint64), ("num_inliers", C.c_uint64),
                 ("inlier_ratio", C.c_double), ("model_score", C.c_double)]
@@ -311,6 +321,9 @@ PROTOTYPES = {
         "mdrp_covisibility_pairs_async": [_p, _i, C.POINTER(DepthPairs), C.POINTER(CovisOpt), _i, _p, _i, _p, _p, _p],
         "mdrp_covisibility_image_pairs_async": [_p, _i, C.POINTER(DepthImagePairs), C.POINTER(CovisOpt), _i, _p, _i, _p, _p, _p],
     },
+    "mdrp_fuse.h": {  # the consistency filter of a scene: only the points that other images' depth maps confirm
+        "mdrp_fuse_scene_async": [_p, _i, C.POINTER(DepthImagePairs), C.POINTER(FuseOpt), _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    },
 }
 # what each header declares: mdrp.h's own list (with the four symbols that only get a restype), then its extension headers'
 EXPORTS = tuple(PROTOTYPES["mdrp.h"]) + ("mdrp_last_error", "mdrp_version", "mdrp_abi_version", "mdrp_hip_build_version")
@@ -322,6 +335,7 @@ EXPORTS_DENSE = tuple(PROTOTYPES["mdrp_dense.h"])
 EXPORTS_RECONSTRUCT = tuple(PROTOTYPES["mdrp_reconstruct.h"])
 EXPORTS_SCENE = tuple(PROTOTYPES["mdrp_scene.h"])
 EXPORTS_COVIS = tuple(PROTOTYPES["mdrp_covis.h"])
+EXPORTS_FUSE = tuple(PROTOTYPES["mdrp_fuse.h"])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -640,7 +654,24 @@ class _CovisCalls:
         self.covisibility_pairs_device(kind, desc, opt, batch, models_ptr, model_stride, counts_ptr, cam1, cam2)
 
 
-class Handle(_ReconstructCalls, _SceneCalls, _CovisCalls):
+class _FuseCalls:
+    """The call of include/mdrp_fuse.h, a method of Handle through this base.  Arguments go to the library as they are: the library checks them."""
+
+    def fuse_scene_device(self, kind, desc, opt, batch, models_ptr, model_stride, tree_ptr, views_ptr, points_ptr, pixel_ptr, support_ptr, offsets_ptr,
+                          cams=None, transforms_ptr=None):
+        """the consistency-filtered cloud of an image set on the handle's stream into the caller's device buffers: points [p_max][3] float32, pixel
+        [p_max] int32, support [p_max][2] uint8, offsets [n_images + 1] int64, and the [n_images] transform records where transforms_ptr is given.
+        desc: a DepthImagePairs; opt: a FuseOpt; views_ptr: int32 [n_images][opt.n_views] on the device; cams: per IMAGE, the calibrated kind
+        alone.  Nothing synchronises."""
+        if not isinstance(desc, DepthImagePairs):
+            raise ValueError("fuse_scene_device takes a DepthImagePairs descriptor")
+        _, c, _ = _tables(None, cams, None)
+        _check(self._lib, _fn(self._lib, "mdrp_fuse_scene_async")(self._h, int(kind), C.byref(desc), C.byref(opt), int(batch), _dev(models_ptr),
+                                                                  int(model_stride), _dev(tree_ptr), _dev(views_ptr), _ptr(c), _dev(transforms_ptr),
+                                                                  _dev(points_ptr), _dev(pixel_ptr), _dev(support_ptr), _dev(offsets_ptr)))
+
+
+class Handle(_ReconstructCalls, _SceneCalls, _CovisCalls, _FuseCalls):
     """One handle = one HIP device + one stream + its scratch buffers.  Calls on one handle are serialised inside the
     library; use one handle per host thread for concurrency (default_handle() does).
 

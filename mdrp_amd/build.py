@@ -25,7 +25,8 @@ DEPS = [SRC, SRC_TU, os.path.join(HERE, "csrc", "mdrp_capi_entry.h"), os.path.jo
         os.path.join(HERE, "csrc", "mdrp_dense.h"), os.path.join(HERE, "..", "include", "mdrp_dense.h"),
         os.path.join(HERE, "csrc", "mdrp_reconstruct.h"), os.path.join(HERE, "..", "include", "mdrp_reconstruct.h"),
         os.path.join(HERE, "csrc", "mdrp_scene.h"), os.path.join(HERE, "..", "include", "mdrp_scene.h"),
-        os.path.join(HERE, "csrc", "mdrp_covis.h"), os.path.join(HERE, "..", "include", "mdrp_covis.h")]
+        os.path.join(HERE, "csrc", "mdrp_covis.h"), os.path.join(HERE, "..", "include", "mdrp_covis.h"),
+        os.path.join(HERE, "csrc", "mdrp_fuse.h"), os.path.join(HERE, "..", "include", "mdrp_fuse.h")]
 OUT = os.path.join(HERE, "libmdrp_hip.so")
 _MARK = b"MDRP_SRC_HASH="
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-ffp-contract=fast", "-no-hip-rt"]

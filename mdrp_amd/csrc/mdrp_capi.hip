@@ -15,6 +15,7 @@
 #include "mdrp_reconstruct.h"
 #include "mdrp_scene.h"
 #include "mdrp_covis.h"
+#include "mdrp_fuse.h"
 // MDRP_SPLIT_TU (the default build): the k_final family, k_from_model, k_prior, kc_from_model, kc_prior and the baselines' kernels are instantiated in mdrp_tu.hip, compiled in parallel with
 // this file; a single-unit build (experiment builds with -D switches: mdrp_amd/build.py single=True) instantiates them here, implicitly.
 #ifdef MDRP_SPLIT_TU
@@ -3091,6 +3092,91 @@ void scene_chain_launch(hipStream_t s, const SceneTree &t, const ReconCam *cams,
     hipLaunchKernelGGL(k_scene_chain, dim3((unsigned)((t.n_images + SCENE_CHAIN_THREADS - 1) / SCENE_CHAIN_THREADS)), dim3(SCENE_CHAIN_THREADS), 0, s, t, cams, T, im);
 }
 
+// what the consistency filter (include/mdrp_fuse.h) adds to a scene's cloud: its views, its gate and the rows' support
+struct FuseCall {
+    const int32_t *views; // device, [n_images][n_views]
+    int n_views;
+    FuseGate gate;
+    uint8_t *support;     // device, [p_max][2]
+};
+const char *fuse_refusal(const FuseCall &f, int n_images, int p_max) {
+    if (f.n_views < 0 || f.n_views > FUSE_MAX_VIEWS) return "n_views must be 0 .. MDRP_FUSE_MAX_VIEWS (8)";
+    if (f.n_views > 0 && n_images > 0 && !f.views) return "NULL views_dev";
+    if (!(std::isfinite(f.gate.lo) && std::isfinite(f.gate.hi) && f.gate.lo >= 0.0 && f.gate.lo <= 1.0 && f.gate.hi >= 1.0))
+        return "lo and hi must be finite with 0 <= lo <= 1 <= hi";
+    if (f.gate.min_consistent < 0 || f.gate.max_violating < 0) return "negative min_consistent or max_violating";
+    if (p_max > 0 && !f.support) return "NULL support";
+    return nullptr;
+}
+
+// The scene's cloud behind both of its entry points: every refusal, the scratch and the kernels on the handle's stream.  fuse: null for the plain
+// cloud; otherwise the count and emit passes are the filter's (k_fuse_count, k_fuse_emit) behind k_fuse_views, between the same chain and scans.
+int scene_cloud(mdrp_handle *h, const char *who, int kind, const mdrp_depth_image_pairs *ip, const mdrp_reconstruct_opt &o, int batch, const void *models_dev,
+                int model_stride, const int32_t *tree_dev, const mdrp_camera *cams_host, void *transforms_dev, float *points, int32_t *pixel, int64_t *offsets,
+                const FuseCall *fuse) {
+    const int n = ip->n_images;
+    const SceneTree t{static_cast<const unsigned char *>(models_dev), ip->pairs, tree_dev, model_stride, kind, batch, n};
+    const int64_t px = (int64_t)ip->h_max * ip->w_max;
+    const auto refusal = [&]() -> const char * {
+        const char *why;
+        if ((why = scene_tree_refusal(t))) return why;
+        if (kind == MDRP_CALIB && n > 0 && !cams_host) return "MDRP_CALIB needs cams_host, one record per image";
+        if ((why = recon_focal_cameras_refusal(kind, cams_host != nullptr))) return why;
+        if ((why = recon_option_refusal(ip->depth_type, o.keep, o.thr, o.p_max))) return why;
+        if ((why = recon_extent_refusal(ip->h_max, ip->w_max, ip->h_max, ip->w_max, n))) return why; // (n >= 0: the tree's refusals)
+        if (!offsets) return "NULL offsets";
+        if (o.p_max > 0 && (!points || !pixel)) return "NULL points or pixel";
+        if (n > 0 && px > 0 && !ip->depth) return "NULL depth map";
+        if (kind == MDRP_CALIB && (why = recon_camera_models_refusal(cams_host, n))) return why;
+        return fuse ? fuse_refusal(*fuse, n, o.p_max) : nullptr;
+    };
+    if (const char *why = refusal()) { g_err = std::string(who) + ": " + why; return MDRP_ERR_INVALID; }
+    SceneArgs a{};
+    a.depth = ip->depth; a.center = ip->center; a.size = ip->size; a.depth_type = ip->depth_type; a.keep = o.keep; a.n_images = n;
+    a.h = ip->h_max; a.w = ip->w_max; a.thr = o.thr; a.seed = (uint32_t)o.seed; a.p_max = o.p_max;
+    a.nt = recon_tiles(a.h, a.w);
+    const size_t tiles = (size_t)n * (size_t)a.nt, nfill = ((size_t)a.p_max + RECON_TILE - 1) / RECON_TILE;
+    if (tiles + nfill > (size_t)INT32_MAX) { g_err = std::string(who) + ": the scene's tiles above 2^31 - 1: split the scene"; return MDRP_ERR_INVALID; }
+    MDRP_ENTER(h);
+    // The scratch is the back end's buffer of the handle, carved for this call's sizes (at least 16 bytes: an empty scene still launches on it); every
+    // word of it that a kernel reads was written by this call.
+    Carve cv;
+    const size_t o_T = cv.take(transforms_dev ? 0 : sizeof(SceneTransform) * (size_t)n), o_im = cv.take(sizeof(SceneImage) * (size_t)n),
+                 o_cam = cv.take(kind == MDRP_CALIB ? sizeof(ReconCam) * (size_t)n : 0), o_tcnt = cv.take(sizeof(uint32_t) * tiles),
+                 o_fv = cv.take(fuse ? sizeof(FuseView) * (size_t)n : 0), o_fr = cv.take(fuse ? sizeof(FuseRow) * (size_t)n : 0);
+    if (int rc = cv.ensure(h->be_scratch, 16)) return rc;
+    hipStream_t s = h->stream;
+    const ReconCam *cams = nullptr;
+    if (kind == MDRP_CALIB && n > 0) {
+        if (int rc = upload_cameras(h, cv.at<ReconCam>(o_cam), cams_host, nullptr, (size_t)n)) return rc;
+        cams = cv.at<ReconCam>(o_cam);
+    }
+    SceneTransform *T = transforms_dev ? static_cast<SceneTransform *>(transforms_dev) : cv.at<SceneTransform>(o_T);
+    SceneImage *im = cv.at<SceneImage>(o_im);
+    uint32_t *tcnt = cv.at<uint32_t>(o_tcnt);
+    const FuseArgs f{cv.at<FuseView>(o_fv), cv.at<FuseRow>(o_fr), fuse ? fuse->gate : FuseGate{}};
+    if (n > 0) {
+        scene_chain_launch(s, t, cams, T, im);
+        if (fuse) {
+            hipLaunchKernelGGL(k_fuse_views, dim3((unsigned)((n + SCENE_CHAIN_THREADS - 1) / SCENE_CHAIN_THREADS)), dim3(SCENE_CHAIN_THREADS), 0, s, a, kind, cams,
+                               (const SceneTransform *)T, fuse->views, fuse->n_views, cv.at<FuseView>(o_fv), cv.at<FuseRow>(o_fr));
+            hipLaunchKernelGGL(k_fuse_count, dim3((unsigned)tiles), dim3(RECON_THREADS), 0, s, a, f, (const SceneTransform *)T, (const SceneImage *)im, tcnt);
+        } else {
+            hipLaunchKernelGGL(k_scene_count, dim3((unsigned)tiles), dim3(RECON_THREADS), 0, s, a, (const SceneTransform *)T, tcnt);
+        }
+        hipLaunchKernelGGL(k_scene_scan, dim3((unsigned)n), dim3(RECON_THREADS), 0, s, 0, n, a.nt, tcnt, offsets);
+    }
+    hipLaunchKernelGGL(k_scene_scan, dim3(1), dim3(RECON_THREADS), 0, s, 1, n, a.nt, tcnt, offsets);
+    if (a.p_max > 0 && fuse)
+        hipLaunchKernelGGL(k_fuse_emit, dim3((unsigned)(tiles + nfill)), dim3(RECON_THREADS), 0, s, a, f, (const uint32_t *)tcnt, (const SceneTransform *)T,
+                           (const SceneImage *)im, (const int64_t *)offsets, points, pixel, fuse->support);
+    else if (a.p_max > 0)
+        hipLaunchKernelGGL(k_scene_emit, dim3((unsigned)(tiles + nfill)), dim3(RECON_THREADS), 0, s, a, (const uint32_t *)tcnt, (const SceneTransform *)T,
+                           (const SceneImage *)im, (const int64_t *)offsets, points, pixel);
+    HIPCHK(hipGetLastError());
+    return MDRP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -3113,55 +3199,8 @@ int mdrp_reconstruct_scene_async(mdrp_handle *h, int kind, const mdrp_depth_imag
                                  int model_stride, const int32_t *tree_dev, const mdrp_camera *cams_host, mdrp_scene_transform *transforms_dev, float *points,
                                  int32_t *pixel, int64_t *offsets) {
     if (!h || !ip || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
-    const int n = ip->n_images;
-    const SceneTree t{static_cast<const unsigned char *>(models_dev), ip->pairs, tree_dev, model_stride, kind, batch, n};
-    const int64_t px = (int64_t)ip->h_max * ip->w_max;
-    const auto refusal = [&]() -> const char * {
-        const char *why;
-        if ((why = scene_tree_refusal(t))) return why;
-        if (kind == MDRP_CALIB && n > 0 && !cams_host) return "MDRP_CALIB needs cams_host, one record per image";
-        if ((why = recon_focal_cameras_refusal(kind, cams_host != nullptr))) return why;
-        if ((why = recon_option_refusal(ip->depth_type, opt->keep, opt->thr, opt->p_max))) return why;
-        if ((why = recon_extent_refusal(ip->h_max, ip->w_max, ip->h_max, ip->w_max, n))) return why; // (n >= 0: the tree's refusals)
-        if (!offsets) return "NULL offsets";
-        if (opt->p_max > 0 && (!points || !pixel)) return "NULL points or pixel";
-        if (n > 0 && px > 0 && !ip->depth) return "NULL depth map";
-        return kind == MDRP_CALIB ? recon_camera_models_refusal(cams_host, n) : nullptr;
-    };
-    if (const char *why = refusal()) { g_err = std::string("mdrp_reconstruct_scene_async: ") + why; return MDRP_ERR_INVALID; }
-    SceneArgs a{};
-    a.depth = ip->depth; a.center = ip->center; a.size = ip->size; a.depth_type = ip->depth_type; a.keep = opt->keep; a.n_images = n;
-    a.h = ip->h_max; a.w = ip->w_max; a.thr = opt->thr; a.seed = (uint32_t)opt->seed; a.p_max = opt->p_max;
-    a.nt = recon_tiles(a.h, a.w);
-    const size_t tiles = (size_t)n * (size_t)a.nt, nfill = ((size_t)a.p_max + RECON_TILE - 1) / RECON_TILE;
-    if (tiles + nfill > (size_t)INT32_MAX) { g_err = "mdrp_reconstruct_scene_async: the scene's tiles above 2^31 - 1: split the scene"; return MDRP_ERR_INVALID; }
-    MDRP_ENTER(h);
-    // The scratch is the back end's buffer of the handle, carved for this call's sizes (at least 16 bytes: an empty scene still launches on it); every
-    // word of it that a kernel reads was written by this call.
-    Carve cv;
-    const size_t o_T = cv.take(transforms_dev ? 0 : sizeof(SceneTransform) * (size_t)n), o_im = cv.take(sizeof(SceneImage) * (size_t)n),
-                 o_cam = cv.take(kind == MDRP_CALIB ? sizeof(ReconCam) * (size_t)n : 0), o_tcnt = cv.take(sizeof(uint32_t) * tiles);
-    if (int rc = cv.ensure(h->be_scratch, 16)) return rc;
-    hipStream_t s = h->stream;
-    const ReconCam *cams = nullptr;
-    if (kind == MDRP_CALIB && n > 0) {
-        if (int rc = upload_cameras(h, cv.at<ReconCam>(o_cam), cams_host, nullptr, (size_t)n)) return rc;
-        cams = cv.at<ReconCam>(o_cam);
-    }
-    SceneTransform *T = transforms_dev ? reinterpret_cast<SceneTransform *>(transforms_dev) : cv.at<SceneTransform>(o_T);
-    SceneImage *im = cv.at<SceneImage>(o_im);
-    uint32_t *tcnt = cv.at<uint32_t>(o_tcnt);
-    if (n > 0) {
-        scene_chain_launch(s, t, cams, T, im);
-        hipLaunchKernelGGL(k_scene_count, dim3((unsigned)tiles), dim3(RECON_THREADS), 0, s, a, (const SceneTransform *)T, tcnt);
-        hipLaunchKernelGGL(k_scene_scan, dim3((unsigned)n), dim3(RECON_THREADS), 0, s, 0, n, a.nt, tcnt, offsets);
-    }
-    hipLaunchKernelGGL(k_scene_scan, dim3(1), dim3(RECON_THREADS), 0, s, 1, n, a.nt, tcnt, offsets);
-    if (a.p_max > 0)
-        hipLaunchKernelGGL(k_scene_emit, dim3((unsigned)(tiles + nfill)), dim3(RECON_THREADS), 0, s, a, (const uint32_t *)tcnt, (const SceneTransform *)T,
-                           (const SceneImage *)im, (const int64_t *)offsets, points, pixel);
-    HIPCHK(hipGetLastError());
-    return MDRP_OK;
+    return scene_cloud(h, "mdrp_reconstruct_scene_async", kind, ip, *opt, batch, models_dev, model_stride, tree_dev, cams_host, transforms_dev, points, pixel,
+                       offsets, nullptr);
 }
 
 } // extern "C"
@@ -3218,6 +3257,25 @@ int mdrp_covisibility_image_pairs_async(mdrp_handle *h, int kind, const mdrp_dep
     ReconCall c = recon_call("mdrp_covisibility_image_pairs_async", kind, batch, models_dev, model_stride, cam1, cam2, nullptr, nullptr, counts);
     recon_flatten(c.a, ip);
     return covis_call(h, c, opt);
+}
+
+} // extern "C"
+
+// ---- the consistency filter of a scene: only the points that other images' depth maps confirm (include/mdrp_fuse.h; mdrp_fuse.h)
+static_assert(MDRP_FUSE_MAX_VIEWS == FUSE_MAX_VIEWS, "values of the header and of the kernels");
+static_assert(sizeof(mdrp_fuse_opt) == 48 && offsetof(mdrp_fuse_opt, seed) == 8 && offsetof(mdrp_fuse_opt, p_max) == 16 && offsetof(mdrp_fuse_opt, n_views) == 20 &&
+              offsetof(mdrp_fuse_opt, lo) == 24 && offsetof(mdrp_fuse_opt, hi) == 32 && offsetof(mdrp_fuse_opt, min_consistent) == 40 &&
+              offsetof(mdrp_fuse_opt, max_violating) == 44, "option layout");
+
+extern "C" {
+
+int mdrp_fuse_scene_async(mdrp_handle *h, int kind, const mdrp_depth_image_pairs *ip, const mdrp_fuse_opt *opt, int batch, const void *models_dev, int model_stride,
+                          const int32_t *tree_dev, const int32_t *views_dev, const mdrp_camera *cams_host, void *transforms_dev, float *points, int32_t *pixel,
+                          uint8_t *support, int64_t *offsets) {
+    if (!h || !ip || !opt) { g_err = "invalid argument"; return MDRP_ERR_INVALID; }
+    const mdrp_reconstruct_opt o{opt->keep, opt->thr, opt->seed, opt->p_max, 0};
+    const FuseCall f{views_dev, opt->n_views, {opt->lo, opt->hi, opt->min_consistent, opt->max_violating}, support};
+    return scene_cloud(h, "mdrp_fuse_scene_async", kind, ip, o, batch, models_dev, model_stride, tree_dev, cams_host, transforms_dev, points, pixel, offsets, &f);
 }
 
 } // extern "C"

@@ -942,3 +942,162 @@ def covisibility_image_pairs_numpy(models, kind, depth_maps, pairs, centers=None
                                             None if cs is None else cs[c], None if cameras1 is None else cameras1[b],
                                             None if cameras2 is None else cameras2[b], thr, seed, lo, hi)
     return counts
+
+
+# ---- the consistency filter of a scene (include/mdrp_fuse.h): a scene's point stays if enough other images' depth maps confirm it and
+# few enough see through it.  Rules F1-F6 of the header.  A candidate pixel's point in its root's frame (S5, S6 before the rounding) is carried into the
+# camera frame of each of its image's views, projected to the nearest pixel there and compared with that map's own depth (C5, C6); the gate takes the
+# numbers of consistent and of violating views.  Every quantity that decides is a fixed sequence of float64 operations, one rounding per arithmetic
+# sign: the device result equals this statement as bytes.
+FUSE_MAX_VIEWS = 8
+FUSE_CLASSES = ("invalid", "not_front", "outside", "unknown", "consistent", "occluded", "violating")  # F5: what one slot says of one pixel (0: F3)
+
+
+def fuse_valid_slots(transforms, views_row, i):
+    """F3: per slot of image i's row of `views` the image it names, -1 where the slot is inert: an index outside [0, I), the image itself, an image
+    that is not attached or hangs on another root, or one an earlier slot of the row holds.  Nothing is read through an inert slot."""
+    I, out = len(transforms), []
+    for n in (int(x) for x in np.asarray(views_row).reshape(-1)):
+        ok = (0 <= n < I and n != i and transforms[n]["depth"] >= 0 and transforms[i]["depth"] >= 0 and transforms[n]["root"] == transforms[i]["root"]
+              and n not in out)
+        out.append(n if ok else -1)
+    return out
+
+
+def fuse_to_view(transform, Q):
+    """F4: points Q (n, 3) float64 of a root's frame in the camera frame of the view with record `transform`: the inverse of the record, sums left
+    to right; a root view's are Q as it stands"""
+    T = np.asarray(transform).reshape(())
+    if T["depth"] == 0:
+        return [Q[:, 0], Q[:, 1], Q[:, 2]]
+    R, t, s = T["R"].reshape(3, 3), T["t"], np.float64(T["s"])
+    Y = [s * Q[:, r] - t[r] for r in range(3)]
+    return [(R[0, r] * Y[0] + R[1, r] * Y[1]) + R[2, r] * Y[2] for r in range(3)]
+
+
+def fuse_slot_numpy(transform, kind, P, depth_tgt, center_tgt=None, camera_tgt=None, lo=0.95, hi=1.05):
+    """F4's FRONT and F5 for one view: points P (three (n,) float64 arrays) of the view's camera frame against its depth map (its valid region) ->
+    (n,) uint8 indices into FUSE_CLASSES, none of them 0.  C5 and C6 with the view as the target."""
+    T = np.asarray(transform).reshape(())
+    tgt = _table(depth_tgt, "depth maps")
+    ht, wt = tgt.shape
+    ct = np.zeros(2) if center_tgt is None else np.asarray(center_tgt, dtype=np.float64).reshape(2)
+    m = {"f1": T["f"], "f2": T["f"]}
+    with np.errstate(all="ignore"):
+        front = np.isfinite(P[2]) & (P[2] > 0.0)
+        _, _, ox, oy = _recon_intrinsics(m, kind, 0, camera_tgt)
+        fx, fy = _covis_focals(m, kind, 0, camera_tgt)
+        xo, yo = P[0] / P[2], P[1] / P[2]
+        px, py = (xo * fx + ox) + ct[0], (yo * fy + oy) + ct[1]
+        a, b = px + 0.5, py + 0.5
+        inside = front & (a >= 0.0) & (a < np.float64(wt)) & (b >= 0.0) & (b < np.float64(ht))
+        ut, vt = np.where(inside, a, 0.0).astype(np.int64), np.where(inside, b, 0.0).astype(np.int64)
+        dt = np.zeros(len(P[2]))
+        dt[inside] = tgt[vt[inside], ut[inside]].astype(np.float64)
+        zt = dt + np.float64(T["shift"])
+        known = inside & np.isfinite(dt) & (zt > 0.0)
+        l, hgh = lo * zt, hi * zt
+        consistent, occluded, violating = known & (P[2] >= l) & (P[2] <= hgh), known & (P[2] > hgh), known & (P[2] < l)
+    cls = np.full(len(P[2]), 1, dtype=np.uint8)
+    for code, member in ((2, front), (3, inside), (4, consistent), (5, occluded), (6, violating)):
+        cls[member] = code
+    return cls
+
+
+def fuse_image_support_numpy(transforms, kind, i, views_row, depth_maps, hs, ws, cs=None, cameras=None, keep="not_inf", thr=RECON_ALL, seed=0, lo=0.95,
+                             hi=1.05):
+    """F1-F5 for one attached image i: (Q (n, 3) float64: its candidates' points in the root's frame, before the rounding; v, u (n,) int64: the
+    candidates, row-major; support (n, 2) uint8: (n_cons, n_viol); classes (n, V) uint8: per slot an index into FUSE_CLASSES).  depth_maps (I, H, W);
+    hs, ws (I,): the valid regions; cs (I, 2) or None; cameras: per image or None."""
+    lo, hi = _covis_check_band(lo, hi)
+    T = transforms[i]
+    cam = (lambda n: None if cameras is None else cameras[n])
+    cen = (lambda n: None if cs is None else cs[n])
+    slots = fuse_valid_slots(transforms, views_row, i)
+    with np.errstate(all="ignore"):
+        d_all = depth_maps[i][:hs[i], :ws[i]].astype(np.float64)
+        kept = recon_candidates(int(hs[i]), int(ws[i]), thr, scene_seed(seed, i), SCENE_STAGE) & recon_keep(d_all, keep)   # F1: S3, S4
+        v, u = np.nonzero(kept)
+        d = d_all[v, u]
+        Q = scene_transform_points(T, scene_unproject(T, kind, v, u, d, cen(i), cam(i))).reshape(-1, 3)
+        tested = np.isfinite(d) & (d + np.float64(T["shift"]) > 0.0)                                                        # F2
+        classes = np.zeros((len(v), len(slots)), dtype=np.uint8)
+        for k, n in enumerate(slots):
+            if n < 0:                                                                                                      # F3
+                continue
+            cls = fuse_slot_numpy(transforms[n], kind, fuse_to_view(transforms[n], Q), depth_maps[n][:hs[n], :ws[n]], cen(n), cam(n), lo, hi)
+            classes[:, k] = np.where(tested, cls, 0)
+    support = np.stack([(classes == 4).sum(axis=1), (classes == 6).sum(axis=1)], axis=1).astype(np.uint8).reshape(-1, 2)
+    return Q, v.astype(np.int64), u.astype(np.int64), support, classes
+
+
+def fuse_gate(support, min_consistent, max_violating):
+    """F6: (n,) bool, the candidates the gate keeps"""
+    s = np.asarray(support).reshape(-1, 2).astype(np.int64)
+    return (s[:, 0] >= int(min_consistent)) & (s[:, 1] <= int(max_violating))
+
+
+def pack_fuse_rows(rows, p_max=None):
+    """F6's placement: per image (points, pixel, support) or None -> (points (p_max, 3) float32, pixel (p_max,) int32, support (p_max, 2) uint8,
+    offsets (I + 1,) int64), as pack_scene_rows places its rows; the filler of support is 0, 0"""
+    points, pixel, offsets = pack_scene_rows([None if r is None else r[:2] for r in rows], p_max)
+    support = np.zeros((len(pixel), 2), dtype=np.uint8)
+    for r, start in zip(rows, offsets[:-1]):
+        if r is None or start >= len(pixel):
+            continue
+        k = min(len(r[1]), len(pixel) - int(start))
+        support[start:start + k] = r[2][:k]
+    return points, pixel, support, offsets
+
+
+def fuse_rows_numpy(transforms, kind, depth_maps, views, centers=None, sizes=None, cameras=None, keep="not_inf", thr=RECON_ALL, seed=0, lo=0.95, hi=1.05,
+                    min_consistent=1, max_violating=0):
+    """per image the kept rows (points (n, 3) float32, pixel (n,) int32, support (n, 2) uint8) by F1-F6, None for an absent or detached image"""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    if keep not in KEEPS:
+        raise ValueError(f"keep must be one of {KEEPS}, not {keep!r}")
+    if int(min_consistent) < 0 or int(max_violating) < 0:
+        raise ValueError("min_consistent and max_violating must not be negative")
+    dm = _table(depth_maps, "depth maps")
+    if dm.ndim != 3:
+        raise ValueError("expected depth maps (I, H, W)")
+    I, H, W = dm.shape
+    if len(transforms) != I:
+        raise ValueError("one transform per image")
+    views = np.asarray(views).astype(np.int64)
+    views = views.reshape(I, views.size // I if I and views.size else 0)
+    if views.shape[1] > FUSE_MAX_VIEWS:
+        raise ValueError(f"views has at most {FUSE_MAX_VIEWS} columns")
+    hw = np.tile(np.array([H, W], dtype=np.int64), (I, 1)) if sizes is None else np.asarray(sizes).reshape(I, 2)
+    hs, ws = clamp_extent(hw[:, 0], H), clamp_extent(hw[:, 1], W)
+    cs = None if centers is None else np.asarray(centers, dtype=np.float64)
+    if cs is not None and cs.size == 2:
+        cs = np.tile(cs.reshape(1, 2), (I, 1))
+    if cs is not None and cs.shape != (I, 2):
+        raise ValueError("centers must have shape (I, 2) or (2,)")
+    if kind == "calibrated" and (cameras is None or len(cameras) != I):
+        raise ValueError("the calibrated kind needs one camera per image")
+    rows = []
+    for i in range(I):
+        if transforms[i]["depth"] < 0:
+            rows.append(None)
+            continue
+        Q, v, u, support, _ = fuse_image_support_numpy(transforms, kind, i, views[i], dm, hs, ws, cs, cameras, keep, thr, seed, lo, hi)
+        g = fuse_gate(support, min_consistent, max_violating)                                                              # F6
+        with np.errstate(over="ignore", invalid="ignore"):
+            rows.append((Q[g].astype(np.float32), (v[g] * W + u[g]).astype(np.int32), support[g]))
+    return rows
+
+
+def fuse_scene_numpy(models, kind, depth_maps, pairs, tree, views, p_max=None, centers=None, sizes=None, cameras=None, keep="not_inf", thr=RECON_ALL,
+                     seed=0, lo=0.95, hi=1.05, min_consistent=1, max_violating=0):
+    """What reconstruct_scene_numpy takes, views (I, V) int32 with 0 <= V <= 8 - per image the images its points are tested against; a view need not
+    be a partner of the image in `pairs` - C6's band lo, hi (covis_band(tol)) and the gate.  Returns (points (p_max, 3) float32, pixel (p_max,)
+    int32, support (p_max, 2) uint8 = (n_cons, n_viol) per row, offsets (I + 1,) int64, transforms (I,) SCENE_TRANSFORM_DTYPE) by F1-F6; p_max None
+    = every kept row.  With min_consistent = 0 and max_violating >= V the first, second and fourth are reconstruct_scene_numpy's.  This function is
+    the definition."""
+    I = np.shape(depth_maps)[0]
+    T = scene_transforms_numpy(models, kind, pairs, tree, I)
+    rows = fuse_rows_numpy(T, kind, depth_maps, views, centers, sizes, cameras, keep, thr, seed, lo, hi, min_consistent, max_violating)
+    return (*pack_fuse_rows(rows, p_max), T)

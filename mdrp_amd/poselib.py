@@ -2015,3 +2015,7 @@ from .scene import reconstruct_scene, reconstruct_scene_torch, scene_transforms_
 # ---- co-visibility (include/mdrp_covis.h): dense depth-consistency counts per pair.  mdrp_amd/covis.py holds the entry points; they are
 # found here, beside the estimators whose records they take.
 from .covis import covisibility_image_pairs_torch, covisibility_pair, covisibility_pairs_torch, covisibility_scores  # noqa: E402, F401
+
+# ---- the consistency filter of a scene (include/mdrp_fuse.h): only the points that other images' depth maps confirm.  mdrp_amd/fuse.py
+# holds the entry points; they are re-exported here.
+from .fuse import fuse_scene, fuse_scene_torch, scene_views  # noqa: E402, F401
