@@ -20,6 +20,10 @@ SEED = 0x1234ABCD5
 EMPTY = {1: "nan_q", 5: "zero_scale", 9: "bad_focal", 13: "inf_t"}  # C1's empty pairs, mixed into every batch of more than one pair
 BEHIND, OUTSIDE = 6, 7                                              # no sampled pixel is FRONT | every one is FRONT and none INSIDE
 INF_MAP = {0: 2, 1: 4}                                              # the map of image 1 | image 2 that is all +inf
+# the wide sizes of tests/reconstruct_cases.py (257, 33 and 514 tiles of 1024 pixels): co-visibility has no scan, but it shares the tile walk, which
+# no size above has taken past tile 33.  Only tests/test_gpu_backend_wide.py takes them: WIDE_B usable pairs each.
+WIDE_SIZES = (((409, 643), (130, 257)), ((130, 257), (409, 643)), ((723, 727), (409, 643)))
+WIDE_B = 2
 
 
 def models(kind, n=B_MAX, seed=41):
@@ -105,12 +109,15 @@ def depth_maps(h, w, dtype, n=B_MAX, seed=44, whole_inf=2):
 
 @functools.lru_cache(maxsize=None)
 def inputs(kind, dtype_name, size):
-    """everything a call of the per-pair form takes, for B_MAX pairs; a batch of B is the first B of each"""
+    """everything a call of the per-pair form takes, for B_MAX pairs; a batch of B is the first B of each.  A size of WIDE_SIZES: WIDE_B pairs, both
+    usable (models 0 and 2), no map all inf"""
     (h1, w1), (h2, w2) = size
     dtype = np.dtype(dtype_name)
-    cam1, cam2 = cameras(size) if kind == "calibrated" else (None, None)
-    c1, c2 = centres(kind, size)
-    return {"models": models(kind), "dm1": depth_maps(h1, w1, dtype, seed=44, whole_inf=INF_MAP[0]), "dm2": depth_maps(h2, w2, dtype, seed=45, whole_inf=INF_MAP[1]),
+    n = WIDE_B if size in WIDE_SIZES else B_MAX
+    cam1, cam2 = cameras(size, n) if kind == "calibrated" else (None, None)
+    c1, c2 = centres(kind, size, n)
+    ms = models(kind, 3)[[0, 2]] if size in WIDE_SIZES else models(kind)
+    return {"models": ms, "dm1": depth_maps(h1, w1, dtype, n, seed=44, whole_inf=INF_MAP[0]), "dm2": depth_maps(h2, w2, dtype, n, seed=45, whole_inf=INF_MAP[1]),
             "c1": c1, "c2": c2, "cam1": cam1, "cam2": cam2}
 
 

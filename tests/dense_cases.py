@@ -54,12 +54,34 @@ def stack(pairs):
 
 _batches = {}
 
+# ---- the wide batches (tests/test_gpu_dense_wide.py, tests/test_scan_runs_host.py): row counts at which k_dense_scan's threads hold runs of more than
+# one block (per = ceil(nblk / 256) > 1) and the weight sum T passes 2^32.  name: (R, make_pair's seeds); every pair is of kind "mixed".
+SCAN_THREADS = 256                       # mdrp_dense.h DENSE_THREADS: the scan's workgroup
+R_WIDE = 256 * BLOCK_ROWS + 17           # the smallest R with nblk = 257, per = 2: threads 0-127 hold two blocks, thread 128 one, the last block is ragged
+R_WIDE3 = 512 * BLOCK_ROWS + 1           # nblk = 513, per = 3: thread 171's lo is clamped to nblk; the last block is one row
+R_MAX = 1 << 22                          # mdrp_dense.h MDRP_DENSE_MAX_ROWS: nblk = 4096, per = 16, every thread busy
+WIDE_BATCHES = {"wide": (R_WIDE, (30, 31)), "wide3": (R_WIDE3, (30,)), "max": (R_MAX, (30,))}
+N_WIDE = 16384                           # mdrp_dense.h's largest n: with expansion 4, m1_max = 65536 and ntile = 256
+
+
+def scan_run(n, threads=SCAN_THREADS):
+    """the run length of the chunked scans (k_dense_scan, k_recon_scan, k_scene_scan): a thread sums per = ceil(n / threads) consecutive values"""
+    return -(-int(n) // threads)
+
+
+def nblk(R):
+    return -(-int(R) // BLOCK_ROWS)
+
 
 def batch(name):
     """B = 3 each.  "blocks": R = 3 blocks + 17, a pair of zero certainties between two live ones, pair 2 = pair 0 (the same pair at two batch
-    positions); "small": R below one block; "duplicates": the duplicate case, pairs 0 and 1"""
+    positions); "small": R below one block; "duplicates": the duplicate case, pairs 0 and 1.  The names of WIDE_BATCHES: B = 2 or 1 mixed pairs of
+    that many rows"""
     if name not in _batches:
-        if name == "blocks":
+        if name in WIDE_BATCHES:
+            R, seeds = WIDE_BATCHES[name]
+            b = stack([make_pair(s, R) for s in seeds])
+        elif name == "blocks":
             a = make_pair(0, R_BLOCKS)
             b = stack([a, make_pair(1, R_BLOCKS, "zero"), a])
         elif name == "small":

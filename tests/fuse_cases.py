@@ -36,6 +36,58 @@ TREES = {
 }
 
 
+# ---- the wide cases (tests/test_gpu_backend_wide.py, tests/test_scan_runs_host.py; scenes and the filter alike).  Only the wide tests take them.
+MANY = 257  # the smallest image count at which k_scene_scan's phase 1 runs per = 2 (thread 128 holds one image); five workgroups of k_scene_chain / k_fuse_views
+
+
+def _many_tree(I=MANY, second_root=200, absent=(72, 250), nan_images=(100, 209)):
+    """Two roots, 0 and 200.  Below a root every fourth image hangs on the root itself (a star) and starts a chain of depth 4; forward and inverse
+    edges alternate.  Images 72 and 250 are absent: 72 ends its chain, 251 and 252 hang on 250 and are detached with it.  The pairs of images 100 and
+    209 carry a NaN pose: 100 ends its chain, 210-212 hang below 209.  So lanes of the second and of the last workgroups of the per-image kernels
+    take every branch, and no composed transform is more than four edges from the identity."""
+    pairs, tree, nan = [], [], []
+    for i in range(I):
+        base = 0 if i < second_root else second_root
+        if i == base:
+            tree.append((len(pairs), ROOT))  # the pair of the next image, which hangs on this root
+        elif i in absent:
+            tree.append((0, ABSENT))
+        else:
+            parent = base if (i - base) % 4 == 1 else i - 1
+            if i in nan_images:
+                nan.append(len(pairs))
+            tree.append((len(pairs), E))
+            pairs.append((i, parent) if i % 2 else (parent, i))
+    return dict(I=I, pairs=pairs, tree=tree, nan=tuple(nan))
+
+
+# "wide": 409 * 643 pixels are 257 tiles, the smallest count at which k_scene_scan's phase 0 runs per = 2, beside an image of one tile (its pixel is one of
+# cc.depth_maps' planted inf: attached, no row) and one whose valid region (189 tiles) ends before the allocation's tile count.  "many": the valid regions of SHAPES["unequal"] repeated; an allocation of 5 x 7
+# clamps them, which leaves 5 x 7 and 1 x 1, and cc.depth_maps makes map 99 all inf: an attached image without a row in the middle of the scan.
+WIDE_SHAPES = {"wide": ((409, 643), ((409, 643), (1, 1), (300, 643))), "many": ((5, 7), tuple(SHAPES["unequal"][1][i % 5] for i in range(MANY)))}
+WIDE_TREES = {"many": _many_tree()}
+# name: shape, tree, the image inside whose last tile the smaller p_max cuts (wide_p_max_cases)
+WIDE_CASES = {"wide": ("wide", "mixed", 0), "many": ("many", "many", MANY - 1)}
+WIDE_KINDS = ("varying_focal", "calibrated")
+WIDE_VS = (0, 8)
+WIDE_RATES = (1.0, 0.5)
+WIDE_TOL = 0.05
+
+
+def wide_gates(V):
+    """the open gate | the default"""
+    return ((0, V), (1, 0))
+
+
+def wide_p_max_cases(rows, image):
+    """rows: per image (points, pixel, ...) or None.  A cut inside the last tile of `image` (half of that tile's rows are written; the tile index
+    is pixel // 1024 where the image's valid width is the allocation's) | the true total"""
+    n = [0 if r is None else len(r[1]) for r in rows]
+    pix = np.zeros(0, dtype=np.int64) if rows[image] is None else rows[image][1].astype(np.int64) // 1024
+    last = int((pix == pix.max()).sum()) if len(pix) else 0
+    return (max(sum(n[:image + 1]) - max(last // 2, 1), 0), sum(n))
+
+
 def views(I, V):
     """(I, V) int32: every row of V = 8 holds the image itself, a duplicate, -1 and I beside its real views; V = 3 ends on the image itself and row 0
     is made of inert slots alone; V = 1 is the next image"""
@@ -51,11 +103,11 @@ def views(I, V):
 @functools.lru_cache(maxsize=None)
 def inputs(kind, dtype_name, shape, tree):
     """everything a call takes but the views and the gate"""
-    (H, W), sizes = SHAPES[shape]
-    t = TREES[tree]
+    (H, W), sizes = SHAPES[shape] if shape in SHAPES else WIDE_SHAPES[shape]
+    t = TREES[tree] if tree in TREES else WIDE_TREES[tree]
     I = t["I"]
     all_models = cc.models(kind)
-    m = all_models[list(_USABLE[:len(t["pairs"])])].copy()
+    m = all_models[[_USABLE[b % len(_USABLE)] for b in range(len(t["pairs"]))]].copy()  # (the usable models go round where a tree has more pairs)
     for b in t.get("nan", ()):
         m[b] = all_models[_NAN_POSE]
     size = ((H, W), (H, W))

@@ -15,6 +15,25 @@ KEEPS = ("not_inf", "finite")
 B_MAX = max(BATCHES)
 SEED = 0x1234ABCD5
 EMPTY = {1: "nan_q", 5: "zero_scale", 9: "bad_focal", 13: "inf_t"}  # R1's empty pairs, mixed into every batch of more than one pair
+# ---- the wide sizes (tests/test_gpu_backend_wide.py, tests/test_scan_runs_host.py): maps of more than 256 tiles, where k_recon_scan's threads hold runs
+# of more than one tile (per = ceil(tiles / 256) > 1).  409 * 643 = 262 987 pixels are 257 tiles, the smallest count with per = 2, the last tile
+# ragged; 723 * 727 = 525 621 pixels are 514 tiles, per = 3; 130 * 257 are 33 tiles, per = 1: s_run is rewritten between the sides with another run
+# length, in both orders.  Only the wide tests take them: B = WIDE_B usable pairs each.
+TILE = 1024                              # mdrp_reconstruct.h RECON_TILE
+SCAN_THREADS = 256                       # mdrp_reconstruct.h RECON_THREADS
+WIDE_SIZES = (((409, 643), (130, 257)), ((130, 257), (409, 643)), ((723, 727), (409, 643)))
+WIDE_B = 2
+WIDE_KINDS = ("varying_focal", "calibrated")
+WIDE_RATES = (1.0, 0.05)
+
+
+def tiles(h, w):
+    return -(-(int(h) * int(w)) // TILE)
+
+
+def scan_run(n, threads=SCAN_THREADS):
+    """the run length of the chunked scans: a thread sums per = ceil(n / threads) consecutive values"""
+    return -(-int(n) // threads)
 
 
 def models(kind, n=B_MAX, seed=11):
@@ -85,12 +104,15 @@ def depth_maps(h, w, dtype, n=B_MAX, seed=14, whole_inf=2):
 
 @functools.lru_cache(maxsize=None)
 def inputs(kind, dtype_name, size):
-    """everything a call of the per-pair form takes, for B_MAX pairs; a batch of B is the first B of each"""
+    """everything a call of the per-pair form takes, for B_MAX pairs; a batch of B is the first B of each.  A size of WIDE_SIZES: WIDE_B pairs, both
+    usable (models 0 and 2), no map all inf"""
     (h1, w1), (h2, w2) = size
     dtype = np.dtype(dtype_name)
-    cam1, cam2 = cameras() if kind == "calibrated" else (None, None)
-    c1, c2 = centres()
-    return {"models": models(kind), "dm1": depth_maps(h1, w1, dtype, seed=14), "dm2": depth_maps(h2, w2, dtype, seed=15, whole_inf=4), "c1": c1, "c2": c2,
+    n = WIDE_B if size in WIDE_SIZES else B_MAX
+    cam1, cam2 = cameras(n) if kind == "calibrated" else (None, None)
+    c1, c2 = centres(n)
+    ms = models(kind, 3)[[0, 2]] if size in WIDE_SIZES else models(kind)
+    return {"models": ms, "dm1": depth_maps(h1, w1, dtype, n, seed=14), "dm2": depth_maps(h2, w2, dtype, n, seed=15, whole_inf=4), "c1": c1, "c2": c2,
             "cam1": cam1, "cam2": cam2}
 
 
@@ -126,6 +148,37 @@ def run(kind, dtype_name, size, keep, rate, B, p_max, device="cuda:0"):
                                           None if x["cam1"] is None else x["cam1"][:B], None if x["cam2"] is None else x["cam2"][:B],
                                           torch.from_numpy(x["c1"][:B]).to(dev), torch.from_numpy(x["c2"][:B]).to(dev), rate, SEED, keep, p_max)
     return tuple(t.cpu().numpy() for t in out)
+
+
+def wide_p_max_cases(kind, dtype_name, size, keep, rate):
+    """p_max_cases' scheme (placed by pair 0's counts) at a size of WIDE_SIZES: a cut inside the last tile of the side with more tiles (tile 256 or
+    513: half of that tile's kept pixels are written) | the true total"""
+    r = rows(kind, dtype_name, size, keep, rate, 0)
+    n1, n2 = len(r[0][1]), len(r[1][1])
+    side = 0 if tiles(*size[0]) >= tiles(*size[1]) else 1
+    last = int((r[side][1] // TILE == tiles(*size[side]) - 1).sum())  # (pixel = v * w + u: the tile walk's own index)
+    return ((n1 if side else 0) + len(r[side][1]) - max(last // 2, 1), n1 + n2)
+
+
+def run_image_form(kind, dtype_name, size, keep, rate, B, p_max, device="cuda:0"):
+    """the first B pairs through poselib.reconstruct_image_pairs_torch: 2 B images in one allocation of the larger extents, image 2 b = pair b's map 1
+    and image 2 b + 1 its map 2 as valid regions, a finite depth behind them.  pixel is re-based from the allocation's width to the map's own, so
+    the result compares with `reference` as it stands."""
+    import torch
+    from mdrp_amd import poselib
+    x = inputs(kind, dtype_name, size)
+    (h1, w1), (h2, w2) = size
+    H, W = max(h1, h2), max(w1, w2)
+    dm = np.full((2 * B, H, W), 3.0, dtype=np.dtype(dtype_name))
+    dm[0::2, :h1, :w1], dm[1::2, :h2, :w2] = x["dm1"][:B], x["dm2"][:B]
+    sizes = np.tile(np.array([[h1, w1], [h2, w2]], dtype=np.int32), (B, 1))
+    cs = np.stack([x["c1"][:B], x["c2"][:B]], axis=1).reshape(2 * B, 2)
+    cams = None if x["cam1"] is None else np.stack([x["cam1"][:B], x["cam2"][:B]], axis=1).reshape(2 * B)
+    out = poselib.reconstruct_image_pairs_torch(kind, x["models"][:B], torch.from_numpy(dm).to(torch.device(device)), np.arange(2 * B).reshape(B, 2), cams, cs, sizes,
+                                                rate=rate, seed=SEED, keep=keep, p_max=p_max)
+    points, pixel, counts = (t.cpu().numpy() for t in out)
+    own = np.where(np.arange(p_max)[None, :] < counts[:, :1], w1, w2)  # a pair's rows below its true n1 are image 1's
+    return points, np.where(pixel >= 0, pixel // W * own + pixel % W, pixel).astype(np.int32), counts
 
 
 def same_bytes(got, want):

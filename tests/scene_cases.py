@@ -106,6 +106,34 @@ def run(kind, dtype_name, name, keep, rate, p_max, models=None, device="cuda:0")
     return tuple(t.cpu().numpy() for t in out[:3]) + (scene._records(out[3]),)
 
 
+# ---- the wide cases (tests/test_gpu_backend_wide.py): the scenes of fuse_cases.WIDE_CASES - maps of 257 tiles, and 257 images - with that module's
+# inputs (models near the identity, so the same scenes serve the consistency filter), by the same definition
+@functools.lru_cache(maxsize=None)
+def wide_rows(kind, dtype_name, case, keep, rate):
+    import fuse_cases as fc
+    shape, tree, _ = fc.WIDE_CASES[case]
+    x = fc.inputs(kind, dtype_name, shape, tree)
+    return frontend.scene_rows_numpy(fc.transforms(kind, tree), kind, x["dm"], x["centers"], x["sizes"], x["cams"], keep, frontend.recon_threshold(rate), fc.SEED)
+
+
+def wide_reference(kind, dtype_name, case, keep, rate, p_max):
+    """(points (p_max, 3), pixel (p_max,), offsets (I + 1,), transforms (I,)) by the definition"""
+    import fuse_cases as fc
+    return (*frontend.pack_scene_rows(wide_rows(kind, dtype_name, case, keep, rate), p_max), fc.transforms(kind, fc.WIDE_CASES[case][1]))
+
+
+def wide_run(kind, dtype_name, case, keep, rate, p_max, device="cuda:0"):
+    """poselib.reconstruct_scene_torch on the wide case: (points, pixel, offsets, transform records) as NumPy arrays"""
+    import torch
+    import fuse_cases as fc
+    from mdrp_amd import poselib, scene
+    shape, tree, _ = fc.WIDE_CASES[case]
+    x = fc.inputs(kind, dtype_name, shape, tree)
+    out = poselib.reconstruct_scene_torch(kind, x["models"], torch.from_numpy(x["dm"]).to(torch.device(device)), x["pairs"], x["tree"], x["cams"], x["centers"],
+                                          x["sizes"], rate, fc.SEED, keep, p_max, return_transforms=True)
+    return tuple(t.cpu().numpy() for t in out[:3]) + (scene._records(out[3]),)
+
+
 def same_bytes(got, want):
     return all(g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes() for g, w in zip(got, want))
 

@@ -4,7 +4,9 @@ estimate_batch_torch on the sampler's output, and every refusal through the raw 
 
 Inputs (tests/dense_cases.py): B = 3, maps of 45 x 61 and 39 x 70 pixels (non-square, different, no multiple of a grid), R = 3 blocks + 17 rows and
 R = 300 (less than a block), a pair of zero certainties between two live ones, the same pair at two batch positions, rows on the maps' borders,
-infinite and NaN depths, tied certainties, and the duplicate case (five rows of weight 65536 among thousands of weight 1 with M1 near K)."""
+infinite and NaN depths, tied certainties, and the duplicate case (five rows of weight 65536 among thousands of weight 1 with M1 near K).  These
+shapes keep k_dense_scan at one block per thread and every running sum below 2^32: the warps of a real matcher (257, 513 and 4096 blocks, weight
+sums beyond 2^32, stage 1 at its limit) are tests/test_gpu_dense_wide.py's."""
 import ctypes as C
 
 import numpy as np
